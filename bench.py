@@ -1,7 +1,15 @@
 #!/usr/bin/env python
 """bench.py -- PLDA LLR trials/sec (and fit-EM iters/sec) on MI355X.
 
-Contract: `python bench.py --gpus N --steps K --warmup W` prints ONE JSON line on rank 0.
+Contract: `python bench.py --gpus N --steps K --warmup W` prints ONE JSON line on rank 0.  Such a plain run does only
+what the headline figure needs: it fits the model (untimed), sets up the enrol / test sets, runs W warm-up steps, times
+the K steps and prints the line (`value`, `ms_per_step` = the wall clock of one timed step, and the roofline of the
+timed launches).  `--full` adds everything else the line has carried: fit timings and stage spans, the skewed-count
+and D = 1024 fits, the oracle check of the timed output, the gather legs (N > 1), z-norm, transform, shader clock,
+EER, the bf16x3 and targetdim-150 arms, the CPU baselines and the end-to-end figures (`--no-cpu` / `--no-extra`
+trim it as before).  `--dump-outputs DIR` writes, after the timed steps, a fixed, seeded sample of the last step's
+scores to DIR/scores.npy (float32) with their global row / column indices (score_rows.npy, score_cols.npy, float64):
+the inputs are seeded, so two builds can be compared output for output.
 
 Default workload (BASELINE.json configs[1], "C2", the configuration the metric is quoted on):
 100 000 random i-vectors, featdim 200, 5 000 speakers; fit = statistics + 10 EM iterations +
@@ -252,6 +260,15 @@ def latest_traffic(M, Nt, dout):
     return best if best else (None, None)
 
 
+def dump_sample(n, k, seed):
+    """--dump-outputs: k of the indices 0 .. n-1, ascending, the first and the last always among them (all n when n <= k);
+    fixed by (n, k, seed)."""
+    if n <= k:
+        return np.arange(n)
+    pick = np.random.default_rng(seed).choice(np.arange(1, n - 1), k - 2, replace=False)
+    return np.sort(np.concatenate([[0, n - 1], pick]))
+
+
 def describe_ranks(descs, scores_numel=0):
     """`multi_gpu` of the printed line from the ranks' own plda_comm_describe answers.  `comm_nranks` is what the transport in use
     reports; `rccl_nranks` / `rccl_version` appear ONLY when that transport is RCCL (then they come from ncclCommCount /
@@ -329,7 +346,18 @@ def main():
     ap.add_argument("--emulate-ranks", type=int, default=0,
                     help="logic check on ONE GPU: play R ranks in turn through plda_comm_emulate (no collective, no gather "
                          "timing); the printed rate is not a multi-GPU measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="also every measurement and check beside the headline figure: fit timings and stage spans, the skewed "
+                         "and D = 1024 fits, the oracle check of the timed output, the gather leg (N > 1), z-norm, transform, "
+                         "shader clock, EER, bf16x3 and targetdim-150 arms, CPU baselines, end-to-end (--no-cpu / --no-extra "
+                         "trim it); without it a run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed to DIR/<name>.npy: a fixed, seeded sample "
+                         "of the scores (float32, at most 1024 x 4096; every row / column when there are fewer) and the "
+                         "global row / column index of every sampled score (float64)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     # `python bench.py --gpus N` without a launcher around it: become the launcher (one process per GPU under
     # torch.distributed.run, rendezvous on 127.0.0.1) -- never a single rank that prints n_gpus: 1 for --gpus 8
@@ -418,6 +446,16 @@ def main():
         del dXl, dyl
         model = eng.get_model()
         packed = np.concatenate([model["mean"], model["transform"].ravel(), model["psi"]])
+    elif rank == 0 and not args.full:
+        # a plain run: the one fit the scored model needs, untimed (its first call also loads code and allocates)
+        dX, dy = fit_rows()
+        eng.fit_dev(dX.data_ptr(), N, D, dy.data_ptr(), K, args.iters)
+        torch.cuda.synchronize(dev)
+        fit_info = {"N": N, "D": D, "K": K, "iters": args.iters, "em_form": eng.fit_plan()["form"],
+                    "timing": "not measured: bench.py --full times the fit"}
+        model = eng.get_model()
+        packed = np.concatenate([model["mean"], model["transform"].ravel(), model["psi"]])
+        del dX, dy
     elif rank == 0:
         dX, dy = fit_rows()
         torch.cuda.synchronize(dev)
@@ -567,8 +605,6 @@ def main():
     elapsed, (gemm_ms, launches, gemm_flop) = timed(False)
     gemm_k = eng.score_last_shape()[2]      # algorithmic GEMM depth of the timed launches: D (uniform n), D + G - 1 (mixed n, G distinct counts), 2 D (depth-2D form)
 
-    # ---- parity of the TIMED output: a 64 x 64 sample (rows of THIS rank's blocks, block boundaries included) against
-    #      the fp64 oracle's per-trial LLR (oracle/plda_oracle.c) and against the engine's own fp64 trial-list kernel ----
     from plda_amd.sharding import local_row_index
     if world > 1:
         grow = local_row_index(M, world, rank, args.block_rows, device=dev)       # global row of every slab row
@@ -577,18 +613,34 @@ def main():
     else:
         grow = torch.arange(M, device=dev)
     nloc = int(grow.numel())
-    pick = torch.unique(torch.cat([torch.tensor([0, nloc - 1], device=dev),
-                                   torch.linspace(0, nloc - 1, 62, device=dev).long()]))[:64]
-    sel_t = torch.unique(torch.cat([torch.tensor([0, 5, Nt - 1], device=dev), torch.linspace(0, Nt - 1, 61, device=dev).long()]))[:64]
-    sel_e = grow[pick]
-    Uh, Th = dU[sel_e].cpu().numpy(), dT[sel_t].cpu().numpy()
-    nh = dn[sel_e].cpu().numpy() if dn is not None else np.full(len(sel_e), n_uniform, np.int32)
-    got = (out[pick] if world > 1 else out[sel_e])[:, sel_t].cpu().numpy().astype(np.float64)
-    ne, nt_ = got.shape
-    ref = eng.score_trials((nh, Uh), (1, Th), np.repeat(np.arange(ne), nt_), np.tile(np.arange(nt_), ne)).reshape(ne, nt_)
-    spot = float(np.abs(got - ref).max())
-    oracle_check = None
-    if True:                 # (always: 4 096 trials of the per-trial oracle take milliseconds; --no-cpu only skips the timed CPU legs)
+
+    # ---- --dump-outputs: the last timed step's scores (rank 0's rows), before any later leg reuses the buffer.  The sample
+    #      depends on the shape alone: at most 1024 rows x 4096 columns, the first and last of each always among them ----
+    if args.dump_outputs and rank == 0:
+        rows_, cols_ = dump_sample(nloc, 1024, 11), dump_sample(Nt, 4096, 12)
+        r_, c_ = torch.from_numpy(rows_).to(dev), torch.from_numpy(cols_).to(dev)
+        got_ = out[r_[:, None], c_[None, :]].cpu().numpy()               # (gathers the sample only: no row or column slab)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "scores.npy"), np.ascontiguousarray(got_, dtype=np.float32))
+        np.save(os.path.join(args.dump_outputs, "score_rows.npy"), grow[r_].cpu().numpy().astype(np.float64))
+        np.save(os.path.join(args.dump_outputs, "score_cols.npy"), cols_.astype(np.float64))
+        del r_, c_, got_
+
+    # ---- parity of the TIMED output (--full): a 64 x 64 sample (rows of THIS rank's blocks, block boundaries included)
+    #      against the fp64 oracle's per-trial LLR (oracle/plda_oracle.c) and against the engine's own fp64 trial-list kernel ----
+    spot = oracle_check = None
+    if args.full:
+        pick = torch.unique(torch.cat([torch.tensor([0, nloc - 1], device=dev),
+                                       torch.linspace(0, nloc - 1, 62, device=dev).long()]))[:64]
+        sel_t = torch.unique(torch.cat([torch.tensor([0, 5, Nt - 1], device=dev), torch.linspace(0, Nt - 1, 61, device=dev).long()]))[:64]
+        sel_e = grow[pick]
+        Uh, Th = dU[sel_e].cpu().numpy(), dT[sel_t].cpu().numpy()
+        nh = dn[sel_e].cpu().numpy() if dn is not None else np.full(len(sel_e), n_uniform, np.int32)
+        got = (out[pick] if world > 1 else out[sel_e])[:, sel_t].cpu().numpy().astype(np.float64)
+        ne, nt_ = got.shape
+        ref = eng.score_trials((nh, Uh), (1, Th), np.repeat(np.arange(ne), nt_), np.tile(np.arange(nt_), ne)).reshape(ne, nt_)
+        spot = float(np.abs(got - ref).max())
+        # (4 096 trials of the per-trial oracle take milliseconds: with --full always; --no-cpu only skips the timed CPU legs)
         try:
             from oracle import binding as ob
             ob.build()
@@ -601,13 +653,13 @@ def main():
                             "oracle": "oracle/plda_oracle.c per-trial LogLikelihoodRatio, fp64"}
         except Exception as e:   # noqa: BLE001
             oracle_check = {"error": "%s: %s" % (type(e).__name__, e)}
-    if world > 1:                                   # every rank's sample must pass, not only rank 0's
-        bad = torch.tensor([0.0 if (oracle_check is None or oracle_check.get("within_1e-4", False)) else 1.0, spot],
-                           dtype=torch.float64, device=dev)
-        dist.all_reduce(bad, op=dist.ReduceOp.MAX)
-        spot = float(bad[1].item())
-        if oracle_check is not None and "within_1e-4" in oracle_check:
-            oracle_check["within_1e-4_on_every_rank"] = bool(bad[0].item() == 0.0)
+        if world > 1:                                   # every rank's sample must pass, not only rank 0's
+            bad = torch.tensor([0.0 if (oracle_check is None or oracle_check.get("within_1e-4", False)) else 1.0, spot],
+                               dtype=torch.float64, device=dev)
+            dist.all_reduce(bad, op=dist.ReduceOp.MAX)
+            spot = float(bad[1].item())
+            if oracle_check is not None and "within_1e-4" in oracle_check:
+                oracle_check["within_1e-4_on_every_rank"] = bool(bad[0].item() == 0.0)
 
     # ---- who took part (as the transport reports it), and the gather-inclusive leg on the single-GPU matrix ----
     multi = None
@@ -616,7 +668,7 @@ def main():
         descs = [None] * world
         dist.all_gather_object(descs, eng.comm_describe())
         multi = describe_ranks(descs, out.numel())
-    if world > 1 and not args.no_gather:
+    if world > 1 and args.full and not args.no_gather:
         try:   # the second leg must not cost the run its (already measured) main line
             err_g = None
             try:
@@ -681,7 +733,7 @@ def main():
     # ---- norm(): z-norm statistics of the first 50k enrol models over a 200k-row cohort (the C5 shape at this D),
     #      outside the timed region: MPlda_norm, pldamodule.cpp:196-256 ----
     zn = None
-    if rank == 0 and world == 1 and not emu and not args.no_extra and not args.targetdim:
+    if rank == 0 and world == 1 and not emu and args.full and not args.no_extra and not args.targetdim:
         zM, zNb = min(M, 50000), 200000
         gz = torch.Generator(device=dev); gz.manual_seed(5)
         cohort = torch.rand((zNb, D), dtype=torch.float64, device=dev, generator=gz)
@@ -714,7 +766,7 @@ def main():
     # ---- transform (K4: rows -> PLDA space -> length norm, pldamodule.cpp:111-194) of the test side's rows, outside
     #      the timed region: 2 N D^2 flop on the fp64 MFMA pipe + a length-norm pass over the output ----
     tf = None
-    if rank == 0 and world == 1 and not emu and not args.no_extra and not args.targetdim:
+    if rank == 0 and world == 1 and not emu and args.full and not args.no_extra and not args.targetdim:
         gx = torch.Generator(device=dev); gx.manual_seed(6)
         Xt = torch.rand((Nt, D), dtype=torch.float64, device=dev, generator=gx)
         Yt = torch.empty((Nt, dout), dtype=torch.float64, device=dev)
@@ -753,7 +805,7 @@ def main():
     #      fraction of the peak is (MFMA-busy in cycles) x (clock / 2.4 GHz) x (1 - tail); the clock differs between the
     #      boxes of a pool by 1-4 %, the cycles do not.  Outside the timed region, on a second handle. ----
     clock_info = None
-    if rank == 0 and world == 1 and not emu and not args.no_extra and not args.targetdim and "bt4" in eng.score_last_kernel():
+    if rank == 0 and world == 1 and not emu and args.full and not args.no_extra and not args.targetdim and "bt4" in eng.score_last_kernel():
         try:
             import ctypes as C
             old_env = os.environ.get("PLDA_GEMM_VARIANT")
@@ -805,7 +857,7 @@ def main():
     #      the exact EER of the timed output (one full pass since round 5), and the same EER straight from the operands
     #      (plda_score_eer_dev: the scores exist one <= 4 GiB row slab at a time).  Synthetic labels: speaker = index mod 5000.
     eer_info = None
-    if rank == 0 and world == 1 and not emu and not args.no_extra and not args.targetdim:
+    if rank == 0 and world == 1 and not emu and args.full and not args.no_extra and not args.targetdim:
         try:
             from plda_amd import eer as geer
             nspk = max(2, min(5000, M // 2))
@@ -838,7 +890,7 @@ def main():
     #      fp32 rate for the bf16 one at fp32-grade accuracy (checked against the oracle below, same tolerance).  Its
     #      roofline is the HBM write of the scores. ----
     b3 = None
-    if rank == 0 and world == 1 and not emu and not args.no_extra and not args.targetdim and os.environ.get("PLDA_SCORE_DTYPE", "") in ("", "f32"):
+    if rank == 0 and world == 1 and not emu and args.full and not args.no_extra and not args.targetdim and os.environ.get("PLDA_SCORE_DTYPE", "") in ("", "f32"):
         try:
             os.environ["PLDA_SCORE_DTYPE"] = "bf16x3"
             e3 = MPlda(local_rank)
@@ -879,7 +931,7 @@ def main():
 
     # ---- build extension named by BASELINE configs[1]: targetdim = 150 (top-psi dims), same trials ----
     td = None
-    if rank == 0 and world == 1 and args.config == "C2" and not args.targetdim and dout > 150 and not args.no_extra:
+    if rank == 0 and world == 1 and args.config == "C2" and not args.targetdim and dout > 150 and args.full and not args.no_extra:
         eng.truncate(150)
         dU150 = torch.empty((M, 150), dtype=torch.float64, device=dev)
         dT150 = torch.empty((Nt, 150), dtype=torch.float64, device=dev)
@@ -910,7 +962,7 @@ def main():
         achieved = (gemm_flop / max(launches, 1)) / avg_gemm_s / 1e12 if avg_gemm_s > 0 else 0.0
         res = {
             "metric": "PLDA LLR trials/sec", "value": value, "unit": "trials/s",
-            "n_gpus": world, **({"emulated_ranks_on_one_gpu": emu} if emu else {}), "steps": args.steps, "warmup": args.warmup,
+            "n_gpus": world, **({"emulated_ranks_on_one_gpu": emu} if emu else {}), "steps": args.steps, "warmup": args.warmup, "full": args.full,
             "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": args.scaling if (world > 1 or emu) else "weak",
             "vs_baseline": None, "dtype": "f32", "data": "synthetic",
             "config": {"workload": "%s; fit %d EM iters; D_eff=%d" % (cfg["what"], args.iters, dout),
@@ -935,7 +987,7 @@ def main():
                          "launches": launches,
                          "hbm_write_GBps": round(gemm_flop / max(launches, 1) / (2 * gemm_k) * 4 / avg_gemm_s / 1e9, 1) if avg_gemm_s > 0 else None,
                          **({"clock": clock_info} if clock_info else {})},
-            "fit": fit_info, "spot_check_max_abs_err": spot, "oracle_check": oracle_check,
+            "fit": fit_info, **({"spot_check_max_abs_err": spot, "oracle_check": oracle_check} if args.full else {}),
         }
         if fit_info and fit_info.get("em_iters_per_s"):
             res["fit_em_iters_per_s"] = fit_info["em_iters_per_s"]           # equal speaker counts (G = 1)
@@ -976,7 +1028,7 @@ def main():
                 res["rccl_nranks"] = multi["rccl_nranks"]
                 res["rccl_version"] = multi["rccl_version"]
             res["distinct_devices"] = multi.get("distinct_devices")
-        if not args.no_cpu and world == 1:
+        if args.full and not args.no_cpu and world == 1:
             cb = cpu_baseline(dout, psi[:dout])
             try:
                 cb["best_effort"] = cpu_best_effort(dout, psi[:dout])
@@ -988,7 +1040,7 @@ def main():
                 except Exception as e:  # the EM leg is informative only
                     cb["fit_em"] = {"error": str(e)}
             res["cpu_baseline"] = cb
-        if world == 1 and not emu and not args.no_extra and not args.targetdim:
+        if world == 1 and not emu and args.full and not args.no_extra and not args.targetdim:
             try:
                 if td:
                     eng.set_model(packed[:D], packed[D:D + D * D].reshape(D, D), psi)    # (the targetdim leg truncated it)

@@ -193,7 +193,7 @@ def test_bench_gpus_2_launches_its_own_ranks():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--transport", "peer",
-                        "--rows", "20000", "--steps", "2", "--warmup", "1", "--no-cpu"],
+                        "--rows", "20000", "--steps", "2", "--warmup", "1", "--no-cpu", "--full"],
                        capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -219,7 +219,7 @@ def test_bench_gpus_2_c4_strong_scaling_over_the_peer_provider():
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--transport", "peer",
                         "--config", "C4", "--scaling", "strong", "--rows", "20003", "--speakers", "700", "--steps", "2",
-                        "--warmup", "1", "--no-cpu"],
+                        "--warmup", "1", "--no-cpu", "--full"],
                        capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

@@ -46,7 +46,7 @@ def test_htk_batch_matches_oracle_and_live_reference(tmp_path):
         for u in (0, 7, 57, 123, 299):
             want = ho.htk_load(raws[u], f)
             np.testing.assert_array_equal(frames[off[u]:off[u + 1]].view(np.uint32), want)
-            if rb.available():
+            if os.path.exists(rb.SO):                   # the reference's reader, where the build compiled it
                 np.testing.assert_array_equal(frames[off[u]:off[u + 1]].view(np.uint32).ravel(), rb.load(paths[u], f))
         full = np.concatenate([ho.htk_load(r, f) for r in raws])
         np.testing.assert_array_equal(frames.view(np.uint32), full)

@@ -224,3 +224,23 @@ def test_bench_skewed_labels_are_dense_and_exact():
     y, nk = bench.skewed_labels(100000, 5000)
     # BASELINE.md C2's "skewed-n_k variant": counts drawn from [5, 60] and rescaled to the 100k rows -> 3 .. 38, 36 distinct values
     assert len(np.unique(nk)) == 36 and nk.min() == 3 and nk.max() == 38
+
+
+def test_bench_dump_sample_is_fixed_and_spans_the_matrix():
+    """`bench.py --dump-outputs`: the sampled rows / columns depend on the shape alone (two builds compare the same scores),
+    hold the first and the last index, are distinct and ascending, and are every index of a small matrix."""
+    import importlib
+    bench = importlib.import_module("bench")
+    for n, k in ((100000, 1024), (1000000, 4096), (4097, 4096), (3, 3)):
+        a, b = bench.dump_sample(n, k, 11), bench.dump_sample(n, k, 11)
+        assert np.array_equal(a, b) and a.shape == (min(n, k),)
+        assert a[0] == 0 and a[-1] == n - 1 and (np.diff(a) > 0).all()
+    assert np.array_equal(bench.dump_sample(300, 1024, 11), np.arange(300))
+    assert bench.dump_sample(100000, 1024, 11).size * bench.dump_sample(100000, 4096, 12).size * 4 <= 64 << 20
+
+
+def test_bench_refuses_zero_steps():
+    """`--steps` is the number of timed steps and `ms_per_step` divides by it: 0 is refused before anything is set up."""
+    import subprocess
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 2 and "--steps must be at least 1" in r.stderr and not r.stdout
