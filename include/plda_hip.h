@@ -62,6 +62,13 @@ int plda_abi_version(void);
 /* bit 0: built with -DPLDA_DIAG=1 (libplda_hip_diag.so: + the measurement arms of the trials GEMM, some of which return
  * garbage scores; selected by PLDA_GEMM_VARIANT).  The product library returns 0 and plda_create refuses those variants. */
 int plda_build_flags(void);
+/* bytes of device memory the library's buffers hold right now, over every handle of the process (the device scratch and
+ * model copies of the handles, the temporaries of calls in flight; not the one uncached flag page of the peer transport,
+ * plda_comm_init_peer).  With PLDA_SCRATCH_POISON=1 in the environment at
+ * plda_create (tests only), every later device allocation of the library is 64 KiB longer than asked for and filled with
+ * 0xFF bytes (NaN as a float) before its first use; an allocation that would need the fill while the handle's stream is
+ * being captured fails with PLDA_E_HIP. */
+int64_t plda_device_bytes_held(void);
 /* enqueue on exactly this hipStream_t (e.g. torch's current stream; NULL is HIP's default
  * stream, with its implicit-synchronisation rules); plda_reset_stream goes back to the
  * handle's own non-blocking stream */

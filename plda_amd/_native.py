@@ -27,6 +27,7 @@ _i32, _i64, _f64 = C.c_int32, C.c_int64, C.c_double
 SIGNATURES = {
     "plda_abi_version": (C.c_int, []),
     "plda_build_flags": (C.c_int, []),
+    "plda_device_bytes_held": (_i64, []),
     "plda_create": (C.c_int, [C.c_int, C.POINTER(_vp)]),
     "plda_destroy": (C.c_int, [_vp]),
     "plda_last_error": (C.c_char_p, [_vp]),

@@ -17,6 +17,9 @@
 
 namespace plda {
 
+std::atomic<int64_t> g_device_bytes{0};
+std::atomic<int> g_scratch_poison{0};
+thread_local hipStream_t g_call_stream = nullptr;
 static thread_local std::string g_create_err;
 
 int fail(plda_handle *h, int code, const char *fmt, ...) {
@@ -133,6 +136,7 @@ static int download(plda_handle *h, void *dst, const void *dsrc, size_t bytes) {
 }
 
 static int set_device(plda_handle *h) {
+  g_call_stream = h->stream;
   PLDA_HIP(h, hipSetDevice(h->device));
   return PLDA_OK;
 }
@@ -162,7 +166,14 @@ namespace {
 int fail_quiet(plda_handle *h, int code, const char *fn, const char *what) noexcept {
   try { return fail(h, code, "%s: %s", fn, what); } catch (...) { return code; }
 }
+// the stream a poison fill checks for a capture (common.hpp): this call's handle's, and nothing once the call returns
+struct CallStream {
+  hipStream_t prev;
+  explicit CallStream(plda_handle *h) : prev(g_call_stream) { g_call_stream = h ? h->stream : nullptr; }
+  ~CallStream() { g_call_stream = prev; }
+};
 template <typename F> int guarded(plda_handle *h, const char *fn, F &&body) noexcept {
+  CallStream cs(h);
   try { return body(); }
   catch (const std::bad_alloc &) { return fail_quiet(h, PLDA_E_HIP, fn, "out of host memory"); }
   catch (const std::exception &e) { return fail_quiet(h, PLDA_E_HIP, fn, e.what()); }
@@ -174,6 +185,7 @@ extern "C" {
 
 int plda_abi_version(void) { return 2; }
 int plda_build_flags(void) { return PLDA_DIAG ? 1 : 0; }
+int64_t plda_device_bytes_held(void) { return g_device_bytes.load(std::memory_order_relaxed); }
 
 int plda_create(int device, plda_handle **out) {
   return guarded(nullptr, "plda_create", [&]() -> int {
@@ -201,6 +213,10 @@ int plda_create(int device, plda_handle **out) {
     }
     if (e != hipSuccess) { delete h; return fail(nullptr, PLDA_E_HIP, "plda_create: %s", hipGetErrorString(e)); }
     h->stream = h->own_stream;
+    {   // tests only (common.hpp): process-wide, taken from the environment of the latest plda_create
+      const char *v = std::getenv("PLDA_SCRATCH_POISON");
+      g_scratch_poison.store(v && std::atoi(v) == 1 ? 1 : 0);
+    }
     if (const char *v = std::getenv("PLDA_GEMM_VARIANT")) h->gemm_variant = std::atoi(v);
 #if !PLDA_DIAG
     {   // measurement arms (garbage scores or clock stamps): not in this build
@@ -249,25 +265,17 @@ int plda_destroy(plda_handle *h) {
       if (trace_summary(h, js, true) == PLDA_OK) std::fprintf(stderr, "[plda_hip trace] %s\n", js.c_str());
     }
     for (auto &sp : h->trace_spans) { (void)hipEventDestroy(sp.e0); (void)hipEventDestroy(sp.e1); }
-    (void)comm_destroy(h);
+    (void)comm_destroy(h);         // first: peers map comm_mm / comm_mc, which are freed with the handle below
     delete h->hostpipe;
     h->hostpipe = nullptr;
-    DevBuf *bufs[] = {&h->d_mean, &h->d_transform, &h->d_psi, &h->d_offset, &h->f_means, &h->f_counts,
-                      &h->f_scatter, &h->f_sum, &h->f_W, &h->f_B, &h->fit_flag, &h->s_Apk, &h->s_Bpk, &h->s_rbias,
-                      &h->s_rscale, &h->s_cbias, &h->s_rpair, &h->s_cpair, &h->tf_pad, &h->l_means, &h->l_priors, &h->l_xbar, &h->l_scalings,
-                      &h->l_coef, &h->l_intercept, &h->l_evr, &h->timeline, &h->eigdc, &h->zn_rows, &h->zn_y, &h->zn_small, &h->hio_O[0], &h->hio_O[1],
-                      &h->bt4_cnt, &h->bt4_fringe, &h->cs_work, &h->comm_mm, &h->comm_mc, &h->eer_list[0], &h->eer_list[1], &h->s_A16, &h->s_B16, &h->eer_slab, &h->eer_smp};
-    for (DevBuf *b : bufs) b->release();
-    for (auto &t : h->bt4_tabs) t.tab.release();
     if (h->cs_pin) (void)hipHostFree(h->cs_pin);
-    for (auto &b : h->w) b.release();
     if (h->one_host) (void)hipHostFree(h->one_host);
     if (h->pin_model) (void)hipHostFree(h->pin_model);
     for (hipEvent_t e : h->fit_ev) if (e) (void)hipEventDestroy(e);
     if (h->jac_exec) (void)hipGraphExecDestroy(h->jac_exec);
     for (auto &ev : h->prof_events) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
     if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
-    delete h;
+    delete h;                      // every DevBuf member frees its memory in its destructor
     return PLDA_OK;
   });
 }

@@ -23,26 +23,79 @@
 
 namespace plda {
 
+// Device-allocation bookkeeping shared by the library's only two allocation sites, DevBuf::reserve and Tmp::alloc.
+//  * g_device_bytes: the bytes every DevBuf / Tmp of the process holds right now (plda_device_bytes_held; the leak tests).
+//  * g_scratch_poison (PLDA_SCRATCH_POISON=1 at plda_create; tests only): every allocation gets POISON_TAIL more bytes and is
+//    filled with 0xFF bytes (NaN as f64 / f32, -1 as an integer) before it is handed out, so that a kernel reading scratch
+//    nobody wrote, or reading past the end of a buffer, shows up as NaN or a bad index instead of the zeros of fresh memory.
+//  * g_call_stream: the stream of the entry point running on this thread (api.hip: guarded, set_device; nullptr outside a
+//    call) -- a fill is refused while it is being captured into a graph.
+// (Not counted or poisoned: the peer transport's flag page, comm.hip, an uncached allocation of its own.)
+extern std::atomic<int64_t> g_device_bytes;
+extern std::atomic<int> g_scratch_poison;
+extern thread_local hipStream_t g_call_stream;
+constexpr size_t POISON_TAIL = (size_t)64 << 10;   // > the row-form EM's worst over-read (15 rows of 8 D bytes at D <= 512)
+
+inline size_t alloc_extra() { return g_scratch_poison.load(std::memory_order_relaxed) ? POISON_TAIL : 0; }
+// after a successful allocation of `bytes` (extra included): count it, and poison it when the switch is on
+inline hipError_t alloc_done(void *p, size_t bytes) {
+  g_device_bytes.fetch_add((int64_t)bytes, std::memory_order_relaxed);
+  if (!g_scratch_poison.load(std::memory_order_relaxed)) return hipSuccess;
+  hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+  if (g_call_stream && hipStreamIsCapturing(g_call_stream, &st) == hipSuccess && st != hipStreamCaptureStatusNone)
+    return hipErrorStreamCaptureUnsupported;
+  hipError_t e = hipMemset(p, 0xFF, bytes);
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  return e;
+}
+inline void free_counted(void *p, size_t bytes) {
+  if (!p) return;
+  (void)hipFree(p);
+  g_device_bytes.fetch_sub((int64_t)bytes, std::memory_order_relaxed);
+}
+
+// a growable device buffer owned by one handle (or one communicator context): freed by its destructor
 struct DevBuf {
   void *p = nullptr;
   size_t cap = 0;
+  size_t held = 0;   // bytes of the allocation (cap + the poison tail)
+  DevBuf() = default;
+  DevBuf(const DevBuf &) = delete;
+  DevBuf &operator=(const DevBuf &) = delete;
+  ~DevBuf() { release(); }
   hipError_t reserve(size_t bytes) {
     if (bytes <= cap) return hipSuccess;
-    if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
-    size_t want = bytes + bytes / 8 + 256;
-    hipError_t e = hipMalloc(&p, want);
-    if (e == hipSuccess) cap = want;
+    release();
+    size_t want = bytes + bytes / 8 + 256, total = want + alloc_extra();
+    hipError_t e = hipMalloc(&p, total);
+    if (e != hipSuccess) { p = nullptr; return e; }
+    cap = want; held = total;
+    e = alloc_done(p, total);
+    if (e != hipSuccess) release();
     return e;
   }
-  void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+  void release() { free_counted(p, held); p = nullptr; cap = 0; held = 0; }
   template <typename T> T *as() const { return reinterpret_cast<T *>(p); }
 };
 
 // RAII device temporary of the host-pointer entry points
 struct Tmp {
   void *p = nullptr;
-  ~Tmp() { if (p) (void)hipFree(p); }
-  hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 8); }
+  size_t held = 0;
+  Tmp() = default;
+  Tmp(const Tmp &) = delete;
+  Tmp &operator=(const Tmp &) = delete;
+  ~Tmp() { free_counted(p, held); }
+  hipError_t alloc(size_t bytes) {
+    free_counted(p, held); p = nullptr; held = 0;
+    const size_t total = (bytes ? bytes : 8) + alloc_extra();
+    hipError_t e = hipMalloc(&p, total);
+    if (e != hipSuccess) { p = nullptr; return e; }
+    held = total;
+    e = alloc_done(p, total);
+    if (e != hipSuccess) { free_counted(p, held); p = nullptr; held = 0; }
+    return e;
+  }
   template <typename T> T *as() { return reinterpret_cast<T *>(p); }
 };
 

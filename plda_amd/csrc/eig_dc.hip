@@ -147,6 +147,9 @@ __global__ __launch_bounds__(1024) void tridiag_reg_kernel(const double *__restr
       const double x0 = x[j + 1];
       if (s2 == 0.0) {   // column already tridiagonal (uniform over the workgroup)
         if (t == 0) { ee[j] = x0; tau[j] = 0.0; }
+        // H = I: its reflector is zero, and the back-transformation's kernels read it (householder_T_kernel,
+        // householder_row*_kernel: 0 * whatever the scratch held would be NaN for a NaN there)
+        for (int k = j + 1 + t; k < n; k += blockDim.x) Vh[(size_t)j * n + k] = 0.0;
         continue;
       }
       const double nx2 = fma(x0, x0, s2);
@@ -328,6 +331,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
       const double x0 = x[((j + 1) & 15) * PAD + ((j + 1) >> 4)];
       if (s2 == 0.0) {   // column already tridiagonal (uniform over the workgroup)
         if (t == 0) { ee[j] = x0; tau[j] = 0.0; }
+        // H = I: its reflector is zero, and the back-transformation's kernels read it (householder_T_kernel,
+        // householder_row*_kernel: 0 * whatever the scratch held would be NaN for a NaN there)
+        for (int k = j + 1 + t; k < n; k += blockDim.x) Vh[(size_t)j * n + k] = 0.0;
         continue;
       }
       const double nx2 = fma(x0, x0, s2);

@@ -978,9 +978,10 @@ int fit_em_device(plda_handle *h, int64_t K, int D, int iters) {
         pin_tiles[ntiles++] = make_int4((int)r, (int)std::min<int64_t>(16 * RB, goff[g + 1] - r), g, 0);
     PLDA_HIP(h, h->w[5].reserve((size_t)K * D * 8 * 3 + (size_t)K * 4 + ntiles * 16 + 64));
     PLDA_HIP(h, h->w[6].reserve((size_t)G * DD * 8 * 5 + DD * 8 * 3 + (size_t)G * 16 + (size_t)GD * 16 + 64));
-    double *Mg = h->w[5].as<double>(), *Zr = Mg + (size_t)K * D, *Wn = Zr + (size_t)K * D;
-    int4 *dtiles = reinterpret_cast<int4 *>(Wn + (size_t)K * D);
-    int *dcls = reinterpret_cast<int *>(dtiles + ntiles);
+    // (the int4 tile table first: behind the three K x D arrays it would be only 8-byte aligned when K D is odd)
+    int4 *dtiles = h->w[5].as<int4>();
+    double *Mg = reinterpret_cast<double *>(dtiles + ntiles), *Zr = Mg + (size_t)K * D, *Wn = Zr + (size_t)K * D;
+    int *dcls = reinterpret_cast<int *>(Wn + (size_t)K * D);
     double *Tg = h->w[6].as<double>(), *Xg = Tg + (size_t)G * DD, *scr = Xg + (size_t)G * DD, *P1 = scr + 3 * (size_t)G * DD,
            *P2 = P1 + DD, *Balt = P2 + DD, *dgn = Balt + DD, *dgk = dgn + G, *kw1 = dgk + G, *kw2 = kw1 + GD;
     int *dflag = h->fit_flag.as<int>();          // (its own buffer: the export kernel that ends the fit reads it)

@@ -2129,7 +2129,8 @@ static int simdiag_run(plda_handle *h, const double *W, const double *B, int D, 
   double *scr = h->w[13].as<double>();                                    // 2 DD: whitening scratch
   double *T1 = scr + 2 * DD, *tmp = T1 + DD, *G = tmp + DD, *Vr = G + DD;   // Vr persists: next call's warm start
   int *dflag = reinterpret_cast<int *>(Vr + DD);
-  const bool warm = warm_start && !fresh && h->simdiag_has_vr;
+  // (warm starts run block Jacobi, which stops at D = 1024: beyond it every call starts cold on the direct method)
+  const bool warm = warm_start && !fresh && h->simdiag_has_vr && D <= 1024;
   const bool direct = allow_direct && !warm && h->eig_variant != 1;
   if (pending) *pending = false;
   PLDA_HIP(h, hipMemsetAsync(dflag, 0, sizeof(int), h->stream));
@@ -2167,7 +2168,8 @@ static int simdiag_run(plda_handle *h, const double *W, const double *B, int D, 
   if (dc_status != 0) {
     if (direct) {   // the direct method gave up: was it the Cholesky factor?
       int hflag = 0;
-      PLDA_HIP(h, hipMemcpy(&hflag, dflag, sizeof(int), hipMemcpyDeviceToHost));
+      PLDA_HIP(h, hipMemcpyAsync(&hflag, dflag, sizeof(int), hipMemcpyDeviceToHost, h->stream));   // (h->stream: the
+      PLDA_HIP(h, hipStreamSynchronize(h->stream));   // flag's reset and the whitening run there, a blocking copy does not wait for them)
       if (hflag) return fail(h, PLDA_E_NUMERIC, "within-class covariance is not positive definite");
     }
     TraceScope ts(h, "getoutput.eig.jacobi");
@@ -2198,7 +2200,8 @@ int simdiag_finish(plda_handle *h, const double *W, const double *B, int D, doub
   const size_t DD = (size_t)D * D;
   const int *dflag = reinterpret_cast<const int *>(h->w[13].as<double>() + 6 * DD);
   int hflag = 0, status = 0;
-  PLDA_HIP(h, hipMemcpy(&hflag, dflag, sizeof(int), hipMemcpyDeviceToHost));
+  PLDA_HIP(h, hipMemcpyAsync(&hflag, dflag, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  PLDA_HIP(h, hipStreamSynchronize(h->stream));
   PLDA_TRY(sym_eig_dc_status(h, &status));
   return simdiag_finish_with(h, W, B, D, T, Tinv, psi, hflag, status, redo);
 }

@@ -368,9 +368,9 @@ def test_fit_with_fewer_samples_than_dimensions(oracle, monkeypatch, n, d, k, fo
 def test_em_against_extended_precision_when_ill_conditioned(oracle, monkeypatch, n, d, k, skew, form):
     """Fewer samples than dimensions, six iterations: W and B against the same EM run in x87 extended precision
     (oracle/plda_oracle_np.py:fit_wb_longdouble).  Both grouped forms have to be at least as close to it as the
-    reference's formulation (the fp64 oracle) is: the moment form (PLDA_EM_VARIANT=3) with its refinement step of Q --
-    without the step it was 500 x (W) and 100 x (B) further away --, the row form (4) because it multiplies by the
-    whitening factor T and never by T^T T (sqrt(cond) instead of cond)."""
+    reference's formulation (the fp64 oracle) is: both the moment form (PLDA_EM_VARIANT=3) and the row form (4) work on
+    the whitening factor T of W + n B and never on an explicit inverse T^T T (sqrt(cond) instead of cond), with no
+    refinement step."""
     from oracle import plda_oracle_np as onp
     from plda_amd import MPlda
     x, y = make_data(777 + d, n, d, k, skew=skew, scale_between=0.5)
