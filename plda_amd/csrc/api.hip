@@ -240,7 +240,16 @@ int plda_create(int device, plda_handle **out) {
     if (const char *v = std::getenv("PLDA_GEMM64_VARIANT")) h->gemm64_variant = std::atoi(v);
     if (const char *v = std::getenv("PLDA_EIG_VARIANT")) h->eig_variant = std::atoi(v);
     if (const char *v = std::getenv("PLDA_EIG_DEBUG")) h->eig_debug = std::atoi(v);
-    if (const char *v = std::getenv("PLDA_TRANSFORM_VARIANT")) h->transform_variant = std::atoi(v);
+    if (const char *v = std::getenv("PLDA_TRANSFORM_VARIANT")) {
+      // 0 or 1 only: the other numbers named A/B and timing arms that are gone -- a script that still sets one fails here
+      // instead of timing the product kernel under the old arm's name
+      if (*v && std::strcmp(v, "0") != 0 && std::strcmp(v, "1") != 0) {
+        delete h;
+        return fail(nullptr, PLDA_E_INVAL, "plda_create: PLDA_TRANSFORM_VARIANT=%s (0: the one-pass kernel, 1: GEMM + length-norm "
+                                           "pass; no other arm exists)", v);
+      }
+      h->transform_variant = std::atoi(v);
+    }
     if (const char *v = std::getenv("PLDA_SORT_VARIANT")) h->sort_variant = std::atoi(v);
     if (const char *v = std::getenv("PLDA_ZNORM_VARIANT")) h->znorm_variant = std::atoi(v);
     if (const char *v = std::getenv("PLDA_EER_VARIANT")) h->eer_variant = std::atoi(v);

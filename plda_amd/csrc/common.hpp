@@ -194,7 +194,7 @@ struct plda_handle {
   bool panel_attr_set[16] = {};
   int num_cus = 256;           // hipDeviceAttributeMultiprocessorCount (persistent grids)
   int sort_variant = 0;        // PLDA_SORT_VARIANT=1: fit groups the rows by the radix sort always (0: by counting where the tables fit)
-  int transform_variant = 0;   // PLDA_TRANSFORM_VARIANT=1: general GEMM + separate length-norm pass; 2: no tail launch (A/B arms)
+  int transform_variant = 0;   // PLDA_TRANSFORM_VARIANT=1: GEMM + separate length-norm pass (the Dout > 512 path, forced)
   int gemm_variant = 0;
   int mixed_variant = 0;   // PLDA_MIXED_VARIANT=1: mixed enrol counts always in the depth-2D form [A1 | A2] x [V | V*V] (A/B arm of the bucketed form)
   const double *gcoef_ptr = nullptr; uint64_t gcoef_epoch = 0; int gcoef_D = 0; plda::CountSet gcoef_set;   // bucket tables in w[11], same rule

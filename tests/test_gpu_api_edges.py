@@ -379,6 +379,25 @@ def test_measurement_arms_are_not_in_the_product_library(monkeypatch, variant):
     MPlda(0)                                            # (and nothing sticks)
 
 
+@pytest.mark.parametrize("variant", ["2", "6", "7", "9", "10", "14"])
+def test_removed_transform_arms_are_refused(monkeypatch, variant):
+    """PLDA_TRANSFORM_VARIANT is 0 (the one-pass transform) or 1 (the GEMM + length-norm pair, forced).  The numbers that
+    once selected K4's A/B and timing arms -- some of them returned GARBAGE transforms with rc = 0 -- are refused by both
+    libraries: the arms are gone, and a script that still sets one must fail instead of timing the product kernel."""
+    from plda_amd import MPlda, _native
+    from plda_amd._native import PldaError
+    diags = [False, True] if os.path.exists(_native.SO_DIAG_PATH) else [False]
+    for diag in diags:
+        monkeypatch.setenv("PLDA_TRANSFORM_VARIANT", variant)
+        with pytest.raises(PldaError, match="PLDA_TRANSFORM_VARIANT=%s " % variant):
+            MPlda(0, diag=diag)
+        for ok in ("0", "1", ""):
+            monkeypatch.setenv("PLDA_TRANSFORM_VARIANT", ok)
+            MPlda(0, diag=diag)
+    monkeypatch.delenv("PLDA_TRANSFORM_VARIANT")
+    MPlda(0)                                            # (and nothing sticks)
+
+
 def test_diagnostic_library_still_has_them(monkeypatch):
     """The diagnostic build accepts the same variants (bench.py's shader-clock reading uses 47: the product kernel + stamps,
     whose scores are the product's)."""

@@ -310,17 +310,16 @@ def test_znorm_statistics_against_the_closed_form():
     assert (np.abs(gs - rs) <= 1e-9 * rs).all(), (np.abs(gs - rs) / rs).max()
 
 
-@pytest.mark.parametrize("variant", ["0", "1", "7"])
+@pytest.mark.parametrize("variant", ["0", "1"])
 @pytest.mark.parametrize("din,dout", [(7, 7), (77, 77), (128, 128), (129, 129), (200, 200), (200, 150), (209, 209),
                                       (256, 256), (257, 257), (300, 300), (385, 385), (512, 512), (512, 200),
                                       (520, 520)])
 def test_transform_rows_all_dimension_classes(din, dout, variant, monkeypatch):
     """K4 through every instantiation of the one-pass kernel -- the five dimension classes, each with its main block shape
     (row counts above one round of the persistent grid: 33 017) and its 64 / 32 / 16-row tail shapes (12 000 / 5 000 /
-    <= 1 000 rows), register-staged (product) and DMA-staged (PLDA_TRANSFORM_VARIANT=7) -- and the GEMM + length-norm
-    pair behind it (Dout > 512, or PLDA_TRANSFORM_VARIANT=1): ragged row counts, K not a multiple of 16 or of 4, truncated
-    models (Dout < Din), per-row and uniform counts, against the NumPy restatement of TransformIvector
-    (pldamodule.cpp:171 -> Plda::TransformIvector)."""
+    <= 1 000 rows) -- and the GEMM + length-norm pair behind it (Dout > 512, or PLDA_TRANSFORM_VARIANT=1): ragged row
+    counts, K not a multiple of 16 or of 4, truncated models (Dout < Din), per-row and uniform counts, against the NumPy
+    restatement of TransformIvector (pldamodule.cpp:171 -> Plda::TransformIvector)."""
     from oracle import plda_oracle_np as onp
     from plda_amd import MPlda
     monkeypatch.setenv("PLDA_TRANSFORM_VARIANT", variant)
@@ -480,13 +479,10 @@ def test_uniform_coefficients_follow_count_and_model(oracle):
 
 
 @pytest.mark.parametrize("dout", [200, 197, 193])
-def test_transform_with_the_matrix_resident_in_registers(dout, monkeypatch):
-    """transform_treg_kernel (round 4, PLDA_TRANSFORM_VARIANT=6: an A/B arm -- measured level with the product kernels, not
-    ahead; the C2 shape: Din = 200, 193 <= Dout <= 208, a uniform count, >= 32 768 rows): T's MFMA fragments stay in the
-    registers of the eight waves of a workgroup, X streams through LDS by DMA one 16-row group at a time -- against the
-    NumPy restatement of TransformIvector and against the product kernels on the same rows: whole groups, a ragged last
-    group, more groups than two rounds of the grid; truncated models put the edge of the output inside the thirteenth
-    (k-split) column tile."""
+def test_transform_c2_shape_rounds_and_tails(dout):
+    """K4 at the C2 shape (Din = 200, a uniform count) against the NumPy restatement of TransformIvector: exactly one round
+    of the persistent grid, whole rounds plus a 32-row and a 16-row tail launch; truncated models put the edge of the
+    output inside the thirteenth column tile; one row of another magnitude (the norm is per row)."""
     from oracle import plda_oracle_np as onp
     from plda_amd import MPlda
     din = 200
@@ -496,19 +492,14 @@ def test_transform_with_the_matrix_resident_in_registers(dout, monkeypatch):
     mean = rng.random(din)
     psi = np.sort(rng.random(dout) * 3.0 + 0.01)[::-1].copy()
     model = dict(mean=mean, transform=T, psi=psi, offset=-T @ mean)
-    engs = {}
-    for variant in ("6", "0"):
-        monkeypatch.setenv("PLDA_TRANSFORM_VARIANT", variant)
-        engs[variant] = MPlda(0)
-        engs[variant].set_model(mean, T, psi)
+    eng = MPlda(0)
+    eng.set_model(mean, T, psi)
     for r, ne in ((32768, 1), (40011, 7), (100000, 3)):
         x = rng.standard_normal((r, din))
         x[r // 3] *= 1e3                                   # one row of another magnitude: the norm is per row
-        got = engs["6"].transform_array(x, ne)
-        old = engs["0"].transform_array(x, ne)
+        got = eng.transform_array(x, ne)
         ref = onp.transform_ivector(model, x, ne)
         np.testing.assert_allclose(got, ref, rtol=1e-12, atol=1e-13)
-        np.testing.assert_allclose(got, old, rtol=1e-13, atol=1e-14)
 
 
 @pytest.mark.parametrize("d,kind", [(50, "mixed"), (200, "uniform"), (129, "many"), (64, "beyond")])
