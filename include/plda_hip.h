@@ -69,6 +69,9 @@ int plda_build_flags(void);
  * 0xFF bytes (NaN as a float) before its first use; an allocation that would need the fill while the handle's stream is
  * being captured fails with PLDA_E_HIP. */
 int64_t plda_device_bytes_held(void);
+/* the high-water mark of that counter since the last call with reset != 0 (process-wide, like the counter; a reset sets the
+ * mark to what is held at that moment).  What a call needed at its worst: read, call, read again. */
+int64_t plda_device_bytes_peak(int32_t reset);
 /* enqueue on exactly this hipStream_t (e.g. torch's current stream; NULL is HIP's default
  * stream, with its implicit-synchronisation rules); plda_reset_stream goes back to the
  * handle's own non-blocking stream */
@@ -263,6 +266,41 @@ int plda_score_last_shape(plda_handle *h, int64_t *M, int64_t *Nt, int32_t *gemm
  * kernel its `roofline` block prices); "" before the first call.  PLDA_E_CAPACITY when it does not fit name[cap]. */
 int plda_score_last_kernel(plda_handle *h, char *name, int64_t cap);
 
+/* ---- S-norm / adaptive S-norm (AS-norm): no counterpart in the reference, whose README says of score normalisation
+ *      "z-norm (other norms are not implemented yet)" ----
+ * A trial is normalised on BOTH sides, the enrol model against a cohort and the test vector against the same cohort, each
+ * side with the top_k LARGEST of its cohort scores (the closest impostors); top_k = Nc is plain S-norm.
+ *
+ * plda_cohort_stats*: X [R, Dout] and the cohort C [Nc, Dout] are already-transformed vectors (the cohort with
+ * num_examples = 1); n / n_uniform are the counts of the rows of X as in plda_score_matrix (test utterances: n_uniform = 1,
+ * where the LLR is symmetric in its two vectors).  With s[r, c] the fp32 score plda_score_matrix_dev(X, n, C) writes
+ * without z-norm statistics, and T(r) the multiset of the top_k largest s[r, .] (-0.0 == +0.0; finite scores only):
+ * mean[r] = mean of T(r), std[r] = POPULATION standard deviation of T(r) (as pldamodule.cpp:240-250 for z-norm), both fp64.
+ * Selection is exact (radix refinement per row, no sort, no cap on top_k); the sums are taken of (s - tau), tau the
+ * top_k-th largest value, so a row whose top_k values are equal has std exactly 0.  The result of a row does not depend on
+ * how the call is cut into slabs.  The R x Nc scores exist one row slab at a time (scored by the trials GEMM with the cohort
+ * side packed once, consumed, dropped): the call holds one slab of <= 4 GiB (by default <= 2 GiB;
+ * PLDA_SNORM_SLAB_ROWS in the environment at plda_create sets the rows per slab) beyond the
+ * packed operands, whatever R x Nc is.  A prepared test side (plda_score_prepare_dev) is dropped.  The _dev form enqueues on
+ * the handle's stream (mixed counts: one wait, as plda_score_matrix_dev).
+ *
+ * plda_score_matrix_snorm*: the trials matrix of plda_score_matrix (no z-norm) mapped with per-row statistics (emean, estd)[M]
+ * and per-column statistics (tmean, tstd)[Nt], in fp64 on the finished fp32 score `raw`, rounded once to fp32:
+ *     side(raw, m, s) = (raw - m) / s  if s != 0  else raw                       (the guard of pldamodule.cpp:269-273)
+ *     out[i, j] = 0.5 * (side(raw, emean[i], estd[i]) + side(raw, tmean[j], tstd[j]))
+ * One pair may be NULL (both of its pointers): out = side of the other pair, without the 0.5.  Both pairs NULL, or one
+ * pointer of a pair alone, is PLDA_E_INVAL.  Columns [Nt, ld_out) are not written. */
+int plda_cohort_stats_dev(plda_handle *h, const double *dX, const int32_t *dn, int32_t n_uniform, int64_t R,
+                          const double *dC, int64_t Nc, int64_t top_k, double *dmean, double *dstd);
+int plda_cohort_stats(plda_handle *h, const double *X, const int32_t *n, int32_t n_uniform, int64_t R,
+                      const double *C, int64_t Nc, int64_t top_k, double *mean, double *std);
+int plda_score_matrix_snorm_dev(plda_handle *h, const double *dU, const int32_t *dn_enrol, int32_t n_uniform, int64_t M,
+                                const double *dV, int64_t Nt, const double *demean, const double *destd,
+                                const double *dtmean, const double *dtstd, float *dout, int64_t ld_out);
+int plda_score_matrix_snorm(plda_handle *h, const double *U, const int32_t *n_enrol, int32_t n_uniform, int64_t M,
+                            const double *V, int64_t Nt, const double *emean, const double *estd, const double *tmean,
+                            const double *tstd, float *out, int64_t ld_out);
+
 /* ---- z-norm: replaces MPlda_norm (pldamodule.cpp:196-256) ----
  * Every cohort row is transformed with num_examples = Nb (:224) and scored as
  * the TRAIN side with n = 1 against every model vector (:235); per model the
@@ -454,6 +492,11 @@ int plda_score_matrix_sharded_local_dev(plda_handle *h, const double *dU, const 
 int plda_znorm_stats_sharded_dev(plda_handle *h, const double *dbkg, int64_t Nb, int32_t num_examples,
                                  int32_t Din, const double *dmodels, int64_t M, double *dout_mean,
                                  double *dout_std);
+/* plda_cohort_stats_dev with the R rows split contiguously over the ranks exactly like plda_znorm_stats_sharded_dev (every rank
+ * passes ALL rows and the whole cohort); one all-gather of the two fp64 result vectors: every rank ends with all R results,
+ * bit-identical to the single-rank call. */
+int plda_cohort_stats_sharded_dev(plda_handle *h, const double *dX, const int32_t *dn, int32_t n_uniform, int64_t R,
+                                  const double *dC, int64_t Nc, int64_t top_k, double *dmean, double *dstd);
 int plda_fit_sharded_dev(plda_handle *h, const double *dX, int64_t N, int32_t D, const uint64_t *dlabels,
                          int64_t K, int32_t iters);
 int plda_eer_matrix_comm_dev(plda_handle *h, const float *dscores, int64_t ld, int64_t M, int64_t Nt,

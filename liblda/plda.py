@@ -36,6 +36,17 @@ class PLDA(object):
     def score_trials(self, enrol, test, e_idx, t_idx, znorm=True):
         return self._instance.score_trials(enrol, test, e_idx, t_idx, znorm)
 
+    def cohort_stats(self, side, cohort, top_k=None):
+        """(mean, std) of the top_k largest cohort scores of every row of `side` (AS-norm statistics)."""
+        return self._instance.cohort_stats(side, cohort, top_k)
+
+    def score_matrix_asnorm(self, enrol, test, cohort, top_k=None):
+        """float32 [M, Nt] matrix, every trial normalised on both sides against the top_k closest cohort vectors."""
+        return self._instance.score_matrix_asnorm(enrol, test, cohort, top_k)
+
+    def score_trials_asnorm(self, enrol, test, e_idx, t_idx, cohort, top_k=None):
+        return self._instance.score_trials_asnorm(enrol, test, e_idx, t_idx, cohort, top_k)
+
     def transform_array(self, xbar, num_examples=1):
         return self._instance.transform_array(xbar, num_examples)
 

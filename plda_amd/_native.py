@@ -28,6 +28,7 @@ SIGNATURES = {
     "plda_abi_version": (C.c_int, []),
     "plda_build_flags": (C.c_int, []),
     "plda_device_bytes_held": (_i64, []),
+    "plda_device_bytes_peak": (_i64, [_i32]),
     "plda_create": (C.c_int, [C.c_int, C.POINTER(_vp)]),
     "plda_destroy": (C.c_int, [_vp]),
     "plda_last_error": (C.c_char_p, [_vp]),
@@ -105,6 +106,11 @@ SIGNATURES = {
     "plda_eer_matrix_comm_dev": (C.c_int, [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp]),
     "plda_znorm_stats": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _i64, _vp, _vp]),
     "plda_znorm_stats_dev": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _i64, _vp, _vp]),
+    "plda_cohort_stats": (C.c_int, [_vp, _vp, _vp, _i32, _i64, _vp, _i64, _i64, _vp, _vp]),
+    "plda_cohort_stats_sharded_dev": (C.c_int, [_vp, _vp, _vp, _i32, _i64, _vp, _i64, _i64, _vp, _vp]),
+    "plda_cohort_stats_dev": (C.c_int, [_vp, _vp, _vp, _i32, _i64, _vp, _i64, _i64, _vp, _vp]),
+    "plda_score_matrix_snorm": (C.c_int, [_vp, _vp, _vp, _i32, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64]),
+    "plda_score_matrix_snorm_dev": (C.c_int, [_vp, _vp, _vp, _i32, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64]),
 }
 
 # plda_collectives / plda_host_collectives (include/plda_hip.h): callback tables of the multi-GPU entry points

@@ -18,6 +18,7 @@
 namespace plda {
 
 std::atomic<int64_t> g_device_bytes{0};
+std::atomic<int64_t> g_device_bytes_peak{0};
 std::atomic<int> g_scratch_poison{0};
 thread_local hipStream_t g_call_stream = nullptr;
 static thread_local std::string g_create_err;
@@ -88,6 +89,8 @@ int score_matrix_sharded_device(plda_handle *h, const double *dU, const int32_t 
 int znorm_stats_sharded_device(plda_handle *h, const double *dbkg, int64_t Nb, int num_examples, int Din,
                                const double *dmodels, int64_t M, double *dmean, double *dstd);
 int fit_sharded_device(plda_handle *h, const double *dX, int64_t N, int D, const uint64_t *dlabels, int64_t K, int iters);
+int cohort_stats_sharded_device(plda_handle *h, const double *dX, const int32_t *dn, int n_uniform, int64_t Rows, const double *dC,
+                                int64_t Nc, int64_t top_k, double *dmean, double *dstd);
 int eer_matrix_comm_device(plda_handle *h, const float *dscores, int64_t ld, int64_t M, int64_t Nt, const int64_t *despk,
                            const int64_t *dtspk, double *out);
 
@@ -186,6 +189,11 @@ extern "C" {
 int plda_abi_version(void) { return 2; }
 int plda_build_flags(void) { return PLDA_DIAG ? 1 : 0; }
 int64_t plda_device_bytes_held(void) { return g_device_bytes.load(std::memory_order_relaxed); }
+int64_t plda_device_bytes_peak(int32_t reset) {
+  const int64_t peak = g_device_bytes_peak.load(std::memory_order_relaxed);
+  if (reset) g_device_bytes_peak.store(g_device_bytes.load(std::memory_order_relaxed), std::memory_order_relaxed);
+  return peak;
+}
 
 int plda_create(int device, plda_handle **out) {
   return guarded(nullptr, "plda_create", [&]() -> int {
@@ -254,6 +262,7 @@ int plda_create(int device, plda_handle **out) {
     if (const char *v = std::getenv("PLDA_ZNORM_VARIANT")) h->znorm_variant = std::atoi(v);
     if (const char *v = std::getenv("PLDA_EER_VARIANT")) h->eer_variant = std::atoi(v);
     if (const char *v = std::getenv("PLDA_EER_SLAB_ROWS")) h->eer_slab_rows = std::atoll(v);
+    if (const char *v = std::getenv("PLDA_SNORM_SLAB_ROWS")) h->sn_slab_rows = std::atoll(v);
     if (const char *v = std::getenv("PLDA_HIP_TRACE")) h->trace_on = h->trace_print = std::atoi(v) != 0;
     if (const char *v = std::getenv("PLDA_HOST_VARIANT")) h->host_variant = std::atoi(v);
     if (const char *v = std::getenv("PLDA_SWEEP_VARIANT")) h->sweep_variant = std::atoi(v);
@@ -1156,6 +1165,105 @@ int plda_znorm_stats(plda_handle *h, const double *bkg, int64_t Nb, int32_t num_
   });
 }
 
+// ---------------------------------------------------------------- AS-norm (snorm.hip)
+int plda_cohort_stats_dev(plda_handle *h, const double *dX, const int32_t *dn, int32_t n_uniform, int64_t R, const double *dC,
+                          int64_t Nc, int64_t top_k, double *dmean, double *dstd) {
+  return guarded(h, "plda_cohort_stats_dev", [&]() -> int {
+    if (!h) return PLDA_E_INVAL;
+    PLDA_LOCK(h);
+    PLDA_TRY(set_device(h));
+    return cohort_stats_device(h, dX, dn, n_uniform, R, dC, Nc, top_k, dmean, dstd);
+  });
+}
+
+int plda_cohort_stats(plda_handle *h, const double *X, const int32_t *n, int32_t n_uniform, int64_t R, const double *Cv,
+                      int64_t Nc, int64_t top_k, double *mean, double *std_) {
+  return guarded(h, "plda_cohort_stats", [&]() -> int {
+    if (!h) return PLDA_E_INVAL;
+    PLDA_LOCK(h);
+    if (!h->fitted) return fail(h, PLDA_E_NOT_FITTED, "cohort_stats: model not fitted");
+    if (R < 1 || Nc < 1) return fail(h, PLDA_E_INVAL, "cohort_stats: R = %lld, Nc = %lld (both must be >= 1)", (long long)R, (long long)Nc);
+    if (top_k < 1 || top_k > Nc) return fail(h, PLDA_E_INVAL, "cohort_stats: top_k = %lld (must be in 1 ... Nc = %lld)", (long long)top_k, (long long)Nc);
+    if (!X || !Cv || !mean || !std_) return fail(h, PLDA_E_INVAL, "cohort_stats: %s is NULL", !X ? "X" : !Cv ? "cohort" : !mean ? "mean" : "std");
+    if (!n && n_uniform <= 0) return fail(h, PLDA_E_INVAL, "cohort_stats: n_uniform must be > 0 when n is NULL");
+    PLDA_TRY(set_device(h));
+    const int D = h->Dout;
+    Tmp dX, dN, dC, dMean, dStd;
+    CountSet cs;                                         // from the host array: no device pass, no wait
+    if (n) score_count_set_host(n, R, &cs);
+    PLDA_TRY(upload(h, dC, Cv, (size_t)Nc * D * 8));
+    PLDA_TRY(upload(h, dX, X, (size_t)R * D * 8));
+    if (n) PLDA_TRY(upload(h, dN, n, (size_t)R * 4));
+    PLDA_HIP(h, dMean.alloc((size_t)R * 8));
+    PLDA_HIP(h, dStd.alloc((size_t)R * 8));
+    const int rc = cohort_stats_device(h, dX.as<double>(), n ? dN.as<int32_t>() : nullptr, n_uniform, R, dC.as<double>(), Nc, top_k,
+                                       dMean.as<double>(), dStd.as<double>(), n ? &cs : nullptr);
+    if (rc != PLDA_OK) { (void)hipStreamSynchronize(h->stream); return rc; }
+    PLDA_HIP(h, hipMemcpyAsync(mean, dMean.p, (size_t)R * 8, hipMemcpyDeviceToHost, h->stream));
+    PLDA_HIP(h, hipMemcpyAsync(std_, dStd.p, (size_t)R * 8, hipMemcpyDeviceToHost, h->stream));
+    PLDA_HIP(h, hipStreamSynchronize(h->stream));
+    return PLDA_OK;
+  });
+}
+
+int plda_score_matrix_snorm_dev(plda_handle *h, const double *dU, const int32_t *dn_enrol, int32_t n_uniform, int64_t M,
+                                const double *dV, int64_t Nt, const double *demean, const double *destd, const double *dtmean,
+                                const double *dtstd, float *dout, int64_t ld_out) {
+  return guarded(h, "plda_score_matrix_snorm_dev", [&]() -> int {
+    if (!h) return PLDA_E_INVAL;
+    PLDA_LOCK(h);
+    PLDA_TRY(set_device(h));
+    return score_matrix_snorm_device(h, dU, dn_enrol, n_uniform, M, dV, Nt, demean, destd, dtmean, dtstd, dout, ld_out);
+  });
+}
+
+// Host pointers: everything but the scores is uploaded once; the scores cross in row slabs of <= 1 GiB through one device buffer.
+int plda_score_matrix_snorm(plda_handle *h, const double *U, const int32_t *n_enrol, int32_t n_uniform, int64_t M, const double *V,
+                            int64_t Nt, const double *emean, const double *estd, const double *tmean, const double *tstd,
+                            float *out, int64_t ld_out) {
+  return guarded(h, "plda_score_matrix_snorm", [&]() -> int {
+    if (!h) return PLDA_E_INVAL;
+    PLDA_LOCK(h);
+    if (!h->fitted) return fail(h, PLDA_E_NOT_FITTED, "score_matrix_snorm: model not fitted");
+    if ((emean == nullptr) != (estd == nullptr)) return fail(h, PLDA_E_INVAL, "score_matrix_snorm: %s is NULL but its partner is not", emean ? "estd" : "emean");
+    if ((tmean == nullptr) != (tstd == nullptr)) return fail(h, PLDA_E_INVAL, "score_matrix_snorm: %s is NULL but its partner is not", tmean ? "tstd" : "tmean");
+    if (!emean && !tmean) return fail(h, PLDA_E_INVAL, "score_matrix_snorm: both statistic pairs are NULL (emean/estd or tmean/tstd must be given)");
+    if (M < 1 || Nt < 1) return fail(h, PLDA_E_INVAL, "score_matrix_snorm: M = %lld, Nt = %lld (both must be >= 1)", (long long)M, (long long)Nt);
+    if (!U || !V || !out) return fail(h, PLDA_E_INVAL, "score_matrix_snorm: %s is NULL", !U ? "U" : !V ? "V" : "out");
+    if (ld_out < Nt) return fail(h, PLDA_E_INVAL, "score_matrix_snorm: ld_out = %lld < Nt = %lld", (long long)ld_out, (long long)Nt);
+    if (!n_enrol && n_uniform <= 0) return fail(h, PLDA_E_INVAL, "score_matrix_snorm: n_uniform must be > 0 when n_enrol is NULL");
+    PLDA_TRY(set_device(h));
+    const int D = h->Dout;
+    Tmp dV, dU, dN, dEm, dEs, dTm, dTs, dO;
+    CountSet cs;                                         // the distinct counts of ALL rows: every slab sees the same set
+    if (n_enrol) score_count_set_host(n_enrol, M, &cs);
+    PLDA_TRY(upload(h, dV, V, (size_t)Nt * D * 8));
+    PLDA_TRY(upload(h, dU, U, (size_t)M * D * 8));
+    if (n_enrol) PLDA_TRY(upload(h, dN, n_enrol, (size_t)M * 4));
+    if (emean) { PLDA_TRY(upload(h, dEm, emean, (size_t)M * 8)); PLDA_TRY(upload(h, dEs, estd, (size_t)M * 8)); }
+    if (tmean) { PLDA_TRY(upload(h, dTm, tmean, (size_t)Nt * 8)); PLDA_TRY(upload(h, dTs, tstd, (size_t)Nt * 8)); }
+    const int64_t ld = round_up(Nt, 4);
+    int64_t slab = std::max<int64_t>(1, std::min<int64_t>(M, ((int64_t)1 << 30) / 4 / ld));
+    PLDA_HIP(h, dO.alloc((size_t)slab * ld * 4));
+    int rc = PLDA_OK;
+    for (int64_t r0 = 0; r0 < M && rc == PLDA_OK; r0 += slab) {
+      const int64_t m = std::min(slab, M - r0);
+      rc = score_matrix_snorm_device(h, dU.as<double>() + r0 * D, n_enrol ? dN.as<int32_t>() + r0 : nullptr, n_uniform, m, dV.as<double>(), Nt,
+                                     emean ? dEm.as<double>() + r0 : nullptr, emean ? dEs.as<double>() + r0 : nullptr,
+                                     tmean ? dTm.as<double>() : nullptr, tmean ? dTs.as<double>() : nullptr, dO.as<float>(), ld,
+                                     n_enrol ? &cs : nullptr, /*reuse_packed_B=*/r0 > 0);
+      if (rc != PLDA_OK) break;
+      const hipError_t e = hipMemcpy2DAsync(out + r0 * ld_out, (size_t)ld_out * 4, dO.p, (size_t)ld * 4, (size_t)Nt * 4, (size_t)m,
+                                            hipMemcpyDeviceToHost, h->stream);
+      if (e != hipSuccess) rc = hip_fail(h, e, "hipMemcpy2DAsync", __FILE__, __LINE__);
+      else if ((rc = (hipStreamSynchronize(h->stream) == hipSuccess) ? PLDA_OK : PLDA_E_HIP) != PLDA_OK) fail(h, rc, "score_matrix_snorm: stream synchronisation failed");
+    }
+    (void)hipStreamSynchronize(h->stream);                // the temporaries go out of scope
+    h->last_M = M;
+    return rc;
+  });
+}
+
 // ---------------------------------------------------------------- d-vector front-end
 int plda_dvector_pool_dev(plda_handle *h, const void *dframes, int32_t dtype, int64_t T, int32_t D,
                           const int64_t *doffsets, int64_t U, int32_t method, int32_t l2norm, double *dout) {
@@ -1503,6 +1611,18 @@ int plda_znorm_stats_sharded_dev(plda_handle *h, const double *dbkg, int64_t Nb,
     if (!dbkg || !dmodels || !dout_mean || !dout_std || Nb <= 0 || M <= 0) return fail(h, PLDA_E_INVAL, "norm: bad argument");
     PLDA_TRY(set_device(h));
     return znorm_stats_sharded_device(h, dbkg, Nb, num_examples, Din, dmodels, M, dout_mean, dout_std);
+  });
+}
+
+int plda_cohort_stats_sharded_dev(plda_handle *h, const double *dX, const int32_t *dn, int32_t n_uniform, int64_t R, const double *dC,
+                                  int64_t Nc, int64_t top_k, double *dmean, double *dstd) {
+  return guarded(h, "plda_cohort_stats_sharded_dev", [&]() -> int {
+    if (!h) return PLDA_E_INVAL;
+    PLDA_LOCK(h);
+    if (!h->fitted) return fail(h, PLDA_E_NOT_FITTED, "cohort_stats: model not fitted");
+    if (!dX || !dC || !dmean || !dstd || R < 1 || Nc < 1 || top_k < 1 || top_k > Nc) return fail(h, PLDA_E_INVAL, "cohort_stats_sharded: bad argument");
+    PLDA_TRY(set_device(h));
+    return cohort_stats_sharded_device(h, dX, dn, n_uniform, R, dC, Nc, top_k, dmean, dstd);
   });
 }
 

@@ -778,6 +778,27 @@ int znorm_stats_sharded_device(plda_handle *h, const double *dbkg, int64_t Nb, i
   return PLDA_OK;
 }
 
+// ------------------------------------------------------------------------------------ AS-norm cohort statistics by row
+// every rank passes ALL R rows and the whole cohort (as the models of the z-norm above); the distinct counts are those of all
+// rows, so that every rank scores in the form the single-rank call would choose
+int cohort_stats_sharded_device(plda_handle *h, const double *dX, const int32_t *dn, int n_uniform, int64_t Rows, const double *dC,
+                                int64_t Nc, int64_t top_k, double *dmean, double *dstd) {
+  const int R = h->comm_nranks, me = h->comm_rank;
+  int64_t b, e;
+  shard_range(Rows, R, me, b, e);
+  CountSet cs;
+  if (dn) PLDA_TRY(score_count_set_device(h, dn, Rows, &cs));
+  if (e > b)
+    PLDA_TRY(cohort_stats_device(h, dX + b * h->Dout, dn ? dn + b : nullptr, n_uniform, e - b, dC, Nc, top_k, dmean + b, dstd + b,
+                                 dn ? &cs : nullptr));
+  if (R == 1 || !h->comm) return PLDA_OK;
+  std::vector<int64_t> offs(R), counts(R);
+  for (int q = 0; q < R; ++q) { int64_t qb, qe; shard_range(Rows, R, q, qb, qe); offs[q] = qb * 8; counts[q] = (qe - qb) * 8; }
+  PLDA_COLL(h, h->coll.all_gather_v(h->coll.ctx, dmean, offs.data(), counts.data(), h->stream), "all_gather_v");
+  PLDA_COLL(h, h->coll.all_gather_v(h->coll.ctx, dstd, offs.data(), counts.data(), h->stream), "all_gather_v");
+  return PLDA_OK;
+}
+
 // ------------------------------------------------------------------------------------ fit by speaker
 int fit_em_device(plda_handle *h, int64_t K, int D, int iters);
 

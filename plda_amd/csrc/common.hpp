@@ -25,6 +25,8 @@ namespace plda {
 
 // Device-allocation bookkeeping shared by the library's only two allocation sites, DevBuf::reserve and Tmp::alloc.
 //  * g_device_bytes: the bytes every DevBuf / Tmp of the process holds right now (plda_device_bytes_held; the leak tests).
+//  * g_device_bytes_peak: the high-water mark of that counter since the last plda_device_bytes_peak(reset) (one atomic max
+//    where the counter grows; the slab-cap test of plda_cohort_stats_dev).
 //  * g_scratch_poison (PLDA_SCRATCH_POISON=1 at plda_create; tests only): every allocation gets POISON_TAIL more bytes and is
 //    filled with 0xFF bytes (NaN as f64 / f32, -1 as an integer) before it is handed out, so that a kernel reading scratch
 //    nobody wrote, or reading past the end of a buffer, shows up as NaN or a bad index instead of the zeros of fresh memory.
@@ -32,6 +34,7 @@ namespace plda {
 //    call) -- a fill is refused while it is being captured into a graph.
 // (Not counted or poisoned: the peer transport's flag page, comm.hip, an uncached allocation of its own.)
 extern std::atomic<int64_t> g_device_bytes;
+extern std::atomic<int64_t> g_device_bytes_peak;
 extern std::atomic<int> g_scratch_poison;
 extern thread_local hipStream_t g_call_stream;
 constexpr size_t POISON_TAIL = (size_t)64 << 10;   // > the row-form EM's worst over-read (15 rows of 8 D bytes at D <= 512)
@@ -39,7 +42,9 @@ constexpr size_t POISON_TAIL = (size_t)64 << 10;   // > the row-form EM's worst 
 inline size_t alloc_extra() { return g_scratch_poison.load(std::memory_order_relaxed) ? POISON_TAIL : 0; }
 // after a successful allocation of `bytes` (extra included): count it, and poison it when the switch is on
 inline hipError_t alloc_done(void *p, size_t bytes) {
-  g_device_bytes.fetch_add((int64_t)bytes, std::memory_order_relaxed);
+  const int64_t now = g_device_bytes.fetch_add((int64_t)bytes, std::memory_order_relaxed) + (int64_t)bytes;
+  int64_t peak = g_device_bytes_peak.load(std::memory_order_relaxed);
+  while (peak < now && !g_device_bytes_peak.compare_exchange_weak(peak, now, std::memory_order_relaxed)) {}
   if (!g_scratch_poison.load(std::memory_order_relaxed)) return hipSuccess;
   hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
   if (g_call_stream && hipStreamIsCapturing(g_call_stream, &st) == hipSuccess && st != hipStreamCaptureStatusNone)
@@ -253,6 +258,8 @@ struct plda_handle {
   plda::DevBuf eer_list[2];      // eer.hip, single-pass form: the impostor / target scores inside the pilot's key window
   int eer_variant = 0;           // PLDA_EER_VARIANT=1: always the three passes; 2: the single-pass form at every size (tests)
   int64_t eer_slab_rows = 0;     // PLDA_EER_SLAB_ROWS: rows per slab of plda_score_eer_dev (0: <= 4 GiB of scores)
+  plda::DevBuf sn_slab;          // plda_cohort_stats_dev (snorm.hip): the row slab of cohort scores in flight
+  int64_t sn_slab_rows = 0;      // PLDA_SNORM_SLAB_ROWS: rows per slab of plda_cohort_stats_dev / plda_score_matrix_snorm_dev (0: by size)
   int eer_last_passes = 0;       // full passes over the matrix the last plda_eer_matrix_dev made (1 or 3)
   const int *eigdc_flag = nullptr;   // device flag of the last direct decomposition (sym_eig_dc_status)
   int eig_variant = 0;           // PLDA_EIG_VARIANT: 0 = direct method where supported, 1 = block Jacobi always
@@ -421,6 +428,14 @@ int quadform_rows_device(plda_handle *h, const double *dX, int64_t R, int D, con
                          double *out_std, bool *used);
 int transform_rows_device(plda_handle *h, const double *dX, int64_t R, int Din,
                           const int32_t *dn, int n_uniform, double *dout);
+
+// ---- snorm.hip (adaptive symmetric score normalisation: top-K cohort statistics, the two-sided map) ----
+// cs: as score_matrix_device (the distinct counts of the caller's whole call; nullptr: found here)
+int cohort_stats_device(plda_handle *h, const double *dX, const int32_t *dn, int n_uniform, int64_t R, const double *dC,
+                        int64_t Nc, int64_t top_k, double *dmean, double *dstd, const CountSet *cs = nullptr);
+int score_matrix_snorm_device(plda_handle *h, const double *dU, const int32_t *dn, int n_uniform, int64_t M, const double *dV,
+                              int64_t Nt, const double *demean, const double *destd, const double *dtmean, const double *dtstd,
+                              float *dout, int64_t ld, const CountSet *cs = nullptr, bool reuse_packed_B = false);
 
 #ifdef __HIPCC__
 // fp64 wave-wide sum through DPP: quad butterflies, then half-row and row mirrors (every

@@ -487,6 +487,67 @@ class MPlda(object):
                                             _ptr(e), _ptr(t), e.shape[0], _ptr(zm), _ptr(zs), _ptr(out)))
         return out
 
+    # ------------------------------------------------- S-norm / adaptive S-norm (csrc/snorm.hip)
+    def _cohort_rows(self, cohort):
+        """[Nc, Dout] array, or a dict / (counts, vecs) as `_unpack` takes (its counts are ignored: a cohort vector is one
+        utterance)."""
+        if isinstance(cohort, (dict, tuple, list)):
+            return self._unpack(cohort)[2]
+        return self._check_dim(np.ascontiguousarray(cohort, np.float64), "cohort")
+
+    def _cohort_stats(self, counts, X, Cv, top_k):
+        r, nc = X.shape[0], Cv.shape[0]
+        k = nc if top_k is None else int(top_k)
+        mean, std = np.empty(r), np.empty(r)
+        if r == 0:
+            return mean, std
+        uniform = int(counts[0]) if np.all(counts == counts[0]) else 0
+        self._ck(self._lib.plda_cohort_stats(self._h, _ptr(X), None if uniform else _ptr(counts), uniform, r, _ptr(Cv), nc, k,
+                                             _ptr(mean), _ptr(std)))
+        return mean, std
+
+    def cohort_stats(self, side, cohort, top_k=None):
+        """(mean, std) float64 [R] in the order of `side`: mean and population std of the top_k LARGEST scores of every
+        row of `side` against the already-transformed `cohort` (top_k=None: all of it -- plain S-norm statistics)."""
+        _, counts, X = self._unpack(side)
+        return self._cohort_stats(counts, X, self._cohort_rows(cohort), top_k)
+
+    def score_matrix_asnorm(self, enrol, test, cohort, top_k=None):
+        """float32 [M, Nt]: every trial normalised on both sides, 0.5 ((s - mean_e) / std_e + (s - mean_t) / std_t), the
+        enrol model and the test vector each against the top_k closest vectors of `cohort` (a side whose std is 0 contributes
+        the raw score).  The test side is scored with n = 1 whatever counts `test` stores, as in score_matrix."""
+        _, counts, U = self._unpack(enrol)
+        _, _, V = self._unpack(test)
+        Cv = self._cohort_rows(cohort)
+        m, nt = U.shape[0], V.shape[0]
+        out = np.empty((m, nt), np.float32)
+        if m == 0 or nt == 0:
+            return out
+        em, es = self._cohort_stats(counts, U, Cv, top_k)
+        tm, ts = self._cohort_stats(np.ones(nt, np.int32), V, Cv, top_k)
+        uniform = int(counts[0]) if np.all(counts == counts[0]) else 0
+        self._ck(self._lib.plda_score_matrix_snorm(self._h, _ptr(U), None if uniform else _ptr(counts), uniform, m, _ptr(V), nt,
+                                                   _ptr(em), _ptr(es), _ptr(tm), _ptr(ts), _ptr(out), nt))
+        return out
+
+    def score_trials_asnorm(self, enrol, test, e_idx, t_idx, cohort, top_k=None):
+        """The fp64 trial-list scores of score_trials(..., znorm=False) with the same two-sided map, applied on the host."""
+        _, counts, U = self._unpack(enrol)
+        _, _, V = self._unpack(test)
+        Cv = self._cohort_rows(cohort)
+        e = np.ascontiguousarray(e_idx, np.int64).reshape(-1)
+        t = np.ascontiguousarray(t_idx, np.int64).reshape(-1)
+        raw = self.score_trials((counts, U), (np.ones(V.shape[0], np.int32), V), e, t, znorm=False)
+        if e.shape[0] == 0:
+            return raw
+        em, es = self._cohort_stats(counts, U, Cv, top_k)
+        tm, ts = self._cohort_stats(np.ones(V.shape[0], np.int32), V, Cv, top_k)
+
+        def side(m, s):
+            ok = s != 0.0
+            return np.where(ok, (raw - m) / np.where(ok, s, 1.0), raw)
+        return 0.5 * (side(em[e], es[e]) + side(tm[t], ts[t]))
+
     # ------------------------------------------------- device-resident path
     def set_stream(self, hip_stream):
         """Enqueue on this hipStream_t (an int handle, e.g. torch.cuda.current_stream().cuda_stream;
@@ -603,6 +664,20 @@ class MPlda(object):
             self._h, C.c_void_p(int(dU)), C.c_void_p(int(dn)) if dn else None, int(n_uniform), int(m),
             C.c_void_p(int(dV)), int(nt), C.c_void_p(int(dzmean)) if dzmean else None,
             C.c_void_p(int(dzstd)) if dzstd else None, C.c_void_p(int(dout)), int(ld)))
+
+    def cohort_stats_dev(self, dX, dn, n_uniform, r, dC, nc, top_k, dmean, dstd):
+        """Enqueue the top_k cohort statistics of r HBM-resident rows (raw device addresses; dmean, dstd: float64 [r])."""
+        self._ck(self._lib.plda_cohort_stats_dev(
+            self._h, C.c_void_p(int(dX)), C.c_void_p(int(dn)) if dn else None, int(n_uniform), int(r), C.c_void_p(int(dC)),
+            int(nc), int(top_k), C.c_void_p(int(dmean)) if dmean else None, C.c_void_p(int(dstd)) if dstd else None))
+
+    def score_matrix_snorm_dev(self, dU, dn, n_uniform, m, dV, nt, dout, ld, demean=None, destd=None, dtmean=None, dtstd=None):
+        """Enqueue one trials block normalised with per-row (demean, destd) and / or per-column (dtmean, dtstd) statistics."""
+        def vp(x):
+            return C.c_void_p(int(x)) if x else None
+        self._ck(self._lib.plda_score_matrix_snorm_dev(
+            self._h, vp(dU), vp(dn), int(n_uniform), int(m), vp(dV), int(nt), vp(demean), vp(destd), vp(dtmean), vp(dtstd),
+            vp(dout), int(ld)))
 
     def score_prepare_dev(self, dV, nt, mixed_counts=False, n_uniform=1):
         """Pack the test side [nt, Dout] (HBM-resident fp64) once; later score_matrix_dev / sharded calls with the same
@@ -721,6 +796,11 @@ class MPlda(object):
         self._ck(self._lib.plda_znorm_stats_sharded_dev(self._h, C.c_void_p(int(dbkg)), int(nb), int(num_examples), int(d),
                                                         C.c_void_p(int(dmodels)), int(m), C.c_void_p(int(dmean)),
                                                         C.c_void_p(int(dstd))))
+
+    def cohort_stats_sharded_dev(self, dX, dn, n_uniform, r, dC, nc, top_k, dmean, dstd):
+        self._ck(self._lib.plda_cohort_stats_sharded_dev(
+            self._h, C.c_void_p(int(dX)), C.c_void_p(int(dn)) if dn else None, int(n_uniform), int(r), C.c_void_p(int(dC)),
+            int(nc), int(top_k), C.c_void_p(int(dmean)), C.c_void_p(int(dstd))))
 
     def fit_sharded_dev(self, dX, n, d, dlabels, k, iters=10):
         """Fit with the statistics pass over THIS rank's speakers (local dense labels 0..k-1)."""

@@ -2,7 +2,7 @@
 
 The sharding itself -- trials by enrol row, z-norm statistics by model, fit statistics by speaker, EER
 counters summed -- lives behind the C ABI (csrc/comm.hip: plda_score_matrix_sharded[_local]_dev,
-plda_znorm_stats_sharded_dev, plda_fit_sharded_dev, plda_eer_matrix_comm_dev); this module only
+plda_znorm_stats_sharded_dev, plda_cohort_stats_sharded_dev, plda_fit_sharded_dev, plda_eer_matrix_comm_dev); this module only
 
   * gives an engine its communicator (`init_comm`): RCCL over xGMI (production), or any
     torch.distributed backend as a HOST transport (`TorchHostTransport`: the two host operations of
@@ -281,6 +281,19 @@ def znorm_stats_sharded(engine, bkg, models, num_examples=0):
     std = torch.empty(m, dtype=torch.float64, device=dev)
     engine.znorm_stats_sharded_dev(bkg.data_ptr(), bkg.shape[0], num_examples, bkg.shape[1], models.data_ptr(), m,
                                    mean.data_ptr(), std.data_ptr())
+    return mean, std
+
+
+def cohort_stats_sharded(engine, X, n, cohort, top_k, n_uniform=0):
+    """AS-norm cohort statistics sharded by ROW: every rank scores its contiguous slab of the replicated rows `X` [R, Dout]
+    (n int32 [R] or None with n_uniform) against the whole `cohort` [Nc, Dout]; (mean[R], std[R]) on every rank."""
+    dev = X.device
+    _on_torch_stream(engine, dev)
+    r = X.shape[0]
+    mean = torch.empty(r, dtype=torch.float64, device=dev)
+    std = torch.empty(r, dtype=torch.float64, device=dev)
+    engine.cohort_stats_sharded_dev(X.data_ptr(), n.data_ptr() if n is not None else None, n_uniform, r, cohort.data_ptr(),
+                                    cohort.shape[0], top_k, mean.data_ptr(), std.data_ptr())
     return mean, std
 
 
