@@ -388,6 +388,92 @@ int plda_eer_matrix_sharded_dev(plda_handle *h, const float *dscores, int64_t ld
                                 const int64_t *denrol_spk, const int64_t *dtest_spk,
                                 plda_eer_reduce_fn reduce, void *ctx, double *out);
 
+/* ---- linear score calibration, Cllr and actual DCF (the step after normalisation; the reference stops at the EER,
+ * scoring/eer.py:68-73, so this is the project's own extension: tests/calibration_model.py pins it).
+ *
+ * A z- or AS-normalised score is not a log-likelihood ratio any more; the affine map llr = a * s + b, trained by
+ * prior-weighted logistic regression on labelled trials (the "linear calibration" of BOSARIS / FoCal), makes it one.
+ * Trials and their class are those of plda_eer_matrix_dev / plda_eer_lists: an fp32 score s, a target iff
+ * enrol_spk[i] == test_spk[j] (matrix and operand forms) or by list.  Np, Nn are the class counts.
+ *
+ * One CALIBRATION PASS at (a, c, theta), all fp64, computes per trial y = a * (double)s + c, e = exp(-|y|), and in the
+ * overflow-free forms softplus(y) = max(y, 0) + log1p(e), p = sigmoid(y) = y >= 0 ? 1/(1+e) : e/(1+e), w = p (1 - p) = e/(1+e)^2:
+ *
+ *     class        L                   G0           G1             H0       H1         H2
+ *     target       sum softplus(-y)    sum (1-p)    sum (1-p) s    sum w    sum w s    sum w s^2
+ *     non-target   sum softplus(y)     sum p        sum p s        sum w    sum w s    sum w s^2
+ *
+ * plus the exact integers Np, Nn, miss = #{target: (double)s < theta}, fa = #{non-target: (double)s >= theta} (the FAR / FRR
+ * convention of the EER above; the threshold is compared on the RAW score, so the counts do not depend on how y was
+ * rounded), the number of non-finite scores, and per class the fp32 minimum and maximum: one plda_calib_record.  Its sums and
+ * counts add across row shards (min / max combine by min / max), so a sharded form is a reduction of records.  The sums are
+ * taken without floating-point atomics in a fixed order: the record of a call is bit-identical from run to run.  Accuracy:
+ * a non-zero term has |y| < 746 and a relative error of at most (|y| + c0) 2^-53, c0 a handful of ulps for exp, log1p
+ * and the divide, i.e. < 8.4e-14; every sum is within 1e-12 * sum |term| of the exact one.
+ *
+ * From one record, with effective target prior pi, tau = log(pi / (1 - pi)) and the pass taken at c = b + tau:
+ *     F(a, b; pi) = pi/Np * L_t + (1-pi)/Nn * L_n   (nats);   dF/da = -pi/Np * G1_t + (1-pi)/Nn * G1_n,  dF/db likewise from
+ *     G0;  the 2 x 2 Hessian from (H2, H1, H0) with the same two weights;
+ *     Cllr = F(1, 0; 0.5) / ln 2 of the scores as they are, Cllr(a, b) = F(a, b; 0.5) / ln 2 after a map;
+ *     actDCF(pi, Cmiss, Cfa) = (Cmiss pi miss/Np + Cfa (1-pi) fa/Nn) / min(Cmiss pi, Cfa (1-pi)) at the Bayes threshold,
+ *     which the caller turns into the raw-score threshold theta = (log(Cfa (1-pi) / (Cmiss pi)) - b) / a  (a > 0) before
+ *     the pass (plda_amd/calibration.py:act_dcf).
+ * A pass that meets a non-finite score returns PLDA_E_INVAL with the count in plda_last_error, Np == 0 or Nn == 0 likewise
+ * (the record is written all the same): no score is silently left out.
+ *
+ * FIT: damped Newton on (a, b) from (0, 0) -- there p = sigmoid(tau) for every trial and the Hessian is the scores'
+ * weighted second-moment matrix, well conditioned whatever the scale of the scores (a = 1 saturates on raw LLRs of a few
+ * hundred).  Direction d = -H^-1 g, decrement lambda2 = g' H^-1 g; stop when lambda2 <= tol (tol == 0: the default 1e-18 --
+ * the host model's floor of lambda2 is 1e-26 .. 1e-33 on sets of 3e3 .. 1e6 trials, so the default stands) or after max_iter
+ * (<= 0: 100) iterations; backtracking t = 1, 1/2, ... (at most 30 halvings) until
+ * F(x + t d) <= F(x) - 1e-4 t lambda2 + 2^-44 |F(x)| -- the last term is the rounding of F itself, without which the final
+ * step, whose gain is below F's resolution, is refused at random.  The accepted point's record is the next iteration's.
+ * `passes` counts every pass of the call: one at (1, 0) for cllr_before, one at the start, one per trial point, and one
+ * more for cllr_after when prior != 0.5.  All scores equal, or a Hessian that is not positive definite in fp64, is
+ * PLDA_E_INVAL; prior outside (0, 1) or tol < 0 likewise.  separable = (min target > max non-target): the optimum is then at
+ * infinity and the caller is told (converged is usually 0) instead of being handed a huge `a` silently.
+ *
+ * APPLY: plda_affine_map_dev writes out[i, j] = (float)fma(a, (double)s[i, j], b) -- one rounding to fp64, one to fp32 --
+ * in place if dout == dscores and ld_out == ld; columns [Nt, ld_out) are not written (plda_score_matrix_snorm's contract).
+ * It enqueues on the handle's stream and does not synchronise.
+ *
+ * The _lists forms take HOST arrays of scores; out_record / out_fit are HOST structures and these calls synchronise the
+ * handle's stream, as plda_score_eer_dev does.  The operand forms (arguments as plda_score_eer_dev) never hold the matrix:
+ * the slabs are RE-SCORED once per pass -- a fit of a dozen passes scores the trials a dozen times -- and give the scores
+ * of plda_score_matrix_dev bit for bit. ---- */
+typedef struct plda_calib_record {
+  double sum[2][6];        /* [0 = non-target, 1 = target][L, G0, G1, H0, H1, H2] */
+  uint64_t np, nn, miss, fa, nonfinite;
+  float min_t, max_t, min_n, max_n;   /* +inf / -inf for a class without trials */
+} plda_calib_record;
+typedef struct plda_calib_fit {
+  double a, b;
+  double objective;        /* F(a, b; prior) / ln 2 */
+  double cllr_before, cllr_after;
+  double lambda2;          /* the Newton decrement at (a, b) */
+  int32_t iterations, passes, converged, separable;
+} plda_calib_fit;
+int plda_calib_pass_matrix_dev(plda_handle *h, const float *dscores, int64_t ld, int64_t M, int64_t Nt,
+                               const int64_t *denrol_spk, const int64_t *dtest_spk, double a, double c, double theta,
+                               plda_calib_record *out_record);
+int plda_calib_pass_lists(plda_handle *h, const float *pos, int64_t np, const float *neg, int64_t nn, double a, double c,
+                          double theta, plda_calib_record *out_record);
+int plda_score_calib_pass_dev(plda_handle *h, const double *dU, const int32_t *dn_enrol, int32_t n_uniform, int64_t M,
+                              const double *dV, int64_t Nt, const double *dzmean, const double *dzstd,
+                              const int64_t *denrol_spk, const int64_t *dtest_spk, double a, double c, double theta,
+                              plda_calib_record *out_record);
+int plda_calib_fit_matrix_dev(plda_handle *h, const float *dscores, int64_t ld, int64_t M, int64_t Nt,
+                              const int64_t *denrol_spk, const int64_t *dtest_spk, double prior, double tol,
+                              int32_t max_iter, plda_calib_fit *out_fit);
+int plda_calib_fit_lists(plda_handle *h, const float *pos, int64_t np, const float *neg, int64_t nn, double prior,
+                         double tol, int32_t max_iter, plda_calib_fit *out_fit);
+int plda_score_calib_fit_dev(plda_handle *h, const double *dU, const int32_t *dn_enrol, int32_t n_uniform, int64_t M,
+                             const double *dV, int64_t Nt, const double *dzmean, const double *dzstd,
+                             const int64_t *denrol_spk, const int64_t *dtest_spk, double prior, double tol,
+                             int32_t max_iter, plda_calib_fit *out_fit);
+int plda_affine_map_dev(plda_handle *h, const float *dscores, int64_t ld, int64_t M, int64_t Nt, double a, double b,
+                        float *dout, int64_t ld_out);
+
 /* ---- several GPUs of one node: one process per GPU, one handle per process.  The reference
  * has no counterpart (one process, one thread; its native object libplda.MPlda, pldamodule.cpp:280-295, is the only
  * thing callers bind, so the sharded path lives behind the same object).

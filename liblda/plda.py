@@ -29,23 +29,29 @@ class PLDA(object):
         return self._instance.score(target, xvec, yvec)
 
     # ---- batched extensions (what the reference's callers loop over in Python) ----
-    def score_matrix(self, enrol, test, znorm=True):
-        """float32 [M, Nt] matrix of score(id_i, enrol_i, test_j) in one launch."""
-        return self._instance.score_matrix(enrol, test, znorm)
+    def score_matrix(self, enrol, test, znorm=True, calibrate=False):
+        """float32 [M, Nt] matrix of score(id_i, enrol_i, test_j) in one launch (calibrate=True: mapped with the stored
+        calibration)."""
+        return self._instance.score_matrix(enrol, test, znorm, calibrate)
 
-    def score_trials(self, enrol, test, e_idx, t_idx, znorm=True):
-        return self._instance.score_trials(enrol, test, e_idx, t_idx, znorm)
+    def score_trials(self, enrol, test, e_idx, t_idx, znorm=True, calibrate=False):
+        return self._instance.score_trials(enrol, test, e_idx, t_idx, znorm, calibrate)
+
+    def calibrate(self, enrol, test, test_speaker, prior=0.5, znorm=True, cohort=None, top_k=None):
+        """Fit and store the linear calibration llr = a * score + b on the trials between two transform() results (enrol keys
+        are the speakers, test_speaker names the speaker of each test entry); returns a plda_amd.calibration.Calibration."""
+        return self._instance.calibrate(enrol, test, test_speaker, prior, znorm, cohort, top_k)
 
     def cohort_stats(self, side, cohort, top_k=None):
         """(mean, std) of the top_k largest cohort scores of every row of `side` (AS-norm statistics)."""
         return self._instance.cohort_stats(side, cohort, top_k)
 
-    def score_matrix_asnorm(self, enrol, test, cohort, top_k=None):
+    def score_matrix_asnorm(self, enrol, test, cohort, top_k=None, calibrate=False):
         """float32 [M, Nt] matrix, every trial normalised on both sides against the top_k closest cohort vectors."""
-        return self._instance.score_matrix_asnorm(enrol, test, cohort, top_k)
+        return self._instance.score_matrix_asnorm(enrol, test, cohort, top_k, calibrate)
 
-    def score_trials_asnorm(self, enrol, test, e_idx, t_idx, cohort, top_k=None):
-        return self._instance.score_trials_asnorm(enrol, test, e_idx, t_idx, cohort, top_k)
+    def score_trials_asnorm(self, enrol, test, e_idx, t_idx, cohort, top_k=None, calibrate=False):
+        return self._instance.score_trials_asnorm(enrol, test, e_idx, t_idx, cohort, top_k, calibrate)
 
     def transform_array(self, xbar, num_examples=1):
         return self._instance.transform_array(xbar, num_examples)

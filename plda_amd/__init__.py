@@ -6,7 +6,10 @@ Layout (only what the hot path needs):
   _native.py  ctypes binding of the C ABI (fails loudly if the .so or a GPU is missing)
   libplda.py  `MPlda`: counterpart of the reference's CPython type libplda.MPlda
   sharding.py row-sharded trials matrix across ranks (torch.distributed / RCCL)
+  calibration.py linear score calibration, Cllr, actual DCF (csrc/calib.hip)
 """
 from .libplda import MPlda  # noqa: F401
+from . import calibration  # noqa: F401
+from .calibration import Calibration  # noqa: F401
 
-__all__ = ["MPlda"]
+__all__ = ["MPlda", "Calibration", "calibration"]

@@ -111,6 +111,13 @@ SIGNATURES = {
     "plda_cohort_stats_dev": (C.c_int, [_vp, _vp, _vp, _i32, _i64, _vp, _i64, _i64, _vp, _vp]),
     "plda_score_matrix_snorm": (C.c_int, [_vp, _vp, _vp, _i32, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64]),
     "plda_score_matrix_snorm_dev": (C.c_int, [_vp, _vp, _vp, _i32, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64]),
+    "plda_calib_pass_matrix_dev": (C.c_int, [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _f64, _f64, _f64, _vp]),
+    "plda_calib_pass_lists": (C.c_int, [_vp, _vp, _i64, _vp, _i64, _f64, _f64, _f64, _vp]),
+    "plda_score_calib_pass_dev": (C.c_int, [_vp, _vp, _vp, _i32, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _f64, _f64, _f64, _vp]),
+    "plda_calib_fit_matrix_dev": (C.c_int, [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _f64, _f64, _i32, _vp]),
+    "plda_calib_fit_lists": (C.c_int, [_vp, _vp, _i64, _vp, _i64, _f64, _f64, _i32, _vp]),
+    "plda_score_calib_fit_dev": (C.c_int, [_vp, _vp, _vp, _i32, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _f64, _f64, _i32, _vp]),
+    "plda_affine_map_dev": (C.c_int, [_vp, _vp, _i64, _i64, _i64, _f64, _f64, _vp, _i64]),
 }
 
 # plda_collectives / plda_host_collectives (include/plda_hip.h): callback tables of the multi-GPU entry points

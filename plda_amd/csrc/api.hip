@@ -73,6 +73,23 @@ int det_matrix_device(plda_handle *h, const float *dscores, int64_t ld, int64_t 
                       int npoints, double *far, double *frr, double *thresholds);
 int det_lists_device(plda_handle *h, const float *dpos, int64_t np, const float *dneg, int64_t nn, int npoints, double *far, double *frr,
                      double *thresholds);
+// calib.hip
+int calib_pass_matrix_device(plda_handle *h, const float *dscores, int64_t ld, int64_t M, int64_t Nt, const int64_t *despk,
+                             const int64_t *dtspk, double a, double c, double theta, plda_calib_record *out);
+int calib_fit_matrix_device(plda_handle *h, const float *dscores, int64_t ld, int64_t M, int64_t Nt, const int64_t *despk,
+                            const int64_t *dtspk, double prior, double tol, int max_iter, plda_calib_fit *out);
+int calib_pass_lists_device(plda_handle *h, const float *dpos, int64_t np, const float *dneg, int64_t nn, double a, double c,
+                            double theta, plda_calib_record *out);
+int calib_fit_lists_device(plda_handle *h, const float *dpos, int64_t np, const float *dneg, int64_t nn, double prior, double tol,
+                           int max_iter, plda_calib_fit *out);
+int score_calib_pass_device(plda_handle *h, const double *dU, const int32_t *dn, int n_uniform, int64_t M, const double *dV, int64_t Nt,
+                            const double *dzmean, const double *dzstd, const int64_t *despk, const int64_t *dtspk, double a, double c,
+                            double theta, plda_calib_record *out);
+int score_calib_fit_device(plda_handle *h, const double *dU, const int32_t *dn, int n_uniform, int64_t M, const double *dV, int64_t Nt,
+                           const double *dzmean, const double *dzstd, const int64_t *despk, const int64_t *dtspk, double prior,
+                           double tol, int max_iter, plda_calib_fit *out);
+int affine_map_device(plda_handle *h, const float *dscores, int64_t ld, int64_t M, int64_t Nt, double a, double b, float *dout,
+                      int64_t ld_out);
 int score_eer_device(plda_handle *h, const double *dU, const int32_t *dn, int n_uniform, int64_t M, const double *dV, int64_t Nt,
                      const double *dzmean, const double *dzstd, const int64_t *despk, const int64_t *dtspk, double *out);
 // comm.hip
@@ -1718,6 +1735,89 @@ int plda_eer_lists(plda_handle *h, const float *pos, int64_t np, const float *ne
     PLDA_TRY(upload(h, dP, pos, (size_t)np * 4));
     PLDA_TRY(upload(h, dN, neg, (size_t)nn * 4));
     return eer_lists_device(h, dP.as<float>(), np, dN.as<float>(), nn, out);
+  });
+}
+
+// ---------------------------------------------------------------- score calibration (calib.hip)
+int plda_calib_pass_matrix_dev(plda_handle *h, const float *dscores, int64_t ld, int64_t M, int64_t Nt, const int64_t *denrol_spk,
+                               const int64_t *dtest_spk, double a, double c, double theta, plda_calib_record *out_record) {
+  return guarded(h, "plda_calib_pass_matrix_dev", [&]() -> int {
+    if (!h) return PLDA_E_INVAL;
+    PLDA_LOCK(h);
+    PLDA_TRY(set_device(h));
+    return calib_pass_matrix_device(h, dscores, ld, M, Nt, denrol_spk, dtest_spk, a, c, theta, out_record);
+  });
+}
+
+int plda_calib_fit_matrix_dev(plda_handle *h, const float *dscores, int64_t ld, int64_t M, int64_t Nt, const int64_t *denrol_spk,
+                              const int64_t *dtest_spk, double prior, double tol, int32_t max_iter, plda_calib_fit *out_fit) {
+  return guarded(h, "plda_calib_fit_matrix_dev", [&]() -> int {
+    if (!h) return PLDA_E_INVAL;
+    PLDA_LOCK(h);
+    PLDA_TRY(set_device(h));
+    return calib_fit_matrix_device(h, dscores, ld, M, Nt, denrol_spk, dtest_spk, prior, tol, max_iter, out_fit);
+  });
+}
+
+int plda_calib_pass_lists(plda_handle *h, const float *pos, int64_t np, const float *neg, int64_t nn, double a, double c,
+                          double theta, plda_calib_record *out_record) {
+  return guarded(h, "plda_calib_pass_lists", [&]() -> int {
+    if (!h) return PLDA_E_INVAL;
+    PLDA_LOCK(h);
+    if (!pos || !neg || !out_record || np <= 0 || nn <= 0)
+      return fail(h, PLDA_E_INVAL, "calib_pass: need at least one target and one non-target score");
+    PLDA_TRY(set_device(h));
+    Tmp dP, dN;
+    PLDA_TRY(upload(h, dP, pos, (size_t)np * 4));
+    PLDA_TRY(upload(h, dN, neg, (size_t)nn * 4));
+    return calib_pass_lists_device(h, dP.as<float>(), np, dN.as<float>(), nn, a, c, theta, out_record);
+  });
+}
+
+int plda_calib_fit_lists(plda_handle *h, const float *pos, int64_t np, const float *neg, int64_t nn, double prior, double tol,
+                         int32_t max_iter, plda_calib_fit *out_fit) {
+  return guarded(h, "plda_calib_fit_lists", [&]() -> int {
+    if (!h) return PLDA_E_INVAL;
+    PLDA_LOCK(h);
+    if (!pos || !neg || !out_fit || np <= 0 || nn <= 0)
+      return fail(h, PLDA_E_INVAL, "calib_fit: need at least one target and one non-target score");
+    PLDA_TRY(set_device(h));
+    Tmp dP, dN;
+    PLDA_TRY(upload(h, dP, pos, (size_t)np * 4));
+    PLDA_TRY(upload(h, dN, neg, (size_t)nn * 4));
+    return calib_fit_lists_device(h, dP.as<float>(), np, dN.as<float>(), nn, prior, tol, max_iter, out_fit);
+  });
+}
+
+int plda_score_calib_pass_dev(plda_handle *h, const double *dU, const int32_t *dn_enrol, int32_t n_uniform, int64_t M,
+                              const double *dV, int64_t Nt, const double *dzmean, const double *dzstd, const int64_t *denrol_spk,
+                              const int64_t *dtest_spk, double a, double c, double theta, plda_calib_record *out_record) {
+  return guarded(h, "plda_score_calib_pass_dev", [&]() -> int {
+    if (!h) return PLDA_E_INVAL;
+    PLDA_LOCK(h);
+    PLDA_TRY(set_device(h));
+    return score_calib_pass_device(h, dU, dn_enrol, n_uniform, M, dV, Nt, dzmean, dzstd, denrol_spk, dtest_spk, a, c, theta, out_record);
+  });
+}
+
+int plda_score_calib_fit_dev(plda_handle *h, const double *dU, const int32_t *dn_enrol, int32_t n_uniform, int64_t M,
+                             const double *dV, int64_t Nt, const double *dzmean, const double *dzstd, const int64_t *denrol_spk,
+                             const int64_t *dtest_spk, double prior, double tol, int32_t max_iter, plda_calib_fit *out_fit) {
+  return guarded(h, "plda_score_calib_fit_dev", [&]() -> int {
+    if (!h) return PLDA_E_INVAL;
+    PLDA_LOCK(h);
+    PLDA_TRY(set_device(h));
+    return score_calib_fit_device(h, dU, dn_enrol, n_uniform, M, dV, Nt, dzmean, dzstd, denrol_spk, dtest_spk, prior, tol, max_iter, out_fit);
+  });
+}
+
+int plda_affine_map_dev(plda_handle *h, const float *dscores, int64_t ld, int64_t M, int64_t Nt, double a, double b, float *dout,
+                        int64_t ld_out) {
+  return guarded(h, "plda_affine_map_dev", [&]() -> int {
+    if (!h) return PLDA_E_INVAL;
+    PLDA_LOCK(h);
+    PLDA_TRY(set_device(h));
+    return affine_map_device(h, dscores, ld, M, Nt, a, b, dout, ld_out);
   });
 }
 

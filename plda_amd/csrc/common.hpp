@@ -258,6 +258,7 @@ struct plda_handle {
   plda::DevBuf eer_list[2];      // eer.hip, single-pass form: the impostor / target scores inside the pilot's key window
   int eer_variant = 0;           // PLDA_EER_VARIANT=1: always the three passes; 2: the single-pass form at every size (tests)
   int64_t eer_slab_rows = 0;     // PLDA_EER_SLAB_ROWS: rows per slab of plda_score_eer_dev (0: <= 4 GiB of scores)
+  plda::DevBuf calib_part;       // calib.hip: one partial plda_calib_record per workgroup of a calibration pass + the reduced one
   plda::DevBuf sn_slab;          // plda_cohort_stats_dev (snorm.hip): the row slab of cohort scores in flight
   int64_t sn_slab_rows = 0;      // PLDA_SNORM_SLAB_ROWS: rows per slab of plda_cohort_stats_dev / plda_score_matrix_snorm_dev (0: by size)
   int eer_last_passes = 0;       // full passes over the matrix the last plda_eer_matrix_dev made (1 or 3)
@@ -436,6 +437,44 @@ int cohort_stats_device(plda_handle *h, const double *dX, const int32_t *dn, int
 int score_matrix_snorm_device(plda_handle *h, const double *dU, const int32_t *dn, int n_uniform, int64_t M, const double *dV,
                               int64_t Nt, const double *demean, const double *destd, const double *dtmean, const double *dtstd,
                               float *dout, int64_t ld, const CountSet *cs = nullptr, bool reuse_packed_B = false);
+
+// ---- eer.hip: what a reduction over labelled trials consumes (the EER passes; calib.hip's calibration pass) ----
+struct EerSource {
+  const float *scores; int64_t ld, M, Nt; const int64_t *espk, *tspk;   // matrix + labels, or
+  const float *pos; int64_t np; const float *neg; int64_t nn;            // two flat lists
+  // row-sharded matrix: after every local pass the caller's reduction makes the counts global
+  // (hist: sum over ranks; below: max; above: min).  nullptr = single process.
+  int (*reduce)(void *ctx, unsigned long long *hist, unsigned *below, unsigned *above) = nullptr;
+  void *ctx = nullptr;
+  int64_t row_step = 1;                        // matrix form: every row_step-th row only (the pilot's sample)
+  // windowed lists (the single-pass form): the lists hold the scores of a key window only; the counts below it and
+  // the class totals come from the full pass
+  bool windowed = false;
+  unsigned long long base_p = 0, base_n = 0, tot_p = 0, tot_n = 0;
+  // a matrix that exists one row slab at a time (plda_score_eer_dev: the scores are produced, consumed and dropped): `scores`
+  // is nullptr, M / Nt / espk / tspk describe the whole matrix
+  const struct EerSlabs *slabs = nullptr;
+};
+// produce: enqueue the scores of rows [r0, r0 + rows) (rows <= slab_rows) on the handle's stream, say where they are;
+// sample: the same for every step-th row of the matrix (<= slab_rows of them) together with THOSE rows' speaker ids
+struct EerSlabs {
+  int64_t slab_rows;
+  int (*produce)(void *ctx, int64_t r0, int64_t rows, const float **scores, int64_t *ld);
+  int (*sample)(void *ctx, int64_t step, const float **scores, int64_t *ld, const int64_t **espk, int64_t *rows);
+  void *ctx;
+};
+// the operand forms (plda_score_eer_dev, plda_score_calib_*_dev): the scores of a row slab are produced by the trials GEMM
+struct ScoreEerCtx {
+  plda_handle *h;
+  const double *dU; const int32_t *dn; int n_uniform; int64_t M; const double *dV; int64_t Nt;
+  const double *dzm, *dzs; const int64_t *despk;
+  CountSet cs; bool has_cs; bool packedB;
+  float *slab; int64_t slab_rows;
+};
+int score_eer_produce(void *ctx, int64_t r0, int64_t rows, const float **scores, int64_t *ld);
+int score_eer_sample(void *ctx, int64_t step, const float **scores, int64_t *ld, const int64_t **espk, int64_t *rows);
+int score_eer_slabs_setup(plda_handle *h, const double *dU, const int32_t *dn, int n_uniform, int64_t M, const double *dV, int64_t Nt,
+                          const double *dzmean, const double *dzstd, const int64_t *despk, ScoreEerCtx *c, EerSlabs *sl);
 
 #ifdef __HIPCC__
 // fp64 wave-wide sum through DPP: quad butterflies, then half-row and row mirrors (every

@@ -260,30 +260,7 @@ __global__ __launch_bounds__(256) void eer_window_strip_kernel(const float *__re
   }
 }
 
-struct EerSource {
-  const float *scores; int64_t ld, M, Nt; const int64_t *espk, *tspk;   // matrix + labels, or
-  const float *pos; int64_t np; const float *neg; int64_t nn;            // two flat lists
-  // row-sharded matrix: after every local pass the caller's reduction makes the counts global
-  // (hist: sum over ranks; below: max; above: min).  nullptr = single process.
-  int (*reduce)(void *ctx, unsigned long long *hist, unsigned *below, unsigned *above) = nullptr;
-  void *ctx = nullptr;
-  int64_t row_step = 1;                        // matrix form: every row_step-th row only (the pilot's sample)
-  // windowed lists (the single-pass form): the lists hold the scores of a key window only; the counts below it and
-  // the class totals come from the full pass
-  bool windowed = false;
-  unsigned long long base_p = 0, base_n = 0, tot_p = 0, tot_n = 0;
-  // a matrix that exists one row slab at a time (plda_score_eer_dev: the scores are produced, consumed and dropped): `scores`
-  // is nullptr, M / Nt / espk / tspk describe the whole matrix
-  const struct EerSlabs *slabs = nullptr;
-};
-// produce: enqueue the scores of rows [r0, r0 + rows) (rows <= slab_rows) on the handle's stream, say where they are;
-// sample: the same for every step-th row of the matrix (<= slab_rows of them) together with THOSE rows' speaker ids
-struct EerSlabs {
-  int64_t slab_rows;
-  int (*produce)(void *ctx, int64_t r0, int64_t rows, const float **scores, int64_t *ld);
-  int (*sample)(void *ctx, int64_t step, const float **scores, int64_t *ld, const int64_t **espk, int64_t *rows);
-  void *ctx;
-};
+// (EerSource / EerSlabs, the data a reduction over labelled trials consumes: common.hpp, shared with calib.hip)
 
 // One histogram pass over the local data -> hh (host).  No reduction here: see eer_device.
 static int eer_pass(plda_handle *h, const EerSource &src, int shift, int nbits, unsigned prefix, int has_prefix,
@@ -601,14 +578,8 @@ __global__ void eer_gather_meta_kernel(const int32_t *__restrict__ n, const doub
   ospk[r] = spk[r * step];
 }
 
-struct ScoreEerCtx {
-  plda_handle *h;
-  const double *dU; const int32_t *dn; int n_uniform; int64_t M; const double *dV; int64_t Nt;
-  const double *dzm, *dzs; const int64_t *despk;
-  CountSet cs; bool has_cs; bool packedB;
-  float *slab; int64_t slab_rows;
-};
-static int score_eer_produce(void *vc, int64_t r0, int64_t rows, const float **scores, int64_t *ld) {
+// (ScoreEerCtx: common.hpp)
+int score_eer_produce(void *vc, int64_t r0, int64_t rows, const float **scores, int64_t *ld) {
   auto *c = static_cast<ScoreEerCtx *>(vc);
   const int D = c->h->Dout;
   PLDA_TRY(score_matrix_device(c->h, c->dU + r0 * D, c->dn ? c->dn + r0 : nullptr, c->n_uniform, rows, c->dV, c->Nt,
@@ -618,7 +589,7 @@ static int score_eer_produce(void *vc, int64_t r0, int64_t rows, const float **s
   *scores = c->slab; *ld = c->Nt;
   return PLDA_OK;
 }
-static int score_eer_sample(void *vc, int64_t step, const float **scores, int64_t *ld, const int64_t **espk, int64_t *rows) {
+int score_eer_sample(void *vc, int64_t step, const float **scores, int64_t *ld, const int64_t **espk, int64_t *rows) {
   auto *c = static_cast<ScoreEerCtx *>(vc);
   plda_handle *h = c->h;
   const int D = h->Dout;
@@ -639,25 +610,35 @@ static int score_eer_sample(void *vc, int64_t step, const float **scores, int64_
   return PLDA_OK;
 }
 
+// The slab set-up of the operand forms (plda_score_eer_dev, plda_score_calib_*_dev): the distinct enrol counts found once, the
+// slab height, the slab buffer.  *c must outlive *sl.
+int score_eer_slabs_setup(plda_handle *h, const double *dU, const int32_t *dn, int n_uniform, int64_t M, const double *dV, int64_t Nt,
+                          const double *dzmean, const double *dzstd, const int64_t *despk, ScoreEerCtx *c, EerSlabs *sl) {
+  *c = ScoreEerCtx{h, dU, dn, n_uniform, M, dV, Nt, (dzmean && dzstd) ? dzmean : nullptr, (dzmean && dzstd) ? dzstd : nullptr, despk};
+  c->has_cs = false; c->packedB = false;
+  if (dn) { PLDA_TRY(score_count_set_device(h, dn, M, &c->cs)); c->has_cs = true; }
+  // slabs of <= 4 GiB of scores, whole 256-row tiles, at least one tile row
+  int64_t rows = std::max<int64_t>(256, (((int64_t)4 << 30) / 4 / Nt) / 256 * 256);
+  if (h->eer_slab_rows > 0) rows = round_up(h->eer_slab_rows, 256);      // PLDA_EER_SLAB_ROWS: small slabs for the tests
+  rows = std::min(rows, round_up(M, 256));
+  c->slab_rows = rows;
+  PLDA_HIP(h, h->eer_slab.reserve((size_t)rows * Nt * 4));
+  c->slab = h->eer_slab.as<float>();
+  *sl = EerSlabs{rows, score_eer_produce, score_eer_sample, c};
+  h->prep_valid = false;           // (the slabs pack the test side themselves)
+  return PLDA_OK;
+}
+
 int score_eer_device(plda_handle *h, const double *dU, const int32_t *dn, int n_uniform, int64_t M, const double *dV, int64_t Nt,
                      const double *dzmean, const double *dzstd, const int64_t *despk, const int64_t *dtspk, double *out) {
   if (!h->fitted) return fail(h, PLDA_E_NOT_FITTED, "score_eer: model not fitted");
   if (!dU || !dV || !despk || !dtspk || !out || M <= 0 || Nt <= 0) return fail(h, PLDA_E_INVAL, "score_eer: bad argument");
   if (!dn && n_uniform <= 0) return fail(h, PLDA_E_INVAL, "score_eer: n_uniform must be > 0 when n_enrol is NULL");
-  ScoreEerCtx c{h, dU, dn, n_uniform, M, dV, Nt, (dzmean && dzstd) ? dzmean : nullptr, (dzmean && dzstd) ? dzstd : nullptr, despk};
-  c.has_cs = false; c.packedB = false;
-  if (dn) { PLDA_TRY(score_count_set_device(h, dn, M, &c.cs)); c.has_cs = true; }
-  // slabs of <= 4 GiB of scores, whole 256-row tiles, at least one tile row
-  int64_t rows = std::max<int64_t>(256, (((int64_t)4 << 30) / 4 / Nt) / 256 * 256);
-  if (h->eer_slab_rows > 0) rows = round_up(h->eer_slab_rows, 256);      // PLDA_EER_SLAB_ROWS: small slabs for the tests
-  rows = std::min(rows, round_up(M, 256));
-  c.slab_rows = rows;
-  PLDA_HIP(h, h->eer_slab.reserve((size_t)rows * Nt * 4));
-  c.slab = h->eer_slab.as<float>();
-  const EerSlabs sl{rows, score_eer_produce, score_eer_sample, &c};
+  ScoreEerCtx c;
+  EerSlabs sl;
+  PLDA_TRY(score_eer_slabs_setup(h, dU, dn, n_uniform, M, dV, Nt, dzmean, dzstd, despk, &c, &sl));
   EerSource src{nullptr, Nt, M, Nt, despk, dtspk, nullptr, 0, nullptr, 0};
   src.slabs = &sl;
-  h->prep_valid = false;           // (the slabs pack the test side themselves)
   h->eer_last_passes = 3;
   if (h->eer_variant != 1 && (h->eer_variant == 2 || (double)M * (double)Nt >= 2.5e8) && M >= 4 * EER_PILOT_STEP) {
     bool done = false;

@@ -139,6 +139,7 @@ class MPlda(object):
         # std::unordered_map<long,double> *meanz, *stdvz (pldamodule.cpp:33)
         self._meanz = {}
         self._stdvz = {}
+        self._calibration = None      # plda_amd.calibration.Calibration of the last calibrate() / load()
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -220,9 +221,13 @@ class MPlda(object):
         """Model + z-norm statistics to .npz (the reference has no persistence)."""
         m = self.get_model()
         ids = np.array(sorted(self._meanz), dtype=np.int64)
+        extra = {}
+        if self._calibration is not None:      # three more keys, only when a calibration is stored
+            c = self._calibration
+            extra = {"calib_a": np.float64(c.a), "calib_b": np.float64(c.b), "calib_prior": np.float64(c.prior)}
         np.savez(_npz_path(path), mean=m["mean"], transform=m["transform"], psi=m["psi"], zn_ids=ids,
                  zn_mean=np.array([self._meanz[i] for i in ids], dtype=np.float64),
-                 zn_std=np.array([self._stdvz[i] for i in ids], dtype=np.float64))
+                 zn_std=np.array([self._stdvz[i] for i in ids], dtype=np.float64), **extra)
 
     def load(self, path):
         z = np.load(_npz_path(path, for_load=True))
@@ -230,6 +235,10 @@ class MPlda(object):
         self._meanz = {int(i): float(v) for i, v in zip(z["zn_ids"], z["zn_mean"])}
         self._stdvz = {int(i): float(v) for i, v in zip(z["zn_ids"], z["zn_std"])}
         self._zn_tag = None         # the sorted copy of _zn_arrays belongs to the dicts just replaced (id() of a new dict may repeat)
+        self._calibration = None    # replaced like the z-norm dictionaries: a file without the keys clears it
+        if "calib_a" in z.files:
+            from .calibration import Calibration
+            self._calibration = Calibration(float(z["calib_a"]), float(z["calib_b"]), float(z["calib_prior"]))
 
     def save_kaldi(self, path, binary=True):
         """Write the model as a Kaldi `Plda` file (plda_amd/kaldi_io.py: format restated, not pinned)."""
@@ -458,9 +467,11 @@ class MPlda(object):
         hit = self._zn_keys[pos] == ids
         return np.where(hit, self._zn_mean[pos], 0.0), np.where(hit, self._zn_std[pos], 0.0)
 
-    def score_matrix(self, enrol, test, znorm=True):
+    def score_matrix(self, enrol, test, znorm=True, calibrate=False):
         """Dense trials matrix: float32 [M, Nt] of score(id_i, enrol_i, test_j) -- the nested
-        loop of scoring/scorePLDA.py:302-318 / tests/pldatest.py:29-33 as one GEMM."""
+        loop of scoring/scorePLDA.py:302-318 / tests/pldatest.py:29-33 as one GEMM.  calibrate=True: mapped with the
+        stored calibration (`calibrate`), (float)fma(a, (double)score, b)."""
+        cal = self._stored_calibration(calibrate)
         ids, counts, U = self._unpack(enrol)
         _, _, V = self._unpack(test)
         m, nt = U.shape[0], V.shape[0]
@@ -469,12 +480,20 @@ class MPlda(object):
             return out
         zm, zs = self._zn_arrays(ids, znorm)
         uniform = int(counts[0]) if np.all(counts == counts[0]) else 0
+        if cal is not None:
+            S = self._trials_matrix_on_device(counts, U, V, zn=(zm, zs))
+            self._affine_map_on_device(S, cal)
+            return S.cpu().numpy()
         self._ck(self._lib.plda_score_matrix(self._h, _ptr(U), None if uniform else _ptr(counts), uniform, m,
                                              _ptr(V), nt, _ptr(zm), _ptr(zs), _ptr(out), nt))
         return out
 
-    def score_trials(self, enrol, test, e_idx, t_idx, znorm=True):
-        """Sparse trial list in fp64: out[p] = score(enrol[e_idx[p]], test[t_idx[p]])."""
+    def score_trials(self, enrol, test, e_idx, t_idx, znorm=True, calibrate=False):
+        """Sparse trial list in fp64: out[p] = score(enrol[e_idx[p]], test[t_idx[p]]).  calibrate=True: a * score + b of the
+        stored calibration, in fp64 on the host."""
+        cal = self._stored_calibration(calibrate)
+        if cal is not None:
+            return cal(self.score_trials(enrol, test, e_idx, t_idx, znorm))
         ids, counts, U = self._unpack(enrol)
         _, _, V = self._unpack(test)
         e = np.ascontiguousarray(e_idx, np.int64).reshape(-1)
@@ -512,10 +531,12 @@ class MPlda(object):
         _, counts, X = self._unpack(side)
         return self._cohort_stats(counts, X, self._cohort_rows(cohort), top_k)
 
-    def score_matrix_asnorm(self, enrol, test, cohort, top_k=None):
+    def score_matrix_asnorm(self, enrol, test, cohort, top_k=None, calibrate=False):
         """float32 [M, Nt]: every trial normalised on both sides, 0.5 ((s - mean_e) / std_e + (s - mean_t) / std_t), the
         enrol model and the test vector each against the top_k closest vectors of `cohort` (a side whose std is 0 contributes
-        the raw score).  The test side is scored with n = 1 whatever counts `test` stores, as in score_matrix."""
+        the raw score).  The test side is scored with n = 1 whatever counts `test` stores, as in score_matrix.
+        calibrate=True: mapped with the stored calibration as in score_matrix."""
+        cal = self._stored_calibration(calibrate)
         _, counts, U = self._unpack(enrol)
         _, _, V = self._unpack(test)
         Cv = self._cohort_rows(cohort)
@@ -525,13 +546,21 @@ class MPlda(object):
             return out
         em, es = self._cohort_stats(counts, U, Cv, top_k)
         tm, ts = self._cohort_stats(np.ones(nt, np.int32), V, Cv, top_k)
+        if cal is not None:
+            S = self._trials_matrix_on_device(counts, U, V, sn=(em, es, tm, ts))
+            self._affine_map_on_device(S, cal)
+            return S.cpu().numpy()
         uniform = int(counts[0]) if np.all(counts == counts[0]) else 0
         self._ck(self._lib.plda_score_matrix_snorm(self._h, _ptr(U), None if uniform else _ptr(counts), uniform, m, _ptr(V), nt,
                                                    _ptr(em), _ptr(es), _ptr(tm), _ptr(ts), _ptr(out), nt))
         return out
 
-    def score_trials_asnorm(self, enrol, test, e_idx, t_idx, cohort, top_k=None):
-        """The fp64 trial-list scores of score_trials(..., znorm=False) with the same two-sided map, applied on the host."""
+    def score_trials_asnorm(self, enrol, test, e_idx, t_idx, cohort, top_k=None, calibrate=False):
+        """The fp64 trial-list scores of score_trials(..., znorm=False) with the same two-sided map, applied on the host.
+        calibrate=True: then a * score + b of the stored calibration."""
+        cal = self._stored_calibration(calibrate)
+        if cal is not None:
+            return cal(self.score_trials_asnorm(enrol, test, e_idx, t_idx, cohort, top_k))
         _, counts, U = self._unpack(enrol)
         _, _, V = self._unpack(test)
         Cv = self._cohort_rows(cohort)
@@ -547,6 +576,90 @@ class MPlda(object):
             ok = s != 0.0
             return np.where(ok, (raw - m) / np.where(ok, s, 1.0), raw)
         return 0.5 * (side(em[e], es[e]) + side(tm[t], ts[t]))
+
+    # ------------------------------------------------- score calibration (csrc/calib.hip, plda_amd/calibration.py)
+    def _stored_calibration(self, calibrate):
+        if not calibrate:
+            return None
+        if self._calibration is None:
+            raise ValueError("calibrate=True needs a stored calibration: call calibrate() (or load a file that holds one) first")
+        return self._calibration
+
+    def _to_device(self, a):
+        import torch
+        return torch.from_numpy(np.ascontiguousarray(a)).to(torch.device("cuda", self.device))
+
+    def _trials_matrix_on_device(self, counts, U, V, zn=(None, None), sn=None):
+        """The fp32 [M, Nt] matrix of score_matrix (zn: z-norm statistics or Nones) or score_matrix_asnorm (sn: the four
+        cohort statistics) as a device tensor."""
+        import torch
+        m, nt = U.shape[0], V.shape[0]
+        uniform = int(counts[0]) if np.all(counts == counts[0]) else 0
+        dU, dV = self._to_device(U), self._to_device(V)
+        dn = None if uniform else self._to_device(counts)
+        S = torch.empty((m, nt), dtype=torch.float32, device=dU.device)
+        ptr = lambda t: t.data_ptr() if t is not None else None      # noqa: E731
+        if sn is not None:
+            st = [self._to_device(x) for x in sn]
+            self.score_matrix_snorm_dev(dU.data_ptr(), ptr(dn), uniform, m, dV.data_ptr(), nt, S.data_ptr(), nt,
+                                        st[0].data_ptr(), st[1].data_ptr(), st[2].data_ptr(), st[3].data_ptr())
+        else:
+            st = [self._to_device(x) if x is not None else None for x in zn]
+            self.score_matrix_dev(dU.data_ptr(), ptr(dn), uniform, m, dV.data_ptr(), nt, S.data_ptr(), nt, ptr(st[0]), ptr(st[1]))
+        self.synchronize()           # (the operands may be freed when this returns)
+        return S
+
+    def _affine_map_on_device(self, S, cal):
+        from . import calibration as CB
+        CB.apply_dev(self, S.data_ptr(), S.shape[1], S.shape[0], S.shape[1], cal)
+        self.synchronize()
+
+    def calibrate(self, enrol, test, test_speaker, prior=0.5, znorm=True, cohort=None, top_k=None):
+        """Fit the linear calibration llr = a * score + b (prior-weighted logistic regression, include/plda_hip.h) on the
+        trials between two transform() results and store it.  The enrol keys are the model speakers; `test_speaker` gives
+        the speaker of every test entry, as a mapping {test key: speaker} or a sequence in the order of `test`.  The
+        scores are normalised first exactly as score_matrix (znorm) or, with a cohort, score_matrix_asnorm would.  Without a
+        cohort the matrix is never held (the trials are re-scored slab by slab once per pass); with one it is.  Returns the
+        `plda_amd.calibration.Calibration`; a separable or unconverged fit raises a RuntimeWarning."""
+        from . import calibration as CB
+        ids, counts, U = self._unpack(enrol)
+        tids, _, V = self._unpack(test)
+        m, nt = U.shape[0], V.shape[0]
+        if ids is None:
+            raise ValueError("calibrate: the enrol side needs its speaker ids (a transform() result or (counts, vecs, ids))")
+        if hasattr(test_speaker, "keys"):
+            if tids is None:
+                raise ValueError("calibrate: a test_speaker mapping needs test keys")
+            tspk = np.array([int(test_speaker[int(k)]) for k in tids], np.int64)
+        else:
+            tspk = np.ascontiguousarray(test_speaker, np.int64).reshape(-1)
+        if tspk.shape[0] != nt:
+            raise ValueError("calibrate: test_speaker must name the speaker of each of the %d test entries" % nt)
+        if m == 0 or nt == 0:
+            raise ValueError("calibrate: no trials")
+        despk, dtspk = self._to_device(np.ascontiguousarray(ids, np.int64)), self._to_device(tspk)
+        if cohort is None:
+            zm, zs = self._zn_arrays(ids, znorm)
+            uniform = int(counts[0]) if np.all(counts == counts[0]) else 0
+            dU, dV = self._to_device(U), self._to_device(V)
+            dn = None if uniform else self._to_device(counts)
+            dzm, dzs = (self._to_device(zm), self._to_device(zs)) if zm is not None else (None, None)
+            ptr = lambda t: t.data_ptr() if t is not None else None      # noqa: E731
+            cal = CB.fit_from_operands_dev(self, dU.data_ptr(), ptr(dn), uniform, m, dV.data_ptr(), nt, despk.data_ptr(),
+                                           dtspk.data_ptr(), ptr(dzm), ptr(dzs), prior=prior)
+        else:
+            Cv = self._cohort_rows(cohort)
+            em, es = self._cohort_stats(counts, U, Cv, top_k)
+            tm, ts = self._cohort_stats(np.ones(nt, np.int32), V, Cv, top_k)
+            S = self._trials_matrix_on_device(counts, U, V, sn=(em, es, tm, ts))
+            cal = CB.fit_from_matrix_dev(self, S.data_ptr(), nt, m, nt, despk.data_ptr(), dtspk.data_ptr(), prior=prior)
+        self._calibration = cal
+        return cal
+
+    @property
+    def calibration(self):
+        """The stored `plda_amd.calibration.Calibration`, or None."""
+        return self._calibration
 
     # ------------------------------------------------- device-resident path
     def set_stream(self, hip_stream):
