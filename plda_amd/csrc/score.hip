@@ -1328,7 +1328,8 @@ __device__ __host__ inline void bt4_patch(int x, I k, int pM, int pN, int colwal
 // launch before left them so (score_bt4.inc: bt4_leave).
 __global__ __launch_bounds__(64) void bt4_table_kernel(int2 *__restrict__ tab, int btM, int btN, int pM, int pN, int colwalk, const Bt4Queues qs) {
   const int x = blockIdx.x, lane = threadIdx.x;
-  int off = qs.qbase[x];
+  int off = BT4_QHDR + qs.qbase[x];
+  if (lane == 0) tab[x] = make_int2(off, qs.qlen[x]);   // the queue table in front of the entries (score_bt4.inc: BT4_QHDR)
   const int64_t nq = bt4_queue_patches(x, pM, pN, colwalk);
   for (int64_t k = 0; k < nq; ++k) {
     int pm, pn;
@@ -1380,7 +1381,7 @@ static int bt4_schedule(plda_handle *h, int btM, int btN, int KQ, Bt4Table **out
     qs.qbase[x] = t.qbase[x]; qs.qlen[x] = t.qlen[x];
   }
   t.btM = t.btN = -1;
-  PLDA_HIP(h, t.tab.reserve(std::max<size_t>((size_t)total, 1) * sizeof(int2)));
+  PLDA_HIP(h, t.tab.reserve((size_t)(total + BT4_QHDR + 1) * sizeof(int2))   /* + 1: a dry queue's fetch reads its first entry and drops it -- of an EMPTY last queue that is one past the end */);
   bt4_table_kernel<<<8, 64, 0, h->stream>>>(t.tab.as<int2>(), btM, btN, pM, pN, colwalk, qs);
   PLDA_LAUNCH_CHECK(h);
   t.btM = btM; t.btN = btN; t.colwalk = colwalk; t.used = ++h->bt4_clock;
@@ -1835,8 +1836,6 @@ static int launch_gemm(plda_handle *h, const TrialOperands &op, int64_t M, int64
       const int rag_m = (M & 255) != 0, rag_n = (Nt & 255) != 0;
       const int fslots = (rag_m || rag_n) ? btM + btN : 0;
       PLDA_HIP(h, h->bt4_fringe.reserve(std::max<size_t>((size_t)fslots * 65536 * 4, 256)));
-      Bt4Queues qs;
-      for (int x = 0; x < 8; ++x) { qs.qbase[x] = tb->qbase[x]; qs.qlen[x] = tb->qlen[x]; }
       if (!h->bt4_attr_set) {
         const void *fns[] = {reinterpret_cast<const void *>(&trials_gemm_bt4_kernel<3, 0>), reinterpret_cast<const void *>(&trials_gemm_bt4_kernel<4, 0>),
 #if PLDA_DIAG
@@ -1852,7 +1851,7 @@ static int launch_gemm(plda_handle *h, const TrialOperands &op, int64_t M, int64
 #define BT4L(FS_, MODE_, DBG_)                                                                            \
   trials_gemm_bt4_kernel<FS_, MODE_><<<256, 256, BT4_LDS, h->stream>>>(                                   \
       h->s_Apk.as<f32x4>(), h->s_Bpk.as<f32x4>(), (unsigned)op.Mpad, (unsigned)op.Npad, op.KQ,            \
-      h->s_rpair.as<float2>(), h->s_cpair.as<float2>(), dout, ld, (int)M, (int)Nt, h->bt4_fringe.as<float>(), tb->tab.as<int2>(), h->bt4_cnt.as<unsigned>(), qs, DBG_)
+      h->s_rpair.as<float2>(), h->s_cpair.as<float2>(), dout, ld, (int)M, (int)Nt, h->bt4_fringe.as<float>(), tb->tab.as<int2>(), h->bt4_cnt.as<unsigned>(), DBG_)
 #if PLDA_DIAG
       if (h->gemm_variant == 41) {
         PLDA_HIP(h, h->timeline.reserve(TIMELINE_WORDS * 8));

@@ -30,6 +30,32 @@
 //     block-major part, per-slot branches between two store forms (each made the compiler copy accumulator blocks into
 //     VGPRs or spill them on the main path); the row offset on the vector offset with the edge in num_records (one v_add
 //     per store: 116 000 against 108 500 cycles per tile); the fringe on the 128 x 128 kernel (0.33 of 28.7 ms at C2).
+// The tile boundary (what lies between the last MFMA of one tile and the first k-step MFMA of the next; figures for <4, 0>,
+// D = 200, profiles/bt4_tile_boundary.txt): 109 245 -> 108 090 cycles per tile, 94.7 -> 95.7 % of them MFMA work.
+//   * the next tile is the tile the DMA cursor stands in during this tile's last stage, so its place, existence and bias
+//     slot are the cursor's own d_r0 / d_c0 / d_ok / d_slot: no three-slot queue beside it, no selects at the back edge;
+//   * its output base, row stride, lane offset (tile_out) are computed between the first MFMA pairs of the block-major part
+//     and its bias fragments are read three MFMA pairs before that part ends: the back edge carries finished values, the
+//     first bias MFMA waits for no LDS round trip, and between the bias MFMAs and the first step only the stage loop's own set-up is left;
+//   * ONE place stores the carried block pair (a workgroup without a further tile passes the bias block once more and
+//     leaves behind it): with a second copy of the 32 stores on the exit path the compiler hoisted their operands to the
+//     loop head, 32 v_accvgpr_read_b32 per tile that waited for the previous tile's last MFMAs.  One is left (a31 -> a VGPR
+//     behind an s_nop 6; it stays whatever the order of the 32 stores and with the carried blocks defined before the loop);
+//   * the cursor's advance at the end of the block-major part is straight-line (dma_advance_mid: d_st == 1 there);
+//   * SGPRs: the queue table lives in front of the tile table (BT4_QHDR) instead of 16 argument SGPRs indexed by compare /
+//     branch cascades, one bias descriptor chosen per wave instead of two, the table entry comes by a global load on the
+//     table's pointer instead of a third descriptor, loop-carried flags are ints (a bool is a lane mask: two SGPRs, and
+//     `pending ? -1 : 0` on one became a VGPR descriptor word, i.e. a waterfall loop around every carried store):
+//     31 SGPRs spilled to VGPR lanes (45 v_readlane / 31 v_writelane, most inside the tile loop) -> none.
+//   ISA of <4, 0>, parent -> now: 2 647 -> 2 084 instructions; v_accvgpr_read_b32 32 -> 1; v_readlane / v_writelane 45 / 31 ->
+//   0 / 0; loop head up to the first bias MFMA 43 + 22 -> 16 instructions; ds_read + lgkmcnt(0) wait in front of the first bias
+//   MFMA: the 4 + 1 are now in the block-major part / satisfied; last bias MFMA -> first k-step MFMA ~55 -> ~25; last
+//   block-major MFMA -> loop head ~45 (3 taken branches) -> ~22 (2); v_mfma 608, ds_read_b128 80 as before; buffer_store_dword
+//   288 -> 256 (the exit path's copy), LDS-DMA 70 -> 66 (one bias piece per site, the advance without one).
+//   Measured and dropped (part B of the same work): skewing the four waves behind a regular stage's early barrier (wave w
+//   waits w passes of an `s_nop 15` loop, ~30 cycles each) so that their 16 DMA pieces do not reach the address unit in
+//   lockstep: 109 085 against 108 085 cycles per tile, 28.49 against 28.32 ms -- every regular stage longer by more than
+//   the skew.  Not built: the stage's pieces spread over its last TWO steps (+32 VGPRs), odd stages without the x/y copy.
 // Stage sizes: nst = ceil(nsteps / 4) balanced stages, the LARGER ones last, so that the block-major
 // part is as long as possible (D = 200: 3,3,3,4,4,4,4 -> FS = 4: 12 288 cycles for the 1024 stores of a CU).
 // Needs nst >= 3 (K >= 72); smaller depths stay on bt2.
@@ -38,6 +64,10 @@ constexpr int BT4_BIAS = 2 * 65536;
 constexpr int BT4_MBOX = BT4_BIAS + 3 * 4096;      // 4 ints: the tile the DMA cursor enters next (wave 0 -> all waves)
 constexpr int BT4_LDS = BT4_MBOX + 64;             // 143424 B
 struct Bt4Queues { int qbase[8]; int qlen[8]; };   // per XCD: first entry and length of its tile queue (score.hip: bt4_schedule)
+// The kernel does not take Bt4Queues as an argument (16 argument SGPRs indexed through compare / branch cascades: 31 SGPRs
+// spilled to VGPR lanes): the first BT4_QHDR entries of the tile table are the queue table, entry x = (first entry of
+// queue x, already counted from the start of the table; its length), read with one scalar load where a queue is entered.
+constexpr int BT4_QHDR = 8;
 // The queue counters (cnt[0 .. 7], device scope).  The first BT4_OWN entries of a queue are the first tiles of its XCD's 32
 // workgroups (taken by position, no round trip); counter value v therefore means entry BT4_OWN + v, and a launch starts from
 // ZERO whatever the tile grid.  The launch leaves them at zero itself: every workgroup counts out on cnt[BT4_DONE] after its
@@ -101,7 +131,7 @@ __device__ __forceinline__ void bt4_leave(unsigned *__restrict__ cnt) {
 template <int FS, int MODE>
 __global__ __launch_bounds__(256, 1) void trials_gemm_bt4_kernel(
     const f32x4 *__restrict__ Apk, const f32x4 *__restrict__ Bpk, unsigned Mpad, unsigned Npad, int KQ,
-    const float2 *__restrict__ rpair, const float2 *__restrict__ cpair, float *__restrict__ out, int64_t ld, int Mrows, int Ncols, float *__restrict__ fringe, const int2 *__restrict__ tab, unsigned *__restrict__ cnt, const Bt4Queues qs,
+    const float2 *__restrict__ rpair, const float2 *__restrict__ cpair, float *__restrict__ out, int64_t ld, int Mrows, int Ncols, float *__restrict__ fringe, const int2 *__restrict__ tab, unsigned *__restrict__ cnt,
     unsigned long long *__restrict__ dbg) {
   extern __shared__ __attribute__((aligned(16))) f32x4 smem[];
   static_assert(FS == 3 || FS == 4, "the last stage has 3 or 4 steps");
@@ -131,12 +161,11 @@ __global__ __launch_bounds__(256, 1) void trials_gemm_bt4_kernel(
   //      a 16-byte mailbox in LDS in front of the barrier of the stage in which the DMA cursor changes tiles.  A queue
   //      that has run dry sends the workgroup on to the next XCD's.
   volatile LDS_AS int *const mbox = (volatile LDS_AS int *)(lds + BT4_MBOX);
-  const __amdgpu_buffer_rsrc_t rsTab = __builtin_amdgcn_make_buffer_rsrc(const_cast<int2 *>(tab), 0, -1, 0x00020000);
   int myq = xcd, q_tries = 0;                 // (wave 0) the queue being consumed and how many have been found dry
-  auto q_len = [&](int q) { return q == 0 ? qs.qlen[0] : q == 1 ? qs.qlen[1] : q == 2 ? qs.qlen[2] : q == 3 ? qs.qlen[3] : q == 4 ? qs.qlen[4] : q == 5 ? qs.qlen[5] : q == 6 ? qs.qlen[6] : qs.qlen[7]; };
-  auto q_base = [&](int q) { return q == 0 ? qs.qbase[0] : q == 1 ? qs.qbase[1] : q == 2 ? qs.qbase[2] : q == 3 ? qs.qbase[3] : q == 4 ? qs.qbase[4] : q == 5 ? qs.qbase[5] : q == 6 ? qs.qbase[6] : qs.qbase[7]; };
-  int q_len_cur = q_len(xcd), q_base_cur = q_base(xcd);
-  auto q_next = [&]() { myq = (myq + 1) & 7; ++q_tries; q_len_cur = q_len(myq); q_base_cur = q_base(myq); };
+  int q_len_cur, q_base_cur;                  // the queue table's entry of myq (a uniform address: one scalar load)
+  auto q_enter = [&](int q) { const int2 e = tab[q]; q_base_cur = __builtin_amdgcn_readfirstlane(e.x); q_len_cur = __builtin_amdgcn_readfirstlane(e.y); };
+  q_enter(xcd);
+  auto q_next = [&]() { myq = (myq + 1) & 7; ++q_tries; q_enter(myq); };
   auto take = [&]() -> int {                  // next slot of queue myq (uniform over the wave)
     unsigned sl = 0;
     if (lane == 0) sl = BT4_OWN + __hip_atomic_fetch_add(cnt + myq, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -173,7 +202,7 @@ __global__ __launch_bounds__(256, 1) void trials_gemm_bt4_kernel(
   }
   const int t0_r0 = __builtin_amdgcn_readfirstlane(mbox[0]), t0_c0 = __builtin_amdgcn_readfirstlane(mbox[1]);
   if (t0_r0 < 0) { bt4_leave(cnt); return; }
-  bool d_ok = true;
+  int d_ok = 1;                               // the cursor stands in a real tile (an int: a loop-carried bool lives in a lane mask)
 
   // ---- DMA cursor.  This wave moves rows [wave*64, +64) of the 8 k-quad planes of a stage, A side then B side:
   //      16 pieces of 1 KiB per stage ----
@@ -181,12 +210,16 @@ __global__ __launch_bounds__(256, 1) void trials_gemm_bt4_kernel(
   const unsigned ldsw = (unsigned)wave * 1024u;
   int d_st = 0, d_slot = 0;
   int d_r0 = t0_r0, d_c0 = t0_c0;
-  int q_r0[3] = {d_r0, 0, 0}, q_c0[3] = {d_c0, 0, 0};
-  int q_ok[3] = {1, 0, 0};
   unsigned d_offA = ((unsigned)d_r0 + (unsigned)wave * 64u) * 16u;
   unsigned d_offB = ((unsigned)d_c0 + (unsigned)wave * 64u) * 16u;
   unsigned d_lds = 0;
   float *const bias_lds = reinterpret_cast<float *>(reinterpret_cast<char *>(smem) + BT4_BIAS);
+  // a tile's bias pairs: 2 KiB per side, one piece from each wave (waves 0, 1 the row side, 2, 3 the column side): ONE
+  // descriptor and one instruction per wave, chosen here
+  const unsigned long long bias_src = reinterpret_cast<unsigned long long>(wave < 2 ? (const void *)rpair : (const void *)cpair);
+  const __amdgpu_buffer_rsrc_t rsBias = __builtin_amdgcn_make_buffer_rsrc(
+      reinterpret_cast<void *>(((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(bias_src >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)bias_src)), 0, -1, 0x00020000);
+  const int bias_w = (wave & 1) * 1024;
 
   auto dma_piece = [&](int jj) {
     if (NODMA) return;
@@ -201,12 +234,7 @@ __global__ __launch_bounds__(256, 1) void trials_gemm_bt4_kernel(
     if (d_st == 0 && d_ok && !NODMA) {
       // the tile's bias pairs: 2 KiB per side, one piece from each wave (MUBUF DMA, see bt2)
       float *dst = bias_lds + d_slot * 1024 + wave * 256;
-      if (wave < 2)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(__builtin_amdgcn_make_buffer_rsrc(const_cast<float2 *>(rpair), 0, -1, 0x00020000),
-                                                 (LDS_AS void *)dst, 16, lane16, d_r0 * 8 + wave * 1024, 0, 0);
-      else
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(__builtin_amdgcn_make_buffer_rsrc(const_cast<float2 *>(cpair), 0, -1, 0x00020000),
-                                                 (LDS_AS void *)dst, 16, lane16, d_c0 * 8 + (wave - 2) * 1024, 0, 0);
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsBias, (LDS_AS void *)dst, 16, lane16, (wave < 2 ? d_r0 : d_c0) * 8 + bias_w, 0, 0);
     }
     const unsigned npd = (unsigned)(sbase + (d_st >= big0 ? 1 : 0));
     d_offA += npd * 2u * strideA1;
@@ -215,14 +243,24 @@ __global__ __launch_bounds__(256, 1) void trials_gemm_bt4_kernel(
     if (++d_st == nst) {
       d_st = 0;
       d_slot = d_slot == 2 ? 0 : d_slot + 1;
-      if (d_ok) d_ok = nx_r0 >= 0;
+      if (d_ok) d_ok = nx_r0 >= 0 ? 1 : 0;
       if (d_ok) { d_r0 = nx_r0; d_c0 = nx_c0; }
-      if (d_slot == 0) { q_r0[0] = d_r0; q_c0[0] = d_c0; q_ok[0] = d_ok ? 1 : 0; }
-      else if (d_slot == 1) { q_r0[1] = d_r0; q_c0[1] = d_c0; q_ok[1] = d_ok ? 1 : 0; }
-      else { q_r0[2] = d_r0; q_c0[2] = d_c0; q_ok[2] = d_ok ? 1 : 0; }
       d_offA = ((unsigned)d_r0 + (unsigned)wave * 64u) * 16u;
       d_offB = ((unsigned)d_c0 + (unsigned)wave * 64u) * 16u;
     }
+  };
+
+  // The advance at the end of the block-major part, straight-line.  Precondition: d_st == 1.  The cursor entered
+  // (t + 1, stage 0) in the last step of stage nst - 2 of tile t (that step's dma_advance() took the tile change or came from
+  // it with d_st == 0 and left d_st == 1; the prologue leaves the same state for the first tile), the block-major part has
+  // just issued the pieces of (t + 1, stage 1), and nst >= 3 (the host requires it where use_bt4 is decided) keeps
+  // stage 2 inside the same tile: no tile change, no bias DMA, nothing to decide.
+  const unsigned np1 = (unsigned)(sbase + (1 >= big0 ? 1 : 0));   // steps of stage 1
+  auto dma_advance_mid = [&]() {
+    d_offA += np1 * 2u * strideA1;
+    d_offB += np1 * 2u * strideB1;
+    d_lds ^= 65536u;
+    ++d_st;
   };
 
   int tseq = 0, st = 0;
@@ -267,15 +305,26 @@ __global__ __launch_bounds__(256, 1) void trials_gemm_bt4_kernel(
   for (int jj = 0; jj < 16; ++jj) dma_piece(jj);
   dma_advance();
 
-  int cur = 0, c_slot = 0;
-  int r0 = q_r0[0], c0 = q_c0[0];
-  bool have = true;
+  int cur = 0;
+  int have = 1;                             // (an int, like pending: a loop-carried bool lives in a lane mask)
   const f32x4 *const Abase = smem + hh * 256 + wm * 128 + i;
   const f32x4 *const Bbase = smem + 8 * 256 + hh * 256 + wn * 128 + i;
   f32x4 xa[4], xb[4], ya[4], yb[4];
   f32x4 fa[FS - 1][4], fb[FS - 1][4];
   f32x16 acc[4][4];
   BT4_LOAD(x, Abase, Bbase)
+  // the bias fragments of a tile are read one tile ahead (in the block-major part of the tile before; the first tile's here,
+  // behind the prologue's barrier, which covered the DMA of bias slot 0), so that the first bias MFMA of a tile waits for no
+  // LDS round trip
+  float ap[4], bp[4];
+  auto bias_read = [&](int slot) {
+    const float *const bl = bias_lds + slot * 1024;
+#pragma unroll
+    for (int tm = 0; tm < 4; ++tm) ap[tm] = bl[(wm * 128 + tm * 32 + i) * 2 + hh];
+#pragma unroll
+    for (int tn = 0; tn < 4; ++tn) bp[tn] = bl[512 + (wn * 128 + tn * 32 + i) * 2 + hh];
+  };
+  bias_read(0);
 
   // ---- output addressing.  A register r = 4 q + e of a 32 x 32 accumulator block holds rows 8 q + e and 8 q + e + 4
   //      (lane >> 5) of 32 consecutive columns: one dword store = two full 128-byte row pieces.  The lane part of the
@@ -284,7 +333,7 @@ __global__ __launch_bounds__(256, 1) void trials_gemm_bt4_kernel(
   //      The matrix edge: a tile that crosses it is written WHOLE into its slot of the `fringe` scratch (256 x 256, row
   //      stride 256) and copied out by fringe_copy_kernel behind this launch -- no bounds in this kernel's store path.
   const int tilesM = (Mrows + 255) >> 8, tilesN = (Ncols + 255) >> 8;
-  const int rag_m = (Mrows & 255) != 0, rag_n = (Ncols & 255) != 0;   // the last tile row / column crosses the edge
+  const int edge_tm = (Mrows & 255) != 0 ? tilesM - 1 : -1, edge_tn = (Ncols & 255) != 0 ? tilesN - 1 : -1;   // the tile row / column that crosses the edge (-1: none)
   int pending = 0, p_lo = 0, p_hi = 0;      // (ints, not bools: they stay on the scalar unit)
   unsigned p_ldb = 0, p_voff = 0;
   auto make_rs = [&](int lo, int hi, int nr) {
@@ -306,21 +355,36 @@ __global__ __launch_bounds__(256, 1) void trials_gemm_bt4_kernel(
   auto store_pair = [&](const __amdgpu_buffer_rsrc_t rs, unsigned vo, unsigned rowb, int p, int k) {
     store_reg(rs, vo, rowb, p >> 1, 2 * (p & 1) + (k & 1), k >> 1);
   };
+  // a tile's output: its place in the matrix, or -- a tile that crosses the matrix edge -- slot `tile row` (last tile
+  // column) / `tilesM + tile column` (last tile row) of the fringe scratch.  Scalar selects only: it runs for the NEXT tile
+  // between the MFMAs of the block-major part (everything it reads exists since the cursor's tile change in stage nst - 3),
+  // so that the back edge carries finished values and nothing stands between a tile's bias MFMAs and its first step.
+  auto tile_out = [&](int tr0, int tc0, int &t_lo, int &t_hi, unsigned &t_ldb, unsigned &t_voff) {
+    const int tmi = tr0 >> 8, tni = tc0 >> 8;
+    const int e_col = tni == edge_tn ? 1 : 0, e_row = tmi == edge_tm ? 1 : 0;
+    const int edge = e_col | e_row;
+    const int fslot = e_col ? tmi : tilesM + tni;
+    const unsigned long long a_f = reinterpret_cast<unsigned long long>(fringe) + 4ull * (unsigned long long)((int64_t)fslot * 65536 + (wm * 128) * 256 + wn * 128);
+    const unsigned long long a_m = reinterpret_cast<unsigned long long>(out) + 4ull * (unsigned long long)(((int64_t)tr0 + wm * 128) * ld + tc0 + wn * 128);
+    const unsigned long long o_addr = edge ? a_f : a_m;
+    t_ldb = (unsigned)__builtin_amdgcn_readfirstlane((int)(edge ? 1024u : 4u * (unsigned)ld));   // bytes per output row (ld < 2^22)
+    t_voff = (unsigned)hh * (4u * t_ldb) + (unsigned)i * 4u;
+    t_lo = __builtin_amdgcn_readfirstlane((int)(unsigned)o_addr); t_hi = __builtin_amdgcn_readfirstlane((int)(unsigned)(o_addr >> 32));
+  };
+  int o_lo, o_hi;                           // this tile's output base, row stride in bytes and lane offset
+  unsigned ldb, voff;
+  tile_out(d_r0, d_c0, o_lo, o_hi, ldb, voff);
   for (;;) {
     // (opaque per tile: the row offsets are then one scalar multiply beside each store; left loop-invariant, the
     //  compiler hoists all 128 of them out of the tile loop and spills them to VGPR lanes)
     p_ldb = (unsigned)__builtin_amdgcn_readfirstlane((int)p_ldb);
     asm volatile("" : "+s"(p_ldb));
+    ldb = (unsigned)__builtin_amdgcn_readfirstlane((int)ldb);
+    asm volatile("" : "+s"(ldb));
     // (rebuilt per tile from scalars that went through readfirstlane: a loop-carried descriptor -- or one the compiler can
     //  prove equal to the previous tile's -- ends up in vector registers and every store in a waterfall loop)
-    const __amdgpu_buffer_rsrc_t p_rs = make_rs(p_lo, p_hi, pending ? -1 : 0);
-    if (!have) {
-      if (pending) {
-#pragma unroll
-        for (int k = 0; k < 32; ++k) store_pair(p_rs, p_voff, p_ldb, 7, k);
-      }
-      break;
-    }
+    const __amdgpu_buffer_rsrc_t p_rs = make_rs(p_lo, p_hi, -pending);   // (num_records 0 on the first tile: nothing carried)
+    const __amdgpu_buffer_rsrc_t rs = make_rs(o_lo, o_hi, -1);
     // ---- the tile queue, one fetch per tile, at three fixed places of the tile's code (all wave 0, none inside the
     //      MFMA-interleaved parts): here the atomic on the queue's counter; behind the last stage's barrier -- whose vmcnt(0)
     //      has seen the slot number arrive -- the load of that slot's table entry; at the end of the tile the entry goes into
@@ -330,7 +394,7 @@ __global__ __launch_bounds__(256, 1) void trials_gemm_bt4_kernel(
     //      s_waitcnt vmcnt(0) for a memory round trip in the middle of wave 0's MFMA stream (~1 500 cycles per tile).
     unsigned long long t_top0 = 0;
     if (TL) t_top0 = __builtin_amdgcn_s_memtime();
-    const bool fetching = wave == 0 && more_tiles != 0;
+    const bool fetching = wave == 0 && more_tiles != 0;   // (more_tiles == 0 where !have: the tile published last was none)
     // (f_raw, f_ent: defined ONLY on the fetching path -- initialised on the other, the merge would be a copy of the
     //  value right behind its issue, i.e. a wait for the memory round trip.  score.hip is compiled with the atomic
     //  optimizer off: it rewrites this one-lane atomic into a wave reduction that reads the result back at once.)
@@ -341,13 +405,11 @@ __global__ __launch_bounds__(256, 1) void trials_gemm_bt4_kernel(
     if (fetching && lane == 0) f_raw = __hip_atomic_fetch_add(cnt + myq, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     // accumulators start from the bias r'_i + s_i q_j: one rank-2 MFMA per block on the tile's bias pairs (srcC = 0).
     // The previous tile's last block pair (blocks 14, 15) is stored under the bias MFMAs of blocks 0 .. 13.
+    // A workgroup that has no further tile (!have) takes this block once more for the carried stores and leaves behind it:
+    // ONE place stores block pair 7.  (With a second copy of the 32 stores on the exit path the compiler hoisted their
+    // common operands to the loop head: 32 v_accvgpr_read_b32 in front of every tile, waiting for the last MFMAs of the
+    // tile before with nothing behind them in the pipe.)
     {
-      const float *const bl = bias_lds + c_slot * 1024;
-      float ap[4], bp[4];
-#pragma unroll
-      for (int tm = 0; tm < 4; ++tm) ap[tm] = bl[(wm * 128 + tm * 32 + i) * 2 + hh];
-#pragma unroll
-      for (int tn = 0; tn < 4; ++tn) bp[tn] = bl[512 + (wn * 128 + tn * 32 + i) * 2 + hh];
       const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
       if (pending) {
 #pragma unroll
@@ -370,6 +432,7 @@ __global__ __launch_bounds__(256, 1) void trials_gemm_bt4_kernel(
       }
       BT4_SB;
     }
+    if (!have) break;
     if (TL) {
       const unsigned long long t_top1 = __builtin_amdgcn_s_memtime();
       if (blockIdx.x == 0 && lane == 0 && tseq < 8) {
@@ -377,20 +440,11 @@ __global__ __launch_bounds__(256, 1) void trials_gemm_bt4_kernel(
         p[2] = t_top0; p[3] = t_top1;      // the tile's top: entry, and behind the bias MFMAs with the carried stores
       }
     }
-    // this tile's output: its place in the matrix, or -- a tile that crosses the matrix edge -- slot `tile row` (last tile
-    // column) / `tilesM + tile column` (last tile row) of the fringe scratch
-    const int tmi = r0 >> 8, tni = c0 >> 8;
-    const int e_col = rag_n & (tni == tilesN - 1 ? 1 : 0), e_row = rag_m & (tmi == tilesM - 1 ? 1 : 0);
-    const int fslot = e_col ? tmi : tilesM + tni;
-    const float *const obase = (e_col | e_row) ? fringe + ((int64_t)fslot * 65536 + (wm * 128) * 256 + wn * 128)
-                                               : out + (((int64_t)r0 + wm * 128) * ld + c0 + wn * 128);
-    unsigned ldb = (unsigned)__builtin_amdgcn_readfirstlane((int)((e_col | e_row) ? 1024u : 4u * (unsigned)ld));   // bytes per output row (ld < 2^22)
-    asm volatile("" : "+s"(ldb));   // (opaque per tile: the row offsets are then one scalar multiply beside each store; left
-                                    //  loop-invariant, the compiler hoists all 128 of them and spills them to VGPR lanes)
-    const unsigned voff = (unsigned)hh * (4u * ldb) + (unsigned)i * 4u;
-    const unsigned long long o_addr = reinterpret_cast<unsigned long long>(obase);
-    const int o_lo = (int)(unsigned)o_addr, o_hi = (int)(unsigned)(o_addr >> 32);
-    const __amdgpu_buffer_rsrc_t rs = make_rs(o_lo, o_hi, -1);
+    // The next tile is the one the DMA cursor stands in during this tile's last stage: it entered it in stage nst - 3 of
+    // this tile and leaves it in stage nst - 3 of the next (nst >= 3), so d_r0 / d_c0 / d_ok / d_slot ARE the next tile's
+    // place, existence and bias slot there -- no queue of tile slots beside the cursor.
+    int n_have = 0, n_lo = 0, n_hi = 0;
+    unsigned n_ldb = 0, n_voff = 0;
 
     for (st = 0; st < nst - 1; ++st) {
       const int np = sbase + (st >= big0 ? 1 : 0);
@@ -434,8 +488,11 @@ __global__ __launch_bounds__(256, 1) void trials_gemm_bt4_kernel(
         f_sl = __builtin_amdgcn_readfirstlane((int)(BT4_OWN + f_raw));
         // (a vector-memory load although the address is uniform: a scalar load's result would sit in lgkmcnt, where the next
         //  fragment wait of this wave -- lgkmcnt(0), scalar loads return out of order -- waits for the table's memory
-        //  latency; a dry queue: entry 0 is read and dropped)
-        f_ent = __builtin_amdgcn_raw_buffer_load_b64(rsTab, (q_base_cur + (f_sl < q_len_cur ? f_sl : 0)) * 8, 0, 0);
+        //  latency; a dry queue: entry 0 is read and dropped.  The index goes through a VGPR on purpose: a global load on the
+        //  table's pointer, which the scalar unit holds anyway, instead of four more SGPRs for a buffer descriptor.)
+        int f_idx = q_base_cur + (f_sl < q_len_cur ? f_sl : 0);
+        asm volatile("" : "+v"(f_idx));
+        f_ent = *reinterpret_cast<const u32x2 *>(tab + f_idx);
       }
       BT4_SB;
       BT4_LOAD(x, An, Bn)
@@ -459,9 +516,22 @@ __global__ __launch_bounds__(256, 1) void trials_gemm_bt4_kernel(
 #pragma unroll
               for (int k = 32 * slot / NSLOT; k < 32 * (slot + 1) / NSLOT; ++k) store_pair(rs, voff, ldb, p - 1, k);
             }
+            if (p == 0 && slot == 0) {          // (pair 0 carries no stores: its issue slots are free)
+              // (the empty asm statements keep the arithmetic HERE: without them the optimiser moves its scalar part in
+              //  front of the part's first MFMA pair and sinks the lane offset to the back edge)
+              int n_r0 = d_r0, n_c0 = d_c0;
+              asm volatile("" : "+s"(n_r0), "+s"(n_c0));
+              n_have = d_ok;
+              tile_out(n_r0, n_c0, n_lo, n_hi, n_ldb, n_voff);
+              asm volatile("" : "+s"(n_lo), "+s"(n_hi), "+s"(n_ldb), "+v"(n_voff));
+            }
+            // the next tile's bias fragments: its slot is in LDS since this stage's barrier (the bias DMA went out with the
+            // cursor's advance in the last step of stage nst - 2 and that barrier's vmcnt(0) covered it); it is written
+            // again two tiles from here
+            if (p == 7 && slot == NSLOT - 3) bias_read(d_slot);
             if (slot == 1) dma_piece(2 * p);
             if (slot == NSLOT / 2 + 1) dma_piece(2 * p + 1);
-            if (p == 7 && slot == NSLOT - 1) dma_advance();
+            if (p == 7 && slot == NSLOT - 1) { dma_advance_mid(); asm volatile("" : "+s"(d_offA), "+s"(d_offB), "+s"(d_lds), "+s"(d_st)); }
             BT4_SB;
           }
       }
@@ -481,11 +551,9 @@ __global__ __launch_bounds__(256, 1) void trials_gemm_bt4_kernel(
       more_tiles = e0 >= 0 ? 1 : 0;
     }
     pending = 1; p_lo = o_lo; p_hi = o_hi; p_ldb = ldb; p_voff = voff;
+    o_lo = n_lo; o_hi = n_hi; ldb = n_ldb; voff = n_voff;
     ++tseq;
-    c_slot = c_slot == 2 ? 0 : c_slot + 1;
-    r0 = c_slot == 0 ? q_r0[0] : (c_slot == 1 ? q_r0[1] : q_r0[2]);
-    c0 = c_slot == 0 ? q_c0[0] : (c_slot == 1 ? q_c0[1] : q_c0[2]);
-    have = (c_slot == 0 ? q_ok[0] : (c_slot == 1 ? q_ok[1] : q_ok[2])) != 0;
+    have = n_have;
   }
   __builtin_amdgcn_s_waitcnt(0x0070);   // no DMA may land in LDS after the workgroup has gone (nor an atomic of the queue be in flight)
   bt4_leave(cnt);
