@@ -474,6 +474,88 @@ int plda_score_calib_fit_dev(plda_handle *h, const double *dU, const int32_t *dn
 int plda_affine_map_dev(plda_handle *h, const float *dscores, int64_t ld, int64_t M, int64_t Nt, double a, double b,
                         float *dout, int64_t ld_out);
 
+/* ---- exact minimum detection cost (minDCF; NIST SRE min_Cprimary, VoxCeleb's minDCF) at up to 8 operating points,
+ * without sorting (csrc/dcf.hip; the project's own extension like the calibration above: tests/mindcf_model.py pins it).
+ * actDCF - minDCF is the calibration loss of a system.
+ *
+ * Trials, classes, key order and rate conventions are those of plda_eer_matrix_dev / plda_eer_lists: an fp32 score, a
+ * target iff enrol_spk[i] == test_spk[j] (or by list), -0.0 == +0.0, FAR(t) = #{non-target >= t} / Nn,
+ * FRR(t) = #{target < t} / Np.  "Key" is the order-preserving 32-bit key of a score (a < b <=> key(a) < key(b)).
+ *   * A CUT is "reject every trial whose key is <= k" for a key k present in the data, plus the cut that rejects nothing.
+ *     (The cut at the largest key rejects everything.)  A cut has exact integer counts miss = #{target key <= k},
+ *     fa = #{non-target key > k}; the empty cut has (0, Nn).
+ *   * An OPERATING POINT is (prior, c_miss, c_fa), 0 < prior < 1, costs > 0.  The cost of a cut is evaluated in fp64 exactly
+ *     as plda_amd/calibration.py:act_dcf evaluates it:
+ *         v = ((c_miss * prior) * miss) / Np + ((c_fa * (1 - prior)) * fa) / Nn,   dcf = v / min(c_miss * prior, c_fa * (1 - prior)).
+ *     minDCF is the smallest v over all cuts; among cuts whose fp64 v are equal the LOWEST cut wins.
+ *     The reported min_dcf is min(dcf, 1): in exact arithmetic the better trivial cut costs exactly min(c_miss * prior,
+ *     c_fa * (1 - prior)), so no minimum exceeds 1, but (b * Nn) / Nn is not b for every Nn in fp64 (Nn = 50, b = 0.95: one ulp
+ *     above), and a quotient of 1 + 2^-52 would be rounding alone.  The winning cut is chosen on v, before this.
+ *   * Reported per point: min_dcf (normalised), miss, fa, far = fa / Nn, frr = miss / Np, and threshold: the smallest score
+ *     for the empty cut, +inf for the cut at the largest key, otherwise s + (s' - s) / 2 in fp64 with s the score of k and
+ *     s' the next larger score present (the EER's midpoint rule).
+ *   * A non-finite score fails the call with PLDA_E_INVAL and the count in plda_last_error, as a calibration pass does;
+ *     Np == 0 or Nn == 0 likewise.
+ * Two properties follow from evaluating v by ONE fixed expression on integers: (1) it is monotone in miss and in fa also
+ * after rounding, so the same expression at (miss at the lower end, fa at the upper end) of a key range is a lower bound on
+ * every cut inside the range with no tolerance; (2) min_dcf <= act_dcf holds bit-wise for any threshold, because a
+ * calibration pass at that threshold returns the counts of some cut.
+ *
+ * METHOD: branch and bound over the three key levels of the EER (bits 11 + 11 + 10).  A NODE is a key prefix whose next
+ * bits are histogrammed per class; level 0 has one node (every key).  After a level the host step (plda_min_dcf_step, a
+ * pure function) forms integer prefix sums: every bin edge is a cut with exact counts and updates each point's incumbent
+ * (value, then lowest cut); a bin SURVIVES for a point iff it holds both classes and v(miss at its lower edge, fa at its
+ * upper edge) <= incumbent; the survivors of a level, the union over the points, are the next level's nodes.  One read of
+ * the scores refines up to 8 nodes at once.  When the trials inside the survivors are few and the next level would need
+ * more than one read, one read appends them to two lists and the remaining levels run on the lists.  The keys next to the
+ * winning cuts come from a last pass over the lists when the counts prove that they lie inside them, otherwise over the
+ * scores.  Integer atomics only: a call is bit-reproducible.
+ *
+ * out[n_points] / info (nullable) are HOST structures; the calls synchronise the handle's stream.  Arguments otherwise as
+ * the EER / calibration siblings; the operand form re-scores the slabs once per read; the _comm form is the row-sharded
+ * matrix of plda_eer_matrix_comm_dev (every histogram summed over the ranks, survivors decided identically everywhere,
+ * lists local).  PLDA_MINDCF_VARIANT (read by plda_create): 1 = never use the lists, 2 = two nodes per read. ---- */
+#define PLDA_MIN_DCF_MAX_POINTS 8
+typedef struct plda_dcf_point { double prior, c_miss, c_fa; } plda_dcf_point;
+typedef struct plda_min_dcf { double min_dcf, threshold, far, frr; uint64_t miss, fa; } plda_min_dcf;
+typedef struct plda_min_dcf_info {
+  uint64_t np, nn;
+  int32_t reads;              /* passes over the scores themselves (matrix, slabs or the caller's lists) */
+  int32_t launches;           /* histogram / append / neighbour passes in all, those over the compact lists included */
+  int32_t lists_used;         /* 1: surviving trials were appended to lists and the remaining levels ran there */
+  int32_t neighbour_reads;    /* of `reads`: passes that only looked for the keys next to the winning cuts */
+  int32_t level_launches[3];  /* histogram passes per level */
+  int32_t reserved;
+  int64_t level_bins[3];      /* nodes refined at each level (1 at level 0) */
+  uint64_t level_trials[3];   /* trials inside them */
+} plda_min_dcf_info;
+int plda_min_dcf_matrix_dev(plda_handle *h, const float *dscores, int64_t ld, int64_t M, int64_t Nt,
+                            const int64_t *denrol_spk, const int64_t *dtest_spk, int32_t n_points,
+                            const plda_dcf_point *points, plda_min_dcf *out, plda_min_dcf_info *info);
+int plda_min_dcf_lists(plda_handle *h, const float *pos, int64_t np, const float *neg, int64_t nn, int32_t n_points,
+                       const plda_dcf_point *points, plda_min_dcf *out, plda_min_dcf_info *info);
+int plda_score_min_dcf_dev(plda_handle *h, const double *dU, const int32_t *dn_enrol, int32_t n_uniform, int64_t M,
+                           const double *dV, int64_t Nt, const double *dzmean, const double *dzstd,
+                           const int64_t *denrol_spk, const int64_t *dtest_spk, int32_t n_points,
+                           const plda_dcf_point *points, plda_min_dcf *out, plda_min_dcf_info *info);
+/* The host step as pure functions (no handle, no GPU; the CPU tests drive the whole refinement through them with NumPy
+ * histograms).  plda_min_dcf_step: `hist` holds, per node, [2][2048] counters (class 0 = non-target) of the level's bits
+ * (level 0, 1: 11 bits; level 2: 10 bits) of the keys under the node's prefix; nodes ascend by prefix.  Level 0 takes one
+ * node (prefix 0), sets state->np / nn / nonfinite from the histogram and starts every incumbent at the empty cut; a
+ * non-finite score, an empty class or a bad point is PLDA_E_INVAL.  The survivors are written to next[0 .. *n_next)
+ * (ascending; PLDA_E_CAPACITY when more than cap_next; none after level 2).  Any subset of a level's nodes may be given per
+ * call: the bound holds against whatever incumbent has been reached.  edge: the cut rejects the keys <= edge.
+ * plda_min_dcf_finish: below[p] / above[p] = the largest key <= best[p].edge and the smallest key above it among the keys
+ * present (0 / 0xffffffff: none; a cut without an edge rejects nothing, above = the smallest key). */
+typedef struct plda_min_dcf_node { uint32_t prefix, reserved; uint64_t miss_below, nn_below, n_pos, n_neg; } plda_min_dcf_node;
+typedef struct plda_min_dcf_cut { double value; uint64_t miss, fa; uint32_t edge; int32_t has_edge; } plda_min_dcf_cut;
+typedef struct plda_min_dcf_state { uint64_t np, nn, nonfinite; plda_min_dcf_cut best[PLDA_MIN_DCF_MAX_POINTS]; } plda_min_dcf_state;
+int plda_min_dcf_step(int32_t level, int64_t n_nodes, const plda_min_dcf_node *nodes, const uint64_t *hist, int32_t n_points,
+                      const plda_dcf_point *points, plda_min_dcf_state *state, int64_t cap_next, plda_min_dcf_node *next,
+                      int64_t *n_next);
+int plda_min_dcf_finish(const plda_min_dcf_state *state, int32_t n_points, const plda_dcf_point *points, const uint32_t *below,
+                        const uint32_t *above, plda_min_dcf *out);
+
 /* ---- several GPUs of one node: one process per GPU, one handle per process.  The reference
  * has no counterpart (one process, one thread; its native object libplda.MPlda, pldamodule.cpp:280-295, is the only
  * thing callers bind, so the sharded path lives behind the same object).
@@ -524,6 +606,7 @@ int plda_affine_map_dev(plda_handle *h, const float *dscores, int64_t ld, int64_
  *       (:102-106) run as replicas on every rank from identical inputs.
  *   plda_eer_matrix_comm_dev        plda_eer_matrix_sharded_dev with the handle's collectives; the compact slab of
  *       plda_score_matrix_sharded_local_dev (with the speaker ids of ITS rows) is what it takes.
+ *   plda_min_dcf_matrix_comm_dev    the same for the minimum detection cost (plda_min_dcf_matrix_dev).
  * Without a communicator all of them run as a single rank. ---- */
 #define PLDA_DT_F64 0
 #define PLDA_DT_U64 1
@@ -587,6 +670,12 @@ int plda_fit_sharded_dev(plda_handle *h, const double *dX, int64_t N, int32_t D,
                          int64_t K, int32_t iters);
 int plda_eer_matrix_comm_dev(plda_handle *h, const float *dscores, int64_t ld, int64_t M, int64_t Nt,
                              const int64_t *denrol_spk, const int64_t *dtest_spk, double *out);
+/* plda_min_dcf_matrix_dev of a row-sharded matrix (arguments as above; M == 0 is allowed: a rank that owns no row still takes
+ * part).  Every rank gets the global result.  A rank that fails keeps its peers out of a blocked collective by the
+ * poisoned-histogram protocol of the sharded EER. */
+int plda_min_dcf_matrix_comm_dev(plda_handle *h, const float *dscores, int64_t ld, int64_t M, int64_t Nt,
+                                 const int64_t *denrol_spk, const int64_t *dtest_spk, int32_t n_points,
+                                 const plda_dcf_point *points, plda_min_dcf *out, plda_min_dcf_info *info);
 
 /* ---- LDA: replaces the reference's second model, the pure-Python
  * class LDA of python/liblda/lda.py (used by scoring/scoreLDA.py:175,224,241), on the same

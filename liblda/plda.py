@@ -42,6 +42,11 @@ class PLDA(object):
         are the speakers, test_speaker names the speaker of each test entry); returns a plda_amd.calibration.Calibration."""
         return self._instance.calibrate(enrol, test, test_speaker, prior, znorm, cohort, top_k)
 
+    def min_dcf(self, enrol, test, test_speaker, points=((0.01, 1.0, 1.0),), znorm=True, cohort=None, top_k=None, calibrate=False):
+        """The exact minimum detection cost of the trials between two transform() results at up to 8 operating points
+        (prior, c_miss, c_fa); returns (one dict per point, info)."""
+        return self._instance.min_dcf(enrol, test, test_speaker, points, znorm, cohort, top_k, calibrate)
+
     def cohort_stats(self, side, cohort, top_k=None):
         """(mean, std) of the top_k largest cohort scores of every row of `side` (AS-norm statistics)."""
         return self._instance.cohort_stats(side, cohort, top_k)

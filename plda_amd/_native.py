@@ -117,6 +117,12 @@ SIGNATURES = {
     "plda_calib_fit_matrix_dev": (C.c_int, [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _f64, _f64, _i32, _vp]),
     "plda_calib_fit_lists": (C.c_int, [_vp, _vp, _i64, _vp, _i64, _f64, _f64, _i32, _vp]),
     "plda_score_calib_fit_dev": (C.c_int, [_vp, _vp, _vp, _i32, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _f64, _f64, _i32, _vp]),
+    "plda_min_dcf_matrix_dev": (C.c_int, [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _i32, _vp, _vp, _vp]),
+    "plda_min_dcf_lists": (C.c_int, [_vp, _vp, _i64, _vp, _i64, _i32, _vp, _vp, _vp]),
+    "plda_score_min_dcf_dev": (C.c_int, [_vp, _vp, _vp, _i32, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp]),
+    "plda_min_dcf_matrix_comm_dev": (C.c_int, [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _i32, _vp, _vp, _vp]),
+    "plda_min_dcf_step": (C.c_int, [_i32, _i64, _vp, _vp, _i32, _vp, _vp, _i64, _vp, C.POINTER(_i64)]),
+    "plda_min_dcf_finish": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _vp]),
     "plda_affine_map_dev": (C.c_int, [_vp, _vp, _i64, _i64, _i64, _f64, _f64, _vp, _i64]),
 }
 

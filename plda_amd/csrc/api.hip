@@ -73,6 +73,21 @@ int det_matrix_device(plda_handle *h, const float *dscores, int64_t ld, int64_t 
                       int npoints, double *far, double *frr, double *thresholds);
 int det_lists_device(plda_handle *h, const float *dpos, int64_t np, const float *dneg, int64_t nn, int npoints, double *far, double *frr,
                      double *thresholds);
+// dcf.hip
+int min_dcf_step(int level, int64_t n_nodes, const plda_min_dcf_node *nodes, const uint64_t *hist, int n_points,
+                 const plda_dcf_point *pts, plda_min_dcf_state *st, int64_t cap_next, plda_min_dcf_node *next, int64_t *n_next);
+int min_dcf_finish(const plda_min_dcf_state *st, int n_points, const plda_dcf_point *pts, const uint32_t *below, const uint32_t *above,
+                   plda_min_dcf *out);
+int min_dcf_matrix_device(plda_handle *h, const float *dscores, int64_t ld, int64_t M, int64_t Nt, const int64_t *despk,
+                          const int64_t *dtspk, int n_points, const plda_dcf_point *pts, plda_min_dcf *out, plda_min_dcf_info *info,
+                          int (*reduce)(void *, unsigned long long *, unsigned *, unsigned *), void *ctx);
+int min_dcf_lists_device(plda_handle *h, const float *dpos, int64_t np, const float *dneg, int64_t nn, int n_points,
+                         const plda_dcf_point *pts, plda_min_dcf *out, plda_min_dcf_info *info);
+int score_min_dcf_device(plda_handle *h, const double *dU, const int32_t *dn, int n_uniform, int64_t M, const double *dV, int64_t Nt,
+                         const double *dzmean, const double *dzstd, const int64_t *despk, const int64_t *dtspk, int n_points,
+                         const plda_dcf_point *pts, plda_min_dcf *out, plda_min_dcf_info *info);
+int min_dcf_matrix_comm_device(plda_handle *h, const float *dscores, int64_t ld, int64_t M, int64_t Nt, const int64_t *despk,
+                               const int64_t *dtspk, int n_points, const plda_dcf_point *pts, plda_min_dcf *out, plda_min_dcf_info *info);
 // calib.hip
 int calib_pass_matrix_device(plda_handle *h, const float *dscores, int64_t ld, int64_t M, int64_t Nt, const int64_t *despk,
                              const int64_t *dtspk, double a, double c, double theta, plda_calib_record *out);
@@ -278,6 +293,7 @@ int plda_create(int device, plda_handle **out) {
     if (const char *v = std::getenv("PLDA_SORT_VARIANT")) h->sort_variant = std::atoi(v);
     if (const char *v = std::getenv("PLDA_ZNORM_VARIANT")) h->znorm_variant = std::atoi(v);
     if (const char *v = std::getenv("PLDA_EER_VARIANT")) h->eer_variant = std::atoi(v);
+    if (const char *v = std::getenv("PLDA_MINDCF_VARIANT")) h->mindcf_variant = std::atoi(v);
     if (const char *v = std::getenv("PLDA_EER_SLAB_ROWS")) h->eer_slab_rows = std::atoll(v);
     if (const char *v = std::getenv("PLDA_SNORM_SLAB_ROWS")) h->sn_slab_rows = std::atoll(v);
     if (const char *v = std::getenv("PLDA_HIP_TRACE")) h->trace_on = h->trace_print = std::atoi(v) != 0;
@@ -1736,6 +1752,67 @@ int plda_eer_lists(plda_handle *h, const float *pos, int64_t np, const float *ne
     PLDA_TRY(upload(h, dN, neg, (size_t)nn * 4));
     return eer_lists_device(h, dP.as<float>(), np, dN.as<float>(), nn, out);
   });
+}
+
+// ---------------------------------------------------------------- minimum detection cost (dcf.hip)
+int plda_min_dcf_matrix_dev(plda_handle *h, const float *dscores, int64_t ld, int64_t M, int64_t Nt, const int64_t *denrol_spk,
+                            const int64_t *dtest_spk, int32_t n_points, const plda_dcf_point *points, plda_min_dcf *out,
+                            plda_min_dcf_info *info) {
+  return guarded(h, "plda_min_dcf_matrix_dev", [&]() -> int {
+    if (!h) return PLDA_E_INVAL;
+    PLDA_LOCK(h);
+    if (M <= 0) return fail(h, PLDA_E_INVAL, "min_dcf: bad argument");
+    PLDA_TRY(set_device(h));
+    return min_dcf_matrix_device(h, dscores, ld, M, Nt, denrol_spk, dtest_spk, n_points, points, out, info, nullptr, nullptr);
+  });
+}
+
+int plda_min_dcf_matrix_comm_dev(plda_handle *h, const float *dscores, int64_t ld, int64_t M, int64_t Nt, const int64_t *denrol_spk,
+                                 const int64_t *dtest_spk, int32_t n_points, const plda_dcf_point *points, plda_min_dcf *out,
+                                 plda_min_dcf_info *info) {
+  return guarded(h, "plda_min_dcf_matrix_comm_dev", [&]() -> int {
+    if (!h) return PLDA_E_INVAL;
+    PLDA_LOCK(h);
+    PLDA_TRY(set_device(h));
+    return min_dcf_matrix_comm_device(h, dscores, ld, M, Nt, denrol_spk, dtest_spk, n_points, points, out, info);
+  });
+}
+
+int plda_min_dcf_lists(plda_handle *h, const float *pos, int64_t np, const float *neg, int64_t nn, int32_t n_points,
+                       const plda_dcf_point *points, plda_min_dcf *out, plda_min_dcf_info *info) {
+  return guarded(h, "plda_min_dcf_lists", [&]() -> int {
+    if (!h) return PLDA_E_INVAL;
+    PLDA_LOCK(h);
+    if (!pos || !neg || !out || np <= 0 || nn <= 0)
+      return fail(h, PLDA_E_INVAL, "min_dcf: need at least one target and one non-target score");
+    PLDA_TRY(set_device(h));
+    Tmp dP, dN;
+    PLDA_TRY(upload(h, dP, pos, (size_t)np * 4));
+    PLDA_TRY(upload(h, dN, neg, (size_t)nn * 4));
+    return min_dcf_lists_device(h, dP.as<float>(), np, dN.as<float>(), nn, n_points, points, out, info);
+  });
+}
+
+int plda_score_min_dcf_dev(plda_handle *h, const double *dU, const int32_t *dn_enrol, int32_t n_uniform, int64_t M, const double *dV,
+                           int64_t Nt, const double *dzmean, const double *dzstd, const int64_t *denrol_spk, const int64_t *dtest_spk,
+                           int32_t n_points, const plda_dcf_point *points, plda_min_dcf *out, plda_min_dcf_info *info) {
+  return guarded(h, "plda_score_min_dcf_dev", [&]() -> int {
+    if (!h) return PLDA_E_INVAL;
+    PLDA_LOCK(h);
+    PLDA_TRY(set_device(h));
+    return score_min_dcf_device(h, dU, dn_enrol, n_uniform, M, dV, Nt, dzmean, dzstd, denrol_spk, dtest_spk, n_points, points, out, info);
+  });
+}
+
+// the host step: pure functions, no handle (include/plda_hip.h)
+int plda_min_dcf_step(int32_t level, int64_t n_nodes, const plda_min_dcf_node *nodes, const uint64_t *hist, int32_t n_points,
+                      const plda_dcf_point *points, plda_min_dcf_state *state, int64_t cap_next, plda_min_dcf_node *next,
+                      int64_t *n_next) {
+  return min_dcf_step(level, n_nodes, nodes, hist, n_points, points, state, cap_next, next, n_next);
+}
+int plda_min_dcf_finish(const plda_min_dcf_state *state, int32_t n_points, const plda_dcf_point *points, const uint32_t *below,
+                        const uint32_t *above, plda_min_dcf *out) {
+  return min_dcf_finish(state, n_points, points, below, above, out);
 }
 
 // ---------------------------------------------------------------- score calibration (calib.hip)

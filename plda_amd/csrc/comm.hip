@@ -874,6 +874,16 @@ int eer_matrix_comm_device(plda_handle *h, const float *dscores, int64_t ld, int
   return eer_matrix_device(h, dscores, ld, M, Nt, despk, dtspk, out, eer_comm_reduce, &ctx);
 }
 
+// minDCF of a row-sharded matrix (dcf.hip): the same reduction, one call per [2][2048] block of counters
+int min_dcf_matrix_device(plda_handle *h, const float *dscores, int64_t ld, int64_t M, int64_t Nt, const int64_t *despk,
+                          const int64_t *dtspk, int n_points, const plda_dcf_point *pts, plda_min_dcf *out, plda_min_dcf_info *info,
+                          int (*reduce)(void *, unsigned long long *, unsigned *, unsigned *), void *ctx);
+int min_dcf_matrix_comm_device(plda_handle *h, const float *dscores, int64_t ld, int64_t M, int64_t Nt, const int64_t *despk,
+                               const int64_t *dtspk, int n_points, const plda_dcf_point *pts, plda_min_dcf *out, plda_min_dcf_info *info) {
+  EerCommCtx ctx{h};
+  return min_dcf_matrix_device(h, dscores, ld, M, Nt, despk, dtspk, n_points, pts, out, info, eer_comm_reduce, &ctx);
+}
+
 }  // namespace plda
 
 using namespace plda;

@@ -257,6 +257,7 @@ struct plda_handle {
   plda::DevBuf eer_slab, eer_smp; // plda_score_eer_dev: the row slab of scores in flight; the pilot's gathered enrol rows
   plda::DevBuf eer_list[2];      // eer.hip, single-pass form: the impostor / target scores inside the pilot's key window
   int eer_variant = 0;           // PLDA_EER_VARIANT=1: always the three passes; 2: the single-pass form at every size (tests)
+  int mindcf_variant = 0;        // PLDA_MINDCF_VARIANT=1: never compact the survivors into lists; 2: two nodes per read (dcf.hip; tests)
   int64_t eer_slab_rows = 0;     // PLDA_EER_SLAB_ROWS: rows per slab of plda_score_eer_dev (0: <= 4 GiB of scores)
   plda::DevBuf calib_part;       // calib.hip: one partial plda_calib_record per workgroup of a calibration pass + the reduced one
   plda::DevBuf sn_slab;          // plda_cohort_stats_dev (snorm.hip): the row slab of cohort scores in flight
@@ -476,7 +477,27 @@ int score_eer_sample(void *ctx, int64_t step, const float **scores, int64_t *ld,
 int score_eer_slabs_setup(plda_handle *h, const double *dU, const int32_t *dn, int n_uniform, int64_t M, const double *dV, int64_t Nt,
                           const double *dzmean, const double *dzstd, const int64_t *despk, ScoreEerCtx *c, EerSlabs *sl);
 
+// the order-preserving key of a score, its inverse, the histogram width and the strip width of the EER passes (moved unchanged
+// from eer.hip: dcf.hip refines the same key over the same three levels)
+constexpr int EER_BINS = 2048;
+constexpr int EER_STRIP = 1024;
+inline float key_score(unsigned k) {
+  const unsigned u = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
+  float f;
+  __builtin_memcpy(&f, &u, 4);
+  return f;
+}
+// one histogram pass of the EER over the local data (eer.hip): bits [shift, shift + nbits) of the keys whose higher bits equal
+// `prefix` (has_prefix = 0: every key) -> hh[2][EER_BINS] on the host, class 0 = non-target; dhist: 2 * EER_BINS * 8 device bytes
+int eer_pass(plda_handle *h, const EerSource &src, int shift, int nbits, unsigned prefix, int has_prefix,
+             unsigned long long *dhist, unsigned *dbelow, unsigned *dabove, std::vector<unsigned long long> &hh);
+
 #ifdef __HIPCC__
+__device__ __forceinline__ unsigned score_key(float f) {
+  unsigned u = __float_as_uint(f);
+  if (u == 0x80000000u) u = 0u;      // -0.0 == +0.0 as scores: one candidate threshold, not two
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);   // monotone: a < b  <=>  key(a) < key(b)
+}
 // fp64 wave-wide sum through DPP: quad butterflies, then half-row and row mirrors (every
 // lane of a 16-lane row then holds the row sum), then four readlanes.  ~6x shorter
 // dependency chain than __shfl_xor, which lowers to ds_bpermute for 64-bit values.

@@ -28,19 +28,7 @@
 
 namespace plda {
 
-__device__ __forceinline__ unsigned score_key(float f) {
-  unsigned u = __float_as_uint(f);
-  if (u == 0x80000000u) u = 0u;      // -0.0 == +0.0 as scores: one candidate threshold, not two
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);   // monotone: a < b  <=>  key(a) < key(b)
-}
-static inline float key_score(unsigned k) {
-  const unsigned u = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
-  float f;
-  std::memcpy(&f, &u, 4);
-  return f;
-}
-
-constexpr int EER_BINS = 2048;
+// (score_key / key_score / EER_BINS / EER_STRIP: common.hpp, shared with dcf.hip)
 
 // one pass: class c (0 = impostor, 1 = target) histogram of bits [shift, shift + nbits) of the
 // keys whose higher bits equal `prefix` (pass 0: every key).  below/above track the largest
@@ -91,7 +79,6 @@ __global__ __launch_bounds__(256) void eer_hist_kernel(const float *__restrict__
 // (Workgroups walking along rows re-read the 8-byte speaker id of every column for every row: 12 B of cache
 // traffic per trial, 39.4 ms for the three passes over 1e10 trials against 20.4 ms here, identical results:
 // profiles/r02_eer_probe.json.)  Four rows are loaded before they are accounted for.
-constexpr int EER_STRIP = 1024;
 __global__ __launch_bounds__(256) void eer_hist_strip_kernel(const float *__restrict__ scores, int64_t ld, int64_t M,
                                                              int64_t Nt, const int64_t *__restrict__ espk,
                                                              const int64_t *__restrict__ tspk, int64_t rows_per_wg,
@@ -262,8 +249,9 @@ __global__ __launch_bounds__(256) void eer_window_strip_kernel(const float *__re
 
 // (EerSource / EerSlabs, the data a reduction over labelled trials consumes: common.hpp, shared with calib.hip)
 
-// One histogram pass over the local data -> hh (host).  No reduction here: see eer_device.
-static int eer_pass(plda_handle *h, const EerSource &src, int shift, int nbits, unsigned prefix, int has_prefix,
+// One histogram pass over the local data -> hh (host).  No reduction here: see eer_device.  (Declared in common.hpp: dcf.hip's
+// level 0 is this pass.)
+int eer_pass(plda_handle *h, const EerSource &src, int shift, int nbits, unsigned prefix, int has_prefix,
                     unsigned long long *dhist, unsigned *dbelow, unsigned *dabove, std::vector<unsigned long long> &hh) {
   PLDA_HIP(h, hipMemsetAsync(dhist, 0, 2 * EER_BINS * 8, h->stream));
   if (src.slabs) {

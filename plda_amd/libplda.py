@@ -614,6 +614,59 @@ class MPlda(object):
         CB.apply_dev(self, S.data_ptr(), S.shape[1], S.shape[0], S.shape[1], cal)
         self.synchronize()
 
+    def _labelled_trials(self, enrol, test, test_speaker, what):
+        """(enrol ids, counts, U, V, int64 speaker of every test entry) of the labelled trials between two transform()
+        results: the argument handling `calibrate` and `min_dcf` share."""
+        ids, counts, U = self._unpack(enrol)
+        tids, _, V = self._unpack(test)
+        m, nt = U.shape[0], V.shape[0]
+        if ids is None:
+            raise ValueError("%s: the enrol side needs its speaker ids (a transform() result or (counts, vecs, ids))" % what)
+        if hasattr(test_speaker, "keys"):
+            if tids is None:
+                raise ValueError("%s: a test_speaker mapping needs test keys" % what)
+            tspk = np.array([int(test_speaker[int(k)]) for k in tids], np.int64)
+        else:
+            tspk = np.ascontiguousarray(test_speaker, np.int64).reshape(-1)
+        if tspk.shape[0] != nt:
+            raise ValueError("%s: test_speaker must name the speaker of each of the %d test entries" % (what, nt))
+        if m == 0 or nt == 0:
+            raise ValueError("%s: no trials" % what)
+        return ids, counts, U, V, tspk
+
+    def min_dcf(self, enrol, test, test_speaker, points=((0.01, 1.0, 1.0),), znorm=True, cohort=None, top_k=None, calibrate=False):
+        """The exact minimum detection cost of the trials between two transform() results at the operating points
+        `points` = ((prior, c_miss, c_fa), ...), at most 8 (include/plda_hip.h, "exact minimum detection cost").  Arguments
+        as `calibrate`; the scores are those of score_matrix (znorm) or, with a cohort, score_matrix_asnorm, and with
+        calibrate=True they are mapped with the stored calibration first.  Without a cohort and without the map the matrix
+        is never held (the trials are re-scored slab by slab once per read); otherwise it is.  Returns (one dict per point:
+        min_dcf, threshold, far, frr, miss, fa; the call's info dict).  The calibration loss at a point is
+        `calibration.act_dcf(...) - min_dcf`."""
+        from . import dcf as DC
+        cal = self._stored_calibration(calibrate)
+        ids, counts, U, V, tspk = self._labelled_trials(enrol, test, test_speaker, "min_dcf")
+        m, nt = U.shape[0], V.shape[0]
+        despk, dtspk = self._to_device(np.ascontiguousarray(ids, np.int64)), self._to_device(tspk)
+        if cohort is None and cal is None:
+            zm, zs = self._zn_arrays(ids, znorm)
+            uniform = int(counts[0]) if np.all(counts == counts[0]) else 0
+            dU, dV = self._to_device(U), self._to_device(V)
+            dn = None if uniform else self._to_device(counts)
+            dzm, dzs = (self._to_device(zm), self._to_device(zs)) if zm is not None else (None, None)
+            ptr = lambda t: t.data_ptr() if t is not None else None      # noqa: E731
+            return DC.min_dcf_from_operands_dev(self, dU.data_ptr(), ptr(dn), uniform, m, dV.data_ptr(), nt, despk.data_ptr(),
+                                                dtspk.data_ptr(), ptr(dzm), ptr(dzs), points=points)
+        if cohort is None:
+            S = self._trials_matrix_on_device(counts, U, V, zn=self._zn_arrays(ids, znorm))
+        else:
+            Cv = self._cohort_rows(cohort)
+            em, es = self._cohort_stats(counts, U, Cv, top_k)
+            tm, ts = self._cohort_stats(np.ones(nt, np.int32), V, Cv, top_k)
+            S = self._trials_matrix_on_device(counts, U, V, sn=(em, es, tm, ts))
+        if cal is not None:
+            self._affine_map_on_device(S, cal)
+        return DC.min_dcf_from_matrix_dev(self, S.data_ptr(), nt, m, nt, despk.data_ptr(), dtspk.data_ptr(), points=points)
+
     def calibrate(self, enrol, test, test_speaker, prior=0.5, znorm=True, cohort=None, top_k=None):
         """Fit the linear calibration llr = a * score + b (prior-weighted logistic regression, include/plda_hip.h) on the
         trials between two transform() results and store it.  The enrol keys are the model speakers; `test_speaker` gives
@@ -622,21 +675,8 @@ class MPlda(object):
         cohort the matrix is never held (the trials are re-scored slab by slab once per pass); with one it is.  Returns the
         `plda_amd.calibration.Calibration`; a separable or unconverged fit raises a RuntimeWarning."""
         from . import calibration as CB
-        ids, counts, U = self._unpack(enrol)
-        tids, _, V = self._unpack(test)
+        ids, counts, U, V, tspk = self._labelled_trials(enrol, test, test_speaker, "calibrate")
         m, nt = U.shape[0], V.shape[0]
-        if ids is None:
-            raise ValueError("calibrate: the enrol side needs its speaker ids (a transform() result or (counts, vecs, ids))")
-        if hasattr(test_speaker, "keys"):
-            if tids is None:
-                raise ValueError("calibrate: a test_speaker mapping needs test keys")
-            tspk = np.array([int(test_speaker[int(k)]) for k in tids], np.int64)
-        else:
-            tspk = np.ascontiguousarray(test_speaker, np.int64).reshape(-1)
-        if tspk.shape[0] != nt:
-            raise ValueError("calibrate: test_speaker must name the speaker of each of the %d test entries" % nt)
-        if m == 0 or nt == 0:
-            raise ValueError("calibrate: no trials")
         despk, dtspk = self._to_device(np.ascontiguousarray(ids, np.int64)), self._to_device(tspk)
         if cohort is None:
             zm, zs = self._zn_arrays(ids, znorm)

@@ -322,3 +322,17 @@ def eer_sharded(engine, scores_local, enrol_spk_local, test_spk):
     m, nt = scores_local.shape
     return engine.eer_matrix_comm_dev(scores_local.data_ptr() if m else 0, nt, m, nt,
                                       enrol_spk_local.data_ptr() if m else 0, test_spk.data_ptr())
+
+
+def min_dcf_sharded(engine, scores_local, enrol_spk_local, test_spk, points=((0.01, 1.0, 1.0),)):
+    """Exact minimum detection cost of a ROW-SHARDED trials matrix without gathering it (arguments as `eer_sharded`):
+    every histogram of the refinement is summed over the ranks by the handle's collectives, the surviving bins are
+    decided identically on every rank, the compact lists stay local.  Identical (results, info) on every rank; a rank may
+    own no row."""
+    from . import dcf
+    dev = test_spk.device
+    _on_torch_stream(engine, dev)
+    scores_local = scores_local.contiguous()
+    m, nt = scores_local.shape
+    return dcf.min_dcf_from_matrix_comm_dev(engine, scores_local.data_ptr() if m else 0, nt, m, nt,
+                                            enrol_spk_local.data_ptr() if m else 0, test_spk.data_ptr(), points=points)
