@@ -1,7 +1,7 @@
 // plda_amd/csrc/api.hip -- the C ABI of libplda_hip.so (include/plda_hip.h).
 // Host-pointer entry points stage through device buffers owned by the handle and
 // call the *_device implementations; nothing here computes on the CPU.
-#include "common.hpp"
+#include "trial_source.hpp"
 #include "hostio.hpp"
 
 #include <mutex>
@@ -65,48 +65,7 @@ int group_by_label_device(plda_handle *h, const uint64_t *dlabels, int64_t N, ui
                           uint64_t **uniq_out, int64_t *G_out);
 int group_centroids_device(plda_handle *h, const double *dX, int64_t N, int D, const uint32_t *perm, const int *offsets,
                            int64_t G, double *dmeans, int32_t *dcounts32);
-int eer_matrix_device(plda_handle *h, const float *dscores, int64_t ld, int64_t M, int64_t Nt, const int64_t *despk,
-                      const int64_t *dtspk, double *out,
-                      int (*reduce)(void *, unsigned long long *, unsigned *, unsigned *) = nullptr, void *ctx = nullptr);
-int eer_lists_device(plda_handle *h, const float *dpos, int64_t np, const float *dneg, int64_t nn, double *out);
-int det_matrix_device(plda_handle *h, const float *dscores, int64_t ld, int64_t M, int64_t Nt, const int64_t *despk, const int64_t *dtspk,
-                      int npoints, double *far, double *frr, double *thresholds);
-int det_lists_device(plda_handle *h, const float *dpos, int64_t np, const float *dneg, int64_t nn, int npoints, double *far, double *frr,
-                     double *thresholds);
-// dcf.hip
-int min_dcf_step(int level, int64_t n_nodes, const plda_min_dcf_node *nodes, const uint64_t *hist, int n_points,
-                 const plda_dcf_point *pts, plda_min_dcf_state *st, int64_t cap_next, plda_min_dcf_node *next, int64_t *n_next);
-int min_dcf_finish(const plda_min_dcf_state *st, int n_points, const plda_dcf_point *pts, const uint32_t *below, const uint32_t *above,
-                   plda_min_dcf *out);
-int min_dcf_matrix_device(plda_handle *h, const float *dscores, int64_t ld, int64_t M, int64_t Nt, const int64_t *despk,
-                          const int64_t *dtspk, int n_points, const plda_dcf_point *pts, plda_min_dcf *out, plda_min_dcf_info *info,
-                          int (*reduce)(void *, unsigned long long *, unsigned *, unsigned *), void *ctx);
-int min_dcf_lists_device(plda_handle *h, const float *dpos, int64_t np, const float *dneg, int64_t nn, int n_points,
-                         const plda_dcf_point *pts, plda_min_dcf *out, plda_min_dcf_info *info);
-int score_min_dcf_device(plda_handle *h, const double *dU, const int32_t *dn, int n_uniform, int64_t M, const double *dV, int64_t Nt,
-                         const double *dzmean, const double *dzstd, const int64_t *despk, const int64_t *dtspk, int n_points,
-                         const plda_dcf_point *pts, plda_min_dcf *out, plda_min_dcf_info *info);
-int min_dcf_matrix_comm_device(plda_handle *h, const float *dscores, int64_t ld, int64_t M, int64_t Nt, const int64_t *despk,
-                               const int64_t *dtspk, int n_points, const plda_dcf_point *pts, plda_min_dcf *out, plda_min_dcf_info *info);
-// calib.hip
-int calib_pass_matrix_device(plda_handle *h, const float *dscores, int64_t ld, int64_t M, int64_t Nt, const int64_t *despk,
-                             const int64_t *dtspk, double a, double c, double theta, plda_calib_record *out);
-int calib_fit_matrix_device(plda_handle *h, const float *dscores, int64_t ld, int64_t M, int64_t Nt, const int64_t *despk,
-                            const int64_t *dtspk, double prior, double tol, int max_iter, plda_calib_fit *out);
-int calib_pass_lists_device(plda_handle *h, const float *dpos, int64_t np, const float *dneg, int64_t nn, double a, double c,
-                            double theta, plda_calib_record *out);
-int calib_fit_lists_device(plda_handle *h, const float *dpos, int64_t np, const float *dneg, int64_t nn, double prior, double tol,
-                           int max_iter, plda_calib_fit *out);
-int score_calib_pass_device(plda_handle *h, const double *dU, const int32_t *dn, int n_uniform, int64_t M, const double *dV, int64_t Nt,
-                            const double *dzmean, const double *dzstd, const int64_t *despk, const int64_t *dtspk, double a, double c,
-                            double theta, plda_calib_record *out);
-int score_calib_fit_device(plda_handle *h, const double *dU, const int32_t *dn, int n_uniform, int64_t M, const double *dV, int64_t Nt,
-                           const double *dzmean, const double *dzstd, const int64_t *despk, const int64_t *dtspk, double prior,
-                           double tol, int max_iter, plda_calib_fit *out);
-int affine_map_device(plda_handle *h, const float *dscores, int64_t ld, int64_t M, int64_t Nt, double a, double b, float *dout,
-                      int64_t ld_out);
-int score_eer_device(plda_handle *h, const double *dU, const int32_t *dn, int n_uniform, int64_t M, const double *dV, int64_t Nt,
-                     const double *dzmean, const double *dzstd, const int64_t *despk, const int64_t *dtspk, double *out);
+// (the EER / DET / minDCF / calibration entry points, eer.hip, dcf.hip, calib.hip and their sharded forms: trial_source.hpp)
 // comm.hip
 int comm_init(plda_handle *h, int nranks, int rank, const void *uid);
 int comm_init_custom(plda_handle *h, int nranks, int rank, const plda_collectives *t);
@@ -123,8 +82,6 @@ int znorm_stats_sharded_device(plda_handle *h, const double *dbkg, int64_t Nb, i
 int fit_sharded_device(plda_handle *h, const double *dX, int64_t N, int D, const uint64_t *dlabels, int64_t K, int iters);
 int cohort_stats_sharded_device(plda_handle *h, const double *dX, const int32_t *dn, int n_uniform, int64_t Rows, const double *dC,
                                 int64_t Nc, int64_t top_k, double *dmean, double *dstd);
-int eer_matrix_comm_device(plda_handle *h, const float *dscores, int64_t ld, int64_t M, int64_t Nt, const int64_t *despk,
-                           const int64_t *dtspk, double *out);
 
 // the pinned ring + copy threads of the host-pointer entry points (hostio.hip), created on first use
 static int host_pipe(plda_handle *h, HostPipe **out) {
@@ -213,6 +170,22 @@ template <typename F> int guarded(plda_handle *h, const char *fn, F &&body) noex
   catch (const std::bad_alloc &) { return fail_quiet(h, PLDA_E_HIP, fn, "out of host memory"); }
   catch (const std::exception &e) { return fail_quiet(h, PLDA_E_HIP, fn, e.what()); }
   catch (...) { return fail_quiet(h, PLDA_E_HIP, fn, "unknown C++ exception"); }
+}
+// The host-list entry points (two lists of scores in caller memory): the argument check with the caller's message, both
+// lists uploaded, then body(device targets, device non-targets).
+template <typename F>
+int with_host_lists(plda_handle *h, const char *fn, const float *pos, int64_t np, const float *neg, int64_t nn, bool outputs_ok,
+                    const char *refusal, F &&body) noexcept {
+  return guarded(h, fn, [&]() -> int {
+    if (!h) return PLDA_E_INVAL;
+    PLDA_LOCK(h);
+    if (!pos || !neg || !outputs_ok || np <= 0 || nn <= 0) return fail(h, PLDA_E_INVAL, "%s", refusal);
+    PLDA_TRY(set_device(h));
+    Tmp dP, dN;
+    PLDA_TRY(upload(h, dP, pos, (size_t)np * 4));
+    PLDA_TRY(upload(h, dN, neg, (size_t)nn * 4));
+    return body(dP.as<float>(), dN.as<float>());
+  });
 }
 }  // namespace
 
@@ -1725,33 +1698,17 @@ int plda_det_matrix_dev(plda_handle *h, const float *dscores, int64_t ld, int64_
 
 int plda_det_lists(plda_handle *h, const float *pos, int64_t np, const float *neg, int64_t nn, int32_t n_points, double *far,
                    double *frr, double *thresholds) {
-  return guarded(h, "plda_det_lists", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
-    if (!pos || !neg || !far || !frr || np <= 0 || nn <= 0)
-      return fail(h, PLDA_E_INVAL, "det: need at least one target and one impostor score");
-    PLDA_TRY(set_device(h));
-    Tmp dP, dN;
-    PLDA_TRY(upload(h, dP, pos, (size_t)np * 4));
-    PLDA_TRY(upload(h, dN, neg, (size_t)nn * 4));
-    const int rc = det_lists_device(h, dP.as<float>(), np, dN.as<float>(), nn, n_points, far, frr, thresholds);
+  return with_host_lists(h, "plda_det_lists", pos, np, neg, nn, far && frr, "det: need at least one target and one impostor score",
+                         [&](const float *dpos, const float *dneg) -> int {
+    const int rc = det_lists_device(h, dpos, np, dneg, nn, n_points, far, frr, thresholds);
     PLDA_HIP(h, hipStreamSynchronize(h->stream));
     return rc;
   });
 }
 
 int plda_eer_lists(plda_handle *h, const float *pos, int64_t np, const float *neg, int64_t nn, double *out) {
-  return guarded(h, "plda_eer_lists", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
-    if (!pos || !neg || !out || np <= 0 || nn <= 0)
-      return fail(h, PLDA_E_INVAL, "eer: need at least one target and one impostor score");
-    PLDA_TRY(set_device(h));
-    Tmp dP, dN;
-    PLDA_TRY(upload(h, dP, pos, (size_t)np * 4));
-    PLDA_TRY(upload(h, dN, neg, (size_t)nn * 4));
-    return eer_lists_device(h, dP.as<float>(), np, dN.as<float>(), nn, out);
-  });
+  return with_host_lists(h, "plda_eer_lists", pos, np, neg, nn, out != nullptr, "eer: need at least one target and one impostor score",
+                         [&](const float *dpos, const float *dneg) { return eer_lists_device(h, dpos, np, dneg, nn, out); });
 }
 
 // ---------------------------------------------------------------- minimum detection cost (dcf.hip)
@@ -1780,17 +1737,8 @@ int plda_min_dcf_matrix_comm_dev(plda_handle *h, const float *dscores, int64_t l
 
 int plda_min_dcf_lists(plda_handle *h, const float *pos, int64_t np, const float *neg, int64_t nn, int32_t n_points,
                        const plda_dcf_point *points, plda_min_dcf *out, plda_min_dcf_info *info) {
-  return guarded(h, "plda_min_dcf_lists", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
-    if (!pos || !neg || !out || np <= 0 || nn <= 0)
-      return fail(h, PLDA_E_INVAL, "min_dcf: need at least one target and one non-target score");
-    PLDA_TRY(set_device(h));
-    Tmp dP, dN;
-    PLDA_TRY(upload(h, dP, pos, (size_t)np * 4));
-    PLDA_TRY(upload(h, dN, neg, (size_t)nn * 4));
-    return min_dcf_lists_device(h, dP.as<float>(), np, dN.as<float>(), nn, n_points, points, out, info);
-  });
+  return with_host_lists(h, "plda_min_dcf_lists", pos, np, neg, nn, out != nullptr, "min_dcf: need at least one target and one non-target score",
+                         [&](const float *dpos, const float *dneg) { return min_dcf_lists_device(h, dpos, np, dneg, nn, n_points, points, out, info); });
 }
 
 int plda_score_min_dcf_dev(plda_handle *h, const double *dU, const int32_t *dn_enrol, int32_t n_uniform, int64_t M, const double *dV,
@@ -1838,32 +1786,14 @@ int plda_calib_fit_matrix_dev(plda_handle *h, const float *dscores, int64_t ld, 
 
 int plda_calib_pass_lists(plda_handle *h, const float *pos, int64_t np, const float *neg, int64_t nn, double a, double c,
                           double theta, plda_calib_record *out_record) {
-  return guarded(h, "plda_calib_pass_lists", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
-    if (!pos || !neg || !out_record || np <= 0 || nn <= 0)
-      return fail(h, PLDA_E_INVAL, "calib_pass: need at least one target and one non-target score");
-    PLDA_TRY(set_device(h));
-    Tmp dP, dN;
-    PLDA_TRY(upload(h, dP, pos, (size_t)np * 4));
-    PLDA_TRY(upload(h, dN, neg, (size_t)nn * 4));
-    return calib_pass_lists_device(h, dP.as<float>(), np, dN.as<float>(), nn, a, c, theta, out_record);
-  });
+  return with_host_lists(h, "plda_calib_pass_lists", pos, np, neg, nn, out_record != nullptr, "calib_pass: need at least one target and one non-target score",
+                         [&](const float *dpos, const float *dneg) { return calib_pass_lists_device(h, dpos, np, dneg, nn, a, c, theta, out_record); });
 }
 
 int plda_calib_fit_lists(plda_handle *h, const float *pos, int64_t np, const float *neg, int64_t nn, double prior, double tol,
                          int32_t max_iter, plda_calib_fit *out_fit) {
-  return guarded(h, "plda_calib_fit_lists", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
-    if (!pos || !neg || !out_fit || np <= 0 || nn <= 0)
-      return fail(h, PLDA_E_INVAL, "calib_fit: need at least one target and one non-target score");
-    PLDA_TRY(set_device(h));
-    Tmp dP, dN;
-    PLDA_TRY(upload(h, dP, pos, (size_t)np * 4));
-    PLDA_TRY(upload(h, dN, neg, (size_t)nn * 4));
-    return calib_fit_lists_device(h, dP.as<float>(), np, dN.as<float>(), nn, prior, tol, max_iter, out_fit);
-  });
+  return with_host_lists(h, "plda_calib_fit_lists", pos, np, neg, nn, out_fit != nullptr, "calib_fit: need at least one target and one non-target score",
+                         [&](const float *dpos, const float *dneg) { return calib_fit_lists_device(h, dpos, np, dneg, nn, prior, tol, max_iter, out_fit); });
 }
 
 int plda_score_calib_pass_dev(plda_handle *h, const double *dU, const int32_t *dn_enrol, int32_t n_uniform, int64_t M,

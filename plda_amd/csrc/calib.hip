@@ -8,9 +8,8 @@
 // prior-weighted logistic regression, Cllr and actDCF are all read off that record on the host, so the damped Newton fit is a
 // host loop over "take a pass" and every source -- matrix, two lists, operands scored slab by slab -- shares it.
 //
-// Sources: the EerSource / EerSlabs abstraction and the slab set-up of plda_score_eer_dev (score_eer_slabs_setup,
-// score_eer_produce) are REUSED, not copied: their declarations moved unchanged from eer.hip to common.hpp, and the set-up
-// lines of score_eer_device became the function both callers use.  This file is its own translation unit.
+// Sources: a pass consumes a TrialSource through for_each_piece (trial_source.hpp), as the EER and minDCF passes do; the
+// operand forms get theirs from operand_source (operand_slabs.hip).  This file is its own translation unit.
 //
 // Kernels.  calib_pass_strip_kernel walks the matrix exactly as eer_hist_strip_kernel does (eer.hip: a workgroup owns 1024
 // columns, 4 per thread with their speaker ids in registers, and a slice of the rows; 16-byte loads where ld and the base
@@ -39,11 +38,10 @@
 // passes.  tol: the host model's lambda2 floor on Gaussian score sets of 3e3 .. 1e6 trials, scaled and shifted, is 1e-26 ..
 // 1e-33 (the sequence ends ... 1e-10, 1e-18, 1e-33: quadratic), so the default 1e-18 is above the floor by eight orders and
 // was kept.
-#include "common.hpp"
+#include "trial_source.hpp"
 
 #include <algorithm>
 #include <cmath>
-#include <functional>
 
 namespace plda {
 
@@ -240,43 +238,25 @@ static int64_t list_blocks(int64_t n) { return std::min<int64_t>(ceil_div(n, 256
 
 // One pass over `src` -> *rec (host); synchronises the stream.  A non-finite score, or a class without trials, is
 // PLDA_E_INVAL (the record is written all the same).
-static int calib_pass(plda_handle *h, const EerSource &src, double a, double c, double theta, plda_calib_record *rec) {
-  int64_t total = 0, rpw = 0;
-  if (src.slabs) {
-    for (int64_t r0 = 0; r0 < src.M; r0 += src.slabs->slab_rows) total += strip_blocks(std::min(src.slabs->slab_rows, src.M - r0), src.Nt, &rpw);
-  } else if (src.scores) {
-    total = strip_blocks(src.M, src.Nt, &rpw);
-  } else {
-    total = list_blocks(src.np) + list_blocks(src.nn);
-  }
+static int calib_pass(plda_handle *h, const TrialSource &src, double a, double c, double theta, plda_calib_record *rec) {
+  int64_t rpw = 0;
+  auto blocks_of = [&](const TrialPiece &pc) { return pc.cls < 0 ? strip_blocks(pc.rows, pc.Nt, &rpw) : list_blocks(pc.Nt); };
+  // the partials of every piece, in the order of the walk: sized from the extents before anything is launched
+  int64_t total = 0, at = 0;
+  PLDA_TRY(for_each_piece(src, [&](const TrialPiece &pc) -> int { total += blocks_of(pc); return PLDA_OK; }, /*produce=*/false));
   if (total > (int64_t)0x7fffffff) return fail(h, PLDA_E_CAPACITY, "calib: too many column strips");
   PLDA_HIP(h, h->calib_part.reserve((size_t)(total + 1) * sizeof(plda_calib_record)));
   plda_calib_record *part = h->calib_part.as<plda_calib_record>();
-  int64_t at = 0;
-  if (src.slabs) {
-    for (int64_t r0 = 0; r0 < src.M; r0 += src.slabs->slab_rows) {
-      const int64_t rows = std::min(src.slabs->slab_rows, src.M - r0);
-      const float *sc = nullptr;
-      int64_t ld = 0;
-      PLDA_TRY(src.slabs->produce(src.slabs->ctx, r0, rows, &sc, &ld));
-      const int64_t blocks = strip_blocks(rows, src.Nt, &rpw);
-      calib_pass_strip_kernel<<<(unsigned)blocks, 256, 0, h->stream>>>(sc, ld, rows, src.Nt, src.espk + r0, src.tspk, rpw, a, c, theta, part + at);
-      PLDA_LAUNCH_CHECK(h);
-      at += blocks;
-    }
-  } else if (src.scores) {
-    const int64_t blocks = strip_blocks(src.M, src.Nt, &rpw);
-    calib_pass_strip_kernel<<<(unsigned)blocks, 256, 0, h->stream>>>(src.scores, src.ld, src.M, src.Nt, src.espk, src.tspk, rpw, a, c, theta, part);
-    at = blocks;
-  } else {
-    for (int cl = 0; cl < 2; ++cl) {
-      const float *p = cl ? src.pos : src.neg;
-      const int64_t n = cl ? src.np : src.nn;
-      const int64_t blocks = list_blocks(n);
-      if (blocks) calib_pass_list_kernel<<<(unsigned)blocks, 256, 0, h->stream>>>(p, n, cl, a, c, theta, part + at);
-      at += blocks;
-    }
-  }
+  PLDA_TRY(for_each_piece(src, [&](const TrialPiece &pc) -> int {
+    const int64_t blocks = blocks_of(pc);
+    if (pc.cls < 0)
+      calib_pass_strip_kernel<<<(unsigned)blocks, 256, 0, h->stream>>>(pc.scores, pc.ld, pc.rows, pc.Nt, pc.espk, src.tspk, rpw, a, c, theta, part + at);
+    else
+      calib_pass_list_kernel<<<(unsigned)blocks, 256, 0, h->stream>>>(pc.scores, pc.Nt, pc.cls, a, c, theta, part + at);
+    PLDA_LAUNCH_CHECK(h);
+    at += blocks;
+    return PLDA_OK;
+  }));
   calib_reduce_kernel<<<1, 256, 0, h->stream>>>(part, at, part + total);
   PLDA_LAUNCH_CHECK(h);
   PLDA_HIP(h, hipMemcpyAsync(rec, part + total, sizeof(*rec), hipMemcpyDeviceToHost, h->stream));
@@ -311,15 +291,14 @@ static bool calib_solve(const CalibModel &m, double d[2], double *lambda2) {
   return true;
 }
 
-typedef std::function<int(double a, double c, plda_calib_record *rec)> CalibTake;
-
-static int calib_fit(plda_handle *h, const CalibTake &take, double prior, double tol, int max_iter, plda_calib_fit *out) {
+static int calib_fit(plda_handle *h, const TrialSource &src, double prior, double tol, int max_iter, plda_calib_fit *out) {
   if (!out || !(prior > 0.0 && prior < 1.0) || !(tol >= 0.0)) return fail(h, PLDA_E_INVAL, "calib_fit: bad argument (prior must lie inside (0, 1), tol >= 0)");
   if (tol == 0.0) tol = 1e-18;
   if (max_iter <= 0) max_iter = 100;
   const double tau = std::log(prior / (1.0 - prior)), ln2 = std::log(2.0);
   plda_calib_record before, rec, trial;
   int passes = 0;
+  auto take = [&](double a, double c, plda_calib_record *rec) { return calib_pass(h, src, a, c, 0.0, rec); };
   PLDA_TRY(take(1.0, 0.0, &before)); ++passes;
   if (std::min(before.min_t, before.min_n) == std::max(before.max_t, before.max_n))
     return fail(h, PLDA_E_INVAL, "calib_fit: all scores are equal (the Hessian is singular)");
@@ -362,57 +341,40 @@ static bool matrix_args_ok(const float *dscores, int64_t ld, int64_t M, int64_t 
 int calib_pass_matrix_device(plda_handle *h, const float *dscores, int64_t ld, int64_t M, int64_t Nt, const int64_t *despk,
                              const int64_t *dtspk, double a, double c, double theta, plda_calib_record *out) {
   if (!out || !matrix_args_ok(dscores, ld, M, Nt, despk, dtspk)) return fail(h, PLDA_E_INVAL, "calib_pass: bad argument");
-  const EerSource s{dscores, ld, M, Nt, despk, dtspk, nullptr, 0, nullptr, 0};
-  return calib_pass(h, s, a, c, theta, out);
+  return calib_pass(h, TrialSource::matrix(dscores, ld, M, Nt, despk, dtspk), a, c, theta, out);
 }
 int calib_fit_matrix_device(plda_handle *h, const float *dscores, int64_t ld, int64_t M, int64_t Nt, const int64_t *despk,
                             const int64_t *dtspk, double prior, double tol, int max_iter, plda_calib_fit *out) {
   if (!out || !matrix_args_ok(dscores, ld, M, Nt, despk, dtspk)) return fail(h, PLDA_E_INVAL, "calib_fit: bad argument");
-  const EerSource s{dscores, ld, M, Nt, despk, dtspk, nullptr, 0, nullptr, 0};
-  return calib_fit(h, [&](double a, double c, plda_calib_record *r) { return calib_pass(h, s, a, c, 0.0, r); }, prior, tol, max_iter, out);
+  return calib_fit(h, TrialSource::matrix(dscores, ld, M, Nt, despk, dtspk), prior, tol, max_iter, out);
 }
 int calib_pass_lists_device(plda_handle *h, const float *dpos, int64_t np, const float *dneg, int64_t nn, double a, double c,
                             double theta, plda_calib_record *out) {
   if (!dpos || !dneg || !out || np <= 0 || nn <= 0) return fail(h, PLDA_E_INVAL, "calib_pass: need at least one target and one non-target score");
-  const EerSource s{nullptr, 0, 0, 0, nullptr, nullptr, dpos, np, dneg, nn};
-  return calib_pass(h, s, a, c, theta, out);
+  return calib_pass(h, TrialSource::lists(dpos, np, dneg, nn), a, c, theta, out);
 }
 int calib_fit_lists_device(plda_handle *h, const float *dpos, int64_t np, const float *dneg, int64_t nn, double prior, double tol,
                            int max_iter, plda_calib_fit *out) {
   if (!dpos || !dneg || !out || np <= 0 || nn <= 0) return fail(h, PLDA_E_INVAL, "calib_fit: need at least one target and one non-target score");
-  const EerSource s{nullptr, 0, 0, 0, nullptr, nullptr, dpos, np, dneg, nn};
-  return calib_fit(h, [&](double a, double c, plda_calib_record *r) { return calib_pass(h, s, a, c, 0.0, r); }, prior, tol, max_iter, out);
+  return calib_fit(h, TrialSource::lists(dpos, np, dneg, nn), prior, tol, max_iter, out);
 }
 
-// the operand forms: the slabs are re-scored once per pass (score_eer_produce), consumed and dropped
-static int score_calib_args(plda_handle *h, const double *dU, const int32_t *dn, int n_uniform, int64_t M, const double *dV, int64_t Nt,
-                            const int64_t *despk, const int64_t *dtspk, const void *out) {
-  if (!h->fitted) return fail(h, PLDA_E_NOT_FITTED, "score_calib: model not fitted");
-  if (!dU || !dV || !despk || !dtspk || !out || M <= 0 || Nt <= 0) return fail(h, PLDA_E_INVAL, "score_calib: bad argument");
-  if (!dn && n_uniform <= 0) return fail(h, PLDA_E_INVAL, "score_calib: n_uniform must be > 0 when n_enrol is NULL");
-  return PLDA_OK;
-}
+// the operand forms: the slabs are re-scored once per pass (operand_slabs.hip), consumed and dropped
 int score_calib_pass_device(plda_handle *h, const double *dU, const int32_t *dn, int n_uniform, int64_t M, const double *dV, int64_t Nt,
                             const double *dzmean, const double *dzstd, const int64_t *despk, const int64_t *dtspk, double a, double c,
                             double theta, plda_calib_record *out) {
-  PLDA_TRY(score_calib_args(h, dU, dn, n_uniform, M, dV, Nt, despk, dtspk, out));
-  ScoreEerCtx ctx;
-  EerSlabs sl;
-  PLDA_TRY(score_eer_slabs_setup(h, dU, dn, n_uniform, M, dV, Nt, dzmean, dzstd, despk, &ctx, &sl));
-  EerSource s{nullptr, Nt, M, Nt, despk, dtspk, nullptr, 0, nullptr, 0};
-  s.slabs = &sl;
+  OperandSlabs os;
+  TrialSource s;
+  PLDA_TRY(operand_source(h, "score_calib", dU, dn, n_uniform, M, dV, Nt, dzmean, dzstd, despk, dtspk, out, &os, &s));
   return calib_pass(h, s, a, c, theta, out);
 }
 int score_calib_fit_device(plda_handle *h, const double *dU, const int32_t *dn, int n_uniform, int64_t M, const double *dV, int64_t Nt,
                            const double *dzmean, const double *dzstd, const int64_t *despk, const int64_t *dtspk, double prior,
                            double tol, int max_iter, plda_calib_fit *out) {
-  PLDA_TRY(score_calib_args(h, dU, dn, n_uniform, M, dV, Nt, despk, dtspk, out));
-  ScoreEerCtx ctx;
-  EerSlabs sl;
-  PLDA_TRY(score_eer_slabs_setup(h, dU, dn, n_uniform, M, dV, Nt, dzmean, dzstd, despk, &ctx, &sl));
-  EerSource s{nullptr, Nt, M, Nt, despk, dtspk, nullptr, 0, nullptr, 0};
-  s.slabs = &sl;
-  return calib_fit(h, [&](double a, double c, plda_calib_record *r) { return calib_pass(h, s, a, c, 0.0, r); }, prior, tol, max_iter, out);
+  OperandSlabs os;
+  TrialSource s;
+  PLDA_TRY(operand_source(h, "score_calib", dU, dn, n_uniform, M, dV, Nt, dzmean, dzstd, despk, dtspk, out, &os, &s));
+  return calib_fit(h, s, prior, tol, max_iter, out);
 }
 
 int affine_map_device(plda_handle *h, const float *dscores, int64_t ld, int64_t M, int64_t Nt, double a, double b, float *dout,

@@ -23,7 +23,7 @@
 // a host-staged adapter over two caller-supplied host operations (MPI / gloo / anything; also what lets
 // several PROCESSES ON ONE GPU drive these very loops, events and offsets in the tests -- RCCL refuses two
 // ranks on one device), or a caller-supplied device-level table.
-#include "common.hpp"
+#include "trial_source.hpp"
 
 #include <rccl/rccl.h>   // types and prototypes only; the functions are resolved with dlsym
 
@@ -39,9 +39,6 @@ namespace plda {
 
 int znorm_stats_device(plda_handle *h, const double *dbkg, int64_t Nb, int num_examples, int Din,
                        const double *dmodels, int64_t M, double *dmean, double *dstd);
-int eer_matrix_device(plda_handle *h, const float *dscores, int64_t ld, int64_t M, int64_t Nt, const int64_t *despk,
-                      const int64_t *dtspk, double *out,
-                      int (*reduce)(void *, unsigned long long *, unsigned *, unsigned *), void *ctx);
 
 // ------------------------------------------------------------------------------------ RCCL, resolved lazily
 namespace {
@@ -875,9 +872,6 @@ int eer_matrix_comm_device(plda_handle *h, const float *dscores, int64_t ld, int
 }
 
 // minDCF of a row-sharded matrix (dcf.hip): the same reduction, one call per [2][2048] block of counters
-int min_dcf_matrix_device(plda_handle *h, const float *dscores, int64_t ld, int64_t M, int64_t Nt, const int64_t *despk,
-                          const int64_t *dtspk, int n_points, const plda_dcf_point *pts, plda_min_dcf *out, plda_min_dcf_info *info,
-                          int (*reduce)(void *, unsigned long long *, unsigned *, unsigned *), void *ctx);
 int min_dcf_matrix_comm_device(plda_handle *h, const float *dscores, int64_t ld, int64_t M, int64_t Nt, const int64_t *despk,
                                const int64_t *dtspk, int n_points, const plda_dcf_point *pts, plda_min_dcf *out, plda_min_dcf_info *info) {
   EerCommCtx ctx{h};

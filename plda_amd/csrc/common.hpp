@@ -439,65 +439,9 @@ int score_matrix_snorm_device(plda_handle *h, const double *dU, const int32_t *d
                               int64_t Nt, const double *demean, const double *destd, const double *dtmean, const double *dtstd,
                               float *dout, int64_t ld, const CountSet *cs = nullptr, bool reuse_packed_B = false);
 
-// ---- eer.hip: what a reduction over labelled trials consumes (the EER passes; calib.hip's calibration pass) ----
-struct EerSource {
-  const float *scores; int64_t ld, M, Nt; const int64_t *espk, *tspk;   // matrix + labels, or
-  const float *pos; int64_t np; const float *neg; int64_t nn;            // two flat lists
-  // row-sharded matrix: after every local pass the caller's reduction makes the counts global
-  // (hist: sum over ranks; below: max; above: min).  nullptr = single process.
-  int (*reduce)(void *ctx, unsigned long long *hist, unsigned *below, unsigned *above) = nullptr;
-  void *ctx = nullptr;
-  int64_t row_step = 1;                        // matrix form: every row_step-th row only (the pilot's sample)
-  // windowed lists (the single-pass form): the lists hold the scores of a key window only; the counts below it and
-  // the class totals come from the full pass
-  bool windowed = false;
-  unsigned long long base_p = 0, base_n = 0, tot_p = 0, tot_n = 0;
-  // a matrix that exists one row slab at a time (plda_score_eer_dev: the scores are produced, consumed and dropped): `scores`
-  // is nullptr, M / Nt / espk / tspk describe the whole matrix
-  const struct EerSlabs *slabs = nullptr;
-};
-// produce: enqueue the scores of rows [r0, r0 + rows) (rows <= slab_rows) on the handle's stream, say where they are;
-// sample: the same for every step-th row of the matrix (<= slab_rows of them) together with THOSE rows' speaker ids
-struct EerSlabs {
-  int64_t slab_rows;
-  int (*produce)(void *ctx, int64_t r0, int64_t rows, const float **scores, int64_t *ld);
-  int (*sample)(void *ctx, int64_t step, const float **scores, int64_t *ld, const int64_t **espk, int64_t *rows);
-  void *ctx;
-};
-// the operand forms (plda_score_eer_dev, plda_score_calib_*_dev): the scores of a row slab are produced by the trials GEMM
-struct ScoreEerCtx {
-  plda_handle *h;
-  const double *dU; const int32_t *dn; int n_uniform; int64_t M; const double *dV; int64_t Nt;
-  const double *dzm, *dzs; const int64_t *despk;
-  CountSet cs; bool has_cs; bool packedB;
-  float *slab; int64_t slab_rows;
-};
-int score_eer_produce(void *ctx, int64_t r0, int64_t rows, const float **scores, int64_t *ld);
-int score_eer_sample(void *ctx, int64_t step, const float **scores, int64_t *ld, const int64_t **espk, int64_t *rows);
-int score_eer_slabs_setup(plda_handle *h, const double *dU, const int32_t *dn, int n_uniform, int64_t M, const double *dV, int64_t Nt,
-                          const double *dzmean, const double *dzstd, const int64_t *despk, ScoreEerCtx *c, EerSlabs *sl);
-
-// the order-preserving key of a score, its inverse, the histogram width and the strip width of the EER passes (moved unchanged
-// from eer.hip: dcf.hip refines the same key over the same three levels)
-constexpr int EER_BINS = 2048;
-constexpr int EER_STRIP = 1024;
-inline float key_score(unsigned k) {
-  const unsigned u = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
-  float f;
-  __builtin_memcpy(&f, &u, 4);
-  return f;
-}
-// one histogram pass of the EER over the local data (eer.hip): bits [shift, shift + nbits) of the keys whose higher bits equal
-// `prefix` (has_prefix = 0: every key) -> hh[2][EER_BINS] on the host, class 0 = non-target; dhist: 2 * EER_BINS * 8 device bytes
-int eer_pass(plda_handle *h, const EerSource &src, int shift, int nbits, unsigned prefix, int has_prefix,
-             unsigned long long *dhist, unsigned *dbelow, unsigned *dabove, std::vector<unsigned long long> &hh);
+// (the labelled-trials source of the EER / DET / calibration / minDCF reductions and their score key: trial_source.hpp)
 
 #ifdef __HIPCC__
-__device__ __forceinline__ unsigned score_key(float f) {
-  unsigned u = __float_as_uint(f);
-  if (u == 0x80000000u) u = 0u;      // -0.0 == +0.0 as scores: one candidate threshold, not two
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);   // monotone: a < b  <=>  key(a) < key(b)
-}
 // fp64 wave-wide sum through DPP: quad butterflies, then half-row and row mirrors (every
 // lane of a 16-lane row then holds the row sum), then four readlanes.  ~6x shorter
 // dependency chain than __shfl_xor, which lowers to ds_bpermute for 64-bit values.

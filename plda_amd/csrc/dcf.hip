@@ -7,7 +7,10 @@
 // (miss at its lower edge, fa at its upper edge) -- a bound with no tolerance, the expression being monotone in both counts
 // also after rounding -- does not exceed the incumbent.  The host step is plda_min_dcf_step (pure; below).
 //
-// Level 0 is the EER's full histogram (eer_pass, has_prefix = 0).  The new kernels:
+// Level 0 is the EER's full histogram (eer_pass, has_prefix = 0; trial_source.hpp).  Every pass reaches its kernels through
+// for_each_piece over a TrialSource (trial_source.hpp) with this file's own grid arithmetic per piece; the operand form's
+// source comes from operand_source (operand_slabs.hip); the sharded form's sums go through reduce_block_or_poison (eer.hip).
+// The new kernels:
 //  * dcf_multi_strip_kernel / dcf_multi_flat_kernel: ONE read of the scores refines up to DCF_S = 8 nodes.  The sorted node
 //    prefixes sit in LDS; a key outside [first, last] prefix is done after two compares, the others find their slot by three
 //    LDS compares; per slot and class a 2048-bin histogram in LDS (n slots x 16 KiB of dynamic LDS: 128 KiB at n = 8, and
@@ -20,7 +23,7 @@
 //    reduction, one atomic pair per wave and cut).
 // More than DCF_S survivors: further launches over the same level.  Every path ends with all surviving ranges resolved to
 // single keys: level 2's bins are keys.
-#include "common.hpp"
+#include "trial_source.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -354,28 +357,6 @@ int min_dcf_finish(const plda_min_dcf_state *st, int n_points, const plda_dcf_po
 // ------------------------------------------------------------------------------------ the device driver
 namespace {
 
-struct DcfPiece { const float *sc; int64_t ld, rows, Nt; const int64_t *espk; int cls; };   // cls < 0: labelled matrix rows
-
-// every piece of the local data in turn: the slabs as they are produced, the matrix, or the two lists
-template <class F>
-int dcf_for_pieces(const EerSource &src, F &&f) {
-  if (src.slabs) {
-    for (int64_t r0 = 0; r0 < src.M; r0 += src.slabs->slab_rows) {
-      const int64_t rows = std::min(src.slabs->slab_rows, src.M - r0);
-      const float *sc = nullptr;
-      int64_t ld = 0;
-      PLDA_TRY(src.slabs->produce(src.slabs->ctx, r0, rows, &sc, &ld));
-      PLDA_TRY(f(DcfPiece{sc, ld, rows, src.Nt, src.espk + r0, -1}));
-    }
-  } else if (src.scores) {
-    if (src.M > 0) PLDA_TRY(f(DcfPiece{src.scores, src.ld, src.M, src.Nt, src.espk, -1}));
-  } else {
-    if (src.nn > 0) PLDA_TRY(f(DcfPiece{src.neg, src.nn, 1, src.nn, nullptr, 0}));
-    if (src.np > 0) PLDA_TRY(f(DcfPiece{src.pos, src.np, 1, src.np, nullptr, 1}));
-  }
-  return PLDA_OK;
-}
-
 int dcf_lds_attr(plda_handle *h) {
   static DeviceOnce attr;
   if (attr.needed(h->device)) {
@@ -388,19 +369,19 @@ int dcf_lds_attr(plda_handle *h) {
 }
 
 // one read: the level's bits under pf.n prefixes -> hh[pf.n][2][EER_BINS] (host, local counts)
-int dcf_multi_pass(plda_handle *h, const EerSource &src, int level, const DcfPrefixes &pf, unsigned long long *dhist, unsigned long long *hh) {
+int dcf_multi_pass(plda_handle *h, const TrialSource &src, int level, const DcfPrefixes &pf, unsigned long long *dhist, unsigned long long *hh) {
   const size_t hb = (size_t)pf.n * 2 * EER_BINS * 8, lds = (size_t)pf.n * 2 * EER_BINS * 4 + DCF_S * 4;
   PLDA_HIP(h, hipMemsetAsync(dhist, 0, hb, h->stream));
-  PLDA_TRY(dcf_for_pieces(src, [&](const DcfPiece &pc) -> int {
+  PLDA_TRY(for_each_piece(src, [&](const TrialPiece &pc) -> int {
     if (pc.cls < 0) {
       const int64_t strips = ceil_div(pc.Nt, (int64_t)EER_STRIP);
       const int64_t slices = std::max<int64_t>(1, std::min<int64_t>(ceil_div(pc.rows, 16), 2048 / strips));
       const int64_t rows_per_wg = ceil_div(pc.rows, slices);
       dcf_multi_strip_kernel<<<(unsigned)(strips * ceil_div(pc.rows, rows_per_wg)), DCF_T, lds, h->stream>>>(
-          pc.sc, pc.ld, pc.rows, pc.Nt, pc.espk, src.tspk, rows_per_wg, DCF_SHIFT[level], DCF_BITS[level], pf, dhist);
+          pc.scores, pc.ld, pc.rows, pc.Nt, pc.espk, src.tspk, rows_per_wg, DCF_SHIFT[level], DCF_BITS[level], pf, dhist);
     } else {
       const unsigned grid = (unsigned)std::min<int64_t>(ceil_div(pc.Nt, (int64_t)DCF_T * 4), 1024);
-      dcf_multi_flat_kernel<<<grid, DCF_T, lds, h->stream>>>(pc.sc, pc.Nt, pc.cls, DCF_SHIFT[level], DCF_BITS[level], pf, dhist);
+      dcf_multi_flat_kernel<<<grid, DCF_T, lds, h->stream>>>(pc.scores, pc.Nt, pc.cls, DCF_SHIFT[level], DCF_BITS[level], pf, dhist);
     }
     PLDA_LAUNCH_CHECK(h);
     return PLDA_OK;
@@ -410,14 +391,14 @@ int dcf_multi_pass(plda_handle *h, const EerSource &src, int level, const DcfPre
   return PLDA_OK;
 }
 
-int dcf_neighbour_pass(plda_handle *h, const EerSource &src, const DcfEdges &ed, unsigned *dnb, unsigned *nb /*[2 P]*/) {
+int dcf_neighbour_pass(plda_handle *h, const TrialSource &src, const DcfEdges &ed, unsigned *dnb, unsigned *nb /*[2 P]*/) {
   unsigned init[2 * PLDA_MIN_DCF_MAX_POINTS];
   for (int p = 0; p < PLDA_MIN_DCF_MAX_POINTS; ++p) { init[2 * p] = 0u; init[2 * p + 1] = 0xffffffffu; }
   PLDA_HIP(h, hipMemcpyAsync(dnb, init, sizeof(init), hipMemcpyHostToDevice, h->stream));
   PLDA_HIP(h, hipStreamSynchronize(h->stream));          // (init is a stack array)
-  PLDA_TRY(dcf_for_pieces(src, [&](const DcfPiece &pc) -> int {
+  PLDA_TRY(for_each_piece(src, [&](const TrialPiece &pc) -> int {
     const int64_t total = pc.rows * pc.Nt;
-    dcf_neighbour_kernel<<<(unsigned)std::min<int64_t>(ceil_div(total, 256 * 8), 256 * 16), 256, 0, h->stream>>>(pc.sc, pc.ld, pc.rows, pc.Nt, ed, dnb);
+    dcf_neighbour_kernel<<<(unsigned)std::min<int64_t>(ceil_div(total, 256 * 8), 256 * 16), 256, 0, h->stream>>>(pc.scores, pc.ld, pc.rows, pc.Nt, ed, dnb);
     PLDA_LAUNCH_CHECK(h);
     return PLDA_OK;
   }));
@@ -431,13 +412,12 @@ int dcf_neighbour_pass(plda_handle *h, const EerSource &src, const DcfEdges &ed,
 // Sharded calls (src.reduce): every histogram is summed over the ranks before the host step sees it, so every rank takes the
 // same decisions and makes the same sequence of reductions.  A rank that fails locally keeps taking part with a poisoned
 // histogram (2^48 on counter 0, as eer_device); every rank sees the poison after that very sum and returns an error then.
-int min_dcf_device(plda_handle *h, EerSource src, int n_points, const plda_dcf_point *pts, plda_min_dcf *out, plda_min_dcf_info *info_out) {
-  constexpr unsigned long long POISON = 1ull << 48;
+static int min_dcf_device(plda_handle *h, const TrialSource &src, int n_points, const plda_dcf_point *pts, plda_min_dcf *out, plda_min_dcf_info *info_out) {
   constexpr int P = PLDA_MIN_DCF_MAX_POINTS;
   if (!out || !dcf_points_ok(n_points, pts))
     return fail(h, PLDA_E_INVAL, "min_dcf: 1 .. %d operating points with 0 < prior < 1 and finite costs > 0", P);
   const int S = h->mindcf_variant == 2 ? 2 : DCF_S;
-  const bool user_lists = !src.scores && !src.slabs;
+  const bool user_lists = src.kind == TrialSource::LISTS;
   plda_min_dcf_info info;
   std::memset(&info, 0, sizeof(info));
   PLDA_TRY(dcf_lds_attr(h));
@@ -450,14 +430,7 @@ int min_dcf_device(plda_handle *h, EerSource src, int n_points, const plda_dcf_p
 
   int rc = PLDA_OK;
   // sums one [2][EER_BINS] block over the ranks; false: the call ends here, on every rank
-  auto reduce_block = [&](unsigned long long *H) -> bool {
-    if (src.reduce) {
-      if (rc != PLDA_OK) { std::fill(H, H + 2 * EER_BINS, 0ull); H[0] = POISON; }
-      if (src.reduce(src.ctx, H, nullptr, nullptr) != 0 && rc == PLDA_OK) rc = fail(h, PLDA_E_INVAL, "min_dcf: the caller's reduction failed");
-      if (rc == PLDA_OK && H[0] >= POISON) rc = fail(h, PLDA_E_NUMERIC, "min_dcf: another rank of the sharded call failed");
-    }
-    return rc == PLDA_OK;
-  };
+  auto reduce_block = [&](unsigned long long *H) -> bool { return reduce_block_or_poison(h, src, "min_dcf", H, &rc); };
 
   plda_min_dcf_state st;
   std::memset(&st, 0, sizeof(st));
@@ -467,7 +440,7 @@ int min_dcf_device(plda_handle *h, EerSource src, int n_points, const plda_dcf_p
   struct CBin { unsigned prefix; unsigned long long c_lo, c_hi; };
   std::vector<CBin> cbins;
   int cshift = 0;
-  EerSource cur = src;                 // the data the levels read: the caller's, then the lists
+  TrialSource cur = src;                 // the data the levels read: the caller's, then the lists
   bool on_lists = false;
 
   for (int level = 0; level < 3 && !nodes.empty(); ++level) {
@@ -549,12 +522,12 @@ int min_dcf_device(plda_handle *h, EerSource src, int n_points, const plda_dcf_p
           PLDA_HIP(h, hipMemsetAsync(dcursor, 0, 16, h->stream));
           PLDA_HIP(h, hipMemcpyAsync(dprefix, pre.data(), pre.size() * 4, hipMemcpyHostToDevice, h->stream));
           const int hi_shift = DCF_SHIFT[level];           // the survivors' prefixes are key >> this level's shift
-          PLDA_TRY(dcf_for_pieces(cur, [&](const DcfPiece &pc) -> int {
+          PLDA_TRY(for_each_piece(cur, [&](const TrialPiece &pc) -> int {
             const int64_t strips = ceil_div(pc.Nt, (int64_t)EER_STRIP);
             const int64_t slices = std::max<int64_t>(1, std::min<int64_t>(pc.rows, (256 * 16) / strips));
             const int64_t rows_per_wg = ceil_div(pc.rows, slices);
             dcf_compact_strip_kernel<<<(unsigned)(strips * ceil_div(pc.rows, rows_per_wg)), 256, 0, h->stream>>>(
-                pc.sc, pc.ld, pc.rows, pc.Nt, pc.espk, src.tspk, rows_per_wg, hi_shift, dprefix, (int)pre.size(), dcursor,
+                pc.scores, pc.ld, pc.rows, pc.Nt, pc.espk, src.tspk, rows_per_wg, hi_shift, dprefix, (int)pre.size(), dcursor,
                 h->eer_list[0].as<float>(), h->eer_list[1].as<float>(), len[0], len[1]);
             PLDA_LAUNCH_CHECK(h);
             return PLDA_OK;
@@ -572,7 +545,7 @@ int min_dcf_device(plda_handle *h, EerSource src, int n_points, const plda_dcf_p
       on_lists = true;
       cshift = DCF_SHIFT[level];
       for (const auto &nd : next) cbins.push_back(CBin{nd.prefix, nd.miss_below + nd.nn_below, nd.miss_below + nd.nn_below + nd.n_pos + nd.n_neg});
-      cur = EerSource{nullptr, 0, 0, 0, nullptr, nullptr, h->eer_list[1].as<float>(), (int64_t)len[1], h->eer_list[0].as<float>(), (int64_t)len[0]};
+      cur = TrialSource::lists(h->eer_list[1].as<float>(), (int64_t)len[1], h->eer_list[0].as<float>(), (int64_t)len[0]);
       // (a failure here is carried to the next reduction, which every rank reaches: the next level has nodes)
     }
     nodes.swap(next);
@@ -642,34 +615,25 @@ int min_dcf_device(plda_handle *h, EerSource src, int n_points, const plda_dcf_p
 
 int min_dcf_matrix_device(plda_handle *h, const float *dscores, int64_t ld, int64_t M, int64_t Nt, const int64_t *despk,
                           const int64_t *dtspk, int n_points, const plda_dcf_point *pts, plda_min_dcf *out, plda_min_dcf_info *info,
-                          int (*reduce)(void *, unsigned long long *, unsigned *, unsigned *), void *ctx) {
+                          TrialReduce reduce, void *ctx) {
   // a rank of a sharded call may own no row at all (M == 0): it still takes part in the reductions
   if (!out || Nt <= 0 || ld < Nt || M < 0 || (M == 0 && !reduce) || !dtspk || (M > 0 && (!dscores || !despk)))
     return fail(h, PLDA_E_INVAL, "min_dcf: bad argument");
-  EerSource s{M > 0 ? dscores : reinterpret_cast<const float *>(dtspk), ld, M, Nt, despk, dtspk, nullptr, 0, nullptr, 0};
-  s.reduce = reduce;
-  s.ctx = ctx;
-  return min_dcf_device(h, s, n_points, pts, out, info);
+  return min_dcf_device(h, TrialSource::matrix(dscores, ld, M, Nt, despk, dtspk).reduced_by(reduce, ctx), n_points, pts, out, info);
 }
 
 int min_dcf_lists_device(plda_handle *h, const float *dpos, int64_t np, const float *dneg, int64_t nn, int n_points,
                          const plda_dcf_point *pts, plda_min_dcf *out, plda_min_dcf_info *info) {
   if (!dpos || !dneg || !out || np <= 0 || nn <= 0) return fail(h, PLDA_E_INVAL, "min_dcf: need at least one target and one non-target score");
-  EerSource s{nullptr, 0, 0, 0, nullptr, nullptr, dpos, np, dneg, nn};
-  return min_dcf_device(h, s, n_points, pts, out, info);
+  return min_dcf_device(h, TrialSource::lists(dpos, np, dneg, nn), n_points, pts, out, info);
 }
 
 int score_min_dcf_device(plda_handle *h, const double *dU, const int32_t *dn, int n_uniform, int64_t M, const double *dV, int64_t Nt,
                          const double *dzmean, const double *dzstd, const int64_t *despk, const int64_t *dtspk, int n_points,
                          const plda_dcf_point *pts, plda_min_dcf *out, plda_min_dcf_info *info) {
-  if (!h->fitted) return fail(h, PLDA_E_NOT_FITTED, "score_min_dcf: model not fitted");
-  if (!dU || !dV || !despk || !dtspk || !out || M <= 0 || Nt <= 0) return fail(h, PLDA_E_INVAL, "score_min_dcf: bad argument");
-  if (!dn && n_uniform <= 0) return fail(h, PLDA_E_INVAL, "score_min_dcf: n_uniform must be > 0 when n_enrol is NULL");
-  ScoreEerCtx c;
-  EerSlabs sl;
-  PLDA_TRY(score_eer_slabs_setup(h, dU, dn, n_uniform, M, dV, Nt, dzmean, dzstd, despk, &c, &sl));
-  EerSource src{nullptr, Nt, M, Nt, despk, dtspk, nullptr, 0, nullptr, 0};
-  src.slabs = &sl;
+  OperandSlabs os;
+  TrialSource src;
+  PLDA_TRY(operand_source(h, "score_min_dcf", dU, dn, n_uniform, M, dV, Nt, dzmean, dzstd, despk, dtspk, out, &os, &src));
   return min_dcf_device(h, src, n_points, pts, out, info);
 }
 

@@ -21,14 +21,19 @@
 // as its starting offsets.  The answer is the three-pass one bit for bit whenever the window holds the crossing key and
 // both of its neighbours -- checked with the exact counts (g(klo) < 0 <= g(khi), neighbours found inside); otherwise, and
 // for small or sharded inputs, the three passes run.  PLDA_EER_VARIANT=1 forces them (A/B arm, and what the test compares with).
-#include "common.hpp"
+//
+// Where things live: the source of the trials (TrialSource: matrix, lists or slabs), the walk over its pieces
+// (for_each_piece), the score key and the prototypes of every entry point here are in trial_source.hpp, shared with calib.hip
+// and dcf.hip; the slab producer of the operand form (plda_score_eer_dev) is operand_slabs.hip.  This file: the kernels, the
+// histogram pass (eer_pass), the poisoned reduction of the sharded forms (reduce_block_or_poison), the refinement, DET.
+#include "trial_source.hpp"
 
 #include <algorithm>
 #include <cstring>
 
 namespace plda {
 
-// (score_key / key_score / EER_BINS / EER_STRIP: common.hpp, shared with dcf.hip)
+// (score_key / key_score / EER_BINS / EER_STRIP: trial_source.hpp, shared with dcf.hip)
 
 // one pass: class c (0 = impostor, 1 = target) histogram of bits [shift, shift + nbits) of the
 // keys whose higher bits equal `prefix` (pass 0: every key).  below/above track the largest
@@ -247,44 +252,27 @@ __global__ __launch_bounds__(256) void eer_window_strip_kernel(const float *__re
   }
 }
 
-// (EerSource / EerSlabs, the data a reduction over labelled trials consumes: common.hpp, shared with calib.hip)
+// (TrialSource, the data a reduction over labelled trials consumes, and the walk over its pieces: trial_source.hpp)
 
-// One histogram pass over the local data -> hh (host).  No reduction here: see eer_device.  (Declared in common.hpp: dcf.hip's
-// level 0 is this pass.)
-int eer_pass(plda_handle *h, const EerSource &src, int shift, int nbits, unsigned prefix, int has_prefix,
-                    unsigned long long *dhist, unsigned *dbelow, unsigned *dabove, std::vector<unsigned long long> &hh) {
+// One histogram pass over the local data -> hh (host).  No reduction here: see eer_device.  (Declared in trial_source.hpp:
+// dcf.hip's level 0 is this pass.)
+int eer_pass(plda_handle *h, const TrialSource &src, int shift, int nbits, unsigned prefix, int has_prefix,
+             unsigned long long *dhist, unsigned *dbelow, unsigned *dabove, std::vector<unsigned long long> &hh) {
   PLDA_HIP(h, hipMemsetAsync(dhist, 0, 2 * EER_BINS * 8, h->stream));
-  if (src.slabs) {
-    for (int64_t r0 = 0; r0 < src.M; r0 += src.slabs->slab_rows) {
-      const int64_t rows = std::min(src.slabs->slab_rows, src.M - r0);
-      const float *sc = nullptr;
-      int64_t ld = 0;
-      PLDA_TRY(src.slabs->produce(src.slabs->ctx, r0, rows, &sc, &ld));
-      const int64_t strips = ceil_div(src.Nt, (int64_t)EER_STRIP);
-      const int64_t slices = std::max<int64_t>(1, std::min<int64_t>(rows, (256 * 16) / strips));
-      const int64_t rows_per_wg = ceil_div(rows, slices);
-      eer_hist_strip_kernel<<<(unsigned)(strips * ceil_div(rows, rows_per_wg)), 256, 0, h->stream>>>(
-          sc, ld, rows, src.Nt, src.espk + r0, src.tspk, rows_per_wg, shift, nbits, prefix, has_prefix, dhist, dbelow, dabove, 1);
+  PLDA_TRY(for_each_piece(src, [&](const TrialPiece &pc) -> int {
+    if (pc.cls < 0) {
+      const int64_t strips = ceil_div(pc.Nt, (int64_t)EER_STRIP);
+      const int64_t slices = std::max<int64_t>(1, std::min<int64_t>(pc.rows, (256 * 16) / strips));
+      const int64_t rows_per_wg = ceil_div(pc.rows, slices);
+      eer_hist_strip_kernel<<<(unsigned)(strips * ceil_div(pc.rows, rows_per_wg)), 256, 0, h->stream>>>(
+          pc.scores, pc.ld, pc.rows, pc.Nt, pc.espk, src.tspk, rows_per_wg, shift, nbits, prefix, has_prefix, dhist, dbelow, dabove,
+          pc.row_step);
+    } else {
+      const unsigned grid = (unsigned)std::min<int64_t>(ceil_div(pc.Nt, 256), 256 * 16);
+      eer_hist_kernel<<<grid, 256, 0, h->stream>>>(pc.scores, pc.Nt, pc.cls, shift, nbits, prefix, has_prefix, dhist, dbelow, dabove);
     }
-  } else if (src.scores) {
-    const int64_t Ms = ceil_div(src.M, src.row_step);          // rows this pass walks
-    const unsigned grid = (unsigned)std::min<int64_t>(Ms, 256 * 16);
-    if (grid) {
-      const int64_t strips = ceil_div(src.Nt, (int64_t)EER_STRIP);
-      const int64_t slices = std::max<int64_t>(1, std::min<int64_t>(Ms, (256 * 16) / strips));
-      const int64_t rows_per_wg = ceil_div(Ms, slices);
-      eer_hist_strip_kernel<<<(unsigned)(strips * ceil_div(Ms, rows_per_wg)), 256, 0, h->stream>>>(
-          src.scores, src.ld, Ms, src.Nt, src.espk, src.tspk, rows_per_wg, shift, nbits, prefix, has_prefix, dhist,
-          dbelow, dabove, src.row_step);
-    }
-  } else {
-    for (int c = 0; c < 2; ++c) {
-      const float *p = c ? src.pos : src.neg;
-      const int64_t n = c ? src.np : src.nn;
-      const unsigned grid = (unsigned)std::min<int64_t>(ceil_div(n, 256), 256 * 16);
-      if (grid) eer_hist_kernel<<<grid, 256, 0, h->stream>>>(p, n, c, shift, nbits, prefix, has_prefix, dhist, dbelow, dabove);
-    }
-  }
+    return PLDA_OK;
+  }));
   PLDA_LAUNCH_CHECK(h);
   hh.resize(2 * EER_BINS);
   PLDA_HIP(h, hipMemcpyAsync(hh.data(), dhist, 2 * EER_BINS * 8, hipMemcpyDeviceToHost, h->stream));
@@ -292,18 +280,25 @@ int eer_pass(plda_handle *h, const EerSource &src, int shift, int nbits, unsigne
   return PLDA_OK;
 }
 
+bool reduce_block_or_poison(plda_handle *h, const TrialSource &src, const char *who, unsigned long long *H, int *rc) {
+  constexpr unsigned long long POISON = 1ull << 48;
+  if (src.reduce) {
+    if (*rc != PLDA_OK) { std::fill(H, H + 2 * EER_BINS, 0ull); H[0] = POISON; }
+    if (src.reduce(src.ctx, H, nullptr, nullptr) != 0 && *rc == PLDA_OK) *rc = fail(h, PLDA_E_INVAL, "%s: the caller's reduction failed", who);
+    if (*rc == PLDA_OK && H[0] >= POISON) *rc = fail(h, PLDA_E_NUMERIC, "%s: another rank of the sharded call failed", who);
+  }
+  return *rc == PLDA_OK;
+}
+
 // out: [0] threshold, [1] FAR, [2] FRR, [3] EER = (FAR + FRR) / 2, [4] #targets, [5] #impostors
 //
-// Sharded calls (src.reduce): every rank makes the SAME four reduction calls whatever happens locally.
-// A rank that fails (HIP error, inconsistent counts) keeps taking part with a poisoned histogram --
-// 2^48 added to counter 0, far above any real count -- so that all ranks see the failure after the
-// next sum and return an error together instead of leaving their peers blocked in a collective.
+// Sharded calls (src.reduce): every rank makes the SAME four reduction calls whatever happens locally; a rank that fails
+// (HIP error, inconsistent counts) keeps taking part (reduce_block_or_poison).
 // window_missed (windowed lists only): set when the crossing key or one of its neighbours is not inside the lists --
 // the caller then runs the three passes over the matrix; nothing is written to `out`.
-int eer_device(plda_handle *h, const EerSource &src, double *out, bool *window_missed = nullptr) {
+static int eer_device(plda_handle *h, const TrialSource &src, double *out, bool *window_missed = nullptr) {
   typedef unsigned __int128 u128;
   if (window_missed) *window_missed = false;
-  constexpr unsigned long long POISON = 1ull << 48;
   PLDA_HIP(h, h->w[10].reserve(2 * EER_BINS * 8 + 64));
   unsigned long long *dhist = h->w[10].as<unsigned long long>();
   unsigned *dbelow = reinterpret_cast<unsigned *>(dhist + 2 * EER_BINS), *dabove = dbelow + 1;
@@ -322,13 +317,8 @@ int eer_device(plda_handle *h, const EerSource &src, double *out, bool *window_m
       if (e != hipSuccess) rc = hip_fail(h, e, "hipMemcpyAsync(dbelow)", __FILE__, __LINE__);
     }
     if (rc == PLDA_OK) rc = eer_pass(h, src, shifts[pass], bits[pass], prefix, pass > 0, dhist, dbelow, dabove, H);
-    if (src.reduce) {
-      if (rc != PLDA_OK) { H.assign(2 * EER_BINS, 0ull); H[0] = POISON; }
-      if (src.reduce(src.ctx, H.data(), nullptr, nullptr) != 0 && rc == PLDA_OK)
-        rc = fail(h, PLDA_E_INVAL, "eer: the caller's reduction failed");
-      if (rc == PLDA_OK && H[0] >= POISON) rc = fail(h, PLDA_E_NUMERIC, "eer: another rank of the sharded call failed");
-    }
-    if (rc != PLDA_OK) continue;
+    H.resize(2 * EER_BINS);                                  // (a failed pass may not have sized it)
+    if (!reduce_block_or_poison(h, src, "eer", H.data(), &rc)) continue;
     const int nb = 1 << bits[pass];
     if (pass == 0) {
       for (int b = 0; b < nb; ++b) { Nn += H[b]; Np += H[EER_BINS + b]; }
@@ -395,26 +385,23 @@ int eer_device(plda_handle *h, const EerSource &src, double *out, bool *window_m
 constexpr int64_t EER_PILOT_STEP = 32;
 // Returns PLDA_OK with *done = true when `out` holds the result; *done = false: run the three passes.
 // (full: the whole matrix -- in memory, or as slabs)
-static int eer_matrix_windowed(plda_handle *h, const EerSource &full, double *out, bool *done) {
+static int eer_matrix_windowed(plda_handle *h, const TrialSource &full, double *out, bool *done) {
   typedef unsigned __int128 u128;
   *done = false;
-  const float *dscores = full.scores;
-  const int64_t ld = full.ld, M = full.M, Nt = full.Nt;
-  const int64_t *despk = full.espk, *dtspk = full.tspk;
+  const int64_t M = full.M, Nt = full.Nt;
   TraceScope ts(h, "eer.pilot");
   PLDA_HIP(h, h->w[10].reserve(2 * EER_BINS * 8 + 64 + sizeof(EerWindowOut)));
   unsigned long long *dhist = h->w[10].as<unsigned long long>();
   unsigned *dbelow = reinterpret_cast<unsigned *>(dhist + 2 * EER_BINS), *dabove = dbelow + 1;
   EerWindowOut *dwo = reinterpret_cast<EerWindowOut *>(dhist + 2 * EER_BINS + 8);
-  EerSource smp{dscores, ld, M, Nt, despk, dtspk, nullptr, 0, nullptr, 0};
-  smp.row_step = EER_PILOT_STEP;
+  TrialSource smp = TrialSource::matrix(full.scores, full.ld, M, Nt, full.espk, full.tspk).every(EER_PILOT_STEP);
   int64_t pilot_step = EER_PILOT_STEP;
-  if (full.slabs) {
+  if (full.kind == TrialSource::SLABS) {
     // the sample is produced (a small GEMM of its own) and must fit the slab buffer
-    pilot_step = std::max<int64_t>(EER_PILOT_STEP, ceil_div(M, full.slabs->slab_rows));
+    pilot_step = std::max<int64_t>(EER_PILOT_STEP, ceil_div(M, full.sl->slab_rows));
     const float *sc = nullptr; const int64_t *se = nullptr; int64_t sld = 0, srows = 0;
-    PLDA_TRY(full.slabs->sample(full.slabs->ctx, pilot_step, &sc, &sld, &se, &srows));
-    smp = EerSource{sc, sld, srows, Nt, se, dtspk, nullptr, 0, nullptr, 0};
+    PLDA_TRY(full.sl->sample(full.sl->ctx, pilot_step, &sc, &sld, &se, &srows));
+    smp = TrialSource::matrix(sc, sld, srows, Nt, se, full.tspk);
   }
   // pilot, pass 0 on the sample: per coarse bin (top 11 key bits) the sample's g = FRR - FAR; the band |g| < delta of five
   // standard errors around the sample's crossing starts in coarse bin ca and ends in cb (often the same); one pass over
@@ -487,19 +474,15 @@ static int eer_matrix_windowed(plda_handle *h, const EerSource &full, double *ou
   PLDA_HIP(h, h->eer_list[1].reserve((size_t)cap * 4));
   ts.next("eer.window_pass", (double)M * (double)Nt * 4.0, 2);
   PLDA_HIP(h, hipMemsetAsync(dwo, 0, sizeof(EerWindowOut), h->stream));
-  const int64_t slab = full.slabs ? full.slabs->slab_rows : M;
-  for (int64_t r0 = 0; r0 < M; r0 += slab) {
-    const int64_t rows = std::min(slab, M - r0);
-    const float *sc = dscores;
-    int64_t sld = ld;
-    if (full.slabs) PLDA_TRY(full.slabs->produce(full.slabs->ctx, r0, rows, &sc, &sld));
+  PLDA_TRY(for_each_piece(full, [&](const TrialPiece &pc) -> int {
     const int64_t strips = ceil_div(Nt, (int64_t)EER_STRIP);
-    const int64_t slices = std::max<int64_t>(1, std::min<int64_t>(rows, (256 * 16) / strips));
-    const int64_t rows_per_wg = ceil_div(rows, slices);
-    eer_window_strip_kernel<<<(unsigned)(strips * ceil_div(rows, rows_per_wg)), 256, 0, h->stream>>>(
-        sc, sld, rows, Nt, despk + r0, dtspk, rows_per_wg, key_score(klo), key_score(khi), dwo, h->eer_list[0].as<float>(), h->eer_list[1].as<float>(), cap);
+    const int64_t slices = std::max<int64_t>(1, std::min<int64_t>(pc.rows, (256 * 16) / strips));
+    const int64_t rows_per_wg = ceil_div(pc.rows, slices);
+    eer_window_strip_kernel<<<(unsigned)(strips * ceil_div(pc.rows, rows_per_wg)), 256, 0, h->stream>>>(
+        pc.scores, pc.ld, pc.rows, Nt, pc.espk, full.tspk, rows_per_wg, key_score(klo), key_score(khi), dwo, h->eer_list[0].as<float>(), h->eer_list[1].as<float>(), cap);
     PLDA_LAUNCH_CHECK(h);
-  }
+    return PLDA_OK;
+  }));
   EerWindowOut wo;
   PLDA_HIP(h, hipMemcpyAsync(&wo, dwo, sizeof(wo), hipMemcpyDeviceToHost, h->stream));
   PLDA_HIP(h, hipStreamSynchronize(h->stream));
@@ -513,128 +496,44 @@ static int eer_matrix_windowed(plda_handle *h, const EerSource &full, double *ou
   if ((u128)wo.below[1] * TN >= (u128)(TN - wo.below[0]) * TP) return PLDA_OK;
   if ((u128)(wo.below[1] + wo.cursor[1]) * TN < (u128)(TN - wo.below[0] - wo.cursor[0]) * TP) return PLDA_OK;
   if (wo.cursor[0] + wo.cursor[1] == 0) return PLDA_OK;
-  EerSource lst{nullptr, 0, 0, 0, nullptr, nullptr, h->eer_list[1].as<float>(), (int64_t)wo.cursor[1], h->eer_list[0].as<float>(), (int64_t)wo.cursor[0]};
-  lst.windowed = true;
-  lst.base_p = wo.below[1]; lst.base_n = wo.below[0]; lst.tot_p = TP; lst.tot_n = TN;
+  const TrialSource lst = TrialSource::lists(h->eer_list[1].as<float>(), (int64_t)wo.cursor[1], h->eer_list[0].as<float>(), (int64_t)wo.cursor[0])
+                              .window_of(wo.below[1], wo.below[0], TP, TN);
   bool missed = false;
   PLDA_TRY(eer_device(h, lst, out, &missed));
   *done = !missed;
   return PLDA_OK;
 }
 
-int eer_matrix_device(plda_handle *h, const float *dscores, int64_t ld, int64_t M, int64_t Nt, const int64_t *despk,
-                      const int64_t *dtspk, double *out,
-                      int (*reduce)(void *, unsigned long long *, unsigned *, unsigned *), void *ctx) {
-  // a rank of a sharded call may own no row at all (M == 0): it still takes part in the reductions
-  if (!out || Nt <= 0 || ld < Nt || M < 0 || (M == 0 && !reduce) || (M > 0 && (!dscores || !despk || !dtspk)))
-    return fail(h, PLDA_E_INVAL, "eer: bad argument");
+// the single-pass form where it applies (one process, large enough), else -- or should its window miss -- the three passes
+static int eer_source_device(plda_handle *h, const TrialSource &src, double *out, const char *three_passes_scope) {
+  const int64_t M = src.M, Nt = src.Nt;
   h->eer_last_passes = 3;
-  if (!reduce && h->eer_variant != 1 && (h->eer_variant == 2 || (double)M * (double)Nt >= 2.5e8) && M >= 4 * EER_PILOT_STEP) {
-    bool done = false;
-    const EerSource fullsrc{dscores, ld, M, Nt, despk, dtspk, nullptr, 0, nullptr, 0};
-    PLDA_TRY(eer_matrix_windowed(h, fullsrc, out, &done));
-    if (done) { h->eer_last_passes = 1; return PLDA_OK; }
-  }
-  TraceScope ts(h, "eer.three_passes", 3.0 * (double)M * (double)Nt * 4.0, 2);
-  EerSource s{M > 0 ? dscores : reinterpret_cast<const float *>(out), ld, M, Nt, despk, dtspk, nullptr, 0, nullptr, 0};
-  s.reduce = reduce;
-  s.ctx = ctx;
-  return eer_device(h, s, out);
-}
-
-// ------------------------------------------------------------------------------------
-// EER of a trials matrix that is never held (round 5: plda_score_eer_dev).  The reference's caller scores every trial and
-// hands the scores to eer.py (scoring/scorePLDA.py:302-318 -> scoring/eer.py:68-76): what it wants is four numbers, not M x Nt
-// floats -- C4's matrix is 192 GB.  Here the scores exist one row slab at a time (<= 4 GiB): the pilot's sample is a GEMM of
-// every step-th enrol row, then every slab is scored (the test side packed once, the distinct enrol counts found once) and
-// consumed by the window pass; the three-pass form, should the window miss, re-scores the slabs per pass.  Identical to
-// plda_eer_matrix_dev on the materialised matrix (the kernels give a trial the same bits wherever its tile lies).
-// Not yet inside the GEMM's epilogue: the slab is written and read back once, through HBM.
-// ------------------------------------------------------------------------------------
-__global__ void eer_gather_rows_kernel(const double *__restrict__ X, int D, int64_t step, int64_t rows, double *__restrict__ out) {
-  const int64_t r = blockIdx.x;
-  if (r >= rows) return;
-  for (int d = threadIdx.x; d < D; d += blockDim.x) out[r * D + d] = X[r * step * D + d];
-}
-__global__ void eer_gather_meta_kernel(const int32_t *__restrict__ n, const double *__restrict__ zm, const double *__restrict__ zs,
-                                       const int64_t *__restrict__ spk, int64_t step, int64_t rows, int32_t *__restrict__ on,
-                                       double *__restrict__ ozm, double *__restrict__ ozs, int64_t *__restrict__ ospk) {
-  const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (r >= rows) return;
-  if (n) on[r] = n[r * step];
-  if (zm) { ozm[r] = zm[r * step]; ozs[r] = zs[r * step]; }
-  ospk[r] = spk[r * step];
-}
-
-// (ScoreEerCtx: common.hpp)
-int score_eer_produce(void *vc, int64_t r0, int64_t rows, const float **scores, int64_t *ld) {
-  auto *c = static_cast<ScoreEerCtx *>(vc);
-  const int D = c->h->Dout;
-  PLDA_TRY(score_matrix_device(c->h, c->dU + r0 * D, c->dn ? c->dn + r0 : nullptr, c->n_uniform, rows, c->dV, c->Nt,
-                               c->dzm ? c->dzm + r0 : nullptr, c->dzs ? c->dzs + r0 : nullptr, c->slab, c->Nt, c->packedB,
-                               c->has_cs ? &c->cs : nullptr));
-  c->packedB = true;
-  *scores = c->slab; *ld = c->Nt;
-  return PLDA_OK;
-}
-int score_eer_sample(void *vc, int64_t step, const float **scores, int64_t *ld, const int64_t **espk, int64_t *rows) {
-  auto *c = static_cast<ScoreEerCtx *>(vc);
-  plda_handle *h = c->h;
-  const int D = h->Dout;
-  const int64_t Ms = ceil_div(c->M, step);
-  const size_t oU = 0, oZ = round_up((size_t)Ms * D * 8, 256), oS = oZ + round_up((size_t)Ms * 16, 256), oN = oS + round_up((size_t)Ms * 8, 256);
-  PLDA_HIP(h, h->eer_smp.reserve(oN + (size_t)Ms * 4 + 256));
-  char *b = h->eer_smp.as<char>();
-  double *sU = reinterpret_cast<double *>(b + oU), *szm = reinterpret_cast<double *>(b + oZ), *szs = szm + Ms;
-  int64_t *sspk = reinterpret_cast<int64_t *>(b + oS);
-  int32_t *sn = reinterpret_cast<int32_t *>(b + oN);
-  eer_gather_rows_kernel<<<(unsigned)Ms, 256, 0, h->stream>>>(c->dU, D, step, Ms, sU);
-  eer_gather_meta_kernel<<<(unsigned)ceil_div(Ms, 256), 256, 0, h->stream>>>(c->dn, c->dzm, c->dzs, c->despk, step, Ms, sn, szm, szs, sspk);
-  PLDA_LAUNCH_CHECK(h);
-  PLDA_TRY(score_matrix_device(h, sU, c->dn ? sn : nullptr, c->n_uniform, Ms, c->dV, c->Nt, c->dzm ? szm : nullptr, c->dzm ? szs : nullptr,
-                               c->slab, c->Nt, c->packedB, c->has_cs ? &c->cs : nullptr));
-  c->packedB = true;
-  *scores = c->slab; *ld = c->Nt; *espk = sspk; *rows = Ms;
-  return PLDA_OK;
-}
-
-// The slab set-up of the operand forms (plda_score_eer_dev, plda_score_calib_*_dev): the distinct enrol counts found once, the
-// slab height, the slab buffer.  *c must outlive *sl.
-int score_eer_slabs_setup(plda_handle *h, const double *dU, const int32_t *dn, int n_uniform, int64_t M, const double *dV, int64_t Nt,
-                          const double *dzmean, const double *dzstd, const int64_t *despk, ScoreEerCtx *c, EerSlabs *sl) {
-  *c = ScoreEerCtx{h, dU, dn, n_uniform, M, dV, Nt, (dzmean && dzstd) ? dzmean : nullptr, (dzmean && dzstd) ? dzstd : nullptr, despk};
-  c->has_cs = false; c->packedB = false;
-  if (dn) { PLDA_TRY(score_count_set_device(h, dn, M, &c->cs)); c->has_cs = true; }
-  // slabs of <= 4 GiB of scores, whole 256-row tiles, at least one tile row
-  int64_t rows = std::max<int64_t>(256, (((int64_t)4 << 30) / 4 / Nt) / 256 * 256);
-  if (h->eer_slab_rows > 0) rows = round_up(h->eer_slab_rows, 256);      // PLDA_EER_SLAB_ROWS: small slabs for the tests
-  rows = std::min(rows, round_up(M, 256));
-  c->slab_rows = rows;
-  PLDA_HIP(h, h->eer_slab.reserve((size_t)rows * Nt * 4));
-  c->slab = h->eer_slab.as<float>();
-  *sl = EerSlabs{rows, score_eer_produce, score_eer_sample, c};
-  h->prep_valid = false;           // (the slabs pack the test side themselves)
-  return PLDA_OK;
-}
-
-int score_eer_device(plda_handle *h, const double *dU, const int32_t *dn, int n_uniform, int64_t M, const double *dV, int64_t Nt,
-                     const double *dzmean, const double *dzstd, const int64_t *despk, const int64_t *dtspk, double *out) {
-  if (!h->fitted) return fail(h, PLDA_E_NOT_FITTED, "score_eer: model not fitted");
-  if (!dU || !dV || !despk || !dtspk || !out || M <= 0 || Nt <= 0) return fail(h, PLDA_E_INVAL, "score_eer: bad argument");
-  if (!dn && n_uniform <= 0) return fail(h, PLDA_E_INVAL, "score_eer: n_uniform must be > 0 when n_enrol is NULL");
-  ScoreEerCtx c;
-  EerSlabs sl;
-  PLDA_TRY(score_eer_slabs_setup(h, dU, dn, n_uniform, M, dV, Nt, dzmean, dzstd, despk, &c, &sl));
-  EerSource src{nullptr, Nt, M, Nt, despk, dtspk, nullptr, 0, nullptr, 0};
-  src.slabs = &sl;
-  h->eer_last_passes = 3;
-  if (h->eer_variant != 1 && (h->eer_variant == 2 || (double)M * (double)Nt >= 2.5e8) && M >= 4 * EER_PILOT_STEP) {
+  if (!src.reduce && h->eer_variant != 1 && (h->eer_variant == 2 || (double)M * (double)Nt >= 2.5e8) && M >= 4 * EER_PILOT_STEP) {
     bool done = false;
     PLDA_TRY(eer_matrix_windowed(h, src, out, &done));
     if (done) { h->eer_last_passes = 1; return PLDA_OK; }
   }
-  TraceScope ts(h, "eer.three_passes (slabs re-scored per pass)", 3.0 * (double)M * (double)Nt * 4.0, 2);
+  TraceScope ts(h, three_passes_scope, 3.0 * (double)M * (double)Nt * 4.0, 2);
   return eer_device(h, src, out);
+}
+
+int eer_matrix_device(plda_handle *h, const float *dscores, int64_t ld, int64_t M, int64_t Nt, const int64_t *despk,
+                      const int64_t *dtspk, double *out, TrialReduce reduce, void *ctx) {
+  // a rank of a sharded call may own no row at all (M == 0): it still takes part in the reductions
+  if (!out || Nt <= 0 || ld < Nt || M < 0 || (M == 0 && !reduce) || (M > 0 && (!dscores || !despk || !dtspk)))
+    return fail(h, PLDA_E_INVAL, "eer: bad argument");
+  return eer_source_device(h, TrialSource::matrix(dscores, ld, M, Nt, despk, dtspk).reduced_by(reduce, ctx), out, "eer.three_passes");
+}
+
+// EER of a trials matrix that is never held (plda_score_eer_dev; operand_slabs.hip): the pilot's sample is a GEMM of every
+// step-th enrol row, every slab is scored and consumed by the window pass; the three-pass form, should the window miss,
+// re-scores the slabs per pass.
+int score_eer_device(plda_handle *h, const double *dU, const int32_t *dn, int n_uniform, int64_t M, const double *dV, int64_t Nt,
+                     const double *dzmean, const double *dzstd, const int64_t *despk, const int64_t *dtspk, double *out) {
+  OperandSlabs os;
+  TrialSource src;
+  PLDA_TRY(operand_source(h, "score_eer", dU, dn, n_uniform, M, dV, Nt, dzmean, dzstd, despk, dtspk, out, &os, &src));
+  return eer_source_device(h, src, out, "eer.three_passes (slabs re-scored per pass)");
 }
 
 // ------------------------------------------------------------------------------------
@@ -688,10 +587,7 @@ __global__ __launch_bounds__(256) void det_hist_kernel(const float *__restrict__
   }
 }
 
-// parts: up to two (scores, ld, M, Nt, cls) pieces -- the labelled matrix (cls = -1), or the impostor and target lists
-struct DetPart { const float *scores; int64_t ld, M, Nt; int cls; };
-static int det_device(plda_handle *h, const DetPart *parts, int nparts, const int64_t *despk, const int64_t *dtspk, int npoints,
-                      double *far, double *frr, double *thresholds) {
+static int det_device(plda_handle *h, const TrialSource &src, int npoints, double *far, double *frr, double *thresholds) {
   if (npoints < 2 || npoints > DET_MAX) return fail(h, PLDA_E_INVAL, "det: 2 <= n_points <= %d", DET_MAX);
   const size_t hb = (size_t)2 * (DET_MAX + 1) * 8;
   PLDA_HIP(h, h->w[10].reserve(hb + 64 + (size_t)DET_MAX * 8 + 64));
@@ -700,10 +596,10 @@ static int det_device(plda_handle *h, const DetPart *parts, int nparts, const in
   double *dthr = reinterpret_cast<double *>(dmm + 16);
   static const unsigned init[2] = {0xffffffffu, 0u};
   PLDA_HIP(h, hipMemcpyAsync(dmm, init, 8, hipMemcpyHostToDevice, h->stream));
-  for (int p = 0; p < nparts; ++p) {
-    const int64_t total = parts[p].M * parts[p].Nt;
-    if (total > 0) det_minmax_kernel<<<(unsigned)std::min<int64_t>(ceil_div(total, 256), 256 * 32), 256, 0, h->stream>>>(parts[p].scores, parts[p].ld, parts[p].M, parts[p].Nt, dmm);
-  }
+  PLDA_TRY(for_each_piece(src, [&](const TrialPiece &pc) -> int {
+    det_minmax_kernel<<<(unsigned)std::min<int64_t>(ceil_div(pc.rows * pc.Nt, 256), 256 * 32), 256, 0, h->stream>>>(pc.scores, pc.ld, pc.rows, pc.Nt, dmm);
+    return PLDA_OK;
+  }));
   PLDA_LAUNCH_CHECK(h);
   unsigned mm[2];
   PLDA_HIP(h, hipMemcpyAsync(mm, dmm, 8, hipMemcpyDeviceToHost, h->stream));
@@ -717,12 +613,11 @@ static int det_device(plda_handle *h, const DetPart *parts, int nparts, const in
   for (int i = 0; i < npoints; ++i) { thr[(size_t)i] = t; t += step; }
   PLDA_HIP(h, hipMemcpyAsync(dthr, thr.data(), (size_t)npoints * 8, hipMemcpyHostToDevice, h->stream));
   PLDA_HIP(h, hipMemsetAsync(dhist, 0, hb, h->stream));
-  for (int p = 0; p < nparts; ++p) {
-    const int64_t total = parts[p].M * parts[p].Nt;
-    if (total > 0)
-      det_hist_kernel<<<(unsigned)std::min<int64_t>(ceil_div(total, 256), 256 * 8), 256, 0, h->stream>>>(
-          parts[p].scores, parts[p].ld, parts[p].M, parts[p].Nt, despk, dtspk, parts[p].cls, dthr, npoints, lo, step > 0.0 ? 1.0 / step : 0.0, dhist);
-  }
+  PLDA_TRY(for_each_piece(src, [&](const TrialPiece &pc) -> int {
+    det_hist_kernel<<<(unsigned)std::min<int64_t>(ceil_div(pc.rows * pc.Nt, 256), 256 * 8), 256, 0, h->stream>>>(
+        pc.scores, pc.ld, pc.rows, pc.Nt, pc.espk, src.tspk, pc.cls, dthr, npoints, lo, step > 0.0 ? 1.0 / step : 0.0, dhist);
+    return PLDA_OK;
+  }));
   PLDA_LAUNCH_CHECK(h);
   std::vector<unsigned long long> H((size_t)2 * (DET_MAX + 1));
   PLDA_HIP(h, hipMemcpyAsync(H.data(), dhist, hb, hipMemcpyDeviceToHost, h->stream));
@@ -745,20 +640,17 @@ static int det_device(plda_handle *h, const DetPart *parts, int nparts, const in
 int det_matrix_device(plda_handle *h, const float *dscores, int64_t ld, int64_t M, int64_t Nt, const int64_t *despk, const int64_t *dtspk,
                       int npoints, double *far, double *frr, double *thresholds) {
   if (!dscores || !despk || !dtspk || !far || !frr || M <= 0 || Nt <= 0 || ld < Nt) return fail(h, PLDA_E_INVAL, "det: bad argument");
-  const DetPart part{dscores, ld, M, Nt, -1};
-  return det_device(h, &part, 1, despk, dtspk, npoints, far, frr, thresholds);
+  return det_device(h, TrialSource::matrix(dscores, ld, M, Nt, despk, dtspk), npoints, far, frr, thresholds);
 }
 int det_lists_device(plda_handle *h, const float *dpos, int64_t np, const float *dneg, int64_t nn, int npoints, double *far, double *frr,
                      double *thresholds) {
   if (!dpos || !dneg || !far || !frr || np <= 0 || nn <= 0) return fail(h, PLDA_E_INVAL, "det: need at least one target and one impostor score");
-  const DetPart parts[2] = {{dneg, nn, 1, nn, 0}, {dpos, np, 1, np, 1}};
-  return det_device(h, parts, 2, nullptr, nullptr, npoints, far, frr, thresholds);
+  return det_device(h, TrialSource::lists(dpos, np, dneg, nn), npoints, far, frr, thresholds);
 }
 
 int eer_lists_device(plda_handle *h, const float *dpos, int64_t np, const float *dneg, int64_t nn, double *out) {
   if (!dpos || !dneg || !out || np <= 0 || nn <= 0) return fail(h, PLDA_E_INVAL, "eer: need at least one target and one impostor score");
-  EerSource s{nullptr, 0, 0, 0, nullptr, nullptr, dpos, np, dneg, nn};
-  return eer_device(h, s, out);
+  return eer_device(h, TrialSource::lists(dpos, np, dneg, nn), out);
 }
 
 }  // namespace plda

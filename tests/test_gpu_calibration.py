@@ -92,9 +92,11 @@ def _points(pos, neg):
 
 # ------------------------------------------------------------------------------------------- 1. + 2. the pass record
 @pytest.mark.parametrize("m,nt,ld,off,k", [(300, 500, 500, 0, 12), (300, 500, 512, 0, 12), (37, 1023, 1023, 0, 5), (64, 512, 512, 1, 6),
-                                           (1, 2000, 2000, 0, 3), (700, 1, 1, 0, 4), (5, 4099, 4100, 0, 5), (4096, 8192, 8192, 0, 200)])
+                                           (1, 2000, 2000, 0, 3), (700, 1, 1, 0, 4), (5, 4099, 4100, 0, 5), (4096, 8192, 8192, 0, 200),
+                                           (513, 1025, 1028, 1, 16)])
 def test_pass_record_matches_the_model(monkeypatch, m, nt, ld, off, k):
-    """ld > Nt, Nt not a multiple of 4, a misaligned base pointer (off: floats), one row, one column, 300 x 500, 4096 x 8192."""
+    """ld > Nt, Nt not a multiple of 4, a misaligned base pointer (off: floats), one row, one column, 300 x 500, 4096 x 8192;
+    513 x 1025 under ld = 1028 from a base pointer one float off: a second column strip of one column."""
     from plda_amd import calibration as CB
     eng = _engine(monkeypatch)
     rng = np.random.default_rng(m * 7919 + nt + ld)
@@ -122,7 +124,7 @@ def test_list_form_matches_the_model_and_is_deterministic(monkeypatch):
     from plda_amd import calibration as CB
     eng = _engine(monkeypatch)
     rng = np.random.default_rng(4)
-    for npos, nneg in ((1, 1), (3, 70000), (2_000_003, 5)):
+    for npos, nneg in ((1, 1), (3, 70000), (2_000_003, 5), (1, 70000), (70000, 1)):
         pos = (2.0 + rng.standard_normal(npos) * 2).astype(np.float32)
         neg = (-2.0 + rng.standard_normal(nneg) * 2).astype(np.float32)
         for a, c in ((0.0, 0.3), (1.0, 0.0), (60.0, -3.0)):
@@ -147,11 +149,12 @@ def _score_matrix(eng, dU, dn, nu, m, dV, nt, dzm=None, dzs=None):
     return S
 
 
-@pytest.mark.parametrize("mixed,zn", [(False, False), (True, True)])
-def test_three_sources_one_answer(monkeypatch, mixed, zn):
+@pytest.mark.parametrize("mixed,zn,m,nt", [(False, False, 900, 1300), (True, True, 900, 1300), (True, True, 513, 1025)],
+                         ids=["False-False", "True-True", "True-True-513x1025"])
+def test_three_sources_one_answer(monkeypatch, mixed, zn, m, nt):
     from plda_amd import calibration as CB
-    d, m, nt = 48, 900, 1300
-    eng = _engine(monkeypatch, d, slab=256)                    # 900 rows: four slabs
+    d = 48
+    eng = _engine(monkeypatch, d, slab=256)                    # 900 rows: four slabs; 513 rows: three, the last of one row
     rng = np.random.default_rng(31 + mixed)
     U, V, n = _operands(rng, m, nt, d, mixed)
     es, ts = _labels(rng, m, nt, 30)
@@ -170,7 +173,7 @@ def test_three_sources_one_answer(monkeypatch, mixed, zn):
         opr = CB.pass_from_operands_dev(eng, dU.data_ptr(), dn.data_ptr() if mixed else None, nu, m, dV.data_ptr(), nt,
                                         des.data_ptr(), dts.data_ptr(), dzm.data_ptr() if zn else None, dzs.data_ptr() if zn else None,
                                         a, c, theta)
-        for what, got in (("matrix", mat), ("lists", lst), ("operands, 4 slabs", opr)):
+        for what, got in (("matrix", mat), ("lists", lst), ("operands, slabs of 256 rows", opr)):
             _compare("%s at (%.3g, %.3g)" % (what, a, c), got, ref)
         # bit for bit the same scores: the extremes and every exact count already agree; the sums of the operand form
         # are those of the matrix form over the same values in another order

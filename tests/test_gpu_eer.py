@@ -14,7 +14,7 @@ def eng():
 
 
 @pytest.mark.parametrize("seed", list(range(24)))
-@pytest.mark.parametrize("case", ["gauss", "ties", "separable", "inverted", "tiny", "wide"])
+@pytest.mark.parametrize("case", ["gauss", "ties", "separable", "inverted", "tiny", "wide", "one_target", "one_impostor"])
 def test_eer_lists_match_restatement(eng, case, seed):
     from plda_amd import eer
     rng = np.random.default_rng(sum(map(ord, case)) + seed)   # (hash() of a str changes from process to process)
@@ -28,6 +28,10 @@ def test_eer_lists_match_restatement(eng, case, seed):
         pos, neg = rng.normal(-2.0, 1.0, 400), rng.normal(2.0, 1.0, 4000)
     elif case == "tiny":
         pos, neg = np.array([0.5]), np.array([-0.25, 0.75])
+    elif case == "one_target":                   # a list of one score against one of many launches, in either order
+        pos, neg = rng.normal(0.5, 1.0, 1), rng.normal(-1.0, 1.0, 70000)
+    elif case == "one_impostor":
+        pos, neg = rng.normal(1.0, 1.0, 70000), rng.normal(-0.5, 1.0, 1)
     else:                                        # many exponents, both signs, zeros
         pos = np.concatenate([rng.normal(0, 1e-3, 500), rng.normal(50, 30, 500), [0.0, -0.0]])
         neg = np.concatenate([rng.normal(0, 1e-3, 5000), rng.normal(-50, 30, 5000), [0.0]])
@@ -63,12 +67,16 @@ def test_eer_of_a_trials_matrix(eng, oracle):
     assert eer.format_line(out[1], out[2], out[0]).startswith("EER = ")
 
 
-@pytest.mark.parametrize("m,nt,ld,k", [(1, 2, 2, 1), (3, 5, 7, 2), (2, 1023, 1023, 3), (257, 1023, 1023, 9),
-                                       (300, 1025, 1028, 16), (7, 4099, 4100, 5), (5000, 3001, 3001, 40)])
-def test_eer_of_ragged_matrices(eng, m, nt, ld, k):
+@pytest.mark.parametrize("m,nt,ld,k,off", [(1, 2, 2, 1, 0), (3, 5, 7, 2, 0), (2, 1023, 1023, 3, 0), (257, 1023, 1023, 9, 0),
+                                           (300, 1025, 1028, 16, 0), (7, 4099, 4100, 5, 0), (5000, 3001, 3001, 40, 0),
+                                           (513, 1025, 1028, 16, 1)],
+                         ids=["1-2-2-1", "3-5-7-2", "2-1023-1023-3", "257-1023-1023-9", "300-1025-1028-16", "7-4099-4100-5",
+                              "5000-3001-3001-40", "513-1025-1028-16-off1"])
+def test_eer_of_ragged_matrices(eng, m, nt, ld, k, off):
     """The matrix passes give each workgroup a strip of 1024 columns and a slice of the rows, four rows at a time:
     widths that are not a multiple of 4 or of 1024, padded and unaligned leading dimensions, fewer rows than one
-    group of four, quantised scores (ties across the two classes)."""
+    group of four, quantised scores (ties across the two classes); off: the base pointer that many floats off a
+    16-byte boundary under a leading dimension that would allow 16-byte loads (a second column strip of one column)."""
     import torch
     from plda_amd import eer
     dev = torch.device("cuda", 0)
@@ -85,9 +93,9 @@ def test_eer_of_ragged_matrices(eng, m, nt, ld, k):
     Sh[:, :nt] += 12.0 * tgt
     if m * nt < 1_000_000:
         Sh = np.round(Sh * 4) / 4
-    S = torch.from_numpy(Sh).to(dev)
+    S = torch.from_numpy(np.concatenate([np.zeros(off, np.float32), Sh.ravel()])).to(dev)
     des, dts = torch.from_numpy(es).to(dev), torch.from_numpy(ts).to(dev)
-    out = eer.eer_from_matrix_dev(eng, S.data_ptr(), ld, m, nt, des.data_ptr(), dts.data_ptr())
+    out = eer.eer_from_matrix_dev(eng, S.data_ptr() + 4 * off, ld, m, nt, des.data_ptr(), dts.data_ptr())
     sub = Sh[:, :nt]
     ref = onp.eer(sub[~tgt], sub[tgt])
     assert out[4] == tgt.sum() and out[5] == (~tgt).sum()
@@ -215,17 +223,21 @@ def test_single_pass_eer_forced_on_small_and_awkward_inputs(monkeypatch, case):
     assert tuple(a[1:4]) == ref[1:] and a[0] == pytest.approx(ref[0], rel=1e-12)
 
 
-@pytest.mark.parametrize("case", ["uniform_windowed", "mixed_znorm_windowed", "three_pass_slabs", "big_uniform"])
+@pytest.mark.parametrize("case", ["uniform_windowed", "mixed_znorm_windowed", "three_pass_slabs", "big_uniform",
+                                  "seam_windowed", "seam_three_pass"])
 def test_eer_without_the_matrix(monkeypatch, case):
     """plda_score_eer_dev (round 5): the EER of the trials between transformed enrol / test vectors with the scores held one
     row slab at a time -- what scoring/scorePLDA.py:302-318 -> scoring/eer.py:68-76 computes from M x Nt calls of MPlda_score.
     Identical (all six numbers) to scoring the matrix and taking plda_eer_matrix_dev of it: several slabs per pass
     (PLDA_EER_SLAB_ROWS), the single-pass form (forced at small sizes, natural at 20 000 x 20 000) and the three-pass form
-    that re-scores the slabs per pass, uniform and mixed enrol counts, z-normalised rows."""
+    that re-scores the slabs per pass, uniform and mixed enrol counts, z-normalised rows.  The seam cases: 513 rows in slabs
+    of 256 -- three slabs, the last of one row -- by 1025 columns -- two column strips, the last of one column -- with mixed
+    counts and z-norm, in both forms."""
     import torch
     from plda_amd import MPlda, eer
     dev = torch.device("cuda", 0)
-    d, m, nt, k = (48, 3000, 2500, 40) if case != "big_uniform" else (32, 20000, 20000, 200)
+    seam = case.startswith("seam")
+    d, m, nt, k = (48, 513, 1025, 40) if seam else (48, 3000, 2500, 40) if case != "big_uniform" else (32, 20000, 20000, 200)
     rng = np.random.default_rng(sum(map(ord, case)))
     q, _ = np.linalg.qr(rng.standard_normal((d, d)))
     model = (rng.random(d), q * (1.0 + rng.random(d))[:, None], np.sort(rng.random(d) * 4.0 + 0.05)[::-1].copy())
@@ -234,13 +246,14 @@ def test_eer_without_the_matrix(monkeypatch, case):
     U = torch.from_numpy(spk[es] + rng.standard_normal((m, d))).to(dev)
     V = torch.from_numpy(spk[ts] + rng.standard_normal((nt, d))).to(dev)
     des, dts = torch.from_numpy(es).to(dev), torch.from_numpy(ts).to(dev)
-    mixed = case == "mixed_znorm_windowed"
+    mixed = case == "mixed_znorm_windowed" or seam
     dn = torch.from_numpy(rng.integers(1, 6, m).astype(np.int32)).to(dev) if mixed else None
     zm = torch.from_numpy(rng.standard_normal(m) * 3.0).to(dev) if mixed else None
     zs = torch.from_numpy(rng.random(m) * 2.0 + 0.5).to(dev) if mixed else None
-    monkeypatch.setenv("PLDA_EER_VARIANT", "1" if case == "three_pass_slabs" else ("0" if case == "big_uniform" else "2"))
+    three_pass = case in ("three_pass_slabs", "seam_three_pass")
+    monkeypatch.setenv("PLDA_EER_VARIANT", "1" if three_pass else ("0" if case == "big_uniform" else "2"))
     if case != "big_uniform":
-        monkeypatch.setenv("PLDA_EER_SLAB_ROWS", "512")           # 6 slabs
+        monkeypatch.setenv("PLDA_EER_SLAB_ROWS", "256" if seam else "512")   # 3 slabs, the last of one row; else 6 slabs
     eng = MPlda(0)
     eng.set_model(*model)
     monkeypatch.setenv("PLDA_EER_VARIANT", "1")
@@ -257,7 +270,7 @@ def test_eer_without_the_matrix(monkeypatch, case):
     names = [sp["name"] for sp in eng.trace_read()]
     assert np.array_equal(got, ref), (case, got, ref)
     assert 0.0 < got[3] < 0.45 and got[4] + got[5] == m * nt
-    if case == "three_pass_slabs":
+    if three_pass:
         assert any(n.startswith("eer.three_passes") for n in names), names
     else:
         assert "eer.pilot" in names, names

@@ -54,8 +54,8 @@ def _case(name):
         ts = np.zeros(2 * len(pos), np.int64)
         ts[0::2] = 1
         return s, s.shape[1], np.array([1], np.int64), ts, ((0.5, 1.0, 1.0),)
-    m, nt, k = (1031, 4099, 12) if name == "ragged" else (1500, 2100, 30)
-    ld = nt + 5 if name == "ragged" else nt
+    m, nt, k = (1031, 4099, 12) if name == "ragged" else (513, 1025, 16) if name == "seam" else (1500, 2100, 30)
+    ld = nt + 5 if name == "ragged" else 1028 if name == "seam" else nt
     es, ts = rng.integers(0, k, m), rng.integers(0, k, nt)
     if name == "few_targets":
         es[:] = np.arange(m) + 1000; ts[:] = np.arange(nt) + 5000; es[:5] = 7; ts[:5] = 7      # 25 targets only
@@ -69,12 +69,13 @@ def _case(name):
     return s, nt, es.astype(np.int64), ts.astype(np.int64), pts
 
 
-def _matrix_call(eng, s, nt, es, ts, pts):
+def _matrix_call(eng, s, nt, es, ts, pts, off=0):
+    """off: the matrix starts that many floats into its buffer (a base pointer off the 16-byte boundary)"""
     from plda_amd import dcf
-    dS, des, dts = _t(s), _t(es), _t(ts)
+    dS, des, dts = _t(np.concatenate([np.zeros(off, np.float32), s.ravel()])), _t(es), _t(ts)
     import torch
     torch.cuda.synchronize()
-    return dcf.min_dcf_from_matrix_dev(eng, dS.data_ptr(), s.shape[1], s.shape[0], nt, des.data_ptr(), dts.data_ptr(), pts)
+    return dcf.min_dcf_from_matrix_dev(eng, dS.data_ptr() + 4 * off, s.shape[1], s.shape[0], nt, des.data_ptr(), dts.data_ptr(), pts)
 
 
 def _assert_same(got, ref, what):
@@ -85,10 +86,11 @@ def _assert_same(got, ref, what):
         assert mm.same(g, r), (what, g, r)
 
 
-@pytest.mark.parametrize("name", ["gauss", "ragged", "ties", "separable", "few_targets", "flat"])
+@pytest.mark.parametrize("name", ["gauss", "ragged", "ties", "separable", "few_targets", "flat", "seam"])
 def test_matrix_and_lists_equal_the_model_under_every_variant(monkeypatch, name):
     """Every arm of PLDA_MINDCF_VARIANT (0: the default, 1: never the lists, 2: two nodes per read) and the list form give
-    the model's answer bit for bit; the flat-cost set, which the bound cannot prune, takes several launches per level."""
+    the model's answer bit for bit; the flat-cost set, which the bound cannot prune, takes several launches per level.
+    seam: 513 x 1025 under ld = 1028 (a second column strip of one column) from a base pointer one float off."""
     from plda_amd import dcf
     s, nt, es, ts, pts = _case(name)
     pos, neg = mm.split(s[:, :nt], es, ts)
@@ -100,7 +102,7 @@ def test_matrix_and_lists_equal_the_model_under_every_variant(monkeypatch, name)
     infos = {}
     for variant in (0, 1, 2):
         eng = _engine(monkeypatch, variant)
-        got, info = _matrix_call(eng, s, nt, es, ts, pts)
+        got, info = _matrix_call(eng, s, nt, es, ts, pts, off=1 if name == "seam" else 0)
         _assert_same(got, ref, "%s matrix variant %d" % (name, variant))
         assert (info["Np"], info["Nn"]) == (len(pos), len(neg)) and info["level_bins"][0] == 1
         infos[variant] = info
@@ -113,6 +115,20 @@ def test_matrix_and_lists_equal_the_model_under_every_variant(monkeypatch, name)
         assert infos[0]["level_bins"][1] > 8 and infos[0]["level_launches"][1] > 1       # more survivors than slots
         assert infos[2]["level_launches"][1] == (infos[2]["level_bins"][1] + 1) // 2 > 1
         assert infos[2]["level_launches"][1] > infos[0]["level_launches"][1]
+
+
+@pytest.mark.parametrize("npos,nneg", [(1, 70000), (70000, 1)])
+def test_a_list_of_one_against_a_list_of_many(monkeypatch, npos, nneg):
+    """One launch of one thread's worth beside one of several workgroups, in either order of the two lists."""
+    from plda_amd import dcf
+    rng = np.random.default_rng(npos)
+    pos = (1.0 + rng.standard_normal(npos)).astype(np.float32)
+    neg = (-1.0 + rng.standard_normal(nneg)).astype(np.float32)
+    ref = mm.model(pos, neg, mm.FIVE)
+    for variant in (0, 2):
+        got, info = dcf.min_dcf_from_lists(_engine(monkeypatch, variant), pos, neg, mm.FIVE)
+        _assert_same(got, ref, "lists %d + %d variant %d" % (npos, nneg, variant))
+        assert (info["Np"], info["Nn"]) == (npos, nneg) and not info["lists_used"]
 
 
 def _torch_model(S, es, ts, pts):
@@ -198,12 +214,13 @@ def test_min_dcf_and_the_calibration_pass(monkeypatch):
         assert (rec["miss"], rec["fa"]) == (g["miss"], g["fa"]), (pt, g, rec["miss"], rec["fa"])
 
 
-@pytest.mark.parametrize("mixed,zn", [(False, False), (True, True)])
-def test_operand_form_is_score_matrix_plus_matrix_form(monkeypatch, mixed, zn):
+@pytest.mark.parametrize("mixed,zn,m,nt", [(False, False, 900, 1300), (True, True, 900, 1300), (True, True, 513, 1025)],
+                         ids=["False-False", "True-True", "True-True-513x1025"])
+def test_operand_form_is_score_matrix_plus_matrix_form(monkeypatch, mixed, zn, m, nt):
     import torch
     from plda_amd import dcf
-    d, m, nt = 48, 900, 1300
-    eng = _engine(monkeypatch, d=d, slab=256)                  # 900 rows: four slabs
+    d = 48
+    eng = _engine(monkeypatch, d=d, slab=256)                  # 900 rows: four slabs; 513 rows: three, the last of one row
     rng = np.random.default_rng(41 + mixed)
     spk = rng.standard_normal((30, d)) * 1.5
     es, ts = rng.integers(0, 30, m), rng.integers(0, 30, nt)
@@ -226,7 +243,8 @@ def test_operand_form_is_score_matrix_plus_matrix_form(monkeypatch, mixed, zn):
     pos, neg = mm.split(S.cpu().numpy(), es, ts)
     ref = mm.model(pos, neg, mm.FIVE)
     _assert_same(mat, ref, "matrix form")
-    _assert_same(opr, ref, "operand form, four slabs")
+    _assert_same(opr, ref, "operand form, slabs of 256 rows")
+    _assert_same(opr, mat, "operand form against matrix form")
     _assert_same(opr2, opr, "operand form again")
     print(oinfo)
 
