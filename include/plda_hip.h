@@ -301,6 +301,40 @@ int plda_score_matrix_snorm(plda_handle *h, const double *U, const int32_t *n_en
                             const double *V, int64_t Nt, const double *emean, const double *estd, const double *tmean,
                             const double *tstd, float *out, int64_t ld_out);
 
+/* ---- top-N retrieval with indices: closed-set identification (for each test utterance the best enrolled models) and
+ *      watch-list retrieval (for each enrolled model the best utterances of an archive); what the reference's callers do
+ *      with the scores of their nested loop (scoring/scorePLDA.py:302-318) ----
+ * S is the fp32 trials matrix [M, Nt].  A LINE is a row (axis = 0: line i is row i, its candidates are the columns j) or a
+ * column (axis = 1: line j is column j, its candidates are the rows i).  With key the order-preserving integer key of a score
+ * (-0.0 == +0.0; a total order on all bit patterns, so non-finite scores are not an error: they sort where their keys put
+ * them), the result of a line is its first top_n candidates in the order (key descending, candidate index ascending):
+ *     out_index[line, r]   int64: the candidate's index
+ *     out_scores[line, r]  fp32: the matrix entry at that index, bit for bit (a -0.0 stays -0.0)
+ * both [L, top_n] row-major, L = M (axis 0) or Nt (axis 1); nothing else is written.  The order is total, so the result does
+ * not depend on the slab height, the grid, the launch order or the run.  Exact for any data; the speed of axis 1 depends on
+ * the data (columns whose scores ascend with the row index are its worst case, descending ones its best).
+ * axis must be 0 or 1, 1 <= top_n <= min(PLDA_TOPN_MAX, length of a line), Nt <= 2^30 (axis 1: M < 2^31); else PLDA_E_INVAL.
+ *
+ * plda_topn_matrix_dev: on a finished matrix in HBM (row pitch ld >= Nt floats; columns [Nt, ld) are never used), walked in
+ * row pieces of the slab height below.  Enqueues on the handle's stream, does not synchronise, allocates nothing.
+ * plda_score_topn*: the operand form -- the matrix is never held.  The scores are those of plda_score_matrix_dev with the
+ * z-norm pair (zmean, zstd)[M] (both NULL: none) or, with one or both S-norm pairs (emean, estd)[M], (tmean, tstd)[Nt], those
+ * of plda_score_matrix_snorm_dev.  The z-norm pair together with an S-norm pair, or one pointer of a pair alone, is
+ * PLDA_E_INVAL.  The scores exist one row slab at a time, as in plda_cohort_stats_dev (the same slab buffer, height rule and
+ * PLDA_SNORM_SLAB_ROWS; the test side packed once, the distinct counts found once; a prepared test side is dropped); beyond
+ * the slab and the packed operands the call allocates nothing: the running result of axis 1 lives in the output arrays. */
+#define PLDA_TOPN_MAX 256
+int plda_topn_matrix_dev(plda_handle *h, const float *dscores, int64_t ld, int64_t M, int64_t Nt, int32_t axis, int64_t top_n,
+                         float *dout_scores, int64_t *dout_index);
+int plda_score_topn_dev(plda_handle *h, const double *dU, const int32_t *dn_enrol, int32_t n_uniform, int64_t M,
+                        const double *dV, int64_t Nt, const double *dzmean, const double *dzstd, const double *demean,
+                        const double *destd, const double *dtmean, const double *dtstd, int32_t axis, int64_t top_n,
+                        float *dout_scores, int64_t *dout_index);
+int plda_score_topn(plda_handle *h, const double *U, const int32_t *n_enrol, int32_t n_uniform, int64_t M, const double *V,
+                    int64_t Nt, const double *zmean, const double *zstd, const double *emean, const double *estd,
+                    const double *tmean, const double *tstd, int32_t axis, int64_t top_n, float *out_scores,
+                    int64_t *out_index);
+
 /* ---- z-norm: replaces MPlda_norm (pldamodule.cpp:196-256) ----
  * Every cohort row is transformed with num_examples = Nb (:224) and scored as
  * the TRAIN side with n = 1 against every model vector (:235); per model the

@@ -58,6 +58,11 @@ class PLDA(object):
     def score_trials_asnorm(self, enrol, test, e_idx, t_idx, cohort, top_k=None, calibrate=False):
         return self._instance.score_trials_asnorm(enrol, test, e_idx, t_idx, cohort, top_k, calibrate)
 
+    def top_n(self, enrol, test, n=10, per="test", znorm=True, cohort=None, top_k=None, calibrate=False):
+        """(scores float32 [L, n], ids int64 [L, n]): the n best enrol models of every test entry (per="test") or the n best
+        test entries of every enrol model (per="enrol"), best first; the trials matrix is never held."""
+        return self._instance.top_n(enrol, test, n, per, znorm, cohort, top_k, calibrate)
+
     def transform_array(self, xbar, num_examples=1):
         return self._instance.transform_array(xbar, num_examples)
 

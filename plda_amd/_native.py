@@ -111,6 +111,9 @@ SIGNATURES = {
     "plda_cohort_stats_dev": (C.c_int, [_vp, _vp, _vp, _i32, _i64, _vp, _i64, _i64, _vp, _vp]),
     "plda_score_matrix_snorm": (C.c_int, [_vp, _vp, _vp, _i32, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64]),
     "plda_score_matrix_snorm_dev": (C.c_int, [_vp, _vp, _vp, _i32, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64]),
+    "plda_topn_matrix_dev": (C.c_int, [_vp, _vp, _i64, _i64, _i64, _i32, _i64, _vp, _vp]),
+    "plda_score_topn_dev": (C.c_int, [_vp, _vp, _vp, _i32, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _vp, _vp]),
+    "plda_score_topn": (C.c_int, [_vp, _vp, _vp, _i32, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _vp, _vp]),
     "plda_calib_pass_matrix_dev": (C.c_int, [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _f64, _f64, _f64, _vp]),
     "plda_calib_pass_lists": (C.c_int, [_vp, _vp, _i64, _vp, _i64, _f64, _f64, _f64, _vp]),
     "plda_score_calib_pass_dev": (C.c_int, [_vp, _vp, _vp, _i32, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _f64, _f64, _f64, _vp]),

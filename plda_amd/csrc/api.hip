@@ -1270,6 +1270,73 @@ int plda_score_matrix_snorm(plda_handle *h, const double *U, const int32_t *n_en
   });
 }
 
+// ---------------------------------------------------------------- top-N retrieval (topn.hip)
+int plda_topn_matrix_dev(plda_handle *h, const float *dscores, int64_t ld, int64_t M, int64_t Nt, int32_t axis, int64_t top_n,
+                         float *dout_scores, int64_t *dout_index) {
+  return guarded(h, "plda_topn_matrix_dev", [&]() -> int {
+    if (!h) return PLDA_E_INVAL;
+    PLDA_LOCK(h);
+    PLDA_TRY(set_device(h));
+    return topn_matrix_device(h, dscores, ld, M, Nt, axis, top_n, dout_scores, dout_index);
+  });
+}
+
+int plda_score_topn_dev(plda_handle *h, const double *dU, const int32_t *dn_enrol, int32_t n_uniform, int64_t M, const double *dV,
+                        int64_t Nt, const double *dzmean, const double *dzstd, const double *demean, const double *destd,
+                        const double *dtmean, const double *dtstd, int32_t axis, int64_t top_n, float *dout_scores,
+                        int64_t *dout_index) {
+  return guarded(h, "plda_score_topn_dev", [&]() -> int {
+    if (!h) return PLDA_E_INVAL;
+    PLDA_LOCK(h);
+    PLDA_TRY(set_device(h));
+    return score_topn_device(h, dU, dn_enrol, n_uniform, M, dV, Nt, dzmean, dzstd, demean, destd, dtmean, dtstd, axis, top_n,
+                             dout_scores, dout_index);
+  });
+}
+
+// Host pointers: the operands and statistics are uploaded once, the [L, top_n] results come back in two copies.
+int plda_score_topn(plda_handle *h, const double *U, const int32_t *n_enrol, int32_t n_uniform, int64_t M, const double *V,
+                    int64_t Nt, const double *zmean, const double *zstd, const double *emean, const double *estd,
+                    const double *tmean, const double *tstd, int32_t axis, int64_t top_n, float *out_scores, int64_t *out_index) {
+  return guarded(h, "plda_score_topn", [&]() -> int {
+    if (!h) return PLDA_E_INVAL;
+    PLDA_LOCK(h);
+    if (!h->fitted) return fail(h, PLDA_E_NOT_FITTED, "score_topn: model not fitted");
+    if (M < 1 || Nt < 1) return fail(h, PLDA_E_INVAL, "score_topn: M = %lld, Nt = %lld (both must be >= 1)", (long long)M, (long long)Nt);
+    if (axis != 0 && axis != 1) return fail(h, PLDA_E_INVAL, "score_topn: axis = %d (must be 0: per row, or 1: per column)", axis);
+    if (top_n < 1 || top_n > PLDA_TOPN_MAX) return fail(h, PLDA_E_INVAL, "score_topn: top_n = %lld (must be in 1 ... %d)", (long long)top_n, PLDA_TOPN_MAX);
+    if (!U || !V || !out_scores || !out_index) return fail(h, PLDA_E_INVAL, "score_topn: %s is NULL", !U ? "U" : !V ? "V" : !out_scores ? "out_scores" : "out_index");
+    if ((zmean == nullptr) != (zstd == nullptr)) return fail(h, PLDA_E_INVAL, "score_topn: %s is NULL but its partner is not", zmean ? "zstd" : "zmean");
+    if ((emean == nullptr) != (estd == nullptr)) return fail(h, PLDA_E_INVAL, "score_topn: %s is NULL but its partner is not", emean ? "estd" : "emean");
+    if ((tmean == nullptr) != (tstd == nullptr)) return fail(h, PLDA_E_INVAL, "score_topn: %s is NULL but its partner is not", tmean ? "tstd" : "tmean");
+    if (!n_enrol && n_uniform <= 0) return fail(h, PLDA_E_INVAL, "score_topn: n_uniform must be > 0 when n_enrol is NULL");
+    PLDA_TRY(set_device(h));
+    const int D = h->Dout;
+    const int64_t L = axis == 0 ? M : Nt;
+    Tmp dV, dU, dN, dZm, dZs, dEm, dEs, dTm, dTs, dOs, dOi;
+    CountSet cs;                                         // from the host array: no device pass, no wait
+    if (n_enrol) score_count_set_host(n_enrol, M, &cs);
+    PLDA_TRY(upload(h, dV, V, (size_t)Nt * D * 8));
+    PLDA_TRY(upload(h, dU, U, (size_t)M * D * 8));
+    if (n_enrol) PLDA_TRY(upload(h, dN, n_enrol, (size_t)M * 4));
+    if (zmean) { PLDA_TRY(upload(h, dZm, zmean, (size_t)M * 8)); PLDA_TRY(upload(h, dZs, zstd, (size_t)M * 8)); }
+    if (emean) { PLDA_TRY(upload(h, dEm, emean, (size_t)M * 8)); PLDA_TRY(upload(h, dEs, estd, (size_t)M * 8)); }
+    if (tmean) { PLDA_TRY(upload(h, dTm, tmean, (size_t)Nt * 8)); PLDA_TRY(upload(h, dTs, tstd, (size_t)Nt * 8)); }
+    PLDA_HIP(h, dOs.alloc((size_t)L * top_n * 4));
+    PLDA_HIP(h, dOi.alloc((size_t)L * top_n * 8));
+    const int rc = score_topn_device(h, dU.as<double>(), n_enrol ? dN.as<int32_t>() : nullptr, n_uniform, M, dV.as<double>(), Nt,
+                                     zmean ? dZm.as<double>() : nullptr, zmean ? dZs.as<double>() : nullptr,
+                                     emean ? dEm.as<double>() : nullptr, emean ? dEs.as<double>() : nullptr,
+                                     tmean ? dTm.as<double>() : nullptr, tmean ? dTs.as<double>() : nullptr, axis, top_n,
+                                     dOs.as<float>(), dOi.as<int64_t>(), n_enrol ? &cs : nullptr);
+    if (rc != PLDA_OK) { (void)hipStreamSynchronize(h->stream); return rc; }
+    PLDA_HIP(h, hipMemcpyAsync(out_scores, dOs.p, (size_t)L * top_n * 4, hipMemcpyDeviceToHost, h->stream));
+    PLDA_HIP(h, hipMemcpyAsync(out_index, dOi.p, (size_t)L * top_n * 8, hipMemcpyDeviceToHost, h->stream));
+    PLDA_HIP(h, hipStreamSynchronize(h->stream));
+    return PLDA_OK;
+  });
+}
+
 // ---------------------------------------------------------------- d-vector front-end
 int plda_dvector_pool_dev(plda_handle *h, const void *dframes, int32_t dtype, int64_t T, int32_t D,
                           const int64_t *doffsets, int64_t U, int32_t method, int32_t l2norm, double *dout) {

@@ -260,8 +260,8 @@ struct plda_handle {
   int mindcf_variant = 0;        // PLDA_MINDCF_VARIANT=1: never compact the survivors into lists; 2: two nodes per read (dcf.hip; tests)
   int64_t eer_slab_rows = 0;     // PLDA_EER_SLAB_ROWS: rows per slab of plda_score_eer_dev (0: <= 4 GiB of scores)
   plda::DevBuf calib_part;       // calib.hip: one partial plda_calib_record per workgroup of a calibration pass + the reduced one
-  plda::DevBuf sn_slab;          // plda_cohort_stats_dev (snorm.hip): the row slab of cohort scores in flight
-  int64_t sn_slab_rows = 0;      // PLDA_SNORM_SLAB_ROWS: rows per slab of plda_cohort_stats_dev / plda_score_matrix_snorm_dev (0: by size)
+  plda::DevBuf sn_slab;          // plda_cohort_stats_dev (snorm.hip), plda_score_topn_dev (topn.hip): the row slab of scores in flight
+  int64_t sn_slab_rows = 0;      // PLDA_SNORM_SLAB_ROWS: rows per slab of plda_cohort_stats_dev / plda_score_matrix_snorm_dev / plda_topn_matrix_dev / plda_score_topn_dev (0: by size)
   int eer_last_passes = 0;       // full passes over the matrix the last plda_eer_matrix_dev made (1 or 3)
   const int *eigdc_flag = nullptr;   // device flag of the last direct decomposition (sym_eig_dc_status)
   int eig_variant = 0;           // PLDA_EIG_VARIANT: 0 = direct method where supported, 1 = block Jacobi always
@@ -438,6 +438,16 @@ int cohort_stats_device(plda_handle *h, const double *dX, const int32_t *dn, int
 int score_matrix_snorm_device(plda_handle *h, const double *dU, const int32_t *dn, int n_uniform, int64_t M, const double *dV,
                               int64_t Nt, const double *demean, const double *destd, const double *dtmean, const double *dtstd,
                               float *dout, int64_t ld, const CountSet *cs = nullptr, bool reuse_packed_B = false);
+// rows of one slab of fp32 scores with ld floats per row (the height rule of every walk over h->sn_slab)
+int64_t sn_slab_rows(const plda_handle *h, int64_t total_rows, int64_t ld);
+
+// ---- topn.hip (top-N selection with indices: per row, axis 0, or per column, axis 1, of a trials matrix)
+int topn_matrix_device(plda_handle *h, const float *dscores, int64_t ld, int64_t M, int64_t Nt, int axis, int64_t top_n,
+                       float *dout_scores, int64_t *dout_index);
+int score_topn_device(plda_handle *h, const double *dU, const int32_t *dn, int n_uniform, int64_t M, const double *dV, int64_t Nt,
+                      const double *dzmean, const double *dzstd, const double *demean, const double *destd, const double *dtmean,
+                      const double *dtstd, int axis, int64_t top_n, float *dout_scores, int64_t *dout_index,
+                      const CountSet *cs = nullptr);
 
 // (the labelled-trials source of the EER / DET / calibration / minDCF reductions and their score key: trial_source.hpp)
 

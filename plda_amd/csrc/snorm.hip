@@ -257,14 +257,14 @@ __global__ __launch_bounds__(256) void snorm_apply_kernel(float *__restrict__ S,
 // 50 000 x 200 000: slabs small enough to stay in the 256 MiB Infinity Cache between the GEMM and its consumer
 // (256 rows) cost 58 ms against 44 ms at 2 560 rows -- a tile grid one tile high leaves the GEMM's per-XCD queues short and
 // pays the per-launch preparation 196 times, which outweighs the consumer's cache hits.
+}  // namespace
+
 int64_t sn_slab_rows(const plda_handle *h, int64_t total_rows, int64_t ld) {
   int64_t rows = std::max<int64_t>(256, (((int64_t)2 << 30) / 4 / ld) / 256 * 256);
   if (h->sn_slab_rows > 0) rows = round_up(h->sn_slab_rows, 128);       // PLDA_SNORM_SLAB_ROWS: small slabs for the tests
   rows = std::min(rows, ((int64_t)4 << 30) / 4 / ld);
   return std::min(rows, total_rows);
 }
-
-}  // namespace
 
 int cohort_stats_device(plda_handle *h, const double *dX, const int32_t *dn, int n_uniform, int64_t R, const double *dC,
                         int64_t Nc, int64_t top_k, double *dmean, double *dstd, const CountSet *cs_in) {

@@ -577,6 +577,46 @@ class MPlda(object):
             return np.where(ok, (raw - m) / np.where(ok, s, 1.0), raw)
         return 0.5 * (side(em[e], es[e]) + side(tm[t], ts[t]))
 
+    # ------------------------------------------------- top-N retrieval / rank-N identification (csrc/topn.hip)
+    def top_n(self, enrol, test, n=10, per="test", znorm=True, cohort=None, top_k=None, calibrate=False):
+        """(scores float32 [L, n], ids int64 [L, n]): per="test" -- for each of the L test entries its n best-scoring enrol
+        models (closed-set identification); per="enrol" -- for each of the L enrol models its n best-scoring test entries
+        (watch-list retrieval).  Best first; equal scores in the order of the other side.  The ids are the other side's keys,
+        or positions where that side has none.  The scores are those of score_matrix (znorm) or, with a cohort, of
+        score_matrix_asnorm; the matrix is never held (include/plda_hip.h, "top-N retrieval").  calibrate=True: the n scores
+        are mapped with the stored calibration on the host, (float)fma(a, (double)score, b); a map with a <= 0 would not keep
+        the order and is refused."""
+        cal = self._stored_calibration(calibrate)
+        if cal is not None and not cal.a > 0.0:
+            raise ValueError("top_n: the stored calibration has a = %r; a map with a <= 0 does not keep the order of the scores" % cal.a)
+        if per not in ("test", "enrol"):
+            raise ValueError("top_n: per must be 'test' or 'enrol', got %r" % (per,))
+        ids, counts, U = self._unpack(enrol)
+        tids, _, V = self._unpack(test)
+        m, nt = U.shape[0], V.shape[0]
+        axis, lines, other = (1, nt, ids) if per == "test" else (0, m, tids)
+        if m == 0 or nt == 0:
+            raise ValueError("top_n: no trials")
+        n = int(n)
+        if n < 1:
+            raise ValueError("top_n: n = %d (must be >= 1)" % n)
+        scores, index = np.empty((lines, n), np.float32), np.empty((lines, n), np.int64)
+        zm = zs = em = es = tm = ts = None
+        if cohort is None:
+            zm, zs = self._zn_arrays(ids, znorm)
+        else:
+            Cv = self._cohort_rows(cohort)
+            em, es = self._cohort_stats(counts, U, Cv, top_k)
+            tm, ts = self._cohort_stats(np.ones(nt, np.int32), V, Cv, top_k)
+        uniform = int(counts[0]) if np.all(counts == counts[0]) else 0
+        self._ck(self._lib.plda_score_topn(self._h, _ptr(U), None if uniform else _ptr(counts), uniform, m, _ptr(V), nt,
+                                           _ptr(zm), _ptr(zs), _ptr(em), _ptr(es), _ptr(tm), _ptr(ts), axis, n,
+                                           _ptr(scores), _ptr(index)))
+        if cal is not None:
+            from . import identify as ID
+            scores = ID.affine_f32(cal.a, scores, cal.b)
+        return scores, (index if other is None else np.asarray(other, np.int64)[index])
+
     # ------------------------------------------------- score calibration (csrc/calib.hip, plda_amd/calibration.py)
     def _stored_calibration(self, calibrate):
         if not calibrate:
@@ -831,6 +871,24 @@ class MPlda(object):
         self._ck(self._lib.plda_score_matrix_snorm_dev(
             self._h, vp(dU), vp(dn), int(n_uniform), int(m), vp(dV), int(nt), vp(demean), vp(destd), vp(dtmean), vp(dtstd),
             vp(dout), int(ld)))
+
+    def topn_matrix_dev(self, dscores, ld, m, nt, axis, top_n, dout_scores, dout_index):
+        """Enqueue the top_n selection with indices on an HBM-resident fp32 matrix [m, nt] (row pitch ld): per row (axis 0) or
+        per column (axis 1); dout_scores float32, dout_index int64, both [lines, top_n]."""
+        def vp(x):
+            return C.c_void_p(int(x)) if x else None
+        self._ck(self._lib.plda_topn_matrix_dev(self._h, vp(dscores), int(ld), int(m), int(nt), int(axis), int(top_n),
+                                                vp(dout_scores), vp(dout_index)))
+
+    def score_topn_dev(self, dU, dn, n_uniform, m, dV, nt, axis, top_n, dout_scores, dout_index, dzmean=None, dzstd=None,
+                       demean=None, destd=None, dtmean=None, dtstd=None):
+        """The same selection on the trials of HBM-resident operands, the matrix never held: the scores of score_matrix_dev
+        (dzmean, dzstd) or, with demean / destd and / or dtmean / dtstd, of score_matrix_snorm_dev."""
+        def vp(x):
+            return C.c_void_p(int(x)) if x else None
+        self._ck(self._lib.plda_score_topn_dev(
+            self._h, vp(dU), vp(dn), int(n_uniform), int(m), vp(dV), int(nt), vp(dzmean), vp(dzstd), vp(demean), vp(destd),
+            vp(dtmean), vp(dtstd), int(axis), int(top_n), vp(dout_scores), vp(dout_index)))
 
     def score_prepare_dev(self, dV, nt, mixed_counts=False, n_uniform=1):
         """Pack the test side [nt, Dout] (HBM-resident fp64) once; later score_matrix_dev / sharded calls with the same
