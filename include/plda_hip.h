@@ -508,6 +508,108 @@ int plda_score_calib_fit_dev(plda_handle *h, const double *dU, const int32_t *dn
 int plda_affine_map_dev(plda_handle *h, const float *dscores, int64_t ld, int64_t M, int64_t Nt, double a, double b,
                         float *dout, int64_t ld_out);
 
+/* ---- multi-system score fusion by prior-weighted logistic regression (csrc/fusion.hip; the "fusion" half of BOSARIS /
+ * FoCal next to the calibration above; the reference writes one score file per back-end -- scoring/scorePLDA.py,
+ * scoring/scoreLDA.py -- and combines nothing, so this is the project's own extension: tests/fusion_model.py pins it).
+ *
+ * INPUTS: K systems, 1 <= K <= PLDA_FUSION_MAX_SYSTEMS; system k gives an fp32 score s_k for every trial.  Trials and their
+ * class are those of plda_eer_matrix_dev / plda_eer_lists.  Matrix form: K matrices [M, Nt], each with its own base pointer
+ * and row pitch ld[k] >= Nt, under ONE pair of speaker-id arrays (trial (i, j) is a target iff enrol_spk[i] == test_spk[j]).
+ * Lists form: K parallel target arrays of length np and K parallel non-target arrays of length nn; element t of every
+ * array is the same trial.
+ *
+ * FUSED VALUE: a fixed chain of fused multiply-adds in fp64,
+ *     y_0 = c,   y_{k+1} = fma(a_k, (double)s_k, y_k),   y = y_K.
+ * The order and the single rounding per step are part of the contract (the apply is pinned bit for bit on it).
+ *
+ * One FUSION PASS at (a[K], c, theta) uses the feature vector phi = (1, s_0, .., s_{K-1}) (K + 1 entries) and e, softplus, p,
+ * w of y exactly as the calibration pass.  Per class (g = 1 - p for a target, p for a non-target):
+ *     L = sum softplus(-/+ y),    G[j] = sum g phi_j,    H[t(i, j)] = sum w phi_i phi_j  for i <= j,  t(i, j) = j (j + 1) / 2 + i
+ * (the packing does not depend on K; at K = 1 G and H are the calibration's G0, G1 and H0, H1, H2), plus the exact integers
+ * np, nn, miss = #{target: y < theta}, fa = #{non-target: y >= theta} (compared on the CHAIN VALUE y, not on a raw score),
+ * nonfinite = the number of trials in which any system's score is non-finite, per class the fp64 minimum and maximum of y,
+ * and per system the fp32 minimum and maximum of s_k over all trials: one plda_fusion_record, with arrays dimensioned for
+ * K = 8, entries beyond K zero and n_systems stored.  A non-finite score, or an empty class, is PLDA_E_INVAL with the count
+ * in plda_last_error; the record is written all the same.  The sums are taken without floating-point atomics in a fixed
+ * order and the grid is a function of the shape and K alone: a call's record is bit-identical from run to run.  Sums and
+ * counts add across row shards (extremes by min / max).
+ *
+ * ACCURACY (derived, not measured).  The chain has K roundings, each of at most u |partial| <= u Y with u = 2^-53 and
+ * Y = |c| + sum_k |a_k s_k| -- Y and not |y|, because the chain can cancel; exp(-|y|) turns the absolute error K u Y of y
+ * into a relative one, and the term's own operations (exp, log1p, the divide, the products with phi) add c0, a handful of
+ * ulps: a non-zero term has a relative error of at most ((K + 1) Y + c0) 2^-53.  Where (K + 1) Ymax <= 2000 over the call's
+ * trials that is at most 2.3e-13 per term.  The additions: a sum is a fixed tree of 34 levels (wave, block, partial records)
+ * over RUNS that are added one term after the other, and a run of n terms adds at most (n - 1) u sum |term|.  With R the rows
+ * a workgroup walks (R = ceil(M / min(M, floor(4096 / ceil(Nt / 1024)))), a non-target run is one thread's 4 R trials; the
+ * target run is the targets of one WAVE (its lanes' targets go into one accumulator per entry), at most 256 R.  So every sum
+ * is within (2.3e-13 + (n + 34) u) sum |term| of the exact one, n = 4 R resp. the largest number of targets one wave meets:
+ * inside the calibration's band 1e-12 sum |term| as a WORST case while n <= 6900 -- every non-target sum up to R = 1700, every
+ * target sum whose waves meet fewer than 6900 targets (at 20 utterances per speaker a wave of a 100k x 100k matrix, R = 2440,
+ * meets about 130).  Beyond that (whole waves of targets over thousands of rows) 1e-12 is a typical figure, the error of
+ * such a run growing like sqrt(n) u for terms of one sign, not a bound.  A list pass has runs of n / (4096 * 256) terms.
+ *
+ * FIT: damped Newton on x = (b, a_0 .. a_{K-1}) from 0.  From the record of a pass at c = b + logit(prior):
+ *     F = pi/Np L_t + (1-pi)/Nn L_n,   g_j = -pi/Np G_t[j] + (1-pi)/Nn G_n[j],   H assembled with the same two weights.
+ * Direction: scale to unit diagonal, Hs = D^-1/2 H D^-1/2 (the outcome is then independent of each system's units: PLDA LLRs
+ * of a few hundred and LDA log-posteriors of -20 are handled alike), Cholesky of Hs, d = -H^-1 g, lambda2 = g' H^-1 g.  A
+ * diagonal entry <= 0, or a Cholesky pivot <= 1e-12, is PLDA_E_INVAL: the entries are known to 1e-12, so a smaller pivot is
+ * indistinguishable from a system that is an affine function of the others; the error names the pivot's system.  A system
+ * with smin == smax is refused before any Newton step, by name.  After the first step, a degenerate Hessian at a point
+ * where the classes are separable (the run-away of a separable set) ends the iteration, unconverged, instead of failing
+ * the call; lambda2 is then the decrement of the last point at which it could be computed, the one before.  Decrement, stopping rule (tol 0 -> 1e-18, max_iter <= 0 ->
+ * 100), Armijo backtracking with the 2^-44 |F| allowance are the calibration's, unchanged.  `passes` counts every pass of the
+ * call: one at the start, one per trial point, one more for cllr_after = F(x; 0.5) / ln 2 when prior != 0.5 (there is no
+ * "before": K systems have no common scale to report one on).  separable = (ymin_t > ymax_n at the returned point).
+ * plda_fusion_newton is the step as a pure function (no handle, no GPU; the pattern of plda_min_dcf_step): from a record taken
+ * at c = b + logit(prior) it returns F (nats), d[n_systems + 1] in the order of x, and lambda2; the device fit calls it and the
+ * CPU tests drive a whole fit through it with the host model's records.  Its refusals leave their text in plda_last_error(NULL).
+ *
+ * APPLY: plda_fusion_map_dev writes out[i, j] = (float)y, the chain with c = b: one rounding to fp32.  In place if dout is
+ * one of the inputs with ld_out == ld[k]; any other overlap is the caller's error.  Columns [Nt, ld_out) are not written.  It
+ * enqueues on the handle's stream and does not synchronise.
+ *
+ * CONVENTIONS: the pointer arrays (const float *const *, const int64_t *ld, const double *a) are HOST arrays of K entries;
+ * the matrices they name are in HBM (_dev) or on the host (_lists).  Records and fit results are HOST structures; the pass
+ * and fit calls synchronise the handle's stream, as the calibration's do.
+ *
+ * OUT OF SCOPE, each on purpose: an operand form (the systems are different models; the caller holds their matrices); the
+ * row-sharded form (the record adds across shards as the calibration's does -- unbuilt there too); quality measures / side
+ * information; regularisation; minCllr. ---- */
+#define PLDA_FUSION_MAX_SYSTEMS 8
+typedef struct plda_fusion_sums {
+  double L;
+  double G[PLDA_FUSION_MAX_SYSTEMS + 1];
+  double H[(PLDA_FUSION_MAX_SYSTEMS + 1) * (PLDA_FUSION_MAX_SYSTEMS + 2) / 2];   /* t(i, j) = j (j + 1) / 2 + i, i <= j */
+} plda_fusion_sums;
+typedef struct plda_fusion_record {
+  plda_fusion_sums sum[2];           /* [0 = non-target, 1 = target] */
+  double ymin[2], ymax[2];           /* of the chain value per class; +inf / -inf for a class without trials */
+  uint64_t np, nn, miss, fa, nonfinite;
+  float smin[PLDA_FUSION_MAX_SYSTEMS], smax[PLDA_FUSION_MAX_SYSTEMS];   /* per system over all trials */
+  int32_t n_systems, reserved;
+} plda_fusion_record;
+typedef struct plda_fusion_fit {
+  double a[PLDA_FUSION_MAX_SYSTEMS];
+  double b;
+  double objective;                  /* F(x; prior) / ln 2 */
+  double cllr_after;
+  double lambda2;                    /* the Newton decrement at the returned point */
+  int32_t iterations, passes, converged, separable;
+} plda_fusion_fit;
+int plda_fusion_pass_matrices_dev(plda_handle *h, int32_t n_systems, const float *const *dscores, const int64_t *ld, int64_t M,
+                                  int64_t Nt, const int64_t *denrol_spk, const int64_t *dtest_spk, const double *a, double c,
+                                  double theta, plda_fusion_record *out_record);
+int plda_fusion_pass_lists(plda_handle *h, int32_t n_systems, const float *const *pos, int64_t np, const float *const *neg,
+                           int64_t nn, const double *a, double c, double theta, plda_fusion_record *out_record);
+int plda_fusion_fit_matrices_dev(plda_handle *h, int32_t n_systems, const float *const *dscores, const int64_t *ld, int64_t M,
+                                 int64_t Nt, const int64_t *denrol_spk, const int64_t *dtest_spk, double prior, double tol,
+                                 int32_t max_iter, plda_fusion_fit *out_fit);
+int plda_fusion_fit_lists(plda_handle *h, int32_t n_systems, const float *const *pos, int64_t np, const float *const *neg,
+                          int64_t nn, double prior, double tol, int32_t max_iter, plda_fusion_fit *out_fit);
+int plda_fusion_map_dev(plda_handle *h, int32_t n_systems, const float *const *dscores, const int64_t *ld, int64_t M, int64_t Nt,
+                        const double *a, double b, float *dout, int64_t ld_out);
+int plda_fusion_newton(const plda_fusion_record *record, double prior, double *F, double *d, double *lambda2);
+
 /* ---- exact minimum detection cost (minDCF; NIST SRE min_Cprimary, VoxCeleb's minDCF) at up to 8 operating points,
  * without sorting (csrc/dcf.hip; the project's own extension like the calibration above: tests/mindcf_model.py pins it).
  * actDCF - minDCF is the calibration loss of a system.

@@ -42,6 +42,15 @@ class PLDA(object):
         are the speakers, test_speaker names the speaker of each test entry); returns a plda_amd.calibration.Calibration."""
         return self._instance.calibrate(enrol, test, test_speaker, prior, znorm, cohort, top_k)
 
+    def fuse(self, enrol, test, test_speaker, others, prior=0.5, znorm=True, cohort=None, top_k=None):
+        """Fit the linear fusion of this model's trials matrix with the fp32 [M, Nt] matrices `others` of other systems
+        (prior-weighted logistic regression); returns a plda_amd.fusion.Fusion (not stored, not saved)."""
+        return self._instance.fuse(enrol, test, test_speaker, others, prior, znorm, cohort, top_k)
+
+    def score_matrix_fused(self, enrol, test, others, fusion, znorm=True, cohort=None, top_k=None):
+        """float32 [M, Nt]: the fused value of `fusion` over this model's matrix and `others`."""
+        return self._instance.score_matrix_fused(enrol, test, others, fusion, znorm, cohort, top_k)
+
     def min_dcf(self, enrol, test, test_speaker, points=((0.01, 1.0, 1.0),), znorm=True, cohort=None, top_k=None, calibrate=False):
         """The exact minimum detection cost of the trials between two transform() results at up to 8 operating points
         (prior, c_miss, c_fa); returns (one dict per point, info)."""

@@ -7,11 +7,14 @@ Layout (only what the hot path needs):
   libplda.py  `MPlda`: counterpart of the reference's CPython type libplda.MPlda
   sharding.py row-sharded trials matrix across ranks (torch.distributed / RCCL)
   calibration.py linear score calibration, Cllr, actual DCF (csrc/calib.hip)
+  fusion.py   linear fusion of K systems' scores by logistic regression (csrc/fusion.hip)
   identify.py rank-N identification rates and the CMC curve from the ids of MPlda.top_n (csrc/topn.hip); pure NumPy
 """
 from .libplda import MPlda  # noqa: F401
 from . import calibration  # noqa: F401
+from . import fusion  # noqa: F401
 from . import identify  # noqa: F401
 from .calibration import Calibration  # noqa: F401
+from .fusion import Fusion  # noqa: F401
 
-__all__ = ["MPlda", "Calibration", "calibration", "identify"]
+__all__ = ["MPlda", "Calibration", "Fusion", "calibration", "fusion", "identify"]

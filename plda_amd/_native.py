@@ -127,6 +127,12 @@ SIGNATURES = {
     "plda_min_dcf_step": (C.c_int, [_i32, _i64, _vp, _vp, _i32, _vp, _vp, _i64, _vp, C.POINTER(_i64)]),
     "plda_min_dcf_finish": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _vp]),
     "plda_affine_map_dev": (C.c_int, [_vp, _vp, _i64, _i64, _i64, _f64, _f64, _vp, _i64]),
+    "plda_fusion_pass_matrices_dev": (C.c_int, [_vp, _i32, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _f64, _f64, _vp]),
+    "plda_fusion_pass_lists": (C.c_int, [_vp, _i32, _vp, _i64, _vp, _i64, _vp, _f64, _f64, _vp]),
+    "plda_fusion_fit_matrices_dev": (C.c_int, [_vp, _i32, _vp, _vp, _i64, _i64, _vp, _vp, _f64, _f64, _i32, _vp]),
+    "plda_fusion_fit_lists": (C.c_int, [_vp, _i32, _vp, _i64, _vp, _i64, _f64, _f64, _i32, _vp]),
+    "plda_fusion_map_dev": (C.c_int, [_vp, _i32, _vp, _vp, _i64, _i64, _vp, _f64, _vp, _i64]),
+    "plda_fusion_newton": (C.c_int, [_vp, _f64, _vp, _vp, _vp]),
 }
 
 # plda_collectives / plda_host_collectives (include/plda_hip.h): callback tables of the multi-GPU entry points

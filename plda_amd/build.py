@@ -17,7 +17,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 SO = os.path.join(LIBDIR, "libplda_hip.so")
 SO_DIAG = os.path.join(LIBDIR, "libplda_hip_diag.so")
-SOURCES = ["api.hip", "score.hip", "linalg.hip", "fit.hip", "frontend.hip", "eer.hip", "operand_slabs.hip", "lda.hip", "comm.hip", "eig_dc.hip", "hostio.hip", "transform.hip", "snorm.hip", "calib.hip", "dcf.hip", "topn.hip"]
+SOURCES = ["api.hip", "score.hip", "linalg.hip", "fit.hip", "frontend.hip", "eer.hip", "operand_slabs.hip", "lda.hip", "comm.hip", "eig_dc.hip", "hostio.hip", "transform.hip", "snorm.hip", "calib.hip", "dcf.hip", "topn.hip", "fusion.hip"]
 HEADERS = [os.path.join(CSRC, "common.hpp"), os.path.join(CSRC, "trial_source.hpp"), os.path.join(CSRC, "hostio.hpp"), os.path.join(CSRC, "sweep_mfma.inc"), os.path.join(CSRC, "score_bt4.inc"), os.path.join(CSRC, "score_bf16x3.inc"), os.path.join(CSRC, "syrk_blk.inc"), os.path.join(HERE, "..", "include", "plda_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics",
          "-Wall", "-Wno-unused-function", "-Wno-unused-result"]
@@ -27,7 +27,18 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-ato
 # rewrites it into a wave reduction that reads the result back on the spot (a memory round trip in the MFMA stream); the
 # tile fetch's two values are deliberately defined on one path only (score_bt4.inc: the warning is silenced by a pragma around
 # that include, not for the file)
-EXTRA = {"score.hip": ["-mllvm", "-amdgpu-atomic-optimizer-strategy=None"]}
+# fusion.hip: machine LICM hoists the fp64 constants of exp / log1p out of the element loop into registers that live through
+# the whole walk.  With the pass ON (the compiler's default) the labelled pass reports, K = 1 .. 8: 126 / 156 / 164 / 190 /
+# 197 / 223 / 249 / 256 VGPRs, scalar-register spills from K = 5 on (2 / 4 / 6 / 14) and at K = 8 19 spilled VGPRs = 80 bytes
+# of scratch per lane; with it OFF 94 .. 244, no spill and no scratch anywhere (the table in csrc/fusion.hip).  It is a hidden
+# LLVM option and applies to the whole file (the list, map and reduce kernels lose nothing they had: their loops hold no
+# hoistable constants beyond the same exp / log1p ones); if a toolchain drops it the build fails loudly on the unknown option --
+# then remove it and accept the K >= 5 spills, or split the constants' live ranges by hand.  Reproduce the table with
+#   hipcc --offload-arch=gfx950 -O3 -std=c++17 -munsafe-fp-atomics -mllvm -disable-machine-licm \
+#         -Rpass-analysis=kernel-resource-usage -c plda_amd/csrc/fusion.hip -o /dev/null
+# Its effect on speed has not been measured apart from the rest (scripts/fusion_bench.py times the kernels as built).
+EXTRA = {"score.hip": ["-mllvm", "-amdgpu-atomic-optimizer-strategy=None"],
+         "fusion.hip": ["-mllvm", "-disable-machine-licm"]}
 
 
 def _stale(target, deps):

@@ -187,6 +187,26 @@ int with_host_lists(plda_handle *h, const char *fn, const float *pos, int64_t np
     return body(dP.as<float>(), dN.as<float>());
   });
 }
+// the host-list forms: K target and K non-target arrays in caller memory, uploaded, then body(device pointer arrays)
+template <typename F>
+int with_host_fusion_lists(plda_handle *h, const char *fn, int32_t K, const float *const *pos, int64_t np, const float *const *neg,
+                           int64_t nn, bool outputs_ok, F &&body) noexcept {
+  return guarded(h, fn, [&]() -> int {
+    if (!h) return PLDA_E_INVAL;
+    PLDA_LOCK(h);
+    if (!outputs_ok) return fail(h, PLDA_E_INVAL, "%s: the output structure or the weight array is NULL", fn);
+    PLDA_TRY(fusion_list_args_check(h, fn, K, pos, np, neg, nn));     // (fusion.hip: the one place that checks them)
+    PLDA_TRY(set_device(h));
+    Tmp dP[PLDA_FUSION_MAX_SYSTEMS], dN[PLDA_FUSION_MAX_SYSTEMS];
+    const float *pp[PLDA_FUSION_MAX_SYSTEMS], *pn[PLDA_FUSION_MAX_SYSTEMS];
+    for (int k = 0; k < K; ++k) {
+      PLDA_TRY(upload(h, dP[k], pos[k], (size_t)np * 4));
+      PLDA_TRY(upload(h, dN[k], neg[k], (size_t)nn * 4));
+      pp[k] = dP[k].as<float>(); pn[k] = dN[k].as<float>();
+    }
+    return body(pp, pn);
+  });
+}
 }  // namespace
 
 extern "C" {
@@ -1893,6 +1913,60 @@ int plda_affine_map_dev(plda_handle *h, const float *dscores, int64_t ld, int64_
     PLDA_TRY(set_device(h));
     return affine_map_device(h, dscores, ld, M, Nt, a, b, dout, ld_out);
   });
+}
+
+// ---------------------------------------------------------------- multi-system score fusion (fusion.hip)
+int plda_fusion_pass_matrices_dev(plda_handle *h, int32_t n_systems, const float *const *dscores, const int64_t *ld, int64_t M,
+                                  int64_t Nt, const int64_t *denrol_spk, const int64_t *dtest_spk, const double *a, double c,
+                                  double theta, plda_fusion_record *out_record) {
+  return guarded(h, "plda_fusion_pass_matrices_dev", [&]() -> int {
+    if (!h) return PLDA_E_INVAL;
+    PLDA_LOCK(h);
+    PLDA_TRY(set_device(h));
+    return fusion_pass_matrices_device(h, n_systems, dscores, ld, M, Nt, denrol_spk, dtest_spk, a, c, theta, out_record);
+  });
+}
+
+int plda_fusion_fit_matrices_dev(plda_handle *h, int32_t n_systems, const float *const *dscores, const int64_t *ld, int64_t M,
+                                 int64_t Nt, const int64_t *denrol_spk, const int64_t *dtest_spk, double prior, double tol,
+                                 int32_t max_iter, plda_fusion_fit *out_fit) {
+  return guarded(h, "plda_fusion_fit_matrices_dev", [&]() -> int {
+    if (!h) return PLDA_E_INVAL;
+    PLDA_LOCK(h);
+    PLDA_TRY(set_device(h));
+    return fusion_fit_matrices_device(h, n_systems, dscores, ld, M, Nt, denrol_spk, dtest_spk, prior, tol, max_iter, out_fit);
+  });
+}
+
+int plda_fusion_pass_lists(plda_handle *h, int32_t n_systems, const float *const *pos, int64_t np, const float *const *neg,
+                           int64_t nn, const double *a, double c, double theta, plda_fusion_record *out_record) {
+  return with_host_fusion_lists(h, "plda_fusion_pass_lists", n_systems, pos, np, neg, nn, out_record != nullptr && a != nullptr,
+                                [&](const float *const *dpos, const float *const *dneg) {
+                                  return fusion_pass_lists_device(h, n_systems, dpos, np, dneg, nn, a, c, theta, out_record);
+                                });
+}
+
+int plda_fusion_fit_lists(plda_handle *h, int32_t n_systems, const float *const *pos, int64_t np, const float *const *neg,
+                          int64_t nn, double prior, double tol, int32_t max_iter, plda_fusion_fit *out_fit) {
+  return with_host_fusion_lists(h, "plda_fusion_fit_lists", n_systems, pos, np, neg, nn, out_fit != nullptr,
+                                [&](const float *const *dpos, const float *const *dneg) {
+                                  return fusion_fit_lists_device(h, n_systems, dpos, np, dneg, nn, prior, tol, max_iter, out_fit);
+                                });
+}
+
+int plda_fusion_map_dev(plda_handle *h, int32_t n_systems, const float *const *dscores, const int64_t *ld, int64_t M, int64_t Nt,
+                        const double *a, double b, float *dout, int64_t ld_out) {
+  return guarded(h, "plda_fusion_map_dev", [&]() -> int {
+    if (!h) return PLDA_E_INVAL;
+    PLDA_LOCK(h);
+    PLDA_TRY(set_device(h));
+    return fusion_map_device(h, n_systems, dscores, ld, M, Nt, a, b, dout, ld_out);
+  });
+}
+
+// the Newton step: a pure function, no handle (include/plda_hip.h)
+int plda_fusion_newton(const plda_fusion_record *record, double prior, double *F, double *d, double *lambda2) {
+  return guarded(nullptr, "plda_fusion_newton", [&]() -> int { return fusion_newton(record, prior, F, d, lambda2); });
 }
 
 }  // extern "C"

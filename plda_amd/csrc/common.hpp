@@ -260,6 +260,7 @@ struct plda_handle {
   int mindcf_variant = 0;        // PLDA_MINDCF_VARIANT=1: never compact the survivors into lists; 2: two nodes per read (dcf.hip; tests)
   int64_t eer_slab_rows = 0;     // PLDA_EER_SLAB_ROWS: rows per slab of plda_score_eer_dev (0: <= 4 GiB of scores)
   plda::DevBuf calib_part;       // calib.hip: one partial plda_calib_record per workgroup of a calibration pass + the reduced one
+  plda::DevBuf fusion_part;      // fusion.hip: one partial plda_fusion_record per workgroup of a fusion pass + the reduced one
   plda::DevBuf sn_slab;          // plda_cohort_stats_dev (snorm.hip), plda_score_topn_dev (topn.hip): the row slab of scores in flight
   int64_t sn_slab_rows = 0;      // PLDA_SNORM_SLAB_ROWS: rows per slab of plda_cohort_stats_dev / plda_score_matrix_snorm_dev / plda_topn_matrix_dev / plda_score_topn_dev (0: by size)
   int eer_last_passes = 0;       // full passes over the matrix the last plda_eer_matrix_dev made (1 or 3)

@@ -180,6 +180,22 @@ int score_calib_fit_device(plda_handle *h, const double *dU, const int32_t *dn, 
                            double tol, int max_iter, plda_calib_fit *out);
 int affine_map_device(plda_handle *h, const float *dscores, int64_t ld, int64_t M, int64_t Nt, double a, double b, float *dout,
                       int64_t ld_out);
+// ---- fusion.hip (K systems in lock-step; pointer arrays are HOST arrays of K device pointers)
+int fusion_pass_matrices_device(plda_handle *h, int K, const float *const *dscores, const int64_t *ld, int64_t M, int64_t Nt,
+                                const int64_t *despk, const int64_t *dtspk, const double *a, double c, double theta,
+                                plda_fusion_record *out);
+int fusion_fit_matrices_device(plda_handle *h, int K, const float *const *dscores, const int64_t *ld, int64_t M, int64_t Nt,
+                               const int64_t *despk, const int64_t *dtspk, double prior, double tol, int max_iter, plda_fusion_fit *out);
+int fusion_pass_lists_device(plda_handle *h, int K, const float *const *dpos, int64_t np, const float *const *dneg, int64_t nn,
+                             const double *a, double c, double theta, plda_fusion_record *out);
+int fusion_fit_lists_device(plda_handle *h, int K, const float *const *dpos, int64_t np, const float *const *dneg, int64_t nn,
+                            double prior, double tol, int max_iter, plda_fusion_fit *out);
+int fusion_map_device(plda_handle *h, int K, const float *const *dscores, const int64_t *ld, int64_t M, int64_t Nt, const double *a,
+                      double b, float *dout, int64_t ld_out);
+// the argument check of the list forms (K, the two pointer arrays, their K entries, the lengths): used by the host-list entry
+// points before they upload, and by the device-list drivers
+int fusion_list_args_check(plda_handle *h, const char *fn, int K, const float *const *pos, int64_t np, const float *const *neg, int64_t nn);
+int fusion_newton(const plda_fusion_record *r, double prior, double *F, double *d, double *lambda2);
 // ---- comm.hip: the row-sharded forms over the installed communicator
 int eer_matrix_comm_device(plda_handle *h, const float *dscores, int64_t ld, int64_t M, int64_t Nt, const int64_t *despk,
                            const int64_t *dtspk, double *out);

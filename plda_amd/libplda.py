@@ -741,6 +741,70 @@ class MPlda(object):
         """The stored `plda_amd.calibration.Calibration`, or None."""
         return self._calibration
 
+    # ------------------------------------------------- multi-system score fusion (csrc/fusion.hip, plda_amd/fusion.py)
+    def _own_matrix_on_device(self, ids, counts, U, V, znorm, cohort, top_k):
+        """This model's fp32 [M, Nt] trials matrix as a device tensor, normalised as score_matrix (znorm) or, with a cohort,
+        score_matrix_asnorm would."""
+        if cohort is None:
+            return self._trials_matrix_on_device(counts, U, V, zn=self._zn_arrays(ids, znorm))
+        Cv = self._cohort_rows(cohort)
+        em, es = self._cohort_stats(counts, U, Cv, top_k)
+        tm, ts = self._cohort_stats(np.ones(V.shape[0], np.int32), V, Cv, top_k)
+        return self._trials_matrix_on_device(counts, U, V, sn=(em, es, tm, ts))
+
+    def _other_matrices_on_device(self, others, m, nt, what):
+        """The other systems' fp32 [M, Nt] matrices as device tensors (NumPy arrays are uploaded; torch device tensors are
+        taken as they are, last dimension contiguous) and their row pitches."""
+        import torch
+        if len(others) < 1 or len(others) > 7:
+            raise ValueError("%s: 1 .. 7 other systems (a fusion has at most 8)" % what)
+        out = []
+        for i, o in enumerate(others):
+            if not isinstance(o, torch.Tensor):
+                o = self._to_device(np.ascontiguousarray(o, np.float32))
+            if o.dtype != torch.float32 or tuple(o.shape) != (m, nt) or not o.is_cuda or (nt > 1 and o.stride(1) != 1):
+                raise ValueError("%s: others[%d] must be an fp32 [%d, %d] matrix (NumPy, or a torch device tensor with "
+                                 "contiguous rows)" % (what, i, m, nt))
+            out.append(o)
+        return out, [int(o.stride(0)) if m > 1 else nt for o in out]
+
+    def fuse(self, enrol, test, test_speaker, others, prior=0.5, znorm=True, cohort=None, top_k=None):
+        """Fit the linear fusion llr = b + a_0 * (this model's score) + sum_k a_k * others[k-1] by prior-weighted logistic
+        regression (include/plda_hip.h, "multi-system score fusion") on the trials between two transform() results.  This
+        model's matrix is normalised exactly as `calibrate` would; `others` is a sequence of fp32 [M, Nt] matrices of other
+        systems in the same row / column order, NumPy or torch device tensors (e.g. the transposed LDA.predict_log_proba
+        columns of the enrolled speakers).  Returns the `plda_amd.fusion.Fusion`; it is NOT stored and not written by save():
+        its weights belong to a set of systems, not to this model.  A separable or unconverged fit raises a RuntimeWarning."""
+        from . import fusion as FU
+        ids, counts, U, V, tspk = self._labelled_trials(enrol, test, test_speaker, "fuse")
+        m, nt = U.shape[0], V.shape[0]
+        oth, lds = self._other_matrices_on_device(others, m, nt, "fuse")
+        despk, dtspk = self._to_device(np.ascontiguousarray(ids, np.int64)), self._to_device(tspk)
+        S = self._own_matrix_on_device(ids, counts, U, V, znorm, cohort, top_k)
+        import torch
+        torch.cuda.synchronize(S.device)     # (uploads and the callers' tensors live on torch's streams)
+        return FU.fit_from_matrices_dev(self, [S.data_ptr()] + [o.data_ptr() for o in oth], [nt] + lds, m, nt, despk.data_ptr(),
+                                        dtspk.data_ptr(), prior=prior)
+
+    def score_matrix_fused(self, enrol, test, others, fusion, znorm=True, cohort=None, top_k=None):
+        """float32 [M, Nt]: the fused value of `fusion` (a `plda_amd.fusion.Fusion` over this model's matrix, normalised as in
+        `fuse`, followed by `others`), the FMA chain of the header rounded once to fp32."""
+        from . import fusion as FU
+        ids, counts, U = self._unpack(enrol)
+        _, _, V = self._unpack(test)
+        m, nt = U.shape[0], V.shape[0]
+        if m == 0 or nt == 0:
+            return np.empty((m, nt), np.float32)
+        oth, lds = self._other_matrices_on_device(others, m, nt, "score_matrix_fused")
+        if fusion.n_systems != 1 + len(oth):
+            raise ValueError("score_matrix_fused: the fusion was fitted on %d systems, got %d" % (fusion.n_systems, 1 + len(oth)))
+        S = self._own_matrix_on_device(ids, counts, U, V, znorm, cohort, top_k)
+        import torch
+        torch.cuda.synchronize(S.device)
+        FU.apply_dev(self, [S.data_ptr()] + [o.data_ptr() for o in oth], [nt] + lds, m, nt, fusion, S.data_ptr(), nt)
+        self.synchronize()
+        return S.cpu().numpy()
+
     # ------------------------------------------------- device-resident path
     def set_stream(self, hip_stream):
         """Enqueue on this hipStream_t (an int handle, e.g. torch.cuda.current_stream().cuda_stream;
