@@ -813,6 +813,88 @@ int plda_min_dcf_matrix_comm_dev(plda_handle *h, const float *dscores, int64_t l
                                  const int64_t *denrol_spk, const int64_t *dtest_spk, int32_t n_points,
                                  const plda_dcf_point *points, plda_min_dcf *out, plda_min_dcf_info *info);
 
+/* ---- PLDA domain adaptation (K14): moving the model on the handle -- the Kaldi `Plda` held at pldamodule.cpp:29 -- onto
+ * another domain, without labels (unsupervised adaptation) or by interpolation with a second model (supervised).  The
+ * reference has NO counterpart: it can only refit.  The unsupervised update restates Kaldi's PldaUnsupervisedAdaptor
+ * (ivector/plda.h, the class behind ivector-adapt-plda) and its defaults from the published algorithm; PARITY UNPINNED, like
+ * the rest of the PLDA path (no Kaldi build to compare with).  All fp64.
+ *
+ * The model is (mean m [D], transform T [D, D], psi [D]); its covariances are within-class W = (T^T T)^-1, between-class
+ * B = T^-1 diag(psi) T^-T, total W + B.  Adaptation needs the SQUARE model: on a handle truncated with plda_truncate
+ * (Dout < Din) every entry point below returns PLDA_E_INVAL ("adapt before truncating").
+ *
+ * Statistics.  The pilot p is the model mean at the first accumulation after a reset.  Over the rows x_i [Din] with weights
+ * w_i >= 0 (NULL: 1) the record is  tw = sum w_i,  rows = the number of rows,  S1 = sum w_i (x_i - p),
+ * S2 = sum w_i (x_i - p)(x_i - p)^T  (symmetric, both triangles stored)  and p itself.  The sums are taken about p, not about
+ * 0 as Kaldi's AddStats takes them: the variance then does not come out of the cancellation sum x x^T / tw - mean mean^T
+ * (at D = 24, 4000 rows of unit spread offset by 1e5 that form loses 7e-5 of the variance, this one 4e-16).  The record adds
+ * over calls, and with an equal pilot over handles and ranks (plda_adapt_get_stats / plda_adapt_add_stats; no collective
+ * is built in).  The rows are read once, slab by slab: each slab is written as centred rows [x - p | 1] into a bounded
+ * buffer and multiplied by the weighted fp64 SYRK of the fit's statistics pass, the augmented column giving S2, S1 and tw in
+ * one product; the slabs' results are added in the order of the rows.  Rows per slab: 64 MiB of centred rows, at most 65 536
+ * rows; PLDA_ADAPT_SLAB_ROWS in the environment at plda_create overrides it.  The record of a call is bit-identical from
+ * run to run (no floating-point atomics); the device scratch of a call does not grow with N.
+ *
+ * Update with (within_scale ws, between_scale bs, mean_diff_scale mds; Kaldi's defaults 0.3 / 0.7 / 1.0):
+ *   1. delta = S1 / tw, mean' = p + delta
+ *   2. V = S2 / tw - (1 - mds) delta delta^T      (Kaldi's centred variance + mds delta delta^T; mds = 1: S2 / tw exactly)
+ *   3. Tm = diag(1 / sqrt(1 + psi)) T             (the basis in which the model's total covariance is the identity)
+ *   4. Vp = Tm V Tm^T, symmetrised, = P diag(s) P^T, s descending
+ *   5. e_i = max(s_i - 1, 0)                      (the variance the data shows beyond the model's)
+ *   6. E = Tm^-1 P diag(e) P^T Tm^-T,  Tm^-1 = W T^T diag(sqrt(1 + psi))
+ *   7. W' = W + ws E,  B' = B + bs E
+ * and the new model is mean', (transform, psi) = the simultaneous diagonalisation of (W', B') exactly as the fit's GetOutput
+ * makes it (Cholesky whitening of W', eigenvalues descending, floored at 0), offset refreshed.  (Kaldi adds ws e and bs e to
+ * the diagonals of P^T diag(1 / (1 + psi)) P and P^T diag(psi / (1 + psi)) P and maps back with (P^T Tm)^-1: the same thing;
+ * the form above leaves the unchanged part alone and needs only the SPD inverse.)
+ * Blend with a second model (mean2, T2, psi2) of the same D and alpha, alpha_mean in [0, 1]:  W' = (1 - alpha) W + alpha W2,
+ * B' likewise, mean' = (1 - alpha_mean) m + alpha_mean mean2, the new model their simultaneous diagonalisation.
+ *
+ * Both enqueue their whole chain of D x D products, the SPD inverse, the eigensolver and the diagonalisation without a host
+ * round trip and synchronise once to read the status words, the eigenvalues and the new model (then once more for the
+ * refreshed offset, as plda_smooth does).  On any failure (a factorisation flag, the eigensolver) the OLD model stays
+ * installed, untouched, and PLDA_E_NUMERIC is returned.  On success the handle behaves as after plda_set_model: a test side
+ * prepared with plda_score_prepare_dev is dropped, plda_score_one sees the new model.  Update and blend are supported up to
+ * D = 2048, the limit of the direct eigensolver (its fallback, block Jacobi, stops at 1024); a larger model is PLDA_E_INVAL,
+ * checked before any work.  The statistics entry points have no such limit.
+ *
+ *   plda_adapt_reset            forgets the record (the next accumulation takes the pilot anew)
+ *   plda_adapt_accumulate_dev   dX [N, Din] and dweights [N] (nullable) in HBM; plda_adapt_accumulate: the same from host
+ *                               memory.  Both synchronise (they report rejected rows).  N == 0: nothing happens.  N < 0, a Din
+ *                               that is not the model's, a model that is not fitted (PLDA_E_NOT_FITTED) or truncated: an
+ *                               error.  A non-finite row or a negative / non-finite weight: PLDA_E_INVAL with the counts in
+ *                               plda_last_error, the record left as it was before the call.  A record taken under an
+ *                               earlier model (the model changed since the pilot): PLDA_E_INVAL ("reset first").
+ *   plda_adapt_get_stats        host outputs, any NULL: tw, rows, pilot [D], s1 [D], s2 [D, D] (an empty record: zeros, the
+ *                               pilot that would be taken).  D is the MODEL's dimension, which is what the caller can size
+ *                               its arrays from: a record whose dimension differs from the model's (the model was replaced by
+ *                               one of another D since the pilot) is PLDA_E_INVAL ("reset first") and nothing is written.  A
+ *                               record of an earlier model of the same D stays readable.
+ *   plda_adapt_add_stats        adds the record of another handle or rank.  Its pilot must equal this record's bit for bit
+ *                               (PLDA_E_INVAL otherwise); an empty record adopts it only if it equals the model mean.
+ *   plda_adapt_update           eig [D] (host, nullable) receives s; info (nullable) the summary below.  tw <= 0, a negative
+ *                               or non-finite scale, or a second update on the same record: PLDA_E_INVAL.
+ *   plda_blend_model            host arrays, as plda_set_model takes them ---- */
+typedef struct {
+  double tot_weight;    /* tw */
+  int64_t rows;
+  int32_t dim;          /* D */
+  int32_t n_excess;     /* number of s_i > 1 */
+  double eig_max;       /* s_0 */
+  double eig_min;       /* s_{D-1} */
+  double mean_shift;    /* ||delta||_2 */
+} plda_adapt_info;
+int plda_adapt_reset(plda_handle *h);
+int plda_adapt_accumulate_dev(plda_handle *h, const double *dX, int64_t N, int32_t Din, const double *dweights);
+int plda_adapt_accumulate(plda_handle *h, const double *X, int64_t N, int32_t Din, const double *weights);
+int plda_adapt_get_stats(plda_handle *h, double *tw, int64_t *rows, double *pilot, double *s1, double *s2);
+int plda_adapt_add_stats(plda_handle *h, double tw, int64_t rows, const double *pilot, const double *s1,
+                         const double *s2);
+int plda_adapt_update(plda_handle *h, double within_scale, double between_scale, double mean_diff_scale,
+                      double *eig, plda_adapt_info *info);
+int plda_blend_model(plda_handle *h, int32_t D, const double *mean2, const double *transform2, const double *psi2,
+                     double alpha, double alpha_mean);
+
 /* ---- LDA: replaces the reference's second model, the pure-Python
  * class LDA of python/liblda/lda.py (used by scoring/scoreLDA.py:175,224,241), on the same
  * handle.  All fp64.  solver: 0 = 'svd' (lda.py:171-209), 1 = 'eigen' (:134-169),

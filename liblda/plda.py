@@ -72,6 +72,17 @@ class PLDA(object):
         test entries of every enrol model (per="enrol"), best first; the trials matrix is never held."""
         return self._instance.top_n(enrol, test, n, per, znorm, cohort, top_k, calibrate)
 
+    def adapt(self, x, weights=None, within_scale=0.3, between_scale=0.7, mean_diff_scale=1.0):
+        """Unsupervised domain adaptation of the model to the unlabelled rows x (Kaldi's PldaUnsupervisedAdaptor restated,
+        parity unpinned); returns a plda_amd.adaptation.Adaptation.  Clears the z-norm statistics and the stored calibration."""
+        return self._instance.adapt(x, weights, within_scale, between_scale, mean_diff_scale)
+
+    def blend(self, other, alpha, alpha_mean=None):
+        """Interpolate this model's covariances (and mean) with those of `other` (a PLDA, an MPlda or a (mean, transform,
+        psi) triple); clears the z-norm statistics and the stored calibration."""
+        self._instance.blend(other, alpha, alpha_mean)
+        return self
+
     def transform_array(self, xbar, num_examples=1):
         return self._instance.transform_array(xbar, num_examples)
 

@@ -8,13 +8,16 @@ Layout (only what the hot path needs):
   sharding.py row-sharded trials matrix across ranks (torch.distributed / RCCL)
   calibration.py linear score calibration, Cllr, actual DCF (csrc/calib.hip)
   fusion.py   linear fusion of K systems' scores by logistic regression (csrc/fusion.hip)
+  adaptation.py the result of MPlda.adapt: unsupervised PLDA domain adaptation and model interpolation (csrc/adapt.hip)
   identify.py rank-N identification rates and the CMC curve from the ids of MPlda.top_n (csrc/topn.hip); pure NumPy
 """
 from .libplda import MPlda  # noqa: F401
 from . import calibration  # noqa: F401
 from . import fusion  # noqa: F401
 from . import identify  # noqa: F401
+from . import adaptation  # noqa: F401
 from .calibration import Calibration  # noqa: F401
 from .fusion import Fusion  # noqa: F401
+from .adaptation import Adaptation  # noqa: F401
 
-__all__ = ["MPlda", "Calibration", "Fusion", "calibration", "fusion", "identify"]
+__all__ = ["MPlda", "Calibration", "Fusion", "Adaptation", "calibration", "fusion", "identify", "adaptation"]

@@ -133,7 +133,20 @@ SIGNATURES = {
     "plda_fusion_fit_lists": (C.c_int, [_vp, _i32, _vp, _i64, _vp, _i64, _f64, _f64, _i32, _vp]),
     "plda_fusion_map_dev": (C.c_int, [_vp, _i32, _vp, _vp, _i64, _i64, _vp, _f64, _vp, _i64]),
     "plda_fusion_newton": (C.c_int, [_vp, _f64, _vp, _vp, _vp]),
+    "plda_adapt_reset": (C.c_int, [_vp]),
+    "plda_adapt_accumulate_dev": (C.c_int, [_vp, _vp, _i64, _i32, _vp]),
+    "plda_adapt_accumulate": (C.c_int, [_vp, _vp, _i64, _i32, _vp]),
+    "plda_adapt_get_stats": (C.c_int, [_vp, C.POINTER(_f64), C.POINTER(_i64), _vp, _vp, _vp]),
+    "plda_adapt_add_stats": (C.c_int, [_vp, _f64, _i64, _vp, _vp, _vp]),
+    "plda_adapt_update": (C.c_int, [_vp, _f64, _f64, _f64, _vp, _vp]),
+    "plda_blend_model": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _f64, _f64]),
 }
+
+
+class AdaptInfo(C.Structure):
+    """plda_adapt_info (include/plda_hip.h)."""
+    _fields_ = [("tot_weight", _f64), ("rows", _i64), ("dim", _i32), ("n_excess", _i32), ("eig_max", _f64),
+                ("eig_min", _f64), ("mean_shift", _f64)]
 
 # plda_collectives / plda_host_collectives (include/plda_hip.h): callback tables of the multi-GPU entry points
 PLDA_DT_F64, PLDA_DT_U64, PLDA_DT_U32 = 0, 1, 2

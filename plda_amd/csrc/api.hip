@@ -289,6 +289,7 @@ int plda_create(int device, plda_handle **out) {
     if (const char *v = std::getenv("PLDA_MINDCF_VARIANT")) h->mindcf_variant = std::atoi(v);
     if (const char *v = std::getenv("PLDA_EER_SLAB_ROWS")) h->eer_slab_rows = std::atoll(v);
     if (const char *v = std::getenv("PLDA_SNORM_SLAB_ROWS")) h->sn_slab_rows = std::atoll(v);
+    if (const char *v = std::getenv("PLDA_ADAPT_SLAB_ROWS")) h->ad_slab_rows = std::atoll(v);
     if (const char *v = std::getenv("PLDA_HIP_TRACE")) h->trace_on = h->trace_print = std::atoi(v) != 0;
     if (const char *v = std::getenv("PLDA_HOST_VARIANT")) h->host_variant = std::atoi(v);
     if (const char *v = std::getenv("PLDA_SWEEP_VARIANT")) h->sweep_variant = std::atoi(v);
@@ -569,6 +570,71 @@ int plda_smooth(plda_handle *h, double factor) {
     PLDA_HIP(h, hipMemcpyAsync(h->h_psi.data(), h->d_psi.p, (size_t)h->Dout * 8, hipMemcpyDeviceToHost, h->stream));
     ++h->model_epoch;
     return refresh_offset(h);
+  });
+}
+
+// ---------------------------------------------------------------- domain adaptation (adapt.hip)
+int plda_adapt_reset(plda_handle *h) {
+  return guarded(h, "plda_adapt_reset", [&]() -> int {
+    if (!h) return PLDA_E_INVAL;
+    PLDA_LOCK(h);
+    return adapt_reset(h);
+  });
+}
+
+int plda_adapt_accumulate_dev(plda_handle *h, const double *dX, int64_t N, int32_t Din, const double *dweights) {
+  return guarded(h, "plda_adapt_accumulate_dev", [&]() -> int {
+    if (!h) return PLDA_E_INVAL;
+    PLDA_LOCK(h);
+    PLDA_TRY(set_device(h));
+    return adapt_accumulate(h, dX, N, Din, dweights, false);
+  });
+}
+
+int plda_adapt_accumulate(plda_handle *h, const double *X, int64_t N, int32_t Din, const double *weights) {
+  return guarded(h, "plda_adapt_accumulate", [&]() -> int {
+    if (!h) return PLDA_E_INVAL;
+    PLDA_LOCK(h);
+    PLDA_TRY(set_device(h));
+    return adapt_accumulate(h, X, N, Din, weights, true);   // slab by slab through a bounded staging buffer
+  });
+}
+
+int plda_adapt_get_stats(plda_handle *h, double *tw, int64_t *rows, double *pilot, double *s1, double *s2) {
+  return guarded(h, "plda_adapt_get_stats", [&]() -> int {
+    if (!h) return PLDA_E_INVAL;
+    PLDA_LOCK(h);
+    PLDA_TRY(set_device(h));
+    return adapt_get_stats(h, tw, rows, pilot, s1, s2);
+  });
+}
+
+int plda_adapt_add_stats(plda_handle *h, double tw, int64_t rows, const double *pilot, const double *s1, const double *s2) {
+  return guarded(h, "plda_adapt_add_stats", [&]() -> int {
+    if (!h) return PLDA_E_INVAL;
+    PLDA_LOCK(h);
+    PLDA_TRY(set_device(h));
+    return adapt_add_stats(h, tw, rows, pilot, s1, s2);
+  });
+}
+
+int plda_adapt_update(plda_handle *h, double within_scale, double between_scale, double mean_diff_scale, double *eig,
+                      plda_adapt_info *info) {
+  return guarded(h, "plda_adapt_update", [&]() -> int {
+    if (!h) return PLDA_E_INVAL;
+    PLDA_LOCK(h);
+    PLDA_TRY(set_device(h));
+    return adapt_update(h, within_scale, between_scale, mean_diff_scale, eig, info);
+  });
+}
+
+int plda_blend_model(plda_handle *h, int32_t D, const double *mean2, const double *transform2, const double *psi2, double alpha,
+                     double alpha_mean) {
+  return guarded(h, "plda_blend_model", [&]() -> int {
+    if (!h) return PLDA_E_INVAL;
+    PLDA_LOCK(h);
+    PLDA_TRY(set_device(h));
+    return blend_model(h, D, mean2, transform2, psi2, alpha, alpha_mean);
   });
 }
 

@@ -268,6 +268,20 @@ struct plda_handle {
   int eig_variant = 0;           // PLDA_EIG_VARIANT: 0 = direct method where supported, 1 = block Jacobi always
   int eig_debug = 0;             // PLDA_EIG_DEBUG (timing experiments only: results are wrong when set)
   int eig_last_method = 0;       // 1 = block Jacobi, 2 = tridiagonalisation + divide and conquer
+
+  // ---- domain adaptation (adapt.hip): the statistics record about the pilot, the slab in flight, the update's matrices ----
+  plda::DevBuf ad_rec;           // [(D + 1)^2 augmented sums: S2 | S1 | tw] then the pilot [D]
+  plda::DevBuf ad_slab;          // one slab of centred rows [x - p | 1] + the call's partial sums + its reject counters
+  plda::DevBuf ad_stage;         // rows (and weights) of one slab of a host-pointer call on their way to the device
+  plda::DevBuf ad_work;          // the D x D matrices of plda_adapt_update / plda_blend_model and the staged new model
+  int64_t ad_slab_rows = 0;      // PLDA_ADAPT_SLAB_ROWS: rows per slab of plda_adapt_accumulate* (0: by size, adapt.hip)
+  bool ad_has = false;           // a record exists (the pilot is set)
+  bool ad_used = false;          // plda_adapt_update has consumed it
+  int ad_D = 0;
+  uint64_t ad_epoch = 0;         // model_epoch at the pilot
+  int64_t ad_rows = 0;
+  double ad_tw = 0.0;            // host mirror of the record's total weight
+  std::vector<double> ad_pilot;  // host mirror of the pilot (bitwise comparisons of plda_adapt_add_stats)
 };
 
 namespace plda {
@@ -397,6 +411,18 @@ int simdiag_finish_with(plda_handle *h, const double *W, const double *B, int D,
 // T [D,D], Tinv = T^{-1} (nullable), psi[D].  W,B are not modified.
 int simdiag_f64(plda_handle *h, const double *W, const double *B, int D, double *T,
                 double *Tinv, double *psi, bool warm_start);
+
+int syrk_f64(plda_handle *h, int D, int64_t K, double alpha, const double *X, int64_t ldx, const double *kw, double beta,
+             double *C, int64_t ldc);   // C = alpha X^T diag(kw) X + beta C, X [K, D] (both triangles written)
+
+// ---- adapt.hip (PLDA domain adaptation: the unsupervised adaptor's statistics and update, interpolation of two models) ----
+int adapt_reset(plda_handle *h);
+int adapt_accumulate(plda_handle *h, const double *X, int64_t N, int Din, const double *weights, bool host);
+int adapt_get_stats(plda_handle *h, double *tw, int64_t *rows, double *pilot, double *s1, double *s2);
+int adapt_add_stats(plda_handle *h, double tw, int64_t rows, const double *pilot, const double *s1, const double *s2);
+int adapt_update(plda_handle *h, double ws, double bs, double mds, double *eig, plda_adapt_info *info);
+int blend_model(plda_handle *h, int D, const double *mean2, const double *transform2, const double *psi2, double alpha,
+                double alpha_mean);
 
 // ---- frontend.hip ----
 int htk_frames_device(plda_handle *h, const void *dblob, const int64_t *dfile_off, const int64_t *dframe_off,

@@ -266,6 +266,100 @@ class MPlda(object):
         """Plda::SmoothWithinClassCovariance (reached at pldamodule.cpp:158-160)."""
         self._ck(self._lib.plda_smooth(self._h, float(factor)))
 
+    # ------------------------------------------------- domain adaptation (csrc/adapt.hip)
+    def _model_replaced(self):
+        """The z-norm maps, their sorted copy and the stored calibration describe the scores of the model that was just
+        replaced; the maps are insert-once, so a later norm() could not overwrite them: they are cleared."""
+        self._meanz = {}
+        self._stdvz = {}
+        self._zn_tag = None
+        self._calibration = None
+
+    def adapt_reset(self):
+        """Forget the adaptation statistics; the next accumulation takes the model mean as its pilot anew."""
+        self._ck(self._lib.plda_adapt_reset(self._h))
+
+    def adapt_accumulate(self, x, weights=None):
+        """Add the rows x [N, D] (weights [N] >= 0, None: 1) to the adaptation statistics: total weight, sum and second
+        moments about the pilot (the model mean at the first accumulation after a reset).  The rows are read once, slab by
+        slab.  A non-finite row or a bad weight raises and leaves the statistics as they were."""
+        X = _features(x)
+        n, d = X.shape
+        w = None
+        if weights is not None:
+            w = np.ascontiguousarray(weights, np.float64).reshape(-1)
+            if w.shape[0] != n:
+                raise ValueError("adapt_accumulate: one weight per row")
+        self._ck(self._lib.plda_adapt_accumulate(self._h, _ptr(X), n, d, _ptr(w)))
+
+    def adapt_accumulate_dev(self, dX, n, d, dweights=None):
+        """The same on rows already in this GPU's memory: dX / dweights are device addresses (ints) of fp64 [n, d] / [n]."""
+        self._ck(self._lib.plda_adapt_accumulate_dev(self._h, C.c_void_p(int(dX)), int(n), int(d),
+                                                     C.c_void_p(int(dweights)) if dweights else None))
+
+    def adapt_stats(self):
+        """dict(tot_weight, rows, pilot [D], s1 [D], s2 [D, D]): the record as it stands (sums about the pilot)."""
+        _, d = self.dims()
+        tw, rows = C.c_double(), C.c_int64()
+        pilot, s1, s2 = np.zeros(d), np.zeros(d), np.zeros((d, d))
+        self._ck(self._lib.plda_adapt_get_stats(self._h, C.byref(tw), C.byref(rows), _ptr(pilot), _ptr(s1), _ptr(s2)))
+        return dict(tot_weight=tw.value, rows=rows.value, pilot=pilot, s1=s1, s2=s2)
+
+    def adapt_add_stats(self, tot_weight, rows, pilot, s1, s2):
+        """Add the record of another handle or rank (the fields of adapt_stats()).  Its pilot must equal this record's bit
+        for bit; an empty record adopts it only if it equals the model mean."""
+        _, d = self.dims()
+        pilot = np.ascontiguousarray(pilot, np.float64)
+        s1 = np.ascontiguousarray(s1, np.float64)
+        s2 = np.ascontiguousarray(s2, np.float64)
+        if pilot.shape != (d,) or s1.shape != (d,) or s2.shape != (d, d):
+            raise ValueError("adapt_add_stats: pilot / s1 must be [%d], s2 [%d, %d]" % (d, d, d))
+        self._ck(self._lib.plda_adapt_add_stats(self._h, float(tot_weight), int(rows), _ptr(pilot), _ptr(s1), _ptr(s2)))
+
+    def adapt_update(self, within_scale=0.3, between_scale=0.7, mean_diff_scale=1.0):
+        """Replace the model by its unsupervised adaptation to the accumulated statistics (Kaldi's PldaUnsupervisedAdaptor
+        restated, defaults included; PARITY UNPINNED): the variance the data shows beyond the model's total covariance is
+        added to the within- and between-class covariances in the given proportions and the mean moves to the data's.
+        Returns a plda_amd.adaptation.Adaptation.  On failure the old model stays.  On success the z-norm statistics and
+        the stored calibration are CLEARED: they describe the scores of the old model (and the z-norm maps are
+        insert-once, so a later norm() could not overwrite them).  Vectors transformed before the update belong to the
+        old model too."""
+        from .adaptation import Adaptation
+        _, d = self.dims()
+        eig = np.zeros(d)
+        info = N.AdaptInfo()
+        self._ck(self._lib.plda_adapt_update(self._h, float(within_scale), float(between_scale), float(mean_diff_scale),
+                                             _ptr(eig), C.byref(info)))
+        self._model_replaced()
+        return Adaptation(eig, info.n_excess, info.tot_weight, info.rows, info.mean_shift)
+
+    def adapt(self, x, weights=None, within_scale=0.3, between_scale=0.7, mean_diff_scale=1.0):
+        """Unsupervised domain adaptation in one call: adapt_reset, adapt_accumulate(x, weights), adapt_update(...).
+        Clears the z-norm statistics and the stored calibration like adapt_update."""
+        self.adapt_reset()
+        self.adapt_accumulate(x, weights)
+        return self.adapt_update(within_scale, between_scale, mean_diff_scale)
+
+    def blend(self, other, alpha, alpha_mean=None):
+        """Supervised adaptation by interpolation: within- and between-class covariances become (1 - alpha) this model's +
+        alpha `other`'s, the mean (1 - alpha_mean) this + alpha_mean other's (alpha_mean=None: alpha).  `other` is an MPlda,
+        a liblda.PLDA or a (mean, transform, psi) triple of the same dimension.  On success the z-norm statistics and the
+        stored calibration are cleared, as by adapt_update."""
+        inner = getattr(other, "_instance", other)
+        if isinstance(inner, MPlda):
+            m = inner.get_model()
+            mean2, T2, psi2 = m["mean"], m["transform"], m["psi"]
+        else:
+            mean2, T2, psi2 = other
+        mean2 = np.ascontiguousarray(mean2, np.float64)
+        T2 = np.ascontiguousarray(T2, np.float64)
+        psi2 = np.ascontiguousarray(psi2, np.float64)
+        if T2.ndim != 2 or T2.shape[0] != T2.shape[1] or mean2.shape != (T2.shape[0],) or psi2.shape != (T2.shape[0],):
+            raise ValueError("blend: the other model must be square: mean [D], transform [D, D], psi [D]")
+        am = float(alpha) if alpha_mean is None else float(alpha_mean)
+        self._ck(self._lib.plda_blend_model(self._h, T2.shape[0], _ptr(mean2), _ptr(T2), _ptr(psi2), float(alpha), am))
+        self._model_replaced()
+
     # ------------------------------------------------------------ transform
     def transform(self, x, y, targetdim=0, smoothfactor=1.0):
         """Mplda_transform (pldamodule.cpp:111-194): {label: (n, ndarray f64[D])},
