@@ -265,6 +265,13 @@ int plda_score_last_shape(plda_handle *h, int64_t *M, int64_t *Nt, int32_t *gemm
 /* name of the trials-GEMM kernel the last plda_score_matrix* call launched (roofline accounting: bench.py names the
  * kernel its `roofline` block prices); "" before the first call.  PLDA_E_CAPACITY when it does not fit name[cap]. */
 int plda_score_last_kernel(plda_handle *h, char *name, int64_t cap);
+/* The kernels that the fp64 building blocks (the eigensolver, the GEMM / SYRK family, the SPD inverse and whitening)
+ * dispatched since the last call of plda_sym_eig, plda_gemm_f64 or plda_spd_inverse, which clear the record on entry
+ * (tests pin a dispatch class by it; the reference has no counterpart).  Host-side text, template arguments included,
+ * entries separated by ';' and each listed once in the order of its first launch, e.g.
+ * "tridiag_full_kernel<7>;gemm_f64_panel_kernel<0,0,2>;householder_row1_kernel<2>"; a record that ran full ends in the
+ * entry "...".  PLDA_E_CAPACITY when it does not fit out[cap] (1024 bytes always do). */
+int plda_linalg_last_kernels(plda_handle *h, char *out, int64_t cap);
 
 /* ---- S-norm / adaptive S-norm (AS-norm): no counterpart in the reference, whose README says of score normalisation
  *      "z-norm (other norms are not implemented yet)" ----

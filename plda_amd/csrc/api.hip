@@ -38,6 +38,46 @@ int hip_fail(plda_handle *h, hipError_t e, const char *what, const char *file, i
   return fail(h, PLDA_E_HIP, "HIP error %d (%s) at %s:%d: %s", (int)e, hipGetErrorString(e), file, line, what);
 }
 
+void note_kernel(plda_handle *h, const char *name, int nargs, int a, int b, int c, const char *suffix) {
+  char e[96];
+  size_t n = 0;
+  auto put = [&](const char *t) { while (*t && n + 1 < sizeof(e)) e[n++] = *t++; };
+  auto num = [&](int v) {
+    char d[12];
+    int k = 0;
+    unsigned u = v < 0 ? 0u : (unsigned)v;
+    do { d[k++] = (char)('0' + u % 10); u /= 10; } while (u);
+    while (k && n + 1 < sizeof(e)) e[n++] = d[--k];
+  };
+  put(name);
+  if (nargs > 0) {
+    const int v[3] = {a, b, c};
+    put("<");
+    for (int i = 0; i < nargs && i < 3; ++i) { if (i) put(","); num(v[i]); }
+    put(">");
+  }
+  if (suffix) put(suffix);
+  char *buf = h->linalg_kernels;
+  const size_t len = (size_t)h->linalg_kernels_len, cap = sizeof(h->linalg_kernels);
+  for (const char *p = buf, *end = buf + len; p < end;) {     // each entry once
+    const char *q = static_cast<const char *>(std::memchr(p, ';', (size_t)(end - p)));
+    if (!q) q = end;
+    if ((size_t)(q - p) == n && std::memcmp(p, e, n) == 0) return;
+    p = q + 1;
+  }
+  size_t at = len;
+  if (len >= 3 && std::memcmp(buf + len - 3, "...", 3) == 0) return;   // ran full earlier: nothing after the mark
+  if (len + 1 + n + 5 > cap) {   // full: the record ends in "..." (room for it is kept free by this very test)
+    n = 0;
+    put("...");
+  }
+  if (at) buf[at++] = ';';
+  std::memcpy(buf + at, e, n);
+  at += n;
+  buf[at] = 0;
+  h->linalg_kernels_len = (int)at;
+}
+
 int model_to_device(plda_handle *h) {
   const size_t Dout = h->Dout, Din = h->Din;
   PLDA_HIP(h, h->d_mean.reserve(Din * 8));
@@ -983,6 +1023,7 @@ int plda_gemm_f64(plda_handle *h, int64_t M, int64_t N, int64_t K, double alpha,
   return guarded(h, "plda_gemm_f64", [&]() -> int {
     if (!h) return PLDA_E_INVAL;
     PLDA_LOCK(h);
+    note_kernels_clear(h);
     if (!A || !B || !C || M <= 0 || N <= 0 || K <= 0 || batch <= 0 || (kw && batch != 1))
       return fail(h, PLDA_E_INVAL, "gemm_f64: bad argument");
     PLDA_TRY(set_device(h));
@@ -1015,6 +1056,7 @@ int plda_spd_inverse(plda_handle *h, const double *A, int32_t D, double *inverse
   return guarded(h, "plda_spd_inverse", [&]() -> int {
     if (!h) return PLDA_E_INVAL;
     PLDA_LOCK(h);
+    note_kernels_clear(h);
     if (!A || !inverse || D <= 0 || D > 2048) return fail(h, PLDA_E_INVAL, "spd_inverse: bad argument");
     PLDA_TRY(set_device(h));
     const size_t DD = (size_t)D * D;
@@ -1041,6 +1083,7 @@ int plda_sym_eig(plda_handle *h, const double *G, int32_t D, int32_t method, dou
   return guarded(h, "plda_sym_eig", [&]() -> int {
     if (!h) return PLDA_E_INVAL;
     PLDA_LOCK(h);
+    note_kernels_clear(h);
     if (!G || !eigenvalues || !eigenvectors || D <= 0 || D > 2048) return fail(h, PLDA_E_INVAL, "sym_eig: bad argument");
     if (method < 0 || method > 2) return fail(h, PLDA_E_INVAL, "sym_eig: method must be 0 (default), 1 (Jacobi) or 2 (direct)");
     if (method == 1 && D > 1024) return fail(h, PLDA_E_INVAL, "sym_eig: the block Jacobi solver (method 1) stops at D = 1024; D = %d needs method 0 or 2", D);
@@ -1095,6 +1138,17 @@ int plda_score_last_kernel(plda_handle *h, char *name, int64_t cap) {
     const char *k = h->last_kernel ? h->last_kernel : "";
     if ((int64_t)std::strlen(k) + 1 > cap) return fail(h, PLDA_E_CAPACITY, "score_last_kernel: need %zu bytes", std::strlen(k) + 1);
     std::memcpy(name, k, std::strlen(k) + 1);
+    return PLDA_OK;
+  });
+}
+
+int plda_linalg_last_kernels(plda_handle *h, char *out, int64_t cap) {
+  return guarded(h, "plda_linalg_last_kernels", [&]() -> int {
+    if (!h || !out || cap <= 0) return PLDA_E_INVAL;
+    PLDA_LOCK(h);
+    const size_t need = (size_t)h->linalg_kernels_len + 1;
+    if ((int64_t)need > cap) return fail(h, PLDA_E_CAPACITY, "linalg_last_kernels: need %zu bytes", need);
+    std::memcpy(out, h->linalg_kernels, need);
     return PLDA_OK;
   });
 }

@@ -175,6 +175,11 @@ struct plda_handle {
   int64_t last_M = 0, last_Nt = 0;
   const char *last_kernel = nullptr;   // the trials-GEMM kernel of the last score_matrix launch (static string)
   int last_k = 0;
+  // the fp64 building blocks' dispatch record (plda_linalg_last_kernels): every dispatch site of linalg.hip and eig_dc.hip
+  // appends the kernel it chose with its template arguments (note_kernel below), ';' between entries, each entry once;
+  // cleared on entry to plda_sym_eig / plda_gemm_f64 / plda_spd_inverse.  A record that ran full ends in "..."
+  char linalg_kernels[1024] = {0};
+  int linalg_kernels_len = 0;
   // a test side packed ahead of time (plda_score_prepare_dev / _counts_dev): reused while pointer, size, model and count
   // kind match.  prep_kind: 0 uniform count (prep_nuniform), 1 mixed counts in the depth-2D form, 2 mixed counts in the
   // bucketed form for the count set prep_counts
@@ -288,6 +293,10 @@ namespace plda {
 
 int fail(plda_handle *h, int code, const char *fmt, ...);
 int hip_fail(plda_handle *h, hipError_t e, const char *what, const char *file, int line);
+// appends "name", "name<a>", "name<a,b>" or "name<a,b,c>" (+ suffix) to h->linalg_kernels: host-side text only, a few
+// dozen nanoseconds per dispatch (no printf formatting: the EM issues hundreds of these products per fit)
+void note_kernel(plda_handle *h, const char *name, int nargs = 0, int a = 0, int b = 0, int c = 0, const char *suffix = nullptr);
+inline void note_kernels_clear(plda_handle *h) { h->linalg_kernels_len = 0; h->linalg_kernels[0] = 0; }
 
 #define PLDA_HIP(h, expr)                                                          \
   do {                                                                             \

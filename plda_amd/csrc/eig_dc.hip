@@ -1733,7 +1733,9 @@ int sym_eig_dc_f64(plda_handle *h, const double *G, int D, double *s, double *Vr
   // round 3: the four-wave register kernel up to n = 224 (PLDA_SWEEP_VARIANT=1 or PLDA_EIG_VARIANT=2 / 3: the round-2 choice)
   if (full_kernel) {   // full storage, one barrier per step (PLDA_SWEEP_VARIANT=2: the symmetric-storage kernel)
     const int nb = (int)ceil_div(n, 16);
-#define TRF(NBB) tridiag_full_kernel<NBB, (NBB + 1) / 2><<<1, 512, 0, h->stream>>>(G, n, scale, dd, ee, Vh, tau, flag)
+#define TRF(NBB)                                \
+  note_kernel(h, "tridiag_full_kernel", 1, NBB); \
+  tridiag_full_kernel<NBB, (NBB + 1) / 2><<<1, 512, 0, h->stream>>>(G, n, scale, dd, ee, Vh, tau, flag)
     switch (nb) {
       case 3: TRF(3); break;
       case 4: TRF(4); break;
@@ -1750,7 +1752,9 @@ int sym_eig_dc_f64(plda_handle *h, const double *G, int D, double *s, double *Vr
 #undef TRF
   } else if (h->sweep_variant != 1 && ev0 && n <= 224) {      // (NB = 15, 16 spill 380 / 680 bytes per lane)
     const int nb = (int)ceil_div(n, 16);
-#define TR16(NBB) tridiag_reg16_kernel<NBB><<<1, 256, 0, h->stream>>>(G, n, scale, dd, ee, Vh, tau)
+#define TR16(NBB)                                \
+  note_kernel(h, "tridiag_reg16_kernel", 1, NBB); \
+  tridiag_reg16_kernel<NBB><<<1, 256, 0, h->stream>>>(G, n, scale, dd, ee, Vh, tau)
     switch (nb) {
       case 1: TR16(1); break;
       case 2: TR16(2); break;
@@ -1772,7 +1776,9 @@ int sym_eig_dc_f64(plda_handle *h, const double *G, int D, double *s, double *Vr
 #undef TR16
   } else if (reg_kernel) {
     const int nb = (int)ceil_div(n, 32);
-#define TR(NBB) tridiag_reg_kernel<NBB><<<1, 1024, 0, h->stream>>>(G, n, scale, dd, ee, Vh, tau)
+#define TR(NBB)                                \
+  note_kernel(h, "tridiag_reg_kernel", 1, NBB); \
+  tridiag_reg_kernel<NBB><<<1, 1024, 0, h->stream>>>(G, n, scale, dd, ee, Vh, tau)
     switch (nb) {
       case 1: TR(1); break;
       case 2: TR(2); break;
@@ -1800,6 +1806,7 @@ int sym_eig_dc_f64(plda_handle *h, const double *G, int D, double *s, double *Vr
                      : E <= 16 ? reinterpret_cast<const void *>(&tridiag_rows_kernel<16, TR_ROWS>)
                      : E <= 32 ? reinterpret_cast<const void *>(&tridiag_rows_kernel<32, TR_ROWS>)
                                : reinterpret_cast<const void *>(&tridiag_rows_kernel<64, TR_ROWS>);
+    note_kernel(h, "tridiag_rows_kernel", 1, NP / 32);
     {
       // a device that cannot hold all W workgroups at once (CU masking, a partitioned GPU) refuses the launch:
       // that is not an error of the fit -- the caller falls back to the block Jacobi solver
@@ -1855,6 +1862,7 @@ int sym_eig_dc_f64(plda_handle *h, const double *G, int D, double *s, double *Vr
   do {                                                                                                                 \
     PLDA_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&householder_rows_kernel<E2>),                       \
                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                            \
+    note_kernel(h, "householder_rows_kernel", 1, E2);                                                                  \
     householder_rows_kernel<E2><<<grid, 256, lds, h->stream>>>(qin, n, Vh, Tg, lin, scale, qout, lamU);               \
   } while (0)
     // n <= 512: one row per wave, the eight dots of a block reduced together (PLDA_EIG_VARIANT=4: the two-row kernel)
@@ -1862,6 +1870,7 @@ int sym_eig_dc_f64(plda_handle *h, const double *G, int D, double *s, double *Vr
   do {                                                                                                                 \
     PLDA_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&householder_row1_kernel<E2>),                       \
                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                            \
+    note_kernel(h, "householder_row1_kernel", 1, E2);                                                                  \
     householder_row1_kernel<E2><<<(unsigned)ceil_div(n, 4), 256, lds, h->stream>>>(qin, n, Vh, Tg, lin, scale, qout, lamU); \
   } while (0)
     const bool row1 = h->eig_variant != 4;

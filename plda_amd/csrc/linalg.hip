@@ -694,6 +694,7 @@ int em_rank_sums_mstep_f64(plda_handle *h, int D, const SyrkChunk *chunks, int n
   const int nt = (int)ceil_div(D, 16), ntri = nt * (nt + 1) / 2;
   PLDA_HIP(h, h->w[15].reserve((size_t)nchunks * ntri * 256 * 8));
   double *part = h->w[15].as<double>();
+  note_kernel(h, "syrk_tri_kernel");
   syrk_tri_kernel<false><<<(unsigned)nchunks, 512, 0, h->stream>>>(D, 0, 0, nullptr, D, nullptr, 0, nullptr, D, 1.0, part, nullptr,
                                                                    nullptr, chunks);
   em_rank_reduce_mstep_kernel<<<dim3((unsigned)ntri, 2), 1024, 0, h->stream>>>(part, chunks, nchunks, D, S, sumK, cw, cntW, cntB, W, Bin, Bout);
@@ -741,6 +742,7 @@ int syrk_f64(plda_handle *h, int D, int64_t K, double alpha, const double *X, in
     splits = (int)ceil_div(K, kchunk);
     PLDA_HIP(h, h->w[15].reserve((size_t)splits * ntri * 256 * 8));
     double *part = h->w[15].as<double>();
+    note_kernel(h, "syrk_tri_kernel");
     syrk_tri_kernel<false><<<(unsigned)splits, 512, 0, h->stream>>>(D, K, kchunk, X, ldx, kw, K, nullptr, 0, 0.0, part, nullptr, nullptr);
     syrk_tri_reduce_kernel<<<(unsigned)ntri, 1024, 0, h->stream>>>(part, splits, D, alpha, beta, C, ldc);
     PLDA_LAUNCH_CHECK(h);
@@ -762,6 +764,8 @@ int syrk_f64(plda_handle *h, int D, int64_t K, double alpha, const double *X, in
   if (nO) plan(nO, so, ko);
   PLDA_HIP(h, h->w[15].reserve((size_t)std::max(sd, so) * nP * 64 * 256 * 8));
   double *part = h->w[15].as<double>();
+  note_kernel(h, "syrk_lower_kernel", 1, 1);
+  if (nO) note_kernel(h, "syrk_lower_kernel", 1, 0);
   syrk_lower_kernel<true><<<(unsigned)(round_up(sd, 8) * nT), 256, 0, h->stream>>>(D, K, kd, X, ldx, kw, part, nP, nT, sd);
   if (nO) syrk_lower_kernel<false><<<(unsigned)(round_up(so, 8) * nO), 256, 0, h->stream>>>(D, K, ko, X, ldx, kw, part, nP, nO, so);
   PLDA_LAUNCH_CHECK(h);
@@ -782,6 +786,7 @@ int syrk_znorm_f64(plda_handle *h, int D0, int64_t K, const double *X, const dou
   splits = (int)ceil_div(K, kchunk);
   PLDA_HIP(h, h->w[15].reserve((size_t)splits * ntri * 256 * 8));
   double *part = h->w[15].as<double>();
+  note_kernel(h, "syrk_tri_kernel", 1, 1);
   syrk_tri_kernel<true><<<(unsigned)splits, 512, 0, h->stream>>>(D, K, kchunk, X, D0, nullptr, K, nullptr, 0, 0.0, part, zc, zs);
   syrk_tri_reduce_kernel<<<(unsigned)ntri, 1024, 0, h->stream>>>(part, splits, D, 1.0, 0.0, C, D);
   PLDA_LAUNCH_CHECK(h);
@@ -800,6 +805,7 @@ int syrk_pair_f64(plda_handle *h, int D, int64_t K1, const double *X, int64_t ld
     splits = (int)ceil_div(K, kchunk);
     PLDA_HIP(h, h->w[15].reserve((size_t)splits * ntri * 256 * 8));
     double *part = h->w[15].as<double>();
+    note_kernel(h, "syrk_tri_kernel");
     syrk_tri_kernel<false><<<(unsigned)splits, 512, 0, h->stream>>>(D, K, kchunk, X, ldx, kw, K1, X2, ldx2, w2, part, nullptr, nullptr);
     syrk_tri_reduce_kernel<<<(unsigned)ntri, 1024, 0, h->stream>>>(part, splits, D, 1.0, 0.0, C, ldc);
     PLDA_LAUNCH_CHECK(h);
@@ -965,6 +971,7 @@ int gemm_f64_batched(plda_handle *h, int64_t M, int64_t N, int64_t K, double alp
     if (batch > 65535) return fail(h, PLDA_E_INVAL, "gemm_f64: batch %d too large", batch);
     const dim3 tgrid((unsigned)ceil_div(N, 16), (unsigned)ceil_div(M, 16), (unsigned)batch);
     const Tile16Operands o{alpha, beta, A, B, C, sam, sak, sbk, sbn, ldc, strideA, strideB, strideC};
+    note_kernel(h, "gemm_f64_tile16_kernel");
     gemm_f64_tile16_kernel<<<tgrid, 256, 0, h->stream>>>((int)M, (int)N, (int)K, o, o, batch);
     PLDA_LAUNCH_CHECK(h);
     return PLDA_OK;
@@ -983,6 +990,7 @@ int gemm_f64_batched(plda_handle *h, int64_t M, int64_t N, int64_t K, double alp
                                       hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 32 * (64 * NBB + 1) * 8)); \
       attr_done = true;                                                                                       \
     }                                                                                                         \
+    note_kernel(h, "gemm_f64_panel_kernel", 3, AK ? 1 : 0, BK ? 1 : 0, NBB);                                  \
     gemm_f64_panel_kernel<AK, BK, NBB><<<pgrid, 256, lds, h->stream>>>((int)M, (int)N, (int)K, alpha, A, sam, \
                                                                        sak, B, sbk, sbn, beta, C, ldc,        \
                                                                        strideA, strideB, strideC);            \
@@ -1024,6 +1032,7 @@ int gemm_f64_batched(plda_handle *h, int64_t M, int64_t N, int64_t K, double alp
   const dim3 grid((unsigned)ceil_div(N, TBsel), (unsigned)ceil_div(M, TBsel), (unsigned)(splits * batch));
 #define GEMM_LAUNCH(AK, BK)                                                                                   \
   do {                                                                                                        \
+    note_kernel(h, "gemm_f64_kernel", 3, AK ? 1 : 0, BK ? 1 : 0, TBsel, splits > 1 ? "+splitk" : nullptr);    \
     if (big)                                                                                                  \
       gemm_f64_kernel<AK, BK, 128><<<grid, 256, 0, h->stream>>>(M, N, K, kchunk, alpha, A, sam, sak, B, sbk,  \
                                                                 sbn, kw, beta, C, ldc, part, splits, strideA, \
@@ -1065,6 +1074,7 @@ int gemm_f64_multi(plda_handle *h, int64_t M, int64_t N, int64_t K, const GemmSe
       o[i] = Tile16Operands{1.0, 0.0, g.A, g.B, g.C, g.sam, g.sak, g.sbk, g.sbn, g.ldc, g.strideA, g.strideB, g.strideC};
     }
     const dim3 tgrid((unsigned)ceil_div(N, 16), (unsigned)ceil_div(M, 16), (unsigned)(nsets * batch));
+    note_kernel(h, "gemm_f64_tile16_kernel");
     gemm_f64_tile16_kernel<<<tgrid, 256, 0, h->stream>>>((int)M, (int)N, (int)K, o[0], o[1], batch, o[2]);
     PLDA_LAUNCH_CHECK(h);
     return PLDA_OK;
@@ -1158,12 +1168,14 @@ __global__ __launch_bounds__(64) void tri_invert_kernel(const double *__restrict
 // L: [batch] D x D factors, leading dimension D, batch stride stride_l
 int tri_invert_ld(plda_handle *h, const double *L, int64_t stride_l, double *X, int D, int ldx, int64_t stride_x, int batch) {
   const int E = (int)ceil_div(D, 64);
-#define TI(EE) tri_invert_kernel<EE><<<dim3(D, batch), 64, 0, h->stream>>>(L, X, D, ldx, stride_x, stride_l)
-  if (E <= 1) TI(1);
-  else if (E <= 2) TI(2);
-  else if (E <= 4) TI(4);
-  else if (E <= 8) TI(8);
-  else if (E <= 16) TI(16);
+#define TI(EE)                                \
+  note_kernel(h, "tri_invert_kernel", 1, EE); \
+  tri_invert_kernel<EE><<<dim3(D, batch), 64, 0, h->stream>>>(L, X, D, ldx, stride_x, stride_l)
+  if (E <= 1) { TI(1); }
+  else if (E <= 2) { TI(2); }
+  else if (E <= 4) { TI(4); }
+  else if (E <= 8) { TI(8); }
+  else if (E <= 16) { TI(16); }
   else return fail(h, PLDA_E_INVAL, "tri_invert: D=%d > 1024 unsupported", D);
 #undef TI
   PLDA_LAUNCH_CHECK(h);
@@ -1390,6 +1402,7 @@ static int spd_block_mfma(plda_handle *h, int mode, const double *W, const doubl
                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                       \
       h->sweep_mfma_attr[NTT] = true;                                                                               \
     }                                                                                                               \
+    note_kernel(h, "spd_inverse_mfma_kernel", 2, NTT, mode == 0 ? 0 : 1);                                           \
     if (mode == 0)                                                                                                  \
       spd_inverse_mfma_kernel<NTT, 0><<<batch, 1024, lds, h->stream>>>(W, B, gn, D, ldin, stride_in, out, ldout,    \
                                                                        stride_out, dflag);                          \
@@ -1424,6 +1437,7 @@ int spd_inverse_small(plda_handle *h, const double *W, const double *B, const do
   if (h->sweep_variant == 0 || h->sweep_variant == 2) {     // four waves, 16 x 16 ownership (2: at every size; 1: the 16-wave kernel of round 2)
     const int nb16 = (int)ceil_div(D, 16);
 #define SW16(NBB)                                                                                             \
+  note_kernel(h, "spd_inverse_sweep16_kernel", 1, NBB);                                                       \
   spd_inverse_sweep16_kernel<NBB><<<batch, 256, 0, h->stream>>>(W, B, gn, D, ldin, stride_in, out, ldout, \
                                                                 stride_out, dflag)
     switch (nb16) {
@@ -1451,6 +1465,7 @@ int spd_inverse_small(plda_handle *h, const double *W, const double *B, const do
   }
   const int nb = (int)ceil_div(D, 32);
 #define SW(NBB)                                                                                              \
+  note_kernel(h, "spd_inverse_sweep_kernel", 1, NBB);                                                        \
   spd_inverse_sweep_kernel<NBB><<<batch, 1024, 0, h->stream>>>(W, B, gn, D, ldin, stride_in, out, ldout, \
                                                                stride_out, dflag)
   switch (nb) {
@@ -1546,7 +1561,9 @@ __global__ __launch_bounds__(1024) void chol_small_kernel(const double *__restri
 int chol_small(plda_handle *h, const double *A, int D, int ldin, int64_t stride_in, double *out, int ldout,
                int64_t stride_out, int *dflag, int batch) {
   const int nb = (int)ceil_div(D, 32);
-#define CS(NBB) chol_small_kernel<NBB><<<batch, 1024, 0, h->stream>>>(A, D, ldin, stride_in, out, ldout, stride_out, dflag)
+#define CS(NBB)                               \
+  note_kernel(h, "chol_small_kernel", 1, NBB); \
+  chol_small_kernel<NBB><<<batch, 1024, 0, h->stream>>>(A, D, ldin, stride_in, out, ldout, stride_out, dflag)
   switch (nb) {
     case 1: CS(1); break;
     case 2: CS(2); break;
@@ -1931,16 +1948,22 @@ __global__ void set_identity_kernel(double *V, int D) {
   if (idx < D * D) V[idx] = (idx / D == idx % D) ? 1.0 : 0.0;
 }
 
-// lambda_p = a_p . v_p (one wave per row)
+// A += sigma V: the rows of V (G + sigma I) from those of V G (sym_eig_f64, second stage)
+__global__ void jacobi_shift_kernel(double *__restrict__ A, const double *__restrict__ V, int64_t DD, double sigma) {
+  const int64_t idx = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (idx < DD) A[idx] = fma(sigma, V[idx], A[idx]);
+}
+
+// lambda_p = a_p . v_p - shift (one wave per row)
 __global__ void eig_values_kernel(const double *__restrict__ A, const double *__restrict__ V, int D,
-                                  double *__restrict__ lam) {
+                                  double *__restrict__ lam, double shift) {
   const int lane = threadIdx.x & 63;
   const int p = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
   if (p >= D) return;
   double acc = 0.0;
   for (int d = lane; d < D; d += 64) acc += A[(size_t)p * D + d] * V[(size_t)p * D + d];
   for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
-  if (lane == 0) lam[p] = acc;
+  if (lane == 0) lam[p] = acc - shift;
 }
 
 // rank sort descending (SortSvd), floor at zero (ApplyFloor), permute eigenvector rows
@@ -1978,6 +2001,8 @@ static int jacobi_sweep_graph(plda_handle *h, double *G, double *V, int D, doubl
   const int E = (int)ceil_div(D, 64);
   const size_t lds = (size_t)4 * JB * D * sizeof(double);
   const bool gram = h->jacobi_variant != 1;
+  if (gram) note_kernel(h, "jacobi_gram_kernel");
+  else note_kernel(h, "jacobi_block_kernel", 1, E <= 1 ? 1 : E <= 2 ? 2 : E <= 4 ? 4 : E <= 8 ? 8 : 16);
   if (h->stream == nullptr) {
     // HIP's legacy default stream cannot be captured: launch the rounds directly
     PLDA_HIP(h, hipFuncSetAttribute(E <= 1 ? reinterpret_cast<const void *>(&jacobi_block_kernel<1>)
@@ -2068,20 +2093,53 @@ int sym_eig_f64(plda_handle *h, double *G, int D, double *s, double *Vrows, int 
   // sweeps are enqueued in batches and the device-side convergence flag is read once per batch (a cold
   // start needs ~11 sweeps at D = 200, ~13 at D = 512; sweeps past convergence return at once)
   const int max_sweeps = 40;
-  int sweeps = 0, hrot[4] = {0, 0, 0, 0};
-  PLDA_HIP(h, hipMemsetAsync(drot, 0, 4 * sizeof(int), h->stream));
-  for (int enq = 0; D > 1 && enq < max_sweeps && !hrot[2];) {
-    const int batch = std::min(max_sweeps - enq, enq == 0 ? (warm ? 3 : 9) : 2);
-    for (int b = 0; b < batch; ++b) PLDA_TRY(jacobi_sweep_graph(h, A, V, D, tol, drot));
-    enq += batch;
-    PLDA_HIP(h, hipMemcpyAsync(hrot, drot, 4 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  int sweeps = 0;
+  // sweeps until the device reports convergence: *took = the sweeps that needed
+  auto run = [&](int first, int *took) -> int {
+    int hrot[4] = {0, 0, 0, 0};
+    PLDA_HIP(h, hipMemsetAsync(drot, 0, 4 * sizeof(int), h->stream));
+    for (int enq = 0; D > 1 && enq < max_sweeps && !hrot[2];) {
+      const int batch = std::min(max_sweeps - enq, enq == 0 ? first : 2);
+      for (int b = 0; b < batch; ++b) PLDA_TRY(jacobi_sweep_graph(h, A, V, D, tol, drot));
+      enq += batch;
+      PLDA_HIP(h, hipMemcpyAsync(hrot, drot, 4 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+      PLDA_HIP(h, hipStreamSynchronize(h->stream));
+    }
+    if (D > 1 && !hrot[2]) return fail(h, PLDA_E_NUMERIC, "sym_eig: Jacobi did not converge in %d sweeps", max_sweeps);
+    *took = D > 1 ? hrot[2] : 0;
+    return PLDA_OK;
+  };
+  PLDA_TRY(run(warm ? 3 : 9, &sweeps));
+  eig_values_kernel<<<(unsigned)ceil_div(D, 4), 256, 0, h->stream>>>(A, V, D, lam, 0.0);
+  PLDA_LAUNCH_CHECK(h);
+  if (h->eig_keep_sign && D > 1) {
+    // Orthogonal rows of A = V G diagonalise G^2, not G: eigenvalues +l_i and -l_j of nearly equal magnitude are a
+    // (nearly) double eigenvalue of G^2, whose basis the rotations leave wherever it stands.  The rows p, q of such a pair
+    // stay mixed by an angle up to tol l / (2 | |l_i| - |l_j| |), harmless in G^2 but a residual tol l^2 / | |l_i| - |l_j| |
+    // in G: 2e-11 .. 4e-10 |G| on Gaussian symmetric matrices of order 87 .. 1024, with eigenvalues and orthogonality at
+    // 1e-13 (tests/test_gpu_eig.py: test_jacobi_every_size).  Callers that floor the spectrum at zero pass (nearly)
+    // semi-definite matrices and never meet it; for a signed spectrum with both signs present, a second stage continues
+    // from the converged V on G + sigma I, sigma = 2 max |lambda|: positive definite, eigenvalues within [sigma / 2,
+    // 3 sigma / 2], so equal magnitudes are equal eigenvalues and any basis of theirs is right.  A' = V (G + sigma I) =
+    // A + sigma V needs no product; one or two sweeps settle it.  (Eigenvalues below 1e-12 max |lambda| can contribute
+    // no more than twice that to the residual and do not count as a sign.)
+    std::vector<double> hl((size_t)D);
+    PLDA_HIP(h, hipMemcpyAsync(hl.data(), lam, (size_t)D * 8, hipMemcpyDeviceToHost, h->stream));
     PLDA_HIP(h, hipStreamSynchronize(h->stream));
+    const double lmax = *std::max_element(hl.begin(), hl.end()), lmin = *std::min_element(hl.begin(), hl.end());
+    const double rho = std::max(std::fabs(lmax), std::fabs(lmin));
+    if (lmin < -1e-12 * rho && lmax > 1e-12 * rho) {
+      const double sigma = 2.0 * rho;
+      int more = 0;
+      jacobi_shift_kernel<<<(unsigned)ceil_div((int64_t)DD, 256), 256, 0, h->stream>>>(A, V, (int64_t)DD, sigma);
+      PLDA_LAUNCH_CHECK(h);
+      PLDA_TRY(run(3, &more));
+      sweeps += more;
+      eig_values_kernel<<<(unsigned)ceil_div(D, 4), 256, 0, h->stream>>>(A, V, D, lam, sigma);
+    }
   }
-  if (D > 1 && !hrot[2]) return fail(h, PLDA_E_NUMERIC, "sym_eig: Jacobi did not converge in %d sweeps", max_sweeps);
-  sweeps = D > 1 ? hrot[2] : 0;
   if (sweeps_out) *sweeps_out = sweeps;
   h->jac_total_sweeps += sweeps;
-  eig_values_kernel<<<(unsigned)ceil_div(D, 4), 256, 0, h->stream>>>(A, V, D, lam);
   eig_sort_kernel<<<D, 64, 0, h->stream>>>(lam, V, D, s, Vrows, !h->eig_keep_sign);
   PLDA_LAUNCH_CHECK(h);
   return PLDA_OK;

@@ -305,6 +305,7 @@ static int syrk_blk_pair(plda_handle *h, int D, int64_t K1, const double *X, int
   ga.K[0] = K1; ga.rows[0] = rows1; ga.ld[0] = ldx; ga.M[0] = X; ga.W[0] = W1;
   ga.K[1] = K2; ga.rows[1] = rows2; ga.ld[1] = K2 > 0 ? ldx2 : ldx; ga.M[1] = K2 > 0 ? X2 : X; ga.W[1] = K2 > 0 ? W2 : W1;
   ga.part = part;
+  note_kernel(h, "syrk_blk_kernel");
   syrk_blk_kernel<<<grid, 512, ldsb, h->stream>>>(ga, plan, groups);
   syrk_tri_reduce_kernel<<<(unsigned)ntri, 1024, 0, h->stream>>>(part, groups, D, alpha, beta, C, ldc);
   PLDA_LAUNCH_CHECK(h);

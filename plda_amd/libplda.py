@@ -1002,6 +1002,13 @@ class MPlda(object):
         self._ck(self._lib.plda_score_last_kernel(self._h, buf, 128))
         return buf.value.decode()
 
+    def linalg_last_kernels(self):
+        """The kernels (template arguments included) that the fp64 building blocks dispatched since the last sym_eig,
+        gemm_f64 or spd_inverse call began, each once, in the order of first launch (tests pin dispatch classes by it)."""
+        buf = C.create_string_buffer(1024)
+        self._ck(self._lib.plda_linalg_last_kernels(self._h, buf, 1024))
+        return [k for k in buf.value.decode().split(";") if k]
+
     def score_last_shape(self):
         """(M, Nt, algorithmic GEMM depth) of the last score_matrix* call: depth Dout (uniform count), Dout + G - 1
         (mixed counts, bucketed by the G distinct counts) or 2 Dout (mixed counts, depth-2D form)."""
