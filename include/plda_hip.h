@@ -902,6 +902,78 @@ int plda_adapt_update(plda_handle *h, double within_scale, double between_scale,
 int plda_blend_model(plda_handle *h, int32_t D, const double *mean2, const double *transform2, const double *psi2,
                      double alpha, double alpha_mean);
 
+/* ---- speaker clustering (K15; csrc/ahc.hip): batched average-linkage agglomerative clustering (AHC / UPGMA) on PLDA score
+ * blocks -- the diarisation use of a PLDA back-end (Kaldi: ivector-plda-scoring-dense + agglomerative-cluster).  The reference
+ * has NO counterpart (it verifies, it does not cluster), so this is the project's own extension: tests/ahc_model.py pins it to
+ * the bit.
+ *
+ * A RECORDING r is a run of N = offsets[r+1] - offsets[r] consecutive segments, 1 <= N <= PLDA_AHC_MAX.  Its input is an fp32
+ * score block S [N, N], row-major.  The diagonal is never read.
+ *
+ * COST.  c(i, j) = -((double)S[i, j] + (double)S[j, i]) / 2 for i != j; both steps are exact in fp64.  (The two fp32
+ * triangles of a PLDA block differ in their last bits, so the block is symmetrised, not half-read.)  A non-finite
+ * off-diagonal score fails the call with PLDA_E_INVAL and the count in plda_last_error, as a calibration pass does; the
+ * outputs of such a call are unspecified.
+ *
+ * STATE.  Clusters live in slots; a cluster's slot is its smallest member index.  Every pair of live slots a < b holds
+ * sum(a, b), the fp64 sum of c over the size(a) * size(b) cross pairs.  At the start sum(i, j) = c(i, j), every size is 1 and
+ * k = N slots are live.
+ *
+ * ONE STEP.  The candidate value of a pair is v(a, b) = sum(a, b) / (double)(size(a) * size(b)): the integer product, one
+ * conversion, one IEEE fp64 division (no fast-math, no reciprocal).  The pair to merge is the minimum under the total order
+ * v ascending, then a ascending, then b ascending; -0.0 == +0.0.  The step STOPS the recording if k <= max(1, min_clusters[r]),
+ * or if has_threshold != 0 and !(v <= -(double)threshold) (a score threshold: pairs whose average score is at least the
+ * threshold merge).  Otherwise, for every other live slot x, sum(a, x) <- sum(a, x) + sum(b, x) -- one fp64 addition with the
+ * operands in that order -- then size(a) += size(b), slot b dies and k drops by one.  This is average linkage on sums, as
+ * Kaldi keeps them.  The result is fully determined by the input bits: it does not depend on the grid, on how recordings are
+ * grouped into launches, or on the run.
+ *
+ * OUTPUTS.  labels int32 [T], T = offsets[R]: within a recording the clusters are numbered 0 .. k-1 by ascending slot.
+ * n_clusters int32 [R].  The merge record is nullable -- pass all three of its pointers or none (one alone: PLDA_E_INVAL):
+ * merge_a, merge_b int32 and merge_cost fp64, each [T - R]; recording r owns entries [offsets[r] - r, offsets[r+1] - r - 1):
+ * the merges made come first, in order, with cost = v; the unused tail holds -1, -1, +inf.  Nothing else is written.
+ *
+ * METHOD.  One workgroup per recording, in two dispatch classes: the LDS class holds the strict upper triangle of the sums in
+ * LDS, the HBM class an N x N fp64 matrix in handle scratch (N * N * 8 bytes per recording in flight); both keep a per-slot
+ * cache (best partner b > a and its v) in LDS, so a step is a workgroup reduction over the cache, an update of row and column
+ * a, and a rescan of only the rows whose cached partner was a or b.  The LDS class takes the largest N whose triangle and
+ * cache fit the 160 KiB of one compute unit.  The recordings of a call are grouped into launches so that the HBM-class scratch
+ * of a launch stays within 2 GiB (never fewer than one recording; PLDA_AHC_SCRATCH_BYTES in the environment at plda_create
+ * sets another budget: tests); the scratch belongs to the handle and is freed by plda_destroy.
+ *
+ *   plda_ahc_plan         out[0] = the class of a recording of N segments (0 LDS, 1 HBM), out[1] = the scratch bytes one
+ *                         such recording takes (0 in the LDS class), out[2] = the largest N of the LDS class.
+ *   plda_ahc_matrix_dev   packed blocks in HBM: block r starts at dscores + block_off[r], row-major N_r x N_r.  block_off
+ *                         [R + 1] (in floats), offsets [R + 1] and min_clusters [R] (nullable: 1 everywhere) are HOST arrays
+ *                         (the host sizes the launches from them; the convention of the fusion's pointer arrays); scores and
+ *                         outputs are in HBM.  PLDA_E_INVAL: offsets that do not ascend from 0, a recording that is empty or
+ *                         above PLDA_AHC_MAX, block_off[r+1] - block_off[r] < N_r * N_r, min_clusters[r] < 1.  Enqueues on the
+ *                         handle's stream and synchronises it once, to read the count of non-finite scores (as the
+ *                         calibration's _dev forms do).
+ *   plda_ahc_matrix       the same with scores and outputs in host memory.
+ *   plda_score_ahc*       the operand form: X [T, Dout] holds already-transformed segment vectors (num_examples = 1).  The
+ *                         block of recording r is what plda_score_matrix_dev(X_r, NULL, 1, N_r, X_r, N_r, NULL, NULL, ..,
+ *                         ld_out = N_r) writes, bit for bit: it comes from that same enqueue path, one call per recording,
+ *                         into the S-norm slab buffer, as many consecutive recordings at a time as the budget above holds
+ *                         (each block at a 256-byte boundary), clustered, dropped.  A prepared test side is dropped, as in
+ *                         plda_cohort_stats_dev.
+ * OUT OF SCOPE, each on purpose: Kaldi's per-recording mean subtraction and PCA before scoring; its two-pass clustering of very
+ * long recordings; RTTM output; DER; several workgroups on one recording. ---- */
+#define PLDA_AHC_MAX 4096
+int plda_ahc_plan(plda_handle *h, int64_t N, int32_t out[3]);
+int plda_ahc_matrix_dev(plda_handle *h, const float *dscores, const int64_t *block_off, const int64_t *offsets, int64_t R,
+                        int32_t has_threshold, double threshold, const int32_t *min_clusters, int32_t *dlabels,
+                        int32_t *dn_clusters, int32_t *dmerge_a, int32_t *dmerge_b, double *dmerge_cost);
+int plda_ahc_matrix(plda_handle *h, const float *scores, const int64_t *block_off, const int64_t *offsets, int64_t R,
+                    int32_t has_threshold, double threshold, const int32_t *min_clusters, int32_t *labels, int32_t *n_clusters,
+                    int32_t *merge_a, int32_t *merge_b, double *merge_cost);
+int plda_score_ahc_dev(plda_handle *h, const double *dX, const int64_t *offsets, int64_t R, int32_t has_threshold,
+                       double threshold, const int32_t *min_clusters, int32_t *dlabels, int32_t *dn_clusters,
+                       int32_t *dmerge_a, int32_t *dmerge_b, double *dmerge_cost);
+int plda_score_ahc(plda_handle *h, const double *X, const int64_t *offsets, int64_t R, int32_t has_threshold, double threshold,
+                   const int32_t *min_clusters, int32_t *labels, int32_t *n_clusters, int32_t *merge_a, int32_t *merge_b,
+                   double *merge_cost);
+
 /* ---- LDA: replaces the reference's second model, the pure-Python
  * class LDA of python/liblda/lda.py (used by scoring/scoreLDA.py:175,224,241), on the same
  * handle.  All fp64.  solver: 0 = 'svd' (lda.py:171-209), 1 = 'eigen' (:134-169),

@@ -83,6 +83,12 @@ class PLDA(object):
         self._instance.blend(other, alpha, alpha_mean)
         return self
 
+    def cluster(self, x, offsets, threshold=0.0, num_speakers=None, return_merges=False):
+        """Cluster the segments of R recordings (diarisation): x [T, featdim] raw segment vectors, recording r owning rows
+        offsets[r] .. offsets[r+1]; average-linkage merging while the best pair's average score is at least `threshold` and
+        more than `num_speakers` clusters are left.  Returns (labels, n_clusters[, merges]); plda_amd/diarize.py."""
+        return self._instance.cluster(x, offsets, threshold, num_speakers, return_merges)
+
     def transform_array(self, xbar, num_examples=1):
         return self._instance.transform_array(xbar, num_examples)
 

@@ -10,14 +10,16 @@ Layout (only what the hot path needs):
   fusion.py   linear fusion of K systems' scores by logistic regression (csrc/fusion.hip)
   adaptation.py the result of MPlda.adapt: unsupervised PLDA domain adaptation and model interpolation (csrc/adapt.hip)
   identify.py rank-N identification rates and the CMC curve from the ids of MPlda.top_n (csrc/topn.hip); pure NumPy
+  diarize.py  speaker clustering: batched average-linkage AHC on score blocks (csrc/ahc.hip), cut() in pure NumPy
 """
 from .libplda import MPlda  # noqa: F401
 from . import calibration  # noqa: F401
 from . import fusion  # noqa: F401
 from . import identify  # noqa: F401
 from . import adaptation  # noqa: F401
+from . import diarize  # noqa: F401
 from .calibration import Calibration  # noqa: F401
 from .fusion import Fusion  # noqa: F401
 from .adaptation import Adaptation  # noqa: F401
 
-__all__ = ["MPlda", "Calibration", "Fusion", "Adaptation", "calibration", "fusion", "identify", "adaptation"]
+__all__ = ["MPlda", "Calibration", "Fusion", "Adaptation", "calibration", "fusion", "identify", "adaptation", "diarize"]

@@ -141,6 +141,11 @@ SIGNATURES = {
     "plda_adapt_add_stats": (C.c_int, [_vp, _f64, _i64, _vp, _vp, _vp]),
     "plda_adapt_update": (C.c_int, [_vp, _f64, _f64, _f64, _vp, _vp]),
     "plda_blend_model": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _f64, _f64]),
+    "plda_ahc_plan": (C.c_int, [_vp, _i64, _vp]),
+    "plda_ahc_matrix_dev": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _f64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "plda_ahc_matrix": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _f64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "plda_score_ahc_dev": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _f64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "plda_score_ahc": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _f64, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
 

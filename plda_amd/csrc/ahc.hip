@@ -1,0 +1,551 @@
+// plda_amd/csrc/ahc.hip -- speaker clustering: batched average-linkage agglomerative clustering (AHC / UPGMA) on PLDA score
+// blocks (the contract is in include/plda_hip.h, the bit-exact host model in tests/ahc_model.py).
+//
+// The reference stops at verification; Kaldi's PLDA is also the back-end of diarisation (ivector-plda-scoring-dense +
+// agglomerative-cluster): every segment of a recording is scored against every other one and the segments are merged
+// bottom-up.  A recording is a chain of up to N - 1 DEPENDENT merges, each a few microseconds of work: one workgroup per
+// recording, many recordings in flight.
+//
+//   ahc_count_kernel    the non-finite off-diagonal scores of every recording of the call (one integer counter; a call that
+//                       meets one fails, and the kernels behind it write nothing)
+//   ahc_load_kernel     HBM class: the fp32 block symmetrised into an N x N fp64 matrix of sums in handle scratch
+//                       (c(i, j) = -((double)S[i, j] + (double)S[j, i]) / 2, both steps exact); the LDS class symmetrises
+//                       straight into LDS at the head of its merge kernel
+//   ahc_merge_kernel    <HBM = false> the strict upper triangle of fp64 sums in LDS, N <= ahc_lds_max();
+//                       <HBM = true>  the full symmetric matrix in scratch (row a and row b of a merge are then contiguous).
+//                       Both keep the per-slot state in LDS: size, best partner b > a and its v, the member list of the slot.
+//   ahc_label_kernel    the final slot of every segment -> cluster numbers 0 .. k - 1 by ascending slot
+//
+// One step: (1) the global minimum (v, a) is a workgroup reduction over the row cache; (2) sum(a, x) += sum(b, x) for every
+// live x, and while x is in hand: a row x < a whose cached partner was a or b, or a row a < x < b whose partner was b, is
+// queued for a rescan; any other row x < a takes the new v(x, a) if it beats its cache under (v, then partner index);
+// (3) sizes and member lists change hands; (4) the queued rows and row a are rescanned, one wave per row.  Rows above b hold
+// only partners above b and are untouched.  Every comparison is on the total order (v, a, b) with IEEE ==, so -0.0 == +0.0,
+// and every v is one fp64 division of the sum by the integer product of the sizes: the result does not depend on the order
+// in which waves take rows, on the grid or on the grouping into launches.  (The file is built with -ffp-contract=off; it has
+// no fast-math and no reciprocal.)
+#include "common.hpp"
+
+#include <algorithm>
+#include <cmath>
+#include <vector>
+
+namespace plda {
+
+namespace {
+
+constexpr int AHC_MAX = PLDA_AHC_MAX;
+constexpr int AHC_LDS_BYTES = 160 * 1024;      // one workgroup may hold all of a CU's LDS
+constexpr int AHC_FIXED_BYTES = 512;           // reduction slots and step scalars
+constexpr int AHC_SLOT_BYTES = 8 + 5 * 4;      // bv | bp, sz, list, next, tail
+constexpr int AHC_T_LDS = 256, AHC_T_HBM = 1024;
+constexpr int AHC_MAX_WAVES = AHC_T_HBM / 64;
+
+// one recording of a launch (host-built, uploaded once per enqueue)
+struct AhcRec {
+  long long boff;    // first float of the block, relative to the scores pointer
+  long long off;     // first segment (labels, slots)
+  long long scr;     // HBM class: first double of the N x N sums in scratch
+  int n, r, minc, pad;
+};
+
+constexpr long long ahc_tri(long long n) { return n * (n - 1) / 2; }
+constexpr long long ahc_lds_bytes(long long n, bool hbm) {
+  return (hbm ? 0 : 8 * ahc_tri(n)) + (long long)AHC_SLOT_BYTES * n + AHC_FIXED_BYTES;
+}
+constexpr int ahc_lds_max_calc() {
+  int n = 1;
+  while (n < AHC_MAX && ahc_lds_bytes(n + 1, false) <= AHC_LDS_BYTES) ++n;
+  return n;
+}
+constexpr int AHC_LDS_MAX = ahc_lds_max_calc();
+static_assert(ahc_lds_bytes(AHC_LDS_MAX, false) <= AHC_LDS_BYTES, "the LDS class must fit one CU's LDS");
+static_assert(ahc_lds_bytes(AHC_MAX, true) <= AHC_LDS_BYTES, "the HBM class's slot state must fit one CU's LDS");
+
+__device__ __forceinline__ bool ahc_finite(float f) { return (__float_as_uint(f) & 0x7f800000u) != 0x7f800000u; }
+__device__ __forceinline__ double ahc_cost(float sij, float sji) { return -(((double)sij + (double)sji) / 2.0); }
+
+// lexicographic minimum of (v, i) over the wave, i < 0 = nothing; every lane ends with the result
+__device__ __forceinline__ void ahc_wave_min(double &v, int &i) {
+#pragma unroll
+  for (int o = 32; o; o >>= 1) {
+    const double ov = __shfl_xor(v, o);
+    const int oi = __shfl_xor(i, o);
+    if (oi >= 0 && (i < 0 || ov < v || (ov == v && oi < i))) { v = ov; i = oi; }
+  }
+}
+
+// grid (pieces, recordings): the off-diagonal scores that are not finite, added to *bad
+__global__ __launch_bounds__(256) void ahc_count_kernel(const float *__restrict__ S, const AhcRec *__restrict__ tab,
+                                                        unsigned long long *bad) {
+  const AhcRec rc = tab[blockIdx.y];
+  const long long n = rc.n, total = n * n;
+  const float *__restrict__ blk = S + rc.boff;
+  unsigned cnt = 0;
+  for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long long)gridDim.x * 256) {
+    const long long i = e / n, j = e - i * n;
+    if (i != j && !ahc_finite(blk[e])) ++cnt;
+  }
+  if (cnt) atomicAdd(bad, (unsigned long long)cnt);   // rare: one integer atomic per lane that met one
+}
+
+// grid (tiles, recordings of the group), 32 x 32 threads: M[i, j] = c(i, j), the transposed tile through LDS; diagonal 0
+__global__ __launch_bounds__(1024) void ahc_load_kernel(const float *__restrict__ S, const AhcRec *__restrict__ tab,
+                                                        double *__restrict__ scratch, const unsigned long long *__restrict__ bad) {
+  __shared__ float tile[32][33];
+  if (*bad) return;
+  const AhcRec rc = tab[blockIdx.y];
+  const int n = rc.n, nt = (n + 31) / 32;
+  if ((int)blockIdx.x >= nt * nt) return;
+  const int ti = blockIdx.x / nt, tj = blockIdx.x - ti * nt;
+  const float *__restrict__ blk = S + rc.boff;
+  double *__restrict__ M = scratch + rc.scr;
+  const int tx = threadIdx.x, ty = threadIdx.y;
+  {   // the mirror tile: rows tj * 32 .., columns ti * 32 ..
+    const int r = tj * 32 + ty, c = ti * 32 + tx;
+    tile[ty][tx] = (r < n && c < n) ? blk[(long long)r * n + c] : 0.f;
+  }
+  __syncthreads();
+  const int i = ti * 32 + ty, j = tj * 32 + tx;
+  if (i < n && j < n) M[(long long)i * n + j] = i == j ? 0.0 : ahc_cost(blk[(long long)i * n + j], tile[tx][ty]);
+}
+
+// the sums of a recording: the strict upper triangle in LDS, or the full symmetric matrix in HBM
+template <bool HBM> struct AhcSums;
+template <> struct AhcSums<false> {
+  double *t; int n;
+  __device__ __forceinline__ int idx(int i, int j) const { return i * (2 * n - i - 1) / 2 + (j - i - 1); }   // i < j
+  __device__ __forceinline__ double get(int i, int j) const { return i < j ? t[idx(i, j)] : t[idx(j, i)]; }
+  __device__ __forceinline__ void set(int i, int j, double s) const { if (i < j) t[idx(i, j)] = s; else t[idx(j, i)] = s; }
+};
+template <> struct AhcSums<true> {
+  double *m; int n;
+  __device__ __forceinline__ double get(int i, int j) const { return m[(long long)i * n + j]; }
+  __device__ __forceinline__ void set(int i, int j, double s) const { m[(long long)i * n + j] = s; m[(long long)j * n + i] = s; }
+};
+
+// row x's best partner y in [y0, y1), y0 > x, among the live slots, by (v, y); one wave, every lane gets the result
+template <bool HBM>
+__device__ __forceinline__ void ahc_scan_row(const AhcSums<HBM> &sums, const int *sz, int x, int y0, int y1, int lane, double &bv,
+                                             int &bp) {
+  const int sx = sz[x];
+  double v = 0.0;
+  int p = -1;
+#pragma unroll 4
+  for (int y = y0 + lane; y < y1; y += 64) {
+    const int sy = sz[y];
+    const double s = sums.get(x, y);             // (a dead slot's entry is stale, in range and unused: the loads of the
+    if (sy > 0) {                                //  unrolled iterations are in flight together)
+      const double c = s / (double)(sx * sy);
+      if (p < 0 || c < v) { v = c; p = y; }      // y ascends within a lane: a tie keeps the smaller y
+    }
+  }
+  ahc_wave_min(v, p);
+  bv = v; bp = p;
+}
+
+template <bool HBM, int T>
+__global__ __launch_bounds__(T) void ahc_merge_kernel(const float *__restrict__ S, const AhcRec *__restrict__ tab, double *scratch,
+                                                      const unsigned long long *__restrict__ bad, int has_thr, double thr,
+                                                      int *__restrict__ slot, int *__restrict__ n_clusters,
+                                                      int *__restrict__ merge_a, int *__restrict__ merge_b,
+                                                      double *__restrict__ merge_cost) {
+  extern __shared__ double ahc_smem[];
+  if (*bad) return;
+  constexpr int W = T / 64;
+  const AhcRec rc = tab[blockIdx.x];
+  const int n = rc.n, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+
+  // LDS: [triangle (LDS class)] | bv[n] | red_v[16] | bp[n] sz[n] list[n] next[n] tail[n] | red_i[16] | cnt
+  double *p8 = ahc_smem;
+  AhcSums<HBM> sums;
+  if constexpr (HBM) { sums.m = scratch + rc.scr; sums.n = n; }
+  else { sums.t = p8; sums.n = n; p8 += ahc_tri(n); }
+  double *bv = p8; p8 += n;
+  double *red_v = p8; p8 += AHC_MAX_WAVES;
+  int *p4 = reinterpret_cast<int *>(p8);
+  int *bp = p4; p4 += n;
+  int *sz = p4; p4 += n;
+  int *list = p4; p4 += n;
+  int *next = p4; p4 += n;
+  int *tail = p4; p4 += n;
+  int *red_i = p4; p4 += AHC_MAX_WAVES;
+  int *cnt = p4;
+
+  if constexpr (!HBM) {
+    const float *__restrict__ blk = S + rc.boff;
+    for (int i = 0; i < n - 1; ++i)
+      for (int j = i + 1 + tid; j < n; j += T) sums.t[sums.idx(i, j)] = ahc_cost(blk[(long long)i * n + j], blk[(long long)j * n + i]);
+  }
+  for (int x = tid; x < n; x += T) { sz[x] = 1; next[x] = -1; tail[x] = x; }
+  if (tid == 0) *cnt = 0;
+  __syncthreads();
+  for (int x = wave; x < n; x += W) {
+    double v; int p;
+    ahc_scan_row<HBM>(sums, sz, x, x + 1, n, lane, v, p);
+    if (lane == 0) { bv[x] = v; bp[x] = p; }
+  }
+  __syncthreads();
+
+  const int stop_k = rc.minc > 1 ? rc.minc : 1;
+  const long long mbase = rc.off - rc.r;      // this recording's first entry of the merge record
+  const double neg_thr = -thr;
+  int k = n, m = 0;
+  while (k > stop_k) {
+    // (1) the pair to merge: minimum over the row cache by (v, a); b comes with the row
+    double v = 0.0;
+    int a = -1;
+    for (int x = tid; x < n; x += T) {
+      if (sz[x] > 0 && bp[x] >= 0) {
+        const double c = bv[x];
+        if (a < 0 || c < v) { v = c; a = x; }    // x ascends within a thread
+      }
+    }
+    ahc_wave_min(v, a);
+    if (lane == 0) { red_v[wave] = v; red_i[wave] = a; }
+    __syncthreads();
+    v = red_v[0]; a = red_i[0];
+#pragma unroll
+    for (int w = 1; w < W; ++w) {
+      const double ov = red_v[w];
+      const int oi = red_i[w];
+      if (oi >= 0 && (a < 0 || ov < v || (ov == v && oi < a))) { v = ov; a = oi; }
+    }
+    if (a < 0) break;                            // (cannot happen while k > 1; keeps every index below in range)
+    if (has_thr && !(v <= neg_thr)) break;
+    const int b = bp[a];
+    if (tid == 0 && merge_a) { merge_a[mbase + m] = a; merge_b[mbase + m] = b; merge_cost[mbase + m] = v; }
+    // (2) the sums of a take b's; rows whose cache the merge touches
+    const int nsa = sz[a] + sz[b];
+    for (int x = tid; x < n; x += T) {
+      const int sx = sz[x];
+      if (sx <= 0 || x == a || x == b) continue;
+      const double s = sums.get(a, x) + sums.get(b, x);
+      sums.set(a, x, s);
+      if (x < a) {
+        const int p = bp[x];
+        if (p == a || p == b) list[atomicAdd(cnt, 1)] = x;
+        else {
+          const double c = s / (double)(nsa * sx);
+          if (c < bv[x] || (c == bv[x] && a < p)) { bv[x] = c; bp[x] = a; }
+        }
+      } else if (x < b) {
+        if (bp[x] == b) list[atomicAdd(cnt, 1)] = x;
+      }
+    }
+    __syncthreads();
+    // (3) sizes and members
+    if (tid == 0) {
+      sz[a] = nsa; sz[b] = 0;
+      next[tail[a]] = b; tail[a] = tail[b];
+      list[atomicAdd(cnt, 1)] = a;
+    }
+    __syncthreads();
+    // (4) rescans: one wave per row, or -- fewer rows than waves, the usual case -- W / nl waves per row, each on a piece of
+    // the row, combined in the order of the pieces (the order (v, y) is total: the split does not change the result)
+    const int nl = *cnt;
+    const int parts = nl >= W ? 1 : W / nl;
+    if (parts == 1) {
+      for (int q = wave; q < nl; q += W) {
+        const int x = list[q];
+        double c; int p;
+        ahc_scan_row<HBM>(sums, sz, x, x + 1, n, lane, c, p);
+        if (lane == 0) { bv[x] = c; bp[x] = p; }
+      }
+    } else {
+      const int q = wave / parts, pi = wave - q * parts;
+      if (q < nl) {
+        const int x = list[q];
+        const int seg = ((n - x - 1 + parts - 1) / parts + 63) & ~63;
+        const int y0 = x + 1 + pi * seg, y1 = min(y0 + seg, n);
+        double c; int p;
+        ahc_scan_row<HBM>(sums, sz, x, y0, y1, lane, c, p);
+        if (lane == 0) { red_v[wave] = c; red_i[wave] = p; }
+      }
+      __syncthreads();
+      if (tid < nl) {
+        double c = 0.0;
+        int p = -1;
+        for (int j = 0; j < parts; ++j) {
+          const double oc = red_v[tid * parts + j];
+          const int op = red_i[tid * parts + j];
+          if (op >= 0 && (p < 0 || oc < c)) { c = oc; p = op; }      // the pieces ascend in y: a tie keeps the smaller y
+        }
+        const int x = list[tid];
+        bv[x] = c; bp[x] = p;
+      }
+    }
+    __syncthreads();
+    if (tid == 0) *cnt = 0;                      // (the next append is behind the next step's first barrier)
+    --k; ++m;
+  }
+
+  // the unused tail of the merge record, the count, and every segment's final slot
+  if (merge_a)
+    for (int q = m + tid; q < n - 1; q += T) { merge_a[mbase + q] = -1; merge_b[mbase + q] = -1; merge_cost[mbase + q] = INFINITY; }
+  if (tid == 0) n_clusters[rc.r] = k;
+  for (int s = tid; s < n; s += T)
+    if (sz[s] > 0)
+      for (int i = s; i >= 0; i = next[i]) slot[rc.off + i] = s;
+}
+
+// one workgroup per recording: a slot is live iff slot[s] == s; label = the number of live slots below the segment's slot
+__global__ __launch_bounds__(256) void ahc_label_kernel(const AhcRec *__restrict__ tab, const int *__restrict__ slot,
+                                                        const unsigned long long *__restrict__ bad, int *__restrict__ labels) {
+  __shared__ int rank[AHC_MAX];
+  __shared__ int part[256];
+  if (*bad) return;
+  const AhcRec rc = tab[blockIdx.x];
+  const int n = rc.n, tid = threadIdx.x;
+  const int *__restrict__ sl = slot + rc.off;
+  const int per = (n + 255) / 256, s0 = min(tid * per, n), s1 = min(s0 + per, n);
+  int c = 0;
+  for (int s = s0; s < s1; ++s) c += sl[s] == s ? 1 : 0;
+  part[tid] = c;
+  __syncthreads();
+  int base = 0;
+  for (int t = 0; t < tid; ++t) base += part[t];
+  for (int s = s0; s < s1; ++s) { rank[s] = base; base += sl[s] == s ? 1 : 0; }
+  __syncthreads();
+  for (int i = tid; i < n; i += 256) labels[rc.off + i] = rank[sl[i]];
+}
+
+template <bool HBM, int T> int ahc_merge_attr(plda_handle *h) {
+  static DeviceOnce attr;
+  if (attr.needed(h->device)) {
+    PLDA_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&ahc_merge_kernel<HBM, T>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    AHC_LDS_BYTES));
+    attr.done(h->device);
+  }
+  return PLDA_OK;
+}
+
+// the scratch of one launch of HBM-class recordings: the S-norm slab's rule (<= 2 GiB; PLDA_AHC_SCRATCH_BYTES at plda_create
+// for the tests), never less than one recording
+int64_t ahc_budget(const plda_handle *h) { return h->ahc_scratch_bytes > 0 ? h->ahc_scratch_bytes : (int64_t)2 << 30; }
+
+struct AhcOut { int32_t *labels, *n_clusters, *merge_a, *merge_b; double *merge_cost; };
+
+// Enqueues the clustering of recordings [r0, r1) whose blocks start at dscores + boff[r - r0].  `tables` keeps the host copy
+// of the launch table alive until the caller has synchronised.  h->ahc_stat[0] must have been zeroed by the caller.
+int ahc_enqueue(plda_handle *h, const float *dscores, const int64_t *boff, const int64_t *offsets, int64_t r0, int64_t r1,
+                int has_thr, double thr, const int32_t *minc, const AhcOut &out, std::vector<std::vector<AhcRec>> &tables) {
+  const int64_t cnt = r1 - r0;
+  if (cnt <= 0) return PLDA_OK;
+  static const int bucket_top[] = {64, 96, 128, 160, AHC_LDS_MAX};
+  constexpr int NB = sizeof(bucket_top) / sizeof(bucket_top[0]);
+  struct Launch { int64_t first, count; int nmax; bool hbm; int64_t scratch; };
+  std::vector<Launch> launches;
+  tables.emplace_back();
+  std::vector<AhcRec> &tab = tables.back();
+  tab.reserve((size_t)cnt);
+  auto rec_of = [&](int64_t r) {
+    AhcRec rc;
+    rc.boff = boff[r - r0]; rc.off = offsets[r]; rc.scr = 0; rc.n = (int)(offsets[r + 1] - offsets[r]); rc.r = (int)r;
+    rc.minc = minc ? minc[r] : 1; rc.pad = 0;
+    return rc;
+  };
+  for (int bk = 0; bk < NB; ++bk) {           // LDS class: one launch per size bucket (the LDS of a launch is its largest N's)
+    const int lo = bk ? bucket_top[bk - 1] : 0, hi = bucket_top[bk];
+    Launch L{(int64_t)tab.size(), 0, 0, false, 0};
+    for (int64_t r = r0; r < r1; ++r) {
+      const int64_t n = offsets[r + 1] - offsets[r];
+      if (n > lo && n <= hi) { tab.push_back(rec_of(r)); ++L.count; L.nmax = std::max(L.nmax, (int)n); }
+    }
+    if (L.count) launches.push_back(L);
+  }
+  const int64_t budget = ahc_budget(h);
+  int64_t scratch_need = 0;
+  {                                           // HBM class: launches under the scratch budget
+    Launch L{(int64_t)tab.size(), 0, 0, true, 0};
+    for (int64_t r = r0; r < r1; ++r) {
+      const int64_t n = offsets[r + 1] - offsets[r];
+      if (n <= AHC_LDS_MAX) continue;
+      const int64_t bytes = n * n * 8;
+      if (L.count && (L.scratch + bytes > budget || L.count >= 32768)) {
+        launches.push_back(L);
+        L = Launch{(int64_t)tab.size(), 0, 0, true, 0};
+      }
+      AhcRec rc = rec_of(r);
+      rc.scr = L.scratch / 8;
+      tab.push_back(rc);
+      ++L.count; L.nmax = std::max(L.nmax, (int)n); L.scratch += bytes;
+      scratch_need = std::max(scratch_need, L.scratch);
+    }
+    if (L.count) launches.push_back(L);
+  }
+  if (scratch_need) PLDA_HIP(h, h->ahc_scratch.reserve((size_t)scratch_need));
+  PLDA_HIP(h, h->ahc_tab.reserve(tab.size() * sizeof(AhcRec)));
+  PLDA_HIP(h, h->ahc_slot.reserve((size_t)offsets[r1] * 4));       // (indexed by the call's segment numbers)
+  PLDA_HIP(h, hipMemcpyAsync(h->ahc_tab.p, tab.data(), tab.size() * sizeof(AhcRec), hipMemcpyHostToDevice, h->stream));
+  const AhcRec *dtab = h->ahc_tab.as<AhcRec>();
+  unsigned long long *dbad = h->ahc_stat.as<unsigned long long>();
+  double *scratch = h->ahc_scratch.as<double>();
+  int *dslot = h->ahc_slot.as<int>();
+  PLDA_TRY((ahc_merge_attr<false, AHC_T_LDS>(h)));
+  PLDA_TRY((ahc_merge_attr<true, AHC_T_HBM>(h)));
+
+  TraceScope ts(h, "ahc.count");
+  for (int64_t c0 = 0; c0 < cnt; c0 += 32768) {
+    const int64_t c = std::min<int64_t>(32768, cnt - c0);
+    int nmax = 0;
+    for (int64_t q = c0; q < c0 + c; ++q) nmax = std::max(nmax, tab[(size_t)q].n);
+    const int64_t pieces = std::max<int64_t>(1, std::min<int64_t>(ceil_div((int64_t)nmax * nmax, 256 * 16), 1024));
+    ahc_count_kernel<<<dim3((unsigned)pieces, (unsigned)c), 256, 0, h->stream>>>(dscores, dtab + c0, dbad);
+    PLDA_LAUNCH_CHECK(h);
+  }
+  ts.next("ahc.merge");
+  for (const Launch &L : launches) {
+    const size_t lds = (size_t)ahc_lds_bytes(L.nmax, L.hbm);
+    if (L.hbm) {
+      const int nt = (L.nmax + 31) / 32;
+      ahc_load_kernel<<<dim3((unsigned)(nt * nt), (unsigned)L.count), dim3(32, 32), 0, h->stream>>>(dscores, dtab + L.first, scratch, dbad);
+      PLDA_LAUNCH_CHECK(h);
+      ahc_merge_kernel<true, AHC_T_HBM><<<(unsigned)L.count, AHC_T_HBM, lds, h->stream>>>(
+          dscores, dtab + L.first, scratch, dbad, has_thr, thr, dslot, out.n_clusters, out.merge_a, out.merge_b, out.merge_cost);
+    } else {
+      ahc_merge_kernel<false, AHC_T_LDS><<<(unsigned)L.count, AHC_T_LDS, lds, h->stream>>>(
+          dscores, dtab + L.first, nullptr, dbad, has_thr, thr, dslot, out.n_clusters, out.merge_a, out.merge_b, out.merge_cost);
+    }
+    PLDA_LAUNCH_CHECK(h);
+  }
+  ts.next("ahc.label");
+  for (int64_t c0 = 0; c0 < cnt; c0 += 65536) {      // (the table is in launch order; the labels do not care)
+    const int64_t c = std::min<int64_t>(65536, cnt - c0);
+    ahc_label_kernel<<<(unsigned)c, 256, 0, h->stream>>>(dtab + c0, dslot, dbad, out.labels);
+    PLDA_LAUNCH_CHECK(h);
+  }
+  return PLDA_OK;
+}
+
+int ahc_check_args(plda_handle *h, const char *fn, const int64_t *offsets, int64_t R, int has_thr, double thr, const int32_t *minc,
+                   const AhcOut &out, const int64_t *block_off = nullptr, bool blocks = false) {
+  if (R < 1) return fail(h, PLDA_E_INVAL, "%s: R = %lld (must be >= 1)", fn, (long long)R);
+  if (R > (int64_t)0x7fffffff) return fail(h, PLDA_E_INVAL, "%s: R = %lld (at most 2^31 - 1)", fn, (long long)R);
+  if (!offsets) return fail(h, PLDA_E_INVAL, "%s: offsets is NULL", fn);
+  if (!out.labels) return fail(h, PLDA_E_INVAL, "%s: labels is NULL", fn);
+  if (!out.n_clusters) return fail(h, PLDA_E_INVAL, "%s: n_clusters is NULL", fn);
+  const int nm = (out.merge_a ? 1 : 0) + (out.merge_b ? 1 : 0) + (out.merge_cost ? 1 : 0);
+  if (nm != 0 && nm != 3) return fail(h, PLDA_E_INVAL, "%s: merge_a, merge_b and merge_cost must be given together or not at all", fn);
+  if (has_thr && std::isnan(thr)) return fail(h, PLDA_E_INVAL, "%s: threshold is NaN", fn);
+  if (offsets[0] != 0) return fail(h, PLDA_E_INVAL, "%s: offsets[0] = %lld (must be 0)", fn, (long long)offsets[0]);
+  for (int64_t r = 0; r < R; ++r) {
+    const int64_t n = offsets[r + 1] - offsets[r];
+    if (n < 1 || n > AHC_MAX)
+      return fail(h, PLDA_E_INVAL, "%s: recording %lld has %lld segments (must be 1 ... PLDA_AHC_MAX = %d; offsets must ascend)", fn,
+                  (long long)r, (long long)n, AHC_MAX);
+    if (minc && minc[r] < 1) return fail(h, PLDA_E_INVAL, "%s: min_clusters[%lld] = %d (must be >= 1)", fn, (long long)r, (int)minc[r]);
+  }
+  if (offsets[R] > (int64_t)0x7fffffff) return fail(h, PLDA_E_INVAL, "%s: %lld segments (at most 2^31 - 1)", fn, (long long)offsets[R]);
+  if (!blocks) return PLDA_OK;
+  if (!block_off) return fail(h, PLDA_E_INVAL, "%s: block_off is NULL", fn);
+  if (block_off[0] < 0) return fail(h, PLDA_E_INVAL, "%s: block_off[0] = %lld (must be >= 0)", fn, (long long)block_off[0]);
+  for (int64_t r = 0; r < R; ++r) {
+    const int64_t n = offsets[r + 1] - offsets[r];
+    if (block_off[r + 1] - block_off[r] < n * n)
+      return fail(h, PLDA_E_INVAL, "%s: block %lld holds %lld floats, its recording needs %lld x %lld", fn, (long long)r,
+                  (long long)(block_off[r + 1] - block_off[r]), (long long)n, (long long)n);
+  }
+  return PLDA_OK;
+}
+
+// reads the counter behind everything enqueued; the one synchronisation of a call
+int ahc_finish(plda_handle *h, const char *fn, int rc) {
+  unsigned long long bad = 0;
+  hipError_t e = hipMemcpyAsync(&bad, h->ahc_stat.p, 8, hipMemcpyDeviceToHost, h->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+  if (rc != PLDA_OK) return rc;
+  PLDA_HIP(h, e);
+  if (bad) return fail(h, PLDA_E_INVAL, "%s: %llu non-finite scores", fn, bad);
+  return PLDA_OK;
+}
+
+}  // namespace
+
+int ahc_validate(plda_handle *h, const char *fn, const int64_t *block_off, bool blocks, const int64_t *offsets, int64_t R, int has_thr,
+                 double thr, const int32_t *minc, const int32_t *labels, const int32_t *n_clusters, const int32_t *merge_a,
+                 const int32_t *merge_b, const double *merge_cost) {
+  const AhcOut out{const_cast<int32_t *>(labels), const_cast<int32_t *>(n_clusters), const_cast<int32_t *>(merge_a),
+                   const_cast<int32_t *>(merge_b), const_cast<double *>(merge_cost)};
+  return ahc_check_args(h, fn, offsets, R, has_thr, thr, minc, out, block_off, blocks);
+}
+
+int ahc_plan(plda_handle *h, int64_t N, int32_t *out) {
+  if (!out) return fail(h, PLDA_E_INVAL, "ahc_plan: out is NULL");
+  if (N < 1 || N > AHC_MAX) return fail(h, PLDA_E_INVAL, "ahc_plan: N = %lld (must be 1 ... PLDA_AHC_MAX = %d)", (long long)N, AHC_MAX);
+  const bool hbm = N > AHC_LDS_MAX;
+  out[0] = hbm ? 1 : 0;
+  out[1] = hbm ? (int32_t)(N * N * 8) : 0;
+  out[2] = AHC_LDS_MAX;
+  return PLDA_OK;
+}
+
+int ahc_matrix_device(plda_handle *h, const float *dscores, const int64_t *block_off, const int64_t *offsets, int64_t R, int has_thr,
+                      double thr, const int32_t *minc, int32_t *dlabels, int32_t *dn_clusters, int32_t *dmerge_a, int32_t *dmerge_b,
+                      double *dmerge_cost) {
+  const char *fn = "ahc_matrix";
+  const AhcOut out{dlabels, dn_clusters, dmerge_a, dmerge_b, dmerge_cost};
+  if (!dscores) return fail(h, PLDA_E_INVAL, "%s: scores is NULL", fn);
+  PLDA_TRY(ahc_check_args(h, fn, offsets, R, has_thr, thr, minc, out, block_off, true));
+  PLDA_HIP(h, h->ahc_stat.reserve(8));
+  PLDA_HIP(h, hipMemsetAsync(h->ahc_stat.p, 0, 8, h->stream));
+  std::vector<std::vector<AhcRec>> tables;
+  const int rc = ahc_enqueue(h, dscores, block_off, offsets, 0, R, has_thr, thr, minc, out, tables);
+  return ahc_finish(h, fn, rc);
+}
+
+int score_ahc_device(plda_handle *h, const double *dX, const int64_t *offsets, int64_t R, int has_thr, double thr,
+                     const int32_t *minc, int32_t *dlabels, int32_t *dn_clusters, int32_t *dmerge_a, int32_t *dmerge_b,
+                     double *dmerge_cost) {
+  const char *fn = "score_ahc";
+  const AhcOut out{dlabels, dn_clusters, dmerge_a, dmerge_b, dmerge_cost};
+  if (!h->fitted) return fail(h, PLDA_E_NOT_FITTED, "%s: model not fitted", fn);
+  if (!dX) return fail(h, PLDA_E_INVAL, "%s: X is NULL", fn);
+  PLDA_TRY(ahc_check_args(h, fn, offsets, R, has_thr, thr, minc, out));
+  const int D = h->Dout;
+  // the score blocks of consecutive recordings, each at a 256-byte boundary of the slab, as many as the budget holds
+  auto padded = [](int64_t n) { return round_up(n * n, 64); };
+  const int64_t budget = ahc_budget(h) / 4;
+  int64_t slab_floats = 0;
+  for (int64_t r = 0, cur = 0; r < R; ++r) {
+    const int64_t f = padded(offsets[r + 1] - offsets[r]);
+    if (cur && cur + f > budget) cur = 0;
+    cur += f;
+    slab_floats = std::max(slab_floats, cur);
+  }
+  PLDA_HIP(h, h->sn_slab.reserve((size_t)slab_floats * 4));
+  float *slab = h->sn_slab.as<float>();
+  h->prep_valid = false;           // (every block packs its own two sides)
+  PLDA_HIP(h, h->ahc_stat.reserve(8));
+  PLDA_HIP(h, hipMemsetAsync(h->ahc_stat.p, 0, 8, h->stream));
+  std::vector<std::vector<AhcRec>> tables;
+  std::vector<int64_t> boff;
+  int rc = PLDA_OK;
+  for (int64_t r0 = 0; r0 < R && rc == PLDA_OK;) {
+    boff.clear();
+    int64_t r1 = r0, cur = 0;
+    while (r1 < R) {
+      const int64_t f = padded(offsets[r1 + 1] - offsets[r1]);
+      if (cur && cur + f > budget) break;
+      boff.push_back(cur);
+      cur += f;
+      ++r1;
+    }
+    {
+      TraceScope ts(h, "ahc.block_gemm", 0.0, 1);
+      double flop = 0.0;
+      for (int64_t r = r0; r < r1 && rc == PLDA_OK; ++r) {
+        const int64_t n = offsets[r + 1] - offsets[r];
+        const double *x = dX + offsets[r] * D;
+        rc = score_matrix_device(h, x, nullptr, 1, n, x, n, nullptr, nullptr, slab + boff[(size_t)(r - r0)], n);
+        flop += 2.0 * (double)D * (double)n * (double)n;
+      }
+      if (ts.idx >= 0) h->trace_spans[ts.idx].work = flop;
+    }
+    if (rc == PLDA_OK) rc = ahc_enqueue(h, slab, boff.data(), offsets, r0, r1, has_thr, thr, minc, out, tables);
+    r0 = r1;
+  }
+  return ahc_finish(h, fn, rc);
+}
+
+}  // namespace plda

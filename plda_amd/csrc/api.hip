@@ -330,6 +330,7 @@ int plda_create(int device, plda_handle **out) {
     if (const char *v = std::getenv("PLDA_EER_SLAB_ROWS")) h->eer_slab_rows = std::atoll(v);
     if (const char *v = std::getenv("PLDA_SNORM_SLAB_ROWS")) h->sn_slab_rows = std::atoll(v);
     if (const char *v = std::getenv("PLDA_ADAPT_SLAB_ROWS")) h->ad_slab_rows = std::atoll(v);
+    if (const char *v = std::getenv("PLDA_AHC_SCRATCH_BYTES")) h->ahc_scratch_bytes = std::atoll(v);
     if (const char *v = std::getenv("PLDA_HIP_TRACE")) h->trace_on = h->trace_print = std::atoi(v) != 0;
     if (const char *v = std::getenv("PLDA_HOST_VARIANT")) h->host_variant = std::atoi(v);
     if (const char *v = std::getenv("PLDA_SWEEP_VARIANT")) h->sweep_variant = std::atoi(v);
@@ -2087,6 +2088,114 @@ int plda_fusion_map_dev(plda_handle *h, int32_t n_systems, const float *const *d
 // the Newton step: a pure function, no handle (include/plda_hip.h)
 int plda_fusion_newton(const plda_fusion_record *record, double prior, double *F, double *d, double *lambda2) {
   return guarded(nullptr, "plda_fusion_newton", [&]() -> int { return fusion_newton(record, prior, F, d, lambda2); });
+}
+
+// ---------------------------------------------------------------- speaker clustering (ahc.hip)
+int plda_ahc_plan(plda_handle *h, int64_t N, int32_t out[3]) {
+  return guarded(h, "plda_ahc_plan", [&]() -> int {
+    if (!h) return PLDA_E_INVAL;
+    PLDA_LOCK(h);
+    return ahc_plan(h, N, out);
+  });
+}
+
+int plda_ahc_matrix_dev(plda_handle *h, const float *dscores, const int64_t *block_off, const int64_t *offsets, int64_t R,
+                        int32_t has_threshold, double threshold, const int32_t *min_clusters, int32_t *dlabels,
+                        int32_t *dn_clusters, int32_t *dmerge_a, int32_t *dmerge_b, double *dmerge_cost) {
+  return guarded(h, "plda_ahc_matrix_dev", [&]() -> int {
+    if (!h) return PLDA_E_INVAL;
+    PLDA_LOCK(h);
+    PLDA_TRY(set_device(h));
+    return ahc_matrix_device(h, dscores, block_off, offsets, R, has_threshold, threshold, min_clusters, dlabels, dn_clusters, dmerge_a,
+                             dmerge_b, dmerge_cost);
+  });
+}
+
+extern "C++" {
+namespace {
+// the host forms: outputs staged in device temporaries, copied back after the call's own synchronisation
+template <typename F>
+int ahc_host_outputs(plda_handle *h, int64_t T, int64_t R, int32_t *labels, int32_t *n_clusters, int32_t *merge_a, int32_t *merge_b,
+                     double *merge_cost, F &&run) {
+  Tmp dL, dK, dA, dB, dC;
+  PLDA_HIP(h, dL.alloc((size_t)T * 4));
+  PLDA_HIP(h, dK.alloc((size_t)R * 4));
+  if (merge_a) {
+    PLDA_HIP(h, dA.alloc((size_t)(T - R) * 4));
+    PLDA_HIP(h, dB.alloc((size_t)(T - R) * 4));
+    PLDA_HIP(h, dC.alloc((size_t)(T - R) * 8));
+  }
+  const int rc = run(dL.as<int32_t>(), dK.as<int32_t>(), merge_a ? dA.as<int32_t>() : nullptr, merge_a ? dB.as<int32_t>() : nullptr,
+                     merge_a ? dC.as<double>() : nullptr);
+  if (rc != PLDA_OK) { (void)hipStreamSynchronize(h->stream); return rc; }
+  PLDA_HIP(h, hipMemcpyAsync(labels, dL.p, (size_t)T * 4, hipMemcpyDeviceToHost, h->stream));
+  PLDA_HIP(h, hipMemcpyAsync(n_clusters, dK.p, (size_t)R * 4, hipMemcpyDeviceToHost, h->stream));
+  if (merge_a && T > R) {
+    PLDA_HIP(h, hipMemcpyAsync(merge_a, dA.p, (size_t)(T - R) * 4, hipMemcpyDeviceToHost, h->stream));
+    PLDA_HIP(h, hipMemcpyAsync(merge_b, dB.p, (size_t)(T - R) * 4, hipMemcpyDeviceToHost, h->stream));
+    PLDA_HIP(h, hipMemcpyAsync(merge_cost, dC.p, (size_t)(T - R) * 8, hipMemcpyDeviceToHost, h->stream));
+  }
+  PLDA_HIP(h, hipStreamSynchronize(h->stream));
+  return PLDA_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+int plda_ahc_matrix(plda_handle *h, const float *scores, const int64_t *block_off, const int64_t *offsets, int64_t R,
+                    int32_t has_threshold, double threshold, const int32_t *min_clusters, int32_t *labels, int32_t *n_clusters,
+                    int32_t *merge_a, int32_t *merge_b, double *merge_cost) {
+  return guarded(h, "plda_ahc_matrix", [&]() -> int {
+    if (!h) return PLDA_E_INVAL;
+    PLDA_LOCK(h);
+    if (!scores) return fail(h, PLDA_E_INVAL, "ahc_matrix: scores is NULL");
+    PLDA_TRY(ahc_validate(h, "ahc_matrix", block_off, true, offsets, R, has_threshold, threshold, min_clusters, labels, n_clusters,
+                          merge_a, merge_b, merge_cost));
+    PLDA_TRY(set_device(h));
+    const int64_t T = offsets[R], first = block_off[0], floats = block_off[R] - first;
+    Tmp dS;
+    PLDA_TRY(upload(h, dS, scores + first, (size_t)floats * 4));
+    std::vector<int64_t> rel((size_t)R + 1);
+    for (int64_t r = 0; r <= R; ++r) rel[(size_t)r] = block_off[r] - first;
+    return ahc_host_outputs(h, T, R, labels, n_clusters, merge_a, merge_b, merge_cost,
+                            [&](int32_t *dl, int32_t *dk, int32_t *da, int32_t *db, double *dc) {
+                              return ahc_matrix_device(h, dS.as<float>(), rel.data(), offsets, R, has_threshold, threshold, min_clusters,
+                                                       dl, dk, da, db, dc);
+                            });
+  });
+}
+
+int plda_score_ahc_dev(plda_handle *h, const double *dX, const int64_t *offsets, int64_t R, int32_t has_threshold,
+                       double threshold, const int32_t *min_clusters, int32_t *dlabels, int32_t *dn_clusters,
+                       int32_t *dmerge_a, int32_t *dmerge_b, double *dmerge_cost) {
+  return guarded(h, "plda_score_ahc_dev", [&]() -> int {
+    if (!h) return PLDA_E_INVAL;
+    PLDA_LOCK(h);
+    PLDA_TRY(set_device(h));
+    return score_ahc_device(h, dX, offsets, R, has_threshold, threshold, min_clusters, dlabels, dn_clusters, dmerge_a, dmerge_b,
+                            dmerge_cost);
+  });
+}
+
+int plda_score_ahc(plda_handle *h, const double *X, const int64_t *offsets, int64_t R, int32_t has_threshold, double threshold,
+                   const int32_t *min_clusters, int32_t *labels, int32_t *n_clusters, int32_t *merge_a, int32_t *merge_b,
+                   double *merge_cost) {
+  return guarded(h, "plda_score_ahc", [&]() -> int {
+    if (!h) return PLDA_E_INVAL;
+    PLDA_LOCK(h);
+    if (!h->fitted) return fail(h, PLDA_E_NOT_FITTED, "score_ahc: model not fitted");
+    if (!X) return fail(h, PLDA_E_INVAL, "score_ahc: X is NULL");
+    PLDA_TRY(ahc_validate(h, "score_ahc", nullptr, false, offsets, R, has_threshold, threshold, min_clusters, labels, n_clusters,
+                          merge_a, merge_b, merge_cost));
+    PLDA_TRY(set_device(h));
+    const int64_t T = offsets[R];
+    Tmp dX;
+    PLDA_TRY(upload(h, dX, X, (size_t)T * h->Dout * 8));
+    return ahc_host_outputs(h, T, R, labels, n_clusters, merge_a, merge_b, merge_cost,
+                            [&](int32_t *dl, int32_t *dk, int32_t *da, int32_t *db, double *dc) {
+                              return score_ahc_device(h, dX.as<double>(), offsets, R, has_threshold, threshold, min_clusters, dl, dk,
+                                                      da, db, dc);
+                            });
+  });
 }
 
 }  // extern "C"

@@ -287,6 +287,13 @@ struct plda_handle {
   int64_t ad_rows = 0;
   double ad_tw = 0.0;            // host mirror of the record's total weight
   std::vector<double> ad_pilot;  // host mirror of the pilot (bitwise comparisons of plda_adapt_add_stats)
+
+  // ---- speaker clustering (ahc.hip) ----
+  plda::DevBuf ahc_scratch;      // the N x N fp64 sums of the HBM-class recordings of one launch
+  plda::DevBuf ahc_tab;          // the launch table of a call (one entry per recording)
+  plda::DevBuf ahc_slot;         // every segment's final slot, between the merge and the label kernel
+  plda::DevBuf ahc_stat;         // the call's count of non-finite scores
+  int64_t ahc_scratch_bytes = 0; // PLDA_AHC_SCRATCH_BYTES: the scratch one launch may take and the score slab of the operand form (0: 2 GiB)
 };
 
 namespace plda {
@@ -432,6 +439,19 @@ int adapt_add_stats(plda_handle *h, double tw, int64_t rows, const double *pilot
 int adapt_update(plda_handle *h, double ws, double bs, double mds, double *eig, plda_adapt_info *info);
 int blend_model(plda_handle *h, int D, const double *mean2, const double *transform2, const double *psi2, double alpha,
                 double alpha_mean);
+
+// ---- ahc.hip (speaker clustering: batched average-linkage AHC on score blocks; block_off / offsets / minc are HOST arrays) ----
+int ahc_plan(plda_handle *h, int64_t N, int32_t *out);
+// the argument check of every form (blocks: block_off is checked against the recordings' sizes); pointers are only compared with NULL
+int ahc_validate(plda_handle *h, const char *fn, const int64_t *block_off, bool blocks, const int64_t *offsets, int64_t R, int has_thr,
+                 double thr, const int32_t *minc, const int32_t *labels, const int32_t *n_clusters, const int32_t *merge_a,
+                 const int32_t *merge_b, const double *merge_cost);
+int ahc_matrix_device(plda_handle *h, const float *dscores, const int64_t *block_off, const int64_t *offsets, int64_t R, int has_thr,
+                      double thr, const int32_t *minc, int32_t *dlabels, int32_t *dn_clusters, int32_t *dmerge_a, int32_t *dmerge_b,
+                      double *dmerge_cost);
+int score_ahc_device(plda_handle *h, const double *dX, const int64_t *offsets, int64_t R, int has_thr, double thr,
+                     const int32_t *minc, int32_t *dlabels, int32_t *dn_clusters, int32_t *dmerge_a, int32_t *dmerge_b,
+                     double *dmerge_cost);
 
 // ---- frontend.hip ----
 int htk_frames_device(plda_handle *h, const void *dblob, const int64_t *dfile_off, const int64_t *dframe_off,

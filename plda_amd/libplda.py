@@ -407,6 +407,42 @@ class MPlda(object):
             self._ck(self._lib.plda_transform_rows(self._h, _ptr(X), r, d, _ptr(ne), 0, _ptr(out)))
         return out
 
+    # ----------------------------------------------------------------- speaker clustering (csrc/ahc.hip)
+    def cluster(self, x, offsets, threshold=0.0, num_speakers=None, return_merges=False):
+        """Cluster the segments of R recordings (diarisation; plda_amd/diarize.py): x [T, Din] raw segment vectors, recording
+        r owning rows offsets[r] .. offsets[r+1].  Every row is transformed with num_examples = 1, every recording's segments
+        are scored against each other on the device and merged bottom-up (average linkage) while the best pair's average
+        score is at least `threshold` (None: no threshold) and more than `num_speakers` (an int or one per recording; None: 1)
+        clusters are left.  Returns (labels int32 [T], n_clusters int32 [R][, (merge_a, merge_b, merge_cost)])."""
+        from . import diarize
+        offsets = np.ascontiguousarray(offsets, np.int64)
+        diarize.stop_args(offsets, threshold, num_speakers)     # (threshold=None without num_speakers: ValueError, before any work)
+        X = _features(x, "Segment vectors")
+        if offsets.ndim != 1 or len(offsets) < 2 or X.shape[0] != int(offsets[-1]):
+            raise ValueError("offsets must hold R + 1 >= 2 entries ending at the number of rows of x")
+        return diarize.ahc_vectors(self, self.transform_array(X, 1), offsets, threshold, num_speakers, return_merges)
+
+    def ahc_matrix_dev(self, dscores, block_off, offsets, has_threshold, threshold, min_clusters, dlabels, dn_clusters,
+                       dmerge_a=None, dmerge_b=None, dmerge_cost=None):
+        """Cluster packed HBM-resident fp32 score blocks (raw device addresses); block_off, offsets (int64) and min_clusters
+        (int32 or None) are HOST arrays."""
+        def vp(x):
+            return C.c_void_p(int(x)) if x else None
+        self._ck(self._lib.plda_ahc_matrix_dev(
+            self._h, vp(dscores), _ptr(block_off), _ptr(offsets), len(offsets) - 1, int(has_threshold), float(threshold),
+            _ptr(min_clusters) if min_clusters is not None else None, vp(dlabels), vp(dn_clusters), vp(dmerge_a), vp(dmerge_b),
+            vp(dmerge_cost)))
+
+    def score_ahc_dev(self, dX, offsets, has_threshold, threshold, min_clusters, dlabels, dn_clusters, dmerge_a=None,
+                      dmerge_b=None, dmerge_cost=None):
+        """The same on HBM-resident transformed segment vectors dX [T, Dout]: the blocks are scored and dropped."""
+        def vp(x):
+            return C.c_void_p(int(x)) if x else None
+        self._ck(self._lib.plda_score_ahc_dev(
+            self._h, vp(dX), _ptr(offsets), len(offsets) - 1, int(has_threshold), float(threshold),
+            _ptr(min_clusters) if min_clusters is not None else None, vp(dlabels), vp(dn_clusters), vp(dmerge_a), vp(dmerge_b),
+            vp(dmerge_cost)))
+
     # ----------------------------------------------------------------- norm
     def norm(self, vectors, transformedvecs, numutts=0):
         """MPlda_norm (pldamodule.cpp:196-256): z-norm statistics of every enrol model
