@@ -974,6 +974,86 @@ int plda_score_ahc(plda_handle *h, const double *X, const int64_t *offsets, int6
                    const int32_t *min_clusters, int32_t *labels, int32_t *n_clusters, int32_t *merge_a, int32_t *merge_b,
                    double *merge_cost);
 
+/* ---- VBx resegmentation (K16; csrc/vbx.hip): a batched variational-Bayes HMM over the segment sequence of every recording,
+ * the step every x-vector diarisation recipe runs behind the AHC (Landini et al., "Bayesian HMM clustering of x-vector
+ * sequences (VBx)", 2022).  The emission model is the PLDA model in its diagonalised space (within-class covariance I,
+ * between-class covariance diag(Phi)); the initialisation is the AHC's labels.  The reference has NO counterpart; this is the
+ * project's own extension, pinned by the NumPy model tests/vbx_model.py.  Everything is fp64.
+ *
+ * A RECORDING r is a run of T = offsets[r+1] - offsets[r] consecutive rows, 1 <= T <= PLDA_AHC_MAX.  Row t holds y_t [D], the
+ * segment vector in the model's diagonalised space WITHOUT the length normalisation of TransformIvector (y = transform x +
+ * offset: plda_project_rows), and an initial label l_t in [0, S), S = 1 + max_t l_t over the recording, 1 <= S <=
+ * PLDA_VBX_MAX_SPK.  A label value with no segment is allowed.  Phi [D] is the between-class variance (NULL: the model's psi;
+ * D must then be Dout).
+ *
+ * PARAMETERS.  Fa > 0 (0.3), Fb > 0 (17), loop_prob P in [0, 1) (0.99), init_smoothing sigma (5.0), max_iters >= 1 (40),
+ * epsilon (1e-4).
+ *
+ * CONSTANTS.  rho[t,d] = y[t,d] sqrt(Phi[d]);  G[t] = -1/2 (sum_d y[t,d]^2 + D ln 2 pi).
+ * START.  gamma[t,s] = e^sigma / (e^sigma + S - 1) for s = l_t and 1 / (e^sigma + S - 1) otherwise;  pi[s] = 1 / S.
+ * ONE ITERATION i = 0, 1, ...
+ *    1.  N[s] = sum_t gamma[t,s]
+ *    2.  invL[s,d] = 1 / (1 + (Fa/Fb) N[s] Phi[d])
+ *    3.  alpha[s,d] = (Fa/Fb) invL[s,d] sum_t gamma[t,s] rho[t,d]
+ *    4.  lp[t,s] = Fa (sum_d rho[t,d] alpha[s,d] - 1/2 sum_d (invL[s,d] + alpha[s,d]^2) Phi[d] + G[t])
+ *    5.  m[t] = max_s lp[t,s],  b[t,s] = exp(lp[t,s] - m[t])
+ *    6.  forward:  u_0 = b_0 o pi,  u_t = b_t o (P a_{t-1} + (1 - P) pi),  c_t = sum_s u_t[s],  a_t = u_t / c_t
+ *    7.  backward: beta_{T-1} = 1,  w = b_{t+1} o beta_{t+1},  beta_t[s] = (P w[s] + (1 - P) sum_j pi[j] w[j]) / c_{t+1}
+ *    8.  gamma = a o beta
+ *    9.  L = sum_t ln c_t + sum_t m[t]
+ *   10.  pi'[s] = gamma[0,s] + (1 - P) pi[s] sum_{t>=1} b[t,s] beta[t,s] / c_t,  then pi = pi' / sum pi'
+ *   11.  ELBO_i = L + (Fb/2) sum_{s,d} (ln invL - invL - alpha^2 + 1)
+ *   12.  stop after iteration i >= 1 when ELBO_i - ELBO_{i-1} < epsilon (a comparison with a NaN is false), and after
+ *        max_iters iterations in any case.
+ * Steps 6 - 10 are the scaled form of the usual log-domain forward-backward for the transition matrix P I + (1 - P) 1 pi^T
+ * (sum a_{t-1} = 1).  It is the DEFINITION: it puts no transcendental on the dependent chain, and a speaker whose pi underflows
+ * to 0 simply dies where the log form gives -inf - -inf.  (The device runs 6 and 7 at the same time: its backward variable is
+ * scaled by its own row sum, which gamma = a o beta / sum_s (a o beta) removes again; csrc/vbx.hip.)
+ *
+ * OUTPUTS.  labels int32 [T_total]: argmax_s gamma[t,s] of the last iteration run, ties to the smallest s, renumbered 0 .. k-1
+ * per recording by ascending smallest member (the AHC's rule).  n_clusters int32 [R]: k.  Nullable: gamma fp64, packed,
+ * recording r at gamma_off[r], row-major T_r x S_r, columns in the INITIAL numbering (gamma and gamma_off together or neither);
+ * pi fp64 packed at pi_off[r], S_r entries (likewise); elbo fp64 [R, max_iters], entries at and beyond iters[r] quiet NaN;
+ * iters int32 [R].  Nothing else is written.
+ *
+ * ERRORS, all PLDA_E_INVAL: offsets that do not ascend from 0, an empty recording or one above PLDA_AHC_MAX, a parameter outside
+ * its range, D outside 1 ... 4096 -- before any device work; a non-finite y, a label outside [0, 64), Phi[d] < 0 or non-finite
+ * -- found on the device, with their count in plda_last_error; gamma_off[r+1] - gamma_off[r] < T_r S_r or pi_off[r+1] -
+ * pi_off[r] < S_r -- known once S is.  None of them writes an output.  A model that is not fitted: PLDA_E_NOT_FITTED.
+ *
+ * DETERMINISM.  Every sum (N, sum_t gamma rho, the d-dots, c_t, sum ln c_t, pi') is taken in an order fixed by (T, S, D) alone
+ * and there are no floating-point atomics: a recording's outputs are bit-identical from run to run, alone or inside any batch,
+ * and under any grouping into launches.
+ *
+ * METHOD.  One workgroup per recording, persistent over the iterations (no host synchronisation between them), one lane per
+ * speaker on the chain.  Two dispatch classes: the LDS class keeps the state (b, a, beta, c, m, G, alpha, invL, sqrt Phi, Phi:
+ * 3 T S + 3 T + 2 S (D | 1) + 2 D doubles) in the LDS of one compute unit, the HBM class in handle scratch, grouped into
+ * launches under 1 GiB (never fewer than one recording; PLDA_VBX_SCRATCH_BYTES in the environment at plda_create sets another
+ * budget: tests); the scratch belongs to the handle and is freed by plda_destroy.
+ *
+ *   plda_vbx_plan            out[0] = the class of a recording of (T, S, D) (0 LDS, 1 HBM), out[1] = the scratch bytes one such
+ *                            recording takes (0 in the LDS class), out[2] = the LDS class's limit in doubles of state.
+ *   plda_vbx_dev             Y, Phi, labels_in and the outputs in HBM; offsets [R + 1], gamma_off [R + 1], pi_off [R + 1] are
+ *                            HOST arrays (the AHC's and the fusion's convention).  Synchronises the handle's stream twice: to
+ *                            read the reject counters and S, and at its end.
+ *   plda_vbx                 the same with everything in host memory.
+ *   plda_project_rows[_dev]  out [R, Dout] = X [R, Din] transform^T + offset: TransformIvector without its normalisation
+ *                            factor, through the library's fp64 GEMM.
+ * OUT OF SCOPE, each on purpose: length normalisation and the LDA fit before the model (the caller's business); more than 64
+ * initial speakers; several workgroups on one recording; RTTM output and DER; overlap handling. ---- */
+#define PLDA_VBX_MAX_SPK 64
+int plda_vbx_plan(plda_handle *h, int64_t T, int64_t S, int64_t D, int32_t out[3]);
+int plda_vbx_dev(plda_handle *h, const double *dY, int64_t D, const double *dPhi, const int32_t *dlabels_in, const int64_t *offsets,
+                 int64_t R, double Fa, double Fb, double loop_prob, double init_smoothing, int64_t max_iters, double epsilon,
+                 int32_t *dlabels, int32_t *dn_clusters, double *dgamma, const int64_t *gamma_off, double *dpi, const int64_t *pi_off,
+                 double *delbo, int32_t *diters);
+int plda_vbx(plda_handle *h, const double *Y, int64_t D, const double *Phi, const int32_t *labels_in, const int64_t *offsets, int64_t R,
+             double Fa, double Fb, double loop_prob, double init_smoothing, int64_t max_iters, double epsilon, int32_t *labels,
+             int32_t *n_clusters, double *gamma, const int64_t *gamma_off, double *pi, const int64_t *pi_off, double *elbo,
+             int32_t *iters);
+int plda_project_rows_dev(plda_handle *h, const double *dX, int64_t R, int32_t Din, double *dout);
+int plda_project_rows(plda_handle *h, const double *X, int64_t R, int32_t Din, double *out);
+
 /* ---- LDA: replaces the reference's second model, the pure-Python
  * class LDA of python/liblda/lda.py (used by scoring/scoreLDA.py:175,224,241), on the same
  * handle.  All fp64.  solver: 0 = 'svd' (lda.py:171-209), 1 = 'eigen' (:134-169),

@@ -89,6 +89,14 @@ class PLDA(object):
         more than `num_speakers` clusters are left.  Returns (labels, n_clusters[, merges]); plda_amd/diarize.py."""
         return self._instance.cluster(x, offsets, threshold, num_speakers, return_merges)
 
+    def resegment(self, x, offsets, labels, **vbx):
+        """VBx resegmentation of the segments of R recordings from initial labels (cluster()'s); plda_amd/diarize.py."""
+        return self._instance.resegment(x, offsets, labels, **vbx)
+
+    def diarize(self, x, offsets, threshold=0.0, num_speakers=None, **vbx):
+        """cluster, then resegment.  Returns (labels, n_clusters[, info])."""
+        return self._instance.diarize(x, offsets, threshold, num_speakers, **vbx)
+
     def transform_array(self, xbar, num_examples=1):
         return self._instance.transform_array(xbar, num_examples)
 

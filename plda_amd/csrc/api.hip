@@ -331,6 +331,7 @@ int plda_create(int device, plda_handle **out) {
     if (const char *v = std::getenv("PLDA_SNORM_SLAB_ROWS")) h->sn_slab_rows = std::atoll(v);
     if (const char *v = std::getenv("PLDA_ADAPT_SLAB_ROWS")) h->ad_slab_rows = std::atoll(v);
     if (const char *v = std::getenv("PLDA_AHC_SCRATCH_BYTES")) h->ahc_scratch_bytes = std::atoll(v);
+    if (const char *v = std::getenv("PLDA_VBX_SCRATCH_BYTES")) h->vbx_scratch_bytes = std::atoll(v);
     if (const char *v = std::getenv("PLDA_HIP_TRACE")) h->trace_on = h->trace_print = std::atoi(v) != 0;
     if (const char *v = std::getenv("PLDA_HOST_VARIANT")) h->host_variant = std::atoi(v);
     if (const char *v = std::getenv("PLDA_SWEEP_VARIANT")) h->sweep_variant = std::atoi(v);
@@ -2195,6 +2196,110 @@ int plda_score_ahc(plda_handle *h, const double *X, const int64_t *offsets, int6
                               return score_ahc_device(h, dX.as<double>(), offsets, R, has_threshold, threshold, min_clusters, dl, dk,
                                                       da, db, dc);
                             });
+  });
+}
+
+// ---------------------------------------------------------------- VBx resegmentation (vbx.hip)
+int plda_vbx_plan(plda_handle *h, int64_t T, int64_t S, int64_t D, int32_t out[3]) {
+  return guarded(h, "plda_vbx_plan", [&]() -> int {
+    if (!h) return PLDA_E_INVAL;
+    PLDA_LOCK(h);
+    return vbx_plan(h, T, S, D, out);
+  });
+}
+
+int plda_vbx_dev(plda_handle *h, const double *dY, int64_t D, const double *dPhi, const int32_t *dlabels_in, const int64_t *offsets,
+                 int64_t R, double Fa, double Fb, double loop_prob, double init_smoothing, int64_t max_iters, double epsilon,
+                 int32_t *dlabels, int32_t *dn_clusters, double *dgamma, const int64_t *gamma_off, double *dpi, const int64_t *pi_off,
+                 double *delbo, int32_t *diters) {
+  return guarded(h, "plda_vbx_dev", [&]() -> int {
+    if (!h) return PLDA_E_INVAL;
+    PLDA_LOCK(h);
+    PLDA_TRY(set_device(h));
+    return vbx_device(h, dY, D, dPhi, dlabels_in, offsets, R, Fa, Fb, loop_prob, init_smoothing, max_iters, epsilon, dlabels,
+                      dn_clusters, dgamma, gamma_off, dpi, pi_off, delbo, diters);
+  });
+}
+
+int plda_vbx(plda_handle *h, const double *Y, int64_t D, const double *Phi, const int32_t *labels_in, const int64_t *offsets, int64_t R,
+             double Fa, double Fb, double loop_prob, double init_smoothing, int64_t max_iters, double epsilon, int32_t *labels,
+             int32_t *n_clusters, double *gamma, const int64_t *gamma_off, double *pi, const int64_t *pi_off, double *elbo,
+             int32_t *iters) {
+  return guarded(h, "plda_vbx", [&]() -> int {
+    if (!h) return PLDA_E_INVAL;
+    PLDA_LOCK(h);
+    if (!h->fitted) return fail(h, PLDA_E_NOT_FITTED, "vbx: model not fitted");
+    if (!Y) return fail(h, PLDA_E_INVAL, "vbx: Y is NULL");
+    if (!labels_in) return fail(h, PLDA_E_INVAL, "vbx: labels_in is NULL");
+    PLDA_TRY(vbx_validate(h, "vbx", D, offsets, R, Fa, Fb, loop_prob, max_iters, labels, n_clusters, gamma, gamma_off, pi, pi_off));
+    PLDA_TRY(set_device(h));
+    const int64_t T = offsets[R];
+    // the intervals of gamma and pi keep their layout, relative to their first entry, in device temporaries
+    const int64_t g0 = gamma ? gamma_off[0] : 0, gn = gamma ? gamma_off[R] - g0 : 0;
+    const int64_t p0 = pi ? pi_off[0] : 0, pn = pi ? pi_off[R] - p0 : 0;
+    if (gn < 0 || pn < 0) return fail(h, PLDA_E_INVAL, "vbx: gamma_off / pi_off must ascend");
+    std::vector<int64_t> grel, prel;
+    if (gamma) { grel.resize((size_t)R + 1); for (int64_t r = 0; r <= R; ++r) grel[(size_t)r] = gamma_off[r] - g0; }
+    if (pi) { prel.resize((size_t)R + 1); for (int64_t r = 0; r <= R; ++r) prel[(size_t)r] = pi_off[r] - p0; }
+    Tmp dY, dPhi, dLin, dL, dK, dG, dP, dE, dI;
+    PLDA_TRY(upload(h, dY, Y, (size_t)T * D * 8));
+    if (Phi) PLDA_TRY(upload(h, dPhi, Phi, (size_t)D * 8));
+    PLDA_TRY(upload(h, dLin, labels_in, (size_t)T * 4));
+    PLDA_HIP(h, dL.alloc((size_t)T * 4));
+    PLDA_HIP(h, dK.alloc((size_t)R * 4));
+    if (gamma) PLDA_HIP(h, dG.alloc((size_t)gn * 8));
+    if (pi) PLDA_HIP(h, dP.alloc((size_t)pn * 8));
+    if (elbo) PLDA_HIP(h, dE.alloc((size_t)R * max_iters * 8));
+    if (iters) PLDA_HIP(h, dI.alloc((size_t)R * 4));
+    const int rc = vbx_device(h, dY.as<double>(), D, Phi ? dPhi.as<double>() : nullptr, dLin.as<int32_t>(), offsets, R, Fa, Fb, loop_prob,
+                              init_smoothing, max_iters, epsilon, dL.as<int32_t>(), dK.as<int32_t>(), gamma ? dG.as<double>() : nullptr,
+                              gamma ? grel.data() : nullptr, pi ? dP.as<double>() : nullptr, pi ? prel.data() : nullptr,
+                              elbo ? dE.as<double>() : nullptr, iters ? dI.as<int32_t>() : nullptr);
+    if (rc != PLDA_OK) { (void)hipStreamSynchronize(h->stream); return rc; }
+    // gamma and pi: only T_r x S_r (S_r) entries of every interval are the call's to write
+    std::vector<int32_t> hl((size_t)T);
+    std::vector<double> hg((size_t)gn), hp((size_t)pn);
+    PLDA_HIP(h, hipMemcpyAsync(labels, dL.p, (size_t)T * 4, hipMemcpyDeviceToHost, h->stream));
+    PLDA_HIP(h, hipMemcpyAsync(n_clusters, dK.p, (size_t)R * 4, hipMemcpyDeviceToHost, h->stream));
+    if (gn) PLDA_HIP(h, hipMemcpyAsync(hg.data(), dG.p, (size_t)gn * 8, hipMemcpyDeviceToHost, h->stream));
+    if (pn) PLDA_HIP(h, hipMemcpyAsync(hp.data(), dP.p, (size_t)pn * 8, hipMemcpyDeviceToHost, h->stream));
+    if (elbo) PLDA_HIP(h, hipMemcpyAsync(elbo, dE.p, (size_t)R * max_iters * 8, hipMemcpyDeviceToHost, h->stream));
+    if (iters) PLDA_HIP(h, hipMemcpyAsync(iters, dI.p, (size_t)R * 4, hipMemcpyDeviceToHost, h->stream));
+    PLDA_HIP(h, hipStreamSynchronize(h->stream));
+    for (int64_t r = 0; r < R && (gamma || pi); ++r) {
+      int S = 0;
+      for (int64_t t = offsets[r]; t < offsets[r + 1]; ++t) S = std::max(S, (int)labels_in[t] + 1);
+      const int64_t n = offsets[r + 1] - offsets[r];
+      if (gamma) std::copy(hg.begin() + grel[(size_t)r], hg.begin() + grel[(size_t)r] + n * S, gamma + gamma_off[r]);
+      if (pi) std::copy(hp.begin() + prel[(size_t)r], hp.begin() + prel[(size_t)r] + S, pi + pi_off[r]);
+    }
+    return PLDA_OK;
+  });
+}
+
+int plda_project_rows_dev(plda_handle *h, const double *dX, int64_t R, int32_t Din, double *dout) {
+  return guarded(h, "plda_project_rows_dev", [&]() -> int {
+    if (!h) return PLDA_E_INVAL;
+    PLDA_LOCK(h);
+    PLDA_TRY(set_device(h));
+    return project_rows_device(h, dX, R, Din, dout);
+  });
+}
+
+int plda_project_rows(plda_handle *h, const double *X, int64_t R, int32_t Din, double *out) {
+  return guarded(h, "plda_project_rows", [&]() -> int {
+    if (!h) return PLDA_E_INVAL;
+    PLDA_LOCK(h);
+    if (!h->fitted) return fail(h, PLDA_E_NOT_FITTED, "project_rows: model not fitted");
+    if (Din != h->Din) return fail(h, PLDA_E_INVAL, "project_rows: feature dim %d != model dim %d", (int)Din, h->Din);
+    if (R <= 0) return R < 0 ? fail(h, PLDA_E_INVAL, "project_rows: R = %lld", (long long)R) : PLDA_OK;
+    if (!X || !out) return fail(h, PLDA_E_INVAL, "project_rows: bad argument");
+    PLDA_TRY(set_device(h));
+    Tmp dX, dO;
+    PLDA_TRY(upload(h, dX, X, (size_t)R * Din * 8));
+    PLDA_HIP(h, dO.alloc((size_t)R * h->Dout * 8));
+    PLDA_TRY(project_rows_device(h, dX.as<double>(), R, Din, dO.as<double>()));
+    return download(h, out, dO.p, (size_t)R * h->Dout * 8);
   });
 }
 

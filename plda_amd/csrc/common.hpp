@@ -294,6 +294,12 @@ struct plda_handle {
   plda::DevBuf ahc_slot;         // every segment's final slot, between the merge and the label kernel
   plda::DevBuf ahc_stat;         // the call's count of non-finite scores
   int64_t ahc_scratch_bytes = 0; // PLDA_AHC_SCRATCH_BYTES: the scratch one launch may take and the score slab of the operand form (0: 2 GiB)
+
+  // ---- VBx resegmentation (vbx.hip) ----
+  plda::DevBuf vbx_scratch;      // the per-recording state of the HBM-class recordings of one launch
+  plda::DevBuf vbx_tab;          // the launch table of a call (one entry per recording)
+  plda::DevBuf vbx_stat;         // the call's three reject counters, then S of every recording
+  int64_t vbx_scratch_bytes = 0; // PLDA_VBX_SCRATCH_BYTES: the scratch one launch may take (0: 1 GiB)
 };
 
 namespace plda {
@@ -452,6 +458,18 @@ int ahc_matrix_device(plda_handle *h, const float *dscores, const int64_t *block
 int score_ahc_device(plda_handle *h, const double *dX, const int64_t *offsets, int64_t R, int has_thr, double thr,
                      const int32_t *minc, int32_t *dlabels, int32_t *dn_clusters, int32_t *dmerge_a, int32_t *dmerge_b,
                      double *dmerge_cost);
+
+// ---- vbx.hip (VBx resegmentation: a batched Bayesian HMM on PLDA vectors; offsets / gamma_off / pi_off are HOST arrays) ----
+int vbx_plan(plda_handle *h, int64_t T, int64_t S, int64_t D, int32_t *out);
+// the argument check of both forms; pointers are only compared with NULL
+int vbx_validate(plda_handle *h, const char *fn, int64_t D, const int64_t *offsets, int64_t R, double Fa, double Fb, double loop_prob,
+                 int64_t max_iters, const void *labels, const void *n_clusters, const void *gamma, const int64_t *gamma_off,
+                 const void *pi, const int64_t *pi_off);
+int vbx_device(plda_handle *h, const double *dY, int64_t D, const double *dPhi, const int32_t *dlabels_in, const int64_t *offsets,
+               int64_t R, double Fa, double Fb, double loop_prob, double init_smoothing, int64_t max_iters, double epsilon,
+               int32_t *dlabels, int32_t *dn_clusters, double *dgamma, const int64_t *gamma_off, double *dpi, const int64_t *pi_off,
+               double *delbo, int32_t *diters);
+int project_rows_device(plda_handle *h, const double *dX, int64_t R, int Din, double *dout);
 
 // ---- frontend.hip ----
 int htk_frames_device(plda_handle *h, const void *dblob, const int64_t *dfile_off, const int64_t *dframe_off,

@@ -1,15 +1,22 @@
-"""plda_amd/diarize.py -- speaker clustering of the segments of recordings (csrc/ahc.hip; the contract is in
-include/plda_hip.h, "speaker clustering"): batched average-linkage agglomerative clustering on PLDA score blocks, the
-diarisation use of a PLDA back-end (Kaldi: ivector-plda-scoring-dense + agglomerative-cluster).
+"""plda_amd/diarize.py -- speaker diarisation of the segments of recordings: batched average-linkage agglomerative clustering
+on PLDA score blocks (csrc/ahc.hip; include/plda_hip.h, "speaker clustering"; Kaldi: ivector-plda-scoring-dense +
+agglomerative-cluster), then VBx resegmentation, a variational-Bayes HMM over the segment sequence with the PLDA model as its
+emission model, initialised from the clustering (csrc/vbx.hip; include/plda_hip.h, "VBx resegmentation"; Landini et al. 2022).
 
     ahc(engine, blocks, ...)          clusters R square fp32 score blocks on the device, one workgroup per recording
     plan(engine, n)                   the dispatch class a recording of n segments takes
     cut(merges, offsets, ...)         pure NumPy: labels at another threshold / speaker count from ONE full merge record
     MPlda.cluster(x, offsets, ...)    raw segment vectors in, labels out (the blocks are scored on the device and dropped)
+    vbx(engine, y, offsets, labels)   resegments R recordings of projected vectors from initial labels, one workgroup each
+    vbx_plan(engine, t, s, d)         the dispatch class a recording of t segments, s initial speakers, dimension d takes
+    MPlda.resegment(x, offsets, labels, ...)   raw segment vectors in: plda_project_rows, then vbx
+    MPlda.diarize(x, offsets, ...)    cluster, then resegment
 
 A recording is merged bottom-up while the best pair's average score is at least `threshold` (None: no threshold) and more than
 `num_speakers` clusters are left (None: 1).  Out of scope, on purpose: Kaldi's per-recording mean subtraction and PCA before
-scoring, its two-pass clustering of very long recordings, RTTM output, DER.
+scoring, its two-pass clustering of very long recordings, RTTM output, DER; for VBx: length normalisation and the LDA fit before
+the model (the caller's business; plda_truncate plays the LDA dimension's role), more than 64 initial speakers, several
+workgroups on one recording, overlap handling.
 """
 import ctypes as C
 
@@ -18,6 +25,7 @@ import numpy as np
 from . import _native as N
 
 AHC_MAX = 4096          # PLDA_AHC_MAX
+VBX_MAX_SPK = 64        # PLDA_VBX_MAX_SPK
 
 
 def _p(a):
@@ -135,3 +143,77 @@ def cut(merges, offsets, threshold=None, num_speakers=None):
         labels[offsets[q]:offsets[q + 1]] = np.searchsorted(live, slot)
         ncl[q] = k
     return labels, ncl
+
+
+# ------------------------------------------------------------------------------------------- VBx resegmentation
+def vbx_plan(engine, t, s, d):
+    """{"cls": 0 (state in LDS) or 1 (state in HBM scratch), "scratch_bytes": per recording, "lds_doubles": the LDS class's
+    limit in doubles of state} of a recording of t segments, s initial speakers and dimension d."""
+    out = (C.c_int32 * 3)()
+    N.check(engine._h, engine._lib.plda_vbx_plan(engine._h, int(t), int(s), int(d), out))
+    return {"cls": int(out[0]), "scratch_bytes": int(out[1]), "lds_doubles": int(out[2])}
+
+
+def vbx_args(y, offsets, labels, phi, Fa, Fb, loop_prob, max_iters):
+    """The argument check of vbx / MPlda.resegment, before any device work -> (y, offsets, labels, phi, S of every recording).
+    ValueError on anything the C ABI would answer with PLDA_E_INVAL and that the host can see."""
+    y = np.ascontiguousarray(y, np.float64)
+    offsets = np.ascontiguousarray(offsets, np.int64)
+    labels = np.ascontiguousarray(labels, np.int32)
+    if offsets.ndim != 1 or len(offsets) < 2:
+        raise ValueError("offsets must hold R + 1 >= 2 entries")
+    if offsets[0] != 0:
+        raise ValueError("offsets must start at 0")
+    sizes = np.diff(offsets)
+    if (sizes < 1).any() or (sizes > AHC_MAX).any():
+        raise ValueError("every recording must hold 1 ... %d segments (offsets must ascend)" % AHC_MAX)
+    if y.ndim != 2 or y.shape[0] != int(offsets[-1]) or y.shape[1] < 1:
+        raise ValueError("y must be [offsets[-1], D], got %r" % (y.shape,))
+    if labels.shape != (y.shape[0],):
+        raise ValueError("labels must hold one entry per row of y, got %r" % (labels.shape,))
+    if (labels < 0).any() or (labels >= VBX_MAX_SPK).any():
+        raise ValueError("labels must lie in [0, %d)" % VBX_MAX_SPK)
+    if not np.isfinite(y).all():
+        raise ValueError("y holds non-finite values")
+    if phi is not None:
+        phi = np.ascontiguousarray(phi, np.float64)
+        if phi.shape != (y.shape[1],):
+            raise ValueError("phi must hold D = %d entries, got %r" % (y.shape[1], phi.shape))
+        if not (np.isfinite(phi).all() and (phi >= 0).all()):
+            raise ValueError("phi must be finite and >= 0")
+    if not (Fa > 0 and np.isfinite(Fa)):
+        raise ValueError("Fa must be > 0")
+    if not (Fb > 0 and np.isfinite(Fb)):
+        raise ValueError("Fb must be > 0")
+    if not 0 <= loop_prob < 1:
+        raise ValueError("loop_prob must lie in [0, 1)")
+    if int(max_iters) != max_iters or max_iters < 1:
+        raise ValueError("max_iters must be an integer >= 1")
+    spk = np.maximum.reduceat(labels, offsets[:-1]).astype(np.int64) + 1
+    return y, offsets, labels, phi, spk
+
+
+def vbx(engine, y, offsets, labels, phi=None, Fa=0.3, Fb=17.0, loop_prob=0.99, init_smoothing=5.0, max_iters=40, epsilon=1e-4,
+        return_posteriors=False):
+    """VBx resegmentation of R recordings: y [T, D] segment vectors in the model's diagonalised space WITHOUT length
+    normalisation (MPlda.project_rows), recording r owning rows offsets[r] .. offsets[r+1], `labels` the initial labels (the
+    AHC's), phi [D] the between-class variance (None: the model's psi).  Returns (labels int32 [T], n_clusters int32 [R][, info]),
+    labels 0 .. k-1 per recording by ascending smallest member; info = {"gamma": a list of [T_r, S_r] arrays (columns in the
+    initial numbering), "pi": a list of [S_r] arrays, "elbo": [R, max_iters] (NaN from iters[r] on), "iters": int32 [R]}."""
+    y, offsets, labels, phi, spk = vbx_args(y, offsets, labels, phi, Fa, Fb, loop_prob, max_iters)
+    r, t = len(offsets) - 1, int(offsets[-1])
+    out_l, out_k = np.empty(t, np.int32), np.empty(r, np.int32)
+    gamma = goff = pi = poff = elbo = iters = None
+    if return_posteriors:
+        goff, poff = offsets_of(np.diff(offsets) * spk), offsets_of(spk)
+        gamma, pi = np.empty(int(goff[-1]), np.float64), np.empty(int(poff[-1]), np.float64)
+        elbo, iters = np.empty((r, int(max_iters)), np.float64), np.empty(r, np.int32)
+    N.check(engine._h, engine._lib.plda_vbx(engine._h, _p(y), y.shape[1], _p(phi), _p(labels), _p(offsets), r, float(Fa), float(Fb),
+                                            float(loop_prob), float(init_smoothing), int(max_iters), float(epsilon), _p(out_l), _p(out_k),
+                                            _p(gamma), _p(goff), _p(pi), _p(poff), _p(elbo), _p(iters)))
+    if not return_posteriors:
+        return out_l, out_k
+    sizes = np.diff(offsets)
+    info = {"gamma": [gamma[goff[q]:goff[q + 1]].reshape(int(sizes[q]), int(spk[q])) for q in range(r)],
+            "pi": [pi[poff[q]:poff[q + 1]] for q in range(r)], "elbo": elbo, "iters": iters}
+    return out_l, out_k, info

@@ -422,6 +422,51 @@ class MPlda(object):
             raise ValueError("offsets must hold R + 1 >= 2 entries ending at the number of rows of x")
         return diarize.ahc_vectors(self, self.transform_array(X, 1), offsets, threshold, num_speakers, return_merges)
 
+    # ----------------------------------------------------------------- VBx resegmentation (csrc/vbx.hip)
+    def project_rows(self, x):
+        """transform . x + offset of every row of x [R, Din] -> [R, Dout]: TransformIvector without its normalisation factor,
+        the space VBx works in."""
+        X = _features(x, "Segment vectors")
+        dout, _ = self.dims()
+        out = np.zeros((X.shape[0], dout), np.float64)
+        self._ck(self._lib.plda_project_rows(self._h, _ptr(X), X.shape[0], X.shape[1], _ptr(out)))
+        return out
+
+    def project_rows_dev(self, dX, R, Din, dout):
+        """The same on HBM-resident rows (raw device addresses)."""
+        self._ck(self._lib.plda_project_rows_dev(self._h, C.c_void_p(int(dX)), int(R), int(Din), C.c_void_p(int(dout))))
+
+    def resegment(self, x, offsets, labels, Fa=0.3, Fb=17.0, loop_prob=0.99, init_smoothing=5.0, max_iters=40, epsilon=1e-4,
+                  return_posteriors=False):
+        """VBx resegmentation (plda_amd/diarize.py: vbx): x [T, Din] raw segment vectors, recording r owning rows offsets[r] ..
+        offsets[r+1], `labels` the initial labels (cluster()'s).  The rows are projected into the model's diagonalised space
+        (project_rows), the between-class variance is the model's psi.  Returns (labels, n_clusters[, info])."""
+        from . import diarize
+        X = _features(x, "Segment vectors")
+        offsets = np.ascontiguousarray(offsets, np.int64)
+        if offsets.ndim != 1 or len(offsets) < 2 or X.shape[0] != int(offsets[-1]):
+            raise ValueError("offsets must hold R + 1 >= 2 entries ending at the number of rows of x")
+        diarize.vbx_args(np.zeros((X.shape[0], 1)), offsets, labels, None, Fa, Fb, loop_prob, max_iters)   # (before any device work)
+        return diarize.vbx(self, self.project_rows(X), offsets, labels, None, Fa, Fb, loop_prob, init_smoothing, max_iters, epsilon,
+                           return_posteriors)
+
+    def diarize(self, x, offsets, threshold=0.0, num_speakers=None, **vbx):
+        """cluster(x, offsets, threshold, num_speakers), then resegment(x, offsets, its labels, **vbx)."""
+        labels, _ = self.cluster(x, offsets, threshold, num_speakers)
+        return self.resegment(x, offsets, labels, **vbx)
+
+    def vbx_dev(self, dY, D, dPhi, dlabels_in, offsets, dlabels, dn_clusters, Fa=0.3, Fb=17.0, loop_prob=0.99, init_smoothing=5.0,
+                max_iters=40, epsilon=1e-4, dgamma=None, gamma_off=None, dpi=None, pi_off=None, delbo=None, diters=None):
+        """VBx on HBM-resident projected rows and labels (raw device addresses); offsets, gamma_off and pi_off (int64) are HOST
+        arrays."""
+        def vp(x):
+            return C.c_void_p(int(x)) if x else None
+        self._ck(self._lib.plda_vbx_dev(
+            self._h, vp(dY), int(D), vp(dPhi), vp(dlabels_in), _ptr(offsets), len(offsets) - 1, float(Fa), float(Fb), float(loop_prob),
+            float(init_smoothing), int(max_iters), float(epsilon), vp(dlabels), vp(dn_clusters), vp(dgamma),
+            _ptr(gamma_off) if gamma_off is not None else None, vp(dpi), _ptr(pi_off) if pi_off is not None else None, vp(delbo),
+            vp(diters)))
+
     def ahc_matrix_dev(self, dscores, block_off, offsets, has_threshold, threshold, min_clusters, dlabels, dn_clusters,
                        dmerge_a=None, dmerge_b=None, dmerge_cost=None):
         """Cluster packed HBM-resident fp32 score blocks (raw device addresses); block_off, offsets (int64) and min_clusters
