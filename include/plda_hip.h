@@ -958,7 +958,8 @@ int plda_blend_model(plda_handle *h, int32_t D, const double *mean2, const doubl
  *                         (each block at a 256-byte boundary), clustered, dropped.  A prepared test side is dropped, as in
  *                         plda_cohort_stats_dev.
  * OUT OF SCOPE, each on purpose: Kaldi's per-recording mean subtraction and PCA before scoring; its two-pass clustering of very
- * long recordings; RTTM output; DER; several workgroups on one recording. ---- */
+ * long recordings; several workgroups on one recording.  (DER is the section "diarisation error rate" below; RTTM files are
+ * read and written by plda_amd/rttm.py, on the host.) ---- */
 #define PLDA_AHC_MAX 4096
 int plda_ahc_plan(plda_handle *h, int64_t N, int32_t out[3]);
 int plda_ahc_matrix_dev(plda_handle *h, const float *dscores, const int64_t *block_off, const int64_t *offsets, int64_t R,
@@ -1040,7 +1041,8 @@ int plda_score_ahc(plda_handle *h, const double *X, const int64_t *offsets, int6
  *   plda_project_rows[_dev]  out [R, Dout] = X [R, Din] transform^T + offset: TransformIvector without its normalisation
  *                            factor, through the library's fp64 GEMM.
  * OUT OF SCOPE, each on purpose: length normalisation and the LDA fit before the model (the caller's business); more than 64
- * initial speakers; several workgroups on one recording; RTTM output and DER; overlap handling. ---- */
+ * initial speakers; several workgroups on one recording; overlap handling.  (DER: the section "diarisation error rate" below;
+ * RTTM: plda_amd/rttm.py.) ---- */
 #define PLDA_VBX_MAX_SPK 64
 int plda_vbx_plan(plda_handle *h, int64_t T, int64_t S, int64_t D, int32_t out[3]);
 int plda_vbx_dev(plda_handle *h, const double *dY, int64_t D, const double *dPhi, const int32_t *dlabels_in, const int64_t *offsets,
@@ -1053,6 +1055,82 @@ int plda_vbx(plda_handle *h, const double *Y, int64_t D, const double *Phi, cons
              int32_t *iters);
 int plda_project_rows_dev(plda_handle *h, const double *dX, int64_t R, int32_t Din, double *dout);
 int plda_project_rows(plda_handle *h, const double *X, int64_t R, int32_t Din, double *out);
+
+/* ---- diarisation error rate (K17; csrc/der.hip): segment-level miss, false alarm and speaker confusion of R recordings under
+ * the OPTIMAL one-to-one mapping of reference to hypothesis speakers, and the sweep of a full AHC merge record over Q
+ * thresholds -- the metric of the diarisation path, on the device like EER, minDCF and Cllr.  The reference has NO counterpart;
+ * tests/der_model.py is the host model.  Everything is an integer: nothing on the device is floating-point but the
+ * comparison of a merge cost with a threshold.
+ *
+ * A RECORDING r owns segments offsets[r] .. offsets[r+1], 1 <= N <= PLDA_AHC_MAX.  Per segment t:
+ *   ref[t]  int32: -1 = reference non-speech, otherwise 0 <= ref < PLDA_DER_MAX_REF;
+ *   hyp[t]  int32: -1 = hypothesis non-speech, otherwise 0 <= hyp < PLDA_AHC_MAX;
+ *   dur[t]  int32 >= 0, in ticks of the caller's choosing; dur is nullable: NULL = 1 everywhere.
+ * A label value with no segment is allowed: the labels of either side are compacted per recording before anything else
+ * (Sr distinct reference labels, Sh distinct hypothesis labels).
+ *
+ * COUNTS, all int64.  With C[i][j] = the sum of dur over the segments with ref = i and hyp = j:
+ *   speech    = sum of dur over ref >= 0
+ *   miss      = sum of dur over ref >= 0 and hyp < 0
+ *   fa        = sum of dur over ref < 0 and hyp >= 0
+ *   correct   = the maximum of sum_i C[i][m(i)] over all one-to-one partial maps m of reference to hypothesis speakers
+ *   confusion = (sum of dur over ref >= 0 and hyp >= 0) - correct
+ * The output is counts int64 [R, 4] = {speech, miss, fa, confusion}.  DER = (miss + fa + confusion) / speech is the CALLER's
+ * division.  The optimum VALUE is unique, so the counts are fully determined by the input: they do not depend on the grid, on
+ * the batch, on the grouping into launches or on the run.
+ *
+ * MAP (nullable), int32 [R, PLDA_DER_MAX_REF]: entry [r, i] = the hypothesis label mapped to reference label i, both in the
+ * caller's own label values; -1 for a reference label that is absent, unmapped, or mapped to a speaker it shares no tick with
+ * (a pair with C = 0 is reported as -1).  The map is one-to-one and attains `correct`.  Among optima of equal weight it is not
+ * canonical, but it is a function of the recording's own matrix: the same alone or in any batch.
+ *
+ * SWEEP.  merge_a, merge_b, merge_cost are a FULL merge record in the layout of plda_ahc_matrix (one taken with has_threshold
+ * = 0 and min_clusters = 1).  For every threshold q and recording r the prefix of the record is replayed under exactly the
+ * stop rule of the AHC: stop when k <= max(1, min_clusters[r]) or !(cost <= -(double)thresholds[q]).  The slots are the
+ * hypothesis labels (no hypothesis non-speech), scored as above: counts int64 [Q, R, 4], n_clusters int32 [Q, R].  A record
+ * that ends (entry -1), or holds an entry that is not 0 <= a < b < N, before the stop rule fires is not a full record:
+ * PLDA_E_INVAL.  So counts[q], n_clusters[q] are what plda_ahc_matrix at thresholds[q] followed by plda_der return, from one
+ * device run of the clustering.
+ *
+ * ERRORS, all PLDA_E_INVAL: offsets that do not ascend from 0, an empty recording or one above PLDA_AHC_MAX, Q < 1 (or above
+ * 65535), a NaN threshold, min_clusters[r] < 1 -- before any device work; a label below -1 or at or above its limit, a negative
+ * dur -- found on the device, with their count in plda_last_error; a record that is not full.  None of them writes an output.
+ *
+ * METHOD.  One pass validates the call and counts Sr and Sh (the sweep: the length of every prefix) per recording; the host
+ * reads that with one synchronisation of the handle's stream and sizes the launches.  Then one workgroup per (recording,
+ * threshold): the labels present as bit sets, the compact Sr x W matrix (W = max(Sr, Sh): zero columns pad a hypothesis
+ * with fewer speakers) filled by integer atomics, and a shortest-augmenting-path assignment (Hungarian / Jonker-Volgenant)
+ * with int64 potentials, rows = reference speakers: at most Sr (Sr + 1) / 2 steps, each an update of the column slack and a
+ * workgroup (value, column) minimum.  Two dispatch classes: the matrix in LDS while matrix and column state (32 bytes a
+ * column) fit the 160 KiB of one compute unit, otherwise in handle scratch (8 Sr W bytes, at most 2 MiB, per recording in
+ * flight), grouped into launches under 256 MiB (never fewer than one recording; PLDA_DER_SCRATCH_BYTES in the environment at
+ * plda_create sets another budget: tests).  The column state is in LDS in both.  The sweep's replay takes 4 N more bytes of
+ * LDS, so near the boundary a sweep entry may take the scratch class where plda_der_plan names the LDS class; no output
+ * shows the class.  Every threshold is solved on its own.  The scratch belongs to the handle and is freed by plda_destroy.
+ *
+ *   plda_der_plan        out[0] = the class of a recording of Sr (0 ... 64) reference and Sh (0 ... PLDA_AHC_MAX) hypothesis
+ *                        speakers (0 LDS, 1 scratch), out[1] = the scratch bytes one such recording takes (0 in the LDS
+ *                        class), out[2] = the largest W = max(Sr, Sh) the LDS class takes at this Sr.
+ *   plda_der_dev         ref, hyp, dur (nullable) and the outputs in HBM; offsets [R + 1] is a HOST array (the convention of
+ *                        plda_ahc_matrix_dev).  Synchronises the handle's stream twice: to read the counters, and at its end.
+ *   plda_der             the same with everything in host memory.
+ *   plda_der_sweep_dev   the merge record, ref, dur (nullable) and the outputs in HBM; offsets [R + 1], thresholds [Q] and
+ *                        min_clusters [R] (nullable: 1 everywhere) are HOST arrays.
+ *   plda_der_sweep       the same with everything in host memory.
+ * OUT OF SCOPE, each on purpose: overlapped speech (a segment has one reference and one hypothesis label); a forgiveness
+ * collar; the Jaccard error rate (JER); a time-based restatement of md-eval (the unit is the caller's segment). ---- */
+#define PLDA_DER_MAX_REF 64
+int plda_der_plan(plda_handle *h, int64_t Sr, int64_t Sh, int32_t out[3]);
+int plda_der_dev(plda_handle *h, const int32_t *dref, const int32_t *dhyp, const int32_t *ddur, const int64_t *offsets, int64_t R,
+                 int64_t *dcounts, int32_t *dmap);
+int plda_der(plda_handle *h, const int32_t *ref, const int32_t *hyp, const int32_t *dur, const int64_t *offsets, int64_t R,
+             int64_t *counts, int32_t *map);
+int plda_der_sweep_dev(plda_handle *h, const int32_t *dmerge_a, const int32_t *dmerge_b, const double *dmerge_cost,
+                       const int64_t *offsets, int64_t R, const int32_t *dref, const int32_t *ddur, const double *thresholds, int64_t Q,
+                       const int32_t *min_clusters, int64_t *dcounts, int32_t *dn_clusters);
+int plda_der_sweep(plda_handle *h, const int32_t *merge_a, const int32_t *merge_b, const double *merge_cost, const int64_t *offsets,
+                   int64_t R, const int32_t *ref, const int32_t *dur, const double *thresholds, int64_t Q, const int32_t *min_clusters,
+                   int64_t *counts, int32_t *n_clusters);
 
 /* ---- LDA: replaces the reference's second model, the pure-Python
  * class LDA of python/liblda/lda.py (used by scoring/scoreLDA.py:175,224,241), on the same

@@ -97,6 +97,16 @@ class PLDA(object):
         """cluster, then resegment.  Returns (labels, n_clusters[, info])."""
         return self._instance.diarize(x, offsets, threshold, num_speakers, **vbx)
 
+    def der(self, ref, hyp, offsets, dur=None, return_map=False):
+        """Diarisation error rate of R recordings from per-segment reference and hypothesis labels (-1 = non-speech), under
+        the optimal speaker mapping; plda_amd/der.py.  Returns a DerResult (counts, der, total[, map])."""
+        return self._instance.der(ref, hyp, offsets, dur, return_map)
+
+    def tune_threshold(self, x, offsets, ref, thresholds, dur=None):
+        """The clustering threshold of the lowest pooled DER on a development set: one clustering, one sweep of its merge
+        record.  Returns (threshold, SweepResult); plda_amd/der.py."""
+        return self._instance.tune_threshold(x, offsets, ref, thresholds, dur)
+
     def transform_array(self, xbar, num_examples=1):
         return self._instance.transform_array(xbar, num_examples)
 

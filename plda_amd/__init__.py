@@ -11,6 +11,8 @@ Layout (only what the hot path needs):
   adaptation.py the result of MPlda.adapt: unsupervised PLDA domain adaptation and model interpolation (csrc/adapt.hip)
   identify.py rank-N identification rates and the CMC curve from the ids of MPlda.top_n (csrc/topn.hip); pure NumPy
   diarize.py  speaker clustering: batched average-linkage AHC on score blocks (csrc/ahc.hip), cut() in pure NumPy; VBx resegmentation (csrc/vbx.hip)
+  der.py      diarisation error rate under the optimal speaker mapping, and the sweep of one merge record over thresholds (csrc/der.hip)
+  rttm.py     RTTM files and per-segment reference labels from reference turns; pure Python / NumPy
 """
 from .libplda import MPlda  # noqa: F401
 from . import calibration  # noqa: F401
@@ -18,8 +20,10 @@ from . import fusion  # noqa: F401
 from . import identify  # noqa: F401
 from . import adaptation  # noqa: F401
 from . import diarize  # noqa: F401
+from . import der  # noqa: F401
+from . import rttm  # noqa: F401
 from .calibration import Calibration  # noqa: F401
 from .fusion import Fusion  # noqa: F401
 from .adaptation import Adaptation  # noqa: F401
 
-__all__ = ["MPlda", "Calibration", "Fusion", "Adaptation", "calibration", "fusion", "identify", "adaptation", "diarize"]
+__all__ = ["MPlda", "Calibration", "Fusion", "Adaptation", "calibration", "fusion", "identify", "adaptation", "diarize", "der", "rttm"]

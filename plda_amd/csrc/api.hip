@@ -332,6 +332,7 @@ int plda_create(int device, plda_handle **out) {
     if (const char *v = std::getenv("PLDA_ADAPT_SLAB_ROWS")) h->ad_slab_rows = std::atoll(v);
     if (const char *v = std::getenv("PLDA_AHC_SCRATCH_BYTES")) h->ahc_scratch_bytes = std::atoll(v);
     if (const char *v = std::getenv("PLDA_VBX_SCRATCH_BYTES")) h->vbx_scratch_bytes = std::atoll(v);
+    if (const char *v = std::getenv("PLDA_DER_SCRATCH_BYTES")) h->der_scratch_bytes = std::atoll(v);
     if (const char *v = std::getenv("PLDA_HIP_TRACE")) h->trace_on = h->trace_print = std::atoi(v) != 0;
     if (const char *v = std::getenv("PLDA_HOST_VARIANT")) h->host_variant = std::atoi(v);
     if (const char *v = std::getenv("PLDA_SWEEP_VARIANT")) h->sweep_variant = std::atoi(v);
@@ -2196,6 +2197,95 @@ int plda_score_ahc(plda_handle *h, const double *X, const int64_t *offsets, int6
                               return score_ahc_device(h, dX.as<double>(), offsets, R, has_threshold, threshold, min_clusters, dl, dk,
                                                       da, db, dc);
                             });
+  });
+}
+
+// ---------------------------------------------------------------- diarisation error rate (der.hip)
+int plda_der_plan(plda_handle *h, int64_t Sr, int64_t Sh, int32_t out[3]) {
+  return guarded(h, "plda_der_plan", [&]() -> int {
+    if (!h) return PLDA_E_INVAL;
+    PLDA_LOCK(h);
+    return der_plan(h, Sr, Sh, out);
+  });
+}
+
+int plda_der_dev(plda_handle *h, const int32_t *dref, const int32_t *dhyp, const int32_t *ddur, const int64_t *offsets, int64_t R,
+                 int64_t *dcounts, int32_t *dmap) {
+  return guarded(h, "plda_der_dev", [&]() -> int {
+    if (!h) return PLDA_E_INVAL;
+    PLDA_LOCK(h);
+    PLDA_TRY(set_device(h));
+    return der_device(h, dref, dhyp, ddur, offsets, R, dcounts, dmap);
+  });
+}
+
+int plda_der(plda_handle *h, const int32_t *ref, const int32_t *hyp, const int32_t *dur, const int64_t *offsets, int64_t R,
+             int64_t *counts, int32_t *map) {
+  return guarded(h, "plda_der", [&]() -> int {
+    if (!h) return PLDA_E_INVAL;
+    PLDA_LOCK(h);
+    if (!ref) return fail(h, PLDA_E_INVAL, "der: ref is NULL");
+    if (!hyp) return fail(h, PLDA_E_INVAL, "der: hyp is NULL");
+    if (!counts) return fail(h, PLDA_E_INVAL, "der: counts is NULL");
+    PLDA_TRY(der_validate(h, "der", offsets, R));
+    PLDA_TRY(set_device(h));
+    const int64_t T = offsets[R];
+    Tmp dRef, dHyp, dDur, dC, dM;
+    PLDA_TRY(upload(h, dRef, ref, (size_t)T * 4));
+    PLDA_TRY(upload(h, dHyp, hyp, (size_t)T * 4));
+    if (dur) PLDA_TRY(upload(h, dDur, dur, (size_t)T * 4));
+    PLDA_HIP(h, dC.alloc((size_t)R * 32));
+    if (map) PLDA_HIP(h, dM.alloc((size_t)R * PLDA_DER_MAX_REF * 4));
+    const int rc = der_device(h, dRef.as<int32_t>(), dHyp.as<int32_t>(), dur ? dDur.as<int32_t>() : nullptr, offsets, R, dC.as<int64_t>(),
+                              map ? dM.as<int32_t>() : nullptr);
+    if (rc != PLDA_OK) { (void)hipStreamSynchronize(h->stream); return rc; }
+    PLDA_HIP(h, hipMemcpyAsync(counts, dC.p, (size_t)R * 32, hipMemcpyDeviceToHost, h->stream));
+    if (map) PLDA_HIP(h, hipMemcpyAsync(map, dM.p, (size_t)R * PLDA_DER_MAX_REF * 4, hipMemcpyDeviceToHost, h->stream));
+    PLDA_HIP(h, hipStreamSynchronize(h->stream));
+    return PLDA_OK;
+  });
+}
+
+int plda_der_sweep_dev(plda_handle *h, const int32_t *dmerge_a, const int32_t *dmerge_b, const double *dmerge_cost,
+                       const int64_t *offsets, int64_t R, const int32_t *dref, const int32_t *ddur, const double *thresholds, int64_t Q,
+                       const int32_t *min_clusters, int64_t *dcounts, int32_t *dn_clusters) {
+  return guarded(h, "plda_der_sweep_dev", [&]() -> int {
+    if (!h) return PLDA_E_INVAL;
+    PLDA_LOCK(h);
+    PLDA_TRY(set_device(h));
+    return der_sweep_device(h, dmerge_a, dmerge_b, dmerge_cost, offsets, R, dref, ddur, thresholds, Q, min_clusters, dcounts,
+                            dn_clusters);
+  });
+}
+
+int plda_der_sweep(plda_handle *h, const int32_t *merge_a, const int32_t *merge_b, const double *merge_cost, const int64_t *offsets,
+                   int64_t R, const int32_t *ref, const int32_t *dur, const double *thresholds, int64_t Q, const int32_t *min_clusters,
+                   int64_t *counts, int32_t *n_clusters) {
+  return guarded(h, "plda_der_sweep", [&]() -> int {
+    if (!h) return PLDA_E_INVAL;
+    PLDA_LOCK(h);
+    if (!ref) return fail(h, PLDA_E_INVAL, "der_sweep: ref is NULL");
+    if (!counts) return fail(h, PLDA_E_INVAL, "der_sweep: counts is NULL");
+    if (!n_clusters) return fail(h, PLDA_E_INVAL, "der_sweep: n_clusters is NULL");
+    PLDA_TRY(der_sweep_validate(h, "der_sweep", offsets, R, thresholds, Q, min_clusters));
+    const int64_t T = offsets[R];
+    if (T > R && !(merge_a && merge_b && merge_cost)) return fail(h, PLDA_E_INVAL, "der_sweep: merge_a, merge_b or merge_cost is NULL");
+    PLDA_TRY(set_device(h));
+    Tmp dA, dB, dCo, dRef, dDur, dC, dK;
+    PLDA_TRY(upload(h, dA, merge_a, (size_t)(T - R) * 4));
+    PLDA_TRY(upload(h, dB, merge_b, (size_t)(T - R) * 4));
+    PLDA_TRY(upload(h, dCo, merge_cost, (size_t)(T - R) * 8));
+    PLDA_TRY(upload(h, dRef, ref, (size_t)T * 4));
+    if (dur) PLDA_TRY(upload(h, dDur, dur, (size_t)T * 4));
+    PLDA_HIP(h, dC.alloc((size_t)Q * R * 32));
+    PLDA_HIP(h, dK.alloc((size_t)Q * R * 4));
+    const int rc = der_sweep_device(h, dA.as<int32_t>(), dB.as<int32_t>(), dCo.as<double>(), offsets, R, dRef.as<int32_t>(),
+                                    dur ? dDur.as<int32_t>() : nullptr, thresholds, Q, min_clusters, dC.as<int64_t>(), dK.as<int32_t>());
+    if (rc != PLDA_OK) { (void)hipStreamSynchronize(h->stream); return rc; }
+    PLDA_HIP(h, hipMemcpyAsync(counts, dC.p, (size_t)Q * R * 32, hipMemcpyDeviceToHost, h->stream));
+    PLDA_HIP(h, hipMemcpyAsync(n_clusters, dK.p, (size_t)Q * R * 4, hipMemcpyDeviceToHost, h->stream));
+    PLDA_HIP(h, hipStreamSynchronize(h->stream));
+    return PLDA_OK;
   });
 }
 

@@ -300,6 +300,12 @@ struct plda_handle {
   plda::DevBuf vbx_tab;          // the launch table of a call (one entry per recording)
   plda::DevBuf vbx_stat;         // the call's three reject counters, then S of every recording
   int64_t vbx_scratch_bytes = 0; // PLDA_VBX_SCRATCH_BYTES: the scratch one launch may take (0: 1 GiB)
+
+  // ---- diarisation error rate (der.hip) ----
+  plda::DevBuf der_scratch;      // the Sr x W int64 confusion matrices of the scratch-class recordings of one launch
+  plda::DevBuf der_tab;          // the launch table of a call (one entry per recording and threshold)
+  plda::DevBuf der_stat;         // the call's two reject counters, its offsets and thresholds, then Sr, Sh / the prefix lengths
+  int64_t der_scratch_bytes = 0; // PLDA_DER_SCRATCH_BYTES: the scratch one launch may take (0: 256 MiB)
 };
 
 namespace plda {
@@ -458,6 +464,18 @@ int ahc_matrix_device(plda_handle *h, const float *dscores, const int64_t *block
 int score_ahc_device(plda_handle *h, const double *dX, const int64_t *offsets, int64_t R, int has_thr, double thr,
                      const int32_t *minc, int32_t *dlabels, int32_t *dn_clusters, int32_t *dmerge_a, int32_t *dmerge_b,
                      double *dmerge_cost);
+
+// ---- der.hip (diarisation error rate: optimal speaker mapping, threshold sweep; offsets / thresholds / minc are HOST arrays) ----
+int der_plan(plda_handle *h, int64_t Sr, int64_t Sh, int32_t *out);
+// the host-side argument checks of the two device forms (the host forms run them before they allocate or upload)
+int der_validate(plda_handle *h, const char *fn, const int64_t *offsets, int64_t R);
+int der_sweep_validate(plda_handle *h, const char *fn, const int64_t *offsets, int64_t R, const double *thresholds, int64_t Q,
+                       const int32_t *minc);
+int der_device(plda_handle *h, const int32_t *dref, const int32_t *dhyp, const int32_t *ddur, const int64_t *offsets, int64_t R,
+               int64_t *dcounts, int32_t *dmap);
+int der_sweep_device(plda_handle *h, const int32_t *dma, const int32_t *dmb, const double *dmc, const int64_t *offsets, int64_t R,
+                     const int32_t *dref, const int32_t *ddur, const double *thresholds, int64_t Q, const int32_t *minc,
+                     int64_t *dcounts, int32_t *dn_clusters);
 
 // ---- vbx.hip (VBx resegmentation: a batched Bayesian HMM on PLDA vectors; offsets / gamma_off / pi_off are HOST arrays) ----
 int vbx_plan(plda_handle *h, int64_t T, int64_t S, int64_t D, int32_t *out);

@@ -1,0 +1,557 @@
+// plda_amd/csrc/der.hip -- diarisation error rate: per-recording miss / false alarm / speaker confusion under the OPTIMAL
+// one-to-one mapping of reference to hypothesis speakers, and the sweep of a full AHC merge record over Q thresholds
+// (the contract is in include/plda_hip.h, the host model in tests/der_model.py).
+//
+// A recording is a small dependent problem: a confusion matrix of at most 64 x 4096 integers and a shortest-augmenting-path
+// assignment on it (Hungarian / Jonker-Volgenant with int64 potentials), at most Sr (Sr + 1) / 2 steps, each a scan of the
+// hypothesis speakers.  There are thousands of independent recordings and a sweep multiplies them by Q: one workgroup per
+// (recording, threshold).  Everything is an integer; the counts are determined by the input alone.
+//
+//   der_count_kernel    one workgroup per recording: the entries that break the contract (a label below -1 or above its
+//                       limit, a negative duration) added to one counter; Sr and Sh, the distinct labels of either side
+//   der_prefix_kernel   sweep, grid (recordings, thresholds): the number of merges the stop rule of the AHC lets through
+//                       (Sh = N - that); a record that ends first, or an entry that is no merge, is counted as a bad record
+//   der_solve_kernel    <HBM = false> the Sr x W int64 confusion matrix in LDS (W = max(Sr, Sh): zero columns pad a
+//                       hypothesis with fewer speakers than the reference);  <HBM = true> the matrix in handle scratch.
+//                       <SWEEP> the hypothesis labels are the slots of the replayed merge prefix.
+//                       Both keep the column state (potential, slack, predecessor, owner, flag, label) in LDS.
+//
+// One workgroup of der_solve_kernel: (1) the labels present, as bit sets (64 bits of reference, 4096 of hypothesis), give
+// the compact numbering by prefix population counts; (2) the matrix is zeroed and filled with integer atomics, the four
+// counters are summed in registers; (3) rows are inserted one by one: each step scans the free columns for the reduced
+// cost against the row just reached, keeps the per-column minimum and its predecessor, and takes the workgroup minimum by
+// (value, column) -- ties to the smaller column, so the path taken, and with it the map, depends on the matrix alone;
+// (4) the potentials move by that minimum, the path is flipped when a free column is reached.
+#include "common.hpp"
+
+#include <algorithm>
+#include <cmath>
+#include <vector>
+
+namespace plda {
+
+namespace {
+
+constexpr int DER_MAX_REF = PLDA_DER_MAX_REF;
+constexpr int DER_MAX_HYP = PLDA_AHC_MAX;
+constexpr int DER_LDS_BYTES = 160 * 1024;     // one workgroup may hold all of a CU's LDS
+constexpr int DER_T = 256;
+constexpr int DER_W = DER_T / 64;
+constexpr int DER_COL_BYTES = 8 + 8 + 4 * 4;   // v, minv | way, own, used, clab
+// red_v[4] cnt[4][4] refmask u[65] hbits[64] | hbase[64] reflab[64] red_i[4]
+constexpr int DER_FIXED_BYTES = 8 * (DER_W + 4 * DER_W + 1 + (DER_MAX_REF + 1) + 64) + 4 * (64 + DER_MAX_REF + DER_W);
+constexpr long long DER_INF = 1ll << 62;
+
+// one (recording, threshold) of a launch (host-built, uploaded once per call)
+struct DerRec {
+  long long off;     // first segment
+  long long scr;     // HBM class: first int64 of the Sr x W matrix in scratch
+  long long out;     // row of counts (and of n_clusters / map)
+  int n, sr, sh, w;  // segments; distinct reference / hypothesis labels; max(sr, sh)
+  int m, r;          // sweep: merges to replay; the recording (its merge entries start at off - r)
+};
+
+constexpr long long der_lds_bytes(long long sr, long long w, long long n_replay, bool hbm) {
+  return (hbm ? 0 : 8 * sr * w) + (long long)DER_COL_BYTES * (w + 1) + 4 * n_replay + DER_FIXED_BYTES;
+}
+static_assert(der_lds_bytes(DER_MAX_REF, DER_MAX_HYP, DER_MAX_HYP, true) <= DER_LDS_BYTES,
+              "the scratch class's column state and the replay must fit one CU's LDS");
+
+__device__ __forceinline__ long long der_wave_sum(long long v) {
+#pragma unroll
+  for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+
+// lexicographic minimum of (v, j) over the wave, j < 0 = nothing; every lane ends with the result
+__device__ __forceinline__ void der_wave_min(long long &v, int &j) {
+#pragma unroll
+  for (int o = 32; o; o >>= 1) {
+    const long long ov = __shfl_xor(v, o);
+    const int oj = __shfl_xor(j, o);
+    if (oj >= 0 && (j < 0 || ov < v || (ov == v && oj < j))) { v = ov; j = oj; }
+  }
+}
+
+__device__ __forceinline__ unsigned long long der_below(int bit) { return bit ? ~0ull >> (64 - bit) : 0ull; }
+
+// one workgroup per recording: stat[0] += the invalid entries; sr[r], sh[r] = the distinct labels (hyp nullable: the sweep)
+__global__ __launch_bounds__(DER_T) void der_count_kernel(const int *__restrict__ ref, const int *__restrict__ hyp,
+                                                          const int *__restrict__ dur, const long long *__restrict__ offsets,
+                                                          unsigned long long *stat, int *__restrict__ sr, int *__restrict__ sh) {
+  __shared__ unsigned long long bits[65];
+  __shared__ int tot[2];
+  const int tid = threadIdx.x, r = blockIdx.x;
+  const long long off = offsets[r];
+  const int n = (int)(offsets[r + 1] - off);
+  if (tid < 65) bits[tid] = 0;
+  if (tid < 2) tot[tid] = 0;
+  __syncthreads();
+  unsigned bad = 0;
+  for (int t = tid; t < n; t += DER_T) {
+    const int a = ref[off + t], b = hyp ? hyp[off + t] : -1, d = dur ? dur[off + t] : 1;
+    bool ok = d >= 0;
+    if (a < -1 || a >= DER_MAX_REF) ok = false;
+    else if (a >= 0) atomicOr(&bits[64], 1ull << a);
+    if (b < -1 || b >= DER_MAX_HYP) ok = false;
+    else if (b >= 0) atomicOr(&bits[b >> 6], 1ull << (b & 63));
+    if (!ok) ++bad;
+  }
+  if (bad) atomicAdd(stat, (unsigned long long)bad);      // rare: one integer atomic per lane that met one
+  __syncthreads();
+  if (tid < 64) { const int c = __popcll(bits[tid]); if (c) atomicAdd(&tot[1], c); }
+  if (tid == 64) tot[0] = __popcll(bits[64]);
+  __syncthreads();
+  if (tid == 0) { sr[r] = tot[0]; if (sh) sh[r] = tot[1]; }
+}
+
+// grid (recordings, thresholds): m[q * R + r] = the merges of recording r that the stop rule lets through at threshold q
+// (diarize.cut's loop: k > max(1, minc), then a missing entry is an error, then !(cost <= -threshold) stops); stat[1] += 1 for
+// a record that ends before the rule fires or whose prefix holds an entry that is no merge (not 0 <= a < b < N)
+__global__ __launch_bounds__(DER_T) void der_prefix_kernel(const int *__restrict__ ma, const int *__restrict__ mb,
+                                                           const double *__restrict__ mc, const long long *__restrict__ offsets,
+                                                           const double *__restrict__ thr, const int *__restrict__ minc, int R,
+                                                           unsigned long long *stat, int *__restrict__ mout) {
+  __shared__ int first[2];     // the first entry that fails the threshold; the first that is no merge
+  const int tid = threadIdx.x, r = blockIdx.x, q = blockIdx.y;
+  const long long off = offsets[r], base = off - r;
+  const int n = (int)(offsets[r + 1] - off);
+  const int stop_k = minc && minc[r] > 1 ? minc[r] : 1;
+  const int limit = n > stop_k ? n - stop_k : 0;
+  const double neg_thr = -thr[q];
+  if (tid < 2) first[tid] = limit;
+  __syncthreads();
+  int f_thr = limit, f_bad = limit;
+  for (int e = tid; e < limit && e < f_thr && e < f_bad; e += DER_T) {
+    const int a = ma[base + e], b = mb[base + e];
+    if (!(a >= 0 && a < b && b < n)) f_bad = e;
+    else if (!(mc[base + e] <= neg_thr)) f_thr = e;
+  }
+  if (f_thr < limit) atomicMin(&first[0], f_thr);
+  if (f_bad < limit) atomicMin(&first[1], f_bad);
+  __syncthreads();
+  if (tid == 0) {
+    const bool bad = first[1] < first[0];
+    if (bad) atomicAdd(stat + 1, 1ull);
+    mout[(long long)q * R + r] = bad ? 0 : first[0];
+  }
+}
+
+// the confusion matrix of a recording: in LDS, or in HBM scratch (filled with atomics that complete in L2: read back with
+// device-scope loads, which do not take a line the CU's vector cache may hold from before)
+template <bool HBM> struct DerMat;
+template <> struct DerMat<false> {
+  long long *c; int w;
+  __device__ __forceinline__ long long get(int i, int j) const { return c[i * w + j]; }
+};
+template <> struct DerMat<true> {
+  long long *c; int w;
+  __device__ __forceinline__ long long get(int i, int j) const {
+    return __hip_atomic_load(c + (long long)i * w + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+};
+
+template <bool HBM, bool SWEEP>
+__global__ __launch_bounds__(DER_T) void der_solve_kernel(const int *__restrict__ ref, const int *__restrict__ hyp,
+                                                          const int *__restrict__ dur, const int *__restrict__ ma,
+                                                          const int *__restrict__ mb, const DerRec *__restrict__ tab,
+                                                          long long *scratch, long long *__restrict__ counts,
+                                                          int *__restrict__ n_clusters, int *__restrict__ map) {
+  extern __shared__ long long der_smem[];
+  const DerRec rc = tab[blockIdx.x];
+  const int n = rc.n, w = rc.w, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+
+  // LDS: [matrix (LDS class)] | v[w+1] minv[w+1] u[65] red_v[4] cnt[16] refmask hbits[64] | way[w+1] own[w+1] used[w+1] clab[w+1]
+  //      hbase[64] reflab[64] red_i[4] | parent[n] (sweep)
+  long long *p8 = der_smem;
+  DerMat<HBM> mat;
+  mat.w = w;
+  if constexpr (HBM) mat.c = scratch + rc.scr;
+  else { mat.c = p8; p8 += (long long)rc.sr * w; }
+  long long *v = p8; p8 += w + 1;
+  long long *minv = p8; p8 += w + 1;
+  long long *u = p8; p8 += DER_MAX_REF + 1;
+  long long *red_v = p8; p8 += DER_W;
+  long long *cnt = p8; p8 += 4 * DER_W;
+  unsigned long long *refmask = reinterpret_cast<unsigned long long *>(p8); p8 += 1;
+  unsigned long long *hbits = reinterpret_cast<unsigned long long *>(p8); p8 += 64;
+  int *p4 = reinterpret_cast<int *>(p8);
+  int *way = p4; p4 += w + 1;
+  int *own = p4; p4 += w + 1;      // the row (1-based) that holds column j, 0 = free
+  int *used = p4; p4 += w + 1;
+  int *clab = p4; p4 += w + 1;     // the caller's label of compact column j (0-based)
+  int *hbase = p4; p4 += 64;
+  int *reflab = p4; p4 += DER_MAX_REF;
+  int *red_i = p4; p4 += DER_W;
+  int *parent = p4;
+
+  const int *__restrict__ rf = ref + rc.off;
+  const int *__restrict__ dr = dur ? dur + rc.off : nullptr;
+
+  // (1a) sweep: the slots of the replayed prefix.  parent[b] = a < b for every merge; pointer jumping to the roots -- a read
+  // that races with a write sees an ancestor either way, and every round at least doubles the distance covered
+  if constexpr (SWEEP) {
+    const long long mbase = rc.off - rc.r;
+    for (int x = tid; x < n; x += DER_T) parent[x] = x;
+    __syncthreads();
+    for (int e = tid; e < rc.m; e += DER_T) parent[mb[mbase + e]] = ma[mbase + e];
+    __syncthreads();
+    for (int round = 0; round < 12; ++round) {
+      for (int x = tid; x < n; x += DER_T) {
+        const int p = parent[x], g = parent[p];
+        if (g != p) parent[x] = g;
+      }
+      __syncthreads();
+    }
+  }
+  auto hyp_of = [&](int t) -> int {
+    if constexpr (SWEEP) return parent[t];
+    else return hyp[rc.off + t];
+  };
+
+  // (1b) the labels present
+  if (tid < 64) hbits[tid] = 0;
+  if (tid == 64) *refmask = 0;
+  __syncthreads();
+  {
+    unsigned long long rm = 0;
+    for (int t = tid; t < n; t += DER_T) {
+      const int a = rf[t], b = hyp_of(t);
+      if (a >= 0) rm |= 1ull << (a & 63);
+      if (b >= 0) atomicOr(&hbits[(b >> 6) & 63], 1ull << (b & 63));
+    }
+    if (rm) atomicOr(refmask, rm);
+  }
+  __syncthreads();
+  if (tid == 0) {
+    int s = 0;
+    for (int k = 0; k < 64; ++k) { hbase[k] = s; s += __popcll(hbits[k]); }
+    int i = 0;
+    for (unsigned long long mk = *refmask; mk; mk &= mk - 1) reflab[i++] = __ffsll((long long)mk) - 1;
+  }
+  __syncthreads();
+  const unsigned long long rmask = *refmask;
+  const int sr = __popcll(rmask), sh = hbase[63] + __popcll(hbits[63]);
+  // (the table was sized from der_count_kernel's reading of the same arrays; input that changed under the call must not
+  // carry an index out of the layout)
+  if (sr != rc.sr || sh != rc.sh) return;
+  if (tid < 64) {
+    int j = hbase[tid];
+    for (unsigned long long mk = hbits[tid]; mk; mk &= mk - 1) clab[j++] = tid * 64 + __ffsll((long long)mk) - 1;
+  }
+  // (2) the matrix and the column state
+  for (long long e = tid; e < (long long)sr * w; e += DER_T) mat.c[e] = 0;
+  for (int j = tid; j <= w; j += DER_T) { v[j] = 0; own[j] = 0; }
+  if (tid <= DER_MAX_REF) u[tid] = 0;
+  __syncthreads();
+  long long c_speech = 0, c_miss = 0, c_fa = 0, c_both = 0;
+  for (int t = tid; t < n; t += DER_T) {
+    const int a = rf[t], b = hyp_of(t);
+    const long long d = dr ? dr[t] : 1;
+    if (a >= 0) {
+      c_speech += d;
+      if (b < 0) c_miss += d;
+      else {
+        c_both += d;
+        const int i = __popcll(rmask & der_below(a)), k = b >> 6;
+        const int j = hbase[k] + __popcll(hbits[k] & der_below(b & 63));
+        if (d) atomicAdd(reinterpret_cast<unsigned long long *>(mat.c) + (long long)i * w + j, (unsigned long long)d);
+      }
+    } else if (b >= 0) c_fa += d;
+  }
+  c_speech = der_wave_sum(c_speech); c_miss = der_wave_sum(c_miss); c_fa = der_wave_sum(c_fa); c_both = der_wave_sum(c_both);
+  if (lane == 0) { cnt[wave * 4 + 0] = c_speech; cnt[wave * 4 + 1] = c_miss; cnt[wave * 4 + 2] = c_fa; cnt[wave * 4 + 3] = c_both; }
+  __syncthreads();
+
+  // (3, 4) the assignment: minimise sum of -C over the rows; thread tid owns the columns j = tid (mod DER_T), column 0 is the
+  // virtual column the new row hangs from
+  for (int i = 1; i <= sr; ++i) {
+    for (int j = tid; j <= w; j += DER_T) { minv[j] = DER_INF; used[j] = 0; }
+    if (tid == 0) own[0] = i;
+    __syncthreads();
+    int j0 = 0;
+    while (true) {
+      if ((j0 & (DER_T - 1)) == tid) used[j0] = 1;
+      const int i0 = own[j0];
+      const long long ui0 = u[i0];
+      long long best = 0;
+      int bj = -1;
+      for (int j = tid ? tid : DER_T; j <= w; j += DER_T) {
+        if (used[j]) continue;
+        const long long cur = (j <= sh ? -mat.get(i0 - 1, j - 1) : 0) - ui0 - v[j];
+        long long mj = minv[j];
+        if (cur < mj) { mj = cur; minv[j] = cur; way[j] = j0; }
+        if (bj < 0 || mj < best) { best = mj; bj = j; }      // j ascends within a thread: a tie keeps the smaller column
+      }
+      der_wave_min(best, bj);
+      if (lane == 0) { red_v[wave] = best; red_i[wave] = bj; }
+      __syncthreads();
+      best = red_v[0]; bj = red_i[0];
+#pragma unroll
+      for (int k = 1; k < DER_W; ++k) {
+        const long long ov = red_v[k];
+        const int oj = red_i[k];
+        if (oj >= 0 && (bj < 0 || ov < best || (ov == best && oj < bj))) { best = ov; bj = oj; }
+      }
+      if (bj < 0) break;                           // (cannot happen: w >= sr leaves a free column; keeps every index in range)
+      const bool reached = own[bj] == 0;           // (read before the barrier below: behind it thread 0 flips the path)
+      for (int j = tid; j <= w; j += DER_T) {
+        if (used[j]) { u[own[j]] += best; v[j] -= best; }     // (the owners of used columns are distinct rows)
+        else minv[j] -= best;
+      }
+      __syncthreads();
+      j0 = bj;
+      if (reached) break;
+    }
+    if (tid == 0)
+      while (j0) { const int j1 = way[j0]; own[j0] = own[j1]; j0 = j1; }
+    __syncthreads();
+  }
+
+  // the weight of the optimum, the counts, the map
+  long long correct = 0;
+  for (int j = tid ? tid : DER_T; j <= sh; j += DER_T)
+    if (own[j]) correct += mat.get(own[j] - 1, j - 1);
+  correct = der_wave_sum(correct);
+  if (lane == 0) red_v[wave] = correct;
+  if (map)
+    for (int k = tid; k < DER_MAX_REF; k += DER_T) map[rc.out * DER_MAX_REF + k] = -1;
+  __syncthreads();
+  if (tid == 0) {
+    long long s[4] = {0, 0, 0, 0}, cor = 0;
+    for (int k = 0; k < DER_W; ++k) {
+      cor += red_v[k];
+      for (int c = 0; c < 4; ++c) s[c] += cnt[k * 4 + c];
+    }
+    counts[rc.out * 4 + 0] = s[0]; counts[rc.out * 4 + 1] = s[1]; counts[rc.out * 4 + 2] = s[2]; counts[rc.out * 4 + 3] = s[3] - cor;
+    if (n_clusters) n_clusters[rc.out] = sh;
+  }
+  if (map)
+    for (int j = tid ? tid : DER_T; j <= sh; j += DER_T)
+      if (own[j] && mat.get(own[j] - 1, j - 1) > 0) map[rc.out * DER_MAX_REF + reflab[own[j] - 1]] = clab[j - 1];
+}
+
+template <bool HBM, bool SWEEP> int der_solve_attr(plda_handle *h) {
+  static DeviceOnce attr;
+  if (attr.needed(h->device)) {
+    PLDA_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&der_solve_kernel<HBM, SWEEP>),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, DER_LDS_BYTES));
+    attr.done(h->device);
+  }
+  return PLDA_OK;
+}
+
+// the scratch of one launch of scratch-class recordings (PLDA_DER_SCRATCH_BYTES at plda_create for the tests), never less
+// than one recording
+int64_t der_budget(const plda_handle *h) { return h->der_scratch_bytes > 0 ? h->der_scratch_bytes : (int64_t)256 << 20; }
+
+int der_check_offsets(plda_handle *h, const char *fn, const int64_t *offsets, int64_t R) {
+  if (R < 1) return fail(h, PLDA_E_INVAL, "%s: R = %lld (must be >= 1)", fn, (long long)R);
+  if (R > (int64_t)0x7fffffff) return fail(h, PLDA_E_INVAL, "%s: R = %lld (at most 2^31 - 1)", fn, (long long)R);
+  if (!offsets) return fail(h, PLDA_E_INVAL, "%s: offsets is NULL", fn);
+  if (offsets[0] != 0) return fail(h, PLDA_E_INVAL, "%s: offsets[0] = %lld (must be 0)", fn, (long long)offsets[0]);
+  for (int64_t r = 0; r < R; ++r) {
+    const int64_t n = offsets[r + 1] - offsets[r];
+    if (n < 1 || n > DER_MAX_HYP)
+      return fail(h, PLDA_E_INVAL, "%s: recording %lld has %lld segments (must be 1 ... PLDA_AHC_MAX = %d; offsets must ascend)", fn,
+                  (long long)r, (long long)n, DER_MAX_HYP);
+  }
+  if (offsets[R] > (int64_t)0x7fffffff) return fail(h, PLDA_E_INVAL, "%s: %lld segments (at most 2^31 - 1)", fn, (long long)offsets[R]);
+  return PLDA_OK;
+}
+
+// Enqueues the solves of `items` (sr, sh, n, m, off, out, r filled in; w, scr and the launch order are this function's);
+// `tab` is the host copy of the launch table, alive until the caller has synchronised.
+template <bool SWEEP>
+int der_solve_enqueue(plda_handle *h, std::vector<DerRec> &items, std::vector<DerRec> &tab, const int *dref, const int *dhyp,
+                      const int *ddur, const int *dma, const int *dmb, long long *dcounts, int *dn_clusters, int *dmap) {
+  static const int bucket_top[] = {8 << 10, 20 << 10, 40 << 10, 80 << 10, DER_LDS_BYTES};
+  constexpr int NB = sizeof(bucket_top) / sizeof(bucket_top[0]);
+  struct Launch { int64_t first, count; int64_t lds; bool hbm; };
+  std::vector<Launch> launches;
+  tab.reserve(items.size());
+  auto lds_of = [](const DerRec &rc, bool hbm) { return der_lds_bytes(rc.sr, rc.w, SWEEP ? rc.n : 0, hbm); };
+  for (DerRec &rc : items) rc.w = std::max(rc.sr, rc.sh);
+  for (int bk = 0; bk < NB; ++bk) {           // LDS class: one launch per bucket of LDS bytes (a launch takes its largest need)
+    const int64_t lo = bk ? bucket_top[bk - 1] : 0, hi = bucket_top[bk];
+    Launch L{(int64_t)tab.size(), 0, 0, false};
+    for (const DerRec &rc : items) {
+      const int64_t b = lds_of(rc, false);
+      if (b > lo && b <= hi) { tab.push_back(rc); ++L.count; L.lds = std::max(L.lds, b); }
+    }
+    if (L.count) launches.push_back(L);
+  }
+  const int64_t budget = der_budget(h);
+  int64_t scratch_need = 0;
+  {                                           // scratch class: launches under the budget
+    Launch L{(int64_t)tab.size(), 0, 0, true};
+    int64_t used = 0;
+    for (const DerRec &it : items) {
+      if (lds_of(it, false) <= DER_LDS_BYTES) continue;
+      const int64_t bytes = (int64_t)8 * it.sr * it.w;
+      if (L.count && used + bytes > budget) {
+        launches.push_back(L);
+        L = Launch{(int64_t)tab.size(), 0, 0, true};
+        used = 0;
+      }
+      DerRec rc = it;
+      rc.scr = used / 8;
+      tab.push_back(rc);
+      ++L.count; L.lds = std::max(L.lds, (int64_t)lds_of(rc, true)); used += bytes;
+      scratch_need = std::max(scratch_need, used);
+    }
+    if (L.count) launches.push_back(L);
+  }
+  if (scratch_need) PLDA_HIP(h, h->der_scratch.reserve((size_t)scratch_need));
+  PLDA_HIP(h, h->der_tab.reserve(tab.size() * sizeof(DerRec)));
+  PLDA_HIP(h, hipMemcpyAsync(h->der_tab.p, tab.data(), tab.size() * sizeof(DerRec), hipMemcpyHostToDevice, h->stream));
+  const DerRec *dtab = h->der_tab.as<DerRec>();
+  long long *scratch = h->der_scratch.as<long long>();
+  PLDA_TRY((der_solve_attr<false, SWEEP>(h)));
+  PLDA_TRY((der_solve_attr<true, SWEEP>(h)));
+  {
+    TraceScope ts(h, SWEEP ? "der.sweep_solve" : "der.solve");
+    for (const Launch &L : launches) {
+      for (int64_t c0 = 0; c0 < L.count; c0 += 1 << 20) {
+        const unsigned c = (unsigned)std::min<int64_t>(1 << 20, L.count - c0);
+        if (L.hbm)
+          der_solve_kernel<true, SWEEP><<<c, DER_T, (size_t)L.lds, h->stream>>>(dref, dhyp, ddur, dma, dmb, dtab + L.first + c0, scratch,
+                                                                                dcounts, dn_clusters, dmap);
+        else
+          der_solve_kernel<false, SWEEP><<<c, DER_T, (size_t)L.lds, h->stream>>>(dref, dhyp, ddur, dma, dmb, dtab + L.first + c0, nullptr,
+                                                                                 dcounts, dn_clusters, dmap);
+        PLDA_LAUNCH_CHECK(h);
+      }
+    }
+  }
+  return PLDA_OK;
+}
+
+// the solves of a call, and the synchronisation behind them (also where the enqueue failed half-way: the table is in flight)
+template <bool SWEEP>
+int der_solve_all(plda_handle *h, std::vector<DerRec> &items, const int *dref, const int *dhyp, const int *ddur, const int *dma,
+                  const int *dmb, long long *dcounts, int *dn_clusters, int *dmap) {
+  std::vector<DerRec> tab;
+  const int rc = der_solve_enqueue<SWEEP>(h, items, tab, dref, dhyp, ddur, dma, dmb, dcounts, dn_clusters, dmap);
+  const hipError_t e = hipStreamSynchronize(h->stream);
+  if (rc != PLDA_OK) return rc;
+  PLDA_HIP(h, e);
+  return PLDA_OK;
+}
+
+}  // namespace
+
+int der_validate(plda_handle *h, const char *fn, const int64_t *offsets, int64_t R) { return der_check_offsets(h, fn, offsets, R); }
+
+int der_sweep_validate(plda_handle *h, const char *fn, const int64_t *offsets, int64_t R, const double *thresholds, int64_t Q,
+                       const int32_t *minc) {
+  PLDA_TRY(der_check_offsets(h, fn, offsets, R));
+  if (Q < 1) return fail(h, PLDA_E_INVAL, "%s: Q = %lld (must be >= 1)", fn, (long long)Q);
+  if (Q > 65535) return fail(h, PLDA_E_INVAL, "%s: Q = %lld (at most 65535)", fn, (long long)Q);
+  if (!thresholds) return fail(h, PLDA_E_INVAL, "%s: thresholds is NULL", fn);
+  for (int64_t q = 0; q < Q; ++q)
+    if (std::isnan(thresholds[q])) return fail(h, PLDA_E_INVAL, "%s: thresholds[%lld] is NaN", fn, (long long)q);
+  for (int64_t r = 0; minc && r < R; ++r)
+    if (minc[r] < 1) return fail(h, PLDA_E_INVAL, "%s: min_clusters[%lld] = %d (must be >= 1)", fn, (long long)r, (int)minc[r]);
+  return PLDA_OK;
+}
+
+int der_plan(plda_handle *h, int64_t Sr, int64_t Sh, int32_t *out) {
+  if (!out) return fail(h, PLDA_E_INVAL, "der_plan: out is NULL");
+  if (Sr < 0 || Sr > DER_MAX_REF) return fail(h, PLDA_E_INVAL, "der_plan: Sr = %lld (must be 0 ... PLDA_DER_MAX_REF = %d)", (long long)Sr, DER_MAX_REF);
+  if (Sh < 0 || Sh > DER_MAX_HYP) return fail(h, PLDA_E_INVAL, "der_plan: Sh = %lld (must be 0 ... PLDA_AHC_MAX = %d)", (long long)Sh, DER_MAX_HYP);
+  const int64_t w = std::max(Sr, Sh);
+  const bool hbm = der_lds_bytes(Sr, w, 0, false) > DER_LDS_BYTES;
+  int64_t wmax = Sr;                          // the widest matrix of Sr rows the LDS class takes
+  while (wmax < DER_MAX_HYP && der_lds_bytes(Sr, wmax + 1, 0, false) <= DER_LDS_BYTES) ++wmax;
+  out[0] = hbm ? 1 : 0;
+  out[1] = hbm ? (int32_t)(8 * Sr * w) : 0;
+  out[2] = (int32_t)wmax;
+  return PLDA_OK;
+}
+
+int der_device(plda_handle *h, const int32_t *dref, const int32_t *dhyp, const int32_t *ddur, const int64_t *offsets, int64_t R,
+               int64_t *dcounts, int32_t *dmap) {
+  const char *fn = "der";
+  if (!dref) return fail(h, PLDA_E_INVAL, "%s: ref is NULL", fn);
+  if (!dhyp) return fail(h, PLDA_E_INVAL, "%s: hyp is NULL", fn);
+  if (!dcounts) return fail(h, PLDA_E_INVAL, "%s: counts is NULL", fn);
+  PLDA_TRY(der_check_offsets(h, fn, offsets, R));
+  // stat: two counters | offsets [R + 1] | sr [R] sh [R]
+  const size_t ints = 16 + 8 * (size_t)(R + 1);
+  PLDA_HIP(h, h->der_stat.reserve(ints + 8 * (size_t)R));
+  char *ds = h->der_stat.as<char>();
+  long long *doff = reinterpret_cast<long long *>(ds + 16);
+  int *dsr = reinterpret_cast<int *>(ds + ints), *dsh = dsr + R;
+  PLDA_HIP(h, hipMemsetAsync(ds, 0, 16, h->stream));
+  PLDA_HIP(h, hipMemcpyAsync(doff, offsets, 8 * (size_t)(R + 1), hipMemcpyHostToDevice, h->stream));
+  {
+    TraceScope ts(h, "der.count");
+    der_count_kernel<<<(unsigned)R, DER_T, 0, h->stream>>>(dref, dhyp, ddur, doff, reinterpret_cast<unsigned long long *>(ds), dsr, dsh);
+    PLDA_LAUNCH_CHECK(h);
+  }
+  unsigned long long bad = 0;
+  std::vector<int> s((size_t)(2 * R));
+  PLDA_HIP(h, hipMemcpyAsync(&bad, ds, 8, hipMemcpyDeviceToHost, h->stream));
+  PLDA_HIP(h, hipMemcpyAsync(s.data(), dsr, 8 * (size_t)R, hipMemcpyDeviceToHost, h->stream));
+  PLDA_HIP(h, hipStreamSynchronize(h->stream));
+  if (bad) return fail(h, PLDA_E_INVAL, "%s: %llu invalid entries (a label below -1 or above its limit, or a negative duration)", fn, bad);
+  std::vector<DerRec> items((size_t)R);
+  for (int64_t r = 0; r < R; ++r) {
+    DerRec &rc = items[(size_t)r];
+    rc.off = offsets[r]; rc.scr = 0; rc.out = r; rc.n = (int)(offsets[r + 1] - offsets[r]);
+    rc.sr = s[(size_t)r]; rc.sh = s[(size_t)(R + r)]; rc.w = 0; rc.m = 0; rc.r = (int)r;
+  }
+  return der_solve_all<false>(h, items, dref, dhyp, ddur, nullptr, nullptr, reinterpret_cast<long long *>(dcounts), nullptr, dmap);
+}
+
+int der_sweep_device(plda_handle *h, const int32_t *dma, const int32_t *dmb, const double *dmc, const int64_t *offsets, int64_t R,
+                     const int32_t *dref, const int32_t *ddur, const double *thresholds, int64_t Q, const int32_t *minc,
+                     int64_t *dcounts, int32_t *dn_clusters) {
+  const char *fn = "der_sweep";
+  if (!dref) return fail(h, PLDA_E_INVAL, "%s: ref is NULL", fn);
+  if (!dcounts) return fail(h, PLDA_E_INVAL, "%s: counts is NULL", fn);
+  if (!dn_clusters) return fail(h, PLDA_E_INVAL, "%s: n_clusters is NULL", fn);
+  PLDA_TRY(der_sweep_validate(h, fn, offsets, R, thresholds, Q, minc));
+  const int64_t T = offsets[R];
+  if (T > R && !(dma && dmb && dmc)) return fail(h, PLDA_E_INVAL, "%s: merge_a, merge_b or merge_cost is NULL", fn);
+  // stat: two counters | offsets [R + 1] | thresholds [Q] | sr [R] m [Q, R] minc [R]
+  const size_t o_thr = 16 + 8 * (size_t)(R + 1), o_int = o_thr + 8 * (size_t)Q;
+  PLDA_HIP(h, h->der_stat.reserve(o_int + 4 * (size_t)(R + Q * R + R)));
+  char *ds = h->der_stat.as<char>();
+  long long *doff = reinterpret_cast<long long *>(ds + 16);
+  double *dthr = reinterpret_cast<double *>(ds + o_thr);
+  int *dsr = reinterpret_cast<int *>(ds + o_int), *dm = dsr + R, *dminc = dm + Q * R;
+  PLDA_HIP(h, hipMemsetAsync(ds, 0, 16, h->stream));
+  PLDA_HIP(h, hipMemcpyAsync(doff, offsets, 8 * (size_t)(R + 1), hipMemcpyHostToDevice, h->stream));
+  PLDA_HIP(h, hipMemcpyAsync(dthr, thresholds, 8 * (size_t)Q, hipMemcpyHostToDevice, h->stream));
+  if (minc) PLDA_HIP(h, hipMemcpyAsync(dminc, minc, 4 * (size_t)R, hipMemcpyHostToDevice, h->stream));
+  {
+    TraceScope ts(h, "der.sweep_count");
+    unsigned long long *dstat = reinterpret_cast<unsigned long long *>(ds);
+    der_count_kernel<<<(unsigned)R, DER_T, 0, h->stream>>>(dref, nullptr, ddur, doff, dstat, dsr, nullptr);
+    PLDA_LAUNCH_CHECK(h);
+    der_prefix_kernel<<<dim3((unsigned)R, (unsigned)Q), DER_T, 0, h->stream>>>(dma, dmb, dmc, doff, dthr, minc ? dminc : nullptr, (int)R,
+                                                                               dstat, dm);
+    PLDA_LAUNCH_CHECK(h);
+  }
+  unsigned long long bad[2] = {0, 0};
+  std::vector<int> s((size_t)(R + Q * R));
+  PLDA_HIP(h, hipMemcpyAsync(bad, ds, 16, hipMemcpyDeviceToHost, h->stream));
+  PLDA_HIP(h, hipMemcpyAsync(s.data(), dsr, 4 * s.size(), hipMemcpyDeviceToHost, h->stream));
+  PLDA_HIP(h, hipStreamSynchronize(h->stream));
+  if (bad[0]) return fail(h, PLDA_E_INVAL, "%s: %llu invalid entries (a label below -1 or above its limit, or a negative duration)", fn, bad[0]);
+  if (bad[1])
+    return fail(h, PLDA_E_INVAL, "%s: %llu (recording, threshold) pairs whose merge record ends, or holds an entry that is no merge, "
+                                 "before the stop rule fires: not a full record", fn, bad[1]);
+  std::vector<DerRec> items((size_t)(Q * R));
+  for (int64_t q = 0; q < Q; ++q)
+    for (int64_t r = 0; r < R; ++r) {
+      DerRec &rc = items[(size_t)(q * R + r)];
+      rc.off = offsets[r]; rc.scr = 0; rc.out = q * R + r; rc.n = (int)(offsets[r + 1] - offsets[r]);
+      rc.sr = s[(size_t)r]; rc.m = s[(size_t)(R + q * R + r)]; rc.sh = rc.n - rc.m; rc.w = 0; rc.r = (int)r;
+    }
+  return der_solve_all<true>(h, items, dref, nullptr, ddur, dma, dmb, reinterpret_cast<long long *>(dcounts), dn_clusters, nullptr);
+}
+
+}  // namespace plda

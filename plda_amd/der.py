@@ -1,0 +1,186 @@
+"""plda_amd/der.py -- diarisation error rate on the device (csrc/der.hip; include/plda_hip.h, "diarisation error rate"):
+segment-level miss, false alarm and speaker confusion under the optimal one-to-one mapping of reference to hypothesis
+speakers, and the sweep of ONE full AHC merge record over Q thresholds.
+
+    der(engine, ref, hyp, offsets, dur=None)              counts [R, 4], per-recording and pooled DER[, the speaker map]
+    sweep(engine, merges, offsets, ref, thresholds, ...)  counts [Q, R, 4], n_clusters [Q, R], pooled DER [Q], the best q
+    plan(engine, sr, sh)                                  the dispatch class of a recording of sr x sh speakers
+    MPlda.der / MPlda.tune_threshold                      the same from an engine; tune_threshold clusters once, then sweeps
+
+Labels: ref in [-1, 64), hyp in [-1, 4096), -1 = non-speech; dur int32 >= 0 in ticks (None: 1 everywhere).  Everything on the
+device is an integer and the counts are exact; the divisions are done here, the pooled ones from Python ints.  Out of scope,
+on purpose: overlapped speech, a collar, JER, a time-based restatement of md-eval (plda_amd/rttm.py turns RTTM turns into
+per-segment labels).
+"""
+import ctypes as C
+
+import numpy as np
+
+from . import _native as N
+from . import diarize
+
+MAX_REF = 64            # PLDA_DER_MAX_REF
+MAX_HYP = diarize.AHC_MAX
+
+_p = diarize._p
+
+
+class DerResult:
+    """counts int64 [R, 4] = {speech, miss, fa, confusion}; der float64 [R] (NaN where speech = 0); total = the pooled
+    sum of errors / sum of speech (NaN when there is no speech); map int32 [R, 64] or None."""
+
+    def __init__(self, counts, map_=None):
+        self.counts = counts
+        self.map = map_
+        self.der = rates(counts)
+        self.total = pooled(counts)
+
+    def __repr__(self):
+        return "DerResult(total=%r, recordings=%d)" % (self.total, len(self.counts))
+
+
+class SweepResult:
+    """counts int64 [Q, R, 4]; n_clusters int32 [Q, R]; der float64 [Q], pooled over the recordings; best = the index of the
+    lowest pooled DER (ties: the lowest index; NaN never wins); thresholds float64 [Q]."""
+
+    def __init__(self, thresholds, counts, n_clusters):
+        self.thresholds = thresholds
+        self.counts = counts
+        self.n_clusters = n_clusters
+        self.der = np.asarray([pooled(c) for c in counts], np.float64)
+        self.best = best_index(counts)
+
+    def __repr__(self):
+        return "SweepResult(best=%d, threshold=%r, der=%r)" % (self.best, float(self.thresholds[self.best]), float(self.der[self.best]))
+
+
+def rates(counts):
+    """(miss + fa + confusion) / speech of every row of counts [..., 4]; NaN where speech = 0."""
+    c = np.asarray(counts, np.int64)
+    err = (c[..., 1] + c[..., 2] + c[..., 3]).astype(np.float64)
+    sp = c[..., 0].astype(np.float64)
+    out = np.full(err.shape, np.nan)
+    np.divide(err, sp, out=out, where=sp > 0)
+    return out
+
+
+def _sums(counts):
+    c = np.asarray(counts, np.int64).reshape(-1, 4)
+    speech = sum(int(v) for v in c[:, 0])
+    err = sum(int(v) for v in c[:, 1:].ravel())
+    return err, speech
+
+
+def pooled(counts):
+    """sum of errors / sum of speech over counts [R, 4], from Python ints; NaN when there is no speech."""
+    err, speech = _sums(counts)
+    return err / speech if speech > 0 else float("nan")
+
+
+def best_index(counts):
+    """argmin over q of the pooled DER of counts [Q, R, 4], compared as exact fractions; ties go to the lowest q."""
+    best, be, bs = 0, None, None
+    for q, c in enumerate(counts):
+        err, speech = _sums(c)
+        if speech <= 0:
+            continue
+        if be is None or err * bs < be * speech:         # err / speech < be / bs
+            best, be, bs = q, err, speech
+    return best
+
+
+def plan(engine, sr, sh):
+    """{"cls": 0 (matrix in LDS) or 1 (in handle scratch), "scratch_bytes": per recording, "lds_max": the widest matrix,
+    max(sr, sh), of the LDS class at this sr}."""
+    out = (C.c_int32 * 3)()
+    N.check(engine._h, engine._lib.plda_der_plan(engine._h, int(sr), int(sh), out))
+    return {"cls": int(out[0]), "scratch_bytes": int(out[1]), "lds_max": int(out[2])}
+
+
+def _offsets(offsets):
+    offsets = np.ascontiguousarray(offsets, np.int64)
+    if offsets.ndim != 1 or len(offsets) < 2:
+        raise ValueError("offsets must hold R + 1 >= 2 entries")
+    if offsets[0] != 0:
+        raise ValueError("offsets must start at 0")
+    sizes = np.diff(offsets)
+    if (sizes < 1).any() or (sizes > MAX_HYP).any():
+        raise ValueError("every recording must hold 1 ... %d segments (offsets must ascend)" % MAX_HYP)
+    return offsets
+
+
+def _labels(a, t, name, limit):
+    a = np.asarray(a)
+    if a.dtype.kind not in "iu":
+        raise ValueError("%s must be an integer array" % name)
+    if a.shape != (t,):
+        raise ValueError("%s must hold one entry per segment (%d), got %r" % (name, t, a.shape))
+    if a.size and (a.min() < -1 or a.max() >= limit):
+        raise ValueError("%s must lie in [-1, %d)" % (name, limit))
+    return np.ascontiguousarray(a, np.int32)
+
+
+def _dur(dur, t):
+    if dur is None:
+        return None
+    d = np.asarray(dur)
+    if d.dtype.kind not in "iu":
+        raise ValueError("dur must be an integer array of ticks")
+    if d.shape != (t,):
+        raise ValueError("dur must hold one entry per segment (%d), got %r" % (t, d.shape))
+    if d.size and (d.min() < 0 or d.max() > 0x7fffffff):
+        raise ValueError("dur must lie in [0, 2^31)")
+    return np.ascontiguousarray(d, np.int32)
+
+
+def der_args(ref, hyp, offsets, dur):
+    """The argument check of der / MPlda.der, before any device work -> (ref, hyp, offsets, dur).  ValueError on anything the
+    C ABI would answer with PLDA_E_INVAL."""
+    offsets = _offsets(offsets)
+    t = int(offsets[-1])
+    return _labels(ref, t, "ref", MAX_REF), _labels(hyp, t, "hyp", MAX_HYP), offsets, _dur(dur, t)
+
+
+def sweep_args(merges, offsets, ref, thresholds, dur, num_speakers):
+    """The argument check of sweep -> (merge_a, merge_b, merge_cost, offsets, ref, thresholds, dur, min_clusters)."""
+    offsets = _offsets(offsets)
+    r, t = len(offsets) - 1, int(offsets[-1])
+    if len(merges) != 3:
+        raise ValueError("merges must be (merge_a, merge_b, merge_cost)")
+    ma, mb = (np.ascontiguousarray(a, np.int32) for a in merges[:2])
+    mc = np.ascontiguousarray(merges[2], np.float64)
+    for a, name in ((ma, "merge_a"), (mb, "merge_b"), (mc, "merge_cost")):
+        if a.shape != (t - r,):
+            raise ValueError("%s must hold T - R = %d entries, got %r" % (name, t - r, a.shape))
+    thresholds = np.ascontiguousarray(thresholds, np.float64)
+    if thresholds.ndim != 1 or len(thresholds) < 1:
+        raise ValueError("thresholds must hold Q >= 1 entries")
+    if np.isnan(thresholds).any():
+        raise ValueError("thresholds must not hold NaN")
+    _, _, minc = diarize.stop_args(offsets, 0.0, num_speakers)
+    if minc is not None and (minc < 1).any():
+        raise ValueError("num_speakers must be >= 1")
+    return ma, mb, mc, offsets, _labels(ref, t, "ref", MAX_REF), thresholds, _dur(dur, t), minc
+
+
+def der(engine, ref, hyp, offsets, dur=None, return_map=False):
+    """Score R recordings: ref, hyp int [T] (-1 = non-speech), recording r owning segments offsets[r] .. offsets[r+1], dur
+    int [T] ticks (None: 1).  Returns a DerResult."""
+    ref, hyp, offsets, dur = der_args(ref, hyp, offsets, dur)
+    r = len(offsets) - 1
+    counts = np.empty((r, 4), np.int64)
+    map_ = np.empty((r, MAX_REF), np.int32) if return_map else None
+    N.check(engine._h, engine._lib.plda_der(engine._h, _p(ref), _p(hyp), _p(dur), _p(offsets), r, _p(counts), _p(map_)))
+    return DerResult(counts, map_)
+
+
+def sweep(engine, merges, offsets, ref, thresholds, dur=None, num_speakers=None):
+    """Score the clusterings that a FULL merge record (diarize.ahc / MPlda.cluster with threshold=None, num_speakers=1,
+    return_merges=True) yields at every one of `thresholds`, with at least `num_speakers` clusters left (None: 1): what
+    diarize.cut at that threshold followed by der returns, for all Q in one device run.  Returns a SweepResult."""
+    ma, mb, mc, offsets, ref, thresholds, dur, minc = sweep_args(merges, offsets, ref, thresholds, dur, num_speakers)
+    r, q = len(offsets) - 1, len(thresholds)
+    counts, ncl = np.empty((q, r, 4), np.int64), np.empty((q, r), np.int32)
+    N.check(engine._h, engine._lib.plda_der_sweep(engine._h, _p(ma), _p(mb), _p(mc), _p(offsets), r, _p(ref), _p(dur), _p(thresholds),
+                                                  q, _p(minc), _p(counts), _p(ncl)))
+    return SweepResult(thresholds, counts, ncl)

@@ -488,6 +488,48 @@ class MPlda(object):
             _ptr(min_clusters) if min_clusters is not None else None, vp(dlabels), vp(dn_clusters), vp(dmerge_a), vp(dmerge_b),
             vp(dmerge_cost)))
 
+    # ----------------------------------------------------------------- diarisation error rate (csrc/der.hip)
+    def der(self, ref, hyp, offsets, dur=None, return_map=False):
+        """Diarisation error rate of R recordings (plda_amd/der.py): ref, hyp int [T] per-segment speaker labels (-1 =
+        non-speech), recording r owning segments offsets[r] .. offsets[r+1], dur int [T] ticks (None: 1 everywhere).  Miss,
+        false alarm and confusion under the optimal one-to-one speaker mapping, exact integers from the device.  Returns a
+        plda_amd.der.DerResult (counts [R, 4], der [R], total[, map [R, 64]])."""
+        from . import der
+        return der.der(self, ref, hyp, offsets, dur, return_map)
+
+    def tune_threshold(self, x, offsets, ref, thresholds, dur=None):
+        """The clustering threshold with the lowest pooled DER on a development set: ONE cluster(x, offsets, threshold=None,
+        num_speakers=1, return_merges=True), then one der.sweep of its full merge record over `thresholds`.  Returns
+        (the best threshold -- the first of equal ones --, the plda_amd.der.SweepResult)."""
+        from . import der
+        offsets = np.ascontiguousarray(offsets, np.int64)
+        X = _features(x, "Segment vectors")
+        if offsets.ndim != 1 or len(offsets) < 2 or X.shape[0] != int(offsets[-1]):
+            raise ValueError("offsets must hold R + 1 >= 2 entries ending at the number of rows of x")
+        t, r = int(offsets[-1]), len(offsets) - 1
+        empty = (np.zeros(t - r, np.int32), np.zeros(t - r, np.int32), np.zeros(t - r))
+        der.sweep_args(empty, offsets, ref, thresholds, dur, None)        # (before any device work)
+        _, _, merges = self.cluster(X, offsets, threshold=None, num_speakers=1, return_merges=True)
+        res = der.sweep(self, merges, offsets, ref, thresholds, dur)
+        return float(res.thresholds[res.best]), res
+
+    def der_dev(self, dref, dhyp, ddur, offsets, dcounts, dmap=None):
+        """plda_der_dev on HBM-resident int32 labels and durations (raw device addresses; ddur and dmap may be None);
+        offsets (int64) is a HOST array; dcounts int64 [R, 4], dmap int32 [R, 64]."""
+        def vp(x):
+            return C.c_void_p(int(x)) if x else None
+        self._ck(self._lib.plda_der_dev(self._h, vp(dref), vp(dhyp), vp(ddur), _ptr(offsets), len(offsets) - 1, vp(dcounts), vp(dmap)))
+
+    def der_sweep_dev(self, dmerge_a, dmerge_b, dmerge_cost, offsets, dref, ddur, thresholds, min_clusters, dcounts, dn_clusters):
+        """plda_der_sweep_dev on an HBM-resident full merge record, labels and durations (raw device addresses); offsets
+        (int64), thresholds (float64) and min_clusters (int32 or None) are HOST arrays; dcounts int64 [Q, R, 4], dn_clusters
+        int32 [Q, R]."""
+        def vp(x):
+            return C.c_void_p(int(x)) if x else None
+        self._ck(self._lib.plda_der_sweep_dev(
+            self._h, vp(dmerge_a), vp(dmerge_b), vp(dmerge_cost), _ptr(offsets), len(offsets) - 1, vp(dref), vp(ddur), _ptr(thresholds),
+            len(thresholds), _ptr(min_clusters) if min_clusters is not None else None, vp(dcounts), vp(dn_clusters)))
+
     # ----------------------------------------------------------------- norm
     def norm(self, vectors, transformedvecs, numutts=0):
         """MPlda_norm (pldamodule.cpp:196-256): z-norm statistics of every enrol model
