@@ -439,6 +439,7 @@ int simdiag_finish_with(plda_handle *h, const double *W, const double *B, int D,
 // T [D,D], Tinv = T^{-1} (nullable), psi[D].  W,B are not modified.
 int simdiag_f64(plda_handle *h, const double *W, const double *B, int D, double *T,
                 double *Tinv, double *psi, bool warm_start);
+const double *simdiag_whitening(plda_handle *h, int D);   // chol(W)^-1 of the last simdiag of size D (device, [D][D])
 
 int syrk_f64(plda_handle *h, int D, int64_t K, double alpha, const double *X, int64_t ldx, const double *kw, double beta,
              double *C, int64_t ldc);   // C = alpha X^T diag(kw) X + beta C, X [K, D] (both triangles written)

@@ -125,6 +125,9 @@ __global__ __launch_bounds__(RS_THREADS) void rs_scatter_kernel(
 // every row read is one contiguous D*8-byte burst; rows are summed in ascending row
 // order (deterministic).  Also emits the per-row weight 1/n_label used by K2.
 // ------------------------------------------------------------------------------------
+// DIV: mean = sum / n, correctly rounded, so that exact sums give exact means (the LDA's class-centred rows must vanish
+// where a feature is constant within a class); otherwise sum * (1 / n), the PLDA statistics pass's form
+template <bool DIV>
 __global__ __launch_bounds__(256) void centroid_kernel(const double *__restrict__ X, int D,
                                                        const uint32_t *__restrict__ perm,
                                                        const int *__restrict__ offsets,
@@ -143,7 +146,7 @@ __global__ __launch_bounds__(256) void centroid_kernel(const double *__restrict_
       acc += a; acc += b; acc += c; acc += e;
     }
     for (; r < end; ++r) acc += X[(int64_t)perm[r] * D + d0];
-    means[(int64_t)k * D + d0] = acc * inv;
+    means[(int64_t)k * D + d0] = DIV ? acc / (double)n : acc * inv;
   }
   for (int r = beg + threadIdx.x; r < end; r += blockDim.x) roww[perm[r]] = inv;
 }
@@ -787,7 +790,7 @@ int fit_stats_device(plda_handle *h, const double *dX, int64_t N, int D, const u
   counts_to_i64_kernel<<<(unsigned)ceil_div(K, 256), 256, 0, h->stream>>>(offsets, K, h->f_counts.as<int64_t>());
   {
     TraceScope ts(h, "fit.centroids (K1)", (double)N * D * 8.0, 2);
-    centroid_kernel<<<(unsigned)K, 256, 0, h->stream>>>(dX, D, perm, offsets, means, roww);
+    centroid_kernel<false><<<(unsigned)K, 256, 0, h->stream>>>(dX, D, perm, offsets, means, roww);
     PLDA_LAUNCH_CHECK(h);
   }
   // offset_scatter = X^T diag(1/n_label) X - sum_k (n_k w_k) m_k m_k^T,  n_k w_k = 1
@@ -1306,7 +1309,7 @@ int group_by_label_device(plda_handle *h, const uint64_t *dlabels, int64_t N, ui
 int group_centroids_device(plda_handle *h, const double *dX, int64_t N, int D, const uint32_t *perm, const int *offsets,
                            int64_t G, double *dmeans, int32_t *dcounts32) {
   PLDA_HIP(h, h->w[3].reserve((size_t)N * 8));
-  centroid_kernel<<<(unsigned)G, 256, 0, h->stream>>>(dX, D, perm, offsets, dmeans, h->w[3].as<double>());
+  centroid_kernel<false><<<(unsigned)G, 256, 0, h->stream>>>(dX, D, perm, offsets, dmeans, h->w[3].as<double>());
   PLDA_LAUNCH_CHECK(h);
   counts_to_i32_kernel<<<(unsigned)ceil_div(G, 256), 256, 0, h->stream>>>(offsets, G, dcounts32);
   PLDA_LAUNCH_CHECK(h);
@@ -1319,7 +1322,7 @@ int group_means_device(plda_handle *h, const double *dX, int64_t N, int D, const
   int *offsets = nullptr;
   PLDA_TRY(sort_by_label(h, ddense, N, Ku, &perm, &offsets));
   PLDA_HIP(h, h->w[3].reserve((size_t)N * 8));
-  centroid_kernel<<<(unsigned)Ku, 256, 0, h->stream>>>(dX, D, perm, offsets, dmeans, h->w[3].as<double>());
+  centroid_kernel<true><<<(unsigned)Ku, 256, 0, h->stream>>>(dX, D, perm, offsets, dmeans, h->w[3].as<double>());
   PLDA_LAUNCH_CHECK(h);
   counts_to_i32_kernel<<<(unsigned)ceil_div(Ku, 256), 256, 0, h->stream>>>(offsets, Ku, dcounts32);
   PLDA_LAUNCH_CHECK(h);

@@ -2,8 +2,11 @@
 // /root/reference/python/liblda/lda.py, rebuilt on the PLDA kernels.
 //
 //   fit   'svd'   lda.py:171-209  within-class whitening + SVD of the scaled centroids.  Both SVDs are taken
-//                                 through the Gram matrix (D x D weighted SYRK over the N rows, then the
-//                                 symmetric eigensolver): X is read once, nothing N-sized is ever factorised.
+//                                 through the Gram matrix (D x D product over the N class-centred rows, then the
+//                                 symmetric eigensolver): nothing N-sized is ever factorised.
+// Every scatter matrix is a product of CENTRED rows (x_i - m_label for Sw and the svd solver's S, x_i - mu for St), as the
+// reference forms them (lda.py:187, np.cov): the difference of uncentred sums X^T X - sum n_k m_k m_k^T loses
+// eps (offset / spread)^2 and leaves noise instead of zero where a feature is constant within every class.
 //         'eigen' lda.py:134-169  Sb v = lambda Sw v by simultaneous diagonalisation (the PLDA GetOutput kernels)
 //         'lsqr'  lda.py:211-240  coef = Sw^+ means^T through the eigendecomposition of Sw
 //   predict       lda.py:242-314  decision = X coef^T + intercept (fp64 MFMA GEMM), row kernels for the
@@ -33,6 +36,16 @@ __global__ void lda_weighted_colsum_kernel(const double *__restrict__ means, con
   double s = 0.0;
   for (int64_t k = 0; k < K; ++k) s = fma(wk[k], means[k * D + d], s);
   out[d] = s;
+}
+
+// out[i][d] = X[i][d] - (labels ? means[labels[i]][d] : means[d])     (labels were checked by group_means_device)
+__global__ void lda_center_rows_kernel(const double *__restrict__ X, const uint64_t *__restrict__ labels,
+                                       const double *__restrict__ means, int64_t N, int D, double *__restrict__ out) {
+  const int64_t idx = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (idx >= N * D) return;
+  const int64_t i = idx / D;
+  const int d = (int)(idx - i * D);
+  out[idx] = X[idx] - means[(labels ? (int64_t)labels[i] * D : 0) + d];
 }
 
 // out[k][d] = (means[k][d] - xbar[d]) * (rowscale ? rowscale[k] : 1)
@@ -72,11 +85,16 @@ __global__ void lda_scal1_kernel(const double *__restrict__ Vrows, const double 
   scal1[idx] = Vrows[(size_t)r * D + d] / std[d] / sqrt(lam[r]);
 }
 
-// A -= alpha * u u^T
-__global__ void lda_rank1_sub_kernel(double *__restrict__ A, const double *__restrict__ u, int D) {
-  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= D * D) return;
-  A[idx] -= u[idx / D] * u[idx % D];
+// *flag = 1 where a Cholesky pivot of Sw, 1 / T1[k][k]^2 with T1 = chol(Sw)^-1, is not above the rounding error of its own
+// computation, D eps Sw[k][k] (the pivot is Sw[k][k] minus a sum of squares below it): Sw is singular to working precision,
+// where scipy.linalg.eigh(Sb, Sw) raises (lda.py:167).  The factorisation itself only flags a pivot <= 0, which an exactly
+// singular Sw of centred rows reaches or misses by its last rounding.
+__global__ void lda_pivot_check_kernel(const double *__restrict__ T1, const double *__restrict__ Sw, int D,
+                                       int *__restrict__ flag) {
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= D) return;
+  const double t = T1[(size_t)k * D + k];
+  if (!(1.0 / (t * t) > (double)D * 2.220446049250313e-16 * Sw[(size_t)k * D + k])) *flag = 1;
 }
 
 // Sb = sym(St - Sw); Sw = sym(Sw)
@@ -222,20 +240,20 @@ int lda_fit_device(plda_handle *h, const double *dX, int64_t N, int D, const uin
          *intercept = h->l_intercept.as<double>();
 
   // ---- class means and counts (the PLDA K1a/K1 kernels) ----
-  // scratch: [counts32 K][cw K][nk K][rw N][S DD][G DD][Vr DD][lam D][std D][mu D][Mc K*D][tmp K*D][small DD*2]
-  const size_t bytes = (size_t)K * 4 + 64 + (size_t)K * 16 + (size_t)N * 8 + DD * 8 * 5 + (size_t)D * 8 * 3 +
-                       (size_t)K * D * 8 * 2 + 256;
+  // scratch: [counts32 K][cw K][rw N][S DD][G DD][Vr DD][lam D][std D][mu D][Mc K*D][tmp K*D][small DD*2][Xc N*D]
+  const size_t bytes = (size_t)K * 4 + 64 + (size_t)K * 8 + (size_t)N * 8 + DD * 8 * 5 + (size_t)D * 8 * 3 +
+                       (size_t)K * D * 8 * 2 + (size_t)N * D * 8 + 256;
   PLDA_HIP(h, h->w[12].reserve(bytes));
   char *base = h->w[12].as<char>();
   int32_t *dcounts = reinterpret_cast<int32_t *>(base);
   double *cw = reinterpret_cast<double *>(base + round_up((int64_t)K * 4, 64));
-  double *nk = cw + K, *rw = nk + K, *S = rw + N, *G = S + DD, *Vr = G + DD, *lam = Vr + DD, *std = lam + D,
-         *mu = std + D, *Mc = mu + D, *tmp = Mc + (size_t)K * D, *sm1 = tmp + (size_t)K * D, *sm2 = sm1 + DD;
+  double *rw = cw + K, *S = rw + N, *G = S + DD, *Vr = G + DD, *lam = Vr + DD, *std = lam + D,
+         *mu = std + D, *Mc = mu + D, *tmp = Mc + (size_t)K * D, *sm1 = tmp + (size_t)K * D, *sm2 = sm1 + DD, *Xc = sm2 + DD;
   PLDA_TRY(group_means_device(h, dX, N, D, dlabels, K, means, dcounts));
   std::vector<int32_t> hc((size_t)K);
   PLDA_HIP(h, hipMemcpyAsync(hc.data(), dcounts, (size_t)K * 4, hipMemcpyDeviceToHost, h->stream));
   PLDA_HIP(h, hipStreamSynchronize(h->stream));
-  std::vector<double> p((size_t)K), hcw((size_t)K), hnk((size_t)K);
+  std::vector<double> p((size_t)K), hcw((size_t)K);
   double psum = 0.0;
   for (int64_t k = 0; k < K; ++k) {
     if (hc[k] <= 0) return fail(h, PLDA_E_LABELS, "lda_fit: labels must be dense 0..K-1 (label %lld unused)", (long long)k);
@@ -247,18 +265,17 @@ int lda_fit_device(plda_handle *h, const double *dX, int64_t N, int D, const uin
   for (int64_t k = 0; k < K; ++k) {
     if (!(p[k] > 0.0)) return fail(h, PLDA_E_INVAL, "lda_fit: priors must be positive");
     hcw[k] = p[k] / (double)hc[k];
-    hnk[k] = (double)hc[k];
   }
   PLDA_HIP(h, hipMemcpyAsync(dpri, p.data(), (size_t)K * 8, hipMemcpyHostToDevice, h->stream));
   PLDA_HIP(h, hipMemcpyAsync(cw, hcw.data(), (size_t)K * 8, hipMemcpyHostToDevice, h->stream));
-  PLDA_HIP(h, hipMemcpyAsync(nk, hnk.data(), (size_t)K * 8, hipMemcpyHostToDevice, h->stream));
   int rank = D;
+  lda_center_rows_kernel<<<blocks(N * (int64_t)D), 256, 0, h->stream>>>(dX, dlabels, means, N, D, Xc);   // x_i - m_label
+  PLDA_LAUNCH_CHECK(h);
 
   if (solver == LDA_SVD) {
     lda_weighted_colsum_kernel<<<blocks(D), 256, 0, h->stream>>>(means, dpri, K, D, xbar);   // xbar = priors . means
-    // within scatter of the class-centred data: X^T X - sum_k n_k m_k m_k^T
-    PLDA_TRY(gemm_f64(h, D, D, N, 1.0, dX, 1, D, dX, D, 1, nullptr, 0.0, S, D));
-    PLDA_TRY(gemm_f64(h, D, D, K, -1.0, means, 1, D, means, D, 1, nk, 1.0, S, D));
+    // within scatter of the class-centred data (lda.py:187)
+    PLDA_TRY(gemm_f64(h, D, D, N, 1.0, Xc, 1, D, Xc, D, 1, nullptr, 0.0, S, D));
     const double fac = 1.0 / (double)(N - K);
     lda_std_kernel<<<blocks(D), 256, 0, h->stream>>>(S, N, D, std);
     lda_whiten_gram_kernel<<<blocks((int64_t)DD), 256, 0, h->stream>>>(S, std, fac, D, G);
@@ -299,21 +316,21 @@ int lda_fit_device(plda_handle *h, const double *dX, int64_t N, int D, const uin
     PLDA_LAUNCH_CHECK(h);
     rank = r2;
   } else {
-    // Sw = sum_k p_k cov_k = X^T diag(p_label / n_label) X - sum_k p_k m_k m_k^T   (lda.py:10-16,153)
+    // Sw = sum_k p_k cov_k = Xc^T diag(p_label / n_label) Xc, Xc the class-centred rows   (lda.py:10-16,153)
     lda_row_weight_kernel<<<blocks(N), 256, 0, h->stream>>>(dlabels, cw, N, rw);
     PLDA_LAUNCH_CHECK(h);
     double *Sw = S;
-    PLDA_TRY(gemm_f64(h, D, D, N, 1.0, dX, 1, D, dX, D, 1, rw, 0.0, Sw, D));
-    PLDA_TRY(gemm_f64(h, D, D, K, -1.0, means, 1, D, means, D, 1, dpri, 1.0, Sw, D));
+    PLDA_TRY(gemm_f64(h, D, D, N, 1.0, Xc, 1, D, Xc, D, 1, rw, 0.0, Sw, D));
     if (solver == LDA_EIGEN) {
-      // St = X^T X / N - mu mu^T (lda.py:156), Sb = St - Sw
+      // St = (X - mu)^T (X - mu) / N (lda.py:156; Xc is free again after Sw), Sb = St - Sw
       double *St = G, *Sb = sm1, *T = sm2;
-      PLDA_TRY(gemm_f64(h, D, D, N, 1.0 / (double)N, dX, 1, D, dX, D, 1, nullptr, 0.0, St, D));
       std::vector<double> hw((size_t)K);
       for (int64_t k = 0; k < K; ++k) hw[k] = (double)hc[k] / (double)N;
       PLDA_HIP(h, hipMemcpyAsync(cw, hw.data(), (size_t)K * 8, hipMemcpyHostToDevice, h->stream));
       lda_weighted_colsum_kernel<<<blocks(D), 256, 0, h->stream>>>(means, cw, K, D, mu);
-      lda_rank1_sub_kernel<<<blocks((int64_t)DD), 256, 0, h->stream>>>(St, mu, D);
+      lda_center_rows_kernel<<<blocks(N * (int64_t)D), 256, 0, h->stream>>>(dX, nullptr, mu, N, D, Xc);
+      PLDA_LAUNCH_CHECK(h);
+      PLDA_TRY(gemm_f64(h, D, D, N, 1.0 / (double)N, Xc, 1, D, Xc, D, 1, nullptr, 0.0, St, D));
       lda_between_kernel<<<blocks((int64_t)DD), 256, 0, h->stream>>>(Sw, St, D, Sb);
       PLDA_LAUNCH_CHECK(h);
       h->simdiag_has_vr = false;
@@ -321,6 +338,11 @@ int lda_fit_device(plda_handle *h, const double *dX, int64_t N, int D, const uin
       const int rc = simdiag_f64(h, Sw, Sb, D, T, nullptr, lam, false);   // T Sw T^T = I, T Sb T^T = diag(lam) desc
       h->eig_keep_sign = false;
       if (rc != PLDA_OK) return rc;
+      int *dsing = dcounts, hsing = 0;                                    // the counts were read back above
+      PLDA_HIP(h, hipMemsetAsync(dsing, 0, sizeof(int), h->stream));
+      lda_pivot_check_kernel<<<blocks(D), 256, 0, h->stream>>>(simdiag_whitening(h, D), Sw, D, dsing);
+      PLDA_LAUNCH_CHECK(h);
+      PLDA_HIP(h, hipMemcpyAsync(&hsing, dsing, sizeof(int), hipMemcpyDeviceToHost, h->stream));
       lda_unit_columns_kernel<<<D, 64, 0, h->stream>>>(T, D, scalings);   // lda.py:162
       PLDA_LAUNCH_CHECK(h);
       // coef = means E E^T
@@ -329,6 +351,7 @@ int lda_fit_device(plda_handle *h, const double *dX, int64_t N, int D, const uin
       std::vector<double> hl((size_t)D);
       PLDA_HIP(h, hipMemcpyAsync(hl.data(), lam, (size_t)D * 8, hipMemcpyDeviceToHost, h->stream));
       PLDA_HIP(h, hipStreamSynchronize(h->stream));
+      if (hsing) return fail(h, PLDA_E_NUMERIC, "within-class covariance is not positive definite");
       double tot = 0.0;
       for (int d = 0; d < D; ++d) tot += hl[d];
       for (int d = 0; d < D; ++d) hl[d] /= tot;

@@ -2270,6 +2270,9 @@ void simdiag_flags(plda_handle *h, int D, const int **chol_flag, const int **eig
   *eig_flag = h->eigdc_flag;          // nullptr: the direct method did not take the problem (status 8)
 }
 
+// T1 = chol(W)^-1 (lower triangular, [D][D]) of the last simdiag of size D, valid until the next one
+const double *simdiag_whitening(plda_handle *h, int D) { return h->w[13].as<double>() + 2 * (size_t)D * D; }
+
 int simdiag_finish_with(plda_handle *h, const double *W, const double *B, int D, double *T, double *Tinv, double *psi,
                         int chol_flag, int eig_status, bool *redo) {
   *redo = false;
