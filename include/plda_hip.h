@@ -1040,8 +1040,8 @@ int plda_score_ahc(plda_handle *h, const double *X, const int64_t *offsets, int6
  *   plda_vbx                 the same with everything in host memory.
  *   plda_project_rows[_dev]  out [R, Dout] = X [R, Din] transform^T + offset: TransformIvector without its normalisation
  *                            factor, through the library's fp64 GEMM.
- * OUT OF SCOPE, each on purpose: length normalisation and the LDA fit before the model (the caller's business); more than 64
- * initial speakers; several workgroups on one recording; overlap handling.  (DER: the section "diarisation error rate" below;
+ * (Length normalisation and the LDA fit before the model: the section "embedding chain" below, K18.)
+ * OUT OF SCOPE, each on purpose: more than 64 initial speakers; several workgroups on one recording; overlap handling.  (DER: the section "diarisation error rate" below;
  * RTTM: plda_amd/rttm.py.) ---- */
 #define PLDA_VBX_MAX_SPK 64
 int plda_vbx_plan(plda_handle *h, int64_t T, int64_t S, int64_t D, int32_t out[3]);
@@ -1131,6 +1131,74 @@ int plda_der_sweep_dev(plda_handle *h, const int32_t *dmerge_a, const int32_t *d
 int plda_der_sweep(plda_handle *h, const int32_t *merge_a, const int32_t *merge_b, const double *merge_cost, const int64_t *offsets,
                    int64_t R, const int32_t *ref, const int32_t *dur, const double *thresholds, int64_t Q, const int32_t *min_clusters,
                    int64_t *counts, int32_t *n_clusters);
+
+/* ---- embedding chain (K18; csrc/embed.hip): what every x-vector / i-vector recipe runs between the extractor and a Gaussian
+ * PLDA -- Kaldi's ivector-subtract-global-mean | transform-vec | ivector-normalize-length, the VBx recipe's
+ * l2(LDA l2(x - m1) - m2).  All arithmetic fp64.  A chain is (Din, Dout, m_in, len_in, A, m_out, len_out); for a row x [Din]:
+ *   1. v = x - m_in                        m_in [Din], NULL = 0
+ *   2. if len_in > 0: v <- v len_in / |v|  (a row with |v| = 0 stays 0)
+ *   3. u = A v                             A [Dout, Din] row-major, NULL = identity (Dout == Din required)
+ *   4. u <- u - m_out                      m_out [Dout], NULL = 0
+ *   5. if len_out > 0: u <- u len_out / |u| (a zero row stays 0)
+ * and the output is u, fp64 [R, Dout].  Kaldi's recipes are (m_in, 0, A, -, sqrt(Dout)), VBx is (m1, 1, LDA, m2, 1), centre
+ * and normalise only is (m, 0, -, -, sqrt(D)).  The input is fp64 (dtype 0) or fp32 (dtype 1); fp32 is widened exactly at the
+ * load, so an fp32 array and its host-widened fp64 copy give the same output bits.  A non-finite input element makes its own
+ * output row non-finite and touches no other row; nothing is rejected on the device.  `out` must not overlap X.
+ * DETERMINISM: a row's output is a function of the row, the chain and the value of the input alone: the same bits from run to
+ * run, alone (R = 1) or at any position of any batch -- an enrolment vector embedded alone scores bit-identically to one
+ * embedded in a batch.  (How each class keeps the order of the k-sum and of both norm sums fixed: csrc/embed.hip.)  The rule
+ * holds per handle configuration: PLDA_EMBED_VARIANT selects another class, which rounds differently.
+ * Limits: 1 <= Din <= PLDA_EMBED_MAX_DIN, 1 <= Dout <= PLDA_EMBED_MAX_DOUT (the PLDA fit's own limit).
+ * Dispatch classes (plda_embed_plan): 0 = no A, one wave per row, one read and one write; 1 = A and Dout <= 512, one pass on
+ * v_mfma_f64_16x16x4_f64, a workgroup owns whole rows and all columns (K4's shape), A zero-padded once per chain; 2 = A and
+ * Dout > 512: row pass into handle scratch, the library's fp64 GEMM, row pass, in chunks of exactly 16 384 rows (at most
+ * 512 MiB + 256 MiB of scratch; the last chunk is padded with zero rows so that the GEMM's dispatch never depends on R).
+ * PLDA_EMBED_VARIANT=1 in the environment at plda_create forces class 2 for every chain with A (tests, the bench's A/B arm;
+ * any value but 0 / 1: PLDA_E_INVAL).  PLDA_EMBED_CUS=n (tests only; a whole number 1 ... 4096, anything else: PLDA_E_INVAL)
+ * sizes class 1's main / tail split for n compute units instead of the device's, so that a few hundred rows reach every block
+ * shape; by the determinism rule it changes no output bit.
+ * The C entry points of the model (plda_fit, plda_transform_rows, ...) never apply a chain implicitly.
+ *   plda_embed_set       installs a chain from HOST arrays (copied).  PLDA_E_INVAL before any device work, the installed chain
+ *                        untouched: a dimension outside its limit, A NULL with Dout != Din, a negative or non-finite len_*, a
+ *                        non-finite element of m_in, A or m_out.
+ *   plda_embed_clear     removes it.
+ *   plda_embed_dims      Din, Dout, flags (bit 0 m_in, 1 A, 2 m_out present); no chain: PLDA_E_NOT_FITTED.
+ *   plda_embed_get       the chain as it was set, bit for bit (host arrays; any NULL; absent parts are not written).
+ *   plda_embed_plan      out[0] = class, out[1] = rows per workgroup of the main launch (class 1: 128, 64 or 32; the tail launch
+ *                        halves that down to 16 until every compute unit has at most one block), out[2] = its LDS bytes.
+ *   plda_embed_apply_dev X [R, Din] of dtype and out [R, Dout] in HBM; enqueues on the handle's stream.  No chain:
+ *                        PLDA_E_NOT_FITTED; Din != the chain's, dtype not 0 / 1: PLDA_E_INVAL; R <= 0: nothing, PLDA_OK.
+ *   plda_embed_apply     the same with host arrays (one upload, one download).
+ *   plda_embed_fit_dev   estimates a chain from rows X [N, Din] and installs it.  m_in = the column mean of X (fp64, about a
+ *                        pilot row, fixed order); v_i = steps 1-2; mu = the mean of the v_i.  kind 0 "centre": A NULL, Dout =
+ *                        Din, m_out = mu.  kind 1 "whiten": C = (1/N) sum (v_i - mu)(v_i - mu)^T = Q L Q^T, L descending, row i
+ *                        of A = l_i^-1/2 q_i^T for i < Dout, m_out = A mu; l_{Dout-1} <= N Din 2^-53 l_0: PLDA_E_NUMERIC.  kind 2
+ *                        "lda" (labels dense 0 .. K-1): W = (1/N) sum_k sum_{i in k} (v_i - mu_k)(v_i - mu_k)^T, B = (1/N)
+ *                        sum_k n_k (mu_k - mu)(mu_k - mu)^T, A W A^T = I, A B A^T = diag(e), e the Dout largest generalised
+ *                        eigenvalues, descending, m_out = A mu; a singular W: PLDA_E_NUMERIC; K < 2: PLDA_E_INVAL.  Plain Fisher
+ *                        LDA: restated, parity unpinned against Kaldi's ivector-compute-lda.  eig (HOST, nullable) receives the
+ *                        Dout eigenvalues (l for kind 1, e for kind 2).  PLDA_E_INVAL before any device work: kind outside
+ *                        0 .. 2, Dout > Din for kinds 1 / 2 (kind 0: Dout != Din), Din > 2048 for kinds 1 / 2 (the eigensolver's
+ *                        limit; kind 0 takes every Din up to PLDA_EMBED_MAX_DIN), kind 2 without labels, N < 2, the errors
+ *                        of plda_embed_set.  An error leaves the installed chain bit-identical.  Scratch: all of v, N Din 8 bytes,
+ *                        plus O(Din^2 + K Din).
+ *   plda_embed_fit       the same with host arrays; K is found from the labels (max + 1).
+ * OUT OF SCOPE, each on purpose: Kaldi's per-recording PCA of ivector-plda-scoring-dense; fp32 or bf16 output; more than one
+ * matrix per chain; within-class covariance normalisation and a cosine back-end. ---- */
+#define PLDA_EMBED_MAX_DIN 4096
+#define PLDA_EMBED_MAX_DOUT 2048
+int plda_embed_set(plda_handle *h, int32_t Din, int32_t Dout, const double *m_in, double len_in, const double *A,
+                   const double *m_out, double len_out);
+int plda_embed_clear(plda_handle *h);
+int plda_embed_dims(plda_handle *h, int32_t *Din, int32_t *Dout, int32_t *flags);
+int plda_embed_get(plda_handle *h, double *m_in, double *len_in, double *A, double *m_out, double *len_out);
+int plda_embed_plan(plda_handle *h, int32_t Din, int32_t Dout, int32_t has_A, int32_t dtype, int32_t out[3]);
+int plda_embed_apply_dev(plda_handle *h, const void *dX, int32_t dtype, int64_t R, int32_t Din, double *dout);
+int plda_embed_apply(plda_handle *h, const void *X, int32_t dtype, int64_t R, int32_t Din, double *out);
+int plda_embed_fit_dev(plda_handle *h, const void *dX, int32_t dtype, int64_t N, int32_t Din, const uint64_t *dlabels, int64_t K,
+                       int32_t kind, int32_t Dout, double len_in, double len_out, double *eig);
+int plda_embed_fit(plda_handle *h, const void *X, int32_t dtype, int64_t N, int32_t Din, const uint64_t *labels, int32_t kind,
+                   int32_t Dout, double len_in, double len_out, double *eig);
 
 /* ---- LDA: replaces the reference's second model, the pure-Python
  * class LDA of python/liblda/lda.py (used by scoring/scoreLDA.py:175,224,241), on the same

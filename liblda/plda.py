@@ -110,6 +110,20 @@ class PLDA(object):
     def transform_array(self, xbar, num_examples=1):
         return self._instance.transform_array(xbar, num_examples)
 
+    def fit_embedding(self, x, y=None, kind="lda", dim=None, len_in=0.0, len_out=None):
+        """Estimate the embedding chain in front of the model (centre, length-normalise, LDA / whitening, re-centre,
+        length-normalise) from raw extractor output on the device and attach it; returns the plda_amd.embed.EmbeddingChain.
+        From then on fit / transform / norm / adapt / cluster / resegment / diarize take raw rows."""
+        return self._instance.fit_embedding(x, y, kind, dim, len_in, len_out)
+
+    def set_embedding(self, chain):
+        """Attach a plda_amd.embed.EmbeddingChain (None: remove it)."""
+        self._instance.set_embedding(chain)
+
+    def embed(self, x):
+        """The attached chain applied to rows x [R, Din] (fp32 or fp64) -> float64 [R, Dout]."""
+        return self._instance.embed(x)
+
     def save(self, path):
         return self._instance.save(path)
 

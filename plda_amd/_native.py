@@ -156,6 +156,15 @@ SIGNATURES = {
     "plda_vbx": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _f64, _f64, _f64, _f64, _i64, _f64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "plda_project_rows_dev": (C.c_int, [_vp, _vp, _i64, _i32, _vp]),
     "plda_project_rows": (C.c_int, [_vp, _vp, _i64, _i32, _vp]),
+    "plda_embed_set": (C.c_int, [_vp, _i32, _i32, _vp, _f64, _vp, _vp, _f64]),
+    "plda_embed_clear": (C.c_int, [_vp]),
+    "plda_embed_dims": (C.c_int, [_vp, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32)]),
+    "plda_embed_get": (C.c_int, [_vp, _vp, C.POINTER(_f64), _vp, _vp, C.POINTER(_f64)]),
+    "plda_embed_plan": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp]),
+    "plda_embed_apply_dev": (C.c_int, [_vp, _vp, _i32, _i64, _i32, _vp]),
+    "plda_embed_apply": (C.c_int, [_vp, _vp, _i32, _i64, _i32, _vp]),
+    "plda_embed_fit_dev": (C.c_int, [_vp, _vp, _i32, _i64, _i32, _vp, _i64, _i32, _i32, _f64, _f64, _vp]),
+    "plda_embed_fit": (C.c_int, [_vp, _vp, _i32, _i64, _i32, _vp, _i32, _i32, _f64, _f64, _vp]),
 }
 
 

@@ -17,7 +17,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 SO = os.path.join(LIBDIR, "libplda_hip.so")
 SO_DIAG = os.path.join(LIBDIR, "libplda_hip_diag.so")
-SOURCES = ["api.hip", "score.hip", "linalg.hip", "fit.hip", "frontend.hip", "eer.hip", "operand_slabs.hip", "lda.hip", "comm.hip", "eig_dc.hip", "hostio.hip", "transform.hip", "snorm.hip", "calib.hip", "dcf.hip", "topn.hip", "fusion.hip", "adapt.hip", "ahc.hip", "vbx.hip", "der.hip"]
+SOURCES = ["api.hip", "score.hip", "linalg.hip", "fit.hip", "frontend.hip", "eer.hip", "operand_slabs.hip", "lda.hip", "comm.hip", "eig_dc.hip", "hostio.hip", "transform.hip", "snorm.hip", "calib.hip", "dcf.hip", "topn.hip", "fusion.hip", "adapt.hip", "ahc.hip", "vbx.hip", "der.hip", "embed.hip"]
 HEADERS = [os.path.join(CSRC, "common.hpp"), os.path.join(CSRC, "trial_source.hpp"), os.path.join(CSRC, "hostio.hpp"), os.path.join(CSRC, "sweep_mfma.inc"), os.path.join(CSRC, "score_bt4.inc"), os.path.join(CSRC, "score_bf16x3.inc"), os.path.join(CSRC, "syrk_blk.inc"), os.path.join(HERE, "..", "include", "plda_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics",
          "-Wall", "-Wno-unused-function", "-Wno-unused-result"]
@@ -39,9 +39,12 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-ato
 # Its effect on speed has not been measured apart from the rest (scripts/fusion_bench.py times the kernels as built).
 # ahc.hip: the clustering is specified to the bit (tests/ahc_model.py): one fp64 addition and one fp64 division where the
 # contract names them, so nothing may be contracted into a fused multiply-add
+# embed.hip: a row's bits may not depend on the block shape or the input dtype's instantiation it runs in (the determinism rule
+# of the embedding chain): every fused multiply-add there is written as fma(), nothing else may be contracted
 EXTRA = {"score.hip": ["-mllvm", "-amdgpu-atomic-optimizer-strategy=None"],
          "fusion.hip": ["-mllvm", "-disable-machine-licm"],
-         "ahc.hip": ["-ffp-contract=off"]}
+         "ahc.hip": ["-ffp-contract=off"],
+         "embed.hip": ["-ffp-contract=off"]}
 
 
 def _stale(target, deps):

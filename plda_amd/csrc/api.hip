@@ -323,6 +323,23 @@ int plda_create(int device, plda_handle **out) {
       }
       h->transform_variant = std::atoi(v);
     }
+    if (const char *v = std::getenv("PLDA_EMBED_VARIANT")) {
+      if (*v && std::strcmp(v, "0") != 0 && std::strcmp(v, "1") != 0) {
+        delete h;
+        return fail(nullptr, PLDA_E_INVAL, "plda_create: PLDA_EMBED_VARIANT=%s (0: by shape, 1: row pass + GEMM + row pass always)", v);
+      }
+      h->embed_variant = std::atoi(v);
+    }
+    if (const char *v = std::getenv("PLDA_EMBED_CUS")) {
+      // tests only: the CU count the fused kernel's main / tail split is sized for; a whole number 1 ... 4096 (empty or 0: the device's)
+      char *end = nullptr;
+      const long n = std::strtol(v, &end, 10);
+      if (*v && (*end != 0 || n < 0 || n > 4096)) {
+        delete h;
+        return fail(nullptr, PLDA_E_INVAL, "plda_create: PLDA_EMBED_CUS=%s (a whole number 1 ... 4096; 0 or empty: the device's count)", v);
+      }
+      h->embed_cus = (int)n;
+    }
     if (const char *v = std::getenv("PLDA_SORT_VARIANT")) h->sort_variant = std::atoi(v);
     if (const char *v = std::getenv("PLDA_ZNORM_VARIANT")) h->znorm_variant = std::atoi(v);
     if (const char *v = std::getenv("PLDA_EER_VARIANT")) h->eer_variant = std::atoi(v);
@@ -2390,6 +2407,119 @@ int plda_project_rows(plda_handle *h, const double *X, int64_t R, int32_t Din, d
     PLDA_HIP(h, dO.alloc((size_t)R * h->Dout * 8));
     PLDA_TRY(project_rows_device(h, dX.as<double>(), R, Din, dO.as<double>()));
     return download(h, out, dO.p, (size_t)R * h->Dout * 8);
+  });
+}
+
+// ---------------------------------------------------------------- embedding chain (embed.hip)
+int plda_embed_set(plda_handle *h, int32_t Din, int32_t Dout, const double *m_in, double len_in, const double *A, const double *m_out,
+                   double len_out) {
+  return guarded(h, "plda_embed_set", [&]() -> int {
+    if (!h) return PLDA_E_INVAL;
+    PLDA_LOCK(h);
+    PLDA_TRY(set_device(h));
+    return embed_set(h, Din, Dout, m_in, len_in, A, m_out, len_out);
+  });
+}
+
+int plda_embed_clear(plda_handle *h) {
+  return guarded(h, "plda_embed_clear", [&]() -> int {
+    if (!h) return PLDA_E_INVAL;
+    PLDA_LOCK(h);
+    return embed_clear(h);
+  });
+}
+
+int plda_embed_dims(plda_handle *h, int32_t *Din, int32_t *Dout, int32_t *flags) {
+  return guarded(h, "plda_embed_dims", [&]() -> int {
+    if (!h) return PLDA_E_INVAL;
+    PLDA_LOCK(h);
+    if (!h->em_has) return fail(h, PLDA_E_NOT_FITTED, "embed_dims: no embedding chain is set");
+    if (Din) *Din = h->em_Din;
+    if (Dout) *Dout = h->em_Dout;
+    if (flags) *flags = (h->em_has_min ? 1 : 0) | (h->em_has_A ? 2 : 0) | (h->em_has_mout ? 4 : 0);
+    return PLDA_OK;
+  });
+}
+
+int plda_embed_get(plda_handle *h, double *m_in, double *len_in, double *A, double *m_out, double *len_out) {
+  return guarded(h, "plda_embed_get", [&]() -> int {
+    if (!h) return PLDA_E_INVAL;
+    PLDA_LOCK(h);
+    if (!h->em_has) return fail(h, PLDA_E_NOT_FITTED, "embed_get: no embedding chain is set");
+    if (m_in && h->em_has_min) std::memcpy(m_in, h->em_h_min.data(), h->em_h_min.size() * 8);
+    if (A && h->em_has_A) std::memcpy(A, h->em_h_A.data(), h->em_h_A.size() * 8);
+    if (m_out && h->em_has_mout) std::memcpy(m_out, h->em_h_mout.data(), h->em_h_mout.size() * 8);
+    if (len_in) *len_in = h->em_len_in;
+    if (len_out) *len_out = h->em_len_out;
+    return PLDA_OK;
+  });
+}
+
+int plda_embed_plan(plda_handle *h, int32_t Din, int32_t Dout, int32_t has_A, int32_t dtype, int32_t out[3]) {
+  return guarded(h, "plda_embed_plan", [&]() -> int {
+    if (!h) return PLDA_E_INVAL;
+    PLDA_LOCK(h);
+    return embed_plan(h, Din, Dout, has_A, dtype, out);
+  });
+}
+
+int plda_embed_apply_dev(plda_handle *h, const void *dX, int32_t dtype, int64_t R, int32_t Din, double *dout) {
+  return guarded(h, "plda_embed_apply_dev", [&]() -> int {
+    if (!h) return PLDA_E_INVAL;
+    PLDA_LOCK(h);
+    PLDA_TRY(set_device(h));
+    return embed_apply_device(h, dX, dtype, R, Din, dout);
+  });
+}
+
+int plda_embed_apply(plda_handle *h, const void *X, int32_t dtype, int64_t R, int32_t Din, double *out) {
+  return guarded(h, "plda_embed_apply", [&]() -> int {
+    if (!h) return PLDA_E_INVAL;
+    PLDA_LOCK(h);
+    if (!h->em_has) return fail(h, PLDA_E_NOT_FITTED, "embed_apply: no embedding chain is set");
+    if (dtype != 0 && dtype != 1) return fail(h, PLDA_E_INVAL, "embed_apply: dtype %d (0 fp64, 1 fp32)", (int)dtype);
+    if (Din != h->em_Din) return fail(h, PLDA_E_INVAL, "embed_apply: feature dim %d != the chain's input dim %d", (int)Din, h->em_Din);
+    if (R <= 0) return PLDA_OK;
+    if (!X || !out) return fail(h, PLDA_E_INVAL, "embed_apply: bad argument");
+    PLDA_TRY(set_device(h));
+    Tmp dX, dO;
+    PLDA_TRY(upload(h, dX, X, (size_t)R * Din * (dtype == 1 ? 4 : 8)));
+    PLDA_HIP(h, dO.alloc((size_t)R * h->em_Dout * 8));
+    PLDA_TRY(embed_apply_device(h, dX.p, dtype, R, Din, dO.as<double>()));
+    return download(h, out, dO.p, (size_t)R * h->em_Dout * 8);
+  });
+}
+
+int plda_embed_fit_dev(plda_handle *h, const void *dX, int32_t dtype, int64_t N, int32_t Din, const uint64_t *dlabels, int64_t K,
+                       int32_t kind, int32_t Dout, double len_in, double len_out, double *eig) {
+  return guarded(h, "plda_embed_fit_dev", [&]() -> int {
+    if (!h) return PLDA_E_INVAL;
+    PLDA_LOCK(h);
+    PLDA_TRY(embed_fit_validate(h, dtype, N, Din, dlabels != nullptr, K, kind, Dout, len_in, len_out));
+    PLDA_TRY(set_device(h));
+    return embed_fit_device(h, dX, dtype, N, Din, dlabels, K, kind, Dout, len_in, len_out, eig);
+  });
+}
+
+int plda_embed_fit(plda_handle *h, const void *X, int32_t dtype, int64_t N, int32_t Din, const uint64_t *labels, int32_t kind,
+                   int32_t Dout, double len_in, double len_out, double *eig) {
+  return guarded(h, "plda_embed_fit", [&]() -> int {
+    if (!h) return PLDA_E_INVAL;
+    PLDA_LOCK(h);
+    int64_t K = 0;
+    if (labels && kind == 2 && N > 0 && N < ((int64_t)1 << 31)) {
+      uint64_t mx = 0;
+      for (int64_t i = 0; i < N; ++i) mx = std::max(mx, labels[i]);
+      if (mx >= (uint64_t)N) return fail(h, PLDA_E_LABELS, "embed_fit: labels must be dense 0..K-1");
+      K = (int64_t)mx + 1;
+    }
+    PLDA_TRY(embed_fit_validate(h, dtype, N, Din, labels != nullptr, K, kind, Dout, len_in, len_out));
+    if (!X) return fail(h, PLDA_E_INVAL, "embed_fit: X is NULL");
+    PLDA_TRY(set_device(h));
+    Tmp dX, dL;
+    PLDA_TRY(upload(h, dX, X, (size_t)N * Din * (dtype == 1 ? 4 : 8)));
+    if (kind == 2) PLDA_TRY(upload(h, dL, labels, (size_t)N * 8));
+    return embed_fit_device(h, dX.p, dtype, N, Din, kind == 2 ? dL.as<uint64_t>() : nullptr, K, kind, Dout, len_in, len_out, eig);
   });
 }
 

@@ -306,6 +306,19 @@ struct plda_handle {
   plda::DevBuf der_tab;          // the launch table of a call (one entry per recording and threshold)
   plda::DevBuf der_stat;         // the call's two reject counters, its offsets and thresholds, then Sr, Sh / the prefix lengths
   int64_t der_scratch_bytes = 0; // PLDA_DER_SCRATCH_BYTES: the scratch one launch may take (0: 256 MiB)
+
+  // ---- embedding chain (embed.hip): host mirror (plda_embed_get returns it bit for bit) + device copies ----
+  bool em_has = false;
+  int em_Din = 0, em_Dout = 0, em_dinp = 0, em_class = 0;
+  bool em_has_min = false, em_has_A = false, em_has_mout = false;
+  double em_len_in = 0.0, em_len_out = 0.0;
+  std::vector<double> em_h_min, em_h_A, em_h_mout;
+  plda::DevBuf em_min, em_A, em_mout;
+  plda::DevBuf em_apad;          // A zero-padded for the fused kernel ([rows of the Dout class][Din rounded up to 16]), rebuilt by every set
+  plda::DevBuf em_v, em_g;       // class 2: one chunk of v and of A v
+  plda::DevBuf em_fit;           // plda_embed_fit*: all of v [N, Din], then the statistics
+  int embed_variant = 0;         // PLDA_EMBED_VARIANT=1: class 2 (row pass + GEMM + row pass) for every chain with A (A/B arm, tests)
+  int embed_cus = 0;             // PLDA_EMBED_CUS: the CU count the fused kernel's main / tail split is sized for (0: the device's; tests)
 };
 
 namespace plda {
@@ -452,6 +465,17 @@ int adapt_add_stats(plda_handle *h, double tw, int64_t rows, const double *pilot
 int adapt_update(plda_handle *h, double ws, double bs, double mds, double *eig, plda_adapt_info *info);
 int blend_model(plda_handle *h, int D, const double *mean2, const double *transform2, const double *psi2, double alpha,
                 double alpha_mean);
+
+// ---- embed.hip (the embedding chain in front of the model: centre, length-normalise, project, re-centre, length-normalise) ----
+int embed_plan(plda_handle *h, int Din, int Dout, int has_A, int dtype, int32_t *out);
+int embed_set(plda_handle *h, int Din, int Dout, const double *m_in, double len_in, const double *A, const double *m_out,
+              double len_out);   // HOST arrays
+int embed_clear(plda_handle *h);
+int embed_apply_device(plda_handle *h, const void *dX, int dtype, int64_t R, int Din, double *dout);
+int embed_fit_validate(plda_handle *h, int dtype, int64_t N, int Din, bool has_labels, int64_t K, int kind, int Dout, double len_in,
+                       double len_out);
+int embed_fit_device(plda_handle *h, const void *dX, int dtype, int64_t N, int Din, const uint64_t *dlabels, int64_t K, int kind,
+                     int Dout, double len_in, double len_out, double *eig);   // eig: HOST, nullable
 
 // ---- ahc.hip (speaker clustering: batched average-linkage AHC on score blocks; block_off / offsets / minc are HOST arrays) ----
 int ahc_plan(plda_handle *h, int64_t N, int32_t *out);

@@ -14,10 +14,11 @@ emission model, initialised from the clustering (csrc/vbx.hip; include/plda_hip.
 
 A recording is merged bottom-up while the best pair's average score is at least `threshold` (None: no threshold) and more than
 `num_speakers` clusters are left (None: 1).  Out of scope, on purpose: Kaldi's per-recording mean subtraction and PCA before
-scoring, its two-pass clustering of very long recordings; for VBx: length normalisation and the LDA fit before the model (the
-caller's business; plda_truncate plays the LDA dimension's role), more than 64 initial speakers, several workgroups on one
+scoring, its two-pass clustering of very long recordings; for VBx: more than 64 initial speakers, several workgroups on one
 recording, overlap handling.  The diarisation error rate, and the threshold sweep that cut() serves on the host, live in
-plda_amd/der.py; RTTM files in plda_amd/rttm.py.
+plda_amd/der.py; RTTM files in plda_amd/rttm.py.  Length normalisation and the LDA fit before the model are the embedding
+chain's (K18: plda_amd/embed.py, MPlda.fit_embedding / set_embedding): with one attached, cluster / resegment / diarize take
+the extractor's output as it is.
 """
 import ctypes as C
 

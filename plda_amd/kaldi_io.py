@@ -140,3 +140,66 @@ def read_plda(path):
     if transform.ndim != 2 or transform.shape[1] != mean.shape[0] or transform.shape[0] != psi.shape[0]:
         raise ValueError("Kaldi Plda file %s: inconsistent dimensions" % path)
     return mean, transform, psi
+
+
+# ---- single vectors and matrices (the files of ivector-mean, ivector-compute-lda, est-pca: mean.vec, transform.mat) ----
+# LAYOUT RESTATED, NOT PINNED, like read_plda above: "\0B" + FV / DV / FM / DM objects in binary mode, " [ v0 v1 ... ]\n"
+# and " [\n  a00 a01 ...\n  a10 ... ]\n" in text mode.  Host code only.
+def _text_rows(txt):
+    body = txt.strip()
+    if not body.startswith("[") or not body.endswith("]"):
+        raise ValueError("Kaldi text: expected [ ... ]")
+    rows = []
+    for line in body[1:-1].split("\n"):
+        vals = line.split()
+        if vals:
+            rows.append([float(v) for v in vals])
+    return rows
+
+
+def read_vector(path):
+    """-> float64 [dim] from a binary (FV / DV) or text Kaldi vector file."""
+    with open(path, "rb") as f:
+        raw = f.read()
+    if raw[:2] == b"\0B":
+        return _Bin(raw, 2).vector()
+    rows = _text_rows(raw.decode("ascii"))
+    return np.array(sum(rows, []), np.float64)
+
+
+def read_matrix(path):
+    """-> float64 [rows, cols] from a binary (FM / DM) or text Kaldi matrix file."""
+    with open(path, "rb") as f:
+        raw = f.read()
+    if raw[:2] == b"\0B":
+        return _Bin(raw, 2).matrix()
+    rows = _text_rows(raw.decode("ascii"))
+    if len(set(len(r) for r in rows)) > 1:
+        raise ValueError("Kaldi text matrix %s: rows of different lengths" % path)
+    return np.array(rows, np.float64).reshape(len(rows), len(rows[0]) if rows else 0)
+
+
+def write_vector(path, v, binary=True, single=False):
+    """Write a Kaldi vector: binary DV (single=True: FV, rounded to float32) or text."""
+    v = np.ascontiguousarray(v, np.float64).reshape(-1)
+    with open(path, "wb") as f:
+        if binary:
+            f.write(b"\0B" + (b"FV " if single else b"DV ") + _wint(v.shape[0]) + v.astype("<f4" if single else "<f8").tobytes())
+        else:
+            vals = v.astype(np.float32) if single else v
+            f.write((" [ " + " ".join(repr(float(x)) for x in vals) + " ]\n").encode("ascii"))
+
+
+def write_matrix(path, m, binary=True, single=False):
+    """Write a Kaldi matrix: binary DM (single=True: FM, rounded to float32) or text."""
+    m = np.ascontiguousarray(m, np.float64)
+    if m.ndim != 2:
+        raise ValueError("write_matrix: a 2-dimensional array is needed")
+    with open(path, "wb") as f:
+        if binary:
+            f.write(b"\0B" + (b"FM " if single else b"DM ") + _wint(m.shape[0]) + _wint(m.shape[1]) +
+                    m.astype("<f4" if single else "<f8").tobytes())
+        else:
+            vals = m.astype(np.float32) if single else m
+            rows = ["  " + " ".join(repr(float(x)) for x in r) for r in vals]
+            f.write((" [\n" + " \n".join(rows) + " ]\n").encode("ascii"))

@@ -140,6 +140,7 @@ class MPlda(object):
         self._meanz = {}
         self._stdvz = {}
         self._calibration = None      # plda_amd.calibration.Calibration of the last calibrate() / load()
+        self._embedding = None        # plda_amd.embed.EmbeddingChain in front of the raw-row methods (set_embedding / fit_embedding)
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -153,11 +154,119 @@ class MPlda(object):
     def _ck(self, rc):
         N.check(self._h, rc)
 
+    # ------------------------------------------------------------------ embedding chain (csrc/embed.hip)
+    def set_embedding(self, chain):
+        """Attach an EmbeddingChain (plda_amd/embed.py), or None to remove it.  While one is attached, the raw-row methods --
+        fit, transform, norm (its `vectors`), adapt, adapt_accumulate, cluster, resegment, diarize, project_rows,
+        tune_threshold -- pass their rows through it first, on the device: centre, length-normalise, project, re-centre,
+        length-normalise (K18).  The host-array methods go through the host entry point, which costs one extra PCIe round
+        trip (the embedded rows come back and go down again); callers with rows in HBM chain embed_dev into the _dev entry
+        points and never leave it.  The _dev methods never apply the chain themselves."""
+        if chain is None:
+            self._ck(self._lib.plda_embed_clear(self._h))
+            self._embedding = None
+            return
+        from .embed import EmbeddingChain
+        if not isinstance(chain, EmbeddingChain):
+            raise TypeError("set_embedding: an EmbeddingChain or None is needed, not %s" % type(chain).__name__)
+        self._ck(self._lib.plda_embed_set(self._h, chain.din, chain.dout, _ptr(chain.m_in), chain.len_in, _ptr(chain.A),
+                                          _ptr(chain.m_out), chain.len_out))
+        self._embedding = chain
+
+    @property
+    def embedding(self):
+        """The attached EmbeddingChain, or None."""
+        return self._embedding
+
+    def _read_embedding(self):
+        from .embed import EmbeddingChain
+        a, b, f = C.c_int32(), C.c_int32(), C.c_int32()
+        self._ck(self._lib.plda_embed_dims(self._h, C.byref(a), C.byref(b), C.byref(f)))
+        din, dout, flags = a.value, b.value, f.value
+        m_in = np.zeros(din) if flags & 1 else None
+        A = np.zeros((dout, din)) if flags & 2 else None
+        m_out = np.zeros(dout) if flags & 4 else None
+        li, lo = C.c_double(), C.c_double()
+        self._ck(self._lib.plda_embed_get(self._h, _ptr(m_in), C.byref(li), _ptr(A), _ptr(m_out), C.byref(lo)))
+        return EmbeddingChain(m_in, li.value, A, m_out, lo.value, dim=din)
+
+    def fit_embedding(self, x, y=None, kind="lda", dim=None, len_in=0.0, len_out=None):
+        """Estimate a chain from rows x [N, Din] on the device and attach it: m_in = the column mean, then kind "centre"
+        (m_out = the mean after the first length normalisation), "whiten" (A = the `dim` leading principal directions scaled
+        to unit variance) or "lda" (labels y; A W A^T = I, A B A^T diagonal, the `dim` leading directions).  dim None: Din;
+        len_out None: sqrt(dim).  fp32 rows go down as fp32.  Returns the EmbeddingChain; its `eig` holds the eigenvalues
+        (None for "centre").  On an error the attached chain stays as it was."""
+        from .embed import KINDS
+        if kind not in KINDS:
+            raise ValueError("fit_embedding: kind %r (one of %s)" % (kind, ", ".join(sorted(KINDS))))
+        X, dtype = self._embed_input(x)
+        n, d = X.shape
+        dim = d if dim is None else int(dim)
+        lo = float(np.sqrt(dim)) if len_out is None else float(len_out)
+        dense = None
+        if KINDS[kind] == 2:
+            if y is None:
+                raise ValueError("fit_embedding: kind 'lda' needs labels y")
+            dense, _ = _compact_labels(_labels(y, n))
+        eig = np.zeros(max(dim, 1))
+        self._ck(self._lib.plda_embed_fit(self._h, _ptr(X), dtype, n, d, _ptr(dense), KINDS[kind], dim, float(len_in), lo, _ptr(eig)))
+        chain = self._read_embedding()
+        chain.eig = eig[:dim].copy() if KINDS[kind] else None
+        self._embedding = chain
+        return chain
+
+    @staticmethod
+    def _embed_input(x):
+        if not isinstance(x, np.ndarray):
+            raise TypeError("argument 1 must be numpy.ndarray, not %s" % type(x).__name__)
+        if x.dtype.kind != "f":
+            raise ValueError(_ERR_X_FLOAT)
+        if x.ndim != 2:
+            raise ValueError("Input features must be 2-dimensional (nsamples, featdim)")
+        if x.dtype == np.float32:
+            return np.ascontiguousarray(x), 1            # fp32 goes down as fp32: the kernel widens it at the load
+        return np.ascontiguousarray(x, dtype=np.float64), 0
+
+    def embed(self, x):
+        """The attached chain applied to rows x [R, Din] (fp32 or fp64) -> float64 [R, Dout]."""
+        if self._embedding is None:
+            raise ValueError("embed: no embedding is set (set_embedding / fit_embedding)")
+        X, dtype = self._embed_input(x)
+        r, d = X.shape
+        if d != self._embedding.din:
+            raise ValueError("embed: rows have %d features, the embedding takes %d" % (d, self._embedding.din))
+        out = np.empty((r, self._embedding.dout), np.float64)
+        self._ck(self._lib.plda_embed_apply(self._h, _ptr(X), dtype, r, d, _ptr(out)))
+        return out
+
+    def embed_dev(self, dX, dtype, R, Din, dout):
+        """The same on HBM-resident rows (raw device addresses): dX [R, Din] of dtype (0 fp64, 1 fp32), dout fp64 [R, Dout]."""
+        self._ck(self._lib.plda_embed_apply_dev(self._h, C.c_void_p(int(dX)), int(dtype), int(R), int(Din), C.c_void_p(int(dout))))
+
+    def _embedded(self, x, X, check_model=True):
+        """The one hook of the raw-row methods: X (the float64 rows the method made of its argument x) as it is when no chain
+        is attached, else the chain applied to x (as fp32 if x is fp32)."""
+        chain = self._embedding
+        if chain is None:
+            return X
+        if check_model:
+            try:
+                din = self.dims()[1]
+            except N.PldaError:
+                din = None           # no model yet: the method's own call reports it
+            if din is not None and chain.dout != din:
+                raise ValueError("the embedding's output dimension %d is not the model's input dimension %d" % (chain.dout, din))
+        fp32 = isinstance(x, np.ndarray) and x.dtype == np.float32 and x.ndim == 2
+        return self.embed(x if fp32 else X)
+
+    def _rows(self, x, what="Input features", check_model=True):
+        return self._embedded(x, _features(x, what), check_model)
+
     # ------------------------------------------------------------------ fit
     def fit(self, x, y, iters=10):
         """MPlda_fit (pldamodule.cpp:42-109).  Returns None."""
         self._dout = None            # the model dimension may change
-        X = _features(x)
+        X = self._rows(x, check_model=False)
         n, d = X.shape
         Y = _labels(y, n)
         # the reference indexes a VLA by label value (:88-92, quirk Q2): labels must be
@@ -225,6 +334,12 @@ class MPlda(object):
         if self._calibration is not None:      # three more keys, only when a calibration is stored
             c = self._calibration
             extra = {"calib_a": np.float64(c.a), "calib_b": np.float64(c.b), "calib_prior": np.float64(c.prior)}
+        if self._embedding is not None:        # five more keys, only when a chain is attached; absent arrays are saved empty
+            e = self._embedding
+            none = np.zeros(0)
+            extra.update(embed_m_in=none if e.m_in is None else e.m_in, embed_len_in=np.float64(e.len_in),
+                         embed_A=np.zeros((0, e.din)) if e.A is None else e.A, embed_m_out=none if e.m_out is None else e.m_out,
+                         embed_len_out=np.float64(e.len_out))
         np.savez(_npz_path(path), mean=m["mean"], transform=m["transform"], psi=m["psi"], zn_ids=ids,
                  zn_mean=np.array([self._meanz[i] for i in ids], dtype=np.float64),
                  zn_std=np.array([self._stdvz[i] for i in ids], dtype=np.float64), **extra)
@@ -239,6 +354,13 @@ class MPlda(object):
         if "calib_a" in z.files:
             from .calibration import Calibration
             self._calibration = Calibration(float(z["calib_a"]), float(z["calib_b"]), float(z["calib_prior"]))
+        chain = None                # a file without the keys clears the chain, like the calibration
+        if "embed_A" in z.files:
+            from .embed import EmbeddingChain
+            A, m_in, m_out = z["embed_A"], z["embed_m_in"], z["embed_m_out"]
+            chain = EmbeddingChain(m_in if m_in.size else None, float(z["embed_len_in"]), A if A.size else None,
+                                   m_out if m_out.size else None, float(z["embed_len_out"]), dim=A.shape[1])
+        self.set_embedding(chain)
 
     def save_kaldi(self, path, binary=True):
         """Write the model as a Kaldi `Plda` file (plda_amd/kaldi_io.py: format restated, not pinned)."""
@@ -283,7 +405,7 @@ class MPlda(object):
         """Add the rows x [N, D] (weights [N] >= 0, None: 1) to the adaptation statistics: total weight, sum and second
         moments about the pilot (the model mean at the first accumulation after a reset).  The rows are read once, slab by
         slab.  A non-finite row or a bad weight raises and leaves the statistics as they were."""
-        X = _features(x)
+        X = self._rows(x)
         n, d = X.shape
         w = None
         if weights is not None:
@@ -372,6 +494,7 @@ class MPlda(object):
         X = np.ascontiguousarray(x, dtype=np.float64)
         if X.ndim != 2:
             raise ValueError("Input features must be 2-dimensional (nsamples, featdim)")
+        X = self._embedded(x, X)
         n, d = X.shape
         Y = _labels(y, n, allow_strings_msg=True)
         if targetdim and int(targetdim) != self.dims()[0]:
@@ -417,7 +540,7 @@ class MPlda(object):
         from . import diarize
         offsets = np.ascontiguousarray(offsets, np.int64)
         diarize.stop_args(offsets, threshold, num_speakers)     # (threshold=None without num_speakers: ValueError, before any work)
-        X = _features(x, "Segment vectors")
+        X = self._rows(x, "Segment vectors")
         if offsets.ndim != 1 or len(offsets) < 2 or X.shape[0] != int(offsets[-1]):
             raise ValueError("offsets must hold R + 1 >= 2 entries ending at the number of rows of x")
         return diarize.ahc_vectors(self, self.transform_array(X, 1), offsets, threshold, num_speakers, return_merges)
@@ -426,7 +549,9 @@ class MPlda(object):
     def project_rows(self, x):
         """transform . x + offset of every row of x [R, Din] -> [R, Dout]: TransformIvector without its normalisation factor,
         the space VBx works in."""
-        X = _features(x, "Segment vectors")
+        return self._project(self._rows(x, "Segment vectors"))
+
+    def _project(self, X):
         dout, _ = self.dims()
         out = np.zeros((X.shape[0], dout), np.float64)
         self._ck(self._lib.plda_project_rows(self._h, _ptr(X), X.shape[0], X.shape[1], _ptr(out)))
@@ -442,12 +567,12 @@ class MPlda(object):
         offsets[r+1], `labels` the initial labels (cluster()'s).  The rows are projected into the model's diagonalised space
         (project_rows), the between-class variance is the model's psi.  Returns (labels, n_clusters[, info])."""
         from . import diarize
-        X = _features(x, "Segment vectors")
+        X = self._rows(x, "Segment vectors")
         offsets = np.ascontiguousarray(offsets, np.int64)
         if offsets.ndim != 1 or len(offsets) < 2 or X.shape[0] != int(offsets[-1]):
             raise ValueError("offsets must hold R + 1 >= 2 entries ending at the number of rows of x")
         diarize.vbx_args(np.zeros((X.shape[0], 1)), offsets, labels, None, Fa, Fb, loop_prob, max_iters)   # (before any device work)
-        return diarize.vbx(self, self.project_rows(X), offsets, labels, None, Fa, Fb, loop_prob, init_smoothing, max_iters, epsilon,
+        return diarize.vbx(self, self._project(X), offsets, labels, None, Fa, Fb, loop_prob, init_smoothing, max_iters, epsilon,
                            return_posteriors)
 
     def diarize(self, x, offsets, threshold=0.0, num_speakers=None, **vbx):
@@ -503,13 +628,15 @@ class MPlda(object):
         (the best threshold -- the first of equal ones --, the plda_amd.der.SweepResult)."""
         from . import der
         offsets = np.ascontiguousarray(offsets, np.int64)
-        X = _features(x, "Segment vectors")
+        X = self._rows(x, "Segment vectors")
         if offsets.ndim != 1 or len(offsets) < 2 or X.shape[0] != int(offsets[-1]):
             raise ValueError("offsets must hold R + 1 >= 2 entries ending at the number of rows of x")
         t, r = int(offsets[-1]), len(offsets) - 1
         empty = (np.zeros(t - r, np.int32), np.zeros(t - r, np.int32), np.zeros(t - r))
         der.sweep_args(empty, offsets, ref, thresholds, dur, None)        # (before any device work)
-        _, _, merges = self.cluster(X, offsets, threshold=None, num_speakers=1, return_merges=True)
+        from . import diarize
+        diarize.stop_args(offsets, None, 1)
+        _, _, merges = diarize.ahc_vectors(self, self.transform_array(X, 1), offsets, None, 1, True)   # cluster() on embedded rows
         res = der.sweep(self, merges, offsets, ref, thresholds, dur)
         return float(res.thresholds[res.best]), res
 
@@ -539,7 +666,7 @@ class MPlda(object):
             raise TypeError("argument 1 must be numpy.ndarray, not %s" % type(vectors).__name__)
         if not isinstance(transformedvecs, dict):
             raise TypeError("argument 2 must be dict, not %s" % type(transformedvecs).__name__)
-        bkg = np.ascontiguousarray(vectors, np.float64)
+        bkg = self._embedded(vectors, np.ascontiguousarray(vectors, np.float64))
         nb, d = bkg.shape
         rows = bkg
         if numutts and int(numutts) < nb:
