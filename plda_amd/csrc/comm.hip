@@ -805,8 +805,8 @@ int fit_sharded_device(plda_handle *h, const double *dX, int64_t N, int D, const
   if (R == 1 || !h->comm) return fit_em_device(h, K, D, iters);
   const size_t DD = (size_t)D * D;
   // speaker counts of all ranks
-  PLDA_HIP(h, h->w[6].reserve((size_t)R * 8));
-  int64_t *dK = h->w[6].as<int64_t>();
+  PLDA_HIP(h, h->comm_counts.reserve((size_t)R * 8));
+  int64_t *dK = h->comm_counts.as<int64_t>();
   PLDA_HIP(h, hipMemcpyAsync(dK + me, &K, 8, hipMemcpyHostToDevice, h->stream));
   PLDA_COLL(h, h->coll.all_gather(h->coll.ctx, dK + me, dK, 8, h->stream), "all_gather");
   std::vector<int64_t> hK(R);
@@ -847,8 +847,8 @@ static int eer_comm_reduce(void *vctx, unsigned long long *hist, unsigned *below
   plda_handle *h = static_cast<EerCommCtx *>(vctx)->h;
   if (!h->comm || h->comm_nranks == 1) return 0;
   constexpr size_t NB = 2 * 2048;
-  if (h->w[7].reserve(NB * 8 + 64) != hipSuccess) return 1;
-  unsigned long long *d = h->w[7].as<unsigned long long>();
+  if (h->comm_hist.reserve(NB * 8 + 64) != hipSuccess) return 1;
+  unsigned long long *d = h->comm_hist.as<unsigned long long>();
   if (hist) {
     if (hipMemcpyAsync(d, hist, NB * 8, hipMemcpyHostToDevice, h->stream) != hipSuccess) return 1;
     if (h->coll.all_reduce(h->coll.ctx, d, (int64_t)NB, PLDA_DT_U64, PLDA_OP_SUM, h->stream) != 0) return 1;

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/plda_hip.h"
+#include "layout.hpp"
 
 // PLDA_DIAG=1 (plda_amd/build.py --diag -> libplda_hip_diag.so): the measurement arms of the trials GEMM -- bounding arms that
 // skip the operand DMA or the stores and return GARBAGE scores, per-wave clock stamps, stage-depth sweeps -- are compiled in and
@@ -141,6 +142,16 @@ struct plda_handle {
   int fit_D = 0;
   plda::DevBuf f_means, f_counts, f_scatter, f_sum, f_W, f_B;
   plda::DevBuf fit_flag;         // the EM's factorisation flag (read by export_model_kernel at the end of a fit)
+  // scratch of the statistics pass and the EM (fit.hip); the grouping's buffers also serve transform's and LDA's grouping
+  plda::DevBuf fit_sort;         // the grouping's row permutation, or the radix sort's keys a/b and values a/b
+  plda::DevBuf fit_offsets;      // class counts -> offsets [K + 1], then the label-check words (plda_fit: read back by the EM's planning copy)
+  plda::DevBuf fit_hist;         // per-chunk class counts -> bases, or the radix sort's digit histograms (+ the largest label)
+  plda::DevBuf fit_roww;         // one weight per row of the centroid kernels
+  plda::DevBuf fit_mu;           // the global mean, then the EM's scalars (alive until the fit's model export)
+  plda::DevBuf fit_csum;         // the class sum's partials per split
+  plda::DevBuf em_rows;          // the EM's K x D arrays (row form: the tile table first; its fragment loads over-read the last row)
+  plda::DevBuf em_mats;          // the EM's D x D matrices per group (or of the simultaneously-diagonalised arm) and the groups' counts
+  plda::DevBuf grp_pos, grp_uniq;   // group_by_label_device: boundary flags -> positions [N + 1]; the distinct labels
   double fit_ms[4] = {0, 0, 0, 0};
   hipEvent_t fit_ev[3] = {nullptr, nullptr, nullptr};   // EM start / end, statistics start on the stream (fit.hip)
   int *fit_dbad = nullptr;       // label-check flags of a statistics pass whose read-back fit_em_device takes over (plda_fit)
@@ -151,6 +162,7 @@ struct plda_handle {
   int lda_solver = 0, lda_D = 0, lda_rank = 0;
   int64_t lda_K = 0;
   plda::DevBuf l_means, l_priors, l_xbar, l_scalings, l_coef, l_intercept, l_evr;
+  plda::DevBuf lda_work;         // lda_fit_device's whole workspace (N x D and smaller); the offset row of lda_transform_device
 
   // ---- host-pointer entry points: pinned ring + copy threads (hostio.hip), two alternating score slabs ----
   plda::HostPipe *hostpipe = nullptr;
@@ -169,6 +181,9 @@ struct plda_handle {
   plda::DevBuf s_Apk, s_Bpk, s_rbias, s_rscale, s_cbias, s_rpair, s_cpair;
   plda::DevBuf s_A16, s_B16;   // the packed operands as three bf16 planes per k-oct (score_bf16x3.inc: opt-in arm)
   int score_dtype = 0;         // PLDA_SCORE_DTYPE=bf16x3 -> 1: the trials GEMM's contraction as three bf16 terms (opt-in; default fp32 MFMA)
+  plda::DevBuf host_flag;      // the 8 bytes a kernel leaves for the host: pairs_validate_device's first bad pair, test_side_fingerprint
+  plda::DevBuf pair_tab;       // score_pairs_device: the per-count tables, the mean's term and every model's bucket
+  plda::DevBuf zn_pilot_rows, zn_pilot_sums;   // z-norm by the pilot: the transformed block of test rows; column sums, squares and counts
   plda::DevBuf tf_pad;   // zero-padded copy of the transform for the one-pass K4 kernel, cached per model
   uint64_t tf_pad_epoch = ~0ull;
   int tf_pad_rows = 0, tf_pad_dinp = 0;
@@ -197,8 +212,14 @@ struct plda_handle {
   double *jac_G = nullptr, *jac_V = nullptr;
   int jac_D = 0;
   long jac_total_sweeps = 0;
+  plda::DevBuf jac_work;        // sym_eig_f64: V, A, the eigenvalues and the sweep counters (the sweep graph holds pointers into it)
+  // PERSISTENT between calls: the last simultaneous diagonalisation's whitening matrix, eigenvectors (the next call's
+  // warm start) and Cholesky flag (linalg.hip: SimdiagState; read back by simdiag_whitening / simdiag_flags / simdiag_finish)
+  plda::DevBuf simdiag_state;
   int simdiag_D = 0;
   bool simdiag_has_vr = false;
+  plda::DevBuf linalg_part;     // split-K and block partials of the fp64 products (linalg.hip, syrk_blk.inc)
+  plda::DevBuf syrk_wts;        // syrk_blk.inc: the row weights of both sources, padded
   bool eig_keep_sign = false;   // LDA: keep negative eigenvalues (PLDA floors them, Kaldi ApplyFloor)
 
   bool panel_attr_set[16] = {};
@@ -207,8 +228,11 @@ struct plda_handle {
   int transform_variant = 0;   // PLDA_TRANSFORM_VARIANT=1: GEMM + separate length-norm pass (the Dout > 512 path, forced)
   int gemm_variant = 0;
   int mixed_variant = 0;   // PLDA_MIXED_VARIANT=1: mixed enrol counts always in the depth-2D form [A1 | A2] x [V | V*V] (A/B arm of the bucketed form)
-  const double *gcoef_ptr = nullptr; uint64_t gcoef_epoch = 0; int gcoef_D = 0; plda::CountSet gcoef_set;   // bucket tables in w[11], same rule
-  const double *ucoef_ptr = nullptr; uint64_t ucoef_epoch = 0; int ucoef_n = 0, ucoef_D = 0;   // uniform-count coefficients in w[11] (score.hip: prepare_operands)
+  // PERSISTENT between calls: the scoring coefficient tables of the last call, uniform-count or bucketed (one buffer: a
+  // call that fills one form invalidates the other).  Valid while ucoef_* / gcoef_* match (score.hip: prepare_operands)
+  plda::DevBuf coef_cache;
+  const double *gcoef_ptr = nullptr; uint64_t gcoef_epoch = 0; int gcoef_D = 0; plda::CountSet gcoef_set;   // bucket tables in coef_cache, same rule
+  const double *ucoef_ptr = nullptr; uint64_t ucoef_epoch = 0; int ucoef_n = 0, ucoef_D = 0;   // uniform-count coefficients in coef_cache
   int prep_variant = 0;    // PLDA_PREP_VARIANT=1: scoring prep as separate bias / pack / pair kernels (A/B arm of prep_side_kernel)
   int gemm64_variant = 0;  // PLDA_GEMM64_VARIANT=1: fp64 GEMM always on 64 x 64 tiles (A/B arm)
   int jacobi_variant = 0;  // 0: Gram-form block Jacobi round; 1: rotation-by-rotation inner tournament
@@ -251,15 +275,17 @@ struct plda_handle {
   hipStream_t comm_stream = nullptr;
   hipEvent_t comm_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
   plda::DevBuf comm_mm, comm_mc;   // merged centroids / counts of a sharded fit (persistent: peers map them)
+  plda::DevBuf comm_counts;        // the speaker count of every rank of a sharded fit
+  plda::DevBuf comm_hist;          // the [2][2048] counters (or the two key bounds) of one all-reduce of a sharded EER / minDCF
 
-  // ---- general scratch (fit / transform / znorm) ----
-  plda::DevBuf w[16];
+  // ---- further scratch ----
   plda::DevBuf em_chunks;                       // the row-form EM's chunk table (device) ...
   std::vector<SyrkChunk> em_chunks_host;        // ... and its host copy, alive while the upload is in flight
   plda::DevBuf eigdc;            // eig_dc.hip workspace
   plda::DevBuf zn_rows, zn_y, zn_small, zn_cpad;   // z-norm statistics by moments (score.hip; zn_cpad: the padded covariance of the model pass, transform.hip)
   int znorm_variant = 0;         // PLDA_ZNORM_VARIANT=1: every LLR on the fused fp32 GEMM (A/B arm); 2: moments in five passes
   plda::DevBuf eer_slab, eer_smp; // plda_score_eer_dev: the row slab of scores in flight; the pilot's gathered enrol rows
+  plda::DevBuf trial_hist;       // eer.hip / dcf.hip: the two histograms of a labelled pass, then its window, DET or survivor output (one buffer: one such call runs at a time)
   plda::DevBuf eer_list[2];      // eer.hip, single-pass form: the impostor / target scores inside the pilot's key window
   int eer_variant = 0;           // PLDA_EER_VARIANT=1: always the three passes; 2: the single-pass form at every size (tests)
   int mindcf_variant = 0;        // PLDA_MINDCF_VARIANT=1: never compact the survivors into lists; 2: two nodes per read (dcf.hip; tests)
@@ -343,6 +369,18 @@ inline void note_kernels_clear(plda_handle *h) { h->linalg_kernels_len = 0; h->l
   } while (0)
 
 #define PLDA_LAUNCH_CHECK(h) PLDA_HIP(h, hipGetLastError())
+
+// Carves `buf` into the arrays of one list (layout.hpp): sizes the list, reserves, then runs it again for the pointers.
+// lay(Layout &) assigns the caller's pointers; they are valid until the next reserve of `buf`.
+template <typename F> int carve(plda_handle *h, DevBuf &buf, F &&lay) {
+  Layout size;
+  lay(size);
+  if (!size.ok) return fail(h, PLDA_E_INVAL, "scratch layout overflows size_t");
+  PLDA_HIP(h, buf.reserve(size.end));
+  Layout at{buf.as<char>()};
+  lay(at);
+  return PLDA_OK;
+}
 
 // RAII span of the trace: records an event on h->stream at construction and destruction (nothing when tracing is off;
 // never inside a stream capture).  `name` must be a string literal.

@@ -421,12 +421,10 @@ static int min_dcf_device(plda_handle *h, const TrialSource &src, int n_points, 
   plda_min_dcf_info info;
   std::memset(&info, 0, sizeof(info));
   PLDA_TRY(dcf_lds_attr(h));
-  const size_t hist_bytes = (size_t)DCF_S * 2 * EER_BINS * 8;
-  PLDA_HIP(h, h->w[10].reserve(hist_bytes + 256 + (size_t)DCF_CMAX * 4));
-  unsigned long long *dhist = h->w[10].as<unsigned long long>();
-  unsigned long long *dcursor = dhist + DCF_S * 2 * EER_BINS;                 // [2]
-  unsigned *dnb = reinterpret_cast<unsigned *>(dcursor + 2);                 // [2 P] neighbour words; (+ the EER's below / above at level 0)
-  unsigned *dprefix = reinterpret_cast<unsigned *>(dhist + DCF_S * 2 * EER_BINS + 32);
+  unsigned long long *dhist, *dcursor;
+  unsigned *dnb;         // [2 P] neighbour words; (+ the EER's below / above at level 0)
+  unsigned *dprefix;     // (256 bytes behind the histograms)
+  PLDA_TRY(carve(h, h->trial_hist, [&](Layout &c) { c.take(dhist, (size_t)DCF_S * 2 * EER_BINS).take(dcursor, 2).take(dnb, 2 * P).take(dprefix, DCF_CMAX, 256); }));
 
   int rc = PLDA_OK;
   // sums one [2][EER_BINS] block over the ranks; false: the call ends here, on every rank

@@ -299,9 +299,10 @@ bool reduce_block_or_poison(plda_handle *h, const TrialSource &src, const char *
 static int eer_device(plda_handle *h, const TrialSource &src, double *out, bool *window_missed = nullptr) {
   typedef unsigned __int128 u128;
   if (window_missed) *window_missed = false;
-  PLDA_HIP(h, h->w[10].reserve(2 * EER_BINS * 8 + 64));
-  unsigned long long *dhist = h->w[10].as<unsigned long long>();
-  unsigned *dbelow = reinterpret_cast<unsigned *>(dhist + 2 * EER_BINS), *dabove = dbelow + 1;
+  unsigned long long *dhist;
+  unsigned *dbelow;      // the nearest keys below / above the range: [2]
+  PLDA_TRY(carve(h, h->trial_hist, [&](Layout &c) { c.take(dhist, 2 * EER_BINS).take(dbelow, 2).slack(56); }));
+  unsigned *dabove = dbelow + 1;
   std::vector<unsigned long long> H;
   // g(k) >= 0  <=>  P(k) * Nn >= (Nn - N(k)) * Np  with P, N = #targets / #impostors with key <= k
   unsigned long long Np = 0, Nn = 0, Pb = 0, Nb = 0;   // totals; counts strictly below the current range
@@ -390,10 +391,11 @@ static int eer_matrix_windowed(plda_handle *h, const TrialSource &full, double *
   *done = false;
   const int64_t M = full.M, Nt = full.Nt;
   TraceScope ts(h, "eer.pilot");
-  PLDA_HIP(h, h->w[10].reserve(2 * EER_BINS * 8 + 64 + sizeof(EerWindowOut)));
-  unsigned long long *dhist = h->w[10].as<unsigned long long>();
-  unsigned *dbelow = reinterpret_cast<unsigned *>(dhist + 2 * EER_BINS), *dabove = dbelow + 1;
-  EerWindowOut *dwo = reinterpret_cast<EerWindowOut *>(dhist + 2 * EER_BINS + 8);
+  unsigned long long *dhist;
+  unsigned *dbelow;      // the nearest keys below / above the range: [2]
+  EerWindowOut *dwo;     // (a 64-byte line of its own)
+  PLDA_TRY(carve(h, h->trial_hist, [&](Layout &c) { c.take(dhist, 2 * EER_BINS).take(dbelow, 2).take(dwo, 1, 64); }));
+  unsigned *dabove = dbelow + 1;
   TrialSource smp = TrialSource::matrix(full.scores, full.ld, M, Nt, full.espk, full.tspk).every(EER_PILOT_STEP);
   int64_t pilot_step = EER_PILOT_STEP;
   if (full.kind == TrialSource::SLABS) {
@@ -590,10 +592,10 @@ __global__ __launch_bounds__(256) void det_hist_kernel(const float *__restrict__
 static int det_device(plda_handle *h, const TrialSource &src, int npoints, double *far, double *frr, double *thresholds) {
   if (npoints < 2 || npoints > DET_MAX) return fail(h, PLDA_E_INVAL, "det: 2 <= n_points <= %d", DET_MAX);
   const size_t hb = (size_t)2 * (DET_MAX + 1) * 8;
-  PLDA_HIP(h, h->w[10].reserve(hb + 64 + (size_t)DET_MAX * 8 + 64));
-  unsigned long long *dhist = h->w[10].as<unsigned long long>();
-  unsigned *dmm = reinterpret_cast<unsigned *>(dhist + 2 * (DET_MAX + 1));
-  double *dthr = reinterpret_cast<double *>(dmm + 16);
+  unsigned long long *dhist;
+  unsigned *dmm;         // the smallest and the largest key, in a 64-byte line
+  double *dthr;
+  PLDA_TRY(carve(h, h->trial_hist, [&](Layout &c) { c.take(dhist, 2 * (DET_MAX + 1)).take(dmm, 16).take(dthr, DET_MAX).slack(64); }));
   static const unsigned init[2] = {0xffffffffu, 0u};
   PLDA_HIP(h, hipMemcpyAsync(dmm, init, 8, hipMemcpyHostToDevice, h->stream));
   PLDA_TRY(for_each_piece(src, [&](const TrialPiece &pc) -> int {

@@ -589,7 +589,7 @@ int compute_offset_device(plda_handle *h) {
 }
 
 // Sort rows by label: outputs perm (row ids grouped by label, ascending row within label)
-// and offsets[K+1] in h->w[0], h->w[1].
+// and offsets[K+1] in h->fit_sort, h->fit_offsets.
 // defer_bad != nullptr: the range check is NOT read back here; *defer_bad receives the device flag (bit 0: a label
 // >= K; dense_check_kernel adds bit 1: an unused label, first one in [1]) for the caller to read with its own
 // synchronisation.  Everything enqueued after a failed check works on valid indices (garbage values only).
@@ -679,11 +679,11 @@ __global__ __launch_bounds__(256) void group_place_kernel(const uint64_t *__rest
 static int group_by_counting(plda_handle *h, const uint64_t *dlabels, int64_t N, int64_t K, uint32_t **perm_out,
                              int **offsets_out, int **defer_bad) {
   const int64_t nchunks = ceil_div(N, (int64_t)GR_CHUNK);
-  PLDA_HIP(h, h->w[0].reserve((size_t)N * 4));                              // perm
-  PLDA_HIP(h, h->w[1].reserve((size_t)(K + 3) * 4 + 64));                   // counts -> offsets (+ bad flag, first unused label)
-  PLDA_HIP(h, h->w[2].reserve((size_t)nchunks * K * 4));                    // per-chunk counts -> bases
-  uint32_t *perm = h->w[0].as<uint32_t>();
-  int *offsets = h->w[1].as<int>(), *bad = offsets + K + 1, *cnt = h->w[2].as<int>();
+  PLDA_HIP(h, h->fit_sort.reserve((size_t)N * 4));                          // perm
+  PLDA_HIP(h, h->fit_offsets.reserve((size_t)(K + 3) * 4 + 64));            // counts -> offsets (+ bad flag, first unused label)
+  PLDA_HIP(h, h->fit_hist.reserve((size_t)nchunks * K * 4));                // per-chunk counts -> bases
+  uint32_t *perm = h->fit_sort.as<uint32_t>();
+  int *offsets = h->fit_offsets.as<int>(), *bad = offsets + K + 1, *cnt = h->fit_hist.as<int>();
   PLDA_HIP(h, hipMemsetAsync(offsets, 0, (size_t)(K + 2) * 4, h->stream));
   PLDA_HIP(h, hipMemsetAsync(bad + 1, 0x7f, 4, h->stream));
   PLDA_HIP(h, hipMemsetAsync(cnt, 0, (size_t)nchunks * K * 4, h->stream));
@@ -708,6 +708,11 @@ static int group_by_counting(plda_handle *h, const uint64_t *dlabels, int64_t N,
   return PLDA_OK;
 }
 
+// the radix sort's two pairs of key / value arrays in h->fit_sort
+static int radix_buffers(plda_handle *h, int64_t N, uint32_t **ka, uint32_t **va, uint32_t **kb, uint32_t **vb) {
+  return carve(h, h->fit_sort, [&](Layout &c) { c.take(*ka, N).take(*va, N).take(*kb, N).take(*vb, N); });
+}
+
 static int sort_by_label(plda_handle *h, const uint64_t *dlabels, int64_t N, int64_t K, uint32_t **perm_out,
                          int **offsets_out, int **defer_bad = nullptr) {
   if (N >= (1ll << 31)) return fail(h, PLDA_E_INVAL, "fit: N too large");
@@ -715,13 +720,13 @@ static int sort_by_label(plda_handle *h, const uint64_t *dlabels, int64_t N, int
   if (defer_bad && K <= GR_KMAX && ceil_div(N, (int64_t)GR_CHUNK) * K <= (64ll << 20) && h->sort_variant == 0)
     return group_by_counting(h, dlabels, N, K, perm_out, offsets_out, defer_bad);
   const int nblocks = (int)ceil_div(N, RS_CHUNK);
-  PLDA_HIP(h, h->w[0].reserve((size_t)N * 4 * 4));                  // keys a/b, vals a/b
-  PLDA_HIP(h, h->w[1].reserve((size_t)(K + 3) * 4 + 64));          // counts -> offsets (+ bad flag, first unused label)
-  PLDA_HIP(h, h->w[2].reserve((size_t)256 * nblocks * 4));          // digit histograms
-  uint32_t *ka = h->w[0].as<uint32_t>(), *va = ka + N, *kb = va + N, *vb = kb + N;
-  int *offsets = h->w[1].as<int>();
+  uint32_t *ka, *va, *kb, *vb;
+  PLDA_TRY(radix_buffers(h, N, &ka, &va, &kb, &vb));
+  PLDA_HIP(h, h->fit_offsets.reserve((size_t)(K + 3) * 4 + 64));   // counts -> offsets (+ bad flag, first unused label)
+  PLDA_HIP(h, h->fit_hist.reserve((size_t)256 * nblocks * 4));      // digit histograms
+  int *offsets = h->fit_offsets.as<int>();
   int *bad = offsets + K + 1;
-  int *hist = h->w[2].as<int>();
+  int *hist = h->fit_hist.as<int>();
   PLDA_HIP(h, hipMemsetAsync(offsets, 0, (size_t)(K + 2) * 4, h->stream));
   PLDA_HIP(h, hipMemsetAsync(bad + 1, 0x7f, 4, h->stream));
   labels_check_kernel<<<(unsigned)ceil_div(N, 256), 256, 0, h->stream>>>(dlabels, N, K, ka, va, offsets, bad);
@@ -783,10 +788,10 @@ int fit_stats_device(plda_handle *h, const double *dX, int64_t N, int D, const u
   PLDA_HIP(h, h->f_means.reserve((size_t)K * D * 8));
   PLDA_HIP(h, h->f_counts.reserve((size_t)K * 8));
   PLDA_HIP(h, h->f_scatter.reserve(DD * 8));
-  PLDA_HIP(h, h->w[3].reserve((size_t)N * 8));               // row weights
+  PLDA_HIP(h, h->fit_roww.reserve((size_t)N * 8));           // row weights
   double *means = h->f_means.as<double>();
   double *S = h->f_scatter.as<double>();
-  double *roww = h->w[3].as<double>();
+  double *roww = h->fit_roww.as<double>();
   counts_to_i64_kernel<<<(unsigned)ceil_div(K, 256), 256, 0, h->stream>>>(offsets, K, h->f_counts.as<int64_t>());
   {
     TraceScope ts(h, "fit.centroids (K1)", (double)N * D * 8.0, 2);
@@ -876,15 +881,14 @@ int fit_em_device(plda_handle *h, int64_t K, int D, int iters) {
   PLDA_HIP(h, h->f_sum.reserve((size_t)D * 8));
   PLDA_HIP(h, h->f_W.reserve(DD * 8));
   PLDA_HIP(h, h->f_B.reserve(DD * 8));
-  PLDA_HIP(h, h->w[1].reserve((size_t)(K + 2) * 4 + 64));
-  PLDA_HIP(h, h->w[4].reserve((size_t)D * 8 * 2 + 64));       // mu, scalars
+  PLDA_HIP(h, h->fit_offsets.reserve((size_t)(K + 2) * 4 + 64));
+  double *mu, *scalars;
+  PLDA_TRY(carve(h, h->fit_mu, [&](Layout &c) { c.take(mu, D).take(scalars, D).slack(64); }));
   double *means = h->f_means.as<double>();
   double *S = h->f_scatter.as<double>();
   double *sum = h->f_sum.as<double>();
   double *W = h->f_W.as<double>(), *B = h->f_B.as<double>();
-  double *mu = h->w[4].as<double>();
-  double *scalars = mu + D;
-  int *offsets = h->w[1].as<int>();
+  int *offsets = h->fit_offsets.as<int>();
   char *const pin_plan = static_cast<char *>(h->pin_model) + pin_model_bytes;
   int64_t *const hcounts = reinterpret_cast<int64_t *>(pin_plan);                      // [K]
   double *const pin_gn = reinterpret_cast<double *>(pin_plan + (size_t)K * 8);         // [<= K]
@@ -905,9 +909,9 @@ int fit_em_device(plda_handle *h, int64_t K, int D, int iters) {
                                                                                 offsets, bad);
   scan_kernel<<<1, 1024, 0, h->stream>>>(offsets, K + 1);
   PLDA_LAUNCH_CHECK(h);
-  PLDA_HIP(h, h->w[7].reserve((size_t)CS_SPLIT * (D + 1) * 8));
   {
-    double *partial = h->w[7].as<double>(), *wpart = partial + (size_t)CS_SPLIT * D;
+    double *partial, *wpart;
+    PLDA_TRY(carve(h, h->fit_csum, [&](Layout &c) { c.take(partial, (size_t)CS_SPLIT * D).take(wpart, CS_SPLIT); }));
     class_sum_partial_kernel<<<dim3((unsigned)ceil_div(D, 64), CS_SPLIT), 256, 0, h->stream>>>(means, offsets, K, D,
                                                                                               partial, wpart);
     class_sum_final_kernel<<<(unsigned)ceil_div(D, 256), 256, 0, h->stream>>>(partial, wpart, D, sum, mu, scalars);
@@ -979,14 +983,15 @@ int fit_em_device(plda_handle *h, int64_t K, int D, int iters) {
     for (int g = 0; g < G; ++g)
       for (int64_t r = goff[g]; r < goff[g + 1]; r += 16 * RB)
         pin_tiles[ntiles++] = make_int4((int)r, (int)std::min<int64_t>(16 * RB, goff[g + 1] - r), g, 0);
-    PLDA_HIP(h, h->w[5].reserve((size_t)K * D * 8 * 3 + (size_t)K * 4 + ntiles * 16 + 64));
-    PLDA_HIP(h, h->w[6].reserve((size_t)G * DD * 8 * 5 + DD * 8 * 3 + (size_t)G * 16 + (size_t)GD * 16 + 64));
-    // (the int4 tile table first: behind the three K x D arrays it would be only 8-byte aligned when K D is odd)
-    int4 *dtiles = h->w[5].as<int4>();
-    double *Mg = reinterpret_cast<double *>(dtiles + ntiles), *Zr = Mg + (size_t)K * D, *Wn = Zr + (size_t)K * D;
-    int *dcls = reinterpret_cast<int *>(Wn + (size_t)K * D);
-    double *Tg = h->w[6].as<double>(), *Xg = Tg + (size_t)G * DD, *scr = Xg + (size_t)G * DD, *P1 = scr + 3 * (size_t)G * DD,
-           *P2 = P1 + DD, *Balt = P2 + DD, *dgn = Balt + DD, *dgk = dgn + G, *kw1 = dgk + G, *kw2 = kw1 + GD;
+    const size_t KD = (size_t)K * D, GDD = (size_t)G * DD;
+    int4 *dtiles;
+    double *Mg, *Zr, *Wn, *Tg, *Xg, *scr, *P1, *P2, *Balt, *dgn, *dgk, *kw1, *kw2;
+    int *dcls;
+    // (the tile table first, as it always lay; the fragment loads of Mg / Zr / Wn over-read their last rows into what follows)
+    PLDA_TRY(carve(h, h->em_rows, [&](Layout &c) { c.take(dtiles, ntiles).take(Mg, KD).take(Zr, KD).take(Wn, KD).take(dcls, K).slack(64); }));
+    PLDA_TRY(carve(h, h->em_mats, [&](Layout &c) {
+      c.take(Tg, GDD).take(Xg, GDD).take(scr, 3 * GDD).take(P1, DD).take(P2, DD).take(Balt, DD).take(dgn, G).take(dgk, G).take(kw1, GD).take(kw2, GD).slack(64);
+    }));
     int *dflag = h->fit_flag.as<int>();          // (its own buffer: the export kernel that ends the fit reads it)
     std::copy(gn.begin(), gn.end(), pin_gn);
     std::copy(gk.begin(), gk.end(), pin_gk);
@@ -1067,13 +1072,15 @@ int fit_em_device(plda_handle *h, int64_t K, int D, int iters) {
     if (Bcur != B) PLDA_HIP(h, hipMemcpyAsync(B, Bcur, DD * 8, hipMemcpyDeviceToDevice, h->stream));   // (the M-step alternates two buffers)
   } else if (grouped) {
     // ---- moment form (header of em_moment_mstep_kernel) ----
-    PLDA_HIP(h, h->w[5].reserve((size_t)K * D * 8 + (size_t)K * 4 + 64));
-    PLDA_HIP(h, h->w[6].reserve(group_bytes + DD * 8 + (size_t)G * 16 + 64));
-    double *Mg = h->w[5].as<double>();
-    int *dcls = reinterpret_cast<int *>(Mg + (size_t)K * D);
     const size_t GDD = (size_t)G * DD;
-    double *Cg = h->w[6].as<double>(), *Tg = Cg + GDD, *Xg = Tg + GDD, *P1 = Xg + GDD, *P2 = P1 + GDD, *QC = P2 + GDD, *XtX = QC + GDD,
-           *Rg = XtX + GDD, *QCQ = Rg + GDD, *Csum = QCQ + GDD, *dgn = Csum + DD, *dgk = dgn + G;
+    double *Mg, *Cg, *Tg, *Xg, *P1, *scr, *Rg, *QCQ, *Csum, *dgn, *dgk;
+    int *dcls;
+    PLDA_TRY(carve(h, h->em_rows, [&](Layout &c) { c.take(Mg, (size_t)K * D).take(dcls, K).slack(64); }));
+    // (scr: P2 | QC | XtX, one array -- dead between iterations, the whitening's 3 G D^2 of scratch)
+    PLDA_TRY(carve(h, h->em_mats, [&](Layout &c) {
+      c.take(Cg, GDD).take(Tg, GDD).take(Xg, GDD).take(P1, GDD).take(scr, 3 * GDD).take(Rg, GDD).take(QCQ, GDD).take(Csum, DD).take(dgn, G).take(dgk, G).slack(64);
+    }));
+    double *P2 = scr, *QC = P2 + GDD, *XtX = QC + GDD;
     int *dflag = h->fit_flag.as<int>();          // (its own buffer: the export kernel that ends the fit reads it)
     std::copy(gn.begin(), gn.end(), pin_gn);
     std::copy(gk.begin(), gk.end(), pin_gk);
@@ -1091,7 +1098,7 @@ int fit_em_device(plda_handle *h, int64_t K, int D, int iters) {
     const int64_t sDD = (int64_t)DD;
     for (int it = 0; it < iters; ++it) {
       if (it == 0) em_first_T_kernel<<<dim3(gDD, G), 256, 0, h->stream>>>(dgn, D, sDD, Tg);
-      else PLDA_TRY(whiten_groups_f64(h, W, B, dgn, D, Tg, P2 /* 3 G D^2 of scratch: P2 | QC | XtX, dead between iterations */, dflag, G));
+      else PLDA_TRY(whiten_groups_f64(h, W, B, dgn, D, Tg, scr, dflag, G));
       PLDA_LAUNCH_CHECK(h);
       // (A(m, k) = A[m sam + k sak], B(k, n) = B[k sbk + n sbn])
       const GemmSet s1[2] = {{Tg, D, 1, sDD, B, D, 1, 0, Xg, D, sDD},            // X  = T B
@@ -1112,11 +1119,10 @@ int fit_em_device(plda_handle *h, int64_t K, int D, int iters) {
     // synchronisation left the GPU idle for ~45 us before GetOutput's first kernel).  A failed factorisation hands
     // GetOutput non-finite matrices, which its kernels refuse at once; the error reported is this one.
   } else {
-  PLDA_HIP(h, h->w[5].reserve((size_t)K * D * 8 * 3));   // Mc / P, Y1, Y2
-  PLDA_HIP(h, h->w[6].reserve(DD * 8 * 7 + (size_t)D * 8));
-  double *Mc = h->w[5].as<double>(), *Y1 = Mc + (size_t)K * D, *Y2 = Y1 + (size_t)K * D;
-  double *T = h->w[6].as<double>(), *Tinv = T + DD, *Bt = Tinv + DD, *Wt = Bt + DD, *tmp = Wt + DD,
-         *Bu = tmp + DD, *Wu = Bu + DD, *psi = Wu + DD;
+  const size_t KD = (size_t)K * D;
+  double *Mc, *Y1, *Y2, *T, *Tinv, *Bt, *Wt, *tmp, *Bu, *Wu, *psi;      // (Mc also holds P)
+  PLDA_TRY(carve(h, h->em_rows, [&](Layout &c) { c.take(Mc, KD).take(Y1, KD).take(Y2, KD); }));
+  PLDA_TRY(carve(h, h->em_mats, [&](Layout &c) { c.take(T, DD).take(Tinv, DD).take(Bt, DD).take(Wt, DD).take(tmp, DD).take(Bu, DD).take(Wu, DD).take(psi, D); }));
   center_kernel<<<gKD, 256, 0, h->stream>>>(means, mu, K, D, Mc);
   PLDA_LAUNCH_CHECK(h);
   for (int it = 0; it < iters; ++it) {
@@ -1256,13 +1262,13 @@ int group_by_label_device(plda_handle *h, const uint64_t *dlabels, int64_t N, ui
                           uint64_t **uniq_out, int64_t *G_out) {
   if (N >= (1ll << 31)) return fail(h, PLDA_E_INVAL, "transform: N too large");
   const int nblocks = (int)ceil_div(N, RS_CHUNK);
-  PLDA_HIP(h, h->w[0].reserve((size_t)N * 4 * 4));                  // keys a/b, vals a/b
-  PLDA_HIP(h, h->w[2].reserve((size_t)256 * nblocks * 4 + 16));     // digit histograms (+ max label)
-  PLDA_HIP(h, h->w[4].reserve((size_t)(N + 2) * 4));                // boundary flags -> positions
-  uint32_t *ka = h->w[0].as<uint32_t>(), *va = ka + N, *kb = va + N, *vb = kb + N;
-  int *hist = h->w[2].as<int>();
-  unsigned long long *dmax = reinterpret_cast<unsigned long long *>(hist + (size_t)256 * nblocks + (((size_t)256 * nblocks) & 1));
-  int *pos = h->w[4].as<int>();
+  uint32_t *ka, *va, *kb, *vb;
+  PLDA_TRY(radix_buffers(h, N, &ka, &va, &kb, &vb));
+  int *hist;
+  unsigned long long *dmax;
+  PLDA_TRY(carve(h, h->fit_hist, [&](Layout &c) { c.take(hist, (size_t)256 * nblocks).take(dmax, 1); }));   // digit histograms, max label
+  PLDA_HIP(h, h->grp_pos.reserve((size_t)(N + 2) * 4));             // boundary flags -> positions
+  int *pos = h->grp_pos.as<int>();
   PLDA_HIP(h, hipMemsetAsync(dmax, 0, 8, h->stream));
   labels_split_kernel<<<(unsigned)ceil_div(N, 256), 256, 0, h->stream>>>(dlabels, N, ka, va, dmax);
   PLDA_LAUNCH_CHECK(h);
@@ -1295,10 +1301,10 @@ int group_by_label_device(plda_handle *h, const uint64_t *dlabels, int64_t N, ui
   PLDA_HIP(h, hipMemcpyAsync(&hG, pos + N, 4, hipMemcpyDeviceToHost, h->stream));
   PLDA_HIP(h, hipStreamSynchronize(h->stream));
   const int64_t G = hG;
-  PLDA_HIP(h, h->w[1].reserve((size_t)(G + 2) * 4 + 64));
-  PLDA_HIP(h, h->w[5].reserve((size_t)G * 8));
-  int *offsets = h->w[1].as<int>();
-  uint64_t *uniq = h->w[5].as<uint64_t>();
+  PLDA_HIP(h, h->fit_offsets.reserve((size_t)(G + 2) * 4 + 64));
+  PLDA_HIP(h, h->grp_uniq.reserve((size_t)G * 8));
+  int *offsets = h->fit_offsets.as<int>();
+  uint64_t *uniq = h->grp_uniq.as<uint64_t>();
   group_emit_kernel<<<(unsigned)ceil_div(N + 1, 256), 256, 0, h->stream>>>(dlabels, va, pos, N, uniq, offsets);
   PLDA_LAUNCH_CHECK(h);
   *perm_out = va; *offsets_out = offsets; *uniq_out = uniq; *G_out = G;
@@ -1308,8 +1314,8 @@ int group_by_label_device(plda_handle *h, const uint64_t *dlabels, int64_t N, ui
 // per-label means of already grouped rows (pldamodule.cpp:147-168)
 int group_centroids_device(plda_handle *h, const double *dX, int64_t N, int D, const uint32_t *perm, const int *offsets,
                            int64_t G, double *dmeans, int32_t *dcounts32) {
-  PLDA_HIP(h, h->w[3].reserve((size_t)N * 8));
-  centroid_kernel<false><<<(unsigned)G, 256, 0, h->stream>>>(dX, D, perm, offsets, dmeans, h->w[3].as<double>());
+  PLDA_HIP(h, h->fit_roww.reserve((size_t)N * 8));
+  centroid_kernel<false><<<(unsigned)G, 256, 0, h->stream>>>(dX, D, perm, offsets, dmeans, h->fit_roww.as<double>());
   PLDA_LAUNCH_CHECK(h);
   counts_to_i32_kernel<<<(unsigned)ceil_div(G, 256), 256, 0, h->stream>>>(offsets, G, dcounts32);
   PLDA_LAUNCH_CHECK(h);
@@ -1321,8 +1327,8 @@ int group_means_device(plda_handle *h, const double *dX, int64_t N, int D, const
   uint32_t *perm = nullptr;
   int *offsets = nullptr;
   PLDA_TRY(sort_by_label(h, ddense, N, Ku, &perm, &offsets));
-  PLDA_HIP(h, h->w[3].reserve((size_t)N * 8));
-  centroid_kernel<true><<<(unsigned)Ku, 256, 0, h->stream>>>(dX, D, perm, offsets, dmeans, h->w[3].as<double>());
+  PLDA_HIP(h, h->fit_roww.reserve((size_t)N * 8));
+  centroid_kernel<true><<<(unsigned)Ku, 256, 0, h->stream>>>(dX, D, perm, offsets, dmeans, h->fit_roww.as<double>());
   PLDA_LAUNCH_CHECK(h);
   counts_to_i32_kernel<<<(unsigned)ceil_div(Ku, 256), 256, 0, h->stream>>>(offsets, Ku, dcounts32);
   PLDA_LAUNCH_CHECK(h);

@@ -240,15 +240,13 @@ int lda_fit_device(plda_handle *h, const double *dX, int64_t N, int D, const uin
          *intercept = h->l_intercept.as<double>();
 
   // ---- class means and counts (the PLDA K1a/K1 kernels) ----
-  // scratch: [counts32 K][cw K][rw N][S DD][G DD][Vr DD][lam D][std D][mu D][Mc K*D][tmp K*D][small DD*2][Xc N*D]
-  const size_t bytes = (size_t)K * 4 + 64 + (size_t)K * 8 + (size_t)N * 8 + DD * 8 * 5 + (size_t)D * 8 * 3 +
-                       (size_t)K * D * 8 * 2 + (size_t)N * D * 8 + 256;
-  PLDA_HIP(h, h->w[12].reserve(bytes));
-  char *base = h->w[12].as<char>();
-  int32_t *dcounts = reinterpret_cast<int32_t *>(base);
-  double *cw = reinterpret_cast<double *>(base + round_up((int64_t)K * 4, 64));
-  double *rw = cw + K, *S = rw + N, *G = S + DD, *Vr = G + DD, *lam = Vr + DD, *std = lam + D,
-         *mu = std + D, *Mc = mu + D, *tmp = Mc + (size_t)K * D, *sm1 = tmp + (size_t)K * D, *sm2 = sm1 + DD, *Xc = sm2 + DD;
+  const size_t KD = (size_t)K * D;
+  int32_t *dcounts;
+  double *cw, *rw, *S, *G, *Vr, *lam, *std, *mu, *Mc, *tmp, *sm1, *sm2, *Xc;
+  PLDA_TRY(carve(h, h->lda_work, [&](Layout &c) {
+    c.take(dcounts, K).take(cw, K, 64).take(rw, N).take(S, DD).take(G, DD).take(Vr, DD).take(lam, D).take(std, D).take(mu, D);
+    c.take(Mc, KD).take(tmp, KD).take(sm1, DD).take(sm2, DD).take(Xc, (size_t)N * D).slack(256);
+  }));
   PLDA_TRY(group_means_device(h, dX, N, D, dlabels, K, means, dcounts));
   std::vector<int32_t> hc((size_t)K);
   PLDA_HIP(h, hipMemcpyAsync(hc.data(), dcounts, (size_t)K * 4, hipMemcpyDeviceToHost, h->stream));
@@ -408,8 +406,8 @@ int lda_transform_device(plda_handle *h, const double *dX, int64_t N, int ncomp,
   const double *sc = h->l_scalings.as<double>();
   PLDA_TRY(gemm_f64(h, N, ncomp, D, 1.0, dX, D, 1, sc, R, 1, nullptr, 0.0, dout, ncomp));
   if (h->lda_solver == LDA_SVD) {
-    PLDA_HIP(h, h->w[12].reserve((size_t)ncomp * 8));
-    double *off = h->w[12].as<double>();
+    PLDA_HIP(h, h->lda_work.reserve((size_t)ncomp * 8));
+    double *off = h->lda_work.as<double>();
     PLDA_TRY(gemm_f64(h, 1, ncomp, D, 1.0, h->l_xbar.as<double>(), D, 1, sc, R, 1, nullptr, 0.0, off, ncomp));
     lda_sub_rowvec_kernel<<<blocks(N * (int64_t)ncomp), 256, 0, h->stream>>>(dout, off, N, ncomp);
     PLDA_LAUNCH_CHECK(h);

@@ -692,8 +692,8 @@ int em_rank_sums_mstep_f64(plda_handle *h, int D, const SyrkChunk *chunks, int n
   *used = false;
   if (D > TRI_NT * 16 || !(h->gemm64_variant == 0 || h->gemm64_variant == 6) || nchunks < 1) return PLDA_OK;
   const int nt = (int)ceil_div(D, 16), ntri = nt * (nt + 1) / 2;
-  PLDA_HIP(h, h->w[15].reserve((size_t)nchunks * ntri * 256 * 8));
-  double *part = h->w[15].as<double>();
+  PLDA_HIP(h, h->linalg_part.reserve((size_t)nchunks * ntri * 256 * 8));
+  double *part = h->linalg_part.as<double>();
   note_kernel(h, "syrk_tri_kernel");
   syrk_tri_kernel<false><<<(unsigned)nchunks, 512, 0, h->stream>>>(D, 0, 0, nullptr, D, nullptr, 0, nullptr, D, 1.0, part, nullptr,
                                                                    nullptr, chunks);
@@ -740,8 +740,8 @@ int syrk_f64(plda_handle *h, int D, int64_t K, double alpha, const double *X, in
     int splits = (int)std::max<int64_t>(1, std::min<int64_t>(256, ceil_div(K, 128)));
     const int64_t kchunk = round_up(ceil_div(K, splits), GK);
     splits = (int)ceil_div(K, kchunk);
-    PLDA_HIP(h, h->w[15].reserve((size_t)splits * ntri * 256 * 8));
-    double *part = h->w[15].as<double>();
+    PLDA_HIP(h, h->linalg_part.reserve((size_t)splits * ntri * 256 * 8));
+    double *part = h->linalg_part.as<double>();
     note_kernel(h, "syrk_tri_kernel");
     syrk_tri_kernel<false><<<(unsigned)splits, 512, 0, h->stream>>>(D, K, kchunk, X, ldx, kw, K, nullptr, 0, 0.0, part, nullptr, nullptr);
     syrk_tri_reduce_kernel<<<(unsigned)ntri, 1024, 0, h->stream>>>(part, splits, D, alpha, beta, C, ldc);
@@ -762,8 +762,8 @@ int syrk_f64(plda_handle *h, int D, int64_t K, double alpha, const double *X, in
   int64_t kd = K, ko = K;
   plan(nT, sd, kd);
   if (nO) plan(nO, so, ko);
-  PLDA_HIP(h, h->w[15].reserve((size_t)std::max(sd, so) * nP * 64 * 256 * 8));
-  double *part = h->w[15].as<double>();
+  PLDA_HIP(h, h->linalg_part.reserve((size_t)std::max(sd, so) * nP * 64 * 256 * 8));
+  double *part = h->linalg_part.as<double>();
   note_kernel(h, "syrk_lower_kernel", 1, 1);
   if (nO) note_kernel(h, "syrk_lower_kernel", 1, 0);
   syrk_lower_kernel<true><<<(unsigned)(round_up(sd, 8) * nT), 256, 0, h->stream>>>(D, K, kd, X, ldx, kw, part, nP, nT, sd);
@@ -784,8 +784,8 @@ int syrk_znorm_f64(plda_handle *h, int D0, int64_t K, const double *X, const dou
   int splits = (int)std::max<int64_t>(1, std::min<int64_t>(256, ceil_div(K, 128)));
   const int64_t kchunk = round_up(ceil_div(K, splits), GK);
   splits = (int)ceil_div(K, kchunk);
-  PLDA_HIP(h, h->w[15].reserve((size_t)splits * ntri * 256 * 8));
-  double *part = h->w[15].as<double>();
+  PLDA_HIP(h, h->linalg_part.reserve((size_t)splits * ntri * 256 * 8));
+  double *part = h->linalg_part.as<double>();
   note_kernel(h, "syrk_tri_kernel", 1, 1);
   syrk_tri_kernel<true><<<(unsigned)splits, 512, 0, h->stream>>>(D, K, kchunk, X, D0, nullptr, K, nullptr, 0, 0.0, part, zc, zs);
   syrk_tri_reduce_kernel<<<(unsigned)ntri, 1024, 0, h->stream>>>(part, splits, D, 1.0, 0.0, C, D);
@@ -803,8 +803,8 @@ int syrk_pair_f64(plda_handle *h, int D, int64_t K1, const double *X, int64_t ld
     int splits = (int)std::max<int64_t>(1, std::min<int64_t>(256, ceil_div(K, 128)));
     const int64_t kchunk = round_up(ceil_div(K, splits), GK);
     splits = (int)ceil_div(K, kchunk);
-    PLDA_HIP(h, h->w[15].reserve((size_t)splits * ntri * 256 * 8));
-    double *part = h->w[15].as<double>();
+    PLDA_HIP(h, h->linalg_part.reserve((size_t)splits * ntri * 256 * 8));
+    double *part = h->linalg_part.as<double>();
     note_kernel(h, "syrk_tri_kernel");
     syrk_tri_kernel<false><<<(unsigned)splits, 512, 0, h->stream>>>(D, K, kchunk, X, ldx, kw, K1, X2, ldx2, w2, part, nullptr, nullptr);
     syrk_tri_reduce_kernel<<<(unsigned)ntri, 1024, 0, h->stream>>>(part, splits, D, 1.0, 0.0, C, ldc);
@@ -1025,8 +1025,8 @@ int gemm_f64_batched(plda_handle *h, int64_t M, int64_t N, int64_t K, double alp
   splits = (int)ceil_div(K, kchunk);
   double *part = nullptr;
   if (splits > 1) {
-    PLDA_HIP(h, h->w[15].reserve((size_t)splits * M * N * 8));
-    part = h->w[15].as<double>();
+    PLDA_HIP(h, h->linalg_part.reserve((size_t)splits * M * N * 8));
+    part = h->linalg_part.as<double>();
   }
   if ((int64_t)splits * batch > 65535) return fail(h, PLDA_E_INVAL, "gemm_f64: batch %d too large", batch);
   const dim3 grid((unsigned)ceil_div(N, TBsel), (unsigned)ceil_div(M, TBsel), (unsigned)(splits * batch));
@@ -2076,11 +2076,9 @@ int sym_eig_f64(plda_handle *h, double *G, int D, double *s, double *Vrows, int 
                 "-- or the method was forced to Jacobi), and the block Jacobi fallback holds 16 rows in LDS, i.e. stops at D = 1024",
                 D, (D + 7) / 8);
   const size_t DD = (size_t)D * D;
-  PLDA_HIP(h, h->w[14].reserve(DD * 8 * 2 + (size_t)D * 8 + 64));
-  double *V = h->w[14].as<double>();
-  double *A = V + DD;
-  double *lam = A + DD;
-  int *drot = reinterpret_cast<int *>(lam + D);   // 4 ints (jacobi_begin_kernel)
+  double *V, *A, *lam;
+  int *drot;   // 4 ints (jacobi_begin_kernel)
+  PLDA_TRY(carve(h, h->jac_work, [&](Layout &c) { c.take(V, DD).take(A, DD).take(lam, D).take(drot, 4).slack(48); }));
   if (warm) {
     PLDA_HIP(h, hipMemcpyAsync(V, warm, DD * 8, hipMemcpyDeviceToDevice, h->stream));
     PLDA_TRY(gemm_f64(h, D, D, D, 1.0, warm, D, 1, G, D, 1, nullptr, 0.0, A, D));
@@ -2177,16 +2175,32 @@ int sym_eig_auto_f64(plda_handle *h, double *G, int D, double *s, double *Vrows)
 int simdiag_finish_with(plda_handle *h, const double *W, const double *B, int D, double *T, double *Tinv, double *psi,
                         int chol_flag, int eig_status, bool *redo);
 
+// The arrays of h->simdiag_state, the one list every reader of it goes through.  T1, Vr and the flag outlive the call.
+struct SimdiagState {
+  double *scr, *T1, *tmp, *G, *Vr;   // whitening scratch [2 DD]; chol(W)^-1; T1 B; the congruence; eigenvectors in rows (the next warm start)
+  int *dflag;                        // the Cholesky's failure flag
+  void lay(Layout &c, size_t DD) { c.take(scr, 2 * DD).take(T1, DD).take(tmp, DD).take(G, DD).take(Vr, DD).take(dflag, 1).slack(60); }
+};
+// the state as the last simdiag_run of size D left it
+static SimdiagState simdiag_arrays(plda_handle *h, int D) {
+  SimdiagState s;
+  Layout at{h->simdiag_state.as<char>()};
+  s.lay(at, (size_t)D * D);
+  return s;
+}
+
 static int simdiag_run(plda_handle *h, const double *W, const double *B, int D, double *T, double *Tinv, double *psi,
                        bool warm_start, bool allow_direct, bool defer, bool *pending) {
   const size_t DD = (size_t)D * D;
-  const size_t need = DD * 8 * 6 + 64;
-  const bool fresh = h->w[13].cap < need || h->simdiag_D != D;
-  PLDA_HIP(h, h->w[13].reserve(need));
+  SimdiagState st;
+  Layout need;
+  st.lay(need, DD);
+  // (cap against the list's own size, the quantity the reserve below is given: a buffer this size or larger was never released)
+  const bool fresh = h->simdiag_state.cap < need.end || h->simdiag_D != D;
+  PLDA_TRY(carve(h, h->simdiag_state, [&](Layout &c) { st.lay(c, DD); }));
   h->simdiag_D = D;
-  double *scr = h->w[13].as<double>();                                    // 2 DD: whitening scratch
-  double *T1 = scr + 2 * DD, *tmp = T1 + DD, *G = tmp + DD, *Vr = G + DD;   // Vr persists: next call's warm start
-  int *dflag = reinterpret_cast<int *>(Vr + DD);
+  double *const scr = st.scr, *const T1 = st.T1, *const tmp = st.tmp, *const G = st.G, *const Vr = st.Vr;
+  int *const dflag = st.dflag;
   // (warm starts run block Jacobi, which stops at D = 1024: beyond it every call starts cold on the direct method)
   const bool warm = warm_start && !fresh && h->simdiag_has_vr && D <= 1024;
   const bool direct = allow_direct && !warm && h->eig_variant != 1;
@@ -2255,8 +2269,7 @@ int simdiag_enqueue(plda_handle *h, const double *W, const double *B, int D, dou
 int simdiag_finish(plda_handle *h, const double *W, const double *B, int D, double *T, double *Tinv, double *psi,
                    bool *redo) {
   *redo = false;
-  const size_t DD = (size_t)D * D;
-  const int *dflag = reinterpret_cast<const int *>(h->w[13].as<double>() + 6 * DD);
+  const int *dflag = simdiag_arrays(h, D).dflag;
   int hflag = 0, status = 0;
   PLDA_HIP(h, hipMemcpyAsync(&hflag, dflag, sizeof(int), hipMemcpyDeviceToHost, h->stream));
   PLDA_HIP(h, hipStreamSynchronize(h->stream));
@@ -2266,12 +2279,12 @@ int simdiag_finish(plda_handle *h, const double *W, const double *B, int D, doub
 
 // the two device flags simdiag_finish reads (for a caller that fetches them with its own copies: fit's model export)
 void simdiag_flags(plda_handle *h, int D, const int **chol_flag, const int **eig_flag) {
-  *chol_flag = reinterpret_cast<const int *>(h->w[13].as<double>() + 6 * (size_t)D * D);
+  *chol_flag = simdiag_arrays(h, D).dflag;
   *eig_flag = h->eigdc_flag;          // nullptr: the direct method did not take the problem (status 8)
 }
 
 // T1 = chol(W)^-1 (lower triangular, [D][D]) of the last simdiag of size D, valid until the next one
-const double *simdiag_whitening(plda_handle *h, int D) { return h->w[13].as<double>() + 2 * (size_t)D * D; }
+const double *simdiag_whitening(plda_handle *h, int D) { return simdiag_arrays(h, D).T1; }
 
 int simdiag_finish_with(plda_handle *h, const double *W, const double *B, int D, double *T, double *Tinv, double *psi,
                         int chol_flag, int eig_status, bool *redo) {

@@ -1456,12 +1456,12 @@ __global__ void pairs_validate_kernel(const int64_t *__restrict__ e, const int64
     if (e[p] < 0 || e[p] >= M || t[p] < 0 || t[p] >= Nt) atomicMin(first_bad, (unsigned long long)p);
 }
 int pairs_validate_device(plda_handle *h, const int64_t *de, const int64_t *dt, int64_t P, int64_t M, int64_t Nt, long long *bad) {
-  PLDA_HIP(h, h->w[12].reserve(8));
-  PLDA_HIP(h, hipMemsetAsync(h->w[12].p, 0xff, 8, h->stream));
-  pairs_validate_kernel<<<(unsigned)std::min<int64_t>(ceil_div(P, 256), 4096), 256, 0, h->stream>>>(de, dt, P, M, Nt, h->w[12].as<unsigned long long>());
+  PLDA_HIP(h, h->host_flag.reserve(8));
+  PLDA_HIP(h, hipMemsetAsync(h->host_flag.p, 0xff, 8, h->stream));
+  pairs_validate_kernel<<<(unsigned)std::min<int64_t>(ceil_div(P, 256), 4096), 256, 0, h->stream>>>(de, dt, P, M, Nt, h->host_flag.as<unsigned long long>());
   PLDA_LAUNCH_CHECK(h);
   unsigned long long v = 0;
-  PLDA_HIP(h, hipMemcpyAsync(&v, h->w[12].p, 8, hipMemcpyDeviceToHost, h->stream));
+  PLDA_HIP(h, hipMemcpyAsync(&v, h->host_flag.p, 8, hipMemcpyDeviceToHost, h->stream));
   PLDA_HIP(h, hipStreamSynchronize(h->stream));
   *bad = v == ~0ull ? -1 : (long long)v;
   return PLDA_OK;
@@ -1599,9 +1599,9 @@ static int prepare_operands(plda_handle *h, const double *dU, const int32_t *dn,
   if (op.kind == 2) {
     // bucketed mixed counts: per-bucket coefficient tables, then one pass over each side (+ the test side's dq planes)
     const int G = cs->G, KQm = Dp / 4, KQx = op.KQ - KQm;
-    PLDA_HIP(h, h->w[11].reserve((size_t)G * (2 * D + 1) * 8));
-    double *coefG = h->w[11].as<double>();
-    h->ucoef_ptr = nullptr;          // (the uniform path's cached coefficients live in the same buffer)
+    PLDA_HIP(h, h->coef_cache.reserve((size_t)G * (2 * D + 1) * 8));
+    double *coefG = h->coef_cache.as<double>();
+    h->ucoef_ptr = nullptr;          // (the uniform path's cached coefficients live in the same buffer, coef_cache)
     // the tables depend on (model, dimension, the set of counts) only: kept across calls like the uniform path's
     if (!(h->gcoef_ptr == coefG && h->gcoef_epoch == h->model_epoch && h->gcoef_D == D && h->gcoef_set.G == G &&
           std::memcmp(h->gcoef_set.vals, cs->vals, (size_t)G * sizeof(int32_t)) == 0)) {
@@ -1656,8 +1656,8 @@ static int prepare_operands(plda_handle *h, const double *dU, const int32_t *dn,
           dU, dn, n_uniform, psi, D, M, dzmean, dzstd, h->s_rbias.as<float>(), h->s_rscale.as<float>());
     if (doB) PLDA_HIP(h, hipMemsetAsync(h->s_cbias.p, 0, (size_t)op.Npad * 4, h->stream));
   } else {
-    PLDA_HIP(h, h->w[11].reserve((size_t)(2 * D + 1) * 8));
-    double *coef = h->w[11].as<double>();
+    PLDA_HIP(h, h->coef_cache.reserve((size_t)(2 * D + 1) * 8));
+    double *coef = h->coef_cache.as<double>();
     // the per-dimension coefficients depend on (model, count) only: kept across calls (4.7 us of launch otherwise)
     if (!(h->ucoef_ptr == coef && h->ucoef_epoch == h->model_epoch && h->ucoef_n == n_uniform && h->ucoef_D == D)) {
       uniform_coef_kernel<<<1, 256, 0, h->stream>>>(psi, D, n_uniform, coef);
@@ -1990,10 +1990,10 @@ __global__ __launch_bounds__(256) void fingerprint_kernel(const double *__restri
 
 // (synchronises the handle's stream: only plda_score_prepare_dev and calls that REUSE a prepared test side pay it)
 static int test_side_fingerprint(plda_handle *h, const double *dV, int64_t Nt, unsigned long long *fp) {
-  PLDA_HIP(h, h->w[12].reserve(8));
-  fingerprint_kernel<<<1, 256, 0, h->stream>>>(dV, Nt, h->Dout, h->w[12].as<unsigned long long>());
+  PLDA_HIP(h, h->host_flag.reserve(8));
+  fingerprint_kernel<<<1, 256, 0, h->stream>>>(dV, Nt, h->Dout, h->host_flag.as<unsigned long long>());
   PLDA_LAUNCH_CHECK(h);
-  PLDA_HIP(h, hipMemcpyAsync(fp, h->w[12].p, 8, hipMemcpyDeviceToHost, h->stream));
+  PLDA_HIP(h, hipMemcpyAsync(fp, h->host_flag.p, 8, hipMemcpyDeviceToHost, h->stream));
   PLDA_HIP(h, hipStreamSynchronize(h->stream));
   return PLDA_OK;
 }
@@ -2174,9 +2174,9 @@ int score_pairs_device(plda_handle *h, const double *dU, const int32_t *dn, cons
   // (PLDA_MIXED_VARIANT=1 keeps everything on the verbatim kernel: the A/B arm)
   if (cs && cs->G >= 1 && cs->G <= CS_MAX && M > 0 && P >= PAIRS_TAB_MIN && h->mixed_variant != 1) {
     const int G = cs->G, S = 2 * D + 1;
-    PLDA_HIP(h, h->w[12].reserve(((size_t)G * S + D) * 8 + (size_t)M * 4));
-    double *tab = h->w[12].as<double>();
-    int32_t *bidx = reinterpret_cast<int32_t *>(tab + (size_t)G * S + D);
+    double *tab;      // G tables of S, then the mean's term [D]
+    int32_t *bidx;    // every model's bucket
+    PLDA_TRY(carve(h, h->pair_tab, [&](Layout &c) { c.take(tab, (size_t)G * S + D).take(bidx, M); }));
     pairs_tables_kernel<<<G + 1, 256, 0, h->stream>>>(h->d_psi.as<double>(), D, *cs, tab);
     pairs_bucket_kernel<<<(unsigned)ceil_div(M, 256), 256, 0, h->stream>>>(dn, M, *cs, bidx);
     constexpr int PPW = 4;
@@ -2442,8 +2442,8 @@ int znorm_stats_device(plda_handle *h, const double *dbkg, int64_t Nb, int num_e
   if (Nb <= 0 || M <= 0) return fail(h, PLDA_E_INVAL, "norm: empty input");
   const int D = h->Dout;
   // cohort rows transformed with num_examples = Nb (quirk Q6, :224)
-  PLDA_HIP(h, h->w[8].reserve((size_t)Nb * D * 8));
-  double *dT = h->w[8].as<double>();
+  PLDA_HIP(h, h->zn_pilot_rows.reserve((size_t)Nb * D * 8));
+  double *dT = h->zn_pilot_rows.as<double>();
   if (num_examples <= 0) num_examples = (int)Nb;
   PLDA_TRY(transform_rows_device(h, dbkg, Nb, Din, nullptr, num_examples, dT));
   // cohort = train side with n = 1 (quirk Q7, :235); models = test side
@@ -2451,10 +2451,10 @@ int znorm_stats_device(plda_handle *h, const double *dbkg, int64_t Nb, int num_e
   // ---- A/B arm: every LLR on the fp32 MFMA GEMM with the fused (sum, sum of squares) epilogue ----
   TrialOperands op;
   PLDA_TRY(prepare_operands(h, dT, nullptr, 1, Nb, dmodels, M, nullptr, nullptr, op));
-  PLDA_HIP(h, h->w[9].reserve((size_t)op.Npad * (8 + 8 + 4)));
-  double *colsum = h->w[9].as<double>();
-  double *colsq = colsum + op.Npad;
-  float *shift = reinterpret_cast<float *>(colsq + op.Npad);
+  double *colsum, *colsq;
+  float *shift;
+  // (Npad is a multiple of 256: the three arrays lie back to back, which the two memsets below rely on)
+  PLDA_TRY(carve(h, h->zn_pilot_sums, [&](Layout &c) { c.take(colsum, op.Npad).take(colsq, op.Npad).take(shift, op.Npad); }));
   // pilot: mean over the first rows -> shift (keeps the single-pass variance well conditioned)
   const int64_t Np = Nb < 128 ? Nb : 128;
   PLDA_HIP(h, hipMemsetAsync(colsum, 0, (size_t)op.Npad * 20, h->stream));

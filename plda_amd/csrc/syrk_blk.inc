@@ -281,17 +281,17 @@ static int syrk_blk_pair(plda_handle *h, int D, int64_t K1, const double *X, int
   const int64_t rows2 = K2 > 0 ? round_up(ceil_div(K2, groups), SB_ROWS) : 0;
   if (rows1 * ldx * 8 >= (1ll << 32) || rows2 * ldx2 * 8 >= (1ll << 32)) return PLDA_OK;   // 32-bit DMA offsets inside a chunk
   const int nt = (int)ceil_div(D, 16), ntri = nt * (nt + 1) / 2;
-  PLDA_HIP(h, h->w[15].reserve((size_t)groups * ntri * 256 * 8));
-  double *part = h->w[15].as<double>();
-  // weights as arrays for both phases (ones when the rows are unweighted, w2 for the second matrix)
-  PLDA_HIP(h, h->w[14].reserve((size_t)(K1 + K2 + 64) * 8));
-  double *wts = h->w[14].as<double>();
+  PLDA_HIP(h, h->linalg_part.reserve((size_t)groups * ntri * 256 * 8));
+  double *part = h->linalg_part.as<double>();
+  // weights as arrays for both phases (ones when the rows are unweighted, w2 for the second matrix), each with room behind
+  // its last row for the block kernel's over-read
+  double *wts, *W2;
+  PLDA_TRY(carve(h, h->syrk_wts, [&](Layout &c) { c.take(wts, K1 + 16).take(W2, K2 + 48); }));
   const double *W1 = kw;
   if (!kw) {
     fill_f64_kernel<<<(unsigned)ceil_div(K1, 256), 256, 0, h->stream>>>(wts, K1, 1.0);
     W1 = wts;
   }
-  double *W2 = wts + K1 + 16;
   if (K2 > 0) fill_f64_kernel<<<(unsigned)ceil_div(K2, 256), 256, 0, h->stream>>>(W2, K2, w2);
   const size_t ldsb = ((size_t)2 * SB_ROWS * ceil_div(D, 128) * 128 + 64) * 8;
   static DeviceOnce attr;

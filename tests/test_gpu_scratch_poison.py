@@ -86,7 +86,7 @@ _FIT_CASES = [(f, d) for f in ("0", "1", "3", "4") for d in (1, 17, 33, 200, 209
 def test_fit_on_poisoned_scratch(monkeypatch, form, d):
     """The four EM forms (PLDA_EM_VARIANT 0 = by shape, 1 = diagonalised basis, 3 = moments, 4 = rows) on 41 speakers with
     skewed counts (19 distinct counts: the row form's G >= 4).  K D = 41 D is odd for odd D: the row form's int4 tile table
-    sits behind three K x D double arrays (fit.hip).  D not a multiple of 16: the row form's fragment loads run past the
+    shares one carved buffer with three K x D double arrays (fit.hip: em_rows).  D not a multiple of 16: the row form's fragment loads run past the
     last row of B, X_g and T_g^T.  D in {209, 300, 512}: the block scatter kernel of the rank-k sums.  Form 1 diagonalises
     W = B = I in its first iteration: the direct eigensolver's reflectors of columns that are already tridiagonal (once
     left unwritten) and, at D = 1025, a cold start on every iteration (block Jacobi stops at 1024)."""
