@@ -41,7 +41,11 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-ato
 # contract names them, so nothing may be contracted into a fused multiply-add
 # embed.hip: a row's bits may not depend on the block shape or the input dtype's instantiation it runs in (the determinism rule
 # of the embedding chain): every fused multiply-add there is written as fma(), nothing else may be contracted
+# frontend.hip: variance pooling subtracts the utterance's first normalised frame y0 = x0 * inv from every y = x * inv; a fused
+# x * inv - y0 would subtract the rounded product from the unrounded one, and a one-frame utterance's variance would not be 0
+# (the fused multiply-adds the kernels do want are written as fma())
 EXTRA = {"score.hip": ["-mllvm", "-amdgpu-atomic-optimizer-strategy=None"],
+         "frontend.hip": ["-ffp-contract=off"],
          "fusion.hip": ["-mllvm", "-disable-machine-licm"],
          "ahc.hip": ["-ffp-contract=off"],
          "embed.hip": ["-ffp-contract=off"]}

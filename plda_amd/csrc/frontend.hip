@@ -7,6 +7,15 @@
 // One workgroup (4 waves) per utterance; a wave takes every 4th frame, lane l owns
 // columns l, l + 64, ... so a frame read is one contiguous burst; the frame norm is a
 // DPP wave reduction; the per-wave partial (sum, sum of squares, max) meet in LDS.
+// Variance (method 2) is the population variance from the running sums of z = y - y0 and z * z, y0 the
+// utterance's first (normalised) frame, which every wave re-reads once: var = q/n - (s/n)^2 of the shifted
+// values.  The shift makes the one pass as accurate as the two-pass definition when |mean| >> std
+// (un-normalised activations, a dominant column under l2norm): the relative error per column is about
+// n eps (1 + ((y0 - mean) / std)^2), some 1e-12 at n = 1000, where the unshifted sums lost everything
+// beyond eps mean^2 / var.  Mean and max accumulate the unshifted values (the kernels are instantiated
+// with and without the shift).  The file is compiled with -ffp-contract=off (build.py) and every fused
+// multiply-add is written as fma(): y - y0 must subtract the rounded product that y0 itself is, so that a
+// one-frame utterance, or a constant column, has variance exactly 0.
 #include "common.hpp"
 
 #include <algorithm>
@@ -15,7 +24,27 @@ namespace plda {
 
 constexpr int DV_MAXE = 16;   // D <= 1024
 
+// 1 / ||row||_2 of one frame, the same value in every lane of the wave
 template <typename T>
+__device__ __forceinline__ double frame_inv_norm(const T *__restrict__ row, int D, int lane) {
+  double ss = 0.0;
+  for (int d = lane; d < D; d += 64) { const double x = (double)row[d]; ss = fma(x, x, ss); }
+  return 1.0 / sqrt(wave_sum_f64(ss));
+}
+
+// the pooled value of one column from its sums over the n frames: s and q are the sums of y and y * y for the mean and the
+// max, of y - y0 and its square for the variance (which the shift leaves unchanged)
+__device__ __forceinline__ double pooled(int method, int64_t n, double s, double q, double m) {
+  if (n == 0) return __builtin_nan("");
+  const double nn = (double)n;
+  if (method == 0) return s / nn;
+  if (method == 1) return m;
+  const double mean = s / nn;
+  const double r = q / nn - mean * mean;
+  return r < 0.0 ? 0.0 : r;
+}
+
+template <typename T, bool VAR>
 __global__ __launch_bounds__(256) void dvector_pool_kernel(const T *__restrict__ frames, int D,
                                                            const int64_t *__restrict__ offsets, int method,
                                                            int l2norm, double *__restrict__ out) {
@@ -26,24 +55,27 @@ __global__ __launch_bounds__(256) void dvector_pool_kernel(const T *__restrict__
   const int64_t n = end - beg;
   // columns are processed in passes of 256 so that the LDS combine stays small
   for (int d0 = 0; d0 < D; d0 += 256) {
-    double sum[4], sq[4], mx[4];
+    double sum[4], sq[4], mx[4], sh[4];
 #pragma unroll
-    for (int e = 0; e < 4; ++e) { sum[e] = 0.0; sq[e] = 0.0; mx[e] = -__builtin_huge_val(); }
+    for (int e = 0; e < 4; ++e) { sum[e] = 0.0; sq[e] = 0.0; mx[e] = -__builtin_huge_val(); sh[e] = 0.0; }
+    if (VAR && n > 0) {   // the variance's shift: the first frame, normalised exactly as the loop does it
+      const T *row = frames + beg * (int64_t)D;
+      const double inv = l2norm ? frame_inv_norm(row, D, lane) : 1.0;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int d = d0 + lane + e * 64;
+        if (d < D) sh[e] = (double)row[d] * inv;
+      }
+    }
     for (int64_t f = beg + wave; f < end; f += 4) {
       const T *row = frames + f * (int64_t)D;
-      double inv = 1.0;
-      if (l2norm) {
-        double ss = 0.0;
-        for (int d = lane; d < D; d += 64) { const double x = (double)row[d]; ss += x * x; }
-        ss = wave_sum_f64(ss);
-        inv = 1.0 / sqrt(ss);
-      }
+      const double inv = l2norm ? frame_inv_norm(row, D, lane) : 1.0;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const int d = d0 + lane + e * 64;
         if (d < D) {
-          const double y = (double)row[d] * inv;
-          sum[e] += y; sq[e] += y * y; mx[e] = y > mx[e] || y != y ? y : mx[e];
+          const double y = (double)row[d] * inv, z = VAR ? y - sh[e] : y;
+          sum[e] += z; sq[e] = fma(z, z, sq[e]); mx[e] = y > mx[e] || y != y ? y : mx[e];
         }
       }
     }
@@ -62,13 +94,7 @@ __global__ __launch_bounds__(256) void dvector_pool_kernel(const T *__restrict__
       double m = part[2][0][c];
 #pragma unroll
       for (int w = 1; w < 4; ++w) { const double v = part[2][w][c]; m = (v > m || v != v) ? v : m; }
-      double r;
-      const double nn = (double)n;
-      if (n == 0) r = __builtin_nan("");
-      else if (method == 0) r = s / nn;
-      else if (method == 1) r = m;
-      else { const double mean = s / nn; r = q / nn - mean * mean; if (r < 0.0) r = 0.0; }
-      out[(int64_t)u * D + d] = r;
+      out[(int64_t)u * D + d] = pooled(method, n, s, q, m);
     }
     __syncthreads();
   }
@@ -94,7 +120,11 @@ __device__ __forceinline__ double group_sum_f64(double x) {
 
 typedef float f32x4v __attribute__((ext_vector_type(4)));
 
-template <int G>
+__device__ __forceinline__ double sum_sq4(const double y[4]) {
+  return fma(y[0], y[0], fma(y[1], y[1], fma(y[2], y[2], y[3] * y[3])));
+}
+
+template <int G, bool VAR>
 __global__ __launch_bounds__(256) void dvector_pool_vec4_kernel(const f32x4v *__restrict__ frames,
                                                                 const int64_t *__restrict__ offsets,
                                                                 int method, int l2norm,
@@ -109,6 +139,16 @@ __global__ __launch_bounds__(256) void dvector_pool_vec4_kernel(const f32x4v *__
   const int64_t n = end - beg;
   double sum[4] = {0, 0, 0, 0}, sq[4] = {0, 0, 0, 0};
   double mx[4] = {-__builtin_huge_val(), -__builtin_huge_val(), -__builtin_huge_val(), -__builtin_huge_val()};
+  double sh[4] = {0, 0, 0, 0};
+  if (VAR && n > 0) {   // the variance's shift: every frame group loads the first frame, normalised as below
+    const f32x4v x0 = frames[beg * G + c];
+    sh[0] = (double)x0.x; sh[1] = (double)x0.y; sh[2] = (double)x0.z; sh[3] = (double)x0.w;
+    if (l2norm) {
+      const double inv = 1.0 / sqrt(group_sum_f64<G>(sum_sq4(sh)));
+#pragma unroll
+      for (int e = 0; e < 4; ++e) sh[e] *= inv;
+    }
+  }
   for (int64_t base = beg + (int64_t)wave * FPW * UNR; base < end; base += 4 * FPW * UNR) {
     f32x4v x[UNR];
     bool ok[UNR];
@@ -122,16 +162,16 @@ __global__ __launch_bounds__(256) void dvector_pool_vec4_kernel(const f32x4v *__
     for (int k = 0; k < UNR; ++k) {
       double y[4] = {(double)x[k].x, (double)x[k].y, (double)x[k].z, (double)x[k].w};
       if (l2norm) {
-        const double ss = group_sum_f64<G>(y[0] * y[0] + y[1] * y[1] + y[2] * y[2] + y[3] * y[3]);
-        const double inv = 1.0 / sqrt(ss);
+        const double inv = 1.0 / sqrt(group_sum_f64<G>(sum_sq4(y)));
 #pragma unroll
         for (int e = 0; e < 4; ++e) y[e] *= inv;
       }
       if (ok[k]) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          sum[e] += y[e];
-          sq[e] += y[e] * y[e];
+          const double z = VAR ? y[e] - sh[e] : y[e];
+          sum[e] += z;
+          sq[e] = fma(z, z, sq[e]);
           mx[e] = (y[e] > mx[e] || y[e] != y[e]) ? y[e] : mx[e];
         }
       }
@@ -164,13 +204,7 @@ __global__ __launch_bounds__(256) void dvector_pool_vec4_kernel(const f32x4v *__
     double m = part[2][0][d];
 #pragma unroll
     for (int w = 1; w < 4; ++w) { const double v = part[2][w][d]; m = (v > m || v != v) ? v : m; }
-    const double nn = (double)n;
-    double r;
-    if (n == 0) r = __builtin_nan("");
-    else if (method == 0) r = s / nn;
-    else if (method == 1) r = m;
-    else { const double mean = s / nn; r = q / nn - mean * mean; if (r < 0.0) r = 0.0; }
-    out[(int64_t)u * (4 * G) + d] = r;
+    out[(int64_t)u * (4 * G) + d] = pooled(method, n, s, q, m);
   }
 }
 
@@ -183,15 +217,28 @@ int dvector_pool_device(plda_handle *h, const void *dframes, int dtype, int64_t 
   if (dtype == 0 && (reinterpret_cast<uintptr_t>(dframes) & 15) == 0 &&
       (D == 16 || D == 32 || D == 64 || D == 128 || D == 256)) {
     const f32x4v *fv = static_cast<const f32x4v *>(dframes);
-#define DV(G_) dvector_pool_vec4_kernel<G_><<<(unsigned)U, 256, 0, h->stream>>>(fv, doffsets, method, l2norm, dout)
-    if (D == 16) DV(4); else if (D == 32) DV(8); else if (D == 64) DV(16); else if (D == 128) DV(32); else DV(64);
+#define DV(G_)                                                                                                  \
+  if (method == 2) dvector_pool_vec4_kernel<G_, true><<<(unsigned)U, 256, 0, h->stream>>>(fv, doffsets, method, l2norm, dout); \
+  else dvector_pool_vec4_kernel<G_, false><<<(unsigned)U, 256, 0, h->stream>>>(fv, doffsets, method, l2norm, dout)
+    switch (D) {
+      case 16: DV(4); break;
+      case 32: DV(8); break;
+      case 64: DV(16); break;
+      case 128: DV(32); break;
+      default: DV(64); break;
+    }
 #undef DV
-  } else if (dtype == 0)
-    dvector_pool_kernel<float><<<(unsigned)U, 256, 0, h->stream>>>(static_cast<const float *>(dframes), D, doffsets,
-                                                                  method, l2norm, dout);
-  else
-    dvector_pool_kernel<double><<<(unsigned)U, 256, 0, h->stream>>>(static_cast<const double *>(dframes), D, doffsets,
-                                                                   method, l2norm, dout);
+  } else {
+#define DS(T_)                                                                                                             \
+  if (method == 2)                                                                                                         \
+    dvector_pool_kernel<T_, true><<<(unsigned)U, 256, 0, h->stream>>>(static_cast<const T_ *>(dframes), D, doffsets, method, \
+                                                                      l2norm, dout);                                       \
+  else                                                                                                                     \
+    dvector_pool_kernel<T_, false><<<(unsigned)U, 256, 0, h->stream>>>(static_cast<const T_ *>(dframes), D, doffsets, method, \
+                                                                       l2norm, dout)
+    if (dtype == 0) { DS(float); } else { DS(double); }
+#undef DS
+  }
   PLDA_LAUNCH_CHECK(h);
   return PLDA_OK;
 }

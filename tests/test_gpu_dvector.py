@@ -8,10 +8,12 @@ from oracle import plda_oracle_np as onp
 pytestmark = pytest.mark.gpu
 
 
-@pytest.mark.parametrize("dtype,tol", [(np.float64, 1e-12), (np.float32, 2e-7)])
+@pytest.mark.parametrize("dtype,tol", [(np.float64, 1e-12), (np.float32, 1e-12)])
 @pytest.mark.parametrize("method", ["mean", "max", "var"])
 @pytest.mark.parametrize("l2norm", [True, False])
 def test_pool_matches_numpy(dtype, tol, method, l2norm):
+    """float32 frames convert exactly and accumulate in fp64, so they meet the float64 tolerance.  The variance is held
+    per column, relative to that column's reference variance, to 1e-10 (the bound of tests/test_gpu_dvector_edges.py)."""
     from plda_amd import dvector
     rng = np.random.default_rng(3)
     lens = [1, 2, 3, 17, 64, 257, 5, 1000]
@@ -22,7 +24,9 @@ def test_pool_matches_numpy(dtype, tol, method, l2norm):
         ref = onp.dvector_pool(frames.astype(np.float64), off, method, l2norm)
         scale = np.abs(ref).max()
         assert got.shape == ref.shape and got.dtype == np.float64
-        assert np.abs(got - ref).max() <= tol * max(scale, 1.0) * (50 if method == "var" and not l2norm else 1)
+        assert np.abs(got - ref).max() <= tol * max(scale, 1.0)
+        if method == "var":
+            assert (np.abs(got - ref) <= 1e-10 * ref).all()
 
 
 def test_reference_named_functions_and_ragged():
