@@ -325,13 +325,14 @@ int plda_oracle_stats(const double *X, int64_t N, int D, const uint64_t *labels,
   int64_t *start = (int64_t *)calloc((size_t)K + 1, sizeof(int64_t));
   int64_t *fill = (int64_t *)calloc((size_t)K + 1, sizeof(int64_t));
   int64_t *rows = (int64_t *)calloc((size_t)(N ? N : 1), sizeof(int64_t));
-  if (!start || !fill || !rows) { free(start); free(fill); free(rows); return -1; }
+  double *xc = (double *)calloc((size_t)(D > 0 ? D : 1), sizeof(double)); /* one class-centred row */
+  if (!start || !fill || !rows || !xc) { free(start); free(fill); free(rows); free(xc); return -1; }
   for (int64_t k = 0; k < K; k++) start[k + 1] = start[k] + counts[k];
   for (int64_t r = 0; r < N; r++) { int64_t k = (int64_t)labels[r]; rows[start[k] + fill[k]++] = r; }
   double cw = 0.0, ew = 0.0;
   for (int64_t k = 0; k < K; k++) {
     int64_t n = counts[k];
-    if (n == 0) { free(start); free(fill); free(rows); return -1; } /* not dense */
+    if (n == 0) { free(start); free(fill); free(rows); free(xc); return -1; } /* not dense */
     double w = 1.0 / (double)n;
     double *m = means + IDX(k, 0, D);
     /* mean->AddRowSumMat(1/n, group) */
@@ -340,20 +341,20 @@ int plda_oracle_stats(const double *X, int64_t N, int D, const uint64_t *labels,
       for (int j = 0; j < D; j++) m[j] += x[j];
     }
     for (int j = 0; j < D; j++) m[j] /= (double)n;
-    /* offset_scatter.AddMat2(w, group, kTrans, 1.0) */
+    /* offset_scatter.AddMat2(w, group, kTrans, 1.0) followed by offset_scatter.AddVec2(-n*w, mean)
+     * (pldamodule.cpp:94-98 -> PldaStats::AddSamples) is  w sum_t x_t x_t^T - n w m m^T,  a difference of
+     * uncentred sums that loses about eps (offset / spread)^2 on data with a common offset.  The same
+     * matrix is accumulated here in the other order,  w sum_t (x_t - m)(x_t - m)^T,  rows centred first
+     * (xc).  PARITY UNPINNED; on the reference's usage distribution (uniform [0, 1) rows) the two orders
+     * agree to 1e-14. */
     for (int64_t t = 0; t < n; t++) {
       const double *x = X + IDX(rows[start[k] + t], 0, D);
+      for (int j = 0; j < D; j++) xc[j] = x[j] - m[j];
       for (int i = 0; i < D; i++) {
-        double wx = w * x[i];
+        double wx = w * xc[i];
         double *srow = scatter + IDX(i, 0, D);
-        for (int j = 0; j <= i; j++) srow[j] += wx * x[j];
+        for (int j = 0; j <= i; j++) srow[j] += wx * xc[j];
       }
-    }
-    /* offset_scatter.AddVec2(-n*w, mean) */
-    for (int i = 0; i < D; i++) {
-      double a = -(double)n * w * m[i];
-      double *srow = scatter + IDX(i, 0, D);
-      for (int j = 0; j <= i; j++) srow[j] += a * m[j];
     }
     cw += w; ew += w * (double)n;
     for (int j = 0; j < D; j++) sum[j] += w * m[j];
@@ -361,7 +362,7 @@ int plda_oracle_stats(const double *X, int64_t N, int D, const uint64_t *labels,
   for (int i = 0; i < D; i++)
     for (int j = 0; j < i; j++) scatter[IDX(j, i, D)] = scatter[IDX(i, j, D)];
   *class_weight = cw; *example_weight = ew;
-  free(start); free(fill); free(rows);
+  free(start); free(fill); free(rows); free(xc);
   return 0;
 }
 

@@ -30,7 +30,15 @@ def stats(X, labels):
     means = sums / counts[:, None]
     w = 1.0 / counts
     wrow = w[labels]
-    scatter = (X * wrow[:, None]).T @ X - (means * (counts * w)[:, None]).T @ means
+    # AddSamples (pldamodule.cpp:94-98 -> offset_scatter.AddMat2(w, group), AddVec2(-n w, mean)) forms
+    #     X^T diag(w) X - sum_k (n_k w_k) m_k m_k^T,
+    # a difference of uncentred sums.  The same matrix is taken here as the product of class-centred rows,
+    #     sum_i w_label(i) (x_i - m_label(i)) (x_i - m_label(i))^T,
+    # because the difference loses about eps (offset / spread)^2 on data with a common offset (tests/fit_model.py:
+    # stats_uncentred keeps Kaldi's order and measures it).  PARITY UNPINNED; on the reference's usage distribution
+    # (uniform [0, 1) rows) the two orders agree to 1e-14.
+    xc = X - means[labels]
+    scatter = (xc * wrow[:, None]).T @ xc
     scatter = 0.5 * (scatter + scatter.T)
     sum_ = (means * w[:, None]).sum(0)
     return dict(means=means, counts=counts, scatter=scatter, sum=sum_,

@@ -147,6 +147,7 @@ struct plda_handle {
   plda::DevBuf fit_offsets;      // class counts -> offsets [K + 1], then the label-check words (plda_fit: read back by the EM's planning copy)
   plda::DevBuf fit_hist;         // per-chunk class counts -> bases, or the radix sort's digit histograms (+ the largest label)
   plda::DevBuf fit_roww;         // one weight per row of the centroid kernels
+  plda::DevBuf fit_xc;           // the statistics pass's class-centred rows [N x D], the operand of the scatter product
   plda::DevBuf fit_mu;           // the global mean, then the EM's scalars (alive until the fit's model export)
   plda::DevBuf fit_csum;         // the class sum's partials per split
   plda::DevBuf em_rows;          // the EM's K x D arrays (row form: the tile table first; its fragment loads over-read the last row)

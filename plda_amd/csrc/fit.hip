@@ -3,7 +3,9 @@
 // Replaces MPlda_fit (/root/reference/src/pldamodule.cpp:42-109):
 //   :76-92   label grouping            -> K1a  stable LSD radix sort of (label,row)
 //   :94-98   AddSamples(1/n_k, rows_k) -> K1   segmented centroid accumulation
-//                                         K2   weighted SYRK  X^T diag(1/n_label) X  -  M^T M
+//                                         K1b  class-centred rows  xc_i = x_i - m_label(i)
+//                                         K2   weighted SYRK  Xc^T diag(1/n_label) Xc  (AddSamples' X^T diag(w) X - M^T M
+//                                              without the cancellation: fit_stats_device)
 //   :100     stats.Sort()              -> not needed (no per-distinct-n inversions below)
 //   :102-106 Estimate(iters)           -> K3   EM in the simultaneously-diagonalised basis
 //                                              (identical maths to A.2)
@@ -149,6 +151,38 @@ __global__ __launch_bounds__(256) void centroid_kernel(const double *__restrict_
     means[(int64_t)k * D + d0] = DIV ? acc / (double)n : acc * inv;
   }
   for (int r = beg + threadIdx.x; r < end; r += blockDim.x) roww[perm[r]] = inv;
+}
+
+// Xc[i][d] = X[i][d] - means[label_i][d], the rows K2 multiplies: a workgroup takes 16 rows, a wave four of them, its lanes
+// the columns (512-byte bursts, no integer division).  A label that failed the check reads class 0: a valid index, garbage
+// values, like everything else enqueued behind a failed check.
+constexpr int CR_ROWS = 16;
+
+__global__ __launch_bounds__(256) void center_rows_kernel(const double *__restrict__ X, const uint64_t *__restrict__ labels,
+                                                          const double *__restrict__ means, int64_t N, int64_t K, int D,
+                                                          double *__restrict__ Xc) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  constexpr int R = CR_ROWS / 4;
+  const int64_t r0 = (int64_t)blockIdx.x * CR_ROWS + wave * R;
+  if (r0 >= N) return;
+  const int nr = (int)min((int64_t)R, N - r0);        // rows of this wave; a missing row repeats the last one's loads
+  const double *x[R], *m[R];
+#pragma unroll
+  for (int u = 0; u < R; ++u) {
+    const int64_t r = r0 + min(u, nr - 1);
+    uint64_t l = labels[r];
+    if (l >= (uint64_t)K) l = 0;
+    x[u] = X + r * D;
+    m[u] = means + (int64_t)l * D;
+  }
+  for (int d = lane; d < D; d += 64) {                // the four rows' loads in flight together
+    double v[R];
+#pragma unroll
+    for (int u = 0; u < R; ++u) v[u] = x[u][d] - m[u][d];
+#pragma unroll
+    for (int u = 0; u < R; ++u)
+      if (u < nr) Xc[(r0 + u) * D + d] = v[u];
+  }
 }
 
 // sum_d = sum_k w_k m_kd (w_k = 1/n_k) and class_weight = sum_k w_k, deterministic two-stage:
@@ -789,23 +823,31 @@ int fit_stats_device(plda_handle *h, const double *dX, int64_t N, int D, const u
   PLDA_HIP(h, h->f_counts.reserve((size_t)K * 8));
   PLDA_HIP(h, h->f_scatter.reserve(DD * 8));
   PLDA_HIP(h, h->fit_roww.reserve((size_t)N * 8));           // row weights
+  PLDA_HIP(h, h->fit_xc.reserve((size_t)N * D * 8));         // class-centred rows
   double *means = h->f_means.as<double>();
   double *S = h->f_scatter.as<double>();
   double *roww = h->fit_roww.as<double>();
+  double *Xc = h->fit_xc.as<double>();
   counts_to_i64_kernel<<<(unsigned)ceil_div(K, 256), 256, 0, h->stream>>>(offsets, K, h->f_counts.as<int64_t>());
   {
     TraceScope ts(h, "fit.centroids (K1)", (double)N * D * 8.0, 2);
     centroid_kernel<false><<<(unsigned)K, 256, 0, h->stream>>>(dX, D, perm, offsets, means, roww);
     PLDA_LAUNCH_CHECK(h);
   }
-  // offset_scatter = X^T diag(1/n_label) X - sum_k (n_k w_k) m_k m_k^T,  n_k w_k = 1
+  // offset_scatter = sum_i (1 / n_label(i)) (x_i - m_label(i)) (x_i - m_label(i))^T: the product of class-centred rows.  Kaldi's
+  // AddSamples forms X^T diag(1 / n_label) X - sum_k m_k m_k^T, a difference of uncentred sums that loses about
+  // eps (offset / spread)^2 of the result on data with a common offset (8e-7 at x + 8192, 2e-4 at x + 131072); this pass formed
+  // it that way, both terms in one launch, until the fit was pinned on offset data.  Centring is local to a shard.
   {
-    // X^T diag(1 / n_label) X and - M^T M in one pass (D <= 208: one launch + one reduction; the centroids' term was a
-    // launch pair of its own, 48 us at 0.10 of the fp64 peak at C2)
-    // work = the flop of the lower TRIANGLE, (N + K) D (D + 1) ("N D (D+1) if only the triangle"):
+    TraceScope ts(h, "fit.center_rows (K1b)", (double)N * D * 16.0, 2);
+    center_rows_kernel<<<(unsigned)ceil_div(N, (int64_t)CR_ROWS), 256, 0, h->stream>>>(dX, dlabels, means, N, K, D, Xc);
+    PLDA_LAUNCH_CHECK(h);
+  }
+  {
+    // work = the flop of the lower TRIANGLE, N D (D + 1) ("N D (D+1) if only the triangle"):
     // what the kernels execute.  (Rounds 1-3 credited the full 2 N D^2 here, which let the reported fraction pass 1.)
-    TraceScope ts(h, "fit.scatter_syrk (K2)", (double)(N + K) * D * (D + 1.0), 1);
-    PLDA_TRY(syrk_pair_f64(h, D, N, dX, D, roww, K, means, D, -1.0, S, D));
+    TraceScope ts(h, "fit.scatter_syrk (K2)", (double)N * D * (D + 1.0), 1);
+    PLDA_TRY(syrk_pair_f64(h, D, N, Xc, D, roww, 0, nullptr, 0, 0.0, S, D));
   }
   // the label checks are read back only now, with the synchronisation the pass ends on anyway: a failed check
   // leaves garbage values (never an invalid index) in what was enqueued after it

@@ -407,8 +407,9 @@ __global__ __launch_bounds__(256) void syrk_reduce_kernel(const double *__restri
 constexpr int TRI_NT = 13;                 // tile rows: D <= 208
 constexpr int TRI_LD = TRI_NT * 16 + 16;   // LDS row stride in doubles
 
-// Rows [0, K1) come from X with the weights kw (nullptr: 1), rows [K1, K) from X2 with the one weight w2 (round 3: the
-// statistics pass folds - M^T M, the centroids' term of the offset scatter, into the same launch as X^T diag(w) X).
+// Rows [0, K1) come from X with the weights kw (nullptr: 1), rows [K1, K) from X2 with the one weight w2 (the row-form EM's
+// rank-k sums; round 3 folded - M^T M, the centroids' term of the offset scatter, into the statistics pass's launch this way,
+// until that pass took the product of class-centred rows instead: K2 = 0, X2 never read).
 //
 // ZN (round 5, MPlda_norm's cohort moments, /root/reference/src/pldamodule.cpp:220-250): the rows are the cohort's
 // TRANSFORMED vectors x_i [D0 wide] and the product is taken of the augmented, shifted rows
@@ -795,6 +796,7 @@ int syrk_znorm_f64(plda_handle *h, int D0, int64_t K, const double *X, const dou
 }
 
 // C = X^T diag(kw) X + w2 X2^T X2 in one pass where the single-launch kernel applies (D <= 208), else as two products
+// (K2 = 0: the first product alone, X2 may be nullptr)
 int syrk_pair_f64(plda_handle *h, int D, int64_t K1, const double *X, int64_t ldx, const double *kw, int64_t K2,
                   const double *X2, int64_t ldx2, double w2, double *C, int64_t ldc) {
   if (D <= TRI_NT * 16 && (h->gemm64_variant == 0 || h->gemm64_variant == 6)) {
@@ -817,6 +819,7 @@ int syrk_pair_f64(plda_handle *h, int D, int64_t K1, const double *X, int64_t ld
     if (used) return PLDA_OK;
   }
   PLDA_TRY(gemm_f64(h, D, D, K1, 1.0, X, 1, ldx, X, ldx, 1, kw, 0.0, C, ldc));
+  if (K2 == 0) return PLDA_OK;           // (one source: the statistics pass's centred rows)
   return gemm_f64(h, D, D, K2, w2, X2, 1, ldx2, X2, ldx2, 1, nullptr, 1.0, C, ldc);
 }
 

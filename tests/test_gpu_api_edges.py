@@ -279,12 +279,13 @@ def test_trace_spans_cover_the_fit_stages():
     eng.trace_enable(True)
     eng.fit(X, y, 3)
     spans = {s["name"]: s for s in eng.trace_read()}
-    for name in ("fit.label_sort (K1a)", "fit.centroids (K1)", "fit.scatter_syrk (K2)", "fit.em (all iterations)",
+    for name in ("fit.label_sort (K1a)", "fit.centroids (K1)", "fit.center_rows (K1b)", "fit.scatter_syrk (K2)", "fit.em (all iterations)",
                  "getoutput.whiten (chol + inverse)", "getoutput.eig.tridiagonalise", "getoutput.eig.divide_and_conquer",
                  "getoutput.eig.back_transform", "getoutput.transform"):
         assert name in spans and spans[name]["calls"] == 1 and spans[name]["ms"] > 0.0, name
-    # (the scatter SYRK carries the centroids' term -M^T M in the same launch: N + K rows)
-    assert spans["fit.scatter_syrk (K2)"]["work"] == (600 + 60) * 40 * 41.0 and spans["fit.scatter_syrk (K2)"]["unit"] == "flop"
+    # (the scatter SYRK multiplies the N class-centred rows: the centroids' term -M^T M and its K rows are gone)
+    assert spans["fit.scatter_syrk (K2)"]["work"] == 600 * 40 * 41.0 and spans["fit.scatter_syrk (K2)"]["unit"] == "flop"
+    assert spans["fit.center_rows (K1b)"]["work"] == 600 * 40 * 16.0 and spans["fit.center_rows (K1b)"]["unit"] == "bytes"
     assert eng.trace_read() == []          # reset by the first read
     eng.trace_enable(False)
     eng.fit(X, y, 1)
