@@ -15,13 +15,15 @@ from conftest import score_tol                      # noqa: E402
 from oracle import binding as ob                    # noqa: E402
 import torch                                        # noqa: E402
 
-ob.build()
-ncases = int(sys.argv[1]) if len(sys.argv) > 1 else 60
-seed0 = int(sys.argv[2]) if len(sys.argv) > 2 else 0
-dev = torch.device("cuda", 0)
-fails = []
-forms = {}
-for case in range(ncases):
+
+def run_case(case, seed0=0, forms=None):
+    """One case of the sweep -> its failures (empty: the case passed).  tests/test_gpu_sweep.py runs a committed number
+    of these; the loop below is the hand-run form.  The creation-time switches it sets are restored on return."""
+    ob.build()
+    dev = torch.device("cuda", 0)
+    fails = []
+    forms = {} if forms is None else forms
+    saved = {k: os.environ.get(k) for k in ("PLDA_GEMM_VARIANT", "PLDA_SCORE_DTYPE", "PLDA_MIXED_VARIANT")}
     rng = np.random.default_rng(31000 + case + seed0)
     d = int(rng.choice([3, 8, 9, 16, 24, 40, 57, 64, 100, 130, 200, 256]))
     m = int(rng.choice([1, 2, 63, 64, 65, 255, 256, 257, 300, 700, 1300]))
@@ -103,7 +105,27 @@ for case in range(ncases):
         fails.append((tag, repr(e)))
         print("ERROR", tag, repr(e), flush=True)
         traceback.print_exc()
-print("stress_mixed_counts: %d cases, %d failures; extra depth histogram (depth - D, or 2D): %s" % (ncases, len(fails), forms))
-for f in fails:
-    print("  ", f)
-sys.exit(1 if fails else 0)
+    finally:
+        for k, v in saved.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+    return fails
+
+
+def main():
+    ncases = int(sys.argv[1]) if len(sys.argv) > 1 else 60
+    seed0 = int(sys.argv[2]) if len(sys.argv) > 2 else 0
+    fails = []
+    forms = {}
+    for case in range(ncases):
+        fails += run_case(case, seed0, forms)
+    print("stress_mixed_counts: %d cases, %d failures; extra depth histogram (depth - D, or 2D): %s" % (ncases, len(fails), forms))
+    for f in fails:
+        print("  ", f)
+    sys.exit(1 if fails else 0)
+
+
+if __name__ == "__main__":
+    main()

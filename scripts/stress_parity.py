@@ -14,17 +14,16 @@ from oracle import binding as ob, lda_oracle_np as lo, plda_oracle_np as onp   #
 from plda_amd import MPlda                          # noqa: E402
 from plda_amd.lda import LDA                        # noqa: E402
 
-ob.build()
-ncases = int(sys.argv[1]) if len(sys.argv) > 1 else 40
-seed0 = int(sys.argv[2]) if len(sys.argv) > 2 else 0      # second argument: offset of every seed (fresh cases)
-fails = []
-
 
 def rel(a, b):
     return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-300))
 
 
-for case in range(ncases):
+def run_case(case, seed0=0):
+    """One case of the sweep -> its failure strings (empty: the case passed).  tests/test_gpu_sweep.py runs a committed
+    number of these; the loop below is the hand-run form."""
+    ob.build()
+    fails = []
     rng = np.random.default_rng(1000 + case + seed0)
     d = int(rng.choice([1, 2, 3, 5, 8, 17, 31, 32, 33, 64, 100, 129, 200, 257, 300]))
     k = int(rng.integers(2, 40))
@@ -83,6 +82,19 @@ for case in range(ncases):
             fails.append(tag + " -> " + "; ".join(msg))
     except Exception as ex:
         fails.append(tag + " -> EXC " + repr(ex)[:200] + " | " + traceback.format_exc().splitlines()[-3][:150])
-print("%d cases, %d failures" % (ncases, len(fails)))
-for f in fails:
-    print(" ", f)
+    return fails
+
+
+def main():
+    ncases = int(sys.argv[1]) if len(sys.argv) > 1 else 40
+    seed0 = int(sys.argv[2]) if len(sys.argv) > 2 else 0      # second argument: offset of every seed (fresh cases)
+    fails = []
+    for case in range(ncases):
+        fails += run_case(case, seed0)
+    print("%d cases, %d failures" % (ncases, len(fails)))
+    for f in fails:
+        print(" ", f)
+
+
+if __name__ == "__main__":
+    main()

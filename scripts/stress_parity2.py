@@ -17,14 +17,14 @@ from plda_amd.dvector import pool                   # noqa: E402
 from plda_amd import eer as geer                    # noqa: E402
 import torch                                        # noqa: E402
 
-ob.build()
-ncases = int(sys.argv[1]) if len(sys.argv) > 1 else 40
-seed0 = int(sys.argv[2]) if len(sys.argv) > 2 else 0      # second argument: offset of every seed (fresh cases)
-fails = []
-dev = torch.device("cuda", 0)
-tmp = tempfile.mkdtemp()
 
-for case in range(ncases):
+def run_case(case, seed0=0, tmp=None):
+    """One case of the sweep -> its failure strings (empty: the case passed).  tests/test_gpu_sweep.py runs a committed
+    number of these; the loop below is the hand-run form."""
+    ob.build()
+    fails = []
+    dev = torch.device("cuda", 0)
+    tmp = tmp or tempfile.mkdtemp()
     rng = np.random.default_rng(7000 + case + seed0)
     tag = "case %d" % case
     try:
@@ -104,6 +104,20 @@ for case in range(ncases):
             fails.append(tag + " htk dim=%d F=%d" % (hd, F))
     except Exception as ex:
         fails.append(tag + " -> EXC " + repr(ex)[:200] + " | " + " / ".join(l.strip() for l in traceback.format_exc().splitlines()[-4:-1])[:300])
-print("%d cases, %d failures" % (ncases, len(fails)))
-for f in fails:
-    print(" ", f)
+    return fails
+
+
+def main():
+    ncases = int(sys.argv[1]) if len(sys.argv) > 1 else 40
+    seed0 = int(sys.argv[2]) if len(sys.argv) > 2 else 0      # second argument: offset of every seed (fresh cases)
+    fails = []
+    tmp = tempfile.mkdtemp()
+    for case in range(ncases):
+        fails += run_case(case, seed0, tmp)
+    print("%d cases, %d failures" % (ncases, len(fails)))
+    for f in fails:
+        print(" ", f)
+
+
+if __name__ == "__main__":
+    main()

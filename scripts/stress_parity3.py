@@ -12,11 +12,11 @@ from conftest import make_data          # noqa: E402
 from oracle import binding as ob        # noqa: E402
 from plda_amd import MPlda              # noqa: E402
 
-ob.build()
-ncases = int(sys.argv[1]) if len(sys.argv) > 1 else 12
-seed0 = int(sys.argv[2]) if len(sys.argv) > 2 else 0      # second argument: offset of every seed (fresh cases)
-fails = []
-for case in range(ncases):
+
+def run_case(case, seed0=0):
+    """One case of the sweep -> its failure strings (empty: the case passed).  tests/test_gpu_sweep.py runs a committed
+    number of these; the loop below is the hand-run form."""
+    ob.build()
     rng = np.random.default_rng(300 + case + seed0)
     d = int(rng.choice([48, 64, 100, 128, 200, 260]))
     k = int(rng.integers(50, 700))
@@ -34,6 +34,17 @@ for case in range(ncases):
     line = "case %d N=%d D=%d K=%d groups=%d iters=%d: psi %.1e W %.1e B %.1e (gpu %.3fs, oracle %.1fs)" % (
         case, n, d, k, groups, iters, e_psi, e_w, e_b, tg, tc)
     print(line, flush=True)
-    if not (e_psi < 1e-8 and e_w < 1e-8 and e_b < 1e-8):
-        fails.append(line)
-print("%d cases, %d failures" % (ncases, len(fails)))
+    return [] if (e_psi < 1e-8 and e_w < 1e-8 and e_b < 1e-8) else [line]
+
+
+def main():
+    ncases = int(sys.argv[1]) if len(sys.argv) > 1 else 12
+    seed0 = int(sys.argv[2]) if len(sys.argv) > 2 else 0      # second argument: offset of every seed (fresh cases)
+    fails = []
+    for case in range(ncases):
+        fails += run_case(case, seed0)
+    print("%d cases, %d failures" % (ncases, len(fails)))
+
+
+if __name__ == "__main__":
+    main()

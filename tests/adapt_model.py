@@ -154,3 +154,19 @@ def blend(model, other, alpha, alpha_mean=None):
 
 def rel(a, b):
     return float(np.abs(np.asarray(a) - np.asarray(b)).max() / np.abs(b).max())
+
+
+# ------------------------------------------------------------------------------------------ the comparison rule
+def gram(T, psi):
+    return T.T @ T, T.T @ (T * psi[:, None])
+
+
+def assert_model(got, ref, band=1e-8):
+    """mean' at 1e-12 relative; T^T T, T^T diag(psi) T and psi at `band` of the reference's largest element (transforms are
+    compared through T^T T: the rows' signs are free)."""
+    assert np.abs(got["mean"] - ref["mean"]).max() <= 1e-12 * np.abs(ref["mean"]).max()
+    g1, g2 = gram(got["transform"], got["psi"])
+    r1, r2 = gram(ref["transform"], ref["psi"])
+    assert np.abs(g1 - r1).max() <= band * np.abs(r1).max()
+    assert np.abs(g2 - r2).max() <= band * np.abs(r2).max()
+    assert np.abs(got["psi"] - ref["psi"]).max() <= band * np.abs(ref["psi"]).max()

@@ -6,6 +6,9 @@ restated in NumPy, independent of the product's arithmetic.
                          np.partition on the fp32 values; moments in np.longdouble, two-pass, around the boundary value tau
                          (s - tau is exact), rounded once to float64.  All-equal top-K sets give std exactly 0 and mean
                          exactly that value.
+  compaction_attempts(row32, K)   the structure of the selection kernel restated: per attempt to compact the candidates into
+                         LDS, (level, candidates, the largest count in one of the 16 wave shares) -- the tests use it to know
+                         which path a row takes (candidates <= GATE and a share above WCAP: the cap overflow)
   snorm_sides / snorm_apply   the two-sided map on finished fp32 scores in fp64 (NOT rounded to fp32: the caller rounds).
 """
 import numpy as np
@@ -38,6 +41,41 @@ def topk_width(S32, K):
     """max T(r) - min T(r) per row, in fp64 (the `w` of the derived tolerances)."""
     S32 = np.atleast_2d(np.asarray(S32, np.float32))
     return np.array([np.float64(T.max()) - np.float64(T.min()) for T in (topk_values(row, K) for row in S32)])
+
+
+WAVES, WCAP, GATE = 16, 1024, 8192         # SN_WAVES, SN_WCAP, SN_GATE of csrc/snorm.hip
+LEVELS = ((21, 11), (10, 11), (0, 10))     # (shift, bits) of the three radix levels
+
+
+def _keys(row32):
+    u = np.ascontiguousarray(row32, np.float32).view(np.uint32).astype(np.uint64)
+    u = np.where(u == 0x80000000, 0, u)
+    return np.where(u & 0x80000000, u ^ 0xffffffff, u | 0x80000000).astype(np.uint64)
+
+
+def compaction_attempts(row32, K):
+    """[(level, candidates, max per wave share)] of one row: after a level the keys at or above the boundary bin's lower edge
+    are compacted, each of the 16 waves its contiguous share of quads, when they number at most GATE; a share above WCAP
+    overflows and the next level tries again."""
+    key = _keys(row32)
+    nc = key.shape[0]
+    seg = -(-((nc + 3) // 4) // WAVES)
+    wave = (np.arange(nc) // 4) // seg
+    prefix, above_all, out = 0, 0, []
+    for level, (shift, bits) in enumerate(LEVELS):
+        live = key if level == 0 else key[(key >> np.uint64(shift + bits)) == prefix]
+        hist = np.bincount(((live >> np.uint64(shift)) & np.uint64((1 << bits) - 1)).astype(np.int64), minlength=1 << bits)[::-1]
+        cum = np.cumsum(hist)
+        i = int(np.searchsorted(cum, K - above_all))
+        above_all += int(cum[i] - hist[i])
+        prefix = (prefix << bits) | ((1 << bits) - 1 - i)
+        if level < 2 and above_all + int(hist[i]) <= GATE:
+            cand = key >= np.uint64(prefix << shift)
+            per = np.bincount(wave[cand], minlength=WAVES)
+            out.append((level, int(cand.sum()), int(per.max())))
+            if per.max() <= WCAP:
+                break
+    return out
 
 
 def snorm_sides(raw32, emean=None, estd=None, tmean=None, tstd=None):

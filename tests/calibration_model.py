@@ -233,3 +233,10 @@ def apply_map(s32, a, b):
     the 53 x 24-bit product exactly on x86; where its 64-bit sum rounds, tests decide with fractions.Fraction)."""
     s = np.asarray(s32, np.float32).astype(np.longdouble)
     return (np.longdouble(a) * s + np.longdouble(b)).astype(np.float64).astype(np.float32)
+
+
+def equivariant(a, b, a2, b2, k, d):
+    """Is (a2, b2) the fit of the scores k * s + d, given the fit (a, b) of s?  The map undoes the scale and the shift: a2 = a / k
+    to 1e-5 relative, b2 = b - a d / k to 1e-5 absolute (the one statement of the equivariance rule: the device test asserts it,
+    the sweep's generator filters its draws by it)."""
+    return abs(a2 - a / k) <= max(1e-5 * abs(a / k), 1e-12) and abs(b2 - (b - a * d / k)) <= 1e-5

@@ -47,19 +47,15 @@ def _same(a, b):
     return all(np.array_equal(x.view(np.uint8), y.view(np.uint8)) for x, y in zip(a, b))
 
 
-def _gram(T, psi):
-    return T.T @ T, T.T @ (T * psi[:, None])
+_gram, _assert_model = AM.gram, AM.assert_model
 
 
-def _assert_model(got, ref, band=1e-8):
-    """mean' at 1e-12 relative; T^T T, T^T diag(psi) T and psi at `band` of the reference's largest element (transforms are
-    compared through T^T T: the rows' signs are free)."""
-    assert np.abs(got["mean"] - ref["mean"]).max() <= 1e-12 * np.abs(ref["mean"]).max()
-    g1, g2 = _gram(got["transform"], got["psi"])
-    r1, r2 = _gram(ref["transform"], ref["psi"])
-    assert np.abs(g1 - r1).max() <= band * np.abs(r1).max()
-    assert np.abs(g2 - r2).max() <= band * np.abs(r2).max()
-    assert np.abs(got["psi"] - ref["psi"]).max() <= band * np.abs(ref["psi"]).max()
+def _assert_record(st, ref, x, mean, w):
+    """the record rule: |delta| <= 1e-12 sum w |x - p|_i |x - p|_j elementwise against the model's record, the pilot the model
+    mean, S2 symmetric to the bit"""
+    assert st["rows"] == x.shape[0] and np.array_equal(st["pilot"], mean)
+    assert (np.abs(_aug(st) - AM.augmented(ref)) <= 1e-12 * AM.record_bound(x, mean, w)).all(), x.shape
+    assert np.array_equal(st["s2"], st["s2"].T)
 
 
 def _domain_rows(model, kind, offset):
@@ -91,9 +87,7 @@ def test_record_matches_model(d):
             eng.adapt_accumulate(x, w)
             st = eng.adapt_stats()
             ref = AM.record(x, mean, w)
-            assert st["rows"] == n and np.array_equal(st["pilot"], mean)
-            assert (np.abs(_aug(st) - AM.augmented(ref)) <= 1e-12 * AM.record_bound(x, mean, w)).all(), (d, n)
-            assert np.array_equal(st["s2"], st["s2"].T)
+            _assert_record(st, ref, x, mean, w)
 
 
 # ------------------------------------------------------------------------------------------------------------ 2. slabs

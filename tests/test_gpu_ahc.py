@@ -340,6 +340,34 @@ def test_create_cluster_destroy_gives_back_every_byte(lds_max):
 
 
 # ------------------------------------------------------------------------------------------- operand form
+def _scored_blocks(eng, dX, offsets):
+    """every recording's block as plda_score_matrix_dev writes it (ld_out = N) from the device rows dX"""
+    import torch
+    blocks = []
+    for q in range(len(offsets) - 1):
+        n = int(offsets[q + 1] - offsets[q])
+        S = torch.full((n, n), float("nan"), dtype=torch.float32, device=_dev())
+        x = dX[int(offsets[q]):int(offsets[q + 1])]
+        torch.cuda.synchronize()
+        eng.score_matrix_dev(x.data_ptr(), None, 1, n, x.data_ptr(), n, S.data_ptr(), n)
+        eng.synchronize()
+        blocks.append(S.cpu().numpy())
+    return blocks
+
+
+def _run_operands(eng, dX, offsets, thr, ns):
+    """plda_score_ahc_dev with guarded outputs -> (labels, n_clusters, merge_a, merge_b, merge_cost)"""
+    import torch
+    has_t, t, minc = _stop(offsets, thr, ns)
+    tot, r = int(offsets[-1]), len(offsets) - 1
+    oL, oK = _Out(tot, torch.int32), _Out(r, torch.int32)
+    oA, oB, oC = _Out(tot - r, torch.int32), _Out(tot - r, torch.int32), _Out(tot - r, torch.float64)
+    torch.cuda.synchronize()
+    eng.score_ahc_dev(dX.data_ptr(), offsets, has_t, t, minc, oL.ptr(), oK.ptr(), oA.ptr(), oB.ptr(), oC.ptr())
+    torch.cuda.synchronize()
+    return (oL.check("labels"), oK.check("n_clusters"), oA.check("merge_a"), oB.check("merge_b"), oC.check("merge_cost"))
+
+
 @pytest.mark.parametrize("d", [8, 200])
 def test_operand_form_equals_matrix_form_on_scored_blocks(eng, d):
     """recordings of 1, 5, 64 and 200 segments: plda_score_ahc_dev == plda_ahc_matrix_dev on the blocks plda_score_matrix_dev
@@ -353,23 +381,9 @@ def test_operand_form_equals_matrix_form_on_scored_blocks(eng, d):
     spk = rng.standard_normal((6, d)) * 1.5
     vecs = np.concatenate([spk[rng.integers(0, 6, n)] + rng.standard_normal((n, d)) for n in sizes])
     dX = torch.from_numpy(vecs).to(_dev())
-    blocks = []
-    for q, n in enumerate(sizes):
-        S = torch.full((n, n), float("nan"), dtype=torch.float32, device=_dev())
-        x = dX[int(offsets[q]):int(offsets[q + 1])]
-        torch.cuda.synchronize()
-        eng.score_matrix_dev(x.data_ptr(), None, 1, n, x.data_ptr(), n, S.data_ptr(), n)
-        eng.synchronize()
-        blocks.append(S.cpu().numpy())
+    blocks = _scored_blocks(eng, dX, offsets)
     for thr, ns in ((0.0, None), (None, 2), (5.0, [1, 2, 3, 4])):
-        has_t, t, minc = _stop(offsets, thr, ns)
-        tot, r = int(offsets[-1]), len(sizes)
-        oL, oK = _Out(tot, torch.int32), _Out(r, torch.int32)
-        oA, oB, oC = _Out(tot - r, torch.int32), _Out(tot - r, torch.int32), _Out(tot - r, torch.float64)
-        torch.cuda.synchronize()
-        eng.score_ahc_dev(dX.data_ptr(), offsets, has_t, t, minc, oL.ptr(), oK.ptr(), oA.ptr(), oB.ptr(), oC.ptr())
-        torch.cuda.synchronize()
-        got = (oL.check("labels"), oK.check("n_clusters"), oA.check("merge_a"), oB.check("merge_b"), oC.check("merge_cost"))
+        got = _run_operands(eng, dX, offsets, thr, ns)
         _assert_equal(got, _run(eng, blocks, thr, ns), "operand against matrix form")
         _assert_equal(got, M.cluster(blocks, thr, ns), "operand form against the model")
         host = diarize.ahc_vectors(eng, vecs, offsets, thr, ns, return_merges=True)

@@ -67,6 +67,13 @@ def test_eer_of_a_trials_matrix(eng, oracle):
     assert eer.format_line(out[1], out[2], out[0]).startswith("EER = ")
 
 
+def _assert_matrix_eer(out, ref, tgt):
+    """the six numbers of eer_from_matrix_dev against onp.eer of the same scores: counts and rates exactly, the threshold to
+    1e-12 relative (the restatement works in fp64 on the fp32 scores)"""
+    assert out[4] == tgt.sum() and out[5] == (~tgt).sum()
+    assert tuple(out[1:4]) == ref[1:] and out[0] == pytest.approx(ref[0], rel=1e-12)
+
+
 @pytest.mark.parametrize("m,nt,ld,k,off", [(1, 2, 2, 1, 0), (3, 5, 7, 2, 0), (2, 1023, 1023, 3, 0), (257, 1023, 1023, 9, 0),
                                            (300, 1025, 1028, 16, 0), (7, 4099, 4100, 5, 0), (5000, 3001, 3001, 40, 0),
                                            (513, 1025, 1028, 16, 1)],
@@ -98,8 +105,7 @@ def test_eer_of_ragged_matrices(eng, m, nt, ld, k, off):
     out = eer.eer_from_matrix_dev(eng, S.data_ptr() + 4 * off, ld, m, nt, des.data_ptr(), dts.data_ptr())
     sub = Sh[:, :nt]
     ref = onp.eer(sub[~tgt], sub[tgt])
-    assert out[4] == tgt.sum() and out[5] == (~tgt).sum()
-    assert tuple(out[1:4]) == ref[1:] and out[0] == pytest.approx(ref[0], rel=1e-12)
+    _assert_matrix_eer(out, ref, tgt)
 
 
 def _eer_rank(rank, world, port, q):

@@ -323,6 +323,22 @@ def _fit_case(rng, m, nt, k):
     return es, ts, tgt, S
 
 
+def _assert_fit_is_optimal(f, pos, neg, k, prior):
+    """the optimality rule: the MODEL's own lambda2 at the device's (a, b) is at most 1e-17 (10 x the fit's tolerance); Cllr
+    after within BOUND of the model's; the pass count.  Returns lambda2."""
+    rec = fm.pass_record(pos, neg, f.a, f.b + fm.logit(prior))
+    assert (k + 1) * rec["Ymax"] <= 2000.0
+    lam2 = fm.newton(rec, prior)[2]
+    assert f.converged and not f.separable and f.n_systems == k and f.prior == prior
+    assert lam2 <= 1e-17, lam2
+    after = fm.pass_record(pos, neg, f.a, f.b)
+    scale = 0.5 / after["Np"] * after["abs"]["L_t"] + 0.5 / after["Nn"] * after["abs"]["L_n"]
+    assert abs(f.cllr_after * fm.LN2 - fm.objective(after, 0.5)) <= BOUND * scale
+    # one pass at the start, one per trial point (at least one per iteration), one more for cllr_after off prior 0.5
+    assert 1 + f.iterations + (prior != 0.5) <= f.passes <= 100 + 30 + 2
+    return lam2
+
+
 @pytest.mark.parametrize("prior", [0.5, 0.05])
 @pytest.mark.parametrize("k", [2, 4])
 def test_fit_is_optimal_by_the_models_own_derivatives(monkeypatch, k, prior):
@@ -340,21 +356,12 @@ def test_fit_is_optimal_by_the_models_own_derivatives(monkeypatch, k, prior):
     singles = [CB.fit_from_matrix_dev(eng, P.ptrs[j], P.lds[j], m, nt, des.data_ptr(), dts.data_ptr(), prior) for j in range(k)]
     best_single = min(c.cllr_after for c in singles)
     for what, f in fits.items():
-        rec = fm.pass_record(pos, neg, f.a, f.b + fm.logit(prior))
-        assert (k + 1) * rec["Ymax"] <= 2000.0
-        lam2 = fm.newton(rec, prior)[2]
+        lam2 = _assert_fit_is_optimal(f, pos, neg, k, prior)
         print("%s K %d prior %g: b = %.9g a = %s, model lambda2 there = %.3g, %d iterations, %d passes (model fit: %d, %d); "
               "Cllr %.5f, best single system %.5f" % (what, k, prior, f.b, f.a, lam2, f.iterations, f.passes, ref["iterations"],
                                                       ref["passes"], f.cllr_after, best_single))
-        assert f.converged and not f.separable and f.n_systems == k and f.prior == prior
-        assert lam2 <= 1e-17
-        after = fm.pass_record(pos, neg, f.a, f.b)
-        scale = 0.5 / after["Np"] * after["abs"]["L_t"] + 0.5 / after["Nn"] * after["abs"]["L_n"]
-        assert abs(f.cllr_after * fm.LN2 - fm.objective(after, 0.5)) <= BOUND * scale
         assert f.cllr_after <= best_single
         assert f.objective <= min(c.objective for c in singles) + 1e-12      # nested models, the same objective: guaranteed
-        # one pass at the start, one per trial point (at least one per iteration), one more for cllr_after off prior 0.5
-        assert 1 + f.iterations + (prior != 0.5) <= f.passes <= 100 + 30 + 2
         assert np.allclose(f.a, ref["a"], rtol=1e-6, atol=0)
     assert P.unchanged()
 
