@@ -964,8 +964,8 @@ int plda_blend_model(plda_handle *h, int32_t D, const double *mean2, const doubl
  *                         into the S-norm slab buffer, as many consecutive recordings at a time as the budget above holds
  *                         (each block at a 256-byte boundary), clustered, dropped.  A prepared test side is dropped, as in
  *                         plda_cohort_stats_dev.
- * OUT OF SCOPE, each on purpose: Kaldi's per-recording mean subtraction and PCA before scoring; its two-pass clustering of very
- * long recordings; several workgroups on one recording.  (DER is the section "diarisation error rate" below; RTTM files are
+ * OUT OF SCOPE, each on purpose: Kaldi's per-recording mean subtraction; its two-pass clustering of very long recordings;
+ * several workgroups on one recording.  (The per-recording PCA before scoring is the next section.)  (DER is the section "diarisation error rate" below; RTTM files are
  * read and written by plda_amd/rttm.py, on the host.) ---- */
 #define PLDA_AHC_MAX 4096
 int plda_ahc_plan(plda_handle *h, int64_t N, int32_t out[3]);
@@ -981,6 +981,77 @@ int plda_score_ahc_dev(plda_handle *h, const double *dX, const int64_t *offsets,
 int plda_score_ahc(plda_handle *h, const double *X, const int64_t *offsets, int64_t R, int32_t has_threshold, double threshold,
                    const int32_t *min_clusters, int32_t *labels, int32_t *n_clusters, int32_t *merge_a, int32_t *merge_b,
                    double *merge_cost);
+
+/* ---- dense scoring in a recording's PCA subspace (K19; csrc/dense_pca.hip): Kaldi's ivector-plda-scoring-dense
+ * --target-energy=t restated (EstPca, Plda::ApplyTransform, TransformIvector, LogLikelihoodRatio; parity unpinned like the rest
+ * of PLDA).  The reference has NO counterpart; tests/dense_pca_model.py is the NumPy model.  Everything is fp64; a score is
+ * rounded to fp32 once.
+ *
+ * The model (mean, transform T [D, D], psi) must be untruncated, Dout = Din = D <= PLDA_DENSE_PCA_MAX_DIM.  Once per model:
+ * W = T^-1 T^-T and B = T^-1 diag(psi) T^-T (the domain adaptation's routine, kept on the handle until the model changes).
+ *
+ * A RECORDING r owns rows offsets[r] .. offsets[r+1] of X [T, D], in the model's INPUT space, 1 <= N <= PLDA_AHC_MAX.
+ *   1. mu = the mean of its rows, formed as x_0 + mean(x_i - x_0) so that equal rows centre to exact zeros;
+ *      C = (1 / N) sum (x_i - mu)(x_i - mu)^T from the centred rows.  m = min(N, D).  For N <= D the solver works on the Gram
+ *      matrix G = (1 / N) Xc Xc^T [N, N], which has the same non-zero eigenvalues; the eigenvectors of C are then
+ *      p_k = Xc^T u_k / sqrt(N lam_k).
+ *   2. lam_1 >= ... >= lam_m (floored at 0), E = their sum in that order; the rank is rho = #{k : lam_k > 2^-40 lam_1}.
+ *   3. Kaldi's rule to the letter: dim = 1, energy = 0; while energy / E <= target_energy: energy += lam[dim - 1], dim++ (one
+ *      more than the smallest count whose energy share exceeds the target).  d = min(dim, rho): where Kaldi would keep a
+ *      direction of zero variance that its SVD picks arbitrarily, it is DROPPED here.  E = 0 (N = 1, or all rows equal):
+ *      d = 0 and the whole block is +0.0f.
+ *   4. P [d, D]: the d leading eigenvectors as rows.
+ *   5. W' = P W P^T, B' = P B P^T (each symmetrised); Cholesky W' = L L^T; L^-1 B' L^-T = U diag(psi') U^T, psi' descending;
+ *      M = U^T L^-1 P [d, D].  W' not positive definite: PLDA_E_NUMERIC naming the (first such) recording.
+ *   6. y_i = M (x_i - mean), scaled by sqrt(d / sum_k y_ik^2 / (psi'_k + 1)): plda_transform_rows with num_examples = 1.
+ *   7. S[i, j] = LogLikelihoodRatio(enrol y_i with n = 1, test y_j), the diagonal like any other entry; no z-norm, no
+ *      calibration.  The block is stored row-major N x N at dscores + block_off[r], the format plda_ahc_matrix_dev reads.
+ * The scores depend on the retained subspace only, not on the basis inside it; with d = D they are the full model's.
+ *
+ * METHOD.  One workgroup per recording runs steps 1 to 7 in one kernel.  Both eigenproblems (order m, then order d) go through
+ * one routine, a two-sided cyclic Jacobi in round-robin order (floor((m + 1) / 2) disjoint rotations per round, odd m with a
+ * bye): the angles of a round, then its row phase (A and the eigenvectors), then its column phase, workgroup barriers between.
+ * A pair is left alone when |a_pq| <= 2^-52 sqrt(|a_pp a_qq|) or |a_pq| <= 2^-92 max_i |a_ii| at entry (on a null direction
+ * a_pp is a rounding residue of either sign and the first test cannot be met; such an entry is 2^52 times below what the rank
+ * rule can see); a sweep without a rotation ends the solve; 40 sweeps without one: PLDA_E_NUMERIC naming the recording.  The
+ * matrix itself is rotated from both sides, never its square.  The rotation order depends on m alone and every sum has a fixed
+ * order: a recording's block is bit-identical alone, in any batch, under any launch grouping, and from run to run.  Two
+ * dispatch classes: the LDS class (m up to out[3] of the plan) keeps the working matrix and the eigenvectors in the 160 KiB of
+ * LDS of one compute unit, the HBM class in handle scratch; centred rows, basis, projected model and projected rows are in
+ * handle scratch in both, carved per recording from one layout list.  Consecutive recordings are grouped into launches under
+ * the AHC's 2 GiB scratch budget (PLDA_AHC_SCRATCH_BYTES sets another: tests), at most two launches per group: the number of
+ * launches of a call does not depend on R.  The scratch belongs to the handle and is freed by plda_destroy.
+ *
+ *   plda_dense_pca_plan        out[0] = the class of a recording of N segments at dimension D (0 LDS, 1 HBM), out[1] = the
+ *                              scratch bytes one such recording takes, out[2] = m, out[3] = the largest m of the LDS class.
+ *   plda_score_dense_pca_dev   X, scores and the nullable ddims int32 [R] (d of every recording) and deig fp64 [T] (recording r
+ *                              owns entries offsets[r] .. offsets[r+1]: its m eigenvalues, descending, then zeros) in HBM;
+ *                              offsets [R + 1] and block_off [R + 1] (floats) are HOST arrays, the convention of
+ *                              plda_ahc_matrix_dev.  Synchronises the handle's stream once (twice on the first call after a
+ *                              model change, which forms W and B).
+ *   plda_score_dense_pca       the same with everything in host memory.
+ *   plda_score_dense_pca_ahc*  the blocks go into the S-norm slab buffer, as many consecutive recordings at a time as the
+ *                              budget holds, are clustered by plda_ahc_matrix_dev's own path and dropped: labels, n_clusters
+ *                              and the nullable merge record as in "speaker clustering" above, equal to plda_ahc_matrix on the
+ *                              blocks of plda_score_dense_pca.
+ * ERRORS.  PLDA_E_NOT_FITTED without a model.  PLDA_E_INVAL: target_energy outside (0, 1), offsets that do not ascend from 0,
+ * an empty recording or one above PLDA_AHC_MAX, block_off[r+1] - block_off[r] < N_r^2, D > PLDA_DENSE_PCA_MAX_DIM, a truncated
+ * model, the clustering's own argument errors; a row with a non-finite element fails the call with the count of such rows in
+ * plda_last_error, and nothing is written.  PLDA_E_NUMERIC as above; the outputs of such a call are unspecified.
+ * OUT OF SCOPE, each on purpose: Kaldi's per-recording mean subtraction of the vectors before the PCA estimate is applied to
+ * them; several workgroups on one recording; an fp64 matrix-core tile for the covariance. ---- */
+#define PLDA_DENSE_PCA_MAX_DIM 512
+int plda_dense_pca_plan(plda_handle *h, int64_t N, int32_t D, int32_t out[4]);
+int plda_score_dense_pca_dev(plda_handle *h, const double *dX, const int64_t *offsets, int64_t R, double target_energy,
+                             float *dscores, const int64_t *block_off, int32_t *ddims, double *deig);
+int plda_score_dense_pca(plda_handle *h, const double *X, const int64_t *offsets, int64_t R, double target_energy, float *scores,
+                         const int64_t *block_off, int32_t *dims, double *eig);
+int plda_score_dense_pca_ahc_dev(plda_handle *h, const double *dX, const int64_t *offsets, int64_t R, double target_energy,
+                                 int32_t has_threshold, double threshold, const int32_t *min_clusters, int32_t *dlabels,
+                                 int32_t *dn_clusters, int32_t *dmerge_a, int32_t *dmerge_b, double *dmerge_cost);
+int plda_score_dense_pca_ahc(plda_handle *h, const double *X, const int64_t *offsets, int64_t R, double target_energy,
+                             int32_t has_threshold, double threshold, const int32_t *min_clusters, int32_t *labels,
+                             int32_t *n_clusters, int32_t *merge_a, int32_t *merge_b, double *merge_cost);
 
 /* ---- VBx resegmentation (K16; csrc/vbx.hip): a batched variational-Bayes HMM over the segment sequence of every recording,
  * the step every x-vector diarisation recipe runs behind the AHC (Landini et al., "Bayesian HMM clustering of x-vector
@@ -1190,7 +1261,7 @@ int plda_der_sweep(plda_handle *h, const int32_t *merge_a, const int32_t *merge_
  *                        of plda_embed_set.  An error leaves the installed chain bit-identical.  Scratch: all of v, N Din 8 bytes,
  *                        plus O(Din^2 + K Din).
  *   plda_embed_fit       the same with host arrays; K is found from the labels (max + 1).
- * OUT OF SCOPE, each on purpose: Kaldi's per-recording PCA of ivector-plda-scoring-dense; fp32 or bf16 output; more than one
+ * OUT OF SCOPE, each on purpose: fp32 or bf16 output; more than one
  * matrix per chain; within-class covariance normalisation and a cosine back-end. ---- */
 #define PLDA_EMBED_MAX_DIN 4096
 #define PLDA_EMBED_MAX_DOUT 2048

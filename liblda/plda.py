@@ -83,29 +83,42 @@ class PLDA(object):
         self._instance.blend(other, alpha, alpha_mean)
         return self
 
-    def cluster(self, x, offsets, threshold=0.0, num_speakers=None, return_merges=False):
+    def cluster(self, x, offsets, threshold=0.0, num_speakers=None, return_merges=False, target_energy=None):
         """Cluster the segments of R recordings (diarisation): x [T, featdim] raw segment vectors, recording r owning rows
         offsets[r] .. offsets[r+1]; average-linkage merging while the best pair's average score is at least `threshold` and
-        more than `num_speakers` clusters are left.  Returns (labels, n_clusters[, merges]); plda_amd/diarize.py."""
-        return self._instance.cluster(x, offsets, threshold, num_speakers, return_merges)
+        more than `num_speakers` clusters are left.  target_energy=t: every recording is scored in the PCA subspace of its own
+        vectors (Kaldi's --target-energy).  Returns (labels, n_clusters[, merges]); plda_amd/diarize.py."""
+        if target_energy is None:
+            return self._instance.cluster(x, offsets, threshold, num_speakers, return_merges)
+        return self._instance.cluster(x, offsets, threshold, num_speakers, return_merges, target_energy=target_energy)
+
+    def score_dense(self, x, offsets, target_energy, return_info=False):
+        """Every recording's segment pairs scored in the PCA subspace of its own segment vectors; a list of [N_r, N_r] float32
+        blocks[, {"dims", "eigenvalues"}]; plda_amd/diarize.py."""
+        return self._instance.score_dense(x, offsets, target_energy, return_info)
 
     def resegment(self, x, offsets, labels, **vbx):
         """VBx resegmentation of the segments of R recordings from initial labels (cluster()'s); plda_amd/diarize.py."""
         return self._instance.resegment(x, offsets, labels, **vbx)
 
-    def diarize(self, x, offsets, threshold=0.0, num_speakers=None, **vbx):
-        """cluster, then resegment.  Returns (labels, n_clusters[, info])."""
-        return self._instance.diarize(x, offsets, threshold, num_speakers, **vbx)
+    def diarize(self, x, offsets, threshold=0.0, num_speakers=None, target_energy=None, **vbx):
+        """cluster, then resegment.  target_energy goes to the clustering only (VBx keeps working on the full model).  Returns
+        (labels, n_clusters[, info])."""
+        if target_energy is None:
+            return self._instance.diarize(x, offsets, threshold, num_speakers, **vbx)
+        return self._instance.diarize(x, offsets, threshold, num_speakers, target_energy=target_energy, **vbx)
 
     def der(self, ref, hyp, offsets, dur=None, return_map=False):
         """Diarisation error rate of R recordings from per-segment reference and hypothesis labels (-1 = non-speech), under
         the optimal speaker mapping; plda_amd/der.py.  Returns a DerResult (counts, der, total[, map])."""
         return self._instance.der(ref, hyp, offsets, dur, return_map)
 
-    def tune_threshold(self, x, offsets, ref, thresholds, dur=None):
-        """The clustering threshold of the lowest pooled DER on a development set: one clustering, one sweep of its merge
-        record.  Returns (threshold, SweepResult); plda_amd/der.py."""
-        return self._instance.tune_threshold(x, offsets, ref, thresholds, dur)
+    def tune_threshold(self, x, offsets, ref, thresholds, dur=None, target_energy=None):
+        """The clustering threshold of the lowest pooled DER on a development set: one clustering (behind the per-recording PCA
+        when target_energy is given), one sweep of its merge record.  Returns (threshold, SweepResult); plda_amd/der.py."""
+        if target_energy is None:
+            return self._instance.tune_threshold(x, offsets, ref, thresholds, dur)
+        return self._instance.tune_threshold(x, offsets, ref, thresholds, dur, target_energy=target_energy)
 
     def transform_array(self, xbar, num_examples=1):
         return self._instance.transform_array(xbar, num_examples)

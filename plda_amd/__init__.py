@@ -10,7 +10,7 @@ Layout (only what the hot path needs):
   fusion.py   linear fusion of K systems' scores by logistic regression (csrc/fusion.hip)
   adaptation.py the result of MPlda.adapt: unsupervised PLDA domain adaptation and model interpolation (csrc/adapt.hip)
   identify.py rank-N identification rates and the CMC curve from the ids of MPlda.top_n (csrc/topn.hip); pure NumPy
-  diarize.py  speaker clustering: batched average-linkage AHC on score blocks (csrc/ahc.hip), cut() in pure NumPy; VBx resegmentation (csrc/vbx.hip)
+  diarize.py  speaker clustering: batched average-linkage AHC on score blocks (csrc/ahc.hip), cut() in pure NumPy; VBx resegmentation (csrc/vbx.hip); dense scoring in every recording's PCA subspace (csrc/dense_pca.hip)
   der.py      diarisation error rate under the optimal speaker mapping, and the sweep of one merge record over thresholds (csrc/der.hip)
   rttm.py     RTTM files and per-segment reference labels from reference turns; pure Python / NumPy
 """

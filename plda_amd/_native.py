@@ -146,6 +146,11 @@ SIGNATURES = {
     "plda_ahc_matrix": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _f64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "plda_score_ahc_dev": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _f64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "plda_score_ahc": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _f64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "plda_dense_pca_plan": (C.c_int, [_vp, _i64, _i32, _vp]),
+    "plda_score_dense_pca_dev": (C.c_int, [_vp, _vp, _vp, _i64, _f64, _vp, _vp, _vp, _vp]),
+    "plda_score_dense_pca": (C.c_int, [_vp, _vp, _vp, _i64, _f64, _vp, _vp, _vp, _vp]),
+    "plda_score_dense_pca_ahc_dev": (C.c_int, [_vp, _vp, _vp, _i64, _f64, _i32, _f64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "plda_score_dense_pca_ahc": (C.c_int, [_vp, _vp, _vp, _i64, _f64, _i32, _f64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "plda_der_plan": (C.c_int, [_vp, _i64, _i64, _vp]),
     "plda_der_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
     "plda_der": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),

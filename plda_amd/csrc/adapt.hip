@@ -203,18 +203,10 @@ int work_layout(plda_handle *h, int D, Work *w) {
   return PLDA_OK;
 }
 
-// W = (T^T T)^-1, Tinv = T^-1 = W T^T, B = Tinv diag(psi) Tinv^T  (tmp, scr: scratch; *flag: set when T^T T is not SPD)
+// W, B and Tinv of a model inside a Work (model_covariances_f64 below)
 int model_covariances(plda_handle *h, const double *T, const double *psi, int D, const Work &w, double *W, double *B,
                       double *Tinv, int *flag) {
-  const size_t DD = w.DD;
-  PLDA_TRY(gemm_f64(h, D, D, D, 1.0, T, 1, D, T, D, 1, nullptr, 0.0, w.tmp, D));
-  PLDA_TRY(spd_inverse_blocked(h, w.tmp, D, D, (int64_t)DD, W, D, (int64_t)DD, w.scr, (int64_t)(3 * DD), flag, 1));
-  adapt_symmetrize_kernel<<<blocks((int64_t)DD), 256, 0, h->stream>>>(W, D);
-  PLDA_LAUNCH_CHECK(h);
-  PLDA_TRY(gemm_f64(h, D, D, D, 1.0, W, D, 1, T, 1, D, nullptr, 0.0, Tinv, D));
-  adapt_scale_kernel<<<blocks((int64_t)DD), 256, 0, h->stream>>>(Tinv, psi, D, 0, 0, w.tmp);
-  PLDA_LAUNCH_CHECK(h);
-  return gemm_f64(h, D, D, D, 1.0, w.tmp, D, 1, w.tmp, 1, D, nullptr, 0.0, B, D);
+  return model_covariances_f64(h, T, psi, D, W, B, Tinv, w.tmp, w.scr, flag);
 }
 
 // (W', B') in w.W / w.B -> the staged model, read back with the status words; installs it on success.  `chain` enqueues
@@ -282,6 +274,21 @@ int64_t slab_rows_for(const plda_handle *h, int ld) {
 }
 
 }  // namespace
+
+// W = (T^T T)^-1, Tinv = T^-1 = W T^T, B = Tinv diag(psi) Tinv^T  (tmp: D^2, scr: 3 D^2 doubles of scratch; *flag: set when
+// T^T T is not SPD).  Shared with dense_pca.hip, which projects the same two covariances.
+int model_covariances_f64(plda_handle *h, const double *T, const double *psi, int D, double *W, double *B, double *Tinv, double *tmp,
+                          double *scr, int *flag) {
+  const size_t DD = (size_t)D * D;
+  PLDA_TRY(gemm_f64(h, D, D, D, 1.0, T, 1, D, T, D, 1, nullptr, 0.0, tmp, D));
+  PLDA_TRY(spd_inverse_blocked(h, tmp, D, D, (int64_t)DD, W, D, (int64_t)DD, scr, (int64_t)(3 * DD), flag, 1));
+  adapt_symmetrize_kernel<<<blocks((int64_t)DD), 256, 0, h->stream>>>(W, D);
+  PLDA_LAUNCH_CHECK(h);
+  PLDA_TRY(gemm_f64(h, D, D, D, 1.0, W, D, 1, T, 1, D, nullptr, 0.0, Tinv, D));
+  adapt_scale_kernel<<<blocks((int64_t)DD), 256, 0, h->stream>>>(Tinv, psi, D, 0, 0, tmp);
+  PLDA_LAUNCH_CHECK(h);
+  return gemm_f64(h, D, D, D, 1.0, tmp, D, 1, tmp, 1, D, nullptr, 0.0, B, D);
+}
 
 int adapt_reset(plda_handle *h) {
   h->ad_has = false;

@@ -2217,6 +2217,100 @@ int plda_score_ahc(plda_handle *h, const double *X, const int64_t *offsets, int6
   });
 }
 
+// ---------------------------------------------------------------- dense scoring in a recording's PCA subspace (dense_pca.hip)
+int plda_dense_pca_plan(plda_handle *h, int64_t N, int32_t D, int32_t out[4]) {
+  return guarded(h, "plda_dense_pca_plan", [&]() -> int {
+    if (!h) return PLDA_E_INVAL;
+    PLDA_LOCK(h);
+    return dense_pca_plan(h, N, D, out);
+  });
+}
+
+int plda_score_dense_pca_dev(plda_handle *h, const double *dX, const int64_t *offsets, int64_t R, double target_energy,
+                             float *dscores, const int64_t *block_off, int32_t *ddims, double *deig) {
+  return guarded(h, "plda_score_dense_pca_dev", [&]() -> int {
+    if (!h) return PLDA_E_INVAL;
+    PLDA_LOCK(h);
+    PLDA_TRY(set_device(h));
+    return score_dense_pca_device(h, dX, offsets, R, target_energy, dscores, block_off, ddims, deig);
+  });
+}
+
+int plda_score_dense_pca(plda_handle *h, const double *X, const int64_t *offsets, int64_t R, double target_energy, float *scores,
+                         const int64_t *block_off, int32_t *dims, double *eig) {
+  return guarded(h, "plda_score_dense_pca", [&]() -> int {
+    if (!h) return PLDA_E_INVAL;
+    PLDA_LOCK(h);
+    PLDA_TRY(dense_pca_validate(h, "score_dense_pca", offsets, R, target_energy, block_off, true));
+    if (!X) return fail(h, PLDA_E_INVAL, "score_dense_pca: X is NULL");
+    if (!scores) return fail(h, PLDA_E_INVAL, "score_dense_pca: scores is NULL");
+    PLDA_TRY(set_device(h));
+    const int64_t T = offsets[R], first = block_off[0], floats = block_off[R] - first;
+    Tmp dX, dS, dD, dE;
+    PLDA_TRY(upload(h, dX, X, (size_t)T * h->Din * 8));
+    PLDA_HIP(h, dS.alloc((size_t)floats * 4));
+    if (dims) PLDA_HIP(h, dD.alloc((size_t)R * 4));
+    if (eig) PLDA_HIP(h, dE.alloc((size_t)T * 8));
+    std::vector<int64_t> rel((size_t)R + 1);
+    bool packed = true;                        // every block exactly N_r^2 floats: one copy back; otherwise block by block
+    for (int64_t r = 0; r <= R; ++r) rel[(size_t)r] = block_off[r] - first;
+    for (int64_t r = 0; r < R; ++r) {
+      const int64_t n = offsets[r + 1] - offsets[r];
+      packed = packed && rel[(size_t)r + 1] - rel[(size_t)r] == n * n;
+    }
+    const int rc = score_dense_pca_device(h, dX.as<double>(), offsets, R, target_energy, dS.as<float>(), rel.data(),
+                                          dims ? dD.as<int32_t>() : nullptr, eig ? dE.as<double>() : nullptr);
+    if (rc != PLDA_OK) { (void)hipStreamSynchronize(h->stream); return rc; }
+    if (packed) {
+      PLDA_HIP(h, hipMemcpyAsync(scores + first, dS.p, (size_t)floats * 4, hipMemcpyDeviceToHost, h->stream));
+    } else {
+      for (int64_t r = 0; r < R; ++r) {
+        const int64_t n = offsets[r + 1] - offsets[r];
+        PLDA_HIP(h, hipMemcpyAsync(scores + block_off[r], dS.as<float>() + rel[(size_t)r], (size_t)(n * n) * 4, hipMemcpyDeviceToHost,
+                                   h->stream));
+      }
+    }
+    if (dims) PLDA_HIP(h, hipMemcpyAsync(dims, dD.p, (size_t)R * 4, hipMemcpyDeviceToHost, h->stream));
+    if (eig) PLDA_HIP(h, hipMemcpyAsync(eig, dE.p, (size_t)T * 8, hipMemcpyDeviceToHost, h->stream));
+    PLDA_HIP(h, hipStreamSynchronize(h->stream));
+    return PLDA_OK;
+  });
+}
+
+int plda_score_dense_pca_ahc_dev(plda_handle *h, const double *dX, const int64_t *offsets, int64_t R, double target_energy,
+                                 int32_t has_threshold, double threshold, const int32_t *min_clusters, int32_t *dlabels,
+                                 int32_t *dn_clusters, int32_t *dmerge_a, int32_t *dmerge_b, double *dmerge_cost) {
+  return guarded(h, "plda_score_dense_pca_ahc_dev", [&]() -> int {
+    if (!h) return PLDA_E_INVAL;
+    PLDA_LOCK(h);
+    PLDA_TRY(set_device(h));
+    return score_dense_pca_ahc_device(h, dX, offsets, R, target_energy, has_threshold, threshold, min_clusters, dlabels, dn_clusters,
+                                      dmerge_a, dmerge_b, dmerge_cost);
+  });
+}
+
+int plda_score_dense_pca_ahc(plda_handle *h, const double *X, const int64_t *offsets, int64_t R, double target_energy,
+                             int32_t has_threshold, double threshold, const int32_t *min_clusters, int32_t *labels,
+                             int32_t *n_clusters, int32_t *merge_a, int32_t *merge_b, double *merge_cost) {
+  return guarded(h, "plda_score_dense_pca_ahc", [&]() -> int {
+    if (!h) return PLDA_E_INVAL;
+    PLDA_LOCK(h);
+    PLDA_TRY(dense_pca_validate(h, "score_dense_pca_ahc", offsets, R, target_energy, nullptr, false));
+    if (!X) return fail(h, PLDA_E_INVAL, "score_dense_pca_ahc: X is NULL");
+    PLDA_TRY(ahc_validate(h, "score_dense_pca_ahc", nullptr, false, offsets, R, has_threshold, threshold, min_clusters, labels,
+                          n_clusters, merge_a, merge_b, merge_cost));
+    PLDA_TRY(set_device(h));
+    const int64_t T = offsets[R];
+    Tmp dX;
+    PLDA_TRY(upload(h, dX, X, (size_t)T * h->Din * 8));
+    return ahc_host_outputs(h, T, R, labels, n_clusters, merge_a, merge_b, merge_cost,
+                            [&](int32_t *dl, int32_t *dk, int32_t *da, int32_t *db, double *dc) {
+                              return score_dense_pca_ahc_device(h, dX.as<double>(), offsets, R, target_energy, has_threshold, threshold,
+                                                                min_clusters, dl, dk, da, db, dc);
+                            });
+  });
+}
+
 // ---------------------------------------------------------------- diarisation error rate (der.hip)
 int plda_der_plan(plda_handle *h, int64_t Sr, int64_t Sh, int32_t out[3]) {
   return guarded(h, "plda_der_plan", [&]() -> int {

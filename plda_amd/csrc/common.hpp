@@ -322,6 +322,14 @@ struct plda_handle {
   plda::DevBuf ahc_stat;         // the call's count of non-finite scores
   int64_t ahc_scratch_bytes = 0; // PLDA_AHC_SCRATCH_BYTES: the scratch one launch may take and the score slab of the operand form (0: 2 GiB)
 
+  // ---- dense scoring in a recording's PCA subspace (dense_pca.hip) ----
+  plda::DevBuf dp_scratch;       // the per-recording arrays of the recordings of one launch group (one layout list per recording)
+  plda::DevBuf dp_tab;           // the launch table of an enqueue (one entry per recording, with its scratch pointers)
+  plda::DevBuf dp_stat;          // the call's count of non-finite rows, then the first recording that failed its Cholesky / eigensolver
+  plda::DevBuf dp_model;         // W and B of the installed model (+ the scratch of forming them), valid while dp_model_epoch matches
+  uint64_t dp_model_epoch = 0;
+  int dp_model_D = 0;
+
   // ---- VBx resegmentation (vbx.hip) ----
   plda::DevBuf vbx_scratch;      // the per-recording state of the HBM-class recordings of one launch
   plda::DevBuf vbx_tab;          // the launch table of a call (one entry per recording)
@@ -504,6 +512,9 @@ int adapt_add_stats(plda_handle *h, double tw, int64_t rows, const double *pilot
 int adapt_update(plda_handle *h, double ws, double bs, double mds, double *eig, plda_adapt_info *info);
 int blend_model(plda_handle *h, int D, const double *mean2, const double *transform2, const double *psi2, double alpha,
                 double alpha_mean);
+// W = (T^T T)^-1, Tinv = T^-1, B = Tinv diag(psi) Tinv^T of a square model (tmp: D^2, scr: 3 D^2 doubles; *flag: T^T T not SPD)
+int model_covariances_f64(plda_handle *h, const double *T, const double *psi, int D, double *W, double *B, double *Tinv, double *tmp,
+                          double *scr, int *flag);
 
 // ---- embed.hip (the embedding chain in front of the model: centre, length-normalise, project, re-centre, length-normalise) ----
 int embed_plan(plda_handle *h, int Din, int Dout, int has_A, int dtype, int32_t *out);
@@ -528,6 +539,17 @@ int ahc_matrix_device(plda_handle *h, const float *dscores, const int64_t *block
 int score_ahc_device(plda_handle *h, const double *dX, const int64_t *offsets, int64_t R, int has_thr, double thr,
                      const int32_t *minc, int32_t *dlabels, int32_t *dn_clusters, int32_t *dmerge_a, int32_t *dmerge_b,
                      double *dmerge_cost);
+
+// ---- dense_pca.hip (recording-dependent PCA before dense scoring; offsets / block_off / minc are HOST arrays) ----
+int dense_pca_plan(plda_handle *h, int64_t N, int32_t D, int32_t *out);
+// the host-side argument check of every form (blocks: block_off is checked against the recordings' sizes)
+int dense_pca_validate(plda_handle *h, const char *fn, const int64_t *offsets, int64_t R, double target, const int64_t *block_off,
+                       bool blocks);
+int score_dense_pca_device(plda_handle *h, const double *dX, const int64_t *offsets, int64_t R, double target, float *dscores,
+                           const int64_t *block_off, int32_t *ddims, double *deig);
+int score_dense_pca_ahc_device(plda_handle *h, const double *dX, const int64_t *offsets, int64_t R, double target, int has_thr,
+                               double thr, const int32_t *minc, int32_t *dlabels, int32_t *dn_clusters, int32_t *dmerge_a,
+                               int32_t *dmerge_b, double *dmerge_cost);
 
 // ---- der.hip (diarisation error rate: optimal speaker mapping, threshold sweep; offsets / thresholds / minc are HOST arrays) ----
 int der_plan(plda_handle *h, int64_t Sr, int64_t Sh, int32_t *out);

@@ -7,14 +7,18 @@ emission model, initialised from the clustering (csrc/vbx.hip; include/plda_hip.
     plan(engine, n)                   the dispatch class a recording of n segments takes
     cut(merges, offsets, ...)         pure NumPy: labels at another threshold / speaker count from ONE full merge record
     MPlda.cluster(x, offsets, ...)    raw segment vectors in, labels out (the blocks are scored on the device and dropped)
+    score_dense_pca(engine, x, offsets, t)   every recording's block scored in the PCA subspace of its own segment vectors
+                                      (Kaldi's --target-energy=t; csrc/dense_pca.hip), one workgroup per recording
+    ahc_dense_pca(engine, x, offsets, t, ...)   the same blocks clustered and dropped (MPlda.cluster(..., target_energy=t))
+    dense_pca_plan(engine, n, d)      the dispatch class a recording of n segments at dimension d takes there
     vbx(engine, y, offsets, labels)   resegments R recordings of projected vectors from initial labels, one workgroup each
     vbx_plan(engine, t, s, d)         the dispatch class a recording of t segments, s initial speakers, dimension d takes
     MPlda.resegment(x, offsets, labels, ...)   raw segment vectors in: plda_project_rows, then vbx
     MPlda.diarize(x, offsets, ...)    cluster, then resegment
 
 A recording is merged bottom-up while the best pair's average score is at least `threshold` (None: no threshold) and more than
-`num_speakers` clusters are left (None: 1).  Out of scope, on purpose: Kaldi's per-recording mean subtraction and PCA before
-scoring, its two-pass clustering of very long recordings; for VBx: more than 64 initial speakers, several workgroups on one
+`num_speakers` clusters are left (None: 1).  Out of scope, on purpose: Kaldi's per-recording mean subtraction, its two-pass
+clustering of very long recordings; for VBx: more than 64 initial speakers, several workgroups on one
 recording, overlap handling.  The diarisation error rate, and the threshold sweep that cut() serves on the host, live in
 plda_amd/der.py; RTTM files in plda_amd/rttm.py.  Length normalisation and the LDA fit before the model are the embedding
 chain's (K18: plda_amd/embed.py, MPlda.fit_embedding / set_embedding): with one attached, cluster / resegment / diarize take
@@ -113,6 +117,79 @@ def ahc_vectors(engine, vecs, offsets, threshold=0.0, num_speakers=None, return_
     labels, ncl, ma, mb, mc = _outputs(t, r, return_merges)
     N.check(engine._h, engine._lib.plda_score_ahc(engine._h, _p(vecs), _p(offsets), r, has_t, thr, _p(minc), _p(labels), _p(ncl),
                                                   _p(ma), _p(mb), _p(mc)))
+    return (labels, ncl, (ma, mb, mc)) if return_merges else (labels, ncl)
+
+
+# ------------------------------------------------------------------------------------------- dense scoring behind a PCA
+DENSE_PCA_MAX_DIM = 512     # PLDA_DENSE_PCA_MAX_DIM
+
+
+def dense_pca_plan(engine, n, d):
+    """{"cls": 0 (working matrix in LDS) or 1 (in HBM scratch), "scratch_bytes": per recording, "m": min(n, d), "lds_max": the
+    largest m of class 0} of a recording of n segments at model dimension d."""
+    out = (C.c_int32 * 4)()
+    N.check(engine._h, engine._lib.plda_dense_pca_plan(engine._h, int(n), int(d), out))
+    return {"cls": int(out[0]), "scratch_bytes": int(out[1]), "m": int(out[2]), "lds_max": int(out[3])}
+
+
+def dense_pca_args(engine, x, offsets, target_energy):
+    """The argument check of score_dense_pca / ahc_dense_pca, before any device work -> (x, offsets).  ValueError on anything
+    the C ABI would answer with PLDA_E_INVAL and that the host can see."""
+    x = np.ascontiguousarray(x, np.float64)
+    offsets = np.ascontiguousarray(offsets, np.int64)
+    if not (isinstance(target_energy, (int, float, np.floating)) and 0.0 < float(target_energy) < 1.0):
+        raise ValueError("target_energy must lie in (0, 1), got %r" % (target_energy,))
+    if offsets.ndim != 1 or len(offsets) < 2:
+        raise ValueError("offsets must hold R + 1 >= 2 entries")
+    if offsets[0] != 0:
+        raise ValueError("offsets must start at 0")
+    sizes = np.diff(offsets)
+    if (sizes < 1).any() or (sizes > AHC_MAX).any():
+        raise ValueError("every recording must hold 1 ... %d segments (offsets must ascend)" % AHC_MAX)
+    if x.ndim != 2 or x.shape[0] != int(offsets[-1]):
+        raise ValueError("x must be [offsets[-1], D], got %r" % (x.shape,))
+    dout, din = engine.dims()
+    if dout != din:
+        raise ValueError("the model is truncated (transform %d x %d): the PCA projects the untruncated model" % (dout, din))
+    if din > DENSE_PCA_MAX_DIM:
+        raise ValueError("model dimension %d: dense PCA scoring is supported up to %d" % (din, DENSE_PCA_MAX_DIM))
+    if x.shape[1] != din:
+        raise ValueError("x has dimension %d, the model's input dimension is %d" % (x.shape[1], din))
+    if not np.isfinite(x).all():
+        raise ValueError("x holds non-finite values")
+    return x, offsets
+
+
+def score_dense_pca(engine, x, offsets, target_energy, return_info=False):
+    """Score every recording's segment pairs in the PCA subspace of its own segment vectors (include/plda_hip.h, "dense scoring
+    in a recording's PCA subspace"): x [T, D] rows in the model's input space, recording r owning rows offsets[r] ..
+    offsets[r+1].  Returns a list of [N_r, N_r] float32 blocks (S[i, j]: enrol i, test j)[, {"dims": int32 [R], the retained
+    dimensions, "eigenvalues": a list of [min(N_r, D)] arrays, descending}]."""
+    x, offsets = dense_pca_args(engine, x, offsets, target_energy)
+    r, t = len(offsets) - 1, int(offsets[-1])
+    sizes = np.diff(offsets)
+    block_off = offsets_of(sizes * sizes)
+    scores = np.empty(int(block_off[-1]), np.float32)
+    dims = np.empty(r, np.int32) if return_info else None
+    eig = np.empty(t, np.float64) if return_info else None
+    N.check(engine._h, engine._lib.plda_score_dense_pca(engine._h, _p(x), _p(offsets), r, float(target_energy), _p(scores),
+                                                        _p(block_off), _p(dims), _p(eig)))
+    blocks = [scores[block_off[q]:block_off[q + 1]].reshape(int(sizes[q]), int(sizes[q])) for q in range(r)]
+    if not return_info:
+        return blocks
+    m = np.minimum(sizes, x.shape[1])
+    return blocks, {"dims": dims, "eigenvalues": [eig[offsets[q]:offsets[q] + m[q]] for q in range(r)]}
+
+
+def ahc_dense_pca(engine, x, offsets, target_energy, threshold=0.0, num_speakers=None, return_merges=False):
+    """score_dense_pca's blocks clustered on the device and dropped: (labels, n_clusters[, merges]) as ahc() returns them on
+    those blocks."""
+    has_t, thr, minc = stop_args(np.ascontiguousarray(offsets, np.int64), threshold, num_speakers)
+    x, offsets = dense_pca_args(engine, x, offsets, target_energy)
+    r, t = len(offsets) - 1, int(offsets[-1])
+    labels, ncl, ma, mb, mc = _outputs(t, r, return_merges)
+    N.check(engine._h, engine._lib.plda_score_dense_pca_ahc(engine._h, _p(x), _p(offsets), r, float(target_energy), has_t, thr,
+                                                            _p(minc), _p(labels), _p(ncl), _p(ma), _p(mb), _p(mc)))
     return (labels, ncl, (ma, mb, mc)) if return_merges else (labels, ncl)
 
 

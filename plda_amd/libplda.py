@@ -531,19 +531,30 @@ class MPlda(object):
         return out
 
     # ----------------------------------------------------------------- speaker clustering (csrc/ahc.hip)
-    def cluster(self, x, offsets, threshold=0.0, num_speakers=None, return_merges=False):
+    def cluster(self, x, offsets, threshold=0.0, num_speakers=None, return_merges=False, target_energy=None):
         """Cluster the segments of R recordings (diarisation; plda_amd/diarize.py): x [T, Din] raw segment vectors, recording
         r owning rows offsets[r] .. offsets[r+1].  Every row is transformed with num_examples = 1, every recording's segments
         are scored against each other on the device and merged bottom-up (average linkage) while the best pair's average
         score is at least `threshold` (None: no threshold) and more than `num_speakers` (an int or one per recording; None: 1)
-        clusters are left.  Returns (labels int32 [T], n_clusters int32 [R][, (merge_a, merge_b, merge_cost)])."""
+        clusters are left.  target_energy=t (0 < t < 1; Kaldi's --target-energy): every recording is scored in the PCA subspace
+        of its own segment vectors instead (score_dense).  Returns (labels int32 [T], n_clusters int32 [R][, (merge_a, merge_b,
+        merge_cost)])."""
         from . import diarize
         offsets = np.ascontiguousarray(offsets, np.int64)
         diarize.stop_args(offsets, threshold, num_speakers)     # (threshold=None without num_speakers: ValueError, before any work)
         X = self._rows(x, "Segment vectors")
         if offsets.ndim != 1 or len(offsets) < 2 or X.shape[0] != int(offsets[-1]):
             raise ValueError("offsets must hold R + 1 >= 2 entries ending at the number of rows of x")
+        if target_energy is not None:
+            return diarize.ahc_dense_pca(self, X, offsets, target_energy, threshold, num_speakers, return_merges)
         return diarize.ahc_vectors(self, self.transform_array(X, 1), offsets, threshold, num_speakers, return_merges)
+
+    def score_dense(self, x, offsets, target_energy, return_info=False):
+        """Every recording's segment pairs scored in the PCA subspace of its own segment vectors (Kaldi's
+        ivector-plda-scoring-dense --target-energy; plda_amd/diarize.py: score_dense_pca): x [T, Din] raw segment vectors.
+        Returns a list of [N_r, N_r] float32 blocks[, {"dims", "eigenvalues"}]."""
+        from . import diarize
+        return diarize.score_dense_pca(self, self._rows(x, "Segment vectors"), offsets, target_energy, return_info)
 
     # ----------------------------------------------------------------- VBx resegmentation (csrc/vbx.hip)
     def project_rows(self, x):
@@ -575,9 +586,13 @@ class MPlda(object):
         return diarize.vbx(self, self._project(X), offsets, labels, None, Fa, Fb, loop_prob, init_smoothing, max_iters, epsilon,
                            return_posteriors)
 
-    def diarize(self, x, offsets, threshold=0.0, num_speakers=None, **vbx):
-        """cluster(x, offsets, threshold, num_speakers), then resegment(x, offsets, its labels, **vbx)."""
-        labels, _ = self.cluster(x, offsets, threshold, num_speakers)
+    def diarize(self, x, offsets, threshold=0.0, num_speakers=None, target_energy=None, **vbx):
+        """cluster(x, offsets, threshold, num_speakers), then resegment(x, offsets, its labels, **vbx).  target_energy goes to
+        the clustering only: VBx keeps working on the full model."""
+        if target_energy is None:
+            labels, _ = self.cluster(x, offsets, threshold, num_speakers)
+        else:
+            labels, _ = self.cluster(x, offsets, threshold, num_speakers, target_energy=target_energy)
         return self.resegment(x, offsets, labels, **vbx)
 
     def vbx_dev(self, dY, D, dPhi, dlabels_in, offsets, dlabels, dn_clusters, Fa=0.3, Fb=17.0, loop_prob=0.99, init_smoothing=5.0,
@@ -613,8 +628,26 @@ class MPlda(object):
             _ptr(min_clusters) if min_clusters is not None else None, vp(dlabels), vp(dn_clusters), vp(dmerge_a), vp(dmerge_b),
             vp(dmerge_cost)))
 
+    def score_dense_pca_dev(self, dX, offsets, target_energy, dscores, block_off, ddims=None, deig=None):
+        """plda_score_dense_pca_dev on HBM-resident rows dX [T, Din] (raw device addresses): block r row-major at dscores +
+        block_off[r] floats; offsets and block_off (int64) are HOST arrays; ddims int32 [R] and deig float64 [T] may be None."""
+        def vp(x):
+            return C.c_void_p(int(x)) if x else None
+        self._ck(self._lib.plda_score_dense_pca_dev(self._h, vp(dX), _ptr(offsets), len(offsets) - 1, float(target_energy),
+                                                    vp(dscores), _ptr(block_off), vp(ddims), vp(deig)))
+
+    def score_dense_pca_ahc_dev(self, dX, offsets, target_energy, has_threshold, threshold, min_clusters, dlabels, dn_clusters,
+                                dmerge_a=None, dmerge_b=None, dmerge_cost=None):
+        """The same blocks clustered and dropped (plda_score_dense_pca_ahc_dev); the outputs as score_ahc_dev's."""
+        def vp(x):
+            return C.c_void_p(int(x)) if x else None
+        self._ck(self._lib.plda_score_dense_pca_ahc_dev(
+            self._h, vp(dX), _ptr(offsets), len(offsets) - 1, float(target_energy), int(has_threshold), float(threshold),
+            _ptr(min_clusters) if min_clusters is not None else None, vp(dlabels), vp(dn_clusters), vp(dmerge_a), vp(dmerge_b),
+            vp(dmerge_cost)))
+
     # ----------------------------------------------------------------- diarisation error rate (csrc/der.hip)
-    def der(self, ref, hyp, offsets, dur=None, return_map=False):
+    def der(self,ref, hyp, offsets, dur=None, return_map=False):
         """Diarisation error rate of R recordings (plda_amd/der.py): ref, hyp int [T] per-segment speaker labels (-1 =
         non-speech), recording r owning segments offsets[r] .. offsets[r+1], dur int [T] ticks (None: 1 everywhere).  Miss,
         false alarm and confusion under the optimal one-to-one speaker mapping, exact integers from the device.  Returns a
@@ -622,10 +655,10 @@ class MPlda(object):
         from . import der
         return der.der(self, ref, hyp, offsets, dur, return_map)
 
-    def tune_threshold(self, x, offsets, ref, thresholds, dur=None):
+    def tune_threshold(self, x, offsets, ref, thresholds, dur=None, target_energy=None):
         """The clustering threshold with the lowest pooled DER on a development set: ONE cluster(x, offsets, threshold=None,
-        num_speakers=1, return_merges=True), then one der.sweep of its full merge record over `thresholds`.  Returns
-        (the best threshold -- the first of equal ones --, the plda_amd.der.SweepResult)."""
+        num_speakers=1, return_merges=True[, target_energy=target_energy]), then one der.sweep of its full merge record over
+        `thresholds`.  Returns (the best threshold -- the first of equal ones --, the plda_amd.der.SweepResult)."""
         from . import der
         offsets = np.ascontiguousarray(offsets, np.int64)
         X = self._rows(x, "Segment vectors")
@@ -636,7 +669,10 @@ class MPlda(object):
         der.sweep_args(empty, offsets, ref, thresholds, dur, None)        # (before any device work)
         from . import diarize
         diarize.stop_args(offsets, None, 1)
-        _, _, merges = diarize.ahc_vectors(self, self.transform_array(X, 1), offsets, None, 1, True)   # cluster() on embedded rows
+        if target_energy is not None:
+            _, _, merges = diarize.ahc_dense_pca(self, X, offsets, target_energy, None, 1, True)
+        else:
+            _, _, merges = diarize.ahc_vectors(self, self.transform_array(X, 1), offsets, None, 1, True)   # cluster() on embedded rows
         res = der.sweep(self, merges, offsets, ref, thresholds, dur)
         return float(res.thresholds[res.best]), res
 
