@@ -148,11 +148,38 @@ int plda_transform_groups_dev(plda_handle *h, const double *dX, int64_t N, int32
                               const uint64_t *dlabels, uint64_t *dout_labels, int32_t *dout_counts,
                               double *dout_vecs, int64_t *Ku);
 /* batched Plda::TransformIvector on R already-averaged rows; num_examples[R]
- * (int32) or, if NULL, `n_uniform` for every row. */
+ * (int32) or, if NULL, `n_uniform` for every row.
+ * DEFINITION.  t = T (x - mean), w_d = 1 / (psi_d + 1/n), s = sum_d t_d^2 w_d, out = sqrt(Dout / s) t, per row, in fp64.  A row's
+ * result depends on that row and its count alone: its bits are the same at every position of a launch and with any neighbours.
+ * EDGES, each pinned by tests/test_gpu_transform_edges.py:
+ *   - t = 0 exactly (x = mean = 0, for instance): the row has no direction and comes back all NaN.  A row EQUAL to a non-zero
+ *     mean gives a t of rounding residue; its result is unspecified (finite or NaN), its neighbours are untouched.
+ *   - a row with a NaN or an Inf element comes back all NaN (given that no element of T is exactly zero); every other row is
+ *     bit-identical to the call without it.
+ *   - counts <= 0 (Kaldi asserts num_examples > 0).  n_uniform <= 0 without an array: PLDA_E_INVAL.  plda_transform_rows, whose
+ *     counts are in host memory, counts such rows before any device work: PLDA_E_INVAL with their number and the first such row
+ *     in plda_last_error, nothing is written, the handle keeps working.  plda_transform_rows_dev does not read device memory
+ *     on the host: a row whose count is <= 0 comes back all NaN, its neighbours are untouched.
+ *   - scale: the sum s is formed from t_d^2 in fp64, so rows with |t| between about 1e-150 and 1e+150 are normalised like any
+ *     other (1e-100 and 1e+100 are tested beside ordinary rows); beyond that s leaves the fp64 range and the row is unspecified.
+ *   - an offset mean.  The product is evaluated in the reference's own form T x + (-T mean), not as T (x - mean): with
+ *     u = 2^-53 an element of t carries an absolute error of up to (Din + 2) u sum_k |T_ok| (|x_k| + |mean_k|), i.e. the
+ *     RELATIVE error of the output grows linearly with |mean| / |x - mean|: the bound is 6e-10 (Dout = 208) to 2e-9 (512) of
+ *     |out| at |mean| = 1e3 spreads and 6e-7 to 2e-6 at 1e6 spreads; the measured deviation is below a hundredth of that
+ *     (profiles/transform_parity.json, per case).
+ *     Callers whose data sit far from the origin centre them first (plda_embed_set's input mean).
+ * plda_transform_plan: what the two entry points run for R rows on the installed model, without touching the device --
+ *   out[0] = the arm: 0 the one-pass kernel, 1 a GEMM and a length-norm pass (Dout > 512, or PLDA_TRANSFORM_VARIANT=1);
+ *   out[1] = the dimension class of arm 0: 0 .. 4 for Dout <= 128 / 208 / 256 / 384 / 512 (-1 on arm 1);
+ *   out[2], out[3] = the rows of the main launch (a whole number of rounds of one block per compute unit; every row on arm 1)
+ *   and the rows of one of its blocks (128 for classes 0 .. 2, 64 for classes 3 and 4; on arm 1 the 4 rows of a length-norm block);
+ *   out[4], out[5] = the rows of the tail launch and of one of its blocks (16, 32, 64 or the main block's rows; 0, 0 without a tail);
+ *   out[6] = the compute units the split was made for; out[7] = 0.  PLDA_E_NOT_FITTED without a model, PLDA_E_INVAL for R < 0. */
 int plda_transform_rows(plda_handle *h, const double *Xbar, int64_t R, int32_t Din,
                         const int32_t *num_examples, int32_t n_uniform, double *out);
 int plda_transform_rows_dev(plda_handle *h, const double *dXbar, int64_t R, int32_t Din,
                             const int32_t *dnum_examples, int32_t n_uniform, double *dout);
+int plda_transform_plan(plda_handle *h, int64_t R, int64_t out[8]);
 
 /* ---- score: replaces MPlda_score (pldamodule.cpp:258-277) ----
  * Trial list: P pairs (enrol row e_idx[p] of U, test row t_idx[p] of V), each

@@ -719,6 +719,12 @@ int plda_transform_rows(plda_handle *h, const double *Xbar, int64_t R, int32_t D
     if (R <= 0) return PLDA_OK;
     if (!Xbar || !out) return fail(h, PLDA_E_INVAL, "transform_rows: bad argument");
     if (!num_examples && n_uniform <= 0) return fail(h, PLDA_E_INVAL, "transform_rows: need num_examples or n_uniform > 0");
+    if (num_examples) {      // (Kaldi asserts num_examples > 0; here the counts are in host memory: look at them before anything is written)
+      int64_t bad = 0, first = -1;
+      for (int64_t r = 0; r < R; ++r)
+        if (num_examples[r] <= 0 && bad++ == 0) first = r;
+      if (bad) return fail(h, PLDA_E_INVAL, "transform_rows: %lld of %lld rows have num_examples <= 0 (the first is row %lld)", (long long)bad, (long long)R, (long long)first);
+    }
     PLDA_TRY(set_device(h));
     Tmp dX, dN, dO;
     PLDA_TRY(upload(h, dX, Xbar, (size_t)R * Din * 8));
@@ -726,6 +732,20 @@ int plda_transform_rows(plda_handle *h, const double *Xbar, int64_t R, int32_t D
     PLDA_HIP(h, dO.alloc((size_t)R * h->Dout * 8));
     PLDA_TRY(transform_rows_device(h, dX.as<double>(), R, Din, num_examples ? dN.as<int32_t>() : nullptr, n_uniform, dO.as<double>()));
     return download(h, out, dO.p, (size_t)R * h->Dout * 8);
+  });
+}
+
+int plda_transform_plan(plda_handle *h, int64_t R, int64_t out[8]) {
+  return guarded(h, "plda_transform_plan", [&]() -> int {
+    if (!h) return PLDA_E_INVAL;
+    PLDA_LOCK(h);
+    if (!h->fitted) return fail(h, PLDA_E_NOT_FITTED, "transform: model not fitted");
+    if (!out) return fail(h, PLDA_E_INVAL, "transform_plan: out is NULL");
+    if (R < 0) return fail(h, PLDA_E_INVAL, "transform_plan: R = %lld (must be >= 0)", (long long)R);
+    const TfPlan p = transform_plan(h, R);
+    out[0] = p.arm; out[1] = p.cls; out[2] = p.main_rows; out[3] = p.main_block; out[4] = p.tail_rows; out[5] = p.tail_block;
+    out[6] = h->num_cus; out[7] = 0;
+    return PLDA_OK;
   });
 }
 

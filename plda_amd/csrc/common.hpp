@@ -608,6 +608,11 @@ int quadform_rows_device(plda_handle *h, const double *dX, int64_t R, int D, con
                          double *out_std, bool *used);
 int transform_rows_device(plda_handle *h, const double *dX, int64_t R, int Din,
                           const int32_t *dn, int n_uniform, double *dout);
+// what transform_rows_device runs for R rows on the installed model (plda_transform_plan reports it): arm 0 = the one-pass kernel
+// (cls 0 .. 4: Dout <= 128 / 208 / 256 / 384 / 512; rows [0, main_rows) in blocks of main_block rows, then tail_rows rows in
+// blocks of tail_block rows, 0 without a tail), arm 1 = GEMM + length-norm pass (cls -1, every row in main_rows)
+struct TfPlan { int arm, cls, main_block, tail_block; int64_t main_rows, tail_rows; };
+TfPlan transform_plan(const plda_handle *h, int64_t R);
 
 // ---- snorm.hip (adaptive symmetric score normalisation: top-K cohort statistics, the two-sided map) ----
 // cs: as score_matrix_device (the distinct counts of the caller's whole call; nullptr: found here)

@@ -58,7 +58,8 @@ __global__ void length_norm_kernel(double *__restrict__ out, int64_t R, int Dout
   const int lane = threadIdx.x & 63;
   const int64_t row = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
   if (row >= R) return;
-  const double inv_n = 1.0 / (n_arr ? (double)n_arr[row] : (double)n_uniform);
+  const int n = n_arr ? n_arr[row] : n_uniform;
+  const double inv_n = n > 0 ? 1.0 / (double)n : __builtin_nan("");   // a count <= 0: the row comes back all NaN
   double *t = out + row * (int64_t)Dout;
   double acc = 0.0;
   for (int d = lane; d < Dout; d += 64) {
@@ -315,7 +316,10 @@ __global__ __launch_bounds__(512) void transform_fused_kernel(const double *__re
     if constexpr (PERROW) {
       double inv_n[4];
 #pragma unroll
-      for (int r = 0; r < 4; ++r) inv_n[r] = 1.0 / (double)n_arr[min(grow[r], R - 1)];
+      // a count <= 0 counts as 0: 1/n = inf, psi + inf = inf, and tf_rcp(inf) is NaN (its first Newton step is fma(-inf, 0, 1)) --
+      // NaN weights, so the row's sum, its factor and the whole row are NaN.  One integer max per row; a compare and a 64-bit
+      // select here measured 0.4 % on 1.2M x 256 rows.
+      for (int r = 0; r < 4; ++r) inv_n[r] = 1.0 / (double)max(n_arr[min(grow[r], R - 1)], 0);
 #pragma unroll
       for (int tn = 0; tn < NT; ++tn) {
         const int col = (ch * NT + tn) * 16 + fi;
@@ -465,8 +469,10 @@ template <int A, int B> constexpr int cmax() { return A > B ? A : B; }
 
 // the instantiations of one dimension class: the main block shape <NT0, CH0> (128 rows for CH0 = 1, 64 for CH0 = 2) and
 // the smaller tail blocks <NT1, 2> (64 rows; CH0 = 1 only), <NT2, 4> (32 rows), <NT3, 8> (16 rows); KS = stage depth
-template <int KS, int NT0, int CH0, int NT1, int NT2, int NT3>
-static int transform_class(plda_handle *h, const double *dX, int64_t R, int Din, const int32_t *dn, int n_uniform,
+constexpr int tf_class_main_block(int cls) { return cls <= 2 ? 128 : 64; }   // rows of the main block shape: TfGeom<NT0, CH0>::ROWS
+
+template <int CLS, int KS, int NT0, int CH0, int NT1, int NT2, int NT3>
+static int transform_class(plda_handle *h, const TfPlan &plan, const double *dX, int Din, const int32_t *dn, int n_uniform,
                            double *dout) {
   // the zero-padded copy of T ([rows >= every block shape's stage rows][Din rounded up to KS]), rebuilt only when the
   // model has changed (or another class's geometry was cached)
@@ -481,24 +487,48 @@ static int transform_class(plda_handle *h, const double *dX, int64_t R, int Din,
     h->tf_pad_epoch = h->model_epoch; h->tf_pad_rows = PADROWS; h->tf_pad_dinp = Dinp;
   }
   constexpr int ROWS0 = TfGeom<NT0, CH0, KS>::ROWS;
-  const int64_t G = h->num_cus;
+  static_assert(ROWS0 == tf_class_main_block(CLS), "transform_plan's main block is not this class's");
   // main launch: a whole number of rounds of the persistent grid
-  const int64_t nb = ceil_div(R, (int64_t)ROWS0);
-  const int64_t rows_main = std::min(R, nb / G * G * ROWS0);
+  const int64_t rows_main = plan.main_rows;
   if (rows_main > 0) PLDA_TRY((launch_transform_fused<NT0, CH0, KS>(h, dX, rows_main, Din, dn, n_uniform, dout, Dinp)));
-  const int64_t Rt = R - rows_main;
+  const int64_t Rt = plan.tail_rows;
   if (Rt <= 0) return PLDA_OK;
-  // the rest: the smallest blocks that still give every CU at most one
+  // the rest: the smallest blocks that still give every CU at most one (transform_plan chose them)
   const double *tX = dX + rows_main * Din;
   const int32_t *tn = dn ? dn + rows_main : nullptr;
   double *to = dout + rows_main * (int64_t)h->Dout;
-  const int64_t per_cu = ceil_div(Rt, G);
-  if (per_cu <= 16) return launch_transform_fused<NT3, 8, KS>(h, tX, Rt, Din, tn, n_uniform, to, Dinp);
-  if (per_cu <= 32) return launch_transform_fused<NT2, 4, KS>(h, tX, Rt, Din, tn, n_uniform, to, Dinp);
+  if (plan.tail_block == 16) return launch_transform_fused<NT3, 8, KS>(h, tX, Rt, Din, tn, n_uniform, to, Dinp);
+  if (plan.tail_block == 32) return launch_transform_fused<NT2, 4, KS>(h, tX, Rt, Din, tn, n_uniform, to, Dinp);
   if constexpr (CH0 == 1) {
-    if (per_cu <= 64) return launch_transform_fused<NT1, 2, KS>(h, tX, Rt, Din, tn, n_uniform, to, Dinp);
+    if (plan.tail_block == 64) return launch_transform_fused<NT1, 2, KS>(h, tX, Rt, Din, tn, n_uniform, to, Dinp);
   }
   return launch_transform_fused<NT0, CH0, KS>(h, tX, Rt, Din, tn, n_uniform, to, Dinp);
+}
+
+// Every decision K4's dispatch takes for R rows on the installed model, as a pure host function: the arm, the dimension class,
+// and how the rows split into the main launch (a whole number of rounds of the persistent grid) and the tail launch.
+// transform_rows_device runs what this returns and plda_transform_plan reports it, so the two cannot drift.
+TfPlan transform_plan(const plda_handle *h, int64_t R) {
+  TfPlan p{};
+  const int D = h->Dout;
+  if (!(D <= 512 && h->transform_variant != 1 && R < ((int64_t)1 << 31) * 64)) {
+    p.arm = 1; p.cls = -1;
+    p.main_rows = R;           // one GEMM and one length-norm launch over every row (length_norm_kernel: 4 rows per workgroup)
+    p.main_block = 4;
+    return p;
+  }
+  p.cls = D <= 128 ? 0 : D <= 208 ? 1 : D <= 256 ? 2 : D <= 384 ? 3 : 4;
+  const int rows0 = tf_class_main_block(p.cls);
+  const int64_t G = h->num_cus;
+  const int64_t nb = ceil_div(R, (int64_t)rows0);
+  p.main_block = rows0;
+  p.main_rows = std::min(R, nb / G * G * rows0);
+  p.tail_rows = R - p.main_rows;
+  if (p.tail_rows > 0) {
+    const int64_t per_cu = ceil_div(p.tail_rows, G);
+    p.tail_block = per_cu <= 16 ? 16 : per_cu <= 32 ? 32 : per_cu <= 64 ? 64 : rows0;
+  }
+  return p;
 }
 
 int transform_rows_device(plda_handle *h, const double *dX, int64_t R, int Din, const int32_t *dn,
@@ -508,17 +538,19 @@ int transform_rows_device(plda_handle *h, const double *dX, int64_t R, int Din, 
   if (R <= 0) return PLDA_OK;
   // out[r][o] = sum_k X[r][k] T[o][k]
   TraceScope ts(h, "transform.gemm + length_norm (K4)", 2.0 * (double)R * h->Dout * Din, 1);
-  if (h->Dout <= 512 && h->transform_variant != 1 && R < ((int64_t)1 << 31) * 64) {
-    const int D = h->Dout;
+  const TfPlan plan = transform_plan(h, R);
+  if (plan.arm == 0) {
     // <stage depth; tiles per wave of the main block shape and its column slices; tiles per wave of the 2 / 4 / 8-slice
     // tail blocks>, NT * CH * 16 >= D in every shape.  Stage depth: 16 k everywhere -- deeper stages (20 ... 32 k, as
     // deep as the LDS allows per class) were measured and are no faster (C2 0.519 against 0.527 of the fp64 peak,
     // C4 0.728 against 0.757), so the 2.5 us a stage's data movement takes is not a latency a longer stage amortises.
-    if (D <= 128) return transform_class<16, 8, 1, 4, 2, 1>(h, dX, R, Din, dn, n_uniform, dout);
-    if (D <= 208) return transform_class<16, 13, 1, 7, 4, 2>(h, dX, R, Din, dn, n_uniform, dout);
-    if (D <= 256) return transform_class<16, 16, 1, 8, 4, 2>(h, dX, R, Din, dn, n_uniform, dout);
-    if (D <= 384) return transform_class<16, 12, 2, 12, 6, 3>(h, dX, R, Din, dn, n_uniform, dout);
-    return transform_class<16, 16, 2, 16, 8, 4>(h, dX, R, Din, dn, n_uniform, dout);
+    switch (plan.cls) {
+      case 0: return transform_class<0, 16, 8, 1, 4, 2, 1>(h, plan, dX, Din, dn, n_uniform, dout);       // Dout <= 128
+      case 1: return transform_class<1, 16, 13, 1, 7, 4, 2>(h, plan, dX, Din, dn, n_uniform, dout);      // <= 208
+      case 2: return transform_class<2, 16, 16, 1, 8, 4, 2>(h, plan, dX, Din, dn, n_uniform, dout);      // <= 256
+      case 3: return transform_class<3, 16, 12, 2, 12, 6, 3>(h, plan, dX, Din, dn, n_uniform, dout);     // <= 384
+      default: return transform_class<4, 16, 16, 2, 16, 8, 4>(h, plan, dX, Din, dn, n_uniform, dout);    // <= 512
+    }
   }
   PLDA_TRY(gemm_f64(h, R, h->Dout, Din, 1.0, dX, Din, 1, h->d_transform.as<double>(), 1, Din,
                     nullptr, 0.0, dout, h->Dout));

@@ -515,8 +515,18 @@ class MPlda(object):
         res._packed = (out_labels[:g].astype(np.int64), out_counts[:g].astype(np.int32), vecs)
         return res
 
+    def transform_plan(self, r):
+        """What K4 runs for r rows on the installed model (plda_transform_plan): {"arm": "fused" (the one-pass kernel) or "pair"
+        (GEMM + length-norm pass), "cls": the dimension class 0 .. 4 (Dout <= 128 / 208 / 256 / 384 / 512; -1 on the pair arm),
+        "main_rows", "main_block": the rows of the main launch and the rows of one of its blocks, "tail_rows", "tail_block": the
+        same of the tail launch (0, 0 without one), "cus": the compute units the split was made for}."""
+        out = (C.c_int64 * 8)()
+        self._ck(self._lib.plda_transform_plan(self._h, int(r), out))
+        return {"arm": "pair" if out[0] else "fused", "cls": int(out[1]), "main_rows": int(out[2]), "main_block": int(out[3]),
+                "tail_rows": int(out[4]), "tail_block": int(out[5]), "cus": int(out[6])}
+
     def transform_array(self, xbar, num_examples=1):
-        """Batched Plda::TransformIvector on already-averaged rows -> ndarray [R, D]."""
+        """Batched Plda::TransformIvector on already-averaged rows -> ndarray [R, D].  ValueError when a count is <= 0."""
         X = np.ascontiguousarray(xbar, np.float64)
         r, d = X.shape
         dout, _ = self.dims()
@@ -527,6 +537,8 @@ class MPlda(object):
             ne = np.ascontiguousarray(num_examples, np.int32)
             if ne.shape != (r,):
                 raise ValueError("num_examples must have one entry per row")
+            if (ne <= 0).any():
+                raise ValueError("num_examples must be > 0: %d of %d rows are not" % (int((ne <= 0).sum()), r))
             self._ck(self._lib.plda_transform_rows(self._h, _ptr(X), r, d, _ptr(ne), 0, _ptr(out)))
         return out
 

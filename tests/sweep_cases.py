@@ -22,8 +22,9 @@ import zlib
 
 import numpy as np
 
-MODULES = ("topn", "der", "ahc", "asnorm", "mindcf", "calibration", "embed", "vbx", "adapt", "fusion")
-COUNTS = {"topn": 24, "der": 24, "ahc": 24, "asnorm": 30, "mindcf": 24, "calibration": 30, "embed": 24, "vbx": 24, "adapt": 24, "fusion": 24}
+MODULES = ("topn", "der", "ahc", "asnorm", "mindcf", "calibration", "embed", "vbx", "adapt", "fusion", "transform")
+COUNTS = {"topn": 24, "der": 24, "ahc": 24, "asnorm": 30, "mindcf": 24, "calibration": 30, "embed": 24, "vbx": 24, "adapt": 24, "fusion": 24,
+          "transform": 24}
 MAX_REDRAWS = 16
 
 
@@ -872,3 +873,51 @@ def _draw_fusion(pick, rng):
 
 
 _GENERATORS["fusion"] = _draw_fusion
+
+
+# ------------------------------------------------------------------------------------------- transform (K4, csrc/transform.hip)
+# Dout: the edges of the five dimension classes of the one-pass kernel and one past each (513: the GEMM + length-norm pair); Din =
+# Dout + ragged (not a multiple of the 4-wide k-step or of the 16-deep stage); the row counts are written in the plan's own
+# terms -- G compute units, R0 rows of a main block (plda_transform_plan) -- and resolved on the device by transform_rows().
+MENUS["transform"] = {
+    "dout": (1, 17, 127, 128, 129, 208, 209, 256, 257, 384, 385, 512, 513),
+    "ragged": (0, 1, 3, 5),
+    "rows": ("1", "17", "16G", "16G+1", "32G+1", "64G+1", "R0G", "R0G+1", "R0G+16G+1"),
+    "form": ("uniform", "perrow"),
+    "arm": ("fused", "fused", "pair"),               # pair: PLDA_TRANSFORM_VARIANT=1 (and whatever Dout > 512 takes)
+    "mean": (0.0, 1.0, 1e3),                         # |mean| in spreads of the rows
+    "uniform": (1, 3, 4096),
+}
+
+
+def transform_rows(entry, g, r0):
+    """the row count of a "rows" entry on a device of g compute units whose class has main blocks of r0 rows"""
+    return {"1": 1, "17": 17, "16G": 16 * g, "16G+1": 16 * g + 1, "32G+1": 32 * g + 1, "64G+1": 64 * g + 1, "R0G": r0 * g,
+            "R0G+1": r0 * g + 1, "R0G+16G+1": r0 * g + 16 * g + 1}[entry]
+
+
+def transform_shapes(entry, r0):
+    """the launches a "rows" entry takes on the one-pass arm, as transform_model.shapes_of reports them (the same on any CU count)"""
+    tail64 = ("tail", 64)                            # (for r0 = 64 that is the main shape used as a tail)
+    return {"1": {("tail", 16)}, "17": {("tail", 16)}, "16G": {("tail", 16)}, "16G+1": {("tail", 32)}, "32G+1": {tail64},
+            "64G+1": {("tail", 128)} if r0 == 128 else {("main", 64), ("tail", 16)}, "R0G": {("main", r0)},
+            "R0G+1": {("main", r0), ("tail", 16)}, "R0G+16G+1": {("main", r0), ("tail", 32)}}[entry]
+
+
+def _draw_transform(pick, rng):
+    import transform_model as M
+    dout, ragged, rows, (form, frank) = pick("dout"), pick("ragged"), pick("rows"), pick.cycle("form")
+    (arm, _), mean_size = pick.cycle("arm"), pick("mean")
+    if dout > 512:
+        arm = pick.force("arm", "pair")
+    din = dout + ragged
+    model = M.make_model(rng, din, dout, mean_size)
+    x, n = M.pool_rows(rng, din, model[0])
+    uniform = pick("uniform", frank) if form == "uniform" else None
+    case = dict(din=din, dout=dout, rows=rows, form=form, arm=arm, model=model, x=x, n=n, uniform=uniform,
+                index_seed=int(rng.integers(1 << 30)))
+    case["what"] = "%dx%d " % (din, dout) + _opts(rows=rows, form=form, arm=arm, mean=mean_size, uniform=uniform)
+    return case
+
+
+_GENERATORS["transform"] = _draw_transform

@@ -95,7 +95,6 @@ def eng():
 @pytest.mark.parametrize("din,dout,r", [(7, 7, 63), (129, 129, 1029), (200, 150, 5001), (257, 257, 333), (520, 520, 77)])
 def test_transform_rows_dev_guards(eng, din, dout, r):
     import torch
-    from oracle import plda_oracle_np as onp
     mean, T, psi = _model(din, din + r)
     T, psi = T[:dout].copy(), psi[:dout].copy()
     eng.set_model(mean, T, psi)
@@ -114,9 +113,11 @@ def test_transform_rows_dev_guards(eng, din, dout, r):
         return dict(u=o1.check("uniform"), m=o2.check("per-row counts"))
 
     a = _both(case)
-    model = dict(mean=mean, transform=T, psi=psi, offset=-T @ mean)
-    np.testing.assert_allclose(a["u"], onp.transform_ivector(model, x, 3), rtol=1e-11, atol=1e-12)
-    np.testing.assert_allclose(a["m"], onp.transform_ivector(model, x, n), rtol=1e-11, atol=1e-12)
+    # the rule of tests/transform_model.py against the longdouble definition of TransformIvector, never looser than the flat band
+    # rtol = 1e-11, atol = 1e-12 these outputs were held to against the NumPy restatement of the device's formula
+    import transform_model as TM
+    TM.assert_rule_many(a["u"], T, mean, psi, x, 3, "uniform", no_looser_than=(1e-11, 1e-12))
+    TM.assert_rule_many(a["m"], T, mean, psi, x, n, "per-row counts", no_looser_than=(1e-11, 1e-12))
 
 
 @pytest.mark.parametrize("d,m,nt,ld,mixed,znorm", [(51, 333, 517, 530, False, False), (51, 333, 517, 517, True, True),

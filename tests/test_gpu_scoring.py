@@ -94,8 +94,14 @@ def test_transform_groups_matches_oracle(engine, oracle):
         n, vec = got[int(k)]
         assert n == rc[i] and vec.dtype == np.float64
         np.testing.assert_allclose(vec, rv[i], rtol=1e-13, atol=1e-13 * np.abs(rv[i]).max())
-        # length-norm invariant: sum t^2/(psi + 1/n) = D
-        assert abs((vec ** 2 / (m["psi"] + 1.0 / n)).sum() - d) < 1e-8
+    # the rule of tests/transform_model.py against the longdouble definition on the longdouble group means: every element within
+    # its derived bound, the length-norm invariant sum t^2 / (psi + 1/n) = D to (D + 24) u (it was held to 1e-8)
+    import transform_model as TM
+    from test_gpu_transform_edges import _groups_reference
+    keys, counts, ref = _groups_reference((m["mean"], m["transform"], m["psi"]), x[:700], labels)
+    TM.assert_well_posed(ref)
+    assert keys.tolist() == [int(v) for v in rl] and counts.tolist() == [int(c) for c in rc]
+    TM.assert_rule(np.stack([got[int(k)][1] for k in keys]), ref, m["psi"], counts, "transform_groups")
 
 
 def test_znorm_stats_and_normalised_scores(engine, oracle):
@@ -318,9 +324,10 @@ def test_transform_rows_all_dimension_classes(din, dout, variant, monkeypatch):
     """K4 through every instantiation of the one-pass kernel -- the five dimension classes, each with its main block shape
     (row counts above one round of the persistent grid: 33 017) and its 64 / 32 / 16-row tail shapes (12 000 / 5 000 /
     <= 1 000 rows) -- and the GEMM + length-norm pair behind it (Dout > 512, or PLDA_TRANSFORM_VARIANT=1): ragged row
-    counts, K not a multiple of 16 or of 4, truncated models (Dout < Din), per-row and uniform counts, against the NumPy
-    restatement of TransformIvector (pldamodule.cpp:171 -> Plda::TransformIvector)."""
-    from oracle import plda_oracle_np as onp
+    counts, K not a multiple of 16 or of 4, truncated models (Dout < Din), per-row and uniform counts, against the longdouble
+    model of TransformIvector's definition (pldamodule.cpp:171 -> Plda::TransformIvector; tests/transform_model.py).  Which
+    shapes a CU count really reaches is asserted by name in tests/test_gpu_transform_edges.py."""
+    import transform_model as TM
     from plda_amd import MPlda
     monkeypatch.setenv("PLDA_TRANSFORM_VARIANT", variant)
     rng = np.random.default_rng(din * 1000 + dout)
@@ -330,14 +337,16 @@ def test_transform_rows_all_dimension_classes(din, dout, variant, monkeypatch):
     psi = np.sort(rng.random(dout) * 3.0 + 0.01)[::-1].copy()
     eng = MPlda(0)
     eng.set_model(mean, T, psi)
-    model = dict(mean=mean, transform=T, psi=psi, offset=-T @ mean)
     for r in (1, 63, 64, 129, 1000) + ((5000, 12000, 33017) if variant != "1" or din == 200 else ()):
         x = rng.standard_normal((r, din))
         n = rng.integers(1, 9, r).astype(np.int32)
         for ne in (3, n):
             got = eng.transform_array(x, ne)
-            ref = onp.transform_ivector(model, x, ne)
-            np.testing.assert_allclose(got, ref, rtol=1e-11, atol=1e-12)
+            # the rule of tests/transform_model.py, against the longdouble DEFINITION T (x - mean) -- and never looser than the
+            # flat band rtol = 1e-11, atol = 1e-12 this test held against the NumPy restatement of the device's own formula
+            plan = eng.transform_plan(r)
+            TM.assert_rule_many(got, T, mean, psi, x, ne, "%dx%d R = %d" % (din, dout, r), also=(plan["main_rows"] - 1, plan["main_rows"]),
+                                no_looser_than=(1e-11, 1e-12))
 
 
 def test_prepared_test_side_is_reused_and_invalidated():
@@ -480,10 +489,10 @@ def test_uniform_coefficients_follow_count_and_model(oracle):
 
 @pytest.mark.parametrize("dout", [200, 197, 193])
 def test_transform_c2_shape_rounds_and_tails(dout):
-    """K4 at the C2 shape (Din = 200, a uniform count) against the NumPy restatement of TransformIvector: exactly one round
+    """K4 at the C2 shape (Din = 200, a uniform count) against the longdouble model of TransformIvector: exactly one round
     of the persistent grid, whole rounds plus a 32-row and a 16-row tail launch; truncated models put the edge of the
     output inside the thirteenth column tile; one row of another magnitude (the norm is per row)."""
-    from oracle import plda_oracle_np as onp
+    import transform_model as TM
     from plda_amd import MPlda
     din = 200
     rng = np.random.default_rng(900 + dout)
@@ -491,15 +500,20 @@ def test_transform_c2_shape_rounds_and_tails(dout):
     T = (q * (0.5 + rng.random(din))[:, None])[:dout]
     mean = rng.random(din)
     psi = np.sort(rng.random(dout) * 3.0 + 0.01)[::-1].copy()
-    model = dict(mean=mean, transform=T, psi=psi, offset=-T @ mean)
     eng = MPlda(0)
     eng.set_model(mean, T, psi)
     for r, ne in ((32768, 1), (40011, 7), (100000, 3)):
         x = rng.standard_normal((r, din))
         x[r // 3] *= 1e3                                   # one row of another magnitude: the norm is per row
         got = eng.transform_array(x, ne)
-        ref = onp.transform_ivector(model, x, ne)
-        np.testing.assert_allclose(got, ref, rtol=1e-12, atol=1e-13)
+        # the rule of tests/transform_model.py against the longdouble definition, never looser than the flat band rtol = 1e-12,
+        # atol = 1e-13 this test held against the NumPy restatement; the plan says which launches these rows took
+        plan = eng.transform_plan(r)
+        assert (plan["arm"], plan["cls"], plan["main_block"]) == ("fused", 1, 128)
+        if plan["cus"] == 256:
+            assert (plan["main_rows"], plan["tail_block"]) == {32768: (32768, 0), 40011: (32768, 32), 100000: (98304, 16)}[r]
+        TM.assert_rule_many(got, T, mean, psi, x, ne, "C2 %d R = %d" % (dout, r), also=(r // 3, plan["main_rows"] - 1, plan["main_rows"]),
+                            no_looser_than=(1e-12, 1e-13))
 
 
 @pytest.mark.parametrize("d,kind", [(50, "mixed"), (200, "uniform"), (129, "many"), (64, "beyond")])

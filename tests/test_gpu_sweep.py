@@ -25,7 +25,7 @@ _CASES = os.environ.get("PLDA_SWEEP_CASES")
 OLD_COUNTS = {"stress_parity": 8, "stress_parity2": 8, "stress_parity3": 8, "stress_eer": 8, "stress_mixed_counts": 8}
 # every creation-time switch an engine of this file may be made under; all are cleared around MPlda(0)
 SWITCHES = ("PLDA_SNORM_SLAB_ROWS", "PLDA_SCRATCH_POISON", "PLDA_MIXED_VARIANT", "PLDA_AHC_SCRATCH_BYTES", "PLDA_DER_SCRATCH_BYTES",
-            "PLDA_EMBED_VARIANT", "PLDA_GEMM_VARIANT", "PLDA_SCORE_DTYPE", "PLDA_EER_VARIANT", "PLDA_EER_SLAB_ROWS", "PLDA_MINDCF_VARIANT", "PLDA_VBX_SCRATCH_BYTES", "PLDA_ADAPT_SLAB_ROWS")
+            "PLDA_EMBED_VARIANT", "PLDA_GEMM_VARIANT", "PLDA_SCORE_DTYPE", "PLDA_EER_VARIANT", "PLDA_EER_SLAB_ROWS", "PLDA_MINDCF_VARIANT", "PLDA_VBX_SCRATCH_BYTES", "PLDA_ADAPT_SLAB_ROWS", "PLDA_TRANSFORM_VARIANT")
 
 
 def _count(name, committed):
@@ -434,7 +434,25 @@ def _run_fusion(case, engines):
     assert P.unchanged()
 
 
-RUNNERS = {"topn": _run_topn, "der": _run_der, "ahc": _run_ahc, "asnorm": _run_asnorm, "mindcf": _run_mindcf, "calibration": _run_calibration, "embed": _run_embed, "vbx": _run_vbx, "adapt": _run_adapt, "fusion": _run_fusion}
+# ------------------------------------------------------------------------------------------- transform
+def _run_transform(case, engines):
+    """rule: test_gpu_transform_edges' (transform_model.assert_rule on one copy per launch and pool entry, all copies of an entry
+    inside a launch bit-identical); the arm and the launches asserted through plda_transform_plan"""
+    import test_gpu_transform_edges as T
+    import transform_model as M
+    eng = engines.get(PLDA_TRANSFORM_VARIANT=1) if case["arm"] == "pair" else engines.get()
+    pool = T._Pool(case["model"], case["x"], case["n"], case["form"], case["uniform"])
+    eng.set_model(*case["model"])
+    p1 = eng.transform_plan(1)
+    pair = case["arm"] == "pair" or case["dout"] > 512
+    assert p1["arm"] == ("pair" if pair else "fused")
+    r = sc.transform_rows(case["rows"], p1["cus"], p1["main_block"] if not pair else 128)
+    fig, plan = pool.run(eng, r, case["tag"], seed=case["index_seed"])
+    assert M.shapes_of(plan) == ({("main", 4)} if pair else sc.transform_shapes(case["rows"], p1["main_block"])), plan
+    print("deviation %.3g B, residual %.2f u" % (fig["dev"], fig["rho"]))
+
+
+RUNNERS = {"topn": _run_topn, "transform": _run_transform, "der": _run_der, "ahc": _run_ahc, "asnorm": _run_asnorm, "mindcf": _run_mindcf, "calibration": _run_calibration, "embed": _run_embed, "vbx": _run_vbx, "adapt": _run_adapt, "fusion": _run_fusion}
 assert sorted(RUNNERS) == sorted(sc.MODULES)
 _IDS = [(m, i) for m in sc.MODULES for i in range(_count(m, sc.COUNTS[m]))]
 

@@ -328,7 +328,37 @@ def _power_fusion(case):
     return _rejects(_compare, "the mutant", mutant, ref)
 
 
-POWER = {"topn": _power_topn, "der": _power_der, "ahc": _power_ahc, "asnorm": _power_asnorm, "mindcf": _power_mindcf,
+def _power_transform(case):
+    """one weight taken with a uniform count instead of the row's (per-row counts), the last k-step dropped (a uniform count)"""
+    import transform_model as M
+    mean, T, psi = case["model"]
+    n = case["n"] if case["form"] == "perrow" else case["uniform"]
+    ref = M.model(T, mean, psi, case["x"], n)
+    M.assert_well_posed(ref, case["tag"])
+    M.assert_rule(M.offset_form(T, mean, psi, case["x"], n), ref, psi, n, "the NumPy evaluation")
+    fault = "weight" if case["form"] == "perrow" else "kstep"
+    return _rejects(M.assert_rule, M.offset_form(T, mean, psi, case["x"], n, fault=fault, n_uniform=7), ref, psi, n, fault)
+
+
+def test_transform_rows_reach_the_shapes_they_name():
+    """transform_rows / transform_shapes against the dispatch's own arithmetic (csrc/transform.hip: transform_plan), on three CU
+    counts: every "rows" entry runs the launches it names, and together they are every block shape of both kinds of class"""
+    for g in (256, 304, 64):
+        for r0 in (128, 64):
+            seen = set()
+            for entry in sc.MENUS["transform"]["rows"]:
+                r = sc.transform_rows(entry, g, r0)
+                nb = -(-r // r0)
+                main = min(r, nb // g * g * r0)
+                tail = r - main
+                per_cu = -(-tail // g)
+                want = ({("main", r0)} if main else set()) | ({("tail", 16 if per_cu <= 16 else 32 if per_cu <= 32 else 64 if per_cu <= 64 else r0)} if tail else set())
+                assert sc.transform_shapes(entry, r0) == want, (g, r0, entry)
+                seen |= want
+            assert seen == {("main", r0)} | {("tail", b) for b in ((16, 32, 64, 128) if r0 == 128 else (16, 32, 64))}
+
+
+POWER = {"topn": _power_topn, "transform": _power_transform, "der": _power_der, "ahc": _power_ahc, "asnorm": _power_asnorm, "mindcf": _power_mindcf,
          "calibration": _power_calibration, "embed": _power_embed, "vbx": _power_vbx, "adapt": _power_adapt, "fusion": _power_fusion}
 
 
