@@ -15,8 +15,6 @@
 
 namespace plda {
 
-int compute_offset_device(plda_handle *h);
-
 namespace {
 
 constexpr int64_t AD_SLAB_BYTES = (int64_t)64 << 20;   // default slab: 64 MiB of centred rows ...

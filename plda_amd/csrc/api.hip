@@ -11,6 +11,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <deque>
 #include <new>
 #include <numeric>
 #include <stdexcept>
@@ -92,37 +93,6 @@ int model_to_device(plda_handle *h) {
   return PLDA_OK;
 }
 
-// implemented in score.hip / fit.hip
-int score_pairs_device(plda_handle *h, const double *dU, const int32_t *dn, const double *dV,
-                       const int64_t *de, const int64_t *dt, int64_t P, const double *dzmean,
-                       const double *dzstd, double *dout, int64_t M = 0, const plda::CountSet *cs = nullptr);
-int znorm_stats_device(plda_handle *h, const double *dbkg, int64_t Nb, int num_examples, int Din,
-                       const double *dmodels, int64_t M, double *dmean, double *dstd);
-int group_means_device(plda_handle *h, const double *dX, int64_t N, int D, const uint64_t *ddense,
-                       int64_t Ku, double *dmeans, int32_t *dcounts32);
-int compute_offset_device(plda_handle *h);
-int group_by_label_device(plda_handle *h, const uint64_t *dlabels, int64_t N, uint32_t **perm_out, int **offsets_out,
-                          uint64_t **uniq_out, int64_t *G_out);
-int group_centroids_device(plda_handle *h, const double *dX, int64_t N, int D, const uint32_t *perm, const int *offsets,
-                           int64_t G, double *dmeans, int32_t *dcounts32);
-// (the EER / DET / minDCF / calibration entry points, eer.hip, dcf.hip, calib.hip and their sharded forms: trial_source.hpp)
-// comm.hip
-int comm_init(plda_handle *h, int nranks, int rank, const void *uid);
-int comm_init_custom(plda_handle *h, int nranks, int rank, const plda_collectives *t);
-int comm_init_host(plda_handle *h, int nranks, int rank, const plda_host_collectives *t);
-int comm_init_peer(plda_handle *h, int nranks, int rank, const plda_host_collectives *t);
-int comm_destroy(plda_handle *h);
-int comm_check(plda_handle *h);
-int comm_describe(plda_handle *h, std::string &js);
-int score_matrix_sharded_device(plda_handle *h, const double *dU, const int32_t *dn, int n_uniform, int64_t M,
-                                const double *dV, int64_t Nt, const double *dzmean, const double *dzstd, float *dlocal,
-                                int64_t ld_local, float *dfull, int64_t ld_full, int64_t block_rows, int gather);
-int znorm_stats_sharded_device(plda_handle *h, const double *dbkg, int64_t Nb, int num_examples, int Din,
-                               const double *dmodels, int64_t M, double *dmean, double *dstd);
-int fit_sharded_device(plda_handle *h, const double *dX, int64_t N, int D, const uint64_t *dlabels, int64_t K, int iters);
-int cohort_stats_sharded_device(plda_handle *h, const double *dX, const int32_t *dn, int n_uniform, int64_t Rows, const double *dC,
-                                int64_t Nc, int64_t top_k, double *dmean, double *dstd);
-
 // the pinned ring + copy threads of the host-pointer entry points (hostio.hip), created on first use
 static int host_pipe(plda_handle *h, HostPipe **out) {
   if (!h->hostpipe) {
@@ -187,9 +157,6 @@ __global__ void smooth_kernel(double *__restrict__ T, double *__restrict__ psi, 
 
 using namespace plda;
 
-// one handle = one GPU + one stream: calls on the same handle from several threads are serialised
-#define PLDA_LOCK(h) std::lock_guard<std::recursive_mutex> plda_lock_guard_((h)->mu)
-
 // Nothing throws across the ABI: every entry point runs its body inside `guarded`, which turns a C++
 // exception (std::bad_alloc / std::length_error from a host-side container, std::system_error from the
 // mutex) into a status code + plda_last_error text.  (The reference lets Kaldi assertions abort the
@@ -211,42 +178,172 @@ template <typename F> int guarded(plda_handle *h, const char *fn, F &&body) noex
   catch (const std::exception &e) { return fail_quiet(h, PLDA_E_HIP, fn, e.what()); }
   catch (...) { return fail_quiet(h, PLDA_E_HIP, fn, "unknown C++ exception"); }
 }
+// Every entry point that takes a handle runs through one of these two.  entry: NULL handle -> PLDA_E_INVAL, then the handle's
+// lock (one handle = one GPU + one stream: calls on the same handle from several threads are serialised; taken inside guarded's
+// try, so a std::system_error from the mutex becomes a status code), then body().  device_entry: the same, and set_device(h)
+// before body() -- under the lock, because plda_set_stream on another thread may have changed h->stream since guarded read it.
+template <typename F> int entry(plda_handle *h, const char *fn, F &&body) noexcept {
+  return guarded(h, fn, [&]() -> int {
+    if (!h) return PLDA_E_INVAL;
+    std::lock_guard<std::recursive_mutex> lock(h->mu);
+    return body();
+  });
+}
+template <typename F> int device_entry(plda_handle *h, const char *fn, F &&body) noexcept {
+  return entry(h, fn, [&]() -> int {
+    PLDA_TRY(set_device(h));
+    return body();
+  });
+}
+
+// The device temporaries of one host-pointer call.  in(): a caller array uploaded into a fresh temporary (upload() above: the
+// pinned ring from 4 MiB on); out(): a temporary for a caller output; finish(rc of the device call): every output copied
+// back, whole, and one synchronisation.  An absent optional argument (NULL) gets no temporary and a NULL device pointer.
+// The temporaries live until the object does, i.e. to the end of the call.
+class Staged {
+ public:
+  explicit Staged(plda_handle *handle) : h(handle) {}
+  int in(const void *src, size_t bytes, const void **d) {
+    *d = nullptr;
+    if (!src) return PLDA_OK;
+    tmps.emplace_back();
+    PLDA_TRY(upload(h, tmps.back(), src, bytes));
+    *d = tmps.back().p;
+    return PLDA_OK;
+  }
+  template <typename T> int in(const T *src, size_t count, const T **d) {
+    const void *p = nullptr;
+    const int rc = in(static_cast<const void *>(src), count * sizeof(T), &p);
+    *d = static_cast<const T *>(p);
+    return rc;
+  }
+  // ring: the output goes back through download() (the pinned ring from 4 MiB on), otherwise by a plain asynchronous copy
+  template <typename T> int out(T *dst, size_t count, T **d, bool ring = false) {
+    *d = nullptr;
+    if (!dst) return PLDA_OK;
+    tmps.emplace_back();
+    PLDA_HIP(h, tmps.back().alloc(count * sizeof(T)));
+    *d = tmps.back().template as<T>();
+    outs.push_back(Out{dst, *d, count * sizeof(T), ring});
+    return PLDA_OK;
+  }
+  // a failed device call: nothing is copied, h->err stays the callee's, and the stream is drained before the temporaries go
+  int finish(int rc) {
+    if (rc != PLDA_OK) { (void)hipStreamSynchronize(h->stream); return rc; }
+    bool drained = false;
+    for (const Out &o : outs) {
+      if (!o.bytes) continue;
+      if (o.ring) PLDA_TRY(download(h, o.dst, o.src, o.bytes));
+      else PLDA_HIP(h, hipMemcpyAsync(o.dst, o.src, o.bytes, hipMemcpyDeviceToHost, h->stream));
+      drained = o.ring;      // (download ends in a synchronisation of its own)
+    }
+    if (!drained) PLDA_HIP(h, hipStreamSynchronize(h->stream));
+    return PLDA_OK;
+  }
+
+ private:
+  struct Out { void *dst; const void *src; size_t bytes; bool ring; };
+  plda_handle *h;
+  std::deque<Tmp> tmps;      // (a deque: Tmp neither copies nor moves)
+  std::vector<Out> outs;
+};
+
 // The host-list entry points (two lists of scores in caller memory): the argument check with the caller's message, both
 // lists uploaded, then body(device targets, device non-targets).
 template <typename F>
 int with_host_lists(plda_handle *h, const char *fn, const float *pos, int64_t np, const float *neg, int64_t nn, bool outputs_ok,
                     const char *refusal, F &&body) noexcept {
-  return guarded(h, fn, [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
+  return entry(h, fn, [&]() -> int {
     if (!pos || !neg || !outputs_ok || np <= 0 || nn <= 0) return fail(h, PLDA_E_INVAL, "%s", refusal);
     PLDA_TRY(set_device(h));
-    Tmp dP, dN;
-    PLDA_TRY(upload(h, dP, pos, (size_t)np * 4));
-    PLDA_TRY(upload(h, dN, neg, (size_t)nn * 4));
-    return body(dP.as<float>(), dN.as<float>());
+    Staged st(h);
+    const float *dpos, *dneg;
+    PLDA_TRY(st.in(pos, (size_t)np, &dpos));
+    PLDA_TRY(st.in(neg, (size_t)nn, &dneg));
+    return body(dpos, dneg);
   });
 }
 // the host-list forms: K target and K non-target arrays in caller memory, uploaded, then body(device pointer arrays)
 template <typename F>
 int with_host_fusion_lists(plda_handle *h, const char *fn, int32_t K, const float *const *pos, int64_t np, const float *const *neg,
                            int64_t nn, bool outputs_ok, F &&body) noexcept {
-  return guarded(h, fn, [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
+  return entry(h, fn, [&]() -> int {
     if (!outputs_ok) return fail(h, PLDA_E_INVAL, "%s: the output structure or the weight array is NULL", fn);
     PLDA_TRY(fusion_list_args_check(h, fn, K, pos, np, neg, nn));     // (fusion.hip: the one place that checks them)
     PLDA_TRY(set_device(h));
-    Tmp dP[PLDA_FUSION_MAX_SYSTEMS], dN[PLDA_FUSION_MAX_SYSTEMS];
+    Staged st(h);
     const float *pp[PLDA_FUSION_MAX_SYSTEMS], *pn[PLDA_FUSION_MAX_SYSTEMS];
     for (int k = 0; k < K; ++k) {
-      PLDA_TRY(upload(h, dP[k], pos[k], (size_t)np * 4));
-      PLDA_TRY(upload(h, dN[k], neg[k], (size_t)nn * 4));
-      pp[k] = dP[k].as<float>(); pn[k] = dN[k].as<float>();
+      PLDA_TRY(st.in(pos[k], (size_t)np, &pp[k]));
+      PLDA_TRY(st.in(neg[k], (size_t)nn, &pn[k]));
     }
     return body(pp, pn);
   });
 }
+// the settings plda_create reads from the environment: whole numbers stored as they are ...
+const struct { const char *name; int plda_handle::*member; } ENV_INT[] = {
+    {"PLDA_GEMM_VARIANT", &plda_handle::gemm_variant},     {"PLDA_PREP_VARIANT", &plda_handle::prep_variant},
+    {"PLDA_MIXED_VARIANT", &plda_handle::mixed_variant},   {"PLDA_EM_VARIANT", &plda_handle::em_variant},
+    {"PLDA_JACOBI_VARIANT", &plda_handle::jacobi_variant}, {"PLDA_GEMM64_VARIANT", &plda_handle::gemm64_variant},
+    {"PLDA_EIG_VARIANT", &plda_handle::eig_variant},       {"PLDA_EIG_DEBUG", &plda_handle::eig_debug},
+    {"PLDA_SORT_VARIANT", &plda_handle::sort_variant},     {"PLDA_ZNORM_VARIANT", &plda_handle::znorm_variant},
+    {"PLDA_EER_VARIANT", &plda_handle::eer_variant},       {"PLDA_MINDCF_VARIANT", &plda_handle::mindcf_variant},
+    {"PLDA_HOST_VARIANT", &plda_handle::host_variant},     {"PLDA_SWEEP_VARIANT", &plda_handle::sweep_variant},
+};
+const struct { const char *name; int64_t plda_handle::*member; } ENV_INT64[] = {
+    {"PLDA_EER_SLAB_ROWS", &plda_handle::eer_slab_rows},         {"PLDA_SNORM_SLAB_ROWS", &plda_handle::sn_slab_rows},
+    {"PLDA_ADAPT_SLAB_ROWS", &plda_handle::ad_slab_rows},        {"PLDA_AHC_SCRATCH_BYTES", &plda_handle::ahc_scratch_bytes},
+    {"PLDA_VBX_SCRATCH_BYTES", &plda_handle::vbx_scratch_bytes}, {"PLDA_DER_SCRATCH_BYTES", &plda_handle::der_scratch_bytes},
+};
+
+// ... and the ones that are checked: a refused value fails plda_create (the text goes to plda_last_error(NULL))
+int read_environment(plda_handle *h) {
+  {   // tests only (common.hpp): process-wide, taken from the environment of the latest plda_create
+    const char *v = std::getenv("PLDA_SCRATCH_POISON");
+    g_scratch_poison.store(v && std::atoi(v) == 1 ? 1 : 0);
+  }
+  for (const auto &e : ENV_INT)
+    if (const char *v = std::getenv(e.name)) h->*e.member = std::atoi(v);
+  for (const auto &e : ENV_INT64)
+    if (const char *v = std::getenv(e.name)) h->*e.member = std::atoll(v);
+  if (const char *v = std::getenv("PLDA_HIP_TRACE")) h->trace_on = h->trace_print = std::atoi(v) != 0;
+#if !PLDA_DIAG
+  {   // measurement arms (garbage scores or clock stamps): not in this build
+    static const int diag_only[] = {1, 2, 3, 4, 9, 10, 11, 12, 31, 33, 34, 35, 36, 37, 41, 44, 45, 46, 47, 54, 58, 62, 63};
+    for (int d : diag_only)
+      if (h->gemm_variant == d)
+        return fail(nullptr, PLDA_E_INVAL, "plda_create: PLDA_GEMM_VARIANT=%d is a measurement arm of the diagnostic build (PLDA_DIAG=1, "
+                                           "libplda_hip_diag.so); this library does not contain it", d);
+  }
+#endif
+  if (const char *v = std::getenv("PLDA_SCORE_DTYPE")) {
+    if (std::strcmp(v, "bf16x3") == 0) h->score_dtype = 1;
+    else if (std::strcmp(v, "f32") != 0 && *v) return fail(nullptr, PLDA_E_INVAL, "plda_create: PLDA_SCORE_DTYPE=%s (f32 or bf16x3)", v);
+  }
+  if (const char *v = std::getenv("PLDA_TRANSFORM_VARIANT")) {
+    // 0 or 1 only: the other numbers named A/B and timing arms that are gone -- a script that still sets one fails here
+    // instead of timing the product kernel under the old arm's name
+    if (*v && std::strcmp(v, "0") != 0 && std::strcmp(v, "1") != 0)
+      return fail(nullptr, PLDA_E_INVAL, "plda_create: PLDA_TRANSFORM_VARIANT=%s (0: the one-pass kernel, 1: GEMM + length-norm "
+                                         "pass; no other arm exists)", v);
+    h->transform_variant = std::atoi(v);
+  }
+  if (const char *v = std::getenv("PLDA_EMBED_VARIANT")) {
+    if (*v && std::strcmp(v, "0") != 0 && std::strcmp(v, "1") != 0)
+      return fail(nullptr, PLDA_E_INVAL, "plda_create: PLDA_EMBED_VARIANT=%s (0: by shape, 1: row pass + GEMM + row pass always)", v);
+    h->embed_variant = std::atoi(v);
+  }
+  if (const char *v = std::getenv("PLDA_EMBED_CUS")) {
+    // tests only: the CU count the fused kernel's main / tail split is sized for; a whole number 1 ... 4096 (empty or 0: the device's)
+    char *end = nullptr;
+    const long n = std::strtol(v, &end, 10);
+    if (*v && (*end != 0 || n < 0 || n > 4096))
+      return fail(nullptr, PLDA_E_INVAL, "plda_create: PLDA_EMBED_CUS=%s (a whole number 1 ... 4096; 0 or empty: the device's count)", v);
+    h->embed_cus = (int)n;
+  }
+  return PLDA_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -284,75 +381,13 @@ int plda_create(int device, plda_handle **out) {
       int n = 0;
       if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && n > 0) h->num_cus = n;
     }
-    if (e != hipSuccess) { delete h; return fail(nullptr, PLDA_E_HIP, "plda_create: %s", hipGetErrorString(e)); }
     h->stream = h->own_stream;
-    {   // tests only (common.hpp): process-wide, taken from the environment of the latest plda_create
-      const char *v = std::getenv("PLDA_SCRATCH_POISON");
-      g_scratch_poison.store(v && std::atoi(v) == 1 ? 1 : 0);
+    const int rc = e == hipSuccess ? read_environment(h) : fail(nullptr, PLDA_E_HIP, "plda_create: %s", hipGetErrorString(e));
+    if (rc != PLDA_OK) {   // the one failure exit once the handle exists: the stream this call created goes with it
+      if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
+      delete h;
+      return rc;
     }
-    if (const char *v = std::getenv("PLDA_GEMM_VARIANT")) h->gemm_variant = std::atoi(v);
-#if !PLDA_DIAG
-    {   // measurement arms (garbage scores or clock stamps): not in this build
-      static const int diag_only[] = {1, 2, 3, 4, 9, 10, 11, 12, 31, 33, 34, 35, 36, 37, 41, 44, 45, 46, 47, 54, 58, 62, 63};
-      for (int d : diag_only)
-        if (h->gemm_variant == d) {
-          delete h;
-          return fail(nullptr, PLDA_E_INVAL, "plda_create: PLDA_GEMM_VARIANT=%d is a measurement arm of the diagnostic build (PLDA_DIAG=1, "
-                                             "libplda_hip_diag.so); this library does not contain it", d);
-        }
-    }
-#endif
-    if (const char *v = std::getenv("PLDA_PREP_VARIANT")) h->prep_variant = std::atoi(v);
-    if (const char *v = std::getenv("PLDA_MIXED_VARIANT")) h->mixed_variant = std::atoi(v);
-    if (const char *v = std::getenv("PLDA_SCORE_DTYPE")) {
-      if (std::strcmp(v, "bf16x3") == 0) h->score_dtype = 1;
-      else if (std::strcmp(v, "f32") != 0 && *v) { delete h; return fail(nullptr, PLDA_E_INVAL, "plda_create: PLDA_SCORE_DTYPE=%s (f32 or bf16x3)", v); }
-    }
-    if (const char *v = std::getenv("PLDA_EM_VARIANT")) h->em_variant = std::atoi(v);
-    if (const char *v = std::getenv("PLDA_JACOBI_VARIANT")) h->jacobi_variant = std::atoi(v);
-    if (const char *v = std::getenv("PLDA_GEMM64_VARIANT")) h->gemm64_variant = std::atoi(v);
-    if (const char *v = std::getenv("PLDA_EIG_VARIANT")) h->eig_variant = std::atoi(v);
-    if (const char *v = std::getenv("PLDA_EIG_DEBUG")) h->eig_debug = std::atoi(v);
-    if (const char *v = std::getenv("PLDA_TRANSFORM_VARIANT")) {
-      // 0 or 1 only: the other numbers named A/B and timing arms that are gone -- a script that still sets one fails here
-      // instead of timing the product kernel under the old arm's name
-      if (*v && std::strcmp(v, "0") != 0 && std::strcmp(v, "1") != 0) {
-        delete h;
-        return fail(nullptr, PLDA_E_INVAL, "plda_create: PLDA_TRANSFORM_VARIANT=%s (0: the one-pass kernel, 1: GEMM + length-norm "
-                                           "pass; no other arm exists)", v);
-      }
-      h->transform_variant = std::atoi(v);
-    }
-    if (const char *v = std::getenv("PLDA_EMBED_VARIANT")) {
-      if (*v && std::strcmp(v, "0") != 0 && std::strcmp(v, "1") != 0) {
-        delete h;
-        return fail(nullptr, PLDA_E_INVAL, "plda_create: PLDA_EMBED_VARIANT=%s (0: by shape, 1: row pass + GEMM + row pass always)", v);
-      }
-      h->embed_variant = std::atoi(v);
-    }
-    if (const char *v = std::getenv("PLDA_EMBED_CUS")) {
-      // tests only: the CU count the fused kernel's main / tail split is sized for; a whole number 1 ... 4096 (empty or 0: the device's)
-      char *end = nullptr;
-      const long n = std::strtol(v, &end, 10);
-      if (*v && (*end != 0 || n < 0 || n > 4096)) {
-        delete h;
-        return fail(nullptr, PLDA_E_INVAL, "plda_create: PLDA_EMBED_CUS=%s (a whole number 1 ... 4096; 0 or empty: the device's count)", v);
-      }
-      h->embed_cus = (int)n;
-    }
-    if (const char *v = std::getenv("PLDA_SORT_VARIANT")) h->sort_variant = std::atoi(v);
-    if (const char *v = std::getenv("PLDA_ZNORM_VARIANT")) h->znorm_variant = std::atoi(v);
-    if (const char *v = std::getenv("PLDA_EER_VARIANT")) h->eer_variant = std::atoi(v);
-    if (const char *v = std::getenv("PLDA_MINDCF_VARIANT")) h->mindcf_variant = std::atoi(v);
-    if (const char *v = std::getenv("PLDA_EER_SLAB_ROWS")) h->eer_slab_rows = std::atoll(v);
-    if (const char *v = std::getenv("PLDA_SNORM_SLAB_ROWS")) h->sn_slab_rows = std::atoll(v);
-    if (const char *v = std::getenv("PLDA_ADAPT_SLAB_ROWS")) h->ad_slab_rows = std::atoll(v);
-    if (const char *v = std::getenv("PLDA_AHC_SCRATCH_BYTES")) h->ahc_scratch_bytes = std::atoll(v);
-    if (const char *v = std::getenv("PLDA_VBX_SCRATCH_BYTES")) h->vbx_scratch_bytes = std::atoll(v);
-    if (const char *v = std::getenv("PLDA_DER_SCRATCH_BYTES")) h->der_scratch_bytes = std::atoll(v);
-    if (const char *v = std::getenv("PLDA_HIP_TRACE")) h->trace_on = h->trace_print = std::atoi(v) != 0;
-    if (const char *v = std::getenv("PLDA_HOST_VARIANT")) h->host_variant = std::atoi(v);
-    if (const char *v = std::getenv("PLDA_SWEEP_VARIANT")) h->sweep_variant = std::atoi(v);
     *out = h;
     return PLDA_OK;
   });
@@ -399,28 +434,21 @@ const char *plda_last_error(const plda_handle *h) {
 }
 
 int plda_set_stream(plda_handle *h, void *hip_stream) {
-  return guarded(h, "plda_set_stream", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
+  return entry(h, "plda_set_stream", [&]() -> int {
     h->stream = reinterpret_cast<hipStream_t>(hip_stream);
     return PLDA_OK;
   });
 }
 
 int plda_reset_stream(plda_handle *h) {
-  return guarded(h, "plda_reset_stream", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
+  return entry(h, "plda_reset_stream", [&]() -> int {
     h->stream = h->own_stream;
     return PLDA_OK;
   });
 }
 
 int plda_synchronize(plda_handle *h) {
-  return guarded(h, "plda_synchronize", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
-    PLDA_TRY(set_device(h));
+  return device_entry(h, "plda_synchronize", [&]() -> int {
     PLDA_HIP(h, hipStreamSynchronize(h->stream));
     return comm_check(h);      // a peer-provider wait that gave up is reported where the caller synchronises
   });
@@ -429,44 +457,32 @@ int plda_synchronize(plda_handle *h) {
 // ---------------------------------------------------------------- fit
 int plda_fit_dev(plda_handle *h, const double *dX, int64_t N, int32_t D, const uint64_t *dlabels, int64_t K,
                  int32_t iters) {
-  return guarded(h, "plda_fit_dev", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
-    PLDA_TRY(set_device(h));
-    return fit_device(h, dX, N, D, dlabels, K, iters);
-  });
+  return device_entry(h, "plda_fit_dev", [&] { return fit_device(h, dX, N, D, dlabels, K, iters); });
 }
 
 int plda_fit(plda_handle *h, const double *X, int64_t N, int32_t D, const uint64_t *labels, int32_t iters) {
-  return guarded(h, "plda_fit", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
+  return entry(h, "plda_fit", [&]() -> int {
     if (!X || !labels || N <= 0 || D <= 0) return fail(h, PLDA_E_INVAL, "fit: bad argument");
     PLDA_TRY(set_device(h));
     uint64_t mx = 0;
     for (int64_t r = 0; r < N; ++r) mx = std::max(mx, labels[r]);
     if (mx >= (uint64_t)N) return fail(h, PLDA_E_LABELS, "fit: labels must be dense 0..K-1");
     const int64_t K = (int64_t)mx + 1;
-    Tmp dX, dL;
-    PLDA_TRY(upload(h, dX, X, (size_t)N * D * 8));
-    PLDA_TRY(upload(h, dL, labels, (size_t)N * 8));
-    return fit_device(h, dX.as<double>(), N, D, dL.as<uint64_t>(), K, iters);
+    Staged st(h);
+    const double *dX;
+    const uint64_t *dL;
+    PLDA_TRY(st.in(X, (size_t)N * D, &dX));
+    PLDA_TRY(st.in(labels, (size_t)N, &dL));
+    return fit_device(h, dX, N, D, dL, K, iters);
   });
 }
 
 int plda_fit_stats_dev(plda_handle *h, const double *dX, int64_t N, int32_t D, const uint64_t *dlabels, int64_t K) {
-  return guarded(h, "plda_fit_stats_dev", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
-    PLDA_TRY(set_device(h));
-    return fit_stats_device(h, dX, N, D, dlabels, K);
-  });
+  return device_entry(h, "plda_fit_stats_dev", [&] { return fit_stats_device(h, dX, N, D, dlabels, K); });
 }
 
 int plda_fit_get_stats_dev(plda_handle *h, double *dmeans, int64_t *dcounts, double *dscatter) {
-  return guarded(h, "plda_fit_get_stats_dev", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
+  return entry(h, "plda_fit_get_stats_dev", [&]() -> int {
     if (h->fit_K <= 0) return fail(h, PLDA_E_NOT_FITTED, "fit_get_stats_dev: no statistics pass has run on this handle");
     PLDA_TRY(set_device(h));
     const size_t K = (size_t)h->fit_K, D = (size_t)h->fit_D;
@@ -480,9 +496,7 @@ int plda_fit_get_stats_dev(plda_handle *h, double *dmeans, int64_t *dcounts, dou
 
 int plda_fit_em_dev(plda_handle *h, const double *dmeans, const int64_t *dcounts, int64_t K, const double *dscatter,
                     int32_t D, int32_t iters) {
-  return guarded(h, "plda_fit_em_dev", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
+  return entry(h, "plda_fit_em_dev", [&]() -> int {
     if (!dmeans || !dcounts || !dscatter || K <= 0 || D <= 0) return fail(h, PLDA_E_INVAL, "fit_em: bad argument");
     if (D > 2048) return fail(h, PLDA_E_INVAL, "fit: featdim %d > 2048 unsupported", D);
     PLDA_TRY(set_device(h));
@@ -501,18 +515,16 @@ int plda_fit_em_dev(plda_handle *h, const double *dmeans, const int64_t *dcounts
 }
 
 int plda_fit_timings(plda_handle *h, double out_ms[4]) {
-  return guarded(h, "plda_fit_timings", [&]() -> int {
-    if (!h || !out_ms) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
+  return entry(h, "plda_fit_timings", [&]() -> int {
+    if (!out_ms) return PLDA_E_INVAL;
     for (int i = 0; i < 4; ++i) out_ms[i] = h->fit_ms[i];
     return PLDA_OK;
   });
 }
 
 int plda_fit_plan(plda_handle *h, int32_t out[2]) {
-  return guarded(h, "plda_fit_plan", [&]() -> int {
-    if (!h || !out) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
+  return entry(h, "plda_fit_plan", [&]() -> int {
+    if (!out) return PLDA_E_INVAL;
     out[0] = h->em_groups;
     out[1] = h->em_form;
     return PLDA_OK;
@@ -520,9 +532,8 @@ int plda_fit_plan(plda_handle *h, int32_t out[2]) {
 }
 
 int plda_fit_num_classes(plda_handle *h, int64_t *K) {
-  return guarded(h, "plda_fit_num_classes", [&]() -> int {
-    if (!h || !K) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
+  return entry(h, "plda_fit_num_classes", [&]() -> int {
+    if (!K) return PLDA_E_INVAL;
     *K = h->fit_K;
     return PLDA_OK;
   });
@@ -530,9 +541,7 @@ int plda_fit_num_classes(plda_handle *h, int64_t *K) {
 
 int plda_fit_get_stats(plda_handle *h, double *means, int64_t *counts, double *scatter, double *sum,
                        double *W, double *B) {
-  return guarded(h, "plda_fit_get_stats", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
+  return entry(h, "plda_fit_get_stats", [&]() -> int {
     if (h->fit_K <= 0) return fail(h, PLDA_E_NOT_FITTED, "fit_get_stats: no fit has run on this handle");
     PLDA_TRY(set_device(h));
     const size_t K = (size_t)h->fit_K, D = (size_t)h->fit_D;
@@ -549,9 +558,7 @@ int plda_fit_get_stats(plda_handle *h, double *means, int64_t *counts, double *s
 
 // ---------------------------------------------------------------- model
 int plda_get_dims(plda_handle *h, int32_t *Dout, int32_t *Din) {
-  return guarded(h, "plda_get_dims", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
+  return entry(h, "plda_get_dims", [&]() -> int {
     if (!h->fitted) return fail(h, PLDA_E_NOT_FITTED, "model not fitted");
     if (Dout) *Dout = h->Dout;
     if (Din) *Din = h->Din;
@@ -560,9 +567,7 @@ int plda_get_dims(plda_handle *h, int32_t *Dout, int32_t *Din) {
 }
 
 int plda_get_model(plda_handle *h, double *mean, double *transform, double *psi, double *offset) {
-  return guarded(h, "plda_get_model", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
+  return entry(h, "plda_get_model", [&]() -> int {
     if (!h->fitted) return fail(h, PLDA_E_NOT_FITTED, "model not fitted");
     if (mean) std::memcpy(mean, h->h_mean.data(), h->h_mean.size() * 8);
     if (transform) std::memcpy(transform, h->h_transform.data(), h->h_transform.size() * 8);
@@ -583,9 +588,7 @@ static int refresh_offset(plda_handle *h) {
 
 int plda_set_model(plda_handle *h, int32_t Dout, int32_t Din, const double *mean, const double *transform,
                    const double *psi) {
-  return guarded(h, "plda_set_model", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
+  return entry(h, "plda_set_model", [&]() -> int {
     if (Dout <= 0 || Din <= 0 || Dout > Din || !mean || !transform || !psi)
       return fail(h, PLDA_E_INVAL, "set_model: bad argument");
     PLDA_TRY(set_device(h));
@@ -602,9 +605,7 @@ int plda_set_model(plda_handle *h, int32_t Dout, int32_t Din, const double *mean
 }
 
 int plda_truncate(plda_handle *h, int32_t targetdim) {
-  return guarded(h, "plda_truncate", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
+  return entry(h, "plda_truncate", [&]() -> int {
     if (!h->fitted) return fail(h, PLDA_E_NOT_FITTED, "model not fitted");
     if (targetdim <= 0 || targetdim > h->Dout) return fail(h, PLDA_E_INVAL, "truncate: targetdim %d not in [1,%d]", targetdim, h->Dout);
     PLDA_TRY(set_device(h));
@@ -618,9 +619,7 @@ int plda_truncate(plda_handle *h, int32_t targetdim) {
 }
 
 int plda_smooth(plda_handle *h, double factor) {
-  return guarded(h, "plda_smooth", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
+  return entry(h, "plda_smooth", [&]() -> int {
     if (!h->fitted) return fail(h, PLDA_E_NOT_FITTED, "model not fitted");
     if (!(factor >= 0.0 && factor <= 1.0)) return fail(h, PLDA_E_INVAL, "smooth: factor must be in [0,1]");
     PLDA_TRY(set_device(h));
@@ -635,75 +634,39 @@ int plda_smooth(plda_handle *h, double factor) {
 
 // ---------------------------------------------------------------- domain adaptation (adapt.hip)
 int plda_adapt_reset(plda_handle *h) {
-  return guarded(h, "plda_adapt_reset", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
-    return adapt_reset(h);
-  });
+  return entry(h, "plda_adapt_reset", [&] { return adapt_reset(h); });
 }
 
 int plda_adapt_accumulate_dev(plda_handle *h, const double *dX, int64_t N, int32_t Din, const double *dweights) {
-  return guarded(h, "plda_adapt_accumulate_dev", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
-    PLDA_TRY(set_device(h));
-    return adapt_accumulate(h, dX, N, Din, dweights, false);
-  });
+  return device_entry(h, "plda_adapt_accumulate_dev", [&] { return adapt_accumulate(h, dX, N, Din, dweights, false); });
 }
 
 int plda_adapt_accumulate(plda_handle *h, const double *X, int64_t N, int32_t Din, const double *weights) {
-  return guarded(h, "plda_adapt_accumulate", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
-    PLDA_TRY(set_device(h));
-    return adapt_accumulate(h, X, N, Din, weights, true);   // slab by slab through a bounded staging buffer
-  });
+  return device_entry(h, "plda_adapt_accumulate", [&] { return adapt_accumulate(h, X, N, Din, weights, true); });
 }
 
 int plda_adapt_get_stats(plda_handle *h, double *tw, int64_t *rows, double *pilot, double *s1, double *s2) {
-  return guarded(h, "plda_adapt_get_stats", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
-    PLDA_TRY(set_device(h));
-    return adapt_get_stats(h, tw, rows, pilot, s1, s2);
-  });
+  return device_entry(h, "plda_adapt_get_stats", [&] { return adapt_get_stats(h, tw, rows, pilot, s1, s2); });
 }
 
 int plda_adapt_add_stats(plda_handle *h, double tw, int64_t rows, const double *pilot, const double *s1, const double *s2) {
-  return guarded(h, "plda_adapt_add_stats", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
-    PLDA_TRY(set_device(h));
-    return adapt_add_stats(h, tw, rows, pilot, s1, s2);
-  });
+  return device_entry(h, "plda_adapt_add_stats", [&] { return adapt_add_stats(h, tw, rows, pilot, s1, s2); });
 }
 
 int plda_adapt_update(plda_handle *h, double within_scale, double between_scale, double mean_diff_scale, double *eig,
                       plda_adapt_info *info) {
-  return guarded(h, "plda_adapt_update", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
-    PLDA_TRY(set_device(h));
-    return adapt_update(h, within_scale, between_scale, mean_diff_scale, eig, info);
-  });
+  return device_entry(h, "plda_adapt_update", [&] { return adapt_update(h, within_scale, between_scale, mean_diff_scale, eig, info); });
 }
 
 int plda_blend_model(plda_handle *h, int32_t D, const double *mean2, const double *transform2, const double *psi2, double alpha,
                      double alpha_mean) {
-  return guarded(h, "plda_blend_model", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
-    PLDA_TRY(set_device(h));
-    return blend_model(h, D, mean2, transform2, psi2, alpha, alpha_mean);
-  });
+  return device_entry(h, "plda_blend_model", [&] { return blend_model(h, D, mean2, transform2, psi2, alpha, alpha_mean); });
 }
 
 // ---------------------------------------------------------------- transform
 int plda_transform_rows_dev(plda_handle *h, const double *dXbar, int64_t R, int32_t Din, const int32_t *dn,
                             int32_t n_uniform, double *dout) {
-  return guarded(h, "plda_transform_rows_dev", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
+  return entry(h, "plda_transform_rows_dev", [&]() -> int {
     if (!dn && n_uniform <= 0) return fail(h, PLDA_E_INVAL, "transform_rows: need num_examples or n_uniform > 0");
     PLDA_TRY(set_device(h));
     return transform_rows_device(h, dXbar, R, Din, dn, n_uniform, dout);
@@ -712,9 +675,7 @@ int plda_transform_rows_dev(plda_handle *h, const double *dXbar, int64_t R, int3
 
 int plda_transform_rows(plda_handle *h, const double *Xbar, int64_t R, int32_t Din, const int32_t *num_examples,
                         int32_t n_uniform, double *out) {
-  return guarded(h, "plda_transform_rows", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
+  return entry(h, "plda_transform_rows", [&]() -> int {
     if (!h->fitted) return fail(h, PLDA_E_NOT_FITTED, "transform: model not fitted");
     if (R <= 0) return PLDA_OK;
     if (!Xbar || !out) return fail(h, PLDA_E_INVAL, "transform_rows: bad argument");
@@ -726,19 +687,19 @@ int plda_transform_rows(plda_handle *h, const double *Xbar, int64_t R, int32_t D
       if (bad) return fail(h, PLDA_E_INVAL, "transform_rows: %lld of %lld rows have num_examples <= 0 (the first is row %lld)", (long long)bad, (long long)R, (long long)first);
     }
     PLDA_TRY(set_device(h));
-    Tmp dX, dN, dO;
-    PLDA_TRY(upload(h, dX, Xbar, (size_t)R * Din * 8));
-    if (num_examples) PLDA_TRY(upload(h, dN, num_examples, (size_t)R * 4));
-    PLDA_HIP(h, dO.alloc((size_t)R * h->Dout * 8));
-    PLDA_TRY(transform_rows_device(h, dX.as<double>(), R, Din, num_examples ? dN.as<int32_t>() : nullptr, n_uniform, dO.as<double>()));
-    return download(h, out, dO.p, (size_t)R * h->Dout * 8);
+    Staged st(h);
+    const double *dX;
+    const int32_t *dN;
+    double *dO;
+    PLDA_TRY(st.in(Xbar, (size_t)R * Din, &dX));
+    PLDA_TRY(st.in(num_examples, (size_t)R, &dN));
+    PLDA_TRY(st.out(out, (size_t)R * h->Dout, &dO, true));
+    return st.finish(transform_rows_device(h, dX, R, Din, dN, n_uniform, dO));
   });
 }
 
 int plda_transform_plan(plda_handle *h, int64_t R, int64_t out[8]) {
-  return guarded(h, "plda_transform_plan", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
+  return entry(h, "plda_transform_plan", [&]() -> int {
     if (!h->fitted) return fail(h, PLDA_E_NOT_FITTED, "transform: model not fitted");
     if (!out) return fail(h, PLDA_E_INVAL, "transform_plan: out is NULL");
     if (R < 0) return fail(h, PLDA_E_INVAL, "transform_plan: R = %lld (must be >= 0)", (long long)R);
@@ -771,9 +732,7 @@ static int transform_groups_device(plda_handle *h, const double *dX, int64_t N, 
 
 int plda_transform_groups_dev(plda_handle *h, const double *dX, int64_t N, int32_t Din, const uint64_t *dlabels,
                               uint64_t *dout_labels, int32_t *dout_counts, double *dout_vecs, int64_t *Ku) {
-  return guarded(h, "plda_transform_groups_dev", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
+  return entry(h, "plda_transform_groups_dev", [&]() -> int {
     if (!h->fitted) return fail(h, PLDA_E_NOT_FITTED, "transform: model not fitted");
     if (!Ku) return fail(h, PLDA_E_INVAL, "transform_groups: Ku is NULL");
     if (N <= 0) { *Ku = 0; return PLDA_OK; }
@@ -789,9 +748,7 @@ int plda_transform_groups_dev(plda_handle *h, const double *dX, int64_t N, int32
 
 int plda_transform_groups(plda_handle *h, const double *X, int64_t N, int32_t Din, const uint64_t *labels,
                           uint64_t *out_labels, int64_t *out_counts, double *out_vecs, int64_t *Ku) {
-  return guarded(h, "plda_transform_groups", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
+  return entry(h, "plda_transform_groups", [&]() -> int {
     if (!h->fitted) return fail(h, PLDA_E_NOT_FITTED, "transform: model not fitted");
     if (!Ku) return fail(h, PLDA_E_INVAL, "transform_groups: Ku is NULL");
     if (N <= 0) { *Ku = 0; return PLDA_OK; }
@@ -800,15 +757,18 @@ int plda_transform_groups(plda_handle *h, const double *X, int64_t N, int32_t Di
     PLDA_TRY(set_device(h));
     const int64_t cap = *Ku;
     if (cap <= 0) return fail(h, PLDA_E_CAPACITY, "transform_groups: capacity must be > 0");
-    Tmp dX, dL, dM, dC, dO, dU;
-    PLDA_TRY(upload(h, dX, X, (size_t)N * Din * 8));
-    PLDA_TRY(upload(h, dL, labels, (size_t)N * 8));
+    Staged st(h);
+    const double *dX;
+    const uint64_t *dL;
+    Tmp dM, dC, dO, dU;
+    PLDA_TRY(st.in(X, (size_t)N * Din, &dX));
+    PLDA_TRY(st.in(labels, (size_t)N, &dL));
     const int64_t gmax = std::min(cap, N);
     PLDA_HIP(h, dC.alloc((size_t)gmax * 4));
     PLDA_HIP(h, dO.alloc((size_t)gmax * h->Dout * 8));
     PLDA_HIP(h, dU.alloc((size_t)gmax * 8));
     int64_t G = gmax;
-    const int rc = transform_groups_device(h, dX.as<double>(), N, Din, dL.as<uint64_t>(), dU.as<uint64_t>(),
+    const int rc = transform_groups_device(h, dX, N, Din, dL, dU.as<uint64_t>(),
                                            dC.as<int32_t>(), dO.as<double>(), &G, dM);
     if (rc != PLDA_OK) { if (rc == PLDA_E_CAPACITY) *Ku = G; return rc; }
     std::vector<int32_t> c32((size_t)G);
@@ -826,28 +786,17 @@ int plda_transform_groups(plda_handle *h, const double *X, int64_t N, int32_t Di
 int plda_score_matrix_dev(plda_handle *h, const double *dU, const int32_t *dn_enrol, int32_t n_uniform, int64_t M,
                           const double *dV, int64_t Nt, const double *dzmean, const double *dzstd, float *dout,
                           int64_t ld_out) {
-  return guarded(h, "plda_score_matrix_dev", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
-    PLDA_TRY(set_device(h));
+  return device_entry(h, "plda_score_matrix_dev", [&] {
     return score_matrix_device(h, dU, dn_enrol, n_uniform, M, dV, Nt, dzmean, dzstd, dout, ld_out);
   });
 }
 
 int plda_score_prepare_dev(plda_handle *h, const double *dV, int64_t Nt, int32_t mixed_counts, int32_t n_uniform) {
-  return guarded(h, "plda_score_prepare_dev", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
-    PLDA_TRY(set_device(h));
-    return score_prepare_device(h, dV, Nt, mixed_counts != 0 ? 1 : 0, n_uniform, nullptr);
-  });
+  return device_entry(h, "plda_score_prepare_dev", [&] { return score_prepare_device(h, dV, Nt, mixed_counts != 0 ? 1 : 0, n_uniform, nullptr); });
 }
 
 int plda_score_prepare_counts_dev(plda_handle *h, const double *dV, int64_t Nt, const int32_t *counts, int32_t num_counts) {
-  return guarded(h, "plda_score_prepare_counts_dev", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
-    PLDA_TRY(set_device(h));
+  return device_entry(h, "plda_score_prepare_counts_dev", [&]() -> int {
     if (!counts || num_counts <= 0) return fail(h, PLDA_E_INVAL, "score_prepare_counts: empty count list");
     CountSet cs;
     score_count_set_host(counts, num_counts, &cs);     // (sorted, duplicates dropped; G = 0: outside what the bucketed form takes)
@@ -857,9 +806,7 @@ int plda_score_prepare_counts_dev(plda_handle *h, const double *dV, int64_t Nt, 
 }
 
 int plda_score_unprepare(plda_handle *h) {
-  return guarded(h, "plda_score_unprepare", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
+  return entry(h, "plda_score_unprepare", [&]() -> int {
     h->prep_valid = false;
     return PLDA_OK;
   });
@@ -872,10 +819,12 @@ static int score_matrix_host_serial(plda_handle *h, const double *U, const int32
                                     const double *V, int64_t Nt, const double *zmean, const double *zstd, float *out,
                                     int64_t ld_out) {
   const int D = h->Dout;
-  Tmp dV, dU, dN, dZm, dZs, dO;
+  Staged st(h);
+  const double *dV;
+  Tmp dU, dN, dZm, dZs, dO;
   CountSet cs;                                           // the distinct counts of ALL rows: every slab sees the same set
   if (n_enrol) score_count_set_host(n_enrol, M, &cs);
-  PLDA_TRY(upload(h, dV, V, (size_t)Nt * D * 8));
+  PLDA_TRY(st.in(V, (size_t)Nt * D, &dV));
   // row slabs so that the device score block stays <= 1 GiB
   int64_t slab = std::max<int64_t>(128, ((1ll << 30) / 4 / Nt) / 128 * 128);
   slab = std::min(slab, round_up(M, 128));
@@ -892,7 +841,7 @@ static int score_matrix_host_serial(plda_handle *h, const double *U, const int32
       PLDA_HIP(h, hipMemcpyAsync(dZs.p, zstd + r0, (size_t)m * 8, hipMemcpyHostToDevice, h->stream));
     }
     PLDA_TRY(score_matrix_device(h, dU.as<double>(), n_enrol ? dN.as<int32_t>() : nullptr, n_uniform, m,
-                                 dV.as<double>(), Nt, (zmean && zstd) ? dZm.as<double>() : nullptr,
+                                 dV, Nt, (zmean && zstd) ? dZm.as<double>() : nullptr,
                                  (zmean && zstd) ? dZs.as<double>() : nullptr, dO.as<float>(), Nt,
                                  /*reuse_packed_B=*/r0 > 0, n_enrol ? &cs : nullptr));   // the test side is packed once, not per slab
     if (ld_out == Nt)
@@ -913,9 +862,7 @@ static int score_matrix_host_serial(plda_handle *h, const double *U, const int32
 int plda_score_matrix(plda_handle *h, const double *U, const int32_t *n_enrol, int32_t n_uniform, int64_t M,
                       const double *V, int64_t Nt, const double *zmean, const double *zstd, float *out,
                       int64_t ld_out) {
-  return guarded(h, "plda_score_matrix", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
+  return entry(h, "plda_score_matrix", [&]() -> int {
     if (!h->fitted) return fail(h, PLDA_E_NOT_FITTED, "score_matrix: model not fitted");
     if (M <= 0 || Nt <= 0) return PLDA_OK;
     if (!U || !V || !out || ld_out < Nt) return fail(h, PLDA_E_INVAL, "score_matrix: bad argument");
@@ -933,13 +880,16 @@ int plda_score_matrix(plda_handle *h, const double *U, const int32_t *n_enrol, i
     HostPipe *hp = nullptr;
     PLDA_TRY(host_pipe(h, &hp));
     const int64_t slab = fit_rows >= 256 ? fit_rows / 128 * 128 : fit_rows;
-    Tmp dV, dU, dN, dZm, dZs;
+    Staged st(h);
+    const double *dV, *dU, *dZm, *dZs;
+    const int32_t *dN;
     CountSet cs;                                         // the distinct counts of ALL rows, from the host array: no device pass
     if (n_enrol) score_count_set_host(n_enrol, M, &cs);
-    PLDA_TRY(upload(h, dV, V, (size_t)Nt * D * 8));
-    PLDA_TRY(upload(h, dU, U, (size_t)M * D * 8));
-    if (n_enrol) PLDA_TRY(upload(h, dN, n_enrol, (size_t)M * 4));
-    if (zn) { PLDA_TRY(upload(h, dZm, zmean, (size_t)M * 8)); PLDA_TRY(upload(h, dZs, zstd, (size_t)M * 8)); }
+    PLDA_TRY(st.in(V, (size_t)Nt * D, &dV));
+    PLDA_TRY(st.in(U, (size_t)M * D, &dU));
+    PLDA_TRY(st.in(n_enrol, (size_t)M, &dN));
+    PLDA_TRY(st.in(zn ? zmean : nullptr, (size_t)M, &dZm));
+    PLDA_TRY(st.in(zn ? zstd : nullptr, (size_t)M, &dZs));
     for (auto &b : h->hio_O) PLDA_HIP(h, b.reserve((size_t)std::min(slab, M) * Nt * 4));
     advise_huge(out, (size_t)((M - 1) * ld_out + Nt) * 4);
     size_t i = 0;
@@ -949,9 +899,8 @@ int plda_score_matrix(plda_handle *h, const double *U, const int32_t *n_enrol, i
       float *dO = h->hio_O[i & 1].as<float>();
       hipError_t e = hp->begin_slab(h->stream, i);
       if (e != hipSuccess) { rc = hip_fail(h, e, "begin_slab", __FILE__, __LINE__); break; }
-      rc = score_matrix_device(h, dU.as<double>() + r0 * D, n_enrol ? dN.as<int32_t>() + r0 : nullptr, n_uniform, m,
-                               dV.as<double>(), Nt, zn ? dZm.as<double>() + r0 : nullptr, zn ? dZs.as<double>() + r0 : nullptr,
-                               dO, Nt, /*reuse_packed_B=*/r0 > 0, n_enrol ? &cs : nullptr);
+      rc = score_matrix_device(h, dU + r0 * D, dN ? dN + r0 : nullptr, n_uniform, m, dV, Nt, zn ? dZm + r0 : nullptr,
+                               zn ? dZs + r0 : nullptr, dO, Nt, /*reuse_packed_B=*/r0 > 0, n_enrol ? &cs : nullptr);
       if (rc != PLDA_OK) break;
       e = hp->ship_slab(h->stream, i, dO, (size_t)m * Nt * 4, reinterpret_cast<char *>(out + r0 * ld_out), (size_t)ld_out * 4,
                         (size_t)Nt * 4, (size_t)m);
@@ -993,18 +942,14 @@ static int trace_summary(plda_handle *h, std::string &out, bool reset) {
 }
 
 int plda_trace_enable(plda_handle *h, int32_t on) {
-  return guarded(h, "plda_trace_enable", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
+  return entry(h, "plda_trace_enable", [&]() -> int {
     h->trace_on = on != 0;
     return PLDA_OK;
   });
 }
 
 int plda_trace_read(plda_handle *h, char *json, int64_t cap, int32_t reset) {
-  return guarded(h, "plda_trace_read", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
+  return entry(h, "plda_trace_read", [&]() -> int {
     if (!json || cap <= 0) return fail(h, PLDA_E_INVAL, "trace_read: bad argument");
     PLDA_TRY(set_device(h));
     std::string js;
@@ -1017,19 +962,14 @@ int plda_trace_read(plda_handle *h, char *json, int64_t cap, int32_t reset) {
 }
 
 int plda_profile_enable(plda_handle *h, int32_t on) {
-  return guarded(h, "plda_profile_enable", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
+  return entry(h, "plda_profile_enable", [&]() -> int {
     h->prof_on = on != 0;
     return PLDA_OK;
   });
 }
 
 int plda_profile_read(plda_handle *h, double *gemm_ms, int64_t *launches, double *gemm_flop, int32_t reset) {
-  return guarded(h, "plda_profile_read", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
-    PLDA_TRY(set_device(h));
+  return device_entry(h, "plda_profile_read", [&]() -> int {
     PLDA_HIP(h, hipStreamSynchronize(h->stream));
     double total = 0.0;
     for (size_t i = 0; i < h->prof_used; ++i) {
@@ -1046,9 +986,7 @@ int plda_profile_read(plda_handle *h, double *gemm_ms, int64_t *launches, double
 }
 
 int plda_profile_timeline(plda_handle *h, uint64_t *out, int64_t cap_words) {
-  return guarded(h, "plda_profile_timeline", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
+  return entry(h, "plda_profile_timeline", [&]() -> int {
     if (!out || cap_words < (int64_t)TIMELINE_WORDS) return fail(h, PLDA_E_CAPACITY, "profile_timeline: need %zu words", TIMELINE_WORDS);
     if (!h->timeline_valid) return fail(h, PLDA_E_INVAL, "profile_timeline: no PLDA_GEMM_VARIANT=31 launch has run on this handle");
     PLDA_TRY(set_device(h));
@@ -1060,9 +998,7 @@ int plda_profile_timeline(plda_handle *h, uint64_t *out, int64_t cap_words) {
 
 int plda_gemm_f64(plda_handle *h, int64_t M, int64_t N, int64_t K, double alpha, const double *A, int32_t transA,
                   const double *B, int32_t transB, const double *kw, double beta, double *C, int32_t batch) {
-  return guarded(h, "plda_gemm_f64", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
+  return entry(h, "plda_gemm_f64", [&]() -> int {
     note_kernels_clear(h);
     if (!A || !B || !C || M <= 0 || N <= 0 || K <= 0 || batch <= 0 || (kw && batch != 1))
       return fail(h, PLDA_E_INVAL, "gemm_f64: bad argument");
@@ -1093,26 +1029,25 @@ int plda_gemm_f64(plda_handle *h, int64_t M, int64_t N, int64_t K, double alpha,
 }
 
 int plda_spd_inverse(plda_handle *h, const double *A, int32_t D, double *inverse) {
-  return guarded(h, "plda_spd_inverse", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
+  return entry(h, "plda_spd_inverse", [&]() -> int {
     note_kernels_clear(h);
     if (!A || !inverse || D <= 0 || D > 2048) return fail(h, PLDA_E_INVAL, "spd_inverse: bad argument");
     PLDA_TRY(set_device(h));
     const size_t DD = (size_t)D * D;
-    Tmp dA, dO, dS, dF;
+    Staged st(h);
+    Tmp dA, dS, dF;
+    double *dO;
     PLDA_HIP(h, dA.alloc(DD * 8));
-    PLDA_HIP(h, dO.alloc(DD * 8));
+    PLDA_TRY(st.out(inverse, DD, &dO));
     PLDA_HIP(h, dS.alloc(3 * DD * 8));
     PLDA_HIP(h, dF.alloc(sizeof(int)));
     PLDA_HIP(h, hipMemcpyAsync(dA.p, A, DD * 8, hipMemcpyHostToDevice, h->stream));
     PLDA_HIP(h, hipMemsetAsync(dF.p, 0, sizeof(int), h->stream));
-    PLDA_TRY(spd_inverse_blocked(h, dA.as<double>(), D, D, (int64_t)DD, dO.as<double>(), D, (int64_t)DD, dS.as<double>(),
-                                 (int64_t)(3 * DD), dF.as<int>(), 1));
+    PLDA_TRY(spd_inverse_blocked(h, dA.as<double>(), D, D, (int64_t)DD, dO, D, (int64_t)DD, dS.as<double>(), (int64_t)(3 * DD),
+                                 dF.as<int>(), 1));
     int bad = 0;
-    PLDA_HIP(h, hipMemcpyAsync(inverse, dO.p, DD * 8, hipMemcpyDeviceToHost, h->stream));
     PLDA_HIP(h, hipMemcpyAsync(&bad, dF.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    PLDA_HIP(h, hipStreamSynchronize(h->stream));
+    PLDA_TRY(st.finish(PLDA_OK));
     if (bad) return fail(h, PLDA_E_NUMERIC, "spd_inverse: the matrix is not positive definite");
     return PLDA_OK;
   });
@@ -1120,50 +1055,45 @@ int plda_spd_inverse(plda_handle *h, const double *A, int32_t D, double *inverse
 
 int plda_sym_eig(plda_handle *h, const double *G, int32_t D, int32_t method, double *eigenvalues, double *eigenvectors,
                  int32_t *method_used) {
-  return guarded(h, "plda_sym_eig", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
+  return entry(h, "plda_sym_eig", [&]() -> int {
     note_kernels_clear(h);
     if (!G || !eigenvalues || !eigenvectors || D <= 0 || D > 2048) return fail(h, PLDA_E_INVAL, "sym_eig: bad argument");
     if (method < 0 || method > 2) return fail(h, PLDA_E_INVAL, "sym_eig: method must be 0 (default), 1 (Jacobi) or 2 (direct)");
     if (method == 1 && D > 1024) return fail(h, PLDA_E_INVAL, "sym_eig: the block Jacobi solver (method 1) stops at D = 1024; D = %d needs method 0 or 2", D);
     PLDA_TRY(set_device(h));
     const size_t DD = (size_t)D * D;
-    Tmp dG, dS, dV;
+    Staged st(h);
+    Tmp dG;
+    double *dS, *dV;
     PLDA_HIP(h, dG.alloc(DD * 8));
-    PLDA_HIP(h, dS.alloc((size_t)D * 8));
-    PLDA_HIP(h, dV.alloc(DD * 8));
+    PLDA_TRY(st.out(eigenvalues, (size_t)D, &dS));
+    PLDA_TRY(st.out(eigenvectors, DD, &dV));
     PLDA_HIP(h, hipMemcpyAsync(dG.p, G, DD * 8, hipMemcpyHostToDevice, h->stream));
     const bool keep = h->eig_keep_sign;
     const int variant = h->eig_variant;
     h->eig_keep_sign = true;                       // signed eigenvalues: this entry point floors nothing
     int rc = PLDA_OK, status = 1;
     if (method == 2 || (method == 0 && variant != 1)) {
-      rc = sym_eig_dc_f64(h, dG.as<double>(), D, dS.as<double>(), dV.as<double>(), &status);
+      rc = sym_eig_dc_f64(h, dG.as<double>(), D, dS, dV, &status);
       if (rc == PLDA_OK && status != 0 && method == 2) {
         h->eig_keep_sign = keep;
         return fail(h, PLDA_E_NUMERIC, "sym_eig: the direct method does not handle this input (status %d)", status);
       }
     }
     if (rc == PLDA_OK && status != 0) {
-      rc = sym_eig_f64(h, dG.as<double>(), D, dS.as<double>(), dV.as<double>(), nullptr, nullptr);
+      rc = sym_eig_f64(h, dG.as<double>(), D, dS, dV, nullptr, nullptr);
       if (method_used) *method_used = 1;
     } else if (method_used) {
       *method_used = 2;
     }
     h->eig_keep_sign = keep;
     PLDA_TRY(rc);
-    PLDA_HIP(h, hipMemcpyAsync(eigenvalues, dS.p, (size_t)D * 8, hipMemcpyDeviceToHost, h->stream));
-    PLDA_HIP(h, hipMemcpyAsync(eigenvectors, dV.p, DD * 8, hipMemcpyDeviceToHost, h->stream));
-    PLDA_HIP(h, hipStreamSynchronize(h->stream));
-    return PLDA_OK;
+    return st.finish(PLDA_OK);
   });
 }
 
 int plda_score_last_shape(plda_handle *h, int64_t *M, int64_t *Nt, int32_t *gemm_k) {
-  return guarded(h, "plda_score_last_shape", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
+  return entry(h, "plda_score_last_shape", [&]() -> int {
     if (M) *M = h->last_M;
     if (Nt) *Nt = h->last_Nt;
     if (gemm_k) *gemm_k = h->last_k;
@@ -1172,9 +1102,8 @@ int plda_score_last_shape(plda_handle *h, int64_t *M, int64_t *Nt, int32_t *gemm
 }
 
 int plda_score_last_kernel(plda_handle *h, char *name, int64_t cap) {
-  return guarded(h, "plda_score_last_kernel", [&]() -> int {
-    if (!h || !name || cap <= 0) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
+  return entry(h, "plda_score_last_kernel", [&]() -> int {
+    if (!name || cap <= 0) return PLDA_E_INVAL;
     const char *k = h->last_kernel ? h->last_kernel : "";
     if ((int64_t)std::strlen(k) + 1 > cap) return fail(h, PLDA_E_CAPACITY, "score_last_kernel: need %zu bytes", std::strlen(k) + 1);
     std::memcpy(name, k, std::strlen(k) + 1);
@@ -1183,9 +1112,8 @@ int plda_score_last_kernel(plda_handle *h, char *name, int64_t cap) {
 }
 
 int plda_linalg_last_kernels(plda_handle *h, char *out, int64_t cap) {
-  return guarded(h, "plda_linalg_last_kernels", [&]() -> int {
-    if (!h || !out || cap <= 0) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
+  return entry(h, "plda_linalg_last_kernels", [&]() -> int {
+    if (!out || cap <= 0) return PLDA_E_INVAL;
     const size_t need = (size_t)h->linalg_kernels_len + 1;
     if ((int64_t)need > cap) return fail(h, PLDA_E_CAPACITY, "linalg_last_kernels: need %zu bytes", need);
     std::memcpy(out, h->linalg_kernels, need);
@@ -1196,9 +1124,7 @@ int plda_linalg_last_kernels(plda_handle *h, char *out, int64_t cap) {
 int plda_score_pairs(plda_handle *h, const double *U, const int32_t *n_enrol, int64_t M, const double *V,
                      int64_t Nt, const int64_t *e_idx, const int64_t *t_idx, int64_t P, const double *zmean,
                      const double *zstd, double *out) {
-  return guarded(h, "plda_score_pairs", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
+  return entry(h, "plda_score_pairs", [&]() -> int {
     if (!h->fitted) return fail(h, PLDA_E_NOT_FITTED, "score: model not fitted");
     if (P <= 0) return PLDA_OK;
     if (!U || !n_enrol || !V || !e_idx || !t_idx || !out || M <= 0 || Nt <= 0) return fail(h, PLDA_E_INVAL, "score_pairs: bad argument");
@@ -1242,27 +1168,28 @@ int plda_score_pairs(plda_handle *h, const double *U, const int32_t *n_enrol, in
       out[0] = hb[2 * D + 2];
       return PLDA_OK;
     }
-    Tmp dU, dN, dV, dE, dT, dZm, dZs, dO;
-    PLDA_TRY(upload(h, dU, U, (size_t)M * D * 8));
-    PLDA_TRY(upload(h, dN, n_enrol, (size_t)M * 4));
-    PLDA_TRY(upload(h, dV, V, (size_t)Nt * D * 8));
-    PLDA_TRY(upload(h, dE, e_idx, (size_t)P * 8));
-    PLDA_TRY(upload(h, dT, t_idx, (size_t)P * 8));
+    Staged st(h);
+    const double *dU, *dV, *dZm, *dZs;
+    const int32_t *dN;
+    const int64_t *dE, *dT;
+    double *dO;
+    PLDA_TRY(st.in(U, (size_t)M * D, &dU));
+    PLDA_TRY(st.in(n_enrol, (size_t)M, &dN));
+    PLDA_TRY(st.in(V, (size_t)Nt * D, &dV));
+    PLDA_TRY(st.in(e_idx, (size_t)P, &dE));
+    PLDA_TRY(st.in(t_idx, (size_t)P, &dT));
     const bool zn = zmean && zstd;
-    if (zn) { PLDA_TRY(upload(h, dZm, zmean, (size_t)M * 8)); PLDA_TRY(upload(h, dZs, zstd, (size_t)M * 8)); }
-    PLDA_HIP(h, dO.alloc((size_t)P * 8));
+    PLDA_TRY(st.in(zn ? zmean : nullptr, (size_t)M, &dZm));
+    PLDA_TRY(st.in(zn ? zstd : nullptr, (size_t)M, &dZs));
+    PLDA_TRY(st.out(out, (size_t)P, &dO, true));
     if (long_list) {
       long long bad = -1;
-      PLDA_TRY(plda::pairs_validate_device(h, dE.as<int64_t>(), dT.as<int64_t>(), P, M, Nt, &bad));
+      PLDA_TRY(plda::pairs_validate_device(h, dE, dT, P, M, Nt, &bad));
       if (bad >= 0) return fail(h, PLDA_E_INVAL, "score_pairs: trial %lld indexes outside the enrol/test sets", bad);
     }
     plda::CountSet cs;                                   // the distinct enrol counts: long lists run on per-count tables (score.hip)
     if (P >= 16384) plda::score_count_set_host(n_enrol, M, &cs);
-    PLDA_TRY(score_pairs_device(h, dU.as<double>(), dN.as<int32_t>(), dV.as<double>(), dE.as<int64_t>(),
-                                dT.as<int64_t>(), P, zn ? dZm.as<double>() : nullptr,
-                                zn ? dZs.as<double>() : nullptr, dO.as<double>(), M, &cs));
-    PLDA_TRY(download(h, out, dO.p, (size_t)P * 8));
-    return PLDA_OK;
+    return st.finish(score_pairs_device(h, dU, dN, dV, dE, dT, P, dZm, dZs, dO, M, &cs));
   });
 }
 
@@ -1277,9 +1204,7 @@ int plda_score_pairs(plda_handle *h, const double *U, const int32_t *n_enrol, in
 // on plda_score_pairs / plda_score_matrix.
 int plda_score_one(plda_handle *h, const double *u, int32_t n, const double *v, int32_t has_z, double zmean, double zstd,
                    double *out) {
-  return guarded(h, "plda_score_one", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
+  return entry(h, "plda_score_one", [&]() -> int {
     if (!h->fitted) return fail(h, PLDA_E_NOT_FITTED, "score: model not fitted");
     if (!u || !v || !out) return fail(h, PLDA_E_INVAL, "score_one: bad argument");
     if (n <= 0) return fail(h, PLDA_E_INVAL, "score_one: num_examples must be > 0");
@@ -1320,53 +1245,36 @@ int plda_score_one(plda_handle *h, const double *u, int32_t n, const double *v, 
 // ---------------------------------------------------------------- z-norm
 int plda_znorm_stats_dev(plda_handle *h, const double *dbkg, int64_t Nb, int32_t num_examples, int32_t Din,
                          const double *dmodels, int64_t M, double *dout_mean, double *dout_std) {
-  return guarded(h, "plda_znorm_stats_dev", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
-    PLDA_TRY(set_device(h));
-    return znorm_stats_device(h, dbkg, Nb, num_examples, Din, dmodels, M, dout_mean, dout_std);
-  });
+  return device_entry(h, "plda_znorm_stats_dev", [&] { return znorm_stats_device(h, dbkg, Nb, num_examples, Din, dmodels, M, dout_mean, dout_std); });
 }
 
 int plda_znorm_stats(plda_handle *h, const double *bkg, int64_t Nb, int32_t num_examples, int32_t Din,
                      const double *models, int64_t M, double *out_mean, double *out_std) {
-  return guarded(h, "plda_znorm_stats", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
+  return entry(h, "plda_znorm_stats", [&]() -> int {
     if (!h->fitted) return fail(h, PLDA_E_NOT_FITTED, "norm: model not fitted");
     if (!bkg || !models || !out_mean || !out_std || Nb <= 0 || M <= 0) return fail(h, PLDA_E_INVAL, "norm: bad argument");
     if (Din != h->Din) return fail(h, PLDA_E_INVAL, "norm: feature dim %d != model dim %d", Din, h->Din);
     PLDA_TRY(set_device(h));
-    Tmp dB, dM, dMean, dStd;
-    PLDA_TRY(upload(h, dB, bkg, (size_t)Nb * Din * 8));
-    PLDA_TRY(upload(h, dM, models, (size_t)M * h->Dout * 8));
-    PLDA_HIP(h, dMean.alloc((size_t)M * 8));
-    PLDA_HIP(h, dStd.alloc((size_t)M * 8));
-    PLDA_TRY(znorm_stats_device(h, dB.as<double>(), Nb, num_examples, Din, dM.as<double>(), M, dMean.as<double>(),
-                                dStd.as<double>()));
-    PLDA_HIP(h, hipMemcpyAsync(out_mean, dMean.p, (size_t)M * 8, hipMemcpyDeviceToHost, h->stream));
-    PLDA_HIP(h, hipMemcpyAsync(out_std, dStd.p, (size_t)M * 8, hipMemcpyDeviceToHost, h->stream));
-    PLDA_HIP(h, hipStreamSynchronize(h->stream));
-    return PLDA_OK;
+    Staged st(h);
+    const double *dB, *dM;
+    double *dMean, *dStd;
+    PLDA_TRY(st.in(bkg, (size_t)Nb * Din, &dB));
+    PLDA_TRY(st.in(models, (size_t)M * h->Dout, &dM));
+    PLDA_TRY(st.out(out_mean, (size_t)M, &dMean));
+    PLDA_TRY(st.out(out_std, (size_t)M, &dStd));
+    return st.finish(znorm_stats_device(h, dB, Nb, num_examples, Din, dM, M, dMean, dStd));
   });
 }
 
 // ---------------------------------------------------------------- AS-norm (snorm.hip)
 int plda_cohort_stats_dev(plda_handle *h, const double *dX, const int32_t *dn, int32_t n_uniform, int64_t R, const double *dC,
                           int64_t Nc, int64_t top_k, double *dmean, double *dstd) {
-  return guarded(h, "plda_cohort_stats_dev", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
-    PLDA_TRY(set_device(h));
-    return cohort_stats_device(h, dX, dn, n_uniform, R, dC, Nc, top_k, dmean, dstd);
-  });
+  return device_entry(h, "plda_cohort_stats_dev", [&] { return cohort_stats_device(h, dX, dn, n_uniform, R, dC, Nc, top_k, dmean, dstd); });
 }
 
 int plda_cohort_stats(plda_handle *h, const double *X, const int32_t *n, int32_t n_uniform, int64_t R, const double *Cv,
                       int64_t Nc, int64_t top_k, double *mean, double *std_) {
-  return guarded(h, "plda_cohort_stats", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
+  return entry(h, "plda_cohort_stats", [&]() -> int {
     if (!h->fitted) return fail(h, PLDA_E_NOT_FITTED, "cohort_stats: model not fitted");
     if (R < 1 || Nc < 1) return fail(h, PLDA_E_INVAL, "cohort_stats: R = %lld, Nc = %lld (both must be >= 1)", (long long)R, (long long)Nc);
     if (top_k < 1 || top_k > Nc) return fail(h, PLDA_E_INVAL, "cohort_stats: top_k = %lld (must be in 1 ... Nc = %lld)", (long long)top_k, (long long)Nc);
@@ -1374,31 +1282,25 @@ int plda_cohort_stats(plda_handle *h, const double *X, const int32_t *n, int32_t
     if (!n && n_uniform <= 0) return fail(h, PLDA_E_INVAL, "cohort_stats: n_uniform must be > 0 when n is NULL");
     PLDA_TRY(set_device(h));
     const int D = h->Dout;
-    Tmp dX, dN, dC, dMean, dStd;
+    Staged st(h);
+    const double *dX, *dC;
+    const int32_t *dN;
+    double *dMean, *dStd;
     CountSet cs;                                         // from the host array: no device pass, no wait
     if (n) score_count_set_host(n, R, &cs);
-    PLDA_TRY(upload(h, dC, Cv, (size_t)Nc * D * 8));
-    PLDA_TRY(upload(h, dX, X, (size_t)R * D * 8));
-    if (n) PLDA_TRY(upload(h, dN, n, (size_t)R * 4));
-    PLDA_HIP(h, dMean.alloc((size_t)R * 8));
-    PLDA_HIP(h, dStd.alloc((size_t)R * 8));
-    const int rc = cohort_stats_device(h, dX.as<double>(), n ? dN.as<int32_t>() : nullptr, n_uniform, R, dC.as<double>(), Nc, top_k,
-                                       dMean.as<double>(), dStd.as<double>(), n ? &cs : nullptr);
-    if (rc != PLDA_OK) { (void)hipStreamSynchronize(h->stream); return rc; }
-    PLDA_HIP(h, hipMemcpyAsync(mean, dMean.p, (size_t)R * 8, hipMemcpyDeviceToHost, h->stream));
-    PLDA_HIP(h, hipMemcpyAsync(std_, dStd.p, (size_t)R * 8, hipMemcpyDeviceToHost, h->stream));
-    PLDA_HIP(h, hipStreamSynchronize(h->stream));
-    return PLDA_OK;
+    PLDA_TRY(st.in(Cv, (size_t)Nc * D, &dC));
+    PLDA_TRY(st.in(X, (size_t)R * D, &dX));
+    PLDA_TRY(st.in(n, (size_t)R, &dN));
+    PLDA_TRY(st.out(mean, (size_t)R, &dMean));
+    PLDA_TRY(st.out(std_, (size_t)R, &dStd));
+    return st.finish(cohort_stats_device(h, dX, dN, n_uniform, R, dC, Nc, top_k, dMean, dStd, n ? &cs : nullptr));
   });
 }
 
 int plda_score_matrix_snorm_dev(plda_handle *h, const double *dU, const int32_t *dn_enrol, int32_t n_uniform, int64_t M,
                                 const double *dV, int64_t Nt, const double *demean, const double *destd, const double *dtmean,
                                 const double *dtstd, float *dout, int64_t ld_out) {
-  return guarded(h, "plda_score_matrix_snorm_dev", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
-    PLDA_TRY(set_device(h));
+  return device_entry(h, "plda_score_matrix_snorm_dev", [&] {
     return score_matrix_snorm_device(h, dU, dn_enrol, n_uniform, M, dV, Nt, demean, destd, dtmean, dtstd, dout, ld_out);
   });
 }
@@ -1407,9 +1309,7 @@ int plda_score_matrix_snorm_dev(plda_handle *h, const double *dU, const int32_t 
 int plda_score_matrix_snorm(plda_handle *h, const double *U, const int32_t *n_enrol, int32_t n_uniform, int64_t M, const double *V,
                             int64_t Nt, const double *emean, const double *estd, const double *tmean, const double *tstd,
                             float *out, int64_t ld_out) {
-  return guarded(h, "plda_score_matrix_snorm", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
+  return entry(h, "plda_score_matrix_snorm", [&]() -> int {
     if (!h->fitted) return fail(h, PLDA_E_NOT_FITTED, "score_matrix_snorm: model not fitted");
     if ((emean == nullptr) != (estd == nullptr)) return fail(h, PLDA_E_INVAL, "score_matrix_snorm: %s is NULL but its partner is not", emean ? "estd" : "emean");
     if ((tmean == nullptr) != (tstd == nullptr)) return fail(h, PLDA_E_INVAL, "score_matrix_snorm: %s is NULL but its partner is not", tmean ? "tstd" : "tmean");
@@ -1420,24 +1320,28 @@ int plda_score_matrix_snorm(plda_handle *h, const double *U, const int32_t *n_en
     if (!n_enrol && n_uniform <= 0) return fail(h, PLDA_E_INVAL, "score_matrix_snorm: n_uniform must be > 0 when n_enrol is NULL");
     PLDA_TRY(set_device(h));
     const int D = h->Dout;
-    Tmp dV, dU, dN, dEm, dEs, dTm, dTs, dO;
+    Staged st(h);
+    const double *dV, *dU, *dEm, *dEs, *dTm, *dTs;
+    const int32_t *dN;
+    Tmp dO;
     CountSet cs;                                         // the distinct counts of ALL rows: every slab sees the same set
     if (n_enrol) score_count_set_host(n_enrol, M, &cs);
-    PLDA_TRY(upload(h, dV, V, (size_t)Nt * D * 8));
-    PLDA_TRY(upload(h, dU, U, (size_t)M * D * 8));
-    if (n_enrol) PLDA_TRY(upload(h, dN, n_enrol, (size_t)M * 4));
-    if (emean) { PLDA_TRY(upload(h, dEm, emean, (size_t)M * 8)); PLDA_TRY(upload(h, dEs, estd, (size_t)M * 8)); }
-    if (tmean) { PLDA_TRY(upload(h, dTm, tmean, (size_t)Nt * 8)); PLDA_TRY(upload(h, dTs, tstd, (size_t)Nt * 8)); }
+    PLDA_TRY(st.in(V, (size_t)Nt * D, &dV));
+    PLDA_TRY(st.in(U, (size_t)M * D, &dU));
+    PLDA_TRY(st.in(n_enrol, (size_t)M, &dN));
+    PLDA_TRY(st.in(emean, (size_t)M, &dEm));
+    PLDA_TRY(st.in(estd, (size_t)M, &dEs));
+    PLDA_TRY(st.in(tmean, (size_t)Nt, &dTm));
+    PLDA_TRY(st.in(tstd, (size_t)Nt, &dTs));
     const int64_t ld = round_up(Nt, 4);
     int64_t slab = std::max<int64_t>(1, std::min<int64_t>(M, ((int64_t)1 << 30) / 4 / ld));
     PLDA_HIP(h, dO.alloc((size_t)slab * ld * 4));
     int rc = PLDA_OK;
     for (int64_t r0 = 0; r0 < M && rc == PLDA_OK; r0 += slab) {
       const int64_t m = std::min(slab, M - r0);
-      rc = score_matrix_snorm_device(h, dU.as<double>() + r0 * D, n_enrol ? dN.as<int32_t>() + r0 : nullptr, n_uniform, m, dV.as<double>(), Nt,
-                                     emean ? dEm.as<double>() + r0 : nullptr, emean ? dEs.as<double>() + r0 : nullptr,
-                                     tmean ? dTm.as<double>() : nullptr, tmean ? dTs.as<double>() : nullptr, dO.as<float>(), ld,
-                                     n_enrol ? &cs : nullptr, /*reuse_packed_B=*/r0 > 0);
+      rc = score_matrix_snorm_device(h, dU + r0 * D, dN ? dN + r0 : nullptr, n_uniform, m, dV, Nt, dEm ? dEm + r0 : nullptr,
+                                     dEs ? dEs + r0 : nullptr, dTm, dTs, dO.as<float>(), ld, n_enrol ? &cs : nullptr,
+                                     /*reuse_packed_B=*/r0 > 0);
       if (rc != PLDA_OK) break;
       const hipError_t e = hipMemcpy2DAsync(out + r0 * ld_out, (size_t)ld_out * 4, dO.p, (size_t)ld * 4, (size_t)Nt * 4, (size_t)m,
                                             hipMemcpyDeviceToHost, h->stream);
@@ -1453,22 +1357,14 @@ int plda_score_matrix_snorm(plda_handle *h, const double *U, const int32_t *n_en
 // ---------------------------------------------------------------- top-N retrieval (topn.hip)
 int plda_topn_matrix_dev(plda_handle *h, const float *dscores, int64_t ld, int64_t M, int64_t Nt, int32_t axis, int64_t top_n,
                          float *dout_scores, int64_t *dout_index) {
-  return guarded(h, "plda_topn_matrix_dev", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
-    PLDA_TRY(set_device(h));
-    return topn_matrix_device(h, dscores, ld, M, Nt, axis, top_n, dout_scores, dout_index);
-  });
+  return device_entry(h, "plda_topn_matrix_dev", [&] { return topn_matrix_device(h, dscores, ld, M, Nt, axis, top_n, dout_scores, dout_index); });
 }
 
 int plda_score_topn_dev(plda_handle *h, const double *dU, const int32_t *dn_enrol, int32_t n_uniform, int64_t M, const double *dV,
                         int64_t Nt, const double *dzmean, const double *dzstd, const double *demean, const double *destd,
                         const double *dtmean, const double *dtstd, int32_t axis, int64_t top_n, float *dout_scores,
                         int64_t *dout_index) {
-  return guarded(h, "plda_score_topn_dev", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
-    PLDA_TRY(set_device(h));
+  return device_entry(h, "plda_score_topn_dev", [&] {
     return score_topn_device(h, dU, dn_enrol, n_uniform, M, dV, Nt, dzmean, dzstd, demean, destd, dtmean, dtstd, axis, top_n,
                              dout_scores, dout_index);
   });
@@ -1478,9 +1374,7 @@ int plda_score_topn_dev(plda_handle *h, const double *dU, const int32_t *dn_enro
 int plda_score_topn(plda_handle *h, const double *U, const int32_t *n_enrol, int32_t n_uniform, int64_t M, const double *V,
                     int64_t Nt, const double *zmean, const double *zstd, const double *emean, const double *estd,
                     const double *tmean, const double *tstd, int32_t axis, int64_t top_n, float *out_scores, int64_t *out_index) {
-  return guarded(h, "plda_score_topn", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
+  return entry(h, "plda_score_topn", [&]() -> int {
     if (!h->fitted) return fail(h, PLDA_E_NOT_FITTED, "score_topn: model not fitted");
     if (M < 1 || Nt < 1) return fail(h, PLDA_E_INVAL, "score_topn: M = %lld, Nt = %lld (both must be >= 1)", (long long)M, (long long)Nt);
     if (axis != 0 && axis != 1) return fail(h, PLDA_E_INVAL, "score_topn: axis = %d (must be 0: per row, or 1: per column)", axis);
@@ -1493,46 +1387,38 @@ int plda_score_topn(plda_handle *h, const double *U, const int32_t *n_enrol, int
     PLDA_TRY(set_device(h));
     const int D = h->Dout;
     const int64_t L = axis == 0 ? M : Nt;
-    Tmp dV, dU, dN, dZm, dZs, dEm, dEs, dTm, dTs, dOs, dOi;
+    Staged st(h);
+    const double *dV, *dU, *dZm, *dZs, *dEm, *dEs, *dTm, *dTs;
+    const int32_t *dN;
+    float *dOs;
+    int64_t *dOi;
     CountSet cs;                                         // from the host array: no device pass, no wait
     if (n_enrol) score_count_set_host(n_enrol, M, &cs);
-    PLDA_TRY(upload(h, dV, V, (size_t)Nt * D * 8));
-    PLDA_TRY(upload(h, dU, U, (size_t)M * D * 8));
-    if (n_enrol) PLDA_TRY(upload(h, dN, n_enrol, (size_t)M * 4));
-    if (zmean) { PLDA_TRY(upload(h, dZm, zmean, (size_t)M * 8)); PLDA_TRY(upload(h, dZs, zstd, (size_t)M * 8)); }
-    if (emean) { PLDA_TRY(upload(h, dEm, emean, (size_t)M * 8)); PLDA_TRY(upload(h, dEs, estd, (size_t)M * 8)); }
-    if (tmean) { PLDA_TRY(upload(h, dTm, tmean, (size_t)Nt * 8)); PLDA_TRY(upload(h, dTs, tstd, (size_t)Nt * 8)); }
-    PLDA_HIP(h, dOs.alloc((size_t)L * top_n * 4));
-    PLDA_HIP(h, dOi.alloc((size_t)L * top_n * 8));
-    const int rc = score_topn_device(h, dU.as<double>(), n_enrol ? dN.as<int32_t>() : nullptr, n_uniform, M, dV.as<double>(), Nt,
-                                     zmean ? dZm.as<double>() : nullptr, zmean ? dZs.as<double>() : nullptr,
-                                     emean ? dEm.as<double>() : nullptr, emean ? dEs.as<double>() : nullptr,
-                                     tmean ? dTm.as<double>() : nullptr, tmean ? dTs.as<double>() : nullptr, axis, top_n,
-                                     dOs.as<float>(), dOi.as<int64_t>(), n_enrol ? &cs : nullptr);
-    if (rc != PLDA_OK) { (void)hipStreamSynchronize(h->stream); return rc; }
-    PLDA_HIP(h, hipMemcpyAsync(out_scores, dOs.p, (size_t)L * top_n * 4, hipMemcpyDeviceToHost, h->stream));
-    PLDA_HIP(h, hipMemcpyAsync(out_index, dOi.p, (size_t)L * top_n * 8, hipMemcpyDeviceToHost, h->stream));
-    PLDA_HIP(h, hipStreamSynchronize(h->stream));
-    return PLDA_OK;
+    PLDA_TRY(st.in(V, (size_t)Nt * D, &dV));
+    PLDA_TRY(st.in(U, (size_t)M * D, &dU));
+    PLDA_TRY(st.in(n_enrol, (size_t)M, &dN));
+    PLDA_TRY(st.in(zmean, (size_t)M, &dZm));
+    PLDA_TRY(st.in(zstd, (size_t)M, &dZs));
+    PLDA_TRY(st.in(emean, (size_t)M, &dEm));
+    PLDA_TRY(st.in(estd, (size_t)M, &dEs));
+    PLDA_TRY(st.in(tmean, (size_t)Nt, &dTm));
+    PLDA_TRY(st.in(tstd, (size_t)Nt, &dTs));
+    PLDA_TRY(st.out(out_scores, (size_t)L * top_n, &dOs));
+    PLDA_TRY(st.out(out_index, (size_t)L * top_n, &dOi));
+    return st.finish(score_topn_device(h, dU, dN, n_uniform, M, dV, Nt, dZm, dZs, dEm, dEs, dTm, dTs, axis, top_n, dOs, dOi,
+                                       n_enrol ? &cs : nullptr));
   });
 }
 
 // ---------------------------------------------------------------- d-vector front-end
 int plda_dvector_pool_dev(plda_handle *h, const void *dframes, int32_t dtype, int64_t T, int32_t D,
                           const int64_t *doffsets, int64_t U, int32_t method, int32_t l2norm, double *dout) {
-  return guarded(h, "plda_dvector_pool_dev", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
-    PLDA_TRY(set_device(h));
-    return dvector_pool_device(h, dframes, dtype, T, D, doffsets, U, method, l2norm, dout);
-  });
+  return device_entry(h, "plda_dvector_pool_dev", [&] { return dvector_pool_device(h, dframes, dtype, T, D, doffsets, U, method, l2norm, dout); });
 }
 
 int plda_dvector_pool(plda_handle *h, const void *frames, int32_t dtype, int64_t T, int32_t D, const int64_t *offsets,
                       int64_t U, int32_t method, int32_t l2norm, double *out) {
-  return guarded(h, "plda_dvector_pool", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
+  return entry(h, "plda_dvector_pool", [&]() -> int {
     if (U <= 0) return PLDA_OK;
     if (!frames || !offsets || !out || T < 0 || D <= 0 || (dtype != 0 && dtype != 1))
       return fail(h, PLDA_E_INVAL, "dvector_pool: bad argument");
@@ -1540,49 +1426,42 @@ int plda_dvector_pool(plda_handle *h, const void *frames, int32_t dtype, int64_t
       if (offsets[u] < 0 || offsets[u + 1] < offsets[u] || offsets[u + 1] > T)
         return fail(h, PLDA_E_INVAL, "dvector_pool: offsets must be non-decreasing within [0, T]");
     PLDA_TRY(set_device(h));
-    Tmp dF, dO, dOut;
-    PLDA_TRY(upload(h, dF, frames, (size_t)T * D * (dtype == 0 ? 4 : 8)));
-    PLDA_TRY(upload(h, dO, offsets, (size_t)(U + 1) * 8));
-    PLDA_HIP(h, dOut.alloc((size_t)U * D * 8));
-    PLDA_TRY(dvector_pool_device(h, dF.p, dtype, T, D, dO.as<int64_t>(), U, method, l2norm, dOut.as<double>()));
-    PLDA_HIP(h, hipMemcpyAsync(out, dOut.p, (size_t)U * D * 8, hipMemcpyDeviceToHost, h->stream));
-    PLDA_HIP(h, hipStreamSynchronize(h->stream));
-    return PLDA_OK;
+    Staged st(h);
+    const void *dF;
+    const int64_t *dO;
+    double *dOut;
+    PLDA_TRY(st.in(frames, (size_t)T * D * (dtype == 0 ? 4 : 8), &dF));
+    PLDA_TRY(st.in(offsets, (size_t)(U + 1), &dO));
+    PLDA_TRY(st.out(out, (size_t)U * D, &dOut));
+    return st.finish(dvector_pool_device(h, dF, dtype, T, D, dO, U, method, l2norm, dOut));
   });
 }
 
 // ---------------------------------------------------------------- LDA (python/liblda/lda.py)
 int plda_lda_fit_dev(plda_handle *h, const double *dX, int64_t N, int32_t D, const uint64_t *dlabels, int64_t K,
                      int32_t solver, const double *priors) {
-  return guarded(h, "plda_lda_fit_dev", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
-    PLDA_TRY(set_device(h));
-    return lda_fit_device(h, dX, N, D, dlabels, K, solver, priors);
-  });
+  return device_entry(h, "plda_lda_fit_dev", [&] { return lda_fit_device(h, dX, N, D, dlabels, K, solver, priors); });
 }
 
 int plda_lda_fit(plda_handle *h, const double *X, int64_t N, int32_t D, const uint64_t *labels, int32_t solver,
                  const double *priors) {
-  return guarded(h, "plda_lda_fit", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
+  return entry(h, "plda_lda_fit", [&]() -> int {
     if (!X || !labels || N <= 0 || D <= 0) return fail(h, PLDA_E_INVAL, "lda_fit: bad argument");
     uint64_t mx = 0;
     for (int64_t r = 0; r < N; ++r) mx = std::max(mx, labels[r]);
     if (mx >= (uint64_t)N) return fail(h, PLDA_E_LABELS, "lda_fit: labels must be dense 0..K-1");
     PLDA_TRY(set_device(h));
-    Tmp dX, dL;
-    PLDA_TRY(upload(h, dX, X, (size_t)N * D * 8));
-    PLDA_TRY(upload(h, dL, labels, (size_t)N * 8));
-    return lda_fit_device(h, dX.as<double>(), N, D, dL.as<uint64_t>(), (int64_t)mx + 1, solver, priors);
+    Staged st(h);
+    const double *dX;
+    const uint64_t *dL;
+    PLDA_TRY(st.in(X, (size_t)N * D, &dX));
+    PLDA_TRY(st.in(labels, (size_t)N, &dL));
+    return lda_fit_device(h, dX, N, D, dL, (int64_t)mx + 1, solver, priors);
   });
 }
 
 int plda_lda_dims(plda_handle *h, int64_t *K, int32_t *D, int32_t *rank, int32_t *solver) {
-  return guarded(h, "plda_lda_dims", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
+  return entry(h, "plda_lda_dims", [&]() -> int {
     if (!h->lda_fitted) return fail(h, PLDA_E_NOT_FITTED, "This LDA instance is not fitted yet");
     if (K) *K = h->lda_K;
     if (D) *D = h->lda_D;
@@ -1594,9 +1473,7 @@ int plda_lda_dims(plda_handle *h, int64_t *K, int32_t *D, int32_t *rank, int32_t
 
 int plda_lda_get_model(plda_handle *h, double *priors, double *means, double *xbar, double *scalings, double *coef,
                        double *intercept, double *evr) {
-  return guarded(h, "plda_lda_get_model", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
+  return entry(h, "plda_lda_get_model", [&]() -> int {
     if (!h->lda_fitted) return fail(h, PLDA_E_NOT_FITTED, "This LDA instance is not fitted yet");
     PLDA_TRY(set_device(h));
     const size_t K = (size_t)h->lda_K, D = (size_t)h->lda_D, R = (size_t)h->lda_rank;
@@ -1618,9 +1495,7 @@ int plda_lda_get_model(plda_handle *h, double *priors, double *means, double *xb
 int plda_lda_set_model(plda_handle *h, int32_t solver, int64_t K, int32_t D, int32_t rank, const double *priors,
                        const double *means, const double *xbar, const double *scalings, const double *coef,
                        const double *intercept) {
-  return guarded(h, "plda_lda_set_model", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
+  return entry(h, "plda_lda_set_model", [&]() -> int {
     if (solver < 0 || solver > 2 || K <= 0 || D <= 0 || rank < 0 || rank > D || !coef || !intercept)
       return fail(h, PLDA_E_INVAL, "lda_set_model: bad argument");
     if (solver != 2 && (!scalings || rank == 0)) return fail(h, PLDA_E_INVAL, "lda_set_model: scalings required");
@@ -1646,18 +1521,11 @@ int plda_lda_set_model(plda_handle *h, int32_t solver, int64_t K, int32_t D, int
 }
 
 int plda_lda_predict_dev(plda_handle *h, const double *dX, int64_t N, int32_t mode, double *dout) {
-  return guarded(h, "plda_lda_predict_dev", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
-    PLDA_TRY(set_device(h));
-    return lda_predict_device(h, dX, N, mode, dout);
-  });
+  return device_entry(h, "plda_lda_predict_dev", [&] { return lda_predict_device(h, dX, N, mode, dout); });
 }
 
 int plda_lda_predict(plda_handle *h, const double *X, int64_t N, int32_t D, int32_t mode, double *out) {
-  return guarded(h, "plda_lda_predict", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
+  return entry(h, "plda_lda_predict", [&]() -> int {
     if (!h->lda_fitted) return fail(h, PLDA_E_NOT_FITTED, "This LDA instance is not fitted yet");
     if (D != h->lda_D)
       return fail(h, PLDA_E_INVAL, "X has %d features per sample; expecting %d", D, h->lda_D);   // lda.py:264-266
@@ -1681,47 +1549,34 @@ int plda_lda_predict(plda_handle *h, const double *X, int64_t N, int32_t D, int3
 }
 
 int plda_lda_transform_dev(plda_handle *h, const double *dX, int64_t N, int32_t ncomp, double *dout) {
-  return guarded(h, "plda_lda_transform_dev", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
-    PLDA_TRY(set_device(h));
-    return lda_transform_device(h, dX, N, ncomp, dout);
-  });
+  return device_entry(h, "plda_lda_transform_dev", [&] { return lda_transform_device(h, dX, N, ncomp, dout); });
 }
 
 int plda_lda_transform(plda_handle *h, const double *X, int64_t N, int32_t D, int32_t ncomp, double *out) {
-  return guarded(h, "plda_lda_transform", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
+  return entry(h, "plda_lda_transform", [&]() -> int {
     if (!h->lda_fitted) return fail(h, PLDA_E_NOT_FITTED, "This LDA instance is not fitted yet");
     if (D != h->lda_D) return fail(h, PLDA_E_INVAL, "X has %d features per sample; expecting %d", D, h->lda_D);
     if (N <= 0 || ncomp <= 0) return PLDA_OK;
     if (!X || !out) return fail(h, PLDA_E_INVAL, "lda_transform: bad argument");
     PLDA_TRY(set_device(h));
-    Tmp dX, dO;
-    PLDA_TRY(upload(h, dX, X, (size_t)N * D * 8));
-    PLDA_HIP(h, dO.alloc((size_t)N * ncomp * 8));
-    PLDA_TRY(lda_transform_device(h, dX.as<double>(), N, ncomp, dO.as<double>()));
-    return download(h, out, dO.p, (size_t)N * ncomp * 8);
+    Staged st(h);
+    const double *dX;
+    double *dO;
+    PLDA_TRY(st.in(X, (size_t)N * D, &dX));
+    PLDA_TRY(st.out(out, (size_t)N * ncomp, &dO, true));
+    return st.finish(lda_transform_device(h, dX, N, ncomp, dO));
   });
 }
 
 // ---------------------------------------------------------------- HTK feature files
 int plda_htk_frames_dev(plda_handle *h, const void *dblob, const int64_t *dfile_off, const int64_t *dframe_off,
                         int64_t U, int64_t T, int32_t samplesize, int32_t frm_ext, float *dout) {
-  return guarded(h, "plda_htk_frames_dev", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
-    PLDA_TRY(set_device(h));
-    return htk_frames_device(h, dblob, dfile_off, dframe_off, U, T, samplesize, frm_ext, dout);
-  });
+  return device_entry(h, "plda_htk_frames_dev", [&] { return htk_frames_device(h, dblob, dfile_off, dframe_off, U, T, samplesize, frm_ext, dout); });
 }
 
 int plda_htk_frames(plda_handle *h, const void *blob, int64_t blob_bytes, const int64_t *file_off,
                     const int64_t *frame_off, int64_t U, int32_t samplesize, int32_t frm_ext, float *out) {
-  return guarded(h, "plda_htk_frames", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
+  return entry(h, "plda_htk_frames", [&]() -> int {
     if (U <= 0) return PLDA_OK;
     if (!blob || !file_off || !frame_off || !out || blob_bytes < 0 || samplesize <= 0 || frm_ext < 0)
       return fail(h, PLDA_E_INVAL, "htk_frames: bad argument");
@@ -1736,67 +1591,41 @@ int plda_htk_frames(plda_handle *h, const void *blob, int64_t blob_bytes, const 
     if (frame_off[0] != 0) return fail(h, PLDA_E_INVAL, "htk_frames: frame_off[0] must be 0");
     if (T <= 0) return PLDA_OK;
     PLDA_TRY(set_device(h));
-    Tmp dB, dF, dO, dOut;
-    PLDA_TRY(upload(h, dB, blob, (size_t)blob_bytes));
-    PLDA_TRY(upload(h, dF, file_off, (size_t)U * 8));
-    PLDA_TRY(upload(h, dO, frame_off, (size_t)(U + 1) * 8));
-    const size_t obytes = (size_t)T * (2 * frm_ext + 1) * samplesize;
-    PLDA_HIP(h, dOut.alloc(obytes));
-    PLDA_TRY(htk_frames_device(h, dB.p, dF.as<int64_t>(), dO.as<int64_t>(), U, T, samplesize, frm_ext, dOut.as<float>()));
-    return download(h, out, dOut.p, obytes);
+    Staged st(h);
+    const void *dB;
+    const int64_t *dF, *dO;
+    float *dOut;
+    PLDA_TRY(st.in(blob, (size_t)blob_bytes, &dB));
+    PLDA_TRY(st.in(file_off, (size_t)U, &dF));
+    PLDA_TRY(st.in(frame_off, (size_t)(U + 1), &dO));
+    PLDA_TRY(st.out(out, (size_t)T * (2 * frm_ext + 1) * W, &dOut, true));     // (W floats per sample: samplesize bytes)
+    return st.finish(htk_frames_device(h, dB, dF, dO, U, T, samplesize, frm_ext, dOut));
   });
 }
 
 // ---------------------------------------------------------------- multi-GPU (comm.hip)
 int plda_comm_init(plda_handle *h, int32_t nranks, int32_t rank, const void *unique_id) {
-  return guarded(h, "plda_comm_init", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
-    PLDA_TRY(set_device(h));
-    return comm_init(h, nranks, rank, unique_id);
-  });
+  return device_entry(h, "plda_comm_init", [&] { return comm_init(h, nranks, rank, unique_id); });
 }
 
 int plda_comm_init_custom(plda_handle *h, int32_t nranks, int32_t rank, const plda_collectives *table) {
-  return guarded(h, "plda_comm_init_custom", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
-    PLDA_TRY(set_device(h));
-    return comm_init_custom(h, nranks, rank, table);
-  });
+  return device_entry(h, "plda_comm_init_custom", [&] { return comm_init_custom(h, nranks, rank, table); });
 }
 
 int plda_comm_init_peer(plda_handle *h, int32_t nranks, int32_t rank, const plda_host_collectives *bootstrap) {
-  return guarded(h, "plda_comm_init_peer", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
-    PLDA_TRY(set_device(h));
-    return comm_init_peer(h, nranks, rank, bootstrap);
-  });
+  return device_entry(h, "plda_comm_init_peer", [&] { return comm_init_peer(h, nranks, rank, bootstrap); });
 }
 
 int plda_comm_init_host(plda_handle *h, int32_t nranks, int32_t rank, const plda_host_collectives *table) {
-  return guarded(h, "plda_comm_init_host", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
-    PLDA_TRY(set_device(h));
-    return comm_init_host(h, nranks, rank, table);
-  });
+  return device_entry(h, "plda_comm_init_host", [&] { return comm_init_host(h, nranks, rank, table); });
 }
 
 int plda_comm_destroy(plda_handle *h) {
-  return guarded(h, "plda_comm_destroy", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
-    PLDA_TRY(set_device(h));
-    return comm_destroy(h);
-  });
+  return device_entry(h, "plda_comm_destroy", [&] { return comm_destroy(h); });
 }
 
 int plda_comm_describe(plda_handle *h, char *json, int64_t cap) {
-  return guarded(h, "plda_comm_describe", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
+  return entry(h, "plda_comm_describe", [&]() -> int {
     if (!json || cap <= 0) return fail(h, PLDA_E_INVAL, "comm_describe: bad argument");
     PLDA_TRY(set_device(h));
     std::string js;
@@ -1808,9 +1637,7 @@ int plda_comm_describe(plda_handle *h, char *json, int64_t cap) {
 }
 
 int plda_comm_emulate(plda_handle *h, int32_t nranks, int32_t rank) {
-  return guarded(h, "plda_comm_emulate", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
+  return entry(h, "plda_comm_emulate", [&]() -> int {
     if (h->comm) return fail(h, PLDA_E_INVAL, "comm_emulate: this handle has a real communicator");
     if (nranks <= 0 || rank < 0 || rank >= nranks) return fail(h, PLDA_E_INVAL, "comm_emulate: bad argument");
     h->comm_nranks = nranks; h->comm_rank = rank;
@@ -1819,9 +1646,7 @@ int plda_comm_emulate(plda_handle *h, int32_t nranks, int32_t rank) {
 }
 
 int plda_comm_info(plda_handle *h, int32_t *nranks, int32_t *rank) {
-  return guarded(h, "plda_comm_info", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
+  return entry(h, "plda_comm_info", [&]() -> int {
     if (nranks) *nranks = h->comm_nranks;
     if (rank) *rank = h->comm_rank;
     return PLDA_OK;
@@ -1831,9 +1656,7 @@ int plda_comm_info(plda_handle *h, int32_t *nranks, int32_t *rank) {
 int plda_score_matrix_sharded_dev(plda_handle *h, const double *dU, const int32_t *dn_enrol, int32_t n_uniform, int64_t M,
                                   const double *dV, int64_t Nt, const double *dzmean, const double *dzstd, float *dout,
                                   int64_t ld_out, int64_t block_rows, int32_t gather) {
-  return guarded(h, "plda_score_matrix_sharded_dev", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
+  return entry(h, "plda_score_matrix_sharded_dev", [&]() -> int {
     if (!dn_enrol && n_uniform <= 0) return fail(h, PLDA_E_INVAL, "score_matrix_sharded: n_uniform must be > 0 when n_enrol is NULL");
     PLDA_TRY(set_device(h));
     return score_matrix_sharded_device(h, dU, dn_enrol, n_uniform, M, dV, Nt, dzmean, dzstd, nullptr, 0, dout, ld_out,
@@ -1844,9 +1667,7 @@ int plda_score_matrix_sharded_dev(plda_handle *h, const double *dU, const int32_
 int plda_score_matrix_sharded_local_dev(plda_handle *h, const double *dU, const int32_t *dn_enrol, int32_t n_uniform,
                                         int64_t M, const double *dV, int64_t Nt, const double *dzmean, const double *dzstd,
                                         float *dlocal, int64_t ld_local, int64_t block_rows, float *dfull, int64_t ld_full) {
-  return guarded(h, "plda_score_matrix_sharded_local_dev", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
+  return entry(h, "plda_score_matrix_sharded_local_dev", [&]() -> int {
     if (!dn_enrol && n_uniform <= 0) return fail(h, PLDA_E_INVAL, "score_matrix_sharded: n_uniform must be > 0 when n_enrol is NULL");
     if (!dlocal) return fail(h, PLDA_E_INVAL, "score_matrix_sharded_local: dlocal is NULL");
     PLDA_TRY(set_device(h));
@@ -1857,9 +1678,7 @@ int plda_score_matrix_sharded_local_dev(plda_handle *h, const double *dU, const 
 
 int plda_znorm_stats_sharded_dev(plda_handle *h, const double *dbkg, int64_t Nb, int32_t num_examples, int32_t Din,
                                  const double *dmodels, int64_t M, double *dout_mean, double *dout_std) {
-  return guarded(h, "plda_znorm_stats_sharded_dev", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
+  return entry(h, "plda_znorm_stats_sharded_dev", [&]() -> int {
     if (!h->fitted) return fail(h, PLDA_E_NOT_FITTED, "norm: model not fitted");
     if (!dbkg || !dmodels || !dout_mean || !dout_std || Nb <= 0 || M <= 0) return fail(h, PLDA_E_INVAL, "norm: bad argument");
     PLDA_TRY(set_device(h));
@@ -1869,9 +1688,7 @@ int plda_znorm_stats_sharded_dev(plda_handle *h, const double *dbkg, int64_t Nb,
 
 int plda_cohort_stats_sharded_dev(plda_handle *h, const double *dX, const int32_t *dn, int32_t n_uniform, int64_t R, const double *dC,
                                   int64_t Nc, int64_t top_k, double *dmean, double *dstd) {
-  return guarded(h, "plda_cohort_stats_sharded_dev", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
+  return entry(h, "plda_cohort_stats_sharded_dev", [&]() -> int {
     if (!h->fitted) return fail(h, PLDA_E_NOT_FITTED, "cohort_stats: model not fitted");
     if (!dX || !dC || !dmean || !dstd || R < 1 || Nc < 1 || top_k < 1 || top_k > Nc) return fail(h, PLDA_E_INVAL, "cohort_stats_sharded: bad argument");
     PLDA_TRY(set_device(h));
@@ -1881,42 +1698,24 @@ int plda_cohort_stats_sharded_dev(plda_handle *h, const double *dX, const int32_
 
 int plda_fit_sharded_dev(plda_handle *h, const double *dX, int64_t N, int32_t D, const uint64_t *dlabels, int64_t K,
                          int32_t iters) {
-  return guarded(h, "plda_fit_sharded_dev", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
-    PLDA_TRY(set_device(h));
-    return fit_sharded_device(h, dX, N, D, dlabels, K, iters);
-  });
+  return device_entry(h, "plda_fit_sharded_dev", [&] { return fit_sharded_device(h, dX, N, D, dlabels, K, iters); });
 }
 
 int plda_eer_matrix_comm_dev(plda_handle *h, const float *dscores, int64_t ld, int64_t M, int64_t Nt,
                              const int64_t *denrol_spk, const int64_t *dtest_spk, double *out) {
-  return guarded(h, "plda_eer_matrix_comm_dev", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
-    PLDA_TRY(set_device(h));
-    return eer_matrix_comm_device(h, dscores, ld, M, Nt, denrol_spk, dtest_spk, out);
-  });
+  return device_entry(h, "plda_eer_matrix_comm_dev", [&] { return eer_matrix_comm_device(h, dscores, ld, M, Nt, denrol_spk, dtest_spk, out); });
 }
 
 // ---------------------------------------------------------------- EER
 int plda_eer_matrix_dev(plda_handle *h, const float *dscores, int64_t ld, int64_t M, int64_t Nt,
                         const int64_t *denrol_spk, const int64_t *dtest_spk, double *out) {
-  return guarded(h, "plda_eer_matrix_dev", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
-    PLDA_TRY(set_device(h));
-    return eer_matrix_device(h, dscores, ld, M, Nt, denrol_spk, dtest_spk, out);
-  });
+  return device_entry(h, "plda_eer_matrix_dev", [&] { return eer_matrix_device(h, dscores, ld, M, Nt, denrol_spk, dtest_spk, out); });
 }
 
 int plda_score_eer_dev(plda_handle *h, const double *dU, const int32_t *dn_enrol, int32_t n_uniform, int64_t M, const double *dV,
                        int64_t Nt, const double *dzmean, const double *dzstd, const int64_t *denrol_spk, const int64_t *dtest_spk,
                        double *out) {
-  return guarded(h, "plda_score_eer_dev", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
-    PLDA_TRY(set_device(h));
+  return device_entry(h, "plda_score_eer_dev", [&] {
     return score_eer_device(h, dU, dn_enrol, n_uniform, M, dV, Nt, dzmean, dzstd, denrol_spk, dtest_spk, out);
   });
 }
@@ -1924,9 +1723,7 @@ int plda_score_eer_dev(plda_handle *h, const double *dU, const int32_t *dn_enrol
 int plda_eer_matrix_sharded_dev(plda_handle *h, const float *dscores, int64_t ld, int64_t M, int64_t Nt,
                                 const int64_t *denrol_spk, const int64_t *dtest_spk, plda_eer_reduce_fn reduce, void *ctx,
                                 double *out) {
-  return guarded(h, "plda_eer_matrix_sharded_dev", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
+  return entry(h, "plda_eer_matrix_sharded_dev", [&]() -> int {
     if (!reduce) return fail(h, PLDA_E_INVAL, "eer_matrix_sharded: a reduction callback is required");
     PLDA_TRY(set_device(h));
     return eer_matrix_device(h, dscores, ld, M, Nt, denrol_spk, dtest_spk, out, reduce, ctx);
@@ -1935,10 +1732,7 @@ int plda_eer_matrix_sharded_dev(plda_handle *h, const float *dscores, int64_t ld
 
 int plda_det_matrix_dev(plda_handle *h, const float *dscores, int64_t ld, int64_t M, int64_t Nt, const int64_t *denrol_spk,
                         const int64_t *dtest_spk, int32_t n_points, double *far, double *frr, double *thresholds) {
-  return guarded(h, "plda_det_matrix_dev", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
-    PLDA_TRY(set_device(h));
+  return device_entry(h, "plda_det_matrix_dev", [&] {
     return det_matrix_device(h, dscores, ld, M, Nt, denrol_spk, dtest_spk, n_points, far, frr, thresholds);
   });
 }
@@ -1962,9 +1756,7 @@ int plda_eer_lists(plda_handle *h, const float *pos, int64_t np, const float *ne
 int plda_min_dcf_matrix_dev(plda_handle *h, const float *dscores, int64_t ld, int64_t M, int64_t Nt, const int64_t *denrol_spk,
                             const int64_t *dtest_spk, int32_t n_points, const plda_dcf_point *points, plda_min_dcf *out,
                             plda_min_dcf_info *info) {
-  return guarded(h, "plda_min_dcf_matrix_dev", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
+  return entry(h, "plda_min_dcf_matrix_dev", [&]() -> int {
     if (M <= 0) return fail(h, PLDA_E_INVAL, "min_dcf: bad argument");
     PLDA_TRY(set_device(h));
     return min_dcf_matrix_device(h, dscores, ld, M, Nt, denrol_spk, dtest_spk, n_points, points, out, info, nullptr, nullptr);
@@ -1974,10 +1766,7 @@ int plda_min_dcf_matrix_dev(plda_handle *h, const float *dscores, int64_t ld, in
 int plda_min_dcf_matrix_comm_dev(plda_handle *h, const float *dscores, int64_t ld, int64_t M, int64_t Nt, const int64_t *denrol_spk,
                                  const int64_t *dtest_spk, int32_t n_points, const plda_dcf_point *points, plda_min_dcf *out,
                                  plda_min_dcf_info *info) {
-  return guarded(h, "plda_min_dcf_matrix_comm_dev", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
-    PLDA_TRY(set_device(h));
+  return device_entry(h, "plda_min_dcf_matrix_comm_dev", [&] {
     return min_dcf_matrix_comm_device(h, dscores, ld, M, Nt, denrol_spk, dtest_spk, n_points, points, out, info);
   });
 }
@@ -1991,10 +1780,7 @@ int plda_min_dcf_lists(plda_handle *h, const float *pos, int64_t np, const float
 int plda_score_min_dcf_dev(plda_handle *h, const double *dU, const int32_t *dn_enrol, int32_t n_uniform, int64_t M, const double *dV,
                            int64_t Nt, const double *dzmean, const double *dzstd, const int64_t *denrol_spk, const int64_t *dtest_spk,
                            int32_t n_points, const plda_dcf_point *points, plda_min_dcf *out, plda_min_dcf_info *info) {
-  return guarded(h, "plda_score_min_dcf_dev", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
-    PLDA_TRY(set_device(h));
+  return device_entry(h, "plda_score_min_dcf_dev", [&] {
     return score_min_dcf_device(h, dU, dn_enrol, n_uniform, M, dV, Nt, dzmean, dzstd, denrol_spk, dtest_spk, n_points, points, out, info);
   });
 }
@@ -2013,20 +1799,14 @@ int plda_min_dcf_finish(const plda_min_dcf_state *state, int32_t n_points, const
 // ---------------------------------------------------------------- score calibration (calib.hip)
 int plda_calib_pass_matrix_dev(plda_handle *h, const float *dscores, int64_t ld, int64_t M, int64_t Nt, const int64_t *denrol_spk,
                                const int64_t *dtest_spk, double a, double c, double theta, plda_calib_record *out_record) {
-  return guarded(h, "plda_calib_pass_matrix_dev", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
-    PLDA_TRY(set_device(h));
+  return device_entry(h, "plda_calib_pass_matrix_dev", [&] {
     return calib_pass_matrix_device(h, dscores, ld, M, Nt, denrol_spk, dtest_spk, a, c, theta, out_record);
   });
 }
 
 int plda_calib_fit_matrix_dev(plda_handle *h, const float *dscores, int64_t ld, int64_t M, int64_t Nt, const int64_t *denrol_spk,
                               const int64_t *dtest_spk, double prior, double tol, int32_t max_iter, plda_calib_fit *out_fit) {
-  return guarded(h, "plda_calib_fit_matrix_dev", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
-    PLDA_TRY(set_device(h));
+  return device_entry(h, "plda_calib_fit_matrix_dev", [&] {
     return calib_fit_matrix_device(h, dscores, ld, M, Nt, denrol_spk, dtest_spk, prior, tol, max_iter, out_fit);
   });
 }
@@ -2046,10 +1826,7 @@ int plda_calib_fit_lists(plda_handle *h, const float *pos, int64_t np, const flo
 int plda_score_calib_pass_dev(plda_handle *h, const double *dU, const int32_t *dn_enrol, int32_t n_uniform, int64_t M,
                               const double *dV, int64_t Nt, const double *dzmean, const double *dzstd, const int64_t *denrol_spk,
                               const int64_t *dtest_spk, double a, double c, double theta, plda_calib_record *out_record) {
-  return guarded(h, "plda_score_calib_pass_dev", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
-    PLDA_TRY(set_device(h));
+  return device_entry(h, "plda_score_calib_pass_dev", [&] {
     return score_calib_pass_device(h, dU, dn_enrol, n_uniform, M, dV, Nt, dzmean, dzstd, denrol_spk, dtest_spk, a, c, theta, out_record);
   });
 }
@@ -2057,32 +1834,21 @@ int plda_score_calib_pass_dev(plda_handle *h, const double *dU, const int32_t *d
 int plda_score_calib_fit_dev(plda_handle *h, const double *dU, const int32_t *dn_enrol, int32_t n_uniform, int64_t M,
                              const double *dV, int64_t Nt, const double *dzmean, const double *dzstd, const int64_t *denrol_spk,
                              const int64_t *dtest_spk, double prior, double tol, int32_t max_iter, plda_calib_fit *out_fit) {
-  return guarded(h, "plda_score_calib_fit_dev", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
-    PLDA_TRY(set_device(h));
+  return device_entry(h, "plda_score_calib_fit_dev", [&] {
     return score_calib_fit_device(h, dU, dn_enrol, n_uniform, M, dV, Nt, dzmean, dzstd, denrol_spk, dtest_spk, prior, tol, max_iter, out_fit);
   });
 }
 
 int plda_affine_map_dev(plda_handle *h, const float *dscores, int64_t ld, int64_t M, int64_t Nt, double a, double b, float *dout,
                         int64_t ld_out) {
-  return guarded(h, "plda_affine_map_dev", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
-    PLDA_TRY(set_device(h));
-    return affine_map_device(h, dscores, ld, M, Nt, a, b, dout, ld_out);
-  });
+  return device_entry(h, "plda_affine_map_dev", [&] { return affine_map_device(h, dscores, ld, M, Nt, a, b, dout, ld_out); });
 }
 
 // ---------------------------------------------------------------- multi-system score fusion (fusion.hip)
 int plda_fusion_pass_matrices_dev(plda_handle *h, int32_t n_systems, const float *const *dscores, const int64_t *ld, int64_t M,
                                   int64_t Nt, const int64_t *denrol_spk, const int64_t *dtest_spk, const double *a, double c,
                                   double theta, plda_fusion_record *out_record) {
-  return guarded(h, "plda_fusion_pass_matrices_dev", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
-    PLDA_TRY(set_device(h));
+  return device_entry(h, "plda_fusion_pass_matrices_dev", [&] {
     return fusion_pass_matrices_device(h, n_systems, dscores, ld, M, Nt, denrol_spk, dtest_spk, a, c, theta, out_record);
   });
 }
@@ -2090,10 +1856,7 @@ int plda_fusion_pass_matrices_dev(plda_handle *h, int32_t n_systems, const float
 int plda_fusion_fit_matrices_dev(plda_handle *h, int32_t n_systems, const float *const *dscores, const int64_t *ld, int64_t M,
                                  int64_t Nt, const int64_t *denrol_spk, const int64_t *dtest_spk, double prior, double tol,
                                  int32_t max_iter, plda_fusion_fit *out_fit) {
-  return guarded(h, "plda_fusion_fit_matrices_dev", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
-    PLDA_TRY(set_device(h));
+  return device_entry(h, "plda_fusion_fit_matrices_dev", [&] {
     return fusion_fit_matrices_device(h, n_systems, dscores, ld, M, Nt, denrol_spk, dtest_spk, prior, tol, max_iter, out_fit);
   });
 }
@@ -2116,12 +1879,7 @@ int plda_fusion_fit_lists(plda_handle *h, int32_t n_systems, const float *const 
 
 int plda_fusion_map_dev(plda_handle *h, int32_t n_systems, const float *const *dscores, const int64_t *ld, int64_t M, int64_t Nt,
                         const double *a, double b, float *dout, int64_t ld_out) {
-  return guarded(h, "plda_fusion_map_dev", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
-    PLDA_TRY(set_device(h));
-    return fusion_map_device(h, n_systems, dscores, ld, M, Nt, a, b, dout, ld_out);
-  });
+  return device_entry(h, "plda_fusion_map_dev", [&] { return fusion_map_device(h, n_systems, dscores, ld, M, Nt, a, b, dout, ld_out); });
 }
 
 // the Newton step: a pure function, no handle (include/plda_hip.h)
@@ -2131,85 +1889,47 @@ int plda_fusion_newton(const plda_fusion_record *record, double prior, double *F
 
 // ---------------------------------------------------------------- speaker clustering (ahc.hip)
 int plda_ahc_plan(plda_handle *h, int64_t N, int32_t out[3]) {
-  return guarded(h, "plda_ahc_plan", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
-    return ahc_plan(h, N, out);
-  });
+  return entry(h, "plda_ahc_plan", [&] { return ahc_plan(h, N, out); });
 }
 
 int plda_ahc_matrix_dev(plda_handle *h, const float *dscores, const int64_t *block_off, const int64_t *offsets, int64_t R,
                         int32_t has_threshold, double threshold, const int32_t *min_clusters, int32_t *dlabels,
                         int32_t *dn_clusters, int32_t *dmerge_a, int32_t *dmerge_b, double *dmerge_cost) {
-  return guarded(h, "plda_ahc_matrix_dev", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
-    PLDA_TRY(set_device(h));
+  return device_entry(h, "plda_ahc_matrix_dev", [&] {
     return ahc_matrix_device(h, dscores, block_off, offsets, R, has_threshold, threshold, min_clusters, dlabels, dn_clusters, dmerge_a,
                              dmerge_b, dmerge_cost);
   });
 }
 
-extern "C++" {
-namespace {
-// the host forms: outputs staged in device temporaries, copied back after the call's own synchronisation
-template <typename F>
-int ahc_host_outputs(plda_handle *h, int64_t T, int64_t R, int32_t *labels, int32_t *n_clusters, int32_t *merge_a, int32_t *merge_b,
-                     double *merge_cost, F &&run) {
-  Tmp dL, dK, dA, dB, dC;
-  PLDA_HIP(h, dL.alloc((size_t)T * 4));
-  PLDA_HIP(h, dK.alloc((size_t)R * 4));
-  if (merge_a) {
-    PLDA_HIP(h, dA.alloc((size_t)(T - R) * 4));
-    PLDA_HIP(h, dB.alloc((size_t)(T - R) * 4));
-    PLDA_HIP(h, dC.alloc((size_t)(T - R) * 8));
-  }
-  const int rc = run(dL.as<int32_t>(), dK.as<int32_t>(), merge_a ? dA.as<int32_t>() : nullptr, merge_a ? dB.as<int32_t>() : nullptr,
-                     merge_a ? dC.as<double>() : nullptr);
-  if (rc != PLDA_OK) { (void)hipStreamSynchronize(h->stream); return rc; }
-  PLDA_HIP(h, hipMemcpyAsync(labels, dL.p, (size_t)T * 4, hipMemcpyDeviceToHost, h->stream));
-  PLDA_HIP(h, hipMemcpyAsync(n_clusters, dK.p, (size_t)R * 4, hipMemcpyDeviceToHost, h->stream));
-  if (merge_a && T > R) {
-    PLDA_HIP(h, hipMemcpyAsync(merge_a, dA.p, (size_t)(T - R) * 4, hipMemcpyDeviceToHost, h->stream));
-    PLDA_HIP(h, hipMemcpyAsync(merge_b, dB.p, (size_t)(T - R) * 4, hipMemcpyDeviceToHost, h->stream));
-    PLDA_HIP(h, hipMemcpyAsync(merge_cost, dC.p, (size_t)(T - R) * 8, hipMemcpyDeviceToHost, h->stream));
-  }
-  PLDA_HIP(h, hipStreamSynchronize(h->stream));
-  return PLDA_OK;
-}
-}  // namespace
-}  // extern "C++"
-
 int plda_ahc_matrix(plda_handle *h, const float *scores, const int64_t *block_off, const int64_t *offsets, int64_t R,
                     int32_t has_threshold, double threshold, const int32_t *min_clusters, int32_t *labels, int32_t *n_clusters,
                     int32_t *merge_a, int32_t *merge_b, double *merge_cost) {
-  return guarded(h, "plda_ahc_matrix", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
+  return entry(h, "plda_ahc_matrix", [&]() -> int {
     if (!scores) return fail(h, PLDA_E_INVAL, "ahc_matrix: scores is NULL");
     PLDA_TRY(ahc_validate(h, "ahc_matrix", block_off, true, offsets, R, has_threshold, threshold, min_clusters, labels, n_clusters,
                           merge_a, merge_b, merge_cost));
     PLDA_TRY(set_device(h));
     const int64_t T = offsets[R], first = block_off[0], floats = block_off[R] - first;
-    Tmp dS;
-    PLDA_TRY(upload(h, dS, scores + first, (size_t)floats * 4));
+    Staged st(h);
+    const float *dS;
+    int32_t *dL, *dK, *dA, *dB;
+    double *dC;
+    PLDA_TRY(st.in(scores + first, (size_t)floats, &dS));
     std::vector<int64_t> rel((size_t)R + 1);
     for (int64_t r = 0; r <= R; ++r) rel[(size_t)r] = block_off[r] - first;
-    return ahc_host_outputs(h, T, R, labels, n_clusters, merge_a, merge_b, merge_cost,
-                            [&](int32_t *dl, int32_t *dk, int32_t *da, int32_t *db, double *dc) {
-                              return ahc_matrix_device(h, dS.as<float>(), rel.data(), offsets, R, has_threshold, threshold, min_clusters,
-                                                       dl, dk, da, db, dc);
-                            });
+    PLDA_TRY(st.out(labels, (size_t)T, &dL));
+    PLDA_TRY(st.out(n_clusters, (size_t)R, &dK));
+    PLDA_TRY(st.out(merge_a, (size_t)(T - R), &dA));
+    PLDA_TRY(st.out(merge_b, (size_t)(T - R), &dB));
+    PLDA_TRY(st.out(merge_cost, (size_t)(T - R), &dC));
+    return st.finish(ahc_matrix_device(h, dS, rel.data(), offsets, R, has_threshold, threshold, min_clusters, dL, dK, dA, dB, dC));
   });
 }
 
 int plda_score_ahc_dev(plda_handle *h, const double *dX, const int64_t *offsets, int64_t R, int32_t has_threshold,
                        double threshold, const int32_t *min_clusters, int32_t *dlabels, int32_t *dn_clusters,
                        int32_t *dmerge_a, int32_t *dmerge_b, double *dmerge_cost) {
-  return guarded(h, "plda_score_ahc_dev", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
-    PLDA_TRY(set_device(h));
+  return device_entry(h, "plda_score_ahc_dev", [&] {
     return score_ahc_device(h, dX, offsets, R, has_threshold, threshold, min_clusters, dlabels, dn_clusters, dmerge_a, dmerge_b,
                             dmerge_cost);
   });
@@ -2218,56 +1938,51 @@ int plda_score_ahc_dev(plda_handle *h, const double *dX, const int64_t *offsets,
 int plda_score_ahc(plda_handle *h, const double *X, const int64_t *offsets, int64_t R, int32_t has_threshold, double threshold,
                    const int32_t *min_clusters, int32_t *labels, int32_t *n_clusters, int32_t *merge_a, int32_t *merge_b,
                    double *merge_cost) {
-  return guarded(h, "plda_score_ahc", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
+  return entry(h, "plda_score_ahc", [&]() -> int {
     if (!h->fitted) return fail(h, PLDA_E_NOT_FITTED, "score_ahc: model not fitted");
     if (!X) return fail(h, PLDA_E_INVAL, "score_ahc: X is NULL");
     PLDA_TRY(ahc_validate(h, "score_ahc", nullptr, false, offsets, R, has_threshold, threshold, min_clusters, labels, n_clusters,
                           merge_a, merge_b, merge_cost));
     PLDA_TRY(set_device(h));
     const int64_t T = offsets[R];
-    Tmp dX;
-    PLDA_TRY(upload(h, dX, X, (size_t)T * h->Dout * 8));
-    return ahc_host_outputs(h, T, R, labels, n_clusters, merge_a, merge_b, merge_cost,
-                            [&](int32_t *dl, int32_t *dk, int32_t *da, int32_t *db, double *dc) {
-                              return score_ahc_device(h, dX.as<double>(), offsets, R, has_threshold, threshold, min_clusters, dl, dk,
-                                                      da, db, dc);
-                            });
+    Staged st(h);
+    const double *dX;
+    int32_t *dL, *dK, *dA, *dB;
+    double *dC;
+    PLDA_TRY(st.in(X, (size_t)T * h->Dout, &dX));
+    PLDA_TRY(st.out(labels, (size_t)T, &dL));
+    PLDA_TRY(st.out(n_clusters, (size_t)R, &dK));
+    PLDA_TRY(st.out(merge_a, (size_t)(T - R), &dA));
+    PLDA_TRY(st.out(merge_b, (size_t)(T - R), &dB));
+    PLDA_TRY(st.out(merge_cost, (size_t)(T - R), &dC));
+    return st.finish(score_ahc_device(h, dX, offsets, R, has_threshold, threshold, min_clusters, dL, dK, dA, dB, dC));
   });
 }
 
 // ---------------------------------------------------------------- dense scoring in a recording's PCA subspace (dense_pca.hip)
 int plda_dense_pca_plan(plda_handle *h, int64_t N, int32_t D, int32_t out[4]) {
-  return guarded(h, "plda_dense_pca_plan", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
-    return dense_pca_plan(h, N, D, out);
-  });
+  return entry(h, "plda_dense_pca_plan", [&] { return dense_pca_plan(h, N, D, out); });
 }
 
 int plda_score_dense_pca_dev(plda_handle *h, const double *dX, const int64_t *offsets, int64_t R, double target_energy,
                              float *dscores, const int64_t *block_off, int32_t *ddims, double *deig) {
-  return guarded(h, "plda_score_dense_pca_dev", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
-    PLDA_TRY(set_device(h));
+  return device_entry(h, "plda_score_dense_pca_dev", [&] {
     return score_dense_pca_device(h, dX, offsets, R, target_energy, dscores, block_off, ddims, deig);
   });
 }
 
 int plda_score_dense_pca(plda_handle *h, const double *X, const int64_t *offsets, int64_t R, double target_energy, float *scores,
                          const int64_t *block_off, int32_t *dims, double *eig) {
-  return guarded(h, "plda_score_dense_pca", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
+  return entry(h, "plda_score_dense_pca", [&]() -> int {
     PLDA_TRY(dense_pca_validate(h, "score_dense_pca", offsets, R, target_energy, block_off, true));
     if (!X) return fail(h, PLDA_E_INVAL, "score_dense_pca: X is NULL");
     if (!scores) return fail(h, PLDA_E_INVAL, "score_dense_pca: scores is NULL");
     PLDA_TRY(set_device(h));
     const int64_t T = offsets[R], first = block_off[0], floats = block_off[R] - first;
-    Tmp dX, dS, dD, dE;
-    PLDA_TRY(upload(h, dX, X, (size_t)T * h->Din * 8));
+    Staged st(h);
+    const double *dX;
+    Tmp dS, dD, dE;
+    PLDA_TRY(st.in(X, (size_t)T * h->Din, &dX));
     PLDA_HIP(h, dS.alloc((size_t)floats * 4));
     if (dims) PLDA_HIP(h, dD.alloc((size_t)R * 4));
     if (eig) PLDA_HIP(h, dE.alloc((size_t)T * 8));
@@ -2278,7 +1993,7 @@ int plda_score_dense_pca(plda_handle *h, const double *X, const int64_t *offsets
       const int64_t n = offsets[r + 1] - offsets[r];
       packed = packed && rel[(size_t)r + 1] - rel[(size_t)r] == n * n;
     }
-    const int rc = score_dense_pca_device(h, dX.as<double>(), offsets, R, target_energy, dS.as<float>(), rel.data(),
+    const int rc = score_dense_pca_device(h, dX, offsets, R, target_energy, dS.as<float>(), rel.data(),
                                           dims ? dD.as<int32_t>() : nullptr, eig ? dE.as<double>() : nullptr);
     if (rc != PLDA_OK) { (void)hipStreamSynchronize(h->stream); return rc; }
     if (packed) {
@@ -2300,10 +2015,7 @@ int plda_score_dense_pca(plda_handle *h, const double *X, const int64_t *offsets
 int plda_score_dense_pca_ahc_dev(plda_handle *h, const double *dX, const int64_t *offsets, int64_t R, double target_energy,
                                  int32_t has_threshold, double threshold, const int32_t *min_clusters, int32_t *dlabels,
                                  int32_t *dn_clusters, int32_t *dmerge_a, int32_t *dmerge_b, double *dmerge_cost) {
-  return guarded(h, "plda_score_dense_pca_ahc_dev", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
-    PLDA_TRY(set_device(h));
+  return device_entry(h, "plda_score_dense_pca_ahc_dev", [&] {
     return score_dense_pca_ahc_device(h, dX, offsets, R, target_energy, has_threshold, threshold, min_clusters, dlabels, dn_clusters,
                                       dmerge_a, dmerge_b, dmerge_cost);
   });
@@ -2312,78 +2024,64 @@ int plda_score_dense_pca_ahc_dev(plda_handle *h, const double *dX, const int64_t
 int plda_score_dense_pca_ahc(plda_handle *h, const double *X, const int64_t *offsets, int64_t R, double target_energy,
                              int32_t has_threshold, double threshold, const int32_t *min_clusters, int32_t *labels,
                              int32_t *n_clusters, int32_t *merge_a, int32_t *merge_b, double *merge_cost) {
-  return guarded(h, "plda_score_dense_pca_ahc", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
+  return entry(h, "plda_score_dense_pca_ahc", [&]() -> int {
     PLDA_TRY(dense_pca_validate(h, "score_dense_pca_ahc", offsets, R, target_energy, nullptr, false));
     if (!X) return fail(h, PLDA_E_INVAL, "score_dense_pca_ahc: X is NULL");
     PLDA_TRY(ahc_validate(h, "score_dense_pca_ahc", nullptr, false, offsets, R, has_threshold, threshold, min_clusters, labels,
                           n_clusters, merge_a, merge_b, merge_cost));
     PLDA_TRY(set_device(h));
     const int64_t T = offsets[R];
-    Tmp dX;
-    PLDA_TRY(upload(h, dX, X, (size_t)T * h->Din * 8));
-    return ahc_host_outputs(h, T, R, labels, n_clusters, merge_a, merge_b, merge_cost,
-                            [&](int32_t *dl, int32_t *dk, int32_t *da, int32_t *db, double *dc) {
-                              return score_dense_pca_ahc_device(h, dX.as<double>(), offsets, R, target_energy, has_threshold, threshold,
-                                                                min_clusters, dl, dk, da, db, dc);
-                            });
+    Staged st(h);
+    const double *dX;
+    int32_t *dL, *dK, *dA, *dB;
+    double *dC;
+    PLDA_TRY(st.in(X, (size_t)T * h->Din, &dX));
+    PLDA_TRY(st.out(labels, (size_t)T, &dL));
+    PLDA_TRY(st.out(n_clusters, (size_t)R, &dK));
+    PLDA_TRY(st.out(merge_a, (size_t)(T - R), &dA));
+    PLDA_TRY(st.out(merge_b, (size_t)(T - R), &dB));
+    PLDA_TRY(st.out(merge_cost, (size_t)(T - R), &dC));
+    return st.finish(score_dense_pca_ahc_device(h, dX, offsets, R, target_energy, has_threshold, threshold, min_clusters, dL, dK, dA, dB,
+                                                dC));
   });
 }
 
 // ---------------------------------------------------------------- diarisation error rate (der.hip)
 int plda_der_plan(plda_handle *h, int64_t Sr, int64_t Sh, int32_t out[3]) {
-  return guarded(h, "plda_der_plan", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
-    return der_plan(h, Sr, Sh, out);
-  });
+  return entry(h, "plda_der_plan", [&] { return der_plan(h, Sr, Sh, out); });
 }
 
 int plda_der_dev(plda_handle *h, const int32_t *dref, const int32_t *dhyp, const int32_t *ddur, const int64_t *offsets, int64_t R,
                  int64_t *dcounts, int32_t *dmap) {
-  return guarded(h, "plda_der_dev", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
-    PLDA_TRY(set_device(h));
-    return der_device(h, dref, dhyp, ddur, offsets, R, dcounts, dmap);
-  });
+  return device_entry(h, "plda_der_dev", [&] { return der_device(h, dref, dhyp, ddur, offsets, R, dcounts, dmap); });
 }
 
 int plda_der(plda_handle *h, const int32_t *ref, const int32_t *hyp, const int32_t *dur, const int64_t *offsets, int64_t R,
              int64_t *counts, int32_t *map) {
-  return guarded(h, "plda_der", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
+  return entry(h, "plda_der", [&]() -> int {
     if (!ref) return fail(h, PLDA_E_INVAL, "der: ref is NULL");
     if (!hyp) return fail(h, PLDA_E_INVAL, "der: hyp is NULL");
     if (!counts) return fail(h, PLDA_E_INVAL, "der: counts is NULL");
     PLDA_TRY(der_validate(h, "der", offsets, R));
     PLDA_TRY(set_device(h));
     const int64_t T = offsets[R];
-    Tmp dRef, dHyp, dDur, dC, dM;
-    PLDA_TRY(upload(h, dRef, ref, (size_t)T * 4));
-    PLDA_TRY(upload(h, dHyp, hyp, (size_t)T * 4));
-    if (dur) PLDA_TRY(upload(h, dDur, dur, (size_t)T * 4));
-    PLDA_HIP(h, dC.alloc((size_t)R * 32));
-    if (map) PLDA_HIP(h, dM.alloc((size_t)R * PLDA_DER_MAX_REF * 4));
-    const int rc = der_device(h, dRef.as<int32_t>(), dHyp.as<int32_t>(), dur ? dDur.as<int32_t>() : nullptr, offsets, R, dC.as<int64_t>(),
-                              map ? dM.as<int32_t>() : nullptr);
-    if (rc != PLDA_OK) { (void)hipStreamSynchronize(h->stream); return rc; }
-    PLDA_HIP(h, hipMemcpyAsync(counts, dC.p, (size_t)R * 32, hipMemcpyDeviceToHost, h->stream));
-    if (map) PLDA_HIP(h, hipMemcpyAsync(map, dM.p, (size_t)R * PLDA_DER_MAX_REF * 4, hipMemcpyDeviceToHost, h->stream));
-    PLDA_HIP(h, hipStreamSynchronize(h->stream));
-    return PLDA_OK;
+    Staged st(h);
+    const int32_t *dRef, *dHyp, *dDur;
+    int64_t *dC;
+    int32_t *dM;
+    PLDA_TRY(st.in(ref, (size_t)T, &dRef));
+    PLDA_TRY(st.in(hyp, (size_t)T, &dHyp));
+    PLDA_TRY(st.in(dur, (size_t)T, &dDur));
+    PLDA_TRY(st.out(counts, (size_t)R * 4, &dC));
+    PLDA_TRY(st.out(map, (size_t)R * PLDA_DER_MAX_REF, &dM));
+    return st.finish(der_device(h, dRef, dHyp, dDur, offsets, R, dC, dM));
   });
 }
 
 int plda_der_sweep_dev(plda_handle *h, const int32_t *dmerge_a, const int32_t *dmerge_b, const double *dmerge_cost,
                        const int64_t *offsets, int64_t R, const int32_t *dref, const int32_t *ddur, const double *thresholds, int64_t Q,
                        const int32_t *min_clusters, int64_t *dcounts, int32_t *dn_clusters) {
-  return guarded(h, "plda_der_sweep_dev", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
-    PLDA_TRY(set_device(h));
+  return device_entry(h, "plda_der_sweep_dev", [&] {
     return der_sweep_device(h, dmerge_a, dmerge_b, dmerge_cost, offsets, R, dref, ddur, thresholds, Q, min_clusters, dcounts,
                             dn_clusters);
   });
@@ -2392,9 +2090,7 @@ int plda_der_sweep_dev(plda_handle *h, const int32_t *dmerge_a, const int32_t *d
 int plda_der_sweep(plda_handle *h, const int32_t *merge_a, const int32_t *merge_b, const double *merge_cost, const int64_t *offsets,
                    int64_t R, const int32_t *ref, const int32_t *dur, const double *thresholds, int64_t Q, const int32_t *min_clusters,
                    int64_t *counts, int32_t *n_clusters) {
-  return guarded(h, "plda_der_sweep", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
+  return entry(h, "plda_der_sweep", [&]() -> int {
     if (!ref) return fail(h, PLDA_E_INVAL, "der_sweep: ref is NULL");
     if (!counts) return fail(h, PLDA_E_INVAL, "der_sweep: counts is NULL");
     if (!n_clusters) return fail(h, PLDA_E_INVAL, "der_sweep: n_clusters is NULL");
@@ -2402,41 +2098,32 @@ int plda_der_sweep(plda_handle *h, const int32_t *merge_a, const int32_t *merge_
     const int64_t T = offsets[R];
     if (T > R && !(merge_a && merge_b && merge_cost)) return fail(h, PLDA_E_INVAL, "der_sweep: merge_a, merge_b or merge_cost is NULL");
     PLDA_TRY(set_device(h));
-    Tmp dA, dB, dCo, dRef, dDur, dC, dK;
-    PLDA_TRY(upload(h, dA, merge_a, (size_t)(T - R) * 4));
-    PLDA_TRY(upload(h, dB, merge_b, (size_t)(T - R) * 4));
-    PLDA_TRY(upload(h, dCo, merge_cost, (size_t)(T - R) * 8));
-    PLDA_TRY(upload(h, dRef, ref, (size_t)T * 4));
-    if (dur) PLDA_TRY(upload(h, dDur, dur, (size_t)T * 4));
-    PLDA_HIP(h, dC.alloc((size_t)Q * R * 32));
-    PLDA_HIP(h, dK.alloc((size_t)Q * R * 4));
-    const int rc = der_sweep_device(h, dA.as<int32_t>(), dB.as<int32_t>(), dCo.as<double>(), offsets, R, dRef.as<int32_t>(),
-                                    dur ? dDur.as<int32_t>() : nullptr, thresholds, Q, min_clusters, dC.as<int64_t>(), dK.as<int32_t>());
-    if (rc != PLDA_OK) { (void)hipStreamSynchronize(h->stream); return rc; }
-    PLDA_HIP(h, hipMemcpyAsync(counts, dC.p, (size_t)Q * R * 32, hipMemcpyDeviceToHost, h->stream));
-    PLDA_HIP(h, hipMemcpyAsync(n_clusters, dK.p, (size_t)Q * R * 4, hipMemcpyDeviceToHost, h->stream));
-    PLDA_HIP(h, hipStreamSynchronize(h->stream));
-    return PLDA_OK;
+    Staged st(h);
+    const int32_t *dA, *dB, *dRef, *dDur;
+    const double *dCo;
+    int64_t *dC;
+    int32_t *dK;
+    PLDA_TRY(st.in(merge_a, (size_t)(T - R), &dA));       // (all three may be NULL when no recording has a merge: T == R)
+    PLDA_TRY(st.in(merge_b, (size_t)(T - R), &dB));
+    PLDA_TRY(st.in(merge_cost, (size_t)(T - R), &dCo));
+    PLDA_TRY(st.in(ref, (size_t)T, &dRef));
+    PLDA_TRY(st.in(dur, (size_t)T, &dDur));
+    PLDA_TRY(st.out(counts, (size_t)Q * R * 4, &dC));
+    PLDA_TRY(st.out(n_clusters, (size_t)Q * R, &dK));
+    return st.finish(der_sweep_device(h, dA, dB, dCo, offsets, R, dRef, dDur, thresholds, Q, min_clusters, dC, dK));
   });
 }
 
 // ---------------------------------------------------------------- VBx resegmentation (vbx.hip)
 int plda_vbx_plan(plda_handle *h, int64_t T, int64_t S, int64_t D, int32_t out[3]) {
-  return guarded(h, "plda_vbx_plan", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
-    return vbx_plan(h, T, S, D, out);
-  });
+  return entry(h, "plda_vbx_plan", [&] { return vbx_plan(h, T, S, D, out); });
 }
 
 int plda_vbx_dev(plda_handle *h, const double *dY, int64_t D, const double *dPhi, const int32_t *dlabels_in, const int64_t *offsets,
                  int64_t R, double Fa, double Fb, double loop_prob, double init_smoothing, int64_t max_iters, double epsilon,
                  int32_t *dlabels, int32_t *dn_clusters, double *dgamma, const int64_t *gamma_off, double *dpi, const int64_t *pi_off,
                  double *delbo, int32_t *diters) {
-  return guarded(h, "plda_vbx_dev", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
-    PLDA_TRY(set_device(h));
+  return device_entry(h, "plda_vbx_dev", [&] {
     return vbx_device(h, dY, D, dPhi, dlabels_in, offsets, R, Fa, Fb, loop_prob, init_smoothing, max_iters, epsilon, dlabels,
                       dn_clusters, dgamma, gamma_off, dpi, pi_off, delbo, diters);
   });
@@ -2446,9 +2133,7 @@ int plda_vbx(plda_handle *h, const double *Y, int64_t D, const double *Phi, cons
              double Fa, double Fb, double loop_prob, double init_smoothing, int64_t max_iters, double epsilon, int32_t *labels,
              int32_t *n_clusters, double *gamma, const int64_t *gamma_off, double *pi, const int64_t *pi_off, double *elbo,
              int32_t *iters) {
-  return guarded(h, "plda_vbx", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
+  return entry(h, "plda_vbx", [&]() -> int {
     if (!h->fitted) return fail(h, PLDA_E_NOT_FITTED, "vbx: model not fitted");
     if (!Y) return fail(h, PLDA_E_INVAL, "vbx: Y is NULL");
     if (!labels_in) return fail(h, PLDA_E_INVAL, "vbx: labels_in is NULL");
@@ -2462,17 +2147,20 @@ int plda_vbx(plda_handle *h, const double *Y, int64_t D, const double *Phi, cons
     std::vector<int64_t> grel, prel;
     if (gamma) { grel.resize((size_t)R + 1); for (int64_t r = 0; r <= R; ++r) grel[(size_t)r] = gamma_off[r] - g0; }
     if (pi) { prel.resize((size_t)R + 1); for (int64_t r = 0; r <= R; ++r) prel[(size_t)r] = pi_off[r] - p0; }
-    Tmp dY, dPhi, dLin, dL, dK, dG, dP, dE, dI;
-    PLDA_TRY(upload(h, dY, Y, (size_t)T * D * 8));
-    if (Phi) PLDA_TRY(upload(h, dPhi, Phi, (size_t)D * 8));
-    PLDA_TRY(upload(h, dLin, labels_in, (size_t)T * 4));
+    Staged st(h);
+    const double *dY, *dPhi;
+    const int32_t *dLin;
+    Tmp dL, dK, dG, dP, dE, dI;
+    PLDA_TRY(st.in(Y, (size_t)T * D, &dY));
+    PLDA_TRY(st.in(Phi, (size_t)D, &dPhi));
+    PLDA_TRY(st.in(labels_in, (size_t)T, &dLin));
     PLDA_HIP(h, dL.alloc((size_t)T * 4));
     PLDA_HIP(h, dK.alloc((size_t)R * 4));
     if (gamma) PLDA_HIP(h, dG.alloc((size_t)gn * 8));
     if (pi) PLDA_HIP(h, dP.alloc((size_t)pn * 8));
     if (elbo) PLDA_HIP(h, dE.alloc((size_t)R * max_iters * 8));
     if (iters) PLDA_HIP(h, dI.alloc((size_t)R * 4));
-    const int rc = vbx_device(h, dY.as<double>(), D, Phi ? dPhi.as<double>() : nullptr, dLin.as<int32_t>(), offsets, R, Fa, Fb, loop_prob,
+    const int rc = vbx_device(h, dY, D, dPhi, dLin, offsets, R, Fa, Fb, loop_prob,
                               init_smoothing, max_iters, epsilon, dL.as<int32_t>(), dK.as<int32_t>(), gamma ? dG.as<double>() : nullptr,
                               gamma ? grel.data() : nullptr, pi ? dP.as<double>() : nullptr, pi ? prel.data() : nullptr,
                               elbo ? dE.as<double>() : nullptr, iters ? dI.as<int32_t>() : nullptr);
@@ -2499,54 +2187,37 @@ int plda_vbx(plda_handle *h, const double *Y, int64_t D, const double *Phi, cons
 }
 
 int plda_project_rows_dev(plda_handle *h, const double *dX, int64_t R, int32_t Din, double *dout) {
-  return guarded(h, "plda_project_rows_dev", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
-    PLDA_TRY(set_device(h));
-    return project_rows_device(h, dX, R, Din, dout);
-  });
+  return device_entry(h, "plda_project_rows_dev", [&] { return project_rows_device(h, dX, R, Din, dout); });
 }
 
 int plda_project_rows(plda_handle *h, const double *X, int64_t R, int32_t Din, double *out) {
-  return guarded(h, "plda_project_rows", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
+  return entry(h, "plda_project_rows", [&]() -> int {
     if (!h->fitted) return fail(h, PLDA_E_NOT_FITTED, "project_rows: model not fitted");
     if (Din != h->Din) return fail(h, PLDA_E_INVAL, "project_rows: feature dim %d != model dim %d", (int)Din, h->Din);
     if (R <= 0) return R < 0 ? fail(h, PLDA_E_INVAL, "project_rows: R = %lld", (long long)R) : PLDA_OK;
     if (!X || !out) return fail(h, PLDA_E_INVAL, "project_rows: bad argument");
     PLDA_TRY(set_device(h));
-    Tmp dX, dO;
-    PLDA_TRY(upload(h, dX, X, (size_t)R * Din * 8));
-    PLDA_HIP(h, dO.alloc((size_t)R * h->Dout * 8));
-    PLDA_TRY(project_rows_device(h, dX.as<double>(), R, Din, dO.as<double>()));
-    return download(h, out, dO.p, (size_t)R * h->Dout * 8);
+    Staged st(h);
+    const double *dX;
+    double *dO;
+    PLDA_TRY(st.in(X, (size_t)R * Din, &dX));
+    PLDA_TRY(st.out(out, (size_t)R * h->Dout, &dO, true));
+    return st.finish(project_rows_device(h, dX, R, Din, dO));
   });
 }
 
 // ---------------------------------------------------------------- embedding chain (embed.hip)
 int plda_embed_set(plda_handle *h, int32_t Din, int32_t Dout, const double *m_in, double len_in, const double *A, const double *m_out,
                    double len_out) {
-  return guarded(h, "plda_embed_set", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
-    PLDA_TRY(set_device(h));
-    return embed_set(h, Din, Dout, m_in, len_in, A, m_out, len_out);
-  });
+  return device_entry(h, "plda_embed_set", [&] { return embed_set(h, Din, Dout, m_in, len_in, A, m_out, len_out); });
 }
 
 int plda_embed_clear(plda_handle *h) {
-  return guarded(h, "plda_embed_clear", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
-    return embed_clear(h);
-  });
+  return entry(h, "plda_embed_clear", [&] { return embed_clear(h); });
 }
 
 int plda_embed_dims(plda_handle *h, int32_t *Din, int32_t *Dout, int32_t *flags) {
-  return guarded(h, "plda_embed_dims", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
+  return entry(h, "plda_embed_dims", [&]() -> int {
     if (!h->em_has) return fail(h, PLDA_E_NOT_FITTED, "embed_dims: no embedding chain is set");
     if (Din) *Din = h->em_Din;
     if (Dout) *Dout = h->em_Dout;
@@ -2556,9 +2227,7 @@ int plda_embed_dims(plda_handle *h, int32_t *Din, int32_t *Dout, int32_t *flags)
 }
 
 int plda_embed_get(plda_handle *h, double *m_in, double *len_in, double *A, double *m_out, double *len_out) {
-  return guarded(h, "plda_embed_get", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
+  return entry(h, "plda_embed_get", [&]() -> int {
     if (!h->em_has) return fail(h, PLDA_E_NOT_FITTED, "embed_get: no embedding chain is set");
     if (m_in && h->em_has_min) std::memcpy(m_in, h->em_h_min.data(), h->em_h_min.size() * 8);
     if (A && h->em_has_A) std::memcpy(A, h->em_h_A.data(), h->em_h_A.size() * 8);
@@ -2570,45 +2239,33 @@ int plda_embed_get(plda_handle *h, double *m_in, double *len_in, double *A, doub
 }
 
 int plda_embed_plan(plda_handle *h, int32_t Din, int32_t Dout, int32_t has_A, int32_t dtype, int32_t out[3]) {
-  return guarded(h, "plda_embed_plan", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
-    return embed_plan(h, Din, Dout, has_A, dtype, out);
-  });
+  return entry(h, "plda_embed_plan", [&] { return embed_plan(h, Din, Dout, has_A, dtype, out); });
 }
 
 int plda_embed_apply_dev(plda_handle *h, const void *dX, int32_t dtype, int64_t R, int32_t Din, double *dout) {
-  return guarded(h, "plda_embed_apply_dev", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
-    PLDA_TRY(set_device(h));
-    return embed_apply_device(h, dX, dtype, R, Din, dout);
-  });
+  return device_entry(h, "plda_embed_apply_dev", [&] { return embed_apply_device(h, dX, dtype, R, Din, dout); });
 }
 
 int plda_embed_apply(plda_handle *h, const void *X, int32_t dtype, int64_t R, int32_t Din, double *out) {
-  return guarded(h, "plda_embed_apply", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
+  return entry(h, "plda_embed_apply", [&]() -> int {
     if (!h->em_has) return fail(h, PLDA_E_NOT_FITTED, "embed_apply: no embedding chain is set");
     if (dtype != 0 && dtype != 1) return fail(h, PLDA_E_INVAL, "embed_apply: dtype %d (0 fp64, 1 fp32)", (int)dtype);
     if (Din != h->em_Din) return fail(h, PLDA_E_INVAL, "embed_apply: feature dim %d != the chain's input dim %d", (int)Din, h->em_Din);
     if (R <= 0) return PLDA_OK;
     if (!X || !out) return fail(h, PLDA_E_INVAL, "embed_apply: bad argument");
     PLDA_TRY(set_device(h));
-    Tmp dX, dO;
-    PLDA_TRY(upload(h, dX, X, (size_t)R * Din * (dtype == 1 ? 4 : 8)));
-    PLDA_HIP(h, dO.alloc((size_t)R * h->em_Dout * 8));
-    PLDA_TRY(embed_apply_device(h, dX.p, dtype, R, Din, dO.as<double>()));
-    return download(h, out, dO.p, (size_t)R * h->em_Dout * 8);
+    Staged st(h);
+    const void *dX;
+    double *dO;
+    PLDA_TRY(st.in(X, (size_t)R * Din * (dtype == 1 ? 4 : 8), &dX));
+    PLDA_TRY(st.out(out, (size_t)R * h->em_Dout, &dO, true));
+    return st.finish(embed_apply_device(h, dX, dtype, R, Din, dO));
   });
 }
 
 int plda_embed_fit_dev(plda_handle *h, const void *dX, int32_t dtype, int64_t N, int32_t Din, const uint64_t *dlabels, int64_t K,
                        int32_t kind, int32_t Dout, double len_in, double len_out, double *eig) {
-  return guarded(h, "plda_embed_fit_dev", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
+  return entry(h, "plda_embed_fit_dev", [&]() -> int {
     PLDA_TRY(embed_fit_validate(h, dtype, N, Din, dlabels != nullptr, K, kind, Dout, len_in, len_out));
     PLDA_TRY(set_device(h));
     return embed_fit_device(h, dX, dtype, N, Din, dlabels, K, kind, Dout, len_in, len_out, eig);
@@ -2617,9 +2274,7 @@ int plda_embed_fit_dev(plda_handle *h, const void *dX, int32_t dtype, int64_t N,
 
 int plda_embed_fit(plda_handle *h, const void *X, int32_t dtype, int64_t N, int32_t Din, const uint64_t *labels, int32_t kind,
                    int32_t Dout, double len_in, double len_out, double *eig) {
-  return guarded(h, "plda_embed_fit", [&]() -> int {
-    if (!h) return PLDA_E_INVAL;
-    PLDA_LOCK(h);
+  return entry(h, "plda_embed_fit", [&]() -> int {
     int64_t K = 0;
     if (labels && kind == 2 && N > 0 && N < ((int64_t)1 << 31)) {
       uint64_t mx = 0;
@@ -2630,10 +2285,12 @@ int plda_embed_fit(plda_handle *h, const void *X, int32_t dtype, int64_t N, int3
     PLDA_TRY(embed_fit_validate(h, dtype, N, Din, labels != nullptr, K, kind, Dout, len_in, len_out));
     if (!X) return fail(h, PLDA_E_INVAL, "embed_fit: X is NULL");
     PLDA_TRY(set_device(h));
-    Tmp dX, dL;
-    PLDA_TRY(upload(h, dX, X, (size_t)N * Din * (dtype == 1 ? 4 : 8)));
-    if (kind == 2) PLDA_TRY(upload(h, dL, labels, (size_t)N * 8));
-    return embed_fit_device(h, dX.p, dtype, N, Din, kind == 2 ? dL.as<uint64_t>() : nullptr, K, kind, Dout, len_in, len_out, eig);
+    Staged st(h);
+    const void *dX;
+    const uint64_t *dL;
+    PLDA_TRY(st.in(X, (size_t)N * Din * (dtype == 1 ? 4 : 8), &dX));
+    PLDA_TRY(st.in(kind == 2 ? labels : nullptr, (size_t)N, &dL));
+    return embed_fit_device(h, dX, dtype, N, Din, dL, K, kind, Dout, len_in, len_out, eig);
   });
 }
 

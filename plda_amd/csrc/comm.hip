@@ -37,9 +37,6 @@
 
 namespace plda {
 
-int znorm_stats_device(plda_handle *h, const double *dbkg, int64_t Nb, int num_examples, int Din,
-                       const double *dmodels, int64_t M, double *dmean, double *dstd);
-
 // ------------------------------------------------------------------------------------ RCCL, resolved lazily
 namespace {
 struct Rccl {
@@ -797,8 +794,6 @@ int cohort_stats_sharded_device(plda_handle *h, const double *dX, const int32_t 
 }
 
 // ------------------------------------------------------------------------------------ fit by speaker
-int fit_em_device(plda_handle *h, int64_t K, int D, int iters);
-
 int fit_sharded_device(plda_handle *h, const double *dX, int64_t N, int D, const uint64_t *dlabels, int64_t K, int iters) {
   const int R = h->comm_nranks, me = h->comm_rank;
   PLDA_TRY(fit_stats_device(h, dX, N, D, dlabels, K));        // means[K, D], counts[K], scatter[D, D] of MY speakers

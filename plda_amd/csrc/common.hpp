@@ -487,6 +487,8 @@ int sym_eig_f64(plda_handle *h, double *G, int D, double *s, double *Vrows, int 
 // *status != 0: not supported / gave up -> use sym_eig_f64.  G is not modified.
 int sym_eig_dc_f64(plda_handle *h, const double *G, int D, double *s, double *Vrows, int *status);   // status == nullptr: deferred
 int sym_eig_dc_status(plda_handle *h, int *status);
+// eig_sort_kernel of linalg.hip (rank sort descending, optional floor at zero, row permutation)
+int eig_sort_rows(plda_handle *h, const double *lam, const double *V, int D, double *s, double *Vsorted);
 int sym_eig_auto_f64(plda_handle *h, double *G, int D, double *s, double *Vrows);   // direct, else block Jacobi
 int simdiag_enqueue(plda_handle *h, const double *W, const double *B, int D, double *T, double *Tinv, double *psi,
                     bool *pending);
@@ -592,6 +594,11 @@ int fit_stats_device(plda_handle *h, const double *dX, int64_t N, int D, const u
 int fit_em_device(plda_handle *h, int64_t K, int D, int iters);
 int fit_device(plda_handle *h, const double *dX, int64_t N, int D, const uint64_t *dlabels,
                int64_t K, int iters);
+int compute_offset_device(plda_handle *h);   // offset = -transform . mean (Plda::ComputeDerivedVars)
+int group_by_label_device(plda_handle *h, const uint64_t *dlabels, int64_t N, uint32_t **perm_out, int **offsets_out,
+                          uint64_t **uniq_out, int64_t *G_out);
+int group_centroids_device(plda_handle *h, const double *dX, int64_t N, int D, const uint32_t *perm, const int *offsets,
+                           int64_t G, double *dmeans, int32_t *dcounts32);
 
 // ---- score.hip ----
 // cs: the distinct enrol counts of the caller's whole call (mixed counts; nullptr: found from dn on the device)
@@ -599,6 +606,12 @@ int score_matrix_device(plda_handle *h, const double *dU, const int32_t *dn, int
                         const double *dV, int64_t Nt, const double *dzmean, const double *dzstd,
                         float *dout, int64_t ld, bool reuse_packed_B = false, const CountSet *cs = nullptr);
 void score_count_set_host(const int32_t *n, int64_t M, CountSet *cs);
+// M, cs: the enrol set's size and its distinct counts (long lists run on per-count tables; M = 0: the list is short)
+int score_pairs_device(plda_handle *h, const double *dU, const int32_t *dn, const double *dV,
+                       const int64_t *de, const int64_t *dt, int64_t P, const double *dzmean,
+                       const double *dzstd, double *dout, int64_t M = 0, const CountSet *cs = nullptr);
+int znorm_stats_device(plda_handle *h, const double *dbkg, int64_t Nb, int num_examples, int Din,
+                       const double *dmodels, int64_t M, double *dmean, double *dstd);
 int pairs_validate_device(plda_handle *h, const int64_t *de, const int64_t *dt, int64_t P, int64_t M, int64_t Nt, long long *bad);
 int score_count_set_device(plda_handle *h, const int32_t *dn, int64_t M, CountSet *cs);
 int score_prepare_device(plda_handle *h, const double *dV, int64_t Nt, int kind, int n_uniform, const CountSet *cs);
@@ -631,6 +644,23 @@ int score_topn_device(plda_handle *h, const double *dU, const int32_t *dn, int n
                       const double *dzmean, const double *dzstd, const double *demean, const double *destd, const double *dtmean,
                       const double *dtstd, int axis, int64_t top_n, float *dout_scores, int64_t *dout_index,
                       const CountSet *cs = nullptr);
+
+// ---- comm.hip (the communicator of a handle and the row-sharded forms over it)
+int comm_init(plda_handle *h, int nranks, int rank, const void *uid);
+int comm_init_custom(plda_handle *h, int nranks, int rank, const plda_collectives *t);
+int comm_init_host(plda_handle *h, int nranks, int rank, const plda_host_collectives *t);
+int comm_init_peer(plda_handle *h, int nranks, int rank, const plda_host_collectives *t);
+int comm_destroy(plda_handle *h);
+int comm_check(plda_handle *h);
+int comm_describe(plda_handle *h, std::string &js);
+int score_matrix_sharded_device(plda_handle *h, const double *dU, const int32_t *dn, int n_uniform, int64_t M,
+                                const double *dV, int64_t Nt, const double *dzmean, const double *dzstd, float *dlocal,
+                                int64_t ld_local, float *dfull, int64_t ld_full, int64_t block_rows, int gather);
+int znorm_stats_sharded_device(plda_handle *h, const double *dbkg, int64_t Nb, int num_examples, int Din,
+                               const double *dmodels, int64_t M, double *dmean, double *dstd);
+int fit_sharded_device(plda_handle *h, const double *dX, int64_t N, int D, const uint64_t *dlabels, int64_t K, int iters);
+int cohort_stats_sharded_device(plda_handle *h, const double *dX, const int32_t *dn, int n_uniform, int64_t Rows, const double *dC,
+                                int64_t Nc, int64_t top_k, double *dmean, double *dstd);
 
 // (the labelled-trials source of the EER / DET / calibration / minDCF reductions and their score key: trial_source.hpp)
 

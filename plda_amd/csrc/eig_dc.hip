@@ -1680,9 +1680,6 @@ __global__ __launch_bounds__(256) void householder_row1_kernel(const double *__r
 
 }  // namespace
 
-// eig_sort_kernel of linalg.hip (rank sort descending, optional floor at zero, row permutation)
-int eig_sort_rows(plda_handle *h, const double *lam, const double *V, int D, double *s, double *Vsorted);
-
 int sym_eig_dc_status(plda_handle *h, int *status) {
   *status = 8;
   if (!h->eigdc_flag) return PLDA_OK;

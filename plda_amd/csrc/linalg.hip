@@ -2175,9 +2175,6 @@ int sym_eig_auto_f64(plda_handle *h, double *G, int D, double *s, double *Vrows)
 //   simdiag_finish    reads the Cholesky and eigensolver flags (after a synchronisation the caller needs
 //                     anyway) and, if the direct method gave up, repeats the decomposition with block Jacobi.
 // simdiag_f64 = both, for callers that want the result at once.
-int simdiag_finish_with(plda_handle *h, const double *W, const double *B, int D, double *T, double *Tinv, double *psi,
-                        int chol_flag, int eig_status, bool *redo);
-
 // The arrays of h->simdiag_state, the one list every reader of it goes through.  T1, Vr and the flag outlive the call.
 struct SimdiagState {
   double *scr, *T1, *tmp, *G, *Vr;   // whitening scratch [2 DD]; chol(W)^-1; T1 B; the congruence; eigenvectors in rows (the next warm start)
