@@ -60,7 +60,8 @@ int plda_destroy(plda_handle *h);
 const char *plda_last_error(const plda_handle *h);
 int plda_abi_version(void);
 /* bit 0: built with -DPLDA_DIAG=1 (libplda_hip_diag.so: + the measurement arms of the trials GEMM, some of which return
- * garbage scores; selected by PLDA_GEMM_VARIANT).  The product library returns 0 and plda_create refuses those variants. */
+ * garbage scores; selected by PLDA_GEMM_VARIANT).  The product library returns 0 and plda_create refuses those variants; both
+ * libraries refuse a PLDA_GEMM_VARIANT that names no arm (profiles/SWITCHES.md lists the arms). */
 int plda_build_flags(void);
 /* bytes of device memory the library's buffers hold right now, over every handle of the process (the device scratch and
  * model copies of the handles, the temporaries of calls in flight; not the one uncached flag page of the peer transport,
@@ -247,9 +248,9 @@ int plda_score_unprepare(plda_handle *h);
 int plda_profile_enable(plda_handle *h, int32_t on);
 int plda_profile_read(plda_handle *h, double *gemm_ms, int64_t *launches, double *gemm_flop,
                       int32_t reset);
-/* Diagnostic (PLDA_HIP tracing knob): with PLDA_GEMM_VARIANT=31 in the environment at
- * plda_create, the trials GEMM runs an instrumented instantiation whose workgroup 0 stamps the
- * shader clock per wave at every stage barrier (arrive, leave) and around every tile epilogue.
+/* Diagnostic (PLDA_HIP tracing knob; diagnostic build only): with a timeline arm in the environment at
+ * plda_create (PLDA_GEMM_VARIANT=31: the two-waves 256 x 256 kernel, 41: the one-wave one), the trials GEMM runs an
+ * instrumented instantiation whose workgroup 0 stamps the shader clock per wave at every stage barrier (arrive, leave) and around every tile epilogue.
  * out[tile < 8][stage < 16][wave < 8][8] = {barrier arrive, leave, start of steps 1..3 of the stage (0 if
  * absent), -, epilogue start, epilogue end (the last two in stage slot 15)}. */
 int plda_profile_timeline(plda_handle *h, uint64_t *out, int64_t cap_words);

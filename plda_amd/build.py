@@ -5,7 +5,7 @@ travels to the GPU box with the snapshot.
 
 `--diag` (build(diag=True)) builds the DIAGNOSTIC library plda_amd/lib/libplda_hip_diag.so from the same sources with
 -DPLDA_DIAG=1 (objects under lib/diag/): it additionally contains the measurement arms of the trials GEMM (bounding arms
-that return garbage scores, clock-stamp and stage-depth arms; csrc/common.hpp).  The profiling scripts and bench.py's
+that return garbage scores, timeline and clock-stamp arms; csrc/common.hpp).  The profiling scripts and bench.py's
 shader-clock reading load it (plda_amd._native.load(diag=True) / PLDA_LIB_DIAG=1); nothing else does.
 """
 import os

@@ -282,8 +282,7 @@ int with_host_fusion_lists(plda_handle *h, const char *fn, int32_t K, const floa
 }
 // the settings plda_create reads from the environment: whole numbers stored as they are ...
 const struct { const char *name; int plda_handle::*member; } ENV_INT[] = {
-    {"PLDA_GEMM_VARIANT", &plda_handle::gemm_variant},     {"PLDA_PREP_VARIANT", &plda_handle::prep_variant},
-    {"PLDA_MIXED_VARIANT", &plda_handle::mixed_variant},   {"PLDA_EM_VARIANT", &plda_handle::em_variant},
+    {"PLDA_PREP_VARIANT", &plda_handle::prep_variant},     {"PLDA_EM_VARIANT", &plda_handle::em_variant},
     {"PLDA_JACOBI_VARIANT", &plda_handle::jacobi_variant}, {"PLDA_GEMM64_VARIANT", &plda_handle::gemm64_variant},
     {"PLDA_EIG_VARIANT", &plda_handle::eig_variant},       {"PLDA_EIG_DEBUG", &plda_handle::eig_debug},
     {"PLDA_SORT_VARIANT", &plda_handle::sort_variant},     {"PLDA_ZNORM_VARIANT", &plda_handle::znorm_variant},
@@ -307,15 +306,24 @@ int read_environment(plda_handle *h) {
   for (const auto &e : ENV_INT64)
     if (const char *v = std::getenv(e.name)) h->*e.member = std::atoll(v);
   if (const char *v = std::getenv("PLDA_HIP_TRACE")) h->trace_on = h->trace_print = std::atoi(v) != 0;
-#if !PLDA_DIAG
-  {   // measurement arms (garbage scores or clock stamps): not in this build
-    static const int diag_only[] = {1, 2, 3, 4, 9, 10, 11, 12, 31, 33, 34, 35, 36, 37, 41, 44, 45, 46, 47, 54, 58, 62, 63};
-    for (int d : diag_only)
-      if (h->gemm_variant == d)
-        return fail(nullptr, PLDA_E_INVAL, "plda_create: PLDA_GEMM_VARIANT=%d is a measurement arm of the diagnostic build (PLDA_DIAG=1, "
-                                           "libplda_hip_diag.so); this library does not contain it", d);
+  if (const char *v = std::getenv("PLDA_GEMM_VARIANT")) {
+    // one row of score.hip's table, or nothing: the numbers of A/B arms that are gone, and numbers nobody assigned, fail here
+    // instead of timing the product kernel under another arm's name
+    char *end = nullptr;
+    const long n = std::strtol(v, &end, 10);
+    const GemmArm *arm = *end == 0 && n == (int)n ? gemm_arm_lookup((int)n) : nullptr;      // (empty: arm 0)
+    if (!arm) return fail(nullptr, PLDA_E_INVAL, "plda_create: PLDA_GEMM_VARIANT=%s: no such arm exists (profiles/SWITCHES.md lists them)", v);
+    if (arm->diag && !PLDA_DIAG)   // measurement arms (garbage scores or clock stamps): not in this build
+      return fail(nullptr, PLDA_E_INVAL, "plda_create: PLDA_GEMM_VARIANT=%d is a measurement arm of the diagnostic build (PLDA_DIAG=1, "
+                                         "libplda_hip_diag.so); this library does not contain it", arm->variant);
+    h->gemm_arm = *arm;
   }
-#endif
+  if (const char *v = std::getenv("PLDA_MIXED_VARIANT")) {
+    if (*v && std::strcmp(v, "0") != 0 && std::strcmp(v, "1") != 0)
+      return fail(nullptr, PLDA_E_INVAL, "plda_create: PLDA_MIXED_VARIANT=%s (0: mixed enrol counts bucketed by distinct count, 1: always "
+                                         "the depth-2D form; no other arm exists)", v);
+    h->mixed_variant = std::atoi(v);
+  }
   if (const char *v = std::getenv("PLDA_SCORE_DTYPE")) {
     if (std::strcmp(v, "bf16x3") == 0) h->score_dtype = 1;
     else if (std::strcmp(v, "f32") != 0 && *v) return fail(nullptr, PLDA_E_INVAL, "plda_create: PLDA_SCORE_DTYPE=%s (f32 or bf16x3)", v);
@@ -988,7 +996,7 @@ int plda_profile_read(plda_handle *h, double *gemm_ms, int64_t *launches, double
 int plda_profile_timeline(plda_handle *h, uint64_t *out, int64_t cap_words) {
   return entry(h, "plda_profile_timeline", [&]() -> int {
     if (!out || cap_words < (int64_t)TIMELINE_WORDS) return fail(h, PLDA_E_CAPACITY, "profile_timeline: need %zu words", TIMELINE_WORDS);
-    if (!h->timeline_valid) return fail(h, PLDA_E_INVAL, "profile_timeline: no PLDA_GEMM_VARIANT=31 launch has run on this handle");
+    if (!h->timeline_valid) return fail(h, PLDA_E_INVAL, "profile_timeline: no launch of a timeline arm (PLDA_GEMM_VARIANT, diagnostic build) has run on this handle");
     PLDA_TRY(set_device(h));
     PLDA_HIP(h, hipStreamSynchronize(h->stream));
     PLDA_HIP(h, hipMemcpy(out, h->timeline.p, TIMELINE_WORDS * 8, hipMemcpyDeviceToHost));

@@ -15,7 +15,7 @@
 #include "layout.hpp"
 
 // PLDA_DIAG=1 (plda_amd/build.py --diag -> libplda_hip_diag.so): the measurement arms of the trials GEMM -- bounding arms that
-// skip the operand DMA or the stores and return GARBAGE scores, per-wave clock stamps, stage-depth sweeps -- are compiled in and
+// skip the operand DMA or the stores and return GARBAGE scores, per-wave timelines, clock stamps -- are compiled in and
 // selectable through PLDA_GEMM_VARIANT.  The product library is built without it: those kernels are not instantiated and
 // plda_create refuses their variant numbers (round-5 review: a stray environment variable must not be able to corrupt scores).
 #ifndef PLDA_DIAG
@@ -117,6 +117,16 @@ constexpr int CS_NMAX = 4095;     // a count above this: the depth-2D form
 struct CountSet { int G = 0; int32_t vals[CS_MAX] = {}; };
 // One (btM, btN) tile grid of trials_gemm_bt4_kernel: per-XCD queues over a table of tiles (score.hip: bt4_schedule)
 struct Bt4Table { int btM = -1, btN = -1, colwalk = 0; DevBuf tab; int qbase[8] = {}, qlen[8] = {}; uint64_t used = 0; };
+// One arm of PLDA_GEMM_VARIANT: a row of score.hip's table GEMM_ARMS, looked up once by plda_create and kept in the handle.
+//  * kernel: which trials-GEMM kernel an fp32 call runs.  GK_SHAPE: the one the shape rule names; GK_128 / GK_BT2 / GK_BT4:
+//    that one wherever its guards let it run, else the 128 x 128 kernel; GK_B3: a row of the bf16x3 kernel's instrumentation
+//    (PLDA_SCORE_DTYPE chooses that kernel, in front of every arm; an fp32 call under such a row runs the 128 x 128 kernel).
+//  * mode: the MODE template bits of the instantiation, for the row's own kernel only (every other kernel runs its MODE 0).
+//  * walk: the order of the patches of the one-wave-per-SIMD and the bf16x3 kernel.
+//  * diag: a measurement arm (garbage scores or clock stamps), in the diagnostic build only.
+enum GemmKernel { GK_SHAPE, GK_128, GK_BT2, GK_BT4, GK_B3 };
+enum GemmWalk { GW_SIZE, GW_ROWS, GW_COLS };
+struct GemmArm { int variant; GemmKernel kernel; int mode; GemmWalk walk; bool diag; };
 }  // namespace plda
 
 // a chunk of rows of ONE source and its coefficients in the EM's two rank-k sums (linalg.hip: em_rank_sums_mstep_f64)
@@ -227,7 +237,7 @@ struct plda_handle {
   int num_cus = 256;           // hipDeviceAttributeMultiprocessorCount (persistent grids)
   int sort_variant = 0;        // PLDA_SORT_VARIANT=1: fit groups the rows by the radix sort always (0: by counting where the tables fit)
   int transform_variant = 0;   // PLDA_TRANSFORM_VARIANT=1: GEMM + separate length-norm pass (the Dout > 512 path, forced)
-  int gemm_variant = 0;
+  plda::GemmArm gemm_arm = {0, plda::GK_SHAPE, 0, plda::GW_SIZE, false};   // PLDA_GEMM_VARIANT, resolved (default: arm 0)
   int mixed_variant = 0;   // PLDA_MIXED_VARIANT=1: mixed enrol counts always in the depth-2D form [A1 | A2] x [V | V*V] (A/B arm of the bucketed form)
   // PERSISTENT between calls: the scoring coefficient tables of the last call, uniform-count or bucketed (one buffer: a
   // call that fills one form invalidates the other).  Valid while ucoef_* / gcoef_* match (score.hip: prepare_operands)
@@ -242,8 +252,6 @@ struct plda_handle {
   int em_variant = 0;     // 0: grouped closed-form EM (moment or row form by shape); 3 / 4: the moment / the row form always; 1: EM in the simultaneously-diagonalised basis
   int em_groups = 0;      // groups (distinct class counts) of the last grouped EM, 0 if the other path ran
   int em_form = 0;        // EM of the last fit: 0 simultaneously-diagonalised basis, 1 grouped moment form, 2 grouped row form
-  bool bt2_attr_set = false;
-  bool bt4_attr_set = false;
   // tile schedule of the one-wave-per-SIMD trials GEMM (score.hip: bt4_schedule): per XCD a queue of tiles, consumed
   // through one device-scope counter per queue; the table is rebuilt when the tile grid changes
   plda::DevBuf bt4_cnt, bt4_fringe;   // (bt4_fringe: 256 x 256 scratch slots of the tiles that cross the matrix edge)
@@ -252,7 +260,7 @@ struct plda_handle {
   // distinct enrol counts of a mixed-count call: presence bytes + result on the device, pinned landing area
   plda::DevBuf cs_work;
   void *cs_pin = nullptr; int cs_seq = 0;   // pinned words of the count-set result + the sequence number its kernel stores last (score.hip)
-  bool timeline_valid = false;   // `timeline` holds the stamps of a PLDA_GEMM_VARIANT=31 launch
+  bool timeline_valid = false;   // `timeline` holds the stamps of a timeline or clock arm's launch (score.hip: timeline_buffer)
   plda::DevBuf timeline;
 
   // ---- profiling (plda_profile_*): event pairs around each trials-GEMM launch ----
@@ -601,6 +609,7 @@ int group_centroids_device(plda_handle *h, const double *dX, int64_t N, int D, c
                            int64_t G, double *dmeans, int32_t *dcounts32);
 
 // ---- score.hip ----
+const GemmArm *gemm_arm_lookup(int variant);   // the row of PLDA_GEMM_VARIANT=variant; nullptr: no such arm
 // cs: the distinct enrol counts of the caller's whole call (mixed counts; nullptr: found from dn on the device)
 int score_matrix_device(plda_handle *h, const double *dU, const int32_t *dn, int n_uniform, int64_t M,
                         const double *dV, int64_t Nt, const double *dzmean, const double *dzstd,

@@ -677,7 +677,9 @@ __global__ __launch_bounds__(256) void prep_buckets_both_kernel(const PrepBucket
 constexpr int PATCH_M = 8;
 constexpr int PATCH_N = 16;
 
-template <int NKQ>
+constexpr int NKQ = 10;   // k-quads per stage: 40 k, with 2 workgroups per CU (round-1 tuning against 32 / 24 / 16 k and 3 per CU)
+static_assert(NKQ % 2 == 0 && NKQ >= 4, "stage must hold whole 8-k steps; epilogue needs 32 KiB");
+
 __device__ __forceinline__ void stage_tiles(const f32x4 *__restrict__ Apk,
                                             const f32x4 *__restrict__ Bpk, int64_t Mpad,
                                             int64_t Npad, int kq0, int KQ, int64_t r0,
@@ -723,14 +725,13 @@ __device__ __forceinline__ void stage_tiles(const f32x4 *__restrict__ Apk,
   acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(A1[T], B0[T], acc[1][0], 0, 0, 0);         \
   acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(A1[T], B1[T], acc[1][1], 0, 0, 0);
 
-template <int NKQ, int EPI, int MINW, int ABL = 0>
-__global__ __launch_bounds__(256, MINW) void trials_gemm_kernel(
+template <int EPI>
+__global__ __launch_bounds__(256, 2) void trials_gemm_kernel(
     const f32x4 *__restrict__ Apk, const f32x4 *__restrict__ Bpk, int64_t Mpad, int64_t Npad,
     int KQ, const float *__restrict__ rbias, const float *__restrict__ rscale,
     const float *__restrict__ cbias, float *__restrict__ out, int64_t ld, int64_t M, int64_t Nt,
     int tilesM, int tilesN, int patchesN, int numPatches, const float *__restrict__ shift,
     double *__restrict__ colsum, double *__restrict__ colsq) {
-  static_assert(NKQ % 2 == 0 && NKQ >= 4, "stage must hold whole 8-k steps; epilogue needs 32 KiB");
   __shared__ f32x4 smem[2 * NKQ * 256];
 
   const unsigned b = blockIdx.x;
@@ -750,7 +751,7 @@ __global__ __launch_bounds__(256, MINW) void trials_gemm_kernel(
   const int i = lane & 31, hh = lane >> 5;
   const int64_t wrow0 = r0 + wm * 64, wcol0 = c0 + wn * 64;
 
-  stage_tiles<NKQ>(Apk, Bpk, Mpad, Npad, 0, KQ, r0, c0, smem, wave, lane);
+  stage_tiles(Apk, Bpk, Mpad, Npad, 0, KQ, r0, c0, smem, wave, lane);
 
   f32x4 rb[2][4];
 #pragma unroll
@@ -781,8 +782,8 @@ __global__ __launch_bounds__(256, MINW) void trials_gemm_kernel(
   __syncthreads();
   for (int st = 0; st < nst; ++st) {
     const f32x4 *cur = smem + (st & 1) * (NKQ * 256);
-    if (st + 1 < nst && !(ABL & 2))
-      stage_tiles<NKQ>(Apk, Bpk, Mpad, Npad, (st + 1) * NKQ, KQ, r0, c0,
+    if (st + 1 < nst)
+      stage_tiles(Apk, Bpk, Mpad, Npad, (st + 1) * NKQ, KQ, r0, c0,
                        smem + ((st + 1) & 1) * (NKQ * 256), wave, lane);
     const int np = min(NKQ, KQ - st * NKQ) >> 1;
     const f32x4 *Al = cur + hh * 128 + wm * 64 + i;
@@ -798,30 +799,21 @@ __global__ __launch_bounds__(256, MINW) void trials_gemm_kernel(
       MFMA4(0, xa0, xa1, xb0, xb1)
       __builtin_amdgcn_sched_barrier(0);
       const int o1 = (p + 1) * 256;
-      if (ABL & 1) { ya0 = xa1; ya1 = xa0; yb0 = xb1; yb1 = xb0; }
-      else { ya0 = Al[o1]; ya1 = Al[o1 + 32]; yb0 = Bl[o1]; yb1 = Bl[o1 + 32]; }
+      ya0 = Al[o1]; ya1 = Al[o1 + 32]; yb0 = Bl[o1]; yb1 = Bl[o1 + 32];
       __builtin_amdgcn_sched_barrier(0);
       MFMA4(1, xa0, xa1, xb0, xb1) MFMA4(2, xa0, xa1, xb0, xb1) MFMA4(3, xa0, xa1, xb0, xb1)
       MFMA4(0, ya0, ya1, yb0, yb1)
       __builtin_amdgcn_sched_barrier(0);
       const int o2 = min(p + 2, np - 1) * 256;
-      if (ABL & 1) { xa0 = ya1; xa1 = ya0; xb0 = yb1; xb1 = yb0; }
-      else { xa0 = Al[o2]; xa1 = Al[o2 + 32]; xb0 = Bl[o2]; xb1 = Bl[o2 + 32]; }
+      xa0 = Al[o2]; xa1 = Al[o2 + 32]; xb0 = Bl[o2]; xb1 = Bl[o2 + 32];
       __builtin_amdgcn_sched_barrier(0);
       MFMA4(1, ya0, ya1, yb0, yb1) MFMA4(2, ya0, ya1, yb0, yb1) MFMA4(3, ya0, ya1, yb0, yb1)
     }
     if (p < np) { MFMA16(xa0, xa1, xb0, xb1) }
-    if (!(ABL & 4)) __syncthreads();
+    __syncthreads();
   }
 
-  if (EPI == 2) {   // ablation only
-#pragma unroll
-    for (int tm = 0; tm < 2; ++tm)
-#pragma unroll
-      for (int tn = 0; tn < 2; ++tn)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) asm volatile("" ::"v"(acc[tm][tn][r]));
-  } else if (EPI == 0) {
+  if (EPI == 0) {
     // wave-private 32 x 64 fp32 staging tile (8 KiB); rows of 256 B, conflict-free both ways
     float *tw = reinterpret_cast<float *>(smem) + wave * 2048;
     const int rrow = lane >> 4, rcol = (lane & 15) * 4;     // transposed read: 4 rows x 256 B
@@ -966,7 +958,6 @@ __global__ __launch_bounds__(512, 2) void trials_gemm_bt2_kernel(
     int numPatches, unsigned long long *__restrict__ dbg) {
   extern __shared__ __attribute__((aligned(16))) f32x4 smem[];
   constexpr bool TL = (MODE & 1) != 0;                            // timeline instrumentation (diagnostic)
-  constexpr bool DIRECT = (MODE & 2) == 0;                        // epilogue stores straight from the accumulator layout (MODE bit 1: the LDS-transpose epilogue, A/B arm)
   // bounding arms (timing only, the scores are garbage): MODE bit 2 = no operand DMA (the MFMA stream, fragment reads,
   // barriers and the epilogue as they are, operands "resident"), bit 3 = no output stores (the epilogue's cost)
   constexpr bool NODMA = (MODE & 4) != 0, NOSTORE = (MODE & 8) != 0;
@@ -1178,11 +1169,11 @@ __global__ __launch_bounds__(512, 2) void trials_gemm_bt2_kernel(
       };
       if (NOSTORE && r0 >= 0) {
         // (bounding arm: r0 is never negative, but the compiler cannot know; the accumulators stay live)
-      } else if (DIRECT && interior) {
+      } else if (interior) {
         // no LDS round trip: a register of the 32 x 32 accumulator holds rows (8 q + e) and (8 q + e + 4) (lane >> 5)
         // of 32 consecutive columns, i.e. one store instruction = two full 128-byte row pieces.  The row walks on a
         // scalar base; the lane offset (half-row, column) is constant.  128 dword stores per tile and wave against
-        // 128 ds_write + 32 ds_read + 32 16-byte stores of the transposing epilogue below: what an epilogue costs
+        // 128 ds_write + 32 ds_read + 32 16-byte stores of the LDS-transposing epilogue it replaced: what an epilogue costs
         // beside an MFMA-dense partner wave is the NUMBER of vector-memory instructions it issues (~31-47 cycles
         // each), not their bytes -- 87.7 -> 88.8 % at D = 200, 94.2 -> 94.7 % at D = 512 in one interleaved sweep.
         const char *tb = reinterpret_cast<const char *>(out + (((int64_t)r0 + wm * 128) * ld + c0 + wn * 64));
@@ -1201,34 +1192,6 @@ __global__ __launch_bounds__(512, 2) void trials_gemm_bt2_kernel(
             }
             tb += 4 * ldb;
           }
-      } else if (interior) {
-        // stores address the tile through a scalar base that walks down the wave's 128 rows, 4 rows per
-        // store, plus a constant 32-bit lane offset (the host guarantees ld < 2^22).
-        // Software pipeline W(c) R(c) S(c-1): a wave's LDS operations execute in order, so W(c) may be
-        // issued behind R(c-1) on the same 2 KiB, and the stores of chunk c-1 wait only for R(c-1).
-        // (the walk is done on the SCALAR base -- two SALU adds per store -- and the lane offset stays
-        //  constant: vector ALU work in the epilogue waits behind the partner wave's MFMAs)
-        const char *tbase = reinterpret_cast<const char *>(out + (((int64_t)r0 + wm * 128) * ld + c0 + wn * 64));
-        const int64_t ldb4 = 16 * ld;                           // bytes per 4 rows
-        unsigned voff = (unsigned)rrow * ((unsigned)ld * 4u) + (unsigned)rcol * 4u;
-        asm volatile("" : "+v"(voff));   // opaque: one live register, not 32 hoisted addresses
-        f32x4 pv[2][2];
-#pragma unroll
-        for (int c = 0; c < 16; ++c) {
-          chunk_w(c);
-          __builtin_amdgcn_sched_barrier(0);
-          pv[c & 1][0] = *reinterpret_cast<const f32x4 *>(stg + lane * 4);
-          pv[c & 1][1] = *reinterpret_cast<const f32x4 *>(stg + 256 + lane * 4);
-          __builtin_amdgcn_sched_barrier(0);
-          if (c > 0) {
-            __builtin_nontemporal_store(pv[(c - 1) & 1][0], reinterpret_cast<f32x4 *>(const_cast<char *>(tbase) + voff));
-            __builtin_nontemporal_store(pv[(c - 1) & 1][1], reinterpret_cast<f32x4 *>(const_cast<char *>(tbase + ldb4) + voff));
-            tbase += 2 * ldb4;
-          }
-          __builtin_amdgcn_sched_barrier(0);
-        }
-        __builtin_nontemporal_store(pv[1][0], reinterpret_cast<f32x4 *>(const_cast<char *>(tbase) + voff));
-        __builtin_nontemporal_store(pv[1][1], reinterpret_cast<f32x4 *>(const_cast<char *>(tbase + ldb4) + voff));
       } else {
         const int64_t wrow0 = (int64_t)r0 + wm * 128, wcol0 = (int64_t)c0 + wn * 64;
         float *dst = out + (wrow0 + rrow) * ld + wcol0 + rcol;
@@ -1313,6 +1276,50 @@ __device__ __host__ inline void bt4_patch(int x, I k, int pM, int pN, int colwal
 #pragma clang diagnostic pop
 #include "score_bf16x3.inc"
 
+// ------------------------------------------------------------------------------------
+// The arms of PLDA_GEMM_VARIANT (common.hpp: GemmArm), the one place that gives a variant number its meaning.  plda_create
+// looks the number up once; a number without a row is refused there, in both builds -- a script that sets the number of a deleted
+// arm (profiles/HISTORY.md names them) must fail, not time the product kernel under that arm's name.
+// ------------------------------------------------------------------------------------
+static const GemmArm GEMM_ARMS[] = {
+    // variant, kernel, MODE, walk, diagnostic build only
+    {0, GK_SHAPE, 0, GW_SIZE, false},     // product: the kernel by shape (choose_gemm_kernel), the walk by operand size (gemm_colwalk)
+    {20, GK_128, 0, GW_SIZE, false},      // forcing arms -- the tests' references, and the only way to each kernel at a small shape:
+    {30, GK_BT2, 0, GW_SIZE, false},      // 128 x 128 / 256 x 256 with two waves per SIMD (rounds 2-3) / with one wave per SIMD
+    {40, GK_BT4, 0, GW_SIZE, false},
+    {48, GK_BT4, 0, GW_ROWS, false},      // 40 with the row walk / the column walk always (A/B arms; the bf16x3 kernel's walk too)
+    {49, GK_BT4, 0, GW_COLS, false},
+    // measurement arms.  MODE bit 0: per-wave timeline of workgroup 0 (plda_profile_timeline); bits 2 / 3: bounding arms without
+    // the operand DMA / without the output stores (timing only, the scores are garbage); bit 4: the product kernel + clock stamps
+    {31, GK_BT2, 1, GW_SIZE, true},  {34, GK_BT2, 4, GW_SIZE, true},  {35, GK_BT2, 8, GW_SIZE, true},  {36, GK_BT2, 12, GW_SIZE, true},
+    {37, GK_BT2, 16, GW_SIZE, true}, {41, GK_BT4, 1, GW_SIZE, true},  {44, GK_BT4, 4, GW_SIZE, true},  {45, GK_BT4, 8, GW_SIZE, true},
+    {46, GK_BT4, 12, GW_SIZE, true}, {47, GK_BT4, 16, GW_SIZE, true}, {54, GK_B3, 4, GW_SIZE, true},   {58, GK_B3, 8, GW_SIZE, true},
+    {62, GK_B3, 12, GW_SIZE, true},  {63, GK_B3, 16, GW_SIZE, true},
+};
+const GemmArm *gemm_arm_lookup(int variant) {
+  for (const GemmArm &a : GEMM_ARMS)
+    if (a.variant == variant) return &a;
+  return nullptr;
+}
+
+// The walk of the patches (trials_gemm_bt4_kernel's queues, the bf16x3 kernel's static walk): 1 = down the columns.
+// Which operand's panels stay in an XCD's L2 from patch to patch, i.e. which operand is fetched again and again (round 5).
+// Along a patch row (rounds 2-5a: always) every B panel is fetched once per patch row; down a patch column every A panel once
+// per patch column.  What decides is where the repeated operand comes from: at C4 the 1.27 GB test side -- five times the
+// 256 MB Infinity Cache -- came from HBM 40 times; down the columns the 42 MB enrol side repeats and the cache holds it.
+// Measured (scripts/probe/colwalk_ab.sh, colwalk_mid.sh; ms per step, row walk -> column walk, same box): C4 183.1 -> 174.2,
+// C3 72.2 -> 71.5 (FETCH_SIZE per launch 56.8 -> 36.0 GB and 35.1 -> 30.5 GB); where both operands fit the cache or neither
+// does the column walk LOSES a little: C2 28.23 -> 28.38 (11.0 -> 4.4 GB), 150k x 150k x 512 156.1 -> 157.4, 200k x 200k x 200
+// and 140k x 140k x 256 equal.  So: down the columns exactly when the enrol side fits half the cache and the test side does
+// not.  (Starting each XCD at a different height of its column, and dealing the columns beyond the last round of eight patch
+// by patch, changed nothing measurable; the second is kept for the balance of the queues.)
+// PLDA_GEMM_VARIANT=48: the row walk always; 49: the column walk always (A/B arms).  bytesA / bytesB: the operands as the calling
+// kernel reads them.
+static inline int gemm_colwalk(const GemmArm &arm, size_t bytesA, size_t bytesB) {
+  const size_t keep = (size_t)128 << 20;
+  return arm.walk == GW_ROWS ? 0 : arm.walk == GW_COLS ? 1 : (bytesA <= keep && bytesB > keep) ? 1 : 0;
+}
+
 // Tile schedule of trials_gemm_bt4_kernel for a btM x btN grid of 256 x 256 tiles: queue x (one per XCD) lists the tiles of
 // patches x, x + 8, ... (BPR x BPC tiles each, row-major inside a patch) -- the order the static walk of bt2 takes them in,
 // so that the 32 workgroups of an XCD still work inside one patch at a time and share its operand panels in their L2 --
@@ -1347,19 +1354,7 @@ static int bt4_schedule(plda_handle *h, int btM, int btN, int KQ, Bt4Table **out
     PLDA_HIP(h, h->bt4_cnt.reserve(32 * sizeof(unsigned)));
     PLDA_HIP(h, hipMemsetAsync(h->bt4_cnt.p, 0, 32 * sizeof(unsigned), h->stream));
   }
-  // Which operand's panels stay in an XCD's L2 from patch to patch, i.e. which operand is fetched again and again (round 5).
-  // Along a patch row (rounds 2-5a: always) every B panel is fetched once per patch row; down a patch column every A panel once
-  // per patch column.  What decides is where the repeated operand comes from: at C4 the 1.27 GB test side -- five times the
-  // 256 MB Infinity Cache -- came from HBM 40 times; down the columns the 42 MB enrol side repeats and the cache holds it.
-  // Measured (scripts/probe/colwalk_ab.sh, colwalk_mid.sh; ms per step, row walk -> column walk, same box): C4 183.1 -> 174.2,
-  // C3 72.2 -> 71.5 (FETCH_SIZE per launch 56.8 -> 36.0 GB and 35.1 -> 30.5 GB); where both operands fit the cache or neither
-  // does the column walk LOSES a little: C2 28.23 -> 28.38 (11.0 -> 4.4 GB), 150k x 150k x 512 156.1 -> 157.4, 200k x 200k x 200
-  // and 140k x 140k x 256 equal.  So: down the columns exactly when the enrol side fits half the cache and the test side does
-  // not.  (Starting each XCD at a different height of its column, and dealing the columns beyond the last round of eight patch
-  // by patch, changed nothing measurable; the second is kept for the balance of the queues.)
-  // PLDA_GEMM_VARIANT=48: the row walk always; 49: the column walk always (A/B arms).
-  const size_t keep = (size_t)128 << 20, bytesA = (size_t)btM * 256 * KQ * 16, bytesB = (size_t)btN * 256 * KQ * 16;
-  const int colwalk = h->gemm_variant == 48 ? 0 : h->gemm_variant == 49 ? 1 : (bytesA <= keep && bytesB > keep) ? 1 : 0;
+  const int colwalk = gemm_colwalk(h->gemm_arm, (size_t)btM * 256 * KQ * 16, (size_t)btN * 256 * KQ * 16);
   Bt4Table *lru = &h->bt4_tabs[0];
   for (auto &t : h->bt4_tabs) {
     if (t.btM == btM && t.btN == btN && t.colwalk == colwalk) { t.used = ++h->bt4_clock; *out = &t; return PLDA_OK; }
@@ -1570,6 +1565,20 @@ static inline int64_t operand_kq(const plda_handle *h, bool has_counts, const Co
   return std::max<int64_t>((has_counts ? 2 : 1) * Dp, 16) / 4;
 }
 
+// Rows per wave of the one-pass prep kernels: 4 while a side has at most 32 768 padded rows, 16 beyond
+// (PLDA_PREP_VARIANT=3 / 2: 4 / 16 forced).  One launcher per kernel picks the instantiation and the grid by it.
+static inline bool prep_few_rows(const plda_handle *h, int64_t rpad) { return h->prep_variant == 3 || (h->prep_variant != 2 && rpad <= 32768); }
+#define PREP_LAUNCHER(NAME_, KERNEL4_, KERNEL16_)                                              \
+  template <typename... Args> static void NAME_(plda_handle *h, int64_t rpad, Args... args) {  \
+    if (prep_few_rows(h, rpad)) KERNEL4_<<<(unsigned)(rpad / 16), 256, 0, h->stream>>>(args...); \
+    else KERNEL16_<<<(unsigned)(rpad / 64), 256, 0, h->stream>>>(args...);                     \
+  }
+PREP_LAUNCHER(launch_prep_enrol_side, (prep_side_kernel<0, 4>), (prep_side_kernel<0, 16>))
+PREP_LAUNCHER(launch_prep_test_side, (prep_side_kernel<1, 4>), (prep_side_kernel<1, 16>))
+PREP_LAUNCHER(launch_prep_enrol_buckets, prep_enrol_buckets_kernel<4>, prep_enrol_buckets_kernel<16>)
+PREP_LAUNCHER(launch_prep_test_buckets, prep_test_buckets_kernel<4>, prep_test_buckets_kernel<16>)
+#undef PREP_LAUNCHER
+
 // doA / doB: (re)build the enrol side (packed A, row biases, row scales) / the test side (packed B,
 // column biases); a blocked call packs each side once per block of its own dimension.
 // cs: the distinct enrol counts of the whole call when dn != nullptr (nullptr / unusable: the depth-2D form)
@@ -1609,8 +1618,7 @@ static int prepare_operands(plda_handle *h, const double *dU, const int32_t *dn,
       PLDA_LAUNCH_CHECK(h);
       h->gcoef_ptr = coefG; h->gcoef_epoch = h->model_epoch; h->gcoef_D = D; h->gcoef_set = *cs;
     }
-    auto few = [&](int64_t rpad) { return h->prep_variant == 3 || (h->prep_variant != 2 && rpad <= 32768); };   // (as the uniform path below)
-    if (doA && doB && few(op.Mpad) && few(op.Npad)) {
+    if (doA && doB && prep_few_rows(h, op.Mpad) && prep_few_rows(h, op.Npad)) {
       const PrepBucketArgs a{dU, dn, M, op.Mpad, h->s_Apk.as<float>(), h->s_rbias.as<float>(), h->s_rscale.as<float>(), h->s_rpair.as<float2>(),
                              dV, Nt, op.Npad, h->s_Bpk.as<float>(), h->s_cbias.as<float>(), h->s_cpair.as<float2>()};
       prep_buckets_both_kernel<<<(unsigned)((op.Mpad + op.Npad) / 16), 256, 0, h->stream>>>(a, (int)(op.Mpad / 16), *cs, coefG, h->d_psi.as<double>(), D,
@@ -1618,28 +1626,13 @@ static int prepare_operands(plda_handle *h, const double *dU, const int32_t *dn,
       PLDA_LAUNCH_CHECK(h);
       return PLDA_OK;
     }
-    if (doA) {
-      if (few(op.Mpad))
-        prep_enrol_buckets_kernel<4><<<(unsigned)(op.Mpad / 16), 256, 0, h->stream>>>(
-            dU, dn, *cs, coefG, h->d_psi.as<double>(), D, M, op.Mpad, KQm, KQx, dzmean, dzstd, h->s_Apk.as<float>(),
-            h->s_rbias.as<float>(), h->s_rscale.as<float>(), h->s_rpair.as<float2>());
-      else
-        prep_enrol_buckets_kernel<16><<<(unsigned)(op.Mpad / 64), 256, 0, h->stream>>>(
-            dU, dn, *cs, coefG, h->d_psi.as<double>(), D, M, op.Mpad, KQm, KQx, dzmean, dzstd, h->s_Apk.as<float>(),
-            h->s_rbias.as<float>(), h->s_rscale.as<float>(), h->s_rpair.as<float2>());
-    }
+    if (doA)
+      launch_prep_enrol_buckets(h, op.Mpad, dU, dn, *cs, coefG, h->d_psi.as<double>(), D, M, op.Mpad, KQm, KQx, dzmean, dzstd, h->s_Apk.as<float>(),
+                                h->s_rbias.as<float>(), h->s_rscale.as<float>(), h->s_rpair.as<float2>());
     if (doB) {
-      if (few(op.Npad)) {
-        prep_side_kernel<1, 4><<<(unsigned)(op.Npad / 16), 256, 0, h->stream>>>(
-            dV, coefG + D, coefG + 2 * D, 0, h->d_psi.as<double>(), D, Nt, op.Npad, KQm, nullptr, nullptr, h->s_Bpk.as<float>(),
-            h->s_cbias.as<float>(), nullptr, h->s_cpair.as<float2>());
-        prep_test_buckets_kernel<4><<<(unsigned)(op.Npad / 16), 256, 0, h->stream>>>(dV, coefG, G, D, Nt, op.Npad, KQm, KQx, h->s_Bpk.as<float>());
-      } else {
-        prep_side_kernel<1, 16><<<(unsigned)(op.Npad / 64), 256, 0, h->stream>>>(
-            dV, coefG + D, coefG + 2 * D, 0, h->d_psi.as<double>(), D, Nt, op.Npad, KQm, nullptr, nullptr, h->s_Bpk.as<float>(),
-            h->s_cbias.as<float>(), nullptr, h->s_cpair.as<float2>());
-        prep_test_buckets_kernel<16><<<(unsigned)(op.Npad / 64), 256, 0, h->stream>>>(dV, coefG, G, D, Nt, op.Npad, KQm, KQx, h->s_Bpk.as<float>());
-      }
+      launch_prep_test_side(h, op.Npad, dV, coefG + D, coefG + 2 * D, 0, h->d_psi.as<double>(), D, Nt, op.Npad, KQm, nullptr, nullptr,
+                            h->s_Bpk.as<float>(), h->s_cbias.as<float>(), nullptr, h->s_cpair.as<float2>());
+      launch_prep_test_buckets(h, op.Npad, dV, coefG, G, D, Nt, op.Npad, KQm, KQx, h->s_Bpk.as<float>());
     }
     PLDA_LAUNCH_CHECK(h);
     return PLDA_OK;
@@ -1668,9 +1661,7 @@ static int prepare_operands(plda_handle *h, const double *dU, const int32_t *dn,
       // one pass per side: bias, bias pair and packed operand together (prep_side_kernel; PLDA_PREP_VARIANT=1: the
       // separate kernels below, kept as the A/B arm and the reference the bit-identity test compares with; 2 / 3: this
       // path with 16 / 4 rows per wave forced)
-      auto few_rows = [&](int64_t rpad) { return h->prep_variant == 3 || (h->prep_variant != 2 && rpad <= 32768); };
-#define PREP_SIDE(SIDE_, RW_, RPAD_, ...) prep_side_kernel<SIDE_, RW_><<<(unsigned)((RPAD_) / (4 * RW_)), 256, 0, h->stream>>>(__VA_ARGS__)
-      if (doA && doB && few_rows(op.Mpad) && few_rows(op.Npad)) {
+      if (doA && doB && prep_few_rows(h, op.Mpad) && prep_few_rows(h, op.Npad)) {
         const PrepSideArgs a{dU, coef, M, op.Mpad, h->s_Apk.as<float>(), h->s_rbias.as<float>(), h->s_rpair.as<float2>()};
         const PrepSideArgs b{dV, coef + D, Nt, op.Npad, h->s_Bpk.as<float>(), h->s_cbias.as<float>(), h->s_cpair.as<float2>()};
         prep_both_kernel<<<(unsigned)((op.Mpad + op.Npad) / 16), 256, 0, h->stream>>>(a, b, (int)(op.Mpad / 16), coef + 2 * D, n_uniform, psi, D, op.KQ,
@@ -1678,23 +1669,12 @@ static int prepare_operands(plda_handle *h, const double *dU, const int32_t *dn,
         PLDA_LAUNCH_CHECK(h);
         return PLDA_OK;
       }
-      if (doA) {
-        if (few_rows(op.Mpad))
-          PREP_SIDE(0, 4, op.Mpad, dU, coef, coef + 2 * D, n_uniform, psi, D, M, op.Mpad, op.KQ, dzmean, dzstd, h->s_Apk.as<float>(),
-                    h->s_rbias.as<float>(), h->s_rscale.as<float>(), h->s_rpair.as<float2>());
-        else
-          PREP_SIDE(0, 16, op.Mpad, dU, coef, coef + 2 * D, n_uniform, psi, D, M, op.Mpad, op.KQ, dzmean, dzstd, h->s_Apk.as<float>(),
-                    h->s_rbias.as<float>(), h->s_rscale.as<float>(), h->s_rpair.as<float2>());
-      }
-      if (doB) {
-        if (few_rows(op.Npad))
-          PREP_SIDE(1, 4, op.Npad, dV, coef + D, coef + 2 * D, 0, psi, D, Nt, op.Npad, op.KQ, nullptr, nullptr, h->s_Bpk.as<float>(),
-                    h->s_cbias.as<float>(), nullptr, h->s_cpair.as<float2>());
-        else
-          PREP_SIDE(1, 16, op.Npad, dV, coef + D, coef + 2 * D, 0, psi, D, Nt, op.Npad, op.KQ, nullptr, nullptr, h->s_Bpk.as<float>(),
-                    h->s_cbias.as<float>(), nullptr, h->s_cpair.as<float2>());
-      }
-#undef PREP_SIDE
+      if (doA)
+        launch_prep_enrol_side(h, op.Mpad, dU, coef, coef + 2 * D, n_uniform, psi, D, M, op.Mpad, op.KQ, dzmean, dzstd, h->s_Apk.as<float>(),
+                               h->s_rbias.as<float>(), h->s_rscale.as<float>(), h->s_rpair.as<float2>());
+      if (doB)
+        launch_prep_test_side(h, op.Npad, dV, coef + D, coef + 2 * D, 0, psi, D, Nt, op.Npad, op.KQ, nullptr, nullptr, h->s_Bpk.as<float>(),
+                              h->s_cbias.as<float>(), nullptr, h->s_cpair.as<float2>());
       PLDA_LAUNCH_CHECK(h);
       return PLDA_OK;
     }
@@ -1734,15 +1714,175 @@ static int prepare_operands(plda_handle *h, const double *dU, const int32_t *dn,
   return PLDA_OK;
 }
 
+// ---- which kernel a trials GEMM runs, and its launch ----
+
+// Which kernel (round 5: measured over sizes with scripts/gemm_sweep.py and scripts/score_size_curve.py under PLDA_GEMM_VARIANT
+// 20 / 30 / 40).  The one-wave-per-SIMD kernel is the fastest per tile but pays ~30 us per launch (cold first stages, the
+// last tiles' 64 MB of stores, all workgroups ending together): it wins from ~1 700 tiles of 256 x 256.  Between 512 and
+// 1 700 tiles the two-waves kernel is 3-9 % ahead of both others (8192 x 8192 x 200: 0.237 ms against 0.249 / 0.252;
+// 2048 x 40000: 0.284 against 0.311 / 0.310) -- when its static 4 x 8 patches are mostly full: 512 x 200000 (two tile rows)
+// takes 0.73 ms on it and 0.49 on the others.  Below 512 tiles the 128 x 128 kernel.
+// No side effects: the kernel of (arm, epilogue, operands, shape, output pitch, contraction dtype).  A forcing arm gets its
+// kernel wherever that kernel's guards hold and the 128 x 128 kernel elsewhere; the fused z-norm statistics (EPI 1) exist in
+// the 128 x 128 kernel only; the bf16x3 kernel (opt-in: PLDA_SCORE_DTYPE=bf16x3, score_bf16x3.inc) goes in front of every arm.
+static GemmKernel choose_gemm_kernel(const GemmArm &arm, int EPI, const TrialOperands &op, int64_t M, int64_t Nt, int64_t ld, int score_dtype) {
+  if (EPI != 0) return GK_128;
+  // the 256-row kernels need 32-bit byte offsets into each packed operand and into a tile's output rows
+  const bool ld_ok = ld < (1ll << 22);
+  if (score_dtype == 1 && ld_ok && (int64_t)3 * ((int)round_up(op.KQ, 4) / 2) * std::max(op.Mpad, op.Npad) * 16 < (1ll << 32)) return GK_B3;
+  const bool fits4g = (int64_t)(op.KQ + 8) * op.Mpad * 16 < (1ll << 32) && (int64_t)(op.KQ + 8) * op.Npad * 16 < (1ll << 32);
+  const int btM = (int)ceil_div(M, 256), btN = (int)(op.Npad / 256);
+  const int64_t tiles = (int64_t)btM * btN;
+  const bool patches_full = (double)tiles >= 0.85 * (double)(round_up(btM, BPR) * round_up(btN, BPC));
+  const bool big = tiles >= 1700;                                       // -> one wave per SIMD (given K >= 72)
+  const bool big2 = tiles >= 1700 || (tiles >= 512 && patches_full);    // -> two waves per SIMD otherwise
+  // one wave per SIMD, 128 x 128 per wave (score_bt4.inc) -- the product path of every BASELINE configuration since round 4;
+  // it needs >= 3 stages per tile (K >= 72)
+  const int nsteps = op.KQ >> 1, nst = (nsteps + 3) >> 2;
+  if (fits4g && ld_ok && nst >= 3 && M < (1ll << 31) && Nt < (1ll << 31) && (arm.kernel == GK_BT4 || (arm.kernel == GK_SHAPE && big))) return GK_BT4;
+  if (fits4g && ld_ok && (arm.kernel == GK_BT2 || (arm.kernel == GK_SHAPE && big2))) return GK_BT2;
+  return GK_128;
+}
+
+// The MODE a launcher runs its kernel in: the arm's, when the arm is a row of that kernel; the product one otherwise.
+static inline int gemm_mode(const GemmArm &arm, GemmKernel k) { return arm.kernel == k ? arm.mode : 0; }
+
+// The stamp buffer of a timeline (MODE bit 0) or clock (bit 4) instantiation, nullptr for every other MODE.  The timeline
+// kernels stamp what workgroup 0 reaches of a cleared buffer; the clock ones write every word that is read afterwards.
+static int timeline_buffer(plda_handle *h, int mode, unsigned long long **dbg) {
+  *dbg = nullptr;
+  if (!(mode & 17)) return PLDA_OK;
+  PLDA_HIP(h, h->timeline.reserve(TIMELINE_WORDS * 8));
+  if (mode & 1) PLDA_HIP(h, hipMemsetAsync(h->timeline.p, 0, TIMELINE_WORDS * 8, h->stream));
+  h->timeline_valid = true;
+  *dbg = h->timeline.as<unsigned long long>();
+  return PLDA_OK;
+}
+
+// The instantiations of one kernel that this library contains, by template arguments (`key`), and the one a launch runs:
+// the dynamic-LDS opt-in of all of them is set once per device, then the instantiation of `key` is looked up.
+template <typename Fn> struct GemmInst { int key; Fn fn; };
+template <typename Fn, size_t N>
+static int gemm_instance(plda_handle *h, const GemmInst<Fn> (&inst)[N], DeviceOnce &once, int lds_bytes, int key, Fn *fn) {
+  if (once.needed(h->device)) {
+    for (const auto &i : inst)
+      PLDA_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void *>(i.fn), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
+    once.done(h->device);
+  }
+  for (const auto &i : inst)
+    if (i.key == key) { *fn = i.fn; return PLDA_OK; }
+  return fail(h, PLDA_E_INVAL, "score_matrix: this library has no trials-GEMM instantiation %d", key);
+}
+
+// the contraction as three bf16 terms per operand (score_bf16x3.inc): MODE 4 / 8 / 12 its bounding arms, 16 its clock stamps
+static int launch_gemm_bf16x3(plda_handle *h, const TrialOperands &op, int64_t M, int64_t Nt, float *dout, int64_t ld) {
+  static const GemmInst<decltype(&trials_gemm_bf16x3_kernel<0>)> inst[] = {
+      {0, &trials_gemm_bf16x3_kernel<0>},
+#if PLDA_DIAG      // measurement arms: only in the diagnostic build (plda_create refuses their variants otherwise)
+      {4, &trials_gemm_bf16x3_kernel<4>}, {8, &trials_gemm_bf16x3_kernel<8>}, {12, &trials_gemm_bf16x3_kernel<12>}, {16, &trials_gemm_bf16x3_kernel<16>},
+#endif
+  };
+  static DeviceOnce once;
+  const int mode = gemm_mode(h->gemm_arm, GK_B3);
+  decltype(inst[0].fn) fn;
+  PLDA_TRY(gemm_instance(h, inst, once, B3_LDS, mode, &fn));
+  const int KO = (int)round_up(op.KQ, 4) / 2, nsteps = KO / 2;          // k-octs (even), 16-k steps
+  const size_t bytesA = (size_t)3 * KO * op.Mpad * 16, bytesB = (size_t)3 * KO * op.Npad * 16;
+  PLDA_HIP(h, h->s_A16.reserve(bytesA));
+  PLDA_HIP(h, h->s_B16.reserve(bytesB));
+  split_bf16x3_kernel<<<dim3((unsigned)(op.Mpad / 256), (unsigned)KO), 256, 0, h->stream>>>(h->s_Apk.as<f32x4>(), op.Mpad, op.KQ, h->s_A16.as<f32x4>());
+  split_bf16x3_kernel<<<dim3((unsigned)(op.Npad / 256), (unsigned)KO), 256, 0, h->stream>>>(h->s_Bpk.as<f32x4>(), op.Npad, op.KQ, h->s_B16.as<f32x4>());
+  const int b3M = (int)ceil_div(M, 256), b3N = (int)ceil_div(Nt, 128);       // 256 x 128 tiles (Npad is a multiple of 256)
+  const int pM = (int)ceil_div(b3M, B3_PR), pN = (int)ceil_div(b3N, B3_PC);
+  unsigned long long *dbg;
+  PLDA_TRY(timeline_buffer(h, mode, &dbg));
+  fn<<<256, 512, B3_LDS, h->stream>>>(h->s_A16.as<f32x4>(), h->s_B16.as<f32x4>(), (unsigned)op.Mpad, (unsigned)op.Npad, nsteps, h->s_rbias.as<float>(),
+                                      h->s_rscale.as<float>(), h->s_cbias.as<float>(), dout, ld, M, Nt, b3M, b3N, pM, pN,
+                                      gemm_colwalk(h->gemm_arm, bytesA, bytesB), dbg);
+  return PLDA_OK;
+}
+
+// one wave per SIMD (score_bt4.inc): MODE 1 its timeline, 4 / 8 / 12 its bounding arms (no DMA / no stores / neither; they exist
+// for a four-step first stage only), 16 its clock stamps
+static int launch_gemm_bt4(plda_handle *h, const TrialOperands &op, int64_t M, int64_t Nt, float *dout, int64_t ld) {
+#define BT4_INST(FS_, MODE_) {100 * FS_ + MODE_, &trials_gemm_bt4_kernel<FS_, MODE_>}
+  static const GemmInst<decltype(&trials_gemm_bt4_kernel<3, 0>)> inst[] = {
+      BT4_INST(3, 0), BT4_INST(4, 0),
+#if PLDA_DIAG
+      BT4_INST(3, 1), BT4_INST(4, 1), BT4_INST(4, 4), BT4_INST(4, 8), BT4_INST(4, 12), BT4_INST(4, 16), BT4_INST(3, 16),
+#endif
+  };
+#undef BT4_INST
+  static DeviceOnce once;
+  const int btM = (int)ceil_div(M, 256), btN = (int)(op.Npad / 256);
+  const int nsteps = op.KQ >> 1, nst = (nsteps + 3) >> 2, sbase = nsteps / nst, fs = sbase + (nsteps - sbase * nst > 0 ? 1 : 0);   // steps of a tile's first stage: 3 or 4
+  int mode = gemm_mode(h->gemm_arm, GK_BT4);
+  if (fs == 3 && (mode & 12)) mode = 0;
+  decltype(inst[0].fn) fn;
+  PLDA_TRY(gemm_instance(h, inst, once, BT4_LDS, 100 * fs + mode, &fn));
+  Bt4Table *tb = nullptr;
+  PLDA_TRY(bt4_schedule(h, btM, btN, op.KQ, &tb));
+  // tiles that cross the matrix edge are written whole into scratch slots and copied out behind the launch
+  const int rag_m = (M & 255) != 0, rag_n = (Nt & 255) != 0;
+  const int fslots = (rag_m || rag_n) ? btM + btN : 0;
+  PLDA_HIP(h, h->bt4_fringe.reserve(std::max<size_t>((size_t)fslots * 65536 * 4, 256)));
+  unsigned long long *dbg;
+  PLDA_TRY(timeline_buffer(h, mode, &dbg));
+  fn<<<256, 256, BT4_LDS, h->stream>>>(h->s_Apk.as<f32x4>(), h->s_Bpk.as<f32x4>(), (unsigned)op.Mpad, (unsigned)op.Npad, op.KQ, h->s_rpair.as<float2>(),
+                                       h->s_cpair.as<float2>(), dout, ld, (int)M, (int)Nt, h->bt4_fringe.as<float>(), tb->tab.as<int2>(),
+                                       h->bt4_cnt.as<unsigned>(), dbg);
+  if (fslots)
+    fringe_copy_kernel<<<(unsigned)(fslots * 8), 256, 0, h->stream>>>(h->bt4_fringe.as<float>(), dout, ld, (int)M, (int)Nt, btM, btN, rag_m, rag_n);
+  return PLDA_OK;
+}
+
+// two waves per SIMD, persistent 256 x 256 tiles: MODE 1 its timeline (per-wave stamps of workgroup 0, plda_profile_timeline),
+// 4 / 8 / 12 its bounding arms, 16 its clock stamps
+static int launch_gemm_bt2(plda_handle *h, const TrialOperands &op, int64_t M, int64_t Nt, float *dout, int64_t ld) {
+  static const GemmInst<decltype(&trials_gemm_bt2_kernel<0>)> inst[] = {
+      {0, &trials_gemm_bt2_kernel<0>},
+#if PLDA_DIAG
+      {1, &trials_gemm_bt2_kernel<1>}, {4, &trials_gemm_bt2_kernel<4>}, {8, &trials_gemm_bt2_kernel<8>}, {12, &trials_gemm_bt2_kernel<12>}, {16, &trials_gemm_bt2_kernel<16>},
+#endif
+  };
+  static DeviceOnce once;
+  const int mode = gemm_mode(h->gemm_arm, GK_BT2);
+  decltype(inst[0].fn) fn;
+  PLDA_TRY(gemm_instance(h, inst, once, BT2_LDS, mode, &fn));
+  const int btM = (int)ceil_div(M, 256), btN = (int)(op.Npad / 256);
+  const int pM = (int)ceil_div(btM, BPR), pN = (int)ceil_div(btN, BPC);
+  unsigned long long *dbg;
+  PLDA_TRY(timeline_buffer(h, mode, &dbg));
+  fn<<<256, 512, BT2_LDS, h->stream>>>(h->s_Apk.as<f32x4>(), h->s_Bpk.as<f32x4>(), (unsigned)op.Mpad, (unsigned)op.Npad, op.KQ, h->s_rpair.as<float2>(),
+                                       h->s_cpair.as<float2>(), dout, ld, M, Nt, btM, btN, pN, pM * pN, dbg);
+  return PLDA_OK;
+}
+
+// 128 x 128 tiles, one block each (static LDS: no opt-in); M may be a row prefix of the packed operand (z-norm pilot): only its
+// tiles are launched
+struct Tg128Grid { int tilesM, tilesN, patchesN; int64_t numPatches, blocks; };
+static Tg128Grid tg128_grid(int64_t M, int64_t Npad) {
+  Tg128Grid g;
+  g.tilesM = (int)ceil_div(M, 128); g.tilesN = (int)(Npad / 128);
+  g.patchesN = (int)ceil_div(g.tilesN, PATCH_N);
+  g.numPatches = (int64_t)ceil_div(g.tilesM, PATCH_M) * g.patchesN;
+  g.blocks = round_up(g.numPatches, 8) * PATCH_M * PATCH_N;
+  return g;
+}
+template <int EPI>
+static int launch_gemm_128(plda_handle *h, const TrialOperands &op, int64_t M, int64_t Nt, float *dout, int64_t ld, const float *shift, double *colsum, double *colsq) {
+  const Tg128Grid g = tg128_grid(M, op.Npad);
+  trials_gemm_kernel<EPI><<<(unsigned)g.blocks, 256, 0, h->stream>>>(h->s_Apk.as<f32x4>(), h->s_Bpk.as<f32x4>(), op.Mpad, op.Npad, op.KQ, h->s_rbias.as<float>(),
+                                                                     h->s_rscale.as<float>(), h->s_cbias.as<float>(), dout, ld, M, Nt, g.tilesM, g.tilesN,
+                                                                     g.patchesN, (int)g.numPatches, shift, colsum, colsq);
+  return PLDA_OK;
+}
+
 template <int EPI>
 static int launch_gemm(plda_handle *h, const TrialOperands &op, int64_t M, int64_t Nt, float *dout, int64_t ld, const float *shift, double *colsum, double *colsq) {
-  // M may be a row prefix of the packed operand (z-norm pilot): only its tiles are launched
-  const int tilesM = (int)ceil_div(M, 128), tilesN = (int)(op.Npad / 128);
-  const int patchesM = (int)ceil_div(tilesM, PATCH_M), patchesN = (int)ceil_div(tilesN, PATCH_N);
-  const int64_t numPatches = (int64_t)patchesM * patchesN;
-  const int64_t grid = round_up(numPatches, 8) * PATCH_M * PATCH_N;
-  if (grid > 0x7fffffffLL) return fail(h, PLDA_E_INVAL, "score_matrix: block too large, shard it");
-  TraceScope ts(h, EPI == 0 ? "score.trials_gemm (K5)" : "score.znorm_stats_gemm (K8)", 2.0 * (double)op.Kg_alg * (double)M * (double)Nt, 1);
+  if (tg128_grid(M, op.Npad).blocks > 0x7fffffffLL) return fail(h, PLDA_E_INVAL, "score_matrix: block too large, shard it");
+  const double flop = 2.0 * (double)op.Kg_alg * (double)M * (double)Nt;
+  TraceScope ts(h, EPI == 0 ? "score.trials_gemm (K5)" : "score.znorm_stats_gemm (K8)", flop, 1);
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   if (h->prof_on) {
     if (h->prof_used == h->prof_events.size()) {
@@ -1753,210 +1893,26 @@ static int launch_gemm(plda_handle *h, const TrialOperands &op, int64_t M, int64
     ev0 = h->prof_events[h->prof_used].first;
     ev1 = h->prof_events[h->prof_used].second;
     h->prof_used++;
-    h->prof_flop += 2.0 * (double)op.Kg_alg * (double)M * (double)Nt;
+    h->prof_flop += flop;
     PLDA_HIP(h, hipEventRecord(ev0, h->stream));
   }
-  // opt-in arm: the contraction as three bf16 terms per operand (score_bf16x3.inc; PLDA_SCORE_DTYPE=bf16x3)
-  if (EPI == 0 && h->score_dtype == 1 && ld < (1ll << 22) &&
-      (int64_t)3 * ((int)round_up(op.KQ, 4) / 2) * std::max(op.Mpad, op.Npad) * 16 < (1ll << 32)) {
-    const int KO = (int)round_up(op.KQ, 4) / 2, nsteps = KO / 2;          // k-octs (even), 16-k steps
-    PLDA_HIP(h, h->s_A16.reserve((size_t)3 * KO * op.Mpad * 16));
-    PLDA_HIP(h, h->s_B16.reserve((size_t)3 * KO * op.Npad * 16));
-    split_bf16x3_kernel<<<dim3((unsigned)(op.Mpad / 256), (unsigned)KO), 256, 0, h->stream>>>(h->s_Apk.as<f32x4>(), op.Mpad, op.KQ, h->s_A16.as<f32x4>());
-    split_bf16x3_kernel<<<dim3((unsigned)(op.Npad / 256), (unsigned)KO), 256, 0, h->stream>>>(h->s_Bpk.as<f32x4>(), op.Npad, op.KQ, h->s_B16.as<f32x4>());
-    static DeviceOnce once;
-    if (once.needed(h->device)) {
-      const void *fns[] = {reinterpret_cast<const void *>(&trials_gemm_bf16x3_kernel<0>),
-#if PLDA_DIAG
-                           reinterpret_cast<const void *>(&trials_gemm_bf16x3_kernel<4>), reinterpret_cast<const void *>(&trials_gemm_bf16x3_kernel<8>),
-                           reinterpret_cast<const void *>(&trials_gemm_bf16x3_kernel<12>), reinterpret_cast<const void *>(&trials_gemm_bf16x3_kernel<16>),
-#endif
-      };
-      for (const void *f : fns) PLDA_HIP(h, hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, B3_LDS));
-      once.done(h->device);
-    }
-    const int b3M = (int)ceil_div(M, 256), b3N = (int)ceil_div(Nt, 128);       // 256 x 128 tiles (Npad is a multiple of 256)
-    const int pM = (int)ceil_div(b3M, B3_PR), pN = (int)ceil_div(b3N, B3_PC);
-    // the walk of the patches: as bt4_schedule chooses it (which operand repeats, and whether the Infinity Cache holds it)
-    const size_t keep3 = (size_t)128 << 20, bytesA3 = (size_t)3 * KO * op.Mpad * 16, bytesB3 = (size_t)3 * KO * op.Npad * 16;
-    const int colwalk3 = h->gemm_variant == 48 ? 0 : h->gemm_variant == 49 ? 1 : (bytesA3 <= keep3 && bytesB3 > keep3) ? 1 : 0;
-    h->last_kernel = "trials_gemm_bf16x3_kernel";
-#define B3L(MODE_)                                                                                                                      \
-  trials_gemm_bf16x3_kernel<MODE_><<<256, 512, B3_LDS, h->stream>>>(h->s_A16.as<f32x4>(), h->s_B16.as<f32x4>(), (unsigned)op.Mpad, (unsigned)op.Npad,  \
-                                                                    nsteps, h->s_rbias.as<float>(), h->s_rscale.as<float>(), h->s_cbias.as<float>(), dout, \
-                                                                    ld, M, Nt, b3M, b3N, pM, pN, colwalk3, h->timeline.as<unsigned long long>())
-#if PLDA_DIAG      // measurement arms: only in the diagnostic build (plda_create refuses their variants otherwise)
-    if (h->gemm_variant == 63) {                  // the product kernel + clock stamps of workgroup 0 (plda_profile_timeline)
-      PLDA_HIP(h, h->timeline.reserve(TIMELINE_WORDS * 8));
-      B3L(16);
-      h->timeline_valid = true;
-    } else if (h->gemm_variant == 54) B3L(4);            // bounding arms (timing only): no DMA / no stores / neither
-    else if (h->gemm_variant == 58) B3L(8);
-    else if (h->gemm_variant == 62) B3L(12);
-    else
-#endif
-      B3L(0);
-#undef B3L
-    PLDA_LAUNCH_CHECK(h);
-    if (ev1) PLDA_HIP(h, hipEventRecord(ev1, h->stream));
-    return PLDA_OK;
-  }
-  // persistent 256 x 256 kernel: when there are enough tiles to keep 256 CUs busy (PLDA_GEMM_VARIANT=20
-  // forces the 128 x 128 kernel, 30 the 256 x 256 one, 31 its timeline-instrumented instantiation)
-  const int btM = (int)ceil_div(M, 256), btN = (int)(op.Npad / 256);
-  // Which kernel (round 5: measured over sizes with scripts/gemm_sweep.py and scripts/score_size_curve.py under PLDA_GEMM_VARIANT
-  // 20 / 30 / 40).  The one-wave-per-SIMD kernel is the fastest per tile but pays ~30 us per launch (cold first stages, the
-  // last tiles' 64 MB of stores, all workgroups ending together): it wins from ~1 700 tiles of 256 x 256.  Between 512 and
-  // 1 700 tiles the two-waves kernel is 3-9 % ahead of both others (8192 x 8192 x 200: 0.237 ms against 0.249 / 0.252;
-  // 2048 x 40000: 0.284 against 0.311 / 0.310) -- when its static 4 x 8 patches are mostly full: 512 x 200000 (two tile rows)
-  // takes 0.73 ms on it and 0.49 on the others.  Below 512 tiles the 128 x 128 kernel.  PLDA_GEMM_VARIANT=50: the thresholds
-  // of rounds 4-5a (1 024 tiles for both 256 x 256 kernels).
-  const int64_t tiles = (int64_t)btM * btN;
-  const bool patches_full = (double)tiles >= 0.85 * (double)(round_up(btM, BPR) * round_up(btN, BPC));
-  const bool old_rule = h->gemm_variant == 50;
-  const bool big = EPI == 0 && tiles >= (old_rule ? 1024 : 1700);                       // -> one wave per SIMD (given K >= 72)
-  const bool big2 = EPI == 0 && (old_rule ? tiles >= 1024 : (tiles >= 1700 || (tiles >= 512 && patches_full)));   // -> two waves per SIMD otherwise
-  // it needs 32-bit byte offsets into each packed operand and into a tile's output rows
-  const bool fits4g = (int64_t)(op.KQ + 8) * op.Mpad * 16 < (1ll << 32) && (int64_t)(op.KQ + 8) * op.Npad * 16 < (1ll << 32);
-  const bool use_bt2 = EPI == 0 && fits4g && ld < (1ll << 22) &&
-                       ((h->gemm_variant >= 30 && h->gemm_variant <= 37) || ((h->gemm_variant == 0 || old_rule) && big2));
-  // one wave per SIMD, 128 x 128 per wave (score_bt4.inc) -- the product path of every BASELINE configuration since round 4
-  // (>= 1 700 tiles of 256 x 256 -- see above -- and K >= 72); PLDA_GEMM_VARIANT 40 forces it, 30 forces the round-2/3 kernel, 41 its timeline
-  // instantiation, 44 / 45 / 46 its bounding arms (no DMA / no stores / neither); needs >= 3 stages per tile (K >= 72).
-  {
-    const int nsteps = op.KQ >> 1, nst = (nsteps + 3) >> 2;
-    const bool use_bt4 = EPI == 0 && fits4g && ld < (1ll << 22) && nst >= 3 && M < (1ll << 31) && Nt < (1ll << 31) &&
-                         (h->gemm_variant == 40 || h->gemm_variant == 41 || h->gemm_variant == 48 || h->gemm_variant == 49 || (h->gemm_variant >= 44 && h->gemm_variant <= 47) || ((h->gemm_variant == 0 || old_rule) && big));
-    if (use_bt4) {
-      const int sbase = nsteps / nst, fs = sbase + (nsteps - sbase * nst > 0 ? 1 : 0);
+  switch (choose_gemm_kernel(h->gemm_arm, EPI, op, M, Nt, ld, h->score_dtype)) {
+    case GK_B3:
+      h->last_kernel = "trials_gemm_bf16x3_kernel";
+      PLDA_TRY(launch_gemm_bf16x3(h, op, M, Nt, dout, ld));
+      break;
+    case GK_BT4:
       h->last_kernel = "trials_gemm_bt4_kernel";
-      Bt4Table *tb = nullptr;
-      PLDA_TRY(bt4_schedule(h, btM, btN, op.KQ, &tb));
-      // tiles that cross the matrix edge are written whole into scratch slots and copied out behind the launch
-      const int rag_m = (M & 255) != 0, rag_n = (Nt & 255) != 0;
-      const int fslots = (rag_m || rag_n) ? btM + btN : 0;
-      PLDA_HIP(h, h->bt4_fringe.reserve(std::max<size_t>((size_t)fslots * 65536 * 4, 256)));
-      if (!h->bt4_attr_set) {
-        const void *fns[] = {reinterpret_cast<const void *>(&trials_gemm_bt4_kernel<3, 0>), reinterpret_cast<const void *>(&trials_gemm_bt4_kernel<4, 0>),
-#if PLDA_DIAG
-                             reinterpret_cast<const void *>(&trials_gemm_bt4_kernel<3, 1>), reinterpret_cast<const void *>(&trials_gemm_bt4_kernel<4, 1>),
-                             reinterpret_cast<const void *>(&trials_gemm_bt4_kernel<4, 4>), reinterpret_cast<const void *>(&trials_gemm_bt4_kernel<4, 8>),
-                             reinterpret_cast<const void *>(&trials_gemm_bt4_kernel<4, 12>), reinterpret_cast<const void *>(&trials_gemm_bt4_kernel<4, 16>),
-                             reinterpret_cast<const void *>(&trials_gemm_bt4_kernel<3, 16>),
-#endif
-        };
-        for (const void *f : fns) PLDA_HIP(h, hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, BT4_LDS));
-        h->bt4_attr_set = true;
-      }
-#define BT4L(FS_, MODE_, DBG_)                                                                            \
-  trials_gemm_bt4_kernel<FS_, MODE_><<<256, 256, BT4_LDS, h->stream>>>(                                   \
-      h->s_Apk.as<f32x4>(), h->s_Bpk.as<f32x4>(), (unsigned)op.Mpad, (unsigned)op.Npad, op.KQ,            \
-      h->s_rpair.as<float2>(), h->s_cpair.as<float2>(), dout, ld, (int)M, (int)Nt, h->bt4_fringe.as<float>(), tb->tab.as<int2>(), h->bt4_cnt.as<unsigned>(), DBG_)
-#if PLDA_DIAG
-      if (h->gemm_variant == 41) {
-        PLDA_HIP(h, h->timeline.reserve(TIMELINE_WORDS * 8));
-        PLDA_HIP(h, hipMemsetAsync(h->timeline.p, 0, TIMELINE_WORDS * 8, h->stream));
-        if (fs == 3) BT4L(3, 1, h->timeline.as<unsigned long long>());
-        else BT4L(4, 1, h->timeline.as<unsigned long long>());
-        h->timeline_valid = true;
-      } else if (h->gemm_variant == 47) {     // the product kernel + clock stamps of workgroup 0
-        PLDA_HIP(h, h->timeline.reserve(TIMELINE_WORDS * 8));
-        if (fs == 3) BT4L(3, 16, h->timeline.as<unsigned long long>());
-        else BT4L(4, 16, h->timeline.as<unsigned long long>());
-        h->timeline_valid = true;
-      } else if (h->gemm_variant >= 44 && h->gemm_variant <= 46 && fs == 4) {
-        if (h->gemm_variant == 44) BT4L(4, 4, nullptr);
-        else if (h->gemm_variant == 45) BT4L(4, 8, nullptr);
-        else BT4L(4, 12, nullptr);
-      } else
-#endif
-      if (fs == 3) {
-        BT4L(3, 0, nullptr);
-      } else {
-        BT4L(4, 0, nullptr);
-      }
-#undef BT4L
-      if (fslots)
-        fringe_copy_kernel<<<(unsigned)(fslots * 8), 256, 0, h->stream>>>(h->bt4_fringe.as<float>(), dout, ld, (int)M, (int)Nt, btM, btN, rag_m, rag_n);
-      PLDA_LAUNCH_CHECK(h);
-      if (ev1) PLDA_HIP(h, hipEventRecord(ev1, h->stream));
-      return PLDA_OK;
-    }
+      PLDA_TRY(launch_gemm_bt4(h, op, M, Nt, dout, ld));
+      break;
+    case GK_BT2:
+      h->last_kernel = "trials_gemm_bt2_kernel";
+      PLDA_TRY(launch_gemm_bt2(h, op, M, Nt, dout, ld));
+      break;
+    default:
+      h->last_kernel = "trials_gemm_kernel";
+      PLDA_TRY(launch_gemm_128<EPI>(h, op, M, Nt, dout, ld, shift, colsum, colsq));
   }
-  if (use_bt2) {
-    h->last_kernel = "trials_gemm_bt2_kernel";
-    const int pM = (int)ceil_div(btM, BPR), pN = (int)ceil_div(btN, BPC);
-    if (!h->bt2_attr_set) {
-      const void *fns[] = {reinterpret_cast<const void *>(&trials_gemm_bt2_kernel<0>), reinterpret_cast<const void *>(&trials_gemm_bt2_kernel<2>),
-#if PLDA_DIAG
-                           reinterpret_cast<const void *>(&trials_gemm_bt2_kernel<1>), reinterpret_cast<const void *>(&trials_gemm_bt2_kernel<3>),
-                           reinterpret_cast<const void *>(&trials_gemm_bt2_kernel<4>), reinterpret_cast<const void *>(&trials_gemm_bt2_kernel<8>),
-                           reinterpret_cast<const void *>(&trials_gemm_bt2_kernel<12>), reinterpret_cast<const void *>(&trials_gemm_bt2_kernel<16>),
-#endif
-      };
-      for (const void *f : fns) PLDA_HIP(h, hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, BT2_LDS));
-      h->bt2_attr_set = true;
-    }
-#define BT2L(MODE_, DBG_)                                                                                 \
-  trials_gemm_bt2_kernel<MODE_><<<256, 512, BT2_LDS, h->stream>>>(                                        \
-      h->s_Apk.as<f32x4>(), h->s_Bpk.as<f32x4>(), (unsigned)op.Mpad, (unsigned)op.Npad, op.KQ,            \
-      h->s_rpair.as<float2>(), h->s_cpair.as<float2>(), dout, ld, M, Nt, btM, btN, pN, pM * pN, DBG_)
-#if PLDA_DIAG
-    if (h->gemm_variant == 31 || h->gemm_variant == 33) {
-      // diagnostic: per-wave timestamps of workgroup 0 (plda_profile_timeline)
-      PLDA_HIP(h, h->timeline.reserve(TIMELINE_WORDS * 8));
-      PLDA_HIP(h, hipMemsetAsync(h->timeline.p, 0, TIMELINE_WORDS * 8, h->stream));
-      if (h->gemm_variant == 31) BT2L(1, h->timeline.as<unsigned long long>());
-      else BT2L(3, h->timeline.as<unsigned long long>());
-      h->timeline_valid = true;
-    } else if (h->gemm_variant == 37) {       // the product kernel + clock stamps of workgroup 0
-      PLDA_HIP(h, h->timeline.reserve(TIMELINE_WORDS * 8));
-      BT2L(16, h->timeline.as<unsigned long long>());
-      h->timeline_valid = true;
-    } else if (h->gemm_variant == 34) {       // bounding arms: timing only
-      BT2L(4, nullptr);
-    } else if (h->gemm_variant == 35) {
-      BT2L(8, nullptr);
-    } else if (h->gemm_variant == 36) {
-      BT2L(12, nullptr);
-    } else
-#endif
-    if (h->gemm_variant == 32) {              // the LDS-transpose epilogue (A/B arm with the same scores: test_gpu_bigtile.py)
-      BT2L(2, nullptr);
-    } else {
-      BT2L(0, nullptr);
-    }
-#undef BT2L
-    PLDA_LAUNCH_CHECK(h);
-    if (ev1) PLDA_HIP(h, hipEventRecord(ev1, h->stream));
-    return PLDA_OK;
-  }
-  // Kernel instantiations.  Variant 0 is the product configuration; the others are the
-  // tuning / ablation arms of scripts/gemm_sweep.py (PLDA_GEMM_VARIANT), kept because the
-  // numbers in DESIGN.md section 3 come from them.
-#define TG(NKQ_, EPI_, MINW_, ABL_)                                                                     \
-  trials_gemm_kernel<NKQ_, EPI_, MINW_, ABL_><<<(unsigned)grid, 256, 0, h->stream>>>(                   \
-      h->s_Apk.as<f32x4>(), h->s_Bpk.as<f32x4>(), op.Mpad, op.Npad, op.KQ, h->s_rbias.as<float>(),      \
-      h->s_rscale.as<float>(), h->s_cbias.as<float>(), dout,                                           \
-      ld, M, Nt, tilesM, tilesN, patchesN, (int)numPatches, shift, colsum, colsq)
-  h->last_kernel = "trials_gemm_kernel";
-#if PLDA_DIAG
-  constexpr int EPI_NOSTORE = (EPI == 0) ? 2 : EPI;
-#endif
-  switch (h->gemm_variant) {
-#if PLDA_DIAG   // tuning / ablation arms of scripts/gemm_sweep.py: diagnostic build only
-    case 1: TG(8, EPI, 2, 0); break;             // stage depth 32 k
-    case 2: TG(6, EPI, 2, 0); break;             // 24 k
-    case 3: TG(6, EPI, 3, 0); break;             // 24 k, 3 workgroups / CU
-    case 4: TG(4, EPI, 3, 0); break;             // 16 k, 3 workgroups / CU
-    case 9: TG(8, EPI_NOSTORE, 2, 0); break;     // ablation: no output stores
-    case 10: TG(8, EPI_NOSTORE, 2, 1); break;    // ... and no in-loop LDS reads
-    case 11: TG(8, EPI_NOSTORE, 2, 2); break;    // ... and no in-loop DMA
-    case 12: TG(8, EPI_NOSTORE, 2, 4); break;    // ... and no stage barriers
-#endif
-    default: TG(10, EPI, 2, 0); break;           // product: 40 k per stage, 2 workgroups / CU
-  }
-#undef TG
   PLDA_LAUNCH_CHECK(h);
   if (ev1) PLDA_HIP(h, hipEventRecord(ev1, h->stream));
   return PLDA_OK;

@@ -9,7 +9,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from plda_amd import MPlda
 
-variants = [int(v) for v in (sys.argv[1].split(",") if len(sys.argv) > 1 else "0,1,2,3,4".split(","))]
+variants = [int(v) for v in (sys.argv[1].split(",") if len(sys.argv) > 1 else "0,20,30,40".split(","))]   # product dispatch and the three kernels forced
 N = int(sys.argv[2]) if len(sys.argv) > 2 else 100000
 D = int(sys.argv[3]) if len(sys.argv) > 3 else 200
 rounds = int(sys.argv[4]) if len(sys.argv) > 4 else 5

@@ -362,7 +362,7 @@ def test_znorm_lookup_for_many_models_matches_the_per_key_lookup(oracle):
     np.testing.assert_allclose(got2[599], (raw[599] - zm2[keys[599]]) / zs2[keys[599]], rtol=2e-5, atol=2e-5)
 
 
-DIAG_ONLY_VARIANTS = [1, 2, 3, 4, 9, 10, 11, 12, 31, 33, 34, 35, 36, 37, 41, 44, 45, 46, 47, 54, 58, 62, 63]
+DIAG_ONLY_VARIANTS = [31, 34, 35, 36, 37, 41, 44, 45, 46, 47, 54, 58, 62, 63]
 
 
 @pytest.mark.parametrize("variant", DIAG_ONLY_VARIANTS)
@@ -396,6 +396,35 @@ def test_removed_transform_arms_are_refused(monkeypatch, variant):
             monkeypatch.setenv("PLDA_TRANSFORM_VARIANT", ok)
             MPlda(0, diag=diag)
     monkeypatch.delenv("PLDA_TRANSFORM_VARIANT")
+    MPlda(0)                                            # (and nothing sticks)
+
+
+@pytest.mark.parametrize("variant", ["1", "2", "3", "4", "9", "10", "11", "12", "32", "33", "50", "5"])
+def test_removed_gemm_arms_are_refused(monkeypatch, variant):
+    """PLDA_GEMM_VARIANT names one row of the library's table of arms.  The numbers whose A/B question is answered and whose
+    arms are gone (1-4, 9-12: stage depths and ablations of the 128 x 128 kernel, some with GARBAGE scores and rc = 0; 32 / 33:
+    the LDS-transposing epilogue; 50: the dispatch thresholds of rounds 4-5a) and a number nobody ever assigned (5) are refused
+    by both libraries with a message that names the value -- a script that still sets one must fail instead of timing the
+    product kernel under a dead arm's name.  The product's and the forcing arms create a handle in both, and PLDA_MIXED_VARIANT
+    is 0, 1 or empty.  (Creation only: no kernel runs.)"""
+    from plda_amd import MPlda, _native
+    from plda_amd._native import PldaError
+    diags = [False, True] if os.path.exists(_native.SO_DIAG_PATH) else [False]
+    for diag in diags:
+        monkeypatch.setenv("PLDA_GEMM_VARIANT", variant)
+        with pytest.raises(PldaError, match=r"PLDA_GEMM_VARIANT=%s: no such arm exists" % variant):
+            MPlda(0, diag=diag)
+        for ok in ("", "0", "20", "30", "40", "48", "49"):
+            monkeypatch.setenv("PLDA_GEMM_VARIANT", ok)
+            MPlda(0, diag=diag)
+        monkeypatch.delenv("PLDA_GEMM_VARIANT")
+        monkeypatch.setenv("PLDA_MIXED_VARIANT", "20")
+        with pytest.raises(PldaError, match="PLDA_MIXED_VARIANT=20 "):
+            MPlda(0, diag=diag)
+        for ok in ("", "0", "1"):
+            monkeypatch.setenv("PLDA_MIXED_VARIANT", ok)
+            MPlda(0, diag=diag)
+        monkeypatch.delenv("PLDA_MIXED_VARIANT")
     MPlda(0)                                            # (and nothing sticks)
 
 

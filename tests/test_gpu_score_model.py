@@ -11,7 +11,7 @@ the host; a case passes when
 
 Each case also asserts the kernel and depth that ran (score_last_kernel / score_last_shape), so a dispatch
 change cannot quietly make it test something else.  Covered: the library's arms PLDA_GEMM_VARIANT 0, 20, 30,
-32, 40, 48, 49, 50; the host and device entries (ld > Nt), prepared test sides, the sharded entries;
+40, 48, 49; the host and device entries (ld > Nt), prepared test sides, the sharded entries;
 PLDA_PREP_VARIANT 1-3 and PLDA_MIXED_VARIANT=1; depths 1 .. 2048, ragged rows and columns, uniform, bucketed
 and depth-2D counts, z-norm (with zstd == 0 rows), extreme psi, a targetdim-truncated model, near-cancelling
 scores and a row whose operands and partial sums are all subnormal.  The opt-in bf16x3 arm is held to its
@@ -62,12 +62,11 @@ def _expect_kernel(variant, M, Nt, Kg, dtype=None):
     tiles = btM * btN
     nst = ((Kg // 4 >> 1) + 3) >> 2
     full = tiles >= 0.85 * (-(-btM // 4) * 4) * (-(-btN // 8) * 8)
-    old = variant == 50
-    big = tiles >= (1024 if old else 1700)
-    big2 = tiles >= 1024 if old else (tiles >= 1700 or (tiles >= 512 and full))
-    if nst >= 3 and (variant in (40, 48, 49) or (variant in (0, 50) and big)):
+    big = tiles >= 1700
+    big2 = tiles >= 1700 or (tiles >= 512 and full)
+    if nst >= 3 and (variant in (40, 48, 49) or (variant == 0 and big)):
         return "trials_gemm_bt4_kernel"
-    if variant in (30, 32) or (variant in (0, 50) and big2):
+    if variant == 30 or (variant == 0 and big2):
         return "trials_gemm_bt2_kernel"
     return "trials_gemm_kernel"
 
@@ -177,7 +176,7 @@ FORMS = {
 }
 
 
-@pytest.mark.parametrize("variant", [0, 20, 30, 32, 40, 48, 49, 50])
+@pytest.mark.parametrize("variant", [0, 20, 30, 40, 48, 49])
 @pytest.mark.parametrize("form", list(FORMS))
 def test_arms(monkeypatch, variant, form):
     d, vals, zn = FORMS[form]

@@ -158,6 +158,10 @@ def test_transform_groups_and_norm_on_poisoned_scratch(monkeypatch, oracle, d):
 
 
 # -------------------------------------------------------------------------------------------------------------- score
+SCORE_ENV_KERNEL = {("PLDA_GEMM_VARIANT", "20"): "trials_gemm_kernel", ("PLDA_GEMM_VARIANT", "40"): "trials_gemm_bt4_kernel",
+                    ("PLDA_MIXED_VARIANT", "1"): "trials_gemm_kernel", ("PLDA_SCORE_DTYPE", "bf16x3"): "trials_gemm_bf16x3_kernel"}
+
+
 @pytest.mark.parametrize("d,m,nt,counts,znorm,env", [
     (51, 333, 517, "uniform", False, {}),
     (51, 333, 517, "mixed", True, {}),
@@ -165,15 +169,19 @@ def test_transform_groups_and_norm_on_poisoned_scratch(monkeypatch, oracle, d):
     (130, 1001, 2003, "mixed", False, {}),
     (63, 4099, 4355, "uniform", False, {}),                             # large enough for the one-wave-per-SIMD tiles
     (63, 4099, 4355, "mixed", True, {}),
-    (94, 700, 1299, "mixed", True, {"PLDA_MIXED_VARIANT": "20"}),
-    (94, 700, 1299, "mixed", False, {"PLDA_MIXED_VARIANT": "40"}),
+    (94, 700, 1299, "mixed", True, {"PLDA_GEMM_VARIANT": "20"}),
+    (94, 700, 1299, "mixed", False, {"PLDA_GEMM_VARIANT": "40"}),
     (94, 700, 1299, "mixed", True, {"PLDA_MIXED_VARIANT": "1"}),
     (77, 1001, 2003, "uniform", True, {"PLDA_SCORE_DTYPE": "bf16x3"}),
     (77, 1001, 2003, "mixed", False, {"PLDA_SCORE_DTYPE": "bf16x3"}),
 ])
 def test_score_matrix_on_poisoned_scratch(monkeypatch, oracle, d, m, nt, counts, znorm, env):
     """The trials GEMM on device operands: M and Nt not multiples of 16 or 256, D not a multiple of 4, uniform and mixed
-    enrol counts (bucketed form, its arms 20 / 40 and the depth-2D arm 1), z-normalised or not, fp32 and bf16x3."""
+    enrol counts (the bucketed form by shape and under the forcing arms PLDA_GEMM_VARIANT 20 / 40, and the depth-2D arm
+    PLDA_MIXED_VARIANT=1), z-normalised or not, fp32 and bf16x3.  A case that sets a switch also asserts the kernel that ran,
+    so that it cannot test something other than its name: at d = 94 with six distinct counts the bucketed depth is 104 (13
+    steps of 8 k, 4 stages >= 3), so arm 40 does run the one-wave-per-SIMD kernel at 700 x 1299; 3 x 6 tiles of 256 x 256 are
+    the 128 x 128 kernel's by shape."""
     import torch
     dev = torch.device("cuda", 0)
     mean, T, psi = _model(d, d + m)
@@ -192,6 +200,8 @@ def test_score_matrix_on_poisoned_scratch(monkeypatch, oracle, d, m, nt, counts,
         eng.score_matrix_dev(dU.data_ptr(), dn.data_ptr() if counts == "mixed" else None, 0 if counts == "mixed" else 3, m,
                              dV.data_ptr(), nt, S.data_ptr(), nt, dzm.data_ptr() if znorm else None, dzs.data_ptr() if znorm else None)
         eng.synchronize()
+        if env:
+            assert eng.score_last_kernel() == SCORE_ENV_KERNEL[next(iter(env.items()))]
         return dict(S=S.cpu().numpy())
 
     a, _ = _twice(monkeypatch, case, env)
