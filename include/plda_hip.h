@@ -1223,8 +1223,8 @@ int plda_project_rows(plda_handle *h, const double *X, int64_t R, int32_t Din, d
  *   plda_der_sweep_dev   the merge record, ref, dur (nullable) and the outputs in HBM; offsets [R + 1], thresholds [Q] and
  *                        min_clusters [R] (nullable: 1 everywhere) are HOST arrays.
  *   plda_der_sweep       the same with everything in host memory.
- * OUT OF SCOPE, each on purpose: overlapped speech (a segment has one reference and one hypothesis label); a forgiveness
- * collar; the Jaccard error rate (JER); a time-based restatement of md-eval (the unit is the caller's segment). ---- */
+ * OUT OF SCOPE, each on purpose: the Jaccard error rate (JER).  (Overlapped reference speech, a forgiveness collar and
+ * time-based scoring are the next section; here a segment has one reference and one hypothesis label.) ---- */
 #define PLDA_DER_MAX_REF 64
 int plda_der_plan(plda_handle *h, int64_t Sr, int64_t Sh, int32_t out[3]);
 int plda_der_dev(plda_handle *h, const int32_t *dref, const int32_t *dhyp, const int32_t *ddur, const int64_t *offsets, int64_t R,
@@ -1237,6 +1237,94 @@ int plda_der_sweep_dev(plda_handle *h, const int32_t *dmerge_a, const int32_t *d
 int plda_der_sweep(plda_handle *h, const int32_t *merge_a, const int32_t *merge_b, const double *merge_cost, const int64_t *offsets,
                    int64_t R, const int32_t *ref, const int32_t *dur, const double *thresholds, int64_t Q, const int32_t *min_clusters,
                    int64_t *counts, int32_t *n_clusters);
+
+/* ---- time-based diarisation error rate (K20; csrc/der_time.hip, the solve of csrc/der.hip): DER over TIME, with overlapped
+ * reference speech, a forgiveness collar and UEM scoring regions.  This is md-eval's definition restated on integer ticks,
+ * with the speaker mapping optimal over the scored region.  Parity with md-eval is UNPINNED: neither md-eval, dscore nor
+ * pyannote.metrics is on the build machine; tests/der_time_model.py holds the two host models (tick by tick, and by intervals).
+ *
+ * All times are integer TICKS (the tick is the caller's; plda_amd/rttm.py uses 0.01 s).  Every interval is half-open,
+ * [start, start + dur).  Per recording r:
+ *   REFERENCE TURNS (turn_start, turn_dur, turn_spk), int32: turns turn_off[r] .. turn_off[r+1], in any order, 0 <= turn_spk <
+ *     PLDA_DER_MAX_REF.  Two or more reference speakers may talk at once.  Turns of the SAME speaker must be disjoint
+ *     (abutting is allowed).  A turn with dur = 0 is ignored.  A recording may have no turn.
+ *   HYPOTHESIS SEGMENTS (seg_start, seg_dur, hyp), int32: segments offsets[r] .. offsets[r+1] (1 <= N <= PLDA_AHC_MAX: the rows
+ *     the clustering labels), in any order, pairwise disjoint in time: at most one hypothesis speaker talks at any tick.
+ *     hyp = -1 is non-speech, otherwise 0 <= hyp < PLDA_AHC_MAX; dur = 0 is ignored.
+ *   UEM (nullable): scored intervals (uem_start, uem_dur), intervals uem_off[r] .. uem_off[r+1]; they may overlap each other,
+ *     a tick is inside if any interval covers it.  uem_off NULL (then uem_start and uem_dur must be NULL): every tick is scored.
+ *   collar c >= 0 ticks: every turn boundary b (start and end of every reference turn AS GIVEN, abutting turns included)
+ *     removes [b - c, b + c) from scoring.  Zones may overlap each other and may reach below tick 0.
+ *   flags: bit 0, PLDA_DER_SKIP_OVERLAP (md-eval's -1), additionally removes every tick with more than one reference speaker.
+ * For a scored tick t: Rset(t) = the reference speakers talking at t, nref = |Rset|; nhyp = 0 or 1, j(t) the hypothesis label
+ * when nhyp = 1.  COUNTS, all int64, in the layout of plda_der:
+ *   speech    = sum of nref
+ *   miss      = sum of max(0, nref - nhyp)
+ *   fa        = sum of max(0, nhyp - nref)
+ *   C[i][j]   = #{scored t : i in Rset(t), j = j(t)}
+ *   correct   = the maximum of sum_i C[i][m(i)] over all one-to-one partial maps m
+ *   confusion = sum of min(nref, nhyp) - correct
+ * counts int64 [R, 4] = {speech, miss, fa, confusion}; DER is the caller's division.  map (nullable) int32 [R, 64] follows the
+ * rules of plda_der's.  EXAMPLE: ref A [0, 10), B [5, 15); hyp X [0, 15).  Collar 0: {20, 5, 0, 5}.  Collar 1 removes [-1, 1),
+ * [4, 6), [9, 11), [14, 16): {12, 3, 0, 3}.
+ *
+ * SWEEP: as plda_der_sweep, the hypothesis label of segment t being the slot of the replayed merge prefix (no hypothesis
+ * non-speech); counts [Q, R, 4], n_clusters [Q, R] (= N - merges, every segment counted, scored or not).  The time line is cut
+ * once per recording; all Q thresholds read the same atoms.
+ *
+ * LIMITS: N <= PLDA_AHC_MAX, PLDA_DER_MAX_TURNS turns and PLDA_DER_MAX_UEM UEM intervals per recording; 0 <= start, start +
+ * dur <= 2^30; 0 <= collar <= 2^20.
+ * ERRORS, all PLDA_E_INVAL, none writes an output.  On the host, before any device work: an offset array (offsets, turn_off,
+ * uem_off) that does not ascend from 0 or exceeds its limit, collar or flags out of range, the sweep's Q, thresholds,
+ * min_clusters as in plda_der_sweep, a NULL array.  On the device, counted, the two counts in plda_last_error: ENTRIES with a
+ * label or a time out of range; EVENTS that meet a state the contract excludes -- a turn that starts inside another turn of
+ * its speaker (its start finds the speaker talking, and a later end finds them silent: one violation may be counted at more
+ * than one event), a hypothesis segment that starts while another is open.  A record that is not full: as plda_der_sweep.
+ *
+ * METHOD.  der_atoms_kernel, one workgroup per recording: one 64-bit key per boundary -- 2 per turn, 4 more per turn when collar
+ * > 0, 2 per segment, 2 per UEM interval, ends before starts on the same tick -- sorted by a bitonic network, in LDS up to
+ * 16384 key slots, above that in handle scratch (8 bytes a slot, slots rounded up to a power of two, at most 1 MiB per
+ * recording, launches grouped under the budget of plda_der's scratch, PLDA_DER_SCRATCH_BYTES).  Scans over the sorted events
+ * give every atom (a maximal run of ticks without an event) its 64-bit reference mask (an XOR scan: same-speaker turns are
+ * disjoint, and the same prefix checks that), collar, UEM and hypothesis depth (+-1 scans) and hypothesis segment (a max
+ * scan).  The scored atoms are compacted in time order into handle scratch (ticks, mask, segment index: 16 bytes each, at
+ * most one per event); plda_der's solve then fills C from atoms (an atom adds its ticks to C[i][j] for every speaker i of
+ * its mask) and runs the same assignment, in the same two classes.  Every sum is an integer: the counts do not depend on the
+ * grid, the batch, the launch grouping or the run.  All scratch belongs to the handle and is freed by plda_destroy.
+ *
+ *   plda_der_timed_plan        out[0] = the event-sort class of a recording of n_turns, n_seg, n_uem at this collar (0 LDS,
+ *                              1 scratch), out[1] = its scratch bytes (0 in the LDS class), out[2] = the largest event-slot
+ *                              count of the LDS class.
+ *   plda_der_timed_dev         the turn, segment and UEM arrays and the outputs in HBM; turn_off, offsets, uem_off [R + 1] are
+ *                              HOST arrays.  Synchronises the handle's stream twice.
+ *   plda_der_timed             the same with everything in host memory.
+ *   plda_der_timed_sweep_dev   the merge record, the arrays and the outputs in HBM; the three offset arrays, thresholds [Q] and
+ *                              min_clusters [R] (nullable) are HOST arrays.
+ *   plda_der_timed_sweep       the same with everything in host memory.
+ * OUT OF SCOPE, each on purpose: overlapping HYPOTHESIS speakers (that needs overlap output from VBx first); JER; per-speaker
+ * error breakdowns; word-level or SAD-only scoring; several workgroups on one recording. ---- */
+#define PLDA_DER_MAX_TURNS 16384
+#define PLDA_DER_MAX_UEM 1024
+#define PLDA_DER_SKIP_OVERLAP 1
+int plda_der_timed_plan(plda_handle *h, int64_t n_turns, int64_t n_seg, int64_t n_uem, int32_t collar, int32_t out[3]);
+int plda_der_timed_dev(plda_handle *h, const int32_t *dturn_start, const int32_t *dturn_dur, const int32_t *dturn_spk,
+                       const int64_t *turn_off, const int32_t *dseg_start, const int32_t *dseg_dur, const int32_t *dhyp,
+                       const int64_t *offsets, int64_t R, const int32_t *duem_start, const int32_t *duem_dur, const int64_t *uem_off,
+                       int32_t collar, int32_t flags, int64_t *dcounts, int32_t *dmap);
+int plda_der_timed(plda_handle *h, const int32_t *turn_start, const int32_t *turn_dur, const int32_t *turn_spk, const int64_t *turn_off,
+                   const int32_t *seg_start, const int32_t *seg_dur, const int32_t *hyp, const int64_t *offsets, int64_t R,
+                   const int32_t *uem_start, const int32_t *uem_dur, const int64_t *uem_off, int32_t collar, int32_t flags,
+                   int64_t *counts, int32_t *map);
+int plda_der_timed_sweep_dev(plda_handle *h, const int32_t *dmerge_a, const int32_t *dmerge_b, const double *dmerge_cost,
+                             const int32_t *dturn_start, const int32_t *dturn_dur, const int32_t *dturn_spk, const int64_t *turn_off,
+                             const int32_t *dseg_start, const int32_t *dseg_dur, const int64_t *offsets, int64_t R,
+                             const int32_t *duem_start, const int32_t *duem_dur, const int64_t *uem_off, int32_t collar, int32_t flags,
+                             const double *thresholds, int64_t Q, const int32_t *min_clusters, int64_t *dcounts, int32_t *dn_clusters);
+int plda_der_timed_sweep(plda_handle *h, const int32_t *merge_a, const int32_t *merge_b, const double *merge_cost,
+                         const int32_t *turn_start, const int32_t *turn_dur, const int32_t *turn_spk, const int64_t *turn_off,
+                         const int32_t *seg_start, const int32_t *seg_dur, const int64_t *offsets, int64_t R, const int32_t *uem_start,
+                         const int32_t *uem_dur, const int64_t *uem_off, int32_t collar, int32_t flags, const double *thresholds,
+                         int64_t Q, const int32_t *min_clusters, int64_t *counts, int32_t *n_clusters);
 
 /* ---- embedding chain (K18; csrc/embed.hip): what every x-vector / i-vector recipe runs between the extractor and a Gaussian
  * PLDA -- Kaldi's ivector-subtract-global-mean | transform-vec | ivector-normalize-length, the VBx recipe's

@@ -113,12 +113,18 @@ class PLDA(object):
         the optimal speaker mapping; plda_amd/der.py.  Returns a DerResult (counts, der, total[, map])."""
         return self._instance.der(ref, hyp, offsets, dur, return_map)
 
-    def tune_threshold(self, x, offsets, ref, thresholds, dur=None, target_energy=None):
+    def der_timed(self, turns, seg_start, seg_dur, hyp, offsets, collar=0, uem=None, skip_overlap=False, return_map=False):
+        """Time-based DER (md-eval's definition on integer ticks): overlapped reference turns, a collar, UEM regions;
+        plda_amd/der.py: der_timed.  Returns a DerResult."""
+        return self._instance.der_timed(turns, seg_start, seg_dur, hyp, offsets, collar, uem, skip_overlap, return_map)
+
+    def tune_threshold(self, x, offsets, ref, thresholds, dur=None, target_energy=None, **timed):
         """The clustering threshold of the lowest pooled DER on a development set: one clustering (behind the per-recording PCA
-        when target_energy is given), one sweep of its merge record.  Returns (threshold, SweepResult); plda_amd/der.py."""
-        if target_energy is None:
-            return self._instance.tune_threshold(x, offsets, ref, thresholds, dur)
-        return self._instance.tune_threshold(x, offsets, ref, thresholds, dur, target_energy=target_energy)
+        when target_energy is given), one sweep of its merge record.  Returns (threshold, SweepResult); plda_amd/der.py.
+        With turns=, seg_start=, seg_dur= (and collar=, uem=, skip_overlap=) and ref=None the sweep is the time-based one."""
+        if target_energy is not None:
+            timed["target_energy"] = target_energy
+        return self._instance.tune_threshold(x, offsets, ref, thresholds, dur, **timed)
 
     def transform_array(self, xbar, num_examples=1):
         return self._instance.transform_array(xbar, num_examples)

@@ -12,6 +12,7 @@ Layout (only what the hot path needs):
   identify.py rank-N identification rates and the CMC curve from the ids of MPlda.top_n (csrc/topn.hip); pure NumPy
   diarize.py  speaker clustering: batched average-linkage AHC on score blocks (csrc/ahc.hip), cut() in pure NumPy; VBx resegmentation (csrc/vbx.hip); dense scoring in every recording's PCA subspace (csrc/dense_pca.hip)
   der.py      diarisation error rate under the optimal speaker mapping, and the sweep of one merge record over thresholds (csrc/der.hip)
+              and its time-based form: overlapped reference speech, collar, UEM (csrc/der_time.hip)
   rttm.py     RTTM files and per-segment reference labels from reference turns; pure Python / NumPy
 """
 from .libplda import MPlda  # noqa: F401

@@ -157,6 +157,11 @@ SIGNATURES = {
     "plda_der": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
     "plda_der_sweep_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
     "plda_der_sweep": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "plda_der_timed_plan": (C.c_int, [_vp, _i64, _i64, _i64, _i32, _vp]),
+    "plda_der_timed_dev": (C.c_int, [_vp] * 9 + [_i64, _vp, _vp, _vp, _i32, _i32, _vp, _vp]),
+    "plda_der_timed": (C.c_int, [_vp] * 9 + [_i64, _vp, _vp, _vp, _i32, _i32, _vp, _vp]),
+    "plda_der_timed_sweep_dev": (C.c_int, [_vp] * 11 + [_i64, _vp, _vp, _vp, _i32, _i32, _vp, _i64, _vp, _vp, _vp]),
+    "plda_der_timed_sweep": (C.c_int, [_vp] * 11 + [_i64, _vp, _vp, _vp, _i32, _i32, _vp, _i64, _vp, _vp, _vp]),
     "plda_vbx_plan": (C.c_int, [_vp, _i64, _i64, _i64, _vp]),
     "plda_vbx_dev": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _f64, _f64, _f64, _f64, _i64, _f64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "plda_vbx": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _f64, _f64, _f64, _f64, _i64, _f64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

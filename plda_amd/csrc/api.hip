@@ -2122,6 +2122,84 @@ int plda_der_sweep(plda_handle *h, const int32_t *merge_a, const int32_t *merge_
   });
 }
 
+// ---------------------------------------------------------------- time-based diarisation error rate (der_time.hip)
+int plda_der_timed_plan(plda_handle *h, int64_t n_turns, int64_t n_seg, int64_t n_uem, int32_t collar, int32_t out[3]) {
+  return entry(h, "plda_der_timed_plan", [&] { return der_timed_plan(h, n_turns, n_seg, n_uem, collar, out); });
+}
+
+int plda_der_timed_dev(plda_handle *h, const int32_t *dturn_start, const int32_t *dturn_dur, const int32_t *dturn_spk,
+                       const int64_t *turn_off, const int32_t *dseg_start, const int32_t *dseg_dur, const int32_t *dhyp,
+                       const int64_t *offsets, int64_t R, const int32_t *duem_start, const int32_t *duem_dur, const int64_t *uem_off,
+                       int32_t collar, int32_t flags, int64_t *dcounts, int32_t *dmap) {
+  return device_entry(h, "plda_der_timed_dev", [&] {
+    const DerTimedArgs a{dturn_start, dturn_dur, dturn_spk, turn_off, dseg_start, dseg_dur, dhyp, offsets, R, duem_start, duem_dur, uem_off,
+                         collar, flags, nullptr, nullptr, nullptr, nullptr, 0, nullptr, dcounts, nullptr, dmap};
+    return der_timed_device(h, "der_timed", a, false);
+  });
+}
+
+namespace {
+// the host form of both time-based calls: the check, every array uploaded, the outputs copied back
+int der_timed_host(plda_handle *h, const char *fn, DerTimedArgs a, bool sweep) {
+  PLDA_TRY(der_timed_validate(h, fn, a, sweep));
+  PLDA_TRY(set_device(h));
+  const int64_t T = a.offsets[a.R], R = a.R, nt = a.turn_off[R], nu = a.uem_off ? a.uem_off[R] : 0;
+  Staged st(h);
+  int64_t *counts = a.counts;
+  int32_t *ncl = a.n_clusters, *map = a.map;
+  PLDA_TRY(st.in(a.tstart, (size_t)nt, &a.tstart));
+  PLDA_TRY(st.in(a.tdur, (size_t)nt, &a.tdur));
+  PLDA_TRY(st.in(a.tspk, (size_t)nt, &a.tspk));
+  PLDA_TRY(st.in(a.sstart, (size_t)T, &a.sstart));
+  PLDA_TRY(st.in(a.sdur, (size_t)T, &a.sdur));
+  PLDA_TRY(st.in(a.hyp, (size_t)T, &a.hyp));
+  PLDA_TRY(st.in(a.ustart, (size_t)nu, &a.ustart));
+  PLDA_TRY(st.in(a.udur, (size_t)nu, &a.udur));
+  PLDA_TRY(st.in(a.ma, (size_t)(T - R), &a.ma));          // (all three may be NULL when no recording has a merge: T == R)
+  PLDA_TRY(st.in(a.mb, (size_t)(T - R), &a.mb));
+  PLDA_TRY(st.in(a.mc, (size_t)(T - R), &a.mc));
+  PLDA_TRY(st.out(counts, (size_t)(sweep ? a.Q : 1) * R * 4, &a.counts));
+  PLDA_TRY(st.out(ncl, (size_t)(sweep ? a.Q * R : 0), &a.n_clusters));
+  PLDA_TRY(st.out(map, (size_t)R * PLDA_DER_MAX_REF, &a.map));
+  return st.finish(der_timed_device(h, fn, a, sweep));
+}
+}  // namespace
+
+int plda_der_timed(plda_handle *h, const int32_t *turn_start, const int32_t *turn_dur, const int32_t *turn_spk, const int64_t *turn_off,
+                   const int32_t *seg_start, const int32_t *seg_dur, const int32_t *hyp, const int64_t *offsets, int64_t R,
+                   const int32_t *uem_start, const int32_t *uem_dur, const int64_t *uem_off, int32_t collar, int32_t flags,
+                   int64_t *counts, int32_t *map) {
+  return entry(h, "plda_der_timed", [&] {
+    const DerTimedArgs a{turn_start, turn_dur, turn_spk, turn_off, seg_start, seg_dur, hyp, offsets, R, uem_start, uem_dur, uem_off,
+                         collar, flags, nullptr, nullptr, nullptr, nullptr, 0, nullptr, counts, nullptr, map};
+    return der_timed_host(h, "der_timed", a, false);
+  });
+}
+
+int plda_der_timed_sweep_dev(plda_handle *h, const int32_t *dmerge_a, const int32_t *dmerge_b, const double *dmerge_cost,
+                             const int32_t *dturn_start, const int32_t *dturn_dur, const int32_t *dturn_spk, const int64_t *turn_off,
+                             const int32_t *dseg_start, const int32_t *dseg_dur, const int64_t *offsets, int64_t R,
+                             const int32_t *duem_start, const int32_t *duem_dur, const int64_t *uem_off, int32_t collar, int32_t flags,
+                             const double *thresholds, int64_t Q, const int32_t *min_clusters, int64_t *dcounts, int32_t *dn_clusters) {
+  return device_entry(h, "plda_der_timed_sweep_dev", [&] {
+    const DerTimedArgs a{dturn_start, dturn_dur, dturn_spk, turn_off, dseg_start, dseg_dur, nullptr, offsets, R, duem_start, duem_dur,
+                         uem_off, collar, flags, dmerge_a, dmerge_b, dmerge_cost, thresholds, Q, min_clusters, dcounts, dn_clusters, nullptr};
+    return der_timed_device(h, "der_timed_sweep", a, true);
+  });
+}
+
+int plda_der_timed_sweep(plda_handle *h, const int32_t *merge_a, const int32_t *merge_b, const double *merge_cost,
+                         const int32_t *turn_start, const int32_t *turn_dur, const int32_t *turn_spk, const int64_t *turn_off,
+                         const int32_t *seg_start, const int32_t *seg_dur, const int64_t *offsets, int64_t R, const int32_t *uem_start,
+                         const int32_t *uem_dur, const int64_t *uem_off, int32_t collar, int32_t flags, const double *thresholds,
+                         int64_t Q, const int32_t *min_clusters, int64_t *counts, int32_t *n_clusters) {
+  return entry(h, "plda_der_timed_sweep", [&] {
+    const DerTimedArgs a{turn_start, turn_dur, turn_spk, turn_off, seg_start, seg_dur, nullptr, offsets, R, uem_start, uem_dur, uem_off,
+                         collar, flags, merge_a, merge_b, merge_cost, thresholds, Q, min_clusters, counts, n_clusters, nullptr};
+    return der_timed_host(h, "der_timed_sweep", a, true);
+  });
+}
+
 // ---------------------------------------------------------------- VBx resegmentation (vbx.hip)
 int plda_vbx_plan(plda_handle *h, int64_t T, int64_t S, int64_t D, int32_t out[3]) {
   return entry(h, "plda_vbx_plan", [&] { return vbx_plan(h, T, S, D, out); });

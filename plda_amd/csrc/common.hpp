@@ -349,6 +349,8 @@ struct plda_handle {
   plda::DevBuf der_tab;          // the launch table of a call (one entry per recording and threshold)
   plda::DevBuf der_stat;         // the call's two reject counters, its offsets and thresholds, then Sr, Sh / the prefix lengths
   int64_t der_scratch_bytes = 0; // PLDA_DER_SCRATCH_BYTES: the scratch one launch may take (0: 256 MiB)
+  plda::DevBuf der_atoms;        // der_time.hip: the call's violation counter, launch table, per-recording records and scored atoms (one layout list)
+  plda::DevBuf der_events;       // der_time.hip: the event keys of the scratch-class recordings of one launch (under the same budget)
 
   // ---- embedding chain (embed.hip): host mirror (plda_embed_get returns it bit for bit) + device copies ----
   bool em_has = false;
@@ -572,6 +574,28 @@ int der_device(plda_handle *h, const int32_t *dref, const int32_t *dhyp, const i
 int der_sweep_device(plda_handle *h, const int32_t *dma, const int32_t *dmb, const double *dmc, const int64_t *offsets, int64_t R,
                      const int32_t *dref, const int32_t *ddur, const double *thresholds, int64_t Q, const int32_t *minc,
                      int64_t *dcounts, int32_t *dn_clusters);
+
+// ---- der_time.hip (time-based DER: overlapped reference speech, collar, UEM; every *_off array is a HOST array) ----
+// one recording's scored atoms, as der_atoms_kernel leaves them and der.hip's solve reads them
+struct DerTimedRec { long long aoff; int natoms, sh; unsigned long long umask; };   // first atom; atoms; distinct hyp labels; union of masks
+struct DerTimedDev { const DerTimedRec *recs; const int *ticks; const int *seg; const unsigned long long *mask; };
+// the arguments of plda_der_timed* (sweep: ma, mb, mc, thresholds, Q, minc, n_clusters; otherwise hyp, map)
+struct DerTimedArgs {
+  const int32_t *tstart, *tdur, *tspk; const int64_t *turn_off;
+  const int32_t *sstart, *sdur, *hyp; const int64_t *offsets; int64_t R;
+  const int32_t *ustart, *udur; const int64_t *uem_off;
+  int32_t collar, flags;
+  const int32_t *ma, *mb; const double *mc; const double *thresholds; int64_t Q; const int32_t *minc;
+  int64_t *counts; int32_t *n_clusters, *map;
+};
+int der_timed_plan(plda_handle *h, int64_t n_turns, int64_t n_seg, int64_t n_uem, int32_t collar, int32_t *out);
+// the host-side argument check (pointers are only compared with NULL; the host forms run it before they allocate or upload)
+int der_timed_validate(plda_handle *h, const char *fn, const DerTimedArgs &a, bool sweep);
+int der_timed_device(plda_handle *h, const char *fn, const DerTimedArgs &a, bool sweep);
+// der.hip: the solves behind the atoms (Q = 0: against dhyp; Q >= 1: the sweep of the merge record)
+int der_timed_solve(plda_handle *h, const char *fn, const DerTimedRec *recs, const DerTimedDev &td, const int32_t *dhyp,
+                    const int32_t *dma, const int32_t *dmb, const double *dmc, const int64_t *offsets, int64_t R, const double *thresholds,
+                    int64_t Q, const int32_t *minc, int64_t *dcounts, int32_t *dn_clusters, int32_t *dmap);
 
 // ---- vbx.hip (VBx resegmentation: a batched Bayesian HMM on PLDA vectors; offsets / gamma_off / pi_off are HOST arrays) ----
 int vbx_plan(plda_handle *h, int64_t T, int64_t S, int64_t D, int32_t *out);

@@ -15,6 +15,9 @@
 //                       hypothesis with fewer speakers than the reference);  <HBM = true> the matrix in handle scratch.
 //                       <SWEEP> the hypothesis labels are the slots of the replayed merge prefix.
 //                       Both keep the column state (potential, slack, predecessor, owner, flag, label) in LDS.
+//   der_solve_timed_kernel  the same body (der_solve_body<HBM, SWEEP, ATOMS = true>) on the scored atoms that der_time.hip cuts
+//                       from reference turns, hypothesis segments, collar and UEM (K20): an atom of `ticks` ticks adds them
+//                       to C[i][j] for every reference speaker i of its 64-bit mask
 //
 // One workgroup of der_solve_kernel: (1) the labels present, as bit sets (64 bits of reference, 4096 of hypothesis), give
 // the compact numbering by prefix population counts; (2) the matrix is zeroed and filled with integer atomics, the four
@@ -151,12 +154,15 @@ template <> struct DerMat<true> {
   }
 };
 
-template <bool HBM, bool SWEEP>
-__global__ __launch_bounds__(DER_T) void der_solve_kernel(const int *__restrict__ ref, const int *__restrict__ hyp,
-                                                          const int *__restrict__ dur, const int *__restrict__ ma,
-                                                          const int *__restrict__ mb, const DerRec *__restrict__ tab,
-                                                          long long *scratch, long long *__restrict__ counts,
-                                                          int *__restrict__ n_clusters, int *__restrict__ map) {
+// One workgroup's solve.  ATOMS = false: the segment form (ref, hyp, dur per segment).  ATOMS = true: the time-based form
+// (der_time.hip): the reference side is the scored atoms of the recording (ticks, 64-bit reference mask, segment index or -1)
+// and the union of their masks; the hypothesis label of an atom is that of its segment (SWEEP: the slot of its segment).
+template <bool HBM, bool SWEEP, bool ATOMS>
+__device__ __forceinline__ void der_solve_body(const int *__restrict__ ref, const int *__restrict__ hyp,
+                                               const int *__restrict__ dur, const int *__restrict__ ma,
+                                               const int *__restrict__ mb, const DerRec *__restrict__ tab,
+                                               long long *scratch, long long *__restrict__ counts,
+                                               int *__restrict__ n_clusters, int *__restrict__ map, const DerTimedDev &td) {
   extern __shared__ long long der_smem[];
   const DerRec rc = tab[blockIdx.x];
   const int n = rc.n, w = rc.w, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -185,8 +191,9 @@ __global__ __launch_bounds__(DER_T) void der_solve_kernel(const int *__restrict_
   int *red_i = p4; p4 += DER_W;
   int *parent = p4;
 
-  const int *__restrict__ rf = ref + rc.off;
-  const int *__restrict__ dr = dur ? dur + rc.off : nullptr;
+  const int *__restrict__ rf = ATOMS ? nullptr : ref + rc.off;
+  const int *__restrict__ dr = !ATOMS && dur ? dur + rc.off : nullptr;
+  const DerTimedRec tr = ATOMS ? td.recs[rc.r] : DerTimedRec{};
 
   // (1a) sweep: the slots of the replayed prefix.  parent[b] = a < b for every merge; pointer jumping to the roots -- a read
   // that races with a write sees an ancestor either way, and every round at least doubles the distance covered
@@ -215,10 +222,18 @@ __global__ __launch_bounds__(DER_T) void der_solve_kernel(const int *__restrict_
   __syncthreads();
   {
     unsigned long long rm = 0;
-    for (int t = tid; t < n; t += DER_T) {
-      const int a = rf[t], b = hyp_of(t);
-      if (a >= 0) rm |= 1ull << (a & 63);
-      if (b >= 0) atomicOr(&hbits[(b >> 6) & 63], 1ull << (b & 63));
+    if constexpr (ATOMS) {
+      for (int t = tid; t < n; t += DER_T) {
+        const int b = hyp_of(t);
+        if (b >= 0) atomicOr(&hbits[(b >> 6) & 63], 1ull << (b & 63));
+      }
+      if (tid == 0) rm = tr.umask;
+    } else {
+      for (int t = tid; t < n; t += DER_T) {
+        const int a = rf[t], b = hyp_of(t);
+        if (a >= 0) rm |= 1ull << (a & 63);
+        if (b >= 0) atomicOr(&hbits[(b >> 6) & 63], 1ull << (b & 63));
+      }
     }
     if (rm) atomicOr(refmask, rm);
   }
@@ -245,6 +260,26 @@ __global__ __launch_bounds__(DER_T) void der_solve_kernel(const int *__restrict_
   if (tid <= DER_MAX_REF) u[tid] = 0;
   __syncthreads();
   long long c_speech = 0, c_miss = 0, c_fa = 0, c_both = 0;
+  if constexpr (ATOMS) {
+    // an atom of `ticks` ticks with nref = popcount(mask) reference speakers and nhyp = 0 or 1 hypothesis speakers
+    for (int e = tid; e < tr.natoms; e += DER_T) {
+      const long long d = td.ticks[tr.aoff + e];
+      const unsigned long long am = td.mask[tr.aoff + e] & rmask;
+      const int sg = td.seg[tr.aoff + e], b = sg >= 0 && sg < n ? hyp_of(sg) : -1;
+      const int nref = __popcll(am), nhyp = b >= 0 ? 1 : 0;
+      c_speech += d * nref;
+      c_miss += d * (nref > nhyp ? nref - nhyp : 0);
+      c_fa += d * (nhyp > nref ? nhyp - nref : 0);
+      c_both += d * (nref < nhyp ? nref : nhyp);
+      if (b >= 0 && b < DER_MAX_HYP && d) {
+        const int k = b >> 6, j = hbase[k] + __popcll(hbits[k] & der_below(b & 63));
+        for (unsigned long long mk = am; mk; mk &= mk - 1) {
+          const int i = __popcll(rmask & der_below(__ffsll((long long)mk) - 1));
+          atomicAdd(reinterpret_cast<unsigned long long *>(mat.c) + (long long)i * w + j, (unsigned long long)d);
+        }
+      }
+    }
+  } else
   for (int t = tid; t < n; t += DER_T) {
     const int a = rf[t], b = hyp_of(t);
     const long long d = dr ? dr[t] : 1;
@@ -331,11 +366,30 @@ __global__ __launch_bounds__(DER_T) void der_solve_kernel(const int *__restrict_
       if (own[j] && mat.get(own[j] - 1, j - 1) > 0) map[rc.out * DER_MAX_REF + reflab[own[j] - 1]] = clab[j - 1];
 }
 
-template <bool HBM, bool SWEEP> int der_solve_attr(plda_handle *h) {
+template <bool HBM, bool SWEEP>
+__global__ __launch_bounds__(DER_T) void der_solve_kernel(const int *__restrict__ ref, const int *__restrict__ hyp,
+                                                          const int *__restrict__ dur, const int *__restrict__ ma,
+                                                          const int *__restrict__ mb, const DerRec *__restrict__ tab,
+                                                          long long *scratch, long long *__restrict__ counts,
+                                                          int *__restrict__ n_clusters, int *__restrict__ map) {
+  der_solve_body<HBM, SWEEP, false>(ref, hyp, dur, ma, mb, tab, scratch, counts, n_clusters, map, DerTimedDev{});
+}
+
+// the time-based form: the atoms of der_atoms_kernel (der_time.hip) in place of ref and dur
+template <bool HBM, bool SWEEP>
+__global__ __launch_bounds__(DER_T) void der_solve_timed_kernel(const int *__restrict__ hyp, const int *__restrict__ ma,
+                                                                const int *__restrict__ mb, const DerRec *__restrict__ tab,
+                                                                long long *scratch, long long *__restrict__ counts,
+                                                                int *__restrict__ n_clusters, int *__restrict__ map, const DerTimedDev td) {
+  der_solve_body<HBM, SWEEP, true>(nullptr, hyp, nullptr, ma, mb, tab, scratch, counts, n_clusters, map, td);
+}
+
+template <bool HBM, bool SWEEP, bool ATOMS> int der_solve_attr(plda_handle *h) {
   static DeviceOnce attr;
   if (attr.needed(h->device)) {
-    PLDA_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&der_solve_kernel<HBM, SWEEP>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, DER_LDS_BYTES));
+    const void *fn = ATOMS ? reinterpret_cast<const void *>(&der_solve_timed_kernel<HBM, SWEEP>)
+                           : reinterpret_cast<const void *>(&der_solve_kernel<HBM, SWEEP>);
+    PLDA_HIP(h, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, DER_LDS_BYTES));
     attr.done(h->device);
   }
   return PLDA_OK;
@@ -362,9 +416,11 @@ int der_check_offsets(plda_handle *h, const char *fn, const int64_t *offsets, in
 
 // Enqueues the solves of `items` (sr, sh, n, m, off, out, r filled in; w, scr and the launch order are this function's);
 // `tab` is the host copy of the launch table, alive until the caller has synchronised.
+// `td` non-null: the time-based form (dref and ddur unused).
 template <bool SWEEP>
 int der_solve_enqueue(plda_handle *h, std::vector<DerRec> &items, std::vector<DerRec> &tab, const int *dref, const int *dhyp,
-                      const int *ddur, const int *dma, const int *dmb, long long *dcounts, int *dn_clusters, int *dmap) {
+                      const int *ddur, const int *dma, const int *dmb, long long *dcounts, int *dn_clusters, int *dmap,
+                      const DerTimedDev *td) {
   static const int bucket_top[] = {8 << 10, 20 << 10, 40 << 10, 80 << 10, DER_LDS_BYTES};
   constexpr int NB = sizeof(bucket_top) / sizeof(bucket_top[0]);
   struct Launch { int64_t first, count; int64_t lds; bool hbm; };
@@ -407,14 +463,25 @@ int der_solve_enqueue(plda_handle *h, std::vector<DerRec> &items, std::vector<De
   PLDA_HIP(h, hipMemcpyAsync(h->der_tab.p, tab.data(), tab.size() * sizeof(DerRec), hipMemcpyHostToDevice, h->stream));
   const DerRec *dtab = h->der_tab.as<DerRec>();
   long long *scratch = h->der_scratch.as<long long>();
-  PLDA_TRY((der_solve_attr<false, SWEEP>(h)));
-  PLDA_TRY((der_solve_attr<true, SWEEP>(h)));
+  if (td) {
+    PLDA_TRY((der_solve_attr<false, SWEEP, true>(h)));
+    PLDA_TRY((der_solve_attr<true, SWEEP, true>(h)));
+  } else {
+    PLDA_TRY((der_solve_attr<false, SWEEP, false>(h)));
+    PLDA_TRY((der_solve_attr<true, SWEEP, false>(h)));
+  }
   {
     TraceScope ts(h, SWEEP ? "der.sweep_solve" : "der.solve");
     for (const Launch &L : launches) {
       for (int64_t c0 = 0; c0 < L.count; c0 += 1 << 20) {
         const unsigned c = (unsigned)std::min<int64_t>(1 << 20, L.count - c0);
-        if (L.hbm)
+        if (td && L.hbm)
+          der_solve_timed_kernel<true, SWEEP><<<c, DER_T, (size_t)L.lds, h->stream>>>(dhyp, dma, dmb, dtab + L.first + c0, scratch, dcounts,
+                                                                                      dn_clusters, dmap, *td);
+        else if (td)
+          der_solve_timed_kernel<false, SWEEP><<<c, DER_T, (size_t)L.lds, h->stream>>>(dhyp, dma, dmb, dtab + L.first + c0, nullptr, dcounts,
+                                                                                       dn_clusters, dmap, *td);
+        else if (L.hbm)
           der_solve_kernel<true, SWEEP><<<c, DER_T, (size_t)L.lds, h->stream>>>(dref, dhyp, ddur, dma, dmb, dtab + L.first + c0, scratch,
                                                                                 dcounts, dn_clusters, dmap);
         else
@@ -430,9 +497,9 @@ int der_solve_enqueue(plda_handle *h, std::vector<DerRec> &items, std::vector<De
 // the solves of a call, and the synchronisation behind them (also where the enqueue failed half-way: the table is in flight)
 template <bool SWEEP>
 int der_solve_all(plda_handle *h, std::vector<DerRec> &items, const int *dref, const int *dhyp, const int *ddur, const int *dma,
-                  const int *dmb, long long *dcounts, int *dn_clusters, int *dmap) {
+                  const int *dmb, long long *dcounts, int *dn_clusters, int *dmap, const DerTimedDev *td = nullptr) {
   std::vector<DerRec> tab;
-  const int rc = der_solve_enqueue<SWEEP>(h, items, tab, dref, dhyp, ddur, dma, dmb, dcounts, dn_clusters, dmap);
+  const int rc = der_solve_enqueue<SWEEP>(h, items, tab, dref, dhyp, ddur, dma, dmb, dcounts, dn_clusters, dmap, td);
   const hipError_t e = hipStreamSynchronize(h->stream);
   if (rc != PLDA_OK) return rc;
   PLDA_HIP(h, e);
@@ -552,6 +619,57 @@ int der_sweep_device(plda_handle *h, const int32_t *dma, const int32_t *dmb, con
       rc.sr = s[(size_t)r]; rc.m = s[(size_t)(R + q * R + r)]; rc.sh = rc.n - rc.m; rc.w = 0; rc.r = (int)r;
     }
   return der_solve_all<true>(h, items, dref, nullptr, ddur, dma, dmb, reinterpret_cast<long long *>(dcounts), dn_clusters, nullptr);
+}
+
+// The solves of a time-based call (der_time.hip has validated the call and cut the atoms; recs is the host copy of td.recs).
+// Q = 0: one solve per recording against dhyp (recs[r].sh = its distinct hypothesis labels).  Q >= 1: the sweep.
+int der_timed_solve(plda_handle *h, const char *fn, const DerTimedRec *recs, const DerTimedDev &td, const int32_t *dhyp,
+                    const int32_t *dma, const int32_t *dmb, const double *dmc, const int64_t *offsets, int64_t R, const double *thresholds,
+                    int64_t Q, const int32_t *minc, int64_t *dcounts, int32_t *dn_clusters, int32_t *dmap) {
+  auto item = [&](int64_t r, int64_t out) {
+    DerRec rc;
+    rc.off = offsets[r]; rc.scr = 0; rc.out = out; rc.n = (int)(offsets[r + 1] - offsets[r]);
+    rc.sr = __builtin_popcountll(recs[r].umask); rc.sh = 0; rc.w = 0; rc.m = 0; rc.r = (int)r;
+    return rc;
+  };
+  if (Q == 0) {
+    std::vector<DerRec> items((size_t)R);
+    for (int64_t r = 0; r < R; ++r) { items[(size_t)r] = item(r, r); items[(size_t)r].sh = recs[r].sh; }
+    return der_solve_all<false>(h, items, nullptr, dhyp, nullptr, nullptr, nullptr, reinterpret_cast<long long *>(dcounts), nullptr, dmap, &td);
+  }
+  // stat: two counters | offsets [R + 1] | thresholds [Q] | m [Q, R] minc [R]
+  const size_t o_thr = 16 + 8 * (size_t)(R + 1), o_int = o_thr + 8 * (size_t)Q;
+  PLDA_HIP(h, h->der_stat.reserve(o_int + 4 * (size_t)(Q * R + R)));
+  char *ds = h->der_stat.as<char>();
+  long long *doff = reinterpret_cast<long long *>(ds + 16);
+  double *dthr = reinterpret_cast<double *>(ds + o_thr);
+  int *dm = reinterpret_cast<int *>(ds + o_int), *dminc = dm + Q * R;
+  PLDA_HIP(h, hipMemsetAsync(ds, 0, 16, h->stream));
+  PLDA_HIP(h, hipMemcpyAsync(doff, offsets, 8 * (size_t)(R + 1), hipMemcpyHostToDevice, h->stream));
+  PLDA_HIP(h, hipMemcpyAsync(dthr, thresholds, 8 * (size_t)Q, hipMemcpyHostToDevice, h->stream));
+  if (minc) PLDA_HIP(h, hipMemcpyAsync(dminc, minc, 4 * (size_t)R, hipMemcpyHostToDevice, h->stream));
+  {
+    TraceScope ts(h, "der.sweep_count");
+    der_prefix_kernel<<<dim3((unsigned)R, (unsigned)Q), DER_T, 0, h->stream>>>(dma, dmb, dmc, doff, dthr, minc ? dminc : nullptr, (int)R,
+                                                                               reinterpret_cast<unsigned long long *>(ds), dm);
+    PLDA_LAUNCH_CHECK(h);
+  }
+  unsigned long long bad[2] = {0, 0};
+  std::vector<int> m((size_t)(Q * R));
+  PLDA_HIP(h, hipMemcpyAsync(bad, ds, 16, hipMemcpyDeviceToHost, h->stream));
+  PLDA_HIP(h, hipMemcpyAsync(m.data(), dm, 4 * m.size(), hipMemcpyDeviceToHost, h->stream));
+  PLDA_HIP(h, hipStreamSynchronize(h->stream));
+  if (bad[1])
+    return fail(h, PLDA_E_INVAL, "%s: %llu (recording, threshold) pairs whose merge record ends, or holds an entry that is no merge, "
+                                 "before the stop rule fires: not a full record", fn, bad[1]);
+  std::vector<DerRec> items((size_t)(Q * R));
+  for (int64_t q = 0; q < Q; ++q)
+    for (int64_t r = 0; r < R; ++r) {
+      DerRec &rc = items[(size_t)(q * R + r)];
+      rc = item(r, q * R + r);
+      rc.m = m[(size_t)(q * R + r)]; rc.sh = rc.n - rc.m;
+    }
+  return der_solve_all<true>(h, items, nullptr, nullptr, nullptr, dma, dmb, reinterpret_cast<long long *>(dcounts), dn_clusters, nullptr, &td);
 }
 
 }  // namespace plda

@@ -9,8 +9,16 @@ speakers, and the sweep of ONE full AHC merge record over Q thresholds.
 
 Labels: ref in [-1, 64), hyp in [-1, 4096), -1 = non-speech; dur int32 >= 0 in ticks (None: 1 everywhere).  Everything on the
 device is an integer and the counts are exact; the divisions are done here, the pooled ones from Python ints.  Out of scope,
-on purpose: overlapped speech, a collar, JER, a time-based restatement of md-eval (plda_amd/rttm.py turns RTTM turns into
-per-segment labels).
+on purpose: JER.
+
+The time-based form (csrc/der_time.hip; include/plda_hip.h, "time-based diarisation error rate") scores TIME, with overlapped
+reference speech, a collar and UEM regions -- md-eval's definition on integer ticks:
+
+    der_timed(engine, turns, seg_start, seg_dur, hyp, offsets, collar=0, uem=None, skip_overlap=False)   a DerResult
+    sweep_timed(engine, merges, turns, seg_start, seg_dur, offsets, thresholds, ...)                     a SweepResult
+    plan_timed(engine, n_turns, n_seg, n_uem=0, collar=0)                                                the event-sort class
+
+turns = (turn_start, turn_dur, turn_spk, turn_off), what rttm.pack_turns returns first; uem = (uem_start, uem_dur, uem_off).
 """
 import ctypes as C
 
@@ -21,6 +29,11 @@ from . import diarize
 
 MAX_REF = 64            # PLDA_DER_MAX_REF
 MAX_HYP = diarize.AHC_MAX
+MAX_TURNS = 16384       # PLDA_DER_MAX_TURNS
+MAX_UEM = 1024          # PLDA_DER_MAX_UEM
+MAX_TIME = 1 << 30
+MAX_COLLAR = 1 << 20
+SKIP_OVERLAP = 1        # PLDA_DER_SKIP_OVERLAP
 
 _p = diarize._p
 
@@ -183,4 +196,101 @@ def sweep(engine, merges, offsets, ref, thresholds, dur=None, num_speakers=None)
     counts, ncl = np.empty((q, r, 4), np.int64), np.empty((q, r), np.int32)
     N.check(engine._h, engine._lib.plda_der_sweep(engine._h, _p(ma), _p(mb), _p(mc), _p(offsets), r, _p(ref), _p(dur), _p(thresholds),
                                                   q, _p(minc), _p(counts), _p(ncl)))
+    return SweepResult(thresholds, counts, ncl)
+
+
+# ------------------------------------------------------------------------------------------- the time-based form
+def _counted(off, r, name, limit):
+    off = np.ascontiguousarray(off, np.int64)
+    if off.shape != (r + 1,):
+        raise ValueError("%s must hold R + 1 = %d entries, got %r" % (name, r + 1, off.shape))
+    if off[0] != 0:
+        raise ValueError("%s must start at 0" % name)
+    sizes = np.diff(off)
+    if (sizes < 0).any() or (sizes > limit).any():
+        raise ValueError("every recording must hold 0 ... %d entries of %s (it must ascend)" % (limit, name))
+    return off
+
+
+def _times(start, dur, n, name):
+    out = []
+    for a, what in ((start, "start"), (dur, "dur")):
+        a = np.asarray(a)
+        if a.dtype.kind not in "iu":
+            raise ValueError("%s_%s must be an integer array of ticks" % (name, what))
+        if a.shape != (n,):
+            raise ValueError("%s_%s must hold %d entries, got %r" % (name, what, n, a.shape))
+        out.append(a.astype(np.int64))
+    if n and (out[0].min() < 0 or out[1].min() < 0 or (out[0] + out[1]).max() > MAX_TIME):
+        raise ValueError("%s times must satisfy 0 <= start, 0 <= dur, start + dur <= 2^30" % name)
+    return np.ascontiguousarray(out[0], np.int32), np.ascontiguousarray(out[1], np.int32)
+
+
+def timed_args(turns, seg_start, seg_dur, offsets, collar, uem, skip_overlap):
+    """The argument check shared by der_timed and sweep_timed, before any device work ->
+    (turn_start, turn_dur, turn_spk, turn_off, seg_start, seg_dur, offsets, uem_start, uem_dur, uem_off, collar, flags); the
+    three uem entries are None without a UEM.  Disjointness (same-speaker turns, segments) is the device's check."""
+    offsets = _offsets(offsets)
+    r, t = len(offsets) - 1, int(offsets[-1])
+    if turns is None or len(turns) != 4:
+        raise ValueError("turns must be (turn_start, turn_dur, turn_spk, turn_off)")
+    toff = _counted(turns[3], r, "turn_off", MAX_TURNS)
+    ts, td = _times(turns[0], turns[1], int(toff[-1]), "turn")
+    tk = _labels(turns[2], int(toff[-1]), "turn_spk", MAX_REF)
+    if tk.size and tk.min() < 0:
+        raise ValueError("turn_spk must lie in [0, %d)" % MAX_REF)
+    ss, sd = _times(seg_start, seg_dur, t, "seg")
+    us = ud = uoff = None
+    if uem is not None:
+        if len(uem) != 3:
+            raise ValueError("uem must be (uem_start, uem_dur, uem_off)")
+        uoff = _counted(uem[2], r, "uem_off", MAX_UEM)
+        us, ud = _times(uem[0], uem[1], int(uoff[-1]), "uem")
+    if isinstance(collar, bool) or not isinstance(collar, (int, np.integer)) or not 0 <= collar <= MAX_COLLAR:
+        raise ValueError("collar must be an integer number of ticks in [0, 2^20]")
+    return ts, td, tk, toff, ss, sd, offsets, us, ud, uoff, int(collar), SKIP_OVERLAP if skip_overlap else 0
+
+
+def plan_timed(engine, n_turns, n_seg, n_uem=0, collar=0):
+    """{"cls": 0 (events sorted in LDS) or 1 (in handle scratch), "scratch_bytes": per recording, "lds_max": the largest
+    event-slot count of the LDS class, "events": the event slots of this recording}."""
+    out = (C.c_int32 * 3)()
+    N.check(engine._h, engine._lib.plda_der_timed_plan(engine._h, int(n_turns), int(n_seg), int(n_uem), int(collar), out))
+    return {"cls": int(out[0]), "scratch_bytes": int(out[1]), "lds_max": int(out[2]),
+            "events": (6 if collar > 0 else 2) * int(n_turns) + 2 * int(n_seg) + 2 * int(n_uem)}
+
+
+def der_timed(engine, turns, seg_start, seg_dur, hyp, offsets, collar=0, uem=None, skip_overlap=False, return_map=False):
+    """Time-based DER of R recordings: reference turns (they may overlap across speakers), disjoint hypothesis segments
+    seg_start, seg_dur, hyp int [T] (-1 = non-speech), recording r owning segments offsets[r] .. offsets[r+1]; collar in
+    ticks; uem the scored regions or None; skip_overlap: md-eval's -1.  Returns a DerResult."""
+    ts, td, tk, toff, ss, sd, offsets, us, ud, uoff, collar, flags = timed_args(turns, seg_start, seg_dur, offsets, collar, uem, skip_overlap)
+    hyp = _labels(hyp, int(offsets[-1]), "hyp", MAX_HYP)
+    r = len(offsets) - 1
+    counts = np.empty((r, 4), np.int64)
+    map_ = np.empty((r, MAX_REF), np.int32) if return_map else None
+    N.check(engine._h, engine._lib.plda_der_timed(engine._h, _p(ts), _p(td), _p(tk), _p(toff), _p(ss), _p(sd), _p(hyp), _p(offsets), r,
+                                                  _p(us), _p(ud), _p(uoff), collar, flags, _p(counts), _p(map_)))
+    return DerResult(counts, map_)
+
+
+def sweep_timed_args(merges, turns, seg_start, seg_dur, offsets, thresholds, num_speakers, collar, uem, skip_overlap):
+    """The argument check of sweep_timed -> (merge_a, merge_b, merge_cost, thresholds, min_clusters) + timed_args' tuple."""
+    targs = timed_args(turns, seg_start, seg_dur, offsets, collar, uem, skip_overlap)
+    ref = np.zeros(int(targs[6][-1]), np.int32)
+    ma, mb, mc, _, _, thresholds, _, minc = sweep_args(merges, targs[6], ref, thresholds, None, num_speakers)
+    return (ma, mb, mc, thresholds, minc) + targs
+
+
+def sweep_timed(engine, merges, turns, seg_start, seg_dur, offsets, thresholds, num_speakers=None, collar=0, uem=None,
+                skip_overlap=False):
+    """sweep() on time: the clusterings a FULL merge record yields at every threshold, each scored as der_timed scores the
+    labels of diarize.cut at that threshold.  The time line is cut once per recording.  Returns a SweepResult."""
+    ma, mb, mc, thresholds, minc, ts, td, tk, toff, ss, sd, offsets, us, ud, uoff, collar, flags = sweep_timed_args(
+        merges, turns, seg_start, seg_dur, offsets, thresholds, num_speakers, collar, uem, skip_overlap)
+    r, q = len(offsets) - 1, len(thresholds)
+    counts, ncl = np.empty((q, r, 4), np.int64), np.empty((q, r), np.int32)
+    N.check(engine._h, engine._lib.plda_der_timed_sweep(engine._h, _p(ma), _p(mb), _p(mc), _p(ts), _p(td), _p(tk), _p(toff), _p(ss), _p(sd),
+                                                        _p(offsets), r, _p(us), _p(ud), _p(uoff), collar, flags, _p(thresholds), q, _p(minc),
+                                                        _p(counts), _p(ncl)))
     return SweepResult(thresholds, counts, ncl)

@@ -667,10 +667,13 @@ class MPlda(object):
         from . import der
         return der.der(self, ref, hyp, offsets, dur, return_map)
 
-    def tune_threshold(self, x, offsets, ref, thresholds, dur=None, target_energy=None):
+    def tune_threshold(self, x, offsets, ref, thresholds, dur=None, target_energy=None, turns=None, seg_start=None, seg_dur=None,
+                       collar=0, uem=None, skip_overlap=False):
         """The clustering threshold with the lowest pooled DER on a development set: ONE cluster(x, offsets, threshold=None,
         num_speakers=1, return_merges=True[, target_energy=target_energy]), then one der.sweep of its full merge record over
-        `thresholds`.  Returns (the best threshold -- the first of equal ones --, the plda_amd.der.SweepResult)."""
+        `thresholds`.  With `turns` (and seg_start, seg_dur; collar, uem, skip_overlap as in der_timed) the sweep is the
+        time-based one, der.sweep_timed, and ref and dur must be None.  Returns (the best threshold -- the first of equal
+        ones --, the plda_amd.der.SweepResult)."""
         from . import der
         offsets = np.ascontiguousarray(offsets, np.int64)
         X = self._rows(x, "Segment vectors")
@@ -678,6 +681,18 @@ class MPlda(object):
             raise ValueError("offsets must hold R + 1 >= 2 entries ending at the number of rows of x")
         t, r = int(offsets[-1]), len(offsets) - 1
         empty = (np.zeros(t - r, np.int32), np.zeros(t - r, np.int32), np.zeros(t - r))
+        if turns is not None:
+            if ref is not None or dur is not None:
+                raise ValueError("with turns, ref and dur must be None (the reference is the turns)")
+            der.sweep_timed_args(empty, turns, seg_start, seg_dur, offsets, thresholds, None, collar, uem, skip_overlap)
+            from . import diarize
+            diarize.stop_args(offsets, None, 1)
+            if target_energy is not None:
+                _, _, merges = diarize.ahc_dense_pca(self, X, offsets, target_energy, None, 1, True)
+            else:
+                _, _, merges = diarize.ahc_vectors(self, self.transform_array(X, 1), offsets, None, 1, True)
+            res = der.sweep_timed(self, merges, turns, seg_start, seg_dur, offsets, thresholds, None, collar, uem, skip_overlap)
+            return float(res.thresholds[res.best]), res
         der.sweep_args(empty, offsets, ref, thresholds, dur, None)        # (before any device work)
         from . import diarize
         diarize.stop_args(offsets, None, 1)
@@ -687,6 +702,40 @@ class MPlda(object):
             _, _, merges = diarize.ahc_vectors(self, self.transform_array(X, 1), offsets, None, 1, True)   # cluster() on embedded rows
         res = der.sweep(self, merges, offsets, ref, thresholds, dur)
         return float(res.thresholds[res.best]), res
+
+    def der_timed(self, turns, seg_start, seg_dur, hyp, offsets, collar=0, uem=None, skip_overlap=False, return_map=False):
+        """Time-based DER of R recordings (plda_amd/der.py: der_timed): reference turns (turn_start, turn_dur, turn_spk,
+        turn_off) that may overlap across speakers, disjoint hypothesis segments, a collar in ticks, UEM regions, md-eval's
+        skip-overlap switch.  Returns a plda_amd.der.DerResult."""
+        from . import der
+        return der.der_timed(self, turns, seg_start, seg_dur, hyp, offsets, collar, uem, skip_overlap, return_map)
+
+    def der_timed_dev(self, dturns, turn_off, dseg_start, dseg_dur, dhyp, offsets, dcounts, dmap=None, duem=None, uem_off=None,
+                      collar=0, flags=0):
+        """plda_der_timed_dev on HBM-resident int32 arrays (raw device addresses): dturns = (turn_start, turn_dur, turn_spk),
+        duem = (uem_start, uem_dur) or None; turn_off, offsets, uem_off (int64) are HOST arrays; dcounts int64 [R, 4], dmap
+        int32 [R, 64] or None."""
+        def vp(x):
+            return C.c_void_p(int(x)) if x else None
+        du = duem if duem is not None else (None, None)
+        self._ck(self._lib.plda_der_timed_dev(
+            self._h, vp(dturns[0]), vp(dturns[1]), vp(dturns[2]), _ptr(turn_off), vp(dseg_start), vp(dseg_dur), vp(dhyp), _ptr(offsets),
+            len(offsets) - 1, vp(du[0]), vp(du[1]), _ptr(uem_off) if uem_off is not None else None, int(collar), int(flags), vp(dcounts),
+            vp(dmap)))
+
+    def der_timed_sweep_dev(self, dmerges, dturns, turn_off, dseg_start, dseg_dur, offsets, thresholds, min_clusters, dcounts,
+                            dn_clusters, duem=None, uem_off=None, collar=0, flags=0):
+        """plda_der_timed_sweep_dev on an HBM-resident full merge record dmerges = (merge_a, merge_b, merge_cost) and the
+        arrays of der_timed_dev; thresholds (float64) and min_clusters (int32 or None) are HOST arrays; dcounts int64
+        [Q, R, 4], dn_clusters int32 [Q, R]."""
+        def vp(x):
+            return C.c_void_p(int(x)) if x else None
+        du = duem if duem is not None else (None, None)
+        self._ck(self._lib.plda_der_timed_sweep_dev(
+            self._h, vp(dmerges[0]), vp(dmerges[1]), vp(dmerges[2]), vp(dturns[0]), vp(dturns[1]), vp(dturns[2]), _ptr(turn_off),
+            vp(dseg_start), vp(dseg_dur), _ptr(offsets), len(offsets) - 1, vp(du[0]), vp(du[1]),
+            _ptr(uem_off) if uem_off is not None else None, int(collar), int(flags), _ptr(thresholds), len(thresholds),
+            _ptr(min_clusters) if min_clusters is not None else None, vp(dcounts), vp(dn_clusters)))
 
     def der_dev(self, dref, dhyp, ddur, offsets, dcounts, dmap=None):
         """plda_der_dev on HBM-resident int32 labels and durations (raw device addresses; ddur and dmap may be None);

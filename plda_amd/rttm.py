@@ -4,6 +4,9 @@ step from reference turns to the per-segment labels plda_amd/der.py scores.  Pur
     write(file, rec_ids, offsets, labels, start, dur, tick=0.01)   one SPEAKER line per maximal run of abutting segments
     read(file, tick=0.01)                                          {recording: [(start, dur, speaker)]}, times in ticks
     segment_labels(turns, seg_start, seg_dur)                      the reference speaker of every segment, by greatest overlap
+    pack_turns(turns_by_recording, rec_ids)                        the packed turn arrays of der.der_timed, + sorted names
+    read_uem(file, tick=0.01)                                      {recording: [(start, dur)]} of a UEM file
+    cut_windows(start, dur, offsets)                               overlapping sliding windows -> disjoint segments
 
 Times are integer ticks of `tick` seconds (0.01 s by default), so that a file written here reads back exactly.
 """
@@ -89,3 +92,89 @@ def segment_labels(turns, seg_start, seg_dur):
     labels = np.argmax(ov, 0).astype(np.int32)           # (the first maximum: the first name in sorted order)
     labels[ov.max(0) <= 0] = -1
     return labels, names
+
+
+def pack_turns(turns_by_recording, rec_ids):
+    """The reference turns {recording: [(start, dur, speaker)]} (read's result) of the recordings rec_ids, packed for
+    der.der_timed: ((turn_start, turn_dur, turn_spk int32, turn_off int64 [R + 1]), names) with names[r] the sorted speaker
+    names of recording r (turn_spk indexes them).  Empty turns are dropped; turns of one speaker that overlap or abut become
+    one turn; a recording absent from the dict has no turn.  More than 64 speakers in a recording: ValueError."""
+    ts, td, tk, off, names_out = [], [], [], [0], []
+    for rec in rec_ids:
+        turns = [(int(s), int(d), k) for s, d, k in turns_by_recording.get(rec, ()) if int(d) > 0]
+        names = sorted({k for _, _, k in turns})
+        if len(names) > MAX_REF:
+            raise ValueError("%s: %d reference speakers (at most %d)" % (rec, len(names), MAX_REF))
+        for idx, name in enumerate(names):
+            run = None                                   # [start, end]
+            for s, d in sorted((s, d) for s, d, k in turns if k == name):
+                if run is not None and s <= run[1]:
+                    run[1] = max(run[1], s + d)
+                    continue
+                if run is not None:
+                    ts.append(run[0]); td.append(run[1] - run[0]); tk.append(idx)
+                run = [s, s + d]
+            if run is not None:
+                ts.append(run[0]); td.append(run[1] - run[0]); tk.append(idx)
+        off.append(len(ts))
+        names_out.append(names)
+    return (np.asarray(ts, np.int32), np.asarray(td, np.int32), np.asarray(tk, np.int32), np.asarray(off, np.int64)), names_out
+
+
+def read_uem(file, tick=0.01):
+    """{recording: [(start, dur)]} of a UEM file ("<recording> <channel> <start> <end>" per line, seconds; lines that are
+    empty or start with ';' or '#' are skipped), in file order, times rounded to integer ticks; an interval that ends before
+    it starts is an error."""
+    out = {}
+    f, close = _open(file, "r")
+    try:
+        for line in f:
+            p = line.split()
+            if not p or p[0][0] in ";#":
+                continue
+            if len(p) < 4:
+                raise ValueError("short UEM line: %r" % line)
+            a, b = int(round(float(p[2]) / tick)), int(round(float(p[3]) / tick))
+            if b < a:
+                raise ValueError("UEM interval ends before it starts: %r" % line)
+            out.setdefault(p[0], []).append((a, b - a))
+    finally:
+        if close:
+            f.close()
+    return out
+
+
+def pack_uem(uem_by_recording, rec_ids):
+    """(uem_start, uem_dur int32, uem_off int64 [R + 1]) of read_uem's result for the recordings rec_ids (a recording absent
+    from the dict gets no interval: nothing of it is scored)."""
+    us, ud, off = [], [], [0]
+    for rec in rec_ids:
+        for s, d in uem_by_recording.get(rec, ()):
+            us.append(int(s)); ud.append(int(d))
+        off.append(len(us))
+    return np.asarray(us, np.int32), np.asarray(ud, np.int32), np.asarray(off, np.int64)
+
+
+def cut_windows(start, dur, offsets):
+    """Overlapping sliding windows -> disjoint segments, the rule of Kaldi's make_rttm.py: where window t + 1 of a recording
+    starts before window t ends, both are cut at the midpoint of the overlap; an odd overlap gives the extra tick to the
+    earlier window.  The windows of a recording (offsets[r] .. offsets[r+1]) must be in time order (starts and ends ascending).
+    Returns (start, dur) int32 [T]."""
+    offsets = np.asarray(offsets, np.int64)
+    start, dur = np.asarray(start, np.int64), np.asarray(dur, np.int64)
+    if not (start.shape == dur.shape == (int(offsets[-1]),)):
+        raise ValueError("start and dur must hold one entry per window")
+    lo, hi = start.copy(), start + dur
+    for r in range(len(offsets) - 1):
+        a, b = int(offsets[r]), int(offsets[r + 1])
+        if (np.diff(start[a:b]) < 0).any() or (np.diff(hi[a:b]) < 0).any() or (dur[a:b] < 0).any():
+            raise ValueError("the windows of recording %d are not in time order" % r)
+        for t in range(a, b - 1):
+            ov = int(hi[t] - lo[t + 1])
+            if ov > 0:
+                cut = int(lo[t + 1]) + (ov + 1) // 2
+                hi[t] = cut
+                lo[t + 1] = cut
+    if (hi < lo).any():
+        raise ValueError("a window lies inside its neighbours' overlap")
+    return lo.astype(np.int32), (hi - lo).astype(np.int32)
