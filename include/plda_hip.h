@@ -1123,6 +1123,17 @@ int plda_score_dense_pca_ahc(plda_handle *h, const double *X, const int64_t *off
  * pi fp64 packed at pi_off[r], S_r entries (likewise); elbo fp64 [R, max_iters], entries at and beyond iters[r] quiet NaN;
  * iters int32 [R].  Nothing else is written.
  *
+ * SECOND SPEAKER (K21; plda_vbx_top2[_dev], the recipe's --output-2nd).  Two more outputs, each nullable on its own, taken from
+ * the same last-iteration gamma.  Let first(t) = argmax_s gamma[t,s], ties to the smallest s (labels before renumbering), and A
+ * the set of speakers that are first(t) for at least one t of the recording, |A| = k = n_clusters[r].  Then
+ *   second(t) = argmax over s in A \ {first(t)} of gamma[t,s], ties to the smallest s;
+ *   post2   fp64  [T_total]: gamma[t, second(t)], the very bits the gamma output holds there;
+ *   labels2 int32 [T_total]: second(t) in the renumbering of labels (0 .. k-1 by ascending smallest first-member).
+ * k = 1: labels2[t] = -1 and post2[t] = 0.  A speaker that is nobody's first choice is dead in the VB sense and gets no number,
+ * however high its posterior in a row: n_clusters and labels stay exactly plda_vbx's.  Where to USE the second speaker is the
+ * caller's decision (an external overlap detector, or a floor on post2: plda_amd/diarize.py, apply_overlap).  The other six
+ * outputs are bit-identical to plda_vbx's on the same input.
+ *
  * ERRORS, all PLDA_E_INVAL: offsets that do not ascend from 0, an empty recording or one above PLDA_AHC_MAX, a parameter outside
  * its range, D outside 1 ... 4096 -- before any device work; a non-finite y, a label outside [0, 64), Phi[d] < 0 or non-finite
  * -- found on the device, with their count in plda_last_error; gamma_off[r+1] - gamma_off[r] < T_r S_r or pi_off[r+1] -
@@ -1130,7 +1141,8 @@ int plda_score_dense_pca_ahc(plda_handle *h, const double *X, const int64_t *off
  *
  * DETERMINISM.  Every sum (N, sum_t gamma rho, the d-dots, c_t, sum ln c_t, pi') is taken in an order fixed by (T, S, D) alone
  * and there are no floating-point atomics: a recording's outputs are bit-identical from run to run, alone or inside any batch,
- * and under any grouping into launches.
+ * and under any grouping into launches.  labels2 and post2 are a selection from that gamma by comparisons alone (a butterfly
+ * over the speaker lanes whose result does not depend on the order of its steps): the same holds for them.
  *
  * METHOD.  One workgroup per recording, persistent over the iterations (no host synchronisation between them), one lane per
  * speaker on the chain.  Two dispatch classes: the LDS class keeps the state (b, a, beta, c, m, G, alpha, invL, sqrt Phi, Phi:
@@ -1144,11 +1156,14 @@ int plda_score_dense_pca_ahc(plda_handle *h, const double *X, const int64_t *off
  *                            HOST arrays (the AHC's and the fusion's convention).  Synchronises the handle's stream twice: to
  *                            read the reject counters and S, and at its end.
  *   plda_vbx                 the same with everything in host memory.
+ *   plda_vbx_top2[_dev]      plda_vbx[_dev] with labels2 and post2 behind its arguments: the same kernels, one more pass over the
+ *                            speaker lanes of every row where the arg-max is taken, in both classes; gamma is not read again
+ *                            from HBM by a second kernel.
  *   plda_project_rows[_dev]  out [R, Dout] = X [R, Din] transform^T + offset: TransformIvector without its normalisation
  *                            factor, through the library's fp64 GEMM.
  * (Length normalisation and the LDA fit before the model: the section "embedding chain" below, K18.)
- * OUT OF SCOPE, each on purpose: more than 64 initial speakers; several workgroups on one recording; overlap handling.  (DER: the section "diarisation error rate" below;
- * RTTM: plda_amd/rttm.py.) ---- */
+ * OUT OF SCOPE, each on purpose: more than 64 initial speakers; several workgroups on one recording; an overlap detector; a third
+ * speaker.  (DER: the section "diarisation error rate" below; RTTM: plda_amd/rttm.py.) ---- */
 #define PLDA_VBX_MAX_SPK 64
 int plda_vbx_plan(plda_handle *h, int64_t T, int64_t S, int64_t D, int32_t out[3]);
 int plda_vbx_dev(plda_handle *h, const double *dY, int64_t D, const double *dPhi, const int32_t *dlabels_in, const int64_t *offsets,
@@ -1159,6 +1174,14 @@ int plda_vbx(plda_handle *h, const double *Y, int64_t D, const double *Phi, cons
              double Fa, double Fb, double loop_prob, double init_smoothing, int64_t max_iters, double epsilon, int32_t *labels,
              int32_t *n_clusters, double *gamma, const int64_t *gamma_off, double *pi, const int64_t *pi_off, double *elbo,
              int32_t *iters);
+int plda_vbx_top2_dev(plda_handle *h, const double *dY, int64_t D, const double *dPhi, const int32_t *dlabels_in, const int64_t *offsets,
+                      int64_t R, double Fa, double Fb, double loop_prob, double init_smoothing, int64_t max_iters, double epsilon,
+                      int32_t *dlabels, int32_t *dn_clusters, double *dgamma, const int64_t *gamma_off, double *dpi, const int64_t *pi_off,
+                      double *delbo, int32_t *diters, int32_t *dlabels2, double *dpost2);
+int plda_vbx_top2(plda_handle *h, const double *Y, int64_t D, const double *Phi, const int32_t *labels_in, const int64_t *offsets,
+                  int64_t R, double Fa, double Fb, double loop_prob, double init_smoothing, int64_t max_iters, double epsilon,
+                  int32_t *labels, int32_t *n_clusters, double *gamma, const int64_t *gamma_off, double *pi, const int64_t *pi_off,
+                  double *elbo, int32_t *iters, int32_t *labels2, double *post2);
 int plda_project_rows_dev(plda_handle *h, const double *dX, int64_t R, int32_t Din, double *dout);
 int plda_project_rows(plda_handle *h, const double *X, int64_t R, int32_t Din, double *out);
 
@@ -1268,6 +1291,23 @@ int plda_der_sweep(plda_handle *h, const int32_t *merge_a, const int32_t *merge_
  * rules of plda_der's.  EXAMPLE: ref A [0, 10), B [5, 15); hyp X [0, 15).  Collar 0: {20, 5, 0, 5}.  Collar 1 removes [-1, 1),
  * [4, 6), [9, 11), [14, 16): {12, 3, 0, 3}.
  *
+ * TWO HYPOTHESIS LABELS PER SEGMENT (K21; plda_der_timed_ovl[_dev]).  hyp2 int32 [T_total], nullable, is the second speaker of
+ * every segment: -1 = none; hyp2[t] >= 0 requires 0 <= hyp2[t] < PLDA_AHC_MAX, hyp[t] >= 0 and hyp2[t] != hyp[t] (anything else
+ * is an ENTRY violation, below).  The segments stay pairwise disjoint in time; a segment carries the label set J = {hyp[t]} u
+ * {hyp2[t]} without the -1s, so at most two hypothesis speakers talk at any tick, and the labels of a recording are compacted
+ * over both arrays.  With J(t) the label set of the segment over a scored tick (empty outside every segment) and nhyp = |J(t)|
+ * in {0, 1, 2}:
+ *   speech   += nref
+ *   miss     += max(0, nref - nhyp)
+ *   fa       += max(0, nhyp - nref)
+ *   C[i][j]  += 1 for every i in Rset(t) and every j in J(t)
+ *   correct   = the maximum of sum_i C[i][m(i)] over all one-to-one partial maps m
+ *   confusion = sum of min(nref, nhyp) - correct
+ * A one-to-one map matches at most min(nref, nhyp) pairs on any tick, so confusion >= 0.  EXAMPLES, ref A [0, 10), B [5, 15),
+ * collar 0:   hyp [0, 5) X, [5, 10) X + Y, [10, 15) Y: {20, 0, 0, 0};   hyp [0, 15) X + Y: {20, 0, 10, 0};   hyp [0, 15) X,
+ * hyp2 = -1: {20, 5, 0, 5} (plda_der_timed's figure).  With hyp2 = NULL, counts and map equal plda_der_timed's.  The atoms do
+ * not change (ticks, reference mask, segment index); the solve looks both labels of an atom's segment up.
+ *
  * SWEEP: as plda_der_sweep, the hypothesis label of segment t being the slot of the replayed merge prefix (no hypothesis
  * non-speech); counts [Q, R, 4], n_clusters [Q, R] (= N - merges, every segment counted, scored or not).  The time line is cut
  * once per recording; all Q thresholds read the same atoms.
@@ -1277,9 +1317,10 @@ int plda_der_sweep(plda_handle *h, const int32_t *merge_a, const int32_t *merge_
  * ERRORS, all PLDA_E_INVAL, none writes an output.  On the host, before any device work: an offset array (offsets, turn_off,
  * uem_off) that does not ascend from 0 or exceeds its limit, collar or flags out of range, the sweep's Q, thresholds,
  * min_clusters as in plda_der_sweep, a NULL array.  On the device, counted, the two counts in plda_last_error: ENTRIES with a
- * label or a time out of range; EVENTS that meet a state the contract excludes -- a turn that starts inside another turn of
- * its speaker (its start finds the speaker talking, and a later end finds them silent: one violation may be counted at more
- * than one event), a hypothesis segment that starts while another is open.  A record that is not full: as plda_der_sweep.
+ * label or a time out of range (plda_der_timed_ovl: also a second label without a first, or equal to it); EVENTS that meet a
+ * state the contract excludes -- a turn that starts inside another turn of its speaker (its start finds the speaker talking,
+ * and a later end finds them silent: one violation may be counted at more than one event), a hypothesis segment that starts
+ * while another is open.  A record that is not full: as plda_der_sweep.
  *
  * METHOD.  der_atoms_kernel, one workgroup per recording: one 64-bit key per boundary -- 2 per turn, 4 more per turn when collar
  * > 0, 2 per segment, 2 per UEM interval, ends before starts on the same tick -- sorted by a bitonic network, in LDS up to
@@ -1298,11 +1339,12 @@ int plda_der_sweep(plda_handle *h, const int32_t *merge_a, const int32_t *merge_
  *   plda_der_timed_dev         the turn, segment and UEM arrays and the outputs in HBM; turn_off, offsets, uem_off [R + 1] are
  *                              HOST arrays.  Synchronises the handle's stream twice.
  *   plda_der_timed             the same with everything in host memory.
+ *   plda_der_timed_ovl[_dev]   plda_der_timed[_dev] with hyp2 behind hyp (nullable: then it IS plda_der_timed[_dev]).
  *   plda_der_timed_sweep_dev   the merge record, the arrays and the outputs in HBM; the three offset arrays, thresholds [Q] and
  *                              min_clusters [R] (nullable) are HOST arrays.
  *   plda_der_timed_sweep       the same with everything in host memory.
- * OUT OF SCOPE, each on purpose: overlapping HYPOTHESIS speakers (that needs overlap output from VBx first); JER; per-speaker
- * error breakdowns; word-level or SAD-only scoring; several workgroups on one recording. ---- */
+ * OUT OF SCOPE, each on purpose: more than two simultaneous hypothesis speakers; second labels in the threshold sweeps (the AHC
+ * has none); JER; per-speaker error breakdowns; word-level or SAD-only scoring; several workgroups on one recording. ---- */
 #define PLDA_DER_MAX_TURNS 16384
 #define PLDA_DER_MAX_UEM 1024
 #define PLDA_DER_SKIP_OVERLAP 1
@@ -1315,6 +1357,14 @@ int plda_der_timed(plda_handle *h, const int32_t *turn_start, const int32_t *tur
                    const int32_t *seg_start, const int32_t *seg_dur, const int32_t *hyp, const int64_t *offsets, int64_t R,
                    const int32_t *uem_start, const int32_t *uem_dur, const int64_t *uem_off, int32_t collar, int32_t flags,
                    int64_t *counts, int32_t *map);
+int plda_der_timed_ovl_dev(plda_handle *h, const int32_t *dturn_start, const int32_t *dturn_dur, const int32_t *dturn_spk,
+                           const int64_t *turn_off, const int32_t *dseg_start, const int32_t *dseg_dur, const int32_t *dhyp,
+                           const int32_t *dhyp2, const int64_t *offsets, int64_t R, const int32_t *duem_start, const int32_t *duem_dur,
+                           const int64_t *uem_off, int32_t collar, int32_t flags, int64_t *dcounts, int32_t *dmap);
+int plda_der_timed_ovl(plda_handle *h, const int32_t *turn_start, const int32_t *turn_dur, const int32_t *turn_spk, const int64_t *turn_off,
+                       const int32_t *seg_start, const int32_t *seg_dur, const int32_t *hyp, const int32_t *hyp2, const int64_t *offsets,
+                       int64_t R, const int32_t *uem_start, const int32_t *uem_dur, const int64_t *uem_off, int32_t collar, int32_t flags,
+                       int64_t *counts, int32_t *map);
 int plda_der_timed_sweep_dev(plda_handle *h, const int32_t *dmerge_a, const int32_t *dmerge_b, const double *dmerge_cost,
                              const int32_t *dturn_start, const int32_t *dturn_dur, const int32_t *dturn_spk, const int64_t *turn_off,
                              const int32_t *dseg_start, const int32_t *dseg_dur, const int64_t *offsets, int64_t R,

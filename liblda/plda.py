@@ -103,7 +103,8 @@ class PLDA(object):
 
     def diarize(self, x, offsets, threshold=0.0, num_speakers=None, target_energy=None, **vbx):
         """cluster, then resegment.  target_energy goes to the clustering only (VBx keeps working on the full model).  Returns
-        (labels, n_clusters[, info])."""
+        (labels, n_clusters[, info]); with overlap= (a per-segment bool mask) or min_posterior= (labels, n_clusters, labels2),
+        labels2 the second speaker of every segment where one is kept, -1 elsewhere."""
         if target_energy is None:
             return self._instance.diarize(x, offsets, threshold, num_speakers, **vbx)
         return self._instance.diarize(x, offsets, threshold, num_speakers, target_energy=target_energy, **vbx)
@@ -113,10 +114,10 @@ class PLDA(object):
         the optimal speaker mapping; plda_amd/der.py.  Returns a DerResult (counts, der, total[, map])."""
         return self._instance.der(ref, hyp, offsets, dur, return_map)
 
-    def der_timed(self, turns, seg_start, seg_dur, hyp, offsets, collar=0, uem=None, skip_overlap=False, return_map=False):
-        """Time-based DER (md-eval's definition on integer ticks): overlapped reference turns, a collar, UEM regions;
-        plda_amd/der.py: der_timed.  Returns a DerResult."""
-        return self._instance.der_timed(turns, seg_start, seg_dur, hyp, offsets, collar, uem, skip_overlap, return_map)
+    def der_timed(self, turns, seg_start, seg_dur, hyp, offsets, collar=0, uem=None, skip_overlap=False, return_map=False, hyp2=None):
+        """Time-based DER (md-eval's definition on integer ticks): overlapped reference turns, a collar, UEM regions; hyp2: a
+        second hypothesis speaker per segment, -1 = none; plda_amd/der.py: der_timed.  Returns a DerResult."""
+        return self._instance.der_timed(turns, seg_start, seg_dur, hyp, offsets, collar, uem, skip_overlap, return_map, hyp2)
 
     def tune_threshold(self, x, offsets, ref, thresholds, dur=None, target_energy=None, **timed):
         """The clustering threshold of the lowest pooled DER on a development set: one clustering (behind the per-recording PCA

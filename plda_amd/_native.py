@@ -160,11 +160,15 @@ SIGNATURES = {
     "plda_der_timed_plan": (C.c_int, [_vp, _i64, _i64, _i64, _i32, _vp]),
     "plda_der_timed_dev": (C.c_int, [_vp] * 9 + [_i64, _vp, _vp, _vp, _i32, _i32, _vp, _vp]),
     "plda_der_timed": (C.c_int, [_vp] * 9 + [_i64, _vp, _vp, _vp, _i32, _i32, _vp, _vp]),
+    "plda_der_timed_ovl_dev": (C.c_int, [_vp] * 10 + [_i64, _vp, _vp, _vp, _i32, _i32, _vp, _vp]),
+    "plda_der_timed_ovl": (C.c_int, [_vp] * 10 + [_i64, _vp, _vp, _vp, _i32, _i32, _vp, _vp]),
     "plda_der_timed_sweep_dev": (C.c_int, [_vp] * 11 + [_i64, _vp, _vp, _vp, _i32, _i32, _vp, _i64, _vp, _vp, _vp]),
     "plda_der_timed_sweep": (C.c_int, [_vp] * 11 + [_i64, _vp, _vp, _vp, _i32, _i32, _vp, _i64, _vp, _vp, _vp]),
     "plda_vbx_plan": (C.c_int, [_vp, _i64, _i64, _i64, _vp]),
     "plda_vbx_dev": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _f64, _f64, _f64, _f64, _i64, _f64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "plda_vbx": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _f64, _f64, _f64, _f64, _i64, _f64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "plda_vbx_top2_dev": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _f64, _f64, _f64, _f64, _i64, _f64] + [_vp] * 10),
+    "plda_vbx_top2": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _f64, _f64, _f64, _f64, _i64, _f64] + [_vp] * 10),
     "plda_project_rows_dev": (C.c_int, [_vp, _vp, _i64, _i32, _vp]),
     "plda_project_rows": (C.c_int, [_vp, _vp, _i64, _i32, _vp]),
     "plda_embed_set": (C.c_int, [_vp, _i32, _i32, _vp, _f64, _vp, _vp, _f64]),

@@ -2153,6 +2153,7 @@ int der_timed_host(plda_handle *h, const char *fn, DerTimedArgs a, bool sweep) {
   PLDA_TRY(st.in(a.sstart, (size_t)T, &a.sstart));
   PLDA_TRY(st.in(a.sdur, (size_t)T, &a.sdur));
   PLDA_TRY(st.in(a.hyp, (size_t)T, &a.hyp));
+  PLDA_TRY(st.in(a.hyp2, (size_t)T, &a.hyp2));
   PLDA_TRY(st.in(a.ustart, (size_t)nu, &a.ustart));
   PLDA_TRY(st.in(a.udur, (size_t)nu, &a.udur));
   PLDA_TRY(st.in(a.ma, (size_t)(T - R), &a.ma));          // (all three may be NULL when no recording has a merge: T == R)
@@ -2173,6 +2174,28 @@ int plda_der_timed(plda_handle *h, const int32_t *turn_start, const int32_t *tur
     const DerTimedArgs a{turn_start, turn_dur, turn_spk, turn_off, seg_start, seg_dur, hyp, offsets, R, uem_start, uem_dur, uem_off,
                          collar, flags, nullptr, nullptr, nullptr, nullptr, 0, nullptr, counts, nullptr, map};
     return der_timed_host(h, "der_timed", a, false);
+  });
+}
+
+int plda_der_timed_ovl_dev(plda_handle *h, const int32_t *dturn_start, const int32_t *dturn_dur, const int32_t *dturn_spk,
+                           const int64_t *turn_off, const int32_t *dseg_start, const int32_t *dseg_dur, const int32_t *dhyp,
+                           const int32_t *dhyp2, const int64_t *offsets, int64_t R, const int32_t *duem_start, const int32_t *duem_dur,
+                           const int64_t *uem_off, int32_t collar, int32_t flags, int64_t *dcounts, int32_t *dmap) {
+  return device_entry(h, "plda_der_timed_ovl_dev", [&] {
+    const DerTimedArgs a{dturn_start, dturn_dur, dturn_spk, turn_off, dseg_start, dseg_dur, dhyp, offsets, R, duem_start, duem_dur, uem_off,
+                         collar, flags, nullptr, nullptr, nullptr, nullptr, 0, nullptr, dcounts, nullptr, dmap, dhyp2};
+    return der_timed_device(h, "der_timed_ovl", a, false);
+  });
+}
+
+int plda_der_timed_ovl(plda_handle *h, const int32_t *turn_start, const int32_t *turn_dur, const int32_t *turn_spk, const int64_t *turn_off,
+                       const int32_t *seg_start, const int32_t *seg_dur, const int32_t *hyp, const int32_t *hyp2, const int64_t *offsets,
+                       int64_t R, const int32_t *uem_start, const int32_t *uem_dur, const int64_t *uem_off, int32_t collar, int32_t flags,
+                       int64_t *counts, int32_t *map) {
+  return entry(h, "plda_der_timed_ovl", [&] {
+    const DerTimedArgs a{turn_start, turn_dur, turn_spk, turn_off, seg_start, seg_dur, hyp, offsets, R, uem_start, uem_dur, uem_off,
+                         collar, flags, nullptr, nullptr, nullptr, nullptr, 0, nullptr, counts, nullptr, map, hyp2};
+    return der_timed_host(h, "der_timed_ovl", a, false);
   });
 }
 
@@ -2215,60 +2238,96 @@ int plda_vbx_dev(plda_handle *h, const double *dY, int64_t D, const double *dPhi
   });
 }
 
+int plda_vbx_top2_dev(plda_handle *h, const double *dY, int64_t D, const double *dPhi, const int32_t *dlabels_in, const int64_t *offsets,
+                      int64_t R, double Fa, double Fb, double loop_prob, double init_smoothing, int64_t max_iters, double epsilon,
+                      int32_t *dlabels, int32_t *dn_clusters, double *dgamma, const int64_t *gamma_off, double *dpi, const int64_t *pi_off,
+                      double *delbo, int32_t *diters, int32_t *dlabels2, double *dpost2) {
+  return device_entry(h, "plda_vbx_top2_dev", [&] {
+    return vbx_device(h, dY, D, dPhi, dlabels_in, offsets, R, Fa, Fb, loop_prob, init_smoothing, max_iters, epsilon, dlabels,
+                      dn_clusters, dgamma, gamma_off, dpi, pi_off, delbo, diters, dlabels2, dpost2);
+  });
+}
+
+namespace {
+// the host form of plda_vbx and plda_vbx_top2 (labels2 and post2 NULL in the former)
+int vbx_host(plda_handle *h, const double *Y, int64_t D, const double *Phi, const int32_t *labels_in, const int64_t *offsets, int64_t R,
+             double Fa, double Fb, double loop_prob, double init_smoothing, int64_t max_iters, double epsilon, int32_t *labels,
+             int32_t *n_clusters, double *gamma, const int64_t *gamma_off, double *pi, const int64_t *pi_off, double *elbo,
+             int32_t *iters, int32_t *labels2, double *post2) {
+  if (!h->fitted) return fail(h, PLDA_E_NOT_FITTED, "vbx: model not fitted");
+  if (!Y) return fail(h, PLDA_E_INVAL, "vbx: Y is NULL");
+  if (!labels_in) return fail(h, PLDA_E_INVAL, "vbx: labels_in is NULL");
+  PLDA_TRY(vbx_validate(h, "vbx", D, offsets, R, Fa, Fb, loop_prob, max_iters, labels, n_clusters, gamma, gamma_off, pi, pi_off));
+  PLDA_TRY(set_device(h));
+  const int64_t T = offsets[R];
+  // the intervals of gamma and pi keep their layout, relative to their first entry, in device temporaries
+  const int64_t g0 = gamma ? gamma_off[0] : 0, gn = gamma ? gamma_off[R] - g0 : 0;
+  const int64_t p0 = pi ? pi_off[0] : 0, pn = pi ? pi_off[R] - p0 : 0;
+  if (gn < 0 || pn < 0) return fail(h, PLDA_E_INVAL, "vbx: gamma_off / pi_off must ascend");
+  std::vector<int64_t> grel, prel;
+  if (gamma) { grel.resize((size_t)R + 1); for (int64_t r = 0; r <= R; ++r) grel[(size_t)r] = gamma_off[r] - g0; }
+  if (pi) { prel.resize((size_t)R + 1); for (int64_t r = 0; r <= R; ++r) prel[(size_t)r] = pi_off[r] - p0; }
+  Staged st(h);
+  const double *dY, *dPhi;
+  const int32_t *dLin;
+  Tmp dL, dK, dG, dP, dE, dI, dL2, dP2;
+  PLDA_TRY(st.in(Y, (size_t)T * D, &dY));
+  PLDA_TRY(st.in(Phi, (size_t)D, &dPhi));
+  PLDA_TRY(st.in(labels_in, (size_t)T, &dLin));
+  PLDA_HIP(h, dL.alloc((size_t)T * 4));
+  PLDA_HIP(h, dK.alloc((size_t)R * 4));
+  if (gamma) PLDA_HIP(h, dG.alloc((size_t)gn * 8));
+  if (pi) PLDA_HIP(h, dP.alloc((size_t)pn * 8));
+  if (elbo) PLDA_HIP(h, dE.alloc((size_t)R * max_iters * 8));
+  if (iters) PLDA_HIP(h, dI.alloc((size_t)R * 4));
+  if (labels2) PLDA_HIP(h, dL2.alloc((size_t)T * 4));
+  if (post2) PLDA_HIP(h, dP2.alloc((size_t)T * 8));
+  const int rc = vbx_device(h, dY, D, dPhi, dLin, offsets, R, Fa, Fb, loop_prob,
+                            init_smoothing, max_iters, epsilon, dL.as<int32_t>(), dK.as<int32_t>(), gamma ? dG.as<double>() : nullptr,
+                            gamma ? grel.data() : nullptr, pi ? dP.as<double>() : nullptr, pi ? prel.data() : nullptr,
+                            elbo ? dE.as<double>() : nullptr, iters ? dI.as<int32_t>() : nullptr,
+                            labels2 ? dL2.as<int32_t>() : nullptr, post2 ? dP2.as<double>() : nullptr);
+  if (rc != PLDA_OK) { (void)hipStreamSynchronize(h->stream); return rc; }
+  // gamma and pi: only T_r x S_r (S_r) entries of every interval are the call's to write
+  std::vector<int32_t> hl((size_t)T);
+  std::vector<double> hg((size_t)gn), hp((size_t)pn);
+  PLDA_HIP(h, hipMemcpyAsync(labels, dL.p, (size_t)T * 4, hipMemcpyDeviceToHost, h->stream));
+  PLDA_HIP(h, hipMemcpyAsync(n_clusters, dK.p, (size_t)R * 4, hipMemcpyDeviceToHost, h->stream));
+  if (gn) PLDA_HIP(h, hipMemcpyAsync(hg.data(), dG.p, (size_t)gn * 8, hipMemcpyDeviceToHost, h->stream));
+  if (pn) PLDA_HIP(h, hipMemcpyAsync(hp.data(), dP.p, (size_t)pn * 8, hipMemcpyDeviceToHost, h->stream));
+  if (elbo) PLDA_HIP(h, hipMemcpyAsync(elbo, dE.p, (size_t)R * max_iters * 8, hipMemcpyDeviceToHost, h->stream));
+  if (iters) PLDA_HIP(h, hipMemcpyAsync(iters, dI.p, (size_t)R * 4, hipMemcpyDeviceToHost, h->stream));
+  if (labels2) PLDA_HIP(h, hipMemcpyAsync(labels2, dL2.p, (size_t)T * 4, hipMemcpyDeviceToHost, h->stream));
+  if (post2) PLDA_HIP(h, hipMemcpyAsync(post2, dP2.p, (size_t)T * 8, hipMemcpyDeviceToHost, h->stream));
+  PLDA_HIP(h, hipStreamSynchronize(h->stream));
+  for (int64_t r = 0; r < R && (gamma || pi); ++r) {
+    int S = 0;
+    for (int64_t t = offsets[r]; t < offsets[r + 1]; ++t) S = std::max(S, (int)labels_in[t] + 1);
+    const int64_t n = offsets[r + 1] - offsets[r];
+    if (gamma) std::copy(hg.begin() + grel[(size_t)r], hg.begin() + grel[(size_t)r] + n * S, gamma + gamma_off[r]);
+    if (pi) std::copy(hp.begin() + prel[(size_t)r], hp.begin() + prel[(size_t)r] + S, pi + pi_off[r]);
+  }
+  return PLDA_OK;
+}
+}  // namespace
+
 int plda_vbx(plda_handle *h, const double *Y, int64_t D, const double *Phi, const int32_t *labels_in, const int64_t *offsets, int64_t R,
              double Fa, double Fb, double loop_prob, double init_smoothing, int64_t max_iters, double epsilon, int32_t *labels,
              int32_t *n_clusters, double *gamma, const int64_t *gamma_off, double *pi, const int64_t *pi_off, double *elbo,
              int32_t *iters) {
-  return entry(h, "plda_vbx", [&]() -> int {
-    if (!h->fitted) return fail(h, PLDA_E_NOT_FITTED, "vbx: model not fitted");
-    if (!Y) return fail(h, PLDA_E_INVAL, "vbx: Y is NULL");
-    if (!labels_in) return fail(h, PLDA_E_INVAL, "vbx: labels_in is NULL");
-    PLDA_TRY(vbx_validate(h, "vbx", D, offsets, R, Fa, Fb, loop_prob, max_iters, labels, n_clusters, gamma, gamma_off, pi, pi_off));
-    PLDA_TRY(set_device(h));
-    const int64_t T = offsets[R];
-    // the intervals of gamma and pi keep their layout, relative to their first entry, in device temporaries
-    const int64_t g0 = gamma ? gamma_off[0] : 0, gn = gamma ? gamma_off[R] - g0 : 0;
-    const int64_t p0 = pi ? pi_off[0] : 0, pn = pi ? pi_off[R] - p0 : 0;
-    if (gn < 0 || pn < 0) return fail(h, PLDA_E_INVAL, "vbx: gamma_off / pi_off must ascend");
-    std::vector<int64_t> grel, prel;
-    if (gamma) { grel.resize((size_t)R + 1); for (int64_t r = 0; r <= R; ++r) grel[(size_t)r] = gamma_off[r] - g0; }
-    if (pi) { prel.resize((size_t)R + 1); for (int64_t r = 0; r <= R; ++r) prel[(size_t)r] = pi_off[r] - p0; }
-    Staged st(h);
-    const double *dY, *dPhi;
-    const int32_t *dLin;
-    Tmp dL, dK, dG, dP, dE, dI;
-    PLDA_TRY(st.in(Y, (size_t)T * D, &dY));
-    PLDA_TRY(st.in(Phi, (size_t)D, &dPhi));
-    PLDA_TRY(st.in(labels_in, (size_t)T, &dLin));
-    PLDA_HIP(h, dL.alloc((size_t)T * 4));
-    PLDA_HIP(h, dK.alloc((size_t)R * 4));
-    if (gamma) PLDA_HIP(h, dG.alloc((size_t)gn * 8));
-    if (pi) PLDA_HIP(h, dP.alloc((size_t)pn * 8));
-    if (elbo) PLDA_HIP(h, dE.alloc((size_t)R * max_iters * 8));
-    if (iters) PLDA_HIP(h, dI.alloc((size_t)R * 4));
-    const int rc = vbx_device(h, dY, D, dPhi, dLin, offsets, R, Fa, Fb, loop_prob,
-                              init_smoothing, max_iters, epsilon, dL.as<int32_t>(), dK.as<int32_t>(), gamma ? dG.as<double>() : nullptr,
-                              gamma ? grel.data() : nullptr, pi ? dP.as<double>() : nullptr, pi ? prel.data() : nullptr,
-                              elbo ? dE.as<double>() : nullptr, iters ? dI.as<int32_t>() : nullptr);
-    if (rc != PLDA_OK) { (void)hipStreamSynchronize(h->stream); return rc; }
-    // gamma and pi: only T_r x S_r (S_r) entries of every interval are the call's to write
-    std::vector<int32_t> hl((size_t)T);
-    std::vector<double> hg((size_t)gn), hp((size_t)pn);
-    PLDA_HIP(h, hipMemcpyAsync(labels, dL.p, (size_t)T * 4, hipMemcpyDeviceToHost, h->stream));
-    PLDA_HIP(h, hipMemcpyAsync(n_clusters, dK.p, (size_t)R * 4, hipMemcpyDeviceToHost, h->stream));
-    if (gn) PLDA_HIP(h, hipMemcpyAsync(hg.data(), dG.p, (size_t)gn * 8, hipMemcpyDeviceToHost, h->stream));
-    if (pn) PLDA_HIP(h, hipMemcpyAsync(hp.data(), dP.p, (size_t)pn * 8, hipMemcpyDeviceToHost, h->stream));
-    if (elbo) PLDA_HIP(h, hipMemcpyAsync(elbo, dE.p, (size_t)R * max_iters * 8, hipMemcpyDeviceToHost, h->stream));
-    if (iters) PLDA_HIP(h, hipMemcpyAsync(iters, dI.p, (size_t)R * 4, hipMemcpyDeviceToHost, h->stream));
-    PLDA_HIP(h, hipStreamSynchronize(h->stream));
-    for (int64_t r = 0; r < R && (gamma || pi); ++r) {
-      int S = 0;
-      for (int64_t t = offsets[r]; t < offsets[r + 1]; ++t) S = std::max(S, (int)labels_in[t] + 1);
-      const int64_t n = offsets[r + 1] - offsets[r];
-      if (gamma) std::copy(hg.begin() + grel[(size_t)r], hg.begin() + grel[(size_t)r] + n * S, gamma + gamma_off[r]);
-      if (pi) std::copy(hp.begin() + prel[(size_t)r], hp.begin() + prel[(size_t)r] + S, pi + pi_off[r]);
-    }
-    return PLDA_OK;
+  return entry(h, "plda_vbx", [&] {
+    return vbx_host(h, Y, D, Phi, labels_in, offsets, R, Fa, Fb, loop_prob, init_smoothing, max_iters, epsilon, labels, n_clusters, gamma,
+                    gamma_off, pi, pi_off, elbo, iters, nullptr, nullptr);
+  });
+}
+
+int plda_vbx_top2(plda_handle *h, const double *Y, int64_t D, const double *Phi, const int32_t *labels_in, const int64_t *offsets,
+                  int64_t R, double Fa, double Fb, double loop_prob, double init_smoothing, int64_t max_iters, double epsilon,
+                  int32_t *labels, int32_t *n_clusters, double *gamma, const int64_t *gamma_off, double *pi, const int64_t *pi_off,
+                  double *elbo, int32_t *iters, int32_t *labels2, double *post2) {
+  return entry(h, "plda_vbx_top2", [&] {
+    return vbx_host(h, Y, D, Phi, labels_in, offsets, R, Fa, Fb, loop_prob, init_smoothing, max_iters, epsilon, labels, n_clusters, gamma,
+                    gamma_off, pi, pi_off, elbo, iters, labels2, post2);
   });
 }
 

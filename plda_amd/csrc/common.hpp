@@ -578,7 +578,10 @@ int der_sweep_device(plda_handle *h, const int32_t *dma, const int32_t *dmb, con
 // ---- der_time.hip (time-based DER: overlapped reference speech, collar, UEM; every *_off array is a HOST array) ----
 // one recording's scored atoms, as der_atoms_kernel leaves them and der.hip's solve reads them
 struct DerTimedRec { long long aoff; int natoms, sh; unsigned long long umask; };   // first atom; atoms; distinct hyp labels; union of masks
-struct DerTimedDev { const DerTimedRec *recs; const int *ticks; const int *seg; const unsigned long long *mask; };
+struct DerTimedDev {
+  const DerTimedRec *recs; const int *ticks; const int *seg; const unsigned long long *mask;
+  const int *hyp2;      // plda_der_timed_ovl: the second label of every segment; NULL: one label per segment
+};
 // the arguments of plda_der_timed* (sweep: ma, mb, mc, thresholds, Q, minc, n_clusters; otherwise hyp, map)
 struct DerTimedArgs {
   const int32_t *tstart, *tdur, *tspk; const int64_t *turn_off;
@@ -587,6 +590,7 @@ struct DerTimedArgs {
   int32_t collar, flags;
   const int32_t *ma, *mb; const double *mc; const double *thresholds; int64_t Q; const int32_t *minc;
   int64_t *counts; int32_t *n_clusters, *map;
+  const int32_t *hyp2 = nullptr;      // plda_der_timed_ovl: the second hypothesis label of every segment (nullable)
 };
 int der_timed_plan(plda_handle *h, int64_t n_turns, int64_t n_seg, int64_t n_uem, int32_t collar, int32_t *out);
 // the host-side argument check (pointers are only compared with NULL; the host forms run it before they allocate or upload)
@@ -606,7 +610,7 @@ int vbx_validate(plda_handle *h, const char *fn, int64_t D, const int64_t *offse
 int vbx_device(plda_handle *h, const double *dY, int64_t D, const double *dPhi, const int32_t *dlabels_in, const int64_t *offsets,
                int64_t R, double Fa, double Fb, double loop_prob, double init_smoothing, int64_t max_iters, double epsilon,
                int32_t *dlabels, int32_t *dn_clusters, double *dgamma, const int64_t *gamma_off, double *dpi, const int64_t *pi_off,
-               double *delbo, int32_t *diters);
+               double *delbo, int32_t *diters, int32_t *dlabels2 = nullptr, double *dpost2 = nullptr);
 int project_rows_device(plda_handle *h, const double *dX, int64_t R, int Din, double *dout);
 
 // ---- frontend.hip ----

@@ -18,6 +18,9 @@
 //   der_solve_timed_kernel  the same body (der_solve_body<HBM, SWEEP, ATOMS = true>) on the scored atoms that der_time.hip cuts
 //                       from reference turns, hypothesis segments, collar and UEM (K20): an atom of `ticks` ticks adds them
 //                       to C[i][j] for every reference speaker i of its 64-bit mask
+//   der_solve_ovl_kernel    the atom form with up to two hypothesis labels per segment (K21, plda_der_timed_ovl; der_solve_body<HBM,
+//                       false, true, OVL = true>): the labels present range over hyp and hyp2, an atom adds its ticks to C[i][j]
+//                       for both labels of its segment, and nhyp in the four counters is the number of labels >= 0
 //
 // One workgroup of der_solve_kernel: (1) the labels present, as bit sets (64 bits of reference, 4096 of hypothesis), give
 // the compact numbering by prefix population counts; (2) the matrix is zeroed and filled with integer atomics, the four
@@ -157,7 +160,8 @@ template <> struct DerMat<true> {
 // One workgroup's solve.  ATOMS = false: the segment form (ref, hyp, dur per segment).  ATOMS = true: the time-based form
 // (der_time.hip): the reference side is the scored atoms of the recording (ticks, 64-bit reference mask, segment index or -1)
 // and the union of their masks; the hypothesis label of an atom is that of its segment (SWEEP: the slot of its segment).
-template <bool HBM, bool SWEEP, bool ATOMS>
+// OVL (with ATOMS, without SWEEP; K21): a segment carries the label set {hyp[t]} u {td.hyp2[t]}, -1 = no such label.
+template <bool HBM, bool SWEEP, bool ATOMS, bool OVL = false>
 __device__ __forceinline__ void der_solve_body(const int *__restrict__ ref, const int *__restrict__ hyp,
                                                const int *__restrict__ dur, const int *__restrict__ ma,
                                                const int *__restrict__ mb, const DerRec *__restrict__ tab,
@@ -215,6 +219,7 @@ __device__ __forceinline__ void der_solve_body(const int *__restrict__ ref, cons
     if constexpr (SWEEP) return parent[t];
     else return hyp[rc.off + t];
   };
+  static_assert(!OVL || (ATOMS && !SWEEP), "the second label belongs to the time-based form against hyp");
 
   // (1b) the labels present
   if (tid < 64) hbits[tid] = 0;
@@ -226,6 +231,10 @@ __device__ __forceinline__ void der_solve_body(const int *__restrict__ ref, cons
       for (int t = tid; t < n; t += DER_T) {
         const int b = hyp_of(t);
         if (b >= 0) atomicOr(&hbits[(b >> 6) & 63], 1ull << (b & 63));
+        if constexpr (OVL) {
+          const int b2 = td.hyp2[rc.off + t];
+          if (b2 >= 0) atomicOr(&hbits[(b2 >> 6) & 63], 1ull << (b2 & 63));
+        }
       }
       if (tid == 0) rm = tr.umask;
     } else {
@@ -261,16 +270,8 @@ __device__ __forceinline__ void der_solve_body(const int *__restrict__ ref, cons
   __syncthreads();
   long long c_speech = 0, c_miss = 0, c_fa = 0, c_both = 0;
   if constexpr (ATOMS) {
-    // an atom of `ticks` ticks with nref = popcount(mask) reference speakers and nhyp = 0 or 1 hypothesis speakers
-    for (int e = tid; e < tr.natoms; e += DER_T) {
-      const long long d = td.ticks[tr.aoff + e];
-      const unsigned long long am = td.mask[tr.aoff + e] & rmask;
-      const int sg = td.seg[tr.aoff + e], b = sg >= 0 && sg < n ? hyp_of(sg) : -1;
-      const int nref = __popcll(am), nhyp = b >= 0 ? 1 : 0;
-      c_speech += d * nref;
-      c_miss += d * (nref > nhyp ? nref - nhyp : 0);
-      c_fa += d * (nhyp > nref ? nhyp - nref : 0);
-      c_both += d * (nref < nhyp ? nref : nhyp);
+    // an atom of `ticks` ticks with nref = popcount(mask) reference speakers and nhyp = 0 or 1 (OVL: or 2) hypothesis speakers
+    auto fill = [&](int b, unsigned long long am, long long d) {
       if (b >= 0 && b < DER_MAX_HYP && d) {
         const int k = b >> 6, j = hbase[k] + __popcll(hbits[k] & der_below(b & 63));
         for (unsigned long long mk = am; mk; mk &= mk - 1) {
@@ -278,6 +279,20 @@ __device__ __forceinline__ void der_solve_body(const int *__restrict__ ref, cons
           atomicAdd(reinterpret_cast<unsigned long long *>(mat.c) + (long long)i * w + j, (unsigned long long)d);
         }
       }
+    };
+    for (int e = tid; e < tr.natoms; e += DER_T) {
+      const long long d = td.ticks[tr.aoff + e];
+      const unsigned long long am = td.mask[tr.aoff + e] & rmask;
+      const int sg = td.seg[tr.aoff + e], b = sg >= 0 && sg < n ? hyp_of(sg) : -1;
+      int b2 = -1;
+      if constexpr (OVL) b2 = sg >= 0 && sg < n ? td.hyp2[rc.off + sg] : -1;
+      const int nref = __popcll(am), nhyp = (b >= 0 ? 1 : 0) + (b2 >= 0 ? 1 : 0);
+      c_speech += d * nref;
+      c_miss += d * (nref > nhyp ? nref - nhyp : 0);
+      c_fa += d * (nhyp > nref ? nhyp - nref : 0);
+      c_both += d * (nref < nhyp ? nref : nhyp);
+      fill(b, am, d);
+      if constexpr (OVL) fill(b2, am, d);
     }
   } else
   for (int t = tid; t < n; t += DER_T) {
@@ -384,11 +399,20 @@ __global__ __launch_bounds__(DER_T) void der_solve_timed_kernel(const int *__res
   der_solve_body<HBM, SWEEP, true>(nullptr, hyp, nullptr, ma, mb, tab, scratch, counts, n_clusters, map, td);
 }
 
-template <bool HBM, bool SWEEP, bool ATOMS> int der_solve_attr(plda_handle *h) {
+// the time-based form with up to two hypothesis labels per segment (plda_der_timed_ovl; td.hyp2 is not NULL)
+template <bool HBM>
+__global__ __launch_bounds__(DER_T) void der_solve_ovl_kernel(const int *__restrict__ hyp, const DerRec *__restrict__ tab,
+                                                              long long *scratch, long long *__restrict__ counts,
+                                                              int *__restrict__ map, const DerTimedDev td) {
+  der_solve_body<HBM, false, true, true>(nullptr, hyp, nullptr, nullptr, nullptr, tab, scratch, counts, nullptr, map, td);
+}
+
+template <bool HBM, bool SWEEP, bool ATOMS, bool OVL = false> int der_solve_attr(plda_handle *h) {
   static DeviceOnce attr;
   if (attr.needed(h->device)) {
-    const void *fn = ATOMS ? reinterpret_cast<const void *>(&der_solve_timed_kernel<HBM, SWEEP>)
-                           : reinterpret_cast<const void *>(&der_solve_kernel<HBM, SWEEP>);
+    const void *fn = OVL     ? reinterpret_cast<const void *>(&der_solve_ovl_kernel<HBM>)
+                     : ATOMS ? reinterpret_cast<const void *>(&der_solve_timed_kernel<HBM, SWEEP>)
+                             : reinterpret_cast<const void *>(&der_solve_kernel<HBM, SWEEP>);
     PLDA_HIP(h, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, DER_LDS_BYTES));
     attr.done(h->device);
   }
@@ -463,7 +487,11 @@ int der_solve_enqueue(plda_handle *h, std::vector<DerRec> &items, std::vector<De
   PLDA_HIP(h, hipMemcpyAsync(h->der_tab.p, tab.data(), tab.size() * sizeof(DerRec), hipMemcpyHostToDevice, h->stream));
   const DerRec *dtab = h->der_tab.as<DerRec>();
   long long *scratch = h->der_scratch.as<long long>();
-  if (td) {
+  const bool ovl = !SWEEP && td && td->hyp2;
+  if (ovl) {
+    PLDA_TRY((der_solve_attr<false, false, true, true>(h)));
+    PLDA_TRY((der_solve_attr<true, false, true, true>(h)));
+  } else if (td) {
     PLDA_TRY((der_solve_attr<false, SWEEP, true>(h)));
     PLDA_TRY((der_solve_attr<true, SWEEP, true>(h)));
   } else {
@@ -475,7 +503,11 @@ int der_solve_enqueue(plda_handle *h, std::vector<DerRec> &items, std::vector<De
     for (const Launch &L : launches) {
       for (int64_t c0 = 0; c0 < L.count; c0 += 1 << 20) {
         const unsigned c = (unsigned)std::min<int64_t>(1 << 20, L.count - c0);
-        if (td && L.hbm)
+        if (ovl && L.hbm)
+          der_solve_ovl_kernel<true><<<c, DER_T, (size_t)L.lds, h->stream>>>(dhyp, dtab + L.first + c0, scratch, dcounts, dmap, *td);
+        else if (ovl)
+          der_solve_ovl_kernel<false><<<c, DER_T, (size_t)L.lds, h->stream>>>(dhyp, dtab + L.first + c0, nullptr, dcounts, dmap, *td);
+        else if (td && L.hbm)
           der_solve_timed_kernel<true, SWEEP><<<c, DER_T, (size_t)L.lds, h->stream>>>(dhyp, dma, dmb, dtab + L.first + c0, scratch, dcounts,
                                                                                       dn_clusters, dmap, *td);
         else if (td)

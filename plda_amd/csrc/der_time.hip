@@ -9,7 +9,8 @@
 //     (1) events.  Every boundary is one 64-bit key (time + 2^20) << 32 | kind << 28 | payload, in a slot fixed by its index:
 //         2 per reference turn (start, end; payload = speaker), 4 more per turn when collar > 0 (the zones [b - c, b + c) of
 //         both boundaries), 2 per hypothesis segment (payload = segment index), 2 per UEM interval.  An empty interval and an
-//         entry that breaks the contract (counted) leave their slots at the all-ones key, which sorts behind every event.
+//         entry that breaks the contract (counted; with hyp2, plda_der_timed_ovl, also a second label without a first or
+//         equal to it) leave their slots at the all-ones key, which sorts behind every event.
 //         The kinds put every end before every start of the same tick.
 //     (2) a bitonic sort of the P keys (P = the slot count rounded up to a power of two, at least 256): in LDS up to
 //         P = 16384 (128 KiB of the 160); <HBM> above that the keys live in handle scratch (8 P bytes, at most 1 MiB per
@@ -96,13 +97,15 @@ __device__ __forceinline__ void dt_bitonic_tile(unsigned long long *buf, int bas
 }
 
 // Resources on gfx950 (kernel-resource-usage): <false> 47 VGPRs, <true> 55 VGPRs; no scratch memory, no spills in either.
-// (der_solve_timed_kernel, der.hip: 44 VGPRs in the LDS class, 40 in the scratch class, as the segment form; no scratch, no spills.)
+// (der_solve_timed_kernel, der.hip: 44 VGPRs in the LDS class, 40 in the scratch class, as the segment form; no scratch, no spills.
+// der_solve_ovl_kernel, the two-label form of K21: the same 44 and 40.  hyp2, K21, left this kernel's 47 and 55 as they were.)
 template <bool HBM>
 __global__ __launch_bounds__(DT_T) void der_atoms_kernel(const int *__restrict__ tstart, const int *__restrict__ tdur,
                                                          const int *__restrict__ tspk, const int *__restrict__ sstart,
                                                          const int *__restrict__ sdur, const int *__restrict__ hyp,
-                                                         const int *__restrict__ ustart, const int *__restrict__ udur,
-                                                         const DtRec *__restrict__ tab, int collar, int flags, int has_uem,
+                                                         const int *__restrict__ hyp2, const int *__restrict__ ustart,
+                                                         const int *__restrict__ udur, const DtRec *__restrict__ tab,
+                                                         int collar, int flags, int has_uem,
                                                          unsigned long long *events, unsigned long long *stat,
                                                          DerTimedRec *__restrict__ recs, int *__restrict__ aticks,
                                                          int *__restrict__ aseg, unsigned long long *__restrict__ amask_out) {
@@ -143,8 +146,11 @@ __global__ __launch_bounds__(DT_T) void der_atoms_kernel(const int *__restrict__
   }
   for (int t = tid; t < rc.n; t += DT_T) {
     const int st = sstart[rc.soff + t], du = sdur[rc.soff + t], b = hyp ? hyp[rc.soff + t] : 0;
-    if (st < 0 || du < 0 || (long long)st + du > DT_MAX_TIME || b < -1 || b >= PLDA_AHC_MAX) { ++bad; continue; }
+    const int b2 = hyp2 ? hyp2[rc.soff + t] : -1;        // (a second label needs a first one, and another one)
+    if (st < 0 || du < 0 || (long long)st + du > DT_MAX_TIME || b < -1 || b >= PLDA_AHC_MAX || b2 < -1 || b2 >= PLDA_AHC_MAX ||
+        (b2 >= 0 && (b < 0 || b2 == b))) { ++bad; continue; }
     if (hyp && b >= 0) atomicOr(&hbits[b >> 6], 1ull << (b & 63));
+    if (b2 >= 0) atomicOr(&hbits[b2 >> 6], 1ull << (b2 & 63));
     if (du == 0) continue;
     keys[hyp0 + 2 * t] = dt_key(st, DT_HYP_START, t);
     keys[hyp0 + 2 * t + 1] = dt_key(st + du, DT_HYP_END, t);
@@ -382,16 +388,17 @@ int der_timed_device(plda_handle *h, const char *fn, const DerTimedArgs &a, bool
     PLDA_HIP(h, hipMemcpyAsync(dtab, tab.data(), tab.size() * sizeof(DtRec), hipMemcpyHostToDevice, h->stream));
     TraceScope ts(h, "der.atoms");
     unsigned long long *dev = h->der_events.as<unsigned long long>();
+    const int32_t *hyp = sweep ? nullptr : a.hyp, *hyp2 = sweep ? nullptr : a.hyp2;      // (the sweep's labels are the replayed slots)
     for (const Launch &L : launches)
       for (int64_t c0 = 0; c0 < L.count; c0 += 1 << 20) {
         const unsigned c = (unsigned)std::min<int64_t>(1 << 20, L.count - c0);
         if (L.hbm)
-          der_atoms_kernel<true><<<c, DT_T, 8 * DT_LDS_EVENTS + DT_FIXED_BYTES, h->stream>>>(a.tstart, a.tdur, a.tspk, a.sstart, a.sdur, sweep ? nullptr : a.hyp,
-                                                                         a.ustart, a.udur, dtab + L.first + c0, a.collar, a.flags,
-                                                                         a.uem_off ? 1 : 0, dev, dstat, drecs, dticks, dseg, dmask);
+          der_atoms_kernel<true><<<c, DT_T, 8 * DT_LDS_EVENTS + DT_FIXED_BYTES, h->stream>>>(
+              a.tstart, a.tdur, a.tspk, a.sstart, a.sdur, hyp, hyp2, a.ustart, a.udur, dtab + L.first + c0, a.collar, a.flags,
+              a.uem_off ? 1 : 0, dev, dstat, drecs, dticks, dseg, dmask);
         else
           der_atoms_kernel<false><<<c, DT_T, (size_t)(8 * L.P + DT_FIXED_BYTES), h->stream>>>(
-              a.tstart, a.tdur, a.tspk, a.sstart, a.sdur, sweep ? nullptr : a.hyp, a.ustart, a.udur, dtab + L.first + c0, a.collar, a.flags,
+              a.tstart, a.tdur, a.tspk, a.sstart, a.sdur, hyp, hyp2, a.ustart, a.udur, dtab + L.first + c0, a.collar, a.flags,
               a.uem_off ? 1 : 0, nullptr, dstat, drecs, dticks, dseg, dmask);
         PLDA_LAUNCH_CHECK(h);
       }
@@ -405,9 +412,10 @@ int der_timed_device(plda_handle *h, const char *fn, const DerTimedArgs &a, bool
   if (rc != PLDA_OK) return rc;
   PLDA_HIP(h, e);
   if (bad[0] || bad[1])
-    return fail(h, PLDA_E_INVAL, "%s: %llu invalid entries (a label or a time out of range) and %llu invalid events (a turn that starts "
-                                 "inside another turn of its speaker, or two hypothesis segments that share a tick)", fn, bad[0], bad[1]);
-  const DerTimedDev td{drecs, dticks, dseg, dmask};
+    return fail(h, PLDA_E_INVAL, "%s: %llu invalid entries (a label or a time out of range%s) and %llu invalid events (a turn that starts "
+                                 "inside another turn of its speaker, or two hypothesis segments that share a tick)", fn, bad[0],
+                a.hyp2 ? ", a second label without a first or equal to it" : "", bad[1]);
+  const DerTimedDev td{drecs, dticks, dseg, dmask, sweep ? nullptr : a.hyp2};     // (hyp2 given: the solve's two-label form)
   return der_timed_solve(h, fn, recs.data(), td, a.hyp, a.ma, a.mb, a.mc, a.offsets, R, a.thresholds, sweep ? a.Q : 0, a.minc, a.counts,
                          a.n_clusters, a.map);
 }

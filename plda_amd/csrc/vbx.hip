@@ -9,6 +9,7 @@
 //
 //   vbx_check_kernel   the non-finite values of y, the labels outside [0, 64), the bad entries of Phi (three integer counters;
 //                      a call that meets one fails and the kernels behind it write nothing) and S = 1 + max label per recording
+//                      (plda_vbx_top2: + labels2 and post2, the second speaker of every segment, selected where the arg-max is)
 //   vbx_kernel         <HBM = false> the per-recording state (b, a / gamma, beta, c, m, G, alpha, invL, sqrt Phi, Phi) in LDS;
 //                      <HBM = true>  the same arrays in handle scratch.  pi, N and the reduction slots are in LDS in both.
 //
@@ -126,14 +127,16 @@ __device__ __forceinline__ void vbx_combine(double x, int SP, int S, int lane, i
 
 // Resource report of the two instantiations (gfx950, -O3, 512 threads: 256 VGPRs per lane are there).  Neither uses scratch
 // memory; the scalar registers the unrolled chain overflows are kept in VGPR lanes, not in memory:
-//   vbx_kernel<false>   VGPRs 160   SGPRs 106 (107 spilled to VGPR lanes)   ScratchSize 0   LDS 7760 static + the state
-//   vbx_kernel<true>    VGPRs 211   SGPRs 106 (160 spilled to VGPR lanes)   ScratchSize 0   LDS 7760 static
+//   vbx_kernel<false>   VGPRs 160   SGPRs 106 (110 spilled to VGPR lanes)   ScratchSize 0   LDS 7760 static + the state
+//   vbx_kernel<true>    VGPRs 211   SGPRs 106 (165 spilled to VGPR lanes)   ScratchSize 0   LDS 7760 static
+// (with the second-speaker pass of K21; without it the SGPR spills were 107 and 160, the VGPRs the same)
 template <bool HBM>
 __global__ __launch_bounds__(VBX_T) void vbx_kernel(const double *__restrict__ Y, const double *__restrict__ Phi,
                                                     const int *__restrict__ lab_in, const VbxRec *__restrict__ tab, double *scratch,
                                                     const unsigned long long *__restrict__ stat, const VbxPar par,
                                                     int *__restrict__ labels, int *__restrict__ n_clusters, double *__restrict__ gamma_out,
-                                                    double *__restrict__ pi_out, double *__restrict__ elbo_out, int *__restrict__ iters_out) {
+                                                    double *__restrict__ pi_out, double *__restrict__ elbo_out, int *__restrict__ iters_out,
+                                                    int *__restrict__ labels2, double *__restrict__ post2) {
   extern __shared__ double vbx_smem[];
   __shared__ double pi[64], Ns[64], qs[64], es[64], g0[64], acc[64];
   __shared__ double part[VBX_W * 64];
@@ -378,6 +381,26 @@ __global__ __launch_bounds__(VBX_T) void vbx_kernel(const double *__restrict__ Y
     if (tid == 0) sc_k = k;
   }
   __syncthreads();
+  // the second speaker (plda_vbx_top2): the same butterfly over the speakers that are somebody's first choice, the row's own
+  // first left out; lab still holds the first choice in the initial numbering.  No candidate (k = 1): -1 and posterior 0
+  if (labels2 || post2) {
+    for (int tb = wave * GR; tb < T; tb += VBX_W * GR) {
+      const int t = tb + sub, tt = t < T ? t : T - 1;
+      const bool cand = act && s != lab[tt] && first[s] != INT_MAX;
+      double v = cand ? A[tt * S + sc] : -INFINITY;
+      int bi = cand ? s : INT_MAX;
+      for (int o = 1; o < SP; o <<= 1) {
+        const double ov = __shfl_xor(v, o);
+        const int oi = __shfl_xor(bi, o);
+        if (oi != INT_MAX && (bi == INT_MAX || ov > v || (ov == v && oi < bi))) { v = ov; bi = oi; }
+      }
+      if (t < T && s == 0) {
+        if (labels2) labels2[rc.off + t] = bi == INT_MAX ? -1 : rank[bi];
+        if (post2) post2[rc.off + t] = bi == INT_MAX ? 0.0 : v;
+      }
+    }
+    __syncthreads();                       // (every row has read its first choice before lab is renumbered)
+  }
   for (int t = tid; t < T; t += VBX_T) lab[t] = rank[lab[t]];
   if (tid == 0) { n_clusters[rc.r] = sc_k; if (iters_out) iters_out[rc.r] = iters; }
   if (gamma_out)
@@ -449,7 +472,7 @@ int vbx_validate(plda_handle *h, const char *fn, int64_t D, const int64_t *offse
 int vbx_device(plda_handle *h, const double *dY, int64_t D64, const double *dPhi, const int32_t *dlabels_in, const int64_t *offsets,
                int64_t R, double Fa, double Fb, double loop_prob, double init_smoothing, int64_t max_iters, double epsilon,
                int32_t *dlabels, int32_t *dn_clusters, double *dgamma, const int64_t *gamma_off, double *dpi, const int64_t *pi_off,
-               double *delbo, int32_t *diters) {
+               double *delbo, int32_t *diters, int32_t *dlabels2, double *dpost2) {
   const char *fn = "vbx";
   if (!h->fitted) return fail(h, PLDA_E_NOT_FITTED, "%s: model not fitted", fn);
   if (!dY) return fail(h, PLDA_E_INVAL, "%s: Y is NULL", fn);
@@ -561,10 +584,10 @@ int vbx_device(plda_handle *h, const double *dY, int64_t D64, const double *dPhi
     for (const Launch &L : launches) {
       if (L.hbm)
         vbx_kernel<true><<<(unsigned)L.count, VBX_T, 0, h->stream>>>(dY, dPhi, dlabels_in, dtab + L.first, h->vbx_scratch.as<double>(), dstat, par,
-                                                                    dlabels, dn_clusters, dgamma, dpi, delbo, diters);
+                                                                    dlabels, dn_clusters, dgamma, dpi, delbo, diters, dlabels2, dpost2);
       else
         vbx_kernel<false><<<(unsigned)L.count, VBX_T, L.lds, h->stream>>>(dY, dPhi, dlabels_in, dtab + L.first, nullptr, dstat, par, dlabels,
-                                                                         dn_clusters, dgamma, dpi, delbo, diters);
+                                                                         dn_clusters, dgamma, dpi, delbo, diters, dlabels2, dpost2);
       PLDA_LAUNCH_CHECK(h);
     }
   }

@@ -14,11 +14,13 @@ on purpose: JER.
 The time-based form (csrc/der_time.hip; include/plda_hip.h, "time-based diarisation error rate") scores TIME, with overlapped
 reference speech, a collar and UEM regions -- md-eval's definition on integer ticks:
 
-    der_timed(engine, turns, seg_start, seg_dur, hyp, offsets, collar=0, uem=None, skip_overlap=False)   a DerResult
+    der_timed(engine, turns, seg_start, seg_dur, hyp, offsets, collar=0, uem=None, skip_overlap=False, hyp2=None)   a DerResult
     sweep_timed(engine, merges, turns, seg_start, seg_dur, offsets, thresholds, ...)                     a SweepResult
     plan_timed(engine, n_turns, n_seg, n_uem=0, collar=0)                                                the event-sort class
 
 turns = (turn_start, turn_dur, turn_spk, turn_off), what rttm.pack_turns returns first; uem = (uem_start, uem_dur, uem_off).
+hyp2 int [T] (K21) is the second hypothesis speaker of every segment, -1 = none: a segment then carries up to two labels
+(diarize.vbx(..., return_second=True) and diarize.apply_overlap make one; rttm.pack_hyp cuts one from RTTM turns).
 """
 import ctypes as C
 
@@ -226,10 +228,27 @@ def _times(start, dur, n, name):
     return np.ascontiguousarray(out[0], np.int32), np.ascontiguousarray(out[1], np.int32)
 
 
-def timed_args(turns, seg_start, seg_dur, offsets, collar, uem, skip_overlap):
+def _second(hyp, hyp2, t):
+    """hyp2 int32 [T] checked against hyp: in [-1, MAX_HYP), and a second label needs a first one and differs from it."""
+    hyp2 = _labels(hyp2, t, "hyp2", MAX_HYP)
+    hyp = _labels(hyp, t, "hyp", MAX_HYP)
+    if ((hyp2 >= 0) & (hyp < 0)).any():
+        raise ValueError("hyp2 >= 0 needs hyp >= 0: a second speaker without a first")
+    if ((hyp2 >= 0) & (hyp2 == hyp)).any():
+        raise ValueError("hyp2 must differ from hyp where it is >= 0")
+    return hyp2
+
+
+def timed_args(turns, seg_start, seg_dur, offsets, collar, uem, skip_overlap, hyp=None, hyp2=None):
     """The argument check shared by der_timed and sweep_timed, before any device work ->
     (turn_start, turn_dur, turn_spk, turn_off, seg_start, seg_dur, offsets, uem_start, uem_dur, uem_off, collar, flags); the
-    three uem entries are None without a UEM.  Disjointness (same-speaker turns, segments) is the device's check."""
+    three uem entries are None without a UEM.  Disjointness (same-speaker turns, segments) is the device's check.  With hyp2
+    (and hyp) the tuple is followed by hyp2 as int32 [T]: its shape, dtype and range, hyp2 >= 0 only where hyp >= 0, hyp2 != hyp."""
+    if hyp2 is not None:
+        if hyp is None:
+            raise ValueError("hyp2 needs hyp")
+        base = timed_args(turns, seg_start, seg_dur, offsets, collar, uem, skip_overlap)
+        return base + (_second(hyp, hyp2, int(base[6][-1])),)
     offsets = _offsets(offsets)
     r, t = len(offsets) - 1, int(offsets[-1])
     if turns is None or len(turns) != 4:
@@ -260,15 +279,22 @@ def plan_timed(engine, n_turns, n_seg, n_uem=0, collar=0):
             "events": (6 if collar > 0 else 2) * int(n_turns) + 2 * int(n_seg) + 2 * int(n_uem)}
 
 
-def der_timed(engine, turns, seg_start, seg_dur, hyp, offsets, collar=0, uem=None, skip_overlap=False, return_map=False):
+def der_timed(engine, turns, seg_start, seg_dur, hyp, offsets, collar=0, uem=None, skip_overlap=False, return_map=False, hyp2=None):
     """Time-based DER of R recordings: reference turns (they may overlap across speakers), disjoint hypothesis segments
     seg_start, seg_dur, hyp int [T] (-1 = non-speech), recording r owning segments offsets[r] .. offsets[r+1]; collar in
-    ticks; uem the scored regions or None; skip_overlap: md-eval's -1.  Returns a DerResult."""
-    ts, td, tk, toff, ss, sd, offsets, us, ud, uoff, collar, flags = timed_args(turns, seg_start, seg_dur, offsets, collar, uem, skip_overlap)
+    ticks; uem the scored regions or None; skip_overlap: md-eval's -1; hyp2 int [T] or None: the second speaker of every
+    segment (-1 = none; plda_der_timed_ovl).  Returns a DerResult."""
+    targs = timed_args(turns, seg_start, seg_dur, offsets, collar, uem, skip_overlap, hyp, hyp2)
+    ts, td, tk, toff, ss, sd, offsets, us, ud, uoff, collar, flags = targs[:12]
     hyp = _labels(hyp, int(offsets[-1]), "hyp", MAX_HYP)
     r = len(offsets) - 1
     counts = np.empty((r, 4), np.int64)
     map_ = np.empty((r, MAX_REF), np.int32) if return_map else None
+    if hyp2 is not None:
+        hyp2 = targs[12]
+        N.check(engine._h, engine._lib.plda_der_timed_ovl(engine._h, _p(ts), _p(td), _p(tk), _p(toff), _p(ss), _p(sd), _p(hyp), _p(hyp2),
+                                                          _p(offsets), r, _p(us), _p(ud), _p(uoff), collar, flags, _p(counts), _p(map_)))
+        return DerResult(counts, map_)
     N.check(engine._h, engine._lib.plda_der_timed(engine._h, _p(ts), _p(td), _p(tk), _p(toff), _p(ss), _p(sd), _p(hyp), _p(offsets), r,
                                                   _p(us), _p(ud), _p(uoff), collar, flags, _p(counts), _p(map_)))
     return DerResult(counts, map_)

@@ -11,7 +11,9 @@ emission model, initialised from the clustering (csrc/vbx.hip; include/plda_hip.
                                       (Kaldi's --target-energy=t; csrc/dense_pca.hip), one workgroup per recording
     ahc_dense_pca(engine, x, offsets, t, ...)   the same blocks clustered and dropped (MPlda.cluster(..., target_energy=t))
     dense_pca_plan(engine, n, d)      the dispatch class a recording of n segments at dimension d takes there
-    vbx(engine, y, offsets, labels)   resegments R recordings of projected vectors from initial labels, one workgroup each
+    vbx(engine, y, offsets, labels)   resegments R recordings of projected vectors from initial labels, one workgroup each;
+                                      return_second=True: + every segment's second most likely speaker and its posterior
+    apply_overlap(labels2, post2, ...)   pure NumPy: where to keep the second speaker (a detector's mask, a posterior floor)
     vbx_plan(engine, t, s, d)         the dispatch class a recording of t segments, s initial speakers, dimension d takes
     MPlda.resegment(x, offsets, labels, ...)   raw segment vectors in: plda_project_rows, then vbx
     MPlda.diarize(x, offsets, ...)    cluster, then resegment
@@ -19,7 +21,7 @@ emission model, initialised from the clustering (csrc/vbx.hip; include/plda_hip.
 A recording is merged bottom-up while the best pair's average score is at least `threshold` (None: no threshold) and more than
 `num_speakers` clusters are left (None: 1).  Out of scope, on purpose: Kaldi's per-recording mean subtraction, its two-pass
 clustering of very long recordings; for VBx: more than 64 initial speakers, several workgroups on one
-recording, overlap handling.  The diarisation error rate, and the threshold sweep that cut() serves on the host, live in
+recording, an overlap detector, a third speaker.  The diarisation error rate, and the threshold sweep that cut() serves on the host, live in
 plda_amd/der.py; RTTM files in plda_amd/rttm.py.  Length normalisation and the LDA fit before the model are the embedding
 chain's (K18: plda_amd/embed.py, MPlda.fit_embedding / set_embedding): with one attached, cluster / resegment / diarize take
 the extractor's output as it is.
@@ -273,12 +275,15 @@ def vbx_args(y, offsets, labels, phi, Fa, Fb, loop_prob, max_iters):
 
 
 def vbx(engine, y, offsets, labels, phi=None, Fa=0.3, Fb=17.0, loop_prob=0.99, init_smoothing=5.0, max_iters=40, epsilon=1e-4,
-        return_posteriors=False):
+        return_posteriors=False, return_second=False):
     """VBx resegmentation of R recordings: y [T, D] segment vectors in the model's diagonalised space WITHOUT length
     normalisation (MPlda.project_rows), recording r owning rows offsets[r] .. offsets[r+1], `labels` the initial labels (the
     AHC's), phi [D] the between-class variance (None: the model's psi).  Returns (labels int32 [T], n_clusters int32 [R][, info]),
     labels 0 .. k-1 per recording by ascending smallest member; info = {"gamma": a list of [T_r, S_r] arrays (columns in the
-    initial numbering), "pi": a list of [S_r] arrays, "elbo": [R, max_iters] (NaN from iters[r] on), "iters": int32 [R]}."""
+    initial numbering), "pi": a list of [S_r] arrays, "elbo": [R, max_iters] (NaN from iters[r] on), "iters": int32 [R]}.
+    return_second=True: (labels, n_clusters, labels2 int32 [T], post2 float64 [T][, info]) -- the second most likely speaker
+    of every segment among those that are some segment's first choice, numbered as labels, and its posterior; -1 and 0 in a
+    recording with one speaker (plda_vbx_top2; the VBx recipe's --output-2nd).  apply_overlap decides where to use it."""
     y, offsets, labels, phi, spk = vbx_args(y, offsets, labels, phi, Fa, Fb, loop_prob, max_iters)
     r, t = len(offsets) - 1, int(offsets[-1])
     out_l, out_k = np.empty(t, np.int32), np.empty(r, np.int32)
@@ -287,12 +292,42 @@ def vbx(engine, y, offsets, labels, phi=None, Fa=0.3, Fb=17.0, loop_prob=0.99, i
         goff, poff = offsets_of(np.diff(offsets) * spk), offsets_of(spk)
         gamma, pi = np.empty(int(goff[-1]), np.float64), np.empty(int(poff[-1]), np.float64)
         elbo, iters = np.empty((r, int(max_iters)), np.float64), np.empty(r, np.int32)
-    N.check(engine._h, engine._lib.plda_vbx(engine._h, _p(y), y.shape[1], _p(phi), _p(labels), _p(offsets), r, float(Fa), float(Fb),
-                                            float(loop_prob), float(init_smoothing), int(max_iters), float(epsilon), _p(out_l), _p(out_k),
-                                            _p(gamma), _p(goff), _p(pi), _p(poff), _p(elbo), _p(iters)))
+    args = (engine._h, _p(y), y.shape[1], _p(phi), _p(labels), _p(offsets), r, float(Fa), float(Fb), float(loop_prob),
+            float(init_smoothing), int(max_iters), float(epsilon), _p(out_l), _p(out_k), _p(gamma), _p(goff), _p(pi), _p(poff), _p(elbo),
+            _p(iters))
+    out = (out_l, out_k)
+    if return_second:
+        out_l2, out_p2 = np.empty(t, np.int32), np.empty(t, np.float64)
+        N.check(engine._h, engine._lib.plda_vbx_top2(*args, _p(out_l2), _p(out_p2)))
+        out += (out_l2, out_p2)
+    else:
+        N.check(engine._h, engine._lib.plda_vbx(*args))
     if not return_posteriors:
-        return out_l, out_k
+        return out
     sizes = np.diff(offsets)
     info = {"gamma": [gamma[goff[q]:goff[q + 1]].reshape(int(sizes[q]), int(spk[q])) for q in range(r)],
             "pi": [pi[poff[q]:poff[q + 1]] for q in range(r)], "elbo": elbo, "iters": iters}
-    return out_l, out_k, info
+    return out + (info,)
+
+
+def apply_overlap(labels2, post2, overlap=None, min_posterior=None):
+    """Where the second speaker of vbx(..., return_second=True) is kept: labels2[t] where overlap[t] holds (an external
+    overlap detector's per-segment bool mask), and also where post2[t] >= min_posterior; -1 everywhere else.  At least one of
+    the two must be given.  Returns int32 [T], what der.der_timed takes as hyp2 and rttm.write as labels2.  Pure NumPy."""
+    if overlap is None and min_posterior is None:
+        raise ValueError("apply_overlap needs overlap, min_posterior or both")
+    labels2 = np.asarray(labels2)
+    post2 = np.asarray(post2, np.float64)
+    if labels2.ndim != 1 or labels2.dtype.kind not in "iu" or post2.shape != labels2.shape:
+        raise ValueError("labels2 (integer) and post2 must be 1-D arrays of one length")
+    keep = np.zeros(labels2.shape, bool)
+    if overlap is not None:
+        overlap = np.asarray(overlap)
+        if overlap.dtype != np.bool_ or overlap.shape != labels2.shape:
+            raise ValueError("overlap must be a bool mask with one entry per segment")
+        keep |= overlap
+    if min_posterior is not None:
+        if isinstance(min_posterior, bool) or not isinstance(min_posterior, (int, float, np.integer, np.floating)) or np.isnan(min_posterior):
+            raise ValueError("min_posterior must be a number")
+        keep |= post2 >= float(min_posterior)
+    return np.where(keep & (labels2 >= 0), labels2, -1).astype(np.int32)

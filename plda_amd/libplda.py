@@ -585,10 +585,11 @@ class MPlda(object):
         self._ck(self._lib.plda_project_rows_dev(self._h, C.c_void_p(int(dX)), int(R), int(Din), C.c_void_p(int(dout))))
 
     def resegment(self, x, offsets, labels, Fa=0.3, Fb=17.0, loop_prob=0.99, init_smoothing=5.0, max_iters=40, epsilon=1e-4,
-                  return_posteriors=False):
+                  return_posteriors=False, return_second=False):
         """VBx resegmentation (plda_amd/diarize.py: vbx): x [T, Din] raw segment vectors, recording r owning rows offsets[r] ..
         offsets[r+1], `labels` the initial labels (cluster()'s).  The rows are projected into the model's diagonalised space
-        (project_rows), the between-class variance is the model's psi.  Returns (labels, n_clusters[, info])."""
+        (project_rows), the between-class variance is the model's psi.  Returns (labels, n_clusters[, info]);
+        return_second=True: (labels, n_clusters, labels2, post2[, info]), every segment's second speaker and its posterior."""
         from . import diarize
         X = self._rows(x, "Segment vectors")
         offsets = np.ascontiguousarray(offsets, np.int64)
@@ -596,16 +597,23 @@ class MPlda(object):
             raise ValueError("offsets must hold R + 1 >= 2 entries ending at the number of rows of x")
         diarize.vbx_args(np.zeros((X.shape[0], 1)), offsets, labels, None, Fa, Fb, loop_prob, max_iters)   # (before any device work)
         return diarize.vbx(self, self._project(X), offsets, labels, None, Fa, Fb, loop_prob, init_smoothing, max_iters, epsilon,
-                           return_posteriors)
+                           return_posteriors, return_second)
 
-    def diarize(self, x, offsets, threshold=0.0, num_speakers=None, target_energy=None, **vbx):
+    def diarize(self, x, offsets, threshold=0.0, num_speakers=None, target_energy=None, overlap=None, min_posterior=None, **vbx):
         """cluster(x, offsets, threshold, num_speakers), then resegment(x, offsets, its labels, **vbx).  target_energy goes to
-        the clustering only: VBx keeps working on the full model."""
+        the clustering only: VBx keeps working on the full model.  With overlap (a per-segment bool mask) or min_posterior the
+        return is (labels, n_clusters, labels2): the second speaker where diarize.apply_overlap keeps it, -1 elsewhere."""
+        if (overlap is not None or min_posterior is not None) and (vbx.get("return_second") or vbx.get("return_posteriors")):
+            raise ValueError("overlap / min_posterior return (labels, n_clusters, labels2): call resegment for the posteriors")
         if target_energy is None:
             labels, _ = self.cluster(x, offsets, threshold, num_speakers)
         else:
             labels, _ = self.cluster(x, offsets, threshold, num_speakers, target_energy=target_energy)
-        return self.resegment(x, offsets, labels, **vbx)
+        if overlap is None and min_posterior is None:
+            return self.resegment(x, offsets, labels, **vbx)
+        from . import diarize
+        labels, ncl, labels2, post2 = self.resegment(x, offsets, labels, return_second=True, **vbx)
+        return labels, ncl, diarize.apply_overlap(labels2, post2, overlap, min_posterior)
 
     def vbx_dev(self, dY, D, dPhi, dlabels_in, offsets, dlabels, dn_clusters, Fa=0.3, Fb=17.0, loop_prob=0.99, init_smoothing=5.0,
                 max_iters=40, epsilon=1e-4, dgamma=None, gamma_off=None, dpi=None, pi_off=None, delbo=None, diters=None):
@@ -618,6 +626,18 @@ class MPlda(object):
             float(init_smoothing), int(max_iters), float(epsilon), vp(dlabels), vp(dn_clusters), vp(dgamma),
             _ptr(gamma_off) if gamma_off is not None else None, vp(dpi), _ptr(pi_off) if pi_off is not None else None, vp(delbo),
             vp(diters)))
+
+    def vbx_top2_dev(self, dY, D, dPhi, dlabels_in, offsets, dlabels, dn_clusters, dlabels2=None, dpost2=None, Fa=0.3, Fb=17.0,
+                     loop_prob=0.99, init_smoothing=5.0, max_iters=40, epsilon=1e-4, dgamma=None, gamma_off=None, dpi=None, pi_off=None,
+                     delbo=None, diters=None):
+        """vbx_dev with the second speaker: dlabels2 int32 [T] and dpost2 float64 [T] (raw device addresses, each may be None)."""
+        def vp(x):
+            return C.c_void_p(int(x)) if x else None
+        self._ck(self._lib.plda_vbx_top2_dev(
+            self._h, vp(dY), int(D), vp(dPhi), vp(dlabels_in), _ptr(offsets), len(offsets) - 1, float(Fa), float(Fb), float(loop_prob),
+            float(init_smoothing), int(max_iters), float(epsilon), vp(dlabels), vp(dn_clusters), vp(dgamma),
+            _ptr(gamma_off) if gamma_off is not None else None, vp(dpi), _ptr(pi_off) if pi_off is not None else None, vp(delbo),
+            vp(diters), vp(dlabels2), vp(dpost2)))
 
     def ahc_matrix_dev(self, dscores, block_off, offsets, has_threshold, threshold, min_clusters, dlabels, dn_clusters,
                        dmerge_a=None, dmerge_b=None, dmerge_cost=None):
@@ -703,12 +723,23 @@ class MPlda(object):
         res = der.sweep(self, merges, offsets, ref, thresholds, dur)
         return float(res.thresholds[res.best]), res
 
-    def der_timed(self, turns, seg_start, seg_dur, hyp, offsets, collar=0, uem=None, skip_overlap=False, return_map=False):
+    def der_timed(self, turns, seg_start, seg_dur, hyp, offsets, collar=0, uem=None, skip_overlap=False, return_map=False, hyp2=None):
         """Time-based DER of R recordings (plda_amd/der.py: der_timed): reference turns (turn_start, turn_dur, turn_spk,
         turn_off) that may overlap across speakers, disjoint hypothesis segments, a collar in ticks, UEM regions, md-eval's
-        skip-overlap switch.  Returns a plda_amd.der.DerResult."""
+        skip-overlap switch; hyp2: the second speaker of every segment, -1 = none.  Returns a plda_amd.der.DerResult."""
         from . import der
-        return der.der_timed(self, turns, seg_start, seg_dur, hyp, offsets, collar, uem, skip_overlap, return_map)
+        return der.der_timed(self, turns, seg_start, seg_dur, hyp, offsets, collar, uem, skip_overlap, return_map, hyp2)
+
+    def der_timed_ovl_dev(self, dturns, turn_off, dseg_start, dseg_dur, dhyp, dhyp2, offsets, dcounts, dmap=None, duem=None,
+                          uem_off=None, collar=0, flags=0):
+        """plda_der_timed_ovl_dev: der_timed_dev with dhyp2 int32 [T], the second label of every segment (None: der_timed_dev)."""
+        def vp(x):
+            return C.c_void_p(int(x)) if x else None
+        du = duem if duem is not None else (None, None)
+        self._ck(self._lib.plda_der_timed_ovl_dev(
+            self._h, vp(dturns[0]), vp(dturns[1]), vp(dturns[2]), _ptr(turn_off), vp(dseg_start), vp(dseg_dur), vp(dhyp), vp(dhyp2),
+            _ptr(offsets), len(offsets) - 1, vp(du[0]), vp(du[1]), _ptr(uem_off) if uem_off is not None else None, int(collar),
+            int(flags), vp(dcounts), vp(dmap)))
 
     def der_timed_dev(self, dturns, turn_off, dseg_start, dseg_dur, dhyp, offsets, dcounts, dmap=None, duem=None, uem_off=None,
                       collar=0, flags=0):

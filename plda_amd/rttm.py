@@ -1,10 +1,13 @@
 """plda_amd/rttm.py -- RTTM files (NIST Rich Transcription Time Marked; the SPEAKER lines diarisation tools exchange) and the
 step from reference turns to the per-segment labels plda_amd/der.py scores.  Pure Python / NumPy, no device.
 
-    write(file, rec_ids, offsets, labels, start, dur, tick=0.01)   one SPEAKER line per maximal run of abutting segments
+    write(file, rec_ids, offsets, labels, start, dur, tick=0.01, labels2=None)   one SPEAKER line per maximal run of abutting
+                                                                   segments of a speaker; labels2: a second speaker per segment
     read(file, tick=0.01)                                          {recording: [(start, dur, speaker)]}, times in ticks
     segment_labels(turns, seg_start, seg_dur)                      the reference speaker of every segment, by greatest overlap
     pack_turns(turns_by_recording, rec_ids)                        the packed turn arrays of der.der_timed, + sorted names
+    pack_hyp(turns_by_recording, rec_ids)                          hypothesis turns cut into disjoint segments of at most two
+                                                                   speakers: der.der_timed's seg_start, seg_dur, hyp, hyp2, offsets
     read_uem(file, tick=0.01)                                      {recording: [(start, dur)]} of a UEM file
     cut_windows(start, dur, offsets)                               overlapping sliding windows -> disjoint segments
 
@@ -26,20 +29,41 @@ def _decimals(tick):
     return d
 
 
-def write(file, rec_ids, offsets, labels, start, dur, tick=0.01):
+def write(file, rec_ids, offsets, labels, start, dur, tick=0.01, labels2=None):
     """Write the segments of R recordings: recording r, named rec_ids[r], owns segments offsets[r] .. offsets[r+1] with
     labels[t] (-1: non-speech, not written), start[t] and dur[t] in ticks.  Consecutive segments of one label that abut
-    (start + dur of one = start of the next) are one SPEAKER line; the speaker of label k is named "spk<k>"."""
+    (start + dur of one = start of the next) are one SPEAKER line; the speaker of label k is named "spk<k>".
+    labels2 (None, or one entry per segment, -1: none) is a second speaker of the segment: the segment then contributes to
+    both speakers' lines, abutting segments are merged per speaker, and a recording's lines come in order of their start
+    (ties: the lower label).  With labels2=None the output is what it was without the argument."""
     offsets = np.asarray(offsets, np.int64)
     labels, start, dur = (np.asarray(a, np.int64) for a in (labels, start, dur))
     if len(rec_ids) != len(offsets) - 1:
         raise ValueError("rec_ids must name every recording")
     if not (labels.shape == start.shape == dur.shape == (int(offsets[-1]),)):
         raise ValueError("labels, start and dur must hold one entry per segment")
+    if labels2 is not None:
+        labels2 = np.asarray(labels2, np.int64)
+        if labels2.shape != labels.shape:
+            raise ValueError("labels2 must hold one entry per segment")
     nd = _decimals(tick)
     f, close = _open(file, "w")
     try:
         for r, rec in enumerate(rec_ids):
+            if labels2 is not None:
+                runs = {}                                # label -> [[start, end]], the segments in their given order
+                for t in range(int(offsets[r]), int(offsets[r + 1])):
+                    for k in {int(labels[t]), int(labels2[t])}:
+                        if k < 0:
+                            continue
+                        mine = runs.setdefault(k, [])
+                        if mine and mine[-1][1] == start[t]:
+                            mine[-1][1] = int(start[t] + dur[t])
+                        else:
+                            mine.append([int(start[t]), int(start[t] + dur[t])])
+                for s, k, e in sorted((s, k, e) for k, mine in runs.items() for s, e in mine):
+                    f.write("SPEAKER %s 1 %.*f %.*f <NA> <NA> spk%d <NA> <NA>\n" % (rec, nd, s * tick, nd, (e - s) * tick, k))
+                continue
             run = None                                   # [label, start, end]
             for t in list(range(int(offsets[r]), int(offsets[r + 1]))) + [None]:
                 if t is not None and run is not None and labels[t] == run[0] and start[t] == run[2]:
@@ -119,6 +143,34 @@ def pack_turns(turns_by_recording, rec_ids):
         off.append(len(ts))
         names_out.append(names)
     return (np.asarray(ts, np.int32), np.asarray(td, np.int32), np.asarray(tk, np.int32), np.asarray(off, np.int64)), names_out
+
+
+def pack_hyp(turns_by_recording, rec_ids):
+    """Hypothesis turns {recording: [(start, dur, speaker)]} (read's result; they may overlap across speakers) of the
+    recordings rec_ids, cut into disjoint segments for der.der_timed(..., hyp2=): (seg_start, seg_dur, hyp, hyp2 int32 [T],
+    offsets int64 [R + 1]); hyp and hyp2 index the sorted speaker names of their recording.  A segment is a stretch between two
+    consecutive turn boundaries with one or two speakers talking; the lower label is hyp, hyp2 = -1 with one speaker.  Empty
+    turns are dropped; turns of one speaker that overlap count once.
+    A recording with no speech gets one empty segment (hyp = -1): der.der_timed takes no recording without a segment.  A
+    stretch with three or more simultaneous speakers: ValueError, naming the recording and the tick."""
+    ss, sd, h1, h2, off = [], [], [], [], [0]
+    for rec in rec_ids:
+        turns = [(int(s), int(d), k) for s, d, k in turns_by_recording.get(rec, ()) if int(d) > 0]
+        names = sorted({k for _, _, k in turns})
+        index = {k: i for i, k in enumerate(names)}
+        bounds = sorted({b for s, d, _ in turns for b in (s, s + d)})
+        n0 = len(ss)
+        for a, b in zip(bounds[:-1], bounds[1:]):
+            talk = sorted({index[k] for s, d, k in turns if s <= a and b <= s + d})
+            if len(talk) > 2:
+                raise ValueError("%s: %d hypothesis speakers at tick %d (at most 2)" % (rec, len(talk), a))
+            if talk:
+                ss.append(a); sd.append(b - a); h1.append(talk[0]); h2.append(talk[1] if len(talk) > 1 else -1)
+        if len(ss) == n0:
+            ss.append(0); sd.append(0); h1.append(-1); h2.append(-1)
+        off.append(len(ss))
+    i32 = lambda a: np.asarray(a, np.int32)
+    return i32(ss), i32(sd), i32(h1), i32(h2), np.asarray(off, np.int64)
 
 
 def read_uem(file, tick=0.01):
