@@ -57,6 +57,28 @@ typedef struct plda_handle plda_handle;
  *      the module init initlibplda (pldamodule.cpp:371-384) ---- */
 int plda_create(int device, plda_handle **out);
 int plda_destroy(plda_handle *h);
+/* A long-lived handle.  A handle owns growable device scratch and caches that survive between calls, and the law that
+ * governs them is part of its contract: after ANY sequence of earlier successful or refused calls on a handle, a call's
+ * outputs equal, bit for bit, the outputs of the same call on a fresh handle that holds the same model (the model a fresh
+ * handle gets from plda_get_model's arrays through plda_set_model).  Scratch an earlier, larger call filled is never read
+ * before it is written; a cache is keyed on everything it was computed from; a refused call leaves nothing a later call can
+ * see.  tests/test_gpu_handle_history.py holds the entry points to it, the bf16x3 contraction and the one-wave-per-SIMD
+ * kernel's tile tables included (tests/history_cases.py lists, per device buffer of the handle, what reaches it).
+ * What persists BY DESIGN, and is therefore state a caller sets and reads, not history:
+ *   - the PLDA model (plda_fit*, plda_set_model, plda_truncate, plda_smooth, plda_adapt_update, plda_blend_model replace it;
+ *     each bumps the model's epoch, on which every model-derived cache is keyed) and the statistics of the last fit
+ *     (plda_fit_get_stats*, plda_fit_plan, plda_fit_timings);
+ *   - the LDA model (plda_lda_*) and the embedding chain (plda_embed_set / _fit / _clear);
+ *   - the adaptation record between plda_adapt_reset and plda_adapt_update (refused under another model epoch);
+ *   - a prepared test side (plda_score_prepare*_dev) until plda_score_unprepare, a call that repacks the test side, or a new
+ *     model; it is reused only while pointer, size, model epoch, count kind and content fingerprint match;
+ *   - the stream (plda_set_stream), the communicator (plda_comm_*), the profile and trace switches and their records;
+ *   - the dispatch records of the last call: plda_score_last_kernel / _shape, plda_linalg_last_kernels, plda_fit_plan.
+ * What persists as an optimisation and never changes a result's bits: the scoring coefficient tables (uniform or bucketed,
+ * one buffer), K4's padded transform, the one-trial host coefficients, the dense-PCA covariances of the model, the tile
+ * tables of the one-wave-per-SIMD trials GEMM, the captured Jacobi sweep graph, and the eigenvector warm start of the
+ * simultaneous diagonalisation (dropped at the start of every fit, so that fits are bit-reproducible).  Scratch grows and
+ * is given back by plda_destroy only. */
 const char *plda_last_error(const plda_handle *h);
 int plda_abi_version(void);
 /* bit 0: built with -DPLDA_DIAG=1 (libplda_hip_diag.so: + the measurement arms of the trials GEMM, some of which return

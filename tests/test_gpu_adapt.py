@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import adapt_model as AM
+from history_cases import adapt_and_blend_case
 from conftest import score_tol
 
 pytestmark = pytest.mark.gpu
@@ -433,18 +434,7 @@ def test_adapt_and_blend_on_poisoned_scratch(monkeypatch, d):
     x = AM.sample(*model, 333, d, scale=1.4, offset=0.1 * np.ones(d))
     w = np.random.default_rng(d).random(333)
 
-    def case(eng):
-        eng.set_model(*model)
-        eng.adapt_accumulate(x[:100], w[:100])
-        eng.adapt_accumulate(x[100:], w[100:])
-        st = eng.adapt_stats()
-        res = eng.adapt_update()
-        g = eng.get_model()
-        eng.blend(other, 0.3, 0.6)
-        b = eng.get_model()
-        return dict(s2=st["s2"], s1=st["s1"], tw=np.array([st["tot_weight"]]), s=res.eigenvalues, T=g["transform"], psi=g["psi"],
-                    mean=g["mean"], off=g["offset"], bT=b["transform"], bpsi=b["psi"], bmean=b["mean"])
-
+    case = adapt_and_blend_case(model, other, x, w)        # (shared with tests/test_gpu_handle_history.py)
     a = _twice(monkeypatch, case)
     ref = AM.update_kaldi(*model, AM.record(x, model[0], w))
     _assert_model(dict(mean=a["mean"], transform=a["T"], psi=a["psi"]), ref)

@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 
 import dense_pca_model as dm
+from history_cases import dense_pca_case
 
 pytestmark = pytest.mark.gpu
 
@@ -305,9 +306,7 @@ def test_poisoned_scratch_is_bit_identical(monkeypatch):
             monkeypatch.delenv("PLDA_SCRATCH_POISON", raising=False)
         eng = _engine(model)
         monkeypatch.delenv("PLDA_SCRATCH_POISON", raising=False)
-        blocks, info = diarize.score_dense_pca(eng, x, offsets, 0.5, return_info=True)
-        lab, ncl, mer = diarize.ahc_dense_pca(eng, x, offsets, 0.5, None, 1, True)
-        out[poison] = [b.copy() for b in blocks] + [info["dims"]] + list(info["eigenvalues"]) + [lab, ncl] + list(mer)
+        out[poison] = list(dense_pca_case(x, offsets, 0.5)(eng).values())       # (shared with tests/test_gpu_handle_history.py)
         eng.synchronize()
         del eng
     MPlda(0)                                         # the switch off again for whatever runs next in this process

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 from conftest import make_data, score_tol
+from history_cases import gemm_f64_case, spd_inverse_case, sym_eig_case      # (shared with tests/test_gpu_handle_history.py)
 
 pytestmark = pytest.mark.gpu
 
@@ -350,15 +351,7 @@ def test_sym_eig_on_poisoned_scratch(monkeypatch, n):
     A = rng.standard_normal((n, n))
     G = A @ A.T / n + np.diag(rng.random(n))
     lam_ref = np.sort(np.linalg.eigvalsh(G))[::-1]
-
-    def case(eng):
-        out = {}
-        for method in (0, 1, 2):
-            lam, V, used = eng.sym_eig(G, method)
-            out["lam%d" % method], out["V%d" % method], out["used%d" % method] = lam, V, np.array([used])
-        return out
-
-    a, _ = _twice(monkeypatch, case)
+    a, _ = _twice(monkeypatch, sym_eig_case(G))
     for method in (0, 1, 2):
         lam, V = a["lam%d" % method], a["V%d" % method]
         assert np.abs(lam - lam_ref).max() < 1e-11 * lam_ref.max()
@@ -393,11 +386,7 @@ def test_spd_inverse_on_poisoned_scratch(monkeypatch, d):
     rng = np.random.default_rng(d)
     A = rng.standard_normal((d, d + 5))
     A = A @ A.T + 0.5 * np.eye(d)
-
-    def case(eng):
-        return dict(x=eng.spd_inverse(A))
-
-    a, _ = _twice(monkeypatch, case)
+    a, _ = _twice(monkeypatch, spd_inverse_case(A))
     assert np.abs(a["x"] @ A - np.eye(d)).max() < 1e-9
 
 
@@ -408,13 +397,7 @@ def test_gemm_f64_on_poisoned_scratch(monkeypatch, m, n, k, batch):
     B = rng.standard_normal((batch, k, n)) if batch > 1 else rng.standard_normal((k, n))
     w = rng.random(k)
     Cin = rng.standard_normal((batch, m, n) if batch > 1 else (m, n))
-
-    def case(eng):
-        if batch > 1:
-            return dict(c=eng.gemm_f64(A, B, alpha=0.5, beta=2.0, C_in=Cin))
-        return dict(c=eng.gemm_f64(A, B, alpha=0.5, beta=2.0, C_in=Cin, transA=True, kw=w))
-
-    a, _ = _twice(monkeypatch, case)
+    a, _ = _twice(monkeypatch, gemm_f64_case(A, B, w, Cin, batch))
     ref = 0.5 * (A @ B) + 2.0 * Cin if batch > 1 else 0.5 * (A.T * w) @ B + 2.0 * Cin
     assert np.abs(a["c"] - ref).max() < 1e-12 * max(1.0, np.abs(ref).max()) * np.sqrt(k)
 
