@@ -1268,8 +1268,8 @@ int plda_project_rows(plda_handle *h, const double *X, int64_t R, int32_t Din, d
  *   plda_der_sweep_dev   the merge record, ref, dur (nullable) and the outputs in HBM; offsets [R + 1], thresholds [Q] and
  *                        min_clusters [R] (nullable: 1 everywhere) are HOST arrays.
  *   plda_der_sweep       the same with everything in host memory.
- * OUT OF SCOPE, each on purpose: the Jaccard error rate (JER).  (Overlapped reference speech, a forgiveness collar and
- * time-based scoring are the next section; here a segment has one reference and one hypothesis label.) ---- */
+ * (Overlapped reference speech, a forgiveness collar and time-based scoring are the next section; here a segment has one
+ * reference and one hypothesis label.  The Jaccard error rate and the per-speaker figures are the section after that.) ---- */
 #define PLDA_DER_MAX_REF 64
 int plda_der_plan(plda_handle *h, int64_t Sr, int64_t Sh, int32_t out[3]);
 int plda_der_dev(plda_handle *h, const int32_t *dref, const int32_t *dhyp, const int32_t *ddur, const int64_t *offsets, int64_t R,
@@ -1366,7 +1366,8 @@ int plda_der_sweep(plda_handle *h, const int32_t *merge_a, const int32_t *merge_
  *                              min_clusters [R] (nullable) are HOST arrays.
  *   plda_der_timed_sweep       the same with everything in host memory.
  * OUT OF SCOPE, each on purpose: more than two simultaneous hypothesis speakers; second labels in the threshold sweeps (the AHC
- * has none); JER; per-speaker error breakdowns; word-level or SAD-only scoring; several workgroups on one recording. ---- */
+ * has none); word-level or SAD-only scoring; several workgroups on one recording.  (JER and the per-speaker figures: the next
+ * section.) ---- */
 #define PLDA_DER_MAX_TURNS 16384
 #define PLDA_DER_MAX_UEM 1024
 #define PLDA_DER_SKIP_OVERLAP 1
@@ -1397,6 +1398,96 @@ int plda_der_timed_sweep(plda_handle *h, const int32_t *merge_a, const int32_t *
                          const int32_t *seg_start, const int32_t *seg_dur, const int64_t *offsets, int64_t R, const int32_t *uem_start,
                          const int32_t *uem_dur, const int64_t *uem_off, int32_t collar, int32_t flags, const double *thresholds,
                          int64_t Q, const int32_t *min_clusters, int64_t *counts, int32_t *n_clusters);
+
+/* ---- Jaccard error rate and per-speaker figures (K22; the JER form of csrc/der.hip's solve): the second metric of every
+ * diarisation evaluation (DIHARD, VoxConverse, dscore), beside DER, from the same call.  Everything is an integer, as in the
+ * three sections above: the device result is a function of the input alone.  tests/jer_model.py is the host model.
+ *
+ * PER RECORDING.  The scored ticks, Rset(t) and J(t) are exactly those of plda_der_timed_ovl (in the segment form: the
+ * segments, each weighted by dur; ref = -1 is "no reference speaker", hyp = -1 "no hypothesis speaker").  With C[i][j] as
+ * defined there:
+ *   rt[i]   = #{scored t : i in Rset(t)}
+ *   ht[j]   = #{scored t : j in J(t)}          (ticks without reference speech count; segment form: segments with ref = -1)
+ *   a reference speaker COUNTS if rt[i] >= 1; n_ref = the number of such speakers.  In the timed form this is the set of map
+ *   (the union of the scored masks); in the segment form a label all of whose segments have dur = 0 does not count
+ *   U[i][j] = rt[i] + ht[j] - C[i][j]           (>= 1 whenever rt[i] >= 1)
+ *   w[i][j] = floor(C[i][j] 2^32 / U[i][j])     an integer in [0, 2^32]: the Jaccard index quantised DOWNWARDS to 2^-32
+ *   jsum    = the maximum of sum_i w[i][m(i)] over all one-to-one partial maps m of reference to hypothesis speakers
+ * OUTPUTS.
+ *   jer  int64 [R, 2] = {n_ref, jsum} (sweeps: [Q, R, 2]).  JER = 1 - jsum / (n_ref 2^32) is the CALLER's division, as DER is;
+ *        n_ref = 0 gives {0, 0}.  Pooled over recordings: 1 - sum jsum / (2^32 sum n_ref), dscore's mean over all reference
+ *        speakers of all files.  jsum is unique: jer does not depend on the grid, the batch, the launch grouping, the dispatch
+ *        class or the run.  BOUND: every w is below the exact index times 2^32 by less than 1, so jsum differs from the
+ *        optimum over exact rationals by less than n_ref, i.e. by less than n_ref 2^-32 in units of the index, and JER
+ *        differs from the exact-rational figure by less than 2^-32.
+ *   jmap int32 [R, 64] (nullable) follows the rules of map: caller's label values; -1 for a speaker that is absent, unmapped
+ *        or mapped to a speaker it shares no tick with; one-to-one; it attains jsum; among equal optima it is not canonical
+ *        but a function of the recording's own matrices alone.  jmap may differ from map (example 3).
+ *   spk  int64 [R, 64, 3] (nullable) = {rt[i], I_i, U_i} per reference label value: under jmap I_i = C[i][jmap(i)] and
+ *        U_i = rt[i] + ht[jmap(i)] - I_i; an unmapped speaker has I_i = 0, U_i = rt[i]; a label that is absent (or does not
+ *        count) has {0, 0, 0}.  LAW: sum_i floor(I_i 2^32 / U_i) == jsum.  The speaker's own error rate is 1 - I_i / U_i.
+ *   counts, map (and n_clusters in the sweeps): the values of plda_der / plda_der_timed_ovl / the sweeps on the same input.
+ * EXAMPLES, collar 0.  (1) ref A [0, 10), B [5, 15); hyp X [0, 15): rt = 10, 10; ht = 15; C = 10, 10; w = 2863311530 for
+ * both pairs, one is mapped: jer = {2, 2863311530}, JER = 2/3.  (2) the same reference; hyp [0, 5) X, [5, 10) X + Y, [10, 15)
+ * Y: jer = {2, 8589934592}, JER = 0.  (3) ref A [0, 100); hyp X [0, 40), Y [40, 70), X [200, 1200): counts = {100, 30, 1000,
+ * 30} with map A -> X; w[A][X] = floor(40 2^32 / 1100) = 156180628, w[A][Y] = floor(30 2^32 / 100) = 1288490188: jmap A -> Y,
+ * jer = {1, 1288490188}, JER = 0.7.
+ *
+ * LIMITS.  The timed forms keep theirs (times <= 2^30, so C 2^32 <= 2^62).  The segment forms ADDITIONALLY require the sum of
+ * dur over a recording's segments to be at most 2^30: a violation is found on the device, counted with the other entry
+ * violations, answered with PLDA_E_INVAL, and nothing is written (plda_der itself keeps accepting larger sums).
+ * ERRORS: those of the entry point each one extends (host checks before any device work, device violations counted, no output
+ * written), and jer = NULL is PLDA_E_INVAL.
+ *
+ * PARITY WITH dscore IS UNPINNED: dscore is not on the build machine.  Known differences: dscore scores JER on 10 ms frames
+ * WITHOUT a collar -- here collar, UEM and PLDA_DER_SKIP_OVERLAP apply as given, so pass collar = 0 for dscore's figure;
+ * dscore's map is optimal on exact Jaccard indices, ours on the indices quantised to 2^-32 (the bound above); dscore reports
+ * 100 % for a file with hypothesis speech and no reference speaker, here that file has n_ref = 0 and no rate.
+ *
+ * METHOD.  The solve of plda_der with two additions in the same workgroup: while C is filled, rt and ht are summed with
+ * integer LDS atomics; after the first assignment (counts, map) every entry of the matrix becomes w << 31 | C in place -- ONE
+ * 64-bit division per entry, no second matrix, nothing wider than 64 bits -- and the assignment runs again on w from fresh
+ * potentials and a fresh column state, under the same (value, column) tie rule.  LDS: 512 bytes of rt and 4 (W + 1) bytes of
+ * ht beyond plda_der's (the sweeps keep ht where the map's column labels would be), so the LDS / scratch boundary is the JER
+ * form's own; the scratch class uses plda_der's scratch under the same budget.
+ *
+ *   plda_der_jer_plan              plda_der_plan under the JER form's LDS accounting (the non-sweep form's).
+ *   plda_der_jer[_dev]             plda_der[_dev], then jer, jmap (nullable), spk (nullable).
+ *   plda_der_timed_jer[_dev]       plda_der_timed_ovl[_dev] (hyp2 nullable), then the same three.
+ *   plda_der_jer_sweep[_dev]       plda_der_sweep[_dev], then jer [Q, R, 2].
+ *   plda_der_timed_jer_sweep[_dev] plda_der_timed_sweep[_dev], then jer [Q, R, 2]. ---- */
+int plda_der_jer_plan(plda_handle *h, int64_t Sr, int64_t Sh, int32_t out[3]);
+int plda_der_jer_dev(plda_handle *h, const int32_t *dref, const int32_t *dhyp, const int32_t *ddur, const int64_t *offsets, int64_t R,
+                     int64_t *dcounts, int32_t *dmap, int64_t *djer, int32_t *djmap, int64_t *dspk);
+int plda_der_jer(plda_handle *h, const int32_t *ref, const int32_t *hyp, const int32_t *dur, const int64_t *offsets, int64_t R,
+                 int64_t *counts, int32_t *map, int64_t *jer, int32_t *jmap, int64_t *spk);
+int plda_der_jer_sweep_dev(plda_handle *h, const int32_t *dmerge_a, const int32_t *dmerge_b, const double *dmerge_cost,
+                           const int64_t *offsets, int64_t R, const int32_t *dref, const int32_t *ddur, const double *thresholds,
+                           int64_t Q, const int32_t *min_clusters, int64_t *dcounts, int32_t *dn_clusters, int64_t *djer);
+int plda_der_jer_sweep(plda_handle *h, const int32_t *merge_a, const int32_t *merge_b, const double *merge_cost, const int64_t *offsets,
+                       int64_t R, const int32_t *ref, const int32_t *dur, const double *thresholds, int64_t Q,
+                       const int32_t *min_clusters, int64_t *counts, int32_t *n_clusters, int64_t *jer);
+int plda_der_timed_jer_dev(plda_handle *h, const int32_t *dturn_start, const int32_t *dturn_dur, const int32_t *dturn_spk,
+                           const int64_t *turn_off, const int32_t *dseg_start, const int32_t *dseg_dur, const int32_t *dhyp,
+                           const int32_t *dhyp2, const int64_t *offsets, int64_t R, const int32_t *duem_start, const int32_t *duem_dur,
+                           const int64_t *uem_off, int32_t collar, int32_t flags, int64_t *dcounts, int32_t *dmap, int64_t *djer,
+                           int32_t *djmap, int64_t *dspk);
+int plda_der_timed_jer(plda_handle *h, const int32_t *turn_start, const int32_t *turn_dur, const int32_t *turn_spk, const int64_t *turn_off,
+                       const int32_t *seg_start, const int32_t *seg_dur, const int32_t *hyp, const int32_t *hyp2, const int64_t *offsets,
+                       int64_t R, const int32_t *uem_start, const int32_t *uem_dur, const int64_t *uem_off, int32_t collar, int32_t flags,
+                       int64_t *counts, int32_t *map, int64_t *jer, int32_t *jmap, int64_t *spk);
+int plda_der_timed_jer_sweep_dev(plda_handle *h, const int32_t *dmerge_a, const int32_t *dmerge_b, const double *dmerge_cost,
+                                 const int32_t *dturn_start, const int32_t *dturn_dur, const int32_t *dturn_spk, const int64_t *turn_off,
+                                 const int32_t *dseg_start, const int32_t *dseg_dur, const int64_t *offsets, int64_t R,
+                                 const int32_t *duem_start, const int32_t *duem_dur, const int64_t *uem_off, int32_t collar,
+                                 int32_t flags, const double *thresholds, int64_t Q, const int32_t *min_clusters, int64_t *dcounts,
+                                 int32_t *dn_clusters, int64_t *djer);
+int plda_der_timed_jer_sweep(plda_handle *h, const int32_t *merge_a, const int32_t *merge_b, const double *merge_cost,
+                             const int32_t *turn_start, const int32_t *turn_dur, const int32_t *turn_spk, const int64_t *turn_off,
+                             const int32_t *seg_start, const int32_t *seg_dur, const int64_t *offsets, int64_t R,
+                             const int32_t *uem_start, const int32_t *uem_dur, const int64_t *uem_off, int32_t collar, int32_t flags,
+                             const double *thresholds, int64_t Q, const int32_t *min_clusters, int64_t *counts, int32_t *n_clusters,
+                             int64_t *jer);
 
 /* ---- embedding chain (K18; csrc/embed.hip): what every x-vector / i-vector recipe runs between the extractor and a Gaussian
  * PLDA -- Kaldi's ivector-subtract-global-mean | transform-vec | ivector-normalize-length, the VBx recipe's

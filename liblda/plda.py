@@ -109,20 +109,24 @@ class PLDA(object):
             return self._instance.diarize(x, offsets, threshold, num_speakers, **vbx)
         return self._instance.diarize(x, offsets, threshold, num_speakers, target_energy=target_energy, **vbx)
 
-    def der(self, ref, hyp, offsets, dur=None, return_map=False):
+    def der(self, ref, hyp, offsets, dur=None, return_map=False, jer=False):
         """Diarisation error rate of R recordings from per-segment reference and hypothesis labels (-1 = non-speech), under
-        the optimal speaker mapping; plda_amd/der.py.  Returns a DerResult (counts, der, total[, map])."""
-        return self._instance.der(ref, hyp, offsets, dur, return_map)
+        the optimal speaker mapping; plda_amd/der.py.  Returns a DerResult (counts, der, total[, map]); jer=True adds the
+        Jaccard error rate and the per-speaker figures (jer, jer_counts, jer_map, speakers)."""
+        return self._instance.der(ref, hyp, offsets, dur, return_map, jer)
 
-    def der_timed(self, turns, seg_start, seg_dur, hyp, offsets, collar=0, uem=None, skip_overlap=False, return_map=False, hyp2=None):
+    def der_timed(self, turns, seg_start, seg_dur, hyp, offsets, collar=0, uem=None, skip_overlap=False, return_map=False, hyp2=None,
+                  jer=False):
         """Time-based DER (md-eval's definition on integer ticks): overlapped reference turns, a collar, UEM regions; hyp2: a
-        second hypothesis speaker per segment, -1 = none; plda_amd/der.py: der_timed.  Returns a DerResult."""
-        return self._instance.der_timed(turns, seg_start, seg_dur, hyp, offsets, collar, uem, skip_overlap, return_map, hyp2)
+        second hypothesis speaker per segment, -1 = none; jer=True adds the Jaccard error rate and the per-speaker figures;
+        plda_amd/der.py: der_timed.  Returns a DerResult."""
+        return self._instance.der_timed(turns, seg_start, seg_dur, hyp, offsets, collar, uem, skip_overlap, return_map, hyp2, jer)
 
     def tune_threshold(self, x, offsets, ref, thresholds, dur=None, target_energy=None, **timed):
         """The clustering threshold of the lowest pooled DER on a development set: one clustering (behind the per-recording PCA
         when target_energy is given), one sweep of its merge record.  Returns (threshold, SweepResult); plda_amd/der.py.
-        With turns=, seg_start=, seg_dur= (and collar=, uem=, skip_overlap=) and ref=None the sweep is the time-based one."""
+        With turns=, seg_start=, seg_dur= (and collar=, uem=, skip_overlap=) and ref=None the sweep is the time-based one.
+        metric="jer" picks the threshold of the lowest pooled Jaccard error rate instead (the default, "der", is unchanged)."""
         if target_energy is not None:
             timed["target_energy"] = target_energy
         return self._instance.tune_threshold(x, offsets, ref, thresholds, dur, **timed)

@@ -164,6 +164,15 @@ SIGNATURES = {
     "plda_der_timed_ovl": (C.c_int, [_vp] * 10 + [_i64, _vp, _vp, _vp, _i32, _i32, _vp, _vp]),
     "plda_der_timed_sweep_dev": (C.c_int, [_vp] * 11 + [_i64, _vp, _vp, _vp, _i32, _i32, _vp, _i64, _vp, _vp, _vp]),
     "plda_der_timed_sweep": (C.c_int, [_vp] * 11 + [_i64, _vp, _vp, _vp, _i32, _i32, _vp, _i64, _vp, _vp, _vp]),
+    "plda_der_jer_plan": (C.c_int, [_vp, _i64, _i64, _vp]),
+    "plda_der_jer_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "plda_der_jer": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "plda_der_jer_sweep_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "plda_der_jer_sweep": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "plda_der_timed_jer_dev": (C.c_int, [_vp] * 10 + [_i64, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "plda_der_timed_jer": (C.c_int, [_vp] * 10 + [_i64, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "plda_der_timed_jer_sweep_dev": (C.c_int, [_vp] * 11 + [_i64, _vp, _vp, _vp, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "plda_der_timed_jer_sweep": (C.c_int, [_vp] * 11 + [_i64, _vp, _vp, _vp, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _vp]),
     "plda_vbx_plan": (C.c_int, [_vp, _i64, _i64, _i64, _vp]),
     "plda_vbx_dev": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _f64, _f64, _f64, _f64, _i64, _f64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "plda_vbx": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _f64, _f64, _f64, _f64, _i64, _f64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -2162,6 +2162,11 @@ int der_timed_host(plda_handle *h, const char *fn, DerTimedArgs a, bool sweep) {
   PLDA_TRY(st.out(counts, (size_t)(sweep ? a.Q : 1) * R * 4, &a.counts));
   PLDA_TRY(st.out(ncl, (size_t)(sweep ? a.Q * R : 0), &a.n_clusters));
   PLDA_TRY(st.out(map, (size_t)R * PLDA_DER_MAX_REF, &a.map));
+  long long *jer = a.jo.jer, *spk = a.jo.spk;               // (all three NULL outside the JER form)
+  int *jmap = a.jo.jmap;
+  PLDA_TRY(st.out(jer, (size_t)(sweep ? a.Q : 1) * R * 2, &a.jo.jer));
+  PLDA_TRY(st.out(jmap, (size_t)R * PLDA_DER_MAX_REF, &a.jo.jmap));
+  PLDA_TRY(st.out(spk, (size_t)R * PLDA_DER_MAX_REF * 3, &a.jo.spk));
   return st.finish(der_timed_device(h, fn, a, sweep));
 }
 }  // namespace
@@ -2220,6 +2225,148 @@ int plda_der_timed_sweep(plda_handle *h, const int32_t *merge_a, const int32_t *
     const DerTimedArgs a{turn_start, turn_dur, turn_spk, turn_off, seg_start, seg_dur, nullptr, offsets, R, uem_start, uem_dur, uem_off,
                          collar, flags, merge_a, merge_b, merge_cost, thresholds, Q, min_clusters, counts, n_clusters, nullptr};
     return der_timed_host(h, "der_timed_sweep", a, true);
+  });
+}
+
+// ---------------------------------------------------------------- Jaccard error rate (der.hip's JER form)
+int plda_der_jer_plan(plda_handle *h, int64_t Sr, int64_t Sh, int32_t out[3]) {
+  return entry(h, "plda_der_jer_plan", [&] { return der_jer_plan(h, Sr, Sh, out); });
+}
+
+int plda_der_jer_dev(plda_handle *h, const int32_t *dref, const int32_t *dhyp, const int32_t *ddur, const int64_t *offsets, int64_t R,
+                     int64_t *dcounts, int32_t *dmap, int64_t *djer, int32_t *djmap, int64_t *dspk) {
+  return device_entry(h, "plda_der_jer_dev", [&] {
+    const DerJerOut jo{reinterpret_cast<long long *>(djer), djmap, reinterpret_cast<long long *>(dspk)};
+    return der_device(h, dref, dhyp, ddur, offsets, R, dcounts, dmap, &jo);
+  });
+}
+
+int plda_der_jer(plda_handle *h, const int32_t *ref, const int32_t *hyp, const int32_t *dur, const int64_t *offsets, int64_t R,
+                 int64_t *counts, int32_t *map, int64_t *jer, int32_t *jmap, int64_t *spk) {
+  return entry(h, "plda_der_jer", [&]() -> int {
+    if (!ref) return fail(h, PLDA_E_INVAL, "der_jer: ref is NULL");
+    if (!hyp) return fail(h, PLDA_E_INVAL, "der_jer: hyp is NULL");
+    if (!counts) return fail(h, PLDA_E_INVAL, "der_jer: counts is NULL");
+    if (!jer) return fail(h, PLDA_E_INVAL, "der_jer: jer is NULL");
+    PLDA_TRY(der_validate(h, "der_jer", offsets, R));
+    PLDA_TRY(set_device(h));
+    const int64_t T = offsets[R];
+    Staged st(h);
+    const int32_t *dRef, *dHyp, *dDur;
+    int64_t *dC, *dJ, *dS;
+    int32_t *dM, *dJm;
+    PLDA_TRY(st.in(ref, (size_t)T, &dRef));
+    PLDA_TRY(st.in(hyp, (size_t)T, &dHyp));
+    PLDA_TRY(st.in(dur, (size_t)T, &dDur));
+    PLDA_TRY(st.out(counts, (size_t)R * 4, &dC));
+    PLDA_TRY(st.out(map, (size_t)R * PLDA_DER_MAX_REF, &dM));
+    PLDA_TRY(st.out(jer, (size_t)R * 2, &dJ));
+    PLDA_TRY(st.out(jmap, (size_t)R * PLDA_DER_MAX_REF, &dJm));
+    PLDA_TRY(st.out(spk, (size_t)R * PLDA_DER_MAX_REF * 3, &dS));
+    const DerJerOut jo{reinterpret_cast<long long *>(dJ), dJm, reinterpret_cast<long long *>(dS)};
+    return st.finish(der_device(h, dRef, dHyp, dDur, offsets, R, dC, dM, &jo));
+  });
+}
+
+int plda_der_jer_sweep_dev(plda_handle *h, const int32_t *dmerge_a, const int32_t *dmerge_b, const double *dmerge_cost,
+                           const int64_t *offsets, int64_t R, const int32_t *dref, const int32_t *ddur, const double *thresholds,
+                           int64_t Q, const int32_t *min_clusters, int64_t *dcounts, int32_t *dn_clusters, int64_t *djer) {
+  return device_entry(h, "plda_der_jer_sweep_dev", [&] {
+    const DerJerOut jo{reinterpret_cast<long long *>(djer), nullptr, nullptr};
+    return der_sweep_device(h, dmerge_a, dmerge_b, dmerge_cost, offsets, R, dref, ddur, thresholds, Q, min_clusters, dcounts,
+                            dn_clusters, &jo);
+  });
+}
+
+int plda_der_jer_sweep(plda_handle *h, const int32_t *merge_a, const int32_t *merge_b, const double *merge_cost, const int64_t *offsets,
+                       int64_t R, const int32_t *ref, const int32_t *dur, const double *thresholds, int64_t Q,
+                       const int32_t *min_clusters, int64_t *counts, int32_t *n_clusters, int64_t *jer) {
+  return entry(h, "plda_der_jer_sweep", [&]() -> int {
+    if (!ref) return fail(h, PLDA_E_INVAL, "der_jer_sweep: ref is NULL");
+    if (!counts) return fail(h, PLDA_E_INVAL, "der_jer_sweep: counts is NULL");
+    if (!n_clusters) return fail(h, PLDA_E_INVAL, "der_jer_sweep: n_clusters is NULL");
+    if (!jer) return fail(h, PLDA_E_INVAL, "der_jer_sweep: jer is NULL");
+    PLDA_TRY(der_sweep_validate(h, "der_jer_sweep", offsets, R, thresholds, Q, min_clusters));
+    const int64_t T = offsets[R];
+    if (T > R && !(merge_a && merge_b && merge_cost))
+      return fail(h, PLDA_E_INVAL, "der_jer_sweep: merge_a, merge_b or merge_cost is NULL");
+    PLDA_TRY(set_device(h));
+    Staged st(h);
+    const int32_t *dA, *dB, *dRef, *dDur;
+    const double *dCo;
+    int64_t *dC, *dJ;
+    int32_t *dK;
+    PLDA_TRY(st.in(merge_a, (size_t)(T - R), &dA));       // (all three may be NULL when no recording has a merge: T == R)
+    PLDA_TRY(st.in(merge_b, (size_t)(T - R), &dB));
+    PLDA_TRY(st.in(merge_cost, (size_t)(T - R), &dCo));
+    PLDA_TRY(st.in(ref, (size_t)T, &dRef));
+    PLDA_TRY(st.in(dur, (size_t)T, &dDur));
+    PLDA_TRY(st.out(counts, (size_t)Q * R * 4, &dC));
+    PLDA_TRY(st.out(n_clusters, (size_t)Q * R, &dK));
+    PLDA_TRY(st.out(jer, (size_t)Q * R * 2, &dJ));
+    const DerJerOut jo{reinterpret_cast<long long *>(dJ), nullptr, nullptr};
+    return st.finish(der_sweep_device(h, dA, dB, dCo, offsets, R, dRef, dDur, thresholds, Q, min_clusters, dC, dK, &jo));
+  });
+}
+
+namespace {
+// the JER form of a time-based call: `a` with the three outputs behind it
+void der_timed_jer_args(DerTimedArgs &a, int64_t *jer, int32_t *jmap, int64_t *spk) {
+  a.jer_form = true;
+  a.jo = DerJerOut{reinterpret_cast<long long *>(jer), jmap, reinterpret_cast<long long *>(spk)};
+}
+}  // namespace
+
+int plda_der_timed_jer_dev(plda_handle *h, const int32_t *dturn_start, const int32_t *dturn_dur, const int32_t *dturn_spk,
+                           const int64_t *turn_off, const int32_t *dseg_start, const int32_t *dseg_dur, const int32_t *dhyp,
+                           const int32_t *dhyp2, const int64_t *offsets, int64_t R, const int32_t *duem_start, const int32_t *duem_dur,
+                           const int64_t *uem_off, int32_t collar, int32_t flags, int64_t *dcounts, int32_t *dmap, int64_t *djer,
+                           int32_t *djmap, int64_t *dspk) {
+  return device_entry(h, "plda_der_timed_jer_dev", [&] {
+    DerTimedArgs a{dturn_start, dturn_dur, dturn_spk, turn_off, dseg_start, dseg_dur, dhyp, offsets, R, duem_start, duem_dur, uem_off,
+                         collar, flags, nullptr, nullptr, nullptr, nullptr, 0, nullptr, dcounts, nullptr, dmap, dhyp2};
+    der_timed_jer_args(a, djer, djmap, dspk);
+    return der_timed_device(h, "der_timed_jer", a, false);
+  });
+}
+
+int plda_der_timed_jer(plda_handle *h, const int32_t *turn_start, const int32_t *turn_dur, const int32_t *turn_spk, const int64_t *turn_off,
+                       const int32_t *seg_start, const int32_t *seg_dur, const int32_t *hyp, const int32_t *hyp2, const int64_t *offsets,
+                       int64_t R, const int32_t *uem_start, const int32_t *uem_dur, const int64_t *uem_off, int32_t collar, int32_t flags,
+                       int64_t *counts, int32_t *map, int64_t *jer, int32_t *jmap, int64_t *spk) {
+  return entry(h, "plda_der_timed_jer", [&] {
+    DerTimedArgs a{turn_start, turn_dur, turn_spk, turn_off, seg_start, seg_dur, hyp, offsets, R, uem_start, uem_dur, uem_off,
+                         collar, flags, nullptr, nullptr, nullptr, nullptr, 0, nullptr, counts, nullptr, map, hyp2};
+    der_timed_jer_args(a, jer, jmap, spk);
+    return der_timed_host(h, "der_timed_jer", a, false);
+  });
+}
+
+int plda_der_timed_jer_sweep_dev(plda_handle *h, const int32_t *dmerge_a, const int32_t *dmerge_b, const double *dmerge_cost,
+                                 const int32_t *dturn_start, const int32_t *dturn_dur, const int32_t *dturn_spk, const int64_t *turn_off,
+                                 const int32_t *dseg_start, const int32_t *dseg_dur, const int64_t *offsets, int64_t R,
+                                 const int32_t *duem_start, const int32_t *duem_dur, const int64_t *uem_off, int32_t collar,
+                                 int32_t flags, const double *thresholds, int64_t Q, const int32_t *min_clusters, int64_t *dcounts,
+                                 int32_t *dn_clusters, int64_t *djer) {
+  return device_entry(h, "plda_der_timed_jer_sweep_dev", [&] {
+    DerTimedArgs a{dturn_start, dturn_dur, dturn_spk, turn_off, dseg_start, dseg_dur, nullptr, offsets, R, duem_start, duem_dur,
+                         uem_off, collar, flags, dmerge_a, dmerge_b, dmerge_cost, thresholds, Q, min_clusters, dcounts, dn_clusters, nullptr};
+    der_timed_jer_args(a, djer, nullptr, nullptr);
+    return der_timed_device(h, "der_timed_jer_sweep", a, true);
+  });
+}
+
+int plda_der_timed_jer_sweep(plda_handle *h, const int32_t *merge_a, const int32_t *merge_b, const double *merge_cost,
+                             const int32_t *turn_start, const int32_t *turn_dur, const int32_t *turn_spk, const int64_t *turn_off,
+                             const int32_t *seg_start, const int32_t *seg_dur, const int64_t *offsets, int64_t R,
+                             const int32_t *uem_start, const int32_t *uem_dur, const int64_t *uem_off, int32_t collar, int32_t flags,
+                             const double *thresholds, int64_t Q, const int32_t *min_clusters, int64_t *counts, int32_t *n_clusters,
+                             int64_t *jer) {
+  return entry(h, "plda_der_timed_jer_sweep", [&] {
+    DerTimedArgs a{turn_start, turn_dur, turn_spk, turn_off, seg_start, seg_dur, nullptr, offsets, R, uem_start, uem_dur, uem_off,
+                         collar, flags, merge_a, merge_b, merge_cost, thresholds, Q, min_clusters, counts, n_clusters, nullptr};
+    der_timed_jer_args(a, jer, nullptr, nullptr);
+    return der_timed_host(h, "der_timed_jer_sweep", a, true);
   });
 }
 

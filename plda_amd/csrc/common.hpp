@@ -565,15 +565,19 @@ int score_dense_pca_ahc_device(plda_handle *h, const double *dX, const int64_t *
 
 // ---- der.hip (diarisation error rate: optimal speaker mapping, threshold sweep; offsets / thresholds / minc are HOST arrays) ----
 int der_plan(plda_handle *h, int64_t Sr, int64_t Sh, int32_t *out);
+int der_jer_plan(plda_handle *h, int64_t Sr, int64_t Sh, int32_t *out);
+// the outputs the JER entry points add (K22): jer [.., 2] = {n_ref, jsum}; jmap [R, 64] and spk [R, 64, 3] nullable
+struct DerJerOut { long long *jer = nullptr; int *jmap = nullptr; long long *spk = nullptr; };
 // the host-side argument checks of the two device forms (the host forms run them before they allocate or upload)
 int der_validate(plda_handle *h, const char *fn, const int64_t *offsets, int64_t R);
 int der_sweep_validate(plda_handle *h, const char *fn, const int64_t *offsets, int64_t R, const double *thresholds, int64_t Q,
                        const int32_t *minc);
+// jo non-null: the JER form (jo->jer is checked there; the sum of a recording's durations is then at most 2^30)
 int der_device(plda_handle *h, const int32_t *dref, const int32_t *dhyp, const int32_t *ddur, const int64_t *offsets, int64_t R,
-               int64_t *dcounts, int32_t *dmap);
+               int64_t *dcounts, int32_t *dmap, const DerJerOut *jo = nullptr);
 int der_sweep_device(plda_handle *h, const int32_t *dma, const int32_t *dmb, const double *dmc, const int64_t *offsets, int64_t R,
                      const int32_t *dref, const int32_t *ddur, const double *thresholds, int64_t Q, const int32_t *minc,
-                     int64_t *dcounts, int32_t *dn_clusters);
+                     int64_t *dcounts, int32_t *dn_clusters, const DerJerOut *jo = nullptr);
 
 // ---- der_time.hip (time-based DER: overlapped reference speech, collar, UEM; every *_off array is a HOST array) ----
 // one recording's scored atoms, as der_atoms_kernel leaves them and der.hip's solve reads them
@@ -591,6 +595,8 @@ struct DerTimedArgs {
   const int32_t *ma, *mb; const double *mc; const double *thresholds; int64_t Q; const int32_t *minc;
   int64_t *counts; int32_t *n_clusters, *map;
   const int32_t *hyp2 = nullptr;      // plda_der_timed_ovl: the second hypothesis label of every segment (nullable)
+  bool jer_form = false;              // plda_der_timed_jer*: jo.jer is required, jo.jmap and jo.spk are nullable
+  DerJerOut jo;
 };
 int der_timed_plan(plda_handle *h, int64_t n_turns, int64_t n_seg, int64_t n_uem, int32_t collar, int32_t *out);
 // the host-side argument check (pointers are only compared with NULL; the host forms run it before they allocate or upload)
@@ -599,7 +605,7 @@ int der_timed_device(plda_handle *h, const char *fn, const DerTimedArgs &a, bool
 // der.hip: the solves behind the atoms (Q = 0: against dhyp; Q >= 1: the sweep of the merge record)
 int der_timed_solve(plda_handle *h, const char *fn, const DerTimedRec *recs, const DerTimedDev &td, const int32_t *dhyp,
                     const int32_t *dma, const int32_t *dmb, const double *dmc, const int64_t *offsets, int64_t R, const double *thresholds,
-                    int64_t Q, const int32_t *minc, int64_t *dcounts, int32_t *dn_clusters, int32_t *dmap);
+                    int64_t Q, const int32_t *minc, int64_t *dcounts, int32_t *dn_clusters, int32_t *dmap, const DerJerOut *jo = nullptr);
 
 // ---- vbx.hip (VBx resegmentation: a batched Bayesian HMM on PLDA vectors; offsets / gamma_off / pi_off are HOST arrays) ----
 int vbx_plan(plda_handle *h, int64_t T, int64_t S, int64_t D, int32_t *out);

@@ -21,6 +21,20 @@
 //   der_solve_ovl_kernel    the atom form with up to two hypothesis labels per segment (K21, plda_der_timed_ovl; der_solve_body<HBM,
 //                       false, true, OVL = true>): the labels present range over hyp and hyp2, an atom adds its ticks to C[i][j]
 //                       for both labels of its segment, and nhyp in the four counters is the number of labels >= 0
+//   der_solve_jer_kernel    <HBM, SWEEP, ATOMS, OVL> the JER form of all four shapes (K22; der_solve_body<.., JER = true>): the
+//                       same fill, with the per-speaker tick sums rt and ht beside it; the same first assignment and outputs;
+//                       then the Jaccard weights in place above C and a second assignment on them (the comment at
+//                       der_solve_body says where w is computed and why); jer, jmap and spk come from the second
+//
+// Resources on gfx950 (hipcc --offload-arch=gfx950 -O3 -Rpass-analysis=kernel-resource-usage), VGPRs in the LDS / scratch class;
+// no kernel of this file has scratch memory or spills:
+//   der_count_kernel 12 (<false> and <true>);  der_prefix_kernel 14
+//   der_solve_kernel, der_solve_timed_kernel, der_solve_ovl_kernel                          44 / 40, sweep or not
+//   der_solve_jer_kernel: segment, atoms, two labels                                        82 / 82
+//                         the two sweeps                                                    76 / 84
+// With JER = false der_solve_body compiles to what it was before the JER form existed: six of the ten plain instantiations are
+// the same instructions in the same order, the other four (segment and two-label form, both classes) differ in the order of
+// two independent register clears.
 //
 // One workgroup of der_solve_kernel: (1) the labels present, as bit sets (64 bits of reference, 4096 of hypothesis), give
 // the compact numbering by prefix population counts; (2) the matrix is zeroed and filled with integer atomics, the four
@@ -63,6 +77,19 @@ constexpr long long der_lds_bytes(long long sr, long long w, long long n_replay,
 static_assert(der_lds_bytes(DER_MAX_REF, DER_MAX_HYP, DER_MAX_HYP, true) <= DER_LDS_BYTES,
               "the scratch class's column state and the replay must fit one CU's LDS");
 
+// The JER form (K22) adds rt[64] (int64) and, outside the sweep, ht[w + 1] (int32).  In the sweep ht takes clab's place: a
+// sweep writes no map, so the caller's label of a column is never read.  The second assignment reuses the column state.
+constexpr int DER_JER_FIXED_BYTES = 8 * DER_MAX_REF;
+constexpr long long der_jer_lds_bytes(long long sr, long long w, long long n_replay, bool hbm, bool sweep) {
+  return der_lds_bytes(sr, w, n_replay, hbm) + DER_JER_FIXED_BYTES + (sweep ? 0 : 4 * (w + 1));
+}
+static_assert(der_jer_lds_bytes(DER_MAX_REF, DER_MAX_HYP, 0, true, false) <= DER_LDS_BYTES &&
+              der_jer_lds_bytes(DER_MAX_REF, DER_MAX_HYP, DER_MAX_HYP, true, true) <= DER_LDS_BYTES,
+              "the JER form's scratch class must fit one CU's LDS");
+// a matrix entry of the JER form once the first assignment is done: w << 31 | C (C <= 2^30, w <= 2^32)
+constexpr int DER_JER_SHIFT = 31;
+constexpr long long DER_JER_MAX_TICKS = 1ll << 30;
+
 __device__ __forceinline__ long long der_wave_sum(long long v) {
 #pragma unroll
   for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o);
@@ -82,15 +109,17 @@ __device__ __forceinline__ void der_wave_min(long long &v, int &j) {
 __device__ __forceinline__ unsigned long long der_below(int bit) { return bit ? ~0ull >> (64 - bit) : 0ull; }
 
 // one workgroup per recording: stat[0] += the invalid entries; sr[r], sh[r] = the distinct labels (hyp nullable: the sweep)
+// <JER>: a recording whose durations add up to more than 2^30 ticks counts as one more invalid entry
+template <bool JER = false>
 __global__ __launch_bounds__(DER_T) void der_count_kernel(const int *__restrict__ ref, const int *__restrict__ hyp,
                                                           const int *__restrict__ dur, const long long *__restrict__ offsets,
                                                           unsigned long long *stat, int *__restrict__ sr, int *__restrict__ sh) {
-  __shared__ unsigned long long bits[65];
+  __shared__ unsigned long long bits[JER ? 66 : 65];      // <JER>: bits[65] = the sum of the recording's durations
   __shared__ int tot[2];
   const int tid = threadIdx.x, r = blockIdx.x;
   const long long off = offsets[r];
   const int n = (int)(offsets[r + 1] - off);
-  if (tid < 65) bits[tid] = 0;
+  if (tid < (JER ? 66 : 65)) bits[tid] = 0;
   if (tid < 2) tot[tid] = 0;
   __syncthreads();
   unsigned bad = 0;
@@ -104,7 +133,19 @@ __global__ __launch_bounds__(DER_T) void der_count_kernel(const int *__restrict_
     if (!ok) ++bad;
   }
   if (bad) atomicAdd(stat, (unsigned long long)bad);      // rare: one integer atomic per lane that met one
+  if constexpr (JER) {
+    long long ticks = 0;
+    for (int t = tid; t < n; t += DER_T) {
+      const int d = dur ? dur[off + t] : 1;
+      if (d > 0) ticks += d;
+    }
+    ticks = der_wave_sum(ticks);
+    if ((tid & 63) == 0) atomicAdd(&bits[65], (unsigned long long)ticks);
+  }
   __syncthreads();
+  if constexpr (JER) {
+    if (tid == 0 && bits[65] > (unsigned long long)DER_JER_MAX_TICKS) atomicAdd(stat, 1ull);
+  }
   if (tid < 64) { const int c = __popcll(bits[tid]); if (c) atomicAdd(&tot[1], c); }
   if (tid == 64) tot[0] = __popcll(bits[64]);
   __syncthreads();
@@ -143,17 +184,27 @@ __global__ __launch_bounds__(DER_T) void der_prefix_kernel(const int *__restrict
   }
 }
 
+// the weight the assignment reads from a matrix entry: C, or in the JER form's second pass the w above C
+template <bool JER> __device__ __forceinline__ long long der_weight(long long e, int pass) {
+  if constexpr (JER) return pass ? (long long)((unsigned long long)e >> DER_JER_SHIFT) : e;
+  else return e;
+}
+
 // the confusion matrix of a recording: in LDS, or in HBM scratch (filled with atomics that complete in L2: read back with
 // device-scope loads, which do not take a line the CU's vector cache may hold from before)
 template <bool HBM> struct DerMat;
 template <> struct DerMat<false> {
   long long *c; int w;
   __device__ __forceinline__ long long get(int i, int j) const { return c[i * w + j]; }
+  __device__ __forceinline__ void put(int i, int j, long long x) const { c[i * w + j] = x; }
 };
 template <> struct DerMat<true> {
   long long *c; int w;
   __device__ __forceinline__ long long get(int i, int j) const {
     return __hip_atomic_load(c + (long long)i * w + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  __device__ __forceinline__ void put(int i, int j, long long x) const {
+    __hip_atomic_store(c + (long long)i * w + j, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
 };
 
@@ -161,18 +212,28 @@ template <> struct DerMat<true> {
 // (der_time.hip): the reference side is the scored atoms of the recording (ticks, 64-bit reference mask, segment index or -1)
 // and the union of their masks; the hypothesis label of an atom is that of its segment (SWEEP: the slot of its segment).
 // OVL (with ATOMS, without SWEEP; K21): a segment carries the label set {hyp[t]} u {td.hyp2[t]}, -1 = no such label.
-template <bool HBM, bool SWEEP, bool ATOMS, bool OVL = false>
+//
+// JER (K22; include/plda_hip.h, "Jaccard error rate"): the fill also sums rt[i], the scored ticks of reference speaker i, and
+// ht[j], those of hypothesis speaker j (integer LDS atomics).  The first assignment and its outputs are those of the plain
+// form.  Then every entry C of the matrix becomes w << 31 | C in place, w = floor(C 2^32 / (rt[i] + ht[j] - C)): ONE 64-bit
+// division per entry (C 2^32 <= 2^62, so nothing wider), where a weight computed in the scan would cost one per column per
+// step (up to Sr (Sr + 1) / 2 steps) and a second matrix beside C would halve the LDS class.  C <= 2^30 and w <= 2^32 share
+// the word.  The second assignment runs the same loop on w from fresh potentials and a fresh column state, under the same
+// (value, column) tie rule; jer, jmap and spk are read from it.
+template <bool HBM, bool SWEEP, bool ATOMS, bool OVL = false, bool JER = false>
 __device__ __forceinline__ void der_solve_body(const int *__restrict__ ref, const int *__restrict__ hyp,
                                                const int *__restrict__ dur, const int *__restrict__ ma,
                                                const int *__restrict__ mb, const DerRec *__restrict__ tab,
                                                long long *scratch, long long *__restrict__ counts,
-                                               int *__restrict__ n_clusters, int *__restrict__ map, const DerTimedDev &td) {
+                                               int *__restrict__ n_clusters, int *__restrict__ map, const DerTimedDev &td,
+                                               const DerJerOut &jo = DerJerOut{}) {
   extern __shared__ long long der_smem[];
   const DerRec rc = tab[blockIdx.x];
   const int n = rc.n, w = rc.w, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
 
   // LDS: [matrix (LDS class)] | v[w+1] minv[w+1] u[65] red_v[4] cnt[16] refmask hbits[64] | way[w+1] own[w+1] used[w+1] clab[w+1]
   //      hbase[64] reflab[64] red_i[4] | parent[n] (sweep)
+  // JER: rt[64] behind hbits, ht[w+1] behind red_i (in the sweep ht IS clab: der_jer_lds_bytes)
   long long *p8 = der_smem;
   DerMat<HBM> mat;
   mat.w = w;
@@ -185,6 +246,8 @@ __device__ __forceinline__ void der_solve_body(const int *__restrict__ ref, cons
   long long *cnt = p8; p8 += 4 * DER_W;
   unsigned long long *refmask = reinterpret_cast<unsigned long long *>(p8); p8 += 1;
   unsigned long long *hbits = reinterpret_cast<unsigned long long *>(p8); p8 += 64;
+  unsigned long long *rt = reinterpret_cast<unsigned long long *>(p8);      // JER: the scored ticks of compact row i
+  if constexpr (JER) p8 += DER_MAX_REF;
   int *p4 = reinterpret_cast<int *>(p8);
   int *way = p4; p4 += w + 1;
   int *own = p4; p4 += w + 1;      // the row (1-based) that holds column j, 0 = free
@@ -193,6 +256,8 @@ __device__ __forceinline__ void der_solve_body(const int *__restrict__ ref, cons
   int *hbase = p4; p4 += 64;
   int *reflab = p4; p4 += DER_MAX_REF;
   int *red_i = p4; p4 += DER_W;
+  int *ht = clab;                  // JER: the scored ticks of compact column j (0-based); the sweep has no use for clab
+  if constexpr (JER && !SWEEP) { ht = p4; p4 += w + 1; }
   int *parent = p4;
 
   const int *__restrict__ rf = ATOMS ? nullptr : ref + rc.off;
@@ -259,14 +324,20 @@ __device__ __forceinline__ void der_solve_body(const int *__restrict__ ref, cons
   // (the table was sized from der_count_kernel's reading of the same arrays; input that changed under the call must not
   // carry an index out of the layout)
   if (sr != rc.sr || sh != rc.sh) return;
-  if (tid < 64) {
-    int j = hbase[tid];
-    for (unsigned long long mk = hbits[tid]; mk; mk &= mk - 1) clab[j++] = tid * 64 + __ffsll((long long)mk) - 1;
+  if constexpr (!(JER && SWEEP)) {
+    if (tid < 64) {
+      int j = hbase[tid];
+      for (unsigned long long mk = hbits[tid]; mk; mk &= mk - 1) clab[j++] = tid * 64 + __ffsll((long long)mk) - 1;
+    }
   }
   // (2) the matrix and the column state
   for (long long e = tid; e < (long long)sr * w; e += DER_T) mat.c[e] = 0;
   for (int j = tid; j <= w; j += DER_T) { v[j] = 0; own[j] = 0; }
   if (tid <= DER_MAX_REF) u[tid] = 0;
+  if constexpr (JER) {
+    for (int j = tid; j <= w; j += DER_T) ht[j] = 0;
+    if (tid < DER_MAX_REF) rt[tid] = 0;
+  }
   __syncthreads();
   long long c_speech = 0, c_miss = 0, c_fa = 0, c_both = 0;
   if constexpr (ATOMS) {
@@ -274,6 +345,7 @@ __device__ __forceinline__ void der_solve_body(const int *__restrict__ ref, cons
     auto fill = [&](int b, unsigned long long am, long long d) {
       if (b >= 0 && b < DER_MAX_HYP && d) {
         const int k = b >> 6, j = hbase[k] + __popcll(hbits[k] & der_below(b & 63));
+        if constexpr (JER) atomicAdd(&ht[j], (int)d);      // (also where the atom holds no reference speaker)
         for (unsigned long long mk = am; mk; mk &= mk - 1) {
           const int i = __popcll(rmask & der_below(__ffsll((long long)mk) - 1));
           atomicAdd(reinterpret_cast<unsigned long long *>(mat.c) + (long long)i * w + j, (unsigned long long)d);
@@ -293,11 +365,22 @@ __device__ __forceinline__ void der_solve_body(const int *__restrict__ ref, cons
       c_both += d * (nref < nhyp ? nref : nhyp);
       fill(b, am, d);
       if constexpr (OVL) fill(b2, am, d);
+      if constexpr (JER) {
+        if (d)
+          for (unsigned long long mk = am; mk; mk &= mk - 1)
+            atomicAdd(&rt[__popcll(rmask & der_below(__ffsll((long long)mk) - 1))], (unsigned long long)d);
+      }
     }
   } else
   for (int t = tid; t < n; t += DER_T) {
     const int a = rf[t], b = hyp_of(t);
     const long long d = dr ? dr[t] : 1;
+    if constexpr (JER) {
+      if (d > 0) {
+        if (a >= 0) atomicAdd(&rt[__popcll(rmask & der_below(a & 63))], (unsigned long long)d);
+        if (b >= 0 && b < DER_MAX_HYP) atomicAdd(&ht[hbase[b >> 6] + __popcll(hbits[b >> 6] & der_below(b & 63))], (int)d);
+      }
+    }
     if (a >= 0) {
       c_speech += d;
       if (b < 0) c_miss += d;
@@ -315,6 +398,27 @@ __device__ __forceinline__ void der_solve_body(const int *__restrict__ ref, cons
 
   // (3, 4) the assignment: minimise sum of -C over the rows; thread tid owns the columns j = tid (mod DER_T), column 0 is the
   // virtual column the new row hangs from
+  // JER: a second pass of the same loop on the weights w, behind the outputs of the first.  (Two jumps, not a loop or a
+  // callable around the text below: either changes the code the plain instantiations compile to; like this they keep it.)
+  int pass = 0;
+der_assign:
+  if constexpr (JER) {
+    if (pass == 1) {
+      __syncthreads();                             // (the first assignment's own[] and red_v[] have been read)
+      // (5) every entry becomes w << 31 | C; the padding columns (C = 0, weight 0) stay 0.  U = 0 needs rt[i] = 0, then C = 0
+      for (int i = 0; i < sr; ++i) {
+        const unsigned long long rti = rt[i];
+        for (int j = tid; j < sh; j += DER_T) {
+          const unsigned long long c = (unsigned long long)mat.get(i, j), un = rti + (unsigned)ht[j] - c;
+          if (c) mat.put(i, j, (long long)((((c << 32) / un) << DER_JER_SHIFT) | c));
+        }
+      }
+      for (int j = tid; j <= w; j += DER_T) { v[j] = 0; own[j] = 0; }
+      if (tid <= DER_MAX_REF) u[tid] = 0;
+      if constexpr (HBM) __threadfence();
+      __syncthreads();
+    }
+  }
   for (int i = 1; i <= sr; ++i) {
     for (int j = tid; j <= w; j += DER_T) { minv[j] = DER_INF; used[j] = 0; }
     if (tid == 0) own[0] = i;
@@ -328,7 +432,7 @@ __device__ __forceinline__ void der_solve_body(const int *__restrict__ ref, cons
       int bj = -1;
       for (int j = tid ? tid : DER_T; j <= w; j += DER_T) {
         if (used[j]) continue;
-        const long long cur = (j <= sh ? -mat.get(i0 - 1, j - 1) : 0) - ui0 - v[j];
+        const long long cur = (j <= sh ? -der_weight<JER>(mat.get(i0 - 1, j - 1), pass) : 0) - ui0 - v[j];
         long long mj = minv[j];
         if (cur < mj) { mj = cur; minv[j] = cur; way[j] = j0; }
         if (bj < 0 || mj < best) { best = mj; bj = j; }      // j ascends within a thread: a tie keeps the smaller column
@@ -359,6 +463,10 @@ __device__ __forceinline__ void der_solve_body(const int *__restrict__ ref, cons
   }
 
   // the weight of the optimum, the counts, the map
+  if constexpr (JER) {
+    if (pass == 1) goto der_jer_out;
+  }
+  {
   long long correct = 0;
   for (int j = tid ? tid : DER_T; j <= sh; j += DER_T)
     if (own[j]) correct += mat.get(own[j] - 1, j - 1);
@@ -379,6 +487,50 @@ __device__ __forceinline__ void der_solve_body(const int *__restrict__ ref, cons
   if (map)
     for (int j = tid ? tid : DER_T; j <= sh; j += DER_T)
       if (own[j] && mat.get(own[j] - 1, j - 1) > 0) map[rc.out * DER_MAX_REF + reflab[own[j] - 1]] = clab[j - 1];
+  }
+
+  if constexpr (JER) {
+    pass = 1;
+    goto der_assign;
+  }
+der_jer_out:
+  if constexpr (JER) {
+    constexpr long long CMASK = (1ll << DER_JER_SHIFT) - 1;
+    // (7) jer = {n_ref, jsum}; jmap and spk by the rules of map
+    long long jsum = 0;
+    for (int j = tid ? tid : DER_T; j <= sh; j += DER_T)
+      if (own[j]) jsum += (long long)((unsigned long long)mat.get(own[j] - 1, j - 1) >> DER_JER_SHIFT);
+    jsum = der_wave_sum(jsum);
+    if (lane == 0) red_v[wave] = jsum;
+    if (jo.jmap)
+      for (int k = tid; k < DER_MAX_REF; k += DER_T) jo.jmap[rc.out * DER_MAX_REF + k] = -1;
+    if (jo.spk)
+      for (int k = tid; k < DER_MAX_REF; k += DER_T) {
+        const long long r0 = (rmask >> k) & 1 ? (long long)rt[__popcll(rmask & der_below(k))] : 0;
+        long long *sp = jo.spk + (rc.out * DER_MAX_REF + k) * 3;
+        sp[0] = r0; sp[1] = 0; sp[2] = r0;
+      }
+    __syncthreads();
+    if (tid == 0) {
+      long long js = 0, nref = 0;
+      for (int k = 0; k < DER_W; ++k) js += red_v[k];
+      for (int i = 0; i < sr; ++i) nref += rt[i] > 0;
+      jo.jer[rc.out * 2 + 0] = nref; jo.jer[rc.out * 2 + 1] = js;
+    }
+    for (int j = tid ? tid : DER_T; j <= sh; j += DER_T) {
+      if (!own[j]) continue;
+      const int i = own[j] - 1;
+      const long long c = mat.get(i, j - 1) & CMASK;
+      if (c <= 0) continue;
+      if constexpr (!SWEEP) {
+        if (jo.jmap) jo.jmap[rc.out * DER_MAX_REF + reflab[i]] = clab[j - 1];
+      }
+      if (jo.spk) {
+        long long *sp = jo.spk + (rc.out * DER_MAX_REF + reflab[i]) * 3;
+        sp[1] = c; sp[2] = (long long)rt[i] + ht[j - 1] - c;
+      }
+    }
+  }
 }
 
 template <bool HBM, bool SWEEP>
@@ -405,6 +557,39 @@ __global__ __launch_bounds__(DER_T) void der_solve_ovl_kernel(const int *__restr
                                                               long long *scratch, long long *__restrict__ counts,
                                                               int *__restrict__ map, const DerTimedDev td) {
   der_solve_body<HBM, false, true, true>(nullptr, hyp, nullptr, nullptr, nullptr, tab, scratch, counts, nullptr, map, td);
+}
+
+// the JER form of all four shapes (K22): one kernel, the shape in its template arguments (td is unused without ATOMS; ref and
+// dur with it).  Resources: the table in the file header.
+template <bool HBM, bool SWEEP, bool ATOMS, bool OVL>
+__global__ __launch_bounds__(DER_T) void der_solve_jer_kernel(const int *__restrict__ ref, const int *__restrict__ hyp,
+                                                              const int *__restrict__ dur, const int *__restrict__ ma,
+                                                              const int *__restrict__ mb, const DerRec *__restrict__ tab,
+                                                              long long *scratch, long long *__restrict__ counts,
+                                                              int *__restrict__ n_clusters, int *__restrict__ map,
+                                                              const DerTimedDev td, const DerJerOut jo) {
+  der_solve_body<HBM, SWEEP, ATOMS, OVL, true>(ref, hyp, dur, ma, mb, tab, scratch, counts, n_clusters, map, td, jo);
+}
+
+// the instantiation of a launch: the class, atoms or segments, one or two labels (the sweeps have no second label)
+using DerJerFn = void (*)(const int *, const int *, const int *, const int *, const int *, const DerRec *, long long *, long long *, int *,
+                          int *, DerTimedDev, DerJerOut);
+template <bool SWEEP> DerJerFn der_jer_fn(bool hbm, bool atoms, bool ovl) {
+  if constexpr (!SWEEP)
+    if (ovl) return hbm ? &der_solve_jer_kernel<true, false, true, true> : &der_solve_jer_kernel<false, false, true, true>;
+  if (atoms) return hbm ? &der_solve_jer_kernel<true, SWEEP, true, false> : &der_solve_jer_kernel<false, SWEEP, true, false>;
+  return hbm ? &der_solve_jer_kernel<true, SWEEP, false, false> : &der_solve_jer_kernel<false, SWEEP, false, false>;
+}
+
+template <bool SWEEP> int der_jer_attr(plda_handle *h) {
+  static DeviceOnce attr;
+  if (attr.needed(h->device)) {
+    for (int k = 0; k < (SWEEP ? 4 : 6); ++k)
+      PLDA_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void *>(der_jer_fn<SWEEP>(k & 1, (k >> 1) != 0, (k >> 1) == 2)),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, DER_LDS_BYTES));
+    attr.done(h->device);
+  }
+  return PLDA_OK;
 }
 
 template <bool HBM, bool SWEEP, bool ATOMS, bool OVL = false> int der_solve_attr(plda_handle *h) {
@@ -440,17 +625,19 @@ int der_check_offsets(plda_handle *h, const char *fn, const int64_t *offsets, in
 
 // Enqueues the solves of `items` (sr, sh, n, m, off, out, r filled in; w, scr and the launch order are this function's);
 // `tab` is the host copy of the launch table, alive until the caller has synchronised.
-// `td` non-null: the time-based form (dref and ddur unused).
+// `td` non-null: the time-based form (dref and ddur unused).  `jo` non-null: the JER form, with its own LDS accounting.
 template <bool SWEEP>
 int der_solve_enqueue(plda_handle *h, std::vector<DerRec> &items, std::vector<DerRec> &tab, const int *dref, const int *dhyp,
                       const int *ddur, const int *dma, const int *dmb, long long *dcounts, int *dn_clusters, int *dmap,
-                      const DerTimedDev *td) {
+                      const DerTimedDev *td, const DerJerOut *jo) {
   static const int bucket_top[] = {8 << 10, 20 << 10, 40 << 10, 80 << 10, DER_LDS_BYTES};
   constexpr int NB = sizeof(bucket_top) / sizeof(bucket_top[0]);
   struct Launch { int64_t first, count; int64_t lds; bool hbm; };
   std::vector<Launch> launches;
   tab.reserve(items.size());
-  auto lds_of = [](const DerRec &rc, bool hbm) { return der_lds_bytes(rc.sr, rc.w, SWEEP ? rc.n : 0, hbm); };
+  auto lds_of = [jo](const DerRec &rc, bool hbm) {
+    return jo ? der_jer_lds_bytes(rc.sr, rc.w, SWEEP ? rc.n : 0, hbm, SWEEP) : der_lds_bytes(rc.sr, rc.w, SWEEP ? rc.n : 0, hbm);
+  };
   for (DerRec &rc : items) rc.w = std::max(rc.sr, rc.sh);
   for (int bk = 0; bk < NB; ++bk) {           // LDS class: one launch per bucket of LDS bytes (a launch takes its largest need)
     const int64_t lo = bk ? bucket_top[bk - 1] : 0, hi = bucket_top[bk];
@@ -488,6 +675,21 @@ int der_solve_enqueue(plda_handle *h, std::vector<DerRec> &items, std::vector<De
   const DerRec *dtab = h->der_tab.as<DerRec>();
   long long *scratch = h->der_scratch.as<long long>();
   const bool ovl = !SWEEP && td && td->hyp2;
+  if (jo) {                                   // the JER form: one kernel signature, the instantiation picked by der_jer_fn
+    PLDA_TRY(der_jer_attr<SWEEP>(h));
+    TraceScope ts(h, SWEEP ? "der.jer_sweep_solve" : "der.jer_solve");
+    const DerTimedDev tdv = td ? *td : DerTimedDev{};
+    for (const Launch &L : launches) {
+      const DerJerFn fn = der_jer_fn<SWEEP>(L.hbm, td != nullptr, ovl);
+      for (int64_t c0 = 0; c0 < L.count; c0 += 1 << 20) {
+        const unsigned c = (unsigned)std::min<int64_t>(1 << 20, L.count - c0);
+        fn<<<c, DER_T, (size_t)L.lds, h->stream>>>(dref, dhyp, ddur, dma, dmb, dtab + L.first + c0, L.hbm ? scratch : nullptr, dcounts,
+                                                   dn_clusters, dmap, tdv, *jo);
+        PLDA_LAUNCH_CHECK(h);
+      }
+    }
+    return PLDA_OK;
+  }
   if (ovl) {
     PLDA_TRY((der_solve_attr<false, false, true, true>(h)));
     PLDA_TRY((der_solve_attr<true, false, true, true>(h)));
@@ -529,9 +731,10 @@ int der_solve_enqueue(plda_handle *h, std::vector<DerRec> &items, std::vector<De
 // the solves of a call, and the synchronisation behind them (also where the enqueue failed half-way: the table is in flight)
 template <bool SWEEP>
 int der_solve_all(plda_handle *h, std::vector<DerRec> &items, const int *dref, const int *dhyp, const int *ddur, const int *dma,
-                  const int *dmb, long long *dcounts, int *dn_clusters, int *dmap, const DerTimedDev *td = nullptr) {
+                  const int *dmb, long long *dcounts, int *dn_clusters, int *dmap, const DerTimedDev *td = nullptr,
+                  const DerJerOut *jo = nullptr) {
   std::vector<DerRec> tab;
-  const int rc = der_solve_enqueue<SWEEP>(h, items, tab, dref, dhyp, ddur, dma, dmb, dcounts, dn_clusters, dmap, td);
+  const int rc = der_solve_enqueue<SWEEP>(h, items, tab, dref, dhyp, ddur, dma, dmb, dcounts, dn_clusters, dmap, td, jo);
   const hipError_t e = hipStreamSynchronize(h->stream);
   if (rc != PLDA_OK) return rc;
   PLDA_HIP(h, e);
@@ -555,26 +758,34 @@ int der_sweep_validate(plda_handle *h, const char *fn, const int64_t *offsets, i
   return PLDA_OK;
 }
 
-int der_plan(plda_handle *h, int64_t Sr, int64_t Sh, int32_t *out) {
-  if (!out) return fail(h, PLDA_E_INVAL, "der_plan: out is NULL");
-  if (Sr < 0 || Sr > DER_MAX_REF) return fail(h, PLDA_E_INVAL, "der_plan: Sr = %lld (must be 0 ... PLDA_DER_MAX_REF = %d)", (long long)Sr, DER_MAX_REF);
-  if (Sh < 0 || Sh > DER_MAX_HYP) return fail(h, PLDA_E_INVAL, "der_plan: Sh = %lld (must be 0 ... PLDA_AHC_MAX = %d)", (long long)Sh, DER_MAX_HYP);
+namespace {
+int der_plan_of(plda_handle *h, const char *fn, bool jer, int64_t Sr, int64_t Sh, int32_t *out) {
+  if (!out) return fail(h, PLDA_E_INVAL, "%s: out is NULL", fn);
+  if (Sr < 0 || Sr > DER_MAX_REF) return fail(h, PLDA_E_INVAL, "%s: Sr = %lld (must be 0 ... PLDA_DER_MAX_REF = %d)", fn, (long long)Sr, DER_MAX_REF);
+  if (Sh < 0 || Sh > DER_MAX_HYP) return fail(h, PLDA_E_INVAL, "%s: Sh = %lld (must be 0 ... PLDA_AHC_MAX = %d)", fn, (long long)Sh, DER_MAX_HYP);
+  auto lds = [&](int64_t w) { return jer ? der_jer_lds_bytes(Sr, w, 0, false, false) : der_lds_bytes(Sr, w, 0, false); };
   const int64_t w = std::max(Sr, Sh);
-  const bool hbm = der_lds_bytes(Sr, w, 0, false) > DER_LDS_BYTES;
+  const bool hbm = lds(w) > DER_LDS_BYTES;
   int64_t wmax = Sr;                          // the widest matrix of Sr rows the LDS class takes
-  while (wmax < DER_MAX_HYP && der_lds_bytes(Sr, wmax + 1, 0, false) <= DER_LDS_BYTES) ++wmax;
+  while (wmax < DER_MAX_HYP && lds(wmax + 1) <= DER_LDS_BYTES) ++wmax;
   out[0] = hbm ? 1 : 0;
   out[1] = hbm ? (int32_t)(8 * Sr * w) : 0;
   out[2] = (int32_t)wmax;
   return PLDA_OK;
 }
+}  // namespace
+
+int der_plan(plda_handle *h, int64_t Sr, int64_t Sh, int32_t *out) { return der_plan_of(h, "der_plan", false, Sr, Sh, out); }
+// the JER form's boundary: its LDS holds rt and ht beside the column state (the sweeps keep ht in clab's place)
+int der_jer_plan(plda_handle *h, int64_t Sr, int64_t Sh, int32_t *out) { return der_plan_of(h, "der_jer_plan", true, Sr, Sh, out); }
 
 int der_device(plda_handle *h, const int32_t *dref, const int32_t *dhyp, const int32_t *ddur, const int64_t *offsets, int64_t R,
-               int64_t *dcounts, int32_t *dmap) {
-  const char *fn = "der";
+               int64_t *dcounts, int32_t *dmap, const DerJerOut *jo) {
+  const char *fn = jo ? "der_jer" : "der";
   if (!dref) return fail(h, PLDA_E_INVAL, "%s: ref is NULL", fn);
   if (!dhyp) return fail(h, PLDA_E_INVAL, "%s: hyp is NULL", fn);
   if (!dcounts) return fail(h, PLDA_E_INVAL, "%s: counts is NULL", fn);
+  if (jo && !jo->jer) return fail(h, PLDA_E_INVAL, "%s: jer is NULL", fn);
   PLDA_TRY(der_check_offsets(h, fn, offsets, R));
   // stat: two counters | offsets [R + 1] | sr [R] sh [R]
   const size_t ints = 16 + 8 * (size_t)(R + 1);
@@ -586,7 +797,8 @@ int der_device(plda_handle *h, const int32_t *dref, const int32_t *dhyp, const i
   PLDA_HIP(h, hipMemcpyAsync(doff, offsets, 8 * (size_t)(R + 1), hipMemcpyHostToDevice, h->stream));
   {
     TraceScope ts(h, "der.count");
-    der_count_kernel<<<(unsigned)R, DER_T, 0, h->stream>>>(dref, dhyp, ddur, doff, reinterpret_cast<unsigned long long *>(ds), dsr, dsh);
+    if (jo) der_count_kernel<true><<<(unsigned)R, DER_T, 0, h->stream>>>(dref, dhyp, ddur, doff, reinterpret_cast<unsigned long long *>(ds), dsr, dsh);
+    else der_count_kernel<false><<<(unsigned)R, DER_T, 0, h->stream>>>(dref, dhyp, ddur, doff, reinterpret_cast<unsigned long long *>(ds), dsr, dsh);
     PLDA_LAUNCH_CHECK(h);
   }
   unsigned long long bad = 0;
@@ -594,23 +806,27 @@ int der_device(plda_handle *h, const int32_t *dref, const int32_t *dhyp, const i
   PLDA_HIP(h, hipMemcpyAsync(&bad, ds, 8, hipMemcpyDeviceToHost, h->stream));
   PLDA_HIP(h, hipMemcpyAsync(s.data(), dsr, 8 * (size_t)R, hipMemcpyDeviceToHost, h->stream));
   PLDA_HIP(h, hipStreamSynchronize(h->stream));
-  if (bad) return fail(h, PLDA_E_INVAL, "%s: %llu invalid entries (a label below -1 or above its limit, or a negative duration)", fn, bad);
+  if (bad)
+    return fail(h, PLDA_E_INVAL, "%s: %llu invalid entries (a label below -1 or above its limit, or a negative duration%s)", fn, bad,
+                jo ? "; a recording whose durations add up to more than 2^30" : "");
   std::vector<DerRec> items((size_t)R);
   for (int64_t r = 0; r < R; ++r) {
     DerRec &rc = items[(size_t)r];
     rc.off = offsets[r]; rc.scr = 0; rc.out = r; rc.n = (int)(offsets[r + 1] - offsets[r]);
     rc.sr = s[(size_t)r]; rc.sh = s[(size_t)(R + r)]; rc.w = 0; rc.m = 0; rc.r = (int)r;
   }
-  return der_solve_all<false>(h, items, dref, dhyp, ddur, nullptr, nullptr, reinterpret_cast<long long *>(dcounts), nullptr, dmap);
+  return der_solve_all<false>(h, items, dref, dhyp, ddur, nullptr, nullptr, reinterpret_cast<long long *>(dcounts), nullptr, dmap, nullptr,
+                              jo);
 }
 
 int der_sweep_device(plda_handle *h, const int32_t *dma, const int32_t *dmb, const double *dmc, const int64_t *offsets, int64_t R,
                      const int32_t *dref, const int32_t *ddur, const double *thresholds, int64_t Q, const int32_t *minc,
-                     int64_t *dcounts, int32_t *dn_clusters) {
-  const char *fn = "der_sweep";
+                     int64_t *dcounts, int32_t *dn_clusters, const DerJerOut *jo) {
+  const char *fn = jo ? "der_jer_sweep" : "der_sweep";
   if (!dref) return fail(h, PLDA_E_INVAL, "%s: ref is NULL", fn);
   if (!dcounts) return fail(h, PLDA_E_INVAL, "%s: counts is NULL", fn);
   if (!dn_clusters) return fail(h, PLDA_E_INVAL, "%s: n_clusters is NULL", fn);
+  if (jo && !jo->jer) return fail(h, PLDA_E_INVAL, "%s: jer is NULL", fn);
   PLDA_TRY(der_sweep_validate(h, fn, offsets, R, thresholds, Q, minc));
   const int64_t T = offsets[R];
   if (T > R && !(dma && dmb && dmc)) return fail(h, PLDA_E_INVAL, "%s: merge_a, merge_b or merge_cost is NULL", fn);
@@ -628,7 +844,8 @@ int der_sweep_device(plda_handle *h, const int32_t *dma, const int32_t *dmb, con
   {
     TraceScope ts(h, "der.sweep_count");
     unsigned long long *dstat = reinterpret_cast<unsigned long long *>(ds);
-    der_count_kernel<<<(unsigned)R, DER_T, 0, h->stream>>>(dref, nullptr, ddur, doff, dstat, dsr, nullptr);
+    if (jo) der_count_kernel<true><<<(unsigned)R, DER_T, 0, h->stream>>>(dref, nullptr, ddur, doff, dstat, dsr, nullptr);
+    else der_count_kernel<false><<<(unsigned)R, DER_T, 0, h->stream>>>(dref, nullptr, ddur, doff, dstat, dsr, nullptr);
     PLDA_LAUNCH_CHECK(h);
     der_prefix_kernel<<<dim3((unsigned)R, (unsigned)Q), DER_T, 0, h->stream>>>(dma, dmb, dmc, doff, dthr, minc ? dminc : nullptr, (int)R,
                                                                                dstat, dm);
@@ -639,7 +856,9 @@ int der_sweep_device(plda_handle *h, const int32_t *dma, const int32_t *dmb, con
   PLDA_HIP(h, hipMemcpyAsync(bad, ds, 16, hipMemcpyDeviceToHost, h->stream));
   PLDA_HIP(h, hipMemcpyAsync(s.data(), dsr, 4 * s.size(), hipMemcpyDeviceToHost, h->stream));
   PLDA_HIP(h, hipStreamSynchronize(h->stream));
-  if (bad[0]) return fail(h, PLDA_E_INVAL, "%s: %llu invalid entries (a label below -1 or above its limit, or a negative duration)", fn, bad[0]);
+  if (bad[0])
+    return fail(h, PLDA_E_INVAL, "%s: %llu invalid entries (a label below -1 or above its limit, or a negative duration%s)", fn, bad[0],
+                jo ? "; a recording whose durations add up to more than 2^30" : "");
   if (bad[1])
     return fail(h, PLDA_E_INVAL, "%s: %llu (recording, threshold) pairs whose merge record ends, or holds an entry that is no merge, "
                                  "before the stop rule fires: not a full record", fn, bad[1]);
@@ -650,14 +869,15 @@ int der_sweep_device(plda_handle *h, const int32_t *dma, const int32_t *dmb, con
       rc.off = offsets[r]; rc.scr = 0; rc.out = q * R + r; rc.n = (int)(offsets[r + 1] - offsets[r]);
       rc.sr = s[(size_t)r]; rc.m = s[(size_t)(R + q * R + r)]; rc.sh = rc.n - rc.m; rc.w = 0; rc.r = (int)r;
     }
-  return der_solve_all<true>(h, items, dref, nullptr, ddur, dma, dmb, reinterpret_cast<long long *>(dcounts), dn_clusters, nullptr);
+  return der_solve_all<true>(h, items, dref, nullptr, ddur, dma, dmb, reinterpret_cast<long long *>(dcounts), dn_clusters, nullptr, nullptr,
+                             jo);
 }
 
 // The solves of a time-based call (der_time.hip has validated the call and cut the atoms; recs is the host copy of td.recs).
 // Q = 0: one solve per recording against dhyp (recs[r].sh = its distinct hypothesis labels).  Q >= 1: the sweep.
 int der_timed_solve(plda_handle *h, const char *fn, const DerTimedRec *recs, const DerTimedDev &td, const int32_t *dhyp,
                     const int32_t *dma, const int32_t *dmb, const double *dmc, const int64_t *offsets, int64_t R, const double *thresholds,
-                    int64_t Q, const int32_t *minc, int64_t *dcounts, int32_t *dn_clusters, int32_t *dmap) {
+                    int64_t Q, const int32_t *minc, int64_t *dcounts, int32_t *dn_clusters, int32_t *dmap, const DerJerOut *jo) {
   auto item = [&](int64_t r, int64_t out) {
     DerRec rc;
     rc.off = offsets[r]; rc.scr = 0; rc.out = out; rc.n = (int)(offsets[r + 1] - offsets[r]);
@@ -667,7 +887,8 @@ int der_timed_solve(plda_handle *h, const char *fn, const DerTimedRec *recs, con
   if (Q == 0) {
     std::vector<DerRec> items((size_t)R);
     for (int64_t r = 0; r < R; ++r) { items[(size_t)r] = item(r, r); items[(size_t)r].sh = recs[r].sh; }
-    return der_solve_all<false>(h, items, nullptr, dhyp, nullptr, nullptr, nullptr, reinterpret_cast<long long *>(dcounts), nullptr, dmap, &td);
+    return der_solve_all<false>(h, items, nullptr, dhyp, nullptr, nullptr, nullptr, reinterpret_cast<long long *>(dcounts), nullptr, dmap, &td,
+                                jo);
   }
   // stat: two counters | offsets [R + 1] | thresholds [Q] | m [Q, R] minc [R]
   const size_t o_thr = 16 + 8 * (size_t)(R + 1), o_int = o_thr + 8 * (size_t)Q;
@@ -701,7 +922,8 @@ int der_timed_solve(plda_handle *h, const char *fn, const DerTimedRec *recs, con
       rc = item(r, q * R + r);
       rc.m = m[(size_t)(q * R + r)]; rc.sh = rc.n - rc.m;
     }
-  return der_solve_all<true>(h, items, nullptr, nullptr, nullptr, dma, dmb, reinterpret_cast<long long *>(dcounts), dn_clusters, nullptr, &td);
+  return der_solve_all<true>(h, items, nullptr, nullptr, nullptr, dma, dmb, reinterpret_cast<long long *>(dcounts), dn_clusters, nullptr, &td,
+                               jo);
 }
 
 }  // namespace plda

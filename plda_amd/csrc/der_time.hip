@@ -318,6 +318,7 @@ int der_timed_validate(plda_handle *h, const char *fn, const DerTimedArgs &a, bo
   if (!a.sdur) return fail(h, PLDA_E_INVAL, "%s: seg_dur is NULL", fn);
   if (!sweep && !a.hyp) return fail(h, PLDA_E_INVAL, "%s: hyp is NULL", fn);
   if (!a.counts) return fail(h, PLDA_E_INVAL, "%s: counts is NULL", fn);
+  if (a.jer_form && !a.jo.jer) return fail(h, PLDA_E_INVAL, "%s: jer is NULL", fn);
   if (sweep && !a.n_clusters) return fail(h, PLDA_E_INVAL, "%s: n_clusters is NULL", fn);
   if (sweep) PLDA_TRY(der_sweep_validate(h, fn, a.offsets, a.R, a.thresholds, a.Q, a.minc));
   else PLDA_TRY(der_validate(h, fn, a.offsets, a.R));
@@ -417,7 +418,7 @@ int der_timed_device(plda_handle *h, const char *fn, const DerTimedArgs &a, bool
                 a.hyp2 ? ", a second label without a first or equal to it" : "", bad[1]);
   const DerTimedDev td{drecs, dticks, dseg, dmask, sweep ? nullptr : a.hyp2};     // (hyp2 given: the solve's two-label form)
   return der_timed_solve(h, fn, recs.data(), td, a.hyp, a.ma, a.mb, a.mc, a.offsets, R, a.thresholds, sweep ? a.Q : 0, a.minc, a.counts,
-                         a.n_clusters, a.map);
+                         a.n_clusters, a.map, a.jer_form ? &a.jo : nullptr);
 }
 
 }  // namespace plda

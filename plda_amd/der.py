@@ -8,8 +8,11 @@ speakers, and the sweep of ONE full AHC merge record over Q thresholds.
     MPlda.der / MPlda.tune_threshold                      the same from an engine; tune_threshold clusters once, then sweeps
 
 Labels: ref in [-1, 64), hyp in [-1, 4096), -1 = non-speech; dur int32 >= 0 in ticks (None: 1 everywhere).  Everything on the
-device is an integer and the counts are exact; the divisions are done here, the pooled ones from Python ints.  Out of scope,
-on purpose: JER.
+device is an integer and the counts are exact; the divisions are done here, the pooled ones from Python ints.
+
+The Jaccard error rate (include/plda_hip.h, "Jaccard error rate and per-speaker figures") comes from the same calls with
+jer=True: der, der_timed return a DerResult that also carries jer, jer_counts, jer_map and speakers; sweep, sweep_timed a
+SweepResult with jer_counts, jer and best_jer.  jer_rates(jer_counts) and pooled_jer(jer_counts) are the divisions.
 
 The time-based form (csrc/der_time.hip; include/plda_hip.h, "time-based diarisation error rate") scores TIME, with overlapped
 reference speech, a collar and UEM regions -- md-eval's definition on integer ticks:
@@ -42,13 +45,21 @@ _p = diarize._p
 
 class DerResult:
     """counts int64 [R, 4] = {speech, miss, fa, confusion}; der float64 [R] (NaN where speech = 0); total = the pooled
-    sum of errors / sum of speech (NaN when there is no speech); map int32 [R, 64] or None."""
+    sum of errors / sum of speech (NaN when there is no speech); map int32 [R, 64] or None.
+    With jer=True also: jer_counts int64 [R, 2] = {n_ref, jsum}; jer float64 [R] (NaN where n_ref = 0); jer_total, pooled
+    over all reference speakers; jer_map int32 [R, 64]; speakers, per recording a list of (ref_label, hyp_label or -1,
+    ref_ticks, intersect, union, jer) for every reference speaker that counts, ascending by ref_label.  Otherwise None."""
 
-    def __init__(self, counts, map_=None):
+    def __init__(self, counts, map_=None, jer_counts=None, jer_map=None, spk=None):
         self.counts = counts
         self.map = map_
         self.der = rates(counts)
         self.total = pooled(counts)
+        self.jer_counts = jer_counts
+        self.jer_map = jer_map
+        self.jer = jer_rates(jer_counts) if jer_counts is not None else None
+        self.jer_total = pooled_jer(jer_counts) if jer_counts is not None else None
+        self.speakers = _speakers(jer_map, spk) if spk is not None else None
 
     def __repr__(self):
         return "DerResult(total=%r, recordings=%d)" % (self.total, len(self.counts))
@@ -56,14 +67,19 @@ class DerResult:
 
 class SweepResult:
     """counts int64 [Q, R, 4]; n_clusters int32 [Q, R]; der float64 [Q], pooled over the recordings; best = the index of the
-    lowest pooled DER (ties: the lowest index; NaN never wins); thresholds float64 [Q]."""
+    lowest pooled DER (ties: the lowest index; NaN never wins); thresholds float64 [Q].
+    With jer=True also: jer_counts int64 [Q, R, 2]; jer float64 [Q], pooled; best_jer = the index of the lowest pooled JER
+    (the same tie rule).  Otherwise None."""
 
-    def __init__(self, thresholds, counts, n_clusters):
+    def __init__(self, thresholds, counts, n_clusters, jer_counts=None):
         self.thresholds = thresholds
         self.counts = counts
         self.n_clusters = n_clusters
         self.der = np.asarray([pooled(c) for c in counts], np.float64)
         self.best = best_index(counts)
+        self.jer_counts = jer_counts
+        self.jer = np.asarray([pooled_jer(c) for c in jer_counts], np.float64) if jer_counts is not None else None
+        self.best_jer = best_jer_index(jer_counts) if jer_counts is not None else None
 
     def __repr__(self):
         return "SweepResult(best=%d, threshold=%r, der=%r)" % (self.best, float(self.thresholds[self.best]), float(self.der[self.best]))
@@ -104,11 +120,80 @@ def best_index(counts):
     return best
 
 
+JER_ONE = 1 << 32       # the weight of a Jaccard index of 1
+
+
+def jer_rates(jer_counts):
+    """1 - jsum / (n_ref 2^32) of every row of jer_counts [..., 2]; NaN where n_ref = 0."""
+    c = np.asarray(jer_counts, np.int64)
+    out = np.full(c.shape[:-1], np.nan)
+    for idx in np.ndindex(*c.shape[:-1]):
+        n, js = int(c[idx + (0,)]), int(c[idx + (1,)])
+        if n > 0:
+            out[idx] = (n * JER_ONE - js) / (n * JER_ONE)
+    return out
+
+
+def _jer_sums(jer_counts):
+    c = np.asarray(jer_counts, np.int64).reshape(-1, 2)
+    return sum(int(v) for v in c[:, 0]), sum(int(v) for v in c[:, 1])
+
+
+def pooled_jer(jer_counts):
+    """1 - sum jsum / (2^32 sum n_ref) over jer_counts [R, 2], from Python ints: the mean over all reference speakers of all
+    recordings (a recording with n_ref = 0 adds nothing); NaN when there is no reference speaker."""
+    n, js = _jer_sums(jer_counts)
+    return (n * JER_ONE - js) / (n * JER_ONE) if n > 0 else float("nan")
+
+
+def best_jer_index(jer_counts):
+    """argmin over q of the pooled JER of jer_counts [Q, R, 2], compared as exact fractions; ties go to the lowest q."""
+    best, bj, bn = 0, None, None
+    for q, c in enumerate(jer_counts):
+        n, js = _jer_sums(c)
+        if n <= 0:
+            continue
+        if bj is None or js * bn > bj * n:               # js / n > bj / bn: a larger mean index is a smaller JER
+            best, bj, bn = q, js, n
+    return best
+
+
+def _speakers(jer_map, spk):
+    out = []
+    for r in range(len(spk)):
+        rows = []
+        for i in np.flatnonzero(spk[r, :, 0] > 0):
+            rt, inter, union = (int(v) for v in spk[r, i])
+            rows.append((int(i), int(jer_map[r, i]), rt, inter, union, 1.0 - inter / union))
+        out.append(rows)
+    return out
+
+
+def _jer_out(r, q=None):
+    """The buffers of a JER call: (jer_counts, jer_map, spk); a sweep (q given) has jer_counts [Q, R, 2] alone."""
+    if q is not None:
+        return np.empty((q, r, 2), np.int64), None, None
+    return np.empty((r, 2), np.int64), np.empty((r, MAX_REF), np.int32), np.empty((r, MAX_REF, 3), np.int64)
+
+
 def plan(engine, sr, sh):
     """{"cls": 0 (matrix in LDS) or 1 (in handle scratch), "scratch_bytes": per recording, "lds_max": the widest matrix,
     max(sr, sh), of the LDS class at this sr}."""
     out = (C.c_int32 * 3)()
     N.check(engine._h, engine._lib.plda_der_plan(engine._h, int(sr), int(sh), out))
+    return {"cls": int(out[0]), "scratch_bytes": int(out[1]), "lds_max": int(out[2])}
+
+
+def _jer_ticks(dur, offsets):
+    """The segment forms of the JER calls: the durations of a recording add up to at most 2^30 (dur None: its segment count)."""
+    if dur is not None and (np.add.reduceat(dur.astype(np.int64), offsets[:-1]) > MAX_TIME).any():
+        raise ValueError("with jer=True the durations of a recording must add up to at most 2^30")
+
+
+def plan_jer(engine, sr, sh):
+    """plan() under the LDS accounting of the JER form (plda_der_jer_plan)."""
+    out = (C.c_int32 * 3)()
+    N.check(engine._h, engine._lib.plda_der_jer_plan(engine._h, int(sr), int(sh), out))
     return {"cls": int(out[0]), "scratch_bytes": int(out[1]), "lds_max": int(out[2])}
 
 
@@ -178,24 +263,37 @@ def sweep_args(merges, offsets, ref, thresholds, dur, num_speakers):
     return ma, mb, mc, offsets, _labels(ref, t, "ref", MAX_REF), thresholds, _dur(dur, t), minc
 
 
-def der(engine, ref, hyp, offsets, dur=None, return_map=False):
+def der(engine, ref, hyp, offsets, dur=None, return_map=False, jer=False):
     """Score R recordings: ref, hyp int [T] (-1 = non-speech), recording r owning segments offsets[r] .. offsets[r+1], dur
-    int [T] ticks (None: 1).  Returns a DerResult."""
+    int [T] ticks (None: 1).  jer=True: the Jaccard error rate and the per-speaker figures from the same call (the durations
+    of a recording then add up to at most 2^30).  Returns a DerResult."""
     ref, hyp, offsets, dur = der_args(ref, hyp, offsets, dur)
     r = len(offsets) - 1
     counts = np.empty((r, 4), np.int64)
     map_ = np.empty((r, MAX_REF), np.int32) if return_map else None
+    if jer:
+        _jer_ticks(dur, offsets)
+        jc, jm, sp = _jer_out(r)
+        N.check(engine._h, engine._lib.plda_der_jer(engine._h, _p(ref), _p(hyp), _p(dur), _p(offsets), r, _p(counts), _p(map_), _p(jc),
+                                                    _p(jm), _p(sp)))
+        return DerResult(counts, map_, jc, jm, sp)
     N.check(engine._h, engine._lib.plda_der(engine._h, _p(ref), _p(hyp), _p(dur), _p(offsets), r, _p(counts), _p(map_)))
     return DerResult(counts, map_)
 
 
-def sweep(engine, merges, offsets, ref, thresholds, dur=None, num_speakers=None):
+def sweep(engine, merges, offsets, ref, thresholds, dur=None, num_speakers=None, jer=False):
     """Score the clusterings that a FULL merge record (diarize.ahc / MPlda.cluster with threshold=None, num_speakers=1,
     return_merges=True) yields at every one of `thresholds`, with at least `num_speakers` clusters left (None: 1): what
     diarize.cut at that threshold followed by der returns, for all Q in one device run.  Returns a SweepResult."""
     ma, mb, mc, offsets, ref, thresholds, dur, minc = sweep_args(merges, offsets, ref, thresholds, dur, num_speakers)
     r, q = len(offsets) - 1, len(thresholds)
     counts, ncl = np.empty((q, r, 4), np.int64), np.empty((q, r), np.int32)
+    if jer:
+        _jer_ticks(dur, offsets)
+        jc = _jer_out(r, q)[0]
+        N.check(engine._h, engine._lib.plda_der_jer_sweep(engine._h, _p(ma), _p(mb), _p(mc), _p(offsets), r, _p(ref), _p(dur),
+                                                          _p(thresholds), q, _p(minc), _p(counts), _p(ncl), _p(jc)))
+        return SweepResult(thresholds, counts, ncl, jc)
     N.check(engine._h, engine._lib.plda_der_sweep(engine._h, _p(ma), _p(mb), _p(mc), _p(offsets), r, _p(ref), _p(dur), _p(thresholds),
                                                   q, _p(minc), _p(counts), _p(ncl)))
     return SweepResult(thresholds, counts, ncl)
@@ -279,7 +377,8 @@ def plan_timed(engine, n_turns, n_seg, n_uem=0, collar=0):
             "events": (6 if collar > 0 else 2) * int(n_turns) + 2 * int(n_seg) + 2 * int(n_uem)}
 
 
-def der_timed(engine, turns, seg_start, seg_dur, hyp, offsets, collar=0, uem=None, skip_overlap=False, return_map=False, hyp2=None):
+def der_timed(engine, turns, seg_start, seg_dur, hyp, offsets, collar=0, uem=None, skip_overlap=False, return_map=False, hyp2=None,
+              jer=False):
     """Time-based DER of R recordings: reference turns (they may overlap across speakers), disjoint hypothesis segments
     seg_start, seg_dur, hyp int [T] (-1 = non-speech), recording r owning segments offsets[r] .. offsets[r+1]; collar in
     ticks; uem the scored regions or None; skip_overlap: md-eval's -1; hyp2 int [T] or None: the second speaker of every
@@ -290,6 +389,13 @@ def der_timed(engine, turns, seg_start, seg_dur, hyp, offsets, collar=0, uem=Non
     r = len(offsets) - 1
     counts = np.empty((r, 4), np.int64)
     map_ = np.empty((r, MAX_REF), np.int32) if return_map else None
+    if jer:
+        jc, jm, sp = _jer_out(r)
+        hyp2 = targs[12] if hyp2 is not None else None
+        N.check(engine._h, engine._lib.plda_der_timed_jer(engine._h, _p(ts), _p(td), _p(tk), _p(toff), _p(ss), _p(sd), _p(hyp), _p(hyp2),
+                                                          _p(offsets), r, _p(us), _p(ud), _p(uoff), collar, flags, _p(counts), _p(map_),
+                                                          _p(jc), _p(jm), _p(sp)))
+        return DerResult(counts, map_, jc, jm, sp)
     if hyp2 is not None:
         hyp2 = targs[12]
         N.check(engine._h, engine._lib.plda_der_timed_ovl(engine._h, _p(ts), _p(td), _p(tk), _p(toff), _p(ss), _p(sd), _p(hyp), _p(hyp2),
@@ -309,13 +415,19 @@ def sweep_timed_args(merges, turns, seg_start, seg_dur, offsets, thresholds, num
 
 
 def sweep_timed(engine, merges, turns, seg_start, seg_dur, offsets, thresholds, num_speakers=None, collar=0, uem=None,
-                skip_overlap=False):
+                skip_overlap=False, jer=False):
     """sweep() on time: the clusterings a FULL merge record yields at every threshold, each scored as der_timed scores the
     labels of diarize.cut at that threshold.  The time line is cut once per recording.  Returns a SweepResult."""
     ma, mb, mc, thresholds, minc, ts, td, tk, toff, ss, sd, offsets, us, ud, uoff, collar, flags = sweep_timed_args(
         merges, turns, seg_start, seg_dur, offsets, thresholds, num_speakers, collar, uem, skip_overlap)
     r, q = len(offsets) - 1, len(thresholds)
     counts, ncl = np.empty((q, r, 4), np.int64), np.empty((q, r), np.int32)
+    if jer:
+        jc = _jer_out(r, q)[0]
+        N.check(engine._h, engine._lib.plda_der_timed_jer_sweep(engine._h, _p(ma), _p(mb), _p(mc), _p(ts), _p(td), _p(tk), _p(toff), _p(ss),
+                                                                _p(sd), _p(offsets), r, _p(us), _p(ud), _p(uoff), collar, flags,
+                                                                _p(thresholds), q, _p(minc), _p(counts), _p(ncl), _p(jc)))
+        return SweepResult(thresholds, counts, ncl, jc)
     N.check(engine._h, engine._lib.plda_der_timed_sweep(engine._h, _p(ma), _p(mb), _p(mc), _p(ts), _p(td), _p(tk), _p(toff), _p(ss), _p(sd),
                                                         _p(offsets), r, _p(us), _p(ud), _p(uoff), collar, flags, _p(thresholds), q, _p(minc),
                                                         _p(counts), _p(ncl)))

@@ -679,22 +679,26 @@ class MPlda(object):
             vp(dmerge_cost)))
 
     # ----------------------------------------------------------------- diarisation error rate (csrc/der.hip)
-    def der(self,ref, hyp, offsets, dur=None, return_map=False):
+    def der(self,ref, hyp, offsets, dur=None, return_map=False, jer=False):
         """Diarisation error rate of R recordings (plda_amd/der.py): ref, hyp int [T] per-segment speaker labels (-1 =
         non-speech), recording r owning segments offsets[r] .. offsets[r+1], dur int [T] ticks (None: 1 everywhere).  Miss,
         false alarm and confusion under the optimal one-to-one speaker mapping, exact integers from the device.  Returns a
-        plda_amd.der.DerResult (counts [R, 4], der [R], total[, map [R, 64]])."""
+        plda_amd.der.DerResult (counts [R, 4], der [R], total[, map [R, 64]]); jer=True: also the Jaccard error rate and the
+        per-speaker figures (jer, jer_counts, jer_map, speakers)."""
         from . import der
-        return der.der(self, ref, hyp, offsets, dur, return_map)
+        return der.der(self, ref, hyp, offsets, dur, return_map, jer)
 
     def tune_threshold(self, x, offsets, ref, thresholds, dur=None, target_energy=None, turns=None, seg_start=None, seg_dur=None,
-                       collar=0, uem=None, skip_overlap=False):
-        """The clustering threshold with the lowest pooled DER on a development set: ONE cluster(x, offsets, threshold=None,
+                       collar=0, uem=None, skip_overlap=False, metric="der"):
+        """The clustering threshold with the lowest pooled DER (metric="jer": the lowest pooled JER) on a development set: ONE cluster(x, offsets, threshold=None,
         num_speakers=1, return_merges=True[, target_energy=target_energy]), then one der.sweep of its full merge record over
         `thresholds`.  With `turns` (and seg_start, seg_dur; collar, uem, skip_overlap as in der_timed) the sweep is the
         time-based one, der.sweep_timed, and ref and dur must be None.  Returns (the best threshold -- the first of equal
-        ones --, the plda_amd.der.SweepResult)."""
+        ones --, the plda_amd.der.SweepResult; under metric="jer" it carries jer_counts, jer and best_jer)."""
         from . import der
+        if metric not in ("der", "jer"):
+            raise ValueError("metric must be 'der' or 'jer'")
+        jer = metric == "jer"
         offsets = np.ascontiguousarray(offsets, np.int64)
         X = self._rows(x, "Segment vectors")
         if offsets.ndim != 1 or len(offsets) < 2 or X.shape[0] != int(offsets[-1]):
@@ -711,24 +715,68 @@ class MPlda(object):
                 _, _, merges = diarize.ahc_dense_pca(self, X, offsets, target_energy, None, 1, True)
             else:
                 _, _, merges = diarize.ahc_vectors(self, self.transform_array(X, 1), offsets, None, 1, True)
-            res = der.sweep_timed(self, merges, turns, seg_start, seg_dur, offsets, thresholds, None, collar, uem, skip_overlap)
-            return float(res.thresholds[res.best]), res
-        der.sweep_args(empty, offsets, ref, thresholds, dur, None)        # (before any device work)
+            res = der.sweep_timed(self, merges, turns, seg_start, seg_dur, offsets, thresholds, None, collar, uem, skip_overlap, jer)
+            return float(res.thresholds[res.best_jer if jer else res.best]), res
+        sargs = der.sweep_args(empty, offsets, ref, thresholds, dur, None)        # (before any device work)
+        if jer:
+            der._jer_ticks(sargs[6], sargs[3])
         from . import diarize
         diarize.stop_args(offsets, None, 1)
         if target_energy is not None:
             _, _, merges = diarize.ahc_dense_pca(self, X, offsets, target_energy, None, 1, True)
         else:
             _, _, merges = diarize.ahc_vectors(self, self.transform_array(X, 1), offsets, None, 1, True)   # cluster() on embedded rows
-        res = der.sweep(self, merges, offsets, ref, thresholds, dur)
-        return float(res.thresholds[res.best]), res
+        res = der.sweep(self, merges, offsets, ref, thresholds, dur, None, jer)
+        return float(res.thresholds[res.best_jer if jer else res.best]), res
 
-    def der_timed(self, turns, seg_start, seg_dur, hyp, offsets, collar=0, uem=None, skip_overlap=False, return_map=False, hyp2=None):
+    def der_timed(self, turns, seg_start, seg_dur, hyp, offsets, collar=0, uem=None, skip_overlap=False, return_map=False, hyp2=None,
+                  jer=False):
         """Time-based DER of R recordings (plda_amd/der.py: der_timed): reference turns (turn_start, turn_dur, turn_spk,
         turn_off) that may overlap across speakers, disjoint hypothesis segments, a collar in ticks, UEM regions, md-eval's
-        skip-overlap switch; hyp2: the second speaker of every segment, -1 = none.  Returns a plda_amd.der.DerResult."""
+        skip-overlap switch; hyp2: the second speaker of every segment, -1 = none; jer=True: also the Jaccard error rate and
+        the per-speaker figures.  Returns a plda_amd.der.DerResult."""
         from . import der
-        return der.der_timed(self, turns, seg_start, seg_dur, hyp, offsets, collar, uem, skip_overlap, return_map, hyp2)
+        return der.der_timed(self, turns, seg_start, seg_dur, hyp, offsets, collar, uem, skip_overlap, return_map, hyp2, jer)
+
+    def der_timed_jer_dev(self, dturns, turn_off, dseg_start, dseg_dur, dhyp, dhyp2, offsets, dcounts, djer, dmap=None, djmap=None,
+                          dspk=None, duem=None, uem_off=None, collar=0, flags=0):
+        """plda_der_timed_jer_dev: der_timed_ovl_dev (dhyp2 may be None), then djer int64 [R, 2], djmap int32 [R, 64] or None,
+        dspk int64 [R, 64, 3] or None."""
+        def vp(x):
+            return C.c_void_p(int(x)) if x else None
+        du = duem if duem is not None else (None, None)
+        self._ck(self._lib.plda_der_timed_jer_dev(
+            self._h, vp(dturns[0]), vp(dturns[1]), vp(dturns[2]), _ptr(turn_off), vp(dseg_start), vp(dseg_dur), vp(dhyp), vp(dhyp2),
+            _ptr(offsets), len(offsets) - 1, vp(du[0]), vp(du[1]), _ptr(uem_off) if uem_off is not None else None, int(collar),
+            int(flags), vp(dcounts), vp(dmap), vp(djer), vp(djmap), vp(dspk)))
+
+    def der_timed_jer_sweep_dev(self, dmerges, dturns, turn_off, dseg_start, dseg_dur, offsets, thresholds, min_clusters, dcounts,
+                                dn_clusters, djer, duem=None, uem_off=None, collar=0, flags=0):
+        """plda_der_timed_jer_sweep_dev: der_timed_sweep_dev, then djer int64 [Q, R, 2]."""
+        def vp(x):
+            return C.c_void_p(int(x)) if x else None
+        du = duem if duem is not None else (None, None)
+        self._ck(self._lib.plda_der_timed_jer_sweep_dev(
+            self._h, vp(dmerges[0]), vp(dmerges[1]), vp(dmerges[2]), vp(dturns[0]), vp(dturns[1]), vp(dturns[2]), _ptr(turn_off),
+            vp(dseg_start), vp(dseg_dur), _ptr(offsets), len(offsets) - 1, vp(du[0]), vp(du[1]),
+            _ptr(uem_off) if uem_off is not None else None, int(collar), int(flags), _ptr(thresholds), len(thresholds),
+            _ptr(min_clusters) if min_clusters is not None else None, vp(dcounts), vp(dn_clusters), vp(djer)))
+
+    def der_jer_dev(self, dref, dhyp, ddur, offsets, dcounts, djer, dmap=None, djmap=None, dspk=None):
+        """plda_der_jer_dev: der_dev, then djer int64 [R, 2], djmap int32 [R, 64] or None, dspk int64 [R, 64, 3] or None."""
+        def vp(x):
+            return C.c_void_p(int(x)) if x else None
+        self._ck(self._lib.plda_der_jer_dev(self._h, vp(dref), vp(dhyp), vp(ddur), _ptr(offsets), len(offsets) - 1, vp(dcounts), vp(dmap),
+                                            vp(djer), vp(djmap), vp(dspk)))
+
+    def der_jer_sweep_dev(self, dmerge_a, dmerge_b, dmerge_cost, offsets, dref, ddur, thresholds, min_clusters, dcounts, dn_clusters,
+                          djer):
+        """plda_der_jer_sweep_dev: der_sweep_dev, then djer int64 [Q, R, 2]."""
+        def vp(x):
+            return C.c_void_p(int(x)) if x else None
+        self._ck(self._lib.plda_der_jer_sweep_dev(
+            self._h, vp(dmerge_a), vp(dmerge_b), vp(dmerge_cost), _ptr(offsets), len(offsets) - 1, vp(dref), vp(ddur), _ptr(thresholds),
+            len(thresholds), _ptr(min_clusters) if min_clusters is not None else None, vp(dcounts), vp(dn_clusters), vp(djer)))
 
     def der_timed_ovl_dev(self, dturns, turn_off, dseg_start, dseg_dur, dhyp, dhyp2, offsets, dcounts, dmap=None, duem=None,
                           uem_off=None, collar=0, flags=0):
