@@ -451,7 +451,21 @@ int plda_htk_frames_dev(plda_handle *h, const void *dblob, const int64_t *dfile_
  * midpoint after the score where |FAR - FRR| is minimal, later candidate on ties).
  * out[6] = threshold, FAR, FRR, EER = (FAR + FRR)/2, #targets, #impostors.
  * _matrix: trial (i, j) of the fp32 score matrix is a target iff enrol_spk[i] == test_spk[j];
- * _lists: separate target / impostor score arrays (the two files eer.py reads). ---- */
+ * _lists: separate target / impostor score arrays (the two files eer.py reads).
+ *
+ * NON-FINITE SCORES ARE REFUSED.  A trial is a column in [0, Nt) of a row in [0, M), or an element of a list.  A NaN of either
+ * sign, +Inf or -Inf among the trials -- an all-NaN row is a regular output of the transform, see there -- makes every EER and
+ * DET entry point (plda_eer_lists, plda_eer_matrix_dev, plda_score_eer_dev, plda_eer_matrix_sharded_dev,
+ * plda_eer_matrix_comm_dev, plda_det_lists, plda_det_matrix_dev) return PLDA_E_INVAL with plda_last_error
+ * "eer: <count> non-finite score(s) among the trials" (resp. "det: ..."), as calibration, fusion and minDCF do.  The count is
+ * exact, and global in the sharded forms, where every rank refuses together; it is reported before "need at least one target
+ * and one impostor".  Nothing is written to out, far, frr or thresholds, and the handle stays usable.
+ * PADDING IS NOT DATA: the columns [Nt, ld) of a matrix may hold anything, NaN and Inf included, and change nothing.
+ * FINITE SCORES: oracle/plda_oracle_np.py:eer is the specification, the extremes (+-FLT_MAX, subnormals, +-0 = one score)
+ * included, and the rates returned are always farfrr at the threshold returned.  The definition's last candidate is
+ * s_max + 1e-8 formed in float64; from |s_max| >= 2^27 on that sum is s_max itself, the candidate then counts the trials AT s_max
+ * as accepted -- the rates of the candidate before it -- and, being the later one, wins their tie: all scores equal to
+ * s >= 2^27 give (s, FAR 1, FRR 0, EER 0.5), where s < 2^27 gives (s + 1e-8, FAR 0, FRR 1, EER 0.5). ---- */
 int plda_eer_matrix_dev(plda_handle *h, const float *dscores, int64_t ld, int64_t M, int64_t Nt,
                         const int64_t *denrol_spk, const int64_t *dtest_spk, double *out);
 int plda_eer_lists(plda_handle *h, const float *pos, int64_t np, const float *neg, int64_t nn,
@@ -459,7 +473,8 @@ int plda_eer_lists(plda_handle *h, const float *pos, int64_t np, const float *ne
 /* The points of the DET curve scoring/eer.py:34-62 plots (bob.measure.plot.det(negatives, positives, 100); definition
  * restated, bob absent): n_points (2 .. 2047) thresholds spread evenly from the smallest to the largest score, accumulated in
  * float64; far[i] = #{impostor >= t_i} / Nn, frr[i] = #{target < t_i} / Np (HOST arrays; thresholds nullable).  The plot's axes
- * are the normal deviates of the two rates (plda_amd.eer.ppndf); drawing it stays with the caller. */
+ * are the normal deviates of the two rates (plda_amd.eer.ppndf); drawing it stays with the caller.  One non-finite score
+ * would make the step and every threshold after the first Inf or NaN: refused with its count, as above; padding is not data. */
 int plda_det_matrix_dev(plda_handle *h, const float *dscores, int64_t ld, int64_t M, int64_t Nt,
                         const int64_t *denrol_spk, const int64_t *dtest_spk, int32_t n_points, double *far, double *frr,
                         double *thresholds);
@@ -479,7 +494,9 @@ int plda_score_eer_dev(plda_handle *h, const double *dU, const int32_t *dn_enrol
  * `reduce(ctx, hist, NULL, NULL)` with hist[2 * 2048] host counters to be SUMMED over the ranks in
  * place, and once at the end `reduce(ctx, NULL, below, above)` with two host words to be replaced
  * by their MAX resp. MIN over the ranks.  The callback returns 0 on success.  Every rank gets the
- * global result; scores never leave their GPU (the exchange is 3 x 32 KiB + 8 bytes).
+ * global result; scores never leave their GPU (the exchange is 3 x 32 KiB + 8 bytes; two more passes, each with its
+ * reduction, where the largest score may reach 2^27 in magnitude -- decided on the summed counters, so on every rank alike).
+ * A rank that refuses (non-finite scores anywhere: the count is the global one) still makes every call its peers wait in.
  * plda_amd/sharding.py:eer_sharded supplies a torch.distributed callback. */
 typedef int (*plda_eer_reduce_fn)(void *ctx, unsigned long long *hist, unsigned *below, unsigned *above);
 int plda_eer_matrix_sharded_dev(plda_handle *h, const float *dscores, int64_t ld, int64_t M, int64_t Nt,

@@ -229,15 +229,27 @@ def dvector_pool(frames, offsets, method="mean", l2norm=True):
     return np.array(out)
 
 
+def _finite_scores(who, negatives, positives):
+    """The two score lists as float32; a NaN (of either sign) or an Inf among them is refused, as the device refuses it."""
+    neg, pos = np.asarray(negatives, np.float32), np.asarray(positives, np.float32)
+    bad = int((~np.isfinite(neg)).sum() + (~np.isfinite(pos)).sum())
+    if bad:
+        raise ValueError("%s: %d non-finite score(s) among the trials" % (who, bad))
+    return neg, pos
+
+
 def eer(negatives, positives):
     """Equal error rate as scoring/eer.py:68-73 computes it through bob.measure (absent,
     un-pinned: published definition restated; PARITY UNPINNED for this row):
       farfrr(neg, pos, t): FAR = #{neg >= t}/Nn, FRR = #{pos < t}/Np;
       eer_threshold: candidates are the minimum score, then the midpoint after each distinct
       score of the union (last one: score + 1e-8); minimal |FAR - FRR| wins, later on ties.
-    Returns (threshold, far, frr, eer) computed on float32 scores in float64."""
-    neg = np.sort(np.asarray(negatives, np.float32).astype(np.float64))
-    pos = np.sort(np.asarray(positives, np.float32).astype(np.float64))
+    Returns (threshold, far, frr, eer) computed on float32 scores in float64; the rates are farfrr at that threshold
+    (from |max| >= 2**27 on, `max + 1e-8` is max itself and counts the scores equal to it as at or above).
+    Non-finite scores raise ValueError."""
+    neg, pos = _finite_scores("eer", negatives, positives)
+    neg = np.sort(neg.astype(np.float64))
+    pos = np.sort(pos.astype(np.float64))
     s = np.unique(np.concatenate([neg, pos]))
     mids = np.concatenate([[s[0]], s[:-1] + (s[1:] - s[:-1]) / 2.0, [s[-1] + 1e-8]])
     far = (len(neg) - np.searchsorted(neg, mids, side="left")) / len(neg)   # #{neg >= t} / Nn
@@ -252,9 +264,10 @@ def det(negatives, positives, n_points):
     (absent, un-pinned: published definition restated; PARITY UNPINNED): n_points thresholds from the smallest to the
     largest score of the union, accumulated as t_0 = min, t_{i+1} = t_i + (max - min) / (n_points - 1) in float64;
     FAR_i = #{neg >= t_i} / Nn, FRR_i = #{pos < t_i} / Np (bob.measure.farfrr).  Returns (thresholds, far, frr); the plot's
-    axes are ppndf (the normal deviate) of the two rates: `ppndf` below."""
-    neg = np.sort(np.asarray(negatives, np.float32).astype(np.float64))
-    pos = np.sort(np.asarray(positives, np.float32).astype(np.float64))
+    axes are ppndf (the normal deviate) of the two rates: `ppndf` below.  Non-finite scores raise ValueError."""
+    neg, pos = _finite_scores("det", negatives, positives)
+    neg = np.sort(neg.astype(np.float64))
+    pos = np.sort(pos.astype(np.float64))
     lo = min(neg[0], pos[0]); hi = max(neg[-1], pos[-1])
     step = (hi - lo) / (n_points - 1.0)
     thr = np.empty(n_points)

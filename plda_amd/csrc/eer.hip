@@ -22,6 +22,14 @@
 // both of its neighbours -- checked with the exact counts (g(klo) < 0 <= g(khi), neighbours found inside); otherwise, and
 // for small or sharded inputs, the three passes run.  PLDA_EER_VARIANT=1 forces them (A/B arm, and what the test compares with).
 //
+// Non-finite scores (NaN of either sign, +-Inf) among the trials are REFUSED with PLDA_E_INVAL and their exact count, as
+// calibration, fusion and minDCF refuse them (the key order would place a NaN at either end of the scores according to its sign
+// bit, and an Inf makes midpoints and DET steps NaN).  Three passes: bins 0..3 and 2044..2047 of the pass-0 histogram hold
+// exactly the keys whose exponent is all ones -- free, and already global in the sharded forms.  Single pass: a counter of the
+// window pass (the pilot sees every 32nd row only; +-Inf pass the window's compares).  DET: a counter of the min/max pass.
+// The padding columns [Nt, ld) are never read as data.  On finite scores the restatement is the specification, including
+// its last candidate `s_max + 1e-8`, which from |s_max| >= 2^27 on is s_max itself (eer_device's end).
+//
 // Where things live: the source of the trials (TrialSource: matrix, lists or slabs), the walk over its pieces
 // (for_each_piece), the score key and the prototypes of every entry point here are in trial_source.hpp, shared with calib.hip
 // and dcf.hip; the slab producer of the operand form (plda_score_eer_dev) is operand_slabs.hip.  This file: the kernels, the
@@ -152,15 +160,18 @@ __global__ __launch_bounds__(256) void eer_hist_strip_kernel(const float *__rest
   }
 }
 
-// The one full pass of the windowed form (same strip layout).  Per trial: three float compares against the window's
-// ends (the key order is the float order, and -0 == +0 in both), the class, four predicated counters -- below the window
-// per class, targets, at-or-above the window -- and, for the few per mille inside it, a slot in the wave's LDS stage
+// The one full pass of the windowed form (same strip layout).  Per trial: two float compares against the window's
+// ends (the key order is the float order, and -0 == +0 in both), one against infinity, the class, four predicated counters
+// -- below the window per class, targets, non-finite scores -- and, for the few per mille inside it, a slot in the wave's LDS stage
 // (an LDS atomic taken by those lanes only), which leaves for the class's list 512+ scores at a time behind ONE global
 // atomic (one global atomic per wave and element serialises on the cursor's line: 0.8 s for a window of a tenth of 1e10
-// trials, measured).  NaN scores satisfy no compare: the caller sees below + inside + above != M Nt and runs the three
-// passes, whose key order places them.  A list that fills up keeps counting (the cursor says by how much it overflowed).
+// trials, measured).  The non-finite scores (NaN of either sign, +-Inf) of the columns inside the matrix are counted here
+// because the pilot sees every 32nd row only and +-Inf pass the window's compares; the caller refuses the call.  What lies at or
+// above the window is not counted: it is the rest.  (It used to be, and the sum of all counters told a NaN; a fifth counter
+// beside it cost the call 4 % -- 11.0 -> 11.5 ms on 1e10 trials -- so the new one took its place: same work per trial.)
+// A list that fills up keeps counting (the cursor says by how much it overflowed).
 struct EerWindowOut {
-  unsigned long long below[2], targets, above, cursor[2];
+  unsigned long long below[2], targets, nonfinite, cursor[2];
 };
 constexpr int EER_WBUF = 1536;       // staged scores per wave and class (48 KB per workgroup); flushed when a batch (<= 1024 more) might not fit
 __global__ __launch_bounds__(256) void eer_window_strip_kernel(const float *__restrict__ scores, int64_t ld, int64_t M, int64_t Nt,
@@ -184,7 +195,7 @@ __global__ __launch_bounds__(256) void eer_window_strip_kernel(const float *__re
   }
   const bool vec = ((ld & 3) == 0) && ((reinterpret_cast<uintptr_t>(scores) & 15) == 0) && ok[3];
   const float qnan = __uint_as_float(0x7fc00000u);
-  unsigned b0 = 0, b1 = 0, t1 = 0, ab = 0;      // (a thread sees <= 4 * rows_per_wg trials: 32 bits)
+  unsigned b0 = 0, b1 = 0, t1 = 0, nf = 0;      // (a thread sees <= 4 * rows_per_wg trials: 32 bits)
   int *const fc = fillc[wave];
   if (lane < 2) fc[lane] = 0;
   auto flush = [&](int c) {
@@ -225,7 +236,7 @@ __global__ __launch_bounds__(256) void eer_window_strip_kernel(const float *__re
         t1 += tgt ? 1u : 0u;
         b1 += (lt_lo && tgt) ? 1u : 0u;
         b0 += (lt_lo && !tgt) ? 1u : 0u;
-        ab += (x >= fhi) ? 1u : 0u;
+        nf += !(__builtin_fabsf(x) < __builtin_inff()) ? 1u : 0u;     // NaN or Inf -- and the NaN put in for a column beyond the matrix
         if (lt_hi && !lt_lo) {
           const int c = tgt ? 1 : 0;
           const int slot = atomicAdd(&fc[c], 1);
@@ -238,7 +249,13 @@ __global__ __launch_bounds__(256) void eer_window_strip_kernel(const float *__re
   }
   flush(0);
   flush(1);
-  unsigned long long c[4] = {b0, b1, t1, ab};
+  if (!vec && r1 > r0) {                        // take the NaNs of this thread's own making out again: one per row and missing column
+    unsigned missing = 0;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) missing += ok[e] ? 0u : 1u;
+    nf -= missing * (unsigned)(r1 - r0);
+  }
+  unsigned long long c[4] = {b0, b1, t1, nf};
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
     for (int o = 32; o > 0; o >>= 1) c[q] += __shfl_xor(c[q], o);
@@ -247,7 +264,7 @@ __global__ __launch_bounds__(256) void eer_window_strip_kernel(const float *__re
   __syncthreads();
   if (threadIdx.x < 4) {
     const unsigned long long sum = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
-    unsigned long long *dst = threadIdx.x == 0 ? &wo->below[0] : threadIdx.x == 1 ? &wo->below[1] : threadIdx.x == 2 ? &wo->targets : &wo->above;
+    unsigned long long *dst = threadIdx.x == 0 ? &wo->below[0] : threadIdx.x == 1 ? &wo->below[1] : threadIdx.x == 2 ? &wo->targets : &wo->nonfinite;
     if (sum) atomicAdd(dst, sum);
   }
 }
@@ -290,7 +307,14 @@ bool reduce_block_or_poison(plda_handle *h, const TrialSource &src, const char *
   return *rc == PLDA_OK;
 }
 
+// The definition's last candidate threshold is `s_max + 1e-8`, formed in float64: from |s_max| >= 2^27 on the sum IS s_max, and
+// farfrr there counts the trials at s_max as at or above the threshold.
+static inline bool last_candidate_collapses(double s) { return s + 1e-8 == s; }
+
 // out: [0] threshold, [1] FAR, [2] FRR, [3] EER = (FAR + FRR) / 2, [4] #targets, [5] #impostors
+//
+// Non-finite scores (NaN of either sign, +-Inf) are refused with their exact count, before anything else is said about the
+// trials; nothing is written to `out`.
 //
 // Sharded calls (src.reduce): every rank makes the SAME four reduction calls whatever happens locally; a rank that fails
 // (HIP error, inconsistent counts) keeps taking part (reduce_block_or_poison).
@@ -309,6 +333,7 @@ static int eer_device(plda_handle *h, const TrialSource &src, double *out, bool 
   unsigned prefix = 0;
   const int shifts[3] = {21, 10, 0}, bits[3] = {11, 11, 10};
   unsigned long long cP = 0, cN = 0;   // counts at k1
+  long long kmax = -1;                 // the largest key of the data, where pass 0 says it may matter (else unknown)
   std::vector<unsigned long long> last;
   static const unsigned init[2] = {0u, 0xffffffffu};   // (static: the async copy below may read it after this frame)
   int rc = PLDA_OK;                                    // first failure seen by this rank
@@ -322,9 +347,33 @@ static int eer_device(plda_handle *h, const TrialSource &src, double *out, bool 
     if (!reduce_block_or_poison(h, src, "eer", H.data(), &rc)) continue;
     const int nb = 1 << bits[pass];
     if (pass == 0) {
+      // bins 0..3 and 2044..2047 of the top 11 key bits hold exactly the keys whose exponent is all ones (dcf.hip's level 0
+      // counts them the same way); sharded: H is global here, every rank refuses together and keeps making the same calls
+      unsigned long long bad = 0;
+      for (int b = 0; b < 4; ++b) bad += H[b] + H[EER_BINS + b] + H[2044 + b] + H[EER_BINS + 2044 + b];
+      if (bad) { rc = fail(h, PLDA_E_INVAL, "eer: %llu non-finite score(s) among the trials", bad); continue; }
       for (int b = 0; b < nb; ++b) { Nn += H[b]; Np += H[EER_BINS + b]; }
       if (src.windowed) { Np = src.tot_p; Nn = src.tot_n; Pb = src.base_p; Nb = src.base_n; }   // the lists are a window of the data
       if (Np == 0 || Nn == 0) { rc = fail(h, PLDA_E_INVAL, "eer: need at least one target and one impostor trial"); continue; }
+      // The largest key, exactly -- wanted only where the last candidate `s_max + 1e-8` can collapse onto s_max (|s_max| >= 2^27,
+      // see the end): two more passes down the top bin.  The decision is taken on the global H, so sharded ranks agree on it.
+      int top = nb - 1;
+      while (top > 0 && !(H[top] | H[EER_BINS + top])) --top;
+      if (!src.windowed && (last_candidate_collapses(key_score((unsigned)top << 21)) ||
+                            last_candidate_collapses(key_score((((unsigned)top + 1u) << 21) - 1u)))) {
+        unsigned kt = (unsigned)top;
+        std::vector<unsigned long long> Ht;
+        for (int lvl = 1; lvl < 3; ++lvl) {                 // (a failure does not end the loop: the same calls on every rank)
+          if (rc == PLDA_OK) rc = eer_pass(h, src, shifts[lvl], bits[lvl], kt, 1, dhist, dbelow, dabove, Ht);
+          Ht.resize(2 * EER_BINS);
+          if (!reduce_block_or_poison(h, src, "eer", Ht.data(), &rc)) continue;
+          int t = (1 << bits[lvl]) - 1;
+          while (t > 0 && !(Ht[t] | Ht[EER_BINS + t])) --t;
+          kt = (kt << bits[lvl]) | (unsigned)t;
+        }
+        if (rc != PLDA_OK) continue;
+        kmax = (long long)kt;
+      }
     }
     int sel = -1;
     unsigned long long P = Pb, N = Nb;
@@ -368,13 +417,23 @@ static int eer_device(plda_handle *h, const TrialSource &src, double *out, bool 
   // stay a tie and go to the later candidate; extended precision breaks it the other way).
   const double far1 = (double)(Nn - Nb - cN) / (double)Nn, frr1 = (double)(Pb + cP) / (double)Np;
   const double far0 = (double)(Nn - Nb) / (double)Nn, frr0 = (double)Pb / (double)Np;
+  // Where the last candidate collapses onto s_max it IS farfrr at s_max: the rates of the candidate before it, which it ties
+  // with and, being later, replaces.  That matters in two places: k1 is the largest key (either branch below would answer
+  // with a candidate next to it), or k1's successor is and the candidate between them wins.
   double thr, far, frr;
-  if (fabs(far1 - frr1) <= fabs(far0 - frr0)) {     // later candidate wins ties
-    const double s = key_score(k1);
+  const double s1 = key_score(k1);
+  if (k2 < 0 && last_candidate_collapses(s1)) {
+    thr = s1; far = far0; frr = frr0;
+  } else if (fabs(far1 - frr1) <= fabs(far0 - frr0)) {     // later candidate wins ties
+    const double s = s1;
     thr = k2 >= 0 ? s + ((double)key_score((unsigned)k2) - s) / 2.0 : s + 1e-8;
     far = (double)(Nn - Nb - cN) / (double)Nn; frr = (double)(Pb + cP) / (double)Np;
+    if (k2 >= 0 && last_candidate_collapses((double)key_score((unsigned)k2))) {
+      // (a window that reaches the top of the data does not know which of its keys is the largest: the three passes do)
+      if (src.windowed && src.none_above) { if (window_missed) *window_missed = true; return PLDA_OK; }
+      if (!src.windowed && k2 == kmax) thr = (double)key_score((unsigned)k2);
+    }
   } else {
-    const double s1 = key_score(k1);
     thr = k0 >= 0 ? (double)key_score((unsigned)k0) + (s1 - (double)key_score((unsigned)k0)) / 2.0 : s1;
     far = (double)(Nn - Nb) / (double)Nn; frr = (double)Pb / (double)Np;
   }
@@ -489,9 +548,11 @@ static int eer_matrix_windowed(plda_handle *h, const TrialSource &full, double *
   PLDA_HIP(h, hipMemcpyAsync(&wo, dwo, sizeof(wo), hipMemcpyDeviceToHost, h->stream));
   PLDA_HIP(h, hipStreamSynchronize(h->stream));
   ts.next("eer.finish_on_window");
+  if (wo.nonfinite) return fail(h, PLDA_E_INVAL, "eer: %llu non-finite score(s) among the trials", wo.nonfinite);
   if (wo.cursor[0] > cap || wo.cursor[1] > cap) return PLDA_OK;     // a list overflowed
-  // every trial is below, inside or above the window -- unless its score is a NaN (the three passes place those by key)
-  if (wo.below[0] + wo.below[1] + wo.cursor[0] + wo.cursor[1] + wo.above != (unsigned long long)M * (unsigned long long)Nt) return PLDA_OK;
+  // every finite trial is below, inside or above the window
+  const unsigned long long seen = wo.below[0] + wo.below[1] + wo.cursor[0] + wo.cursor[1], total = (unsigned long long)M * (unsigned long long)Nt;
+  if (seen > total) return PLDA_OK;
   const unsigned long long TP = wo.targets, TN = (unsigned long long)M * (unsigned long long)Nt - wo.targets;
   if (TP == 0 || TN == 0) return fail(h, PLDA_E_INVAL, "eer: need at least one target and one impostor trial");
   // exact g at the window's ends: below it FRR - FAR must still be negative, at its end non-negative
@@ -499,7 +560,7 @@ static int eer_matrix_windowed(plda_handle *h, const TrialSource &full, double *
   if ((u128)(wo.below[1] + wo.cursor[1]) * TN < (u128)(TN - wo.below[0] - wo.cursor[0]) * TP) return PLDA_OK;
   if (wo.cursor[0] + wo.cursor[1] == 0) return PLDA_OK;
   const TrialSource lst = TrialSource::lists(h->eer_list[1].as<float>(), (int64_t)wo.cursor[1], h->eer_list[0].as<float>(), (int64_t)wo.cursor[0])
-                              .window_of(wo.below[1], wo.below[0], TP, TN);
+                              .window_of(wo.below[1], wo.below[0], TP, TN, seen == total);
   bool missed = false;
   PLDA_TRY(eer_device(h, lst, out, &missed));
   *done = !missed;
@@ -548,18 +609,25 @@ int score_eer_device(plda_handle *h, const double *dU, const int32_t *dn, int n_
 // ------------------------------------------------------------------------------------
 constexpr int DET_MAX = 2047;
 __global__ __launch_bounds__(256) void det_minmax_kernel(const float *__restrict__ scores, int64_t ld, int64_t M, int64_t Nt,
-                                                         unsigned *__restrict__ mm /*[0] min key, [1] max key*/) {
+                                                         unsigned *__restrict__ mm /*[0] min key, [1] max key, [2..3] a 64-bit count of non-finite scores*/) {
   unsigned lo = 0xffffffffu, hi = 0u;
+  unsigned long long nf = 0;
   const int64_t total = M * Nt;
   for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * 256) {
-    const unsigned k = score_key(scores[(idx / Nt) * ld + idx % Nt]);
+    const float sc = scores[(idx / Nt) * ld + idx % Nt];
+    const unsigned k = score_key(sc);
     lo = k < lo ? k : lo; hi = k > hi ? k : hi;
+    nf += (__float_as_uint(sc) & 0x7f800000u) == 0x7f800000u ? 1u : 0u;      // NaN of either sign, +-Inf
   }
   for (int o = 32; o > 0; o >>= 1) {
     const unsigned a = __shfl_xor(lo, o), b = __shfl_xor(hi, o);
     lo = a < lo ? a : lo; hi = b > hi ? b : hi;
+    nf += __shfl_xor(nf, o);
   }
-  if ((threadIdx.x & 63) == 0) { atomicMin(mm, lo); atomicMax(mm + 1, hi); }
+  if ((threadIdx.x & 63) == 0) {
+    atomicMin(mm, lo); atomicMax(mm + 1, hi);
+    if (nf) atomicAdd(reinterpret_cast<unsigned long long *>(mm + 2), nf);
+  }
 }
 // cls < 0: the class of trial (i, j) is espk[i] == tspk[j]; else every score is of class cls (the two-list form, M = 1)
 __global__ __launch_bounds__(256) void det_hist_kernel(const float *__restrict__ scores, int64_t ld, int64_t M, int64_t Nt,
@@ -593,19 +661,22 @@ static int det_device(plda_handle *h, const TrialSource &src, int npoints, doubl
   if (npoints < 2 || npoints > DET_MAX) return fail(h, PLDA_E_INVAL, "det: 2 <= n_points <= %d", DET_MAX);
   const size_t hb = (size_t)2 * (DET_MAX + 1) * 8;
   unsigned long long *dhist;
-  unsigned *dmm;         // the smallest and the largest key, in a 64-byte line
+  unsigned *dmm;         // the smallest and the largest key and the count of non-finite scores, in a 64-byte line
   double *dthr;
   PLDA_TRY(carve(h, h->trial_hist, [&](Layout &c) { c.take(dhist, 2 * (DET_MAX + 1)).take(dmm, 16).take(dthr, DET_MAX).slack(64); }));
-  static const unsigned init[2] = {0xffffffffu, 0u};
-  PLDA_HIP(h, hipMemcpyAsync(dmm, init, 8, hipMemcpyHostToDevice, h->stream));
+  static const unsigned init[4] = {0xffffffffu, 0u, 0u, 0u};
+  PLDA_HIP(h, hipMemcpyAsync(dmm, init, 16, hipMemcpyHostToDevice, h->stream));
   PLDA_TRY(for_each_piece(src, [&](const TrialPiece &pc) -> int {
     det_minmax_kernel<<<(unsigned)std::min<int64_t>(ceil_div(pc.rows * pc.Nt, 256), 256 * 32), 256, 0, h->stream>>>(pc.scores, pc.ld, pc.rows, pc.Nt, dmm);
     return PLDA_OK;
   }));
   PLDA_LAUNCH_CHECK(h);
-  unsigned mm[2];
-  PLDA_HIP(h, hipMemcpyAsync(mm, dmm, 8, hipMemcpyDeviceToHost, h->stream));
+  unsigned mm[4];
+  PLDA_HIP(h, hipMemcpyAsync(mm, dmm, 16, hipMemcpyDeviceToHost, h->stream));
   PLDA_HIP(h, hipStreamSynchronize(h->stream));
+  // one Inf or NaN would make the step, and every threshold after the first, Inf or NaN: refused, like the EER's
+  const unsigned long long bad = (unsigned long long)mm[2] | ((unsigned long long)mm[3] << 32);
+  if (bad) return fail(h, PLDA_E_INVAL, "det: %llu non-finite score(s) among the trials", bad);
   if (mm[0] > mm[1]) return fail(h, PLDA_E_INVAL, "det: no scores");
   // the thresholds exactly as the definition accumulates them (float64 running sum)
   const double lo = (double)key_score(mm[0]), hi = (double)key_score(mm[1]);

@@ -55,7 +55,7 @@ struct TrialSource {
   int64_t row_step = 1;                        // MATRIX: every row_step-th row only (the pilot's sample)
   // windowed lists (the EER's single-pass form): the lists hold the scores of a key window only; the counts below it and
   // the class totals come from the full pass
-  bool windowed = false;
+  bool windowed = false, none_above = false;   // none_above: no trial lies above the window (its top is the data's top)
   unsigned long long base_p = 0, base_n = 0, tot_p = 0, tot_n = 0;
 
   // (M == 0: a rank of a sharded call that owns no row -- no piece, but it takes part in the reductions)
@@ -76,8 +76,8 @@ struct TrialSource {
   }
   TrialSource &reduced_by(TrialReduce r, void *c) { reduce = r; ctx = c; return *this; }
   TrialSource &every(int64_t step) { row_step = step; return *this; }
-  TrialSource &window_of(unsigned long long bp, unsigned long long bn, unsigned long long tp, unsigned long long tn) {
-    windowed = true; base_p = bp; base_n = bn; tot_p = tp; tot_n = tn;
+  TrialSource &window_of(unsigned long long bp, unsigned long long bn, unsigned long long tp, unsigned long long tn, bool no_above) {
+    windowed = true; none_above = no_above; base_p = bp; base_n = bn; tot_p = tp; tot_n = tn;
     return *this;
   }
 };

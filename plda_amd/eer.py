@@ -8,7 +8,8 @@ from . import _native as N
 
 
 def eer_from_lists(engine, truescores, impostscores):
-    """(threshold, FAR, FRR, EER) from target / impostor score arrays (eer.py's two files)."""
+    """(threshold, FAR, FRR, EER) from target / impostor score arrays (eer.py's two files).  The rates are farfrr at the
+    threshold.  A NaN or an Inf among the scores is refused: PldaError, code -1, with their count (every function here)."""
     pos = np.ascontiguousarray(truescores, np.float32)
     neg = np.ascontiguousarray(impostscores, np.float32)
     out = np.zeros(6)
@@ -20,7 +21,8 @@ def eer_from_lists(engine, truescores, impostscores):
 def eer_from_matrix_dev(engine, dscores, ld, m, nt, denrol_spk, dtest_spk):
     """Same on an HBM-resident fp32 trials matrix; trial (i, j) is a target iff
     enrol_spk[i] == test_spk[j] (int64 device arrays).  Returns the 6-vector
-    (threshold, FAR, FRR, EER, #targets, #impostors)."""
+    (threshold, FAR, FRR, EER, #targets, #impostors).  Non-finite trials are refused; the padding columns [nt, ld) may hold
+    anything."""
     out = np.zeros(6)
     N.check(engine._h, engine._lib.plda_eer_matrix_dev(engine._h, C.c_void_p(int(dscores)), int(ld), int(m), int(nt),
                                                        C.c_void_p(int(denrol_spk)), C.c_void_p(int(dtest_spk)),
@@ -42,7 +44,8 @@ def eer_from_operands_dev(engine, dU, dn, n_uniform, m, dV, nt, denrol_spk, dtes
 
 def det_from_lists(engine, truescores, impostscores, n_points=100):
     """(thresholds, FAR, FRR) at the n_points thresholds of the DET curve eer.py:34-62 plots (`bob.measure.plot.det(neg, pos,
-    100)`): arrays of length n_points.  The plot's coordinates are `ppndf(FRR)`, `ppndf(FAR)`."""
+    100)`): arrays of length n_points.  The plot's coordinates are `ppndf(FRR)`, `ppndf(FAR)`.  Non-finite scores are
+    refused."""
     pos = np.ascontiguousarray(truescores, np.float32)
     neg = np.ascontiguousarray(impostscores, np.float32)
     far, frr, thr = np.zeros(n_points), np.zeros(n_points), np.zeros(n_points)

@@ -162,6 +162,62 @@ def test_eer_restatement_properties():
     assert far == (n32 >= thr).mean() and frr == (p32 < thr).mean() and abs(far - frr) < 0.01
 
 
+def _eer_without_the_check(negatives, positives):
+    """oracle eer() as it stood before it refused non-finite scores, statement for statement"""
+    neg = np.sort(np.asarray(negatives, np.float32).astype(np.float64))
+    pos = np.sort(np.asarray(positives, np.float32).astype(np.float64))
+    s = np.unique(np.concatenate([neg, pos]))
+    mids = np.concatenate([[s[0]], s[:-1] + (s[1:] - s[:-1]) / 2.0, [s[-1] + 1e-8]])
+    far = (len(neg) - np.searchsorted(neg, mids, side="left")) / len(neg)
+    frr = np.searchsorted(pos, mids, side="left") / len(pos)
+    pred = np.abs(far - frr)
+    best = len(pred) - 1 - int(np.argmin(pred[::-1]))
+    return float(mids[best]), float(far[best]), float(frr[best]), float(0.5 * (far[best] + frr[best]))
+
+
+def _det_without_the_check(negatives, positives, n_points):
+    neg = np.sort(np.asarray(negatives, np.float32).astype(np.float64))
+    pos = np.sort(np.asarray(positives, np.float32).astype(np.float64))
+    lo = min(neg[0], pos[0]); hi = max(neg[-1], pos[-1])
+    step = (hi - lo) / (n_points - 1.0)
+    thr = np.empty(n_points)
+    t = lo
+    for i in range(n_points):
+        thr[i] = t
+        t += step
+    far = (len(neg) - np.searchsorted(neg, thr, side="left")) / len(neg)
+    frr = np.searchsorted(pos, thr, side="left") / len(pos)
+    return thr, far, frr
+
+
+def test_eer_and_det_restatements_refuse_non_finite_scores():
+    """oracle eer() / det(): a NaN of either sign or an Inf in either list raises ValueError with the count (the device's
+    contract, include/plda_hip.h) -- before, eer([-inf, -inf], [1.0]) answered (1.00000001, FAR 0, FRR 1) for separable data and
+    searchsorted put NaNs of both signs on top; on finite scores nothing changes, to the bit."""
+    rng = np.random.default_rng(3)
+    neg, pos = rng.normal(-1, 1, 500).astype(np.float32), rng.normal(1, 1, 60).astype(np.float32)
+    for bits in (0x7FC00000, 0xFFC00000, 0x7F800000, 0xFF800000):
+        bad = np.array([bits], np.uint32).view(np.float32)[0]
+        for n_bad_neg, n_bad_pos in ((1, 0), (0, 1), (2, 3)):
+            n, p = neg.copy(), pos.copy()
+            n[:n_bad_neg] = bad
+            p[len(p) - n_bad_pos:] = bad
+            with pytest.raises(ValueError, match="eer: %d non-finite" % (n_bad_neg + n_bad_pos)):
+                onp.eer(n, p)
+            with pytest.raises(ValueError, match="det: %d non-finite" % (n_bad_neg + n_bad_pos)):
+                onp.det(n, p, 100)
+    with pytest.raises(ValueError):
+        onp.eer([-np.inf, -np.inf], [1.0])
+    fixtures = [(neg, pos), ([0.1, 0.4, 0.35, 0.8], [0.3, 0.6, 0.9]), (np.round(neg, 1), np.round(pos, 1)), ([-0.25, 0.75], [0.5]),
+                (np.full(5, 3e8), np.full(3, 3e8)), ([0.0, -0.0, 1e-45], [-1e-45, 3.4028235e38]), (rng.normal(-1, 1, 2000), rng.normal(1, 1, 300))]
+    for n, p in fixtures:
+        assert onp.eer(n, p) == _eer_without_the_check(n, p)
+        for n_points in (2, 100):
+            for a, b in zip(onp.det(n, p, n_points), _det_without_the_check(n, p, n_points)):
+                assert np.array_equal(a.view(np.uint64), b.view(np.uint64))
+    assert onp.eer(np.full(5, 3e8), np.full(3, 3e8)) == (3e8, 1.0, 0.0, 0.5)      # farfrr at 3e8 + 1e-8 == 3e8
+
+
 def test_em_recovers_a_generating_two_covariance_model(oracle):
     """A known-answer test that does not come from this repository's own restatement: data DRAWN from the
     two-covariance model  x_ki = mu + y_k + e_ki,  y_k ~ N(0, B*),  e_ki ~ N(0, W*)  with many balanced speakers.
