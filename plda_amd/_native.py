@@ -165,14 +165,6 @@ SIGNATURES = {
     "plda_der_timed_sweep_dev": (C.c_int, [_vp] * 11 + [_i64, _vp, _vp, _vp, _i32, _i32, _vp, _i64, _vp, _vp, _vp]),
     "plda_der_timed_sweep": (C.c_int, [_vp] * 11 + [_i64, _vp, _vp, _vp, _i32, _i32, _vp, _i64, _vp, _vp, _vp]),
     "plda_der_jer_plan": (C.c_int, [_vp, _i64, _i64, _vp]),
-    "plda_der_jer_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
-    "plda_der_jer": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
-    "plda_der_jer_sweep_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
-    "plda_der_jer_sweep": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
-    "plda_der_timed_jer_dev": (C.c_int, [_vp] * 10 + [_i64, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
-    "plda_der_timed_jer": (C.c_int, [_vp] * 10 + [_i64, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
-    "plda_der_timed_jer_sweep_dev": (C.c_int, [_vp] * 11 + [_i64, _vp, _vp, _vp, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _vp]),
-    "plda_der_timed_jer_sweep": (C.c_int, [_vp] * 11 + [_i64, _vp, _vp, _vp, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _vp]),
     "plda_vbx_plan": (C.c_int, [_vp, _i64, _i64, _i64, _vp]),
     "plda_vbx_dev": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _f64, _f64, _f64, _f64, _i64, _f64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "plda_vbx": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _f64, _f64, _f64, _f64, _i64, _f64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -190,6 +182,14 @@ SIGNATURES = {
     "plda_embed_fit_dev": (C.c_int, [_vp, _vp, _i32, _i64, _i32, _vp, _i64, _i32, _i32, _f64, _f64, _vp]),
     "plda_embed_fit": (C.c_int, [_vp, _vp, _i32, _i64, _i32, _vp, _i32, _i32, _f64, _f64, _vp]),
 }
+
+
+# The JER entry points take the arguments of their plain form and the JER outputs behind them (jer, jmap, spk; a sweep: jer).
+# plda_der_timed_jer* is the JER form of the two-label entry point plda_der_timed_ovl*.
+for _jer, _base, _tail in (("plda_der_jer", "plda_der", 3), ("plda_der_jer_sweep", "plda_der_sweep", 1),
+                           ("plda_der_timed_jer", "plda_der_timed_ovl", 3), ("plda_der_timed_jer_sweep", "plda_der_timed_sweep", 1)):
+    for _form in ("", "_dev"):
+        SIGNATURES[_jer + _form] = (C.c_int, SIGNATURES[_base + _form][1] + [_vp] * _tail)
 
 
 class AdaptInfo(C.Structure):

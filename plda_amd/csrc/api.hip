@@ -2054,99 +2054,51 @@ int plda_score_dense_pca_ahc(plda_handle *h, const double *X, const int64_t *off
   });
 }
 
-// ---------------------------------------------------------------- diarisation error rate (der.hip)
-int plda_der_plan(plda_handle *h, int64_t Sr, int64_t Sh, int32_t out[3]) {
-  return entry(h, "plda_der_plan", [&] { return der_plan(h, Sr, Sh, out); });
-}
-
-int plda_der_dev(plda_handle *h, const int32_t *dref, const int32_t *dhyp, const int32_t *ddur, const int64_t *offsets, int64_t R,
-                 int64_t *dcounts, int32_t *dmap) {
-  return device_entry(h, "plda_der_dev", [&] { return der_device(h, dref, dhyp, ddur, offsets, R, dcounts, dmap); });
-}
-
-int plda_der(plda_handle *h, const int32_t *ref, const int32_t *hyp, const int32_t *dur, const int64_t *offsets, int64_t R,
-             int64_t *counts, int32_t *map) {
-  return entry(h, "plda_der", [&]() -> int {
-    if (!ref) return fail(h, PLDA_E_INVAL, "der: ref is NULL");
-    if (!hyp) return fail(h, PLDA_E_INVAL, "der: hyp is NULL");
-    if (!counts) return fail(h, PLDA_E_INVAL, "der: counts is NULL");
-    PLDA_TRY(der_validate(h, "der", offsets, R));
-    PLDA_TRY(set_device(h));
-    const int64_t T = offsets[R];
-    Staged st(h);
-    const int32_t *dRef, *dHyp, *dDur;
-    int64_t *dC;
-    int32_t *dM;
-    PLDA_TRY(st.in(ref, (size_t)T, &dRef));
-    PLDA_TRY(st.in(hyp, (size_t)T, &dHyp));
-    PLDA_TRY(st.in(dur, (size_t)T, &dDur));
-    PLDA_TRY(st.out(counts, (size_t)R * 4, &dC));
-    PLDA_TRY(st.out(map, (size_t)R * PLDA_DER_MAX_REF, &dM));
-    return st.finish(der_device(h, dRef, dHyp, dDur, offsets, R, dC, dM));
-  });
-}
-
-int plda_der_sweep_dev(plda_handle *h, const int32_t *dmerge_a, const int32_t *dmerge_b, const double *dmerge_cost,
-                       const int64_t *offsets, int64_t R, const int32_t *dref, const int32_t *ddur, const double *thresholds, int64_t Q,
-                       const int32_t *min_clusters, int64_t *dcounts, int32_t *dn_clusters) {
-  return device_entry(h, "plda_der_sweep_dev", [&] {
-    return der_sweep_device(h, dmerge_a, dmerge_b, dmerge_cost, offsets, R, dref, ddur, thresholds, Q, min_clusters, dcounts,
-                            dn_clusters);
-  });
-}
-
-int plda_der_sweep(plda_handle *h, const int32_t *merge_a, const int32_t *merge_b, const double *merge_cost, const int64_t *offsets,
-                   int64_t R, const int32_t *ref, const int32_t *dur, const double *thresholds, int64_t Q, const int32_t *min_clusters,
-                   int64_t *counts, int32_t *n_clusters) {
-  return entry(h, "plda_der_sweep", [&]() -> int {
-    if (!ref) return fail(h, PLDA_E_INVAL, "der_sweep: ref is NULL");
-    if (!counts) return fail(h, PLDA_E_INVAL, "der_sweep: counts is NULL");
-    if (!n_clusters) return fail(h, PLDA_E_INVAL, "der_sweep: n_clusters is NULL");
-    PLDA_TRY(der_sweep_validate(h, "der_sweep", offsets, R, thresholds, Q, min_clusters));
-    const int64_t T = offsets[R];
-    if (T > R && !(merge_a && merge_b && merge_cost)) return fail(h, PLDA_E_INVAL, "der_sweep: merge_a, merge_b or merge_cost is NULL");
-    PLDA_TRY(set_device(h));
-    Staged st(h);
-    const int32_t *dA, *dB, *dRef, *dDur;
-    const double *dCo;
-    int64_t *dC;
-    int32_t *dK;
-    PLDA_TRY(st.in(merge_a, (size_t)(T - R), &dA));       // (all three may be NULL when no recording has a merge: T == R)
-    PLDA_TRY(st.in(merge_b, (size_t)(T - R), &dB));
-    PLDA_TRY(st.in(merge_cost, (size_t)(T - R), &dCo));
-    PLDA_TRY(st.in(ref, (size_t)T, &dRef));
-    PLDA_TRY(st.in(dur, (size_t)T, &dDur));
-    PLDA_TRY(st.out(counts, (size_t)Q * R * 4, &dC));
-    PLDA_TRY(st.out(n_clusters, (size_t)Q * R, &dK));
-    return st.finish(der_sweep_device(h, dA, dB, dCo, offsets, R, dRef, dDur, thresholds, Q, min_clusters, dC, dK));
-  });
-}
-
-// ---------------------------------------------------------------- time-based diarisation error rate (der_time.hip)
-int plda_der_timed_plan(plda_handle *h, int64_t n_turns, int64_t n_seg, int64_t n_uem, int32_t collar, int32_t out[3]) {
-  return entry(h, "plda_der_timed_plan", [&] { return der_timed_plan(h, n_turns, n_seg, n_uem, collar, out); });
-}
-
-int plda_der_timed_dev(plda_handle *h, const int32_t *dturn_start, const int32_t *dturn_dur, const int32_t *dturn_spk,
-                       const int64_t *turn_off, const int32_t *dseg_start, const int32_t *dseg_dur, const int32_t *dhyp,
-                       const int64_t *offsets, int64_t R, const int32_t *duem_start, const int32_t *duem_dur, const int64_t *uem_off,
-                       int32_t collar, int32_t flags, int64_t *dcounts, int32_t *dmap) {
-  return device_entry(h, "plda_der_timed_dev", [&] {
-    const DerTimedArgs a{dturn_start, dturn_dur, dturn_spk, turn_off, dseg_start, dseg_dur, dhyp, offsets, R, duem_start, duem_dur, uem_off,
-                         collar, flags, nullptr, nullptr, nullptr, nullptr, 0, nullptr, dcounts, nullptr, dmap};
-    return der_timed_device(h, "der_timed", a, false);
-  });
-}
-
+// ---------------------------------------------------------------- diarisation error rate (der.hip, der_time.hip)
+// Every entry point below fills a DerArgs by field name -- the group all forms of its family share through one of the two
+// functions here, the rest by assignment -- and hands it to the device form (der_seg_device, der_timed_device) or to der_host.
 namespace {
-// the host form of both time-based calls: the check, every array uploaded, the outputs copied back
-int der_timed_host(plda_handle *h, const char *fn, DerTimedArgs a, bool sweep) {
-  PLDA_TRY(der_timed_validate(h, fn, a, sweep));
+DerArgs der_seg_args(const int32_t *ref, const int32_t *dur, const int64_t *offsets, int64_t R, int64_t *counts) {
+  DerArgs a;
+  a.ref = ref; a.dur = dur; a.offsets = offsets; a.R = R; a.counts = counts;
+  return a;
+}
+
+DerArgs der_timed_args(const int32_t *turn_start, const int32_t *turn_dur, const int32_t *turn_spk, const int64_t *turn_off,
+                       const int32_t *seg_start, const int32_t *seg_dur, const int64_t *offsets, int64_t R, const int32_t *uem_start,
+                       const int32_t *uem_dur, const int64_t *uem_off, int32_t collar, int32_t flags, int64_t *counts) {
+  DerArgs a;
+  a.tstart = turn_start; a.tdur = turn_dur; a.tspk = turn_spk; a.turn_off = turn_off;
+  a.sstart = seg_start; a.sdur = seg_dur; a.offsets = offsets; a.R = R;
+  a.ustart = uem_start; a.udur = uem_dur; a.uem_off = uem_off; a.collar = collar; a.flags = flags;
+  a.counts = counts;
+  return a;
+}
+
+// the sweep of a full merge record over Q thresholds
+void der_sweep_args(DerArgs &a, const int32_t *merge_a, const int32_t *merge_b, const double *merge_cost, const double *thresholds,
+                    int64_t Q, const int32_t *min_clusters, int32_t *n_clusters) {
+  a.ma = merge_a; a.mb = merge_b; a.mc = merge_cost; a.thresholds = thresholds; a.Q = Q; a.minc = min_clusters;
+  a.n_clusters = n_clusters;
+}
+
+// the JER form: jer behind the outputs of the plain form (a sweep has neither jmap nor spk)
+void der_jer_args(DerArgs &a, int64_t *jer, int32_t *jmap = nullptr, int64_t *spk = nullptr) {
+  a.jer_form = true;
+  a.jo.jer = reinterpret_cast<long long *>(jer); a.jo.jmap = jmap; a.jo.spk = reinterpret_cast<long long *>(spk);
+}
+
+// the host form of every DER call: the check, every array uploaded, the outputs copied back (an array the form does not
+// have is NULL and gets no temporary)
+int der_host(plda_handle *h, const char *fn, DerArgs a, bool sweep, bool timed) {
+  PLDA_TRY(timed ? der_timed_validate(h, fn, a, sweep) : der_seg_validate(h, fn, a, sweep));
   PLDA_TRY(set_device(h));
-  const int64_t T = a.offsets[a.R], R = a.R, nt = a.turn_off[R], nu = a.uem_off ? a.uem_off[R] : 0;
+  const int64_t T = a.offsets[a.R], R = a.R, nt = timed ? a.turn_off[R] : 0, nu = a.uem_off ? a.uem_off[R] : 0;
   Staged st(h);
   int64_t *counts = a.counts;
   int32_t *ncl = a.n_clusters, *map = a.map;
+  PLDA_TRY(st.in(a.ref, (size_t)T, &a.ref));
+  PLDA_TRY(st.in(a.dur, (size_t)T, &a.dur));
   PLDA_TRY(st.in(a.tstart, (size_t)nt, &a.tstart));
   PLDA_TRY(st.in(a.tdur, (size_t)nt, &a.tdur));
   PLDA_TRY(st.in(a.tspk, (size_t)nt, &a.tspk));
@@ -2167,18 +2119,78 @@ int der_timed_host(plda_handle *h, const char *fn, DerTimedArgs a, bool sweep) {
   PLDA_TRY(st.out(jer, (size_t)(sweep ? a.Q : 1) * R * 2, &a.jo.jer));
   PLDA_TRY(st.out(jmap, (size_t)R * PLDA_DER_MAX_REF, &a.jo.jmap));
   PLDA_TRY(st.out(spk, (size_t)R * PLDA_DER_MAX_REF * 3, &a.jo.spk));
-  return st.finish(der_timed_device(h, fn, a, sweep));
+  return st.finish(timed ? der_timed_device(h, fn, a, sweep) : der_seg_device(h, fn, a, sweep));
 }
 }  // namespace
+
+int plda_der_plan(plda_handle *h, int64_t Sr, int64_t Sh, int32_t out[3]) {
+  return entry(h, "plda_der_plan", [&] { return der_plan(h, Sr, Sh, out); });
+}
+
+int plda_der_dev(plda_handle *h, const int32_t *dref, const int32_t *dhyp, const int32_t *ddur, const int64_t *offsets, int64_t R,
+                 int64_t *dcounts, int32_t *dmap) {
+  return device_entry(h, "plda_der_dev", [&] {
+    DerArgs a = der_seg_args(dref, ddur, offsets, R, dcounts);
+    a.hyp = dhyp; a.map = dmap;
+    return der_seg_device(h, "der", a, false);
+  });
+}
+
+int plda_der(plda_handle *h, const int32_t *ref, const int32_t *hyp, const int32_t *dur, const int64_t *offsets, int64_t R,
+             int64_t *counts, int32_t *map) {
+  return entry(h, "plda_der", [&] {
+    DerArgs a = der_seg_args(ref, dur, offsets, R, counts);
+    a.hyp = hyp; a.map = map;
+    return der_host(h, "der", a, false, false);
+  });
+}
+
+int plda_der_sweep_dev(plda_handle *h, const int32_t *dmerge_a, const int32_t *dmerge_b, const double *dmerge_cost,
+                       const int64_t *offsets, int64_t R, const int32_t *dref, const int32_t *ddur, const double *thresholds, int64_t Q,
+                       const int32_t *min_clusters, int64_t *dcounts, int32_t *dn_clusters) {
+  return device_entry(h, "plda_der_sweep_dev", [&] {
+    DerArgs a = der_seg_args(dref, ddur, offsets, R, dcounts);
+    der_sweep_args(a, dmerge_a, dmerge_b, dmerge_cost, thresholds, Q, min_clusters, dn_clusters);
+    return der_seg_device(h, "der_sweep", a, true);
+  });
+}
+
+int plda_der_sweep(plda_handle *h, const int32_t *merge_a, const int32_t *merge_b, const double *merge_cost, const int64_t *offsets,
+                   int64_t R, const int32_t *ref, const int32_t *dur, const double *thresholds, int64_t Q, const int32_t *min_clusters,
+                   int64_t *counts, int32_t *n_clusters) {
+  return entry(h, "plda_der_sweep", [&] {
+    DerArgs a = der_seg_args(ref, dur, offsets, R, counts);
+    der_sweep_args(a, merge_a, merge_b, merge_cost, thresholds, Q, min_clusters, n_clusters);
+    return der_host(h, "der_sweep", a, true, false);
+  });
+}
+
+// ---------------------------------------------------------------- time-based diarisation error rate (der_time.hip)
+int plda_der_timed_plan(plda_handle *h, int64_t n_turns, int64_t n_seg, int64_t n_uem, int32_t collar, int32_t out[3]) {
+  return entry(h, "plda_der_timed_plan", [&] { return der_timed_plan(h, n_turns, n_seg, n_uem, collar, out); });
+}
+
+int plda_der_timed_dev(plda_handle *h, const int32_t *dturn_start, const int32_t *dturn_dur, const int32_t *dturn_spk,
+                       const int64_t *turn_off, const int32_t *dseg_start, const int32_t *dseg_dur, const int32_t *dhyp,
+                       const int64_t *offsets, int64_t R, const int32_t *duem_start, const int32_t *duem_dur, const int64_t *uem_off,
+                       int32_t collar, int32_t flags, int64_t *dcounts, int32_t *dmap) {
+  return device_entry(h, "plda_der_timed_dev", [&] {
+    DerArgs a = der_timed_args(dturn_start, dturn_dur, dturn_spk, turn_off, dseg_start, dseg_dur, offsets, R, duem_start, duem_dur, uem_off,
+                               collar, flags, dcounts);
+    a.hyp = dhyp; a.map = dmap;
+    return der_timed_device(h, "der_timed", a, false);
+  });
+}
 
 int plda_der_timed(plda_handle *h, const int32_t *turn_start, const int32_t *turn_dur, const int32_t *turn_spk, const int64_t *turn_off,
                    const int32_t *seg_start, const int32_t *seg_dur, const int32_t *hyp, const int64_t *offsets, int64_t R,
                    const int32_t *uem_start, const int32_t *uem_dur, const int64_t *uem_off, int32_t collar, int32_t flags,
                    int64_t *counts, int32_t *map) {
   return entry(h, "plda_der_timed", [&] {
-    const DerTimedArgs a{turn_start, turn_dur, turn_spk, turn_off, seg_start, seg_dur, hyp, offsets, R, uem_start, uem_dur, uem_off,
-                         collar, flags, nullptr, nullptr, nullptr, nullptr, 0, nullptr, counts, nullptr, map};
-    return der_timed_host(h, "der_timed", a, false);
+    DerArgs a = der_timed_args(turn_start, turn_dur, turn_spk, turn_off, seg_start, seg_dur, offsets, R, uem_start, uem_dur, uem_off, collar,
+                               flags, counts);
+    a.hyp = hyp; a.map = map;
+    return der_host(h, "der_timed", a, false, true);
   });
 }
 
@@ -2187,8 +2199,9 @@ int plda_der_timed_ovl_dev(plda_handle *h, const int32_t *dturn_start, const int
                            const int32_t *dhyp2, const int64_t *offsets, int64_t R, const int32_t *duem_start, const int32_t *duem_dur,
                            const int64_t *uem_off, int32_t collar, int32_t flags, int64_t *dcounts, int32_t *dmap) {
   return device_entry(h, "plda_der_timed_ovl_dev", [&] {
-    const DerTimedArgs a{dturn_start, dturn_dur, dturn_spk, turn_off, dseg_start, dseg_dur, dhyp, offsets, R, duem_start, duem_dur, uem_off,
-                         collar, flags, nullptr, nullptr, nullptr, nullptr, 0, nullptr, dcounts, nullptr, dmap, dhyp2};
+    DerArgs a = der_timed_args(dturn_start, dturn_dur, dturn_spk, turn_off, dseg_start, dseg_dur, offsets, R, duem_start, duem_dur, uem_off,
+                               collar, flags, dcounts);
+    a.hyp = dhyp; a.hyp2 = dhyp2; a.map = dmap;
     return der_timed_device(h, "der_timed_ovl", a, false);
   });
 }
@@ -2198,9 +2211,10 @@ int plda_der_timed_ovl(plda_handle *h, const int32_t *turn_start, const int32_t 
                        int64_t R, const int32_t *uem_start, const int32_t *uem_dur, const int64_t *uem_off, int32_t collar, int32_t flags,
                        int64_t *counts, int32_t *map) {
   return entry(h, "plda_der_timed_ovl", [&] {
-    const DerTimedArgs a{turn_start, turn_dur, turn_spk, turn_off, seg_start, seg_dur, hyp, offsets, R, uem_start, uem_dur, uem_off,
-                         collar, flags, nullptr, nullptr, nullptr, nullptr, 0, nullptr, counts, nullptr, map, hyp2};
-    return der_timed_host(h, "der_timed_ovl", a, false);
+    DerArgs a = der_timed_args(turn_start, turn_dur, turn_spk, turn_off, seg_start, seg_dur, offsets, R, uem_start, uem_dur, uem_off, collar,
+                               flags, counts);
+    a.hyp = hyp; a.hyp2 = hyp2; a.map = map;
+    return der_host(h, "der_timed_ovl", a, false, true);
   });
 }
 
@@ -2210,8 +2224,9 @@ int plda_der_timed_sweep_dev(plda_handle *h, const int32_t *dmerge_a, const int3
                              const int32_t *duem_start, const int32_t *duem_dur, const int64_t *uem_off, int32_t collar, int32_t flags,
                              const double *thresholds, int64_t Q, const int32_t *min_clusters, int64_t *dcounts, int32_t *dn_clusters) {
   return device_entry(h, "plda_der_timed_sweep_dev", [&] {
-    const DerTimedArgs a{dturn_start, dturn_dur, dturn_spk, turn_off, dseg_start, dseg_dur, nullptr, offsets, R, duem_start, duem_dur,
-                         uem_off, collar, flags, dmerge_a, dmerge_b, dmerge_cost, thresholds, Q, min_clusters, dcounts, dn_clusters, nullptr};
+    DerArgs a = der_timed_args(dturn_start, dturn_dur, dturn_spk, turn_off, dseg_start, dseg_dur, offsets, R, duem_start, duem_dur, uem_off,
+                               collar, flags, dcounts);
+    der_sweep_args(a, dmerge_a, dmerge_b, dmerge_cost, thresholds, Q, min_clusters, dn_clusters);
     return der_timed_device(h, "der_timed_sweep", a, true);
   });
 }
@@ -2222,9 +2237,10 @@ int plda_der_timed_sweep(plda_handle *h, const int32_t *merge_a, const int32_t *
                          const int32_t *uem_dur, const int64_t *uem_off, int32_t collar, int32_t flags, const double *thresholds,
                          int64_t Q, const int32_t *min_clusters, int64_t *counts, int32_t *n_clusters) {
   return entry(h, "plda_der_timed_sweep", [&] {
-    const DerTimedArgs a{turn_start, turn_dur, turn_spk, turn_off, seg_start, seg_dur, nullptr, offsets, R, uem_start, uem_dur, uem_off,
-                         collar, flags, merge_a, merge_b, merge_cost, thresholds, Q, min_clusters, counts, n_clusters, nullptr};
-    return der_timed_host(h, "der_timed_sweep", a, true);
+    DerArgs a = der_timed_args(turn_start, turn_dur, turn_spk, turn_off, seg_start, seg_dur, offsets, R, uem_start, uem_dur, uem_off, collar,
+                               flags, counts);
+    der_sweep_args(a, merge_a, merge_b, merge_cost, thresholds, Q, min_clusters, n_clusters);
+    return der_host(h, "der_timed_sweep", a, true, true);
   });
 }
 
@@ -2236,35 +2252,20 @@ int plda_der_jer_plan(plda_handle *h, int64_t Sr, int64_t Sh, int32_t out[3]) {
 int plda_der_jer_dev(plda_handle *h, const int32_t *dref, const int32_t *dhyp, const int32_t *ddur, const int64_t *offsets, int64_t R,
                      int64_t *dcounts, int32_t *dmap, int64_t *djer, int32_t *djmap, int64_t *dspk) {
   return device_entry(h, "plda_der_jer_dev", [&] {
-    const DerJerOut jo{reinterpret_cast<long long *>(djer), djmap, reinterpret_cast<long long *>(dspk)};
-    return der_device(h, dref, dhyp, ddur, offsets, R, dcounts, dmap, &jo);
+    DerArgs a = der_seg_args(dref, ddur, offsets, R, dcounts);
+    a.hyp = dhyp; a.map = dmap;
+    der_jer_args(a, djer, djmap, dspk);
+    return der_seg_device(h, "der_jer", a, false);
   });
 }
 
 int plda_der_jer(plda_handle *h, const int32_t *ref, const int32_t *hyp, const int32_t *dur, const int64_t *offsets, int64_t R,
                  int64_t *counts, int32_t *map, int64_t *jer, int32_t *jmap, int64_t *spk) {
-  return entry(h, "plda_der_jer", [&]() -> int {
-    if (!ref) return fail(h, PLDA_E_INVAL, "der_jer: ref is NULL");
-    if (!hyp) return fail(h, PLDA_E_INVAL, "der_jer: hyp is NULL");
-    if (!counts) return fail(h, PLDA_E_INVAL, "der_jer: counts is NULL");
-    if (!jer) return fail(h, PLDA_E_INVAL, "der_jer: jer is NULL");
-    PLDA_TRY(der_validate(h, "der_jer", offsets, R));
-    PLDA_TRY(set_device(h));
-    const int64_t T = offsets[R];
-    Staged st(h);
-    const int32_t *dRef, *dHyp, *dDur;
-    int64_t *dC, *dJ, *dS;
-    int32_t *dM, *dJm;
-    PLDA_TRY(st.in(ref, (size_t)T, &dRef));
-    PLDA_TRY(st.in(hyp, (size_t)T, &dHyp));
-    PLDA_TRY(st.in(dur, (size_t)T, &dDur));
-    PLDA_TRY(st.out(counts, (size_t)R * 4, &dC));
-    PLDA_TRY(st.out(map, (size_t)R * PLDA_DER_MAX_REF, &dM));
-    PLDA_TRY(st.out(jer, (size_t)R * 2, &dJ));
-    PLDA_TRY(st.out(jmap, (size_t)R * PLDA_DER_MAX_REF, &dJm));
-    PLDA_TRY(st.out(spk, (size_t)R * PLDA_DER_MAX_REF * 3, &dS));
-    const DerJerOut jo{reinterpret_cast<long long *>(dJ), dJm, reinterpret_cast<long long *>(dS)};
-    return st.finish(der_device(h, dRef, dHyp, dDur, offsets, R, dC, dM, &jo));
+  return entry(h, "plda_der_jer", [&] {
+    DerArgs a = der_seg_args(ref, dur, offsets, R, counts);
+    a.hyp = hyp; a.map = map;
+    der_jer_args(a, jer, jmap, spk);
+    return der_host(h, "der_jer", a, false, false);
   });
 }
 
@@ -2272,50 +2273,23 @@ int plda_der_jer_sweep_dev(plda_handle *h, const int32_t *dmerge_a, const int32_
                            const int64_t *offsets, int64_t R, const int32_t *dref, const int32_t *ddur, const double *thresholds,
                            int64_t Q, const int32_t *min_clusters, int64_t *dcounts, int32_t *dn_clusters, int64_t *djer) {
   return device_entry(h, "plda_der_jer_sweep_dev", [&] {
-    const DerJerOut jo{reinterpret_cast<long long *>(djer), nullptr, nullptr};
-    return der_sweep_device(h, dmerge_a, dmerge_b, dmerge_cost, offsets, R, dref, ddur, thresholds, Q, min_clusters, dcounts,
-                            dn_clusters, &jo);
+    DerArgs a = der_seg_args(dref, ddur, offsets, R, dcounts);
+    der_sweep_args(a, dmerge_a, dmerge_b, dmerge_cost, thresholds, Q, min_clusters, dn_clusters);
+    der_jer_args(a, djer);
+    return der_seg_device(h, "der_jer_sweep", a, true);
   });
 }
 
 int plda_der_jer_sweep(plda_handle *h, const int32_t *merge_a, const int32_t *merge_b, const double *merge_cost, const int64_t *offsets,
                        int64_t R, const int32_t *ref, const int32_t *dur, const double *thresholds, int64_t Q,
                        const int32_t *min_clusters, int64_t *counts, int32_t *n_clusters, int64_t *jer) {
-  return entry(h, "plda_der_jer_sweep", [&]() -> int {
-    if (!ref) return fail(h, PLDA_E_INVAL, "der_jer_sweep: ref is NULL");
-    if (!counts) return fail(h, PLDA_E_INVAL, "der_jer_sweep: counts is NULL");
-    if (!n_clusters) return fail(h, PLDA_E_INVAL, "der_jer_sweep: n_clusters is NULL");
-    if (!jer) return fail(h, PLDA_E_INVAL, "der_jer_sweep: jer is NULL");
-    PLDA_TRY(der_sweep_validate(h, "der_jer_sweep", offsets, R, thresholds, Q, min_clusters));
-    const int64_t T = offsets[R];
-    if (T > R && !(merge_a && merge_b && merge_cost))
-      return fail(h, PLDA_E_INVAL, "der_jer_sweep: merge_a, merge_b or merge_cost is NULL");
-    PLDA_TRY(set_device(h));
-    Staged st(h);
-    const int32_t *dA, *dB, *dRef, *dDur;
-    const double *dCo;
-    int64_t *dC, *dJ;
-    int32_t *dK;
-    PLDA_TRY(st.in(merge_a, (size_t)(T - R), &dA));       // (all three may be NULL when no recording has a merge: T == R)
-    PLDA_TRY(st.in(merge_b, (size_t)(T - R), &dB));
-    PLDA_TRY(st.in(merge_cost, (size_t)(T - R), &dCo));
-    PLDA_TRY(st.in(ref, (size_t)T, &dRef));
-    PLDA_TRY(st.in(dur, (size_t)T, &dDur));
-    PLDA_TRY(st.out(counts, (size_t)Q * R * 4, &dC));
-    PLDA_TRY(st.out(n_clusters, (size_t)Q * R, &dK));
-    PLDA_TRY(st.out(jer, (size_t)Q * R * 2, &dJ));
-    const DerJerOut jo{reinterpret_cast<long long *>(dJ), nullptr, nullptr};
-    return st.finish(der_sweep_device(h, dA, dB, dCo, offsets, R, dRef, dDur, thresholds, Q, min_clusters, dC, dK, &jo));
+  return entry(h, "plda_der_jer_sweep", [&] {
+    DerArgs a = der_seg_args(ref, dur, offsets, R, counts);
+    der_sweep_args(a, merge_a, merge_b, merge_cost, thresholds, Q, min_clusters, n_clusters);
+    der_jer_args(a, jer);
+    return der_host(h, "der_jer_sweep", a, true, false);
   });
 }
-
-namespace {
-// the JER form of a time-based call: `a` with the three outputs behind it
-void der_timed_jer_args(DerTimedArgs &a, int64_t *jer, int32_t *jmap, int64_t *spk) {
-  a.jer_form = true;
-  a.jo = DerJerOut{reinterpret_cast<long long *>(jer), jmap, reinterpret_cast<long long *>(spk)};
-}
-}  // namespace
 
 int plda_der_timed_jer_dev(plda_handle *h, const int32_t *dturn_start, const int32_t *dturn_dur, const int32_t *dturn_spk,
                            const int64_t *turn_off, const int32_t *dseg_start, const int32_t *dseg_dur, const int32_t *dhyp,
@@ -2323,9 +2297,10 @@ int plda_der_timed_jer_dev(plda_handle *h, const int32_t *dturn_start, const int
                            const int64_t *uem_off, int32_t collar, int32_t flags, int64_t *dcounts, int32_t *dmap, int64_t *djer,
                            int32_t *djmap, int64_t *dspk) {
   return device_entry(h, "plda_der_timed_jer_dev", [&] {
-    DerTimedArgs a{dturn_start, dturn_dur, dturn_spk, turn_off, dseg_start, dseg_dur, dhyp, offsets, R, duem_start, duem_dur, uem_off,
-                         collar, flags, nullptr, nullptr, nullptr, nullptr, 0, nullptr, dcounts, nullptr, dmap, dhyp2};
-    der_timed_jer_args(a, djer, djmap, dspk);
+    DerArgs a = der_timed_args(dturn_start, dturn_dur, dturn_spk, turn_off, dseg_start, dseg_dur, offsets, R, duem_start, duem_dur, uem_off,
+                               collar, flags, dcounts);
+    a.hyp = dhyp; a.hyp2 = dhyp2; a.map = dmap;
+    der_jer_args(a, djer, djmap, dspk);
     return der_timed_device(h, "der_timed_jer", a, false);
   });
 }
@@ -2335,10 +2310,11 @@ int plda_der_timed_jer(plda_handle *h, const int32_t *turn_start, const int32_t 
                        int64_t R, const int32_t *uem_start, const int32_t *uem_dur, const int64_t *uem_off, int32_t collar, int32_t flags,
                        int64_t *counts, int32_t *map, int64_t *jer, int32_t *jmap, int64_t *spk) {
   return entry(h, "plda_der_timed_jer", [&] {
-    DerTimedArgs a{turn_start, turn_dur, turn_spk, turn_off, seg_start, seg_dur, hyp, offsets, R, uem_start, uem_dur, uem_off,
-                         collar, flags, nullptr, nullptr, nullptr, nullptr, 0, nullptr, counts, nullptr, map, hyp2};
-    der_timed_jer_args(a, jer, jmap, spk);
-    return der_timed_host(h, "der_timed_jer", a, false);
+    DerArgs a = der_timed_args(turn_start, turn_dur, turn_spk, turn_off, seg_start, seg_dur, offsets, R, uem_start, uem_dur, uem_off, collar,
+                               flags, counts);
+    a.hyp = hyp; a.hyp2 = hyp2; a.map = map;
+    der_jer_args(a, jer, jmap, spk);
+    return der_host(h, "der_timed_jer", a, false, true);
   });
 }
 
@@ -2349,9 +2325,10 @@ int plda_der_timed_jer_sweep_dev(plda_handle *h, const int32_t *dmerge_a, const 
                                  int32_t flags, const double *thresholds, int64_t Q, const int32_t *min_clusters, int64_t *dcounts,
                                  int32_t *dn_clusters, int64_t *djer) {
   return device_entry(h, "plda_der_timed_jer_sweep_dev", [&] {
-    DerTimedArgs a{dturn_start, dturn_dur, dturn_spk, turn_off, dseg_start, dseg_dur, nullptr, offsets, R, duem_start, duem_dur,
-                         uem_off, collar, flags, dmerge_a, dmerge_b, dmerge_cost, thresholds, Q, min_clusters, dcounts, dn_clusters, nullptr};
-    der_timed_jer_args(a, djer, nullptr, nullptr);
+    DerArgs a = der_timed_args(dturn_start, dturn_dur, dturn_spk, turn_off, dseg_start, dseg_dur, offsets, R, duem_start, duem_dur, uem_off,
+                               collar, flags, dcounts);
+    der_sweep_args(a, dmerge_a, dmerge_b, dmerge_cost, thresholds, Q, min_clusters, dn_clusters);
+    der_jer_args(a, djer);
     return der_timed_device(h, "der_timed_jer_sweep", a, true);
   });
 }
@@ -2363,10 +2340,11 @@ int plda_der_timed_jer_sweep(plda_handle *h, const int32_t *merge_a, const int32
                              const double *thresholds, int64_t Q, const int32_t *min_clusters, int64_t *counts, int32_t *n_clusters,
                              int64_t *jer) {
   return entry(h, "plda_der_timed_jer_sweep", [&] {
-    DerTimedArgs a{turn_start, turn_dur, turn_spk, turn_off, seg_start, seg_dur, nullptr, offsets, R, uem_start, uem_dur, uem_off,
-                         collar, flags, merge_a, merge_b, merge_cost, thresholds, Q, min_clusters, counts, n_clusters, nullptr};
-    der_timed_jer_args(a, jer, nullptr, nullptr);
-    return der_timed_host(h, "der_timed_jer_sweep", a, true);
+    DerArgs a = der_timed_args(turn_start, turn_dur, turn_spk, turn_off, seg_start, seg_dur, offsets, R, uem_start, uem_dur, uem_off, collar,
+                               flags, counts);
+    der_sweep_args(a, merge_a, merge_b, merge_cost, thresholds, Q, min_clusters, n_clusters);
+    der_jer_args(a, jer);
+    return der_host(h, "der_timed_jer_sweep", a, true, true);
   });
 }
 

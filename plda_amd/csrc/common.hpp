@@ -568,16 +568,30 @@ int der_plan(plda_handle *h, int64_t Sr, int64_t Sh, int32_t *out);
 int der_jer_plan(plda_handle *h, int64_t Sr, int64_t Sh, int32_t *out);
 // the outputs the JER entry points add (K22): jer [.., 2] = {n_ref, jsum}; jmap [R, 64] and spk [R, 64, 3] nullable
 struct DerJerOut { long long *jer = nullptr; int *jmap = nullptr; long long *spk = nullptr; };
-// the host-side argument checks of the two device forms (the host forms run them before they allocate or upload)
+// the checks of offsets / R and of the sweep's thresholds, Q and min_clusters, shared by every form
 int der_validate(plda_handle *h, const char *fn, const int64_t *offsets, int64_t R);
 int der_sweep_validate(plda_handle *h, const char *fn, const int64_t *offsets, int64_t R, const double *thresholds, int64_t Q,
                        const int32_t *minc);
-// jo non-null: the JER form (jo->jer is checked there; the sum of a recording's durations is then at most 2^30)
-int der_device(plda_handle *h, const int32_t *dref, const int32_t *dhyp, const int32_t *ddur, const int64_t *offsets, int64_t R,
-               int64_t *dcounts, int32_t *dmap, const DerJerOut *jo = nullptr);
-int der_sweep_device(plda_handle *h, const int32_t *dma, const int32_t *dmb, const double *dmc, const int64_t *offsets, int64_t R,
-                     const int32_t *dref, const int32_t *ddur, const double *thresholds, int64_t Q, const int32_t *minc,
-                     int64_t *dcounts, int32_t *dn_clusters, const DerJerOut *jo = nullptr);
+// The arguments of every plda_der* call; a field the form does not have stays NULL / 0.  Segment forms: ref, dur; time-based
+// forms: the turns, segments and UEM.  sweep: ma, mb, mc, thresholds, Q, minc, n_clusters; otherwise hyp (hyp2), map.
+struct DerArgs {
+  const int32_t *ref = nullptr, *dur = nullptr;
+  const int32_t *tstart = nullptr, *tdur = nullptr, *tspk = nullptr; const int64_t *turn_off = nullptr;
+  const int32_t *sstart = nullptr, *sdur = nullptr;
+  const int32_t *hyp = nullptr, *hyp2 = nullptr;      // hyp2: the second hypothesis label of every segment (plda_der_timed_ovl, nullable)
+  const int64_t *offsets = nullptr; int64_t R = 0;
+  const int32_t *ustart = nullptr, *udur = nullptr; const int64_t *uem_off = nullptr;
+  int32_t collar = 0, flags = 0;
+  const int32_t *ma = nullptr, *mb = nullptr; const double *mc = nullptr;
+  const double *thresholds = nullptr; int64_t Q = 0; const int32_t *minc = nullptr;
+  int64_t *counts = nullptr; int32_t *n_clusters = nullptr, *map = nullptr;
+  bool jer_form = false;              // plda_der*_jer*: jo.jer is required, jo.jmap and jo.spk are nullable
+  DerJerOut jo;
+};
+// the host-side argument check of the segment forms (pointers are only compared with NULL; the host forms run it before they
+// allocate or upload) and their device form (jer_form: the sum of a recording's durations is at most 2^30)
+int der_seg_validate(plda_handle *h, const char *fn, const DerArgs &a, bool sweep);
+int der_seg_device(plda_handle *h, const char *fn, const DerArgs &a, bool sweep);
 
 // ---- der_time.hip (time-based DER: overlapped reference speech, collar, UEM; every *_off array is a HOST array) ----
 // one recording's scored atoms, as der_atoms_kernel leaves them and der.hip's solve reads them
@@ -586,26 +600,12 @@ struct DerTimedDev {
   const DerTimedRec *recs; const int *ticks; const int *seg; const unsigned long long *mask;
   const int *hyp2;      // plda_der_timed_ovl: the second label of every segment; NULL: one label per segment
 };
-// the arguments of plda_der_timed* (sweep: ma, mb, mc, thresholds, Q, minc, n_clusters; otherwise hyp, map)
-struct DerTimedArgs {
-  const int32_t *tstart, *tdur, *tspk; const int64_t *turn_off;
-  const int32_t *sstart, *sdur, *hyp; const int64_t *offsets; int64_t R;
-  const int32_t *ustart, *udur; const int64_t *uem_off;
-  int32_t collar, flags;
-  const int32_t *ma, *mb; const double *mc; const double *thresholds; int64_t Q; const int32_t *minc;
-  int64_t *counts; int32_t *n_clusters, *map;
-  const int32_t *hyp2 = nullptr;      // plda_der_timed_ovl: the second hypothesis label of every segment (nullable)
-  bool jer_form = false;              // plda_der_timed_jer*: jo.jer is required, jo.jmap and jo.spk are nullable
-  DerJerOut jo;
-};
 int der_timed_plan(plda_handle *h, int64_t n_turns, int64_t n_seg, int64_t n_uem, int32_t collar, int32_t *out);
 // the host-side argument check (pointers are only compared with NULL; the host forms run it before they allocate or upload)
-int der_timed_validate(plda_handle *h, const char *fn, const DerTimedArgs &a, bool sweep);
-int der_timed_device(plda_handle *h, const char *fn, const DerTimedArgs &a, bool sweep);
-// der.hip: the solves behind the atoms (Q = 0: against dhyp; Q >= 1: the sweep of the merge record)
-int der_timed_solve(plda_handle *h, const char *fn, const DerTimedRec *recs, const DerTimedDev &td, const int32_t *dhyp,
-                    const int32_t *dma, const int32_t *dmb, const double *dmc, const int64_t *offsets, int64_t R, const double *thresholds,
-                    int64_t Q, const int32_t *minc, int64_t *dcounts, int32_t *dn_clusters, int32_t *dmap, const DerJerOut *jo = nullptr);
+int der_timed_validate(plda_handle *h, const char *fn, const DerArgs &a, bool sweep);
+int der_timed_device(plda_handle *h, const char *fn, const DerArgs &a, bool sweep);
+// der.hip: the solves behind the atoms (against a.hyp, or the sweep of the merge record); recs is the host copy of td.recs
+int der_timed_solve(plda_handle *h, const char *fn, const DerTimedRec *recs, const DerTimedDev &td, const DerArgs &a, bool sweep);
 
 // ---- vbx.hip (VBx resegmentation: a batched Bayesian HMM on PLDA vectors; offsets / gamma_off / pi_off are HOST arrays) ----
 int vbx_plan(plda_handle *h, int64_t T, int64_t S, int64_t D, int32_t *out);

@@ -11,27 +11,34 @@
 //                       limit, a negative duration) added to one counter; Sr and Sh, the distinct labels of either side
 //   der_prefix_kernel   sweep, grid (recordings, thresholds): the number of merges the stop rule of the AHC lets through
 //                       (Sh = N - that); a record that ends first, or an entry that is no merge, is counted as a bad record
-//   der_solve_kernel    <HBM = false> the Sr x W int64 confusion matrix in LDS (W = max(Sr, Sh): zero columns pad a
+//   der_solve_kernel    <HBM, SWEEP, ATOMS, OVL, JER>, the one __global__ around der_solve_body; all 20 instantiations share one
+//                       signature (a form reads only its own arguments) and are launched through der_solve_fn's pointer.
+//                       <HBM = false> the Sr x W int64 confusion matrix in LDS (W = max(Sr, Sh): zero columns pad a
 //                       hypothesis with fewer speakers than the reference);  <HBM = true> the matrix in handle scratch.
-//                       <SWEEP> the hypothesis labels are the slots of the replayed merge prefix.
 //                       Both keep the column state (potential, slack, predecessor, owner, flag, label) in LDS.
-//   der_solve_timed_kernel  the same body (der_solve_body<HBM, SWEEP, ATOMS = true>) on the scored atoms that der_time.hip cuts
-//                       from reference turns, hypothesis segments, collar and UEM (K20): an atom of `ticks` ticks adds them
-//                       to C[i][j] for every reference speaker i of its 64-bit mask
-//   der_solve_ovl_kernel    the atom form with up to two hypothesis labels per segment (K21, plda_der_timed_ovl; der_solve_body<HBM,
-//                       false, true, OVL = true>): the labels present range over hyp and hyp2, an atom adds its ticks to C[i][j]
-//                       for both labels of its segment, and nhyp in the four counters is the number of labels >= 0
-//   der_solve_jer_kernel    <HBM, SWEEP, ATOMS, OVL> the JER form of all four shapes (K22; der_solve_body<.., JER = true>): the
-//                       same fill, with the per-speaker tick sums rt and ht beside it; the same first assignment and outputs;
-//                       then the Jaccard weights in place above C and a second assignment on them (the comment at
-//                       der_solve_body says where w is computed and why); jer, jmap and spk come from the second
+//                       <SWEEP> the hypothesis labels are the slots of the replayed merge prefix.
+//                       <ATOMS> the reference side is the scored atoms that der_time.hip cuts from reference turns,
+//                       hypothesis segments, collar and UEM (K20): an atom of `ticks` ticks adds them to C[i][j] for every
+//                       reference speaker i of its 64-bit mask
+//                       <OVL> (with ATOMS, without SWEEP) up to two hypothesis labels per segment (K21, plda_der_timed_ovl):
+//                       the labels present range over hyp and hyp2, an atom adds its ticks to C[i][j] for both labels of
+//                       its segment, and nhyp in the four counters is the number of labels >= 0
+//                       <JER> the JER form of all five shapes (K22): the same fill, with the per-speaker tick sums rt and ht
+//                       beside it; the same first assignment and outputs; then the Jaccard weights in place above C and a
+//                       second assignment on them (the comment at der_solve_body says where w is computed and why); jer,
+//                       jmap and spk come from the second
 //
-// Resources on gfx950 (hipcc --offload-arch=gfx950 -O3 -Rpass-analysis=kernel-resource-usage), VGPRs in the LDS / scratch class;
-// no kernel of this file has scratch memory or spills:
-//   der_count_kernel 12 (<false> and <true>);  der_prefix_kernel 14
-//   der_solve_kernel, der_solve_timed_kernel, der_solve_ovl_kernel                          44 / 40, sweep or not
-//   der_solve_jer_kernel: segment, atoms, two labels                                        82 / 82
-//                         the two sweeps                                                    76 / 84
+// Resources on gfx950 (hipcc --offload-arch=gfx950 -O3 -Rpass-analysis=kernel-resource-usage), LDS / scratch class; no kernel
+// of this file has scratch memory or spills, and der_solve_kernel has no static LDS:
+//   der_count_kernel 12 VGPRs (<false> and <true>);  der_prefix_kernel 14
+//   der_solve_kernel <SWEEP, ATOMS, OVL>     plain: VGPRs   SGPRs     waves/SIMD     JER: VGPRs   SGPRs     waves/SIMD
+//     segments            <0, 0, 0>                 44 / 40   48 / 54   8 / 8             82 / 82   83 / 91   5 / 5
+//     atoms               <0, 1, 0>                 44 / 40   52 / 60   8 / 8             82 / 82   83 / 91   5 / 5
+//     atoms, two labels   <0, 1, 1>                 44 / 40   58 / 65   8 / 8             82 / 82   83 / 91   5 / 5
+//     sweep of segments   <1, 0, 0>                 44 / 40   52 / 55   8 / 8             76 / 84   82 / 90   6 / 5
+//     sweep of atoms      <1, 1, 0>                 44 / 40   59 / 62   8 / 8             76 / 84   82 / 90   6 / 5
+// (the figures of the four kernels with four signatures that this one replaced; the plain two-label shape alone moved, by two
+// SGPRs, from 56 / 63)
 // With JER = false der_solve_body compiles to what it was before the JER form existed: six of the ten plain instantiations are
 // the same instructions in the same order, the other four (segment and two-label form, both classes) differ in the order of
 // two independent register clears.
@@ -533,72 +540,42 @@ der_jer_out:
   }
 }
 
-template <bool HBM, bool SWEEP>
+// Every form is this one kernel, the form in its template arguments (ref and dur are unused with ATOMS, td without it, ma and
+// mb without SWEEP, jo without JER: the body reads none of them then).  Resources: the table in the file header.
+template <bool HBM, bool SWEEP, bool ATOMS, bool OVL, bool JER>
 __global__ __launch_bounds__(DER_T) void der_solve_kernel(const int *__restrict__ ref, const int *__restrict__ hyp,
                                                           const int *__restrict__ dur, const int *__restrict__ ma,
                                                           const int *__restrict__ mb, const DerRec *__restrict__ tab,
                                                           long long *scratch, long long *__restrict__ counts,
-                                                          int *__restrict__ n_clusters, int *__restrict__ map) {
-  der_solve_body<HBM, SWEEP, false>(ref, hyp, dur, ma, mb, tab, scratch, counts, n_clusters, map, DerTimedDev{});
+                                                          int *__restrict__ n_clusters, int *__restrict__ map,
+                                                          const DerTimedDev td, const DerJerOut jo) {
+  der_solve_body<HBM, SWEEP, ATOMS, OVL, JER>(ref, hyp, dur, ma, mb, tab, scratch, counts, n_clusters, map, td, jo);
 }
 
-// the time-based form: the atoms of der_atoms_kernel (der_time.hip) in place of ref and dur
-template <bool HBM, bool SWEEP>
-__global__ __launch_bounds__(DER_T) void der_solve_timed_kernel(const int *__restrict__ hyp, const int *__restrict__ ma,
-                                                                const int *__restrict__ mb, const DerRec *__restrict__ tab,
-                                                                long long *scratch, long long *__restrict__ counts,
-                                                                int *__restrict__ n_clusters, int *__restrict__ map, const DerTimedDev td) {
-  der_solve_body<HBM, SWEEP, true>(nullptr, hyp, nullptr, ma, mb, tab, scratch, counts, n_clusters, map, td);
+// the instantiation of a launch: 2 classes x 2 (plain, JER) x 5 shapes -- segments, atoms, atoms with two labels, and the
+// sweeps of segments and of atoms (a sweep has no second label, and a second label belongs to atoms)
+using DerSolveFn = void (*)(const int *, const int *, const int *, const int *, const int *, const DerRec *, long long *, long long *, int *,
+                            int *, DerTimedDev, DerJerOut);
+template <bool HBM, bool JER> DerSolveFn der_solve_shape(bool sweep, bool atoms, bool ovl) {
+  if (sweep) return atoms ? &der_solve_kernel<HBM, true, true, false, JER> : &der_solve_kernel<HBM, true, false, false, JER>;
+  if (ovl) return &der_solve_kernel<HBM, false, true, true, JER>;
+  return atoms ? &der_solve_kernel<HBM, false, true, false, JER> : &der_solve_kernel<HBM, false, false, false, JER>;
+}
+DerSolveFn der_solve_fn(bool hbm, bool sweep, bool atoms, bool ovl, bool jer) {
+  if (hbm) return jer ? der_solve_shape<true, true>(sweep, atoms, ovl) : der_solve_shape<true, false>(sweep, atoms, ovl);
+  return jer ? der_solve_shape<false, true>(sweep, atoms, ovl) : der_solve_shape<false, false>(sweep, atoms, ovl);
 }
 
-// the time-based form with up to two hypothesis labels per segment (plda_der_timed_ovl; td.hyp2 is not NULL)
-template <bool HBM>
-__global__ __launch_bounds__(DER_T) void der_solve_ovl_kernel(const int *__restrict__ hyp, const DerRec *__restrict__ tab,
-                                                              long long *scratch, long long *__restrict__ counts,
-                                                              int *__restrict__ map, const DerTimedDev td) {
-  der_solve_body<HBM, false, true, true>(nullptr, hyp, nullptr, nullptr, nullptr, tab, scratch, counts, nullptr, map, td);
-}
-
-// the JER form of all four shapes (K22): one kernel, the shape in its template arguments (td is unused without ATOMS; ref and
-// dur with it).  Resources: the table in the file header.
-template <bool HBM, bool SWEEP, bool ATOMS, bool OVL>
-__global__ __launch_bounds__(DER_T) void der_solve_jer_kernel(const int *__restrict__ ref, const int *__restrict__ hyp,
-                                                              const int *__restrict__ dur, const int *__restrict__ ma,
-                                                              const int *__restrict__ mb, const DerRec *__restrict__ tab,
-                                                              long long *scratch, long long *__restrict__ counts,
-                                                              int *__restrict__ n_clusters, int *__restrict__ map,
-                                                              const DerTimedDev td, const DerJerOut jo) {
-  der_solve_body<HBM, SWEEP, ATOMS, OVL, true>(ref, hyp, dur, ma, mb, tab, scratch, counts, n_clusters, map, td, jo);
-}
-
-// the instantiation of a launch: the class, atoms or segments, one or two labels (the sweeps have no second label)
-using DerJerFn = void (*)(const int *, const int *, const int *, const int *, const int *, const DerRec *, long long *, long long *, int *,
-                          int *, DerTimedDev, DerJerOut);
-template <bool SWEEP> DerJerFn der_jer_fn(bool hbm, bool atoms, bool ovl) {
-  if constexpr (!SWEEP)
-    if (ovl) return hbm ? &der_solve_jer_kernel<true, false, true, true> : &der_solve_jer_kernel<false, false, true, true>;
-  if (atoms) return hbm ? &der_solve_jer_kernel<true, SWEEP, true, false> : &der_solve_jer_kernel<false, SWEEP, true, false>;
-  return hbm ? &der_solve_jer_kernel<true, SWEEP, false, false> : &der_solve_jer_kernel<false, SWEEP, false, false>;
-}
-
-template <bool SWEEP> int der_jer_attr(plda_handle *h) {
+// every instantiation may take a whole CU's LDS: set once per device
+int der_solve_attr(plda_handle *h) {
   static DeviceOnce attr;
   if (attr.needed(h->device)) {
-    for (int k = 0; k < (SWEEP ? 4 : 6); ++k)
-      PLDA_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void *>(der_jer_fn<SWEEP>(k & 1, (k >> 1) != 0, (k >> 1) == 2)),
+    for (int k = 0; k < 32; ++k) {
+      const bool hbm = k & 1, jer = k & 2, sweep = k & 4, atoms = k & 8, ovl = k & 16;
+      if (ovl && (sweep || !atoms)) continue;
+      PLDA_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void *>(der_solve_fn(hbm, sweep, atoms, ovl, jer)),
                                       hipFuncAttributeMaxDynamicSharedMemorySize, DER_LDS_BYTES));
-    attr.done(h->device);
-  }
-  return PLDA_OK;
-}
-
-template <bool HBM, bool SWEEP, bool ATOMS, bool OVL = false> int der_solve_attr(plda_handle *h) {
-  static DeviceOnce attr;
-  if (attr.needed(h->device)) {
-    const void *fn = OVL     ? reinterpret_cast<const void *>(&der_solve_ovl_kernel<HBM>)
-                     : ATOMS ? reinterpret_cast<const void *>(&der_solve_timed_kernel<HBM, SWEEP>)
-                             : reinterpret_cast<const void *>(&der_solve_kernel<HBM, SWEEP>);
-    PLDA_HIP(h, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, DER_LDS_BYTES));
+    }
     attr.done(h->device);
   }
   return PLDA_OK;
@@ -675,54 +652,17 @@ int der_solve_enqueue(plda_handle *h, std::vector<DerRec> &items, std::vector<De
   const DerRec *dtab = h->der_tab.as<DerRec>();
   long long *scratch = h->der_scratch.as<long long>();
   const bool ovl = !SWEEP && td && td->hyp2;
-  if (jo) {                                   // the JER form: one kernel signature, the instantiation picked by der_jer_fn
-    PLDA_TRY(der_jer_attr<SWEEP>(h));
-    TraceScope ts(h, SWEEP ? "der.jer_sweep_solve" : "der.jer_solve");
-    const DerTimedDev tdv = td ? *td : DerTimedDev{};
-    for (const Launch &L : launches) {
-      const DerJerFn fn = der_jer_fn<SWEEP>(L.hbm, td != nullptr, ovl);
-      for (int64_t c0 = 0; c0 < L.count; c0 += 1 << 20) {
-        const unsigned c = (unsigned)std::min<int64_t>(1 << 20, L.count - c0);
-        fn<<<c, DER_T, (size_t)L.lds, h->stream>>>(dref, dhyp, ddur, dma, dmb, dtab + L.first + c0, L.hbm ? scratch : nullptr, dcounts,
-                                                   dn_clusters, dmap, tdv, *jo);
-        PLDA_LAUNCH_CHECK(h);
-      }
-    }
-    return PLDA_OK;
-  }
-  if (ovl) {
-    PLDA_TRY((der_solve_attr<false, false, true, true>(h)));
-    PLDA_TRY((der_solve_attr<true, false, true, true>(h)));
-  } else if (td) {
-    PLDA_TRY((der_solve_attr<false, SWEEP, true>(h)));
-    PLDA_TRY((der_solve_attr<true, SWEEP, true>(h)));
-  } else {
-    PLDA_TRY((der_solve_attr<false, SWEEP, false>(h)));
-    PLDA_TRY((der_solve_attr<true, SWEEP, false>(h)));
-  }
-  {
-    TraceScope ts(h, SWEEP ? "der.sweep_solve" : "der.solve");
-    for (const Launch &L : launches) {
-      for (int64_t c0 = 0; c0 < L.count; c0 += 1 << 20) {
-        const unsigned c = (unsigned)std::min<int64_t>(1 << 20, L.count - c0);
-        if (ovl && L.hbm)
-          der_solve_ovl_kernel<true><<<c, DER_T, (size_t)L.lds, h->stream>>>(dhyp, dtab + L.first + c0, scratch, dcounts, dmap, *td);
-        else if (ovl)
-          der_solve_ovl_kernel<false><<<c, DER_T, (size_t)L.lds, h->stream>>>(dhyp, dtab + L.first + c0, nullptr, dcounts, dmap, *td);
-        else if (td && L.hbm)
-          der_solve_timed_kernel<true, SWEEP><<<c, DER_T, (size_t)L.lds, h->stream>>>(dhyp, dma, dmb, dtab + L.first + c0, scratch, dcounts,
-                                                                                      dn_clusters, dmap, *td);
-        else if (td)
-          der_solve_timed_kernel<false, SWEEP><<<c, DER_T, (size_t)L.lds, h->stream>>>(dhyp, dma, dmb, dtab + L.first + c0, nullptr, dcounts,
-                                                                                       dn_clusters, dmap, *td);
-        else if (L.hbm)
-          der_solve_kernel<true, SWEEP><<<c, DER_T, (size_t)L.lds, h->stream>>>(dref, dhyp, ddur, dma, dmb, dtab + L.first + c0, scratch,
-                                                                                dcounts, dn_clusters, dmap);
-        else
-          der_solve_kernel<false, SWEEP><<<c, DER_T, (size_t)L.lds, h->stream>>>(dref, dhyp, ddur, dma, dmb, dtab + L.first + c0, nullptr,
-                                                                                 dcounts, dn_clusters, dmap);
-        PLDA_LAUNCH_CHECK(h);
-      }
+  PLDA_TRY(der_solve_attr(h));
+  TraceScope ts(h, jo ? (SWEEP ? "der.jer_sweep_solve" : "der.jer_solve") : (SWEEP ? "der.sweep_solve" : "der.solve"));
+  const DerTimedDev tdv = td ? *td : DerTimedDev{};
+  const DerJerOut jov = jo ? *jo : DerJerOut{};
+  for (const Launch &L : launches) {
+    const DerSolveFn fn = der_solve_fn(L.hbm, SWEEP, td != nullptr, ovl, jo != nullptr);
+    for (int64_t c0 = 0; c0 < L.count; c0 += 1 << 20) {
+      const unsigned c = (unsigned)std::min<int64_t>(1 << 20, L.count - c0);
+      fn<<<c, DER_T, (size_t)L.lds, h->stream>>>(dref, dhyp, ddur, dma, dmb, dtab + L.first + c0, L.hbm ? scratch : nullptr, dcounts,
+                                                 dn_clusters, dmap, tdv, jov);
+      PLDA_LAUNCH_CHECK(h);
     }
   }
   return PLDA_OK;
@@ -730,11 +670,12 @@ int der_solve_enqueue(plda_handle *h, std::vector<DerRec> &items, std::vector<De
 
 // the solves of a call, and the synchronisation behind them (also where the enqueue failed half-way: the table is in flight)
 template <bool SWEEP>
-int der_solve_all(plda_handle *h, std::vector<DerRec> &items, const int *dref, const int *dhyp, const int *ddur, const int *dma,
-                  const int *dmb, long long *dcounts, int *dn_clusters, int *dmap, const DerTimedDev *td = nullptr,
-                  const DerJerOut *jo = nullptr) {
+int der_solve_all(plda_handle *h, std::vector<DerRec> &items, const int *dref, const int *dhyp, const int *ddur,
+                  const int *dma, const int *dmb, int64_t *dcounts, int *dn_clusters, int *dmap, const DerTimedDev *td,
+                  const DerJerOut *jo) {
   std::vector<DerRec> tab;
-  const int rc = der_solve_enqueue<SWEEP>(h, items, tab, dref, dhyp, ddur, dma, dmb, dcounts, dn_clusters, dmap, td, jo);
+  const int rc = der_solve_enqueue<SWEEP>(h, items, tab, dref, dhyp, ddur, dma, dmb, reinterpret_cast<long long *>(dcounts), dn_clusters,
+                                   dmap, td, jo);
   const hipError_t e = hipStreamSynchronize(h->stream);
   if (rc != PLDA_OK) return rc;
   PLDA_HIP(h, e);
@@ -779,26 +720,101 @@ int der_plan(plda_handle *h, int64_t Sr, int64_t Sh, int32_t *out) { return der_
 // the JER form's boundary: its LDS holds rt and ht beside the column state (the sweeps keep ht in clab's place)
 int der_jer_plan(plda_handle *h, int64_t Sr, int64_t Sh, int32_t *out) { return der_plan_of(h, "der_jer_plan", true, Sr, Sh, out); }
 
-int der_device(plda_handle *h, const int32_t *dref, const int32_t *dhyp, const int32_t *ddur, const int64_t *offsets, int64_t R,
-               int64_t *dcounts, int32_t *dmap, const DerJerOut *jo) {
-  const char *fn = jo ? "der_jer" : "der";
-  if (!dref) return fail(h, PLDA_E_INVAL, "%s: ref is NULL", fn);
-  if (!dhyp) return fail(h, PLDA_E_INVAL, "%s: hyp is NULL", fn);
-  if (!dcounts) return fail(h, PLDA_E_INVAL, "%s: counts is NULL", fn);
-  if (jo && !jo->jer) return fail(h, PLDA_E_INVAL, "%s: jer is NULL", fn);
-  PLDA_TRY(der_check_offsets(h, fn, offsets, R));
+namespace {
+// one (recording, threshold) of a call: w, scr and the launch order are der_solve_enqueue's
+DerRec der_rec(const int64_t *offsets, int64_t r, int64_t out, int sr, int sh, int m) {
+  DerRec rc;
+  rc.off = offsets[r]; rc.scr = 0; rc.out = out; rc.n = (int)(offsets[r + 1] - offsets[r]);
+  rc.sr = sr; rc.sh = sh; rc.w = 0; rc.m = m; rc.r = (int)r;
+  return rc;
+}
+
+// what der_count_kernel refuses
+int der_bad_entries(plda_handle *h, const char *fn, unsigned long long bad, bool jer) {
+  return fail(h, PLDA_E_INVAL, "%s: %llu invalid entries (a label below -1 or above its limit, or a negative duration%s)", fn, bad,
+              jer ? "; a recording whose durations add up to more than 2^30" : "");
+}
+
+// The sweep of either form behind its argument check: the prefix pass (der_prefix_kernel; in the segment form, td NULL, behind
+// der_count_kernel), then the Q x R solves.  sr_of(r): the distinct reference labels of recording r in the time-based form;
+// the segment form reads them from its count.
+// stat: two counters | offsets [R + 1] | thresholds [Q] | sr [R] (segment form only) m [Q, R] minc [R]
+template <typename SrOf>
+int der_sweep_solve(plda_handle *h, const char *fn, const DerArgs &a, const DerTimedDev *td, SrOf sr_of) {
+  const int64_t R = a.R, Q = a.Q, nsr = td ? 0 : R;
+  const DerJerOut *jo = a.jer_form ? &a.jo : nullptr;
+  const size_t o_thr = 16 + 8 * (size_t)(R + 1), o_int = o_thr + 8 * (size_t)Q;
+  PLDA_HIP(h, h->der_stat.reserve(o_int + 4 * (size_t)(nsr + Q * R + R)));
+  char *ds = h->der_stat.as<char>();
+  unsigned long long *dstat = reinterpret_cast<unsigned long long *>(ds);
+  long long *doff = reinterpret_cast<long long *>(ds + 16);
+  double *dthr = reinterpret_cast<double *>(ds + o_thr);
+  int *dsr = reinterpret_cast<int *>(ds + o_int), *dm = dsr + nsr, *dminc = dm + Q * R;
+  PLDA_HIP(h, hipMemsetAsync(ds, 0, 16, h->stream));
+  PLDA_HIP(h, hipMemcpyAsync(doff, a.offsets, 8 * (size_t)(R + 1), hipMemcpyHostToDevice, h->stream));
+  PLDA_HIP(h, hipMemcpyAsync(dthr, a.thresholds, 8 * (size_t)Q, hipMemcpyHostToDevice, h->stream));
+  if (a.minc) PLDA_HIP(h, hipMemcpyAsync(dminc, a.minc, 4 * (size_t)R, hipMemcpyHostToDevice, h->stream));
+  {
+    TraceScope ts(h, "der.sweep_count");
+    if (!td) {
+      if (jo) der_count_kernel<true><<<(unsigned)R, DER_T, 0, h->stream>>>(a.ref, nullptr, a.dur, doff, dstat, dsr, nullptr);
+      else der_count_kernel<false><<<(unsigned)R, DER_T, 0, h->stream>>>(a.ref, nullptr, a.dur, doff, dstat, dsr, nullptr);
+      PLDA_LAUNCH_CHECK(h);
+    }
+    der_prefix_kernel<<<dim3((unsigned)R, (unsigned)Q), DER_T, 0, h->stream>>>(a.ma, a.mb, a.mc, doff, dthr, a.minc ? dminc : nullptr, (int)R,
+                                                                               dstat, dm);
+    PLDA_LAUNCH_CHECK(h);
+  }
+  unsigned long long bad[2] = {0, 0};
+  std::vector<int> s((size_t)(nsr + Q * R));      // sr (segment form only), then m
+  PLDA_HIP(h, hipMemcpyAsync(bad, ds, 16, hipMemcpyDeviceToHost, h->stream));
+  PLDA_HIP(h, hipMemcpyAsync(s.data(), dsr, 4 * s.size(), hipMemcpyDeviceToHost, h->stream));
+  PLDA_HIP(h, hipStreamSynchronize(h->stream));
+  if (bad[0]) return der_bad_entries(h, fn, bad[0], jo != nullptr);      // (the count alone adds to it)
+  if (bad[1])
+    return fail(h, PLDA_E_INVAL, "%s: %llu (recording, threshold) pairs whose merge record ends, or holds an entry that is no merge, "
+                                 "before the stop rule fires: not a full record", fn, bad[1]);
+  std::vector<DerRec> items((size_t)(Q * R));
+  for (int64_t q = 0; q < Q; ++q)
+    for (int64_t r = 0; r < R; ++r) {
+      DerRec &rc = items[(size_t)(q * R + r)];
+      rc = der_rec(a.offsets, r, q * R + r, td ? sr_of(r) : s[(size_t)r], 0, s[(size_t)(nsr + q * R + r)]);
+      rc.sh = rc.n - rc.m;
+    }
+  return der_solve_all<true>(h, items, a.ref, nullptr, a.dur, a.ma, a.mb, a.counts, a.n_clusters, nullptr, td, jo);
+}
+}  // namespace
+
+int der_seg_validate(plda_handle *h, const char *fn, const DerArgs &a, bool sweep) {
+  if (!a.ref) return fail(h, PLDA_E_INVAL, "%s: ref is NULL", fn);
+  if (!sweep && !a.hyp) return fail(h, PLDA_E_INVAL, "%s: hyp is NULL", fn);
+  if (!a.counts) return fail(h, PLDA_E_INVAL, "%s: counts is NULL", fn);
+  if (sweep && !a.n_clusters) return fail(h, PLDA_E_INVAL, "%s: n_clusters is NULL", fn);
+  if (a.jer_form && !a.jo.jer) return fail(h, PLDA_E_INVAL, "%s: jer is NULL", fn);
+  if (sweep) PLDA_TRY(der_sweep_validate(h, fn, a.offsets, a.R, a.thresholds, a.Q, a.minc));
+  else PLDA_TRY(der_validate(h, fn, a.offsets, a.R));
+  if (sweep && a.offsets[a.R] > a.R && !(a.ma && a.mb && a.mc)) return fail(h, PLDA_E_INVAL, "%s: merge_a, merge_b or merge_cost is NULL", fn);
+  return PLDA_OK;
+}
+
+int der_seg_device(plda_handle *h, const char *fn, const DerArgs &a, bool sweep) {
+  PLDA_TRY(der_seg_validate(h, fn, a, sweep));
+  if (sweep) return der_sweep_solve(h, fn, a, nullptr, [](int64_t) { return 0; });
+  const int64_t R = a.R;
+  const DerJerOut *jo = a.jer_form ? &a.jo : nullptr;
   // stat: two counters | offsets [R + 1] | sr [R] sh [R]
   const size_t ints = 16 + 8 * (size_t)(R + 1);
   PLDA_HIP(h, h->der_stat.reserve(ints + 8 * (size_t)R));
   char *ds = h->der_stat.as<char>();
+  unsigned long long *dstat = reinterpret_cast<unsigned long long *>(ds);
   long long *doff = reinterpret_cast<long long *>(ds + 16);
   int *dsr = reinterpret_cast<int *>(ds + ints), *dsh = dsr + R;
   PLDA_HIP(h, hipMemsetAsync(ds, 0, 16, h->stream));
-  PLDA_HIP(h, hipMemcpyAsync(doff, offsets, 8 * (size_t)(R + 1), hipMemcpyHostToDevice, h->stream));
+  PLDA_HIP(h, hipMemcpyAsync(doff, a.offsets, 8 * (size_t)(R + 1), hipMemcpyHostToDevice, h->stream));
   {
     TraceScope ts(h, "der.count");
-    if (jo) der_count_kernel<true><<<(unsigned)R, DER_T, 0, h->stream>>>(dref, dhyp, ddur, doff, reinterpret_cast<unsigned long long *>(ds), dsr, dsh);
-    else der_count_kernel<false><<<(unsigned)R, DER_T, 0, h->stream>>>(dref, dhyp, ddur, doff, reinterpret_cast<unsigned long long *>(ds), dsr, dsh);
+    if (jo) der_count_kernel<true><<<(unsigned)R, DER_T, 0, h->stream>>>(a.ref, a.hyp, a.dur, doff, dstat, dsr, dsh);
+    else der_count_kernel<false><<<(unsigned)R, DER_T, 0, h->stream>>>(a.ref, a.hyp, a.dur, doff, dstat, dsr, dsh);
     PLDA_LAUNCH_CHECK(h);
   }
   unsigned long long bad = 0;
@@ -806,124 +822,20 @@ int der_device(plda_handle *h, const int32_t *dref, const int32_t *dhyp, const i
   PLDA_HIP(h, hipMemcpyAsync(&bad, ds, 8, hipMemcpyDeviceToHost, h->stream));
   PLDA_HIP(h, hipMemcpyAsync(s.data(), dsr, 8 * (size_t)R, hipMemcpyDeviceToHost, h->stream));
   PLDA_HIP(h, hipStreamSynchronize(h->stream));
-  if (bad)
-    return fail(h, PLDA_E_INVAL, "%s: %llu invalid entries (a label below -1 or above its limit, or a negative duration%s)", fn, bad,
-                jo ? "; a recording whose durations add up to more than 2^30" : "");
+  if (bad) return der_bad_entries(h, fn, bad, jo != nullptr);
   std::vector<DerRec> items((size_t)R);
-  for (int64_t r = 0; r < R; ++r) {
-    DerRec &rc = items[(size_t)r];
-    rc.off = offsets[r]; rc.scr = 0; rc.out = r; rc.n = (int)(offsets[r + 1] - offsets[r]);
-    rc.sr = s[(size_t)r]; rc.sh = s[(size_t)(R + r)]; rc.w = 0; rc.m = 0; rc.r = (int)r;
-  }
-  return der_solve_all<false>(h, items, dref, dhyp, ddur, nullptr, nullptr, reinterpret_cast<long long *>(dcounts), nullptr, dmap, nullptr,
-                              jo);
+  for (int64_t r = 0; r < R; ++r) items[(size_t)r] = der_rec(a.offsets, r, r, s[(size_t)r], s[(size_t)(R + r)], 0);
+  return der_solve_all<false>(h, items, a.ref, a.hyp, a.dur, nullptr, nullptr, a.counts, nullptr, a.map, nullptr, jo);
 }
 
-int der_sweep_device(plda_handle *h, const int32_t *dma, const int32_t *dmb, const double *dmc, const int64_t *offsets, int64_t R,
-                     const int32_t *dref, const int32_t *ddur, const double *thresholds, int64_t Q, const int32_t *minc,
-                     int64_t *dcounts, int32_t *dn_clusters, const DerJerOut *jo) {
-  const char *fn = jo ? "der_jer_sweep" : "der_sweep";
-  if (!dref) return fail(h, PLDA_E_INVAL, "%s: ref is NULL", fn);
-  if (!dcounts) return fail(h, PLDA_E_INVAL, "%s: counts is NULL", fn);
-  if (!dn_clusters) return fail(h, PLDA_E_INVAL, "%s: n_clusters is NULL", fn);
-  if (jo && !jo->jer) return fail(h, PLDA_E_INVAL, "%s: jer is NULL", fn);
-  PLDA_TRY(der_sweep_validate(h, fn, offsets, R, thresholds, Q, minc));
-  const int64_t T = offsets[R];
-  if (T > R && !(dma && dmb && dmc)) return fail(h, PLDA_E_INVAL, "%s: merge_a, merge_b or merge_cost is NULL", fn);
-  // stat: two counters | offsets [R + 1] | thresholds [Q] | sr [R] m [Q, R] minc [R]
-  const size_t o_thr = 16 + 8 * (size_t)(R + 1), o_int = o_thr + 8 * (size_t)Q;
-  PLDA_HIP(h, h->der_stat.reserve(o_int + 4 * (size_t)(R + Q * R + R)));
-  char *ds = h->der_stat.as<char>();
-  long long *doff = reinterpret_cast<long long *>(ds + 16);
-  double *dthr = reinterpret_cast<double *>(ds + o_thr);
-  int *dsr = reinterpret_cast<int *>(ds + o_int), *dm = dsr + R, *dminc = dm + Q * R;
-  PLDA_HIP(h, hipMemsetAsync(ds, 0, 16, h->stream));
-  PLDA_HIP(h, hipMemcpyAsync(doff, offsets, 8 * (size_t)(R + 1), hipMemcpyHostToDevice, h->stream));
-  PLDA_HIP(h, hipMemcpyAsync(dthr, thresholds, 8 * (size_t)Q, hipMemcpyHostToDevice, h->stream));
-  if (minc) PLDA_HIP(h, hipMemcpyAsync(dminc, minc, 4 * (size_t)R, hipMemcpyHostToDevice, h->stream));
-  {
-    TraceScope ts(h, "der.sweep_count");
-    unsigned long long *dstat = reinterpret_cast<unsigned long long *>(ds);
-    if (jo) der_count_kernel<true><<<(unsigned)R, DER_T, 0, h->stream>>>(dref, nullptr, ddur, doff, dstat, dsr, nullptr);
-    else der_count_kernel<false><<<(unsigned)R, DER_T, 0, h->stream>>>(dref, nullptr, ddur, doff, dstat, dsr, nullptr);
-    PLDA_LAUNCH_CHECK(h);
-    der_prefix_kernel<<<dim3((unsigned)R, (unsigned)Q), DER_T, 0, h->stream>>>(dma, dmb, dmc, doff, dthr, minc ? dminc : nullptr, (int)R,
-                                                                               dstat, dm);
-    PLDA_LAUNCH_CHECK(h);
-  }
-  unsigned long long bad[2] = {0, 0};
-  std::vector<int> s((size_t)(R + Q * R));
-  PLDA_HIP(h, hipMemcpyAsync(bad, ds, 16, hipMemcpyDeviceToHost, h->stream));
-  PLDA_HIP(h, hipMemcpyAsync(s.data(), dsr, 4 * s.size(), hipMemcpyDeviceToHost, h->stream));
-  PLDA_HIP(h, hipStreamSynchronize(h->stream));
-  if (bad[0])
-    return fail(h, PLDA_E_INVAL, "%s: %llu invalid entries (a label below -1 or above its limit, or a negative duration%s)", fn, bad[0],
-                jo ? "; a recording whose durations add up to more than 2^30" : "");
-  if (bad[1])
-    return fail(h, PLDA_E_INVAL, "%s: %llu (recording, threshold) pairs whose merge record ends, or holds an entry that is no merge, "
-                                 "before the stop rule fires: not a full record", fn, bad[1]);
-  std::vector<DerRec> items((size_t)(Q * R));
-  for (int64_t q = 0; q < Q; ++q)
-    for (int64_t r = 0; r < R; ++r) {
-      DerRec &rc = items[(size_t)(q * R + r)];
-      rc.off = offsets[r]; rc.scr = 0; rc.out = q * R + r; rc.n = (int)(offsets[r + 1] - offsets[r]);
-      rc.sr = s[(size_t)r]; rc.m = s[(size_t)(R + q * R + r)]; rc.sh = rc.n - rc.m; rc.w = 0; rc.r = (int)r;
-    }
-  return der_solve_all<true>(h, items, dref, nullptr, ddur, dma, dmb, reinterpret_cast<long long *>(dcounts), dn_clusters, nullptr, nullptr,
-                             jo);
-}
-
-// The solves of a time-based call (der_time.hip has validated the call and cut the atoms; recs is the host copy of td.recs).
-// Q = 0: one solve per recording against dhyp (recs[r].sh = its distinct hypothesis labels).  Q >= 1: the sweep.
-int der_timed_solve(plda_handle *h, const char *fn, const DerTimedRec *recs, const DerTimedDev &td, const int32_t *dhyp,
-                    const int32_t *dma, const int32_t *dmb, const double *dmc, const int64_t *offsets, int64_t R, const double *thresholds,
-                    int64_t Q, const int32_t *minc, int64_t *dcounts, int32_t *dn_clusters, int32_t *dmap, const DerJerOut *jo) {
-  auto item = [&](int64_t r, int64_t out) {
-    DerRec rc;
-    rc.off = offsets[r]; rc.scr = 0; rc.out = out; rc.n = (int)(offsets[r + 1] - offsets[r]);
-    rc.sr = __builtin_popcountll(recs[r].umask); rc.sh = 0; rc.w = 0; rc.m = 0; rc.r = (int)r;
-    return rc;
-  };
-  if (Q == 0) {
-    std::vector<DerRec> items((size_t)R);
-    for (int64_t r = 0; r < R; ++r) { items[(size_t)r] = item(r, r); items[(size_t)r].sh = recs[r].sh; }
-    return der_solve_all<false>(h, items, nullptr, dhyp, nullptr, nullptr, nullptr, reinterpret_cast<long long *>(dcounts), nullptr, dmap, &td,
-                                jo);
-  }
-  // stat: two counters | offsets [R + 1] | thresholds [Q] | m [Q, R] minc [R]
-  const size_t o_thr = 16 + 8 * (size_t)(R + 1), o_int = o_thr + 8 * (size_t)Q;
-  PLDA_HIP(h, h->der_stat.reserve(o_int + 4 * (size_t)(Q * R + R)));
-  char *ds = h->der_stat.as<char>();
-  long long *doff = reinterpret_cast<long long *>(ds + 16);
-  double *dthr = reinterpret_cast<double *>(ds + o_thr);
-  int *dm = reinterpret_cast<int *>(ds + o_int), *dminc = dm + Q * R;
-  PLDA_HIP(h, hipMemsetAsync(ds, 0, 16, h->stream));
-  PLDA_HIP(h, hipMemcpyAsync(doff, offsets, 8 * (size_t)(R + 1), hipMemcpyHostToDevice, h->stream));
-  PLDA_HIP(h, hipMemcpyAsync(dthr, thresholds, 8 * (size_t)Q, hipMemcpyHostToDevice, h->stream));
-  if (minc) PLDA_HIP(h, hipMemcpyAsync(dminc, minc, 4 * (size_t)R, hipMemcpyHostToDevice, h->stream));
-  {
-    TraceScope ts(h, "der.sweep_count");
-    der_prefix_kernel<<<dim3((unsigned)R, (unsigned)Q), DER_T, 0, h->stream>>>(dma, dmb, dmc, doff, dthr, minc ? dminc : nullptr, (int)R,
-                                                                               reinterpret_cast<unsigned long long *>(ds), dm);
-    PLDA_LAUNCH_CHECK(h);
-  }
-  unsigned long long bad[2] = {0, 0};
-  std::vector<int> m((size_t)(Q * R));
-  PLDA_HIP(h, hipMemcpyAsync(bad, ds, 16, hipMemcpyDeviceToHost, h->stream));
-  PLDA_HIP(h, hipMemcpyAsync(m.data(), dm, 4 * m.size(), hipMemcpyDeviceToHost, h->stream));
-  PLDA_HIP(h, hipStreamSynchronize(h->stream));
-  if (bad[1])
-    return fail(h, PLDA_E_INVAL, "%s: %llu (recording, threshold) pairs whose merge record ends, or holds an entry that is no merge, "
-                                 "before the stop rule fires: not a full record", fn, bad[1]);
-  std::vector<DerRec> items((size_t)(Q * R));
-  for (int64_t q = 0; q < Q; ++q)
-    for (int64_t r = 0; r < R; ++r) {
-      DerRec &rc = items[(size_t)(q * R + r)];
-      rc = item(r, q * R + r);
-      rc.m = m[(size_t)(q * R + r)]; rc.sh = rc.n - rc.m;
-    }
-  return der_solve_all<true>(h, items, nullptr, nullptr, nullptr, dma, dmb, reinterpret_cast<long long *>(dcounts), dn_clusters, nullptr, &td,
-                               jo);
+// The solves of a time-based call (der_time.hip has validated the call and cut the atoms; recs is the host copy of td.recs):
+// one solve per recording against a.hyp (recs[r].sh = its distinct hypothesis labels), or the sweep.
+int der_timed_solve(plda_handle *h, const char *fn, const DerTimedRec *recs, const DerTimedDev &td, const DerArgs &a, bool sweep) {
+  auto sr_of = [recs](int64_t r) { return __builtin_popcountll(recs[r].umask); };
+  if (sweep) return der_sweep_solve(h, fn, a, &td, sr_of);
+  std::vector<DerRec> items((size_t)a.R);
+  for (int64_t r = 0; r < a.R; ++r) items[(size_t)r] = der_rec(a.offsets, r, r, sr_of(r), recs[r].sh, 0);
+  return der_solve_all<false>(h, items, nullptr, a.hyp, nullptr, nullptr, nullptr, a.counts, nullptr, a.map, &td, a.jer_form ? &a.jo : nullptr);
 }
 
 }  // namespace plda

@@ -2,7 +2,7 @@
 // scoring regions (the contract is in include/plda_hip.h, "time-based diarisation error rate"; the host models
 // are tests/der_time_model.py).  This file cuts every recording's time line into ATOMS -- maximal runs of ticks over which
 // the set of reference speakers, the hypothesis segment, the collar depth and the UEM depth do not change -- and keeps the
-// scored ones; der.hip's solve then reads atoms where the segment form reads segments (der_solve_timed_kernel: the same
+// scored ones; der.hip's solve then reads atoms where the segment form reads segments (der_solve_kernel<.., ATOMS = true>: the same
 // assignment, the matrix filled from atoms).  Everything is an integer; the atoms are a function of the recording alone.
 //
 //   der_atoms_kernel<HBM>   one workgroup of 256 threads per recording.
@@ -97,8 +97,8 @@ __device__ __forceinline__ void dt_bitonic_tile(unsigned long long *buf, int bas
 }
 
 // Resources on gfx950 (kernel-resource-usage): <false> 47 VGPRs, <true> 55 VGPRs; no scratch memory, no spills in either.
-// (der_solve_timed_kernel, der.hip: 44 VGPRs in the LDS class, 40 in the scratch class, as the segment form; no scratch, no spills.
-// der_solve_ovl_kernel, the two-label form of K21: the same 44 and 40.  hyp2, K21, left this kernel's 47 and 55 as they were.)
+// (der_solve_kernel on atoms, der.hip: 44 VGPRs in the LDS class, 40 in the scratch class, as the segment form; no scratch, no spills.
+// Its two-label form of K21: the same 44 and 40.  hyp2, K21, left this kernel's 47 and 55 as they were.)
 template <bool HBM>
 __global__ __launch_bounds__(DT_T) void der_atoms_kernel(const int *__restrict__ tstart, const int *__restrict__ tdur,
                                                          const int *__restrict__ tspk, const int *__restrict__ sstart,
@@ -312,7 +312,7 @@ int der_timed_plan(plda_handle *h, int64_t n_turns, int64_t n_seg, int64_t n_uem
   return PLDA_OK;
 }
 
-int der_timed_validate(plda_handle *h, const char *fn, const DerTimedArgs &a, bool sweep) {
+int der_timed_validate(plda_handle *h, const char *fn, const DerArgs &a, bool sweep) {
   if (!a.turn_off) return fail(h, PLDA_E_INVAL, "%s: turn_off is NULL", fn);
   if (!a.sstart) return fail(h, PLDA_E_INVAL, "%s: seg_start is NULL", fn);
   if (!a.sdur) return fail(h, PLDA_E_INVAL, "%s: seg_dur is NULL", fn);
@@ -336,7 +336,7 @@ int der_timed_validate(plda_handle *h, const char *fn, const DerTimedArgs &a, bo
   return PLDA_OK;
 }
 
-int der_timed_device(plda_handle *h, const char *fn, const DerTimedArgs &a, bool sweep) {
+int der_timed_device(plda_handle *h, const char *fn, const DerArgs &a, bool sweep) {
   PLDA_TRY(der_timed_validate(h, fn, a, sweep));
   const int64_t R = a.R;
   // the launch table: the LDS class by ascending P (one launch per P), then the scratch class in launches under the budget
@@ -417,8 +417,7 @@ int der_timed_device(plda_handle *h, const char *fn, const DerTimedArgs &a, bool
                                  "inside another turn of its speaker, or two hypothesis segments that share a tick)", fn, bad[0],
                 a.hyp2 ? ", a second label without a first or equal to it" : "", bad[1]);
   const DerTimedDev td{drecs, dticks, dseg, dmask, sweep ? nullptr : a.hyp2};     // (hyp2 given: the solve's two-label form)
-  return der_timed_solve(h, fn, recs.data(), td, a.hyp, a.ma, a.mb, a.mc, a.offsets, R, a.thresholds, sweep ? a.Q : 0, a.minc, a.counts,
-                         a.n_clusters, a.map, a.jer_form ? &a.jo : nullptr);
+  return der_timed_solve(h, fn, recs.data(), td, a, sweep);
 }
 
 }  // namespace plda

@@ -176,6 +176,11 @@ def _jer_out(r, q=None):
     return np.empty((r, 2), np.int64), np.empty((r, MAX_REF), np.int32), np.empty((r, MAX_REF, 3), np.int64)
 
 
+def _call(engine, name, args):
+    """The one library call of a DER function: entry point `name` on args, arrays (None: NULL) as pointers."""
+    N.check(engine._h, getattr(engine._lib, name)(engine._h, *[a if isinstance(a, int) else _p(a) for a in args]))
+
+
 def plan(engine, sr, sh):
     """{"cls": 0 (matrix in LDS) or 1 (in handle scratch), "scratch_bytes": per recording, "lds_max": the widest matrix,
     max(sr, sh), of the LDS class at this sr}."""
@@ -273,12 +278,9 @@ def der(engine, ref, hyp, offsets, dur=None, return_map=False, jer=False):
     map_ = np.empty((r, MAX_REF), np.int32) if return_map else None
     if jer:
         _jer_ticks(dur, offsets)
-        jc, jm, sp = _jer_out(r)
-        N.check(engine._h, engine._lib.plda_der_jer(engine._h, _p(ref), _p(hyp), _p(dur), _p(offsets), r, _p(counts), _p(map_), _p(jc),
-                                                    _p(jm), _p(sp)))
-        return DerResult(counts, map_, jc, jm, sp)
-    N.check(engine._h, engine._lib.plda_der(engine._h, _p(ref), _p(hyp), _p(dur), _p(offsets), r, _p(counts), _p(map_)))
-    return DerResult(counts, map_)
+    jout = _jer_out(r) if jer else ()
+    _call(engine, "plda_der_jer" if jer else "plda_der", [ref, hyp, dur, offsets, r, counts, map_] + list(jout))
+    return DerResult(counts, map_, *jout)
 
 
 def sweep(engine, merges, offsets, ref, thresholds, dur=None, num_speakers=None, jer=False):
@@ -290,13 +292,10 @@ def sweep(engine, merges, offsets, ref, thresholds, dur=None, num_speakers=None,
     counts, ncl = np.empty((q, r, 4), np.int64), np.empty((q, r), np.int32)
     if jer:
         _jer_ticks(dur, offsets)
-        jc = _jer_out(r, q)[0]
-        N.check(engine._h, engine._lib.plda_der_jer_sweep(engine._h, _p(ma), _p(mb), _p(mc), _p(offsets), r, _p(ref), _p(dur),
-                                                          _p(thresholds), q, _p(minc), _p(counts), _p(ncl), _p(jc)))
-        return SweepResult(thresholds, counts, ncl, jc)
-    N.check(engine._h, engine._lib.plda_der_sweep(engine._h, _p(ma), _p(mb), _p(mc), _p(offsets), r, _p(ref), _p(dur), _p(thresholds),
-                                                  q, _p(minc), _p(counts), _p(ncl)))
-    return SweepResult(thresholds, counts, ncl)
+    jout = _jer_out(r, q)[:1] if jer else ()
+    _call(engine, "plda_der_jer_sweep" if jer else "plda_der_sweep",
+          [ma, mb, mc, offsets, r, ref, dur, thresholds, q, minc, counts, ncl] + list(jout))
+    return SweepResult(thresholds, counts, ncl, *jout)
 
 
 # ------------------------------------------------------------------------------------------- the time-based form
@@ -389,21 +388,12 @@ def der_timed(engine, turns, seg_start, seg_dur, hyp, offsets, collar=0, uem=Non
     r = len(offsets) - 1
     counts = np.empty((r, 4), np.int64)
     map_ = np.empty((r, MAX_REF), np.int32) if return_map else None
-    if jer:
-        jc, jm, sp = _jer_out(r)
-        hyp2 = targs[12] if hyp2 is not None else None
-        N.check(engine._h, engine._lib.plda_der_timed_jer(engine._h, _p(ts), _p(td), _p(tk), _p(toff), _p(ss), _p(sd), _p(hyp), _p(hyp2),
-                                                          _p(offsets), r, _p(us), _p(ud), _p(uoff), collar, flags, _p(counts), _p(map_),
-                                                          _p(jc), _p(jm), _p(sp)))
-        return DerResult(counts, map_, jc, jm, sp)
-    if hyp2 is not None:
-        hyp2 = targs[12]
-        N.check(engine._h, engine._lib.plda_der_timed_ovl(engine._h, _p(ts), _p(td), _p(tk), _p(toff), _p(ss), _p(sd), _p(hyp), _p(hyp2),
-                                                          _p(offsets), r, _p(us), _p(ud), _p(uoff), collar, flags, _p(counts), _p(map_)))
-        return DerResult(counts, map_)
-    N.check(engine._h, engine._lib.plda_der_timed(engine._h, _p(ts), _p(td), _p(tk), _p(toff), _p(ss), _p(sd), _p(hyp), _p(offsets), r,
-                                                  _p(us), _p(ud), _p(uoff), collar, flags, _p(counts), _p(map_)))
-    return DerResult(counts, map_)
+    jout = _jer_out(r) if jer else ()
+    # the two-label entry points take hyp2 behind hyp; the JER one also where there is none (NULL), plda_der_timed has no such argument
+    second = [targs[12] if hyp2 is not None else None] if jer or hyp2 is not None else []
+    _call(engine, "plda_der_timed_jer" if jer else "plda_der_timed_ovl" if hyp2 is not None else "plda_der_timed",
+          [ts, td, tk, toff, ss, sd, hyp] + second + [offsets, r, us, ud, uoff, collar, flags, counts, map_] + list(jout))
+    return DerResult(counts, map_, *jout)
 
 
 def sweep_timed_args(merges, turns, seg_start, seg_dur, offsets, thresholds, num_speakers, collar, uem, skip_overlap):
@@ -422,13 +412,7 @@ def sweep_timed(engine, merges, turns, seg_start, seg_dur, offsets, thresholds, 
         merges, turns, seg_start, seg_dur, offsets, thresholds, num_speakers, collar, uem, skip_overlap)
     r, q = len(offsets) - 1, len(thresholds)
     counts, ncl = np.empty((q, r, 4), np.int64), np.empty((q, r), np.int32)
-    if jer:
-        jc = _jer_out(r, q)[0]
-        N.check(engine._h, engine._lib.plda_der_timed_jer_sweep(engine._h, _p(ma), _p(mb), _p(mc), _p(ts), _p(td), _p(tk), _p(toff), _p(ss),
-                                                                _p(sd), _p(offsets), r, _p(us), _p(ud), _p(uoff), collar, flags,
-                                                                _p(thresholds), q, _p(minc), _p(counts), _p(ncl), _p(jc)))
-        return SweepResult(thresholds, counts, ncl, jc)
-    N.check(engine._h, engine._lib.plda_der_timed_sweep(engine._h, _p(ma), _p(mb), _p(mc), _p(ts), _p(td), _p(tk), _p(toff), _p(ss), _p(sd),
-                                                        _p(offsets), r, _p(us), _p(ud), _p(uoff), collar, flags, _p(thresholds), q, _p(minc),
-                                                        _p(counts), _p(ncl)))
-    return SweepResult(thresholds, counts, ncl)
+    jout = _jer_out(r, q)[:1] if jer else ()
+    _call(engine, "plda_der_timed_jer_sweep" if jer else "plda_der_timed_sweep",
+          [ma, mb, mc, ts, td, tk, toff, ss, sd, offsets, r, us, ud, uoff, collar, flags, thresholds, q, minc, counts, ncl] + list(jout))
+    return SweepResult(thresholds, counts, ncl, *jout)

@@ -25,6 +25,11 @@ def _ptr(a):
     return C.c_void_p(a.ctypes.data) if a is not None else None
 
 
+def _vp(x):
+    """A raw device address as a void pointer; None (or 0): NULL."""
+    return C.c_void_p(int(x)) if x else None
+
+
 def _features(x, what="Input features"):
     if not isinstance(x, np.ndarray):
         raise TypeError("argument 1 must be numpy.ndarray, not %s" % type(x).__name__)  # "O!" parse
@@ -619,64 +624,52 @@ class MPlda(object):
                 max_iters=40, epsilon=1e-4, dgamma=None, gamma_off=None, dpi=None, pi_off=None, delbo=None, diters=None):
         """VBx on HBM-resident projected rows and labels (raw device addresses); offsets, gamma_off and pi_off (int64) are HOST
         arrays."""
-        def vp(x):
-            return C.c_void_p(int(x)) if x else None
         self._ck(self._lib.plda_vbx_dev(
-            self._h, vp(dY), int(D), vp(dPhi), vp(dlabels_in), _ptr(offsets), len(offsets) - 1, float(Fa), float(Fb), float(loop_prob),
-            float(init_smoothing), int(max_iters), float(epsilon), vp(dlabels), vp(dn_clusters), vp(dgamma),
-            _ptr(gamma_off) if gamma_off is not None else None, vp(dpi), _ptr(pi_off) if pi_off is not None else None, vp(delbo),
-            vp(diters)))
+            self._h, _vp(dY), int(D), _vp(dPhi), _vp(dlabels_in), _ptr(offsets), len(offsets) - 1, float(Fa), float(Fb), float(loop_prob),
+            float(init_smoothing), int(max_iters), float(epsilon), _vp(dlabels), _vp(dn_clusters), _vp(dgamma),
+            _ptr(gamma_off) if gamma_off is not None else None, _vp(dpi), _ptr(pi_off) if pi_off is not None else None, _vp(delbo),
+            _vp(diters)))
 
     def vbx_top2_dev(self, dY, D, dPhi, dlabels_in, offsets, dlabels, dn_clusters, dlabels2=None, dpost2=None, Fa=0.3, Fb=17.0,
                      loop_prob=0.99, init_smoothing=5.0, max_iters=40, epsilon=1e-4, dgamma=None, gamma_off=None, dpi=None, pi_off=None,
                      delbo=None, diters=None):
         """vbx_dev with the second speaker: dlabels2 int32 [T] and dpost2 float64 [T] (raw device addresses, each may be None)."""
-        def vp(x):
-            return C.c_void_p(int(x)) if x else None
         self._ck(self._lib.plda_vbx_top2_dev(
-            self._h, vp(dY), int(D), vp(dPhi), vp(dlabels_in), _ptr(offsets), len(offsets) - 1, float(Fa), float(Fb), float(loop_prob),
-            float(init_smoothing), int(max_iters), float(epsilon), vp(dlabels), vp(dn_clusters), vp(dgamma),
-            _ptr(gamma_off) if gamma_off is not None else None, vp(dpi), _ptr(pi_off) if pi_off is not None else None, vp(delbo),
-            vp(diters), vp(dlabels2), vp(dpost2)))
+            self._h, _vp(dY), int(D), _vp(dPhi), _vp(dlabels_in), _ptr(offsets), len(offsets) - 1, float(Fa), float(Fb), float(loop_prob),
+            float(init_smoothing), int(max_iters), float(epsilon), _vp(dlabels), _vp(dn_clusters), _vp(dgamma),
+            _ptr(gamma_off) if gamma_off is not None else None, _vp(dpi), _ptr(pi_off) if pi_off is not None else None, _vp(delbo),
+            _vp(diters), _vp(dlabels2), _vp(dpost2)))
 
     def ahc_matrix_dev(self, dscores, block_off, offsets, has_threshold, threshold, min_clusters, dlabels, dn_clusters,
                        dmerge_a=None, dmerge_b=None, dmerge_cost=None):
         """Cluster packed HBM-resident fp32 score blocks (raw device addresses); block_off, offsets (int64) and min_clusters
         (int32 or None) are HOST arrays."""
-        def vp(x):
-            return C.c_void_p(int(x)) if x else None
         self._ck(self._lib.plda_ahc_matrix_dev(
-            self._h, vp(dscores), _ptr(block_off), _ptr(offsets), len(offsets) - 1, int(has_threshold), float(threshold),
-            _ptr(min_clusters) if min_clusters is not None else None, vp(dlabels), vp(dn_clusters), vp(dmerge_a), vp(dmerge_b),
-            vp(dmerge_cost)))
+            self._h, _vp(dscores), _ptr(block_off), _ptr(offsets), len(offsets) - 1, int(has_threshold), float(threshold),
+            _ptr(min_clusters) if min_clusters is not None else None, _vp(dlabels), _vp(dn_clusters), _vp(dmerge_a), _vp(dmerge_b),
+            _vp(dmerge_cost)))
 
     def score_ahc_dev(self, dX, offsets, has_threshold, threshold, min_clusters, dlabels, dn_clusters, dmerge_a=None,
                       dmerge_b=None, dmerge_cost=None):
         """The same on HBM-resident transformed segment vectors dX [T, Dout]: the blocks are scored and dropped."""
-        def vp(x):
-            return C.c_void_p(int(x)) if x else None
         self._ck(self._lib.plda_score_ahc_dev(
-            self._h, vp(dX), _ptr(offsets), len(offsets) - 1, int(has_threshold), float(threshold),
-            _ptr(min_clusters) if min_clusters is not None else None, vp(dlabels), vp(dn_clusters), vp(dmerge_a), vp(dmerge_b),
-            vp(dmerge_cost)))
+            self._h, _vp(dX), _ptr(offsets), len(offsets) - 1, int(has_threshold), float(threshold),
+            _ptr(min_clusters) if min_clusters is not None else None, _vp(dlabels), _vp(dn_clusters), _vp(dmerge_a), _vp(dmerge_b),
+            _vp(dmerge_cost)))
 
     def score_dense_pca_dev(self, dX, offsets, target_energy, dscores, block_off, ddims=None, deig=None):
         """plda_score_dense_pca_dev on HBM-resident rows dX [T, Din] (raw device addresses): block r row-major at dscores +
         block_off[r] floats; offsets and block_off (int64) are HOST arrays; ddims int32 [R] and deig float64 [T] may be None."""
-        def vp(x):
-            return C.c_void_p(int(x)) if x else None
-        self._ck(self._lib.plda_score_dense_pca_dev(self._h, vp(dX), _ptr(offsets), len(offsets) - 1, float(target_energy),
-                                                    vp(dscores), _ptr(block_off), vp(ddims), vp(deig)))
+        self._ck(self._lib.plda_score_dense_pca_dev(self._h, _vp(dX), _ptr(offsets), len(offsets) - 1, float(target_energy),
+                                                    _vp(dscores), _ptr(block_off), _vp(ddims), _vp(deig)))
 
     def score_dense_pca_ahc_dev(self, dX, offsets, target_energy, has_threshold, threshold, min_clusters, dlabels, dn_clusters,
                                 dmerge_a=None, dmerge_b=None, dmerge_cost=None):
         """The same blocks clustered and dropped (plda_score_dense_pca_ahc_dev); the outputs as score_ahc_dev's."""
-        def vp(x):
-            return C.c_void_p(int(x)) if x else None
         self._ck(self._lib.plda_score_dense_pca_ahc_dev(
-            self._h, vp(dX), _ptr(offsets), len(offsets) - 1, float(target_energy), int(has_threshold), float(threshold),
-            _ptr(min_clusters) if min_clusters is not None else None, vp(dlabels), vp(dn_clusters), vp(dmerge_a), vp(dmerge_b),
-            vp(dmerge_cost)))
+            self._h, _vp(dX), _ptr(offsets), len(offsets) - 1, float(target_energy), int(has_threshold), float(threshold),
+            _ptr(min_clusters) if min_clusters is not None else None, _vp(dlabels), _vp(dn_clusters), _vp(dmerge_a), _vp(dmerge_b),
+            _vp(dmerge_cost)))
 
     # ----------------------------------------------------------------- diarisation error rate (csrc/der.hip)
     def der(self,ref, hyp, offsets, dur=None, return_map=False, jer=False):
@@ -709,24 +702,20 @@ class MPlda(object):
             if ref is not None or dur is not None:
                 raise ValueError("with turns, ref and dur must be None (the reference is the turns)")
             der.sweep_timed_args(empty, turns, seg_start, seg_dur, offsets, thresholds, None, collar, uem, skip_overlap)
-            from . import diarize
-            diarize.stop_args(offsets, None, 1)
-            if target_energy is not None:
-                _, _, merges = diarize.ahc_dense_pca(self, X, offsets, target_energy, None, 1, True)
-            else:
-                _, _, merges = diarize.ahc_vectors(self, self.transform_array(X, 1), offsets, None, 1, True)
-            res = der.sweep_timed(self, merges, turns, seg_start, seg_dur, offsets, thresholds, None, collar, uem, skip_overlap, jer)
-            return float(res.thresholds[res.best_jer if jer else res.best]), res
-        sargs = der.sweep_args(empty, offsets, ref, thresholds, dur, None)        # (before any device work)
-        if jer:
-            der._jer_ticks(sargs[6], sargs[3])
+        else:
+            sargs = der.sweep_args(empty, offsets, ref, thresholds, dur, None)        # (before any device work)
+            if jer:
+                der._jer_ticks(sargs[6], sargs[3])
         from . import diarize
         diarize.stop_args(offsets, None, 1)
         if target_energy is not None:
             _, _, merges = diarize.ahc_dense_pca(self, X, offsets, target_energy, None, 1, True)
         else:
             _, _, merges = diarize.ahc_vectors(self, self.transform_array(X, 1), offsets, None, 1, True)   # cluster() on embedded rows
-        res = der.sweep(self, merges, offsets, ref, thresholds, dur, None, jer)
+        if turns is not None:
+            res = der.sweep_timed(self, merges, turns, seg_start, seg_dur, offsets, thresholds, None, collar, uem, skip_overlap, jer)
+        else:
+            res = der.sweep(self, merges, offsets, ref, thresholds, dur, None, jer)
         return float(res.thresholds[res.best_jer if jer else res.best]), res
 
     def der_timed(self, turns, seg_start, seg_dur, hyp, offsets, collar=0, uem=None, skip_overlap=False, return_map=False, hyp2=None,
@@ -738,100 +727,87 @@ class MPlda(object):
         from . import der
         return der.der_timed(self, turns, seg_start, seg_dur, hyp, offsets, collar, uem, skip_overlap, return_map, hyp2, jer)
 
+    # the four call shapes of the DER *_dev methods; jer: the outputs the JER entry point of that shape takes behind the rest
+    def _der_seg_dev(self, name, dref, dhyp, ddur, offsets, dcounts, dmap, *jer):
+        self._ck(getattr(self._lib, name)(self._h, _vp(dref), _vp(dhyp), _vp(ddur), _ptr(offsets), len(offsets) - 1, _vp(dcounts), _vp(dmap),
+                                          *map(_vp, jer)))
+
+    def _der_seg_sweep_dev(self, name, dmerges, offsets, dref, ddur, thresholds, min_clusters, dcounts, dn_clusters, *jer):
+        self._ck(getattr(self._lib, name)(
+            self._h, _vp(dmerges[0]), _vp(dmerges[1]), _vp(dmerges[2]), _ptr(offsets), len(offsets) - 1, _vp(dref), _vp(ddur),
+            _ptr(thresholds), len(thresholds), _ptr(min_clusters), _vp(dcounts), _vp(dn_clusters), *map(_vp, jer)))
+
+    def _der_timed_dev(self, name, dturns, turn_off, dseg_start, dseg_dur, dhyps, offsets, duem, uem_off, collar, flags, dcounts, dmap, *jer):
+        du = duem if duem is not None else (None, None)      # dhyps: (dhyp,), or (dhyp, dhyp2) where the entry point takes two labels
+        self._ck(getattr(self._lib, name)(
+            self._h, _vp(dturns[0]), _vp(dturns[1]), _vp(dturns[2]), _ptr(turn_off), _vp(dseg_start), _vp(dseg_dur), *map(_vp, dhyps),
+            _ptr(offsets), len(offsets) - 1, _vp(du[0]), _vp(du[1]), _ptr(uem_off), int(collar), int(flags), _vp(dcounts), _vp(dmap),
+            *map(_vp, jer)))
+
+    def _der_timed_sweep_dev(self, name, dmerges, dturns, turn_off, dseg_start, dseg_dur, offsets, duem, uem_off, collar, flags, thresholds,
+                             min_clusters, dcounts, dn_clusters, *jer):
+        du = duem if duem is not None else (None, None)
+        self._ck(getattr(self._lib, name)(
+            self._h, _vp(dmerges[0]), _vp(dmerges[1]), _vp(dmerges[2]), _vp(dturns[0]), _vp(dturns[1]), _vp(dturns[2]), _ptr(turn_off),
+            _vp(dseg_start), _vp(dseg_dur), _ptr(offsets), len(offsets) - 1, _vp(du[0]), _vp(du[1]), _ptr(uem_off), int(collar), int(flags),
+            _ptr(thresholds), len(thresholds), _ptr(min_clusters), _vp(dcounts), _vp(dn_clusters), *map(_vp, jer)))
+
     def der_timed_jer_dev(self, dturns, turn_off, dseg_start, dseg_dur, dhyp, dhyp2, offsets, dcounts, djer, dmap=None, djmap=None,
                           dspk=None, duem=None, uem_off=None, collar=0, flags=0):
         """plda_der_timed_jer_dev: der_timed_ovl_dev (dhyp2 may be None), then djer int64 [R, 2], djmap int32 [R, 64] or None,
         dspk int64 [R, 64, 3] or None."""
-        def vp(x):
-            return C.c_void_p(int(x)) if x else None
-        du = duem if duem is not None else (None, None)
-        self._ck(self._lib.plda_der_timed_jer_dev(
-            self._h, vp(dturns[0]), vp(dturns[1]), vp(dturns[2]), _ptr(turn_off), vp(dseg_start), vp(dseg_dur), vp(dhyp), vp(dhyp2),
-            _ptr(offsets), len(offsets) - 1, vp(du[0]), vp(du[1]), _ptr(uem_off) if uem_off is not None else None, int(collar),
-            int(flags), vp(dcounts), vp(dmap), vp(djer), vp(djmap), vp(dspk)))
+        self._der_timed_dev("plda_der_timed_jer_dev", dturns, turn_off, dseg_start, dseg_dur, (dhyp, dhyp2), offsets, duem, uem_off, collar,
+                            flags, dcounts, dmap, djer, djmap, dspk)
 
     def der_timed_jer_sweep_dev(self, dmerges, dturns, turn_off, dseg_start, dseg_dur, offsets, thresholds, min_clusters, dcounts,
                                 dn_clusters, djer, duem=None, uem_off=None, collar=0, flags=0):
         """plda_der_timed_jer_sweep_dev: der_timed_sweep_dev, then djer int64 [Q, R, 2]."""
-        def vp(x):
-            return C.c_void_p(int(x)) if x else None
-        du = duem if duem is not None else (None, None)
-        self._ck(self._lib.plda_der_timed_jer_sweep_dev(
-            self._h, vp(dmerges[0]), vp(dmerges[1]), vp(dmerges[2]), vp(dturns[0]), vp(dturns[1]), vp(dturns[2]), _ptr(turn_off),
-            vp(dseg_start), vp(dseg_dur), _ptr(offsets), len(offsets) - 1, vp(du[0]), vp(du[1]),
-            _ptr(uem_off) if uem_off is not None else None, int(collar), int(flags), _ptr(thresholds), len(thresholds),
-            _ptr(min_clusters) if min_clusters is not None else None, vp(dcounts), vp(dn_clusters), vp(djer)))
+        self._der_timed_sweep_dev("plda_der_timed_jer_sweep_dev", dmerges, dturns, turn_off, dseg_start, dseg_dur, offsets, duem, uem_off,
+                                  collar, flags, thresholds, min_clusters, dcounts, dn_clusters, djer)
 
     def der_jer_dev(self, dref, dhyp, ddur, offsets, dcounts, djer, dmap=None, djmap=None, dspk=None):
         """plda_der_jer_dev: der_dev, then djer int64 [R, 2], djmap int32 [R, 64] or None, dspk int64 [R, 64, 3] or None."""
-        def vp(x):
-            return C.c_void_p(int(x)) if x else None
-        self._ck(self._lib.plda_der_jer_dev(self._h, vp(dref), vp(dhyp), vp(ddur), _ptr(offsets), len(offsets) - 1, vp(dcounts), vp(dmap),
-                                            vp(djer), vp(djmap), vp(dspk)))
+        self._der_seg_dev("plda_der_jer_dev", dref, dhyp, ddur, offsets, dcounts, dmap, djer, djmap, dspk)
 
     def der_jer_sweep_dev(self, dmerge_a, dmerge_b, dmerge_cost, offsets, dref, ddur, thresholds, min_clusters, dcounts, dn_clusters,
                           djer):
         """plda_der_jer_sweep_dev: der_sweep_dev, then djer int64 [Q, R, 2]."""
-        def vp(x):
-            return C.c_void_p(int(x)) if x else None
-        self._ck(self._lib.plda_der_jer_sweep_dev(
-            self._h, vp(dmerge_a), vp(dmerge_b), vp(dmerge_cost), _ptr(offsets), len(offsets) - 1, vp(dref), vp(ddur), _ptr(thresholds),
-            len(thresholds), _ptr(min_clusters) if min_clusters is not None else None, vp(dcounts), vp(dn_clusters), vp(djer)))
+        self._der_seg_sweep_dev("plda_der_jer_sweep_dev", (dmerge_a, dmerge_b, dmerge_cost), offsets, dref, ddur, thresholds, min_clusters,
+                                dcounts, dn_clusters, djer)
 
     def der_timed_ovl_dev(self, dturns, turn_off, dseg_start, dseg_dur, dhyp, dhyp2, offsets, dcounts, dmap=None, duem=None,
                           uem_off=None, collar=0, flags=0):
         """plda_der_timed_ovl_dev: der_timed_dev with dhyp2 int32 [T], the second label of every segment (None: der_timed_dev)."""
-        def vp(x):
-            return C.c_void_p(int(x)) if x else None
-        du = duem if duem is not None else (None, None)
-        self._ck(self._lib.plda_der_timed_ovl_dev(
-            self._h, vp(dturns[0]), vp(dturns[1]), vp(dturns[2]), _ptr(turn_off), vp(dseg_start), vp(dseg_dur), vp(dhyp), vp(dhyp2),
-            _ptr(offsets), len(offsets) - 1, vp(du[0]), vp(du[1]), _ptr(uem_off) if uem_off is not None else None, int(collar),
-            int(flags), vp(dcounts), vp(dmap)))
+        self._der_timed_dev("plda_der_timed_ovl_dev", dturns, turn_off, dseg_start, dseg_dur, (dhyp, dhyp2), offsets, duem, uem_off, collar,
+                            flags, dcounts, dmap)
 
     def der_timed_dev(self, dturns, turn_off, dseg_start, dseg_dur, dhyp, offsets, dcounts, dmap=None, duem=None, uem_off=None,
                       collar=0, flags=0):
         """plda_der_timed_dev on HBM-resident int32 arrays (raw device addresses): dturns = (turn_start, turn_dur, turn_spk),
         duem = (uem_start, uem_dur) or None; turn_off, offsets, uem_off (int64) are HOST arrays; dcounts int64 [R, 4], dmap
         int32 [R, 64] or None."""
-        def vp(x):
-            return C.c_void_p(int(x)) if x else None
-        du = duem if duem is not None else (None, None)
-        self._ck(self._lib.plda_der_timed_dev(
-            self._h, vp(dturns[0]), vp(dturns[1]), vp(dturns[2]), _ptr(turn_off), vp(dseg_start), vp(dseg_dur), vp(dhyp), _ptr(offsets),
-            len(offsets) - 1, vp(du[0]), vp(du[1]), _ptr(uem_off) if uem_off is not None else None, int(collar), int(flags), vp(dcounts),
-            vp(dmap)))
+        self._der_timed_dev("plda_der_timed_dev", dturns, turn_off, dseg_start, dseg_dur, (dhyp,), offsets, duem, uem_off, collar, flags,
+                            dcounts, dmap)
 
     def der_timed_sweep_dev(self, dmerges, dturns, turn_off, dseg_start, dseg_dur, offsets, thresholds, min_clusters, dcounts,
                             dn_clusters, duem=None, uem_off=None, collar=0, flags=0):
         """plda_der_timed_sweep_dev on an HBM-resident full merge record dmerges = (merge_a, merge_b, merge_cost) and the
         arrays of der_timed_dev; thresholds (float64) and min_clusters (int32 or None) are HOST arrays; dcounts int64
         [Q, R, 4], dn_clusters int32 [Q, R]."""
-        def vp(x):
-            return C.c_void_p(int(x)) if x else None
-        du = duem if duem is not None else (None, None)
-        self._ck(self._lib.plda_der_timed_sweep_dev(
-            self._h, vp(dmerges[0]), vp(dmerges[1]), vp(dmerges[2]), vp(dturns[0]), vp(dturns[1]), vp(dturns[2]), _ptr(turn_off),
-            vp(dseg_start), vp(dseg_dur), _ptr(offsets), len(offsets) - 1, vp(du[0]), vp(du[1]),
-            _ptr(uem_off) if uem_off is not None else None, int(collar), int(flags), _ptr(thresholds), len(thresholds),
-            _ptr(min_clusters) if min_clusters is not None else None, vp(dcounts), vp(dn_clusters)))
+        self._der_timed_sweep_dev("plda_der_timed_sweep_dev", dmerges, dturns, turn_off, dseg_start, dseg_dur, offsets, duem, uem_off, collar,
+                                  flags, thresholds, min_clusters, dcounts, dn_clusters)
 
     def der_dev(self, dref, dhyp, ddur, offsets, dcounts, dmap=None):
         """plda_der_dev on HBM-resident int32 labels and durations (raw device addresses; ddur and dmap may be None);
         offsets (int64) is a HOST array; dcounts int64 [R, 4], dmap int32 [R, 64]."""
-        def vp(x):
-            return C.c_void_p(int(x)) if x else None
-        self._ck(self._lib.plda_der_dev(self._h, vp(dref), vp(dhyp), vp(ddur), _ptr(offsets), len(offsets) - 1, vp(dcounts), vp(dmap)))
+        self._der_seg_dev("plda_der_dev", dref, dhyp, ddur, offsets, dcounts, dmap)
 
     def der_sweep_dev(self, dmerge_a, dmerge_b, dmerge_cost, offsets, dref, ddur, thresholds, min_clusters, dcounts, dn_clusters):
         """plda_der_sweep_dev on an HBM-resident full merge record, labels and durations (raw device addresses); offsets
         (int64), thresholds (float64) and min_clusters (int32 or None) are HOST arrays; dcounts int64 [Q, R, 4], dn_clusters
         int32 [Q, R]."""
-        def vp(x):
-            return C.c_void_p(int(x)) if x else None
-        self._ck(self._lib.plda_der_sweep_dev(
-            self._h, vp(dmerge_a), vp(dmerge_b), vp(dmerge_cost), _ptr(offsets), len(offsets) - 1, vp(dref), vp(ddur), _ptr(thresholds),
-            len(thresholds), _ptr(min_clusters) if min_clusters is not None else None, vp(dcounts), vp(dn_clusters)))
+        self._der_seg_sweep_dev("plda_der_sweep_dev", (dmerge_a, dmerge_b, dmerge_cost), offsets, dref, ddur, thresholds, min_clusters,
+                                dcounts, dn_clusters)
 
     # ----------------------------------------------------------------- norm
     def norm(self, vectors, transformedvecs, numutts=0):
@@ -1457,29 +1433,23 @@ class MPlda(object):
 
     def score_matrix_snorm_dev(self, dU, dn, n_uniform, m, dV, nt, dout, ld, demean=None, destd=None, dtmean=None, dtstd=None):
         """Enqueue one trials block normalised with per-row (demean, destd) and / or per-column (dtmean, dtstd) statistics."""
-        def vp(x):
-            return C.c_void_p(int(x)) if x else None
         self._ck(self._lib.plda_score_matrix_snorm_dev(
-            self._h, vp(dU), vp(dn), int(n_uniform), int(m), vp(dV), int(nt), vp(demean), vp(destd), vp(dtmean), vp(dtstd),
-            vp(dout), int(ld)))
+            self._h, _vp(dU), _vp(dn), int(n_uniform), int(m), _vp(dV), int(nt), _vp(demean), _vp(destd), _vp(dtmean), _vp(dtstd),
+            _vp(dout), int(ld)))
 
     def topn_matrix_dev(self, dscores, ld, m, nt, axis, top_n, dout_scores, dout_index):
         """Enqueue the top_n selection with indices on an HBM-resident fp32 matrix [m, nt] (row pitch ld): per row (axis 0) or
         per column (axis 1); dout_scores float32, dout_index int64, both [lines, top_n]."""
-        def vp(x):
-            return C.c_void_p(int(x)) if x else None
-        self._ck(self._lib.plda_topn_matrix_dev(self._h, vp(dscores), int(ld), int(m), int(nt), int(axis), int(top_n),
-                                                vp(dout_scores), vp(dout_index)))
+        self._ck(self._lib.plda_topn_matrix_dev(self._h, _vp(dscores), int(ld), int(m), int(nt), int(axis), int(top_n),
+                                                _vp(dout_scores), _vp(dout_index)))
 
     def score_topn_dev(self, dU, dn, n_uniform, m, dV, nt, axis, top_n, dout_scores, dout_index, dzmean=None, dzstd=None,
                        demean=None, destd=None, dtmean=None, dtstd=None):
         """The same selection on the trials of HBM-resident operands, the matrix never held: the scores of score_matrix_dev
         (dzmean, dzstd) or, with demean / destd and / or dtmean / dtstd, of score_matrix_snorm_dev."""
-        def vp(x):
-            return C.c_void_p(int(x)) if x else None
         self._ck(self._lib.plda_score_topn_dev(
-            self._h, vp(dU), vp(dn), int(n_uniform), int(m), vp(dV), int(nt), vp(dzmean), vp(dzstd), vp(demean), vp(destd),
-            vp(dtmean), vp(dtstd), int(axis), int(top_n), vp(dout_scores), vp(dout_index)))
+            self._h, _vp(dU), _vp(dn), int(n_uniform), int(m), _vp(dV), int(nt), _vp(dzmean), _vp(dzstd), _vp(demean), _vp(destd),
+            _vp(dtmean), _vp(dtstd), int(axis), int(top_n), _vp(dout_scores), _vp(dout_index)))
 
     def score_prepare_dev(self, dV, nt, mixed_counts=False, n_uniform=1):
         """Pack the test side [nt, Dout] (HBM-resident fp64) once; later score_matrix_dev / sharded calls with the same

@@ -294,6 +294,79 @@ def test_ring_threshold_of_transform_rows(ctx, rows):
 
 
 # ---------------------------------------------------------------- refusals
+DER_SEG = ["ref", "hyp", "dur", "offsets", "R", "counts", "map"]
+DER_SWEEP = ["ma", "mb", "mc", "offsets", "R", "ref", "dur", "thr", "Q", "minc", "counts", "ncl"]
+DER_TIMED = ["tstart", "tdur", "tspk", "turn_off", "sstart", "sdur", "hyp", "offsets", "R", "ustart", "udur", "uem_off", "collar",
+             "flags", "counts", "map"]
+DER_TIMED_OVL = DER_TIMED[:7] + ["hyp2"] + DER_TIMED[7:]
+DER_TIMED_SWEEP = ["ma", "mb", "mc"] + DER_TIMED[:6] + DER_TIMED[7:14] + ["thr", "Q", "minc", "counts", "ncl"]
+# entry point (and its _dev form, which takes the same arguments) -> (the text's prefix, argument order, sweep, timed, JER)
+DER_FORMS = {
+    "plda_der": ("der", DER_SEG, False, False, False),
+    "plda_der_sweep": ("der_sweep", DER_SWEEP, True, False, False),
+    "plda_der_jer": ("der_jer", DER_SEG + ["jer", "jmap", "spk"], False, False, True),
+    "plda_der_jer_sweep": ("der_jer_sweep", DER_SWEEP + ["jer"], True, False, True),
+    "plda_der_timed": ("der_timed", DER_TIMED, False, True, False),
+    "plda_der_timed_ovl": ("der_timed_ovl", DER_TIMED_OVL, False, True, False),
+    "plda_der_timed_sweep": ("der_timed_sweep", DER_TIMED_SWEEP, True, True, False),
+    "plda_der_timed_jer": ("der_timed_jer", DER_TIMED_OVL + ["jer", "jmap", "spk"], False, True, True),
+    "plda_der_timed_jer_sweep": ("der_timed_jer_sweep", DER_TIMED_SWEEP + ["jer"], True, True, True),
+}
+
+
+def _der_refusals(c):
+    """The whole refusal ladder of every DER entry point, host and device form (plda_der and plda_der_sweep: the device form; their
+    host forms are in the table below).  A ladder starts with every argument in the state its check refuses and mends ONE
+    argument per row, in the order of the library's checks: each row fails on the check behind the previous row's, while
+    everything a later check looks at is still wrong.  No row gets as far as a launch or an allocation."""
+    P = c.zero.ctypes.data
+    off, off1, offgap = _hp(OFFSETS), np.array([1, 5, 6, 13], np.int64), np.array([0, 5, 5, 13], np.int64)
+    desc = np.array([0, 5, 2, 6], np.int64)
+    thr, thr_nan, minc0 = np.array([0.0, 1.0]), np.array([0.0, float("nan")]), np.array([1, 0, 1], np.int32)
+    c.keep_der = [off1, offgap, desc, thr, thr_nan, minc0]
+    rows = []
+    for name, (pfx, order, sweep, timed, jer) in DER_FORMS.items():
+        st = dict.fromkeys(order)                 # every pointer NULL ...
+        st.update(R=0, Q=0, collar=-1, flags=2, minc=_hp(minc0), mb=P, mc=P, tdur=P, tspk=P, udur=P, uem_off=_hp(off1))
+        ladder = []
+        if timed:
+            ladder += [("turn_off is NULL", "turn_off", _hp(off1)), ("seg_start is NULL", "sstart", P), ("seg_dur is NULL", "sdur", P)]
+            ladder += [] if sweep else [("hyp is NULL", "hyp", P)]
+            ladder += [("counts is NULL", "counts", P)]
+            ladder += [("jer is NULL", "jer", P)] if jer else []
+            ladder += [("n_clusters is NULL", "ncl", P)] if sweep else []
+        else:
+            ladder += [("ref is NULL", "ref", P)]
+            ladder += [] if sweep else [("hyp is NULL", "hyp", P)]
+            ladder += [("counts is NULL", "counts", P)]
+            ladder += [("n_clusters is NULL", "ncl", P)] if sweep else []
+            ladder += [("jer is NULL", "jer", P)] if jer else []
+        ladder += [("R = 0 (must be >= 1)", "R", 1 << 31), ("R = 2147483648 (at most 2^31 - 1)", "R", R),
+                   ("offsets is NULL", "offsets", _hp(off1)), ("offsets[0] = 1 (must be 0)", "offsets", _hp(offgap)),
+                   ("recording 1 has 0 segments (must be 1 ... PLDA_AHC_MAX = 4096; offsets must ascend)", "offsets", off)]
+        if sweep:
+            ladder += [("Q = 0 (must be >= 1)", "Q", 65536), ("Q = 65536 (at most 65535)", "Q", 2), ("thresholds is NULL", "thr", _hp(thr_nan)),
+                       ("thresholds[1] is NaN", "thr", _hp(thr)), ("min_clusters[1] = 0 (must be >= 1)", "minc", None)]
+        if timed:
+            ladder += [("turn_off[0] = 1 (must be 0)", "turn_off", _hp(desc)),
+                       ("recording 1 has -3 turns (must be 0 ... PLDA_DER_MAX_TURNS = 16384; turn_off must ascend)", "turn_off", off),
+                       ("turn_start, turn_dur or turn_spk is NULL", "tstart", P),
+                       ("uem_off[0] = 1 (must be 0)", "uem_off", _hp(desc)),
+                       ("recording 1 has -3 UEM intervals (must be 0 ... PLDA_DER_MAX_UEM = 1024; uem_off must ascend)", "uem_off", off),
+                       ("uem_start or uem_dur is NULL", "uem_off", None),      # (the UEM arrays without their offsets: udur is still given)
+                       ("uem_off is NULL", "udur", None),
+                       ("collar = -1 (must be 0 ... 2^20)", "collar", 0),
+                       ("flags = 2 (bit 0, PLDA_DER_SKIP_OVERLAP, is the only one)", "flags", 0)]
+        if sweep:
+            ladder += [("merge_a, merge_b or merge_cost is NULL", "ma", P)]
+        fns = [name + "_dev"] if name in ("plda_der", "plda_der_sweep") else [name, name + "_dev"]
+        for text, key, mended in ladder:
+            assert key in st, (name, key)
+            rows += [(fn, c.h, [st[k] for k in order], INVAL, "%s: %s" % (pfx, text)) for fn in fns]
+            st[key] = mended
+    return rows
+
+
 def _refusals(c):
     """(entry point, handle, arguments, status, plda_last_error text or None).  Texts are the library's, letter for letter."""
     h, f, P = c.h, c.f, c.zero.ctypes.data
@@ -462,6 +535,7 @@ def _refusals(c):
         ("plda_der_sweep", h, [None, None, None, off, R, P, None, _hp(thr), Q, _hp(minc0), P, P], INVAL, "der_sweep: min_clusters[1] = 0 (must be >= 1)"),
         ("plda_der_sweep", h, [P, P, None, off, R, P, None, _hp(thr), Q, None, P, P], INVAL, "der_sweep: merge_a, merge_b or merge_cost is NULL"),
 
+    ] + _der_refusals(c) + [
         ("plda_vbx", f, vbx(Y=None, R=0), NOT_FITTED, "vbx: model not fitted"),
         ("plda_vbx", h, vbx(Y=None, lin=None), INVAL, "vbx: Y is NULL"),
         ("plda_vbx", h, vbx(lin=None, R=0), INVAL, "vbx: labels_in is NULL"),
@@ -533,7 +607,8 @@ def test_refusals_status_text_and_order(ctx):
                   "plda_score_dense_pca_ahc", "plda_der", "plda_der_sweep", "plda_vbx", "plda_project_rows", "plda_embed_apply",
                   "plda_embed_fit", "plda_gemm_f64", "plda_spd_inverse", "plda_sym_eig", "plda_eer_lists", "plda_det_lists",
                   "plda_min_dcf_lists", "plda_calib_pass_lists", "plda_calib_fit_lists", "plda_fusion_pass_lists", "plda_fusion_fit_lists"}
-    assert host_forms <= seen
+    host_forms |= set(DER_FORMS)
+    assert host_forms <= seen and {fn + "_dev" for fn in DER_FORMS} <= seen
     assert ctx.eng.dims() == (D, D)     # the handles still work
     assert lib.plda_adapt_accumulate(None, None, 0, D, None) == INVAL
 
