@@ -773,6 +773,107 @@ int plda_min_dcf_step(int32_t level, int64_t n_nodes, const plda_min_dcf_node *n
 int plda_min_dcf_finish(const plda_min_dcf_state *state, int32_t n_points, const plda_dcf_point *points, const uint32_t *below,
                         const uint32_t *above, plda_min_dcf *out);
 
+/* ---- ROC convex hull (ROCCH), minCllr, the ROCCH-EER and PAV calibration, exact on integers and without a global sort
+ * (csrc/rocch.hip; the remaining corner of the BOSARIS evaluation set next to the EER, Cllr / actDCF and minDCF above; the
+ * project's own extension: tests/rocch_model.py pins it).  Cllr = minCllr + calibration loss.
+ *
+ * Trials, classes, keys and cuts are those of plda_min_dcf_*: an fp32 score, -0.0 == +0.0, `key` the order-preserving 32-bit
+ * key, a CUT "reject every key <= k" for a key k present in the data, plus the empty cut.  A non-finite score fails the call
+ * with PLDA_E_INVAL and the count in plda_last_error; Np == 0 or Nn == 0 likewise.
+ *   * ROC POINT of a cut: x = #{non-target key <= k}, y = #{target key <= k}, both integers.  The empty cut is (0, 0), the cut
+ *     at the largest key (Nn, Np).  Tied keys of both classes move together: one key is one point.
+ *   * ROCCH: the lower convex hull of those points from (0, 0) to (Nn, Np).  Only strict vertices are kept: a middle point is
+ *     dropped when the cross product (128-bit integers on the host: it reaches 1e20 at 1e10 trials) is <= 0.  A vertex
+ *     record carries x, y, fa = Nn - x, miss = y, the key of its cut (has_key = 0 for the empty cut) and a threshold by the
+ *     EER's midpoint rule exactly as plda_min_dcf reports it: the smallest score for the empty cut, +inf for the last
+ *     vertex, otherwise s + (s' - s) / 2 in fp64 with s the score of the key and s' the next larger score present.
+ *   * PAV: segment i between the vertices i and i + 1 has dn_i = delta x, dt_i = delta y and covers the keys in
+ *     (key(V_i), key(V_i+1)]; the first segment also takes everything below, the last everything above.
+ *     llr_i = log(dt_i / dn_i) - log(Np / Nn), -inf when dt_i == 0, +inf when dn_i == 0.  The slopes rise strictly, so the
+ *     map is non-decreasing.  NO Laplace dummy trials are added: BOSARIS's optloglr adds them (its end segments are finite);
+ *     parity with BOSARIS is unpinned (it is not on the build machine).
+ *   * minCllr = [ sum_i (dt_i / Np) log1p((dn_i Np) / (dt_i Nn)) + sum_i (dn_i / Nn) log1p((dt_i Nn) / (dn_i Np)) ] / (2 ln 2),
+ *     a segment with dt_i == 0 or dn_i == 0 contributing 0; fp64, two sums over the segments in ascending order.  It is the
+ *     optimum of the calibration's Cllr over all non-decreasing maps of the score: 0 for separated lists, exactly 1 for a
+ *     single key or for targets entirely below the non-targets.
+ *   * ROCCH-EER: the point where the hull meets y / Np = 1 - x / Nn, in fp64 from the integer vertices a, b of the segment
+ *     that crosses (b the first vertex with y Nn + x Np >= Np Nn): with D = dy Nn + dx Np and tn = Np Nn - (a.y Nn + a.x Np),
+ *     eer = (a.y D + tn dy) / (Np D), the numerator an exact 128-bit integer.  eer_far_lo / eer_frr_lo are the rates of a,
+ *     eer_far_hi / eer_frr_hi those of b.
+ *
+ * METHOD: a strict vertex is a cut whose own key group holds a non-target and whose next key group holds a target, so only
+ * the cuts next to the keys of ONE class can be vertices.  The EDGE class is the one with fewer trials (the targets on a
+ * tie; a matrix: counted from the speaker ids alone).  With u_1 < ... < u_T its distinct keys, the hull of the 2 T points
+ * (#other < u_j, #edge < u_j), (#other <= u_j, #edge <= u_j), oriented to (x, y), plus the two end points is the hull of all
+ * points.  Read 1 appends the edge keys (at most PLDA_ROCCH_EDGE_CAP of them, default 2^24: PLDA_E_CAPACITY above, the
+ * message naming both numbers), which are sorted on the device; read 2 ranks the other class among them (counter 2 g for a
+ * key strictly inside gap g, 2 g + 1 for a key equal to the g-th sorted edge key; a window of 4096 gaps in LDS chosen from a
+ * coarse count at every ceil(T / 2048)-th edge key -- a read of its own, every 16th row of a matrix of >= 4096 rows -- the
+ * rest by 64-bit global atomics); the host forms the distinct keys, the integer prefix sums and the monotone chain
+ * (plda_rocch_hull); read 3 finds the keys next to each vertex's cut (plda_rocch_finish), 4095 cuts per read.  Integer
+ * atomics only: a call is bit-reproducible.  The operand form re-scores its slabs once per read.  There is no row-sharded
+ * (_comm) form: it would need the edge keys gathered.
+ * PLDA_ROCCH_VARIANT (read by plda_create): 1 = no LDS window, every rank through global atomics; 2 = a window of 256 gaps.
+ *
+ * out / vertices[cap_vertices] / llr[cap_vertices - 1] / points / info are HOST memory; the calls synchronise the handle's
+ * stream.  out is written (np, nn, n_vertices, min_cllr, eer, ...) also when the hull has more than cap_vertices vertices:
+ * that is PLDA_E_CAPACITY with the needed count in out->n_vertices and the arrays untouched (cap_vertices == 0 asks for the
+ * figures alone and fails the same way).  points (nullable): the caller sets cap and the five arrays; the call writes T and
+ * edge_class (1: the targets are the edge class) and, when cap >= T, per distinct edge key j: edge_key, other_lt / other_le =
+ * #{other-class key < / <= u_j}, edge_lt / edge_le likewise for the edge class; cap < T is PLDA_E_CAPACITY.
+ *
+ * plda_pav_map_dev: out[i, j] = (float) llr[segment of key(s[i, j])] from a vertex array and its llrs (HOST arrays, as the
+ * calls above return them; at most 4097 vertices, PLDA_E_CAPACITY above: there is no global-table fall-back).  NaN in gives
+ * that NaN out; +-inf fall into the end segments by their keys; bound > 0 clamps the table to [-bound, bound] before the
+ * cast.  Layout, columns [Nt, ld_out) and the in-place rule (dout == dscores, ld_out == ld) as plda_affine_map_dev.  The
+ * table is uploaded first and the stream synchronised once for it; the map itself is enqueued and not waited for. ---- */
+typedef struct plda_rocch_vertex { uint64_t x, y, fa, miss; double threshold; uint32_t key; int32_t has_key; } plda_rocch_vertex;
+typedef struct plda_rocch {
+  uint64_t np, nn;
+  int64_t n_vertices;
+  double min_cllr, eer, eer_far_lo, eer_far_hi, eer_frr_lo, eer_frr_hi;
+} plda_rocch;
+typedef struct plda_rocch_points {
+  int64_t cap, T;
+  int32_t edge_class, reserved;
+  uint32_t *edge_key;
+  uint64_t *other_lt, *other_le, *edge_lt, *edge_le;
+} plda_rocch_points;
+typedef struct plda_rocch_info {
+  uint64_t np, nn;
+  uint64_t t_raw, t_distinct;      /* trials of the edge class; its distinct keys */
+  uint64_t n_lds, n_global_atomic, n_register;   /* ranks counted in the LDS window / by global atomics / outside [u_1, u_T] */
+  int64_t window_start, window_size;   /* the window's first gap and its gaps (0: none) */
+  int32_t reads;                   /* passes over the scores (the coarse and the neighbour reads included) */
+  int32_t launches;
+  int32_t edge_class;              /* 1: targets */
+  int32_t coarse_read;             /* 1: the window was chosen from a coarse count, taken in a read of its own */
+  int32_t neighbour_reads;
+  int32_t reserved;
+} plda_rocch_info;
+int plda_rocch_matrix_dev(plda_handle *h, const float *dscores, int64_t ld, int64_t M, int64_t Nt, const int64_t *denrol_spk,
+                          const int64_t *dtest_spk, int64_t cap_vertices, plda_rocch *out, plda_rocch_vertex *vertices,
+                          double *llr, plda_rocch_points *points, plda_rocch_info *info);
+int plda_rocch_lists(plda_handle *h, const float *pos, int64_t np, const float *neg, int64_t nn, int64_t cap_vertices,
+                     plda_rocch *out, plda_rocch_vertex *vertices, double *llr, plda_rocch_points *points, plda_rocch_info *info);
+int plda_score_rocch_dev(plda_handle *h, const double *dU, const int32_t *dn_enrol, int32_t n_uniform, int64_t M,
+                         const double *dV, int64_t Nt, const double *dzmean, const double *dzstd, const int64_t *denrol_spk,
+                         const int64_t *dtest_spk, int64_t cap_vertices, plda_rocch *out, plda_rocch_vertex *vertices,
+                         double *llr, plda_rocch_points *points, plda_rocch_info *info);
+int plda_pav_map_dev(plda_handle *h, const float *dscores, int64_t ld, int64_t M, int64_t Nt, int64_t n_vertices,
+                     const plda_rocch_vertex *vertices, const double *llr, double bound, float *dout, int64_t ld_out);
+/* The host steps as pure functions (no handle, no GPU; the pattern of plda_min_dcf_step).  plda_rocch_hull: the reduced
+ * points of T >= 1 distinct ascending edge keys (edge_lt[0] == 0, edge_lt[j] == edge_le[j - 1], the last edge_le the class
+ * total; anything inconsistent is PLDA_E_INVAL) -> out, the vertices and llr[n_vertices - 1].  A vertex's `key` is here the
+ * EDGE of its cut -- "reject every key <= key": u_j, or u_j - 1 for the cut just below u_j, the largest word for the last
+ * vertex -- and its threshold NaN.  plda_rocch_finish: below[v] = the largest key present <= that edge, above[v] = the
+ * smallest key present above it (above[0]: the smallest key of all; below[0] and above[n - 1] are not read) -> key = below[v]
+ * and the threshold. */
+int plda_rocch_hull(int64_t T, const uint32_t *edge_key, const uint64_t *other_lt, const uint64_t *other_le,
+                    const uint64_t *edge_lt, const uint64_t *edge_le, int32_t edge_class, uint64_t np, uint64_t nn,
+                    int64_t cap_vertices, plda_rocch *out, plda_rocch_vertex *vertices, double *llr);
+int plda_rocch_finish(int64_t n_vertices, plda_rocch_vertex *vertices, const uint32_t *below, const uint32_t *above);
+
 /* ---- several GPUs of one node: one process per GPU, one handle per process.  The reference
  * has no counterpart (one process, one thread; its native object libplda.MPlda, pldamodule.cpp:280-295, is the only
  * thing callers bind, so the sharded path lives behind the same object).

@@ -56,6 +56,15 @@ class PLDA(object):
         (prior, c_miss, c_fa); returns (one dict per point, info)."""
         return self._instance.min_dcf(enrol, test, test_speaker, points, znorm, cohort, top_k, calibrate)
 
+    def min_cllr(self, enrol, test, test_speaker, znorm=True, cohort=None, top_k=None):
+        """minCllr and the ROC convex hull of the trials between two transform() results; returns (result dict, a
+        plda_amd.rocch.Pav holding the hull's vertices and the PAV llrs)."""
+        return self._instance.min_cllr(enrol, test, test_speaker, znorm, cohort, top_k)
+
+    def calibrate_pav(self, enrol, test, test_speaker, znorm=True, cohort=None, top_k=None):
+        """Fit and store the PAV (pool adjacent violators) map of those trials; returns the plda_amd.rocch.Pav."""
+        return self._instance.calibrate_pav(enrol, test, test_speaker, znorm, cohort, top_k)
+
     def cohort_stats(self, side, cohort, top_k=None):
         """(mean, std) of the top_k largest cohort scores of every row of `side` (AS-norm statistics)."""
         return self._instance.cohort_stats(side, cohort, top_k)

@@ -128,6 +128,12 @@ SIGNATURES = {
     "plda_min_dcf_matrix_comm_dev": (C.c_int, [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _i32, _vp, _vp, _vp]),
     "plda_min_dcf_step": (C.c_int, [_i32, _i64, _vp, _vp, _i32, _vp, _vp, _i64, _vp, C.POINTER(_i64)]),
     "plda_min_dcf_finish": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _vp]),
+    "plda_rocch_matrix_dev": (C.c_int, [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "plda_rocch_lists": (C.c_int, [_vp, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "plda_score_rocch_dev": (C.c_int, [_vp, _vp, _vp, _i32, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "plda_pav_map_dev": (C.c_int, [_vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _f64, _vp, _i64]),
+    "plda_rocch_hull": (C.c_int, [_i64, _vp, _vp, _vp, _vp, _vp, _i32, C.c_uint64, C.c_uint64, _i64, _vp, _vp, _vp]),
+    "plda_rocch_finish": (C.c_int, [_i64, _vp, _vp, _vp]),
     "plda_affine_map_dev": (C.c_int, [_vp, _vp, _i64, _i64, _i64, _f64, _f64, _vp, _i64]),
     "plda_fusion_pass_matrices_dev": (C.c_int, [_vp, _i32, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _f64, _f64, _vp]),
     "plda_fusion_pass_lists": (C.c_int, [_vp, _i32, _vp, _i64, _vp, _i64, _vp, _f64, _f64, _vp]),

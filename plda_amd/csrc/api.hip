@@ -288,11 +288,13 @@ const struct { const char *name; int plda_handle::*member; } ENV_INT[] = {
     {"PLDA_SORT_VARIANT", &plda_handle::sort_variant},     {"PLDA_ZNORM_VARIANT", &plda_handle::znorm_variant},
     {"PLDA_EER_VARIANT", &plda_handle::eer_variant},       {"PLDA_MINDCF_VARIANT", &plda_handle::mindcf_variant},
     {"PLDA_HOST_VARIANT", &plda_handle::host_variant},     {"PLDA_SWEEP_VARIANT", &plda_handle::sweep_variant},
+    {"PLDA_ROCCH_VARIANT", &plda_handle::rocch_variant},
 };
 const struct { const char *name; int64_t plda_handle::*member; } ENV_INT64[] = {
     {"PLDA_EER_SLAB_ROWS", &plda_handle::eer_slab_rows},         {"PLDA_SNORM_SLAB_ROWS", &plda_handle::sn_slab_rows},
     {"PLDA_ADAPT_SLAB_ROWS", &plda_handle::ad_slab_rows},        {"PLDA_AHC_SCRATCH_BYTES", &plda_handle::ahc_scratch_bytes},
     {"PLDA_VBX_SCRATCH_BYTES", &plda_handle::vbx_scratch_bytes}, {"PLDA_DER_SCRATCH_BYTES", &plda_handle::der_scratch_bytes},
+    {"PLDA_ROCCH_EDGE_CAP", &plda_handle::rocch_edge_cap},
 };
 
 // ... and the ones that are checked: a refused value fails plda_create (the text goes to plda_last_error(NULL))
@@ -1758,6 +1760,49 @@ int plda_det_lists(plda_handle *h, const float *pos, int64_t np, const float *ne
 int plda_eer_lists(plda_handle *h, const float *pos, int64_t np, const float *neg, int64_t nn, double *out) {
   return with_host_lists(h, "plda_eer_lists", pos, np, neg, nn, out != nullptr, "eer: need at least one target and one impostor score",
                          [&](const float *dpos, const float *dneg) { return eer_lists_device(h, dpos, np, dneg, nn, out); });
+}
+
+// ---------------------------------------------------------------- ROC convex hull, minCllr, PAV (rocch.hip)
+int plda_rocch_matrix_dev(plda_handle *h, const float *dscores, int64_t ld, int64_t M, int64_t Nt, const int64_t *denrol_spk,
+                          const int64_t *dtest_spk, int64_t cap_vertices, plda_rocch *out, plda_rocch_vertex *vertices, double *llr,
+                          plda_rocch_points *points, plda_rocch_info *info) {
+  return device_entry(h, "plda_rocch_matrix_dev", [&] {
+    return rocch_matrix_device(h, dscores, ld, M, Nt, denrol_spk, dtest_spk, cap_vertices, out, vertices, llr, points, info);
+  });
+}
+
+int plda_rocch_lists(plda_handle *h, const float *pos, int64_t np, const float *neg, int64_t nn, int64_t cap_vertices, plda_rocch *out,
+                     plda_rocch_vertex *vertices, double *llr, plda_rocch_points *points, plda_rocch_info *info) {
+  return with_host_lists(h, "plda_rocch_lists", pos, np, neg, nn, out != nullptr, "rocch: need at least one target and one non-target score",
+                         [&](const float *dpos, const float *dneg) {
+                           return rocch_lists_device(h, dpos, np, dneg, nn, cap_vertices, out, vertices, llr, points, info);
+                         });
+}
+
+int plda_score_rocch_dev(plda_handle *h, const double *dU, const int32_t *dn_enrol, int32_t n_uniform, int64_t M, const double *dV,
+                         int64_t Nt, const double *dzmean, const double *dzstd, const int64_t *denrol_spk, const int64_t *dtest_spk,
+                         int64_t cap_vertices, plda_rocch *out, plda_rocch_vertex *vertices, double *llr, plda_rocch_points *points,
+                         plda_rocch_info *info) {
+  return device_entry(h, "plda_score_rocch_dev", [&] {
+    return score_rocch_device(h, dU, dn_enrol, n_uniform, M, dV, Nt, dzmean, dzstd, denrol_spk, dtest_spk, cap_vertices, out, vertices, llr,
+                              points, info);
+  });
+}
+
+int plda_pav_map_dev(plda_handle *h, const float *dscores, int64_t ld, int64_t M, int64_t Nt, int64_t n_vertices,
+                     const plda_rocch_vertex *vertices, const double *llr, double bound, float *dout, int64_t ld_out) {
+  return device_entry(h, "plda_pav_map_dev", [&] { return pav_map_device(h, dscores, ld, M, Nt, n_vertices, vertices, llr, bound, dout, ld_out); });
+}
+
+// the host steps: pure functions, no handle (the CPU suite drives them with NumPy ranks)
+int plda_rocch_hull(int64_t T, const uint32_t *edge_key, const uint64_t *other_lt, const uint64_t *other_le, const uint64_t *edge_lt,
+                    const uint64_t *edge_le, int32_t edge_class, uint64_t np, uint64_t nn, int64_t cap_vertices, plda_rocch *out,
+                    plda_rocch_vertex *vertices, double *llr) {
+  try { return rocch_hull(T, edge_key, other_lt, other_le, edge_lt, edge_le, edge_class, np, nn, cap_vertices, out, vertices, llr); }
+  catch (...) { return PLDA_E_HIP; }      // (std::bad_alloc of the vertex stack)
+}
+int plda_rocch_finish(int64_t n_vertices, plda_rocch_vertex *vertices, const uint32_t *below, const uint32_t *above) {
+  return rocch_finish(n_vertices, vertices, below, above);
 }
 
 // ---------------------------------------------------------------- minimum detection cost (dcf.hip)

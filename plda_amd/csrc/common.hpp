@@ -294,10 +294,12 @@ struct plda_handle {
   plda::DevBuf zn_rows, zn_y, zn_small, zn_cpad;   // z-norm statistics by moments (score.hip; zn_cpad: the padded covariance of the model pass, transform.hip)
   int znorm_variant = 0;         // PLDA_ZNORM_VARIANT=1: every LLR on the fused fp32 GEMM (A/B arm); 2: moments in five passes
   plda::DevBuf eer_slab, eer_smp; // plda_score_eer_dev: the row slab of scores in flight; the pilot's gathered enrol rows
-  plda::DevBuf trial_hist;       // eer.hip / dcf.hip: the two histograms of a labelled pass, then its window, DET or survivor output (one buffer: one such call runs at a time)
+  plda::DevBuf trial_hist;       // eer.hip / dcf.hip: the two histograms of a labelled pass, then its window, DET or survivor output (one buffer: one such call runs at a time); rocch.hip: the edge keys (twice: the sort's two sides), digit histograms, search table, rank counters and neighbour words of a hull call (one layout list), or the PAV map's vertex keys and llr table
   plda::DevBuf eer_list[2];      // eer.hip, single-pass form: the impostor / target scores inside the pilot's key window
   int eer_variant = 0;           // PLDA_EER_VARIANT=1: always the three passes; 2: the single-pass form at every size (tests)
   int mindcf_variant = 0;        // PLDA_MINDCF_VARIANT=1: never compact the survivors into lists; 2: two nodes per read (dcf.hip; tests)
+  int rocch_variant = 0;         // PLDA_ROCCH_VARIANT=1: no LDS window, every rank through global atomics; 2: a window of 256 gaps (tests)
+  int64_t rocch_edge_cap = 0;    // PLDA_ROCCH_EDGE_CAP: the most edge-class trials a ROCCH call accepts (0: 2^24)
   int64_t eer_slab_rows = 0;     // PLDA_EER_SLAB_ROWS: rows per slab of plda_score_eer_dev (0: <= 4 GiB of scores)
   plda::DevBuf calib_part;       // calib.hip: one partial plda_calib_record per workgroup of a calibration pass + the reduced one
   plda::DevBuf fusion_part;      // fusion.hip: one partial plda_fusion_record per workgroup of a fusion pass + the reduced one

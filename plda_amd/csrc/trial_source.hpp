@@ -1,6 +1,7 @@
 // plda_amd/csrc/trial_source.hpp -- what a reduction over labelled trials consumes, and the one walk over it.
 //
-// The EER and DET points (eer.hip), the calibration pass (calib.hip) and the minDCF levels (dcf.hip) all read labelled trials
+// The EER and DET points (eer.hip), the calibration pass (calib.hip), the minDCF levels (dcf.hip) and the ROC convex hull
+// (rocch.hip) all read labelled trials
 // that arrive in one of three kinds: a trials matrix in HBM with the speaker ids of its rows and columns (possibly the local
 // rows of a row-sharded matrix), two flat lists of target / non-target scores, or a matrix that exists one row slab at a time
 // (the operand forms: operand_slabs.hip scores a slab, the consumer reads it, the next slab overwrites it).  A TrialSource
@@ -163,6 +164,21 @@ int min_dcf_lists_device(plda_handle *h, const float *dpos, int64_t np, const fl
 int score_min_dcf_device(plda_handle *h, const double *dU, const int32_t *dn, int n_uniform, int64_t M, const double *dV, int64_t Nt,
                          const double *dzmean, const double *dzstd, const int64_t *despk, const int64_t *dtspk, int n_points,
                          const plda_dcf_point *pts, plda_min_dcf *out, plda_min_dcf_info *info);
+// ---- rocch.hip
+int rocch_hull(int64_t T, const uint32_t *edge_key, const uint64_t *other_lt, const uint64_t *other_le, const uint64_t *edge_lt,
+               const uint64_t *edge_le, int edge_class, uint64_t Np, uint64_t Nn, int64_t cap_vertices, plda_rocch *out,
+               plda_rocch_vertex *vertices, double *llr);
+int rocch_finish(int64_t n_vertices, plda_rocch_vertex *vertices, const uint32_t *below, const uint32_t *above);
+int rocch_matrix_device(plda_handle *h, const float *dscores, int64_t ld, int64_t M, int64_t Nt, const int64_t *despk, const int64_t *dtspk,
+                        int64_t cap_vertices, plda_rocch *out, plda_rocch_vertex *vertices, double *llr, plda_rocch_points *points,
+                        plda_rocch_info *info);
+int rocch_lists_device(plda_handle *h, const float *dpos, int64_t np, const float *dneg, int64_t nn, int64_t cap_vertices, plda_rocch *out,
+                       plda_rocch_vertex *vertices, double *llr, plda_rocch_points *points, plda_rocch_info *info);
+int score_rocch_device(plda_handle *h, const double *dU, const int32_t *dn, int n_uniform, int64_t M, const double *dV, int64_t Nt,
+                       const double *dzmean, const double *dzstd, const int64_t *despk, const int64_t *dtspk, int64_t cap_vertices,
+                       plda_rocch *out, plda_rocch_vertex *vertices, double *llr, plda_rocch_points *points, plda_rocch_info *info);
+int pav_map_device(plda_handle *h, const float *dscores, int64_t ld, int64_t M, int64_t Nt, int64_t n_vertices,
+                   const plda_rocch_vertex *vertices, const double *llr, double bound, float *dout, int64_t ld_out);
 // ---- calib.hip
 int calib_pass_matrix_device(plda_handle *h, const float *dscores, int64_t ld, int64_t M, int64_t Nt, const int64_t *despk,
                              const int64_t *dtspk, double a, double c, double theta, plda_calib_record *out);

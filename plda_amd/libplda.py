@@ -145,6 +145,7 @@ class MPlda(object):
         self._meanz = {}
         self._stdvz = {}
         self._calibration = None      # plda_amd.calibration.Calibration of the last calibrate() / load()
+        self.pav = None               # plda_amd.rocch.Pav of the last calibrate_pav()
         self._embedding = None        # plda_amd.embed.EmbeddingChain in front of the raw-row methods (set_embedding / fit_embedding)
 
     def __del__(self):
@@ -1202,6 +1203,40 @@ class MPlda(object):
         if cal is not None:
             self._affine_map_on_device(S, cal)
         return DC.min_dcf_from_matrix_dev(self, S.data_ptr(), nt, m, nt, despk.data_ptr(), dtspk.data_ptr(), points=points)
+
+    def min_cllr(self, enrol, test, test_speaker, znorm=True, cohort=None, top_k=None):
+        """minCllr, the ROC convex hull and the PAV map of the trials between two transform() results (include/plda_hip.h,
+        "ROC convex hull").  Arguments as `min_dcf`; the scores are those of score_matrix (znorm) or, with a cohort,
+        score_matrix_asnorm.  Without a cohort the matrix is never held (the trials are re-scored slab by slab once per
+        read).  Returns (result dict: Np, Nn, n_vertices, min_cllr, eer, ...; a plda_amd.rocch.Pav).  The calibration loss of
+        a calibration is its `cllr_after - min_cllr`."""
+        from . import rocch as RC
+        ids, counts, U, V, tspk = self._labelled_trials(enrol, test, test_speaker, "min_cllr")
+        m, nt = U.shape[0], V.shape[0]
+        despk, dtspk = self._to_device(np.ascontiguousarray(ids, np.int64)), self._to_device(tspk)
+        if cohort is None:
+            zm, zs = self._zn_arrays(ids, znorm)
+            uniform = int(counts[0]) if np.all(counts == counts[0]) else 0
+            dU, dV = self._to_device(U), self._to_device(V)
+            dn = None if uniform else self._to_device(counts)
+            dzm, dzs = (self._to_device(zm), self._to_device(zs)) if zm is not None else (None, None)
+            ptr = lambda t: t.data_ptr() if t is not None else None      # noqa: E731
+            res, pav, _ = RC.rocch_from_operands_dev(self, dU.data_ptr(), ptr(dn), uniform, m, dV.data_ptr(), nt, despk.data_ptr(),
+                                                     dtspk.data_ptr(), ptr(dzm), ptr(dzs))
+            return res, pav
+        Cv = self._cohort_rows(cohort)
+        em, es = self._cohort_stats(counts, U, Cv, top_k)
+        tm, ts = self._cohort_stats(np.ones(nt, np.int32), V, Cv, top_k)
+        S = self._trials_matrix_on_device(counts, U, V, sn=(em, es, tm, ts))
+        res, pav, _ = RC.rocch_from_matrix_dev(self, S.data_ptr(), nt, m, nt, despk.data_ptr(), dtspk.data_ptr())
+        return res, pav
+
+    def calibrate_pav(self, enrol, test, test_speaker, znorm=True, cohort=None, top_k=None):
+        """`min_cllr`, and the PAV map is stored as `self.pav` (the non-parametric reference beside `calibrate`'s affine map:
+        apply it with `self.pav(scores)` or `self.pav.apply_dev(...)`).  The affine calibration, `score_matrix` and their
+        `calibrate=True` paths are not touched.  Returns the Pav."""
+        _, self.pav = self.min_cllr(enrol, test, test_speaker, znorm, cohort, top_k)
+        return self.pav
 
     def calibrate(self, enrol, test, test_speaker, prior=0.5, znorm=True, cohort=None, top_k=None):
         """Fit the linear calibration llr = a * score + b (prior-weighted logistic regression, include/plda_hip.h) on the
