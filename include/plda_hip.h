@@ -1150,6 +1150,89 @@ int plda_score_ahc(plda_handle *h, const double *X, const int64_t *offsets, int6
                    const int32_t *min_clusters, int32_t *labels, int32_t *n_clusters, int32_t *merge_a, int32_t *merge_b,
                    double *merge_cost);
 
+/* ---- spectral clustering with auto-tuned pruning (K24; csrc/spectral.hip): the clusterer that needs no threshold and no
+ * development set -- a pruned k-nearest-neighbour affinity graph, the speaker count from the largest eigengap of its
+ * Laplacian, the pruning value by the normalised-maximum-eigengap rule (NME-SC; Park et al. 2020), k-means on the spectral
+ * embedding.  Only the ORDER of the scores within a row matters, so PLDA LLRs, the PCA blocks of the next section and cosine
+ * similarities are treated alike.  The reference has NO counterpart; tests/spectral_model.py is the NumPy model.
+ *
+ * A RECORDING r is a run of N = offsets[r+1] - offsets[r] consecutive segments, 1 <= N <= PLDA_SPECTRAL_MAX (the direct
+ * eigensolver's limit).  Its input is an fp32 score block S [N, N], row-major, in the format of "speaker clustering" above.
+ *
+ * 1 SIMILARITY.  c(i, j) = ((double)S[i, j] + (double)S[j, i]) / 2 for i != j, exact.  The diagonal is never read.  A
+ *   non-finite off-diagonal score fails the call with PLDA_E_INVAL and the count in plda_last_error; nothing is written (the
+ *   count is read before anything else is enqueued; the operand form scores a call of several slabs twice for that).
+ * 2 GRAPH at pruning value p.  p_eff = min(p, N - 1).  Row i keeps its p_eff best partners j != i under the total order
+ *   (c descending, j ascending), -0.0 == +0.0: B[i, j] = 1 for those, else 0.  A = (B + B^T) / 2 (entries 0, 1/2, 1; diagonal
+ *   0), deg_i = sum_j A[i, j], L = diag(deg) - A.  Exact, a function of the input bits alone.
+ * 3 SPECTRUM.  The eigenvalues of L ascending, l_1 <= ... <= l_N, as the library's fp64 eigensolver returns them (floored at
+ *   0: L is positive semi-definite).  K' = min(max_speakers, N - 1), 1 <= max_speakers <= PLDA_SPECTRAL_MAX_SPK (the VBx's
+ *   label limit).  e_k = l_{k+1} - l_k for k = 1 .. K'; k_gap = the smallest k whose gap is maximal; g = e_{k_gap} /
+ *   (l_N + 1e-10); r = (double)p_eff / g, +inf if g <= 0.  Plain fp64, one operation each, IEEE < and ==.
+ * 4 SWEEP.  Row r of p_table [R, P] holds the recording's P pruning values (1 <= P <= PLDA_SPECTRAL_MAX_P, every value >= 1,
+ *   duplicates allowed; equal p_eff are solved once).  The value used is the one of the smallest r, ties to the smaller p_eff,
+ *   then to the earlier position.  k = min(num_speakers[r], N) when num_speakers is given and > 0 (it may not exceed
+ *   max_speakers), else k_gap at the value used.
+ * 5 EMBEDDING.  U [N, k]: the eigenvectors of the k smallest eigenvalues at the value used (kept from the sweep: nothing is
+ *   solved twice), no row normalisation.
+ * 6 K-MEANS, to the operation.  d(i, m) = sum_c (u_ic - m_c)^2, c ascending, fp64, the product and the sum unfused.  Centre 0 =
+ *   row 0; every further centre is the row with the largest minimum d to the centres so far, ties to the lowest row.  A Lloyd
+ *   step sends every row to its nearest centre (ties to the lowest centre); if no row moved (every row moves in the first
+ *   step) the iteration stops, else every centre with members becomes (sum_i u_ic, i ascending from 0.0) / (double)count -- an
+ *   empty centre keeps its place -- and the next step follows, max_iters steps at most (1 ... 1000).  Labels are renumbered
+ *   0 .. by first occurrence; n_clusters = the number of distinct labels.
+ *   N = 1: one cluster, no eigenproblem: label 0, p_used 0, k_gap 1, eigenvalue 0, embedding 1.0, deg2 0.
+ *
+ * A recording's outputs are bit-identical alone, in any batch, under any grouping into launches and from run to run: every
+ * dispatch depends on N (and, in the k-means, on k) only, and the two k-means classes run the same operations in the same order.
+ *
+ * OUTPUTS.  labels int32 [T], n_clusters int32 [R].  Nullable: p_used int32 [R] (the p_eff used), k_gap int32 [R]; eig fp64
+ * [R, P, max_speakers + 2]: per pruning value the min(max_speakers + 1, N) smallest eigenvalues ascending, +inf behind them,
+ * l_N in the last slot; embed fp64 [T, max_speakers]: a row's first k entries are its embedding, the rest +0.0; deg2 int32 [T]
+ * = 2 deg at the value used.  Nothing else is written.
+ *
+ * METHOD.  Per recording: the symmetrised block once; per distinct p_eff a selection kernel (one wave per row, the row's
+ * order keys in registers, the p-th largest key by bisection over the key bits, then the j-ascending cut among its equals),
+ * the Laplacian from the two cuts of every pair, the library's fp64 eigensolver (direct up to PLDA_SPECTRAL_MAX, one problem
+ * at a time; it synchronises the stream once per problem), and a kernel that forms r and keeps the columns if it is the best
+ * so far.  Per group of recordings one k-means launch, one workgroup per recording, the embedding in LDS where N k doubles
+ * fit 64 KiB and read from scratch above.  The scratch belongs to the handle (freed by plda_destroy); the kept columns of a
+ * group and the operand form's score slab stay within the AHC's budget (2 GiB; PLDA_AHC_SCRATCH_BYTES), never fewer than one
+ * recording.
+ *
+ *   plda_spectral_plan        out[0] = keys per lane of the selection kernel for N (1, 2, 4 ... 32), out[1] = the largest N of
+ *                             that class, out[2] = the k-means class of (N, k) (0 LDS, 1 scratch), out[3] = the largest N of
+ *                             class 0 at this k, out[4] = the scratch bytes of one eigenproblem of order N.
+ *   plda_spectral_matrix_dev  packed blocks in HBM as plda_ahc_matrix_dev takes them.  block_off [R + 1], offsets [R + 1],
+ *                             p_table [R, P] and num_speakers [R] (nullable: k_gap everywhere) are HOST arrays.
+ *   plda_spectral_matrix      the same with scores and outputs in host memory.
+ *   plda_score_spectral*      the operand form: X [T, Dout] transformed segment vectors; the blocks come from the enqueue path
+ *                             and the slab walk of plda_score_ahc*, bit for bit what plda_score_matrix_dev writes.
+ * ERRORS.  PLDA_E_INVAL: the argument errors of plda_ahc_matrix_dev; a recording above PLDA_SPECTRAL_MAX; P, max_speakers or
+ * max_iters out of range; a p < 1; num_speakers[r] < 0 or > max_speakers -- all before any device work.  PLDA_E_NUMERIC: the
+ * eigensolver gave up; the message names the recording (outputs of earlier groups may have been written).
+ * OUT OF SCOPE, each on purpose: a batched eigensolver for many small recordings and an eigenvalues-only sweep (what they
+ * would be worth: scripts/spectral_bench.py's eigensolver share); recordings above 2048 (only the block Jacobi is left there);
+ * a normalised Laplacian; a device-resident chain from the per-recording PCA. ---- */
+#define PLDA_SPECTRAL_MAX 2048
+#define PLDA_SPECTRAL_MAX_SPK 64
+#define PLDA_SPECTRAL_MAX_P 16
+int plda_spectral_plan(plda_handle *h, int64_t N, int32_t k, int32_t out[5]);
+int plda_spectral_matrix_dev(plda_handle *h, const float *dscores, const int64_t *block_off, const int64_t *offsets, int64_t R,
+                             const int32_t *p_table, int32_t P, int32_t max_speakers, const int32_t *num_speakers, int32_t max_iters,
+                             int32_t *dlabels, int32_t *dn_clusters, int32_t *dp_used, int32_t *dk_gap, double *deig, double *dembed,
+                             int32_t *ddeg2);
+int plda_spectral_matrix(plda_handle *h, const float *scores, const int64_t *block_off, const int64_t *offsets, int64_t R,
+                         const int32_t *p_table, int32_t P, int32_t max_speakers, const int32_t *num_speakers, int32_t max_iters,
+                         int32_t *labels, int32_t *n_clusters, int32_t *p_used, int32_t *k_gap, double *eig, double *embed,
+                         int32_t *deg2);
+int plda_score_spectral_dev(plda_handle *h, const double *dX, const int64_t *offsets, int64_t R, const int32_t *p_table, int32_t P,
+                            int32_t max_speakers, const int32_t *num_speakers, int32_t max_iters, int32_t *dlabels,
+                            int32_t *dn_clusters, int32_t *dp_used, int32_t *dk_gap, double *deig, double *dembed, int32_t *ddeg2);
+int plda_score_spectral(plda_handle *h, const double *X, const int64_t *offsets, int64_t R, const int32_t *p_table, int32_t P,
+                        int32_t max_speakers, const int32_t *num_speakers, int32_t max_iters, int32_t *labels, int32_t *n_clusters,
+                        int32_t *p_used, int32_t *k_gap, double *eig, double *embed, int32_t *deg2);
+
 /* ---- dense scoring in a recording's PCA subspace (K19; csrc/dense_pca.hip): Kaldi's ivector-plda-scoring-dense
  * --target-energy=t restated (EstPca, Plda::ApplyTransform, TransformIvector, LogLikelihoodRatio; parity unpinned like the rest
  * of PLDA).  The reference has NO counterpart; tests/dense_pca_model.py is the NumPy model.  Everything is fp64; a score is

@@ -92,11 +92,16 @@ class PLDA(object):
         self._instance.blend(other, alpha, alpha_mean)
         return self
 
-    def cluster(self, x, offsets, threshold=0.0, num_speakers=None, return_merges=False, target_energy=None):
+    def cluster(self, x, offsets, threshold=0.0, num_speakers=None, return_merges=False, target_energy=None, method="ahc", **spectral):
         """Cluster the segments of R recordings (diarisation): x [T, featdim] raw segment vectors, recording r owning rows
         offsets[r] .. offsets[r+1]; average-linkage merging while the best pair's average score is at least `threshold` and
         more than `num_speakers` clusters are left.  target_energy=t: every recording is scored in the PCA subspace of its own
-        vectors (Kaldi's --target-energy).  Returns (labels, n_clusters[, merges]); plda_amd/diarize.py."""
+        vectors (Kaldi's --target-energy).  Returns (labels, n_clusters[, merges]); plda_amd/diarize.py.
+        method="spectral": spectral clustering with auto-tuned pruning, no threshold (keywords p, p_fractions, max_speakers,
+        max_iters, return_info); returns (labels, n_clusters[, info])."""
+        if method != "ahc" or spectral:
+            return self._instance.cluster(x, offsets, threshold, num_speakers, return_merges, target_energy=target_energy, method=method,
+                                          **spectral)
         if target_energy is None:
             return self._instance.cluster(x, offsets, threshold, num_speakers, return_merges)
         return self._instance.cluster(x, offsets, threshold, num_speakers, return_merges, target_energy=target_energy)
@@ -110,10 +115,13 @@ class PLDA(object):
         """VBx resegmentation of the segments of R recordings from initial labels (cluster()'s); plda_amd/diarize.py."""
         return self._instance.resegment(x, offsets, labels, **vbx)
 
-    def diarize(self, x, offsets, threshold=0.0, num_speakers=None, target_energy=None, **vbx):
+    def diarize(self, x, offsets, threshold=0.0, num_speakers=None, target_energy=None, method="ahc", **vbx):
         """cluster, then resegment.  target_energy goes to the clustering only (VBx keeps working on the full model).  Returns
         (labels, n_clusters[, info]); with overlap= (a per-segment bool mask) or min_posterior= (labels, n_clusters, labels2),
-        labels2 the second speaker of every segment where one is kept, -1 elsewhere."""
+        labels2 the second speaker of every segment where one is kept, -1 elsewhere.  method="spectral" (keywords p,
+        p_fractions, max_speakers): the spectral clustering's labels start VBx."""
+        if method != "ahc":
+            return self._instance.diarize(x, offsets, threshold, num_speakers, target_energy=target_energy, method=method, **vbx)
         if target_energy is None:
             return self._instance.diarize(x, offsets, threshold, num_speakers, **vbx)
         return self._instance.diarize(x, offsets, threshold, num_speakers, target_energy=target_energy, **vbx)

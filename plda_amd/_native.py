@@ -156,6 +156,11 @@ SIGNATURES = {
     "plda_dense_pca_plan": (C.c_int, [_vp, _i64, _i32, _vp]),
     "plda_score_dense_pca_dev": (C.c_int, [_vp, _vp, _vp, _i64, _f64, _vp, _vp, _vp, _vp]),
     "plda_score_dense_pca": (C.c_int, [_vp, _vp, _vp, _i64, _f64, _vp, _vp, _vp, _vp]),
+    "plda_spectral_plan": (C.c_int, [_vp, _i64, _i32, _vp]),
+    "plda_spectral_matrix_dev": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "plda_spectral_matrix": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "plda_score_spectral_dev": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "plda_score_spectral": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "plda_score_dense_pca_ahc_dev": (C.c_int, [_vp, _vp, _vp, _i64, _f64, _i32, _f64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "plda_score_dense_pca_ahc": (C.c_int, [_vp, _vp, _vp, _i64, _f64, _i32, _f64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "plda_der_plan": (C.c_int, [_vp, _i64, _i64, _vp]),

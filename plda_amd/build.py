@@ -17,7 +17,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 SO = os.path.join(LIBDIR, "libplda_hip.so")
 SO_DIAG = os.path.join(LIBDIR, "libplda_hip_diag.so")
-SOURCES = ["api.hip", "score.hip", "linalg.hip", "fit.hip", "frontend.hip", "eer.hip", "operand_slabs.hip", "lda.hip", "comm.hip", "eig_dc.hip", "hostio.hip", "transform.hip", "snorm.hip", "calib.hip", "dcf.hip", "rocch.hip", "topn.hip", "fusion.hip", "adapt.hip", "ahc.hip", "dense_pca.hip", "vbx.hip", "der.hip", "der_time.hip", "embed.hip"]
+SOURCES = ["api.hip", "score.hip", "linalg.hip", "fit.hip", "frontend.hip", "eer.hip", "operand_slabs.hip", "lda.hip", "comm.hip", "eig_dc.hip", "hostio.hip", "transform.hip", "snorm.hip", "calib.hip", "dcf.hip", "rocch.hip", "topn.hip", "fusion.hip", "adapt.hip", "ahc.hip", "dense_pca.hip", "vbx.hip", "der.hip", "der_time.hip", "embed.hip", "spectral.hip"]
 HEADERS = [os.path.join(CSRC, "common.hpp"), os.path.join(CSRC, "layout.hpp"), os.path.join(CSRC, "trial_source.hpp"), os.path.join(CSRC, "hostio.hpp"), os.path.join(CSRC, "sweep_mfma.inc"), os.path.join(CSRC, "score_bt4.inc"), os.path.join(CSRC, "score_bf16x3.inc"), os.path.join(CSRC, "syrk_blk.inc"), os.path.join(HERE, "..", "include", "plda_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics",
          "-Wall", "-Wno-unused-function", "-Wno-unused-result"]
@@ -39,6 +39,8 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-ato
 # Its effect on speed has not been measured apart from the rest (scripts/fusion_bench.py times the kernels as built).
 # ahc.hip: the clustering is specified to the bit (tests/ahc_model.py): one fp64 addition and one fp64 division where the
 # contract names them, so nothing may be contracted into a fused multiply-add
+# spectral.hip: the graph, the selection of the pruning value and the k-means are specified to the operation
+# (tests/spectral_model.py): a squared distance is a product and a sum, never a fused multiply-add
 # embed.hip: a row's bits may not depend on the block shape or the input dtype's instantiation it runs in (the determinism rule
 # of the embedding chain): every fused multiply-add there is written as fma(), nothing else may be contracted
 # frontend.hip: variance pooling subtracts the utterance's first normalised frame y0 = x0 * inv from every y = x * inv; a fused
@@ -48,7 +50,8 @@ EXTRA = {"score.hip": ["-mllvm", "-amdgpu-atomic-optimizer-strategy=None"],
          "frontend.hip": ["-ffp-contract=off"],
          "fusion.hip": ["-mllvm", "-disable-machine-licm"],
          "ahc.hip": ["-ffp-contract=off"],
-         "embed.hip": ["-ffp-contract=off"]}
+         "embed.hip": ["-ffp-contract=off"],
+         "spectral.hip": ["-ffp-contract=off"]}
 
 
 def _stale(target, deps):

@@ -2012,6 +2012,96 @@ int plda_score_ahc(plda_handle *h, const double *X, const int64_t *offsets, int6
   });
 }
 
+// ---------------------------------------------------------------- spectral clustering (spectral.hip)
+namespace {
+SpectralArgs spectral_args(const int64_t *offsets, int64_t R, const int32_t *p_table, int32_t P, int32_t max_speakers,
+                           const int32_t *num_speakers, int32_t max_iters, int32_t *labels, int32_t *n_clusters, int32_t *p_used,
+                           int32_t *k_gap, double *eig, double *embed, int32_t *deg2) {
+  SpectralArgs a;
+  a.offsets = offsets; a.R = R; a.p_table = p_table; a.P = P; a.max_spk = max_speakers; a.num_spk = num_speakers; a.max_iters = max_iters;
+  a.labels = labels; a.n_clusters = n_clusters; a.p_used = p_used; a.k_gap = k_gap; a.eig = eig; a.embed = embed; a.deg2 = deg2;
+  return a;
+}
+// the device outputs of a host form, sized from the (validated) host arguments
+int spectral_stage_outputs(Staged &st, const SpectralArgs &host, SpectralArgs *dev) {
+  const size_t T = (size_t)host.offsets[host.R], R = (size_t)host.R;
+  *dev = host;
+  PLDA_TRY(st.out(host.labels, T, &dev->labels));
+  PLDA_TRY(st.out(host.n_clusters, R, &dev->n_clusters));
+  PLDA_TRY(st.out(host.p_used, R, &dev->p_used));
+  PLDA_TRY(st.out(host.k_gap, R, &dev->k_gap));
+  PLDA_TRY(st.out(host.eig, R * (size_t)host.P * (size_t)(host.max_spk + 2), &dev->eig));
+  PLDA_TRY(st.out(host.embed, T * (size_t)host.max_spk, &dev->embed));
+  PLDA_TRY(st.out(host.deg2, T, &dev->deg2));
+  return PLDA_OK;
+}
+}  // namespace
+
+int plda_spectral_plan(plda_handle *h, int64_t N, int32_t k, int32_t out[5]) {
+  return entry(h, "plda_spectral_plan", [&] { return spectral_plan(h, N, k, out); });
+}
+
+int plda_spectral_matrix_dev(plda_handle *h, const float *dscores, const int64_t *block_off, const int64_t *offsets, int64_t R,
+                             const int32_t *p_table, int32_t P, int32_t max_speakers, const int32_t *num_speakers, int32_t max_iters,
+                             int32_t *dlabels, int32_t *dn_clusters, int32_t *dp_used, int32_t *dk_gap, double *deig, double *dembed,
+                             int32_t *ddeg2) {
+  return device_entry(h, "plda_spectral_matrix_dev", [&] {
+    return spectral_matrix_device(h, dscores, block_off,
+                                  spectral_args(offsets, R, p_table, P, max_speakers, num_speakers, max_iters, dlabels, dn_clusters,
+                                                dp_used, dk_gap, deig, dembed, ddeg2));
+  });
+}
+
+int plda_spectral_matrix(plda_handle *h, const float *scores, const int64_t *block_off, const int64_t *offsets, int64_t R,
+                         const int32_t *p_table, int32_t P, int32_t max_speakers, const int32_t *num_speakers, int32_t max_iters,
+                         int32_t *labels, int32_t *n_clusters, int32_t *p_used, int32_t *k_gap, double *eig, double *embed,
+                         int32_t *deg2) {
+  return entry(h, "plda_spectral_matrix", [&]() -> int {
+    const SpectralArgs host = spectral_args(offsets, R, p_table, P, max_speakers, num_speakers, max_iters, labels, n_clusters, p_used,
+                                            k_gap, eig, embed, deg2);
+    if (!scores) return fail(h, PLDA_E_INVAL, "spectral_matrix: scores is NULL");
+    PLDA_TRY(spectral_validate(h, "spectral_matrix", block_off, true, host));
+    PLDA_TRY(set_device(h));
+    const int64_t first = block_off[0], floats = block_off[R] - first;
+    Staged st(h);
+    const float *dS;
+    PLDA_TRY(st.in(scores + first, (size_t)floats, &dS));
+    std::vector<int64_t> rel((size_t)R + 1);
+    for (int64_t r = 0; r <= R; ++r) rel[(size_t)r] = block_off[r] - first;
+    SpectralArgs dev;
+    PLDA_TRY(spectral_stage_outputs(st, host, &dev));
+    return st.finish(spectral_matrix_device(h, dS, rel.data(), dev));
+  });
+}
+
+int plda_score_spectral_dev(plda_handle *h, const double *dX, const int64_t *offsets, int64_t R, const int32_t *p_table, int32_t P,
+                            int32_t max_speakers, const int32_t *num_speakers, int32_t max_iters, int32_t *dlabels,
+                            int32_t *dn_clusters, int32_t *dp_used, int32_t *dk_gap, double *deig, double *dembed, int32_t *ddeg2) {
+  return device_entry(h, "plda_score_spectral_dev", [&] {
+    return score_spectral_device(h, dX, spectral_args(offsets, R, p_table, P, max_speakers, num_speakers, max_iters, dlabels,
+                                                      dn_clusters, dp_used, dk_gap, deig, dembed, ddeg2));
+  });
+}
+
+int plda_score_spectral(plda_handle *h, const double *X, const int64_t *offsets, int64_t R, const int32_t *p_table, int32_t P,
+                        int32_t max_speakers, const int32_t *num_speakers, int32_t max_iters, int32_t *labels, int32_t *n_clusters,
+                        int32_t *p_used, int32_t *k_gap, double *eig, double *embed, int32_t *deg2) {
+  return entry(h, "plda_score_spectral", [&]() -> int {
+    const SpectralArgs host = spectral_args(offsets, R, p_table, P, max_speakers, num_speakers, max_iters, labels, n_clusters, p_used,
+                                            k_gap, eig, embed, deg2);
+    if (!h->fitted) return fail(h, PLDA_E_NOT_FITTED, "score_spectral: model not fitted");
+    if (!X) return fail(h, PLDA_E_INVAL, "score_spectral: X is NULL");
+    PLDA_TRY(spectral_validate(h, "score_spectral", nullptr, false, host));
+    PLDA_TRY(set_device(h));
+    Staged st(h);
+    const double *dX;
+    PLDA_TRY(st.in(X, (size_t)offsets[R] * h->Dout, &dX));
+    SpectralArgs dev;
+    PLDA_TRY(spectral_stage_outputs(st, host, &dev));
+    return st.finish(score_spectral_device(h, dX, dev));
+  });
+}
+
 // ---------------------------------------------------------------- dense scoring in a recording's PCA subspace (dense_pca.hip)
 int plda_dense_pca_plan(plda_handle *h, int64_t N, int32_t D, int32_t out[4]) {
   return entry(h, "plda_dense_pca_plan", [&] { return dense_pca_plan(h, N, D, out); });

@@ -325,12 +325,12 @@ struct plda_handle {
   double ad_tw = 0.0;            // host mirror of the record's total weight
   std::vector<double> ad_pilot;  // host mirror of the pilot (bitwise comparisons of plda_adapt_add_stats)
 
-  // ---- speaker clustering (ahc.hip) ----
-  plda::DevBuf ahc_scratch;      // the N x N fp64 sums of the HBM-class recordings of one launch
-  plda::DevBuf ahc_tab;          // the launch table of a call (one entry per recording)
+  // ---- speaker clustering (ahc.hip, spectral.hip: one call of either runs at a time and carves these anew) ----
+  plda::DevBuf ahc_scratch;      // ahc.hip: the N x N fp64 sums of the HBM-class recordings of one launch; spectral.hip: one eigenproblem's working set, then the kept columns, degrees and best-so-far records of one group (one layout list)
+  plda::DevBuf ahc_tab;          // ahc.hip: the launch table of a call (one entry per recording); spectral.hip: the call's count of non-finite scores, then the launch table of an enqueue (one layout list)
   plda::DevBuf ahc_slot;         // every segment's final slot, between the merge and the label kernel
   plda::DevBuf ahc_stat;         // the call's count of non-finite scores
-  int64_t ahc_scratch_bytes = 0; // PLDA_AHC_SCRATCH_BYTES: the scratch one launch may take and the score slab of the operand form (0: 2 GiB)
+  int64_t ahc_scratch_bytes = 0; // PLDA_AHC_SCRATCH_BYTES: the scratch one launch (spectral.hip: one group) may take and the score slab of the operand forms (0: 2 GiB)
 
   // ---- dense scoring in a recording's PCA subspace (dense_pca.hip) ----
   plda::DevBuf dp_scratch;       // the per-recording arrays of the recordings of one launch group (one layout list per recording)
@@ -553,6 +553,22 @@ int ahc_matrix_device(plda_handle *h, const float *dscores, const int64_t *block
 int score_ahc_device(plda_handle *h, const double *dX, const int64_t *offsets, int64_t R, int has_thr, double thr,
                      const int32_t *minc, int32_t *dlabels, int32_t *dn_clusters, int32_t *dmerge_a, int32_t *dmerge_b,
                      double *dmerge_cost);
+
+// ---- spectral.hip (spectral clustering with auto-tuned pruning; offsets / block_off / p_table / num_spk are HOST arrays) ----
+// The arguments every plda_spectral* / plda_score_spectral* call shares.  Outputs: labels and n_clusters are required, the rest nullable.
+struct SpectralArgs {
+  const int64_t *offsets = nullptr; int64_t R = 0;
+  const int32_t *p_table = nullptr; int P = 0, max_spk = 0;
+  const int32_t *num_spk = nullptr; int max_iters = 0;
+  int32_t *labels = nullptr, *n_clusters = nullptr, *p_used = nullptr, *k_gap = nullptr;
+  double *eig = nullptr, *embed = nullptr;
+  int32_t *deg2 = nullptr;
+};
+int spectral_plan(plda_handle *h, int64_t N, int32_t k, int32_t *out);
+// the argument check of every form (blocks: block_off is checked against the recordings' sizes); pointers are only compared with NULL
+int spectral_validate(plda_handle *h, const char *fn, const int64_t *block_off, bool blocks, const SpectralArgs &a);
+int spectral_matrix_device(plda_handle *h, const float *dscores, const int64_t *block_off, const SpectralArgs &a);
+int score_spectral_device(plda_handle *h, const double *dX, const SpectralArgs &a);
 
 // ---- dense_pca.hip (recording-dependent PCA before dense scoring; offsets / block_off / minc are HOST arrays) ----
 int dense_pca_plan(plda_handle *h, int64_t N, int32_t D, int32_t *out);

@@ -9,6 +9,10 @@ emission model, initialised from the clustering (csrc/vbx.hip; include/plda_hip.
     MPlda.cluster(x, offsets, ...)    raw segment vectors in, labels out (the blocks are scored on the device and dropped)
     score_dense_pca(engine, x, offsets, t)   every recording's block scored in the PCA subspace of its own segment vectors
                                       (Kaldi's --target-energy=t; csrc/dense_pca.hip), one workgroup per recording
+    spectral(engine, blocks, ...)     clusters the same blocks without a threshold: spectral clustering on a pruned
+                                      nearest-neighbour graph, the pruning value by the normalised-maximum-eigengap rule, the
+                                      speaker count from the largest eigengap (csrc/spectral.hip; MPlda.cluster(method="spectral"))
+    spectral_vectors(engine, vecs, offsets, ...)   its operand form; spectral_plan(engine, n, k): its dispatch classes
     ahc_dense_pca(engine, x, offsets, t, ...)   the same blocks clustered and dropped (MPlda.cluster(..., target_energy=t))
     dense_pca_plan(engine, n, d)      the dispatch class a recording of n segments at dimension d takes there
     vbx(engine, y, offsets, labels)   resegments R recordings of projected vectors from initial labels, one workgroup each;
@@ -120,6 +124,99 @@ def ahc_vectors(engine, vecs, offsets, threshold=0.0, num_speakers=None, return_
     N.check(engine._h, engine._lib.plda_score_ahc(engine._h, _p(vecs), _p(offsets), r, has_t, thr, _p(minc), _p(labels), _p(ncl),
                                                   _p(ma), _p(mb), _p(mc)))
     return (labels, ncl, (ma, mb, mc)) if return_merges else (labels, ncl)
+
+
+# ------------------------------------------------------------------------------------------- spectral clustering
+SPECTRAL_MAX = 2048         # PLDA_SPECTRAL_MAX
+SPECTRAL_MAX_SPK = 64       # PLDA_SPECTRAL_MAX_SPK
+SPECTRAL_MAX_P = 16         # PLDA_SPECTRAL_MAX_P
+P_FRACTIONS = (0.03, 0.05, 0.08, 0.12, 0.16, 0.2, 0.25, 0.3)
+
+
+def spectral_plan(engine, n, k=1):
+    """{"select_class": keys per lane of the neighbour selection for n segments, "select_max": the largest n of that class,
+    "kmeans_cls": 0 (embedding in LDS) or 1 (in scratch) for k columns, "kmeans_lds_max": the largest n of class 0 at this k,
+    "scratch_bytes": the working set of one eigenproblem of order n}."""
+    out = (C.c_int32 * 5)()
+    N.check(engine._h, engine._lib.plda_spectral_plan(engine._h, int(n), int(k), out))
+    return {"select_class": int(out[0]), "select_max": int(out[1]), "kmeans_cls": int(out[2]), "kmeans_lds_max": int(out[3]),
+            "scratch_bytes": int(out[4])}
+
+
+def spectral_args(offsets, p=None, p_fractions=P_FRACTIONS, max_speakers=16, num_speakers=None, max_iters=20):
+    """(p_table int32 [R, P], num_speakers int32 [R] or None) of the C ABI from the Python arguments, checked before any device
+    work.  p=None: p = min(N - 1, max(2, ceil(f N))) per recording for every f of p_fractions (1 at least); an int: that value
+    for every recording; a list: those values for every recording; an [R, P] array: as given."""
+    offsets = np.asarray(offsets, np.int64)
+    if offsets.ndim != 1 or len(offsets) < 2:
+        raise ValueError("offsets must hold R + 1 >= 2 entries")
+    r = len(offsets) - 1
+    sizes = np.diff(offsets)
+    if offsets[0] != 0 or (sizes < 1).any() or (sizes > SPECTRAL_MAX).any():
+        raise ValueError("every recording must hold 1 ... %d segments (offsets must ascend from 0)" % SPECTRAL_MAX)
+    if isinstance(max_speakers, bool) or int(max_speakers) != max_speakers or not 1 <= max_speakers <= SPECTRAL_MAX_SPK:
+        raise ValueError("max_speakers must be an integer in 1 ... %d" % SPECTRAL_MAX_SPK)
+    if isinstance(max_iters, bool) or int(max_iters) != max_iters or not 1 <= max_iters <= 1000:
+        raise ValueError("max_iters must be an integer in 1 ... 1000")
+    if p is None:
+        f = np.asarray(p_fractions, np.float64)
+        if f.ndim != 1 or not 1 <= len(f) <= SPECTRAL_MAX_P or not (np.isfinite(f).all() and (f > 0).all()):
+            raise ValueError("p_fractions must hold 1 ... %d positive fractions" % SPECTRAL_MAX_P)
+        table = np.maximum(1, np.minimum(sizes[:, None] - 1, np.maximum(2, np.ceil(f[None, :] * sizes[:, None]).astype(np.int64))))
+    else:
+        table = np.asarray(p)
+        if table.dtype.kind not in "iu":
+            raise ValueError("p must be an integer, a list of integers or an [R, P] integer array")
+        table = np.broadcast_to(table.reshape(1, -1) if table.ndim < 2 else table, (r, table.shape[-1] if table.ndim else 1))
+        if not 1 <= table.shape[1] <= SPECTRAL_MAX_P or (table < 1).any() or (table > 0x7fffffff).any():
+            raise ValueError("p must hold 1 ... %d values >= 1 per recording" % SPECTRAL_MAX_P)
+    ns = None
+    if num_speakers is not None:
+        ns = np.ascontiguousarray(np.broadcast_to(np.asarray(num_speakers), (r,)), np.int32)
+        if (ns < 0).any() or (ns > max_speakers).any():
+            raise ValueError("num_speakers must lie in 0 ... max_speakers = %d (0: the eigengap's count)" % max_speakers)
+    return np.ascontiguousarray(table, np.int32), ns
+
+
+def _spectral_call(engine, fn, head, offsets, table, ns, max_speakers, max_iters, return_info):
+    r, t, ms = len(offsets) - 1, int(offsets[-1]), int(max_speakers)
+    labels, ncl = np.empty(t, np.int32), np.empty(r, np.int32)
+    pu = kg = eig = emb = d2 = None
+    if return_info:
+        pu, kg, d2 = np.empty(r, np.int32), np.empty(r, np.int32), np.empty(t, np.int32)
+        eig, emb = np.empty((r, table.shape[1], ms + 2), np.float64), np.empty((t, ms), np.float64)
+    N.check(engine._h, fn(engine._h, *head, _p(offsets), r, _p(table), table.shape[1], ms, _p(ns), int(max_iters), _p(labels), _p(ncl),
+                          _p(pu), _p(kg), _p(eig), _p(emb), _p(d2)))
+    if not return_info:
+        return labels, ncl
+    return labels, ncl, {"p_used": pu, "k_gap": kg, "eig": eig, "embed": emb, "deg2": d2, "p_table": table}
+
+
+def spectral(engine, blocks, p=None, p_fractions=P_FRACTIONS, max_speakers=16, num_speakers=None, max_iters=20, return_info=False):
+    """Cluster the recordings whose square fp32 score blocks are `blocks` by spectral clustering with auto-tuned pruning
+    (include/plda_hip.h, "spectral clustering with auto-tuned pruning"): no threshold, the speaker count from the largest
+    eigengap (at most max_speakers) unless num_speakers (an int or one per recording; 0: the eigengap's) gives it.  Returns
+    (labels int32 [T], n_clusters int32 [R][, info]): labels 0 .. per recording by first occurrence; info = {"p_used", "k_gap"
+    int32 [R], "eig" [R, P, max_speakers + 2], "embed" [T, max_speakers], "deg2" int32 [T], "p_table" int32 [R, P]}."""
+    scores, block_off, offsets = pack(blocks)
+    table, ns = spectral_args(offsets, p, p_fractions, max_speakers, num_speakers, max_iters)
+    return _spectral_call(engine, engine._lib.plda_spectral_matrix, (_p(scores), _p(block_off)), offsets, table, ns, max_speakers,
+                          max_iters, return_info)
+
+
+def spectral_vectors(engine, vecs, offsets, p=None, p_fractions=P_FRACTIONS, max_speakers=16, num_speakers=None, max_iters=20,
+                     return_info=False):
+    """The operand form: `vecs` [T, Dout] are already-transformed segment vectors (num_examples = 1); every recording's block
+    is scored on the device exactly as score_matrix_dev would write it, clustered and dropped."""
+    vecs = np.ascontiguousarray(vecs, np.float64)
+    offsets = np.ascontiguousarray(offsets, np.int64)
+    table, ns = spectral_args(offsets, p, p_fractions, max_speakers, num_speakers, max_iters)
+    if vecs.ndim != 2 or vecs.shape[0] != int(offsets[-1]):
+        raise ValueError("vecs must be [offsets[-1], Dout], got %r" % (vecs.shape,))
+    dout, _ = engine.dims()
+    if vecs.shape[1] != dout:
+        raise ValueError("vecs have dimension %d, the model's output dimension is %d" % (vecs.shape[1], dout))
+    return _spectral_call(engine, engine._lib.plda_score_spectral, (_p(vecs),), offsets, table, ns, max_speakers, max_iters, return_info)
 
 
 # ------------------------------------------------------------------------------------------- dense scoring behind a PCA

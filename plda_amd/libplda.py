@@ -549,16 +549,38 @@ class MPlda(object):
         return out
 
     # ----------------------------------------------------------------- speaker clustering (csrc/ahc.hip)
-    def cluster(self, x, offsets, threshold=0.0, num_speakers=None, return_merges=False, target_energy=None):
+    def cluster(self, x, offsets, threshold=0.0, num_speakers=None, return_merges=False, target_energy=None, method="ahc", p=None,
+                p_fractions=None, max_speakers=16, max_iters=20, return_info=False):
         """Cluster the segments of R recordings (diarisation; plda_amd/diarize.py): x [T, Din] raw segment vectors, recording
         r owning rows offsets[r] .. offsets[r+1].  Every row is transformed with num_examples = 1, every recording's segments
         are scored against each other on the device and merged bottom-up (average linkage) while the best pair's average
         score is at least `threshold` (None: no threshold) and more than `num_speakers` (an int or one per recording; None: 1)
         clusters are left.  target_energy=t (0 < t < 1; Kaldi's --target-energy): every recording is scored in the PCA subspace
         of its own segment vectors instead (score_dense).  Returns (labels int32 [T], n_clusters int32 [R][, (merge_a, merge_b,
-        merge_cost)])."""
+        merge_cost)]).
+        method="spectral": spectral clustering with auto-tuned pruning instead (diarize.spectral: no threshold; p, p_fractions,
+        max_speakers, max_iters and return_info as there; num_speakers None: the eigengap's count).  A non-default threshold or
+        return_merges=True is a ValueError; with target_energy the blocks of score_dense are clustered.  Returns (labels,
+        n_clusters[, info])."""
         from . import diarize
         offsets = np.ascontiguousarray(offsets, np.int64)
+        if method == "spectral":
+            if return_merges or not (isinstance(threshold, (int, float)) and not isinstance(threshold, bool) and threshold == 0.0):
+                raise ValueError('method="spectral" has no threshold and no merge record')
+            fr = diarize.P_FRACTIONS if p_fractions is None else p_fractions
+            diarize.spectral_args(offsets, p, fr, max_speakers, num_speakers, max_iters)       # (before any device work)
+            X = self._rows(x, "Segment vectors")
+            if X.shape[0] != int(offsets[-1]):
+                raise ValueError("offsets must hold R + 1 >= 2 entries ending at the number of rows of x")
+            if target_energy is not None:
+                return diarize.spectral(self, diarize.score_dense_pca(self, X, offsets, target_energy), p, fr, max_speakers, num_speakers,
+                                        max_iters, return_info)
+            return diarize.spectral_vectors(self, self.transform_array(X, 1), offsets, p, fr, max_speakers, num_speakers, max_iters,
+                                            return_info)
+        if method != "ahc":
+            raise ValueError('method must be "ahc" or "spectral", got %r' % (method,))
+        if p is not None or p_fractions is not None or max_speakers != 16 or max_iters != 20 or return_info:
+            raise ValueError('p, p_fractions, max_speakers, max_iters and return_info belong to method="spectral"')
         diarize.stop_args(offsets, threshold, num_speakers)     # (threshold=None without num_speakers: ValueError, before any work)
         X = self._rows(x, "Segment vectors")
         if offsets.ndim != 1 or len(offsets) < 2 or X.shape[0] != int(offsets[-1]):
@@ -605,13 +627,18 @@ class MPlda(object):
         return diarize.vbx(self, self._project(X), offsets, labels, None, Fa, Fb, loop_prob, init_smoothing, max_iters, epsilon,
                            return_posteriors, return_second)
 
-    def diarize(self, x, offsets, threshold=0.0, num_speakers=None, target_energy=None, overlap=None, min_posterior=None, **vbx):
+    def diarize(self, x, offsets, threshold=0.0, num_speakers=None, target_energy=None, overlap=None, min_posterior=None, method="ahc",
+                p=None, p_fractions=None, max_speakers=16, **vbx):
         """cluster(x, offsets, threshold, num_speakers), then resegment(x, offsets, its labels, **vbx).  target_energy goes to
         the clustering only: VBx keeps working on the full model.  With overlap (a per-segment bool mask) or min_posterior the
-        return is (labels, n_clusters, labels2): the second speaker where diarize.apply_overlap keeps it, -1 elsewhere."""
+        return is (labels, n_clusters, labels2): the second speaker where diarize.apply_overlap keeps it, -1 elsewhere.
+        method="spectral" (with p, p_fractions, max_speakers as cluster takes them): the spectral clustering's labels start VBx."""
         if (overlap is not None or min_posterior is not None) and (vbx.get("return_second") or vbx.get("return_posteriors")):
             raise ValueError("overlap / min_posterior return (labels, n_clusters, labels2): call resegment for the posteriors")
-        if target_energy is None:
+        if method != "ahc" or p is not None or p_fractions is not None or max_speakers != 16:
+            labels, _ = self.cluster(x, offsets, threshold, num_speakers, target_energy=target_energy, method=method, p=p,
+                                     p_fractions=p_fractions, max_speakers=max_speakers)
+        elif target_energy is None:
             labels, _ = self.cluster(x, offsets, threshold, num_speakers)
         else:
             labels, _ = self.cluster(x, offsets, threshold, num_speakers, target_energy=target_energy)
@@ -657,6 +684,23 @@ class MPlda(object):
             self._h, _vp(dX), _ptr(offsets), len(offsets) - 1, int(has_threshold), float(threshold),
             _ptr(min_clusters) if min_clusters is not None else None, _vp(dlabels), _vp(dn_clusters), _vp(dmerge_a), _vp(dmerge_b),
             _vp(dmerge_cost)))
+
+    def spectral_matrix_dev(self, dscores, block_off, offsets, p_table, max_speakers, num_speakers, max_iters, dlabels, dn_clusters,
+                            dp_used=None, dk_gap=None, deig=None, dembed=None, ddeg2=None):
+        """Spectral clustering of packed HBM-resident fp32 score blocks (raw device addresses; plda_spectral_matrix_dev);
+        block_off, offsets (int64), p_table (int32 [R, P]) and num_speakers (int32 [R] or None) are HOST arrays."""
+        self._ck(self._lib.plda_spectral_matrix_dev(
+            self._h, _vp(dscores), _ptr(block_off), _ptr(offsets), len(offsets) - 1, _ptr(p_table), p_table.shape[1], int(max_speakers),
+            _ptr(num_speakers) if num_speakers is not None else None, int(max_iters), _vp(dlabels), _vp(dn_clusters), _vp(dp_used),
+            _vp(dk_gap), _vp(deig), _vp(dembed), _vp(ddeg2)))
+
+    def score_spectral_dev(self, dX, offsets, p_table, max_speakers, num_speakers, max_iters, dlabels, dn_clusters, dp_used=None,
+                           dk_gap=None, deig=None, dembed=None, ddeg2=None):
+        """The same on HBM-resident transformed segment vectors dX [T, Dout]: the blocks are scored and dropped."""
+        self._ck(self._lib.plda_score_spectral_dev(
+            self._h, _vp(dX), _ptr(offsets), len(offsets) - 1, _ptr(p_table), p_table.shape[1], int(max_speakers),
+            _ptr(num_speakers) if num_speakers is not None else None, int(max_iters), _vp(dlabels), _vp(dn_clusters), _vp(dp_used),
+            _vp(dk_gap), _vp(deig), _vp(dembed), _vp(ddeg2)))
 
     def score_dense_pca_dev(self, dX, offsets, target_energy, dscores, block_off, ddims=None, deig=None):
         """plda_score_dense_pca_dev on HBM-resident rows dX [T, Din] (raw device addresses): block r row-major at dscores +
