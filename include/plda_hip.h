@@ -654,8 +654,8 @@ int plda_affine_map_dev(plda_handle *h, const float *dscores, int64_t ld, int64_
  * and fit calls synchronise the handle's stream, as the calibration's do.
  *
  * OUT OF SCOPE, each on purpose: an operand form (the systems are different models; the caller holds their matrices); the
- * row-sharded form (the record adds across shards as the calibration's does -- unbuilt there too); quality measures / side
- * information; regularisation; minCllr. ---- */
+ * row-sharded form (the record adds across shards as the calibration's does -- unbuilt there too); regularisation; minCllr.
+ * (Quality measures / side information and this model's own operand form: the next section.) ---- */
 #define PLDA_FUSION_MAX_SYSTEMS 8
 typedef struct plda_fusion_sums {
   double L;
@@ -690,6 +690,74 @@ int plda_fusion_fit_lists(plda_handle *h, int32_t n_systems, const float *const 
 int plda_fusion_map_dev(plda_handle *h, int32_t n_systems, const float *const *dscores, const int64_t *ld, int64_t M, int64_t Nt,
                         const double *a, double b, float *dout, int64_t ld_out);
 int plda_fusion_newton(const plda_fusion_record *record, double prior, double *F, double *d, double *lambda2);
+
+/* ---- quality-aware calibration: side-information terms in the fusion (K25; csrc/fusion_side.hip; the quality measure
+ * functions -- duration, embedding norm, the AS-norm cohort mean -- put in front of reported verification numbers since
+ * VoxSRC-20; the project's own extension like the fusion above, pinned by tests/fusion_side_model.py).
+ *
+ * A call has K >= 1 SYSTEMS (fp32 matrices, exactly as plda_fusion_*_matrices_dev takes them) and Q >= 0 SIDES with
+ * K + Q <= PLDA_FUSION_MAX_SYSTEMS.  Side q is {op, enrol[M], test[Nt]}: two fp32 DEVICE vectors and an op code; its value
+ * for trial (i, j) is ONE IEEE fp32 operation on e = enrol[i], t = test[j]:
+ *     PLDA_SIDE_MIN      e < t ? e : t          PLDA_SIDE_MAX   e > t ? e : t          PLDA_SIDE_SUM   e + t
+ *     PLDA_SIDE_ABSDIFF  fabsf(e - t)           PLDA_SIDE_PROD  e * t
+ * Ties and signed zeros follow the written comparison (MIN of (+0, -0) is -0, the `t`; with a NaN operand the comparison is false, so MIN
+ * and MAX return t, whatever it is; the other three return NaN).  A one-sided quality is SUM with a zero vector on the other side.  The value never exists
+ * in memory: the kernels form it in registers, so a side costs M + Nt floats where a materialised "system" costs M * Nt.
+ *
+ * FEATURE VECTOR phi = (1, s_0 .. s_{K-1}, q_0 .. q_{Q-1}); the CHAIN is the fusion's over these K + Q fp32 values in that
+ * order with weights a[K + Q]; the RECORD is an unchanged plda_fusion_record with n_systems = K + Q (smin / smax of a side
+ * are the extremes of its values over all trials; a trial whose side value is non-finite counts in `nonfinite` like a
+ * non-finite score); the FIT is the fusion's, and plda_fusion_newton takes these records as they are.
+ *
+ * THE CONTRACT: a side pass, fit or map is BIT-IDENTICAL to plda_fusion_pass_matrices_dev / _fit_matrices_dev / _map_dev
+ * over K + Q matrices in which every side has been materialised with the fp32 operation above, at any pitch or alignment
+ * of those matrices: same grid, same visiting order, same account (the accuracy statement of the fusion holds unchanged).
+ * Q = 0 is accepted and IS the existing path.
+ *
+ * OPERAND FORM (plda_score_fusion_side_*_dev): system 0 is this model's own score matrix -- the arguments of
+ * plda_score_calib_fit_dev -- produced slab by slab and never held; K = 1, a[1 + Q].  Its record sums across slabs (one
+ * launch per slab, the partial records of all slabs reduced together in slab order), so it is NOT bit-identical to the
+ * matrix form: integers are equal, sums agree within the fusion's band, and it is bit-identical from run to run.
+ *
+ * REFUSALS, PLDA_E_INVAL with a text naming the argument or side: n_systems < 1 or n_systems + n_sides > 8 (n_sides < 0); a
+ * NULL `sides` with n_sides > 0; an op outside 0 .. 4; a NULL vector.  A side with smin == smax is refused before any Newton
+ * step, by name ("side q"), like a constant system; linearly dependent sides (the same side twice; MIN, MAX and SUM of one
+ * pair of vectors) meet the fusion's Cholesky-pivot refusal, whose text names the side.
+ *
+ * CONVENTIONS: `sides` is a HOST array of n_sides entries, like the pointer arrays of the fusion; the vectors it names are in
+ * HBM.  The map may run in place over one of the K matrices under the fusion's rule; columns [Nt, ld_out) stay untouched.
+ *
+ * OUT OF SCOPE, each on purpose: regularisation; non-linear quality maps (a side enters the chain linearly; log-duration
+ * and the like are the caller's transform of the vectors); a row-sharded form; quality terms in the LIST forms -- there the
+ * caller evaluates the side per listed trial and passes it as one more list, which the list forms already take. ---- */
+#define PLDA_SIDE_MIN 0
+#define PLDA_SIDE_MAX 1
+#define PLDA_SIDE_SUM 2
+#define PLDA_SIDE_ABSDIFF 3
+#define PLDA_SIDE_PROD 4
+typedef struct plda_fusion_side {
+  const float *enrol, *test;         /* device vectors [M], [Nt] */
+  int32_t op, reserved;              /* PLDA_SIDE_*; reserved = 0 */
+} plda_fusion_side;
+int plda_fusion_side_pass_dev(plda_handle *h, int32_t n_systems, const float *const *dscores, const int64_t *ld, int32_t n_sides,
+                              const plda_fusion_side *sides, int64_t M, int64_t Nt, const int64_t *denrol_spk,
+                              const int64_t *dtest_spk, const double *a, double c, double theta, plda_fusion_record *out_record);
+int plda_fusion_side_fit_dev(plda_handle *h, int32_t n_systems, const float *const *dscores, const int64_t *ld, int32_t n_sides,
+                             const plda_fusion_side *sides, int64_t M, int64_t Nt, const int64_t *denrol_spk,
+                             const int64_t *dtest_spk, double prior, double tol, int32_t max_iter, plda_fusion_fit *out_fit);
+int plda_fusion_side_map_dev(plda_handle *h, int32_t n_systems, const float *const *dscores, const int64_t *ld, int32_t n_sides,
+                             const plda_fusion_side *sides, int64_t M, int64_t Nt, const double *a, double b, float *dout,
+                             int64_t ld_out);
+int plda_score_fusion_side_pass_dev(plda_handle *h, const double *dU, const int32_t *dn_enrol, int32_t n_uniform, int64_t M,
+                                    const double *dV, int64_t Nt, const double *dzmean, const double *dzstd,
+                                    const int64_t *denrol_spk, const int64_t *dtest_spk, int32_t n_sides,
+                                    const plda_fusion_side *sides, const double *a, double c, double theta,
+                                    plda_fusion_record *out_record);
+int plda_score_fusion_side_fit_dev(plda_handle *h, const double *dU, const int32_t *dn_enrol, int32_t n_uniform, int64_t M,
+                                   const double *dV, int64_t Nt, const double *dzmean, const double *dzstd,
+                                   const int64_t *denrol_spk, const int64_t *dtest_spk, int32_t n_sides,
+                                   const plda_fusion_side *sides, double prior, double tol, int32_t max_iter,
+                                   plda_fusion_fit *out_fit);
 
 /* ---- exact minimum detection cost (minDCF; NIST SRE min_Cprimary, VoxCeleb's minDCF) at up to 8 operating points,
  * without sorting (csrc/dcf.hip; the project's own extension like the calibration above: tests/mindcf_model.py pins it).

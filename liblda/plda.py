@@ -47,9 +47,17 @@ class PLDA(object):
         (prior-weighted logistic regression); returns a plda_amd.fusion.Fusion (not stored, not saved)."""
         return self._instance.fuse(enrol, test, test_speaker, others, prior, znorm, cohort, top_k)
 
-    def score_matrix_fused(self, enrol, test, others, fusion, znorm=True, cohort=None, top_k=None):
-        """float32 [M, Nt]: the fused value of `fusion` over this model's matrix and `others`."""
-        return self._instance.score_matrix_fused(enrol, test, others, fusion, znorm, cohort, top_k)
+    def score_matrix_fused(self, enrol, test, others, fusion, znorm=True, cohort=None, top_k=None, quality=None):
+        """float32 [M, Nt]: the fused value of `fusion` over this model's matrix and `others` (and, with `quality`, the
+        side-information terms of a `calibrate_quality` result)."""
+        return self._instance.score_matrix_fused(enrol, test, others, fusion, znorm, cohort, top_k, quality)
+
+    def calibrate_quality(self, enrol, test, test_speaker, quality, others=(), prior=0.5, znorm=True, cohort=None, top_k=None):
+        """Quality-aware calibration: the fusion of this model's score (and `others`) with side-information terms
+        `quality` = ((op, enrol_values, test_values), ...), op one of "min" | "max" | "sum" | "absdiff" | "prod" of the
+        row's and the column's quality (duration, embedding norm, cohort mean ...), formed on the device without ever
+        holding their matrices; returns a plda_amd.fusion.QualityFusion (not stored, not saved)."""
+        return self._instance.calibrate_quality(enrol, test, test_speaker, quality, others, prior, znorm, cohort, top_k)
 
     def min_dcf(self, enrol, test, test_speaker, points=((0.01, 1.0, 1.0),), znorm=True, cohort=None, top_k=None, calibrate=False):
         """The exact minimum detection cost of the trials between two transform() results at up to 8 operating points

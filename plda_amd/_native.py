@@ -141,6 +141,11 @@ SIGNATURES = {
     "plda_fusion_fit_lists": (C.c_int, [_vp, _i32, _vp, _i64, _vp, _i64, _f64, _f64, _i32, _vp]),
     "plda_fusion_map_dev": (C.c_int, [_vp, _i32, _vp, _vp, _i64, _i64, _vp, _f64, _vp, _i64]),
     "plda_fusion_newton": (C.c_int, [_vp, _f64, _vp, _vp, _vp]),
+    "plda_fusion_side_pass_dev": (C.c_int, [_vp, _i32, _vp, _vp, _i32, _vp, _i64, _i64, _vp, _vp, _vp, _f64, _f64, _vp]),
+    "plda_fusion_side_fit_dev": (C.c_int, [_vp, _i32, _vp, _vp, _i32, _vp, _i64, _i64, _vp, _vp, _f64, _f64, _i32, _vp]),
+    "plda_fusion_side_map_dev": (C.c_int, [_vp, _i32, _vp, _vp, _i32, _vp, _i64, _i64, _vp, _f64, _vp, _i64]),
+    "plda_score_fusion_side_pass_dev": (C.c_int, [_vp, _vp, _vp, _i32, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _f64, _f64, _vp]),
+    "plda_score_fusion_side_fit_dev": (C.c_int, [_vp, _vp, _vp, _i32, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i32, _vp, _f64, _f64, _i32, _vp]),
     "plda_adapt_reset": (C.c_int, [_vp]),
     "plda_adapt_accumulate_dev": (C.c_int, [_vp, _vp, _i64, _i32, _vp]),
     "plda_adapt_accumulate": (C.c_int, [_vp, _vp, _i64, _i32, _vp]),

@@ -1940,6 +1940,53 @@ int plda_fusion_newton(const plda_fusion_record *record, double prior, double *F
   return guarded(nullptr, "plda_fusion_newton", [&]() -> int { return fusion_newton(record, prior, F, d, lambda2); });
 }
 
+// ---------------------------------------------------------------- quality-aware calibration (fusion.hip, fusion_side.hip)
+int plda_fusion_side_pass_dev(plda_handle *h, int32_t n_systems, const float *const *dscores, const int64_t *ld, int32_t n_sides,
+                              const plda_fusion_side *sides, int64_t M, int64_t Nt, const int64_t *denrol_spk,
+                              const int64_t *dtest_spk, const double *a, double c, double theta, plda_fusion_record *out_record) {
+  return device_entry(h, "plda_fusion_side_pass_dev", [&] {
+    return fusion_side_pass_device(h, n_systems, dscores, ld, n_sides, sides, M, Nt, denrol_spk, dtest_spk, a, c, theta, out_record);
+  });
+}
+
+int plda_fusion_side_fit_dev(plda_handle *h, int32_t n_systems, const float *const *dscores, const int64_t *ld, int32_t n_sides,
+                             const plda_fusion_side *sides, int64_t M, int64_t Nt, const int64_t *denrol_spk,
+                             const int64_t *dtest_spk, double prior, double tol, int32_t max_iter, plda_fusion_fit *out_fit) {
+  return device_entry(h, "plda_fusion_side_fit_dev", [&] {
+    return fusion_side_fit_device(h, n_systems, dscores, ld, n_sides, sides, M, Nt, denrol_spk, dtest_spk, prior, tol, max_iter, out_fit);
+  });
+}
+
+int plda_fusion_side_map_dev(plda_handle *h, int32_t n_systems, const float *const *dscores, const int64_t *ld, int32_t n_sides,
+                             const plda_fusion_side *sides, int64_t M, int64_t Nt, const double *a, double b, float *dout,
+                             int64_t ld_out) {
+  return device_entry(h, "plda_fusion_side_map_dev", [&] {
+    return fusion_side_map_device(h, n_systems, dscores, ld, n_sides, sides, M, Nt, a, b, dout, ld_out);
+  });
+}
+
+int plda_score_fusion_side_pass_dev(plda_handle *h, const double *dU, const int32_t *dn_enrol, int32_t n_uniform, int64_t M,
+                                    const double *dV, int64_t Nt, const double *dzmean, const double *dzstd,
+                                    const int64_t *denrol_spk, const int64_t *dtest_spk, int32_t n_sides,
+                                    const plda_fusion_side *sides, const double *a, double c, double theta,
+                                    plda_fusion_record *out_record) {
+  return device_entry(h, "plda_score_fusion_side_pass_dev", [&] {
+    return score_fusion_side_pass_device(h, dU, dn_enrol, n_uniform, M, dV, Nt, dzmean, dzstd, denrol_spk, dtest_spk, n_sides, sides, a, c,
+                                         theta, out_record);
+  });
+}
+
+int plda_score_fusion_side_fit_dev(plda_handle *h, const double *dU, const int32_t *dn_enrol, int32_t n_uniform, int64_t M,
+                                   const double *dV, int64_t Nt, const double *dzmean, const double *dzstd,
+                                   const int64_t *denrol_spk, const int64_t *dtest_spk, int32_t n_sides,
+                                   const plda_fusion_side *sides, double prior, double tol, int32_t max_iter,
+                                   plda_fusion_fit *out_fit) {
+  return device_entry(h, "plda_score_fusion_side_fit_dev", [&] {
+    return score_fusion_side_fit_device(h, dU, dn_enrol, n_uniform, M, dV, Nt, dzmean, dzstd, denrol_spk, dtest_spk, n_sides, sides, prior,
+                                        tol, max_iter, out_fit);
+  });
+}
+
 // ---------------------------------------------------------------- speaker clustering (ahc.hip)
 int plda_ahc_plan(plda_handle *h, int64_t N, int32_t out[3]) {
   return entry(h, "plda_ahc_plan", [&] { return ahc_plan(h, N, out); });

@@ -34,6 +34,11 @@
 // Resources (hipcc --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage with this file's flags, plda_amd/build.py):
 // the table at fusion_pass_strip_kernel below -- no scratch and no spill in any instantiation, the K = 8 labelled pass in 244
 // registers (two waves per SIMD).  Speed: scripts/fusion_bench.py writes profiles/fusion_*.json.
+//
+// SHARED WITH fusion_side.hip (K matrices + Q side-information terms formed in registers, K25): that file includes THIS one
+// with PLDA_FUSION_SHARED_ONLY defined and so gets the argument record, the accumulators, fusion_account and
+// fusion_block_store -- everything up to the first #ifndef below -- and none of the kernels or host drivers.  One text, two
+// translation units compiled with the same flags: that is what makes a side pass bit-identical to a matrix pass.
 #include "trial_source.hpp"
 
 #include <algorithm>
@@ -233,6 +238,23 @@ __device__ __forceinline__ void fusion_block_store(const FusionAcc<K> &A, int cn
 }
 
 template <int K> constexpr int fusion_rows_in_flight() { return K <= 2 ? 4 : K <= 4 ? 2 : 1; }
+
+// ---- fusion_side.hip: K matrices followed by Q sides, T = K + Q features.  Feature slot k < K is a matrix exactly as in
+// FusionArgs; slot k >= K is a side: P.s[k] is its TEST vector and P.ld[k] = 0 (a "matrix" of pitch 0, so the strip walk's
+// address and alignment arithmetic is the matrix kernel's own), enrol[k] its ENROL vector (already offset to the first row of
+// the launch), op[k] its PLDA_SIDE_* code.  P stays the first member: the kernels re-read it at offset 0 of the
+// kernel-argument segment (see fusion_pass_strip_kernel).
+struct FusionSideArgs {
+  FusionArgs P;
+  const float *enrol[FUSION_KMAX];
+  int32_t op[FUSION_KMAX];
+  int32_t K, reserved;
+};
+void fusion_side_launch_strip(plda_handle *h, const FusionSideArgs &S, int T, int64_t rows, int64_t Nt, const int64_t *espk,
+                              const int64_t *tspk, int64_t blocks, int64_t rows_per_wg, plda_fusion_record *part);
+void fusion_side_launch_map(plda_handle *h, const FusionSideArgs &S, int T, int64_t M, int64_t Nt, float *out, int64_t ld_out);
+
+#ifndef PLDA_FUSION_SHARED_ONLY
 
 // The labelled pass over K matrices: block b writes part[b].  Traversal and labelling of calib_pass_strip_kernel.
 // Resources on gfx950 (kernel-resource-usage; VGPRs per lane, no AGPRs; scratch 0, SGPR and VGPR spills 0 in every row):
@@ -467,7 +489,10 @@ __global__ __launch_bounds__(256) void fusion_map_kernel(const FusionArgs P, int
   }
 }
 
+#endif  // PLDA_FUSION_SHARED_ONLY (the kernels)
+
 // ------------------------------------------------------------------------------------ host drivers
+#ifndef PLDA_FUSION_SHARED_ONLY
 static int64_t fusion_strip_blocks(int64_t rows, int64_t Nt, int64_t *rows_per_wg) {
   const int64_t strips = ceil_div(Nt, (int64_t)FUSION_STRIP);
   const int64_t slices = std::max<int64_t>(1, std::min<int64_t>(rows, FUSION_MAX_BLOCKS / strips));
@@ -476,19 +501,25 @@ static int64_t fusion_strip_blocks(int64_t rows, int64_t Nt, int64_t *rows_per_w
 }
 static int64_t fusion_list_blocks(int64_t n) { return std::min<int64_t>(ceil_div(n, 256), FUSION_MAX_BLOCKS); }
 
-// the labelled trials of a fusion call: K matrices under one pair of speaker-id arrays, or K target + K non-target lists
+// the labelled trials of a fusion call: K matrices under one pair of speaker-id arrays, or K target + K non-target lists.
+// With sides (K25, fusion_side.hip): K counts every FEATURE, the first `nsys` of them matrices and the rest sides -- slot
+// k >= nsys holds the side's test vector in s[k] (pitch 0), its enrol vector in enrol[k] and its op in op[k].  Operand form:
+// `slabs` produces system 0 one row slab at a time (s[0] / ld[0] are then filled per slab).
 struct FusionSource {
-  int K = 0;
+  int K = 0, nsys = 0;
   bool lists = false;
   const float *s[FUSION_KMAX] = {}, *neg[FUSION_KMAX] = {};   // matrices, or the target lists; the non-target lists
   int64_t ld[FUSION_KMAX] = {};
   int64_t M = 0, Nt = 0;                                       // lists: np, nn
   const int64_t *espk = nullptr, *tspk = nullptr;
+  const float *enrol[FUSION_KMAX] = {};
+  int32_t op[FUSION_KMAX] = {};
+  const TrialSource *slabs = nullptr;
 };
 
-template <int K> static void fusion_launch_strip(plda_handle *h, const FusionArgs &P, const FusionSource &src, int64_t blocks,
-                                                 int64_t rpw, plda_fusion_record *part) {
-  fusion_pass_strip_kernel<K><<<(unsigned)blocks, 256, 0, h->stream>>>(P, src.M, src.Nt, src.espk, src.tspk, rpw, part);
+template <int K> static void fusion_launch_strip(plda_handle *h, const FusionArgs &P, int64_t rows, int64_t Nt, const int64_t *espk,
+                                                 const int64_t *tspk, int64_t blocks, int64_t rpw, plda_fusion_record *part) {
+  fusion_pass_strip_kernel<K><<<(unsigned)blocks, 256, 0, h->stream>>>(P, rows, Nt, espk, tspk, rpw, part);
 }
 template <int K> static void fusion_launch_list(plda_handle *h, const FusionArgs &P, int64_t n, int cls, int64_t blocks,
                                                 plda_fusion_record *part) {
@@ -505,18 +536,45 @@ template <int K> static void fusion_launch_map(plda_handle *h, const FusionArgs 
     case 5: CALL(5); break; case 6: CALL(6); break; case 7: CALL(7); break; default: CALL(8); break; \
   }
 
+static void fusion_dispatch_strip(plda_handle *h, int K, const FusionArgs &P, int64_t rows, int64_t Nt, const int64_t *espk,
+                                  const int64_t *tspk, int64_t blocks, int64_t rpw, plda_fusion_record *part) {
+#define FUSION_CALL(KK) fusion_launch_strip<KK>(h, P, rows, Nt, espk, tspk, blocks, rpw, part)
+  FUSION_DISPATCH(K, FUSION_CALL)
+#undef FUSION_CALL
+}
+
+// the side half of the kernel arguments (slots nsys .. K), with the enrol vectors offset to row r0 of the call
+static FusionSideArgs fusion_side_args(const FusionArgs &P, const FusionSource &src, int64_t r0) {
+  FusionSideArgs S = {};
+  S.P = P;
+  S.K = src.nsys;
+  for (int k = src.nsys; k < src.K; ++k) { S.enrol[k] = src.enrol[k] + r0; S.op[k] = src.op[k]; }
+  return S;
+}
+
 // One pass over `src` at (a, c, theta) -> *rec (host); synchronises the stream.  A non-finite score, or a class without
-// trials, is PLDA_E_INVAL (the record is written all the same).
+// trials, is PLDA_E_INVAL (the record is written all the same).  A matrix call is one piece on the grid of its shape; the
+// operand form is one piece per slab (trial_source.hpp), the partials of all slabs sized before anything is launched, as
+// calib_pass does, and reduced together in slab order.
 static int fusion_pass(plda_handle *h, const FusionSource &src, const double *a, double c, double theta, plda_fusion_record *rec) {
   FusionArgs P = {};
   for (int k = 0; k < src.K; ++k) { P.s[k] = src.s[k]; P.ld[k] = src.ld[k]; P.a[k] = a[k]; }
   P.c = c; P.theta = theta;
-  int64_t rpw = 0, total = 0;
+  const TrialSource whole = TrialSource::matrix(src.s[0], src.ld[0], src.M, src.Nt, src.espk, src.tspk);
+  const TrialSource &ts = src.slabs ? *src.slabs : whole;
+  int64_t total = 0;
   if (src.lists) total = fusion_list_blocks(src.M) + fusion_list_blocks(src.Nt);
   else {
     if (ceil_div(src.Nt, (int64_t)FUSION_STRIP) > (int64_t)0x7fffffff) return fail(h, PLDA_E_CAPACITY, "fusion: too many column strips");
-    total = fusion_strip_blocks(src.M, src.Nt, &rpw);
-    if (total > (int64_t)0x7fffffff || rpw > (int64_t)0x3fffffff) return fail(h, PLDA_E_CAPACITY, "fusion: too many column strips or rows per workgroup");
+    bool fits = true;
+    PLDA_TRY(for_each_piece(ts, [&](const TrialPiece &pc) -> int {
+      int64_t rpw = 0;
+      const int64_t blocks = fusion_strip_blocks(pc.rows, pc.Nt, &rpw);
+      fits = fits && blocks <= (int64_t)0x7fffffff && rpw <= (int64_t)0x3fffffff;
+      total += blocks;
+      return PLDA_OK;
+    }, /*produce=*/false));
+    if (!fits || total > (int64_t)0x7fffffff) return fail(h, PLDA_E_CAPACITY, "fusion: too many column strips or rows per workgroup");
   }
   PLDA_HIP(h, h->fusion_part.reserve((size_t)(total + 1) * sizeof(plda_fusion_record)));
   plda_fusion_record *part = h->fusion_part.as<plda_fusion_record>();
@@ -532,16 +590,28 @@ static int fusion_pass(plda_handle *h, const FusionSource &src, const double *a,
 #undef FUSION_CALL
     PLDA_LAUNCH_CHECK(h);
   } else {
-#define FUSION_CALL(KK) fusion_launch_strip<KK>(h, P, src, total, rpw, part)
-    FUSION_DISPATCH(src.K, FUSION_CALL)
-#undef FUSION_CALL
-    PLDA_LAUNCH_CHECK(h);
+    int64_t at = 0;
+    PLDA_TRY(for_each_piece(ts, [&](const TrialPiece &pc) -> int {
+      int64_t rpw = 0;
+      const int64_t blocks = fusion_strip_blocks(pc.rows, pc.Nt, &rpw);
+      P.s[0] = pc.scores; P.ld[0] = pc.ld;
+      if (src.K == src.nsys) {
+        fusion_dispatch_strip(h, src.K, P, pc.rows, pc.Nt, pc.espk, src.tspk, blocks, rpw, part + at);
+      } else {
+        fusion_side_launch_strip(h, fusion_side_args(P, src, pc.espk - src.espk), src.K, pc.rows, pc.Nt, pc.espk, src.tspk, blocks, rpw, part + at);
+      }
+      PLDA_LAUNCH_CHECK(h);
+      at += blocks;
+      return PLDA_OK;
+    }));
   }
   fusion_reduce_kernel<<<1, 1024, 0, h->stream>>>(part, total, src.K, part + total);
   PLDA_LAUNCH_CHECK(h);
   PLDA_HIP(h, hipMemcpyAsync(rec, part + total, sizeof(*rec), hipMemcpyDeviceToHost, h->stream));
   PLDA_HIP(h, hipStreamSynchronize(h->stream));
-  if (rec->nonfinite) return fail(h, PLDA_E_INVAL, "fusion: %llu trials with a non-finite score", (unsigned long long)rec->nonfinite);
+  if (rec->nonfinite)
+    return fail(h, PLDA_E_INVAL, src.K == src.nsys ? "fusion: %llu trials with a non-finite score" : "fusion: %llu trials with a non-finite score or side value",
+                (unsigned long long)rec->nonfinite);
   if (rec->np == 0 || rec->nn == 0) return fail(h, PLDA_E_INVAL, "fusion: need at least one target and one non-target trial");
   return PLDA_OK;
 }
@@ -593,9 +663,10 @@ static int fusion_newton_core(const plda_fusion_record *r, double prior, double 
   *lambda2 = lam;
   return 0;
 }
-static int fusion_newton_fail(plda_handle *h, int why, int at) {
+static int fusion_newton_fail(plda_handle *h, int why, int at, int nsys = FUSION_KMAX) {   // features from nsys on are sides (K25)
   char who[32];
   if (at == 0) std::snprintf(who, sizeof(who), "the offset");
+  else if (at - 1 >= nsys) std::snprintf(who, sizeof(who), "side %d", at - 1 - nsys);
   else std::snprintf(who, sizeof(who), "system %d", at - 1);
   if (why == 2) return fail(h, PLDA_E_INVAL, "fusion_newton: the Hessian's diagonal entry of %s is not positive", who);
   if (why == 3)
@@ -625,7 +696,9 @@ static int fusion_fit(plda_handle *h, const FusionSource &src, double prior, dou
   auto take = [&](const double *xx, double shift, plda_fusion_record *r) { return fusion_pass(h, src, xx + 1, xx[0] + shift, 0.0, r); };
   PLDA_TRY(take(x, tau, &rec)); ++passes;
   for (int k = 0; k < K; ++k)
-    if (rec.smin[k] == rec.smax[k]) return fail(h, PLDA_E_INVAL, "fusion_fit: system %d is constant (every score equals %g): the Hessian is singular", k, (double)rec.smin[k]);
+    if (rec.smin[k] == rec.smax[k])
+      return k < src.nsys ? fail(h, PLDA_E_INVAL, "fusion_fit: system %d is constant (every score equals %g): the Hessian is singular", k, (double)rec.smin[k])
+                          : fail(h, PLDA_E_INVAL, "fusion_fit: side %d is constant (every value equals %g): the Hessian is singular", k - src.nsys, (double)rec.smin[k]);
   double lam2 = INFINITY, F = 0.0;
   int it = 0;
   bool converged = false;
@@ -636,7 +709,7 @@ static int fusion_fit(plda_handle *h, const FusionSource &src, double prior, dou
     // on separable data the iteration runs away and the weights w die out trial by trial until fewer than K + 1 trials carry
     // the Hessian: that is where the iteration stops (not converged, separable reported), not a refusal of the systems
     if (why >= 2 && it > 0 && rec.ymin[1] > rec.ymax[0]) break;
-    if (why) return fusion_newton_fail(h, why, at);
+    if (why) return fusion_newton_fail(h, why, at, src.nsys);
     if (lam2 <= tol) { converged = true; break; }
     if (it >= max_iter) break;
     double t = 1.0;
@@ -672,7 +745,7 @@ static int fusion_matrix_source(plda_handle *h, const char *fn, int K, const flo
     if (ld[k] < Nt) return fail(h, PLDA_E_INVAL, "%s: ld[%d] = %lld < Nt = %lld", fn, k, (long long)ld[k], (long long)Nt);
     s->s[k] = dscores[k]; s->ld[k] = ld[k];
   }
-  s->K = K; s->lists = false; s->M = M; s->Nt = Nt; s->espk = despk; s->tspk = dtspk;
+  s->K = K; s->nsys = K; s->lists = false; s->M = M; s->Nt = Nt; s->espk = despk; s->tspk = dtspk;
   return PLDA_OK;
 }
 int fusion_list_args_check(plda_handle *h, const char *fn, int K, const float *const *pos, int64_t np, const float *const *neg, int64_t nn) {
@@ -687,7 +760,7 @@ static int fusion_list_source(plda_handle *h, const char *fn, int K, const float
                               int64_t nn, FusionSource *s) {
   PLDA_TRY(fusion_list_args_check(h, fn, K, dpos, np, dneg, nn));
   for (int k = 0; k < K; ++k) { s->s[k] = dpos[k]; s->neg[k] = dneg[k]; }
-  s->K = K; s->lists = true; s->M = np; s->Nt = nn;
+  s->K = K; s->nsys = K; s->lists = true; s->M = np; s->Nt = nn;
   return PLDA_OK;
 }
 
@@ -735,5 +808,86 @@ int fusion_map_device(plda_handle *h, int K, const float *const *dscores, const 
   PLDA_LAUNCH_CHECK(h);
   return PLDA_OK;
 }
+
+// ------------------------------------------------------------------------------------ sides (K25; kernels in fusion_side.hip)
+// appends the Q sides of a call to a source that holds its K systems: feature slot K + q is side q
+static int fusion_side_source(plda_handle *h, const char *fn, int K, int Q, const plda_fusion_side *sides, FusionSource *s) {
+  if (Q < 0 || K + Q > FUSION_KMAX)
+    return fail(h, PLDA_E_INVAL, "%s: n_systems + n_sides must be at most %d with n_sides >= 0 (got %d + %d)", fn, FUSION_KMAX, K, Q);
+  if (Q > 0 && !sides) return fail(h, PLDA_E_INVAL, "%s: the array of sides is NULL", fn);
+  for (int q = 0; q < Q; ++q) {
+    if (sides[q].op < PLDA_SIDE_MIN || sides[q].op > PLDA_SIDE_PROD) return fail(h, PLDA_E_INVAL, "%s: side %d has op %d (must be 0 .. 4)", fn, q, (int)sides[q].op);
+    if (!sides[q].enrol || !sides[q].test) return fail(h, PLDA_E_INVAL, "%s: the %s vector of side %d is NULL", fn, !sides[q].enrol ? "enrol" : "test", q);
+    s->s[K + q] = sides[q].test; s->ld[K + q] = 0; s->enrol[K + q] = sides[q].enrol; s->op[K + q] = sides[q].op;
+  }
+  s->nsys = K; s->K = K + Q;
+  return PLDA_OK;
+}
+
+int fusion_side_pass_device(plda_handle *h, int K, const float *const *dscores, const int64_t *ld, int Q, const plda_fusion_side *sides,
+                            int64_t M, int64_t Nt, const int64_t *despk, const int64_t *dtspk, const double *a, double c, double theta,
+                            plda_fusion_record *out) {
+  if (!out || !a) return fail(h, PLDA_E_INVAL, "fusion_side_pass: the output record or the weight array is NULL");
+  FusionSource s;
+  PLDA_TRY(fusion_matrix_source(h, "fusion_side_pass", K, dscores, ld, M, Nt, despk, dtspk, true, &s));
+  PLDA_TRY(fusion_side_source(h, "fusion_side_pass", K, Q, sides, &s));
+  return fusion_pass(h, s, a, c, theta, out);
+}
+int fusion_side_fit_device(plda_handle *h, int K, const float *const *dscores, const int64_t *ld, int Q, const plda_fusion_side *sides,
+                           int64_t M, int64_t Nt, const int64_t *despk, const int64_t *dtspk, double prior, double tol, int max_iter,
+                           plda_fusion_fit *out) {
+  if (!out) return fail(h, PLDA_E_INVAL, "fusion_side_fit: the output structure is NULL");
+  FusionSource s;
+  PLDA_TRY(fusion_matrix_source(h, "fusion_side_fit", K, dscores, ld, M, Nt, despk, dtspk, true, &s));
+  PLDA_TRY(fusion_side_source(h, "fusion_side_fit", K, Q, sides, &s));
+  return fusion_fit(h, s, prior, tol, max_iter, out);
+}
+int fusion_side_map_device(plda_handle *h, int K, const float *const *dscores, const int64_t *ld, int Q, const plda_fusion_side *sides,
+                           int64_t M, int64_t Nt, const double *a, double b, float *dout, int64_t ld_out) {
+  if (!a || !dout || ld_out < Nt) return fail(h, PLDA_E_INVAL, "fusion_side_map: bad argument");
+  FusionSource s;
+  PLDA_TRY(fusion_matrix_source(h, "fusion_side_map", K, dscores, ld, M, Nt, nullptr, nullptr, false, &s));
+  PLDA_TRY(fusion_side_source(h, "fusion_side_map", K, Q, sides, &s));
+  if (Q == 0) return fusion_map_device(h, K, dscores, ld, M, Nt, a, b, dout, ld_out);
+  if (ceil_div(Nt, (int64_t)FUSION_STRIP) > (int64_t)0x7fffffff) return fail(h, PLDA_E_CAPACITY, "fusion_side_map: too many column strips");
+  FusionArgs P = {};
+  for (int k = 0; k < s.K; ++k) { P.s[k] = s.s[k]; P.ld[k] = s.ld[k]; P.a[k] = a[k]; }
+  P.c = b;
+  fusion_side_launch_map(h, fusion_side_args(P, s, 0), s.K, M, Nt, dout, ld_out);
+  PLDA_LAUNCH_CHECK(h);
+  return PLDA_OK;
+}
+
+// the operand forms: system 0 is this model's own matrix, re-scored slab by slab once per pass (operand_slabs.hip)
+static int score_fusion_side_source(plda_handle *h, const char *fn, const double *dU, const int32_t *dn, int n_uniform, int64_t M,
+                                    const double *dV, int64_t Nt, const double *dzmean, const double *dzstd, const int64_t *despk,
+                                    const int64_t *dtspk, int Q, const plda_fusion_side *sides, const void *out, OperandSlabs *os,
+                                    TrialSource *ts, FusionSource *s) {
+  PLDA_TRY(fusion_side_source(h, fn, 1, Q, sides, s));
+  PLDA_TRY(operand_source(h, fn, dU, dn, n_uniform, M, dV, Nt, dzmean, dzstd, despk, dtspk, out, os, ts));
+  s->lists = false; s->M = M; s->Nt = Nt; s->espk = despk; s->tspk = dtspk; s->ld[0] = Nt; s->slabs = ts;
+  return PLDA_OK;
+}
+int score_fusion_side_pass_device(plda_handle *h, const double *dU, const int32_t *dn, int n_uniform, int64_t M, const double *dV,
+                                  int64_t Nt, const double *dzmean, const double *dzstd, const int64_t *despk, const int64_t *dtspk, int Q,
+                                  const plda_fusion_side *sides, const double *a, double c, double theta, plda_fusion_record *out) {
+  if (!a) return fail(h, PLDA_E_INVAL, "score_fusion_side_pass: the weight array is NULL");
+  OperandSlabs os;
+  TrialSource ts;
+  FusionSource s;
+  PLDA_TRY(score_fusion_side_source(h, "score_fusion_side_pass", dU, dn, n_uniform, M, dV, Nt, dzmean, dzstd, despk, dtspk, Q, sides, out, &os, &ts, &s));
+  return fusion_pass(h, s, a, c, theta, out);
+}
+int score_fusion_side_fit_device(plda_handle *h, const double *dU, const int32_t *dn, int n_uniform, int64_t M, const double *dV,
+                                 int64_t Nt, const double *dzmean, const double *dzstd, const int64_t *despk, const int64_t *dtspk, int Q,
+                                 const plda_fusion_side *sides, double prior, double tol, int max_iter, plda_fusion_fit *out) {
+  OperandSlabs os;
+  TrialSource ts;
+  FusionSource s;
+  PLDA_TRY(score_fusion_side_source(h, "score_fusion_side_fit", dU, dn, n_uniform, M, dV, Nt, dzmean, dzstd, despk, dtspk, Q, sides, out, &os, &ts, &s));
+  return fusion_fit(h, s, prior, tol, max_iter, out);
+}
+
+#endif  // PLDA_FUSION_SHARED_ONLY (the host drivers)
 
 }  // namespace plda

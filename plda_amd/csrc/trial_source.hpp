@@ -208,6 +208,21 @@ int fusion_fit_lists_device(plda_handle *h, int K, const float *const *dpos, int
                             double prior, double tol, int max_iter, plda_fusion_fit *out);
 int fusion_map_device(plda_handle *h, int K, const float *const *dscores, const int64_t *ld, int64_t M, int64_t Nt, const double *a,
                       double b, float *dout, int64_t ld_out);
+// K matrices + Q sides formed in registers (K25; kernels in fusion_side.hip); `sides` is a HOST array of Q entries
+int fusion_side_pass_device(plda_handle *h, int K, const float *const *dscores, const int64_t *ld, int Q, const plda_fusion_side *sides,
+                            int64_t M, int64_t Nt, const int64_t *despk, const int64_t *dtspk, const double *a, double c, double theta,
+                            plda_fusion_record *out);
+int fusion_side_fit_device(plda_handle *h, int K, const float *const *dscores, const int64_t *ld, int Q, const plda_fusion_side *sides,
+                           int64_t M, int64_t Nt, const int64_t *despk, const int64_t *dtspk, double prior, double tol, int max_iter,
+                           plda_fusion_fit *out);
+int fusion_side_map_device(plda_handle *h, int K, const float *const *dscores, const int64_t *ld, int Q, const plda_fusion_side *sides,
+                           int64_t M, int64_t Nt, const double *a, double b, float *dout, int64_t ld_out);
+int score_fusion_side_pass_device(plda_handle *h, const double *dU, const int32_t *dn, int n_uniform, int64_t M, const double *dV,
+                                  int64_t Nt, const double *dzmean, const double *dzstd, const int64_t *despk, const int64_t *dtspk, int Q,
+                                  const plda_fusion_side *sides, const double *a, double c, double theta, plda_fusion_record *out);
+int score_fusion_side_fit_device(plda_handle *h, const double *dU, const int32_t *dn, int n_uniform, int64_t M, const double *dV,
+                                 int64_t Nt, const double *dzmean, const double *dzstd, const int64_t *despk, const int64_t *dtspk, int Q,
+                                 const plda_fusion_side *sides, double prior, double tol, int max_iter, plda_fusion_fit *out);
 // the argument check of the list forms (K, the two pointer arrays, their K entries, the lengths): used by the host-list entry
 // points before they upload, and by the device-list drivers
 int fusion_list_args_check(plda_handle *h, const char *fn, int K, const float *const *pos, int64_t np, const float *const *neg, int64_t nn);

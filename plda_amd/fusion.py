@@ -232,3 +232,199 @@ def apply_dev(engine, dscores, ld, m, nt, fusion, dout, ld_out):
     a = _weights(fusion.a, k)
     N.check(engine._h, engine._lib.plda_fusion_map_dev(engine._h, k, _vp(ptrs), _vp(lds), int(m), int(nt), _vp(a), float(fusion.b),
                                                        _p(dout), int(ld_out)))
+
+
+# ---------------------------------------------------------------------------------------------- sides (K25, csrc/fusion_side.hip)
+SIDE_OPS = ("min", "max", "sum", "absdiff", "prod")          # PLDA_SIDE_MIN .. PLDA_SIDE_PROD of include/plda_hip.h
+SIDE_DTYPE = np.dtype([("enrol", np.uint64), ("test", np.uint64), ("op", np.int32), ("reserved", np.int32)], align=True)
+assert SIDE_DTYPE.itemsize == 24
+
+
+def _side_op(op):
+    if isinstance(op, str):
+        if op not in SIDE_OPS:
+            raise ValueError("unknown side op %r: one of %s" % (op, ", ".join(SIDE_OPS)))
+        return SIDE_OPS.index(op)
+    if isinstance(op, (int, np.integer)) and 0 <= int(op) < len(SIDE_OPS):
+        return int(op)
+    raise ValueError("unknown side op %r: one of %s" % (op, ", ".join(SIDE_OPS)))
+
+
+def side_values(op, e, t):
+    """The value of a side as include/plda_hip.h defines it, in NumPy: ONE fp32 operation on e and t (broadcast against each
+    other: e[:, None] and t[None, :] give the [M, Nt] matrix of a side, two equally long arrays the values of listed
+    trials).  Ties and signed zeros follow the written comparison: min is `e < t ? e : t`, max is `e > t ? e : t`."""
+    code = _side_op(op)
+    e, t = np.asarray(e, np.float32), np.asarray(t, np.float32)
+    with np.errstate(all="ignore"):
+        if code == 0:
+            return np.where(e < t, e, t).astype(np.float32)
+        if code == 1:
+            return np.where(e > t, e, t).astype(np.float32)
+        if code == 2:
+            return np.add(e, t, dtype=np.float32)
+        if code == 3:
+            return np.abs(np.subtract(e, t, dtype=np.float32))
+        return np.multiply(e, t, dtype=np.float32)
+
+
+class Side(object):
+    """One side-information term of a quality-aware calibration: `op` ("min" | "max" | "sum" | "absdiff" | "prod") on a
+    per-enrol-row and a per-test-column quality.  `enrol` / `test` are 1-D float32 torch tensors on the device, or host
+    sequences (uploaded by `on(device)`); their lengths are checked against (M, Nt) before any device call."""
+
+    def __init__(self, op, enrol, test):
+        self.code = _side_op(op)
+        self.op = SIDE_OPS[self.code]
+        self.enrol, self.test = enrol, test
+        for name, v in (("enrol", enrol), ("test", test)):
+            if v is None or len(np.shape(v)) != 1:
+                raise ValueError("side %r: the %s values are a 1-D sequence (one per %s row)" % (self.op, name, name))
+
+    def check(self, m, nt):
+        if len(self.enrol) != int(m) or len(self.test) != int(nt):
+            raise ValueError("side %r: %d enrol and %d test values for a %d x %d trials matrix"
+                             % (self.op, len(self.enrol), len(self.test), int(m), int(nt)))
+
+    def on(self, device):
+        """The side with both vectors as contiguous float32 device tensors (itself if they already are)."""
+        import torch
+
+        def up(v):
+            if isinstance(v, torch.Tensor):
+                if v.dtype != torch.float32:
+                    raise ValueError("side %r: device vectors are float32" % self.op)
+                return v.to(device).contiguous()
+            return torch.from_numpy(np.ascontiguousarray(v, np.float32)).to(device)
+        return Side(self.code, up(self.enrol), up(self.test))
+
+    def __repr__(self):
+        return "Side(%r, enrol[%d], test[%d])" % (self.op, len(self.enrol), len(self.test))
+
+
+def _side_args(sides, m, nt):
+    """(Q, the host array of Q plda_fusion_side, the device tensors it points into -- keep them alive over the call)."""
+    sides = list(sides)
+    for s in sides:
+        if not isinstance(s, Side):
+            raise ValueError("a side is a plda_amd.fusion.Side")
+        s.check(m, nt)
+    raw = np.zeros(max(len(sides), 1), SIDE_DTYPE)
+    keep = []
+    for q, s in enumerate(sides):
+        if not (hasattr(s.enrol, "data_ptr") and hasattr(s.test, "data_ptr")):
+            raise ValueError("side %d: the vectors must be on the device (Side.on(device))" % q)
+        if str(s.enrol.dtype) != "torch.float32" or str(s.test.dtype) != "torch.float32" or not s.enrol.is_contiguous() or not s.test.is_contiguous():
+            raise ValueError("side %d: the device vectors are contiguous float32" % q)
+        raw[q]["enrol"], raw[q]["test"], raw[q]["op"] = s.enrol.data_ptr(), s.test.data_ptr(), s.code
+        keep.append((s.enrol, s.test))
+    return len(sides), raw, keep
+
+
+class QualityFusion(Fusion):
+    """A fusion over K systems and Q sides: a = (a of the systems, then a of the sides).  Calling it maps HOST values in
+    fp64: `scores` a sequence of K arrays, `qualities` a sequence of Q (enrol_values, test_values) pairs broadcast against
+    the scores' shape ([M] and [Nt] for [M, Nt] scores; equally long arrays for listed trials)."""
+
+    def __init__(self, a, b, ops, **kw):
+        Fusion.__init__(self, a, b, **kw)
+        self.ops = tuple(SIDE_OPS[_side_op(o)] for o in ops)
+        if self.n_sides >= self.a.shape[0]:
+            raise ValueError("a quality fusion has at least one system beside its %d sides" % self.n_sides)
+
+    @property
+    def n_sides(self):
+        return len(self.ops)
+
+    @property
+    def n_systems(self):
+        return int(self.a.shape[0]) - self.n_sides
+
+    def __call__(self, scores, qualities=()):
+        if len(scores) != self.n_systems or len(qualities) != self.n_sides:
+            raise ValueError("this fusion takes the scores of %d systems and %d qualities" % (self.n_systems, self.n_sides))
+        shape = np.shape(scores[0])
+        feats = [np.asarray(s, np.float64) for s in scores]
+        for op, (e, t) in zip(self.ops, qualities):
+            e, t = np.asarray(e, np.float32), np.asarray(t, np.float32)
+            if len(shape) == 2 and e.ndim == 1 and t.ndim == 1:
+                e, t = e[:, None], t[None, :]
+            feats.append(side_values(op, e, t).astype(np.float64))
+        y = np.full(shape, self.b, np.float64)
+        for ak, f in zip(self.a, feats):
+            y = y + ak * f
+        return y
+
+    def __repr__(self):
+        return "QualityFusion(a=%r, b=%r, ops=%r, prior=%r, cllr_after=%r, converged=%r, separable=%r)" % (
+            self.a.tolist(), self.b, self.ops, self.prior, self.cllr_after, self.converged, self.separable)
+
+
+def _quality_fusion(raw, k, sides, prior):
+    f = _fusion(raw, k + len(sides), prior)
+    return QualityFusion(f.a, f.b, [s.code for s in sides], prior=f.prior, cllr_after=f.cllr_after, converged=f.converged,
+                         separable=f.separable, objective=f.objective, lambda2=f.lambda2, iterations=f.iterations, passes=f.passes)
+
+
+def pass_with_sides_dev(engine, dscores, ld, sides, m, nt, denrol_spk, dtest_spk, a, c=0.0, theta=0.0):
+    """One pass over K HBM-resident matrices and Q sides (`Side`s with device vectors); a has K + Q weights.  Bit-identical
+    to `pass_from_matrices_dev` over K + Q matrices with the sides materialised by `side_values`."""
+    k, ptrs, lds = _matrix_args(dscores, ld)
+    q, sraw, keep = _side_args(sides, m, nt)
+    a = _weights(a, k + q)
+    raw = np.zeros(1, RECORD_DTYPE)
+    N.check(engine._h, engine._lib.plda_fusion_side_pass_dev(engine._h, k, _vp(ptrs), _vp(lds), q, _vp(sraw), int(m), int(nt),
+                                                             _p(denrol_spk), _p(dtest_spk), _vp(a), float(c), float(theta), _vp(raw)))
+    del keep
+    return _record(raw)
+
+
+def fit_with_sides_dev(engine, dscores, ld, sides, m, nt, denrol_spk, dtest_spk, prior=0.5, tol=0.0, max_iter=0):
+    """The fusion fit over K matrices and Q sides -> `QualityFusion`."""
+    k, ptrs, lds = _matrix_args(dscores, ld)
+    sides = list(sides)
+    q, sraw, keep = _side_args(sides, m, nt)
+    raw = np.zeros(1, FIT_DTYPE)
+    N.check(engine._h, engine._lib.plda_fusion_side_fit_dev(engine._h, k, _vp(ptrs), _vp(lds), q, _vp(sraw), int(m), int(nt),
+                                                            _p(denrol_spk), _p(dtest_spk), float(prior), float(tol), int(max_iter), _vp(raw)))
+    del keep
+    return _quality_fusion(raw, k, sides, prior)
+
+
+def apply_with_sides_dev(engine, dscores, ld, sides, m, nt, fusion, dout, ld_out):
+    """out[i, j] = (float)(the FMA chain from b over the K systems and the Q sides); dout may be one of the K matrices with
+    ld_out equal to its pitch.  Enqueued on the engine's stream (no synchronisation): the side vectors must stay alive
+    until the stream has run it."""
+    k, ptrs, lds = _matrix_args(dscores, ld)
+    q, sraw, keep = _side_args(sides, m, nt)
+    a = _weights(fusion.a, k + q)
+    N.check(engine._h, engine._lib.plda_fusion_side_map_dev(engine._h, k, _vp(ptrs), _vp(lds), q, _vp(sraw), int(m), int(nt), _vp(a),
+                                                            float(fusion.b), _p(dout), int(ld_out)))
+    return keep
+
+
+def fit_from_operands_with_sides_dev(engine, du, dn, n_uniform, m, dv, nt, dzmean, dzstd, denrol_spk, dtest_spk, sides, prior=0.5,
+                                     tol=0.0, max_iter=0):
+    """The operand form: system 0 is the engine's own score matrix of (du, dn | n_uniform, dv, z-norm), produced slab by slab
+    and never held (the arguments of plda_score_calib_fit_dev) -> `QualityFusion` over 1 system and Q sides."""
+    sides = list(sides)
+    q, sraw, keep = _side_args(sides, m, nt)
+    raw = np.zeros(1, FIT_DTYPE)
+    N.check(engine._h, engine._lib.plda_score_fusion_side_fit_dev(engine._h, _p(du), _p(dn), int(n_uniform), int(m), _p(dv), int(nt),
+                                                                  _p(dzmean), _p(dzstd), _p(denrol_spk), _p(dtest_spk), q, _vp(sraw),
+                                                                  float(prior), float(tol), int(max_iter), _vp(raw)))
+    del keep
+    return _quality_fusion(raw, 1, sides, prior)
+
+
+def pass_from_operands_with_sides_dev(engine, du, dn, n_uniform, m, dv, nt, dzmean, dzstd, denrol_spk, dtest_spk, sides, a, c=0.0,
+                                      theta=0.0):
+    """One pass of the operand form; a has 1 + Q weights."""
+    q, sraw, keep = _side_args(sides, m, nt)
+    a = _weights(a, 1 + q)
+    raw = np.zeros(1, RECORD_DTYPE)
+    N.check(engine._h, engine._lib.plda_score_fusion_side_pass_dev(engine._h, _p(du), _p(dn), int(n_uniform), int(m), _p(dv), int(nt),
+                                                                   _p(dzmean), _p(dzstd), _p(denrol_spk), _p(dtest_spk), q, _vp(sraw),
+                                                                   _vp(a), float(c), float(theta), _vp(raw)))
+    del keep
+    return _record(raw)

@@ -1361,24 +1361,100 @@ class MPlda(object):
         return FU.fit_from_matrices_dev(self, [S.data_ptr()] + [o.data_ptr() for o in oth], [nt] + lds, m, nt, despk.data_ptr(),
                                         dtspk.data_ptr(), prior=prior)
 
-    def score_matrix_fused(self, enrol, test, others, fusion, znorm=True, cohort=None, top_k=None):
+    def score_matrix_fused(self, enrol, test, others, fusion, znorm=True, cohort=None, top_k=None, quality=None):
         """float32 [M, Nt]: the fused value of `fusion` (a `plda_amd.fusion.Fusion` over this model's matrix, normalised as in
-        `fuse`, followed by `others`), the FMA chain of the header rounded once to fp32."""
+        `fuse`, followed by `others`), the FMA chain of the header rounded once to fp32.  With `quality` (the argument of
+        `calibrate_quality`) `fusion` is that call's `QualityFusion`, and `others` may be empty."""
         from . import fusion as FU
         ids, counts, U = self._unpack(enrol)
-        _, _, V = self._unpack(test)
+        tids, _, V = self._unpack(test)
         m, nt = U.shape[0], V.shape[0]
         if m == 0 or nt == 0:
             return np.empty((m, nt), np.float32)
-        oth, lds = self._other_matrices_on_device(others, m, nt, "score_matrix_fused")
-        if fusion.n_systems != 1 + len(oth):
-            raise ValueError("score_matrix_fused: the fusion was fitted on %d systems, got %d" % (fusion.n_systems, 1 + len(oth)))
+        if quality is None:
+            oth, lds = self._other_matrices_on_device(others, m, nt, "score_matrix_fused")
+            sides = []
+        else:
+            oth, lds = self._other_matrices_on_device(others, m, nt, "score_matrix_fused") if len(others) else ([], [])
+            sides = self._quality_sides(quality, ids, tids, m, nt, "score_matrix_fused")
+            if getattr(fusion, "n_sides", 0) != len(sides) or tuple(fusion.ops) != tuple(s.op for s in sides):
+                raise ValueError("score_matrix_fused: the fusion was fitted on the sides %r, got %r"
+                                 % (getattr(fusion, "ops", ()), tuple(s.op for s in sides)))
+        if fusion.n_systems != 1 + len(oth) or (quality is None and getattr(fusion, "n_sides", 0)):
+            raise ValueError("score_matrix_fused: the fusion was fitted on %d systems%s, got %d" % (
+                fusion.n_systems, " and %d sides" % fusion.n_sides if getattr(fusion, "n_sides", 0) else "", 1 + len(oth)))
         S = self._own_matrix_on_device(ids, counts, U, V, znorm, cohort, top_k)
         import torch
         torch.cuda.synchronize(S.device)
-        FU.apply_dev(self, [S.data_ptr()] + [o.data_ptr() for o in oth], [nt] + lds, m, nt, fusion, S.data_ptr(), nt)
+        ptrs, pitches = [S.data_ptr()] + [o.data_ptr() for o in oth], [nt] + lds
+        if sides:
+            keep = FU.apply_with_sides_dev(self, ptrs, pitches, sides, m, nt, fusion, S.data_ptr(), nt)
+        else:
+            FU.apply_dev(self, ptrs, pitches, m, nt, fusion, S.data_ptr(), nt)
         self.synchronize()
+        keep = None     # noqa: F841  (the side vectors had to outlive the enqueued map)
         return S.cpu().numpy()
+
+    # ------------------------------------------------- quality-aware calibration (K25; csrc/fusion_side.hip)
+    def _quality_sides(self, quality, ids, tids, m, nt, what):
+        """`quality` = ((op, enrol_values, test_values), ...) -> `plda_amd.fusion.Side`s with device vectors.  Each values
+        argument is a mapping {key: value} (looked up by the enrol / test keys) or a sequence in the order of enrol / test:
+        the convention of `test_speaker`."""
+        from . import fusion as FU
+
+        def values(v, keys, n, which, q):
+            if hasattr(v, "keys"):
+                if keys is None:
+                    raise ValueError("%s: quality %d: a mapping of %s values needs %s keys" % (what, q, which, which))
+                v = [float(v[int(k)]) for k in keys]
+            v = np.ascontiguousarray(v, np.float32).reshape(-1)
+            if v.shape[0] != n:
+                raise ValueError("%s: quality %d: %d %s values for %d %s entries" % (what, q, v.shape[0], which, n, which))
+            return v
+        sides = []
+        for q, item in enumerate(quality):
+            if len(item) != 3:
+                raise ValueError("%s: quality %d is not (op, enrol_values, test_values)" % (what, q))
+            op, ev, tv = item
+            sides.append(FU.Side(op, values(ev, ids, m, "enrol", q), values(tv, tids, nt, "test", q)))
+        import torch
+        dev = torch.device("cuda", self.device)
+        return [s.on(dev) for s in sides]
+
+    def calibrate_quality(self, enrol, test, test_speaker, quality, others=(), prior=0.5, znorm=True, cohort=None, top_k=None):
+        """Quality-aware calibration (include/plda_hip.h, "quality-aware calibration"): fit llr = b + a_0 * (this model's
+        score) + sum a_k * others[k-1] + sum a_q * side_q, where side q = op(enrol quality of the row, test quality of the
+        column) -- `quality` is a sequence of (op, enrol_values, test_values), op one of "min" | "max" | "sum" | "absdiff" |
+        "prod", each values argument a mapping {key: value} or a sequence in the order of `enrol` / `test` (the convention of
+        `test_speaker`).  A side's [M, Nt] values are formed in registers, never in memory.  Other arguments as `fuse`; at
+        most 8 systems and sides together.  With no `others` and no cohort this model's matrix is never held either (the
+        operand form, as `calibrate`); otherwise it is.  Returns the `plda_amd.fusion.QualityFusion`; it is NOT stored,
+        like `fuse`'s result.  Apply it with `score_matrix_fused(..., quality=quality)`."""
+        from . import fusion as FU
+        ids, counts, U, V, tspk = self._labelled_trials(enrol, test, test_speaker, "calibrate_quality")
+        tids = self._unpack(test)[0]
+        m, nt = U.shape[0], V.shape[0]
+        quality = list(quality)
+        if 1 + len(others) + len(quality) > FU.MAX_SYSTEMS:
+            raise ValueError("calibrate_quality: at most %d systems and sides together" % FU.MAX_SYSTEMS)
+        sides = self._quality_sides(quality, ids, tids, m, nt, "calibrate_quality")
+        despk, dtspk = self._to_device(np.ascontiguousarray(ids, np.int64)), self._to_device(tspk)
+        import torch
+        if cohort is None and not len(others):
+            zm, zs = self._zn_arrays(ids, znorm)
+            uniform = int(counts[0]) if np.all(counts == counts[0]) else 0
+            dU, dV = self._to_device(U), self._to_device(V)
+            dn = None if uniform else self._to_device(counts)
+            dzm, dzs = (self._to_device(zm), self._to_device(zs)) if zm is not None else (None, None)
+            ptr = lambda t: t.data_ptr() if t is not None else None      # noqa: E731
+            torch.cuda.synchronize(dU.device)
+            return FU.fit_from_operands_with_sides_dev(self, dU.data_ptr(), ptr(dn), uniform, m, dV.data_ptr(), nt, ptr(dzm), ptr(dzs),
+                                                       despk.data_ptr(), dtspk.data_ptr(), sides, prior=prior)
+        oth, lds = self._other_matrices_on_device(others, m, nt, "calibrate_quality") if len(others) else ([], [])
+        S = self._own_matrix_on_device(ids, counts, U, V, znorm, cohort, top_k)
+        torch.cuda.synchronize(S.device)
+        return FU.fit_with_sides_dev(self, [S.data_ptr()] + [o.data_ptr() for o in oth], [nt] + lds, sides, m, nt, despk.data_ptr(),
+                                     dtspk.data_ptr(), prior=prior)
 
     # ------------------------------------------------- device-resident path
     def set_stream(self, hip_stream):
