@@ -691,7 +691,7 @@ int plda_fusion_map_dev(plda_handle *h, int32_t n_systems, const float *const *d
                         const double *a, double b, float *dout, int64_t ld_out);
 int plda_fusion_newton(const plda_fusion_record *record, double prior, double *F, double *d, double *lambda2);
 
-/* ---- quality-aware calibration: side-information terms in the fusion (K25; csrc/fusion_side.hip; the quality measure
+/* ---- quality-aware calibration: side-information terms in the fusion (K25; csrc/fusion.hip; the quality measure
  * functions -- duration, embedding norm, the AS-norm cohort mean -- put in front of reported verification numbers since
  * VoxSRC-20; the project's own extension like the fusion above, pinned by tests/fusion_side_model.py).
  *

@@ -17,7 +17,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 SO = os.path.join(LIBDIR, "libplda_hip.so")
 SO_DIAG = os.path.join(LIBDIR, "libplda_hip_diag.so")
-SOURCES = ["api.hip", "score.hip", "linalg.hip", "fit.hip", "frontend.hip", "eer.hip", "operand_slabs.hip", "lda.hip", "comm.hip", "eig_dc.hip", "hostio.hip", "transform.hip", "snorm.hip", "calib.hip", "dcf.hip", "rocch.hip", "topn.hip", "fusion.hip", "fusion_side.hip", "adapt.hip", "ahc.hip", "dense_pca.hip", "vbx.hip", "der.hip", "der_time.hip", "embed.hip", "spectral.hip"]
+SOURCES = ["api.hip", "score.hip", "linalg.hip", "fit.hip", "frontend.hip", "eer.hip", "operand_slabs.hip", "lda.hip", "comm.hip", "eig_dc.hip", "hostio.hip", "transform.hip", "snorm.hip", "calib.hip", "dcf.hip", "rocch.hip", "topn.hip", "fusion.hip", "adapt.hip", "ahc.hip", "dense_pca.hip", "vbx.hip", "der.hip", "der_time.hip", "embed.hip", "spectral.hip"]
 HEADERS = [os.path.join(CSRC, "common.hpp"), os.path.join(CSRC, "layout.hpp"), os.path.join(CSRC, "trial_source.hpp"), os.path.join(CSRC, "hostio.hpp"), os.path.join(CSRC, "sweep_mfma.inc"), os.path.join(CSRC, "score_bt4.inc"), os.path.join(CSRC, "score_bf16x3.inc"), os.path.join(CSRC, "syrk_blk.inc"), os.path.join(HERE, "..", "include", "plda_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics",
          "-Wall", "-Wno-unused-function", "-Wno-unused-result"]
@@ -32,14 +32,12 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-ato
 # 197 / 223 / 249 / 256 VGPRs, scalar-register spills from K = 5 on (2 / 4 / 6 / 14) and at K = 8 19 spilled VGPRs = 80 bytes
 # of scratch per lane; with it OFF 94 .. 244, no spill and no scratch anywhere (the table in csrc/fusion.hip).  It is a hidden
 # LLVM option and applies to the whole file (the list, map and reduce kernels lose nothing they had: their loops hold no
-# hoistable constants beyond the same exp / log1p ones); if a toolchain drops it the build fails loudly on the unknown option --
+# hoistable constants beyond the same exp / log1p ones; the instantiations with sides, K25, walk with the same account and
+# report the same figures); if a toolchain drops it the build fails loudly on the unknown option --
 # then remove it and accept the K >= 5 spills, or split the constants' live ranges by hand.  Reproduce the table with
 #   hipcc --offload-arch=gfx950 -O3 -std=c++17 -munsafe-fp-atomics -mllvm -disable-machine-licm \
 #         -Rpass-analysis=kernel-resource-usage -c plda_amd/csrc/fusion.hip -o /dev/null
 # Its effect on speed has not been measured apart from the rest (scripts/fusion_bench.py times the kernels as built).
-# fusion_side.hip: the same account (it includes the shared part of csrc/fusion.hip, see DEPENDS) in the side kernels, so the same flag for the same reason, and
-# the same flags altogether: a side pass is specified bit-identical to fusion.hip's matrix pass, so both files must contract
-# and schedule the shared code alike.  Its table is reproduced by the command above with fusion_side.hip for fusion.hip.
 # ahc.hip: the clustering is specified to the bit (tests/ahc_model.py): one fp64 addition and one fp64 division where the
 # contract names them, so nothing may be contracted into a fused multiply-add
 # spectral.hip: the graph, the selection of the pruning value and the k-means are specified to the operation
@@ -52,13 +50,9 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-ato
 EXTRA = {"score.hip": ["-mllvm", "-amdgpu-atomic-optimizer-strategy=None"],
          "frontend.hip": ["-ffp-contract=off"],
          "fusion.hip": ["-mllvm", "-disable-machine-licm"],
-         "fusion_side.hip": ["-mllvm", "-disable-machine-licm"],
          "ahc.hip": ["-ffp-contract=off"],
          "embed.hip": ["-ffp-contract=off"],
          "spectral.hip": ["-ffp-contract=off"]}
-
-# a source that includes another source: rebuilt when that one changes
-DEPENDS = {"fusion_side.hip": ["fusion.hip"]}
 
 
 def _stale(target, deps):
@@ -80,7 +74,7 @@ def build(force=False, verbose=False, diag=False):
         s = os.path.join(CSRC, src)
         o = os.path.join(objdir, src.replace(".hip", ".o"))
         objs.append(o)
-        if force or _stale(o, [s] + [os.path.join(CSRC, d) for d in DEPENDS.get(src, [])] + HEADERS):
+        if force or _stale(o, [s] + HEADERS):
             cmd = [hipcc] + flags + EXTRA.get(src, []) + ["-c", s, "-o", o]
             if verbose:
                 print(" ".join(cmd), flush=True)

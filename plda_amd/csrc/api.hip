@@ -1940,7 +1940,7 @@ int plda_fusion_newton(const plda_fusion_record *record, double prior, double *F
   return guarded(nullptr, "plda_fusion_newton", [&]() -> int { return fusion_newton(record, prior, F, d, lambda2); });
 }
 
-// ---------------------------------------------------------------- quality-aware calibration (fusion.hip, fusion_side.hip)
+// ---------------------------------------------------------------- quality-aware calibration (fusion.hip)
 int plda_fusion_side_pass_dev(plda_handle *h, int32_t n_systems, const float *const *dscores, const int64_t *ld, int32_t n_sides,
                               const plda_fusion_side *sides, int64_t M, int64_t Nt, const int64_t *denrol_spk,
                               const int64_t *dtest_spk, const double *a, double c, double theta, plda_fusion_record *out_record) {

@@ -8,9 +8,18 @@
 // extremes of y per class and the fp32 extremes of every system.  The Newton fit is host arithmetic on records
 // (fusion_newton, a pure function), the apply is the same chain rounded once to fp32 (fusion_map_kernel).
 //
+// QUALITY-AWARE CALIBRATION (K25; include/plda_hip.h, "quality-aware calibration") adds Q SIDES to the K matrices.  A side is
+// one fp32 operation on a per-enrol-row and a per-test-column number (duration, embedding norm, cohort mean ...); its [M, Nt]
+// values never exist in memory -- fusion_pass_strip_kernel<K, true> and fusion_side_map_kernel<K> form them in registers; the
+// pass hands the assembled fp32 feature array (s_0 .. s_{K-1}, q_0 .. q_{Q-1}) to the same account, store, grid and visiting
+// order.  A side pass is therefore bit-identical to a matrix pass over K + Q matrices in which the sides have been
+// materialised, and the Newton fit, the record and the refusals are used as they are.  Below, K counts every FEATURE where
+// sides are present.
+//
 // Kernels, all instantiated on K = 1 .. 8 so that every accumulator index is a compile-time constant (a runtime-indexed
-// per-thread array would live in scratch):
-//   fusion_pass_strip_kernel<K>  walks the K matrices as calib_pass_strip_kernel walks one: a workgroup owns 1024 columns, 4
+// per-thread array would live in scratch); with sides, the number of matrices among the K features is wave-uniform at run
+// time (one uniform branch per unrolled feature slot: 8 instantiations instead of 36 on (K, Q)):
+//   fusion_pass_strip_kernel<K, SIDES>  walks the K matrices as calib_pass_strip_kernel walks one: a workgroup owns 1024 columns, 4
 //       per thread with their test speaker ids in registers, and a slice of the rows.  The K base pointers, pitches and
 //       weights travel by value in one kernel-argument struct; 16-byte or scalar loads are chosen PER SYSTEM (each has its
 //       own base alignment and pitch).  Rows in flight per thread: 4 (K <= 2), 2 (K <= 4), 1 (K > 4) -- 4 K floats each.
@@ -24,6 +33,9 @@
 //   fusion_pass_list_kernel<K>   K parallel flat arrays of one fixed class: everything goes through the per-thread set.
 //   fusion_reduce_kernel         one block of 1024 threads adds the per-block partial records in a fixed order.
 //   fusion_map_kernel<K>         out = (float)chain with c = b; in place over one of the inputs allowed.
+//   fusion_side_map_kernel<K>    the same over matrices and sides, a side's four test values held in registers.
+// The operand form (system 0 produced slab by slab, fusion_pass) launches the same pass kernel per slab with the enrol vectors
+// offset to the slab's first row.
 // A wave reduces its NE sums by DPP (wave_sum_f64), the four waves of a block are added as (w0 + w1) + (w2 + w3), the block
 // writes ONE partial record into handle scratch (h->fusion_part).  No floating-point atomics and no integer ones: a call's
 // record is bit-identical from run to run.  The grid is a function of the shape alone (the same for every K; not tunable).
@@ -33,16 +45,14 @@
 //
 // Resources (hipcc --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage with this file's flags, plda_amd/build.py):
 // the table at fusion_pass_strip_kernel below -- no scratch and no spill in any instantiation, the K = 8 labelled pass in 244
-// registers (two waves per SIMD).  Speed: scripts/fusion_bench.py writes profiles/fusion_*.json.
-//
-// SHARED WITH fusion_side.hip (K matrices + Q side-information terms formed in registers, K25): that file includes THIS one
-// with PLDA_FUSION_SHARED_ONLY defined and so gets the argument record, the accumulators, fusion_account and
-// fusion_block_store -- everything up to the first #ifndef below -- and none of the kernels or host drivers.  One text, two
-// translation units compiled with the same flags: that is what makes a side pass bit-identical to a matrix pass.
+// registers (two waves per SIMD).  Speed: scripts/fusion_bench.py writes profiles/fusion_*.json,
+// scripts/fusion_side_bench.py profiles/fusion_side_*.json (K25).
 #include "trial_source.hpp"
 
 #include <algorithm>
 #include <cmath>
+#include <cstddef>
+#include <type_traits>
 
 namespace plda {
 
@@ -239,29 +249,40 @@ __device__ __forceinline__ void fusion_block_store(const FusionAcc<K> &A, int cn
 
 template <int K> constexpr int fusion_rows_in_flight() { return K <= 2 ? 4 : K <= 4 ? 2 : 1; }
 
-// ---- fusion_side.hip: K matrices followed by Q sides, T = K + Q features.  Feature slot k < K is a matrix exactly as in
-// FusionArgs; slot k >= K is a side: P.s[k] is its TEST vector and P.ld[k] = 0 (a "matrix" of pitch 0, so the strip walk's
-// address and alignment arithmetic is the matrix kernel's own), enrol[k] its ENROL vector (already offset to the first row of
-// the launch), op[k] its PLDA_SIDE_* code.  P stays the first member: the kernels re-read it at offset 0 of the
-// kernel-argument segment (see fusion_pass_strip_kernel).
+// With sides: S.K matrices followed by sides, up to the kernel's K features.  Feature slot k < S.K is a matrix exactly as in
+// FusionArgs; slot k >= S.K is a side: P.s[k] is its TEST vector and P.ld[k] = 0 (a "matrix" of pitch 0, so the strip walk's
+// address and alignment arithmetic is the matrix's own), enrol[k] its ENROL vector (already offset to the first row of the
+// launch), op[k] its PLDA_SIDE_* code.  P stays the FIRST member: the kernels re-read it at offset 0 of the kernel-argument
+// segment (see fusion_pass_strip_kernel).
 struct FusionSideArgs {
   FusionArgs P;
   const float *enrol[FUSION_KMAX];
   int32_t op[FUSION_KMAX];
   int32_t K, reserved;
 };
-void fusion_side_launch_strip(plda_handle *h, const FusionSideArgs &S, int T, int64_t rows, int64_t Nt, const int64_t *espk,
-                              const int64_t *tspk, int64_t blocks, int64_t rows_per_wg, plda_fusion_record *part);
-void fusion_side_launch_map(plda_handle *h, const FusionSideArgs &S, int T, int64_t M, int64_t Nt, float *out, int64_t ld_out);
+static_assert(offsetof(FusionSideArgs, P) == 0, "the kernels read the FusionArgs at offset 0 of the kernel-argument segment");
 
-#ifndef PLDA_FUSION_SHARED_ONLY
+template <bool SIDES> using FusionKernelArgs = std::conditional_t<SIDES, FusionSideArgs, FusionArgs>;
+__device__ __forceinline__ const FusionArgs &fusion_systems(const FusionArgs &P) { return P; }
+__device__ __forceinline__ const FusionArgs &fusion_systems(const FusionSideArgs &S) { return S.P; }
 
-// The labelled pass over K matrices: block b writes part[b].  Traversal and labelling of calib_pass_strip_kernel.
+typedef const FusionSideArgs __attribute__((address_space(4))) *FusionSideArgsPtr;   // the struct where the kernel arguments live
+typedef const float __attribute__((address_space(4))) *SideEnrolPtr;                 // read-only for the kernel's life: scalar loads
+
+// the value of a side for (e = enrol[i], t = test[j]): ONE IEEE fp32 operation, ties and signed zeros by the written comparison
+__device__ __forceinline__ float fusion_side_value(int op, float e, float t) {
+  const float mn = e < t ? e : t, mx = e > t ? e : t, sm = e + t, ad = fabsf(e - t), pr = e * t;
+  return op == PLDA_SIDE_MIN ? mn : op == PLDA_SIDE_MAX ? mx : op == PLDA_SIDE_SUM ? sm : op == PLDA_SIDE_ABSDIFF ? ad : pr;
+}
+
+// The labelled pass over K matrices, or (SIDES) over S.K matrices and K - S.K sides: block b writes part[b].  Traversal and
+// labelling of calib_pass_strip_kernel.
 // Resources on gfx950 (kernel-resource-usage; VGPRs per lane, no AGPRs; scratch 0, SGPR and VGPR spills 0 in every row):
 //     K                  1     2     3     4     5     6     7     8
-//     labelled pass     94   122   130   156   162   188   214   244     waves per SIMD 5 4 3 3 3 2 2 2
+//     labelled pass     94   122   130   156   162   188   214   244     waves per SIMD 5 4 3 3 3 2 2 2  (SIDES or not)
 //     list pass         60    69    86   103   122   143   166   191
 //     map               16    20    24    28    32    36    40    44
+//     side map          20    26    34    42    50    58    66    74
 // fusion_reduce_kernel: 73.  Three things keep the K = 8 labelled pass inside the 256 registers of two waves per SIMD:
 //   * the file is compiled without machine LICM (build.py, which says what the compiler does with it on and how to
 //     reproduce this table): hoisted out of the walk, the fp64 constants of exp / log1p sit in some forty registers for the
@@ -273,15 +294,33 @@ void fusion_side_launch_map(plda_handle *h, const FusionSideArgs &S, int T, int6
 //     per-thread bit mask, instead of 4 K + 2 K scalar registers held across the account.
 // amdgpu_waves_per_eu(2) states the budget; nothing is spilled to meet it.
 //
-// REQUIREMENT of the re-read: `P` is the FIRST kernel parameter, so that it lies at offset 0 of the kernel-argument segment
+// REQUIREMENT of the re-read: the argument record `S` is the FIRST kernel parameter in both instantiations, and the
+// FusionArgs the first member of a FusionSideArgs, so that it lies at offset 0 of the kernel-argument segment
 // (explicit arguments are laid out in declaration order from offset 0, a by-value aggregate in place; hidden arguments follow
 // them).  Whoever reorders the parameters must move the re-read with them: nothing else would notice.  The empty asm beside
 // it has no instruction; its "+s" / "+v" operands only make the three values opaque once per step, so that the loads, the
 // bit tests of `vec` and the column bounds are recomputed there instead of being held in scalar registers across the account.
-template <int K>
+//
+// THE SIDE BRANCH (SIDES) lives in the load stage, where the account's registers are not yet live: the instantiations with
+// it report the figures of those without exactly.  A side being a matrix of pitch 0, the address, the per-slot choice between
+// 16-byte and scalar loads and the column bounds are the matrix's own code; the four test values are RE-READ per row from the
+// L2-resident vector (a plain load, where a matrix streams with a non-temporal one), enrol[row] is one scalar load
+// (wave-uniform address, constant address space), and the op is a wave-uniform select over the five fp32 results: about 12
+// fp32 VALU instructions per side per trial (the five results, four selects, the column bound) beside the account's 221+
+// fp64 ones -- MEASURED, they are not free: 20 000 x 20 000 at 2.39 GHz, (K, Q) = (1, 3) 5.80 ms against 4.86 ms for the
+// matrix pass on materialised sides, (1, 7) 10.35 against 8.27 ms (profiles/fusion_side_*.json), the pass being bound by VALU
+// issue.  A wave-uniform BRANCH on the op (one body of 1 - 2 instructions per value) was tried and not kept: at K = 8 it
+// spills two scalar registers (245 VGPRs); it is the next step, for K <= 7 or with the scalar pressure of the K = 8 walk
+// reduced first.  Holding the 4 Q test values in registers across the walk instead was not built: the walk already sits at
+// 244 of 256 VGPRs at K = 8 and 130 .. 214 in between, so the persistent floats fit only the smallest K, and the pass is
+// bound by fp64 VALU issue, not by these loads (has the measurement).  One form for every (K, Q).
+// Elements beyond the last column get 0.f, as a matrix's loads give them: they count for nothing, but a NaN from enrol[row]
+// in such a lane would otherwise reach the accumulators through 0 * NaN.
+template <int K, bool SIDES>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2)))
-void fusion_pass_strip_kernel(const FusionArgs P, int64_t M, int64_t Nt, const int64_t *__restrict__ espk,
+void fusion_pass_strip_kernel(const FusionKernelArgs<SIDES> S, int64_t M, int64_t Nt, const int64_t *__restrict__ espk,
                               const int64_t *__restrict__ tspk, int64_t rows_per_wg, plda_fusion_record *__restrict__ part) {
+  const FusionArgs &P = fusion_systems(S);
   constexpr int U = fusion_rows_in_flight<K>();
   const int64_t strips = (Nt + FUSION_STRIP - 1) / FUSION_STRIP;
   const int64_t strip = blockIdx.x % strips, slice = blockIdx.x / strips;
@@ -294,7 +333,7 @@ void fusion_pass_strip_kernel(const FusionArgs P, int64_t M, int64_t Nt, const i
     ok[e] = col + e < Nt;
     ts[e] = ok[e] ? tspk[col + e] : 0;
   }
-  unsigned vec = 0;                          // bit k: system k takes 16-byte loads (one register, not K lane masks)
+  unsigned vec = 0;                          // bit k: slot k takes 16-byte loads (one register, not K lane masks; a side's pitch 0 passes)
 #pragma unroll
   for (int k = 0; k < K; ++k) vec |= (((P.ld[k] & 3) == 0) && ((reinterpret_cast<uintptr_t>(P.s[k]) & 15) == 0) && ok[3]) ? 1u << k : 0u;
   FusionAcc<K> A;
@@ -305,18 +344,29 @@ void fusion_pass_strip_kernel(const FusionArgs P, int64_t M, int64_t Nt, const i
     FusionArgsPtr pp = (FusionArgsPtr)__builtin_amdgcn_kernarg_segment_ptr();
     int64_t colv = col;
     asm volatile("" : "+s"(pp), "+v"(vec), "+v"(colv));   // (nor are the bit tests of `vec` and the column bounds hoisted into lane masks)
+    [[maybe_unused]] const FusionSideArgsPtr sp = (FusionSideArgsPtr)pp;   // SIDES: the same record, with what follows the FusionArgs
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       if (row + u >= r1) break;
 #pragma unroll
       for (int k = 0; k < K; ++k) {
         const float *src = const_cast<const float *>(pp->s[k]) + (row + u) * pp->ld[k] + col;
+        bool side = false;                                   // wave-uniform; slot 0 is always a matrix
+        if constexpr (SIDES) side = k > 0 && k >= sp->K;
         if (vec >> k & 1u) {
-          const f32x4f x = __builtin_nontemporal_load(reinterpret_cast<const f32x4f *>(src));
+          const f32x4f x = side ? *reinterpret_cast<const f32x4f *>(src) : __builtin_nontemporal_load(reinterpret_cast<const f32x4f *>(src));
           v[u][k][0] = x.x; v[u][k][1] = x.y; v[u][k][2] = x.z; v[u][k][3] = x.w;
         } else {
 #pragma unroll
           for (int e = 0; e < 4; ++e) v[u][k][e] = colv + e < Nt ? src[e] : 0.f;
+        }
+        if constexpr (SIDES) {
+          if (side) {
+            const float ev = ((SideEnrolPtr)sp->enrol[k])[row + u];
+            const int op = sp->op[k];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[u][k][e] = colv + e < Nt ? fusion_side_value(op, ev, v[u][k][e]) : 0.f;
+          }
         }
       }
     }
@@ -451,6 +501,9 @@ __global__ __launch_bounds__(1024) void fusion_reduce_kernel(const plda_fusion_r
 // out[i, j] = (float)chain(b; s_0[i, j] .. s_{K-1}[i, j]): strips of 1024 columns, rows dealt out over gridDim.y.  In place over
 // one of the inputs is allowed (an element is read from every system, then written, by the same thread); columns
 // [Nt, ld_out) are not touched.  16-byte access per system and for the output where base and pitch allow.
+// (Giving this kernel fusion_side_map_kernel's form -- one template on <K, SIDES> -- was built and measured: 20 / 22 / .. / 46
+// VGPRs and 30 .. 47 SGPRs, and at 20 000 x 20 000 its medians lay within 0.5 % of this form's, but at K = 1 outside the spread of
+// this form's own two medians, which was the bar: profiles/fusion_map_merge.json.  So matrices keep this text.)
 template <int K>
 __global__ __launch_bounds__(256) void fusion_map_kernel(const FusionArgs P, int64_t M, int64_t Nt, float *out, int64_t ld_out) {
   const int64_t col = (int64_t)blockIdx.x * FUSION_STRIP + (int64_t)threadIdx.x * 4;
@@ -489,10 +542,79 @@ __global__ __launch_bounds__(256) void fusion_map_kernel(const FusionArgs P, int
   }
 }
 
-#endif  // PLDA_FUSION_SHARED_ONLY (the kernels)
+// The map over S.K matrices and K - S.K sides: out[i, j] = (float)chain(b; s_0[i, j] .. , q_0(i, j) ..), fusion_map_kernel's
+// walk and rules (in place over one of the matrices allowed, columns [Nt, ld_out) not touched).  Here the four test values of
+// every side ARE held in registers (tv, 4 K floats; the kernel has room -- the table at fusion_pass_strip_kernel), so a trial
+// costs the matrix reads, one scalar load per side per row and the store: 4 S.K + 4 bytes instead of 4 K + 4.
+template <int K>
+__global__ __launch_bounds__(256) void fusion_side_map_kernel(const FusionSideArgs S, int64_t M, int64_t Nt, float *out, int64_t ld_out) {
+  const int64_t col = (int64_t)blockIdx.x * FUSION_STRIP + (int64_t)threadIdx.x * 4;
+  if (col >= Nt) return;
+  const bool full = col + 3 < Nt;
+  unsigned vec = 0;                          // bit k: slot k takes 16-byte loads; bit K: the output takes 16-byte stores
+  float tv[K][4];                            // slot k >= S.K: the side's test values of this thread's columns
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    const bool wide = ((S.P.ld[k] & 3) == 0) && ((reinterpret_cast<uintptr_t>(S.P.s[k]) & 15) == 0) && full;
+    vec |= wide ? 1u << k : 0u;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) tv[k][e] = 0.f;
+    if (k > 0 && k >= S.K) {
+      const float *src = S.P.s[k] + col;
+      if (wide) {
+        const f32x4f q = *reinterpret_cast<const f32x4f *>(src);
+        tv[k][0] = q.x; tv[k][1] = q.y; tv[k][2] = q.z; tv[k][3] = q.w;
+      } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) tv[k][e] = col + e < Nt ? src[e] : 0.f;
+      }
+    }
+  }
+  vec |= (((ld_out & 3) == 0) && ((reinterpret_cast<uintptr_t>(out) & 15) == 0) && full) ? 1u << K : 0u;
+  for (int64_t row = blockIdx.y; row < M; row += gridDim.y) {
+    // bases, pitches, weights, enrol vectors and ops are re-read from the kernel-argument segment per row (scalar loads; S is
+    // the FIRST parameter, see fusion_pass_strip_kernel) and the 16-byte flags sit in one per-thread bit mask: held across the
+    // loop they are some 90 scalar registers at K = 8, which spilled from K = 6 on (14 / 30 / 46 SGPRs)
+    FusionSideArgsPtr pp = (FusionSideArgsPtr)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(pp), "+v"(vec));
+    const double c = pp->P.c;
+    double y[4] = {c, c, c, c};
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      float x[4];
+      if (k > 0 && k >= pp->K) {
+        const float ev = ((SideEnrolPtr)pp->enrol[k])[row];
+        const int op = pp->op[k];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) x[e] = fusion_side_value(op, ev, tv[k][e]);
+      } else {
+        const float *src = const_cast<const float *>(pp->P.s[k]) + row * pp->P.ld[k] + col;
+        if (vec >> k & 1u) {
+          const f32x4f q = *reinterpret_cast<const f32x4f *>(src);
+          x[0] = q.x; x[1] = q.y; x[2] = q.z; x[3] = q.w;
+        } else {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) x[e] = col + e < Nt ? src[e] : 0.f;
+        }
+      }
+      const double ak = pp->P.a[k];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) y[e] = fma(ak, (double)x[e], y[e]);
+    }
+    float *dst = out + row * ld_out + col;
+    if (vec >> K & 1u) {
+      f32x4f q;
+      q.x = (float)y[0]; q.y = (float)y[1]; q.z = (float)y[2]; q.w = (float)y[3];
+      *reinterpret_cast<f32x4f *>(dst) = q;
+    } else {
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        if (col + e < Nt) dst[e] = (float)y[e];
+    }
+  }
+}
 
 // ------------------------------------------------------------------------------------ host drivers
-#ifndef PLDA_FUSION_SHARED_ONLY
 static int64_t fusion_strip_blocks(int64_t rows, int64_t Nt, int64_t *rows_per_wg) {
   const int64_t strips = ceil_div(Nt, (int64_t)FUSION_STRIP);
   const int64_t slices = std::max<int64_t>(1, std::min<int64_t>(rows, FUSION_MAX_BLOCKS / strips));
@@ -502,7 +624,7 @@ static int64_t fusion_strip_blocks(int64_t rows, int64_t Nt, int64_t *rows_per_w
 static int64_t fusion_list_blocks(int64_t n) { return std::min<int64_t>(ceil_div(n, 256), FUSION_MAX_BLOCKS); }
 
 // the labelled trials of a fusion call: K matrices under one pair of speaker-id arrays, or K target + K non-target lists.
-// With sides (K25, fusion_side.hip): K counts every FEATURE, the first `nsys` of them matrices and the rest sides -- slot
+// With sides (K25): K counts every FEATURE, the first `nsys` of them matrices and the rest sides -- slot
 // k >= nsys holds the side's test vector in s[k] (pitch 0), its enrol vector in enrol[k] and its op in op[k].  Operand form:
 // `slabs` produces system 0 one row slab at a time (s[0] / ld[0] are then filled per slab).
 struct FusionSource {
@@ -517,49 +639,53 @@ struct FusionSource {
   const TrialSource *slabs = nullptr;
 };
 
-template <int K> static void fusion_launch_strip(plda_handle *h, const FusionArgs &P, int64_t rows, int64_t Nt, const int64_t *espk,
-                                                 const int64_t *tspk, int64_t blocks, int64_t rpw, plda_fusion_record *part) {
-  fusion_pass_strip_kernel<K><<<(unsigned)blocks, 256, 0, h->stream>>>(P, rows, Nt, espk, tspk, rpw, part);
+// the kernel arguments of `src` at weights a[src.K] and offset c, the enrol vectors of its sides offset to row r0 of the call
+static FusionSideArgs fusion_kernel_args(const FusionSource &src, const double *a, double c, int64_t r0) {
+  FusionSideArgs S = {};
+  for (int k = 0; k < src.K; ++k) { S.P.s[k] = src.s[k]; S.P.ld[k] = src.ld[k]; S.P.a[k] = a[k]; }
+  S.P.c = c;
+  S.K = src.nsys;
+  for (int k = src.nsys; k < src.K; ++k) { S.enrol[k] = src.enrol[k] + r0; S.op[k] = src.op[k]; }
+  return S;
 }
-template <int K> static void fusion_launch_list(plda_handle *h, const FusionArgs &P, int64_t n, int cls, int64_t blocks,
-                                                plda_fusion_record *part) {
-  if (cls) fusion_pass_list_kernel<K, 1><<<(unsigned)blocks, 256, 0, h->stream>>>(P, n, part);
-  else fusion_pass_list_kernel<K, 0><<<(unsigned)blocks, 256, 0, h->stream>>>(P, n, part);
-}
-template <int K> static void fusion_launch_map(plda_handle *h, const FusionArgs &P, int64_t M, int64_t Nt, float *out, int64_t ld_out) {
-  const dim3 grid((unsigned)ceil_div(Nt, (int64_t)FUSION_STRIP), (unsigned)std::min<int64_t>(M, 4096));
-  fusion_map_kernel<K><<<grid, 256, 0, h->stream>>>(P, M, Nt, out, ld_out);
-}
+
+// the launches: instantiation K = the number of feature slots, SIDES where some of them are sides (S.K matrices < K)
 #define FUSION_DISPATCH(K, CALL)                                              \
   switch (K) {                                                               \
     case 1: CALL(1); break; case 2: CALL(2); break; case 3: CALL(3); break; case 4: CALL(4); break; \
     case 5: CALL(5); break; case 6: CALL(6); break; case 7: CALL(7); break; default: CALL(8); break; \
   }
 
-static void fusion_dispatch_strip(plda_handle *h, int K, const FusionArgs &P, int64_t rows, int64_t Nt, const int64_t *espk,
+static void fusion_dispatch_strip(plda_handle *h, int K, const FusionSideArgs &S, int64_t rows, int64_t Nt, const int64_t *espk,
                                   const int64_t *tspk, int64_t blocks, int64_t rpw, plda_fusion_record *part) {
-#define FUSION_CALL(KK) fusion_launch_strip<KK>(h, P, rows, Nt, espk, tspk, blocks, rpw, part)
+#define FUSION_CALL(KK)                                                                                                        \
+  if (S.K != K) fusion_pass_strip_kernel<KK, true><<<(unsigned)blocks, 256, 0, h->stream>>>(S, rows, Nt, espk, tspk, rpw, part); \
+  else fusion_pass_strip_kernel<KK, false><<<(unsigned)blocks, 256, 0, h->stream>>>(S.P, rows, Nt, espk, tspk, rpw, part)
   FUSION_DISPATCH(K, FUSION_CALL)
 #undef FUSION_CALL
 }
-
-// the side half of the kernel arguments (slots nsys .. K), with the enrol vectors offset to row r0 of the call
-static FusionSideArgs fusion_side_args(const FusionArgs &P, const FusionSource &src, int64_t r0) {
-  FusionSideArgs S = {};
-  S.P = P;
-  S.K = src.nsys;
-  for (int k = src.nsys; k < src.K; ++k) { S.enrol[k] = src.enrol[k] + r0; S.op[k] = src.op[k]; }
-  return S;
+static void fusion_dispatch_list(plda_handle *h, int K, const FusionArgs &P, int64_t n, int cls, int64_t blocks, plda_fusion_record *part) {
+#define FUSION_CALL(KK)                                                                            \
+  if (cls) fusion_pass_list_kernel<KK, 1><<<(unsigned)blocks, 256, 0, h->stream>>>(P, n, part);    \
+  else fusion_pass_list_kernel<KK, 0><<<(unsigned)blocks, 256, 0, h->stream>>>(P, n, part)
+  FUSION_DISPATCH(K, FUSION_CALL)
+#undef FUSION_CALL
 }
+static void fusion_dispatch_map(plda_handle *h, int K, const FusionSideArgs &S, int64_t M, int64_t Nt, float *out, int64_t ld_out) {
+  const dim3 grid((unsigned)ceil_div(Nt, (int64_t)FUSION_STRIP), (unsigned)std::min<int64_t>(M, 4096));
+#define FUSION_CALL(KK)                                                                             \
+  if (S.K != K) fusion_side_map_kernel<KK><<<grid, 256, 0, h->stream>>>(S, M, Nt, out, ld_out);     \
+  else fusion_map_kernel<KK><<<grid, 256, 0, h->stream>>>(S.P, M, Nt, out, ld_out)
+  FUSION_DISPATCH(K, FUSION_CALL)
+#undef FUSION_CALL
+}
+#undef FUSION_DISPATCH
 
 // One pass over `src` at (a, c, theta) -> *rec (host); synchronises the stream.  A non-finite score, or a class without
 // trials, is PLDA_E_INVAL (the record is written all the same).  A matrix call is one piece on the grid of its shape; the
 // operand form is one piece per slab (trial_source.hpp), the partials of all slabs sized before anything is launched, as
 // calib_pass does, and reduced together in slab order.
 static int fusion_pass(plda_handle *h, const FusionSource &src, const double *a, double c, double theta, plda_fusion_record *rec) {
-  FusionArgs P = {};
-  for (int k = 0; k < src.K; ++k) { P.s[k] = src.s[k]; P.ld[k] = src.ld[k]; P.a[k] = a[k]; }
-  P.c = c; P.theta = theta;
   const TrialSource whole = TrialSource::matrix(src.s[0], src.ld[0], src.M, src.Nt, src.espk, src.tspk);
   const TrialSource &ts = src.slabs ? *src.slabs : whole;
   int64_t total = 0;
@@ -580,26 +706,22 @@ static int fusion_pass(plda_handle *h, const FusionSource &src, const double *a,
   plda_fusion_record *part = h->fusion_part.as<plda_fusion_record>();
   if (src.lists) {
     const int64_t bp = fusion_list_blocks(src.M), bn = fusion_list_blocks(src.Nt);
-#define FUSION_CALL(KK) fusion_launch_list<KK>(h, P, src.M, 1, bp, part)
-    FUSION_DISPATCH(src.K, FUSION_CALL)
-#undef FUSION_CALL
+    FusionArgs P = fusion_kernel_args(src, a, c, 0).P;
+    P.theta = theta;
+    fusion_dispatch_list(h, src.K, P, src.M, 1, bp, part);
     PLDA_LAUNCH_CHECK(h);
     for (int k = 0; k < src.K; ++k) P.s[k] = src.neg[k];
-#define FUSION_CALL(KK) fusion_launch_list<KK>(h, P, src.Nt, 0, bn, part + bp)
-    FUSION_DISPATCH(src.K, FUSION_CALL)
-#undef FUSION_CALL
+    fusion_dispatch_list(h, src.K, P, src.Nt, 0, bn, part + bp);
     PLDA_LAUNCH_CHECK(h);
   } else {
     int64_t at = 0;
     PLDA_TRY(for_each_piece(ts, [&](const TrialPiece &pc) -> int {
       int64_t rpw = 0;
       const int64_t blocks = fusion_strip_blocks(pc.rows, pc.Nt, &rpw);
-      P.s[0] = pc.scores; P.ld[0] = pc.ld;
-      if (src.K == src.nsys) {
-        fusion_dispatch_strip(h, src.K, P, pc.rows, pc.Nt, pc.espk, src.tspk, blocks, rpw, part + at);
-      } else {
-        fusion_side_launch_strip(h, fusion_side_args(P, src, pc.espk - src.espk), src.K, pc.rows, pc.Nt, pc.espk, src.tspk, blocks, rpw, part + at);
-      }
+      FusionSideArgs S = fusion_kernel_args(src, a, c, pc.espk - src.espk);
+      S.P.theta = theta;
+      S.P.s[0] = pc.scores; S.P.ld[0] = pc.ld;
+      fusion_dispatch_strip(h, src.K, S, pc.rows, pc.Nt, pc.espk, src.tspk, blocks, rpw, part + at);
       PLDA_LAUNCH_CHECK(h);
       at += blocks;
       return PLDA_OK;
@@ -793,23 +915,23 @@ int fusion_fit_lists_device(plda_handle *h, int K, const float *const *dpos, int
   PLDA_TRY(fusion_list_source(h, "fusion_fit", K, dpos, np, dneg, nn, &s));
   return fusion_fit(h, s, prior, tol, max_iter, out);
 }
+// out = (float)chain(b; the features of `src`), the one map behind both entry points (a call without sides is fusion_map's)
+static int fusion_map(plda_handle *h, const FusionSource &src, const double *a, double b, float *out, int64_t ld_out) {
+  if (ceil_div(src.Nt, (int64_t)FUSION_STRIP) > (int64_t)0x7fffffff)
+    return fail(h, PLDA_E_CAPACITY, src.K == src.nsys ? "fusion_map: too many column strips" : "fusion_side_map: too many column strips");
+  fusion_dispatch_map(h, src.K, fusion_kernel_args(src, a, b, 0), src.M, src.Nt, out, ld_out);
+  PLDA_LAUNCH_CHECK(h);
+  return PLDA_OK;
+}
 int fusion_map_device(plda_handle *h, int K, const float *const *dscores, const int64_t *ld, int64_t M, int64_t Nt, const double *a,
                       double b, float *dout, int64_t ld_out) {
   if (!a || !dout || ld_out < Nt) return fail(h, PLDA_E_INVAL, "fusion_map: bad argument");
   FusionSource s;
   PLDA_TRY(fusion_matrix_source(h, "fusion_map", K, dscores, ld, M, Nt, nullptr, nullptr, false, &s));
-  if (ceil_div(Nt, (int64_t)FUSION_STRIP) > (int64_t)0x7fffffff) return fail(h, PLDA_E_CAPACITY, "fusion_map: too many column strips");
-  FusionArgs P = {};
-  for (int k = 0; k < K; ++k) { P.s[k] = s.s[k]; P.ld[k] = s.ld[k]; P.a[k] = a[k]; }
-  P.c = b;
-#define FUSION_CALL(KK) fusion_launch_map<KK>(h, P, M, Nt, dout, ld_out)
-  FUSION_DISPATCH(K, FUSION_CALL)
-#undef FUSION_CALL
-  PLDA_LAUNCH_CHECK(h);
-  return PLDA_OK;
+  return fusion_map(h, s, a, b, dout, ld_out);
 }
 
-// ------------------------------------------------------------------------------------ sides (K25; kernels in fusion_side.hip)
+// ------------------------------------------------------------------------------------ sides (K25)
 // appends the Q sides of a call to a source that holds its K systems: feature slot K + q is side q
 static int fusion_side_source(plda_handle *h, const char *fn, int K, int Q, const plda_fusion_side *sides, FusionSource *s) {
   if (Q < 0 || K + Q > FUSION_KMAX)
@@ -848,14 +970,7 @@ int fusion_side_map_device(plda_handle *h, int K, const float *const *dscores, c
   FusionSource s;
   PLDA_TRY(fusion_matrix_source(h, "fusion_side_map", K, dscores, ld, M, Nt, nullptr, nullptr, false, &s));
   PLDA_TRY(fusion_side_source(h, "fusion_side_map", K, Q, sides, &s));
-  if (Q == 0) return fusion_map_device(h, K, dscores, ld, M, Nt, a, b, dout, ld_out);
-  if (ceil_div(Nt, (int64_t)FUSION_STRIP) > (int64_t)0x7fffffff) return fail(h, PLDA_E_CAPACITY, "fusion_side_map: too many column strips");
-  FusionArgs P = {};
-  for (int k = 0; k < s.K; ++k) { P.s[k] = s.s[k]; P.ld[k] = s.ld[k]; P.a[k] = a[k]; }
-  P.c = b;
-  fusion_side_launch_map(h, fusion_side_args(P, s, 0), s.K, M, Nt, dout, ld_out);
-  PLDA_LAUNCH_CHECK(h);
-  return PLDA_OK;
+  return fusion_map(h, s, a, b, dout, ld_out);
 }
 
 // the operand forms: system 0 is this model's own matrix, re-scored slab by slab once per pass (operand_slabs.hip)
@@ -887,7 +1002,5 @@ int score_fusion_side_fit_device(plda_handle *h, const double *dU, const int32_t
   PLDA_TRY(score_fusion_side_source(h, "score_fusion_side_fit", dU, dn, n_uniform, M, dV, Nt, dzmean, dzstd, despk, dtspk, Q, sides, out, &os, &ts, &s));
   return fusion_fit(h, s, prior, tol, max_iter, out);
 }
-
-#endif  // PLDA_FUSION_SHARED_ONLY (the host drivers)
 
 }  // namespace plda

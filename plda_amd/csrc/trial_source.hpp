@@ -208,7 +208,7 @@ int fusion_fit_lists_device(plda_handle *h, int K, const float *const *dpos, int
                             double prior, double tol, int max_iter, plda_fusion_fit *out);
 int fusion_map_device(plda_handle *h, int K, const float *const *dscores, const int64_t *ld, int64_t M, int64_t Nt, const double *a,
                       double b, float *dout, int64_t ld_out);
-// K matrices + Q sides formed in registers (K25; kernels in fusion_side.hip); `sides` is a HOST array of Q entries
+// K matrices + Q sides formed in registers (K25; kernels in fusion.hip); `sides` is a HOST array of Q entries
 int fusion_side_pass_device(plda_handle *h, int K, const float *const *dscores, const int64_t *ld, int Q, const plda_fusion_side *sides,
                             int64_t M, int64_t Nt, const int64_t *despk, const int64_t *dtspk, const double *a, double c, double theta,
                             plda_fusion_record *out);

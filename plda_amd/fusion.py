@@ -234,7 +234,7 @@ def apply_dev(engine, dscores, ld, m, nt, fusion, dout, ld_out):
                                                        _p(dout), int(ld_out)))
 
 
-# ---------------------------------------------------------------------------------------------- sides (K25, csrc/fusion_side.hip)
+# ---------------------------------------------------------------------------------------------- sides (K25, csrc/fusion.hip)
 SIDE_OPS = ("min", "max", "sum", "absdiff", "prod")          # PLDA_SIDE_MIN .. PLDA_SIDE_PROD of include/plda_hip.h
 SIDE_DTYPE = np.dtype([("enrol", np.uint64), ("test", np.uint64), ("op", np.int32), ("reserved", np.int32)], align=True)
 assert SIDE_DTYPE.itemsize == 24

@@ -1395,7 +1395,7 @@ class MPlda(object):
         keep = None     # noqa: F841  (the side vectors had to outlive the enqueued map)
         return S.cpu().numpy()
 
-    # ------------------------------------------------- quality-aware calibration (K25; csrc/fusion_side.hip)
+    # ------------------------------------------------- quality-aware calibration (K25; csrc/fusion.hip)
     def _quality_sides(self, quality, ids, tids, m, nt, what):
         """`quality` = ((op, enrol_values, test_values), ...) -> `plda_amd.fusion.Side`s with device vectors.  Each values
         argument is a mapping {key: value} (looked up by the enrol / test keys) or a sequence in the order of enrol / test:

@@ -1,5 +1,5 @@
-"""Quality-aware calibration measurements: the side kernels of csrc/fusion_side.hip against the
-existing matrix kernels of csrc/fusion.hip on MATERIALISED sides -- the same library, the same process, the same trials.
+"""Quality-aware calibration measurements: the side instantiations of csrc/fusion.hip against its
+matrix kernels on MATERIALISED sides -- the same library, the same process, the same trials.
 
 Method: every arm is warmed first, then the two arms of a pair ALTERNATE (A B A B ...) between HIP events in one process, so
 that clock drift and whatever else moves during the run lands on both; per arm the median, minimum and maximum, and per pair
@@ -134,7 +134,7 @@ def main():
         sides7 = qualities(M, Nt, 7)
         mats = [materialised(s) for s in sides7]
         out_s, out_m = torch.empty_like(S), torch.empty_like(S)
-        out = {"what": "csrc/fusion_side.hip against csrc/fusion.hip on materialised sides", "M": M, "Nt": Nt, "trials": M * Nt, "ops": ops}
+        out = {"what": "the side kernels of csrc/fusion.hip against its matrix kernels on materialised sides", "M": M, "Nt": Nt, "trials": M * Nt, "ops": ops}
         c, theta = -0.4, 0.3
         for q in (3, 7):
             T = 1 + q

@@ -2,13 +2,17 @@
 // the kernel text itself (kernels.inc, cut out of fusion.hip by the test) compiled for the host, 256 host threads per block, every
 // cross-lane operation (ballot, readlane, shuffles, the wave sum, the block barrier) through barriers.  It checks the LOGIC of the
 // walk -- steps of U rows, partial steps, edges, the cooperative target sum, the block and grid reductions -- not the GPU's
-// arithmetic: exp / log1p are the host's, the wave sum adds in lane order.
+// arithmetic: exp / log1p are the host's, the wave sum adds in lane order.  With Q sides it runs the SIDES = true instantiation
+// on K + Q feature slots, the kernel-argument segment then being the whole FusionSideArgs.
+#include <algorithm>
 #include <cmath>
+#include <cstddef>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <pthread.h>
+#include <type_traits>
 #include <vector>
 #include "plda_hip.h"
 #define __device__
@@ -79,31 +83,47 @@ static void run_grid(unsigned blocks, unsigned threads, void (*fn)(void *), void
     for (unsigned t = 0; t < threads; ++t) pthread_join(th[t], nullptr);
   }
 }
-struct Ctx { FusionArgs P; int64_t M, Nt; const int64_t *es, *ts; int64_t rpw; plda_fusion_record *part; int64_t nparts; int K; };
-template <int K> static void strip_fn(void *c) { Ctx *x = (Ctx *)c; fusion_pass_strip_kernel<K>(x->P, x->M, x->Nt, x->es, x->ts, x->rpw, x->part); }
+struct Ctx { FusionSideArgs S; int64_t M, Nt; const int64_t *es, *ts; int64_t rpw; plda_fusion_record *part; int64_t nparts; int K; };
+template <int K, bool SIDES> static void strip_fn(void *c) {
+  Ctx *x = (Ctx *)c;
+  if constexpr (SIDES) fusion_pass_strip_kernel<K, true>(x->S, x->M, x->Nt, x->es, x->ts, x->rpw, x->part);
+  else fusion_pass_strip_kernel<K, false>(x->S.P, x->M, x->Nt, x->es, x->ts, x->rpw, x->part);
+}
+template <int K> static void (*strip_of(bool sides))(void *) { return sides ? strip_fn<K, true> : strip_fn<K, false>; }
 static void reduce_fn(void *c) { Ctx *x = (Ctx *)c; fusion_reduce_kernel(x->part, x->nparts, x->K, x->part + x->nparts); }
 
-// usage: emu K M Nt in.bin out.bin ; in.bin: K x (ld int64, off int64), a[K], c, theta, es[M], ts[Nt], then per system (off + M * ld) floats
+// usage: emu K M Nt in.bin out.bin [Q] ; in.bin: K x (ld int64, off int64), Q x (op int64, off int64, test floats int64), a[K + Q],
+// c, theta, es[M], ts[Nt], then per system (off + M * ld) floats, then per side M enrol floats and its test floats (the vector
+// starts `off` floats into them; what follows its Nt values is padding that the kernel must not use)
 int main(int argc, char **argv) {
-  const int K = atoi(argv[1]);
+  const int K = atoi(argv[1]), Q = argc > 6 ? atoi(argv[6]) : 0, T = K + Q;
   const int64_t M = atoll(argv[2]), Nt = atoll(argv[3]);
+  if (K < 1 || Q < 0 || T > FUSION_KMAX) return 2;
   FILE *f = fopen(argv[4], "rb");
   Ctx x;
-  memset(&x.P, 0, sizeof(x.P));
-  int64_t ld[8], off[8];
+  memset(&x.S, 0, sizeof(x.S));
+  FusionArgs &P = x.S.P;
+  int64_t ld[8], off[8], op[8], toff[8], tlen[8];
   for (int k = 0; k < K; ++k) { fread(&ld[k], 8, 1, f); fread(&off[k], 8, 1, f); }
-  fread(x.P.a, 8, K, f); fread(&x.P.c, 8, 1, f); fread(&x.P.theta, 8, 1, f);
+  for (int k = K; k < T; ++k) { fread(&op[k], 8, 1, f); fread(&toff[k], 8, 1, f); fread(&tlen[k], 8, 1, f); }
+  fread(P.a, 8, T, f); fread(&P.c, 8, 1, f); fread(&P.theta, 8, 1, f);
   std::vector<int64_t> es(M), ts(Nt);
   fread(es.data(), 8, M, f); fread(ts.data(), 8, Nt, f);
-  std::vector<float *> bufs;
-  for (int k = 0; k < K; ++k) {
-    float *b = (float *)aligned_alloc(64, ((off[k] + M * ld[k]) * 4 + 63) / 64 * 64);
-    fread(b, 4, off[k] + M * ld[k], f);
-    bufs.push_back(b);
-    x.P.s[k] = b + off[k]; x.P.ld[k] = ld[k];
+  auto floats = [&](int64_t n) {
+    float *b = (float *)aligned_alloc(64, (n * 4 + 63) / 64 * 64);
+    fread(b, 4, n, f);
+    return b;
+  };
+  for (int k = 0; k < K; ++k) { P.s[k] = floats(off[k] + M * ld[k]) + off[k]; P.ld[k] = ld[k]; }
+  for (int k = K; k < T; ++k) {
+    if (toff[k] + Nt > tlen[k]) return 2;
+    x.S.enrol[k] = floats(M);
+    P.s[k] = floats(tlen[k]) + toff[k]; P.ld[k] = 0;
+    x.S.op[k] = (int32_t)op[k];
   }
+  x.S.K = K;
   fclose(f);
-  g_kernarg = &x.P;
+  g_kernarg = &x.S;                          // the FusionArgs at offset 0, as in the kernel-argument segment
   const int64_t strips = ceil_div(Nt, (int64_t)FUSION_STRIP);
   const int64_t slices = std::max<int64_t>(1, std::min<int64_t>(M, FUSION_MAX_BLOCKS / strips));
   // the emulation creates 256 threads per block: keep the grid small (the library's rule with a cap of 8 slices)
@@ -112,8 +132,8 @@ int main(int argc, char **argv) {
   const int64_t total = strips * ceil_div(M, x.rpw);
   std::vector<plda_fusion_record> part(total + 1);
   memset(part.data(), 0xff, part.size() * sizeof(plda_fusion_record));
-  x.M = M; x.Nt = Nt; x.es = es.data(); x.ts = ts.data(); x.part = part.data(); x.nparts = total; x.K = K;
-  void (*fn)(void *) = K == 1 ? strip_fn<1> : K == 2 ? strip_fn<2> : K == 3 ? strip_fn<3> : K == 4 ? strip_fn<4> : K == 5 ? strip_fn<5> : K == 6 ? strip_fn<6> : K == 7 ? strip_fn<7> : strip_fn<8>;
+  x.M = M; x.Nt = Nt; x.es = es.data(); x.ts = ts.data(); x.part = part.data(); x.nparts = total; x.K = T;
+  void (*fn)(void *) = T == 1 ? strip_of<1>(Q) : T == 2 ? strip_of<2>(Q) : T == 3 ? strip_of<3>(Q) : T == 4 ? strip_of<4>(Q) : T == 5 ? strip_of<5>(Q) : T == 6 ? strip_of<6>(Q) : T == 7 ? strip_of<7>(Q) : strip_of<8>(Q);
   run_grid((unsigned)total, 256, fn, &x);
   run_grid(1, 1024, reduce_fn, &x);
   f = fopen(argv[5], "wb");

@@ -1,5 +1,5 @@
 """Host model of the side-information terms of a quality-aware calibration (include/plda_hip.h, "quality-aware
-calibration"; csrc/fusion_side.hip).  A side is ONE IEEE fp32 operation on a per-enrol-row and a per-test-column number;
+calibration"; csrc/fusion.hip).  A side is ONE IEEE fp32 operation on a per-enrol-row and a per-test-column number;
 everything after it -- the chain, the record, the Newton fit -- is tests/fusion_model.py on the MATERIALISED side, which is
 the contract the device is held to bit for bit.  Written from the header's table alone (plda_amd/fusion.py has its own)."""
 import numpy as np

@@ -1,4 +1,4 @@
-"""GPU: quality-aware calibration -- side-information terms in the fusion (csrc/fusion_side.hip; include/plda_hip.h
+"""GPU: quality-aware calibration -- side-information terms in the fusion (csrc/fusion.hip; include/plda_hip.h
 "quality-aware calibration"), every call through the C ABI.
 
 THE CONTRACT under test: a side pass, fit or map is BIT-IDENTICAL to the existing plda_fusion_pass_matrices_dev /
