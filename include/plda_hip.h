@@ -942,6 +942,87 @@ int plda_rocch_hull(int64_t T, const uint32_t *edge_key, const uint64_t *other_l
                     int64_t cap_vertices, plda_rocch *out, plda_rocch_vertex *vertices, double *llr);
 int plda_rocch_finish(int64_t n_vertices, plda_rocch_vertex *vertices, const uint32_t *below, const uint32_t *above);
 
+/* ---- trial keys: masked trials and per-condition lists (K26; csrc/partition.hip; what BOSARIS calls a Key).  For the matrix
+ * and operand forms above every one of the M x Nt pairs is a trial.  A key says which pairs are trials and which condition
+ * bucket each trial belongs to, and a stable multi-way partition turns a trials matrix -- resident, or produced slab by slab
+ * from the operands -- into score lists on the device, one per (bucket, class), for the device-list forms of the consumers.
+ *
+ * The key.  enrol_code[M] and test_code[Nt] are uint8 with values < n_enrol_codes / < n_test_codes, both
+ * 1 ... PLDA_KEY_MAX_CODES.  table[n_enrol_codes * n_test_codes] is a HOST int8 array, row-major by enrol code: entry
+ * (e, t) is the bucket 0 ... n_buckets - 1 of a pair with those codes, or -1: the pair is not a trial;
+ * 1 <= n_buckets <= PLDA_KEY_MAX_BUCKETS.  Class as everywhere: pair (i, j) is a target (class 1) iff
+ * enrol_spk[i] == test_spk[j], a non-target (class 0) otherwise.  A trial's list is L = 2 * bucket + class.  A code out of
+ * range, a table entry outside [-1, n_buckets), a limit exceeded or a NULL array: PLDA_E_INVAL with a message, nothing is
+ * written.
+ *
+ * The output.  Two device buffers of floats: dtar (class 1) and dnon (class 0).  In each, bucket 0's list comes first, then
+ * bucket 1's, ..., contiguously: list (b, c) is count[b][c] scores from offset[b][c] of its class buffer, and the first
+ * total[c] floats of a buffer are the POOLED list of that class, with no copy.  Nothing is written beyond total[c].
+ *
+ * The order (PLDA_PARTITION_STRIP = 256).  Within a list, trials are ordered by (column strip j / 256, row i, column j); for
+ * Nt <= 256 that is row-major order.  The order is a function of the key, the speaker ids and the shape alone: not of the
+ * scores, ld, the base pointer's alignment, the slab height of the operand form or anything the library chooses (slice
+ * height, grid).  K matrices partitioned with one key therefore give aligned lists (element k of list L is the same trial
+ * in each: the list forms of the fusion apply per bucket), and the fp64 sums the consumers form are reproducible to the bit.
+ * Scores are copied verbatim: the bits of -0.0, of every NaN and of +-Inf arrive unchanged (refusing non-finite scores
+ * stays the consumers' job); the padding columns [Nt, ld) are never read as data.
+ *
+ * plda_partition_plan: a pure host function (no handle, no GPU; the pattern of plda_rocch_hull; its message goes to
+ * plda_last_error(NULL)).  From HOST speaker ids and a key whose code arrays are HOST arrays it fills the record in
+ * O(M + Nt + n_enrol_codes * n_test_codes): the per-code counts and the table give every bucket's trials, a hash join of the
+ * speaker ids gives its targets.  Callers size the buffers from total[].
+ * plda_partition_matrix_dev: the key carries DEVICE code arrays (and the HOST table).  The ids and codes are brought to the
+ * host, checked and planned as above; cap_tar < total[1] or cap_non < total[0] (capacities in floats; a buffer may be NULL
+ * when its total is 0) is PLDA_E_INVAL before anything is written, with *plan_out filled so that the caller can size.  A
+ * counting kernel then reads ids and codes only -- its grand totals must equal the plan's, anything else is PLDA_E_HIP --
+ * and one kernel reads every score once and writes the selected ones.  The call synchronises for the counts; the partition
+ * kernel itself is enqueued on the handle's stream and not waited for.
+ * plda_score_partition_dev: the operand form (arguments as plda_score_eer_dev): the matrix is never held, only the selected
+ * trials are written; its lists are bit-identical to plda_score_matrix_dev + plda_partition_matrix_dev.
+ *
+ * The device-list forms of the consumers (plda_*_lists_dev): each is its _lists sibling on lists that are already on the
+ * device (two device pointers; the fusion's pos / neg stay HOST arrays of n_systems DEVICE pointers) -- no upload, the same
+ * argument checks and messages, results bit-identical to the host form on the same values in the same order.  Outputs are
+ * HOST structures and arrays as in the host forms. ---- */
+#define PLDA_KEY_MAX_CODES 128
+#define PLDA_KEY_MAX_BUCKETS 8
+#define PLDA_PARTITION_STRIP 256
+typedef struct plda_trial_key {
+  const uint8_t *enrol_code, *test_code;   /* [M], [Nt]: HOST for plda_partition_plan, DEVICE for the _dev forms */
+  const int8_t *table;                     /* HOST [n_enrol_codes * n_test_codes] */
+  int32_t n_enrol_codes, n_test_codes, n_buckets, reserved;
+} plda_trial_key;
+typedef struct plda_partition_record {     /* the plan of a partition; [bucket][class], class 1 = targets */
+  int64_t count[PLDA_KEY_MAX_BUCKETS][2];
+  int64_t offset[PLDA_KEY_MAX_BUCKETS][2]; /* a list's start within its class buffer, in floats */
+  int64_t total[2];
+} plda_partition_record;
+int plda_partition_plan(const int64_t *enrol_spk, int64_t M, const int64_t *test_spk, int64_t Nt, const plda_trial_key *key,
+                        plda_partition_record *plan);
+int plda_partition_matrix_dev(plda_handle *h, const float *dscores, int64_t ld, int64_t M, int64_t Nt, const int64_t *denrol_spk,
+                              const int64_t *dtest_spk, const plda_trial_key *key, float *dtar, int64_t cap_tar, float *dnon,
+                              int64_t cap_non, plda_partition_record *plan_out);
+int plda_score_partition_dev(plda_handle *h, const double *dU, const int32_t *dn_enrol, int32_t n_uniform, int64_t M,
+                             const double *dV, int64_t Nt, const double *dzmean, const double *dzstd, const int64_t *denrol_spk,
+                             const int64_t *dtest_spk, const plda_trial_key *key, float *dtar, int64_t cap_tar, float *dnon,
+                             int64_t cap_non, plda_partition_record *plan_out);
+int plda_eer_lists_dev(plda_handle *h, const float *dpos, int64_t np, const float *dneg, int64_t nn, double *out);
+int plda_det_lists_dev(plda_handle *h, const float *dpos, int64_t np, const float *dneg, int64_t nn, int32_t n_points, double *far,
+                       double *frr, double *thresholds);
+int plda_min_dcf_lists_dev(plda_handle *h, const float *dpos, int64_t np, const float *dneg, int64_t nn, int32_t n_points,
+                           const plda_dcf_point *points, plda_min_dcf *out, plda_min_dcf_info *info);
+int plda_calib_pass_lists_dev(plda_handle *h, const float *dpos, int64_t np, const float *dneg, int64_t nn, double a, double c,
+                              double theta, plda_calib_record *out_record);
+int plda_calib_fit_lists_dev(plda_handle *h, const float *dpos, int64_t np, const float *dneg, int64_t nn, double prior, double tol,
+                             int32_t max_iter, plda_calib_fit *out_fit);
+int plda_rocch_lists_dev(plda_handle *h, const float *dpos, int64_t np, const float *dneg, int64_t nn, int64_t cap_vertices,
+                         plda_rocch *out, plda_rocch_vertex *vertices, double *llr, plda_rocch_points *points,
+                         plda_rocch_info *info);
+int plda_fusion_pass_lists_dev(plda_handle *h, int32_t n_systems, const float *const *dpos, int64_t np, const float *const *dneg,
+                               int64_t nn, const double *a, double c, double theta, plda_fusion_record *out_record);
+int plda_fusion_fit_lists_dev(plda_handle *h, int32_t n_systems, const float *const *dpos, int64_t np, const float *const *dneg,
+                              int64_t nn, double prior, double tol, int32_t max_iter, plda_fusion_fit *out_fit);
+
 /* ---- several GPUs of one node: one process per GPU, one handle per process.  The reference
  * has no counterpart (one process, one thread; its native object libplda.MPlda, pldamodule.cpp:280-295, is the only
  * thing callers bind, so the sharded path lives behind the same object).

@@ -69,6 +69,17 @@ class PLDA(object):
         plda_amd.rocch.Pav holding the hull's vertices and the PAV llrs)."""
         return self._instance.min_cllr(enrol, test, test_speaker, znorm, cohort, top_k)
 
+    def partition(self, enrol, test, test_speaker, key=None, znorm=True, cohort=None, top_k=None, calibrate=False):
+        """The per-(condition bucket, class) score lists of the trials under a plda_amd.trialkey.TrialKey (None: every pair),
+        on the device; returns a plda_amd.trialkey.Partition."""
+        return self._instance.partition(enrol, test, test_speaker, key, znorm, cohort, top_k, calibrate)
+
+    def evaluate(self, enrol, test, test_speaker, key=None, points=((0.01, 1.0, 1.0),), znorm=True, cohort=None, top_k=None,
+                 calibrate=False, prior=0.5):
+        """EER, minDCF, actual DCF, Cllr and minCllr per condition bucket of a trial key, pooled and equalised; returns
+        {"buckets": {name: figures}, "pooled": figures, "equalised": means}."""
+        return self._instance.evaluate(enrol, test, test_speaker, key, points, znorm, cohort, top_k, calibrate, prior)
+
     def calibrate_pav(self, enrol, test, test_speaker, znorm=True, cohort=None, top_k=None):
         """Fit and store the PAV (pool adjacent violators) map of those trials; returns the plda_amd.rocch.Pav."""
         return self._instance.calibrate_pav(enrol, test, test_speaker, znorm, cohort, top_k)

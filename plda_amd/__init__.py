@@ -13,6 +13,7 @@ Layout (only what the hot path needs):
   diarize.py  speaker clustering: batched average-linkage AHC on score blocks (csrc/ahc.hip), cut() in pure NumPy; VBx resegmentation (csrc/vbx.hip); dense scoring in every recording's PCA subspace (csrc/dense_pca.hip)
   der.py      diarisation error rate under the optimal speaker mapping, and the sweep of one merge record over thresholds (csrc/der.hip)
               and its time-based form: overlapped reference speech, collar, UEM (csrc/der_time.hip)
+  trialkey.py trial keys: which pairs are trials and their condition buckets, the per-(bucket, class) score lists on the device and per-condition metrics (csrc/partition.hip)
   rttm.py     RTTM files and per-segment reference labels from reference turns; pure Python / NumPy
 """
 from .libplda import MPlda  # noqa: F401
@@ -23,8 +24,10 @@ from . import adaptation  # noqa: F401
 from . import diarize  # noqa: F401
 from . import der  # noqa: F401
 from . import rttm  # noqa: F401
+from . import trialkey  # noqa: F401
 from .calibration import Calibration  # noqa: F401
 from .fusion import Fusion  # noqa: F401
 from .adaptation import Adaptation  # noqa: F401
+from .trialkey import TrialKey  # noqa: F401
 
-__all__ = ["MPlda", "Calibration", "Fusion", "Adaptation", "calibration", "fusion", "identify", "adaptation", "diarize", "der", "rttm"]
+__all__ = ["MPlda", "Calibration", "Fusion", "Adaptation", "TrialKey", "trialkey", "calibration", "fusion", "identify", "adaptation", "diarize", "der", "rttm"]

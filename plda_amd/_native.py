@@ -134,6 +134,17 @@ SIGNATURES = {
     "plda_pav_map_dev": (C.c_int, [_vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _f64, _vp, _i64]),
     "plda_rocch_hull": (C.c_int, [_i64, _vp, _vp, _vp, _vp, _vp, _i32, C.c_uint64, C.c_uint64, _i64, _vp, _vp, _vp]),
     "plda_rocch_finish": (C.c_int, [_i64, _vp, _vp, _vp]),
+    "plda_partition_plan": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp]),
+    "plda_partition_matrix_dev": (C.c_int, [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp]),
+    "plda_score_partition_dev": (C.c_int, [_vp, _vp, _vp, _i32, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp]),
+    "plda_eer_lists_dev": (C.c_int, [_vp, _vp, _i64, _vp, _i64, _vp]),
+    "plda_det_lists_dev": (C.c_int, [_vp, _vp, _i64, _vp, _i64, _i32, _vp, _vp, _vp]),
+    "plda_min_dcf_lists_dev": (C.c_int, [_vp, _vp, _i64, _vp, _i64, _i32, _vp, _vp, _vp]),
+    "plda_calib_pass_lists_dev": (C.c_int, [_vp, _vp, _i64, _vp, _i64, _f64, _f64, _f64, _vp]),
+    "plda_calib_fit_lists_dev": (C.c_int, [_vp, _vp, _i64, _vp, _i64, _f64, _f64, _i32, _vp]),
+    "plda_rocch_lists_dev": (C.c_int, [_vp, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "plda_fusion_pass_lists_dev": (C.c_int, [_vp, _i32, _vp, _i64, _vp, _i64, _vp, _f64, _f64, _vp]),
+    "plda_fusion_fit_lists_dev": (C.c_int, [_vp, _i32, _vp, _i64, _vp, _i64, _f64, _f64, _i32, _vp]),
     "plda_affine_map_dev": (C.c_int, [_vp, _vp, _i64, _i64, _i64, _f64, _f64, _vp, _i64]),
     "plda_fusion_pass_matrices_dev": (C.c_int, [_vp, _i32, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _f64, _f64, _vp]),
     "plda_fusion_pass_lists": (C.c_int, [_vp, _i32, _vp, _i64, _vp, _i64, _vp, _f64, _f64, _vp]),

@@ -263,6 +263,16 @@ int with_host_lists(plda_handle *h, const char *fn, const float *pos, int64_t np
     return body(dpos, dneg);
   });
 }
+// The device-list entry points (the two lists are on the device already): the same check and message, no upload, then body().
+template <typename F>
+int with_device_lists(plda_handle *h, const char *fn, const float *dpos, int64_t np, const float *dneg, int64_t nn, bool outputs_ok,
+                      const char *refusal, F &&body) noexcept {
+  return entry(h, fn, [&]() -> int {
+    if (!dpos || !dneg || !outputs_ok || np <= 0 || nn <= 0) return fail(h, PLDA_E_INVAL, "%s", refusal);
+    PLDA_TRY(set_device(h));
+    return body();
+  });
+}
 // the host-list forms: K target and K non-target arrays in caller memory, uploaded, then body(device pointer arrays)
 template <typename F>
 int with_host_fusion_lists(plda_handle *h, const char *fn, int32_t K, const float *const *pos, int64_t np, const float *const *neg,
@@ -294,7 +304,7 @@ const struct { const char *name; int64_t plda_handle::*member; } ENV_INT64[] = {
     {"PLDA_EER_SLAB_ROWS", &plda_handle::eer_slab_rows},         {"PLDA_SNORM_SLAB_ROWS", &plda_handle::sn_slab_rows},
     {"PLDA_ADAPT_SLAB_ROWS", &plda_handle::ad_slab_rows},        {"PLDA_AHC_SCRATCH_BYTES", &plda_handle::ahc_scratch_bytes},
     {"PLDA_VBX_SCRATCH_BYTES", &plda_handle::vbx_scratch_bytes}, {"PLDA_DER_SCRATCH_BYTES", &plda_handle::der_scratch_bytes},
-    {"PLDA_ROCCH_EDGE_CAP", &plda_handle::rocch_edge_cap},
+    {"PLDA_ROCCH_EDGE_CAP", &plda_handle::rocch_edge_cap},       {"PLDA_PARTITION_SLICE_ROWS", &plda_handle::partition_slice_rows},
 };
 
 // ... and the ones that are checked: a refused value fails plda_create (the text goes to plda_last_error(NULL))
@@ -1803,6 +1813,83 @@ int plda_rocch_hull(int64_t T, const uint32_t *edge_key, const uint64_t *other_l
 }
 int plda_rocch_finish(int64_t n_vertices, plda_rocch_vertex *vertices, const uint32_t *below, const uint32_t *above) {
   return rocch_finish(n_vertices, vertices, below, above);
+}
+
+// ---------------------------------------------------------------- trial keys: the partition (partition.hip) and the device-list forms
+int plda_partition_plan(const int64_t *enrol_spk, int64_t M, const int64_t *test_spk, int64_t Nt, const plda_trial_key *key,
+                        plda_partition_record *plan) {
+  return guarded(nullptr, "plda_partition_plan", [&]() -> int { return partition_plan(nullptr, "partition_plan", enrol_spk, M, test_spk, Nt, key, plan); });
+}
+
+int plda_partition_matrix_dev(plda_handle *h, const float *dscores, int64_t ld, int64_t M, int64_t Nt, const int64_t *denrol_spk,
+                              const int64_t *dtest_spk, const plda_trial_key *key, float *dtar, int64_t cap_tar, float *dnon,
+                              int64_t cap_non, plda_partition_record *plan_out) {
+  return device_entry(h, "plda_partition_matrix_dev", [&] {
+    return partition_matrix_device(h, dscores, ld, M, Nt, denrol_spk, dtest_spk, key, dtar, cap_tar, dnon, cap_non, plan_out);
+  });
+}
+
+int plda_score_partition_dev(plda_handle *h, const double *dU, const int32_t *dn_enrol, int32_t n_uniform, int64_t M, const double *dV,
+                             int64_t Nt, const double *dzmean, const double *dzstd, const int64_t *denrol_spk, const int64_t *dtest_spk,
+                             const plda_trial_key *key, float *dtar, int64_t cap_tar, float *dnon, int64_t cap_non,
+                             plda_partition_record *plan_out) {
+  return device_entry(h, "plda_score_partition_dev", [&] {
+    return score_partition_device(h, dU, dn_enrol, n_uniform, M, dV, Nt, dzmean, dzstd, denrol_spk, dtest_spk, key, dtar, cap_tar, dnon,
+                                  cap_non, plan_out);
+  });
+}
+
+// each is its _lists sibling without the upload: the same check, the same message, the same *_lists_device call
+int plda_eer_lists_dev(plda_handle *h, const float *dpos, int64_t np, const float *dneg, int64_t nn, double *out) {
+  return with_device_lists(h, "plda_eer_lists_dev", dpos, np, dneg, nn, out != nullptr, "eer: need at least one target and one impostor score",
+                           [&] { return eer_lists_device(h, dpos, np, dneg, nn, out); });
+}
+int plda_det_lists_dev(plda_handle *h, const float *dpos, int64_t np, const float *dneg, int64_t nn, int32_t n_points, double *far,
+                       double *frr, double *thresholds) {
+  return with_device_lists(h, "plda_det_lists_dev", dpos, np, dneg, nn, far && frr, "det: need at least one target and one impostor score",
+                           [&]() -> int {
+    const int rc = det_lists_device(h, dpos, np, dneg, nn, n_points, far, frr, thresholds);
+    PLDA_HIP(h, hipStreamSynchronize(h->stream));
+    return rc;
+  });
+}
+int plda_min_dcf_lists_dev(plda_handle *h, const float *dpos, int64_t np, const float *dneg, int64_t nn, int32_t n_points,
+                           const plda_dcf_point *points, plda_min_dcf *out, plda_min_dcf_info *info) {
+  return with_device_lists(h, "plda_min_dcf_lists_dev", dpos, np, dneg, nn, out != nullptr, "min_dcf: need at least one target and one non-target score",
+                           [&] { return min_dcf_lists_device(h, dpos, np, dneg, nn, n_points, points, out, info); });
+}
+int plda_calib_pass_lists_dev(plda_handle *h, const float *dpos, int64_t np, const float *dneg, int64_t nn, double a, double c,
+                              double theta, plda_calib_record *out_record) {
+  return with_device_lists(h, "plda_calib_pass_lists_dev", dpos, np, dneg, nn, out_record != nullptr, "calib_pass: need at least one target and one non-target score",
+                           [&] { return calib_pass_lists_device(h, dpos, np, dneg, nn, a, c, theta, out_record); });
+}
+int plda_calib_fit_lists_dev(plda_handle *h, const float *dpos, int64_t np, const float *dneg, int64_t nn, double prior, double tol,
+                             int32_t max_iter, plda_calib_fit *out_fit) {
+  return with_device_lists(h, "plda_calib_fit_lists_dev", dpos, np, dneg, nn, out_fit != nullptr, "calib_fit: need at least one target and one non-target score",
+                           [&] { return calib_fit_lists_device(h, dpos, np, dneg, nn, prior, tol, max_iter, out_fit); });
+}
+int plda_rocch_lists_dev(plda_handle *h, const float *dpos, int64_t np, const float *dneg, int64_t nn, int64_t cap_vertices,
+                         plda_rocch *out, plda_rocch_vertex *vertices, double *llr, plda_rocch_points *points, plda_rocch_info *info) {
+  return with_device_lists(h, "plda_rocch_lists_dev", dpos, np, dneg, nn, out != nullptr, "rocch: need at least one target and one non-target score",
+                           [&] { return rocch_lists_device(h, dpos, np, dneg, nn, cap_vertices, out, vertices, llr, points, info); });
+}
+int plda_fusion_pass_lists_dev(plda_handle *h, int32_t n_systems, const float *const *dpos, int64_t np, const float *const *dneg,
+                               int64_t nn, const double *a, double c, double theta, plda_fusion_record *out_record) {
+  return entry(h, "plda_fusion_pass_lists_dev", [&]() -> int {
+    if (!out_record || !a) return fail(h, PLDA_E_INVAL, "%s: the output structure or the weight array is NULL", "plda_fusion_pass_lists_dev");
+    PLDA_TRY(fusion_list_args_check(h, "plda_fusion_pass_lists_dev", n_systems, dpos, np, dneg, nn));
+    PLDA_TRY(set_device(h));
+    return fusion_pass_lists_device(h, n_systems, dpos, np, dneg, nn, a, c, theta, out_record);
+  });
+}
+int plda_fusion_fit_lists_dev(plda_handle *h, int32_t n_systems, const float *const *dpos, int64_t np, const float *const *dneg,
+                              int64_t nn, double prior, double tol, int32_t max_iter, plda_fusion_fit *out_fit) {
+  return entry(h, "plda_fusion_fit_lists_dev", [&]() -> int {
+    if (!out_fit) return fail(h, PLDA_E_INVAL, "%s: the output structure or the weight array is NULL", "plda_fusion_fit_lists_dev");
+    PLDA_TRY(fusion_list_args_check(h, "plda_fusion_fit_lists_dev", n_systems, dpos, np, dneg, nn));
+    PLDA_TRY(set_device(h));
+    return fusion_fit_lists_device(h, n_systems, dpos, np, dneg, nn, prior, tol, max_iter, out_fit);
+  });
 }
 
 // ---------------------------------------------------------------- minimum detection cost (dcf.hip)

@@ -301,6 +301,7 @@ struct plda_handle {
   int rocch_variant = 0;         // PLDA_ROCCH_VARIANT=1: no LDS window, every rank through global atomics; 2: a window of 256 gaps (tests)
   int64_t rocch_edge_cap = 0;    // PLDA_ROCCH_EDGE_CAP: the most edge-class trials a ROCCH call accepts (0: 2^24)
   int64_t eer_slab_rows = 0;     // PLDA_EER_SLAB_ROWS: rows per slab of plda_score_eer_dev (0: <= 4 GiB of scores)
+  int64_t partition_slice_rows = 0;   // PLDA_PARTITION_SLICE_ROWS: rows per slice of the partition's units (0: by size, partition.hip; tests -- the output does not depend on it); the partition carves trial_hist (table, unit counts, unit cursors: one layout list)
   plda::DevBuf calib_part;       // calib.hip: one partial plda_calib_record per workgroup of a calibration pass + the reduced one
   plda::DevBuf fusion_part;      // fusion.hip: one partial plda_fusion_record per workgroup of a fusion pass + the reduced one
   plda::DevBuf sn_slab;          // plda_cohort_stats_dev (snorm.hip), plda_score_topn_dev (topn.hip): the row slab of scores in flight

@@ -227,6 +227,16 @@ int score_fusion_side_fit_device(plda_handle *h, const double *dU, const int32_t
 // points before they upload, and by the device-list drivers
 int fusion_list_args_check(plda_handle *h, const char *fn, int K, const float *const *pos, int64_t np, const float *const *neg, int64_t nn);
 int fusion_newton(const plda_fusion_record *r, double prior, double *F, double *d, double *lambda2);
+// ---- partition.hip (trial keys, K26): the plan on the host (h: where a message goes, may be nullptr), the two device forms
+int partition_plan(plda_handle *h, const char *fn, const int64_t *espk, int64_t M, const int64_t *tspk, int64_t Nt,
+                   const plda_trial_key *key, plda_partition_record *plan);
+int partition_matrix_device(plda_handle *h, const float *dscores, int64_t ld, int64_t M, int64_t Nt, const int64_t *despk,
+                            const int64_t *dtspk, const plda_trial_key *key, float *dtar, int64_t cap_tar, float *dnon, int64_t cap_non,
+                            plda_partition_record *plan_out);
+int score_partition_device(plda_handle *h, const double *dU, const int32_t *dn, int n_uniform, int64_t M, const double *dV, int64_t Nt,
+                           const double *dzmean, const double *dzstd, const int64_t *despk, const int64_t *dtspk,
+                           const plda_trial_key *key, float *dtar, int64_t cap_tar, float *dnon, int64_t cap_non,
+                           plda_partition_record *plan_out);
 // ---- comm.hip: the row-sharded forms over the installed communicator
 int eer_matrix_comm_device(plda_handle *h, const float *dscores, int64_t ld, int64_t M, int64_t Nt, const int64_t *despk,
                            const int64_t *dtspk, double *out);

@@ -1248,6 +1248,46 @@ class MPlda(object):
             self._affine_map_on_device(S, cal)
         return DC.min_dcf_from_matrix_dev(self, S.data_ptr(), nt, m, nt, despk.data_ptr(), dtspk.data_ptr(), points=points)
 
+    # ------------------------------------------------- trial keys (csrc/partition.hip, plda_amd/trialkey.py)
+    def partition(self, enrol, test, test_speaker, key=None, znorm=True, cohort=None, top_k=None, calibrate=False):
+        """The per-(bucket, class) score lists of the trials between two transform() results under a
+        `plda_amd.trialkey.TrialKey` (None: every pair is a trial, one bucket), on the device: a
+        `plda_amd.trialkey.Partition` (include/plda_hip.h, "trial keys"), for a DET plot or a score file.  Arguments as
+        `min_dcf`.  Without a cohort and without the map the matrix is never held (the trials are scored slab by slab and
+        only the selected ones are written); otherwise it is."""
+        from . import trialkey as TK
+        cal = self._stored_calibration(calibrate)
+        ids, counts, U, V, tspk = self._labelled_trials(enrol, test, test_speaker, "partition")
+        m, nt = U.shape[0], V.shape[0]
+        if key is None:
+            key = TK.TrialKey(m, nt, "all")
+        if key.shape != (m, nt):
+            raise ValueError("partition: the key covers %d x %d pairs, the trials are %d x %d" % (key.shape + (m, nt)))
+        despk, dtspk = self._to_device(np.ascontiguousarray(ids, np.int64)), self._to_device(tspk)
+        if cohort is None and cal is None:
+            zm, zs = self._zn_arrays(ids, znorm)
+            uniform = int(counts[0]) if np.all(counts == counts[0]) else 0
+            dU, dV = self._to_device(U), self._to_device(V)
+            dn = None if uniform else self._to_device(counts)
+            dzm, dzs = (self._to_device(zm), self._to_device(zs)) if zm is not None else (None, None)
+            return TK.partition_from_operands_dev(self, key, dU, dn, uniform, dV, despk, dtspk, dzm, dzs)
+        S = self._own_matrix_on_device(ids, counts, U, V, znorm, cohort, top_k)
+        if cal is not None:
+            self._affine_map_on_device(S, cal)
+        part = TK.partition_matrix_dev(self, key, S, despk, dtspk)
+        self.synchronize()           # (the matrix may be freed when this returns)
+        return part
+
+    def evaluate(self, enrol, test, test_speaker, key=None, points=((0.01, 1.0, 1.0),), znorm=True, cohort=None, top_k=None,
+                 calibrate=False, prior=0.5):
+        """Per-condition, pooled and equalised figures of the trials between two transform() results under a trial key
+        (None: every pair, one bucket): `plda_amd.trialkey.metrics` of `partition(...)` -- EER, minDCF and actual DCF at
+        `points`, Cllr and minCllr per bucket, over all trials, and as the unweighted mean over the buckets that hold both
+        classes (NIST's equalisation).  Nothing leaves the device but the figures."""
+        from . import trialkey as TK
+        part = self.partition(enrol, test, test_speaker, key, znorm, cohort, top_k, calibrate)
+        return TK.metrics(self, part, points=points, prior=prior)
+
     def min_cllr(self, enrol, test, test_speaker, znorm=True, cohort=None, top_k=None):
         """minCllr, the ROC convex hull and the PAV map of the trials between two transform() results (include/plda_hip.h,
         "ROC convex hull").  Arguments as `min_dcf`; the scores are those of score_matrix (znorm) or, with a cohort,
