@@ -1891,7 +1891,9 @@ int plda_der_timed_jer_sweep(plda_handle *h, const int32_t *merge_a, const int32
  *                        plus O(Din^2 + K Din).
  *   plda_embed_fit       the same with host arrays; K is found from the labels (max + 1).
  * OUT OF SCOPE, each on purpose: fp32 or bf16 output; more than one
- * matrix per chain; within-class covariance normalisation and a cosine back-end. ---- */
+ * matrix per chain.  (The cosine back-end is the section "cosine back-end" below, K27.  Within-class covariance normalisation
+ * needs no kernel of its own under it: WCCN is A with A W A^T = I, full-rank LDA (kind 2, Dout = Din) differs from it by a
+ * rotation, and a cosine is invariant to rotations -- MPlda.fit_embedding(kind="wccn") fits kind 2 at Dout = Din.) ---- */
 #define PLDA_EMBED_MAX_DIN 4096
 #define PLDA_EMBED_MAX_DOUT 2048
 int plda_embed_set(plda_handle *h, int32_t Din, int32_t Dout, const double *m_in, double len_in, const double *A,
@@ -1906,6 +1908,41 @@ int plda_embed_fit_dev(plda_handle *h, const void *dX, int32_t dtype, int64_t N,
                        int32_t kind, int32_t Dout, double len_in, double len_out, double *eig);
 int plda_embed_fit(plda_handle *h, const void *X, int32_t dtype, int64_t N, int32_t Din, const uint64_t *labels, int32_t kind,
                    int32_t Dout, double len_in, double len_out, double *eig);
+
+/* ---- cosine back-end (K27; csrc/cosine.hip): a second back-end behind every scoring entry point.  A handle is a PLDA handle
+ * (the default) or a cosine handle, never both.  On a cosine handle a score is the cosine of the two rows,
+ *     c(u, v) = (sum_d u_d v_d) inv(u) inv(v),   inv(x) = 1 / sqrt(sum_d x_d^2), 0 for a zero row (which scores 0),
+ * and with z-norm statistics (c - zmean_i) / zstd_i where zstd_i != 0 (such a row is left un-normalised, as on a PLDA handle).
+ * The operand forms reach the trials GEMM through the same seam as PLDA scores: the packed operands are the unit rows
+ * (the enrol side times 1 / zstd_i), rounded once from fp64 to fp32, q_j = 0 and r'_i = -zmean_i / zstd_i; the GEMM kernels
+ * and every consumer are the PLDA ones -- plda_score_matrix[_dev] and its sharded pair, plda_score_matrix_snorm*,
+ * plda_cohort_stats*, plda_score_topn*, plda_score_eer_dev, plda_score_min_dcf_dev, plda_score_rocch_dev, plda_score_calib_*_dev,
+ * plda_score_fusion_side_*_dev, plda_score_partition_dev, plda_score_ahc*, plda_score_spectral*, plda_score_prepare*_dev.
+ * plda_score_pairs and plda_score_one evaluate c in fp64.  Rows are [.., D] fp64 of ANY length: they are length-normalised
+ * here.  n_enrol / n_uniform are checked as on a PLDA handle and then ignored (a model vector is a model vector: GEMM depth D,
+ * the uniform path); plda_score_prepare[_counts]_dev prepares the one form a cosine test side has.
+ * A row's packed bits depend on the row and its own zstd alone (not on the batch, the launch shape or PLDA_PREP_VARIANT 2 / 3;
+ * PLDA_PREP_VARIANT=1 is ignored).  A non-finite element makes its own row's (column's) scores NaN and touches no other.
+ *   plda_backend_set(h, PLDA_BACKEND_COSINE, D)   1 <= D <= 2048, and the handle holds no PLDA model (PLDA_E_INVAL otherwise:
+ *                        create another handle).  Dout = Din = D (plda_get_dims answers (D, D)); a test side prepared before is
+ *                        dropped, the coefficient caches too.
+ *   plda_backend_set(h, PLDA_BACKEND_PLDA, 0)     a cosine handle returns to the empty PLDA state (no model); a PLDA handle is
+ *                        left as it is, model included.  D != 0 here, or any other kind: PLDA_E_INVAL.
+ *   plda_backend_get     kind, and D of a cosine handle (0 on a PLDA handle); either pointer may be NULL.
+ * ON A COSINE HANDLE every entry point that installs a PLDA model (plda_fit*, plda_fit_em_dev, plda_fit_sharded*,
+ * plda_set_model) returns PLDA_E_INVAL and says why; every entry point that needs the model proper (plda_transform*,
+ * plda_adapt_*, plda_blend_model, plda_truncate, plda_smooth, plda_znorm_stats*, plda_vbx*, plda_project_rows*, the dense-PCA
+ * forms, plda_get_model, the sharded cohort statistics) returns PLDA_E_NOT_FITTED, and plda_last_error ends in
+ * "(cosine back-end selected: this entry point needs a PLDA model)".  The embedding chain, the LDA model, the matrix forms and
+ * everything that takes scores are independent of the back-end.
+ * OUT OF SCOPE, each on purpose: fp32 or bf16 row input to the operand forms; a closed form of plda_znorm_stats for cosines
+ * (z-norm statistics of a cosine handle come from plda_cohort_stats with top_k = Nc); score averaging instead of model
+ * averaging for multi-session enrolment.  The sharded forms and the opt-in bf16x3 arm consume the same operands and work by
+ * construction; they are not tested on a cosine handle. ---- */
+#define PLDA_BACKEND_PLDA 0
+#define PLDA_BACKEND_COSINE 1
+int plda_backend_set(plda_handle *h, int32_t kind, int32_t D);
+int plda_backend_get(plda_handle *h, int32_t *kind, int32_t *D);
 
 /* ---- LDA: replaces the reference's second model, the pure-Python
  * class LDA of python/liblda/lda.py (used by scoring/scoreLDA.py:175,224,241), on the same

@@ -5,6 +5,7 @@ Layout (only what the hot path needs):
   lib/        built libplda_hip.so (in-tree, git-ignored)
   _native.py  ctypes binding of the C ABI (fails loudly if the .so or a GPU is missing)
   libplda.py  `MPlda`: counterpart of the reference's CPython type libplda.MPlda
+  cosine.py   `Cosine`: the cosine back-end behind MPlda's scoring interface (csrc/cosine.hip)
   sharding.py row-sharded trials matrix across ranks (torch.distributed / RCCL)
   calibration.py linear score calibration, Cllr, actual DCF (csrc/calib.hip)
   fusion.py   linear fusion of K systems' scores by logistic regression (csrc/fusion.hip)
@@ -17,6 +18,7 @@ Layout (only what the hot path needs):
   rttm.py     RTTM files and per-segment reference labels from reference turns; pure Python / NumPy
 """
 from .libplda import MPlda  # noqa: F401
+from .cosine import Cosine  # noqa: F401
 from . import calibration  # noqa: F401
 from . import fusion  # noqa: F401
 from . import identify  # noqa: F401
@@ -30,4 +32,4 @@ from .fusion import Fusion  # noqa: F401
 from .adaptation import Adaptation  # noqa: F401
 from .trialkey import TrialKey  # noqa: F401
 
-__all__ = ["MPlda", "Calibration", "Fusion", "Adaptation", "TrialKey", "trialkey", "calibration", "fusion", "identify", "adaptation", "diarize", "der", "rttm"]
+__all__ = ["MPlda", "Cosine", "Calibration", "Fusion", "Adaptation", "TrialKey", "trialkey", "calibration", "fusion", "identify", "adaptation", "diarize", "der", "rttm"]

@@ -56,6 +56,8 @@ SIGNATURES = {
     "plda_fit_get_stats": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "plda_fit_num_classes": (C.c_int, [_vp, C.POINTER(_i64)]),
     "plda_get_dims": (C.c_int, [_vp, C.POINTER(_i32), C.POINTER(_i32)]),
+    "plda_backend_set": (C.c_int, [_vp, _i32, _i32]),
+    "plda_backend_get": (C.c_int, [_vp, C.POINTER(_i32), C.POINTER(_i32)]),
     "plda_get_model": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "plda_set_model": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp]),
     "plda_truncate": (C.c_int, [_vp, _i32]),

@@ -17,7 +17,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 SO = os.path.join(LIBDIR, "libplda_hip.so")
 SO_DIAG = os.path.join(LIBDIR, "libplda_hip_diag.so")
-SOURCES = ["api.hip", "score.hip", "linalg.hip", "fit.hip", "frontend.hip", "eer.hip", "operand_slabs.hip", "lda.hip", "comm.hip", "eig_dc.hip", "hostio.hip", "transform.hip", "snorm.hip", "calib.hip", "dcf.hip", "rocch.hip", "topn.hip", "fusion.hip", "adapt.hip", "ahc.hip", "dense_pca.hip", "vbx.hip", "der.hip", "der_time.hip", "embed.hip", "spectral.hip", "partition.hip"]
+SOURCES = ["api.hip", "score.hip", "linalg.hip", "fit.hip", "frontend.hip", "eer.hip", "operand_slabs.hip", "lda.hip", "comm.hip", "eig_dc.hip", "hostio.hip", "transform.hip", "snorm.hip", "calib.hip", "dcf.hip", "rocch.hip", "topn.hip", "fusion.hip", "adapt.hip", "ahc.hip", "dense_pca.hip", "vbx.hip", "der.hip", "der_time.hip", "embed.hip", "spectral.hip", "partition.hip", "cosine.hip"]
 HEADERS = [os.path.join(CSRC, "common.hpp"), os.path.join(CSRC, "layout.hpp"), os.path.join(CSRC, "trial_source.hpp"), os.path.join(CSRC, "hostio.hpp"), os.path.join(CSRC, "sweep_mfma.inc"), os.path.join(CSRC, "score_bt4.inc"), os.path.join(CSRC, "score_bf16x3.inc"), os.path.join(CSRC, "syrk_blk.inc"), os.path.join(HERE, "..", "include", "plda_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics",
          "-Wall", "-Wno-unused-function", "-Wno-unused-result"]
@@ -47,12 +47,15 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-ato
 # frontend.hip: variance pooling subtracts the utterance's first normalised frame y0 = x0 * inv from every y = x * inv; a fused
 # x * inv - y0 would subtract the rounded product from the unrounded one, and a one-frame utterance's variance would not be 0
 # (the fused multiply-adds the kernels do want are written as fma())
+# cosine.hip: a row's packed bits are a function of the row and its own zstd alone, whichever launch shape runs, and they are
+# specified to the operation (tests/cosine_model.py): a square is a product and a sum, nothing may be contracted
 EXTRA = {"score.hip": ["-mllvm", "-amdgpu-atomic-optimizer-strategy=None"],
          "frontend.hip": ["-ffp-contract=off"],
          "fusion.hip": ["-mllvm", "-disable-machine-licm"],
          "ahc.hip": ["-ffp-contract=off"],
          "embed.hip": ["-ffp-contract=off"],
-         "spectral.hip": ["-ffp-contract=off"]}
+         "spectral.hip": ["-ffp-contract=off"],
+         "cosine.hip": ["-ffp-contract=off"]}
 
 
 def _stale(target, deps):

@@ -499,7 +499,7 @@ int score_ahc_device(plda_handle *h, const double *dX, const int64_t *offsets, i
                      double *dmerge_cost) {
   const char *fn = "score_ahc";
   const AhcOut out{dlabels, dn_clusters, dmerge_a, dmerge_b, dmerge_cost};
-  if (!h->fitted) return fail(h, PLDA_E_NOT_FITTED, "%s: model not fitted", fn);
+  if (!can_score(h)) return fail(h, PLDA_E_NOT_FITTED, "%s: model not fitted", fn);
   if (!dX) return fail(h, PLDA_E_INVAL, "%s: X is NULL", fn);
   PLDA_TRY(ahc_check_args(h, fn, offsets, R, has_thr, thr, minc, out));
   const int D = h->Dout;

@@ -34,6 +34,12 @@ int fail(plda_handle *h, int code, const char *fmt, ...) {
   return code;
 }
 
+int refuse_on_cosine(plda_handle *h, const char *fn) {
+  if (h->backend != PLDA_BACKEND_COSINE) return PLDA_OK;
+  return fail(h, PLDA_E_INVAL, "%s: the cosine back-end is selected on this handle, which holds no PLDA model and takes none "
+                               "(plda_backend_set(h, PLDA_BACKEND_PLDA, 0) returns it to the PLDA state)", fn);
+}
+
 int hip_fail(plda_handle *h, hipError_t e, const char *what, const char *file, int line) {
   (void)hipGetLastError();   // a failed call leaves its code behind: the next launch check would report it again
   return fail(h, PLDA_E_HIP, "HIP error %d (%s) at %s:%d: %s", (int)e, hipGetErrorString(e), file, line, what);
@@ -186,7 +192,11 @@ template <typename F> int entry(plda_handle *h, const char *fn, F &&body) noexce
   return guarded(h, fn, [&]() -> int {
     if (!h) return PLDA_E_INVAL;
     std::lock_guard<std::recursive_mutex> lock(h->mu);
-    return body();
+    const int rc = body();
+    // the one place that says why a cosine handle has no model (every entry point that needs the model proper ends up here)
+    if (rc == PLDA_E_NOT_FITTED && h->backend == PLDA_BACKEND_COSINE && h->err.find("(cosine back-end selected") == std::string::npos)
+      h->err += " (cosine back-end selected: this entry point needs a PLDA model)";
+    return rc;
   });
 }
 template <typename F> int device_entry(plda_handle *h, const char *fn, F &&body) noexcept {
@@ -579,9 +589,36 @@ int plda_fit_get_stats(plda_handle *h, double *means, int64_t *counts, double *s
 // ---------------------------------------------------------------- model
 int plda_get_dims(plda_handle *h, int32_t *Dout, int32_t *Din) {
   return entry(h, "plda_get_dims", [&]() -> int {
-    if (!h->fitted) return fail(h, PLDA_E_NOT_FITTED, "model not fitted");
+    if (!can_score(h)) return fail(h, PLDA_E_NOT_FITTED, "model not fitted");
     if (Dout) *Dout = h->Dout;
     if (Din) *Din = h->Din;
+    return PLDA_OK;
+  });
+}
+
+// ---------------------------------------------------------------- back-end (cosine.hip)
+int plda_backend_set(plda_handle *h, int32_t kind, int32_t D) {
+  return entry(h, "plda_backend_set", [&]() -> int {
+    if (kind != PLDA_BACKEND_PLDA && kind != PLDA_BACKEND_COSINE) return fail(h, PLDA_E_INVAL, "backend_set: kind = %d (must be 0: PLDA, or 1: cosine)", kind);
+    if (kind == PLDA_BACKEND_PLDA && D != 0) return fail(h, PLDA_E_INVAL, "backend_set: D = %d with the PLDA back-end (must be 0: the model brings its dimensions)", D);
+    if (kind == PLDA_BACKEND_COSINE && (D < 1 || D > 2048)) return fail(h, PLDA_E_INVAL, "backend_set: D = %d (must be in 1 ... 2048)", D);
+    if (kind == PLDA_BACKEND_COSINE && h->fitted)
+      return fail(h, PLDA_E_INVAL, "backend_set: the handle holds a PLDA model; the cosine back-end takes a handle without one (create another handle)");
+    if (kind == PLDA_BACKEND_PLDA && h->backend == PLDA_BACKEND_PLDA) return PLDA_OK;      // nothing to leave: the handle and its model stay as they are
+    h->backend = kind;
+    h->fitted = false;                 // (a cosine handle never had one; back to the EMPTY PLDA state)
+    h->Dout = h->Din = kind == PLDA_BACKEND_COSINE ? D : 0;
+    ++h->model_epoch;                  // whatever is keyed on the model -- the prepared test side among it -- is stale
+    h->prep_valid = false;
+    h->ucoef_ptr = nullptr; h->gcoef_ptr = nullptr;
+    return PLDA_OK;
+  });
+}
+
+int plda_backend_get(plda_handle *h, int32_t *kind, int32_t *D) {
+  return entry(h, "plda_backend_get", [&]() -> int {
+    if (kind) *kind = h->backend;
+    if (D) *D = h->backend == PLDA_BACKEND_COSINE ? h->Dout : 0;
     return PLDA_OK;
   });
 }
@@ -611,6 +648,7 @@ int plda_set_model(plda_handle *h, int32_t Dout, int32_t Din, const double *mean
   return entry(h, "plda_set_model", [&]() -> int {
     if (Dout <= 0 || Din <= 0 || Dout > Din || !mean || !transform || !psi)
       return fail(h, PLDA_E_INVAL, "set_model: bad argument");
+    PLDA_TRY(refuse_on_cosine(h, "set_model"));
     PLDA_TRY(set_device(h));
     h->Dout = Dout; h->Din = Din;
     h->h_mean.assign(mean, mean + Din);
@@ -883,7 +921,7 @@ int plda_score_matrix(plda_handle *h, const double *U, const int32_t *n_enrol, i
                       const double *V, int64_t Nt, const double *zmean, const double *zstd, float *out,
                       int64_t ld_out) {
   return entry(h, "plda_score_matrix", [&]() -> int {
-    if (!h->fitted) return fail(h, PLDA_E_NOT_FITTED, "score_matrix: model not fitted");
+    if (!can_score(h)) return fail(h, PLDA_E_NOT_FITTED, "score_matrix: model not fitted");
     if (M <= 0 || Nt <= 0) return PLDA_OK;
     if (!U || !V || !out || ld_out < Nt) return fail(h, PLDA_E_INVAL, "score_matrix: bad argument");
     if (!n_enrol && n_uniform <= 0) return fail(h, PLDA_E_INVAL, "score_matrix: n_uniform must be > 0 when n_enrol is NULL");
@@ -1145,7 +1183,7 @@ int plda_score_pairs(plda_handle *h, const double *U, const int32_t *n_enrol, in
                      int64_t Nt, const int64_t *e_idx, const int64_t *t_idx, int64_t P, const double *zmean,
                      const double *zstd, double *out) {
   return entry(h, "plda_score_pairs", [&]() -> int {
-    if (!h->fitted) return fail(h, PLDA_E_NOT_FITTED, "score: model not fitted");
+    if (!can_score(h)) return fail(h, PLDA_E_NOT_FITTED, "score: model not fitted");
     if (P <= 0) return PLDA_OK;
     if (!U || !n_enrol || !V || !e_idx || !t_idx || !out || M <= 0 || Nt <= 0) return fail(h, PLDA_E_INVAL, "score_pairs: bad argument");
     const bool long_list = P >= 16384;      // (long lists: the indices are checked on the device, below -- 10^7 pairs are 10 ms of this loop)
@@ -1225,10 +1263,11 @@ int plda_score_pairs(plda_handle *h, const double *U, const int32_t *n_enrol, in
 int plda_score_one(plda_handle *h, const double *u, int32_t n, const double *v, int32_t has_z, double zmean, double zstd,
                    double *out) {
   return entry(h, "plda_score_one", [&]() -> int {
-    if (!h->fitted) return fail(h, PLDA_E_NOT_FITTED, "score: model not fitted");
+    if (!can_score(h)) return fail(h, PLDA_E_NOT_FITTED, "score: model not fitted");
     if (!u || !v || !out) return fail(h, PLDA_E_INVAL, "score_one: bad argument");
     if (n <= 0) return fail(h, PLDA_E_INVAL, "score_one: num_examples must be > 0");
     const int D = h->Dout;
+    if (h->backend == PLDA_BACKEND_COSINE) { *out = cosine_one_host(u, v, D, has_z != 0, zmean, zstd); return PLDA_OK; }
     auto &o = h->one;
     if (o.epoch != h->model_epoch || o.n != n || o.D != D) {
       o.c.resize(D); o.ivar.resize(D); o.ipsi1.resize(D);
@@ -1295,7 +1334,7 @@ int plda_cohort_stats_dev(plda_handle *h, const double *dX, const int32_t *dn, i
 int plda_cohort_stats(plda_handle *h, const double *X, const int32_t *n, int32_t n_uniform, int64_t R, const double *Cv,
                       int64_t Nc, int64_t top_k, double *mean, double *std_) {
   return entry(h, "plda_cohort_stats", [&]() -> int {
-    if (!h->fitted) return fail(h, PLDA_E_NOT_FITTED, "cohort_stats: model not fitted");
+    if (!can_score(h)) return fail(h, PLDA_E_NOT_FITTED, "cohort_stats: model not fitted");
     if (R < 1 || Nc < 1) return fail(h, PLDA_E_INVAL, "cohort_stats: R = %lld, Nc = %lld (both must be >= 1)", (long long)R, (long long)Nc);
     if (top_k < 1 || top_k > Nc) return fail(h, PLDA_E_INVAL, "cohort_stats: top_k = %lld (must be in 1 ... Nc = %lld)", (long long)top_k, (long long)Nc);
     if (!X || !Cv || !mean || !std_) return fail(h, PLDA_E_INVAL, "cohort_stats: %s is NULL", !X ? "X" : !Cv ? "cohort" : !mean ? "mean" : "std");
@@ -1330,7 +1369,7 @@ int plda_score_matrix_snorm(plda_handle *h, const double *U, const int32_t *n_en
                             int64_t Nt, const double *emean, const double *estd, const double *tmean, const double *tstd,
                             float *out, int64_t ld_out) {
   return entry(h, "plda_score_matrix_snorm", [&]() -> int {
-    if (!h->fitted) return fail(h, PLDA_E_NOT_FITTED, "score_matrix_snorm: model not fitted");
+    if (!can_score(h)) return fail(h, PLDA_E_NOT_FITTED, "score_matrix_snorm: model not fitted");
     if ((emean == nullptr) != (estd == nullptr)) return fail(h, PLDA_E_INVAL, "score_matrix_snorm: %s is NULL but its partner is not", emean ? "estd" : "emean");
     if ((tmean == nullptr) != (tstd == nullptr)) return fail(h, PLDA_E_INVAL, "score_matrix_snorm: %s is NULL but its partner is not", tmean ? "tstd" : "tmean");
     if (!emean && !tmean) return fail(h, PLDA_E_INVAL, "score_matrix_snorm: both statistic pairs are NULL (emean/estd or tmean/tstd must be given)");
@@ -1395,7 +1434,7 @@ int plda_score_topn(plda_handle *h, const double *U, const int32_t *n_enrol, int
                     int64_t Nt, const double *zmean, const double *zstd, const double *emean, const double *estd,
                     const double *tmean, const double *tstd, int32_t axis, int64_t top_n, float *out_scores, int64_t *out_index) {
   return entry(h, "plda_score_topn", [&]() -> int {
-    if (!h->fitted) return fail(h, PLDA_E_NOT_FITTED, "score_topn: model not fitted");
+    if (!can_score(h)) return fail(h, PLDA_E_NOT_FITTED, "score_topn: model not fitted");
     if (M < 1 || Nt < 1) return fail(h, PLDA_E_INVAL, "score_topn: M = %lld, Nt = %lld (both must be >= 1)", (long long)M, (long long)Nt);
     if (axis != 0 && axis != 1) return fail(h, PLDA_E_INVAL, "score_topn: axis = %d (must be 0: per row, or 1: per column)", axis);
     if (top_n < 1 || top_n > PLDA_TOPN_MAX) return fail(h, PLDA_E_INVAL, "score_topn: top_n = %lld (must be in 1 ... %d)", (long long)top_n, PLDA_TOPN_MAX);
@@ -2126,7 +2165,7 @@ int plda_score_ahc(plda_handle *h, const double *X, const int64_t *offsets, int6
                    const int32_t *min_clusters, int32_t *labels, int32_t *n_clusters, int32_t *merge_a, int32_t *merge_b,
                    double *merge_cost) {
   return entry(h, "plda_score_ahc", [&]() -> int {
-    if (!h->fitted) return fail(h, PLDA_E_NOT_FITTED, "score_ahc: model not fitted");
+    if (!can_score(h)) return fail(h, PLDA_E_NOT_FITTED, "score_ahc: model not fitted");
     if (!X) return fail(h, PLDA_E_INVAL, "score_ahc: X is NULL");
     PLDA_TRY(ahc_validate(h, "score_ahc", nullptr, false, offsets, R, has_threshold, threshold, min_clusters, labels, n_clusters,
                           merge_a, merge_b, merge_cost));
@@ -2223,7 +2262,7 @@ int plda_score_spectral(plda_handle *h, const double *X, const int64_t *offsets,
   return entry(h, "plda_score_spectral", [&]() -> int {
     const SpectralArgs host = spectral_args(offsets, R, p_table, P, max_speakers, num_speakers, max_iters, labels, n_clusters, p_used,
                                             k_gap, eig, embed, deg2);
-    if (!h->fitted) return fail(h, PLDA_E_NOT_FITTED, "score_spectral: model not fitted");
+    if (!can_score(h)) return fail(h, PLDA_E_NOT_FITTED, "score_spectral: model not fitted");
     if (!X) return fail(h, PLDA_E_INVAL, "score_spectral: X is NULL");
     PLDA_TRY(spectral_validate(h, "score_spectral", nullptr, false, host));
     PLDA_TRY(set_device(h));

@@ -695,7 +695,7 @@ int shard_plan(int64_t M, int R, int rank, int64_t block_rows, int64_t *row_star
 int score_matrix_sharded_device(plda_handle *h, const double *dU, const int32_t *dn, int n_uniform, int64_t M,
                                 const double *dV, int64_t Nt, const double *dzmean, const double *dzstd, float *dlocal,
                                 int64_t ld_local, float *dfull, int64_t ld_full, int64_t block_rows, int gather) {
-  if (!h->fitted) return fail(h, PLDA_E_NOT_FITTED, "score_matrix_sharded: model not fitted");
+  if (!can_score(h)) return fail(h, PLDA_E_NOT_FITTED, "score_matrix_sharded: model not fitted");
   if (M <= 0 || Nt <= 0) return PLDA_OK;
   if (!dU || !dV || (!dlocal && !dfull)) return fail(h, PLDA_E_INVAL, "score_matrix_sharded: bad argument");
   if ((dlocal && ld_local < Nt) || (dfull && ld_full < Nt)) return fail(h, PLDA_E_INVAL, "score_matrix_sharded: ld < Nt");
@@ -795,6 +795,7 @@ int cohort_stats_sharded_device(plda_handle *h, const double *dX, const int32_t 
 
 // ------------------------------------------------------------------------------------ fit by speaker
 int fit_sharded_device(plda_handle *h, const double *dX, int64_t N, int D, const uint64_t *dlabels, int64_t K, int iters) {
+  PLDA_TRY(refuse_on_cosine(h, "fit_sharded"));
   const int R = h->comm_nranks, me = h->comm_rank;
   PLDA_TRY(fit_stats_device(h, dX, N, D, dlabels, K));        // means[K, D], counts[K], scatter[D, D] of MY speakers
   if (R == 1 || !h->comm) return fit_em_device(h, K, D, iters);

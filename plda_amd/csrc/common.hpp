@@ -141,6 +141,7 @@ struct plda_handle {
 
   // ---- model (Kaldi `Plda`, pldamodule.cpp:29): host mirror + device copies ----
   bool fitted = false;
+  int backend = 0;               // PLDA_BACKEND_PLDA / PLDA_BACKEND_COSINE (plda_backend_set): a cosine handle holds no model, Dout = Din = its dimension
   int Dout = 0, Din = 0;
   std::vector<double> h_mean, h_transform, h_psi, h_offset;
   plda::DevBuf d_mean, d_transform, d_psi, d_offset;
@@ -372,6 +373,10 @@ struct plda_handle {
 namespace plda {
 
 int fail(plda_handle *h, int code, const char *fmt, ...);
+// what a scoring entry point needs: a PLDA model, or the cosine back-end (which scores without one)
+inline bool can_score(const plda_handle *h) { return h->fitted || h->backend == PLDA_BACKEND_COSINE; }
+// the refusal of every entry point that would install a PLDA model on a cosine handle (nullptr handle text: none)
+int refuse_on_cosine(plda_handle *h, const char *fn);
 int hip_fail(plda_handle *h, hipError_t e, const char *what, const char *file, int line);
 // appends "name", "name<a>", "name<a,b>" or "name<a,b,c>" (+ suffix) to h->linalg_kernels: host-side text only, a few
 // dozen nanoseconds per dispatch (no printf formatting: the EM issues hundreds of these products per fit)
@@ -662,6 +667,17 @@ int group_centroids_device(plda_handle *h, const double *dX, int64_t N, int D, c
                            int64_t G, double *dmeans, int32_t *dcounts32);
 
 // ---- score.hip ----
+// the packed operands of one trials GEMM (score.hip: prepare_operands fills it)
+struct TrialOperands {
+  int64_t Mpad, Npad;
+  int KQ, Kg;   // padded GEMM depth (multiple of 8) and its k-quad count
+  int Kg_alg;   // algorithmic depth: Dout (uniform n, cosine), Dout + G - 1 (mixed n, bucketed) or 2 Dout (mixed n, depth-2D form)
+  int kind;     // 0 uniform count, 1 mixed counts in the depth-2D form, 2 mixed counts bucketed by distinct count
+  bool mixed;   // kind == 1
+};
+// Rows per wave of the one-pass prep kernels: 4 while a side has at most 32 768 padded rows, 16 beyond
+// (PLDA_PREP_VARIANT=3 / 2: 4 / 16 forced).
+inline bool prep_few_rows(const plda_handle *h, int64_t rpad) { return h->prep_variant == 3 || (h->prep_variant != 2 && rpad <= 32768); }
 const GemmArm *gemm_arm_lookup(int variant);   // the row of PLDA_GEMM_VARIANT=variant; nullptr: no such arm
 // cs: the distinct enrol counts of the caller's whole call (mixed counts; nullptr: found from dn on the device)
 int score_matrix_device(plda_handle *h, const double *dU, const int32_t *dn, int n_uniform, int64_t M,
@@ -688,6 +704,15 @@ int transform_rows_device(plda_handle *h, const double *dX, int64_t R, int Din,
 // blocks of tail_block rows, 0 without a tail), arm 1 = GEMM + length-norm pass (cls -1, every row in main_rows)
 struct TfPlan { int arm, cls, main_block, tail_block; int64_t main_rows, tail_rows; };
 TfPlan transform_plan(const plda_handle *h, int64_t R);
+
+// ---- cosine.hip (the cosine back-end: the operands of the trials GEMM from length-normalised rows, and trial lists) ----
+// fills the buffers prepare_operands reserved (s_Apk / s_Bpk, s_rbias, s_rscale, s_rpair, s_cbias, s_cpair) for the sides asked for
+int cosine_prepare_operands(plda_handle *h, const double *dU, int64_t M, const double *dV, int64_t Nt, const double *dzmean,
+                            const double *dzstd, const TrialOperands &op, bool doA, bool doB);
+int cosine_pairs_device(plda_handle *h, const double *dU, const double *dV, const int64_t *de, const int64_t *dt, int64_t P,
+                        const double *dzmean, const double *dzstd, double *dout);
+// one trial on the host, the expression of cosine_pairs_kernel
+double cosine_one_host(const double *u, const double *v, int D, bool has_z, double zmean, double zstd);
 
 // ---- snorm.hip (adaptive symmetric score normalisation: top-K cohort statistics, the two-sided map) ----
 // cs: as score_matrix_device (the distinct counts of the caller's whole call; nullptr: found here)

@@ -888,6 +888,7 @@ int fit_em_device(plda_handle *h, int64_t K, int D, int iters) {
   //  plda_fit_em_dev down the no-synchronisation path with a stale pointer and start time; round-4 advisor)
   int *const stats_bad = h->fit_dbad;      // a statistics pass of this same plda_fit is still on the stream: no synchronisation,
   h->fit_dbad = nullptr;                   // its label checks come back with the planning copies below
+  PLDA_TRY(refuse_on_cosine(h, "fit"));
   if (K <= 0 || D <= 0 || iters < 0) return fail(h, PLDA_E_INVAL, "fit: bad argument");
   if (K == 1)
     return fail(h, PLDA_E_ONE_SPEAKER,
@@ -1250,6 +1251,7 @@ int fit_em_device(plda_handle *h, int64_t K, int D, int iters) {
 
 int fit_device(plda_handle *h, const double *dX, int64_t N, int D, const uint64_t *dlabels, int64_t K,
                int iters) {
+  PLDA_TRY(refuse_on_cosine(h, "fit"));
   if (!dX || !dlabels || N <= 0 || D <= 0 || iters < 0) return fail(h, PLDA_E_INVAL, "fit: bad argument");
   if (K == 1)
     return fail(h, PLDA_E_ONE_SPEAKER,

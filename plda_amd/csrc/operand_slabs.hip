@@ -62,7 +62,7 @@ static int operand_sample(void *vc, int64_t step, const float **scores, int64_t 
 int operand_source(plda_handle *h, const char *who, const double *dU, const int32_t *dn, int n_uniform, int64_t M, const double *dV,
                    int64_t Nt, const double *dzmean, const double *dzstd, const int64_t *despk, const int64_t *dtspk, const void *out,
                    OperandSlabs *c, TrialSource *src) {
-  if (!h->fitted) return fail(h, PLDA_E_NOT_FITTED, "%s: model not fitted", who);
+  if (!can_score(h)) return fail(h, PLDA_E_NOT_FITTED, "%s: model not fitted", who);
   if (!dU || !dV || !despk || !dtspk || !out || M <= 0 || Nt <= 0) return fail(h, PLDA_E_INVAL, "%s: bad argument", who);
   if (!dn && n_uniform <= 0) return fail(h, PLDA_E_INVAL, "%s: n_uniform must be > 0 when n_enrol is NULL", who);
   // the set-up: the distinct enrol counts found once, the slab height, the slab buffer

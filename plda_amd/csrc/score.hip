@@ -1544,14 +1544,6 @@ __global__ __launch_bounds__(256) void score_pairs_tab_kernel(const double *__re
 // host orchestration of a trials-matrix call
 // ------------------------------------------------------------------------------------
 
-struct TrialOperands {
-  int64_t Mpad, Npad;
-  int KQ, Kg;   // padded GEMM depth (multiple of 8) and its k-quad count
-  int Kg_alg;   // algorithmic depth: Dout (uniform n), Dout + G - 1 (mixed n, bucketed) or 2 Dout (mixed n, depth-2D form)
-  int kind;     // 0 uniform count, 1 mixed counts in the depth-2D form, 2 mixed counts bucketed by distinct count
-  bool mixed;   // kind == 1
-};
-
 // does the bucketed form apply (and pay) for this set of distinct counts?  cs.G == 0: the set is unknown / unusable
 static inline bool buckets_usable(const plda_handle *h, const CountSet *cs) {
   if (!cs || h->mixed_variant == 1) return false;
@@ -1565,9 +1557,7 @@ static inline int64_t operand_kq(const plda_handle *h, bool has_counts, const Co
   return std::max<int64_t>((has_counts ? 2 : 1) * Dp, 16) / 4;
 }
 
-// Rows per wave of the one-pass prep kernels: 4 while a side has at most 32 768 padded rows, 16 beyond
-// (PLDA_PREP_VARIANT=3 / 2: 4 / 16 forced).  One launcher per kernel picks the instantiation and the grid by it.
-static inline bool prep_few_rows(const plda_handle *h, int64_t rpad) { return h->prep_variant == 3 || (h->prep_variant != 2 && rpad <= 32768); }
+// Rows per wave of the one-pass prep kernels: prep_few_rows (common.hpp).  One launcher per kernel picks the instantiation and the grid by it.
 #define PREP_LAUNCHER(NAME_, KERNEL4_, KERNEL16_)                                              \
   template <typename... Args> static void NAME_(plda_handle *h, int64_t rpad, Args... args) {  \
     if (prep_few_rows(h, rpad)) KERNEL4_<<<(unsigned)(rpad / 16), 256, 0, h->stream>>>(args...); \
@@ -1605,6 +1595,8 @@ static int prepare_operands(plda_handle *h, const double *dU, const int32_t *dn,
   PLDA_HIP(h, h->s_cbias.reserve((size_t)op.Npad * 4));
   PLDA_HIP(h, h->s_rpair.reserve((size_t)op.Mpad * 8));
   PLDA_HIP(h, h->s_cpair.reserve((size_t)op.Npad * 8));
+  // the cosine back-end: the same buffers in the same layout from length-normalised rows (cosine.hip); no model, no coefficients
+  if (h->backend == PLDA_BACKEND_COSINE) return cosine_prepare_operands(h, dU, M, dV, Nt, dzmean, dzstd, op, doA, doB);
   if (op.kind == 2) {
     // bucketed mixed counts: per-bucket coefficient tables, then one pass over each side (+ the test side's dq planes)
     const int G = cs->G, KQm = Dp / 4, KQx = op.KQ - KQm;
@@ -2028,10 +2020,12 @@ static bool count_subset(const CountSet &a, const CountSet &b) {   // a's counts
 int score_matrix_device(plda_handle *h, const double *dU, const int32_t *dn, int n_uniform, int64_t M,
                         const double *dV, int64_t Nt, const double *dzmean, const double *dzstd,
                         float *dout, int64_t ld, bool reuse_packed_B, const CountSet *cs_in) {
-  if (!h->fitted) return fail(h, PLDA_E_NOT_FITTED, "score_matrix: model not fitted");
+  if (!can_score(h)) return fail(h, PLDA_E_NOT_FITTED, "score_matrix: model not fitted");
   if (M <= 0 || Nt <= 0) return PLDA_OK;
   if (!dU || !dV || !dout || ld < Nt) return fail(h, PLDA_E_INVAL, "score_matrix: bad argument");
   if (!dn && n_uniform <= 0) return fail(h, PLDA_E_INVAL, "score_matrix: n_uniform must be > 0 when n_enrol is NULL");
+  // cosine: a model vector is a model vector -- the counts are checked as ever and then ignored (uniform path, no count scan, depth D)
+  if (h->backend == PLDA_BACKEND_COSINE) { dn = nullptr; n_uniform = 1; cs_in = nullptr; }
   const int D = h->Dout;
   const bool zn = dzmean && dzstd;
   // mixed counts: the set of distinct counts decides the form of the operands
@@ -2097,11 +2091,12 @@ int score_matrix_device(plda_handle *h, const double *dU, const int32_t *dn, int
 // 1: mixed counts in the depth-2D form (+ V*V); 2: mixed counts bucketed, for the distinct counts *cs (later calls whose
 // counts are a subset reuse it).
 int score_prepare_device(plda_handle *h, const double *dV, int64_t Nt, int kind, int n_uniform, const CountSet *cs) {
-  if (!h->fitted) return fail(h, PLDA_E_NOT_FITTED, "score_prepare: model not fitted");
+  if (!can_score(h)) return fail(h, PLDA_E_NOT_FITTED, "score_prepare: model not fitted");
   if (!dV || Nt <= 0) return fail(h, PLDA_E_INVAL, "score_prepare: bad argument");
   if (kind == 0 && n_uniform <= 0) return fail(h, PLDA_E_INVAL, "score_prepare: n_uniform must be > 0 for uniform enrol counts");
+  if (kind == 2 && (!cs || cs->G < 1)) return fail(h, PLDA_E_INVAL, "score_prepare_counts: empty or invalid count list");
+  if (h->backend == PLDA_BACKEND_COSINE) { kind = 0; n_uniform = 1; }   // the one form a cosine test side has (score_matrix_device looks for it)
   if (kind == 2) {
-    if (!cs || cs->G < 1) return fail(h, PLDA_E_INVAL, "score_prepare_counts: empty or invalid count list");
     if (cs->G == 1) { kind = 0; n_uniform = cs->vals[0]; }
     else if (!buckets_usable(h, cs)) kind = 1;        // too many distinct counts for this dimension: the depth-2D form
   }
@@ -2123,8 +2118,9 @@ int score_prepare_device(plda_handle *h, const double *dV, int64_t Nt, int kind,
 int score_pairs_device(plda_handle *h, const double *dU, const int32_t *dn, const double *dV,
                        const int64_t *de, const int64_t *dt, int64_t P, const double *dzmean,
                        const double *dzstd, double *dout, int64_t M, const CountSet *cs) {
-  if (!h->fitted) return fail(h, PLDA_E_NOT_FITTED, "score_pairs: model not fitted");
+  if (!can_score(h)) return fail(h, PLDA_E_NOT_FITTED, "score_pairs: model not fitted");
   if (P <= 0) return PLDA_OK;
+  if (h->backend == PLDA_BACKEND_COSINE) return cosine_pairs_device(h, dU, dV, de, dt, P, dzmean, dzstd, dout);
   const int wpb = 4;
   const int D = h->Dout;
   // (PLDA_MIXED_VARIANT=1 keeps everything on the verbatim kernel: the A/B arm)

@@ -268,7 +268,7 @@ int64_t sn_slab_rows(const plda_handle *h, int64_t total_rows, int64_t ld) {
 
 int cohort_stats_device(plda_handle *h, const double *dX, const int32_t *dn, int n_uniform, int64_t R, const double *dC,
                         int64_t Nc, int64_t top_k, double *dmean, double *dstd, const CountSet *cs_in) {
-  if (!h->fitted) return fail(h, PLDA_E_NOT_FITTED, "cohort_stats: model not fitted");
+  if (!can_score(h)) return fail(h, PLDA_E_NOT_FITTED, "cohort_stats: model not fitted");
   if (R < 1) return fail(h, PLDA_E_INVAL, "cohort_stats: R = %lld (must be >= 1)", (long long)R);
   if (Nc < 1) return fail(h, PLDA_E_INVAL, "cohort_stats: Nc = %lld (must be >= 1)", (long long)Nc);
   if (Nc > ((int64_t)1 << 30)) return fail(h, PLDA_E_INVAL, "cohort_stats: Nc = %lld (at most 2^30: one row of scores must fit a slab)", (long long)Nc);
@@ -309,7 +309,7 @@ int cohort_stats_device(plda_handle *h, const double *dX, const int32_t *dn, int
 int score_matrix_snorm_device(plda_handle *h, const double *dU, const int32_t *dn, int n_uniform, int64_t M, const double *dV,
                               int64_t Nt, const double *demean, const double *destd, const double *dtmean, const double *dtstd,
                               float *dout, int64_t ld, const CountSet *cs_in, bool reuse_packed_B) {
-  if (!h->fitted) return fail(h, PLDA_E_NOT_FITTED, "score_matrix_snorm: model not fitted");
+  if (!can_score(h)) return fail(h, PLDA_E_NOT_FITTED, "score_matrix_snorm: model not fitted");
   if ((demean == nullptr) != (destd == nullptr)) return fail(h, PLDA_E_INVAL, "score_matrix_snorm: %s is NULL but its partner is not", demean ? "estd" : "emean");
   if ((dtmean == nullptr) != (dtstd == nullptr)) return fail(h, PLDA_E_INVAL, "score_matrix_snorm: %s is NULL but its partner is not", dtmean ? "tstd" : "tmean");
   if (!demean && !dtmean) return fail(h, PLDA_E_INVAL, "score_matrix_snorm: both statistic pairs are NULL (emean/estd or tmean/tstd must be given)");

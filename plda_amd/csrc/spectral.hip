@@ -576,7 +576,7 @@ int spectral_matrix_device(plda_handle *h, const float *dscores, const int64_t *
 
 int score_spectral_device(plda_handle *h, const double *dX, const SpectralArgs &a) {
   const char *fn = "score_spectral";
-  if (!h->fitted) return fail(h, PLDA_E_NOT_FITTED, "%s: model not fitted", fn);
+  if (!can_score(h)) return fail(h, PLDA_E_NOT_FITTED, "%s: model not fitted", fn);
   if (!dX) return fail(h, PLDA_E_INVAL, "%s: X is NULL", fn);
   PLDA_TRY(spectral_validate(h, fn, nullptr, false, a));
   const int D = h->Dout;

@@ -371,7 +371,7 @@ int topn_matrix_device(plda_handle *h, const float *dscores, int64_t ld, int64_t
 int score_topn_device(plda_handle *h, const double *dU, const int32_t *dn, int n_uniform, int64_t M, const double *dV, int64_t Nt,
                       const double *dzmean, const double *dzstd, const double *demean, const double *destd, const double *dtmean,
                       const double *dtstd, int axis, int64_t top_n, float *dos, int64_t *doi, const CountSet *cs_in) {
-  if (!h->fitted) return fail(h, PLDA_E_NOT_FITTED, "score_topn: model not fitted");
+  if (!can_score(h)) return fail(h, PLDA_E_NOT_FITTED, "score_topn: model not fitted");
   PLDA_TRY(topn_check(h, "score_topn", M, Nt, axis, top_n, dos, doi));
   if ((dzmean == nullptr) != (dzstd == nullptr)) return fail(h, PLDA_E_INVAL, "score_topn: %s is NULL but its partner is not", dzmean ? "zstd" : "zmean");
   if ((demean == nullptr) != (destd == nullptr)) return fail(h, PLDA_E_INVAL, "score_topn: %s is NULL but its partner is not", demean ? "estd" : "emean");
