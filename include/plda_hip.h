@@ -1282,7 +1282,9 @@ int plda_blend_model(plda_handle *h, int32_t D, const double *mean2, const doubl
  *                         (each block at a 256-byte boundary), clustered, dropped.  A prepared test side is dropped, as in
  *                         plda_cohort_stats_dev.
  * OUT OF SCOPE, each on purpose: Kaldi's per-recording mean subtraction; its two-pass clustering of very long recordings;
- * several workgroups on one recording.  (The per-recording PCA before scoring is the next section.)  (DER is the section "diarisation error rate" below; RTTM files are
+ * one problem above PLDA_AHC_WIDE_MAX = 32768 vectors; one problem on more than one GPU.  (Several workgroups on one problem,
+ * for N above PLDA_AHC_MAX, are the section "corpus-scale clustering" below.)  (The per-recording PCA before scoring is the
+ * section after it.)  (DER is the section "diarisation error rate" below; RTTM files are
  * read and written by plda_amd/rttm.py, on the host.) ---- */
 #define PLDA_AHC_MAX 4096
 int plda_ahc_plan(plda_handle *h, int64_t N, int32_t out[3]);
@@ -1298,6 +1300,60 @@ int plda_score_ahc_dev(plda_handle *h, const double *dX, const int64_t *offsets,
 int plda_score_ahc(plda_handle *h, const double *X, const int64_t *offsets, int64_t R, int32_t has_threshold, double threshold,
                    const int32_t *min_clusters, int32_t *labels, int32_t *n_clusters, int32_t *merge_a, int32_t *merge_b,
                    double *merge_cost);
+
+/* ---- corpus-scale clustering (K28; csrc/ahc.hip, the "wide" class): ONE clustering problem of N vectors, 1 <= N <=
+ * PLDA_AHC_WIDE_MAX, spread over the whole device -- the first step of clustering-based domain adaptation (Garcia-Romero et
+ * al. 2014: cluster the unlabelled in-domain corpus with the out-of-domain model, fit a model on the pseudo-labels,
+ * interpolate), and recordings longer than PLDA_AHC_MAX segments.
+ *
+ * The CONTRACT is that of "speaker clustering" above with R = 1, word for word: the cost c(i, j), sums updated by one fp64
+ * addition with the operands in that order, v = one IEEE division by the integer product of the sizes (below 2^28 at this N),
+ * the order (v, a, b) with -0.0 == +0.0, the stop rule, labels by ascending slot, the merge record [N - 1] with its -1 / -1 /
+ * +inf tail, and the failure on a non-finite off-diagonal score with the count.  tests/ahc_model.py is the model of both; at
+ * N <= PLDA_AHC_MAX the wide class and the one-workgroup classes give the same bits.
+ *
+ * METHOD.  The state lives in handle scratch (one layout list in the clustering scratch buffer: the operand form's fp32 block,
+ * 4 N^2 bytes; the N x N fp64 sums, 8 N^2 bytes -- 8 GiB at the maximum; sizes; the row cache, best partner b > a and its v;
+ * parents; the rescan list; the row scans' partial results; the control words with the merge cursor), freed by plda_destroy.
+ * A STEP is three launches, and launch boundaries are the only synchronisation between workgroups: SELECT (one workgroup: the
+ * minimum of the row cache under (v, a), the stop rule -- a stop sets a device-side `done` word --, the merge entry, sizes,
+ * parent[b] = a), UPDATE (a grid over x: sum(a, x) += sum(b, x) into row a and column a; a row whose cached partner was a or b
+ * is appended to the rescan list, any other row x < a takes v(x, a) if it wins), RESCAN (a grid striding over the list and
+ * row a; a row is scanned in a fixed number of column pieces, each by one workgroup, and the workgroup that finishes a row's
+ * last piece combines them in piece order -- nobody waits).  Every kernel returns at once when `done` is set.  No workgroup
+ * waits on another inside a launch; every loop is bounded by N.  With a threshold the host enqueues a batch of steps and then
+ * reads `done`; when only a cluster count stops the run the number of steps is known and nothing is read until the end.  The
+ * final slot of every vector comes from the parents (parent[b] = a < b) by pointer jumping, then the label rule.
+ *
+ *   plda_ahc_wide_plan        out[0] = the scratch bytes of the matrix form at N (the operand form adds 4 N^2), out[1] = the
+ *                             launches per step, out[2] = the steps per host check, out[3] = the pieces a row scan is split
+ *                             into.  PLDA_AHC_WIDE_BATCH and PLDA_AHC_WIDE_PIECES in the environment at plda_create set the
+ *                             last two (tests; 1 ... 65536 and 1 ... 64, anything else: the default); the result depends on
+ *                             neither.
+ *   plda_ahc_wide_matrix_dev  the fp32 block in HBM, row-major N x N with row stride ld >= N (in floats); min_clusters is ONE
+ *                             value >= 1; outputs in HBM: labels [N], n_clusters [1], the nullable merge record [N - 1].
+ *                             Takes EVERY N from 1 up and always runs the wide class.  PLDA_E_INVAL: N < 1 or N >
+ *                             PLDA_AHC_WIDE_MAX, ld < N, a NaN threshold, min_clusters < 1, one or two of the three merge
+ *                             pointers.  Synchronises the stream at every host check and once at the end.
+ *   plda_ahc_wide_matrix      the same with scores and outputs in host memory.
+ *   plda_score_ahc_wide*      the operand form: X [N, Dout] already-transformed vectors (num_examples = 1).  The block is what
+ *                             plda_score_matrix_dev(X, NULL, 1, N, X, N, NULL, NULL, .., ld_out = N) writes, bit for bit,
+ *                             scored into the class's own block array (not the S-norm slab: its 2 GiB rule does not fit),
+ *                             clustered, dropped.  A cosine handle takes the same path.  A prepared test side is dropped.
+ * OUT OF SCOPE: see "speaker clustering". ---- */
+#define PLDA_AHC_WIDE_MAX 32768
+int plda_ahc_wide_plan(plda_handle *h, int64_t N, int64_t out[4]);
+int plda_ahc_wide_matrix_dev(plda_handle *h, const float *dscores, int64_t N, int64_t ld, int32_t has_threshold, double threshold,
+                             int32_t min_clusters, int32_t *dlabels, int32_t *dn_clusters, int32_t *dmerge_a, int32_t *dmerge_b,
+                             double *dmerge_cost);
+int plda_ahc_wide_matrix(plda_handle *h, const float *scores, int64_t N, int64_t ld, int32_t has_threshold, double threshold,
+                         int32_t min_clusters, int32_t *labels, int32_t *n_clusters, int32_t *merge_a, int32_t *merge_b,
+                         double *merge_cost);
+int plda_score_ahc_wide_dev(plda_handle *h, const double *dX, int64_t N, int32_t has_threshold, double threshold,
+                            int32_t min_clusters, int32_t *dlabels, int32_t *dn_clusters, int32_t *dmerge_a, int32_t *dmerge_b,
+                            double *dmerge_cost);
+int plda_score_ahc_wide(plda_handle *h, const double *X, int64_t N, int32_t has_threshold, double threshold, int32_t min_clusters,
+                        int32_t *labels, int32_t *n_clusters, int32_t *merge_a, int32_t *merge_b, double *merge_cost);
 
 /* ---- spectral clustering with auto-tuned pruning (K24; csrc/spectral.hip): the clusterer that needs no threshold and no
  * development set -- a pruned k-nearest-neighbour affinity graph, the speaker count from the largest eigengap of its

@@ -125,6 +125,17 @@ class PLDA(object):
             return self._instance.cluster(x, offsets, threshold, num_speakers, return_merges)
         return self._instance.cluster(x, offsets, threshold, num_speakers, return_merges, target_energy=target_energy)
 
+    def cluster_corpus(self, x, threshold=0.0, num_speakers=None, return_merges=False):
+        """Cluster a whole unlabelled corpus x [N, featdim] (N up to 32768, one problem on the whole device) into
+        pseudo-speakers; returns (labels, n_clusters[, merges]); plda_amd/diarize.py."""
+        return self._instance.cluster_corpus(x, threshold, num_speakers, return_merges)
+
+    def adapt_clustered(self, x, threshold=0.0, num_speakers=None, alpha=0.5, alpha_mean=None, min_cluster_size=2, iters=10):
+        """Clustering-based domain adaptation: cluster_corpus(x), fit an in-domain model on the pseudo-labels of the clusters of
+        at least min_cluster_size rows, blend it in; returns a plda_amd.adaptation.ClusteredAdaptation.  Clears the z-norm
+        statistics and the stored calibration."""
+        return self._instance.adapt_clustered(x, threshold, num_speakers, alpha, alpha_mean, min_cluster_size, iters)
+
     def score_dense(self, x, offsets, target_energy, return_info=False):
         """Every recording's segment pairs scored in the PCA subspace of its own segment vectors; a list of [N_r, N_r] float32
         blocks[, {"dims", "eigenvalues"}]; plda_amd/diarize.py."""

@@ -171,6 +171,11 @@ SIGNATURES = {
     "plda_ahc_matrix": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _f64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "plda_score_ahc_dev": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _f64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "plda_score_ahc": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _f64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "plda_ahc_wide_plan": (C.c_int, [_vp, _i64, _vp]),
+    "plda_ahc_wide_matrix_dev": (C.c_int, [_vp, _vp, _i64, _i64, _i32, _f64, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "plda_ahc_wide_matrix": (C.c_int, [_vp, _vp, _i64, _i64, _i32, _f64, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "plda_score_ahc_wide_dev": (C.c_int, [_vp, _vp, _i64, _i32, _f64, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "plda_score_ahc_wide": (C.c_int, [_vp, _vp, _i64, _i32, _f64, _i32, _vp, _vp, _vp, _vp, _vp]),
     "plda_dense_pca_plan": (C.c_int, [_vp, _i64, _i32, _vp]),
     "plda_score_dense_pca_dev": (C.c_int, [_vp, _vp, _vp, _i64, _f64, _vp, _vp, _vp, _vp]),
     "plda_score_dense_pca": (C.c_int, [_vp, _vp, _vp, _i64, _f64, _vp, _vp, _vp, _vp]),

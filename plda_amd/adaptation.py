@@ -31,3 +31,24 @@ class Adaptation(object):
     def __repr__(self):
         return "Adaptation(rows=%d, tot_weight=%g, n_excess=%d of %d, mean_shift=%g)" % (
             self.rows, self.tot_weight, self.n_excess, self.eigenvalues.shape[0], self.mean_shift)
+
+
+class ClusteredAdaptation(object):
+    """Result of one clustering-based adaptation (MPlda.adapt_clustered; Garcia-Romero et al. 2014).
+
+    labels         int32 [N]: the pseudo-speaker of every corpus row, as cluster_corpus numbers them
+    n_clusters     how many clusters the corpus fell into
+    rows_kept      the rows the in-domain model was fitted on (those of clusters of at least min_cluster_size members)
+    clusters_kept  the clusters they belong to
+    """
+    __slots__ = ("labels", "n_clusters", "rows_kept", "clusters_kept")
+
+    def __init__(self, labels, n_clusters, rows_kept, clusters_kept):
+        self.labels = np.asarray(labels, np.int32)
+        self.n_clusters = int(n_clusters)
+        self.rows_kept = int(rows_kept)
+        self.clusters_kept = int(clusters_kept)
+
+    def __repr__(self):
+        return "ClusteredAdaptation(rows_kept=%d of %d, clusters_kept=%d of %d)" % (
+            self.rows_kept, self.labels.shape[0], self.clusters_kept, self.n_clusters)

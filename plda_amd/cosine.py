@@ -3,7 +3,7 @@
 A Cosine object is an MPlda whose handle was switched with plda_backend_set(h, PLDA_BACKEND_COSINE, dim): it holds no PLDA
 model, a score is the cosine of the two vectors (length-normalised on the device, in fp64, before the one rounding to the
 trials GEMM's fp32 operands), and everything behind the score is MPlda's own: score_matrix, score_trials,
-score_matrix_asnorm, top_n, min_dcf, min_cllr, calibrate*, fuse, evaluate, partition, cluster (AHC and spectral) and the
+score_matrix_asnorm, top_n, min_dcf, min_cllr, calibrate*, fuse, evaluate, partition, cluster (AHC and spectral), cluster_corpus and the
 *_dev methods, unchanged.
 """
 import ctypes as C
@@ -36,6 +36,9 @@ class Cosine(MPlda):
 
     def adapt(self, *a, **kw):
         raise ValueError(_NEEDS_MODEL % "adapt")
+
+    def adapt_clustered(self, *a, **kw):
+        raise ValueError(_NEEDS_MODEL % "adapt_clustered")
 
     def resegment(self, *a, **kw):
         raise ValueError(_NEEDS_MODEL % "resegment")

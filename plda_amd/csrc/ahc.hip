@@ -15,6 +15,8 @@
 //                       <HBM = true>  the full symmetric matrix in scratch (row a and row b of a merge are then contiguous).
 //                       Both keep the per-slot state in LDS: size, best partner b > a and its v, the member list of the slot.
 //   ahc_label_kernel    the final slot of every segment -> cluster numbers 0 .. k - 1 by ascending slot
+//   ahcw_*_kernel       the WIDE class (K28, at the end of the file): ONE problem of up to PLDA_AHC_WIDE_MAX vectors on the whole
+//                       device under the same contract -- the state in handle scratch, a step cut into three launches
 //
 // One step: (1) the global minimum (v, a) is a workgroup reduction over the row cache; (2) sum(a, x) += sum(b, x) for every
 // live x, and while x is in hand: a row x < a whose cached partner was a or b, or a row a < x < b whose partner was b, is
@@ -460,7 +462,382 @@ int ahc_finish(plda_handle *h, const char *fn, int rc) {
   return PLDA_OK;
 }
 
+// ================================================================================================ the wide class (K28)
+// ONE problem of N <= PLDA_AHC_WIDE_MAX vectors on the whole device: the same contract, the state in handle scratch, a step
+// cut into three launches (select, update, rescan) so that launch boundaries are the only synchronisation between
+// workgroups.  No kernel waits on another workgroup; every loop is bounded by N; every kernel returns at once when the
+// control block's `done` is set.
+constexpr int AHCW_MAX = PLDA_AHC_WIDE_MAX;
+constexpr int AHCW_LAUNCHES = 3;               // select, update, rescan
+constexpr int AHCW_BATCH = 256;                // steps between two host reads of `done` (a threshold run only)
+constexpr int AHCW_T = 256;                    // update: rows per workgroup; rescan: threads of a piece
+constexpr int AHCW_T_SELECT = 1024;
+constexpr int AHCW_PIECE_ALIGN = 256;          // a piece's length is a multiple of this
+constexpr int AHCW_PIECE_COLS = 4096;          // default: one piece per this many columns, at most AHCW_PIECES_MAX
+constexpr int AHCW_PIECES_DEFAULT_MAX = 8, AHCW_PIECES_MAX = 64;
+constexpr int AHCW_SCAN_ROWS = 128;            // rescan: the rows of the grid (it strides over the list)
+constexpr int AHCW_JUMP_ROUNDS = 16;           // pointer jumping: a chain of parents is shorter than 2^15
+static_assert(AHCW_MAX <= (1 << 15), "the jump rounds, the 32-bit size product and the label kernel's LDS assume N <= 2^15");
+
+struct AhcwCtl { int done, m, k, a, b, nsa, cnt, pad; };   // merge cursor m, live slots k, the step's pair and new size, list length
+
+// the arrays of the wide class in h->ahc_scratch: one layout list (common.hpp: carve)
+struct AhcwState {
+  float *block;            // the operand form's fp32 score block [N, N] (the matrix form: empty)
+  double *sums;            // [N, N] fp64, full and symmetric
+  double *bv;              // [N] row cache: the value of the best partner
+  double *part_v;          // [(N + 1) * P] a row scan's partial results, by list position and piece
+  int *sz, *bp, *parent;   // [N] sizes (0: dead), row cache: best partner b > a (-1: none), parent[b] = a of the merge that ended b
+  int *list;               // [N + 1] the rows a step rescans (list positions 0 .. cnt - 1; row a is position cnt)
+  int *part_p;             // [(N + 1) * P]
+  unsigned *arrive;        // [N + 1] pieces of a list position that have finished (back to 0 when the last one has combined)
+  AhcwCtl *ctl;
+  void lay(Layout &c, size_t n, size_t P, bool with_block) {
+    c.take(block, with_block ? n * n : 0, 256).take(sums, n * n, 256).take(bv, n).take(part_v, (n + 1) * P).take(sz, n).take(bp, n)
+        .take(parent, n).take(list, n + 1).take(part_p, (n + 1) * P).take(arrive, n + 1).take(ctl, 1);
+  }
+};
+
+int ahcw_batch(const plda_handle *h) { return h->ahc_wide_batch >= 1 && h->ahc_wide_batch <= 65536 ? (int)h->ahc_wide_batch : AHCW_BATCH; }
+int ahcw_pieces(const plda_handle *h, int64_t n) {
+  if (h->ahc_wide_pieces >= 1 && h->ahc_wide_pieces <= AHCW_PIECES_MAX) return (int)h->ahc_wide_pieces;
+  return (int)std::max<int64_t>(1, std::min<int64_t>(ceil_div(n, (int64_t)AHCW_PIECE_COLS), AHCW_PIECES_DEFAULT_MAX));
+}
+int ahcw_piece_len(int64_t n, int P) { return (int)round_up(ceil_div(n, (int64_t)P), (int64_t)AHCW_PIECE_ALIGN); }
+
+// grid (pieces): the off-diagonal scores that are not finite, added to *bad
+__global__ __launch_bounds__(256) void ahcw_count_kernel(const float *__restrict__ S, int n, long long ld, unsigned long long *bad) {
+  const long long total = (long long)n * n;
+  unsigned cnt = 0;
+  for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long long)gridDim.x * 256) {
+    const long long i = e / n, j = e - i * n;
+    if (i != j && !ahc_finite(S[i * ld + j])) ++cnt;
+  }
+  if (cnt) atomicAdd(bad, (unsigned long long)cnt);
+}
+
+// grid (tiles, tiles), 32 x 32 threads: sums[i, j] = c(i, j), the transposed tile through LDS; diagonal 0
+__global__ __launch_bounds__(1024) void ahcw_load_kernel(const float *__restrict__ S, int n, long long ld, double *__restrict__ sums,
+                                                         const unsigned long long *__restrict__ bad) {
+  __shared__ float tile[32][33];
+  if (*bad) return;
+  const int ti = blockIdx.y, tj = blockIdx.x, tx = threadIdx.x, ty = threadIdx.y;
+  {
+    const int r = tj * 32 + ty, c = ti * 32 + tx;
+    tile[ty][tx] = (r < n && c < n) ? S[(long long)r * ld + c] : 0.f;
+  }
+  __syncthreads();
+  const int i = ti * 32 + ty, j = tj * 32 + tx;
+  if (i < n && j < n) sums[(long long)i * n + j] = i == j ? 0.0 : ahc_cost(S[(long long)i * ld + j], tile[tx][ty]);
+}
+
+// grid over x: every slot alive and its own parent, every row on the list (the first rescan fills the whole row cache)
+__global__ __launch_bounds__(AHCW_T) void ahcw_init_kernel(int n, AhcwState st, const unsigned long long *__restrict__ bad) {
+  const int x = blockIdx.x * AHCW_T + threadIdx.x;
+  if (x < n) { st.sz[x] = 1; st.parent[x] = x; st.list[x] = x; st.arrive[x] = 0u; }
+  if (x == 0) {
+    st.arrive[n] = 0u;
+    AhcwCtl c;
+    c.done = *bad ? 1 : 0; c.m = 0; c.k = n; c.a = -1; c.b = -1; c.nsa = 0; c.cnt = n; c.pad = 0;
+    *st.ctl = c;
+  }
+}
+
+// one workgroup: the pair to merge is the minimum over the row cache by (v, a), b comes with the row; the stop rule; the merge
+// entry, the sizes, the parent of b and the step's descriptor
+__global__ __launch_bounds__(AHCW_T_SELECT) void ahcw_select_kernel(int n, AhcwState st, int stop_k, int has_thr, double neg_thr,
+                                                                    int *__restrict__ merge_a, int *__restrict__ merge_b,
+                                                                    double *__restrict__ merge_cost) {
+  __shared__ double red_v[AHCW_T_SELECT / 64];
+  __shared__ int red_i[AHCW_T_SELECT / 64];
+  if (st.ctl->done) return;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  double v = 0.0;
+  int a = -1;
+  for (int x = tid; x < n; x += AHCW_T_SELECT) {
+    if (st.sz[x] > 0 && st.bp[x] >= 0) {
+      const double c = st.bv[x];
+      if (a < 0 || c < v) { v = c; a = x; }      // x ascends within a thread
+    }
+  }
+  ahc_wave_min(v, a);
+  if (lane == 0) { red_v[wave] = v; red_i[wave] = a; }
+  __syncthreads();
+  if (tid != 0) return;
+  v = red_v[0]; a = red_i[0];
+  for (int w = 1; w < AHCW_T_SELECT / 64; ++w) {
+    const double ov = red_v[w];
+    const int oi = red_i[w];
+    if (oi >= 0 && (a < 0 || ov < v || (ov == v && oi < a))) { v = ov; a = oi; }
+  }
+  AhcwCtl c = *st.ctl;
+  if (c.k <= stop_k || a < 0 || (has_thr && !(v <= neg_thr))) { st.ctl->done = 1; return; }
+  const int b = st.bp[a];
+  if (merge_a) { merge_a[c.m] = a; merge_b[c.m] = b; merge_cost[c.m] = v; }
+  c.nsa = st.sz[a] + st.sz[b];
+  st.sz[a] = c.nsa; st.sz[b] = 0;
+  st.parent[b] = a;
+  c.a = a; c.b = b; c.m += 1; c.k -= 1; c.cnt = 0;
+  *st.ctl = c;
+}
+
+// grid over x, one thread per slot: the sums of a take b's (row a and column a), and while x is in hand the cache logic: a row
+// x < a whose cached partner was a or b, or a row a < x < b whose partner was b, goes on the rescan list (in any order: every
+// row of it is rescanned on its own); any other row x < a takes the new v(x, a) if it beats its cache under (v, partner)
+__global__ __launch_bounds__(AHCW_T) void ahcw_update_kernel(int n, AhcwState st) {
+  if (st.ctl->done) return;
+  const int x = blockIdx.x * AHCW_T + threadIdx.x;
+  if (x >= n) return;
+  const int a = st.ctl->a, b = st.ctl->b, nsa = st.ctl->nsa;
+  const int sx = st.sz[x];
+  if (sx <= 0 || x == a || x == b) return;
+  const double s = st.sums[(long long)a * n + x] + st.sums[(long long)b * n + x];
+  st.sums[(long long)a * n + x] = s;
+  st.sums[(long long)x * n + a] = s;
+  if (x < a) {
+    const int p = st.bp[x];
+    if (p == a || p == b) st.list[atomicAdd(&st.ctl->cnt, 1)] = x;      // (at most n - 2 appends: x != a, x != b)
+    else {
+      const double c = s / (double)(nsa * sx);
+      const double o = st.bv[x];
+      if (c < o || (c == o && a < p)) { st.bv[x] = c; st.bp[x] = a; }
+    }
+  } else if (x < b) {
+    if (st.bp[x] == b) st.list[atomicAdd(&st.ctl->cnt, 1)] = x;
+  }
+}
+
+// grid (P pieces, rows): the grid's rows stride over the list positions 0 .. cnt - 1 and, with_a, position cnt = row a.  A
+// workgroup scans the live y > x of its piece [piece * L, (piece + 1) * L) of the row by (v, y).  P == 1: that is the row's
+// result.  P > 1: it publishes its partial result and counts itself in; the workgroup that counts in last combines the P
+// partial results in piece order (the pieces ascend in y: a tie keeps the smaller y) -- whoever that is, the result is the
+// same, and nobody waits.
+__global__ __launch_bounds__(AHCW_T) void ahcw_rescan_kernel(int n, AhcwState st, int P, int L, int with_a) {
+  __shared__ double red_v[AHCW_T / 64];
+  __shared__ int red_i[AHCW_T / 64];
+  if (st.ctl->done) return;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, piece = blockIdx.x;
+  const int nl = st.ctl->cnt, total = min(nl + (with_a ? 1 : 0), n + 1);
+  for (int q = blockIdx.y; q < total; q += gridDim.y) {
+    const int x = q < nl ? st.list[q] : st.ctl->a;
+    const int sx = st.sz[x];
+    const int y0 = max(piece * L, x + 1), y1 = min((piece + 1) * L, n);
+    const double *__restrict__ row = st.sums + (long long)x * n;
+    double v = 0.0;
+    int p = -1;
+#pragma unroll 4
+    for (int y = y0 + tid; y < y1; y += AHCW_T) {
+      const int sy = st.sz[y];
+      const double s = row[y];
+      if (sy > 0) {
+        const double c = s / (double)(sx * sy);
+        if (p < 0 || c < v) { v = c; p = y; }      // y ascends within a thread: a tie keeps the smaller y
+      }
+    }
+    ahc_wave_min(v, p);
+    if (lane == 0) { red_v[wave] = v; red_i[wave] = p; }
+    __syncthreads();
+    if (tid == 0) {
+      for (int w = 1; w < AHCW_T / 64; ++w) {
+        const double ov = red_v[w];
+        const int oi = red_i[w];
+        if (oi >= 0 && (p < 0 || ov < v || (ov == v && oi < p))) { v = ov; p = oi; }
+      }
+      if (P == 1) { st.bv[x] = v; st.bp[x] = p; }
+      else {
+        const long long slot = (long long)q * P;
+        __hip_atomic_store(&st.part_v[slot + piece], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(&st.part_p[slot + piece], p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const unsigned before = __hip_atomic_fetch_add(&st.arrive[q], 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+        if (before == (unsigned)(P - 1)) {
+          double c = 0.0;
+          int bp = -1;
+          for (int j = 0; j < P; ++j) {
+            const double oc = __hip_atomic_load(&st.part_v[slot + j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const int op = __hip_atomic_load(&st.part_p[slot + j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (op >= 0 && (bp < 0 || oc < c)) { c = oc; bp = op; }
+          }
+          st.bv[x] = c; st.bp[x] = bp;
+          __hip_atomic_store(&st.arrive[q], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+      }
+    }
+    __syncthreads();
+  }
+}
+
+// one workgroup: every vector's final slot from the parents (parent[b] = a < b; a dead slot's chain ends at a live one) by
+// pointer jumping in LDS, the live slots ranked in ascending order, the labels, the cluster count and the record's tail
+__global__ __launch_bounds__(1024) void ahcw_label_kernel(int n, AhcwState st, const unsigned long long *__restrict__ bad,
+                                                          int *__restrict__ labels, int *__restrict__ n_clusters,
+                                                          int *__restrict__ merge_a, int *__restrict__ merge_b,
+                                                          double *__restrict__ merge_cost) {
+  extern __shared__ int ahcw_par[];
+  __shared__ int part[1024];
+  if (*bad) return;
+  volatile int *par = ahcw_par;
+  const int tid = threadIdx.x;
+  for (int i = tid; i < n; i += 1024) par[i] = st.parent[i];
+  __syncthreads();
+  // in place: whatever a read meets, old or new, is an ancestor at least as far as the old one, so a chain halves per round
+  for (int r = 0; r < AHCW_JUMP_ROUNDS; ++r) {
+    for (int i = tid; i < n; i += 1024) par[i] = par[par[i]];
+    __syncthreads();
+  }
+  const int per = (n + 1023) / 1024, s0 = min(tid * per, n), s1 = min(s0 + per, n);
+  int c = 0;
+  for (int s = s0; s < s1; ++s) c += par[s] == s ? 1 : 0;
+  part[tid] = c;
+  __syncthreads();
+  int base = 0;
+  for (int t = 0; t < tid; ++t) base += part[t];
+  __syncthreads();
+  for (int s = s0; s < s1; ++s)
+    if (par[s] == s) { par[s] = -1 - base; ++base; }      // a live slot now holds its rank, encoded below zero
+  __syncthreads();
+  for (int i = tid; i < n; i += 1024) {
+    const int p = par[i];
+    labels[i] = p < 0 ? -1 - p : -1 - par[p];
+  }
+  const int m = st.ctl->m;
+  if (merge_a)
+    for (int q = m + tid; q < n - 1; q += 1024) { merge_a[q] = -1; merge_b[q] = -1; merge_cost[q] = INFINITY; }
+  if (tid == 0) n_clusters[0] = st.ctl->k;
+}
+
+int ahcw_label_attr(plda_handle *h) {
+  static DeviceOnce attr;
+  if (attr.needed(h->device)) {
+    PLDA_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&ahcw_label_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    AHCW_MAX * 4));
+    attr.done(h->device);
+  }
+  return PLDA_OK;
+}
+
+int ahcw_check_args(plda_handle *h, const char *fn, int64_t N, int64_t ld, int has_thr, double thr, int32_t minc, const AhcOut &out) {
+  if (N < 1 || N > AHCW_MAX)
+    return fail(h, PLDA_E_INVAL, "%s: N = %lld (must be 1 ... PLDA_AHC_WIDE_MAX = %d)", fn, (long long)N, AHCW_MAX);
+  if (ld < N) return fail(h, PLDA_E_INVAL, "%s: ld = %lld (must be >= N = %lld)", fn, (long long)ld, (long long)N);
+  if (!out.labels) return fail(h, PLDA_E_INVAL, "%s: labels is NULL", fn);
+  if (!out.n_clusters) return fail(h, PLDA_E_INVAL, "%s: n_clusters is NULL", fn);
+  const int nm = (out.merge_a ? 1 : 0) + (out.merge_b ? 1 : 0) + (out.merge_cost ? 1 : 0);
+  if (nm != 0 && nm != 3) return fail(h, PLDA_E_INVAL, "%s: merge_a, merge_b and merge_cost must be given together or not at all", fn);
+  if (has_thr && std::isnan(thr)) return fail(h, PLDA_E_INVAL, "%s: threshold is NaN", fn);
+  if (minc < 1) return fail(h, PLDA_E_INVAL, "%s: min_clusters = %d (must be >= 1)", fn, (int)minc);
+  return PLDA_OK;
+}
+
+// carves the state (the operand form: with its block array) and zeroes the counter of non-finite scores
+int ahcw_prepare(plda_handle *h, int64_t N, bool with_block, AhcwState &st) {
+  const int P = ahcw_pieces(h, N);
+  PLDA_TRY(carve(h, h->ahc_scratch, [&](Layout &c) { st.lay(c, (size_t)N, (size_t)P, with_block); }));
+  PLDA_HIP(h, h->ahc_stat.reserve(8));
+  PLDA_HIP(h, hipMemsetAsync(h->ahc_stat.p, 0, 8, h->stream));
+  return PLDA_OK;
+}
+
+// Enqueues the whole clustering of the block at dscores (row stride ld) on the state st; reads `done` between batches of
+// steps when a threshold may stop the run early.  The caller finishes with ahc_finish.
+int ahcw_enqueue(plda_handle *h, const float *dscores, int64_t N, int64_t ld, int has_thr, double thr, int32_t minc, const AhcwState &st,
+                 const AhcOut &out) {
+  const int n = (int)N, P = ahcw_pieces(h, N), L = ahcw_piece_len(N, P), batch = ahcw_batch(h);
+  const int stop_k = minc > 1 ? minc : 1;
+  unsigned long long *dbad = h->ahc_stat.as<unsigned long long>();
+  PLDA_TRY(ahcw_label_attr(h));
+  TraceScope ts(h, "ahc.wide_load");
+  {
+    const int64_t pieces = std::max<int64_t>(1, std::min<int64_t>(ceil_div(N * N, (int64_t)256 * 16), 4096));
+    ahcw_count_kernel<<<(unsigned)pieces, 256, 0, h->stream>>>(dscores, n, (long long)ld, dbad);
+    PLDA_LAUNCH_CHECK(h);
+    const unsigned nt = (unsigned)((n + 31) / 32);
+    ahcw_load_kernel<<<dim3(nt, nt), dim3(32, 32), 0, h->stream>>>(dscores, n, (long long)ld, st.sums, dbad);
+    PLDA_LAUNCH_CHECK(h);
+    const unsigned gx = (unsigned)ceil_div((int64_t)n, (int64_t)AHCW_T);
+    ahcw_init_kernel<<<gx, AHCW_T, 0, h->stream>>>(n, st, dbad);
+    PLDA_LAUNCH_CHECK(h);
+    ahcw_rescan_kernel<<<dim3((unsigned)P, (unsigned)std::min(n, 4096)), AHCW_T, 0, h->stream>>>(n, st, P, L, 0);
+    PLDA_LAUNCH_CHECK(h);
+  }
+  ts.next("ahc.wide_merge");
+  const unsigned gx = (unsigned)ceil_div((int64_t)n, (int64_t)AHCW_T);
+  const dim3 gscan((unsigned)P, (unsigned)std::min(n, AHCW_SCAN_ROWS));
+  int64_t left = N - stop_k;
+  while (left > 0) {
+    const int64_t c = has_thr ? std::min<int64_t>(batch, left) : left;
+    for (int64_t s = 0; s < c; ++s) {
+      ahcw_select_kernel<<<1, AHCW_T_SELECT, 0, h->stream>>>(n, st, stop_k, has_thr, -thr, out.merge_a, out.merge_b, out.merge_cost);
+      ahcw_update_kernel<<<gx, AHCW_T, 0, h->stream>>>(n, st);
+      ahcw_rescan_kernel<<<gscan, AHCW_T, 0, h->stream>>>(n, st, P, L, 1);
+      PLDA_LAUNCH_CHECK(h);
+    }
+    left -= c;
+    if (has_thr && left > 0) {
+      int done = 0;
+      PLDA_HIP(h, hipMemcpyAsync(&done, &st.ctl->done, 4, hipMemcpyDeviceToHost, h->stream));
+      PLDA_HIP(h, hipStreamSynchronize(h->stream));
+      if (done) break;
+    }
+  }
+  ts.next("ahc.wide_label");
+  ahcw_label_kernel<<<1, 1024, (size_t)n * 4, h->stream>>>(n, st, dbad, out.labels, out.n_clusters, out.merge_a, out.merge_b, out.merge_cost);
+  PLDA_LAUNCH_CHECK(h);
+  return PLDA_OK;
+}
+
 }  // namespace
+
+int ahc_wide_plan(plda_handle *h, int64_t N, int64_t *out) {
+  if (!out) return fail(h, PLDA_E_INVAL, "ahc_wide_plan: out is NULL");
+  if (N < 1 || N > AHCW_MAX)
+    return fail(h, PLDA_E_INVAL, "ahc_wide_plan: N = %lld (must be 1 ... PLDA_AHC_WIDE_MAX = %d)", (long long)N, AHCW_MAX);
+  const int P = ahcw_pieces(h, N);
+  AhcwState st;
+  Layout size;
+  st.lay(size, (size_t)N, (size_t)P, false);
+  out[0] = (int64_t)size.end;
+  out[1] = AHCW_LAUNCHES;
+  out[2] = ahcw_batch(h);
+  out[3] = P;
+  return PLDA_OK;
+}
+
+int ahc_wide_validate(plda_handle *h, const char *fn, int64_t N, int64_t ld, int has_thr, double thr, int32_t minc, const int32_t *labels,
+                      const int32_t *n_clusters, const int32_t *merge_a, const int32_t *merge_b, const double *merge_cost) {
+  const AhcOut out{const_cast<int32_t *>(labels), const_cast<int32_t *>(n_clusters), const_cast<int32_t *>(merge_a),
+                   const_cast<int32_t *>(merge_b), const_cast<double *>(merge_cost)};
+  return ahcw_check_args(h, fn, N, ld, has_thr, thr, minc, out);
+}
+
+int ahc_wide_matrix_device(plda_handle *h, const float *dscores, int64_t N, int64_t ld, int has_thr, double thr, int32_t minc,
+                           int32_t *dlabels, int32_t *dn_clusters, int32_t *dmerge_a, int32_t *dmerge_b, double *dmerge_cost) {
+  const char *fn = "ahc_wide_matrix";
+  const AhcOut out{dlabels, dn_clusters, dmerge_a, dmerge_b, dmerge_cost};
+  if (!dscores) return fail(h, PLDA_E_INVAL, "%s: scores is NULL", fn);
+  PLDA_TRY(ahcw_check_args(h, fn, N, ld, has_thr, thr, minc, out));
+  AhcwState st;
+  PLDA_TRY(ahcw_prepare(h, N, false, st));
+  return ahc_finish(h, fn, ahcw_enqueue(h, dscores, N, ld, has_thr, thr, minc, st, out));
+}
+
+int score_ahc_wide_device(plda_handle *h, const double *dX, int64_t N, int has_thr, double thr, int32_t minc, int32_t *dlabels,
+                          int32_t *dn_clusters, int32_t *dmerge_a, int32_t *dmerge_b, double *dmerge_cost) {
+  const char *fn = "score_ahc_wide";
+  const AhcOut out{dlabels, dn_clusters, dmerge_a, dmerge_b, dmerge_cost};
+  if (!can_score(h)) return fail(h, PLDA_E_NOT_FITTED, "%s: model not fitted", fn);
+  if (!dX) return fail(h, PLDA_E_INVAL, "%s: X is NULL", fn);
+  PLDA_TRY(ahcw_check_args(h, fn, N, N, has_thr, thr, minc, out));
+  AhcwState st;
+  PLDA_TRY(ahcw_prepare(h, N, true, st));
+  h->prep_valid = false;           // (the block packs its own two sides)
+  int rc;
+  {
+    TraceScope ts(h, "ahc.block_gemm", 2.0 * (double)h->Dout * (double)N * (double)N, 1);
+    rc = score_matrix_device(h, dX, nullptr, 1, N, dX, N, nullptr, nullptr, st.block, N);
+  }
+  if (rc == PLDA_OK) rc = ahcw_enqueue(h, st.block, N, N, has_thr, thr, minc, st, out);
+  return ahc_finish(h, fn, rc);
+}
 
 int ahc_validate(plda_handle *h, const char *fn, const int64_t *block_off, bool blocks, const int64_t *offsets, int64_t R, int has_thr,
                  double thr, const int32_t *minc, const int32_t *labels, const int32_t *n_clusters, const int32_t *merge_a,

@@ -315,6 +315,7 @@ const struct { const char *name; int64_t plda_handle::*member; } ENV_INT64[] = {
     {"PLDA_ADAPT_SLAB_ROWS", &plda_handle::ad_slab_rows},        {"PLDA_AHC_SCRATCH_BYTES", &plda_handle::ahc_scratch_bytes},
     {"PLDA_VBX_SCRATCH_BYTES", &plda_handle::vbx_scratch_bytes}, {"PLDA_DER_SCRATCH_BYTES", &plda_handle::der_scratch_bytes},
     {"PLDA_ROCCH_EDGE_CAP", &plda_handle::rocch_edge_cap},       {"PLDA_PARTITION_SLICE_ROWS", &plda_handle::partition_slice_rows},
+    {"PLDA_AHC_WIDE_BATCH", &plda_handle::ahc_wide_batch},       {"PLDA_AHC_WIDE_PIECES", &plda_handle::ahc_wide_pieces},
 };
 
 // ... and the ones that are checked: a refused value fails plda_create (the text goes to plda_last_error(NULL))
@@ -2182,6 +2183,72 @@ int plda_score_ahc(plda_handle *h, const double *X, const int64_t *offsets, int6
     PLDA_TRY(st.out(merge_b, (size_t)(T - R), &dB));
     PLDA_TRY(st.out(merge_cost, (size_t)(T - R), &dC));
     return st.finish(score_ahc_device(h, dX, offsets, R, has_threshold, threshold, min_clusters, dL, dK, dA, dB, dC));
+  });
+}
+
+// ---------------------------------------------------------------- corpus-scale clustering (ahc.hip, the wide class)
+int plda_ahc_wide_plan(plda_handle *h, int64_t N, int64_t out[4]) {
+  return entry(h, "plda_ahc_wide_plan", [&] { return ahc_wide_plan(h, N, out); });
+}
+
+int plda_ahc_wide_matrix_dev(plda_handle *h, const float *dscores, int64_t N, int64_t ld, int32_t has_threshold, double threshold,
+                             int32_t min_clusters, int32_t *dlabels, int32_t *dn_clusters, int32_t *dmerge_a, int32_t *dmerge_b,
+                             double *dmerge_cost) {
+  return device_entry(h, "plda_ahc_wide_matrix_dev", [&] {
+    return ahc_wide_matrix_device(h, dscores, N, ld, has_threshold, threshold, min_clusters, dlabels, dn_clusters, dmerge_a, dmerge_b,
+                                  dmerge_cost);
+  });
+}
+
+int plda_ahc_wide_matrix(plda_handle *h, const float *scores, int64_t N, int64_t ld, int32_t has_threshold, double threshold,
+                         int32_t min_clusters, int32_t *labels, int32_t *n_clusters, int32_t *merge_a, int32_t *merge_b,
+                         double *merge_cost) {
+  return entry(h, "plda_ahc_wide_matrix", [&]() -> int {
+    if (!scores) return fail(h, PLDA_E_INVAL, "ahc_wide_matrix: scores is NULL");
+    PLDA_TRY(ahc_wide_validate(h, "ahc_wide_matrix", N, ld, has_threshold, threshold, min_clusters, labels, n_clusters, merge_a, merge_b,
+                               merge_cost));
+    PLDA_TRY(set_device(h));
+    Staged st(h);
+    const float *dS;
+    int32_t *dL, *dK, *dA, *dB;
+    double *dC;
+    PLDA_TRY(st.in(scores, (size_t)((N - 1) * ld + N), &dS));
+    PLDA_TRY(st.out(labels, (size_t)N, &dL));
+    PLDA_TRY(st.out(n_clusters, (size_t)1, &dK));
+    PLDA_TRY(st.out(merge_a, (size_t)(N - 1), &dA));
+    PLDA_TRY(st.out(merge_b, (size_t)(N - 1), &dB));
+    PLDA_TRY(st.out(merge_cost, (size_t)(N - 1), &dC));
+    return st.finish(ahc_wide_matrix_device(h, dS, N, ld, has_threshold, threshold, min_clusters, dL, dK, dA, dB, dC));
+  });
+}
+
+int plda_score_ahc_wide_dev(plda_handle *h, const double *dX, int64_t N, int32_t has_threshold, double threshold,
+                            int32_t min_clusters, int32_t *dlabels, int32_t *dn_clusters, int32_t *dmerge_a, int32_t *dmerge_b,
+                            double *dmerge_cost) {
+  return device_entry(h, "plda_score_ahc_wide_dev", [&] {
+    return score_ahc_wide_device(h, dX, N, has_threshold, threshold, min_clusters, dlabels, dn_clusters, dmerge_a, dmerge_b, dmerge_cost);
+  });
+}
+
+int plda_score_ahc_wide(plda_handle *h, const double *X, int64_t N, int32_t has_threshold, double threshold, int32_t min_clusters,
+                        int32_t *labels, int32_t *n_clusters, int32_t *merge_a, int32_t *merge_b, double *merge_cost) {
+  return entry(h, "plda_score_ahc_wide", [&]() -> int {
+    if (!can_score(h)) return fail(h, PLDA_E_NOT_FITTED, "score_ahc_wide: model not fitted");
+    if (!X) return fail(h, PLDA_E_INVAL, "score_ahc_wide: X is NULL");
+    PLDA_TRY(ahc_wide_validate(h, "score_ahc_wide", N, N, has_threshold, threshold, min_clusters, labels, n_clusters, merge_a, merge_b,
+                               merge_cost));
+    PLDA_TRY(set_device(h));
+    Staged st(h);
+    const double *dX;
+    int32_t *dL, *dK, *dA, *dB;
+    double *dC;
+    PLDA_TRY(st.in(X, (size_t)N * h->Dout, &dX));
+    PLDA_TRY(st.out(labels, (size_t)N, &dL));
+    PLDA_TRY(st.out(n_clusters, (size_t)1, &dK));
+    PLDA_TRY(st.out(merge_a, (size_t)(N - 1), &dA));
+    PLDA_TRY(st.out(merge_b, (size_t)(N - 1), &dB));
+    PLDA_TRY(st.out(merge_cost, (size_t)(N - 1), &dC));
+    return st.finish(score_ahc_wide_device(h, dX, N, has_threshold, threshold, min_clusters, dL, dK, dA, dB, dC));
   });
 }
 

@@ -328,11 +328,13 @@ struct plda_handle {
   std::vector<double> ad_pilot;  // host mirror of the pilot (bitwise comparisons of plda_adapt_add_stats)
 
   // ---- speaker clustering (ahc.hip, spectral.hip: one call of either runs at a time and carves these anew) ----
-  plda::DevBuf ahc_scratch;      // ahc.hip: the N x N fp64 sums of the HBM-class recordings of one launch; spectral.hip: one eigenproblem's working set, then the kept columns, degrees and best-so-far records of one group (one layout list)
+  plda::DevBuf ahc_scratch;      // ahc.hip: the N x N fp64 sums of the HBM-class recordings of one launch, or the wide class's whole state (one layout list: block, sums, sizes, row cache, parents, rescan list, scan partials, control words); spectral.hip: one eigenproblem's working set, then the kept columns, degrees and best-so-far records of one group (one layout list)
   plda::DevBuf ahc_tab;          // ahc.hip: the launch table of a call (one entry per recording); spectral.hip: the call's count of non-finite scores, then the launch table of an enqueue (one layout list)
   plda::DevBuf ahc_slot;         // every segment's final slot, between the merge and the label kernel
   plda::DevBuf ahc_stat;         // the call's count of non-finite scores
   int64_t ahc_scratch_bytes = 0; // PLDA_AHC_SCRATCH_BYTES: the scratch one launch (spectral.hip: one group) may take and the score slab of the operand forms (0: 2 GiB)
+  int64_t ahc_wide_batch = 0;    // PLDA_AHC_WIDE_BATCH: the wide class's steps per host check (0: AHCW_BATCH, ahc.hip; tests -- the result does not depend on it)
+  int64_t ahc_wide_pieces = 0;   // PLDA_AHC_WIDE_PIECES: the column pieces of one row scan of the wide class (0: by N, ahc.hip; tests -- the result does not depend on it)
 
   // ---- dense scoring in a recording's PCA subspace (dense_pca.hip) ----
   plda::DevBuf dp_scratch;       // the per-recording arrays of the recordings of one launch group (one layout list per recording)
@@ -559,6 +561,14 @@ int ahc_matrix_device(plda_handle *h, const float *dscores, const int64_t *block
 int score_ahc_device(plda_handle *h, const double *dX, const int64_t *offsets, int64_t R, int has_thr, double thr,
                      const int32_t *minc, int32_t *dlabels, int32_t *dn_clusters, int32_t *dmerge_a, int32_t *dmerge_b,
                      double *dmerge_cost);
+// the wide class: one problem of N <= PLDA_AHC_WIDE_MAX vectors on the whole device (K28)
+int ahc_wide_plan(plda_handle *h, int64_t N, int64_t *out);
+int ahc_wide_validate(plda_handle *h, const char *fn, int64_t N, int64_t ld, int has_thr, double thr, int32_t minc, const int32_t *labels,
+                      const int32_t *n_clusters, const int32_t *merge_a, const int32_t *merge_b, const double *merge_cost);
+int ahc_wide_matrix_device(plda_handle *h, const float *dscores, int64_t N, int64_t ld, int has_thr, double thr, int32_t minc,
+                           int32_t *dlabels, int32_t *dn_clusters, int32_t *dmerge_a, int32_t *dmerge_b, double *dmerge_cost);
+int score_ahc_wide_device(plda_handle *h, const double *dX, int64_t N, int has_thr, double thr, int32_t minc, int32_t *dlabels,
+                          int32_t *dn_clusters, int32_t *dmerge_a, int32_t *dmerge_b, double *dmerge_cost);
 
 // ---- spectral.hip (spectral clustering with auto-tuned pruning; offsets / block_off / p_table / num_spk are HOST arrays) ----
 // The arguments every plda_spectral* / plda_score_spectral* call shares.  Outputs: labels and n_clusters are required, the rest nullable.

@@ -7,6 +7,10 @@ emission model, initialised from the clustering (csrc/vbx.hip; include/plda_hip.
     plan(engine, n)                   the dispatch class a recording of n segments takes
     cut(merges, offsets, ...)         pure NumPy: labels at another threshold / speaker count from ONE full merge record
     MPlda.cluster(x, offsets, ...)    raw segment vectors in, labels out (the blocks are scored on the device and dropped)
+    ahc_wide(engine, block, ...)      ONE problem of up to AHC_WIDE_MAX = 32768 vectors on the whole device, the same contract
+                                      (K28, "corpus-scale clustering"); ahc_wide_vectors: its operand form; plan_wide(engine, n);
+                                      MPlda.cluster_corpus(x, ...) takes raw vectors, MPlda.adapt_clustered(x, ...) fits an
+                                      in-domain model on the pseudo-labels (keep_clusters: its filter) and blends it in
     score_dense_pca(engine, x, offsets, t)   every recording's block scored in the PCA subspace of its own segment vectors
                                       (Kaldi's --target-energy=t; csrc/dense_pca.hip), one workgroup per recording
     spectral(engine, blocks, ...)     clusters the same blocks without a threshold: spectral clustering on a pruned
@@ -124,6 +128,86 @@ def ahc_vectors(engine, vecs, offsets, threshold=0.0, num_speakers=None, return_
     N.check(engine._h, engine._lib.plda_score_ahc(engine._h, _p(vecs), _p(offsets), r, has_t, thr, _p(minc), _p(labels), _p(ncl),
                                                   _p(ma), _p(mb), _p(mc)))
     return (labels, ncl, (ma, mb, mc)) if return_merges else (labels, ncl)
+
+
+# ------------------------------------------------------------------------------------------- corpus-scale clustering (K28)
+AHC_WIDE_MAX = 32768    # PLDA_AHC_WIDE_MAX
+
+
+def plan_wide(engine, n):
+    """{"scratch_bytes": the wide class's state for n vectors (the operand form adds 4 n^2), "launches_per_step",
+    "steps_per_check": the steps enqueued between two host reads of the stop word, "pieces": the column pieces of a row scan}."""
+    out = (C.c_int64 * 4)()
+    N.check(engine._h, engine._lib.plda_ahc_wide_plan(engine._h, int(n), out))
+    return {"scratch_bytes": int(out[0]), "launches_per_step": int(out[1]), "steps_per_check": int(out[2]), "pieces": int(out[3])}
+
+
+def wide_args(n, threshold, num_speakers):
+    """The argument check of ahc_wide / ahc_wide_vectors / MPlda.cluster_corpus, before any device work ->
+    (has_threshold, threshold, min_clusters) of the C ABI.  ONE problem: num_speakers is one integer >= 1 or None."""
+    if isinstance(n, bool) or int(n) != n or not 1 <= n <= AHC_WIDE_MAX:
+        raise ValueError("one problem must hold 1 ... %d vectors, got %r" % (AHC_WIDE_MAX, n))
+    if num_speakers is not None:
+        if isinstance(num_speakers, (bool, np.bool_)) or np.ndim(num_speakers) != 0 or not isinstance(num_speakers, (int, np.integer)):
+            raise ValueError("num_speakers must be one integer >= 1 (the corpus is one problem), got %r" % (num_speakers,))
+        if not 1 <= int(num_speakers) <= 0x7fffffff:
+            raise ValueError("num_speakers must be >= 1, got %r" % (num_speakers,))
+    if threshold is not None:
+        if isinstance(threshold, (bool, np.bool_)) or not isinstance(threshold, (int, float, np.integer, np.floating)):
+            raise ValueError("threshold must be a number or None, got %r" % (threshold,))
+        if np.isnan(threshold):
+            raise ValueError("threshold is NaN")
+    has_t, thr, minc = stop_args(np.asarray([0, int(n)], np.int64), threshold, num_speakers)
+    return has_t, thr, (1 if minc is None else int(minc[0]))
+
+
+def ahc_wide(engine, block, threshold=0.0, num_speakers=None, return_merges=False):
+    """Cluster ONE problem of n <= AHC_WIDE_MAX vectors whose square fp32 score block is `block`, on the whole device
+    (include/plda_hip.h, "corpus-scale clustering"): the contract of ahc() with one recording, for every n from 1 up.  Returns
+    (labels int32 [n], n_clusters int[, (merge_a, merge_b, merge_cost)])."""
+    block = np.asarray(block)
+    if block.ndim != 2 or block.shape[0] != block.shape[1]:
+        raise ValueError("the block must be a square 2-D array, got shape %r" % (block.shape,))
+    n = block.shape[0]
+    has_t, thr, minc = wide_args(n, threshold, num_speakers)
+    block = np.ascontiguousarray(block, np.float32)
+    labels, ncl, ma, mb, mc = _outputs(n, 1, return_merges)
+    N.check(engine._h, engine._lib.plda_ahc_wide_matrix(engine._h, _p(block), n, n, has_t, thr, minc, _p(labels), _p(ncl), _p(ma), _p(mb),
+                                                        _p(mc)))
+    return (labels, int(ncl[0]), (ma, mb, mc)) if return_merges else (labels, int(ncl[0]))
+
+
+def ahc_wide_vectors(engine, y, threshold=0.0, num_speakers=None, return_merges=False):
+    """The operand form: `y` [n, Dout] are already-transformed vectors (num_examples = 1); the block is scored on the device
+    exactly as score_matrix_dev would write it, clustered and dropped."""
+    y = np.asarray(y)
+    if y.ndim != 2:
+        raise ValueError("y must be [n, Dout], got %r" % (y.shape,))
+    has_t, thr, minc = wide_args(y.shape[0], threshold, num_speakers)
+    y = np.ascontiguousarray(y, np.float64)
+    dout, _ = engine.dims()
+    if y.shape[1] != dout:
+        raise ValueError("y has dimension %d, the model's output dimension is %d" % (y.shape[1], dout))
+    n = y.shape[0]
+    labels, ncl, ma, mb, mc = _outputs(n, 1, return_merges)
+    N.check(engine._h, engine._lib.plda_score_ahc_wide(engine._h, _p(y), n, has_t, thr, minc, _p(labels), _p(ncl), _p(ma), _p(mb), _p(mc)))
+    return (labels, int(ncl[0]), (ma, mb, mc)) if return_merges else (labels, int(ncl[0]))
+
+
+def keep_clusters(labels, min_cluster_size=2):
+    """The filter and renumber step of MPlda.adapt_clustered, pure NumPy: (rows int64 [m], the rows of clusters with at least
+    min_cluster_size members, ascending; new_labels int64 [m], those clusters renumbered 0 .. kept - 1 in their old order;
+    kept)."""
+    labels = np.asarray(labels)
+    if labels.ndim != 1 or labels.dtype.kind not in "iu" or (labels.size and labels.min() < 0):
+        raise ValueError("labels must be a 1-D array of integers >= 0")
+    if isinstance(min_cluster_size, bool) or int(min_cluster_size) != min_cluster_size or min_cluster_size < 1:
+        raise ValueError("min_cluster_size must be an integer >= 1, got %r" % (min_cluster_size,))
+    counts = np.bincount(labels) if labels.size else np.zeros(0, np.int64)
+    keep = counts >= int(min_cluster_size)
+    new_id = np.cumsum(keep) - 1
+    rows = np.nonzero(keep[labels])[0].astype(np.int64)
+    return rows, new_id[labels[rows]].astype(np.int64), int(keep.sum())
 
 
 # ------------------------------------------------------------------------------------------- spectral clustering

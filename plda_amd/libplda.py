@@ -589,6 +589,49 @@ class MPlda(object):
             return diarize.ahc_dense_pca(self, X, offsets, target_energy, threshold, num_speakers, return_merges)
         return diarize.ahc_vectors(self, self.transform_array(X, 1), offsets, threshold, num_speakers, return_merges)
 
+    # ----------------------------------------------------------------- corpus-scale clustering (csrc/ahc.hip, the wide class)
+    def cluster_corpus(self, x, threshold=0.0, num_speakers=None, return_merges=False):
+        """Cluster a whole unlabelled corpus into pseudo-speakers: x [N, Din] raw vectors, ONE problem of up to
+        diarize.AHC_WIDE_MAX = 32768 rows on the whole device (include/plda_hip.h, "corpus-scale clustering").  Every row is
+        transformed with num_examples = 1, all rows are scored against each other on the device and merged bottom-up (average
+        linkage, the contract of cluster() with one recording) while the best pair's average score is at least `threshold`
+        (None: no threshold) and more than `num_speakers` (None: 1) clusters are left.  Returns (labels int32 [N],
+        n_clusters[, (merge_a, merge_b, merge_cost)])."""
+        from . import diarize
+        if not isinstance(x, np.ndarray) or x.ndim != 2:
+            raise ValueError("Corpus vectors must be a 2-dimensional ndarray (nsamples, featdim)")
+        diarize.wide_args(x.shape[0], threshold, num_speakers)       # (before any device work)
+        X = self._rows(x, "Corpus vectors")
+        return diarize.ahc_wide_vectors(self, self.transform_array(X, 1), threshold, num_speakers, return_merges)
+
+    def adapt_clustered(self, x, threshold=0.0, num_speakers=None, alpha=0.5, alpha_mean=None, min_cluster_size=2, iters=10):
+        """Clustering-based domain adaptation (Garcia-Romero et al. 2014) in one call: cluster_corpus(x, threshold,
+        num_speakers) with this (out-of-domain) model; the rows of clusters smaller than `min_cluster_size` are dropped and the
+        rest renumbered (diarize.keep_clusters); an in-domain model is fitted on those pseudo-labels on a second handle of the
+        same device (`iters` EM iterations); blend(that model, alpha, alpha_mean).  Returns a
+        plda_amd.adaptation.ClusteredAdaptation(labels, n_clusters, rows_kept, clusters_kept).  ValueError, before the fit and
+        with the model untouched, if fewer than two clusters survive.  Clears the z-norm statistics and the stored calibration,
+        as blend does."""
+        from . import diarize
+        from .adaptation import ClusteredAdaptation
+        if isinstance(min_cluster_size, bool) or not isinstance(min_cluster_size, (int, np.integer)) or min_cluster_size < 1:
+            raise ValueError("min_cluster_size must be an integer >= 1, got %r" % (min_cluster_size,))
+        if isinstance(iters, bool) or not isinstance(iters, (int, np.integer)) or iters < 1:
+            raise ValueError("iters must be an integer >= 1, got %r" % (iters,))
+        for name, v in (("alpha", alpha), ("alpha_mean", alpha if alpha_mean is None else alpha_mean)):
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not 0.0 <= float(v) <= 1.0:
+                raise ValueError("%s must lie in [0, 1], got %r" % (name, v))
+        labels, ncl = self.cluster_corpus(x, threshold, num_speakers)
+        rows, new_labels, kept = diarize.keep_clusters(labels, min_cluster_size)
+        if kept < 2:
+            raise ValueError("adapt_clustered: %d of %d clusters have at least %d members; an in-domain model needs two"
+                             % (kept, ncl, int(min_cluster_size)))
+        X = self._rows(x, "Corpus vectors")
+        other = MPlda(self.device)
+        other.fit(np.ascontiguousarray(X[rows]), new_labels.astype(np.uint64), int(iters))
+        self.blend(other, alpha, alpha_mean)
+        return ClusteredAdaptation(labels, ncl, int(rows.shape[0]), kept)
+
     def score_dense(self, x, offsets, target_energy, return_info=False):
         """Every recording's segment pairs scored in the PCA subspace of its own segment vectors (Kaldi's
         ivector-plda-scoring-dense --target-energy; plda_amd/diarize.py: score_dense_pca): x [T, Din] raw segment vectors.
@@ -684,6 +727,21 @@ class MPlda(object):
             self._h, _vp(dX), _ptr(offsets), len(offsets) - 1, int(has_threshold), float(threshold),
             _ptr(min_clusters) if min_clusters is not None else None, _vp(dlabels), _vp(dn_clusters), _vp(dmerge_a), _vp(dmerge_b),
             _vp(dmerge_cost)))
+
+    def ahc_wide_matrix_dev(self, dscores, n, ld, has_threshold, threshold, min_clusters, dlabels, dn_clusters, dmerge_a=None,
+                            dmerge_b=None, dmerge_cost=None):
+        """Cluster ONE HBM-resident fp32 score block [n, n] at row stride ld on the whole device (raw device addresses;
+        plda_ahc_wide_matrix_dev); min_clusters is one int >= 1."""
+        self._ck(self._lib.plda_ahc_wide_matrix_dev(
+            self._h, _vp(dscores), int(n), int(ld), int(has_threshold), float(threshold), int(min_clusters), _vp(dlabels),
+            _vp(dn_clusters), _vp(dmerge_a), _vp(dmerge_b), _vp(dmerge_cost)))
+
+    def score_ahc_wide_dev(self, dX, n, has_threshold, threshold, min_clusters, dlabels, dn_clusters, dmerge_a=None, dmerge_b=None,
+                           dmerge_cost=None):
+        """The same on HBM-resident transformed vectors dX [n, Dout]: the block is scored and dropped."""
+        self._ck(self._lib.plda_score_ahc_wide_dev(
+            self._h, _vp(dX), int(n), int(has_threshold), float(threshold), int(min_clusters), _vp(dlabels), _vp(dn_clusters),
+            _vp(dmerge_a), _vp(dmerge_b), _vp(dmerge_cost)))
 
     def spectral_matrix_dev(self, dscores, block_off, offsets, p_table, max_speakers, num_speakers, max_iters, dlabels, dn_clusters,
                             dp_used=None, dk_gap=None, deig=None, dembed=None, ddeg2=None):
