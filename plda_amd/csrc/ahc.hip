@@ -6,17 +6,19 @@
 // bottom-up.  A recording is a chain of up to N - 1 DEPENDENT merges, each a few microseconds of work: one workgroup per
 // recording, many recordings in flight.
 //
-//   ahc_count_kernel    the non-finite off-diagonal scores of every recording of the call (one integer counter; a call that
-//                       meets one fails, and the kernels behind it write nothing)
+//   cluster_count_kernel<AhcRec>  (common.hpp) the non-finite off-diagonal scores of every recording of the call (one integer
+//                       counter; a call that meets one fails, and the kernels behind it write nothing)
 //   ahc_load_kernel     HBM class: the fp32 block symmetrised into an N x N fp64 matrix of sums in handle scratch
-//                       (c(i, j) = -((double)S[i, j] + (double)S[j, i]) / 2, both steps exact); the LDS class symmetrises
-//                       straight into LDS at the head of its merge kernel
+//                       (c(i, j) = -((double)S[i, j] + (double)S[j, i]) / 2, both steps exact; the tile body is ahc_load_tile,
+//                       which the wide class's ahcw_load_kernel shares); the LDS class symmetrises straight into LDS at the
+//                       head of its merge kernel
 //   ahc_merge_kernel    <HBM = false> the strict upper triangle of fp64 sums in LDS, N <= ahc_lds_max();
 //                       <HBM = true>  the full symmetric matrix in scratch (row a and row b of a merge are then contiguous).
 //                       Both keep the per-slot state in LDS: size, best partner b > a and its v, the member list of the slot.
 //   ahc_label_kernel    the final slot of every segment -> cluster numbers 0 .. k - 1 by ascending slot
 //   ahcw_*_kernel       the WIDE class (K28, at the end of the file): ONE problem of up to PLDA_AHC_WIDE_MAX vectors on the whole
-//                       device under the same contract -- the state in handle scratch, a step cut into three launches
+//                       device under the same contract -- the state in handle scratch, a step cut into three launches; its
+//                       count and load kernels are one-block wrappers of cluster_count_block and ahc_load_tile
 //
 // One step: (1) the global minimum (v, a) is a workgroup reduction over the row cache; (2) sum(a, x) += sum(b, x) for every
 // live x, and while x is in hand: a row x < a whose cached partner was a or b, or a row a < x < b whose partner was b, is
@@ -27,6 +29,7 @@
 // in which waves take rows, on the grid or on the grouping into launches.  (The file is built with -ffp-contract=off; it has
 // no fast-math and no reciprocal.)
 #include "common.hpp"
+#include "slab_walk.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -64,7 +67,6 @@ constexpr int AHC_LDS_MAX = ahc_lds_max_calc();
 static_assert(ahc_lds_bytes(AHC_LDS_MAX, false) <= AHC_LDS_BYTES, "the LDS class must fit one CU's LDS");
 static_assert(ahc_lds_bytes(AHC_MAX, true) <= AHC_LDS_BYTES, "the HBM class's slot state must fit one CU's LDS");
 
-__device__ __forceinline__ bool ahc_finite(float f) { return (__float_as_uint(f) & 0x7f800000u) != 0x7f800000u; }
 __device__ __forceinline__ double ahc_cost(float sij, float sji) { return -(((double)sij + (double)sji) / 2.0); }
 
 // lexicographic minimum of (v, i) over the wave, i < 0 = nothing; every lane ends with the result
@@ -77,39 +79,29 @@ __device__ __forceinline__ void ahc_wave_min(double &v, int &i) {
   }
 }
 
-// grid (pieces, recordings): the off-diagonal scores that are not finite, added to *bad
-__global__ __launch_bounds__(256) void ahc_count_kernel(const float *__restrict__ S, const AhcRec *__restrict__ tab,
-                                                        unsigned long long *bad) {
-  const AhcRec rc = tab[blockIdx.y];
-  const long long n = rc.n, total = n * n;
-  const float *__restrict__ blk = S + rc.boff;
-  unsigned cnt = 0;
-  for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long long)gridDim.x * 256) {
-    const long long i = e / n, j = e - i * n;
-    if (i != j && !ahc_finite(blk[e])) ++cnt;
+// 32 x 32 threads: tile (ti, tj) of M[i, j] = c(i, j) (M dense, n x n) from the block at S with row stride ld, the transposed
+// tile through LDS; diagonal 0.  Every thread of the workgroup must arrive.
+__device__ __forceinline__ void ahc_load_tile(const float *__restrict__ S, int n, long long ld, int ti, int tj, double *__restrict__ M) {
+  __shared__ float tile[32][33];
+  const int tx = threadIdx.x, ty = threadIdx.y;
+  {   // the mirror tile: rows tj * 32 .., columns ti * 32 ..
+    const int r = tj * 32 + ty, c = ti * 32 + tx;
+    tile[ty][tx] = (r < n && c < n) ? S[(long long)r * ld + c] : 0.f;
   }
-  if (cnt) atomicAdd(bad, (unsigned long long)cnt);   // rare: one integer atomic per lane that met one
+  __syncthreads();
+  const int i = ti * 32 + ty, j = tj * 32 + tx;
+  if (i < n && j < n) M[(long long)i * n + j] = i == j ? 0.0 : ahc_cost(S[(long long)i * ld + j], tile[tx][ty]);
 }
 
-// grid (tiles, recordings of the group), 32 x 32 threads: M[i, j] = c(i, j), the transposed tile through LDS; diagonal 0
+// grid (tiles, recordings of the group): the tiles of every recording's block, found through the launch table
 __global__ __launch_bounds__(1024) void ahc_load_kernel(const float *__restrict__ S, const AhcRec *__restrict__ tab,
                                                         double *__restrict__ scratch, const unsigned long long *__restrict__ bad) {
-  __shared__ float tile[32][33];
   if (*bad) return;
   const AhcRec rc = tab[blockIdx.y];
   const int n = rc.n, nt = (n + 31) / 32;
   if ((int)blockIdx.x >= nt * nt) return;
-  const int ti = blockIdx.x / nt, tj = blockIdx.x - ti * nt;
-  const float *__restrict__ blk = S + rc.boff;
-  double *__restrict__ M = scratch + rc.scr;
-  const int tx = threadIdx.x, ty = threadIdx.y;
-  {   // the mirror tile: rows tj * 32 .., columns ti * 32 ..
-    const int r = tj * 32 + ty, c = ti * 32 + tx;
-    tile[ty][tx] = (r < n && c < n) ? blk[(long long)r * n + c] : 0.f;
-  }
-  __syncthreads();
-  const int i = ti * 32 + ty, j = tj * 32 + tx;
-  if (i < n && j < n) M[(long long)i * n + j] = i == j ? 0.0 : ahc_cost(blk[(long long)i * n + j], tile[tx][ty]);
+  const int ti = blockIdx.x / nt;
+  ahc_load_tile(S + rc.boff, n, n, ti, blockIdx.x - ti * nt, scratch + rc.scr);
 }
 
 // the sums of a recording: the strict upper triangle in LDS, or the full symmetric matrix in HBM
@@ -322,16 +314,10 @@ template <bool HBM, int T> int ahc_merge_attr(plda_handle *h) {
   return PLDA_OK;
 }
 
-// the scratch of one launch of HBM-class recordings: the S-norm slab's rule (<= 2 GiB; PLDA_AHC_SCRATCH_BYTES at plda_create
-// for the tests), never less than one recording
-int64_t ahc_budget(const plda_handle *h) { return h->ahc_scratch_bytes > 0 ? h->ahc_scratch_bytes : (int64_t)2 << 30; }
-
-struct AhcOut { int32_t *labels, *n_clusters, *merge_a, *merge_b; double *merge_cost; };
-
 // Enqueues the clustering of recordings [r0, r1) whose blocks start at dscores + boff[r - r0].  `tables` keeps the host copy
 // of the launch table alive until the caller has synchronised.  h->ahc_stat[0] must have been zeroed by the caller.
 int ahc_enqueue(plda_handle *h, const float *dscores, const int64_t *boff, const int64_t *offsets, int64_t r0, int64_t r1,
-                int has_thr, double thr, const int32_t *minc, const AhcOut &out, std::vector<std::vector<AhcRec>> &tables) {
+                const AhcArgs &a, std::vector<std::vector<AhcRec>> &tables) {
   const int64_t cnt = r1 - r0;
   if (cnt <= 0) return PLDA_OK;
   static const int bucket_top[] = {64, 96, 128, 160, AHC_LDS_MAX};
@@ -344,7 +330,7 @@ int ahc_enqueue(plda_handle *h, const float *dscores, const int64_t *boff, const
   auto rec_of = [&](int64_t r) {
     AhcRec rc;
     rc.boff = boff[r - r0]; rc.off = offsets[r]; rc.scr = 0; rc.n = (int)(offsets[r + 1] - offsets[r]); rc.r = (int)r;
-    rc.minc = minc ? minc[r] : 1; rc.pad = 0;
+    rc.minc = a.minc ? a.minc[r] : 1; rc.pad = 0;
     return rc;
   };
   for (int bk = 0; bk < NB; ++bk) {           // LDS class: one launch per size bucket (the LDS of a launch is its largest N's)
@@ -356,7 +342,7 @@ int ahc_enqueue(plda_handle *h, const float *dscores, const int64_t *boff, const
     }
     if (L.count) launches.push_back(L);
   }
-  const int64_t budget = ahc_budget(h);
+  const int64_t budget = cluster_budget(h);
   int64_t scratch_need = 0;
   {                                           // HBM class: launches under the scratch budget
     Launch L{(int64_t)tab.size(), 0, 0, true, 0};
@@ -388,14 +374,7 @@ int ahc_enqueue(plda_handle *h, const float *dscores, const int64_t *boff, const
   PLDA_TRY((ahc_merge_attr<true, AHC_T_HBM>(h)));
 
   TraceScope ts(h, "ahc.count");
-  for (int64_t c0 = 0; c0 < cnt; c0 += 32768) {
-    const int64_t c = std::min<int64_t>(32768, cnt - c0);
-    int nmax = 0;
-    for (int64_t q = c0; q < c0 + c; ++q) nmax = std::max(nmax, tab[(size_t)q].n);
-    const int64_t pieces = std::max<int64_t>(1, std::min<int64_t>(ceil_div((int64_t)nmax * nmax, 256 * 16), 1024));
-    ahc_count_kernel<<<dim3((unsigned)pieces, (unsigned)c), 256, 0, h->stream>>>(dscores, dtab + c0, dbad);
-    PLDA_LAUNCH_CHECK(h);
-  }
+  PLDA_TRY(cluster_count_enqueue(h, dscores, tab.data(), cnt, dtab, dbad));
   ts.next("ahc.merge");
   for (const Launch &L : launches) {
     const size_t lds = (size_t)ahc_lds_bytes(L.nmax, L.hbm);
@@ -404,61 +383,29 @@ int ahc_enqueue(plda_handle *h, const float *dscores, const int64_t *boff, const
       ahc_load_kernel<<<dim3((unsigned)(nt * nt), (unsigned)L.count), dim3(32, 32), 0, h->stream>>>(dscores, dtab + L.first, scratch, dbad);
       PLDA_LAUNCH_CHECK(h);
       ahc_merge_kernel<true, AHC_T_HBM><<<(unsigned)L.count, AHC_T_HBM, lds, h->stream>>>(
-          dscores, dtab + L.first, scratch, dbad, has_thr, thr, dslot, out.n_clusters, out.merge_a, out.merge_b, out.merge_cost);
+          dscores, dtab + L.first, scratch, dbad, a.has_thr, a.thr, dslot, a.n_clusters, a.merge_a, a.merge_b, a.merge_cost);
     } else {
       ahc_merge_kernel<false, AHC_T_LDS><<<(unsigned)L.count, AHC_T_LDS, lds, h->stream>>>(
-          dscores, dtab + L.first, nullptr, dbad, has_thr, thr, dslot, out.n_clusters, out.merge_a, out.merge_b, out.merge_cost);
+          dscores, dtab + L.first, nullptr, dbad, a.has_thr, a.thr, dslot, a.n_clusters, a.merge_a, a.merge_b, a.merge_cost);
     }
     PLDA_LAUNCH_CHECK(h);
   }
   ts.next("ahc.label");
   for (int64_t c0 = 0; c0 < cnt; c0 += 65536) {      // (the table is in launch order; the labels do not care)
     const int64_t c = std::min<int64_t>(65536, cnt - c0);
-    ahc_label_kernel<<<(unsigned)c, 256, 0, h->stream>>>(dtab + c0, dslot, dbad, out.labels);
+    ahc_label_kernel<<<(unsigned)c, 256, 0, h->stream>>>(dtab + c0, dslot, dbad, a.labels);
     PLDA_LAUNCH_CHECK(h);
   }
   return PLDA_OK;
 }
 
-int ahc_check_args(plda_handle *h, const char *fn, const int64_t *offsets, int64_t R, int has_thr, double thr, const int32_t *minc,
-                   const AhcOut &out, const int64_t *block_off = nullptr, bool blocks = false) {
-  if (R < 1) return fail(h, PLDA_E_INVAL, "%s: R = %lld (must be >= 1)", fn, (long long)R);
-  if (R > (int64_t)0x7fffffff) return fail(h, PLDA_E_INVAL, "%s: R = %lld (at most 2^31 - 1)", fn, (long long)R);
-  if (!offsets) return fail(h, PLDA_E_INVAL, "%s: offsets is NULL", fn);
-  if (!out.labels) return fail(h, PLDA_E_INVAL, "%s: labels is NULL", fn);
-  if (!out.n_clusters) return fail(h, PLDA_E_INVAL, "%s: n_clusters is NULL", fn);
-  const int nm = (out.merge_a ? 1 : 0) + (out.merge_b ? 1 : 0) + (out.merge_cost ? 1 : 0);
+// the checks the batched and the wide class share, between each one's own first and last ones
+int ahc_check_outputs(plda_handle *h, const char *fn, const AhcArgs &a) {
+  if (!a.labels) return fail(h, PLDA_E_INVAL, "%s: labels is NULL", fn);
+  if (!a.n_clusters) return fail(h, PLDA_E_INVAL, "%s: n_clusters is NULL", fn);
+  const int nm = (a.merge_a ? 1 : 0) + (a.merge_b ? 1 : 0) + (a.merge_cost ? 1 : 0);
   if (nm != 0 && nm != 3) return fail(h, PLDA_E_INVAL, "%s: merge_a, merge_b and merge_cost must be given together or not at all", fn);
-  if (has_thr && std::isnan(thr)) return fail(h, PLDA_E_INVAL, "%s: threshold is NaN", fn);
-  if (offsets[0] != 0) return fail(h, PLDA_E_INVAL, "%s: offsets[0] = %lld (must be 0)", fn, (long long)offsets[0]);
-  for (int64_t r = 0; r < R; ++r) {
-    const int64_t n = offsets[r + 1] - offsets[r];
-    if (n < 1 || n > AHC_MAX)
-      return fail(h, PLDA_E_INVAL, "%s: recording %lld has %lld segments (must be 1 ... PLDA_AHC_MAX = %d; offsets must ascend)", fn,
-                  (long long)r, (long long)n, AHC_MAX);
-    if (minc && minc[r] < 1) return fail(h, PLDA_E_INVAL, "%s: min_clusters[%lld] = %d (must be >= 1)", fn, (long long)r, (int)minc[r]);
-  }
-  if (offsets[R] > (int64_t)0x7fffffff) return fail(h, PLDA_E_INVAL, "%s: %lld segments (at most 2^31 - 1)", fn, (long long)offsets[R]);
-  if (!blocks) return PLDA_OK;
-  if (!block_off) return fail(h, PLDA_E_INVAL, "%s: block_off is NULL", fn);
-  if (block_off[0] < 0) return fail(h, PLDA_E_INVAL, "%s: block_off[0] = %lld (must be >= 0)", fn, (long long)block_off[0]);
-  for (int64_t r = 0; r < R; ++r) {
-    const int64_t n = offsets[r + 1] - offsets[r];
-    if (block_off[r + 1] - block_off[r] < n * n)
-      return fail(h, PLDA_E_INVAL, "%s: block %lld holds %lld floats, its recording needs %lld x %lld", fn, (long long)r,
-                  (long long)(block_off[r + 1] - block_off[r]), (long long)n, (long long)n);
-  }
-  return PLDA_OK;
-}
-
-// reads the counter behind everything enqueued; the one synchronisation of a call
-int ahc_finish(plda_handle *h, const char *fn, int rc) {
-  unsigned long long bad = 0;
-  hipError_t e = hipMemcpyAsync(&bad, h->ahc_stat.p, 8, hipMemcpyDeviceToHost, h->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-  if (rc != PLDA_OK) return rc;
-  PLDA_HIP(h, e);
-  if (bad) return fail(h, PLDA_E_INVAL, "%s: %llu non-finite scores", fn, bad);
+  if (a.has_thr && std::isnan(a.thr)) return fail(h, PLDA_E_INVAL, "%s: threshold is NaN", fn);
   return PLDA_OK;
 }
 
@@ -507,28 +454,14 @@ int ahcw_piece_len(int64_t n, int P) { return (int)round_up(ceil_div(n, (int64_t
 
 // grid (pieces): the off-diagonal scores that are not finite, added to *bad
 __global__ __launch_bounds__(256) void ahcw_count_kernel(const float *__restrict__ S, int n, long long ld, unsigned long long *bad) {
-  const long long total = (long long)n * n;
-  unsigned cnt = 0;
-  for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long long)gridDim.x * 256) {
-    const long long i = e / n, j = e - i * n;
-    if (i != j && !ahc_finite(S[i * ld + j])) ++cnt;
-  }
-  if (cnt) atomicAdd(bad, (unsigned long long)cnt);
+  cluster_count_block(S, n, ld, bad);
 }
 
-// grid (tiles, tiles), 32 x 32 threads: sums[i, j] = c(i, j), the transposed tile through LDS; diagonal 0
+// grid (tiles, tiles), 32 x 32 threads: sums[i, j] = c(i, j)
 __global__ __launch_bounds__(1024) void ahcw_load_kernel(const float *__restrict__ S, int n, long long ld, double *__restrict__ sums,
                                                          const unsigned long long *__restrict__ bad) {
-  __shared__ float tile[32][33];
   if (*bad) return;
-  const int ti = blockIdx.y, tj = blockIdx.x, tx = threadIdx.x, ty = threadIdx.y;
-  {
-    const int r = tj * 32 + ty, c = ti * 32 + tx;
-    tile[ty][tx] = (r < n && c < n) ? S[(long long)r * ld + c] : 0.f;
-  }
-  __syncthreads();
-  const int i = ti * 32 + ty, j = tj * 32 + tx;
-  if (i < n && j < n) sums[(long long)i * n + j] = i == j ? 0.0 : ahc_cost(S[(long long)i * ld + j], tile[tx][ty]);
+  ahc_load_tile(S, n, ld, blockIdx.y, blockIdx.x, sums);
 }
 
 // grid over x: every slot alive and its own parent, every row on the list (the first rescan fills the whole row cache)
@@ -715,19 +648,6 @@ int ahcw_label_attr(plda_handle *h) {
   return PLDA_OK;
 }
 
-int ahcw_check_args(plda_handle *h, const char *fn, int64_t N, int64_t ld, int has_thr, double thr, int32_t minc, const AhcOut &out) {
-  if (N < 1 || N > AHCW_MAX)
-    return fail(h, PLDA_E_INVAL, "%s: N = %lld (must be 1 ... PLDA_AHC_WIDE_MAX = %d)", fn, (long long)N, AHCW_MAX);
-  if (ld < N) return fail(h, PLDA_E_INVAL, "%s: ld = %lld (must be >= N = %lld)", fn, (long long)ld, (long long)N);
-  if (!out.labels) return fail(h, PLDA_E_INVAL, "%s: labels is NULL", fn);
-  if (!out.n_clusters) return fail(h, PLDA_E_INVAL, "%s: n_clusters is NULL", fn);
-  const int nm = (out.merge_a ? 1 : 0) + (out.merge_b ? 1 : 0) + (out.merge_cost ? 1 : 0);
-  if (nm != 0 && nm != 3) return fail(h, PLDA_E_INVAL, "%s: merge_a, merge_b and merge_cost must be given together or not at all", fn);
-  if (has_thr && std::isnan(thr)) return fail(h, PLDA_E_INVAL, "%s: threshold is NaN", fn);
-  if (minc < 1) return fail(h, PLDA_E_INVAL, "%s: min_clusters = %d (must be >= 1)", fn, (int)minc);
-  return PLDA_OK;
-}
-
 // carves the state (the operand form: with its block array) and zeroes the counter of non-finite scores
 int ahcw_prepare(plda_handle *h, int64_t N, bool with_block, AhcwState &st) {
   const int P = ahcw_pieces(h, N);
@@ -738,11 +658,10 @@ int ahcw_prepare(plda_handle *h, int64_t N, bool with_block, AhcwState &st) {
 }
 
 // Enqueues the whole clustering of the block at dscores (row stride ld) on the state st; reads `done` between batches of
-// steps when a threshold may stop the run early.  The caller finishes with ahc_finish.
-int ahcw_enqueue(plda_handle *h, const float *dscores, int64_t N, int64_t ld, int has_thr, double thr, int32_t minc, const AhcwState &st,
-                 const AhcOut &out) {
+// steps when a threshold may stop the run early.  The caller finishes with cluster_counted.
+int ahcw_enqueue(plda_handle *h, const float *dscores, int64_t N, int64_t ld, const AhcArgs &a, const AhcwState &st) {
   const int n = (int)N, P = ahcw_pieces(h, N), L = ahcw_piece_len(N, P), batch = ahcw_batch(h);
-  const int stop_k = minc > 1 ? minc : 1;
+  const int stop_k = a.minc_wide > 1 ? a.minc_wide : 1;
   unsigned long long *dbad = h->ahc_stat.as<unsigned long long>();
   PLDA_TRY(ahcw_label_attr(h));
   TraceScope ts(h, "ahc.wide_load");
@@ -764,15 +683,15 @@ int ahcw_enqueue(plda_handle *h, const float *dscores, int64_t N, int64_t ld, in
   const dim3 gscan((unsigned)P, (unsigned)std::min(n, AHCW_SCAN_ROWS));
   int64_t left = N - stop_k;
   while (left > 0) {
-    const int64_t c = has_thr ? std::min<int64_t>(batch, left) : left;
+    const int64_t c = a.has_thr ? std::min<int64_t>(batch, left) : left;
     for (int64_t s = 0; s < c; ++s) {
-      ahcw_select_kernel<<<1, AHCW_T_SELECT, 0, h->stream>>>(n, st, stop_k, has_thr, -thr, out.merge_a, out.merge_b, out.merge_cost);
+      ahcw_select_kernel<<<1, AHCW_T_SELECT, 0, h->stream>>>(n, st, stop_k, a.has_thr, -a.thr, a.merge_a, a.merge_b, a.merge_cost);
       ahcw_update_kernel<<<gx, AHCW_T, 0, h->stream>>>(n, st);
       ahcw_rescan_kernel<<<gscan, AHCW_T, 0, h->stream>>>(n, st, P, L, 1);
       PLDA_LAUNCH_CHECK(h);
     }
     left -= c;
-    if (has_thr && left > 0) {
+    if (a.has_thr && left > 0) {
       int done = 0;
       PLDA_HIP(h, hipMemcpyAsync(&done, &st.ctl->done, 4, hipMemcpyDeviceToHost, h->stream));
       PLDA_HIP(h, hipStreamSynchronize(h->stream));
@@ -780,7 +699,7 @@ int ahcw_enqueue(plda_handle *h, const float *dscores, int64_t N, int64_t ld, in
     }
   }
   ts.next("ahc.wide_label");
-  ahcw_label_kernel<<<1, 1024, (size_t)n * 4, h->stream>>>(n, st, dbad, out.labels, out.n_clusters, out.merge_a, out.merge_b, out.merge_cost);
+  ahcw_label_kernel<<<1, 1024, (size_t)n * 4, h->stream>>>(n, st, dbad, a.labels, a.n_clusters, a.merge_a, a.merge_b, a.merge_cost);
   PLDA_LAUNCH_CHECK(h);
   return PLDA_OK;
 }
@@ -802,31 +721,29 @@ int ahc_wide_plan(plda_handle *h, int64_t N, int64_t *out) {
   return PLDA_OK;
 }
 
-int ahc_wide_validate(plda_handle *h, const char *fn, int64_t N, int64_t ld, int has_thr, double thr, int32_t minc, const int32_t *labels,
-                      const int32_t *n_clusters, const int32_t *merge_a, const int32_t *merge_b, const double *merge_cost) {
-  const AhcOut out{const_cast<int32_t *>(labels), const_cast<int32_t *>(n_clusters), const_cast<int32_t *>(merge_a),
-                   const_cast<int32_t *>(merge_b), const_cast<double *>(merge_cost)};
-  return ahcw_check_args(h, fn, N, ld, has_thr, thr, minc, out);
+int ahc_wide_validate(plda_handle *h, const char *fn, int64_t N, int64_t ld, const AhcArgs &a) {
+  if (N < 1 || N > AHCW_MAX)
+    return fail(h, PLDA_E_INVAL, "%s: N = %lld (must be 1 ... PLDA_AHC_WIDE_MAX = %d)", fn, (long long)N, AHCW_MAX);
+  if (ld < N) return fail(h, PLDA_E_INVAL, "%s: ld = %lld (must be >= N = %lld)", fn, (long long)ld, (long long)N);
+  PLDA_TRY(ahc_check_outputs(h, fn, a));
+  if (a.minc_wide < 1) return fail(h, PLDA_E_INVAL, "%s: min_clusters = %d (must be >= 1)", fn, (int)a.minc_wide);
+  return PLDA_OK;
 }
 
-int ahc_wide_matrix_device(plda_handle *h, const float *dscores, int64_t N, int64_t ld, int has_thr, double thr, int32_t minc,
-                           int32_t *dlabels, int32_t *dn_clusters, int32_t *dmerge_a, int32_t *dmerge_b, double *dmerge_cost) {
+int ahc_wide_matrix_device(plda_handle *h, const float *dscores, int64_t N, int64_t ld, const AhcArgs &a) {
   const char *fn = "ahc_wide_matrix";
-  const AhcOut out{dlabels, dn_clusters, dmerge_a, dmerge_b, dmerge_cost};
   if (!dscores) return fail(h, PLDA_E_INVAL, "%s: scores is NULL", fn);
-  PLDA_TRY(ahcw_check_args(h, fn, N, ld, has_thr, thr, minc, out));
+  PLDA_TRY(ahc_wide_validate(h, fn, N, ld, a));
   AhcwState st;
   PLDA_TRY(ahcw_prepare(h, N, false, st));
-  return ahc_finish(h, fn, ahcw_enqueue(h, dscores, N, ld, has_thr, thr, minc, st, out));
+  return cluster_counted(h, fn, h->ahc_stat.p, ahcw_enqueue(h, dscores, N, ld, a, st));
 }
 
-int score_ahc_wide_device(plda_handle *h, const double *dX, int64_t N, int has_thr, double thr, int32_t minc, int32_t *dlabels,
-                          int32_t *dn_clusters, int32_t *dmerge_a, int32_t *dmerge_b, double *dmerge_cost) {
+int score_ahc_wide_device(plda_handle *h, const double *dX, int64_t N, const AhcArgs &a) {
   const char *fn = "score_ahc_wide";
-  const AhcOut out{dlabels, dn_clusters, dmerge_a, dmerge_b, dmerge_cost};
   if (!can_score(h)) return fail(h, PLDA_E_NOT_FITTED, "%s: model not fitted", fn);
   if (!dX) return fail(h, PLDA_E_INVAL, "%s: X is NULL", fn);
-  PLDA_TRY(ahcw_check_args(h, fn, N, N, has_thr, thr, minc, out));
+  PLDA_TRY(ahc_wide_validate(h, fn, N, N, a));
   AhcwState st;
   PLDA_TRY(ahcw_prepare(h, N, true, st));
   h->prep_valid = false;           // (the block packs its own two sides)
@@ -835,16 +752,48 @@ int score_ahc_wide_device(plda_handle *h, const double *dX, int64_t N, int has_t
     TraceScope ts(h, "ahc.block_gemm", 2.0 * (double)h->Dout * (double)N * (double)N, 1);
     rc = score_matrix_device(h, dX, nullptr, 1, N, dX, N, nullptr, nullptr, st.block, N);
   }
-  if (rc == PLDA_OK) rc = ahcw_enqueue(h, st.block, N, N, has_thr, thr, minc, st, out);
-  return ahc_finish(h, fn, rc);
+  if (rc == PLDA_OK) rc = ahcw_enqueue(h, st.block, N, N, a, st);
+  return cluster_counted(h, fn, h->ahc_stat.p, rc);
 }
 
-int ahc_validate(plda_handle *h, const char *fn, const int64_t *block_off, bool blocks, const int64_t *offsets, int64_t R, int has_thr,
-                 double thr, const int32_t *minc, const int32_t *labels, const int32_t *n_clusters, const int32_t *merge_a,
-                 const int32_t *merge_b, const double *merge_cost) {
-  const AhcOut out{const_cast<int32_t *>(labels), const_cast<int32_t *>(n_clusters), const_cast<int32_t *>(merge_a),
-                   const_cast<int32_t *>(merge_b), const_cast<double *>(merge_cost)};
-  return ahc_check_args(h, fn, offsets, R, has_thr, thr, minc, out, block_off, blocks);
+int ahc_validate(plda_handle *h, const char *fn, const int64_t *block_off, bool blocks, const int64_t *offsets, int64_t R,
+                 const AhcArgs &a) {
+  if (R < 1) return fail(h, PLDA_E_INVAL, "%s: R = %lld (must be >= 1)", fn, (long long)R);
+  if (R > (int64_t)0x7fffffff) return fail(h, PLDA_E_INVAL, "%s: R = %lld (at most 2^31 - 1)", fn, (long long)R);
+  if (!offsets) return fail(h, PLDA_E_INVAL, "%s: offsets is NULL", fn);
+  PLDA_TRY(ahc_check_outputs(h, fn, a));
+  PLDA_TRY(check_recordings(h, fn, offsets, R, AHC_MAX, "PLDA_AHC_MAX", [&](int64_t r, int64_t) {
+    if (a.minc && a.minc[r] < 1)
+      return fail(h, PLDA_E_INVAL, "%s: min_clusters[%lld] = %d (must be >= 1)", fn, (long long)r, (int)a.minc[r]);
+    return (int)PLDA_OK;
+  }));
+  return blocks ? check_block_off(h, fn, block_off, offsets, R) : PLDA_OK;
+}
+
+int cluster_counted(plda_handle *h, const char *fn, const void *dbad, int rc) {
+  unsigned long long bad = 0;
+  hipError_t e = hipMemcpyAsync(&bad, dbad, 8, hipMemcpyDeviceToHost, h->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+  if (rc != PLDA_OK) return rc;
+  PLDA_HIP(h, e);
+  if (bad) return fail(h, PLDA_E_INVAL, "%s: %llu non-finite scores", fn, bad);
+  return PLDA_OK;
+}
+
+int score_blocks_device(plda_handle *h, const char *span, const double *dX, const int64_t *offsets, int64_t r0, int64_t r1,
+                        const int64_t *boff, float *slab) {
+  const int D = h->Dout;
+  TraceScope ts(h, span, 0.0, 1);
+  double flop = 0.0;
+  int rc = PLDA_OK;
+  for (int64_t r = r0; r < r1 && rc == PLDA_OK; ++r) {
+    const int64_t n = offsets[r + 1] - offsets[r];
+    const double *x = dX + offsets[r] * D;
+    rc = score_matrix_device(h, x, nullptr, 1, n, x, n, nullptr, nullptr, slab + boff[r - r0], n);
+    flop += 2.0 * (double)D * (double)n * (double)n;
+  }
+  if (ts.idx >= 0) h->trace_spans[ts.idx].work = flop;
+  return rc;
 }
 
 int ahc_plan(plda_handle *h, int64_t N, int32_t *out) {
@@ -857,72 +806,36 @@ int ahc_plan(plda_handle *h, int64_t N, int32_t *out) {
   return PLDA_OK;
 }
 
-int ahc_matrix_device(plda_handle *h, const float *dscores, const int64_t *block_off, const int64_t *offsets, int64_t R, int has_thr,
-                      double thr, const int32_t *minc, int32_t *dlabels, int32_t *dn_clusters, int32_t *dmerge_a, int32_t *dmerge_b,
-                      double *dmerge_cost) {
+int ahc_matrix_device(plda_handle *h, const float *dscores, const int64_t *block_off, const int64_t *offsets, int64_t R,
+                      const AhcArgs &a) {
   const char *fn = "ahc_matrix";
-  const AhcOut out{dlabels, dn_clusters, dmerge_a, dmerge_b, dmerge_cost};
   if (!dscores) return fail(h, PLDA_E_INVAL, "%s: scores is NULL", fn);
-  PLDA_TRY(ahc_check_args(h, fn, offsets, R, has_thr, thr, minc, out, block_off, true));
+  PLDA_TRY(ahc_validate(h, fn, block_off, true, offsets, R, a));
   PLDA_HIP(h, h->ahc_stat.reserve(8));
   PLDA_HIP(h, hipMemsetAsync(h->ahc_stat.p, 0, 8, h->stream));
   std::vector<std::vector<AhcRec>> tables;
-  const int rc = ahc_enqueue(h, dscores, block_off, offsets, 0, R, has_thr, thr, minc, out, tables);
-  return ahc_finish(h, fn, rc);
+  const int rc = ahc_enqueue(h, dscores, block_off, offsets, 0, R, a, tables);
+  return cluster_counted(h, fn, h->ahc_stat.p, rc);
 }
 
-int score_ahc_device(plda_handle *h, const double *dX, const int64_t *offsets, int64_t R, int has_thr, double thr,
-                     const int32_t *minc, int32_t *dlabels, int32_t *dn_clusters, int32_t *dmerge_a, int32_t *dmerge_b,
-                     double *dmerge_cost) {
+int score_ahc_device(plda_handle *h, const double *dX, const int64_t *offsets, int64_t R, const AhcArgs &a) {
   const char *fn = "score_ahc";
-  const AhcOut out{dlabels, dn_clusters, dmerge_a, dmerge_b, dmerge_cost};
   if (!can_score(h)) return fail(h, PLDA_E_NOT_FITTED, "%s: model not fitted", fn);
   if (!dX) return fail(h, PLDA_E_INVAL, "%s: X is NULL", fn);
-  PLDA_TRY(ahc_check_args(h, fn, offsets, R, has_thr, thr, minc, out));
-  const int D = h->Dout;
-  // the score blocks of consecutive recordings, each at a 256-byte boundary of the slab, as many as the budget holds
-  auto padded = [](int64_t n) { return round_up(n * n, 64); };
-  const int64_t budget = ahc_budget(h) / 4;
-  int64_t slab_floats = 0;
-  for (int64_t r = 0, cur = 0; r < R; ++r) {
-    const int64_t f = padded(offsets[r + 1] - offsets[r]);
-    if (cur && cur + f > budget) cur = 0;
-    cur += f;
-    slab_floats = std::max(slab_floats, cur);
-  }
-  PLDA_HIP(h, h->sn_slab.reserve((size_t)slab_floats * 4));
+  PLDA_TRY(ahc_validate(h, fn, nullptr, false, offsets, R, a));
+  SlabWalk walk(offsets, R, cluster_budget(h) / 4);
+  PLDA_HIP(h, h->sn_slab.reserve((size_t)walk.largest * 4));
   float *slab = h->sn_slab.as<float>();
   h->prep_valid = false;           // (every block packs its own two sides)
   PLDA_HIP(h, h->ahc_stat.reserve(8));
   PLDA_HIP(h, hipMemsetAsync(h->ahc_stat.p, 0, 8, h->stream));
   std::vector<std::vector<AhcRec>> tables;
-  std::vector<int64_t> boff;
   int rc = PLDA_OK;
-  for (int64_t r0 = 0; r0 < R && rc == PLDA_OK;) {
-    boff.clear();
-    int64_t r1 = r0, cur = 0;
-    while (r1 < R) {
-      const int64_t f = padded(offsets[r1 + 1] - offsets[r1]);
-      if (cur && cur + f > budget) break;
-      boff.push_back(cur);
-      cur += f;
-      ++r1;
-    }
-    {
-      TraceScope ts(h, "ahc.block_gemm", 0.0, 1);
-      double flop = 0.0;
-      for (int64_t r = r0; r < r1 && rc == PLDA_OK; ++r) {
-        const int64_t n = offsets[r + 1] - offsets[r];
-        const double *x = dX + offsets[r] * D;
-        rc = score_matrix_device(h, x, nullptr, 1, n, x, n, nullptr, nullptr, slab + boff[(size_t)(r - r0)], n);
-        flop += 2.0 * (double)D * (double)n * (double)n;
-      }
-      if (ts.idx >= 0) h->trace_spans[ts.idx].work = flop;
-    }
-    if (rc == PLDA_OK) rc = ahc_enqueue(h, slab, boff.data(), offsets, r0, r1, has_thr, thr, minc, out, tables);
-    r0 = r1;
+  while (rc == PLDA_OK && walk.next()) {      // every slab scored, counted and clustered in one pass
+    rc = score_blocks_device(h, "ahc.block_gemm", dX, offsets, walk.r0, walk.r1, walk.boff.data(), slab);
+    if (rc == PLDA_OK) rc = ahc_enqueue(h, slab, walk.boff.data(), offsets, walk.r0, walk.r1, a, tables);
   }
-  return ahc_finish(h, fn, rc);
+  return cluster_counted(h, fn, h->ahc_stat.p, rc);
 }
 
 }  // namespace plda

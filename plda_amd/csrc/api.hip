@@ -377,6 +377,36 @@ int read_environment(plda_handle *h) {
 
 }  // namespace
 
+// The argument record and the staging of the AHC host forms (plda_*ahc*), and the block range every *_matrix host form stages.
+namespace {
+// minc: the batched classes' min_clusters per recording; minc_wide: the wide class's one (each form passes the other as NULL / 1)
+AhcArgs ahc_args(int32_t has_threshold, double threshold, const int32_t *minc, int32_t minc_wide, int32_t *labels, int32_t *n_clusters,
+                 int32_t *merge_a, int32_t *merge_b, double *merge_cost) {
+  AhcArgs a;
+  a.has_thr = has_threshold; a.thr = threshold; a.minc = minc; a.minc_wide = minc_wide;
+  a.labels = labels; a.n_clusters = n_clusters; a.merge_a = merge_a; a.merge_b = merge_b; a.merge_cost = merge_cost;
+  return a;
+}
+// the device outputs of a host form: labels_len labels, merges_len entries of the merge record (nullable as a group) and one
+// cluster count per recording, i.e. labels_len - merges_len of them (T, T - R, R; the wide class: N, N - 1, 1)
+int ahc_stage_outputs(Staged &st, const AhcArgs &host, size_t labels_len, size_t merges_len, AhcArgs *dev) {
+  *dev = host;
+  PLDA_TRY(st.out(host.labels, labels_len, &dev->labels));
+  PLDA_TRY(st.out(host.n_clusters, labels_len - merges_len, &dev->n_clusters));
+  PLDA_TRY(st.out(host.merge_a, merges_len, &dev->merge_a));
+  PLDA_TRY(st.out(host.merge_b, merges_len, &dev->merge_b));
+  PLDA_TRY(st.out(host.merge_cost, merges_len, &dev->merge_cost));
+  return PLDA_OK;
+}
+// the blocks' offsets relative to the first one: a host form stages the floats [block_off[0], block_off[R]) of the caller's
+// array, rel[R] of them, and the device form addresses that copy
+std::vector<int64_t> block_rel(const int64_t *block_off, int64_t R) {
+  std::vector<int64_t> rel((size_t)R + 1);
+  for (int64_t r = 0; r <= R; ++r) rel[(size_t)r] = block_off[r] - block_off[0];
+  return rel;
+}
+}  // namespace
+
 extern "C" {
 
 int plda_abi_version(void) { return 2; }
@@ -2123,8 +2153,8 @@ int plda_ahc_matrix_dev(plda_handle *h, const float *dscores, const int64_t *blo
                         int32_t has_threshold, double threshold, const int32_t *min_clusters, int32_t *dlabels,
                         int32_t *dn_clusters, int32_t *dmerge_a, int32_t *dmerge_b, double *dmerge_cost) {
   return device_entry(h, "plda_ahc_matrix_dev", [&] {
-    return ahc_matrix_device(h, dscores, block_off, offsets, R, has_threshold, threshold, min_clusters, dlabels, dn_clusters, dmerge_a,
-                             dmerge_b, dmerge_cost);
+    return ahc_matrix_device(h, dscores, block_off, offsets, R,
+                             ahc_args(has_threshold, threshold, min_clusters, 1, dlabels, dn_clusters, dmerge_a, dmerge_b, dmerge_cost));
   });
 }
 
@@ -2132,24 +2162,18 @@ int plda_ahc_matrix(plda_handle *h, const float *scores, const int64_t *block_of
                     int32_t has_threshold, double threshold, const int32_t *min_clusters, int32_t *labels, int32_t *n_clusters,
                     int32_t *merge_a, int32_t *merge_b, double *merge_cost) {
   return entry(h, "plda_ahc_matrix", [&]() -> int {
+    const AhcArgs host = ahc_args(has_threshold, threshold, min_clusters, 1, labels, n_clusters, merge_a, merge_b, merge_cost);
     if (!scores) return fail(h, PLDA_E_INVAL, "ahc_matrix: scores is NULL");
-    PLDA_TRY(ahc_validate(h, "ahc_matrix", block_off, true, offsets, R, has_threshold, threshold, min_clusters, labels, n_clusters,
-                          merge_a, merge_b, merge_cost));
+    PLDA_TRY(ahc_validate(h, "ahc_matrix", block_off, true, offsets, R, host));
     PLDA_TRY(set_device(h));
-    const int64_t T = offsets[R], first = block_off[0], floats = block_off[R] - first;
+    const size_t T = (size_t)offsets[R];
+    const std::vector<int64_t> rel = block_rel(block_off, R);
     Staged st(h);
     const float *dS;
-    int32_t *dL, *dK, *dA, *dB;
-    double *dC;
-    PLDA_TRY(st.in(scores + first, (size_t)floats, &dS));
-    std::vector<int64_t> rel((size_t)R + 1);
-    for (int64_t r = 0; r <= R; ++r) rel[(size_t)r] = block_off[r] - first;
-    PLDA_TRY(st.out(labels, (size_t)T, &dL));
-    PLDA_TRY(st.out(n_clusters, (size_t)R, &dK));
-    PLDA_TRY(st.out(merge_a, (size_t)(T - R), &dA));
-    PLDA_TRY(st.out(merge_b, (size_t)(T - R), &dB));
-    PLDA_TRY(st.out(merge_cost, (size_t)(T - R), &dC));
-    return st.finish(ahc_matrix_device(h, dS, rel.data(), offsets, R, has_threshold, threshold, min_clusters, dL, dK, dA, dB, dC));
+    AhcArgs dev;
+    PLDA_TRY(st.in(scores + block_off[0], (size_t)rel[(size_t)R], &dS));
+    PLDA_TRY(ahc_stage_outputs(st, host, T, T - (size_t)R, &dev));
+    return st.finish(ahc_matrix_device(h, dS, rel.data(), offsets, R, dev));
   });
 }
 
@@ -2157,8 +2181,8 @@ int plda_score_ahc_dev(plda_handle *h, const double *dX, const int64_t *offsets,
                        double threshold, const int32_t *min_clusters, int32_t *dlabels, int32_t *dn_clusters,
                        int32_t *dmerge_a, int32_t *dmerge_b, double *dmerge_cost) {
   return device_entry(h, "plda_score_ahc_dev", [&] {
-    return score_ahc_device(h, dX, offsets, R, has_threshold, threshold, min_clusters, dlabels, dn_clusters, dmerge_a, dmerge_b,
-                            dmerge_cost);
+    return score_ahc_device(h, dX, offsets, R,
+                            ahc_args(has_threshold, threshold, min_clusters, 1, dlabels, dn_clusters, dmerge_a, dmerge_b, dmerge_cost));
   });
 }
 
@@ -2166,23 +2190,18 @@ int plda_score_ahc(plda_handle *h, const double *X, const int64_t *offsets, int6
                    const int32_t *min_clusters, int32_t *labels, int32_t *n_clusters, int32_t *merge_a, int32_t *merge_b,
                    double *merge_cost) {
   return entry(h, "plda_score_ahc", [&]() -> int {
+    const AhcArgs host = ahc_args(has_threshold, threshold, min_clusters, 1, labels, n_clusters, merge_a, merge_b, merge_cost);
     if (!can_score(h)) return fail(h, PLDA_E_NOT_FITTED, "score_ahc: model not fitted");
     if (!X) return fail(h, PLDA_E_INVAL, "score_ahc: X is NULL");
-    PLDA_TRY(ahc_validate(h, "score_ahc", nullptr, false, offsets, R, has_threshold, threshold, min_clusters, labels, n_clusters,
-                          merge_a, merge_b, merge_cost));
+    PLDA_TRY(ahc_validate(h, "score_ahc", nullptr, false, offsets, R, host));
     PLDA_TRY(set_device(h));
-    const int64_t T = offsets[R];
+    const size_t T = (size_t)offsets[R];
     Staged st(h);
     const double *dX;
-    int32_t *dL, *dK, *dA, *dB;
-    double *dC;
-    PLDA_TRY(st.in(X, (size_t)T * h->Dout, &dX));
-    PLDA_TRY(st.out(labels, (size_t)T, &dL));
-    PLDA_TRY(st.out(n_clusters, (size_t)R, &dK));
-    PLDA_TRY(st.out(merge_a, (size_t)(T - R), &dA));
-    PLDA_TRY(st.out(merge_b, (size_t)(T - R), &dB));
-    PLDA_TRY(st.out(merge_cost, (size_t)(T - R), &dC));
-    return st.finish(score_ahc_device(h, dX, offsets, R, has_threshold, threshold, min_clusters, dL, dK, dA, dB, dC));
+    AhcArgs dev;
+    PLDA_TRY(st.in(X, T * h->Dout, &dX));
+    PLDA_TRY(ahc_stage_outputs(st, host, T, T - (size_t)R, &dev));
+    return st.finish(score_ahc_device(h, dX, offsets, R, dev));
   });
 }
 
@@ -2195,8 +2214,9 @@ int plda_ahc_wide_matrix_dev(plda_handle *h, const float *dscores, int64_t N, in
                              int32_t min_clusters, int32_t *dlabels, int32_t *dn_clusters, int32_t *dmerge_a, int32_t *dmerge_b,
                              double *dmerge_cost) {
   return device_entry(h, "plda_ahc_wide_matrix_dev", [&] {
-    return ahc_wide_matrix_device(h, dscores, N, ld, has_threshold, threshold, min_clusters, dlabels, dn_clusters, dmerge_a, dmerge_b,
-                                  dmerge_cost);
+    return ahc_wide_matrix_device(h, dscores, N, ld,
+                                  ahc_args(has_threshold, threshold, nullptr, min_clusters, dlabels, dn_clusters, dmerge_a, dmerge_b,
+                                           dmerge_cost));
   });
 }
 
@@ -2204,21 +2224,16 @@ int plda_ahc_wide_matrix(plda_handle *h, const float *scores, int64_t N, int64_t
                          int32_t min_clusters, int32_t *labels, int32_t *n_clusters, int32_t *merge_a, int32_t *merge_b,
                          double *merge_cost) {
   return entry(h, "plda_ahc_wide_matrix", [&]() -> int {
+    const AhcArgs host = ahc_args(has_threshold, threshold, nullptr, min_clusters, labels, n_clusters, merge_a, merge_b, merge_cost);
     if (!scores) return fail(h, PLDA_E_INVAL, "ahc_wide_matrix: scores is NULL");
-    PLDA_TRY(ahc_wide_validate(h, "ahc_wide_matrix", N, ld, has_threshold, threshold, min_clusters, labels, n_clusters, merge_a, merge_b,
-                               merge_cost));
+    PLDA_TRY(ahc_wide_validate(h, "ahc_wide_matrix", N, ld, host));
     PLDA_TRY(set_device(h));
     Staged st(h);
     const float *dS;
-    int32_t *dL, *dK, *dA, *dB;
-    double *dC;
+    AhcArgs dev;
     PLDA_TRY(st.in(scores, (size_t)((N - 1) * ld + N), &dS));
-    PLDA_TRY(st.out(labels, (size_t)N, &dL));
-    PLDA_TRY(st.out(n_clusters, (size_t)1, &dK));
-    PLDA_TRY(st.out(merge_a, (size_t)(N - 1), &dA));
-    PLDA_TRY(st.out(merge_b, (size_t)(N - 1), &dB));
-    PLDA_TRY(st.out(merge_cost, (size_t)(N - 1), &dC));
-    return st.finish(ahc_wide_matrix_device(h, dS, N, ld, has_threshold, threshold, min_clusters, dL, dK, dA, dB, dC));
+    PLDA_TRY(ahc_stage_outputs(st, host, (size_t)N, (size_t)(N - 1), &dev));
+    return st.finish(ahc_wide_matrix_device(h, dS, N, ld, dev));
   });
 }
 
@@ -2226,29 +2241,26 @@ int plda_score_ahc_wide_dev(plda_handle *h, const double *dX, int64_t N, int32_t
                             int32_t min_clusters, int32_t *dlabels, int32_t *dn_clusters, int32_t *dmerge_a, int32_t *dmerge_b,
                             double *dmerge_cost) {
   return device_entry(h, "plda_score_ahc_wide_dev", [&] {
-    return score_ahc_wide_device(h, dX, N, has_threshold, threshold, min_clusters, dlabels, dn_clusters, dmerge_a, dmerge_b, dmerge_cost);
+    return score_ahc_wide_device(h, dX, N,
+                                 ahc_args(has_threshold, threshold, nullptr, min_clusters, dlabels, dn_clusters, dmerge_a, dmerge_b,
+                                          dmerge_cost));
   });
 }
 
 int plda_score_ahc_wide(plda_handle *h, const double *X, int64_t N, int32_t has_threshold, double threshold, int32_t min_clusters,
                         int32_t *labels, int32_t *n_clusters, int32_t *merge_a, int32_t *merge_b, double *merge_cost) {
   return entry(h, "plda_score_ahc_wide", [&]() -> int {
+    const AhcArgs host = ahc_args(has_threshold, threshold, nullptr, min_clusters, labels, n_clusters, merge_a, merge_b, merge_cost);
     if (!can_score(h)) return fail(h, PLDA_E_NOT_FITTED, "score_ahc_wide: model not fitted");
     if (!X) return fail(h, PLDA_E_INVAL, "score_ahc_wide: X is NULL");
-    PLDA_TRY(ahc_wide_validate(h, "score_ahc_wide", N, N, has_threshold, threshold, min_clusters, labels, n_clusters, merge_a, merge_b,
-                               merge_cost));
+    PLDA_TRY(ahc_wide_validate(h, "score_ahc_wide", N, N, host));
     PLDA_TRY(set_device(h));
     Staged st(h);
     const double *dX;
-    int32_t *dL, *dK, *dA, *dB;
-    double *dC;
+    AhcArgs dev;
     PLDA_TRY(st.in(X, (size_t)N * h->Dout, &dX));
-    PLDA_TRY(st.out(labels, (size_t)N, &dL));
-    PLDA_TRY(st.out(n_clusters, (size_t)1, &dK));
-    PLDA_TRY(st.out(merge_a, (size_t)(N - 1), &dA));
-    PLDA_TRY(st.out(merge_b, (size_t)(N - 1), &dB));
-    PLDA_TRY(st.out(merge_cost, (size_t)(N - 1), &dC));
-    return st.finish(score_ahc_wide_device(h, dX, N, has_threshold, threshold, min_clusters, dL, dK, dA, dB, dC));
+    PLDA_TRY(ahc_stage_outputs(st, host, (size_t)N, (size_t)(N - 1), &dev));
+    return st.finish(score_ahc_wide_device(h, dX, N, dev));
   });
 }
 
@@ -2302,12 +2314,10 @@ int plda_spectral_matrix(plda_handle *h, const float *scores, const int64_t *blo
     if (!scores) return fail(h, PLDA_E_INVAL, "spectral_matrix: scores is NULL");
     PLDA_TRY(spectral_validate(h, "spectral_matrix", block_off, true, host));
     PLDA_TRY(set_device(h));
-    const int64_t first = block_off[0], floats = block_off[R] - first;
+    const std::vector<int64_t> rel = block_rel(block_off, R);
     Staged st(h);
     const float *dS;
-    PLDA_TRY(st.in(scores + first, (size_t)floats, &dS));
-    std::vector<int64_t> rel((size_t)R + 1);
-    for (int64_t r = 0; r <= R; ++r) rel[(size_t)r] = block_off[r] - first;
+    PLDA_TRY(st.in(scores + block_off[0], (size_t)rel[(size_t)R], &dS));
     SpectralArgs dev;
     PLDA_TRY(spectral_stage_outputs(st, host, &dev));
     return st.finish(spectral_matrix_device(h, dS, rel.data(), dev));
@@ -2361,7 +2371,9 @@ int plda_score_dense_pca(plda_handle *h, const double *X, const int64_t *offsets
     if (!X) return fail(h, PLDA_E_INVAL, "score_dense_pca: X is NULL");
     if (!scores) return fail(h, PLDA_E_INVAL, "score_dense_pca: scores is NULL");
     PLDA_TRY(set_device(h));
-    const int64_t T = offsets[R], first = block_off[0], floats = block_off[R] - first;
+    const int64_t T = offsets[R], first = block_off[0];
+    const std::vector<int64_t> rel = block_rel(block_off, R);
+    const int64_t floats = rel[(size_t)R];
     Staged st(h);
     const double *dX;
     Tmp dS, dD, dE;
@@ -2369,9 +2381,7 @@ int plda_score_dense_pca(plda_handle *h, const double *X, const int64_t *offsets
     PLDA_HIP(h, dS.alloc((size_t)floats * 4));
     if (dims) PLDA_HIP(h, dD.alloc((size_t)R * 4));
     if (eig) PLDA_HIP(h, dE.alloc((size_t)T * 8));
-    std::vector<int64_t> rel((size_t)R + 1);
     bool packed = true;                        // every block exactly N_r^2 floats: one copy back; otherwise block by block
-    for (int64_t r = 0; r <= R; ++r) rel[(size_t)r] = block_off[r] - first;
     for (int64_t r = 0; r < R; ++r) {
       const int64_t n = offsets[r + 1] - offsets[r];
       packed = packed && rel[(size_t)r + 1] - rel[(size_t)r] == n * n;
@@ -2399,8 +2409,9 @@ int plda_score_dense_pca_ahc_dev(plda_handle *h, const double *dX, const int64_t
                                  int32_t has_threshold, double threshold, const int32_t *min_clusters, int32_t *dlabels,
                                  int32_t *dn_clusters, int32_t *dmerge_a, int32_t *dmerge_b, double *dmerge_cost) {
   return device_entry(h, "plda_score_dense_pca_ahc_dev", [&] {
-    return score_dense_pca_ahc_device(h, dX, offsets, R, target_energy, has_threshold, threshold, min_clusters, dlabels, dn_clusters,
-                                      dmerge_a, dmerge_b, dmerge_cost);
+    return score_dense_pca_ahc_device(h, dX, offsets, R, target_energy,
+                                      ahc_args(has_threshold, threshold, min_clusters, 1, dlabels, dn_clusters, dmerge_a, dmerge_b,
+                                               dmerge_cost));
   });
 }
 
@@ -2408,24 +2419,18 @@ int plda_score_dense_pca_ahc(plda_handle *h, const double *X, const int64_t *off
                              int32_t has_threshold, double threshold, const int32_t *min_clusters, int32_t *labels,
                              int32_t *n_clusters, int32_t *merge_a, int32_t *merge_b, double *merge_cost) {
   return entry(h, "plda_score_dense_pca_ahc", [&]() -> int {
+    const AhcArgs host = ahc_args(has_threshold, threshold, min_clusters, 1, labels, n_clusters, merge_a, merge_b, merge_cost);
     PLDA_TRY(dense_pca_validate(h, "score_dense_pca_ahc", offsets, R, target_energy, nullptr, false));
     if (!X) return fail(h, PLDA_E_INVAL, "score_dense_pca_ahc: X is NULL");
-    PLDA_TRY(ahc_validate(h, "score_dense_pca_ahc", nullptr, false, offsets, R, has_threshold, threshold, min_clusters, labels,
-                          n_clusters, merge_a, merge_b, merge_cost));
+    PLDA_TRY(ahc_validate(h, "score_dense_pca_ahc", nullptr, false, offsets, R, host));
     PLDA_TRY(set_device(h));
-    const int64_t T = offsets[R];
+    const size_t T = (size_t)offsets[R];
     Staged st(h);
     const double *dX;
-    int32_t *dL, *dK, *dA, *dB;
-    double *dC;
-    PLDA_TRY(st.in(X, (size_t)T * h->Din, &dX));
-    PLDA_TRY(st.out(labels, (size_t)T, &dL));
-    PLDA_TRY(st.out(n_clusters, (size_t)R, &dK));
-    PLDA_TRY(st.out(merge_a, (size_t)(T - R), &dA));
-    PLDA_TRY(st.out(merge_b, (size_t)(T - R), &dB));
-    PLDA_TRY(st.out(merge_cost, (size_t)(T - R), &dC));
-    return st.finish(score_dense_pca_ahc_device(h, dX, offsets, R, target_energy, has_threshold, threshold, min_clusters, dL, dK, dA, dB,
-                                                dC));
+    AhcArgs dev;
+    PLDA_TRY(st.in(X, T * h->Din, &dX));
+    PLDA_TRY(ahc_stage_outputs(st, host, T, T - (size_t)R, &dev));
+    return st.finish(score_dense_pca_ahc_device(h, dX, offsets, R, target_energy, dev));
   });
 }
 

@@ -4,6 +4,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <mutex>
@@ -549,26 +550,79 @@ int embed_fit_validate(plda_handle *h, int dtype, int64_t N, int Din, bool has_l
 int embed_fit_device(plda_handle *h, const void *dX, int dtype, int64_t N, int Din, const uint64_t *dlabels, int64_t K, int kind,
                      int Dout, double len_in, double len_out, double *eig);   // eig: HOST, nullable
 
+// ---- the clustering family (ahc.hip, spectral.hip, dense_pca.hip, vbx.hip, der.hip): what its files share ----
+// The recordings check of every validator, behind the validator's own head (its R, NULL and scalar checks): offsets[0], every
+// recording's size in 1 ... max_n (printed as `max_name`), each(r, n) for the checks that belong inside the same walk, the total.
+template <typename F>
+int check_recordings(plda_handle *h, const char *fn, const int64_t *offsets, int64_t R, int max_n, const char *max_name, F &&each) {
+  if (offsets[0] != 0) return fail(h, PLDA_E_INVAL, "%s: offsets[0] = %lld (must be 0)", fn, (long long)offsets[0]);
+  for (int64_t r = 0; r < R; ++r) {
+    const int64_t n = offsets[r + 1] - offsets[r];
+    if (n < 1 || n > max_n)
+      return fail(h, PLDA_E_INVAL, "%s: recording %lld has %lld segments (must be 1 ... %s = %d; offsets must ascend)", fn, (long long)r,
+                  (long long)n, max_name, max_n);
+    PLDA_TRY(each(r, n));
+  }
+  if (offsets[R] > (int64_t)0x7fffffff) return fail(h, PLDA_E_INVAL, "%s: %lld segments (at most 2^31 - 1)", fn, (long long)offsets[R]);
+  return PLDA_OK;
+}
+inline int check_recordings(plda_handle *h, const char *fn, const int64_t *offsets, int64_t R, int max_n, const char *max_name) {
+  return check_recordings(h, fn, offsets, R, max_n, max_name, [](int64_t, int64_t) { return PLDA_OK; });
+}
+// behind it, in the forms that take score blocks: block r holds at least N_r x N_r floats
+inline int check_block_off(plda_handle *h, const char *fn, const int64_t *block_off, const int64_t *offsets, int64_t R) {
+  if (!block_off) return fail(h, PLDA_E_INVAL, "%s: block_off is NULL", fn);
+  if (block_off[0] < 0) return fail(h, PLDA_E_INVAL, "%s: block_off[0] = %lld (must be >= 0)", fn, (long long)block_off[0]);
+  for (int64_t r = 0; r < R; ++r) {
+    const int64_t n = offsets[r + 1] - offsets[r];
+    if (block_off[r + 1] - block_off[r] < n * n)
+      return fail(h, PLDA_E_INVAL, "%s: block %lld holds %lld floats, its recording needs %lld x %lld", fn, (long long)r,
+                  (long long)(block_off[r + 1] - block_off[r]), (long long)n, (long long)n);
+  }
+  return PLDA_OK;
+}
+// the scratch of one launch or group of the AHC, spectral and dense-PCA back-ends, and four times the floats of one score slab
+// of their operand forms (slab_walk.hpp): the S-norm slab's rule (<= 2 GiB; PLDA_AHC_SCRATCH_BYTES at plda_create for the
+// tests), never less than one recording
+inline int64_t cluster_budget(const plda_handle *h) { return h->ahc_scratch_bytes > 0 ? h->ahc_scratch_bytes : (int64_t)2 << 30; }
+// ahc.hip: scores the blocks of recordings [r0, r1) of dX into the slab at boff[r - r0] (a SlabWalk's run), under one trace
+// span `span` (a string literal) that carries their flop count
+int score_blocks_device(plda_handle *h, const char *span, const double *dX, const int64_t *offsets, int64_t r0, int64_t r1,
+                        const int64_t *boff, float *slab);
+// ahc.hip: reads the 8-byte counter of non-finite scores behind everything enqueued, and synchronises even when rc has already
+// failed (the host tables of the launches must outlive the stream); rc if it failed, else the count's error, else PLDA_OK
+int cluster_counted(plda_handle *h, const char *fn, const void *dbad, int rc = PLDA_OK);
+
 // ---- ahc.hip (speaker clustering: batched average-linkage AHC on score blocks; block_off / offsets / minc are HOST arrays) ----
+// The arguments every plda_*ahc* call shares.  Outputs: labels and n_clusters are required, the merge record is nullable as a group.
+struct AhcArgs {
+  int has_thr = 0; double thr = 0.0;
+  const int32_t *minc = nullptr;      // the batched classes: min_clusters per recording (HOST, nullable)
+  int32_t minc_wide = 1;              // the wide class: its one min_clusters
+  int32_t *labels = nullptr, *n_clusters = nullptr, *merge_a = nullptr, *merge_b = nullptr;
+  double *merge_cost = nullptr;
+  // the record of the recordings from r0 on, whose first segment is seg0, numbered from 0 (their merge record starts at seg0 - r0)
+  AhcArgs from(int64_t r0, int64_t seg0) const {
+    AhcArgs s = *this;
+    const int64_t m0 = seg0 - r0;
+    s.minc = minc ? minc + r0 : nullptr; s.labels = labels + seg0; s.n_clusters = n_clusters + r0;
+    s.merge_a = merge_a ? merge_a + m0 : nullptr; s.merge_b = merge_b ? merge_b + m0 : nullptr;
+    s.merge_cost = merge_cost ? merge_cost + m0 : nullptr;
+    return s;
+  }
+};
 int ahc_plan(plda_handle *h, int64_t N, int32_t *out);
 // the argument check of every form (blocks: block_off is checked against the recordings' sizes); pointers are only compared with NULL
-int ahc_validate(plda_handle *h, const char *fn, const int64_t *block_off, bool blocks, const int64_t *offsets, int64_t R, int has_thr,
-                 double thr, const int32_t *minc, const int32_t *labels, const int32_t *n_clusters, const int32_t *merge_a,
-                 const int32_t *merge_b, const double *merge_cost);
-int ahc_matrix_device(plda_handle *h, const float *dscores, const int64_t *block_off, const int64_t *offsets, int64_t R, int has_thr,
-                      double thr, const int32_t *minc, int32_t *dlabels, int32_t *dn_clusters, int32_t *dmerge_a, int32_t *dmerge_b,
-                      double *dmerge_cost);
-int score_ahc_device(plda_handle *h, const double *dX, const int64_t *offsets, int64_t R, int has_thr, double thr,
-                     const int32_t *minc, int32_t *dlabels, int32_t *dn_clusters, int32_t *dmerge_a, int32_t *dmerge_b,
-                     double *dmerge_cost);
+int ahc_validate(plda_handle *h, const char *fn, const int64_t *block_off, bool blocks, const int64_t *offsets, int64_t R,
+                 const AhcArgs &a);
+int ahc_matrix_device(plda_handle *h, const float *dscores, const int64_t *block_off, const int64_t *offsets, int64_t R,
+                      const AhcArgs &a);
+int score_ahc_device(plda_handle *h, const double *dX, const int64_t *offsets, int64_t R, const AhcArgs &a);
 // the wide class: one problem of N <= PLDA_AHC_WIDE_MAX vectors on the whole device (K28)
 int ahc_wide_plan(plda_handle *h, int64_t N, int64_t *out);
-int ahc_wide_validate(plda_handle *h, const char *fn, int64_t N, int64_t ld, int has_thr, double thr, int32_t minc, const int32_t *labels,
-                      const int32_t *n_clusters, const int32_t *merge_a, const int32_t *merge_b, const double *merge_cost);
-int ahc_wide_matrix_device(plda_handle *h, const float *dscores, int64_t N, int64_t ld, int has_thr, double thr, int32_t minc,
-                           int32_t *dlabels, int32_t *dn_clusters, int32_t *dmerge_a, int32_t *dmerge_b, double *dmerge_cost);
-int score_ahc_wide_device(plda_handle *h, const double *dX, int64_t N, int has_thr, double thr, int32_t minc, int32_t *dlabels,
-                          int32_t *dn_clusters, int32_t *dmerge_a, int32_t *dmerge_b, double *dmerge_cost);
+int ahc_wide_validate(plda_handle *h, const char *fn, int64_t N, int64_t ld, const AhcArgs &a);
+int ahc_wide_matrix_device(plda_handle *h, const float *dscores, int64_t N, int64_t ld, const AhcArgs &a);
+int score_ahc_wide_device(plda_handle *h, const double *dX, int64_t N, const AhcArgs &a);
 
 // ---- spectral.hip (spectral clustering with auto-tuned pruning; offsets / block_off / p_table / num_spk are HOST arrays) ----
 // The arguments every plda_spectral* / plda_score_spectral* call shares.  Outputs: labels and n_clusters are required, the rest nullable.
@@ -593,9 +647,7 @@ int dense_pca_validate(plda_handle *h, const char *fn, const int64_t *offsets, i
                        bool blocks);
 int score_dense_pca_device(plda_handle *h, const double *dX, const int64_t *offsets, int64_t R, double target, float *dscores,
                            const int64_t *block_off, int32_t *ddims, double *deig);
-int score_dense_pca_ahc_device(plda_handle *h, const double *dX, const int64_t *offsets, int64_t R, double target, int has_thr,
-                               double thr, const int32_t *minc, int32_t *dlabels, int32_t *dn_clusters, int32_t *dmerge_a,
-                               int32_t *dmerge_b, double *dmerge_cost);
+int score_dense_pca_ahc_device(plda_handle *h, const double *dX, const int64_t *offsets, int64_t R, double target, const AhcArgs &a);
 
 // ---- der.hip (diarisation error rate: optimal speaker mapping, threshold sweep; offsets / thresholds / minc are HOST arrays) ----
 int der_plan(plda_handle *h, int64_t Sr, int64_t Sh, int32_t *out);
@@ -782,6 +834,39 @@ __device__ __forceinline__ double wave_sum_f64(double x) {
   x += dpp_f64<0x141>(x);   // row_half_mirror
   x += dpp_f64<0x140>(x);   // row_mirror
   return (readlane_f64(x, 0) + readlane_f64(x, 16)) + (readlane_f64(x, 32) + readlane_f64(x, 48));
+}
+
+// ---- the clustering family: the count of non-finite scores (ahc.hip, spectral.hip) ----
+__device__ __forceinline__ bool cluster_finite(float f) { return (__float_as_uint(f) & 0x7f800000u) != 0x7f800000u; }
+// the off-diagonal elements of the n x n block at blk (row stride ld) that are not finite, added to *bad; the workgroups
+// blockIdx.x of 256 threads share the block
+__device__ __forceinline__ void cluster_count_block(const float *__restrict__ blk, long long n, long long ld, unsigned long long *bad) {
+  const long long total = n * n;
+  unsigned cnt = 0;
+  for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long long)gridDim.x * 256) {
+    const long long i = e / n, j = e - i * n;
+    if (i != j && !cluster_finite(blk[i * ld + j])) ++cnt;
+  }
+  if (cnt) atomicAdd(bad, (unsigned long long)cnt);   // rare: one integer atomic per lane that met one
+}
+// grid (pieces, recordings): the blocks of a launch table (Rec: boff, n), each dense
+template <typename Rec>
+__global__ __launch_bounds__(256) void cluster_count_kernel(const float *__restrict__ S, const Rec *__restrict__ tab, unsigned long long *bad) {
+  const long long n = tab[blockIdx.y].n;
+  cluster_count_block(S + tab[blockIdx.y].boff, n, n, bad);
+}
+// enqueues the count over the cnt recordings of a table (tab: its host copy, dtab: the uploaded one), 32768 recordings a launch
+template <typename Rec>
+int cluster_count_enqueue(plda_handle *h, const float *dscores, const Rec *tab, int64_t cnt, const Rec *dtab, unsigned long long *dbad) {
+  for (int64_t c0 = 0; c0 < cnt; c0 += 32768) {
+    const int64_t c = std::min<int64_t>(32768, cnt - c0);
+    int nmax = 0;
+    for (int64_t q = c0; q < c0 + c; ++q) nmax = std::max(nmax, tab[q].n);
+    const int64_t pieces = std::max<int64_t>(1, std::min<int64_t>(ceil_div((int64_t)nmax * nmax, 256 * 16), 1024));
+    cluster_count_kernel<Rec><<<dim3((unsigned)pieces, (unsigned)c), 256, 0, h->stream>>>(dscores, dtab + c0, dbad);
+    PLDA_LAUNCH_CHECK(h);
+  }
+  return PLDA_OK;
 }
 #endif
 

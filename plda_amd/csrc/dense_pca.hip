@@ -18,6 +18,7 @@
 // and every sum runs over ascending indices in one thread: a recording's block does not depend on the batch it is in, on the
 // grouping into launches or on the run.  Phases communicate through LDS or through scratch behind __syncthreads() only.
 #include "common.hpp"
+#include "slab_walk.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -438,8 +439,6 @@ template <bool HBM, int T> int dp_attr(plda_handle *h, int bytes) {
   return PLDA_OK;
 }
 
-int64_t dp_budget(const plda_handle *h) { return h->ahc_scratch_bytes > 0 ? h->ahc_scratch_bytes : (int64_t)2 << 30; }
-
 int64_t dp_rec_bytes(int64_t n, int64_t D, int64_t m, bool hbm) {
   Layout size;
   DpRec rc;
@@ -476,7 +475,7 @@ int dp_enqueue(plda_handle *h, const double *dX, const int64_t *offsets, int64_t
                const int64_t *boff, int32_t *ddims, double *deig, const double *W, const double *B,
                std::vector<std::vector<DpRec>> &tables) {
   const int D = h->Din;
-  const int64_t budget = dp_budget(h);
+  const int64_t budget = cluster_budget(h);
   struct Group { int64_t first, n_lds, n_hbm; int m_lds; };
   std::vector<Group> groups;
   tables.emplace_back();
@@ -573,24 +572,8 @@ int dense_pca_validate(plda_handle *h, const char *fn, const int64_t *offsets, i
   if (!(target > 0.0 && target < 1.0)) return fail(h, PLDA_E_INVAL, "%s: target_energy = %g (must lie in (0, 1))", fn, target);
   if (R < 1 || R > (int64_t)0x7fffffff) return fail(h, PLDA_E_INVAL, "%s: R = %lld (must be 1 ... 2^31 - 1)", fn, (long long)R);
   if (!offsets) return fail(h, PLDA_E_INVAL, "%s: offsets is NULL", fn);
-  if (offsets[0] != 0) return fail(h, PLDA_E_INVAL, "%s: offsets[0] = %lld (must be 0)", fn, (long long)offsets[0]);
-  for (int64_t r = 0; r < R; ++r) {
-    const int64_t n = offsets[r + 1] - offsets[r];
-    if (n < 1 || n > PLDA_AHC_MAX)
-      return fail(h, PLDA_E_INVAL, "%s: recording %lld has %lld segments (must be 1 ... PLDA_AHC_MAX = %d; offsets must ascend)", fn,
-                  (long long)r, (long long)n, PLDA_AHC_MAX);
-  }
-  if (offsets[R] > (int64_t)0x7fffffff) return fail(h, PLDA_E_INVAL, "%s: %lld segments (at most 2^31 - 1)", fn, (long long)offsets[R]);
-  if (!blocks) return PLDA_OK;
-  if (!block_off) return fail(h, PLDA_E_INVAL, "%s: block_off is NULL", fn);
-  if (block_off[0] < 0) return fail(h, PLDA_E_INVAL, "%s: block_off[0] = %lld (must be >= 0)", fn, (long long)block_off[0]);
-  for (int64_t r = 0; r < R; ++r) {
-    const int64_t n = offsets[r + 1] - offsets[r];
-    if (block_off[r + 1] - block_off[r] < n * n)
-      return fail(h, PLDA_E_INVAL, "%s: block %lld holds %lld floats, its recording needs %lld x %lld", fn, (long long)r,
-                  (long long)(block_off[r + 1] - block_off[r]), (long long)n, (long long)n);
-  }
-  return PLDA_OK;
+  PLDA_TRY(check_recordings(h, fn, offsets, R, PLDA_AHC_MAX, "PLDA_AHC_MAX"));
+  return blocks ? check_block_off(h, fn, block_off, offsets, R) : PLDA_OK;
 }
 
 int dense_pca_plan(plda_handle *h, int64_t N, int32_t D, int32_t *out) {
@@ -620,52 +603,28 @@ int score_dense_pca_device(plda_handle *h, const double *dX, const int64_t *offs
   return dp_finish(h, fn, rc);
 }
 
-int score_dense_pca_ahc_device(plda_handle *h, const double *dX, const int64_t *offsets, int64_t R, double target, int has_thr,
-                               double thr, const int32_t *minc, int32_t *dlabels, int32_t *dn_clusters, int32_t *dmerge_a,
-                               int32_t *dmerge_b, double *dmerge_cost) {
+int score_dense_pca_ahc_device(plda_handle *h, const double *dX, const int64_t *offsets, int64_t R, double target, const AhcArgs &a) {
   const char *fn = "score_dense_pca_ahc";
   PLDA_TRY(dense_pca_validate(h, fn, offsets, R, target, nullptr, false));
   if (!dX) return fail(h, PLDA_E_INVAL, "%s: X is NULL", fn);
-  PLDA_TRY(ahc_validate(h, fn, nullptr, false, offsets, R, has_thr, thr, minc, dlabels, dn_clusters, dmerge_a, dmerge_b, dmerge_cost));
+  PLDA_TRY(ahc_validate(h, fn, nullptr, false, offsets, R, a));
   const double *W = nullptr, *B = nullptr;
   PLDA_TRY(dp_model(h, fn, &W, &B));
-  // the score blocks of consecutive recordings, each at a 256-byte boundary of the S-norm slab, as many as the budget holds
-  // (plda_score_ahc's rule); every slab is scored, clustered by the AHC's own entry and dropped
-  auto padded = [](int64_t n) { return round_up(n * n, 64); };
-  const int64_t budget = dp_budget(h) / 4;
-  int64_t slab_floats = 0;
-  for (int64_t r = 0, cur = 0; r < R; ++r) {
-    const int64_t f = padded(offsets[r + 1] - offsets[r]);
-    if (cur && cur + f > budget) cur = 0;
-    cur += f;
-    slab_floats = std::max(slab_floats, cur);
-  }
-  PLDA_HIP(h, h->sn_slab.reserve((size_t)slab_floats * 4));
+  // every slab of the walk is scored, clustered by the AHC's own matrix form (its blocks at the walk's boff, closing entry
+  // included) and dropped
+  SlabWalk walk(offsets, R, cluster_budget(h) / 4);
+  PLDA_HIP(h, h->sn_slab.reserve((size_t)walk.largest * 4));
   float *slab = h->sn_slab.as<float>();
   PLDA_TRY(dp_begin(h, dX, offsets[R]));
   std::vector<std::vector<DpRec>> tables;
-  std::vector<int64_t> boff, rel;
-  for (int64_t r0 = 0; r0 < R;) {
-    boff.clear();
+  std::vector<int64_t> rel;
+  while (walk.next()) {
+    const int64_t r0 = walk.r0, r1 = walk.r1;
     rel.clear();
-    int64_t r1 = r0, cur = 0;
-    while (r1 < R) {
-      const int64_t f = padded(offsets[r1 + 1] - offsets[r1]);
-      if (cur && cur + f > budget) break;
-      boff.push_back(cur);
-      rel.push_back(offsets[r1] - offsets[r0]);
-      cur += f;
-      ++r1;
-    }
-    boff.push_back(cur);
-    rel.push_back(offsets[r1] - offsets[r0]);
-    const int rc = dp_enqueue(h, dX, offsets, r0, r1, target, slab, boff.data(), nullptr, nullptr, W, B, tables);
+    for (int64_t r = r0; r <= r1; ++r) rel.push_back(offsets[r] - offsets[r0]);
+    const int rc = dp_enqueue(h, dX, offsets, r0, r1, target, slab, walk.boff.data(), nullptr, nullptr, W, B, tables);
     PLDA_TRY(dp_finish(h, fn, rc));           // (a failed recording leaves its block unwritten: nothing is clustered)
-    const int64_t moff = offsets[r0] - r0;    // the slab's first entry of the merge record
-    PLDA_TRY(ahc_matrix_device(h, slab, boff.data(), rel.data(), r1 - r0, has_thr, thr, minc ? minc + r0 : nullptr,
-                               dlabels + offsets[r0], dn_clusters + r0, dmerge_a ? dmerge_a + moff : nullptr,
-                               dmerge_b ? dmerge_b + moff : nullptr, dmerge_cost ? dmerge_cost + moff : nullptr));
-    r0 = r1;
+    PLDA_TRY(ahc_matrix_device(h, slab, walk.boff.data(), rel.data(), r1 - r0, a.from(r0, offsets[r0])));
   }
   return PLDA_OK;
 }

@@ -589,15 +589,7 @@ int der_check_offsets(plda_handle *h, const char *fn, const int64_t *offsets, in
   if (R < 1) return fail(h, PLDA_E_INVAL, "%s: R = %lld (must be >= 1)", fn, (long long)R);
   if (R > (int64_t)0x7fffffff) return fail(h, PLDA_E_INVAL, "%s: R = %lld (at most 2^31 - 1)", fn, (long long)R);
   if (!offsets) return fail(h, PLDA_E_INVAL, "%s: offsets is NULL", fn);
-  if (offsets[0] != 0) return fail(h, PLDA_E_INVAL, "%s: offsets[0] = %lld (must be 0)", fn, (long long)offsets[0]);
-  for (int64_t r = 0; r < R; ++r) {
-    const int64_t n = offsets[r + 1] - offsets[r];
-    if (n < 1 || n > DER_MAX_HYP)
-      return fail(h, PLDA_E_INVAL, "%s: recording %lld has %lld segments (must be 1 ... PLDA_AHC_MAX = %d; offsets must ascend)", fn,
-                  (long long)r, (long long)n, DER_MAX_HYP);
-  }
-  if (offsets[R] > (int64_t)0x7fffffff) return fail(h, PLDA_E_INVAL, "%s: %lld segments (at most 2^31 - 1)", fn, (long long)offsets[R]);
-  return PLDA_OK;
+  return check_recordings(h, fn, offsets, R, DER_MAX_HYP, "PLDA_AHC_MAX");
 }
 
 // Enqueues the solves of `items` (sr, sh, n, m, off, out, r filled in; w, scr and the launch order are this function's);

@@ -2,8 +2,8 @@
 // affinity graph with the pruning value chosen by the normalised-maximum-eigengap rule (NME-SC, Park et al. 2020), batched
 // over recordings (the contract is in include/plda_hip.h, the host model in tests/spectral_model.py).
 //
-//   spectral_count_kernel      the non-finite off-diagonal scores of every recording of the call (one integer counter; a call
-//                              that meets one fails before anything else is enqueued)
+//   cluster_count_kernel<SpecRec>  (common.hpp) the non-finite off-diagonal scores of every recording of the call (one integer
+//                              counter; a call that meets one fails before anything else is enqueued)
 //   spectral_sym_kernel        c(i, j) = ((double)S[i, j] + (double)S[j, i]) / 2 of one recording, once for all its pruning values
 //   spectral_select_kernel<E>  one wave per row, the row's order keys in registers (E per lane): the p-th largest key by
 //                              bisection over the 64 key bits (topn.hip's idea), then the j-ascending cut among the keys equal
@@ -19,6 +19,7 @@
 // Everything up to L is exact; steps 3, 4 and 6 of the contract are single fp64 operations in a fixed order (the file is built
 // with -ffp-contract=off; no fast-math), so a recording's outputs depend on its block, its pruning values and N alone.
 #include "common.hpp"
+#include "slab_walk.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -47,26 +48,11 @@ struct SpecRec {
 // the best pruning value of a recording so far
 struct SpecState { double r; int p_eff, k_gap, have, pad; };
 
-__device__ __forceinline__ bool spec_finite(float f) { return (__float_as_uint(f) & 0x7f800000u) != 0x7f800000u; }
 // the order key of a similarity: larger c <=> larger key, -0.0 == +0.0; a finite c never has key 0
 __device__ __forceinline__ unsigned long long spec_key(double c) {
   unsigned long long b = (unsigned long long)__double_as_longlong(c);
   if ((b << 1) == 0) b = 0;
   return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-
-// grid (pieces, recordings): the off-diagonal scores that are not finite, added to *bad
-__global__ __launch_bounds__(256) void spectral_count_kernel(const float *__restrict__ S, const SpecRec *__restrict__ tab,
-                                                             unsigned long long *bad) {
-  const SpecRec rc = tab[blockIdx.y];
-  const long long n = rc.n, total = n * n;
-  const float *__restrict__ blk = S + rc.boff;
-  unsigned cnt = 0;
-  for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long long)gridDim.x * 256) {
-    const long long i = e / n, j = e - i * n;
-    if (i != j && !spec_finite(blk[e])) ++cnt;
-  }
-  if (cnt) atomicAdd(bad, (unsigned long long)cnt);
 }
 
 __global__ __launch_bounds__(256) void spectral_sym_kernel(const float *__restrict__ blk, int n, double *__restrict__ Cm) {
@@ -341,8 +327,6 @@ int spectral_kmeans_attr(plda_handle *h) {
   return PLDA_OK;
 }
 
-// the AHC's budget: the kept columns of one group of recordings and the score slab of the operand form
-int64_t spec_budget(const plda_handle *h) { return h->ahc_scratch_bytes > 0 ? h->ahc_scratch_bytes : (int64_t)2 << 30; }
 int spec_class(int n) { int e = 1; while (e * 64 < n) e *= 2; return e; }     // keys per lane of the selection kernel
 
 struct SpecGroup { int64_t first, count, segs; int nmax; };   // table entries [first, first + count), their segments, largest N
@@ -361,7 +345,7 @@ struct SpecWork {
   }
 };
 
-// the table of recordings [r0, r1) (blocks at boff[r - r0]) in groups under the budget, uploaded; `tables` keeps the host copy
+// the table of recordings [r0, r1) (blocks at boff[r - r0]) in groups whose kept columns fit cluster_budget, uploaded; `tables` keeps the host copy
 // alive until the caller has synchronised
 int spectral_table(plda_handle *h, const int64_t *boff, const SpectralArgs &a, int64_t r0, int64_t r1,
                    std::vector<std::vector<SpecRec>> &tables, std::vector<SpecGroup> &groups, const SpecRec **dtab,
@@ -370,7 +354,7 @@ int spectral_table(plda_handle *h, const int64_t *boff, const SpectralArgs &a, i
   std::vector<SpecRec> &tab = tables.back();
   tab.reserve((size_t)(r1 - r0));
   groups.clear();
-  const int64_t budget = spec_budget(h);
+  const int64_t budget = cluster_budget(h);
   SpecGroup g{0, 0, 0, 0};
   int64_t bytes = 0;
   for (int64_t r = r0; r < r1; ++r) {
@@ -395,28 +379,6 @@ int spectral_table(plda_handle *h, const int64_t *boff, const SpectralArgs &a, i
   PLDA_HIP(h, hipMemcpyAsync(dt, tab.data(), cnt * sizeof(SpecRec), hipMemcpyHostToDevice, h->stream));
   *dtab = dt;
   *dbad = db;
-  return PLDA_OK;
-}
-
-int spectral_count(plda_handle *h, const float *dscores, const std::vector<SpecRec> &tab, const SpecRec *dtab, unsigned long long *dbad) {
-  const int64_t cnt = (int64_t)tab.size();
-  for (int64_t c0 = 0; c0 < cnt; c0 += 32768) {
-    const int64_t c = std::min<int64_t>(32768, cnt - c0);
-    int nmax = 0;
-    for (int64_t q = c0; q < c0 + c; ++q) nmax = std::max(nmax, tab[(size_t)q].n);
-    const int64_t pieces = std::max<int64_t>(1, std::min<int64_t>(ceil_div((int64_t)nmax * nmax, 256 * 16), 1024));
-    spectral_count_kernel<<<dim3((unsigned)pieces, (unsigned)c), 256, 0, h->stream>>>(dscores, dtab + c0, dbad);
-    PLDA_LAUNCH_CHECK(h);
-  }
-  return PLDA_OK;
-}
-
-// reads the counter: nothing of the clustering is enqueued before it is known to be zero
-int spectral_counted(plda_handle *h, const char *fn, const unsigned long long *dbad) {
-  unsigned long long bad = 0;
-  PLDA_HIP(h, hipMemcpyAsync(&bad, dbad, 8, hipMemcpyDeviceToHost, h->stream));
-  PLDA_HIP(h, hipStreamSynchronize(h->stream));
-  if (bad) return fail(h, PLDA_E_INVAL, "%s: %llu non-finite scores", fn, bad);
   return PLDA_OK;
 }
 
@@ -513,30 +475,16 @@ int spectral_validate(plda_handle *h, const char *fn, const int64_t *block_off, 
   if (a.max_spk < 1 || a.max_spk > SPEC_MAX_SPK)
     return fail(h, PLDA_E_INVAL, "%s: max_speakers = %d (must be 1 ... PLDA_SPECTRAL_MAX_SPK = %d)", fn, a.max_spk, SPEC_MAX_SPK);
   if (a.max_iters < 1 || a.max_iters > 1000) return fail(h, PLDA_E_INVAL, "%s: max_iters = %d (must be 1 ... 1000)", fn, a.max_iters);
-  if (a.offsets[0] != 0) return fail(h, PLDA_E_INVAL, "%s: offsets[0] = %lld (must be 0)", fn, (long long)a.offsets[0]);
-  for (int64_t r = 0; r < R; ++r) {
-    const int64_t n = a.offsets[r + 1] - a.offsets[r];
-    if (n < 1 || n > SPEC_MAX)
-      return fail(h, PLDA_E_INVAL, "%s: recording %lld has %lld segments (must be 1 ... PLDA_SPECTRAL_MAX = %d; offsets must ascend)", fn,
-                  (long long)r, (long long)n, SPEC_MAX);
+  PLDA_TRY(check_recordings(h, fn, a.offsets, R, SPEC_MAX, "PLDA_SPECTRAL_MAX", [&](int64_t r, int64_t) {
     for (int q = 0; q < a.P; ++q)
       if (a.p_table[r * a.P + q] < 1)
         return fail(h, PLDA_E_INVAL, "%s: p_table[%lld, %d] = %d (must be >= 1)", fn, (long long)r, q, (int)a.p_table[r * a.P + q]);
     if (a.num_spk && (a.num_spk[r] < 0 || a.num_spk[r] > a.max_spk))
       return fail(h, PLDA_E_INVAL, "%s: num_speakers[%lld] = %d (must be 0 ... max_speakers = %d)", fn, (long long)r, (int)a.num_spk[r],
                   a.max_spk);
-  }
-  if (a.offsets[R] > (int64_t)0x7fffffff) return fail(h, PLDA_E_INVAL, "%s: %lld segments (at most 2^31 - 1)", fn, (long long)a.offsets[R]);
-  if (!blocks) return PLDA_OK;
-  if (!block_off) return fail(h, PLDA_E_INVAL, "%s: block_off is NULL", fn);
-  if (block_off[0] < 0) return fail(h, PLDA_E_INVAL, "%s: block_off[0] = %lld (must be >= 0)", fn, (long long)block_off[0]);
-  for (int64_t r = 0; r < R; ++r) {
-    const int64_t n = a.offsets[r + 1] - a.offsets[r];
-    if (block_off[r + 1] - block_off[r] < n * n)
-      return fail(h, PLDA_E_INVAL, "%s: block %lld holds %lld floats, its recording needs %lld x %lld", fn, (long long)r,
-                  (long long)(block_off[r + 1] - block_off[r]), (long long)n, (long long)n);
-  }
-  return PLDA_OK;
+    return (int)PLDA_OK;
+  }));
+  return blocks ? check_block_off(h, fn, block_off, a.offsets, R) : PLDA_OK;
 }
 
 int spectral_plan(plda_handle *h, int64_t N, int32_t k, int32_t *out) {
@@ -565,8 +513,8 @@ int spectral_matrix_device(plda_handle *h, const float *dscores, const int64_t *
   unsigned long long *dbad;
   PLDA_TRY(spectral_table(h, block_off, a, 0, a.R, tables, groups, &dtab, &dbad));
   PLDA_HIP(h, hipMemsetAsync(dbad, 0, 8, h->stream));
-  int rc = spectral_count(h, dscores, tables.back(), dtab, dbad);
-  if (rc == PLDA_OK) rc = spectral_counted(h, fn, dbad);
+  int rc = cluster_count_enqueue(h, dscores, tables.back().data(), a.R, dtab, dbad);
+  if (rc == PLDA_OK) rc = cluster_counted(h, fn, dbad);      // (nothing of the clustering is enqueued before it is known to be zero)
   if (rc == PLDA_OK) rc = spectral_enqueue(h, fn, dscores, a, tables.back(), dtab, groups);
   const hipError_t e = hipStreamSynchronize(h->stream);      // (the host tables go with this frame)
   PLDA_TRY(rc);
@@ -579,62 +527,29 @@ int score_spectral_device(plda_handle *h, const double *dX, const SpectralArgs &
   if (!can_score(h)) return fail(h, PLDA_E_NOT_FITTED, "%s: model not fitted", fn);
   if (!dX) return fail(h, PLDA_E_INVAL, "%s: X is NULL", fn);
   PLDA_TRY(spectral_validate(h, fn, nullptr, false, a));
-  const int D = h->Dout;
-  const int64_t R = a.R;
-  const int64_t *offsets = a.offsets;
-  // the score blocks of consecutive recordings, each at a 256-byte boundary of the slab, as many as the budget holds: the
-  // walk of plda_score_ahc_dev
-  auto padded = [](int64_t n) { return round_up(n * n, 64); };
-  const int64_t budget = spec_budget(h) / 4;
-  int64_t slab_floats = 0, slabs = 1;
-  for (int64_t r = 0, cur = 0; r < R; ++r) {
-    const int64_t f = padded(offsets[r + 1] - offsets[r]);
-    if (cur && cur + f > budget) { cur = 0; ++slabs; }
-    cur += f;
-    slab_floats = std::max(slab_floats, cur);
-  }
-  PLDA_HIP(h, h->sn_slab.reserve((size_t)slab_floats * 4));
+  SlabWalk walk(a.offsets, a.R, cluster_budget(h) / 4);
+  PLDA_HIP(h, h->sn_slab.reserve((size_t)walk.largest * 4));
   float *slab = h->sn_slab.as<float>();
   h->prep_valid = false;           // (every block packs its own two sides)
   std::vector<std::vector<SpecRec>> tables;
   std::vector<SpecGroup> groups;
-  std::vector<int64_t> boff;
   // pass 0 (only when the call takes several slabs): every block scored and counted, so that a non-finite score anywhere
   // fails the call before the first output is written; pass 1: scored (again), counted if pass 0 did not run, clustered
   int rc = PLDA_OK;
-  for (int pass = slabs > 1 ? 0 : 1; pass < 2 && rc == PLDA_OK; ++pass) {
-    for (int64_t r0 = 0; r0 < R && rc == PLDA_OK;) {
-      boff.clear();
-      int64_t r1 = r0, cur = 0;
-      while (r1 < R) {
-        const int64_t f = padded(offsets[r1 + 1] - offsets[r1]);
-        if (cur && cur + f > budget) break;
-        boff.push_back(cur);
-        cur += f;
-        ++r1;
-      }
-      {
-        TraceScope ts(h, "spectral.block_gemm", 0.0, 1);
-        double flop = 0.0;
-        for (int64_t r = r0; r < r1 && rc == PLDA_OK; ++r) {
-          const int64_t n = offsets[r + 1] - offsets[r];
-          const double *x = dX + offsets[r] * D;
-          rc = score_matrix_device(h, x, nullptr, 1, n, x, n, nullptr, nullptr, slab + boff[(size_t)(r - r0)], n);
-          flop += 2.0 * (double)D * (double)n * (double)n;
-        }
-        if (ts.idx >= 0) h->trace_spans[ts.idx].work = flop;
-      }
+  for (int pass = walk.slabs > 1 ? 0 : 1; pass < 2 && rc == PLDA_OK; ++pass) {
+    walk.rewind();
+    while (rc == PLDA_OK && walk.next()) {
+      rc = score_blocks_device(h, "spectral.block_gemm", dX, a.offsets, walk.r0, walk.r1, walk.boff.data(), slab);
       const SpecRec *dtab = nullptr;
       unsigned long long *dbad = nullptr;
-      if (rc == PLDA_OK) rc = spectral_table(h, boff.data(), a, r0, r1, tables, groups, &dtab, &dbad);
-      if (rc == PLDA_OK && (pass == 0 || slabs == 1)) {
+      if (rc == PLDA_OK) rc = spectral_table(h, walk.boff.data(), a, walk.r0, walk.r1, tables, groups, &dtab, &dbad);
+      if (rc == PLDA_OK && (pass == 0 || walk.slabs == 1)) {
         const hipError_t e = hipMemsetAsync(dbad, 0, 8, h->stream);
         if (e != hipSuccess) rc = hip_fail(h, e, "hipMemsetAsync", __FILE__, __LINE__);
-        if (rc == PLDA_OK) rc = spectral_count(h, slab, tables.back(), dtab, dbad);
-        if (rc == PLDA_OK) rc = spectral_counted(h, fn, dbad);
+        if (rc == PLDA_OK) rc = cluster_count_enqueue(h, slab, tables.back().data(), walk.r1 - walk.r0, dtab, dbad);
+        if (rc == PLDA_OK) rc = cluster_counted(h, fn, dbad);
       }
       if (rc == PLDA_OK && pass == 1) rc = spectral_enqueue(h, fn, slab, a, tables.back(), dtab, groups);
-      r0 = r1;
     }
   }
   const hipError_t e = hipStreamSynchronize(h->stream);

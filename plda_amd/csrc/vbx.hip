@@ -456,14 +456,7 @@ int vbx_validate(plda_handle *h, const char *fn, int64_t D, const int64_t *offse
   if (max_iters < 1 || max_iters > (1 << 20)) return fail(h, PLDA_E_INVAL, "%s: max_iters = %lld (must be >= 1)", fn, (long long)max_iters);
   if ((gamma != nullptr) != (gamma_off != nullptr)) return fail(h, PLDA_E_INVAL, "%s: gamma and gamma_off must be given together", fn);
   if ((pi != nullptr) != (pi_off != nullptr)) return fail(h, PLDA_E_INVAL, "%s: pi and pi_off must be given together", fn);
-  if (offsets[0] != 0) return fail(h, PLDA_E_INVAL, "%s: offsets[0] = %lld (must be 0)", fn, (long long)offsets[0]);
-  for (int64_t r = 0; r < R; ++r) {
-    const int64_t n = offsets[r + 1] - offsets[r];
-    if (n < 1 || n > PLDA_AHC_MAX)
-      return fail(h, PLDA_E_INVAL, "%s: recording %lld has %lld segments (must be 1 ... PLDA_AHC_MAX = %d; offsets must ascend)", fn,
-                  (long long)r, (long long)n, PLDA_AHC_MAX);
-  }
-  if (offsets[R] > (int64_t)0x7fffffff) return fail(h, PLDA_E_INVAL, "%s: %lld segments (at most 2^31 - 1)", fn, (long long)offsets[R]);
+  PLDA_TRY(check_recordings(h, fn, offsets, R, PLDA_AHC_MAX, "PLDA_AHC_MAX"));
   if (gamma_off && gamma_off[0] < 0) return fail(h, PLDA_E_INVAL, "%s: gamma_off[0] = %lld (must be >= 0)", fn, (long long)gamma_off[0]);
   if (pi_off && pi_off[0] < 0) return fail(h, PLDA_E_INVAL, "%s: pi_off[0] = %lld (must be >= 0)", fn, (long long)pi_off[0]);
   return PLDA_OK;

@@ -183,6 +183,32 @@ def test_batch_is_bit_equal_to_single_calls_and_to_other_groupings(monkeypatch):
         assert np.array_equal(a, b)
 
 
+@pytest.mark.parametrize("threshold", [None, 0.0])
+def test_ahc_form_over_three_slabs_equals_single_calls(monkeypatch, threshold):
+    """plda_score_dense_pca_ahc when the blocks take three slabs: recordings of 3, 70, 1, 200 and 9 segments are 64 + 4928 + 64,
+    40000 and 128 padded floats, and a budget of 5056 floats holds the first three exactly, then the fourth alone (it is larger
+    than the budget), then the fifth.  With min_clusters per recording and the merge record asked for, every recording's labels,
+    count and entries of the record equal the same recording's in a call of its own: the slabs' outputs start at offsets[r0],
+    r0 and offsets[r0] - r0 of the caller's arrays, and min_clusters is read from r0 on."""
+    from plda_amd import diarize
+    sizes, minc = [3, 70, 1, 200, 9], [2, 3, 1, 4, 2]
+    padded = [(n * n + 63) // 64 * 64 for n in sizes]
+    assert padded[0] + padded[1] + padded[2] == 5056 and padded[3] > 5056
+    model, x, offsets = dm.case(19, sizes, 32, 0.3)
+    monkeypatch.setenv("PLDA_AHC_SCRATCH_BYTES", str(4 * 5056))
+    small = _engine(model)
+    monkeypatch.delenv("PLDA_AHC_SCRATCH_BYTES")
+    eng = _engine(model)
+    labels, ncl, merges = diarize.ahc_dense_pca(small, x, offsets, 0.3, threshold, minc, True)
+    for r, (m0, m1) in enumerate(diarize.merge_slices(offsets)):
+        xr = x[offsets[r]:offsets[r + 1]]
+        l1, k1, g1 = diarize.ahc_dense_pca(eng, xr, [0, len(xr)], 0.3, threshold, minc[r], True)
+        assert np.array_equal(labels[offsets[r]:offsets[r + 1]], l1) and ncl[r] == k1[0], "recording %d" % r
+        assert k1[0] >= minc[r] and (threshold is not None or k1[0] == minc[r])
+        for a, b in zip(merges, g1):
+            assert np.array_equal(a[m0:m1], b), "recording %d: merge record" % r
+
+
 # ------------------------------------------------------------------------------------- facts independent of the model
 def test_full_dimension_equals_the_full_model():
     """target 0.9999 and N > D: the model keeps every direction, and the scores are the full model's (oracle LLR)."""
